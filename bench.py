@@ -10,7 +10,8 @@ mono stream resident in HBM before the timed region.  Default = BASELINE.json co
 nFeatures 1000, 8 levels, ARUCO dictionary).  Each rank owns an independent stream (frames / streams shard with no
 data-path collective, SURVEY 8e: weak scaling); the only collective is the RCCL gather of the fixed-capacity result records
 to rank 0, once per batch, inside the timed region.  After the clock stops rank 0 checks sampled frames of the last timed
-step against the CPU oracle ("verified_frames").  Prints ONE JSON line on rank 0.
+step against the CPU oracle ("verified_frames").  Prints ONE JSON line on rank 0.  --dump-outputs DIR also writes what that last
+step returned (record set and matches, float32 .npy, at most 64 MB: dump_outputs), so that two builds can be compared output for output.
 
     python bench.py --latency        drop-in latency of one frame through the host-pointer ABI (one JSON line, separate metric)
 """
@@ -73,7 +74,13 @@ def parse():
     ap.add_argument("--from-host", action="store_true", help="frames start in page-locked HOST memory and the record sets end there: upload, "
                     "engines and read-back overlapped by the pipeline (orbfe_pipeline_step_host); a separate metric, never the headline value")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last one returned (rank 0's "
+                    "record set and matches) as DIR/<name>.npy in float32, at most 64 MB (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.latency:
+        ap.error("--dump-outputs writes the batched path's records; --latency times single frames")
     cfg = CONFIGS[args.config]
     for k, v in cfg.items():
         if getattr(args, k, None) is None:
@@ -86,10 +93,15 @@ def parse():
 
 
 def make_stream(args, rank):
-    """Synthetic stream of this rank (seed base differs per rank), cached under /tmp across runs on one box."""
+    """Synthetic stream of this rank (seed base differs per rank), cached under build/streams/ across runs of this checkout; the
+    file name carries every generator argument and the generator's source hash, so a cached stream is the one synth would render."""
+    import hashlib
     from orb_slam2_aruco_amd import synth, sharding
     seed = sharding.stream_seed(rank)
-    path = "/tmp/orbfe_stream_%dx%d_%d_%d_%s.npy" % (args.cols, args.rows, args.frames, seed, args.dictionary)
+    synth_sha = hashlib.sha256(open(synth.__file__, "rb").read()).hexdigest()[:12]
+    cache = os.path.join(ROOT, "build", "streams")
+    path = os.path.join(cache, "stream_%dx%d_%d_%d_%s_m%d_%s.npy" % (args.cols, args.rows, args.frames, seed, args.dictionary, args.n_markers,
+                                                                      synth_sha))
     if os.path.exists(path):
         try:
             return np.load(path)
@@ -102,11 +114,74 @@ def make_stream(args, rank):
     workers = 1 if profiled else max(1, min(16, (os.cpu_count() or 1) // max(1, int(os.environ.get("WORLD_SIZE", "1")))))
     s = synth.stream(args.rows, args.cols, args.frames, seed, args.dictionary, n_markers=args.n_markers, workers=workers)
     try:
-        np.save(path + ".tmp.npy", s)
-        os.replace(path + ".tmp.npy", path)
+        os.makedirs(cache, exist_ok=True)
+        tmp = "%s.%d.tmp.npy" % (path, os.getpid())
+        np.save(tmp, s)
+        os.replace(tmp, path)
     except Exception:
         pass
     return s
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, rec, matches, stream_index, halo_index, use_orb=True, use_aruco=True):
+    """--dump-outputs: what the timed path handed its caller in its last step -- the record set (keypoints, descriptors, markers, poses
+    of every frame, and the halo slot: the previous batch's last frame) and the frame-to-frame matches -- as DIR/<name>.npy in float32.
+    Every stored value is a float32 already or an integer of at most 24 bits, so nothing is rounded.  Shapes follow from the arguments
+    alone: per frame the keypoint, descriptor and match rows at the pipeline's keypoint capacity, the marker and pose rows at its marker
+    capacity, zero past the frame's count (the records leave those entries unspecified).  Match row f pairs the frame in front of
+    frame f (the halo slot for f = 0) with frame f.  A batch larger than the limit is dumped as a fixed, seeded sample of its frames,
+    sorted, whose size depends on the batch length and the capacities only; frame_index gives each dumped frame's place in the
+    synthetic stream (halo_frame_index that of the halo slot).  Returns the names written."""
+    B = len(stream_index)
+    cap = rec["kps"].shape[1]
+    mcap = rec["markers"].shape[1] if use_aruco else 0
+    frame_bytes = 4 * ((cap * (7 + 32 + 4) + 2) * use_orb + (mcap * (9 + 14) + 1) * use_aruco + 1)
+    halo_bytes = 4 * (cap * (7 + 32) + 2) * use_orb
+    headers = 128 * 16                                          # one .npy header per file, at most 16 files
+    keep = min(B, (DUMP_LIMIT_BYTES - halo_bytes - headers) // frame_bytes)
+    if keep < 1:
+        raise SystemExit("bench.py --dump-outputs: one frame's records (%d bytes) exceed the %d byte limit" % (frame_bytes, DUMP_LIMIT_BYTES))
+    fids = np.arange(B) if keep == B else np.sort(np.random.default_rng(20240917).choice(B, keep, replace=False))
+    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+
+    def rows_upto(a, counts):                                   # zero every entry past its row's count
+        a = f32(a)
+        a[np.arange(a.shape[1])[None, :] >= np.asarray(counts)[:, None]] = 0
+        return a
+
+    def kp_fields(kps):
+        return np.stack([kps[f].astype(np.float32) for f in ("x", "y", "size", "angle", "response", "octave", "class_id")], axis=-1)
+
+    out = {"frame_index": f32(np.asarray(stream_index)[fids])}
+    if use_orb:
+        n = np.asarray(rec["n"], np.int64)
+        halo_n = np.asarray(rec["halo_n"], np.int64)
+        out["n_keypoints"] = f32(n[fids])
+        out["keypoints"] = rows_upto(kp_fields(rec["kps"][fids]), n[fids])
+        out["descriptors"] = rows_upto(rec["desc"][fids], n[fids])
+        out["halo_frame_index"] = f32([halo_index])
+        out["halo_n_keypoints"] = f32(halo_n)
+        out["halo_keypoints"] = rows_upto(kp_fields(rec["halo_kps"]), halo_n)
+        out["halo_descriptors"] = rows_upto(rec["halo_desc"], halo_n)
+        n1 = np.concatenate([halo_n, n[:-1]])[fids]             # keypoints of each match row's first frame
+        for name, key in (("knn2_best_idx", "best_idx"), ("knn2_best_dist", "best_dist"), ("knn2_second_dist", "second_dist"),
+                          ("init_matches12", "matches12")):
+            out[name] = rows_upto(matches[key][fids], n1)
+        out["init_n_matches"] = f32(matches["nmatches"][fids])
+    if use_aruco:
+        nmk = np.asarray(rec["nmk"], np.int64)[fids]
+        m = np.minimum(nmk, mcap)
+        mk, ps = rec["markers"][fids], rec["poses"][fids]
+        out["n_markers"] = f32(nmk)
+        out["markers"] = rows_upto(np.concatenate([mk["id"][..., None].astype(np.float32), mk["corners"].reshape(len(fids), mcap, 8)], -1), m)
+        out["poses"] = rows_upto(np.concatenate([ps[f].reshape(len(fids), mcap, -1) for f in ("rvec", "tvec", "rvec2", "tvec2", "err")], -1), m)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(out)
 
 
 def oracle_module():
@@ -373,6 +448,8 @@ def from_host_mode(args):
     rec = pipe.host_records(cur)                    # what arrived in host memory
     matches = pipe.read_matches()
     r_last, r_prev = (args.steps - 1) % R, (args.steps - 2) % R
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rec, matches, (np.arange(B) + shifts[r_last]) % B, (B - 1 + shifts[r_prev]) % B)
     verified = None
     if not args.no_verify:
         O = oracle_module()          # (puts tests/ on the path)
@@ -684,6 +761,9 @@ def main():
     gathered = [valid_records(pipe.gathered(r), use_orb) for r in range(world)] if (multi and backend == "rccl" and rank == 0) else None
     if gloo_gather is not None and rank == 0:
         gathered = [valid_records(pipe.layout.unpack(b.numpy()), use_orb) for b in gloo_gather.blocks]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, rec, matches, (np.arange(B) + shifts[r_last]) % B, (B - 1 + shifts[r_hist[-2]]) % B,
+                     use_orb=use_orb, use_aruco=use_aruco)
 
     # ---- the stages ALONE on the GPU (outside the clock): each engine by itself on a stream of its own, three batches, median of its
     # HIP events.  In the timed pipeline a stage's launch time is stretched by whatever else shares the chip -- two extractor batches,

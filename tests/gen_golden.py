@@ -6,6 +6,10 @@ the oracle on seeded synthetic inputs; they freeze the oracle's behaviour (any l
 results is caught by tests/test_oracle_cpu.py) and give the GPU tests data that does not need the oracle at all.
 
     python tests/gen_golden.py
+
+`python tests/gen_golden.py dbow2` writes the one fixture that does not come from the oracle: what the reference's own DBoW2
+BowVector / FeatureVector classes (oracle/_ref/libdbow2_ref.so, `make -C oracle ref`) return on the inputs of
+tests/test_oracle_cpu.py::test_bow_vectors_pinned_by_reference_classes.
 """
 import os
 import sys
@@ -63,7 +67,26 @@ def natural():
     print("wrote natural_images.json")
 
 
+def dbow2():
+    """The reference's BowVector / FeatureVector on every case of test_bow_vectors_pinned_by_reference_classes: bag-of-words
+    words and values, feature-vector nodes, offsets and features, keyed "w<weighting>_s<scoring>_<field>"."""
+    import test_oracle_cpu as T
+    R = T._dbow2_ref()
+    if R is None:
+        raise SystemExit("%s is not built: make -C oracle ref (needs the reference's sources)" % T.DBOW2_REF_SO)
+    out = {}
+    for weighting, scoring in T.DBOW2_REF_CASES:
+        _, feed = T.dbow2_case(O, weighting, scoring)
+        for f, v in T.dbow2_ref_run(R, weighting, scoring, feed).items():
+            out["w%d_s%d_%s" % (weighting, scoring, f)] = np.ascontiguousarray(v)
+    np.savez_compressed(os.path.join(OUT, "dbow2_ref_vectors.npz"), **out)
+    print("wrote dbow2_ref_vectors.npz")
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "dbow2":
+        os.makedirs(OUT, exist_ok=True)
+        return dbow2()
     if len(sys.argv) > 1 and sys.argv[1] == "natural":
         os.makedirs(OUT, exist_ok=True)
         return natural()

@@ -587,12 +587,16 @@ def test_search_by_projection_keyframe_hand_case(oracle):
 
 
 # ---------------------------------------------------------------- the reference's own BowVector / FeatureVector (oracle/_ref)
+DBOW2_REF_SO = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "libdbow2_ref.so")
+DBOW2_REF_CASES = [(0, 0), (1, 0), (2, 0), (3, 0), (0, 1), (0, 5), (1, 5), (0, 2)]        # (weighting, scoring)
+DBOW2_REF_FIELDS = ("bow_words", "bow_values", "fv_nodes", "fv_offsets", "fv_features")
+
+
 def _dbow2_ref():
-    import ctypes as C
-    so = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "libdbow2_ref.so")
-    if not os.path.exists(so):
-        pytest.skip("oracle/_ref/libdbow2_ref.so not built (make -C oracle ref needs /root/reference)")
-    L = C.CDLL(so)
+    """oracle/_ref/libdbow2_ref.so (make -C oracle ref, only where the reference's sources are present), or None."""
+    if not os.path.exists(DBOW2_REF_SO):
+        return None
+    L = C.CDLL(DBOW2_REF_SO)
     L.dbow2_ref_bowvector.restype = C.c_int
     L.dbow2_ref_bowvector.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     L.dbow2_ref_featurevector.restype = C.c_int
@@ -600,35 +604,57 @@ def _dbow2_ref():
     return L
 
 
-@pytest.mark.parametrize("weighting,scoring", [(0, 0), (1, 0), (2, 0), (3, 0), (0, 1), (0, 5), (1, 5), (0, 2)])
-def test_bow_vectors_pinned_by_reference_classes(oracle, weighting, scoring):
-    """The oracle's BowVector / FeatureVector (oracle/bow_oracle.cpp restating BowVector.cpp:32-89, FeatureVector.cpp:30-45 and the
-    accumulation / normalisation switch of TemplatedVocabulary.h:1143-1191, ScoringObject.h:74-91) against the REFERENCE's own
-    classes compiled from /root/reference (oracle/_ref/libdbow2_ref.so): the per-feature (word, weight, node) stream of the
-    oracle's tree descent goes through the real addWeight / addIfNotExist / normalize / addFeature -- doubles bit-exact."""
+def dbow2_case(oracle, weighting, scoring):
+    """The oracle's transform of one case's seeded vocabulary and descriptors, and the per-feature (word, weight, node) stream of
+    its tree descent that the reference's classes are fed (shared with tests/gen_golden.py dbow2)."""
     import voc_cases as vc
-    R = _dbow2_ref()
     voc = vc.make(9, 3, 17 + weighting + 10 * scoring, irregular=True)
     ov = oracle.VocabularyOracle.from_arrays(9, 3, scoring, weighting, voc["parent"], voc["is_leaf"], voc["desc"], voc["weight"])
     desc = np.random.default_rng(weighting * 7 + scoring).integers(0, 256, (700, 32), dtype=np.uint8)
     desc[100:140] = desc[0:40]                     # repeated words: accumulation order matters
     t = ov.transform(desc, 2)
     keep = t["weight"] > 0                          # "not stopped" (TemplatedVocabulary.h:1159,1183)
-    word = np.ascontiguousarray(t["word"][keep], np.uint32); w = np.ascontiguousarray(t["weight"][keep], np.float64)
+    feed = dict(word=np.ascontiguousarray(t["word"][keep], np.uint32), weight=np.ascontiguousarray(t["weight"][keep], np.float64),
+                node=np.ascontiguousarray(t["node"][keep], np.uint32), feat=np.ascontiguousarray(np.nonzero(keep)[0], np.uint32))
+    return t, feed
+
+
+def dbow2_ref_run(R, weighting, scoring, feed):
+    """The reference's BowVector (addWeight / addIfNotExist, normalize) and FeatureVector (addFeature) on the fed stream."""
+    word, w, node, feat = feed["word"], feed["weight"], feed["node"], feed["feat"]
     n = len(word)
-    assert n > 300
     mode = 0 if weighting in (0, 1) else 1
     norm = {0: 1, 1: 2, 2: 1, 3: 1, 4: 1, 5: 0}[scoring]     # ScoringObject.h:74-91: L1 / L2 / none (DOT_PRODUCT)
     ow = np.zeros(n, np.uint32); ov_ = np.zeros(n, np.float64)
     k = R.dbow2_ref_bowvector(word.ctypes.data, w.ctypes.data, n, mode, norm, ow.ctypes.data, ov_.ctypes.data)
     if mode == 0 and norm == 0:                     # TF / TF_IDF without normalisation: divided by the vector size (:1168-1174)
         ov_[:k] = ov_[:k] / float(k)
-    assert np.array_equal(ow[:k], t["bow"][0])
-    assert np.array_equal(ov_[:k].view(np.uint64), t["bow"][1].view(np.uint64))
-    node = np.ascontiguousarray(t["node"][keep], np.uint32); feat = np.ascontiguousarray(np.nonzero(keep)[0], np.uint32)
     on = np.zeros(n, np.uint32); oo = np.zeros(n + 1, np.int32); of = np.zeros(n, np.uint32)
     kf = R.dbow2_ref_featurevector(node.ctypes.data, feat.ctypes.data, n, on.ctypes.data, oo.ctypes.data, of.ctypes.data)
-    assert np.array_equal(on[:kf], t["fv"][0]) and np.array_equal(oo[:kf + 1], t["fv"][1]) and np.array_equal(of[:oo[kf]], t["fv"][2])
+    return dict(bow_words=ow[:k], bow_values=ov_[:k], fv_nodes=on[:kf], fv_offsets=oo[:kf + 1], fv_features=of[:oo[kf]])
+
+
+@pytest.mark.parametrize("weighting,scoring", DBOW2_REF_CASES)
+def test_bow_vectors_pinned_by_reference_classes(oracle, weighting, scoring):
+    """The oracle's BowVector / FeatureVector (oracle/bow_oracle.cpp restating BowVector.cpp:32-89, FeatureVector.cpp:30-45 and the
+    accumulation / normalisation switch of TemplatedVocabulary.h:1143-1191, ScoringObject.h:74-91) against the REFERENCE's own
+    classes compiled from the reference's sources (oracle/_ref/libdbow2_ref.so): the per-feature (word, weight, node) stream of the
+    oracle's tree descent goes through the real addWeight / addIfNotExist / normalize / addFeature -- doubles bit-exact.  What
+    those classes return is frozen in tests/golden/dbow2_ref_vectors.npz (tests/gen_golden.py dbow2); where the library is built
+    it runs as well and must still return exactly that."""
+    t, feed = dbow2_case(oracle, weighting, scoring)
+    assert len(feed["word"]) > 300
+    g = np.load(os.path.join(GOLD, "dbow2_ref_vectors.npz"))
+    want = {f: g["w%d_s%d_%s" % (weighting, scoring, f)] for f in DBOW2_REF_FIELDS}
+    R = _dbow2_ref()
+    if R is not None:
+        live = dbow2_ref_run(R, weighting, scoring, feed)
+        for f in DBOW2_REF_FIELDS:
+            assert live[f].dtype == want[f].dtype and live[f].tobytes() == want[f].tobytes(), f
+    assert np.array_equal(want["bow_words"], t["bow"][0])
+    assert np.array_equal(want["bow_values"].view(np.uint64), t["bow"][1].view(np.uint64))
+    assert np.array_equal(want["fv_nodes"], t["fv"][0]) and np.array_equal(want["fv_offsets"], t["fv"][1])
+    assert np.array_equal(want["fv_features"], t["fv"][2])
 
 
 def test_distinctive_descriptor_known_answers(oracle):
