@@ -20,6 +20,8 @@
  *   orbfe_hamming*,     ORBmatcher::DescriptorDistance     src/ORBmatcher.cc:1651-1667
  *   orbfe_knn2*,        best/second-best inner loop of every SearchBy*  
  *   orbfe_search_for_initialization   ORBmatcher::SearchForInitialization  src/ORBmatcher.cc:409-524
+ *   orbfe_initialize*   ORB_SLAM2::Initializer::Initialize src/Initializer.cc:44-121  (called from Tracking.cc:497-680)
+ *                       Initializer::InitializeUseAruco    src/Initializer.cc:124-189 (Tracking.cc:632)
  *
  * Memory convention: functions without a suffix take HOST pointers (drop-in for
  * the reference's call sites, which hand over cv::Mat / std::vector storage) and
@@ -386,6 +388,65 @@ int orbfe_search_for_initialization_batch_device(const orbfe_keypoint* d_kps, co
  * keypoints in a frame: ORBFE_ERR_CAPACITY (*overflow = that count).  The flag covers every batch since it was last read (reading
  * clears it). */
 int orbfe_search_for_initialization_batch_status(void* stream, int32_t* overflow);
+
+/* ------------------------------------------------------------ monocular two-view initializer -- */
+/* ORB_SLAM2::Initializer (src/Initializer.cc), constructed as Initializer(frame1, sigma, iterations) and called with frame 2.
+ * Keypoints are the UNDISTORTED ones (mvKeysUn) of the two frames, as for orbfe_search_for_initialization; matches12 is its
+ * output (n1 entries, -1 = none: vMatches12).  K4 = fx, fy, cx, cy (mK).
+ *
+ * Random sets: the reference seeds rand() once per process (DUtils::Random::SeedRandOnce(0)) and draws iterations * 8 values;
+ * rand_words holds them as rand() returned them, in draw order, and the call maps each through RandomInt(0, size - 1) with the
+ * swap-with-back removal of Initializer.cc:80-97.  The rand() state stays with the caller.
+ *
+ * Deviations from the reference, where it has undefined behaviour:
+ *   - fewer than 8 matches (RandomInt(0, -1)): ORBFE_OK, initialized = 0, best_h = best_f = -1, every other field 0;
+ *   - the F branch taken with no F hypothesis of positive score (RH <= 0.40 or SH = SF = 0: ReconstructF would read an empty
+ *     inlier vector): ORBFE_OK, initialized = 0, no motion checked.
+ * p3d (n1 x 3) / triangulated (n1) are written exactly when the reference assigns vP3D / vbTriangulated: when the call
+ * initializes.  On a failed reconstruction ReconstructH and ReconstructF leave both untouched, and so does this call.  Where they
+ * are written, p3d is 0 for every keypoint CheckRT did not count.  Either may be NULL.  A matches12 entry outside [-1, n2) is
+ * ORBFE_ERR_INVALID.  Host pointers. */
+typedef struct orbfe_init_result {
+    int32_t initialized;        /* Initialize()'s return value */
+    int32_t model;              /* 0 = homography branch (RH > 0.40), 1 = fundamental; 2 = orbfe_initialize_check_poses */
+    float   SH, SF, RH;
+    int32_t best_h, best_f;     /* winning RANSAC iteration of each model (first strict maximum), -1 = none; check_poses: best_h = bestIdA */
+    float   H21[9], F21[9];     /* the winning models, row-major, as FindHomography / FindFundamental return them (0 when none) */
+    float   R21[9], t21[3];     /* valid when initialized; zero otherwise */
+    int32_t n_good;             /* CheckRT's nGood of the accepted motion (or of the best one when not accepted) */
+    float   parallax;           /* degrees, as CheckRT computes it, of that motion */
+} orbfe_init_result;
+
+int orbfe_initialize(const orbfe_keypoint* kps1, int n1, const orbfe_keypoint* kps2, int n2, const int32_t* matches12, const float* K4,
+                     float sigma, int iterations, const int32_t* rand_words, orbfe_init_result* res, float* p3d, uint8_t* triangulated,
+                     int device);
+
+/* The batched device variant over npairs frame pairs, in the pair convention of orbfe_search_for_initialization_batch_device:
+ * pair p is frame p (side 1) against frame p + 1 (side 2); d_kps / d_n / capacity are that call's blocks (npairs + 1 frames) and
+ * d_matches12 its output (block p of `capacity` entries; an entry outside [-1, d_n[p+1]) counts as no match).  d_rand_words:
+ * npairs x iterations x 8 (a word outside 0 .. RAND_MAX is clamped to the ends of the index range).  Outputs: d_res[npairs], d_p3d blocks of capacity x 3, d_triangulated blocks of capacity, written as
+ * orbfe_initialize writes them (untouched for a pair that does not initialize).  K4 is read at the call.  Runs on `stream`,
+ * no host synchronisation; scratch per (thread, device, stream). */
+int orbfe_initialize_batch_device(const orbfe_keypoint* d_kps, const int32_t* d_n, int capacity, int npairs, const int32_t* d_matches12,
+                                  const float* K4, float sigma, int iterations, const int32_t* d_rand_words, orbfe_init_result* d_res,
+                                  float* d_p3d, uint8_t* d_triangulated, void* stream);
+
+/* Initializer::InitializeUseAruco (src/Initializer.cc:124-189): CheckRT of npose caller-given motions (poses: npose x 12 floats,
+ * R row-major then t) with every match an inlier and th2 = 4 sigma^2.  res->best_h = bestIdA (the first strict maximum of nGood,
+ * -1 when no pose counts a point), n_good / parallax of it, initialized = !(bestGood < 0.7 N), R21 / t21 = that pose when
+ * initialized; model = 2.  p3d / triangulated are those of bestIdA whenever there is one (the reference assigns them inside the
+ * loop, also when it then returns false); npose = 0 returns at once (initialized = 0).  Host pointers. */
+int orbfe_initialize_check_poses(const orbfe_keypoint* kps1, int n1, const orbfe_keypoint* kps2, int n2, const int32_t* matches12,
+                                 const float* K4, float sigma, const float* poses, int npose, orbfe_init_result* res, float* p3d,
+                                 uint8_t* triangulated, int device);
+
+/* DIAGNOSTIC / TEST INTERFACE, no stability promise (its arguments may change with the kernels): orbfe_initialize with its
+ * intermediate results (the parity tests): nmatches = N; sets: iterations x 8 match indices; T12: T1 then
+ * T2 (row-major); pn1 / pn2: the normalised points of every keypoint (n1 x 2, n2 x 2); models: iterations x 27 (H21, H12, F21);
+ * scores: SH of every iteration, then SF of every iteration.  sets / models / scores are left untouched when N < 8. */
+int orbfe_initialize_inspect(const orbfe_keypoint* kps1, int n1, const orbfe_keypoint* kps2, int n2, const int32_t* matches12,
+                             const float* K4, float sigma, int iterations, const int32_t* rand_words, orbfe_init_result* res,
+                             int32_t* nmatches, int32_t* sets, float* T12, float* pn1, float* pn2, float* models, float* scores, int device);
 
 /* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:270-333; called after every new observation by Tracking,
  * LocalMapping and LoopClosing): for every map point, among the descriptors it was observed with (CSR: point p owns rows

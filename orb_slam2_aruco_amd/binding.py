@@ -55,6 +55,8 @@ SYMBOLS = [
     "orbfe_pipeline_host_copy_us", "orbfe_pipeline_gathered_set", "orbfe_pipeline_gathered_wait", "orbfe_pipeline_gathered_release", "orbfe_pipeline_gathered_batch", "orbfe_pipeline_copy_stream_priority", "orbfe_pipeline_gather_plan",
     "orbfe_pipeline_step_host", "orbfe_pipeline_host_records", "orbfe_host_alloc", "orbfe_host_free",
     "orbfe_device_alloc", "orbfe_device_free", "orbfe_device_upload_rows", "orbfe_device_download",
+    # the monocular initializer (csrc/initializer.hip)
+    "orbfe_initialize", "orbfe_initialize_batch_device", "orbfe_initialize_check_poses", "orbfe_initialize_inspect",
 ]
 
 _lib = None
@@ -182,6 +184,11 @@ def load():
         L.orbfe_search_by_bow_batch_device.argtypes = [vp] * 8 + [i32, vp, vp, i32, i32, f32, i32, i32, f32, vp, vp, vp, vp]
         L.orbfe_marker_poses.argtypes = [vp, i32, f32, vp, vp, i32, vp, i32]
         L.orbfe_marker_poses_batch_device.argtypes = [vp, vp, i32, i32, f32, vp, vp, i32, vp, vp]
+    if hasattr(L, "orbfe_initialize"):
+        L.orbfe_initialize.argtypes = [vp, i32, vp, i32, vp, vp, f32, i32, vp, vp, vp, vp, i32]
+        L.orbfe_initialize_inspect.argtypes = [vp, i32, vp, i32, vp, vp, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
+        L.orbfe_initialize_check_poses.argtypes = [vp, i32, vp, i32, vp, vp, f32, vp, i32, vp, vp, vp, i32]
+        L.orbfe_initialize_batch_device.argtypes = [vp, vp, i32, i32, vp, vp, f32, i32, vp, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -643,6 +650,112 @@ class ORBmatcher:
                                                               int(self.mbCheckOrientation), C.byref(n), self.device),
                "orbfe_search_for_initialization")
         return n.value, m12, prev
+
+
+# ------------------------------------------------------------------------------------- Initializer ----
+INIT_RESULT_DTYPE = np.dtype([("initialized", "<i4"), ("model", "<i4"), ("SH", "<f4"), ("SF", "<f4"), ("RH", "<f4"),
+                              ("best_h", "<i4"), ("best_f", "<i4"), ("H21", "<f4", 9), ("F21", "<f4", 9), ("R21", "<f4", 9),
+                              ("t21", "<f4", 3), ("n_good", "<i4"), ("parallax", "<f4")])
+assert INIT_RESULT_DTYPE.itemsize == 156
+
+_libc_rand = None
+
+
+def draw_rand_words(count):
+    """`count` values of the C library's rand(), seeded once per process with srand(0) -- what DUtils::Random::SeedRandOnce(0) and
+    RandomInt do for Initializer::Initialize (Initializer.cc:80-97).  Successive calls continue the same sequence."""
+    global _libc_rand
+    if _libc_rand is None:
+        libc = C.CDLL(None)
+        libc.srand.argtypes = [C.c_uint]
+        libc.rand.restype = C.c_int
+        libc.srand(0)
+        _libc_rand = libc.rand
+    return np.array([_libc_rand() for _ in range(int(count))], np.int32)
+
+
+def _init_inputs(kps1, kps2, matches12, K):
+    k1 = np.ascontiguousarray(kps1, KP_DTYPE); k2 = np.ascontiguousarray(kps2, KP_DTYPE)
+    m12 = np.ascontiguousarray(matches12, np.int32)
+    if len(m12) != len(k1):
+        raise ValueError("matches12 has %d entries for %d keypoints" % (len(m12), len(k1)))
+    K = np.asarray(K, np.float32)
+    K4 = np.ascontiguousarray([K[0, 0], K[1, 1], K[0, 2], K[1, 2]] if K.shape == (3, 3) else K.reshape(4), np.float32)
+    return k1, k2, m12, K4
+
+
+def _ptr_or_none(a):
+    return _p(a) if a.size else None
+
+
+def initialize(kps1, kps2, matches12, K, sigma=1.0, iterations=200, rand_words=None, device=0):
+    """Initializer(frame1, sigma, iterations).Initialize(frame2, vMatches12, ...) (Initializer.cc:44-121) on the GPU.
+    kps1 / kps2: undistorted keypoints (KP_DTYPE); matches12: len(kps1) ints, -1 = none; K: 3 x 3 or (fx, fy, cx, cy).
+    rand_words: iterations * 8 rand() values; None draws them from the C library's rand() seeded once with srand(0).
+    Returns (result record of INIT_RESULT_DTYPE, p3d (n1 x 3), triangulated (n1 bools)); the last two are None when the call does
+    not initialize (the reference leaves vP3D / vbTriangulated untouched then)."""
+    L = load()
+    k1, k2, m12, K4 = _init_inputs(kps1, kps2, matches12, K)
+    w = draw_rand_words(iterations * 8) if rand_words is None else np.ascontiguousarray(rand_words, np.int32)
+    if len(w) != iterations * 8:
+        raise ValueError("rand_words needs iterations * 8 = %d values" % (iterations * 8))
+    res = np.zeros(1, INIT_RESULT_DTYPE)
+    p3d = np.zeros((max(len(k1), 1), 3), np.float32); tri = np.zeros(max(len(k1), 1), np.uint8)
+    _check(L, L.orbfe_initialize(_ptr_or_none(k1), len(k1), _ptr_or_none(k2), len(k2), _ptr_or_none(m12), _p(K4), float(sigma),
+                                 int(iterations), _p(w), _p(res), _p(p3d), _p(tri), device), "orbfe_initialize")
+    if not res[0]["initialized"]:
+        return res[0], None, None
+    return res[0], p3d[:len(k1)], tri[:len(k1)].astype(bool)
+
+
+def initialize_inspect(kps1, kps2, matches12, K, sigma=1.0, iterations=200, rand_words=None, device=0):
+    """initialize() plus its intermediate results: dict with N, sets (iterations x 8), T1, T2, pn1, pn2, H21 / H12 / F21 of every
+    hypothesis (iterations x 3 x 3), SH / SF of every hypothesis, and the result record."""
+    L = load()
+    k1, k2, m12, K4 = _init_inputs(kps1, kps2, matches12, K)
+    w = draw_rand_words(iterations * 8) if rand_words is None else np.ascontiguousarray(rand_words, np.int32)
+    res = np.zeros(1, INIT_RESULT_DTYPE)
+    n = C.c_int32(0)
+    sets = np.zeros((iterations, 8), np.int32); T = np.zeros(18, np.float32)
+    pn1 = np.zeros((max(len(k1), 1), 2), np.float32); pn2 = np.zeros((max(len(k2), 1), 2), np.float32)
+    models = np.zeros((iterations, 27), np.float32); scores = np.zeros(2 * iterations, np.float32)
+    _check(L, L.orbfe_initialize_inspect(_ptr_or_none(k1), len(k1), _ptr_or_none(k2), len(k2), _ptr_or_none(m12), _p(K4), float(sigma),
+                                         int(iterations), _p(w), _p(res), C.byref(n), _p(sets), _p(T), _p(pn1), _p(pn2), _p(models),
+                                         _p(scores), device), "orbfe_initialize_inspect")
+    return dict(N=n.value, sets=sets, T1=T[:9].reshape(3, 3), T2=T[9:].reshape(3, 3), pn1=pn1[:len(k1)], pn2=pn2[:len(k2)],
+                H21=models[:, :9].reshape(-1, 3, 3), H12=models[:, 9:18].reshape(-1, 3, 3), F21=models[:, 18:].reshape(-1, 3, 3),
+                SH=scores[:iterations], SF=scores[iterations:], result=res[0])
+
+
+def initialize_check_poses(kps1, kps2, matches12, K, R, t, sigma=1.0, device=0):
+    """Initializer::InitializeUseAruco (Initializer.cc:124-189): CheckRT of the given motions R (npose x 3 x 3), t (npose x 3).
+    Returns (result record: initialized, best_h = bestIdA, n_good, parallax, R21 / t21; p3d, triangulated) -- the last two None
+    when no pose counts a point."""
+    L = load()
+    k1, k2, m12, K4 = _init_inputs(kps1, kps2, matches12, K)
+    R = np.asarray(R, np.float32).reshape(-1, 9); t = np.asarray(t, np.float32).reshape(-1, 3)
+    poses = np.ascontiguousarray(np.concatenate([R, t], 1), np.float32)
+    res = np.zeros(1, INIT_RESULT_DTYPE)
+    p3d = np.zeros((max(len(k1), 1), 3), np.float32); tri = np.zeros(max(len(k1), 1), np.uint8)
+    _check(L, L.orbfe_initialize_check_poses(_ptr_or_none(k1), len(k1), _ptr_or_none(k2), len(k2), _ptr_or_none(m12), _p(K4),
+                                             float(sigma), _ptr_or_none(poses), len(poses), _p(res), _p(p3d), _p(tri), device),
+           "orbfe_initialize_check_poses")
+    if res[0]["best_h"] < 0:
+        return res[0], None, None
+    return res[0], p3d[:len(k1)], tri[:len(k1)].astype(bool)
+
+
+def initialize_batch_device(d_kps_ptr, d_n_ptr, capacity, npairs, d_matches12_ptr, K, sigma, iterations, d_rand_words_ptr, d_res_ptr,
+                            d_p3d_ptr, d_tri_ptr, stream=0):
+    """orbfe_initialize_batch_device: pair p = frame p against frame p + 1 of the blocks orbfe_search_for_initialization_batch_device
+    reads and writes (device pointers); results: npairs INIT_RESULT_DTYPE records, capacity x 3 p3d and capacity triangulated
+    blocks per pair.  Asynchronous on `stream`."""
+    L = load()
+    K = np.asarray(K, np.float32)
+    K4 = np.ascontiguousarray([K[0, 0], K[1, 1], K[0, 2], K[1, 2]] if K.shape == (3, 3) else K.reshape(4), np.float32)
+    _check(L, L.orbfe_initialize_batch_device(d_kps_ptr, d_n_ptr, int(capacity), int(npairs), d_matches12_ptr, _p(K4), float(sigma),
+                                              int(iterations), d_rand_words_ptr, d_res_ptr, d_p3d_ptr, d_tri_ptr, stream),
+           "orbfe_initialize_batch_device")
 
 
 # ------------------------------------------------------------------------------------------ ArUco ----
