@@ -141,8 +141,8 @@ int orbfe_extractor_debug_level_image(orbfe_extractor* h, int frame, int level, 
  * stage 1: keypoints kept by the quadtree (level coordinates).  Returns count in *n (<= capacity copied). */
 int orbfe_extractor_debug_level_keypoints(orbfe_extractor* h, int frame, int level, int stage, orbfe_keypoint* out,
                                           int capacity, int32_t* n);
-/* per-kernel timing of the last batch call on this handle, microseconds, in launch order; returns number written.
- * out_us == NULL: `capacity` is a control code (0 / 1 = event timing off / on, which also clears the history).  capacity < 0:
+/* per-kernel timing of the last batch call on this handle, microseconds, in launch order; returns number written (0 while timing is
+ * off: orbfe_extractor_debug_control "kernel_timing"; out_us == NULL is ORBFE_ERR_INVALID).  capacity < 0:
  * the per-interval MEDIAN over the batches recorded since timing was switched on (the newest 64 at most), -capacity slots --
  * what bench.py reports, because one batch's events are not the steady state of a pipelined run. */
 /* The extractor forks one launch (the blur, which only needs the pyramid) onto a second stream so that it overlaps with
@@ -185,6 +185,19 @@ int orbfe_extractor_debug_kernel_times(orbfe_extractor* h, float* out_us, int ca
  * Both kernels give identical results.  No key of the shipped library skips work ("orb_skip" / "aruco_skip" exist only in
  * the -DORBFE_ABLATION diagnosis build, whose orbfe_version() says "+ablation"; here they are ORBFE_ERR_INVALID). */
 int orbfe_debug_control(const char* key, int value);
+/* The same for one engine handle.  An unknown key or a value outside its range is ORBFE_ERR_INVALID and changes nothing.
+ * Extractor:  "kernel_timing" 0 / 1 (event timing off / on; either clears the history), "general_quadtree" 0 / 1 (the general
+ *   quadtree kernel for every level), "pyramid_depth" 0 .. 6 (depth of the quadtree count pyramid; 0 = by the levels' node counts),
+ *   "blur_mfma" 1 / 0 (the blur on the matrix cores where it applies, the default / k_blur7).
+ * Detector:  "kernel_timing" 0 / 1, "legacy_contours" 0 / 1 (the single-walker contour kernel for every frame), "tiled_contours"
+ *   -1 / 0 / 1 (the tiled contour path by frame and batch size, the default / never / always), "speck_passes" 0 / 1 (as a launch of
+ *   their own: never / wherever their tile fits LDS), "speck_passes_in_kernel" 0 / 1 (inside the one-workgroup relay kernels),
+ *   "threshold_pyr" 1 / 0 (k_threshold_pyr where it applies, the default / k_adaptive_threshold_t), "threshold_mfma" -1 / 0 / 1
+ *   (k_threshold_mfma for calls of 8 frames and more, the default / never / wherever it applies), "half_pyr" 1 / 0 (k_half_pyr, the
+ *   default / a launch per level).  ORBFE_ARUCO_TILED and ORBFE_ARUCO_SPECKS set the same switches when the handle is created.
+ * Results do not depend on any of them. */
+int orbfe_extractor_debug_control(orbfe_extractor* h, const char* key, int value);
+int orbfe_aruco_debug_control(orbfe_aruco* h, const char* key, int value);
 
 /* popcount(a XOR b) over 256 bits, host pointers (ORBmatcher::DescriptorDistance) */
 int orbfe_hamming(const uint8_t* a, const uint8_t* b);
@@ -655,6 +668,9 @@ int orbfe_aruco_debug_image(orbfe_aruco* h, int frame, int stage, uint8_t* out);
 /* As orbfe_extractor_set_aux_stream, for the detector's forked launches (the /2 pyramid). */
 int orbfe_aruco_set_aux_stream(orbfe_aruco* h, void* stream);
 int orbfe_aruco_debug_kernel_times(orbfe_aruco* h, float* out_us, int capacity);
+/* How many batches of this handle were done again on the next contour path (tiled -> one workgroup -> single walker) because a
+ * frame exceeded a capacity of the one they ran on. */
+int orbfe_aruco_debug_contour_retries(const orbfe_aruco* h);
 
 /* ------------------------------------------------------------------ marker pose (IPPE) -- */
 /* Marker pose: what MarkerDetector::detect adds to every marker when it is given camera parameters and a marker size

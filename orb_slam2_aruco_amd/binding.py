@@ -27,13 +27,13 @@ SYMBOLS = [
     "orbfe_extractor_max_keypoints", "orbfe_extract", "orbfe_extract_batch", "orbfe_extract_batch_device",
     "orbfe_extractor_batch_status", "orbfe_search_for_initialization_batch_status", "orbfe_extractor_set_gaussian_taps",
     "orbfe_extractor_debug_level_size", "orbfe_extractor_debug_level_image",
-    "orbfe_extractor_debug_level_keypoints", "orbfe_extractor_debug_kernel_times", "orbfe_extractor_set_aux_stream", "orbfe_extractor_set_early_stream", "orbfe_extractor_follow", "orbfe_extractor_stage_wait", "orbfe_extractor_pair_detector",
+    "orbfe_extractor_debug_level_keypoints", "orbfe_extractor_debug_kernel_times", "orbfe_extractor_debug_control", "orbfe_extractor_set_aux_stream", "orbfe_extractor_set_early_stream", "orbfe_extractor_follow", "orbfe_extractor_stage_wait", "orbfe_extractor_pair_detector",
     "orbfe_debug_control", "orbfe_hamming", "orbfe_three_maxima", "orbfe_epipolar_distance_ok", "orbfe_knn2", "orbfe_knn2_csr", "orbfe_knn2_batch_device", "orbfe_search_for_initialization",
     "orbfe_search_for_initialization_batch_device", "orbfe_search_by_projection",
     "orbfe_undistort_points", "orbfe_undistort_keypoints_batch_device", "orbfe_compute_image_bounds",
     "orbfe_aruco_create", "orbfe_aruco_destroy", "orbfe_aruco_set_dictionary", "orbfe_aruco_max_markers",
     "orbfe_aruco_detect", "orbfe_aruco_detect_batch", "orbfe_aruco_detect_batch_device", "orbfe_aruco_debug_image",
-    "orbfe_aruco_debug_kernel_times", "orbfe_aruco_set_aux_stream",
+    "orbfe_aruco_debug_kernel_times", "orbfe_aruco_debug_control", "orbfe_aruco_debug_contour_retries", "orbfe_aruco_set_aux_stream",
     "orbfe_aruco_batch_status", "orbfe_aruco_set_big_frames", "orbfe_aruco_set_error_correction_rate",
     "orbfe_aruco_set_detection_mode", "orbfe_aruco_set_corner_refinement", "orbfe_aruco_marker_contour", "orbfe_aruco_marker_contours",
     "orbfe_camera_resize", "orbfe_marker_poses", "orbfe_marker_poses_batch_device", "orbfe_aruco_detect_poses",
@@ -97,6 +97,7 @@ def load():
     L.orbfe_extractor_debug_level_image.argtypes = [vp, i32, i32, i32, vp]
     L.orbfe_extractor_debug_level_keypoints.argtypes = [vp, i32, i32, i32, vp, i32, vp]
     L.orbfe_extractor_debug_kernel_times.argtypes = [vp, vp, i32]
+    L.orbfe_extractor_debug_control.argtypes = [vp, C.c_char_p, i32]
     L.orbfe_extractor_set_early_stream.argtypes = [vp, vp]
     L.orbfe_extractor_follow.argtypes = [vp, vp, i32]
     L.orbfe_extractor_stage_wait.argtypes = [vp, i32, vp]
@@ -146,6 +147,8 @@ def load():
         L.orbfe_aruco_detect_batch_device.argtypes = [vp, vp, i32, sz, i32, i32, sz, vp, i32, vp, vp]
         L.orbfe_aruco_debug_image.argtypes = [vp, i32, i32, vp]
         L.orbfe_aruco_debug_kernel_times.argtypes = [vp, vp, i32]
+        L.orbfe_aruco_debug_control.argtypes = [vp, C.c_char_p, i32]
+        L.orbfe_aruco_debug_contour_retries.argtypes = [vp]
         L.orbfe_aruco_set_aux_stream.argtypes = [vp, vp]
         L.orbfe_aruco_batch_status.argtypes = [vp, vp, vp]
         L.orbfe_aruco_set_big_frames.argtypes = [vp, i32]
@@ -345,20 +348,24 @@ class ORBextractor:
         """Run the extractor's launch that needs no pyramid (FAST of level 0) on the caller's stream (None: the handle's own)."""
         _check(self.L, self.L.orbfe_extractor_set_early_stream(self.h, stream_ptr), "set_early_stream")
 
+    def debug_control(self, key, value):
+        """orbfe_extractor_debug_control: a named test / diagnosis switch of this handle (include/orbfe.h lists the keys)."""
+        _check(self.L, self.L.orbfe_extractor_debug_control(self.h, key.encode(), int(value)), "extractor_debug_control")
+
     def enable_kernel_timing(self, on=True):
-        self.L.orbfe_extractor_debug_kernel_times(self.h, None, int(on))
+        self.debug_control("kernel_timing", on)
 
     def set_blur_on_matrix_cores(self, on=True):
         """k_blur7_mfma (default) / k_blur7: the tests run both."""
-        self.L.orbfe_extractor_debug_kernel_times(self.h, None, 23 if on else 24)
+        self.debug_control("blur_mfma", on)
 
     def force_general_quadtree(self, on=True):
         """Test hook: bypass the count-pyramid fast path of DistributeOctTree."""
-        self.L.orbfe_extractor_debug_kernel_times(self.h, None, 2 if on else 3)
+        self.debug_control("general_quadtree", on)
 
     def set_pyramid_depth(self, depth=0):
         """Test hook: depth of the quadtree count pyramid (0 = default); shallow values force the fallback."""
-        self.L.orbfe_extractor_debug_kernel_times(self.h, None, 10 + depth)
+        self.debug_control("pyramid_depth", depth)
 
     def quadtree_fell_back(self, frame, level):
         n = C.c_int32(0)
@@ -1079,34 +1086,38 @@ class MarkerDetector:
         return dict(nkept=int(out[0]), nrect=int(out[1]), flags=int(out[2]), ncand=int(out[3]) & 0x3fffffff,
                     fell_back=bool(int(out[3]) >> 30))   # the relay contour kernel handed the frame to the legacy one
 
+    def debug_control(self, key, value):
+        """orbfe_aruco_debug_control: a named test / diagnosis switch of this handle (include/orbfe.h lists the keys)."""
+        _check(self.L, self.L.orbfe_aruco_debug_control(self.h, key.encode(), int(value)), "aruco_debug_control")
+
     def force_legacy_contours(self, on=True):
         """Debug: run every frame through the single-walker contour kernel (the relay kernel's fallback)."""
-        self.L.orbfe_aruco_debug_kernel_times(self.h, None, 2 if on else 3)
+        self.debug_control("legacy_contours", on)
 
     def set_tiled_contours(self, mode):
         """Debug: the tiled contour path (aruco_tiles.hip) None = by frame / batch size (default), True = every batch, False = never."""
-        self.L.orbfe_aruco_debug_kernel_times(self.h, None, 4 if mode is None else 5 if mode else 6)
+        self.debug_control("tiled_contours", -1 if mode is None else bool(mode))
 
     def set_speck_passes(self, on=True):
         """Debug: the speck passes between threshold and contours (k_speck_clean) on / off (default); the results do not change."""
-        self.L.orbfe_aruco_debug_kernel_times(self.h, None, 8 if on else 9)
+        self.debug_control("speck_passes", on)
 
     def set_threshold_on_matrix_cores(self, on=True):
         """True: k_threshold_mfma wherever it applies (windows up to 15); False: the dot-product kernels; None: the default rule -- the
         matrix-core kernel for calls of 8 frames and more, k_threshold_pyr (one launch instead of five) for the drop-in call's few."""
-        self.L.orbfe_aruco_debug_kernel_times(self.h, None, 16 if on is None else 14 if on else 15)
+        self.debug_control("threshold_mfma", -1 if on is None else bool(on))
 
     def set_threshold_pyramid_kernel(self, on=True):
         """k_threshold_pyr (threshold + the /2 pyramid levels a tile holds, the default where it applies) / k_adaptive_threshold_t + k_half_area4."""
-        self.L.orbfe_aruco_debug_kernel_times(self.h, None, 12 if on else 13)
+        self.debug_control("threshold_pyr", on)
 
     def set_half_pyramid_kernel(self, on=True):
         """k_half_pyr (the leading exact /2 levels in one launch, default) / one k_half_area4 launch a level."""
-        self.L.orbfe_aruco_debug_kernel_times(self.h, None, 18 if on else 19)
+        self.debug_control("half_pyr", on)
 
     def set_speck_passes_in_kernel(self, on=True):
         """Debug: the speck passes inside the one-workgroup relay kernels (full batches of frames whose bit image fits LDS) on / off (default)."""
-        self.L.orbfe_aruco_debug_kernel_times(self.h, None, 10 if on else 11)
+        self.debug_control("speck_passes_in_kernel", on)
 
     def contour_image(self, frame=0):
         """Debug: the bit image the contour kernels of the last batch read from HBM (the thresholded image after the speck passes where
@@ -1118,7 +1129,7 @@ class MarkerDetector:
     def contour_retries(self):
         """Debug: how many batches of this detector were done again on the next contour path (tiled -> one workgroup -> single walker)
         because a frame exceeded a capacity of the one they ran on."""
-        return int(self.L.orbfe_aruco_debug_kernel_times(self.h, None, 7))
+        return _check(self.L, self.L.orbfe_aruco_debug_contour_retries(self.h), "debug_contour_retries")
 
     def rects(self, frame=0):
         out = np.zeros(self.capacity, RECT_DTYPE)
@@ -1130,7 +1141,7 @@ class MarkerDetector:
         _check(self.L, self.L.orbfe_aruco_set_aux_stream(self.h, stream_ptr), "set_aux_stream")
 
     def enable_kernel_timing(self, on=True):
-        self.L.orbfe_aruco_debug_kernel_times(self.h, None, int(on))
+        self.debug_control("kernel_timing", on)
 
     def kernel_times_us(self, median=False):
         """Stage times of the last batch, or (median=True) the per-stage median over the batches since timing was enabled."""

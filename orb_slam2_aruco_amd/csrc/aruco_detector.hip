@@ -78,12 +78,12 @@ struct orbfe_aruco {
     // 4.13 -> 3.96 - 4.07 ms) or whose bit image does not fit LDS at all (1920 x 1080: 100-frame step 4.88 -> 3.41 ms), and batches of
     // up to 32 frames (a frame's walks spread over ~40 CUs instead of one); full batches of 640 x 480 frames keep the one-workgroup
     // kernel, whose single launch costs the pipeline less than band + lists + points (1.32 - 1.34 against 1.45 - 1.62 ms per step).
-    // ORBFE_ARUCO_TILED = 0 / 1 forces it off / on for every batch (tests, A/B); ORBFE_ARUCO_TILE_W = tile width in pixels,
-    // ORBFE_ARUCO_TPW = tiles per wave of k_ct_walk: measurement switches.
-    int tiled = getenv("ORBFE_ARUCO_TILED") ? (atoi(getenv("ORBFE_ARUCO_TILED")) ? 1 : 0) : -1;
+    // ORBFE_ARUCO_TILED = 0 / 1 (debug key "tiled_contours") forces it off / on for every batch (tests, A/B); ORBFE_ARUCO_TILE_W = tile
+    // width in pixels, ORBFE_ARUCO_TPW = tiles per wave of k_ct_walk: measurement switches.
+    int tiled = -1;
     bool tiled_off = false;    // set while a batch is redone by the relay kernels
     bool tiled_ran = false;    // the last batch took the tiled path
-    int n_escalations = 0;     // batches done again on the next contour path (debug query 7: the tests assert 0 for ordinary frames)
+    int n_escalations = 0;     // batches done again on the next contour path (orbfe_aruco_debug_contour_retries: the tests assert 0 for ordinary frames)
     // the walks of the tiled path by BANDS of cell rows, a workgroup of eight waves each (k_ct_band), instead of a wave per tile
     // (k_ct_walk): -1 = by frame / batch size, 0 / 1 forced; ORBFE_ARUCO_BAND_ROWS = cell rows per band (0: what fits ~36 KB of LDS, at most 8)
     int banded = getenv("ORBFE_ARUCO_BANDED") ? (atoi(getenv("ORBFE_ARUCO_BANDED")) ? 1 : 0) : -1;
@@ -105,16 +105,16 @@ struct orbfe_aruco {
     //     32 frames whose image fits LDS): 462 -> 440 us alone and 140 -> 120 us of VALU issue, the C2 step unchanged (1.343 against
     //     1.333 ms, four interleaved runs) -- and the rim masks and anchors of a frame (120 KB) go through scratch in HBM, which
     //     doubles the stage's HBM traffic (148 -> 268 MB per step).
-    // ORBFE_ARUCO_SPECKS = 0 (default) / 1 / 2.  Debug codes 8 / 9: the launch on / off, 10 / 11: inside.  Tested either way
-    // (tests/test_aruco_gpu.py, tests/test_stress_gpu.py).
+    // ORBFE_ARUCO_SPECKS = 0 (default) / 1 / 2.  Debug keys "speck_passes": the launch on / off, "speck_passes_in_kernel": inside.
+    // Tested either way (tests/test_aruco_gpu.py, tests/test_stress_gpu.py).
     // the speck passes as a launch between threshold and contours: -1 = where they pay (full batches on the one-workgroup relay kernels:
     // 1.246 against 1.263 ms per C2 step with them, round 6; on the tiled paths 3.99 against 3.74 ms at 1280 x 720, 3.53 against 3.21 at
-    // 1920 x 1080), 0 / 1 = never / wherever their tile fits LDS (ORBFE_ARUCO_SPECKS, debug codes 8 / 9)
-    int specks = !getenv("ORBFE_ARUCO_SPECKS") ? -1 : atoi(getenv("ORBFE_ARUCO_SPECKS")) == 1 ? 1 : 0;
-    bool specks_inkernel = getenv("ORBFE_ARUCO_SPECKS") && atoi(getenv("ORBFE_ARUCO_SPECKS")) == 2;
-    bool half_pyr = true;   // the leading exact pyramid levels in one launch (k_half_pyr; debug code 18 / 19 = on / off)
-    bool thr_mfma = true;   // k_threshold_mfma where it applies (windows up to 15; debug code 14 / 15)
-    bool thr_mfma_auto = true; // ... but k_threshold_pyr for calls of fewer than 8 frames (debug code 14 forces the matrix-core kernel, 16 = this rule again)
+    // 1920 x 1080), 0 / 1 = never / wherever their tile fits LDS (ORBFE_ARUCO_SPECKS, debug key "speck_passes")
+    int specks = -1;
+    bool specks_inkernel = false;
+    bool half_pyr = true;   // the leading exact pyramid levels in one launch (k_half_pyr; debug key "half_pyr")
+    bool thr_mfma = true;   // k_threshold_mfma where it applies (windows up to 15; debug key "threshold_mfma" = 1 / 0)
+    bool thr_mfma_auto = true; // ... but k_threshold_pyr for calls of fewer than 8 frames ("threshold_mfma" = 1 forces the matrix-core kernel, -1 = this rule again)
     DevBuf d_tstrips, d_ttabs, d_ttab2;
     int n_tstrips = 0, ttab_rows = 0, ttab_cols = 0, ttab_win = 0, ttab_rb = 0;
     bool thr_mfma_ok = false;
@@ -189,7 +189,7 @@ struct orbfe_aruco {
         thr_mfma_ok = true;
         return ORBFE_OK;
     }
-    bool thr_v2 = true;   // k_threshold_pyr where it applies (debug code 12 / 13: the tests run both threshold kernels)
+    bool thr_v2 = true;   // k_threshold_pyr where it applies (debug key "threshold_pyr": the tests run both threshold kernels)
     bool specks_ran = false;   // the last batch's contour kernels read d_bitsc
     DevBuf d_bitsc;
     bool relay_global = false; // k_contours_relay8g: the bit image stays in HBM (it does not fit LDS)
@@ -1063,6 +1063,12 @@ orbfe_aruco* orbfe_aruco_create(const char* dictionary, int device)
     if (use_device(device) != ORBFE_OK) return nullptr;
     orbfe_aruco* h = new orbfe_aruco();
     h->device = device;
+    // the environment switches that have a debug key go through its setter
+    if (const char* v = getenv("ORBFE_ARUCO_TILED")) (void)orbfe_aruco_debug_control(h, "tiled_contours", atoi(v) ? 1 : 0);
+    if (const char* v = getenv("ORBFE_ARUCO_SPECKS")) {
+        (void)orbfe_aruco_debug_control(h, "speck_passes", atoi(v) == 1);
+        (void)orbfe_aruco_debug_control(h, "speck_passes_in_kernel", atoi(v) == 2);
+    }
     if (hipStreamCreate(&h->own_stream) != hipSuccess ||
         hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
@@ -1734,27 +1740,34 @@ int orbfe_aruco_set_aux_stream(orbfe_aruco* h, void* stream)
     return ORBFE_OK;
 }
 
-int orbfe_aruco_debug_kernel_times(orbfe_aruco* h, float* out_us, int capacity)
+int orbfe_aruco_debug_control(orbfe_aruco* h, const char* key, int value)
+{
+    if (!h || !key) return fail(ORBFE_ERR_INVALID, "orbfe_aruco_debug_control: null argument");
+    const bool on_off = value == 0 || value == 1, by_rule = on_off || value == -1;
+    if (!strcmp(key, "kernel_timing") && on_off) { h->timer.enabled = value; h->timer.reset_history(); }
+    else if (!strcmp(key, "legacy_contours") && on_off) h->force_legacy = value;
+    else if (!strcmp(key, "tiled_contours") && by_rule) {
+        if (h->tiled == 0 && value != 0) h->batch_cap = 0;   // the tiled path's workspace is only allocated while it can run: allocate on the next batch
+        h->tiled = value;
+    }
+    else if (!strcmp(key, "speck_passes") && on_off) h->specks = value;
+    else if (!strcmp(key, "speck_passes_in_kernel") && on_off) { h->specks_inkernel = value; h->rows = h->cols = 0; }   // (the queue's size depends on it: geometry rebuilt)
+    else if (!strcmp(key, "threshold_pyr") && on_off) h->thr_v2 = value;
+    else if (!strcmp(key, "threshold_mfma") && by_rule) { h->thr_mfma = value != 0; h->thr_mfma_auto = value == -1; }
+    else if (!strcmp(key, "half_pyr") && on_off) h->half_pyr = value;
+    else return fail(ORBFE_ERR_INVALID, "orbfe_aruco_debug_control: unknown key \"%s\" or value %d", key, value);
+    return ORBFE_OK;
+}
+
+int orbfe_aruco_debug_contour_retries(const orbfe_aruco* h)
 {
     if (!h) return fail(ORBFE_ERR_INVALID, "null handle");
-    if (!out_us) { // control codes: 0/1 kernel timing off/on, 2/3 force the legacy contour kernel on/off, 4/5/6 tiled contour path by size / always / never,
-                   // 7 returns the number of batches that were done again on the next contour path, 8 / 9 the speck passes on / off
-        if (capacity == 7) return h->n_escalations;
-        if (capacity == 8 || capacity == 9) { h->specks = capacity == 8 ? 1 : 0; return 0; }   // the speck passes on / off (default)
-        if (capacity == 10 || capacity == 11) { h->specks_inkernel = capacity == 10; h->rows = h->cols = 0; return 0; }   // (the queue's size depends on it: geometry rebuilt)
-        if (capacity == 14 || capacity == 15) { h->thr_mfma = capacity == 14; h->thr_mfma_auto = false; return 0; }
-        if (capacity == 16) { h->thr_mfma = true; h->thr_mfma_auto = true; return 0; }
-        if (capacity == 18 || capacity == 19) { h->half_pyr = capacity == 18; return 0; }   // k_half_pyr on (default) / off   // the threshold on the matrix cores on (default) / off
-        if (capacity == 12 || capacity == 13) { h->thr_v2 = capacity == 12; return 0; }   // the threshold kernel with the fused pyramid on (default) / off   // ... inside the relay kernels on / off (default)
-        if (capacity == 2 || capacity == 3) h->force_legacy = capacity == 2;
-        else if (capacity >= 4 && capacity <= 6) {
-            const int t = capacity == 4 ? -1 : capacity == 5 ? 1 : 0;
-            if (h->tiled == 0 && t != 0) h->batch_cap = 0;   // the tiled path's workspace is only allocated while it can run: allocate on the next batch
-            h->tiled = t;
-        }
-        else { h->timer.enabled = capacity != 0; h->timer.reset_history(); }
-        return 0;
-    }
+    return h->n_escalations;
+}
+
+int orbfe_aruco_debug_kernel_times(orbfe_aruco* h, float* out_us, int capacity)
+{
+    if (!h || !out_us) return fail(ORBFE_ERR_INVALID, "orbfe_aruco_debug_kernel_times: null argument");
     if (capacity < 0) return h->timer.collect_median(out_us, -capacity, nullptr);
     return h->timer.collect(out_us, capacity);
 }

@@ -90,7 +90,7 @@ struct orbfe_extractor {
         mix((uint64_t)(uintptr_t)d_in.p); mix((uint64_t)(uintptr_t)d_kps.p); mix((uint64_t)(uintptr_t)d_desc.p); mix((uint64_t)(uintptr_t)d_nout.p);
         mix((uint64_t)(uintptr_t)d_pyr.p); mix((uint64_t)(uintptr_t)d_blur.p); mix((uint64_t)(uintptr_t)d_slots.p); mix((uint64_t)(uintptr_t)d_keys.p);
         mix((uint64_t)(uintptr_t)d_flatkv.p); mix((uint64_t)(uintptr_t)d_lvlout.p); mix((uint64_t)(uintptr_t)user_aux); mix((uint64_t)(uintptr_t)user_early);
-        mix((uint64_t)gaussian_ed); mix((uint64_t)force_general_quadtree); mix((uint64_t)force_pyramid_depth); mix((uint64_t)blur_place);
+        mix((uint64_t)gaussian_ed); mix((uint64_t)force_general_quadtree); mix((uint64_t)force_pyramid_depth);
         mix((uint64_t)fast0_mode); mix((uint64_t)batch_cap);
         return k | 1ull;
     }
@@ -119,7 +119,6 @@ struct orbfe_extractor {
     DevBuf d_geom, d_cellinfo, d_tiles, d_tabs, d_pattern, d_umax;
     DevBuf d_pyr, d_blur, d_slots, d_cellcnt, d_keys, d_lvlout, d_lvlcnt, d_lvloff, d_lvlncand, d_overflow, d_fallback,
         d_flatkv, d_flatlvl, d_worklist;
-    int blur_place = 1;                  // where the blur is forked: 1 in front of FAST (default), 0 after FAST, 2 no fork (main stream, before orient)
     bool gaussian_ed = false;            // orbfe_extractor_set_gaussian_taps: 18 34 48 56 48 34 18 instead of 18 34 49 55 49 34 18
     // workgroups per CU the VALU-bound kernels may occupy (0 = what the hardware allows): the launch asks for LDS it does not use
     // so that the other engine's latency-bound kernels (8 waves and 50-77 KB of LDS per workgroup) always find room on every CU
@@ -383,7 +382,7 @@ struct orbfe_extractor {
     DevBuf d_bstrips, d_btabs, d_btab2;
     int n_bstrips = 0, blur_tabs_ed = -1, blur_tabs_rows = 0, blur_tabs_cols = 0;
     bool blur_mfma_ok = false;
-    bool blur_mfma = true;               // test hook (debug code 23 / 24): k_blur7 instead
+    bool blur_mfma = true;               // test hook (debug key "blur_mfma" = 0): k_blur7 instead
     int build_blur_tables()
     {
         if (blur_tabs_ed == (int)gaussian_ed && blur_tabs_rows == rows && blur_tabs_cols == cols) return ORBFE_OK;
@@ -522,7 +521,7 @@ struct orbfe_extractor {
         // Level 0 needs no resize: its cells (a third of all pixels) can be searched on a stream of their own from the start of the
         // batch, next to the resize chain instead of behind it (fast0_mode; off by default, see there).
         const int ncells_l0 = nlevels > 1 ? geom[1].cell_first : ncells_total;
-        const bool fast0 = fast0_mode != 0 && nlevels > 1 && blur_place != 2;
+        const bool fast0 = fast0_mode != 0 && nlevels > 1;
         hipStream_t fast0_stream = user_early ? user_early : fast0_mode == 2 && user_aux ? user_aux : this->aux_stream;
         if (fast0) {
             ORBFE_HIP(hipEventRecord(ev_fork0, s));
@@ -560,10 +559,8 @@ struct orbfe_extractor {
         }
         // The blur only needs the pyramid, and only k_orient_describe needs the blur: it runs on a second stream, forked in front of
         // FAST.  Measured on the C2 batch (step time with the detector running / extractor alone, ms): fork in front of FAST 1.83 /
-        // 1.76, fork after FAST (blur next to the quadtree) 1.88 / 1.76, no fork 1.97 / 1.75 -- orbfe_extractor_debug_kernel_times
-        // codes 20..22 switch, ORBFE_BLUR_PLACE in the bench.
+        // 1.76, fork after FAST (blur next to the quadtree) 1.88 / 1.76, no fork 1.97 / 1.75 (again in round 6: tools/sweeps.md).
         hipStream_t aux_stream = user_aux ? user_aux : this->aux_stream;
-        if (blur_place == 2) aux_stream = s;
         // strips [first, first + count) of the strip list (level-major: level 0's strips come first)
         auto blur_strips = [&](int first, int count) {
             if (count <= 0) return;
@@ -590,7 +587,7 @@ struct orbfe_extractor {
             ORBFE_HIP(hipEventRecord(ev_join, aux_stream));
             return ORBFE_OK;
         };
-        if (blur_place == 1) { int rcb = launch_blur(); if (rcb) return rcb; }
+        if ((rc = launch_blur())) return rc;
         if (follow && follow != this && follow->stage_recorded && follow_fast_stage >= 1 && follow_fast_stage <= 4)
             ORBFE_HIP(hipStreamWaitEvent(s, follow->ev_stage[follow_fast_stage - 1], 0));
         if ((rc = launch_fast(s, fast0 ? ncells_l0 : 0, ncells_total))) return rc;
@@ -602,7 +599,6 @@ struct orbfe_extractor {
             return ORBFE_OK;
         };
         if ((rc = stage_event(0))) return rc;
-        if (blur_place == 0) { int rcb = launch_blur(); if (rcb) return rcb; }
         {
             // fast path: count-pyramid quadtree (no keypoint movement); general kernel only for flagged levels
             int max_ini = 1;
@@ -642,14 +638,7 @@ struct orbfe_extractor {
         hipLaunchKernelGGL(k_level_offsets, dim3(B), dim3(256), 0, s, d_lvlcnt.as<int32_t>(), d_lvloff.as<int32_t>(),
                            d_n, nlevels, B, capacity, d_overflow.as<int32_t>() + flag_word, dg, d_lvlout.as<uint32_t>(), out_total,
                            d_flatkv.as<uint32_t>(), d_flatlvl.as<uint8_t>(), d_worklist.as<int32_t>());
-        if (blur_place == 2) { // no fork: the blur runs in the main stream between the quadtree and the descriptors
-            hipStream_t keep = aux_stream;
-            aux_stream = s;
-            int rcb = launch_blur();
-            aux_stream = keep;
-            if (rcb) return rcb;
-        } else
-            ORBFE_HIP(hipStreamWaitEvent(s, ev_join, 0));
+        ORBFE_HIP(hipStreamWaitEvent(s, ev_join, 0));
         stage_recorded = true;
         // the descriptors: here, or -- extractor_defer_describe(), the batched pipeline -- when the caller says so (describe_deferred())
         late = Late{true, src0, B, capacity, d_kps_out, d_desc_out, d_n, s};
@@ -1013,18 +1002,21 @@ int orbfe_extractor_set_early_stream(orbfe_extractor* h, void* stream)
     return ORBFE_OK;
 }
 
+int orbfe_extractor_debug_control(orbfe_extractor* h, const char* key, int value)
+{
+    if (!h || !key) return fail(ORBFE_ERR_INVALID, "orbfe_extractor_debug_control: null argument");
+    const bool on_off = value == 0 || value == 1;
+    if (!strcmp(key, "kernel_timing") && on_off) { h->timer.enabled = value; h->timer.reset_history(); }
+    else if (!strcmp(key, "general_quadtree") && on_off) h->force_general_quadtree = value;
+    else if (!strcmp(key, "pyramid_depth") && value >= 0 && value <= 6) h->force_pyramid_depth = value;   // 0 = by the levels' node counts
+    else if (!strcmp(key, "blur_mfma") && on_off) h->blur_mfma = value;   // the blur on the matrix cores (default) / k_blur7
+    else return fail(ORBFE_ERR_INVALID, "orbfe_extractor_debug_control: unknown key \"%s\" or value %d", key, value);
+    return ORBFE_OK;
+}
+
 int orbfe_extractor_debug_kernel_times(orbfe_extractor* h, float* out_us, int capacity)
 {
-    if (!h) return fail(ORBFE_ERR_INVALID, "null handle");
-    if (!out_us) { // toggles: 0/1 = kernel timing off/on; 2/3 = force the general quadtree kernel on/off (tests)
-        if (capacity == 2) h->force_general_quadtree = true;
-        else if (capacity == 3) h->force_general_quadtree = false;
-        else if (capacity >= 10 && capacity <= 16) h->force_pyramid_depth = capacity - 10; // 10 = default depth
-        else if (capacity >= 20 && capacity <= 22) h->blur_place = capacity - 20;
-        else if (capacity == 23 || capacity == 24) h->blur_mfma = capacity == 23;   // the blur on the matrix cores (default) / k_blur7
-        else { h->timer.enabled = capacity != 0; h->timer.reset_history(); }
-        return 0;
-    }
+    if (!h || !out_us) return fail(ORBFE_ERR_INVALID, "orbfe_extractor_debug_kernel_times: null argument");
     if (capacity < 0) return h->timer.collect_median(out_us, -capacity, nullptr);
     return h->timer.collect(out_us, capacity);
 }
