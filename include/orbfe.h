@@ -747,7 +747,11 @@ typedef struct orbfe_pipeline_config {
     int32_t check_orientation;         /* 1 */
     /* scheduling; -1 = the measured default for the frame size: extractor engine sets, result sets in rotation,
      * phase lock of the engine sets (orbfe_extractor_follow stage), stage of the extractor's previous batch the detector's batch starts
-     * behind, matching enqueued one step late, the detector's /2 pyramid in line on its stream */
+     * behind, matching enqueued one step late, the detector's /2 pyramid in line on its stream.  They change the order of work, never
+     * the results.  With two or more engine sets a batch's descriptor kernel is enqueued one step late (ORBFE_DESCRIBE_LATE, on by
+     * default), and that forces defer_post on whatever was asked for.  A lock on stage 3, the descriptors (phase_pin % 10 == 3,
+     * phase_pin / 10 == 3 or det_pin % 10 == 3), turns the late describe off.  orbfe_pipeline_engine_sets reads back the six fields in
+     * effect; whether the late describe is on is not reported (above 640 x 480, where defer_post defaults to 0, it shows there). */
     int32_t engine_sets, record_sets, phase_pin, det_pin, defer_post, det_nofork;
 } orbfe_pipeline_config;
 typedef struct orbfe_record_layout {
@@ -763,13 +767,15 @@ int orbfe_pipeline_config_default(orbfe_pipeline_config* cfg, int frames, int ro
 orbfe_pipeline* orbfe_pipeline_create(const orbfe_pipeline_config* cfg);
 void orbfe_pipeline_destroy(orbfe_pipeline* p);
 int orbfe_pipeline_layout(const orbfe_pipeline* p, orbfe_record_layout* out);
-/* One batch: d_imgs = frames x rows x pitch bytes on the pipeline's device (pitch >= cols; frames only have to stay valid until the
- * step's engines are done -- orbfe_pipeline_input_done).  *record_set = index of the set the batch is written to. */
+/* One batch: d_imgs = frames x rows x pitch bytes on the pipeline's device (pitch >= cols; the frames have to stay valid and unchanged
+ * until orbfe_pipeline_input_done for the batch, or orbfe_pipeline_synchronize, has returned: a kernel of the batch may be enqueued
+ * after this call).  *record_set = index of the set the batch is written to. */
 int orbfe_pipeline_step(orbfe_pipeline* p, const uint8_t* d_imgs, size_t pitch, int32_t* record_set);
 /* The same with the frames in HOST memory (rows of `step` bytes, frames contiguous; page-locked -- orbfe_host_alloc -- for the copy to
  * overlap): the pipeline uploads the batch into a ring of three device buffers on a copy stream of its own, ahead of the engines,
  * and copies every batch's record set back to page-locked host memory on a second copy stream behind the batch's post-work; both
- * overlap with the engines of the neighbouring batches.  h_imgs must stay valid until the upload is done (orbfe_pipeline_input_done).
+ * overlap with the engines of the neighbouring batches.  h_imgs must stay valid and unchanged until orbfe_pipeline_input_done for
+ * the batch, or orbfe_pipeline_synchronize, has returned.
  * orbfe_pipeline_host_records: the host copy of record set `set` (waits for its copy; valid until the set is written again, R steps on). */
 int orbfe_pipeline_step_host(orbfe_pipeline* p, const uint8_t* h_imgs, size_t step, int32_t* record_set);
 int orbfe_pipeline_host_records(orbfe_pipeline* p, int set, const uint8_t** h_records);
@@ -791,8 +797,9 @@ int orbfe_device_upload_rows(void* d_dst, size_t dpitch, const void* src, size_t
 int orbfe_device_download(void* dst, const void* d_src, size_t bytes);
 int orbfe_pipeline_flush(orbfe_pipeline* p);                 /* enqueue the held-back post-work (matching, gather) of the newest batch */
 int orbfe_pipeline_synchronize(orbfe_pipeline* p);           /* flush + wait for everything enqueued */
-/* wait until the engines of the batch written to `record_set` have read their frames (the input buffer may be reused).  The engines
- * of a step are enqueued by the step itself, so nothing has to be flushed first. */
+/* wait until the engines of the batch written to `record_set` have read their frames: the call that releases the caller's input buffer,
+ * device frames and host frames alike.  The batch's descriptor kernel may still be held back (the late describe of the next step): for
+ * the newest batch this call enqueues it first, so nothing has to be flushed before. */
 int orbfe_pipeline_input_done(orbfe_pipeline* p, int record_set);
 /* capacity flags since the last call (synchronises): out[0] extractor overflow, [1] SearchForInitialization pool overflow (the pool
  * has been grown: repeat), [2] frames the detector flagged, [3] the union of their flags.  All zero = results complete. */

@@ -103,7 +103,9 @@ struct orbfe_extractor {
     int follow_stage = 0;                // 1 = the other's FAST, 2 = its quadtree, 3 = its descriptors (the whole batch), 4 = its resize chain
     int follow_fast_stage = 0;           // a second gate in front of this handle's FAST (0 = none): the resize chain may run earlier
     hipEvent_t ev_stage[4] = {nullptr, nullptr, nullptr, nullptr};   // after FAST, the quadtree, the descriptors; [3] = after the resize chain (FAST starts)
-    bool stage_recorded = false;
+    bool stage_recorded = false;         // a batch's front part has been enqueued.  A stage's event is created when the stage is first
+                                         // enqueued -- the descriptors may come a step later (extractor_defer_describe) -- and a wait skips
+                                         // an event that does not exist yet
     // FAST of level 0 from the start of the batch, next to the resize chain: 0 off (default), 1 on the handle's second stream (or the one
     // named by orbfe_extractor_set_early_stream), 2 on the lent one.  Measured in round 3 (profiles/r03_fast0_early.txt): the launch
     // does overlap the resize chain, but the C2 step does not move (1.5365 ms either way) -- the chip was issue-bound there already
@@ -497,7 +499,7 @@ struct orbfe_extractor {
         last_nframes = B;
         last_src0 = src0;
         timer.begin();
-        if (follow && follow != this && follow->stage_recorded && follow_stage >= 1 && follow_stage <= 4)
+        if (follow && follow != this && follow->stage_recorded && follow_stage >= 1 && follow_stage <= 4 && follow->ev_stage[follow_stage - 1])
             ORBFE_HIP(hipStreamWaitEvent(s, follow->ev_stage[follow_stage - 1], 0));
         timer.mark(s, "start");
         auto launch_fast = [&](hipStream_t st, int cell_base, int cell_end) -> int {
@@ -588,7 +590,7 @@ struct orbfe_extractor {
             return ORBFE_OK;
         };
         if ((rc = launch_blur())) return rc;
-        if (follow && follow != this && follow->stage_recorded && follow_fast_stage >= 1 && follow_fast_stage <= 4)
+        if (follow && follow != this && follow->stage_recorded && follow_fast_stage >= 1 && follow_fast_stage <= 4 && follow->ev_stage[follow_fast_stage - 1])
             ORBFE_HIP(hipStreamWaitEvent(s, follow->ev_stage[follow_fast_stage - 1], 0));
         if ((rc = launch_fast(s, fast0 ? ncells_l0 : 0, ncells_total))) return rc;
         timer.mark(s, "fast_cells");
@@ -655,7 +657,7 @@ struct orbfe_extractor {
         if (!late.pending) return ORBFE_OK;
         late.pending = false;
         hipStream_t s = late.s;
-        if (gate && gate != this && gate->stage_recorded && gate_stage >= 1 && gate_stage <= 4)
+        if (gate && gate != this && gate->stage_recorded && gate_stage >= 1 && gate_stage <= 4 && gate->ev_stage[gate_stage - 1])
             ORBFE_HIP(hipStreamWaitEvent(s, gate->ev_stage[gate_stage - 1], 0));
         ImgView pyr{d_pyr.as<uint8_t>(), d_pyr.as<uint8_t>(), pyr_fbytes, 0};
         ImgView blur{d_blur.as<uint8_t>(), d_blur.as<uint8_t>(), blur_fbytes, 0};
@@ -990,7 +992,7 @@ int orbfe_extractor_stage_wait(orbfe_extractor* h, int stage, void* stream)
     if (!h || stage < 1 || stage > 4) return fail(ORBFE_ERR_INVALID, "orbfe_extractor_stage_wait: invalid argument");
     int rc = use_device(h->device);
     if (rc) return rc;
-    if (h->stage_recorded) ORBFE_HIP(hipStreamWaitEvent((hipStream_t)stream, h->ev_stage[stage - 1], 0));
+    if (h->stage_recorded && h->ev_stage[stage - 1]) ORBFE_HIP(hipStreamWaitEvent((hipStream_t)stream, h->ev_stage[stage - 1], 0));
     return ORBFE_OK;
 }
 

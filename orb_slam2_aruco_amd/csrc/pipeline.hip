@@ -392,7 +392,10 @@ orbfe_pipeline* orbfe_pipeline_create(const orbfe_pipeline_config* cfg)
         // 1.308 against 1.338 ms per C2 step (twelve interleaved runs each; resize 294 - 336 us, FAST 810 - 890 instead of 610 - 690).
         // With the blur on the matrix cores (k_blur7_mfma) FAST has the vector ALUs more to itself and every size gains: C2 1.265
         // against 1.327, 1280 x 720 3.70 against 3.74, 1920 x 1080 3.13 against 3.21 ms.
-        p->describe_late = pick(-1, "ORBFE_DESCRIBE_LATE", 1) != 0 && p->D > 1;
+        // A lock on stage 3 -- the descriptors of a batch -- would be circular with it: the descriptors of batch i - 1 wait for the
+        // resize chain of batch i.  Such a lock turns it off.
+        const bool stage3_lock = p->phase_pin % 10 == 3 || p->phase_pin / 10 == 3 || p->det_pin % 10 == 3;
+        p->describe_late = pick(-1, "ORBFE_DESCRIBE_LATE", 1) != 0 && p->D > 1 && !stage3_lock;
         if (p->describe_late) p->defer_post = true;
         p->cap = orbfe_extractor_max_keypoints(p->ex[0]);
     } else
@@ -630,7 +633,7 @@ static int step_body(orbfe_pipeline* p, const uint8_t* d_imgs, size_t pitch, int
         if (p->comm && i >= p->R) ORBFE_HIP(hipStreamWaitEvent(st_det_i, p->gather_done[cur], 0)); // batch i - R has left this record set
         if (p->host_mode && p->rb_valid[(size_t)cur]) ORBFE_HIP(hipStreamWaitEvent(st_det_i, p->rb_done[(size_t)cur], 0)); // ... and has been copied to the host
         if (in_slot >= 0) { ORBFE_HIP(hipStreamWaitEvent(st_det_i, p->in_ready[in_slot], 0)); }
-        if (p->det_pin && p->use_orb) {
+        if (p->det_pin % 10 && p->use_orb) {   // (det_pin = 10: the extractor first, the detector ungated)
             const long j = p->det_pin >= 10 ? i : i - 1; // + 10: a stage of THIS batch's extractor, which is then enqueued first
             if (j >= 0 && (rc = orbfe_extractor_stage_wait(p->ex[(size_t)(j % p->D)], p->det_pin % 10, st_det_i))) return rc;
         }
@@ -716,6 +719,9 @@ int orbfe_pipeline_input_done(orbfe_pipeline* p, int set)
     if (!p || set < 0 || set >= p->R) return fail(ORBFE_ERR_INVALID, "orbfe_pipeline_input_done: invalid argument");
     int rc = use_device(p->cfg.device);
     if (rc) return rc;
+    // the newest batch's descriptor kernel, held back by the late describe, reads level 0 from the caller's frames and records the
+    // batch's ex_done: enqueue it now (ungated) instead of at the next step
+    if (p->late_set >= 0 && p->late_cur == set && (rc = p->finish_describe(-1))) { p->failed = true; return rc; }
     if (p->use_orb) ORBFE_HIP(hipEventSynchronize(p->ex_done[(size_t)set]));
     if (p->use_aruco) ORBFE_HIP(hipEventSynchronize(p->det_done[(size_t)set]));
     return ORBFE_OK;
