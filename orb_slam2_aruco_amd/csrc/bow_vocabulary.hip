@@ -378,6 +378,36 @@ struct BowMatchWorkspace {
 };
 thread_local ThreadWorkspaces<BowMatchWorkspace> tl_bow_ws; // per (thread, device): host-pointer entry points only
 
+// one frame of a host-pointer BoW search: keypoints, descriptors and its FeatureVector (nfv nodes)
+struct BowHostFrame {
+    const orbfe_keypoint* kps; const uint8_t* desc; int n;
+    const uint32_t* fv_node; const int32_t* fv_offset; const uint32_t* fv_feature; int nfv;
+};
+
+// stages the two frames of a host-pointer BoW search in w as the batch layout of one pair (frame 1 in block 0, frame 2 in block 1
+// of `cap` keypoints) with their per-keypoint flags (2 cap bytes)
+int bow_stage_pair(BowMatchWorkspace& w, const BowHostFrame (&f)[2], int cap, const uint8_t* flags)
+{
+    const size_t C = (size_t)cap;
+    int rc;
+    if ((rc = w.kps.ensure(2 * C * sizeof(orbfe_keypoint))) || (rc = w.desc.ensure(2 * C * 32)) || (rc = w.valid.ensure(2 * C)) ||
+        (rc = w.n.ensure(16)) || (rc = w.fn.ensure(2 * C * 4)) || (rc = w.fo.ensure(2 * (C + 1) * 4)) || (rc = w.ff.ensure(2 * C * 4)) ||
+        (rc = w.nf.ensure(16)) || (rc = w.m12.ensure(C * 4)) || (rc = w.m21.ensure(C * 4)) || (rc = w.nm.ensure(64)))
+        return rc;
+    const int32_t nn[2] = {f[0].n, f[1].n}, nf[2] = {f[0].nfv, f[1].nfv};
+    ORBFE_HIP(hipMemcpy(w.valid.p, flags, 2 * C, hipMemcpyHostToDevice));
+    ORBFE_HIP(hipMemcpy(w.n.p, nn, 8, hipMemcpyHostToDevice));
+    ORBFE_HIP(hipMemcpy(w.nf.p, nf, 8, hipMemcpyHostToDevice));
+    for (int i = 0; i < 2; i++) {
+        ORBFE_HIP(hipMemcpy(w.kps.as<orbfe_keypoint>() + i * C, f[i].kps, (size_t)f[i].n * sizeof(orbfe_keypoint), hipMemcpyHostToDevice));
+        ORBFE_HIP(hipMemcpy(w.desc.as<uint8_t>() + i * C * 32, f[i].desc, (size_t)f[i].n * 32, hipMemcpyHostToDevice));
+        ORBFE_HIP(hipMemcpy(w.fn.as<uint32_t>() + i * C, f[i].fv_node, (size_t)f[i].nfv * 4, hipMemcpyHostToDevice));
+        ORBFE_HIP(hipMemcpy(w.fo.as<int32_t>() + i * (C + 1), f[i].fv_offset, (size_t)(f[i].nfv + 1) * 4, hipMemcpyHostToDevice));
+        ORBFE_HIP(hipMemcpy(w.ff.as<uint32_t>() + i * C, f[i].fv_feature, (size_t)f[i].fv_offset[f[i].nfv] * 4, hipMemcpyHostToDevice));
+    }
+    return ORBFE_OK;
+}
+
 int norm_of(int scoring) { return scoring == 5 ? 0 : scoring == 1 ? 2 : 1; } // ScoringObject.h:74-91
 
 // builds the device tree from nodes given in file order (node 0 = root, implicit)
@@ -685,31 +715,14 @@ int orbfe_search_for_triangulation(const orbfe_keypoint* kps1, const uint8_t* de
     if (n1 == 0 || n2 == 0 || nfv1 == 0 || nfv2 == 0) return ORBFE_OK;
     const int cap = std::max(n1, n2);
     if (cap > SB_MAX) return fail(ORBFE_ERR_CAPACITY, "orbfe_search_for_triangulation: at most %d features per frame", SB_MAX);
-    BowMatchWorkspace& w = tl_bow_ws.get();
-    const size_t C = (size_t)cap;
-    if ((rc = w.kps.ensure(2 * C * sizeof(orbfe_keypoint))) || (rc = w.desc.ensure(2 * C * 32)) || (rc = w.valid.ensure(2 * C)) ||
-        (rc = w.n.ensure(16)) || (rc = w.fn.ensure(2 * C * 4)) || (rc = w.fo.ensure(2 * (C + 1) * 4)) || (rc = w.ff.ensure(2 * C * 4)) ||
-        (rc = w.nf.ensure(64)) || (rc = w.m12.ensure(C * 4)) || (rc = w.m21.ensure(C * 4)) || (rc = w.nm.ensure(64)))
-        return rc;
-    std::vector<uint8_t> freef(2 * C, 1); // "no map point yet" (:710-714, :731-735)
+    std::vector<uint8_t> freef(2 * (size_t)cap, 1); // "no map point yet" (:710-714, :731-735)
     if (has_mp1) for (int i = 0; i < n1; i++) freef[i] = !has_mp1[i];
-    if (has_mp2) for (int i = 0; i < n2; i++) freef[C + i] = !has_mp2[i];
-    const int32_t nn[2] = {n1, n2}, nf[2] = {nfv1, nfv2};
+    if (has_mp2) for (int i = 0; i < n2; i++) freef[cap + i] = !has_mp2[i];
+    BowMatchWorkspace& w = tl_bow_ws.get();
+    const BowHostFrame f[2] = {{kps1, desc1, n1, fv_node1, fv_offset1, fv_feature1, nfv1}, {kps2, desc2, n2, fv_node2, fv_offset2, fv_feature2, nfv2}};
+    if ((rc = bow_stage_pair(w, f, cap, freef.data()))) return rc;
     const float fe[11] = {F12[0], F12[1], F12[2], F12[3], F12[4], F12[5], F12[6], F12[7], F12[8], ex, ey};
-    ORBFE_HIP(hipMemcpy(w.kps.p, kps1, (size_t)n1 * sizeof(orbfe_keypoint), hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.kps.as<orbfe_keypoint>() + C, kps2, (size_t)n2 * sizeof(orbfe_keypoint), hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.desc.p, desc1, (size_t)n1 * 32, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.desc.as<uint8_t>() + C * 32, desc2, (size_t)n2 * 32, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.valid.p, freef.data(), 2 * C, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.n.p, nn, 8, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.nf.p, nf, 8, hipMemcpyHostToDevice));
     ORBFE_HIP(hipMemcpy(w.nm.as<float>() + 4, fe, sizeof fe, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.fn.p, fv_node1, (size_t)nfv1 * 4, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.fn.as<uint32_t>() + C, fv_node2, (size_t)nfv2 * 4, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.fo.p, fv_offset1, (size_t)(nfv1 + 1) * 4, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.fo.as<int32_t>() + C + 1, fv_offset2, (size_t)(nfv2 + 1) * 4, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.ff.p, fv_feature1, (size_t)fv_offset1[nfv1] * 4, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.ff.as<uint32_t>() + C, fv_feature2, (size_t)fv_offset2[nfv2] * 4, hipMemcpyHostToDevice));
     rc = orbfe_search_for_triangulation_batch_device(w.kps.as<orbfe_keypoint>(), w.desc.as<uint8_t>(), w.valid.as<uint8_t>(), w.n.as<int32_t>(),
                                                      w.fn.as<uint32_t>(), w.fo.as<int32_t>(), w.ff.as<uint32_t>(), w.nf.as<int32_t>(), cap, nullptr,
                                                      nullptr, 1, w.nm.as<float>() + 4, w.nm.as<float>() + 13, scale_factors2, level_sigma2_2,
@@ -741,30 +754,13 @@ int orbfe_search_by_bow(const orbfe_keypoint* kps1, const uint8_t* desc1, const 
     if (n1 == 0 || n2 == 0 || nfv1 == 0 || nfv2 == 0) return ORBFE_OK;
     const int cap = std::max(n1, n2);
     if (cap > SB_MAX) return fail(ORBFE_ERR_CAPACITY, "orbfe_search_by_bow: at most %d features per frame", SB_MAX);
-    BowMatchWorkspace& w = tl_bow_ws.get();
-    const size_t C = (size_t)cap;
-    if ((rc = w.kps.ensure(2 * C * sizeof(orbfe_keypoint))) || (rc = w.desc.ensure(2 * C * 32)) || (rc = w.valid.ensure(2 * C)) ||
-        (rc = w.n.ensure(16)) || (rc = w.fn.ensure(2 * C * 4)) || (rc = w.fo.ensure(2 * (C + 1) * 4)) || (rc = w.ff.ensure(2 * C * 4)) ||
-        (rc = w.nf.ensure(16)) || (rc = w.m12.ensure(C * 4)) || (rc = w.m21.ensure(C * 4)) || (rc = w.nm.ensure(16)))
-        return rc;
     const bool any_valid = valid1 || valid2;
-    std::vector<uint8_t> valid(2 * C, 1);
+    std::vector<uint8_t> valid(2 * (size_t)cap, 1);
     if (valid1) memcpy(valid.data(), valid1, n1);
-    if (valid2) memcpy(valid.data() + C, valid2, n2);
-    const int32_t nn[2] = {n1, n2}, nf[2] = {nfv1, nfv2};
-    ORBFE_HIP(hipMemcpy(w.kps.p, kps1, (size_t)n1 * sizeof(orbfe_keypoint), hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.kps.as<orbfe_keypoint>() + C, kps2, (size_t)n2 * sizeof(orbfe_keypoint), hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.desc.p, desc1, (size_t)n1 * 32, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.desc.as<uint8_t>() + C * 32, desc2, (size_t)n2 * 32, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.valid.p, valid.data(), 2 * C, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.n.p, nn, 8, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.nf.p, nf, 8, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.fn.p, fv_node1, (size_t)nfv1 * 4, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.fn.as<uint32_t>() + C, fv_node2, (size_t)nfv2 * 4, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.fo.p, fv_offset1, (size_t)(nfv1 + 1) * 4, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.fo.as<int32_t>() + C + 1, fv_offset2, (size_t)(nfv2 + 1) * 4, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.ff.p, fv_feature1, (size_t)fv_offset1[nfv1] * 4, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.ff.as<uint32_t>() + C, fv_feature2, (size_t)fv_offset2[nfv2] * 4, hipMemcpyHostToDevice));
+    if (valid2) memcpy(valid.data() + cap, valid2, n2);
+    BowMatchWorkspace& w = tl_bow_ws.get();
+    const BowHostFrame f[2] = {{kps1, desc1, n1, fv_node1, fv_offset1, fv_feature1, nfv1}, {kps2, desc2, n2, fv_node2, fv_offset2, fv_feature2, nfv2}};
+    if ((rc = bow_stage_pair(w, f, cap, valid.data()))) return rc;
     rc = orbfe_search_by_bow_batch_device(w.kps.as<orbfe_keypoint>(), w.desc.as<uint8_t>(), any_valid ? w.valid.as<uint8_t>() : nullptr,
                                           w.n.as<int32_t>(), w.fn.as<uint32_t>(), w.fo.as<int32_t>(), w.ff.as<uint32_t>(), w.nf.as<int32_t>(),
                                           cap, nullptr, nullptr, 1, valid2 != nullptr, nnratio, check_orientation, accept_max, factor,

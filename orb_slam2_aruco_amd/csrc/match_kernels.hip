@@ -776,7 +776,7 @@ __global__ __launch_bounds__(256) void k_knn2_csr(const uint8_t* __restrict__ Q,
 
 // ---------------------------------------------------------------------------- SearchByProjection ---------------
 // The matching loop of ORBmatcher::SearchByProjection (ORBmatcher.cc:45-129) on flat arrays; see include/orbfe.h.
-// One workgroup (16 waves) per call.
+// One workgroup (16 waves) per frame.
 //   A  the Frame grid (Frame.cc:183-198, :335-345): keypoints sorted by (cell, index); cell start offsets; per-rank
 //      position / octave / taken flag in LDS.  Sorted order inside a run of cells of one grid column IS the order in
 //      which GetFeaturesInArea (Frame.cc:280-333) walks them, so a query's candidates are one contiguous range per column.
@@ -799,7 +799,7 @@ struct SbpBest { // mode 2 only (q_blocks: modes 1 and 2)
     int32_t* qbin;            // nq entries of scratch
     // any mode: the reprojection gate of Fuse (ORBmatcher.cc:925-931): skip a candidate when e2 * inv_sigma2[level] > chi2
     double chi2;              // 0 = no gate
-    float inv_sigma2[16];
+    const float* inv_sigma2;  // 16 entries (the kernel argument's: a copy here would live in scratch)
 };
 
 __device__ __forceinline__ void sbp_frame(
@@ -1052,20 +1052,9 @@ __device__ __forceinline__ void sbp_frame(
     if (lane == 0) *nmatches_out = nmatches;
 }
 
-__global__ __launch_bounds__(SBP_THREADS) void k_search_by_projection(
-    const orbfe_keypoint* __restrict__ kps, const uint8_t* __restrict__ desc, int n, int ncap /*pow2 >= n*/, float4 bnd,
-    const SbpQuery* __restrict__ queries, const uint8_t* __restrict__ qdesc, int nq, uint8_t* __restrict__ taken, int mode,
-    int th_high, float nnratio, uint16_t* __restrict__ row_rank, uint8_t* __restrict__ row_dist, int32_t* __restrict__ row_cnt,
-    int row_stride, int32_t* __restrict__ best_idx, int32_t* __restrict__ best_dist, int32_t* __restrict__ best_level,
-    int32_t* __restrict__ second_dist, int32_t* __restrict__ second_level, int32_t* __restrict__ match,
-    int32_t* __restrict__ nmatches_out, int32_t* __restrict__ overflow, SbpBest bo)
-{
-    sbp_frame(kps, desc, n, ncap, bnd, queries, qdesc, nq, taken, mode, th_high, nnratio, row_rank, row_dist, row_cnt, row_stride, best_idx,
-              best_dist, best_level, second_dist, second_level, match, nmatches_out, overflow, bo);
-}
-
-// The same search over the frames of a batch resident on the device: workgroup f = frame f of blocks of `capacity` keypoint
-// records and `qcapacity` query records (the layouts of orbfe_extract_batch_device).
+// The search over the frames of a batch resident on the device: workgroup f = frame f of blocks of `capacity` keypoint
+// records and `qcapacity` query records (the layouts of orbfe_extract_batch_device).  n / nq NULL: every frame holds `capacity`
+// keypoints / `qcapacity` queries (the host-pointer searches: one frame whose counts are known on the host).
 struct SbpBatch {
     const orbfe_keypoint* kps; const uint8_t* desc; const int32_t* n; int capacity;
     const SbpQuery* queries; const uint8_t* qdesc; const int32_t* nq; int qcapacity;
@@ -1081,7 +1070,7 @@ __global__ __launch_bounds__(SBP_THREADS) void k_search_by_projection_batch(SbpB
                                                                             float nnratio, float factor, int check_ori)
 {
     const size_t f = blockIdx.x, ko = f * B.capacity, qo = f * B.qcapacity;
-    const int n = min(B.n[f], B.capacity), nq = min(B.nq[f], B.qcapacity);
+    const int n = B.n ? min(B.n[f], B.capacity) : B.capacity, nq = B.nq ? min(B.nq[f], B.qcapacity) : B.qcapacity;
     SbpBest bo{};
     bo.q_angle = B.q_angle ? B.q_angle + qo : nullptr;
     bo.q_blocks = B.q_observed ? B.q_observed + qo : nullptr;
@@ -1089,8 +1078,7 @@ __global__ __launch_bounds__(SBP_THREADS) void k_search_by_projection_batch(SbpB
     bo.match_cur = B.match_cur ? B.match_cur + ko : nullptr;
     bo.qbin = B.qbin ? B.qbin + qo : nullptr;
     bo.chi2 = B.chi2;
-#pragma unroll
-    for (int l = 0; l < 16; l++) bo.inv_sigma2[l] = B.inv_sigma2[l];
+    bo.inv_sigma2 = B.inv_sigma2;
     sbp_frame(B.kps + ko, B.desc + ko * 32, n, ncap, bnd, B.queries + qo, B.qdesc + (B.qdesc_shared ? 0 : qo * 32), nq, B.taken ? B.taken + ko : nullptr, mode, th_high,
               nnratio, B.row_rank + qo * B.row_stride, B.row_dist + qo * B.row_stride, B.row_cnt + qo, B.row_stride,
               B.best_idx ? B.best_idx + qo : nullptr, B.best_dist ? B.best_dist + qo : nullptr, B.best_level ? B.best_level + qo : nullptr,
@@ -1305,12 +1293,13 @@ __global__ __launch_bounds__(256) void k_distinctive(const uint8_t* __restrict__
 }
 
 struct MatchWorkspace {
-    DevBuf pidx, pbest, psecond, csr_cnt, csr_idx, csr_dist, scratch, overflow, prev;
+    DevBuf pidx, pbest, psecond, csr_cnt, csr_idx, csr_dist, scratch, prev;
     DevBuf sbp_batch_overflow; // flag of the _batch_device searches: sticky until orbfe_search_by_projection_batch_status reads it
     DevBuf sfi_overflow;  // SearchForInitialization's two flag words: zeroed when allocated and whenever they are read (no memset launch per batch)
-    DevBuf q, t, nq, nt, oidx, obest, osecond, kps, desc, nk, m12, nm;
+    DevBuf sbp_host;      // the host-pointer projection searches: inputs and results of one call, in slices (sbp_host_run)
+    DevBuf q, t, nt, oidx, obest, osecond, kps, desc, nk, m12, nm;
     int csr_per_pair = 0; // candidate pool entries per frame pair of SearchForInitialization (grown on overflow)
-    int sbp_stride = 0;   // candidate row stride of k_search_by_projection (grown on overflow)
+    int sbp_stride = 0;   // candidate row stride of k_search_by_projection_batch (grown on overflow)
     // host-pointer SearchForInitialization: a stream of its own (the null stream synchronises with every blocking stream of the
     // process) and page-locked staging, so that a call is a few queued copies and one wait
     hipStream_t host_stream = nullptr;
@@ -1449,6 +1438,149 @@ static int sfi_read_flags(MatchWorkspace& w, int32_t* need)
     if (f[0] > SFI_MAXL0) return fail(ORBFE_ERR_CAPACITY, "%d level-0 keypoints in a frame exceed the supported %d", f[0], SFI_MAXL0);
     if (f[1] > w.csr_per_pair) w.csr_per_pair = (f[1] + 1023) / 1024 * 1024; // the next batch on this stream has the room
     return ORBFE_OK;
+}
+
+// the longest candidate list of a search that overflowed decides the row stride of the next one
+static void sbp_grow_stride(MatchWorkspace& w, int overflow)
+{
+    if (overflow > w.sbp_stride) w.sbp_stride = (overflow + 63) / 64 * 64;
+}
+
+// Every projection search is this launch: nframes workgroups over B, whose candidate rows (row_*) it sizes at the workspace's
+// stride.  A frame's grid lives in LDS, sized by the keypoint capacity.
+static int sbp_launch(MatchWorkspace& w, SbpBatch B, int nframes, float4 bnd, int mode, int th_high, float nnratio, float factor,
+                      int check_ori, hipStream_t s)
+{
+    if (B.capacity > 65535) return fail(ORBFE_ERR_INVALID, "more than 65535 keypoints per frame are unsupported");
+    int ncap = 64;
+    while (ncap < B.capacity) ncap <<= 1;
+    const size_t lds = (size_t)ncap * (4 + 8 + 1 + 1) + (SBP_CELLS + 2) * 2 + 64;
+    if (lds > 150 * 1024) return fail(ORBFE_ERR_CAPACITY, "%d keypoints do not fit the grid kernel's LDS", B.capacity);
+    w.sbp_stride = std::max(w.sbp_stride, 128);
+    const size_t NQ = (size_t)nframes * B.qcapacity;
+    int rc;
+    if ((rc = w.csr_idx.ensure(NQ * w.sbp_stride * 2)) || (rc = w.csr_dist.ensure(NQ * w.sbp_stride)) || (rc = w.csr_cnt.ensure(NQ * 4)) ||
+        (rc = ensure_dyn_lds(reinterpret_cast<const void*>(&k_search_by_projection_batch), lds)))
+        return rc;
+    B.row_rank = w.csr_idx.as<uint16_t>(); B.row_dist = w.csr_dist.as<uint8_t>(); B.row_cnt = w.csr_cnt.as<int32_t>(); B.row_stride = w.sbp_stride;
+    hipLaunchKernelGGL(k_search_by_projection_batch, dim3(nframes), dim3(SBP_THREADS), lds, s, B, ncap, bnd, mode, th_high, nnratio, factor,
+                       check_ori);
+    ORBFE_HIP(hipGetLastError());
+    return ORBFE_OK;
+}
+
+// a host array that may be absent (NULL) or empty: copied when it is there
+static int upload(void* d, const void* h, size_t bytes)
+{
+    if (h && bytes) ORBFE_HIP(hipMemcpy(d, h, bytes, hipMemcpyHostToDevice));
+    return ORBFE_OK;
+}
+static int download(void* h, const void* d, size_t bytes)
+{
+    if (h && bytes) ORBFE_HIP(hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost));
+    return ORBFE_OK;
+}
+
+// uploads n map points (in w.scratch) and leaves their queries in d_q, on the null stream
+static int project_run(MatchWorkspace& w, const float* p3Dw, const uint8_t* valid, const float* min_dist, const float* max_dist,
+                       const float* normal, int n, const ProjectParams& P, SbpQuery* d_q)
+{
+    const size_t N = (size_t)n;
+    int rc;
+    if ((rc = w.scratch.ensure(N * (12 + 4 + 4 + 12 + 1)))) return rc;
+    float* d_p = w.scratch.as<float>();
+    float *d_min = d_p + 3 * N, *d_max = d_min + N, *d_nrm = d_max + N;
+    uint8_t* d_valid = reinterpret_cast<uint8_t*>(d_nrm + 3 * N);
+    if ((rc = upload(d_p, p3Dw, N * 12)) || (rc = upload(d_min, min_dist, N * 4)) || (rc = upload(d_max, max_dist, N * 4)) ||
+        (rc = upload(d_nrm, normal, N * 12)) || (rc = upload(d_valid, valid, N)))
+        return rc;
+    hipLaunchKernelGGL(k_project_map_points, dim3((n + 255) / 256), dim3(256), 0, 0, d_p, valid ? d_valid : nullptr, d_min, d_max,
+                       normal ? d_nrm : nullptr, n, P, d_q);
+    ORBFE_HIP(hipGetLastError());
+    return ORBFE_OK;
+}
+
+// One host-pointer search of one frame (orbfe_search_by_projection and the entry points after it).  Host arrays: a NULL input is
+// absent, a NULL output is not copied back.
+struct SbpHostCall {
+    const orbfe_keypoint* kps; const uint8_t* desc; int n; float4 bnd;
+    const uint8_t* taken;          // the frame's taken flags
+    int nq; const uint8_t* qdesc; const uint8_t* q_observed; const float* q_angle;
+    // the queries: the caller's windows, or map points x3Dw (valid: which exist) projected on the device by k_project_last_frame
+    // (kps_last != NULL, whose angles become q_angle) or by k_project_map_points (P != NULL)
+    const orbfe_window_query* window;
+    const float* x3Dw; const uint8_t* valid;
+    const orbfe_keypoint* kps_last; const float* Tcw; const float* K4; const float* scale; int nlevels; float th;
+    const ProjectParams* P; const float* min_dist; const float* max_dist; const float* normal;
+    int mode, th_high; float nnratio, factor; int check_ori;
+    double chi2; const float* inv_sigma2; // Fuse's gate: chi2 > 0, nlevels entries
+    int32_t *best_idx, *best_dist, *best_level, *second_dist, *second_level, *match, *match_cur, *nmatches;
+    uint8_t* taken_out;            // the taken flags after the search
+};
+
+// stages the call in w.sbp_host, builds or uploads the queries, searches (a second time, with a longer row stride, after an
+// overflow) and copies the results back; the null stream, one device synchronisation per search
+static int sbp_host_run(const SbpHostCall& c)
+{
+    MatchWorkspace& w = ws();
+    const size_t n = (size_t)c.n, nq = (size_t)c.nq;
+    size_t end = 0;
+    auto slice = [&end](size_t bytes) { const size_t o = end; end += (bytes + 255) / 256 * 256; return o; };
+    const size_t s_kps = slice(n * sizeof(orbfe_keypoint)), s_desc = slice(n * 32), s_taken = slice(n), s_cur = slice(n * 4);
+    const size_t s_q = slice(nq * sizeof(SbpQuery)), s_qdesc = slice(nq * 32), s_obs = slice(nq), s_angle = slice(nq * 4);
+    const size_t s_x3 = slice(nq * 12), s_last = slice(nq * sizeof(orbfe_keypoint)), s_valid = slice(nq), s_cam = slice((12 + 16) * 4);
+    const size_t s_out = slice(nq * 4 * 7), s_cnt = slice(8); // best_idx .. second_level, match, qbin | nmatches, overflow
+    int rc = w.sbp_host.ensure(end);
+    if (rc) return rc;
+    uint8_t* b = w.sbp_host.as<uint8_t>();
+    int32_t* o = reinterpret_cast<int32_t*>(b + s_out);
+    SbpBatch B{};
+    B.kps = reinterpret_cast<const orbfe_keypoint*>(b + s_kps); B.desc = b + s_desc; B.capacity = c.n;
+    B.queries = reinterpret_cast<const SbpQuery*>(b + s_q); B.qdesc = b + s_qdesc; B.qcapacity = c.nq;
+    B.taken = c.taken ? b + s_taken : nullptr; B.q_observed = c.q_observed ? b + s_obs : nullptr;
+    B.q_angle = c.q_angle || c.kps_last ? reinterpret_cast<float*>(b + s_angle) : nullptr;
+    if (c.best_idx) { B.best_idx = o; B.best_dist = o + nq; B.best_level = o + 2 * nq; B.second_dist = o + 3 * nq; B.second_level = o + 4 * nq; }
+    B.match = o + 5 * nq; B.qbin = o + 6 * nq; B.match_cur = reinterpret_cast<int32_t*>(b + s_cur);
+    B.nmatches = reinterpret_cast<int32_t*>(b + s_cnt); B.overflow = B.nmatches + 1;
+    if (c.chi2 > 0.0) { B.chi2 = c.chi2; for (int l = 0; l < 16; l++) B.inv_sigma2[l] = c.inv_sigma2[std::min(l, c.nlevels - 1)]; }
+    if ((rc = upload(b + s_kps, c.kps, n * sizeof(orbfe_keypoint))) || (rc = upload(b + s_desc, c.desc, n * 32)) ||
+        (rc = upload(b + s_qdesc, c.qdesc, nq * 32)) || (rc = upload(b + s_obs, c.q_observed, nq)) || (rc = upload(b + s_angle, c.q_angle, nq * 4)))
+        return rc;
+    SbpQuery* d_q = reinterpret_cast<SbpQuery*>(b + s_q);
+    if (c.window) rc = upload(d_q, c.window, nq * sizeof(orbfe_window_query));
+    else if (c.P) rc = project_run(w, c.x3Dw, c.valid, c.min_dist, c.max_dist, c.normal, c.nq, *c.P, d_q);
+    else {
+        float cam[12 + 16]; // Tcw, the scale factors
+        memcpy(cam, c.Tcw, 48);
+        for (int l = 0; l < 16; l++) cam[12 + l] = l < c.nlevels ? c.scale[l] : 0.0f;
+        if ((rc = upload(b + s_x3, c.x3Dw, nq * 12)) || (rc = upload(b + s_last, c.kps_last, nq * sizeof(orbfe_keypoint))) ||
+            (rc = upload(b + s_valid, c.valid, nq)) || (rc = upload(b + s_cam, cam, sizeof cam)))
+            return rc;
+        const float* d_cam = reinterpret_cast<const float*>(b + s_cam);
+        hipLaunchKernelGGL(k_project_last_frame, dim3((c.nq + 255) / 256), dim3(256), 0, 0, reinterpret_cast<const float*>(b + s_x3),
+                           c.valid ? b + s_valid : nullptr, reinterpret_cast<const orbfe_keypoint*>(b + s_last), c.nq, d_cam,
+                           make_float4(c.K4[0], c.K4[1], c.K4[2], c.K4[3]), c.bnd, d_cam + 12, c.nlevels, c.th, d_q,
+                           reinterpret_cast<float*>(b + s_angle));
+        ORBFE_HIP(hipGetLastError());
+    }
+    if (rc) return rc;
+    for (int attempt = 0;; attempt++) {
+        // a search marks keypoints taken: every attempt starts from the caller's flags
+        if ((rc = upload(b + s_taken, c.taken, n))) return rc;
+        ORBFE_HIP(hipMemset(B.overflow, 0, 4));
+        if ((rc = sbp_launch(w, B, 1, c.bnd, c.mode, c.th_high, c.nnratio, c.factor, c.check_ori, nullptr))) return rc;
+        ORBFE_HIP(hipDeviceSynchronize());
+        int32_t ovf = 0;
+        ORBFE_HIP(hipMemcpy(&ovf, B.overflow, 4, hipMemcpyDeviceToHost));
+        if (!ovf) break;
+        if (attempt) return fail(ORBFE_ERR_CAPACITY, "candidate row overflow (%d)", ovf);
+        sbp_grow_stride(w, ovf);
+    }
+    int32_t* const out[6] = {c.best_idx, c.best_dist, c.best_level, c.second_dist, c.second_level, c.match};
+    for (int k = 0; k < 6; k++)
+        if ((rc = download(out[k], o + k * nq, nq * 4))) return rc;
+    if ((rc = download(c.match_cur, B.match_cur, n * 4)) || (rc = download(c.nmatches, B.nmatches, 4))) return rc;
+    return download(c.taken_out, b + s_taken, n);
 }
 
 } // namespace orbfe
@@ -1653,154 +1785,16 @@ int orbfe_search_by_projection(const orbfe_keypoint* kps, const uint8_t* desc, i
         (nq && (!queries || !qdesc)) || (mode == 1 && nq && (!match || !nmatches)) ||
         (best_idx && (!best_dist || !best_level || !second_dist || !second_level)))
         return fail(ORBFE_ERR_INVALID, "orbfe_search_by_projection: invalid argument");
-    if (n > 65535) return fail(ORBFE_ERR_INVALID, "more than 65535 keypoints per frame are unsupported");
     int rc = use_device(device);
     if (rc) return rc;
     if (nmatches) *nmatches = 0;
     if (nq == 0) return ORBFE_OK;
-    int ncap = 64;
-    while (ncap < n) ncap <<= 1;
-    const size_t lds = (size_t)ncap * (4 + 8 + 1 + 1) + (SBP_CELLS + 2) * 2 + 64;
-    if (lds > 150 * 1024) return fail(ORBFE_ERR_CAPACITY, "%d keypoints do not fit the grid kernel's LDS", n);
-    MatchWorkspace& w = ws();
-    const size_t qo = (size_t)nq * 4;
-    for (int attempt = 0;; attempt++) {
-        const int stride = std::max(w.sbp_stride, 128);
-        if ((rc = w.kps.ensure((size_t)std::max(n, 1) * sizeof(orbfe_keypoint))) || (rc = w.desc.ensure((size_t)std::max(n, 1) * 32)) ||
-            (rc = w.q.ensure((size_t)nq * sizeof(orbfe_window_query))) || (rc = w.t.ensure((size_t)nq * 32)) ||
-            (rc = w.prev.ensure((size_t)std::max(n, 1))) || (rc = w.csr_idx.ensure((size_t)nq * stride * 2)) ||
-            (rc = w.csr_dist.ensure((size_t)nq * stride)) || (rc = w.csr_cnt.ensure(qo)) || (rc = w.obest.ensure(qo * 6)) ||
-            (rc = w.nm.ensure(16)) || (rc = w.overflow.ensure(16)) || (rc = w.pidx.ensure((size_t)nq + 16)))
-            return rc;
-        if (q_observed) ORBFE_HIP(hipMemcpy(w.pidx.p, q_observed, (size_t)nq, hipMemcpyHostToDevice));
-        if (n) {
-            ORBFE_HIP(hipMemcpy(w.kps.p, kps, (size_t)n * sizeof(orbfe_keypoint), hipMemcpyHostToDevice));
-            ORBFE_HIP(hipMemcpy(w.desc.p, desc, (size_t)n * 32, hipMemcpyHostToDevice));
-            if (taken) ORBFE_HIP(hipMemcpy(w.prev.p, taken, (size_t)n, hipMemcpyHostToDevice));
-        }
-        ORBFE_HIP(hipMemcpy(w.q.p, queries, (size_t)nq * sizeof(orbfe_window_query), hipMemcpyHostToDevice));
-        ORBFE_HIP(hipMemcpy(w.t.p, qdesc, (size_t)nq * 32, hipMemcpyHostToDevice));
-        ORBFE_HIP(hipMemset(w.overflow.p, 0, 4));
-        ORBFE_HIP(hipMemset(w.nm.p, 0, 4));
-        int32_t* o = w.obest.as<int32_t>();
-        SbpBest sb{};
-        sb.q_blocks = q_observed ? w.pidx.as<uint8_t>() : nullptr;
-        { int rc_lds_ = ensure_dyn_lds(reinterpret_cast<const void*>(&k_search_by_projection), (size_t)(lds)); if (rc_lds_) return rc_lds_; }
-        hipLaunchKernelGGL(k_search_by_projection, dim3(1), dim3(SBP_THREADS), lds, 0, w.kps.as<orbfe_keypoint>(),
-                           w.desc.as<uint8_t>(), n, ncap, frame_bounds(cols, rows, bounds), w.q.as<SbpQuery>(), w.t.as<uint8_t>(), nq,
-                           taken ? w.prev.as<uint8_t>() : nullptr, mode, th_high, nnratio, w.csr_idx.as<uint16_t>(),
-                           w.csr_dist.as<uint8_t>(), w.csr_cnt.as<int32_t>(), stride, o, o + nq, o + 2 * nq, o + 3 * nq,
-                           o + 4 * nq, o + 5 * nq, w.nm.as<int32_t>(), w.overflow.as<int32_t>(), sb);
-        ORBFE_HIP(hipGetLastError());
-        ORBFE_HIP(hipDeviceSynchronize());
-        int32_t ovf = 0;
-        ORBFE_HIP(hipMemcpy(&ovf, w.overflow.p, 4, hipMemcpyDeviceToHost));
-        if (!ovf) break;
-        if (attempt) return fail(ORBFE_ERR_CAPACITY, "candidate row overflow (%d)", ovf);
-        w.sbp_stride = (ovf + 63) / 64 * 64; // the longest candidate list decides the row stride; run again
-    }
-    const int32_t* o = w.obest.as<int32_t>();
-    if (best_idx) {
-        ORBFE_HIP(hipMemcpy(best_idx, o, qo, hipMemcpyDeviceToHost));
-        ORBFE_HIP(hipMemcpy(best_dist, o + nq, qo, hipMemcpyDeviceToHost));
-        ORBFE_HIP(hipMemcpy(best_level, o + 2 * nq, qo, hipMemcpyDeviceToHost));
-        ORBFE_HIP(hipMemcpy(second_dist, o + 3 * nq, qo, hipMemcpyDeviceToHost));
-        ORBFE_HIP(hipMemcpy(second_level, o + 4 * nq, qo, hipMemcpyDeviceToHost));
-    }
-    if (mode == 1) {
-        ORBFE_HIP(hipMemcpy(match, o + 5 * nq, qo, hipMemcpyDeviceToHost));
-        ORBFE_HIP(hipMemcpy(nmatches, w.nm.p, 4, hipMemcpyDeviceToHost));
-        if (taken && n) ORBFE_HIP(hipMemcpy(taken, w.prev.p, (size_t)n, hipMemcpyDeviceToHost));
-    }
-    return ORBFE_OK;
-}
-
-static int project_run(MatchWorkspace& w, const float* p3Dw, const uint8_t* valid, const float* min_dist, const float* max_dist,
-                       const float* normal, int n, const ProjectParams& P);
-
-// shared plumbing of the "best only" entry points: queries either come from the host or are projected on the device
-static int sbp_best_run(const orbfe_keypoint* kps, const uint8_t* desc, int n, int cols, int rows, const float* bounds,
-                        const orbfe_window_query* queries, const float* q_angle, const uint8_t* qdesc, const uint8_t* q_blocks, int nq,
-                        const uint8_t* taken, int th_high, int check_ori, float factor, int32_t* match_cur, int32_t* nmatches,
-                        // projection request (x3Dw != NULL): the queries are built on the device
-                        const float* x3Dw, const uint8_t* valid, const orbfe_keypoint* kps_last, const float* Tcw, const float* K4,
-                        const float* scale, int nlevels, float th,
-                        // map-point projection request (PP != NULL): k_project_map_points builds the queries from x3Dw / valid / the distances
-                        const ProjectParams* PP = nullptr, const float* min_dist = nullptr, const float* max_dist = nullptr)
-{
-    if (n > 65535) return fail(ORBFE_ERR_INVALID, "more than 65535 keypoints per frame are unsupported");
-    *nmatches = 0;
-    for (int i = 0; i < n; i++) match_cur[i] = -1;
-    if (nq == 0 || n == 0) return ORBFE_OK;
-    int ncap = 64;
-    while (ncap < n) ncap <<= 1;
-    const size_t lds = (size_t)ncap * (4 + 8 + 1 + 1) + (SBP_CELLS + 2) * 2 + 64;
-    if (lds > 150 * 1024) return fail(ORBFE_ERR_CAPACITY, "%d keypoints do not fit the grid kernel's LDS", n);
-    MatchWorkspace& w = ws();
-    const size_t qo = (size_t)nq * 4;
-    int rc;
-    for (int attempt = 0;; attempt++) {
-        const int stride = std::max(w.sbp_stride, 128);
-        if ((rc = w.kps.ensure((size_t)n * sizeof(orbfe_keypoint))) || (rc = w.desc.ensure((size_t)n * 32)) ||
-            (rc = w.q.ensure((size_t)nq * sizeof(orbfe_window_query))) || (rc = w.t.ensure((size_t)nq * 32)) ||
-            (rc = w.prev.ensure((size_t)n)) || (rc = w.csr_idx.ensure((size_t)nq * stride * 2)) ||
-            (rc = w.csr_dist.ensure((size_t)nq * stride)) || (rc = w.csr_cnt.ensure(qo)) || (rc = w.obest.ensure(qo * 3)) ||
-            (rc = w.nm.ensure(16)) || (rc = w.overflow.ensure(16)) || (rc = w.m12.ensure((size_t)n * 4)) ||
-            (rc = w.scratch.ensure((size_t)nq * 32 + 256)) || (rc = w.pidx.ensure((size_t)nq * sizeof(orbfe_keypoint) + nq + 256)))
-            return rc;
-        ORBFE_HIP(hipMemcpy(w.kps.p, kps, (size_t)n * sizeof(orbfe_keypoint), hipMemcpyHostToDevice));
-        ORBFE_HIP(hipMemcpy(w.desc.p, desc, (size_t)n * 32, hipMemcpyHostToDevice));
-        if (taken) ORBFE_HIP(hipMemcpy(w.prev.p, taken, (size_t)n, hipMemcpyHostToDevice));
-        ORBFE_HIP(hipMemcpy(w.t.p, qdesc, (size_t)nq * 32, hipMemcpyHostToDevice));
-        // scratch: [q_angle f32 x nq | x3Dw f32 x 3nq]; pidx: [kps_last | valid / blocks bytes]
-        float* d_angle = w.scratch.as<float>();
-        uint8_t* d_flags = w.pidx.as<uint8_t>() + (size_t)nq * sizeof(orbfe_keypoint);
-        if (PP) {
-            // the staging of project_run shares w.scratch / w.pidx (already large enough: no reallocation) with the arrays below
-            if ((rc = project_run(w, x3Dw, valid, min_dist, max_dist, nullptr, nq, *PP))) return rc;
-            ORBFE_HIP(hipDeviceSynchronize());
-            ORBFE_HIP(hipMemcpy(d_angle, q_angle, (size_t)nq * 4, hipMemcpyHostToDevice));
-        } else if (x3Dw) {
-            float* d_x = d_angle + nq;
-            ORBFE_HIP(hipMemcpy(d_x, x3Dw, (size_t)nq * 12, hipMemcpyHostToDevice));
-            ORBFE_HIP(hipMemcpy(w.pidx.p, kps_last, (size_t)nq * sizeof(orbfe_keypoint), hipMemcpyHostToDevice));
-            if (valid) ORBFE_HIP(hipMemcpy(d_flags, valid, (size_t)nq, hipMemcpyHostToDevice));
-            float h[12 + 16];
-            memcpy(h, Tcw, 48);
-            for (int l = 0; l < 16; l++) h[12 + l] = l < nlevels ? scale[l] : 0.0f;
-            if ((rc = w.pbest.ensure(sizeof h))) return rc;
-            ORBFE_HIP(hipMemcpy(w.pbest.p, h, sizeof h, hipMemcpyHostToDevice));
-            hipLaunchKernelGGL(k_project_last_frame, dim3((nq + 255) / 256), dim3(256), 0, 0, d_x, valid ? d_flags : nullptr,
-                               w.pidx.as<orbfe_keypoint>(), nq, w.pbest.as<float>(), make_float4(K4[0], K4[1], K4[2], K4[3]),
-                               frame_bounds(cols, rows, bounds), w.pbest.as<float>() + 12, nlevels, th, w.q.as<SbpQuery>(), d_angle);
-            ORBFE_HIP(hipGetLastError());
-            ORBFE_HIP(hipDeviceSynchronize()); // d_flags is reused for the blocks flags below
-        } else {
-            ORBFE_HIP(hipMemcpy(w.q.p, queries, (size_t)nq * sizeof(orbfe_window_query), hipMemcpyHostToDevice));
-            ORBFE_HIP(hipMemcpy(d_angle, q_angle, (size_t)nq * 4, hipMemcpyHostToDevice));
-        }
-        if (q_blocks) ORBFE_HIP(hipMemcpy(d_flags, q_blocks, (size_t)nq, hipMemcpyHostToDevice));
-        ORBFE_HIP(hipMemset(w.overflow.p, 0, 4));
-        ORBFE_HIP(hipMemset(w.nm.p, 0, 4));
-        int32_t* o = w.obest.as<int32_t>();
-        SbpBest bo{d_angle, q_blocks ? d_flags : nullptr, factor, check_ori, w.m12.as<int32_t>(), o + nq};
-        { int rc_lds_ = ensure_dyn_lds(reinterpret_cast<const void*>(&k_search_by_projection), (size_t)(lds)); if (rc_lds_) return rc_lds_; }
-        hipLaunchKernelGGL(k_search_by_projection, dim3(1), dim3(SBP_THREADS), lds, 0, w.kps.as<orbfe_keypoint>(), w.desc.as<uint8_t>(), n,
-                           ncap, frame_bounds(cols, rows, bounds), w.q.as<SbpQuery>(), w.t.as<uint8_t>(), nq,
-                           taken ? w.prev.as<uint8_t>() : nullptr, 2, th_high, 0.0f, w.csr_idx.as<uint16_t>(), w.csr_dist.as<uint8_t>(),
-                           w.csr_cnt.as<int32_t>(), stride, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr,
-                           (int32_t*)nullptr, o, w.nm.as<int32_t>(), w.overflow.as<int32_t>(), bo);
-        ORBFE_HIP(hipGetLastError());
-        ORBFE_HIP(hipDeviceSynchronize());
-        int32_t ovf = 0;
-        ORBFE_HIP(hipMemcpy(&ovf, w.overflow.p, 4, hipMemcpyDeviceToHost));
-        if (!ovf) break;
-        if (attempt) return fail(ORBFE_ERR_CAPACITY, "candidate row overflow (%d)", ovf);
-        w.sbp_stride = (ovf + 63) / 64 * 64;
-    }
-    ORBFE_HIP(hipMemcpy(match_cur, w.m12.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    ORBFE_HIP(hipMemcpy(nmatches, w.nm.p, 4, hipMemcpyDeviceToHost));
-    return ORBFE_OK;
+    SbpHostCall c{kps, desc, n, frame_bounds(cols, rows, bounds), taken, nq, qdesc, q_observed};
+    c.window = queries;
+    c.mode = mode; c.th_high = th_high; c.nnratio = nnratio;
+    c.best_idx = best_idx; c.best_dist = best_dist; c.best_level = best_level; c.second_dist = second_dist; c.second_level = second_level;
+    if (mode == 1) { c.match = match; c.nmatches = nmatches; c.taken_out = taken; }
+    return sbp_host_run(c);
 }
 
 int orbfe_search_by_projection_best(const orbfe_keypoint* kps, const uint8_t* desc, int n, int cols, int rows, const float* bounds,
@@ -1813,10 +1807,14 @@ int orbfe_search_by_projection_best(const orbfe_keypoint* kps, const uint8_t* de
         return fail(ORBFE_ERR_INVALID, "orbfe_search_by_projection_best: invalid argument");
     int rc = use_device(device);
     if (rc) return rc;
-    std::vector<float> zero;
-    if (!q_angle) { zero.assign(std::max(nq, 1), 0.0f); q_angle = zero.data(); }
-    return sbp_best_run(kps, desc, n, cols, rows, bounds, queries, q_angle, qdesc, q_blocks, nq, taken, th_high, check_orientation, factor,
-                        match_cur, nmatches, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0.0f);
+    *nmatches = 0;
+    for (int i = 0; i < n; i++) match_cur[i] = -1;
+    if (nq == 0 || n == 0) return ORBFE_OK;
+    SbpHostCall c{kps, desc, n, frame_bounds(cols, rows, bounds), taken, nq, qdesc, q_blocks, q_angle};
+    c.window = queries;
+    c.mode = 2; c.th_high = th_high; c.factor = factor; c.check_ori = check_orientation;
+    c.match_cur = match_cur; c.nmatches = nmatches;
+    return sbp_host_run(c);
 }
 
 int orbfe_search_by_projection_last_frame(const orbfe_keypoint* kps_cur, const uint8_t* desc_cur, int n_cur, const uint8_t* taken_cur,
@@ -1830,9 +1828,14 @@ int orbfe_search_by_projection_last_frame(const orbfe_keypoint* kps_cur, const u
         return fail(ORBFE_ERR_INVALID, "orbfe_search_by_projection_last_frame: invalid argument");
     int rc = use_device(device);
     if (rc) return rc;
-    return sbp_best_run(kps_cur, desc_cur, n_cur, cols, rows, bounds, nullptr, nullptr, mp_desc, mp_observed, n_last, taken_cur, th_high,
-                        check_orientation, 1.0f / 30 /* :1341 */, match_cur, nmatches, x3Dw, valid_last, kps_last, Tcw, K4, scale_factors,
-                        nlevels, th);
+    *nmatches = 0;
+    for (int i = 0; i < n_cur; i++) match_cur[i] = -1;
+    if (n_last == 0 || n_cur == 0) return ORBFE_OK;
+    SbpHostCall c{kps_cur, desc_cur, n_cur, frame_bounds(cols, rows, bounds), taken_cur, n_last, mp_desc, mp_observed};
+    c.x3Dw = x3Dw; c.valid = valid_last; c.kps_last = kps_last; c.Tcw = Tcw; c.K4 = K4; c.scale = scale_factors; c.nlevels = nlevels; c.th = th;
+    c.mode = 2; c.th_high = th_high; c.factor = 1.0f / 30 /* :1341 */; c.check_ori = check_orientation;
+    c.match_cur = match_cur; c.nmatches = nmatches;
+    return sbp_host_run(c);
 }
 
 static int project_params(ProjectParams& P, const float* Tcw, const float* Ow, const float* K4, int cols, int rows, const float* bounds,
@@ -1851,27 +1854,6 @@ static int project_params(ProjectParams& P, const float* Tcw, const float* Ow, c
     return ORBFE_OK;
 }
 
-// uploads the map points and leaves their queries in w.q
-static int project_run(MatchWorkspace& w, const float* p3Dw, const uint8_t* valid, const float* min_dist, const float* max_dist,
-                       const float* normal, int n, const ProjectParams& P)
-{
-    int rc;
-    const size_t N = (size_t)n;
-    if ((rc = w.q.ensure(N * sizeof(orbfe_window_query))) || (rc = w.scratch.ensure(N * (12 + 4 + 4 + 12) + 256)) || (rc = w.pidx.ensure(N + 256)))
-        return rc;
-    float* d_p = w.scratch.as<float>();
-    float *d_min = d_p + 3 * N, *d_max = d_min + N, *d_nrm = d_max + N;
-    ORBFE_HIP(hipMemcpy(d_p, p3Dw, N * 12, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(d_min, min_dist, N * 4, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(d_max, max_dist, N * 4, hipMemcpyHostToDevice));
-    if (normal) ORBFE_HIP(hipMemcpy(d_nrm, normal, N * 12, hipMemcpyHostToDevice));
-    if (valid) ORBFE_HIP(hipMemcpy(w.pidx.p, valid, N, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_project_map_points, dim3((n + 255) / 256), dim3(256), 0, 0, d_p, valid ? w.pidx.as<uint8_t>() : nullptr, d_min, d_max,
-                       normal ? d_nrm : nullptr, n, P, w.q.as<SbpQuery>());
-    ORBFE_HIP(hipGetLastError());
-    return ORBFE_OK;
-}
-
 int orbfe_project_map_points(const float* p3Dw, const uint8_t* valid, const float* min_dist, const float* max_dist, const float* normal, int n,
                              const float* Tcw, const float* Ow, const float* K4, int cols, int rows, const float* bounds, int keyframe_variant,
                              const float* scale_factors, int nlevels, float log_scale_factor, float th, int level_below, int level_above,
@@ -1885,57 +1867,10 @@ int orbfe_project_map_points(const float* p3Dw, const uint8_t* valid, const floa
     P.frame_variant = !keyframe_variant;
     if (rc || (rc = use_device(device)) || n == 0) return rc;
     MatchWorkspace& w = ws();
-    if ((rc = project_run(w, p3Dw, valid, min_dist, max_dist, normal, n, P))) return rc;
+    if ((rc = w.q.ensure((size_t)n * sizeof(orbfe_window_query))) ||
+        (rc = project_run(w, p3Dw, valid, min_dist, max_dist, normal, n, P, w.q.as<SbpQuery>())))
+        return rc;
     ORBFE_HIP(hipMemcpy(queries, w.q.p, (size_t)n * sizeof(orbfe_window_query), hipMemcpyDeviceToHost));
-    return ORBFE_OK;
-}
-
-// projection + grid search + best distance for nmp map points against one keyframe (Fuse, SearchBySim3)
-static int guided_best(const orbfe_keypoint* kps, const uint8_t* desc, int n, int cols, int rows, const float* bounds, const float* p3Dw,
-                       const uint8_t* valid, const float* min_dist, const float* max_dist, const float* normal, const uint8_t* mp_desc, int nmp,
-                       const ProjectParams& P, double chi2, const float* inv_level_sigma2, int nlevels, int32_t* best_idx, int32_t* best_dist)
-{
-    if (n > 65535) return fail(ORBFE_ERR_INVALID, "more than 65535 keypoints per frame are unsupported");
-    for (int i = 0; i < nmp; i++) { best_idx[i] = -1; best_dist[i] = 256; }
-    if (nmp == 0 || n == 0) return ORBFE_OK;
-    int ncap = 64;
-    while (ncap < n) ncap <<= 1;
-    const size_t lds = (size_t)ncap * (4 + 8 + 1 + 1) + (SBP_CELLS + 2) * 2 + 64;
-    if (lds > 150 * 1024) return fail(ORBFE_ERR_CAPACITY, "%d keypoints do not fit the grid kernel's LDS", n);
-    MatchWorkspace& w = ws();
-    const size_t qo = (size_t)nmp * 4;
-    SbpBest bo{};
-    bo.chi2 = chi2 > 0.0 ? chi2 : 0.0;
-    if (chi2 > 0.0)
-        for (int l = 0; l < 16; l++) bo.inv_sigma2[l] = inv_level_sigma2[std::min(l, nlevels - 1)];
-    int rc;
-    for (int attempt = 0;; attempt++) {
-        const int stride = std::max(w.sbp_stride, 128);
-        if ((rc = w.kps.ensure((size_t)n * sizeof(orbfe_keypoint))) || (rc = w.desc.ensure((size_t)n * 32)) || (rc = w.t.ensure((size_t)nmp * 32)) ||
-            (rc = w.csr_idx.ensure((size_t)nmp * stride * 2)) || (rc = w.csr_dist.ensure((size_t)nmp * stride)) || (rc = w.csr_cnt.ensure(qo)) ||
-            (rc = w.obest.ensure(qo * 6)) || (rc = w.nm.ensure(16)) || (rc = w.overflow.ensure(16)))
-            return rc;
-        ORBFE_HIP(hipMemcpy(w.kps.p, kps, (size_t)n * sizeof(orbfe_keypoint), hipMemcpyHostToDevice));
-        ORBFE_HIP(hipMemcpy(w.desc.p, desc, (size_t)n * 32, hipMemcpyHostToDevice));
-        ORBFE_HIP(hipMemcpy(w.t.p, mp_desc, (size_t)nmp * 32, hipMemcpyHostToDevice));
-        if ((rc = project_run(w, p3Dw, valid, min_dist, max_dist, normal, nmp, P))) return rc;
-        ORBFE_HIP(hipMemset(w.overflow.p, 0, 4));
-        int32_t* o = w.obest.as<int32_t>();
-        { int rc_lds_ = ensure_dyn_lds(reinterpret_cast<const void*>(&k_search_by_projection), (size_t)(lds)); if (rc_lds_) return rc_lds_; }
-        hipLaunchKernelGGL(k_search_by_projection, dim3(1), dim3(SBP_THREADS), lds, 0, w.kps.as<orbfe_keypoint>(), w.desc.as<uint8_t>(), n,
-                           ncap, frame_bounds(cols, rows, bounds), w.q.as<SbpQuery>(), w.t.as<uint8_t>(), nmp, (uint8_t*)nullptr, 0, 256, 0.0f,
-                           w.csr_idx.as<uint16_t>(), w.csr_dist.as<uint8_t>(), w.csr_cnt.as<int32_t>(), stride, o, o + nmp, o + 2 * nmp,
-                           o + 3 * nmp, o + 4 * nmp, o + 5 * nmp, w.nm.as<int32_t>(), w.overflow.as<int32_t>(), bo);
-        ORBFE_HIP(hipGetLastError());
-        ORBFE_HIP(hipDeviceSynchronize());
-        int32_t ovf = 0;
-        ORBFE_HIP(hipMemcpy(&ovf, w.overflow.p, 4, hipMemcpyDeviceToHost));
-        if (!ovf) break;
-        if (attempt) return fail(ORBFE_ERR_CAPACITY, "candidate row overflow (%d)", ovf);
-        w.sbp_stride = (ovf + 63) / 64 * 64;
-    }
-    ORBFE_HIP(hipMemcpy(best_idx, w.obest.p, qo, hipMemcpyDeviceToHost));
-    ORBFE_HIP(hipMemcpy(best_dist, w.obest.as<int32_t>() + nmp, qo, hipMemcpyDeviceToHost));
     return ORBFE_OK;
 }
 
@@ -1950,8 +1885,12 @@ int orbfe_fuse_search(const orbfe_keypoint* kps, const uint8_t* desc, int n, int
     ProjectParams P;
     int rc = project_params(P, Tcw, Ow, K4, cols, rows, bounds, 1, scale_factors, nlevels, log_scale_factor, th, 1, 0, "orbfe_fuse_search");
     if (rc || (rc = use_device(device))) return rc;
-    return guided_best(kps, desc, n, cols, rows, bounds, p3Dw, valid, min_dist, max_dist, normal, mp_desc, nmp, P, chi2, inv_level_sigma2, nlevels,
-                       best_idx, best_dist);
+    for (int i = 0; i < nmp; i++) { best_idx[i] = -1; best_dist[i] = 256; }
+    if (nmp == 0 || n == 0) return ORBFE_OK;
+    SbpHostCall c{kps, desc, n, frame_bounds(cols, rows, bounds), nullptr, nmp, mp_desc};
+    c.x3Dw = p3Dw; c.valid = valid; c.P = &P; c.min_dist = min_dist; c.max_dist = max_dist; c.normal = normal;
+    c.chi2 = chi2; c.inv_sigma2 = inv_level_sigma2; c.nlevels = nlevels; c.best_idx = best_idx; c.best_dist = best_dist;
+    return sbp_host_run(c);
 }
 
 int orbfe_search_by_sim3(const orbfe_keypoint* kps1, const uint8_t* desc1, int n1, const orbfe_keypoint* kps2, const uint8_t* desc2, int n2,
@@ -1977,11 +1916,12 @@ int orbfe_search_by_sim3(const orbfe_keypoint* kps1, const uint8_t* desc1, int n
     for (int i = 0; i < n1; i++) match12[i] = -1;
     if (n1 == 0 || n2 == 0) return ORBFE_OK;
     std::vector<int32_t> m1(n1), d1(n1), m2(n2), d2(n2);
-    if ((rc = guided_best(kps2, desc2, n2, cols, rows, bounds, p3Dw1, valid1, min_dist1, max_dist1, nullptr, mp_desc1, n1, P12, 0.0, nullptr,
-                          nlevels, m1.data(), d1.data())) ||
-        (rc = guided_best(kps1, desc1, n1, cols, rows, bounds, p3Dw2, valid2, min_dist2, max_dist2, nullptr, mp_desc2, n2, P21, 0.0, nullptr,
-                          nlevels, m2.data(), d2.data())))
-        return rc;
+    // the best keypoint (mode 0) of every map point of one keyframe in the other
+    const float4 bnd = frame_bounds(cols, rows, bounds);
+    SbpHostCall c12{kps2, desc2, n2, bnd, nullptr, n1, mp_desc1}, c21{kps1, desc1, n1, bnd, nullptr, n2, mp_desc2};
+    c12.x3Dw = p3Dw1; c12.valid = valid1; c12.P = &P12; c12.min_dist = min_dist1; c12.max_dist = max_dist1; c12.best_idx = m1.data(); c12.best_dist = d1.data();
+    c21.x3Dw = p3Dw2; c21.valid = valid2; c21.P = &P21; c21.min_dist = min_dist2; c21.max_dist = max_dist2; c21.best_idx = m2.data(); c21.best_dist = d2.data();
+    if ((rc = sbp_host_run(c12)) || (rc = sbp_host_run(c21))) return rc;
     int found = 0;
     for (int i1 = 0; i1 < n1; i1++) { // check agreement (:1302-1318)
         const int idx2 = d1[i1] <= th_high ? m1[i1] : -1;
@@ -2026,11 +1966,14 @@ int orbfe_search_by_projection_keyframe(const orbfe_keypoint* kps_cur, const uin
                             "orbfe_search_by_projection_keyframe");
     P.frame_variant = 1;
     if (rc || (rc = use_device(device))) return rc;
-    std::vector<float> zero;
-    if (!kf_angle) { zero.assign(std::max(n_kf, 1), 0.0f); kf_angle = zero.data(); }
-    return sbp_best_run(kps_cur, desc_cur, n_cur, cols, rows, bounds, nullptr, kf_angle, mp_desc, nullptr, n_kf, taken_cur, orb_dist,
-                        check_orientation, 1.0f / 30 /* :1488 */, match_cur, nmatches, p3Dw, valid, nullptr, nullptr, nullptr, nullptr, 0, 0.0f,
-                        &P, min_dist, max_dist);
+    *nmatches = 0;
+    for (int i = 0; i < n_cur; i++) match_cur[i] = -1;
+    if (n_kf == 0 || n_cur == 0) return ORBFE_OK;
+    SbpHostCall c{kps_cur, desc_cur, n_cur, frame_bounds(cols, rows, bounds), taken_cur, n_kf, mp_desc, nullptr, kf_angle};
+    c.x3Dw = p3Dw; c.valid = valid; c.P = &P; c.min_dist = min_dist; c.max_dist = max_dist;
+    c.mode = 2; c.th_high = orb_dist; c.factor = 1.0f / 30 /* :1488 */; c.check_ori = check_orientation;
+    c.match_cur = match_cur; c.nmatches = nmatches;
+    return sbp_host_run(c);
 }
 
 int orbfe_search_by_projection_batch_device(const orbfe_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_n, int capacity, int nframes,
@@ -2045,33 +1988,18 @@ int orbfe_search_by_projection_batch_device(const orbfe_keypoint* d_kps, const u
         nframes <= 0 || cols <= 0 || rows <= 0 || mode < 0 || mode > 2 || (mode == 2 && (!d_match_cur || (check_orientation && !d_q_angle))) ||
         (d_best_idx && (!d_best_dist || !d_best_level || !d_second_dist || !d_second_level)))
         return fail(ORBFE_ERR_INVALID, "orbfe_search_by_projection_batch_device: invalid argument");
-    if (capacity > 65535) return fail(ORBFE_ERR_INVALID, "more than 65535 keypoints per frame are unsupported");
-    int ncap = 64;
-    while (ncap < capacity) ncap <<= 1;
-    const size_t lds = (size_t)ncap * (4 + 8 + 1 + 1) + (SBP_CELLS + 2) * 2 + 64;
-    if (lds > 150 * 1024) return fail(ORBFE_ERR_CAPACITY, "%d keypoints do not fit the grid kernel's LDS", capacity);
     hipStream_t s = (hipStream_t)stream;
     MatchWorkspace& w = ws(s);
-    const int stride = std::max(w.sbp_stride, 128);
-    w.sbp_stride = stride;
-    const size_t NQ = (size_t)nframes * qcapacity;
     int rc;
-    if ((rc = w.csr_idx.ensure(NQ * stride * 2)) || (rc = w.csr_dist.ensure(NQ * stride)) || (rc = w.csr_cnt.ensure(NQ * 4)) ||
-        (rc = w.scratch.ensure(NQ * 4 + 256)) || (rc = ensure_sticky_flag(w.sbp_batch_overflow)))
-        return rc;
+    if ((rc = w.scratch.ensure((size_t)nframes * qcapacity * 4 + 256)) || (rc = ensure_sticky_flag(w.sbp_batch_overflow))) return rc;
     SbpBatch B{};
     B.kps = d_kps; B.desc = d_desc; B.n = d_n; B.capacity = capacity;
     B.queries = reinterpret_cast<const SbpQuery*>(d_queries); B.qdesc = d_qdesc; B.nq = d_nq; B.qcapacity = qcapacity;
     B.taken = d_taken; B.q_observed = d_q_observed; B.q_angle = d_q_angle;
-    B.row_rank = w.csr_idx.as<uint16_t>(); B.row_dist = w.csr_dist.as<uint8_t>(); B.row_cnt = w.csr_cnt.as<int32_t>(); B.row_stride = stride;
     B.best_idx = d_best_idx; B.best_dist = d_best_dist; B.best_level = d_best_level; B.second_dist = d_second_dist; B.second_level = d_second_level;
     B.match = d_match; B.nmatches = d_nmatches; B.overflow = w.sbp_batch_overflow.as<int32_t>();
     B.match_cur = d_match_cur; B.qbin = w.scratch.as<int32_t>();
-    if ((rc = ensure_dyn_lds(reinterpret_cast<const void*>(&k_search_by_projection_batch), lds))) return rc;
-    hipLaunchKernelGGL(k_search_by_projection_batch, dim3(nframes), dim3(SBP_THREADS), lds, s, B, ncap, frame_bounds(cols, rows, bounds), mode,
-                       th_high, nnratio, factor, check_orientation);
-    ORBFE_HIP(hipGetLastError());
-    return ORBFE_OK;
+    return sbp_launch(w, B, nframes, frame_bounds(cols, rows, bounds), mode, th_high, nnratio, factor, check_orientation, s);
 }
 
 int orbfe_fuse_search_batch_device(const orbfe_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_n, int capacity, int nkf, int cols, int rows,
@@ -2083,20 +2011,13 @@ int orbfe_fuse_search_batch_device(const orbfe_keypoint* d_kps, const uint8_t* d
     if (!d_kps || !d_desc || !d_n || capacity <= 0 || nkf <= 0 || nmp <= 0 || !d_p3Dw || !d_min_dist || !d_max_dist || !d_normal || !d_mp_desc ||
         !Tcw || !Ow || !d_best_idx || !d_best_dist || (chi2 > 0.0 && !inv_level_sigma2))
         return fail(ORBFE_ERR_INVALID, "orbfe_fuse_search_batch_device: invalid argument");
-    if (capacity > 65535) return fail(ORBFE_ERR_INVALID, "more than 65535 keypoints per frame are unsupported");
-    int ncap = 64;
-    while (ncap < capacity) ncap <<= 1;
-    const size_t lds = (size_t)ncap * (4 + 8 + 1 + 1) + (SBP_CELLS + 2) * 2 + 64;
-    if (lds > 150 * 1024) return fail(ORBFE_ERR_CAPACITY, "%d keypoints do not fit the grid kernel's LDS", capacity);
     hipStream_t s = (hipStream_t)stream;
     MatchWorkspace& w = ws(s);
-    const int stride = std::max(w.sbp_stride, 128);
-    w.sbp_stride = stride;
     const size_t NQ = (size_t)nkf * nmp;
     int rc;
     // obest: [best_level | second_dist | second_level | match] x NQ, then nq[nkf], nmatches[nkf]
-    if ((rc = w.q.ensure(NQ * sizeof(orbfe_window_query))) || (rc = w.csr_idx.ensure(NQ * stride * 2)) || (rc = w.csr_dist.ensure(NQ * stride)) ||
-        (rc = w.csr_cnt.ensure(NQ * 4)) || (rc = w.obest.ensure((NQ * 4 + 2 * (size_t)nkf) * 4 + 256)) || (rc = ensure_sticky_flag(w.sbp_batch_overflow)))
+    if ((rc = w.q.ensure(NQ * sizeof(orbfe_window_query))) || (rc = w.obest.ensure((NQ * 4 + 2 * (size_t)nkf) * 4 + 256)) ||
+        (rc = ensure_sticky_flag(w.sbp_batch_overflow)))
         return rc;
     for (int k = 0; k < nkf; k++) { // the projection and the gates of :848-915, one small launch per keyframe pose
         ProjectParams P;
@@ -2112,17 +2033,10 @@ int orbfe_fuse_search_batch_device(const orbfe_keypoint* d_kps, const uint8_t* d
     SbpBatch B{};
     B.kps = d_kps; B.desc = d_desc; B.n = d_n; B.capacity = capacity;
     B.queries = w.q.as<SbpQuery>(); B.qdesc = d_mp_desc; B.qdesc_shared = 1; B.nq = d_nq; B.qcapacity = nmp;
-    B.row_rank = w.csr_idx.as<uint16_t>(); B.row_dist = w.csr_dist.as<uint8_t>(); B.row_cnt = w.csr_cnt.as<int32_t>(); B.row_stride = stride;
     B.best_idx = d_best_idx; B.best_dist = d_best_dist; B.best_level = o; B.second_dist = o + NQ; B.second_level = o + 2 * NQ;
     B.match = o + 3 * NQ; B.nmatches = d_nq + nkf; B.overflow = w.sbp_batch_overflow.as<int32_t>();
-    B.chi2 = chi2 > 0.0 ? chi2 : 0.0;
-    if (chi2 > 0.0)
-        for (int l = 0; l < 16; l++) B.inv_sigma2[l] = inv_level_sigma2[std::min(l, nlevels - 1)];
-    if ((rc = ensure_dyn_lds(reinterpret_cast<const void*>(&k_search_by_projection_batch), lds))) return rc;
-    hipLaunchKernelGGL(k_search_by_projection_batch, dim3(nkf), dim3(SBP_THREADS), lds, s, B, ncap, frame_bounds(cols, rows, bounds), 0, 256, 0.0f,
-                       0.0f, 0);
-    ORBFE_HIP(hipGetLastError());
-    return ORBFE_OK;
+    if (chi2 > 0.0) { B.chi2 = chi2; for (int l = 0; l < 16; l++) B.inv_sigma2[l] = inv_level_sigma2[std::min(l, nlevels - 1)]; }
+    return sbp_launch(w, B, nkf, frame_bounds(cols, rows, bounds), 0, 256, 0.0f, 0.0f, 0, s);
 }
 
 int orbfe_search_by_projection_batch_status(void* stream, int32_t* overflow)
@@ -2135,7 +2049,7 @@ int orbfe_search_by_projection_batch_status(void* stream, int32_t* overflow)
     ORBFE_HIP(hipStreamSynchronize(s));
     ORBFE_HIP(hipMemcpy(overflow, w.sbp_batch_overflow.p, 4, hipMemcpyDeviceToHost));
     if (*overflow) ORBFE_HIP(hipMemset(w.sbp_batch_overflow.p, 0, 4)); // covers every batch since it was last read
-    if (*overflow > w.sbp_stride) w.sbp_stride = (*overflow + 63) / 64 * 64; // the next batch on this stream has the room
+    sbp_grow_stride(w, *overflow); // the next batch on this stream has the room
     return ORBFE_OK;
 }
 
