@@ -30,6 +30,33 @@ struct ModeRun {
     std::function<int(hipStream_t)> before_finalize; // trackingMinDetections: the host looks at the decode results and may adopt rejected candidates
 };
 
+// The contour paths: tiled (aruco_tiles.hip), the one-workgroup relay kernels, k_contours_t where neither can run or forced ("walker"),
+// k_contours_t in big-frame mode (bit image in HBM, AR_MAX_KEPT_BIG kept borders).  A batch with a frame over a capacity of its path is
+// done again on the next (escalate(): tiled -> relay, which coarsen their grid -> (kept borders / pool) big); run_device takes the first.
+enum class Contours : int8_t { tiled, relay, walker, big, none };
+enum class Thr : int8_t { fixed, mfma, pyr, magic, box };   // k_fixed_threshold, _mfma, _pyr<WIN>, k_adaptive_threshold_t<WIN>, <R>
+enum class Relay : int8_t { relay, relay8, wide, relay8g }; // k_contours_relay, _relay8, _relay_wide, _relay8g
+
+static Contours escalate(Contours ran, int flags_or, bool relay_ok)
+{
+    const bool was_tiled = ran == Contours::tiled;
+    // from the tiled path any exceeded capacity (segment lists, kept borders, pool) goes to the one-workgroup relay kernels first:
+    // they coarsen their grid and follow what is left whole, and get through frames of dense noise that neither the tiles nor the
+    // single-walker kernel's per-lane arenas hold (480 x 640 with +-40 grey levels of noise: 203 kept borders, no flag)
+    if (was_tiled && (flags_or & (2 | 4 | RL_FALLBACK_FLAGS)) && relay_ok) return Contours::relay;
+    return ran != Contours::big && (flags_or & (2 | 4 | (was_tiled ? RL_FALLBACK_FLAGS : 0))) ? Contours::big : Contours::none;
+}
+
+// the window of cv::cornerSubPix for half size w, (2 w + 1)^2 weights: exp(-y^2) exp(-x^2) in float, by the host's expf like the reference
+static void subpix_window(int w, float* mk)
+{
+    for (int i = 0; i < 2 * w + 1; i++)
+        for (int j = 0; j < 2 * w + 1; j++) {
+            const float y = (float)(i - w) / w, x = (float)(j - w) / w;
+            mk[i * (2 * w + 1) + j] = (float)(std::exp(-y * y) * std::exp(-x * x));
+        }
+}
+
 struct orbfe_aruco {
     int device = 0;
     std::string dict_name;
@@ -81,8 +108,6 @@ struct orbfe_aruco {
     // ORBFE_ARUCO_TILED = 0 / 1 (debug key "tiled_contours") forces it off / on for every batch (tests, A/B); ORBFE_ARUCO_TILE_W = tile
     // width in pixels, ORBFE_ARUCO_TPW = tiles per wave of k_ct_walk: measurement switches.
     int tiled = -1;
-    bool tiled_off = false;    // set while a batch is redone by the relay kernels
-    bool tiled_ran = false;    // the last batch took the tiled path
     int n_escalations = 0;     // batches done again on the next contour path (orbfe_aruco_debug_contour_retries: the tests assert 0 for ordinary frames)
     // the walks of the tiled path by BANDS of cell rows, a workgroup of eight waves each (k_ct_band), instead of a wave per tile
     // (k_ct_walk): -1 = by frame / batch size, 0 / 1 forced; ORBFE_ARUCO_BAND_ROWS = cell rows per band (0: what fits ~36 KB of LDS, at most 8)
@@ -195,7 +220,7 @@ struct orbfe_aruco {
     bool relay_global = false; // k_contours_relay8g: the bit image stays in HBM (it does not fit LDS)
     int relay_tbits = 0;       // hash-table size of k_contours_relay (0: the kernel cannot run at this image size)
     bool force_legacy = false; // debug: always use k_contours_t
-    bool big_mode = false;     // frames with more kept borders than the LDS-resident kernels hold: bit image in HBM, AR_MAX_KEPT_BIG
+    bool big_mode = false;     // orbfe_aruco_set_big_frames: every batch on Contours::big (a retry passes its path to run_device instead)
     DevBuf d_codes, d_levels, d_tabs, d_bits, d_pyr, d_candq, d_pool, d_kept, d_rects, d_counts, d_candidx, d_ncand,
         d_result, d_gpad;
     DevBuf d_in, d_out, d_nout;
@@ -224,19 +249,18 @@ struct orbfe_aruco {
     int last_attempts = 0, last_work_rows = 0, last_work_cols = 0;
     size_t rl_static = 0;
     DevBuf d_red, d_mhist, d_masks, d_bgr, d_bits2;
-    // A batch with a frame that exceeded a capacity of the contour path it ran on is done again on the next one: tiled -> (its
-    // segment lists full: noise) the one-workgroup relay kernels, which coarsen their grid -> (kept borders / pool) the single-walker
-    // kernel in big-frame mode.  The callers restore tiled_off / big_mode afterwards.
-    bool escalate(int flags_or)
+    // batch(floor, &ran) enqueues the pipeline on the contour paths from `floor` on and the copy of its nframes x 4 counts to `counts`;
+    // done again on the next path while a frame exceeded a capacity (escalate(); not while "legacy_contours" pins the single walker)
+    template <class Batch> int with_retries(Batch&& batch, const int32_t* counts, int nframes)
     {
-        if (big_mode || force_legacy) return false;
-        const bool was_tiled = tiled_ran;
-        // from the tiled path any exceeded capacity (segment lists, kept borders, pool) goes to the one-workgroup relay kernels first:
-        // they coarsen their grid and follow what is left whole, and get through frames of dense noise that neither the tiles nor the
-        // single-walker kernel's per-lane arenas hold (480 x 640 with +-40 grey levels of noise: 203 kept borders, no flag)
-        if (was_tiled && (flags_or & (2 | 4 | RL_FALLBACK_FLAGS)) && relay_tbits) { tiled_off = true; n_escalations++; return true; }
-        if (flags_or & (2 | 4 | (was_tiled ? RL_FALLBACK_FLAGS : 0))) { big_mode = true; n_escalations++; return true; }
-        return false;
+        for (Contours floor = Contours::tiled;;) {
+            Contours ran = Contours::none; int flags_or = 0, rc;
+            if ((rc = batch(floor, &ran))) return rc;
+            ORBFE_HIP(hipStreamSynchronize(own_stream));
+            for (int f = 0; f < nframes; f++) flags_or |= counts[f * 4 + 2];
+            if (force_legacy || (floor = escalate(ran, flags_or, relay_tbits != 0)) == Contours::none) return ORBFE_OK;
+            n_escalations++;
+        }
     }
     bool stateful() const { return thres_method == 1 || auto_size || tracking_min > 0; } // a frame's result depends on the frames before it
     KernelTimer timer;
@@ -481,31 +505,76 @@ struct orbfe_aruco {
         return ORBFE_OK;
     }
 
-    // window tables of cv::cornerSubPix for half sizes 1 .. 8: exp(-y^2) exp(-x^2) in float, by the host's expf like the reference
+    // window tables of cv::cornerSubPix for half sizes 1 .. 8
     int ensure_subpix_masks()
     {
         if (d_masks.p) return ORBFE_OK;
         std::vector<float> m((size_t)8 * 17 * 17, 0.f);
-        for (int w = 1; w <= 8; w++) {
-            const int ww = 2 * w + 1;
-            float* mk = m.data() + (size_t)(w - 1) * 17 * 17;
-            for (int i = 0; i < ww; i++) {
-                const float y = (float)(i - w) / w;
-                const float vy = std::exp(-y * y);
-                for (int j = 0; j < ww; j++) {
-                    const float x = (float)(j - w) / w;
-                    mk[i * ww + j] = (float)(vy * std::exp(-x * x));
-                }
-            }
-        }
-        int rc = d_masks.ensure(m.size() * 4);
-        if (rc) return rc;
+        for (int w = 1; w <= 8; w++) subpix_window(w, m.data() + (size_t)(w - 1) * 17 * 17);
+        if (int rc = d_masks.ensure(m.size() * 4)) return rc;
         ORBFE_HIP(hipMemcpy(d_masks.p, m.data(), m.size() * 4, hipMemcpyHostToDevice));
         return ORBFE_OK;
     }
 
-    int run_device(const uint8_t* d_imgs, int B, size_t frame_stride, int rows_, int cols_, size_t step,
-                   orbfe_marker* d_out_m, int capacity, int32_t* d_n, hipStream_t s, const ModeRun* mr = nullptr)
+    // What run_device launches for a batch: every choice of kernel, variant and size, made once before its first launch
+    struct BatchPlan {
+        Thr thr = Thr::box; uint32_t thr_kk = 0;   // the threshold kernel; k_threshold_pyr: K | K << 16
+        int nfuse = 0;                // pyramid levels k_threshold_pyr writes, the rest in line behind it (0: the pyramid on the aux stream)
+        bool specks = false;          // k_speck_clean between threshold and contours
+        Contours contours = Contours::tiled;   // the path that runs; its variants:
+        bool band = false; int band_rows = 0, tile_w = 0, tpw = 0;   // tiled: k_ct_band, band_rows cell rows a band (else k_ct_walk: tile_w-pixel tiles, tpw tiles a wave)
+        Relay relay = Relay::relay;   // relay: the kernel, and k_contours_small behind it or not
+        bool small_separate = false, walker_hbm = false;   // walker: k_contours_t with its bit image in HBM and AR_MAX_KEPT_BIG kept borders
+    };
+    int plan_batch(int B, const ModeRun* mr, Contours floor, BatchPlan& p)
+    {
+        const bool reduced = mr && mr->d_full;
+        // The threshold kernel of the batched configuration writes the pyramid levels its 64 x 64 tiles hold whole (k_threshold_pyr): the
+        // exact halvings, at most four, when the pyramid starts from the thresholded frame itself and n v + K stays within 16 bits
+        const long n2 = (long)win * win, K = n2 * thres_value - n2 / 2;
+        const bool adaptive = !(mr && mr->fixed_thr >= 0), win_t = win == 5 || win == 7 || win == 11 || win == 15;
+        const bool fused_ok = adaptive && thr_v2 && th_magic && win_t && K >= 0 && n2 * 255 + K <= 65535;
+        // A call of a few frames (the drop-in call: one) is a chain of launches that each wait for the one before: there the kernel that
+        // also writes the pyramid (one launch instead of five) is the shorter chain -- detect 0.333 -> 0.303 ms per 640 x 480 frame;
+        // a batch has the pyramid next to the contour kernels on a stream of its own and takes the matrix-core kernel
+        const bool try_mfma = adaptive && thr_mfma && th_magic && K > -(1 << 20) && K < (1 << 20) && !(fused_ok && !reduced && B < 8 && thr_mfma_auto);
+        if (int rc = try_mfma ? build_threshold_tables() : ORBFE_OK) return rc;
+        p.thr = !adaptive ? Thr::fixed : try_mfma && thr_mfma_ok ? Thr::mfma : fused_ok ? Thr::pyr : th_magic && win_t ? Thr::magic : Thr::box;
+        if (p.thr == Thr::pyr) p.thr_kk = (uint32_t)K | ((uint32_t)K << 16);
+        for (int l = 1; p.thr == Thr::pyr && !reduced && l < npyr && l <= 4; l++) {
+            if (!lvl_exact[l] || levels[l].pitch % 4 != 0 || levels[l].pitch < 4 * ((levels[l].w + 3) / 4)) break;
+            p.nfuse = l;
+        }
+        // the first contour path from `floor` on that may run (big_mode: orbfe_aruco_set_big_frames; the tiled rule: at `tiled`)
+        if (big_mode || floor >= Contours::big) p.contours = Contours::big;
+        else if (!force_legacy && floor <= Contours::tiled && (tiled > 0 || (tiled < 0 && (relay_global || !relay_tbits || relay_tbits > 12 || B <= 32))))
+            p.contours = Contours::tiled;
+        else p.contours = !force_legacy && floor <= Contours::relay && relay_tbits ? Contours::relay : Contours::walker;
+        // the bit image the contour kernels read: after the speck passes, unless switched off or the frame is too wide for their LDS tile
+        p.specks = (specks > 0 || (specks < 0 && p.contours == Contours::relay && !relay_global && B > 32)) && speck_lds_bytes(cols) <= 150 * 1024;
+        // Tile width and waves.  k_ct_walk's waves are persistent and overlap their tiles, so a wave wants several tiles (its
+        // lanes always find work) and a SIMD wants several waves (a step is a chain of dependent LDS reads): narrow tiles for a
+        // batch -- ORBFE_ARUCO_TILE_W / ORBFE_ARUCO_TPW (tiles per wave) are measurement switches --, and for a few frames as many
+        // waves as there are tiles.
+        const int target = tile_w_env > 0 ? tile_w_env : (B <= 32 ? 192 : 480), ncols0 = std::max(1, (cols + target - 1) / target);
+        p.tile_w = std::min(CTW_MAX_CW, std::max(32, ((cols + ncols0 - 1) / ncols0 + 31) / 32 * 32));
+        p.tpw = tpw_env > 0 ? tpw_env : (B <= 32 ? 1 : 2);
+        // bands for full batches (eight waves level each other's load through the band's ticket counters) and, one cell row each, for
+        // up to four frames (single-frame call 0.385 -> 0.355 ms: the waves of a band share its start candidates, where a wave of
+        // k_ct_walk has its tile's to itself); a wave per tile in between
+        p.band = banded > 0 || (banded < 0 && (B > 32 || B <= 4));
+        const int pw = (cols + 2 + 31) / 32, rb = band_rows_env > 0 ? band_rows_env : B <= 4 ? 1 : std::max(1, std::min(8, (int)((36 * 1024 / (pw * 4) - 3) / 32)));
+        p.band_rows = std::max(1, std::min(rb, (rows + 31) / 32));
+        const bool wide = relay_tbits <= 12 && B <= 32 && relay_wide;   // few frames: 16 waves per frame (see k_contours_relay_wide)
+        p.relay = relay_global ? Relay::relay8g : relay_tbits > 12 ? Relay::relay8 : wide ? Relay::wide : Relay::relay;
+        p.small_separate = relay_global || (small_separate_mode < 0 ? B <= 32 : small_separate_mode != 0);   // (always behind relay8g)
+        p.walker_hbm = p.contours == Contours::big || !lds_bits_words;
+        return ORBFE_OK;
+    }
+
+    // A batch: the pipeline on the first contour path from `floor` on that may run; *ran = the one it took (escalate())
+    int run_device(const uint8_t* d_imgs, int B, size_t frame_stride, int rows_, int cols_, size_t step, orbfe_marker* d_out_m, int capacity,
+                   int32_t* d_n, hipStream_t s, const ModeRun* mr = nullptr, Contours floor = Contours::tiled, Contours* ran = nullptr)
     {
         int rc;
         const bool reduced = mr && mr->d_full;
@@ -516,48 +585,45 @@ struct orbfe_aruco {
         const ImgView srcW{d_imgs, nullptr, frame_stride, (int)step}; // what is thresholded and traced
         // the frame the pyramid starts from and the patches are warped from (level 0)
         const ImgView src0 = reduced ? ImgView{mr->d_full, nullptr, mr->full_fstride, (int)mr->full_step} : srcW;
-        ImgView pyr{d_pyr.as<uint8_t>(), d_pyr.as<uint8_t>(), pyr_fbytes, 0};
         timer.begin();
         timer.mark(s, "start");
-        // The threshold kernel of the batched configuration writes the pyramid levels its 64 x 64 tiles hold whole (k_threshold_pyr): the
-        // exact halvings, at most four, when the pyramid starts from the thresholded frame itself and n v + K stays within 16 bits
-        int nfuse = 0;
-        uint32_t thr_kk = 0;
-        bool use_thr_mfma = false;
-        {
-            const long n2 = (long)win * win, K = n2 * thres_value - n2 / 2;
-            const bool adaptive = !(mr && mr->fixed_thr >= 0);
-            const bool fused_ok = adaptive && thr_v2 && th_magic && (win == 5 || win == 7 || win == 11 || win == 15) && K >= 0 && n2 * 255 + K <= 65535;
-            // A call of a few frames (the drop-in call: one) is a chain of launches that each wait for the one before: there the kernel that
-            // also writes the pyramid (one launch instead of five) is the shorter chain -- detect 0.333 -> 0.303 ms per 640 x 480 frame;
-            // a batch has the pyramid next to the contour kernels on a stream of its own and takes the matrix-core kernel
-            if (adaptive && thr_mfma && th_magic && K > -(1 << 20) && K < (1 << 20) && !(fused_ok && !reduced && B < 8 && thr_mfma_auto)) {
-                if ((rc = build_threshold_tables())) return rc;
-                use_thr_mfma = thr_mfma_ok;
-            }
-            if (!use_thr_mfma && fused_ok) {
-                thr_kk = (uint32_t)K | ((uint32_t)K << 16);
-                nfuse = -1;   // the kernel applies, with no level so far
-                if (!reduced)
-                    for (int p = 1; p < npyr && p <= 4; p++) {
-                        if (!lvl_exact[p] || levels[p].pitch % 4 != 0 || levels[p].pitch < 4 * ((levels[p].w + 3) / 4)) break;
-                        nfuse = p;
-                    }
-            }
-        }
-        const bool thr_pyr = nfuse != 0;
-        if (nfuse < 0) nfuse = 0;
+        BatchPlan p;
+        if ((rc = plan_batch(B, mr, floor, p))) return rc;
+        if (ran) *ran = p.contours;
         // the /2 pyramid is only needed by k_decode: it runs on a second stream next to threshold + contours (what the threshold kernel
         // leaves of it: behind that kernel, in line)
-        hipStream_t aux_stream = user_aux ? user_aux : this->aux_stream;
-        if (nfuse) aux_stream = s;
-        else {
-            ORBFE_HIP(hipEventRecord(ev_fork, s));
-            ORBFE_HIP(hipStreamWaitEvent(aux_stream, ev_fork, 0));
-        }
+        hipStream_t aux = p.nfuse ? s : user_aux ? user_aux : aux_stream;
+        if (!p.nfuse) { ORBFE_HIP(hipEventRecord(ev_fork, s)); ORBFE_HIP(hipStreamWaitEvent(aux, ev_fork, 0)); }
+        timer.mark(aux, "pyramid starts", true);
+        if (!p.nfuse) pyramid(1, src0, B, aux);
+        timer.mark(aux, "pyramid");
+        if (!p.nfuse) ORBFE_HIP(hipEventRecord(ev_join, aux));
+        int enlarge_k = win;   // detectEnclosedMarkers: the candidates grow by half the adaptive window, or half the erosion size
+        if ((rc = threshold(p, srcW, src0, mr ? mr->fixed_thr : -1, B, s, &enlarge_k))) return rc;
+        timer.mark(s, "threshold");
+        ORBFE_HIP(hipGetLastError());
+        if ((rc = speck_pass(p, B, s))) return rc;
+        const uint32_t* cbits = (p.specks ? d_bitsc : d_bits).as<uint32_t>();
         bool finish_in_prefilter = false;   // k_tail_finish's work inside k_prefilter (set where the tail kernels are launched)
-        timer.mark(aux_stream, "pyramid starts", true);
-        auto rest_of_pyramid = [&](int first) -> int {
+        for (int r_ = 0; p.contours <= Contours::relay && r_ < ORBFE_REPS_ARUCO(1); r_++)
+            if ((rc = p.contours == Contours::tiled ? contours_tiled(p, B, cbits, s) : contours_relay(p, B, cbits, s)) || (rc = relay_tail(B, s, &finish_in_prefilter))) return rc;
+        if (p.contours >= Contours::walker && (rc = contours_single_walker(p, B, cbits, s))) return rc;
+        timer.mark(s, "contours");
+        ORBFE_HIP(hipGetLastError());
+        if ((rc = prefilter_decode(p, B, s, src0, enlarge_k, finish_in_prefilter))) return rc;
+        timer.mark(s, "decode");
+        if ((rc = finalize(B, s, src0, mr, d_out_m, capacity, d_n))) return rc;
+        timer.mark(s, "finalize");
+        ORBFE_HIP(hipGetLastError());
+        decode_dirty = false;   // k_finalize leaves the work-list length at zero
+        return ORBFE_OK;
+    }
+
+    ImgView pyr_view() { return ImgView{d_pyr.as<uint8_t>(), d_pyr.as<uint8_t>(), pyr_fbytes, 0}; }
+    // the /2 pyramid from level `first` on
+    void pyramid(int first, const ImgView& src0, int B, hipStream_t st)
+    {
+        const ImgView pyr = pyr_view();
         if (first == 1 && half_pyr) {
             // the leading exact halvings in one launch (k_half_pyr): four from 16 x 16 source blocks, or three from 8 x 8
             for (int nf = 4; nf >= 3 && first == 1; nf--) {
@@ -574,258 +640,227 @@ struct orbfe_aruco {
                 P.base = pyr.base_w; P.fstride = pyr_fbytes;
                 for (int p = 1; p <= nf; p++) { P.off[p - 1] = (uint32_t)levels[p].off; P.pitch[p - 1] = levels[p].pitch; }
                 const int bw = levels[0].w / bs, nblocks = bw * (levels[0].h / bs);
-                if (nf == 4) hipLaunchKernelGGL(k_half_pyr<4>, dim3((nblocks + 255) / 256, B), dim3(256), 0, aux_stream, src0, P, bw, nblocks);
-                else hipLaunchKernelGGL(k_half_pyr<3>, dim3((nblocks + 255) / 256, B), dim3(256), 0, aux_stream, src0, P, bw, nblocks);
+                if (nf == 4) hipLaunchKernelGGL(k_half_pyr<4>, dim3((nblocks + 255) / 256, B), dim3(256), 0, st, src0, P, bw, nblocks);
+                else hipLaunchKernelGGL(k_half_pyr<3>, dim3((nblocks + 255) / 256, B), dim3(256), 0, st, src0, P, bw, nblocks);
                 first = nf + 1;
             }
         }
         for (int p = first; p < npyr; p++) {
-            const ArLevel& L = levels[p];
-            const ArLevel& Lp = levels[p - 1];
+            const ArLevel &L = levels[p], &Lp = levels[p - 1];
             ImgView sv = (p == 1) ? src0 : ImgView{pyr.base + Lp.off, nullptr, pyr_fbytes, Lp.pitch};
             ImgView dv{pyr.base + L.off, pyr.base_w + L.off, pyr_fbytes, L.pitch};
             if (lvl_exact[p] && sv.pitch % 8 == 0 && sv.fstride % 8 == 0 && ((uintptr_t)sv.base & 7) == 0 && dv.pitch % 4 == 0 && dv.pitch >= 4 * ((L.w + 3) / 4)) {
                 const int dw4 = (L.w + 3) / 4, nthreads = dw4 * ((L.h + 1) / 2);   // reads up to 2 * L.w + 6 < the source pitch (64-byte rows)
-                hipLaunchKernelGGL(k_half_area4, dim3((nthreads + 255) / 256, B), dim3(256), 0, aux_stream, sv, dv, dw4, L.h);
+                hipLaunchKernelGGL(k_half_area4, dim3((nthreads + 255) / 256, B), dim3(256), 0, st, sv, dv, dw4, L.h);
             } else if (lvl_exact[p]) {
-                hipLaunchKernelGGL(k_half_area, dim3((L.w + 63) / 64, (L.h + 3) / 4, B), dim3(256), 0, aux_stream, sv, dv, L.w, L.h);
+                hipLaunchKernelGGL(k_half_area, dim3((L.w + 63) / 64, (L.h + 3) / 4, B), dim3(256), 0, st, sv, dv, L.w, L.h);
             } else {
                 const int dw4 = (L.w + 3) / 4;
                 const double scale_x = 1. / ((double)L.w / Lp.w), scale_y = 1. / ((double)L.h / Lp.h);
-                hipLaunchKernelGGL(k_resize_level, dim3((dw4 + 63) / 64, (L.h + 7) / 8, B), dim3(256), 0, aux_stream, sv, dv,
+                hipLaunchKernelGGL(k_resize_level, dim3((dw4 + 63) / 64, (L.h + 7) / 8, B), dim3(256), 0, st, sv, dv,
                                    Lp.w, Lp.h, dw4, L.h, scale_x, scale_y, L.w);
             }
         }
-        return ORBFE_OK;
-        };
-        if (!nfuse && (rc = rest_of_pyramid(1))) return rc;
-        timer.mark(aux_stream, "pyramid");
-        if (!nfuse) ORBFE_HIP(hipEventRecord(ev_join, aux_stream));
-        int enlarge_k = win;   // detectEnclosedMarkers: the candidates grow by half the adaptive window, or half the erosion size
+    }
+    // the instance of k_threshold_pyr / k_adaptive_threshold_t for the window (they are built for windows 5, 7, 11 and 15)
+    template <class K> K by_window(K k5, K k7, K k11, K k15) const { return win == 5 ? k5 : win == 7 ? k7 : win == 11 ? k11 : k15; }
+    // the bit image d_bits (k_threshold_pyr: and the pyramid, its first levels in the kernel and the rest behind it)
+    int threshold(const BatchPlan& p, const ImgView& srcW, const ImgView& src0, int fixed_thr, int B, hipStream_t s, int* enlarge_k)
+    {
         for (int r_ = 0; r_ < ORBFE_REPS_ARUCO(8); r_++) {
-            const dim3 tg((cols + 63) / 64, (rows + 63) / 64, B);
             const int ntx = (cols + 63) / 64, ntl = ntx * ((rows + 63) / 64);
-            const dim3 tg1(xcd_grid(ntl * B));
+            const dim3 tg(ntx, (rows + 63) / 64, B), tg1(xcd_grid(ntl * B));
             uint32_t* bp = d_bits.as<uint32_t>();
-            if (mr && mr->fixed_thr >= 0) {   // THRES_AUTO_FIXED: cv::threshold(THRESH_BINARY_INV) at the carried-over threshold
+            if (p.thr == Thr::fixed) {   // THRES_AUTO_FIXED: cv::threshold(THRESH_BINARY_INV) at the carried-over threshold
                 if (enclosed) {               // detectEnclosedMarkers: the inner edge band of the thresholded regions (erode + xor)
-                    if ((rc = d_bits2.ensure(bits_fu32 * 4 * B))) return rc;
-                    int k = int(std::max(3.0, 3. / 1920. * float(cols)));
-                    if (k % 2 == 0) k++;
-                    enlarge_k = k;
+                    if (int rc = d_bits2.ensure(bits_fu32 * 4 * B)) return rc;
+                    const int k = *enlarge_k = int(std::max(3.0, 3. / 1920. * float(cols))) | 1;   // (made odd)
                     if (k / 2 > 15) return fail(ORBFE_ERR_INVALID, "detectEnclosedMarkers: frame too wide (erosion size %d)", k);
-                    hipLaunchKernelGGL(k_fixed_threshold, dim3((wpr * rows + 255) / 256, B), dim3(256), 0, s, srcW, cols, rows, mr->fixed_thr, d_bits2.as<uint32_t>(), bits_fu32, wpr);
-                    hipLaunchKernelGGL(k_erode_cross_xor, dim3((wpr * rows + 255) / 256, B), dim3(256), 0, s, d_bits2.as<uint32_t>(), bp, bits_fu32, wpr, cols, rows, k / 2);
-                } else
-                    hipLaunchKernelGGL(k_fixed_threshold, dim3((wpr * rows + 255) / 256, B), dim3(256), 0, s, srcW, cols, rows, mr->fixed_thr, bp, bits_fu32, wpr);
-            } else if (use_thr_mfma) {
+                }
+                hipLaunchKernelGGL(k_fixed_threshold, dim3((wpr * rows + 255) / 256, B), dim3(256), 0, s, srcW, cols, rows, fixed_thr, enclosed ? d_bits2.as<uint32_t>() : bp, bits_fu32, wpr);
+                if (enclosed) hipLaunchKernelGGL(k_erode_cross_xor, dim3((wpr * rows + 255) / 256, B), dim3(256), 0, s, d_bits2.as<uint32_t>(), bp, bits_fu32, wpr, cols, rows, *enlarge_k / 2);
+            } else if (p.thr == Thr::mfma) {
                 const int n2 = win * win, nxs = (n_tstrips + 3) / 4;
                 hipLaunchKernelGGL(k_threshold_mfma, dim3(xcd_grid(nxs * B)), dim3(256), 0, s, srcW, cols, rows, ttab_rb, -(n2 * thres_value - n2 / 2),
                                    d_tstrips.as<ThrStrip>(), d_ttabs.as<uint4>(), d_ttab2.as<uint4>(), bp, bits_fu32, wpr, n_tstrips, nxs, nxs * B, n2 > 127 ? 1 : 0);
-            } else if (thr_pyr) {
+            } else if (p.thr == Thr::pyr) {
                 ThrPyr P{};
-                P.n = nfuse;
-                for (int p = 1; p <= nfuse; p++) { P.w[p - 1] = levels[p].w; P.h[p - 1] = levels[p].h; P.pitch[p - 1] = levels[p].pitch; P.off[p - 1] = levels[p].off; }
-                if (win == 5) hipLaunchKernelGGL(k_threshold_pyr<5>, tg1, dim3(256), 0, s, srcW, cols, rows, thr_kk, bp, bits_fu32, wpr, ntx, ntl, ntl * B, pyr, P);
-                else if (win == 7) hipLaunchKernelGGL(k_threshold_pyr<7>, tg1, dim3(256), 0, s, srcW, cols, rows, thr_kk, bp, bits_fu32, wpr, ntx, ntl, ntl * B, pyr, P);
-                else if (win == 11) hipLaunchKernelGGL(k_threshold_pyr<11>, tg1, dim3(256), 0, s, srcW, cols, rows, thr_kk, bp, bits_fu32, wpr, ntx, ntl, ntl * B, pyr, P);
-                else hipLaunchKernelGGL(k_threshold_pyr<15>, tg1, dim3(256), 0, s, srcW, cols, rows, thr_kk, bp, bits_fu32, wpr, ntx, ntl, ntl * B, pyr, P);
-                if (nfuse && r_ == 0 && (rc = rest_of_pyramid(nfuse + 1))) return rc;
-            } else if (th_magic && win == 5) hipLaunchKernelGGL(k_adaptive_threshold_t<5>, tg1, dim3(256), 0, s, srcW, cols, rows, thres_value, th_magic, bp, bits_fu32, wpr, ntx, ntl, ntl * B);
-            else if (th_magic && win == 7) hipLaunchKernelGGL(k_adaptive_threshold_t<7>, tg1, dim3(256), 0, s, srcW, cols, rows, thres_value, th_magic, bp, bits_fu32, wpr, ntx, ntl, ntl * B);
-            else if (th_magic && win == 11) hipLaunchKernelGGL(k_adaptive_threshold_t<11>, tg1, dim3(256), 0, s, srcW, cols, rows, thres_value, th_magic, bp, bits_fu32, wpr, ntx, ntl, ntl * B);
-            else if (th_magic && win == 15) hipLaunchKernelGGL(k_adaptive_threshold_t<15>, tg1, dim3(256), 0, s, srcW, cols, rows, thres_value, th_magic, bp, bits_fu32, wpr, ntx, ntl, ntl * B);
+                P.n = p.nfuse;
+                for (int l = 1; l <= p.nfuse; l++) { P.w[l - 1] = levels[l].w; P.h[l - 1] = levels[l].h; P.pitch[l - 1] = levels[l].pitch; P.off[l - 1] = levels[l].off; }
+                hipLaunchKernelGGL(by_window(k_threshold_pyr<5>, k_threshold_pyr<7>, k_threshold_pyr<11>, k_threshold_pyr<15>), tg1, dim3(256), 0, s,
+                                   srcW, cols, rows, p.thr_kk, bp, bits_fu32, wpr, ntx, ntl, ntl * B, pyr_view(), P);
+                if (p.nfuse && r_ == 0) pyramid(p.nfuse + 1, src0, B, s);
+            } else if (p.thr == Thr::magic)
+                hipLaunchKernelGGL(by_window(k_adaptive_threshold_t<5>, k_adaptive_threshold_t<7>, k_adaptive_threshold_t<11>, k_adaptive_threshold_t<15>), tg1,
+                                   dim3(256), 0, s, srcW, cols, rows, thres_value, th_magic, bp, bits_fu32, wpr, ntx, ntl, ntl * B);
             else if (win <= 15) hipLaunchKernelGGL(k_adaptive_threshold<7>, tg, dim3(256), 0, s, srcW, cols, rows, win, thres_value, 1.0 / (win * win), bp, bits_fu32, wpr);
             else hipLaunchKernelGGL(k_adaptive_threshold<15>, tg, dim3(256), 0, s, srcW, cols, rows, win, thres_value, 1.0 / (win * win), bp, bits_fu32, wpr);
         }
-        timer.mark(s, "threshold");
-        const bool big = big_mode || !lds_bits_words;
-        const int legacy_kcap = big ? AR_MAX_KEPT_BIG : AR_MAX_KEPT, legacy_ldsw = big ? 0 : lds_bits_words;
-        const size_t lds = contours_lds_bytes(legacy_ldsw, legacy_kcap);
-        ORBFE_HIP(hipGetLastError());
-        auto kfn = big ? k_contours_t<false> : k_contours_t<true>;
-        { int rc_lds_ = ensure_dyn_lds(reinterpret_cast<const void*>(kfn), (size_t)(lds)); if (rc_lds_) return rc_lds_; }
-        const bool use_tiled = (tiled > 0 || (tiled < 0 && (relay_global || !relay_tbits || relay_tbits > 12 || B <= 32))) && !tiled_off && !force_legacy && !big_mode;
-        tiled_ran = use_tiled;
-        const bool relay = (relay_tbits || use_tiled) && !force_legacy && !big_mode;
-        // the bit image the contour kernels read: after the speck passes, unless switched off or the frame is too wide for their LDS tile
+        return ORBFE_OK;
+    }
+    // the speck passes as a launch of their own: d_bits -> d_bitsc
+    int speck_pass(const BatchPlan& p, int B, hipStream_t s)
+    {
+        int rc;
         const size_t spk_lds = speck_lds_bytes(cols);
-        specks_ran = (specks > 0 || (specks < 0 && relay && !use_tiled && !relay_global && B > 32)) && spk_lds <= 150 * 1024;
-        if (specks_ran) {
-            if ((rc = d_bitsc.ensure(bits_fu32 * 4 * batch_cap))) return rc;
-            { int rc_lds_ = ensure_dyn_lds(reinterpret_cast<const void*>(k_speck_clean), spk_lds); if (rc_lds_) return rc_lds_; }
-            hipLaunchKernelGGL(k_speck_clean, dim3((rows + SPK_ROWS - 1) / SPK_ROWS, B), dim3(SPK_THREADS), spk_lds, s, d_bits.as<uint32_t>(), bits_fu32, wpr,
-                               cols, rows, d_bitsc.as<uint32_t>());
-        }
-        const uint32_t* cbits = specks_ran ? d_bitsc.as<uint32_t>() : d_bits.as<uint32_t>();
-
-        for (int r_ = 0; relay && r_ < ORBFE_REPS_ARUCO(1); r_++) {
-            if (use_tiled) {
-                // Tile width and waves.  k_ct_walk's waves are persistent and overlap their tiles, so a wave wants several tiles (its
-                // lanes always find work) and a SIMD wants several waves (a step is a chain of dependent LDS reads): narrow tiles for a
-                // batch -- ORBFE_ARUCO_TILE_W / ORBFE_ARUCO_TPW (tiles per wave) are measurement switches --, and for a few frames as many
-                // waves as there are tiles.
-                const int target = tile_w_env > 0 ? tile_w_env : (B <= 32 ? 192 : 480);
-                const int ncols0 = std::max(1, (cols + target - 1) / target);
-                const int cw = std::min(CTW_MAX_CW, std::max(32, ((cols + ncols0 - 1) / ncols0 + 31) / 32 * 32));
-                const int ncols = (cols + cw - 1) / cw, nbands = (rows + 31) / 32;
-                const int wave_bytes = ctw_wave_lds_bytes(cw), wlds = wave_bytes * (CTW_THREADS / 64);
-                const int total_tiles = ncols * nbands * B;
-                const int tpw = tpw_env > 0 ? tpw_env : (B <= 32 ? 1 : 2);
-                const int walk_wgs = std::max(1, std::min((total_tiles / tpw + CTW_THREADS / 64 - 1) / (CTW_THREADS / 64), 256 * 8));
-                const size_t llds = (size_t)ct_lcap * 8 + 16;
-                { int rc_lds_ = ensure_dyn_lds(reinterpret_cast<const void*>(k_ct_walk), (size_t)wlds); if (rc_lds_) return rc_lds_; }
-                { int rc_lds_ = ensure_dyn_lds(reinterpret_cast<const void*>(k_ct_lists), llds); if (rc_lds_) return rc_lds_; }
-                if (ct_dirty) ORBFE_HIP(hipMemsetAsync(d_ctstate.p, 0, (size_t)CT_STATE_INTS * 4 * B, s)); // first use, or a batch abandoned before k_ct_lists (which leaves them at zero)
-                ct_gen = (ct_gen + 1) & 0xffffu;
-                if (ct_gen == 0) { ct_gen = 1; ct_tab_dirty = true; }
-                if (ct_tab_dirty) { ORBFE_HIP(hipMemsetAsync(d_cthtab.p, 0, d_cthtab.bytes, s)); ct_tab_dirty = false; }
-                ct_dirty = true;
-                // bands for full batches (eight waves level each other's load through the band's ticket counters) and, one cell row each, for
-                // up to four frames (single-frame call 0.385 -> 0.355 ms: the waves of a band share its start candidates, where a wave of
-                // k_ct_walk has its tile's to itself); a wave per tile in between
-                const bool use_band = banded > 0 || (banded < 0 && (B > 32 || B <= 4));
-                if (use_band) {
-                    const int pw = (cols + 2 + 31) / 32, crows = (rows + 31) / 32;
-                    int rb = band_rows_env > 0 ? band_rows_env : B <= 4 ? 1 : std::max(1, std::min(8, (int)((36 * 1024 / (pw * 4) - 3) / 32)));
-                    rb = std::max(1, std::min(rb, crows));
-                    const int nb = (crows + rb - 1) / rb;
-                    const size_t blds = ctb_lds_bytes(cols, rb);
-                    { int rc_lds_ = ensure_dyn_lds(reinterpret_cast<const void*>(k_ct_band), blds); if (rc_lds_) return rc_lds_; }
-                    hipLaunchKernelGGL(k_ct_band, dim3(nb, B), dim3(CTB_THREADS), blds, s, cbits, bits_fu32, wpr, cols, rows, 70,
-                                       d_lut.as<uint16_t>(), rb, d_ctmlist.as<uint32_t>(), CTB_MCAP, d_cthtab.as<unsigned long long>(), ct_hbits, ct_gen,
-                                       d_ctseg.as<uint32_t>(), (size_t)5 * ct_segcap, ct_segcap, d_ctstate.as<int32_t>(), d_pool.as<uint32_t>(), pool_fu32,
-                                       (int)pool_fu32, relay_kcap, d_tailkeys.as<unsigned long long>(), d_tailoff.as<int32_t>(), d_ctcodes.as<uint4>());
-                } else
-                hipLaunchKernelGGL(k_ct_walk, dim3(walk_wgs), dim3(CTW_THREADS), wlds, s, cbits, bits_fu32, wpr, cols, rows, 70,
-                                   d_lut.as<uint16_t>(), cw, ncols, nbands, total_tiles, d_cthtab.as<unsigned long long>(), ct_hbits, ct_gen,
-                                   d_ctseg.as<uint32_t>(), (size_t)5 * ct_segcap, ct_segcap, d_ctstate.as<int32_t>(), d_pool.as<uint32_t>(), pool_fu32,
-                                   (int)pool_fu32, relay_kcap, d_tailkeys.as<unsigned long long>(), d_tailoff.as<int32_t>(), wave_bytes,
-                                   d_ctcodes.as<uint4>());
-                hipLaunchKernelGGL(k_ct_lists, dim3(B), dim3(ct_lcap > 4096 ? 1024 : 512), llds, s, d_ctseg.as<uint32_t>(), (size_t)5 * ct_segcap, ct_segcap,
-                                   d_ctstate.as<int32_t>(), d_cthtab.as<unsigned long long>(), ct_hbits, ct_gen, d_ctelem.as<unsigned long long>(), ct_lcap, 70,
-                                   (int)pool_fu32, relay_kcap, d_tailkeys.as<unsigned long long>(), d_tailoff.as<int32_t>(), d_counts.as<int32_t>(),
-                                   d_rstate.as<int32_t>(), d_ctitemsA.as<uint4>(), d_ctitemsB.as<uint2>(), ct_items_per_frame, d_ctnitems.as<int32_t>());
-                if (hipPeekAtLastError() == hipSuccess) ct_dirty = false;
-                hipLaunchKernelGGL(k_ct_points, dim3(ct_items_per_frame >= 8192 ? 32 : 8, B), dim3(256), 0, s, d_ctitemsA.as<uint4>(), d_ctitemsB.as<uint2>(),
-                                   ct_items_per_frame, d_ctnitems.as<int32_t>(), d_ctcodes.as<uint32_t>(), ct_segcap, d_pool.as<uint32_t>(), pool_fu32);
-            } else {
-            const size_t rlds = relay_lds_bytes(relay_global ? 0 : lds_bits_words, relay_kcap, relay_tbits);
-            // (round 2 launched the large-frame kernels, whose workgroups take a CU's whole LDS, in chunks of N frames: no gain at 128 / 192,
-            // worse below -- profiles/r02_relay_chunks.txt; one launch since round 5)
-            const bool small_separate = small_separate_mode < 0 ? B <= 32 : small_separate_mode != 0;
-            const int chunk = B;
-            for (int f0 = 0; f0 < B; f0 += chunk) {
-            const int nb_ = std::min(chunk, B - f0);
-            if (relay_global) {
-                { int rc_lds_ = ensure_dyn_lds(reinterpret_cast<const void*>(k_contours_relay8g), (size_t)(rlds)); if (rc_lds_) return rc_lds_; }
-                hipLaunchKernelGGL(k_contours_relay8g, dim3(nb_), dim3(RL_THREADS_BIG), rlds, s, cbits, bits_fu32, wpr,
-                                   cols, rows, 0, 70, relay_kshift, relay_tbits, d_segs.as<RelaySeg>(),
-                                   d_pool.as<uint32_t>(), pool_fu32, (int)pool_fu32, d_kept.as<ArKept>(), relay_kcap, relay_kcap,
-                                   d_tailkeys.as<unsigned long long>(), d_tailoff.as<int32_t>(), d_counts.as<int32_t>(), d_hint.as<int32_t>(),
-                                   d_small.as<uint4>(), d_rstate.as<int32_t>(), d_gpad.as<uint32_t>(), gpad_fu32, d_lut.as<uint16_t>(), f0);
-            } else {
-            const bool wide = relay_tbits <= 12 && B <= 32 && relay_wide;   // few frames: 16 waves per frame (see k_contours_relay_wide)
-            auto rfn = relay_tbits > 12 ? k_contours_relay8 : wide ? k_contours_relay_wide : k_contours_relay;
-            { int rc_lds_ = ensure_dyn_lds(reinterpret_cast<const void*>(rfn), (size_t)(rlds)); if (rc_lds_) return rc_lds_; }
-            hipLaunchKernelGGL(rfn, dim3(nb_), dim3(relay_tbits > 12 || wide ? RL_THREADS_BIG : RL_THREADS), rlds, s, cbits, bits_fu32, wpr,
+        if (!(specks_ran = p.specks)) return ORBFE_OK;
+        if ((rc = d_bitsc.ensure(bits_fu32 * 4 * batch_cap)) || (rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_speck_clean), spk_lds))) return rc;
+        hipLaunchKernelGGL(k_speck_clean, dim3((rows + SPK_ROWS - 1) / SPK_ROWS, B), dim3(SPK_THREADS), spk_lds, s, d_bits.as<uint32_t>(), bits_fu32, wpr,
+                           cols, rows, d_bitsc.as<uint32_t>());
+        return ORBFE_OK;
+    }
+    // the tiled relay formulation (aruco_tiles.hip): k_ct_band or k_ct_walk, k_ct_lists, k_ct_points
+    int contours_tiled(const BatchPlan& p, int B, const uint32_t* cbits, hipStream_t s)
+    {
+        int rc;
+        const int cw = p.tile_w, ncols = (cols + cw - 1) / cw, nbands = (rows + 31) / 32, total_tiles = ncols * nbands * B;
+        const int wave_bytes = ctw_wave_lds_bytes(cw), wlds = wave_bytes * (CTW_THREADS / 64);
+        const int walk_wgs = std::max(1, std::min((total_tiles / p.tpw + CTW_THREADS / 64 - 1) / (CTW_THREADS / 64), 256 * 8));
+        const size_t llds = (size_t)ct_lcap * 8 + 16;
+        if ((rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_ct_walk), (size_t)wlds)) || (rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_ct_lists), llds))) return rc;
+        if (ct_dirty) ORBFE_HIP(hipMemsetAsync(d_ctstate.p, 0, (size_t)CT_STATE_INTS * 4 * B, s)); // first use, or a batch abandoned before k_ct_lists (which leaves them at zero)
+        ct_gen = (ct_gen + 1) & 0xffffu;
+        if (ct_gen == 0) { ct_gen = 1; ct_tab_dirty = true; }
+        if (ct_tab_dirty) { ORBFE_HIP(hipMemsetAsync(d_cthtab.p, 0, d_cthtab.bytes, s)); ct_tab_dirty = false; }
+        ct_dirty = true;
+        if (p.band) {
+            const int nb = ((rows + 31) / 32 + p.band_rows - 1) / p.band_rows;
+            const size_t blds = ctb_lds_bytes(cols, p.band_rows);
+            if ((rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_ct_band), blds))) return rc;
+            hipLaunchKernelGGL(k_ct_band, dim3(nb, B), dim3(CTB_THREADS), blds, s, cbits, bits_fu32, wpr, cols, rows, 70,
+                               d_lut.as<uint16_t>(), p.band_rows, d_ctmlist.as<uint32_t>(), CTB_MCAP, d_cthtab.as<unsigned long long>(), ct_hbits, ct_gen,
+                               d_ctseg.as<uint32_t>(), (size_t)5 * ct_segcap, ct_segcap, d_ctstate.as<int32_t>(), d_pool.as<uint32_t>(), pool_fu32,
+                               (int)pool_fu32, relay_kcap, d_tailkeys.as<unsigned long long>(), d_tailoff.as<int32_t>(), d_ctcodes.as<uint4>());
+        } else
+            hipLaunchKernelGGL(k_ct_walk, dim3(walk_wgs), dim3(CTW_THREADS), wlds, s, cbits, bits_fu32, wpr, cols, rows, 70,
+                               d_lut.as<uint16_t>(), cw, ncols, nbands, total_tiles, d_cthtab.as<unsigned long long>(), ct_hbits, ct_gen,
+                               d_ctseg.as<uint32_t>(), (size_t)5 * ct_segcap, ct_segcap, d_ctstate.as<int32_t>(), d_pool.as<uint32_t>(), pool_fu32,
+                               (int)pool_fu32, relay_kcap, d_tailkeys.as<unsigned long long>(), d_tailoff.as<int32_t>(), wave_bytes,
+                               d_ctcodes.as<uint4>());
+        hipLaunchKernelGGL(k_ct_lists, dim3(B), dim3(ct_lcap > 4096 ? 1024 : 512), llds, s, d_ctseg.as<uint32_t>(), (size_t)5 * ct_segcap, ct_segcap,
+                           d_ctstate.as<int32_t>(), d_cthtab.as<unsigned long long>(), ct_hbits, ct_gen, d_ctelem.as<unsigned long long>(), ct_lcap, 70,
+                           (int)pool_fu32, relay_kcap, d_tailkeys.as<unsigned long long>(), d_tailoff.as<int32_t>(), d_counts.as<int32_t>(),
+                           d_rstate.as<int32_t>(), d_ctitemsA.as<uint4>(), d_ctitemsB.as<uint2>(), ct_items_per_frame, d_ctnitems.as<int32_t>());
+        if (hipPeekAtLastError() == hipSuccess) ct_dirty = false;
+        hipLaunchKernelGGL(k_ct_points, dim3(ct_items_per_frame >= 8192 ? 32 : 8, B), dim3(256), 0, s, d_ctitemsA.as<uint4>(), d_ctitemsB.as<uint2>(),
+                           ct_items_per_frame, d_ctnitems.as<int32_t>(), d_ctcodes.as<uint32_t>(), ct_segcap, d_pool.as<uint32_t>(), pool_fu32);
+        return ORBFE_OK;
+    }
+    // the one-workgroup relay kernels (a workgroup per frame), then k_contours_small
+    int contours_relay(const BatchPlan& p, int B, const uint32_t* cbits, hipStream_t s)
+    {
+        const size_t rlds = relay_lds_bytes(relay_global ? 0 : lds_bits_words, relay_kcap, relay_tbits);
+        // (round 2 launched the large-frame kernels, whose workgroups take a CU's whole LDS, in chunks of N frames: no gain at 128 / 192,
+        // worse below -- profiles/r02_relay_chunks.txt; one launch since round 5)
+        if (p.relay == Relay::relay8g) {
+            if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_contours_relay8g), rlds)) return rc;
+            hipLaunchKernelGGL(k_contours_relay8g, dim3(B), dim3(RL_THREADS_BIG), rlds, s, cbits, bits_fu32, wpr,
+                               cols, rows, 0, 70, relay_kshift, relay_tbits, d_segs.as<RelaySeg>(),
+                               d_pool.as<uint32_t>(), pool_fu32, (int)pool_fu32, d_kept.as<ArKept>(), relay_kcap, relay_kcap,
+                               d_tailkeys.as<unsigned long long>(), d_tailoff.as<int32_t>(), d_counts.as<int32_t>(), d_hint.as<int32_t>(),
+                               d_small.as<uint4>(), d_rstate.as<int32_t>(), d_gpad.as<uint32_t>(), gpad_fu32, d_lut.as<uint16_t>(), 0);
+        } else {
+            auto rfn = p.relay == Relay::relay8 ? k_contours_relay8 : p.relay == Relay::wide ? k_contours_relay_wide : k_contours_relay;
+            if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(rfn), rlds)) return rc;
+            hipLaunchKernelGGL(rfn, dim3(B), dim3(p.relay == Relay::relay ? RL_THREADS : RL_THREADS_BIG), rlds, s, cbits, bits_fu32, wpr,
                                cols, rows, lds_bits_words, 70, relay_kshift, relay_tbits, d_segs.as<RelaySeg>(),
                                d_pool.as<uint32_t>(), pool_fu32, (int)pool_fu32, d_kept.as<ArKept>(), relay_kcap, relay_kcap,
                                d_tailkeys.as<unsigned long long>(), d_tailoff.as<int32_t>(), d_counts.as<int32_t>(), d_hint.as<int32_t>(),
-                               d_small.as<uint4>(), d_rstate.as<int32_t>(), (small_separate ? 1 : 0) | (specks_inkernel && !specks_ran && !small_separate ? 2 : 0), d_lut.as<uint16_t>(), f0,
-                               d_candq.as<uint32_t>(), candq_fu32);
-            }
-            }
-            // the borders that touch no grid line, for frames done with a grid by a relay kernel that leaves them out (the
-            // HBM-resident one: its bands fit LDS here; for LDS-resident frames the separate launch halves the relay kernel's time
-            // but issues twice the instructions of the in-kernel phase -- measured 1.85 -> 1.98 ms per C2 step -- so those keep
-            // phase (c) inside): bands of K rows, K >= 2^relay_kshift
-            if (relay_global || small_separate) {
-                const int nwaves = ((cols >> RS_BLOCK_SHIFT) + 1) * ((rows >> relay_kshift) + 1); // blocks of the finest grid
-                hipLaunchKernelGGL(k_contours_small, dim3((nwaves + RS_THREADS / 64 - 1) / (RS_THREADS / 64), B), dim3(RS_THREADS), 0, s,
-                                   cbits, bits_fu32, wpr, cols, rows, 70, d_lut.as<uint16_t>(), d_rstate.as<int32_t>(),
-                                   d_pool.as<uint32_t>(), pool_fu32, (int)pool_fu32, relay_kcap, d_tailkeys.as<unsigned long long>(),
-                                   d_tailoff.as<int32_t>(), d_counts.as<int32_t>());
-            }
-            } // (the relay kernels)
-            // (g): sort + rank per frame, approxPolyDP by persistent waves over the whole batch's borders, rectangles per frame
-            {
-                const int pts = RT_PTS;   // LDS point buffer per wave; longer borders are read from the pool
-                const size_t alds = tail_approx_lds_bytes(pts);
-                const int tail_wgs = std::min(RT_WGS, B * 128);
-                { int rc_lds_ = ensure_dyn_lds(reinterpret_cast<const void*>(k_tail_prep), tail_prep_lds_bytes(relay_kcap)); if (rc_lds_) return rc_lds_; }
-                { int rc_lds_ = ensure_dyn_lds(reinterpret_cast<const void*>(k_tail_approx), alds); if (rc_lds_) return rc_lds_; }
-                if (tail_dirty) ORBFE_HIP(hipMemsetAsync(d_tctr.p, 0, 16, s));   // a previous batch was abandoned between prep and finish
-                tail_dirty = true;
-                hipLaunchKernelGGL(k_tail_prep, dim3(B), dim3(relay_global ? 1024 : 256), tail_prep_lds_bytes(relay_kcap), s,
-                                   d_tailkeys.as<unsigned long long>(), d_tailoff.as<int32_t>(), relay_kcap, d_counts.as<int32_t>(),
-                                   d_twork.as<uint4>(), (size_t)relay_kcap * B, d_tctr.as<int32_t>());
-                hipLaunchKernelGGL(k_tail_approx, dim3(tail_wgs), dim3(256), alds, s, relay_kcap, d_twork.as<uint4>(), (size_t)relay_kcap * B, d_tctr.as<int32_t>(),
-                                   d_pool.as<uint32_t>(), pool_fu32, d_kept.as<ArKept>(), relay_kcap, d_trect.as<uint8_t>(), pts);
-                // (the rectangle lists: a launch of their own only when the enclosed-marker pass sits between them and k_prefilter)
-                finish_in_prefilter = !enclosed;
-                if (!finish_in_prefilter) {
-                    hipLaunchKernelGGL(k_tail_finish, dim3(B), dim3(64), 0, s, relay_kcap, d_trect.as<uint8_t>(), d_kept.as<ArKept>(), relay_kcap,
-                                       d_rects.as<ArRect>(), AR_MAX_RECTS, d_counts.as<int32_t>(), d_tctr.as<int32_t>());
-                    if (hipPeekAtLastError() == hipSuccess) tail_dirty = false;   // k_tail_finish leaves the list lengths at zero
-                }
-            }
+                               d_small.as<uint4>(), d_rstate.as<int32_t>(), (p.small_separate ? 1 : 0) | (specks_inkernel && !p.specks && !p.small_separate ? 2 : 0),
+                               d_lut.as<uint16_t>(), 0, d_candq.as<uint32_t>(), candq_fu32);
         }
-        // the single-walker kernel: images whose bit image does not fit LDS next to the relay kernel's tables, or forced
-        if (!relay && !ORBFE_SKIP_ARUCO(1)) hipLaunchKernelGGL(kfn, dim3(B), dim3(CT_PROBE_THREADS), lds, s, cbits, bits_fu32, wpr, cols, rows,
-                           legacy_ldsw, 70, d_candq.as<uint32_t>(), candq_fu32, (int)candq_fu32,
-                           d_pool.as<uint32_t>(), pool_fu32, (int)pool_fu32, d_kept.as<ArKept>(), legacy_kcap,
-                           d_rects.as<ArRect>(), AR_MAX_RECTS, d_counts.as<int32_t>(), d_gpad.as<uint32_t>(),
-                           gpad_fu32, 0);
-        timer.mark(s, "contours");
-        ORBFE_HIP(hipGetLastError());
+        // the borders that touch no grid line, for frames done with a grid by a relay kernel that leaves them out (the
+        // HBM-resident one: its bands fit LDS here; for LDS-resident frames the separate launch halves the relay kernel's time
+        // but issues twice the instructions of the in-kernel phase -- measured 1.85 -> 1.98 ms per C2 step -- so those keep
+        // phase (c) inside): bands of K rows, K >= 2^relay_kshift
+        if (p.small_separate) {
+            const int nwaves = ((cols >> RS_BLOCK_SHIFT) + 1) * ((rows >> relay_kshift) + 1); // blocks of the finest grid
+            hipLaunchKernelGGL(k_contours_small, dim3((nwaves + RS_THREADS / 64 - 1) / (RS_THREADS / 64), B), dim3(RS_THREADS), 0, s,
+                               cbits, bits_fu32, wpr, cols, rows, 70, d_lut.as<uint16_t>(), d_rstate.as<int32_t>(),
+                               d_pool.as<uint32_t>(), pool_fu32, (int)pool_fu32, relay_kcap, d_tailkeys.as<unsigned long long>(),
+                               d_tailoff.as<int32_t>(), d_counts.as<int32_t>());
+        }
+        return ORBFE_OK;
+    }
+    // (g) of the tiled and relay paths: sort + rank per frame, approxPolyDP by persistent waves over the whole batch's borders, rectangles per frame
+    int relay_tail(int B, hipStream_t s, bool* finish_in_prefilter)
+    {
+        int rc;
+        const int pts = RT_PTS, tail_wgs = std::min(RT_WGS, B * 128);   // pts: LDS point buffer per wave; longer borders are read from the pool
+        const size_t alds = tail_approx_lds_bytes(pts);
+        if ((rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_tail_prep), tail_prep_lds_bytes(relay_kcap))) || (rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_tail_approx), alds))) return rc;
+        if (tail_dirty) ORBFE_HIP(hipMemsetAsync(d_tctr.p, 0, 16, s));   // a previous batch was abandoned between prep and finish
+        tail_dirty = true;
+        hipLaunchKernelGGL(k_tail_prep, dim3(B), dim3(relay_global ? 1024 : 256), tail_prep_lds_bytes(relay_kcap), s,
+                           d_tailkeys.as<unsigned long long>(), d_tailoff.as<int32_t>(), relay_kcap, d_counts.as<int32_t>(),
+                           d_twork.as<uint4>(), (size_t)relay_kcap * B, d_tctr.as<int32_t>());
+        hipLaunchKernelGGL(k_tail_approx, dim3(tail_wgs), dim3(256), alds, s, relay_kcap, d_twork.as<uint4>(), (size_t)relay_kcap * B, d_tctr.as<int32_t>(),
+                           d_pool.as<uint32_t>(), pool_fu32, d_kept.as<ArKept>(), relay_kcap, d_trect.as<uint8_t>(), pts);
+        // (the rectangle lists: a launch of their own only when the enclosed-marker pass sits between them and k_prefilter)
+        if ((*finish_in_prefilter = !enclosed)) return ORBFE_OK;
+        hipLaunchKernelGGL(k_tail_finish, dim3(B), dim3(64), 0, s, relay_kcap, d_trect.as<uint8_t>(), d_kept.as<ArKept>(), relay_kcap,
+                           d_rects.as<ArRect>(), AR_MAX_RECTS, d_counts.as<int32_t>(), d_tctr.as<int32_t>());
+        if (hipPeekAtLastError() == hipSuccess) tail_dirty = false;   // k_tail_finish leaves the list lengths at zero
+        return ORBFE_OK;
+    }
+    // the single-walker kernel: images whose bit image does not fit LDS next to the relay kernel's tables, big-frame mode, or forced
+    int contours_single_walker(const BatchPlan& p, int B, const uint32_t* cbits, hipStream_t s)
+    {
+        const int kcap = p.walker_hbm ? AR_MAX_KEPT_BIG : AR_MAX_KEPT, ldsw = p.walker_hbm ? 0 : lds_bits_words;
+        const size_t lds = contours_lds_bytes(ldsw, kcap);
+        auto kfn = p.walker_hbm ? k_contours_t<false> : k_contours_t<true>;
+        if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(kfn), lds)) return rc;
+        if (!ORBFE_SKIP_ARUCO(1))
+            hipLaunchKernelGGL(kfn, dim3(B), dim3(CT_PROBE_THREADS), lds, s, cbits, bits_fu32, wpr, cols, rows, ldsw, 70, d_candq.as<uint32_t>(),
+                               candq_fu32, (int)candq_fu32, d_pool.as<uint32_t>(), pool_fu32, (int)pool_fu32, d_kept.as<ArKept>(), kcap,
+                               d_rects.as<ArRect>(), AR_MAX_RECTS, d_counts.as<int32_t>(), d_gpad.as<uint32_t>(), gpad_fu32, 0);
+        return ORBFE_OK;
+    }
+    // prefilterCandidates, then the batch's candidates decoded as one work list: a wave per candidate (persistent: 32 candidates per
+    // frame is more than the streams here produce, a busier batch loops), 64 candidates per Otsu wave
+    int prefilter_decode(const BatchPlan& p, int B, hipStream_t s, const ImgView& src0, int enlarge_k, bool finish_in_prefilter)
+    {
         if (enclosed)   // enlargeMarkerCandidate on every rectangle, before prefilterCandidates sees them (:3560-3590)
             hipLaunchKernelGGL(k_enlarge_candidates, dim3(B), dim3(AR_MAX_RECTS), 0, s, d_rects.as<ArRect>(), AR_MAX_RECTS, d_counts.as<int32_t>(),
                                (int)(float(enlarge_k) / 2.));
         if (decode_dirty) ORBFE_HIP(hipMemsetAsync(d_dctr.p, 0, 16, s));   // a previous batch was abandoned between prefilter and finalize
         decode_dirty = true;
-        {
-            TailFinish tf{};
-            if (finish_in_prefilter) tf = TailFinish{relay_kcap, d_trect.as<uint8_t>(), d_kept.as<ArKept>(), relay_kcap, d_tctr.as<int32_t>()};
-            hipLaunchKernelGGL(k_prefilter, dim3(B), dim3(256), 0, s, d_rects.as<ArRect>(), AR_MAX_RECTS,
-                               d_counts.as<int32_t>(), cols, rows, win, d_candidx.as<int32_t>(), d_ncand.as<int32_t>(),
-                               d_dwork.as<uint32_t>(), d_dctr.as<int32_t>(), tf);
-            if (finish_in_prefilter && hipPeekAtLastError() == hipSuccess) tail_dirty = false;   // (it leaves the tail's list lengths at zero)
+        const TailFinish tf = finish_in_prefilter ? TailFinish{relay_kcap, d_trect.as<uint8_t>(), d_kept.as<ArKept>(), relay_kcap, d_tctr.as<int32_t>()} : TailFinish{};
+        hipLaunchKernelGGL(k_prefilter, dim3(B), dim3(256), 0, s, d_rects.as<ArRect>(), AR_MAX_RECTS,
+                           d_counts.as<int32_t>(), cols, rows, win, d_candidx.as<int32_t>(), d_ncand.as<int32_t>(),
+                           d_dwork.as<uint32_t>(), d_dctr.as<int32_t>(), tf);
+        if (finish_in_prefilter && hipPeekAtLastError() == hipSuccess) tail_dirty = false;   // (it leaves the tail's list lengths at zero)
+        if (!p.nfuse) ORBFE_HIP(hipStreamWaitEvent(s, ev_join, 0));   // the pyramid of the aux stream
+        const int max_items = B * AR_MAX_RECTS, wgs = std::max(1, std::min((B * 32 + DC_WAVES - 1) / DC_WAVES, 4096));
+        for (int r_ = 0; r_ < ORBFE_REPS_ARUCO(2); r_++) {
+            hipLaunchKernelGGL(k_decode_warp, dim3(wgs), dim3(DC_WAVES * 64), 0, s, src0, pyr_view(), d_levels.as<ArLevel>(), npyr,
+                               d_rects.as<ArRect>(), AR_MAX_RECTS, d_candidx.as<int32_t>(), S, cols, d_dwork.as<uint32_t>(),
+                               d_dctr.as<int32_t>(), d_ditems.as<DcItem>(), d_dhist.as<uint16_t>(), d_dpatch.as<uint8_t>());
+            hipLaunchKernelGGL(k_decode_otsu, dim3((max_items + 63) / 64), dim3(64), 0, s, d_dctr.as<int32_t>(), d_ditems.as<DcItem>(),
+                               d_dhist.as<uint16_t>(), S);
+            hipLaunchKernelGGL(k_decode_vote, dim3(wgs), dim3(DC_WAVES * 64), 0, s, src0, pyr_view(), d_levels.as<ArLevel>(), AR_MAX_RECTS, S, nb,
+                               d_codes.as<unsigned long long>(), ncodes, d_scodes.as<unsigned long long>(), d_sids.as<int32_t>(),
+                               nsorted, max_corr, d_dwork.as<uint32_t>(), d_dctr.as<int32_t>(), d_ditems.as<DcItem>(),
+                               d_dpatch.as<uint8_t>(), d_result.as<int32_t>());
         }
-        if (!nfuse) ORBFE_HIP(hipStreamWaitEvent(s, ev_join, 0));
-        {
-            // the batch's candidates as one work list: a wave per candidate (persistent: 32 candidates per frame is more than the
-            // streams here produce, a busier batch loops), 64 candidates per Otsu wave
-            const int max_items = B * AR_MAX_RECTS;
-            const int wgs = std::max(1, std::min((B * 32 + DC_WAVES - 1) / DC_WAVES, 4096));
-            for (int r_ = 0; r_ < ORBFE_REPS_ARUCO(2); r_++) {
-                hipLaunchKernelGGL(k_decode_warp, dim3(wgs), dim3(DC_WAVES * 64), 0, s, src0, pyr, d_levels.as<ArLevel>(), npyr,
-                                   d_rects.as<ArRect>(), AR_MAX_RECTS, d_candidx.as<int32_t>(), S, cols, d_dwork.as<uint32_t>(),
-                                   d_dctr.as<int32_t>(), d_ditems.as<DcItem>(), d_dhist.as<uint16_t>(), d_dpatch.as<uint8_t>());
-                hipLaunchKernelGGL(k_decode_otsu, dim3((max_items + 63) / 64), dim3(64), 0, s, d_dctr.as<int32_t>(), d_ditems.as<DcItem>(),
-                                   d_dhist.as<uint16_t>(), S);
-                hipLaunchKernelGGL(k_decode_vote, dim3(wgs), dim3(DC_WAVES * 64), 0, s, src0, pyr, d_levels.as<ArLevel>(), AR_MAX_RECTS, S, nb,
-                                   d_codes.as<unsigned long long>(), ncodes, d_scodes.as<unsigned long long>(), d_sids.as<int32_t>(),
-                                   nsorted, max_corr, d_dwork.as<uint32_t>(), d_dctr.as<int32_t>(), d_ditems.as<DcItem>(),
-                                   d_dpatch.as<uint8_t>(), d_result.as<int32_t>());
-            }
-        }
-        timer.mark(s, "decode");
+        return ORBFE_OK;
+    }
+    // the mode runs' histogram and corner upsampling, sort / dedupe into the marker records (k_finalize), cornerSubPix
+    int finalize(int B, hipStream_t s, const ImgView& src0, const ModeRun* mr, orbfe_marker* d_out_m, int capacity, int32_t* d_n)
+    {
+        const bool reduced = mr && mr->d_full;
         if (mr && mr->d_hist)   // the pixels of the accepted candidates: the next frame's threshold is Otsu over them
             hipLaunchKernelGGL(k_marker_hist, dim3(B), dim3(256), 0, s, d_dwork.as<uint32_t>(), d_dctr.as<int32_t>(), d_result.as<int32_t>(),
                                AR_MAX_RECTS, d_dhist.as<uint16_t>(), mr->d_hist);
         if (reduced) {   // cornerUpsample: before sort / dedupe, whose perimeters are those of the upsampled corners
             int start = 0;
-            for (int i = 0; i < npyr; i++) {
-                if (cols < levels[i].w) start = i;
-                else break;
-            }
+            for (int i = 0; i < npyr && cols < levels[i].w; i++) start = i;
             const int wgs = std::max(1, std::min((B * 32 * 4 + 3) / 4, 2048));
-            hipLaunchKernelGGL(k_upsample_corners, dim3(wgs), dim3(256), 0, s, src0, pyr, d_levels.as<ArLevel>(), start, cols,
+            hipLaunchKernelGGL(k_upsample_corners, dim3(wgs), dim3(256), 0, s, src0, pyr_view(), d_levels.as<ArLevel>(), start, cols,
                                d_rects.as<ArRect>(), AR_MAX_RECTS, d_candidx.as<int32_t>(), d_dwork.as<uint32_t>(), d_dctr.as<int32_t>(),
                                d_result.as<int32_t>(), d_masks.as<float>());
         }
-        if (mr && mr->before_finalize && (rc = mr->before_finalize(s))) return rc;
+        if (int rc = mr && mr->before_finalize ? mr->before_finalize(s) : ORBFE_OK) return rc;
         // corner refinement applies only when the input was not reduced (:8420): CORNER_LINES inside k_finalize, CORNER_SUBPIX after it
         for (int r_ = 0; r_ < ORBFE_REPS_ARUCO(4); r_++) hipLaunchKernelGGL(k_finalize, dim3(B), dim3(256), 0, s, d_rects.as<ArRect>(), AR_MAX_RECTS,
                            d_candidx.as<int32_t>(), d_ncand.as<int32_t>(), d_result.as<int32_t>(),
@@ -834,9 +869,6 @@ struct orbfe_aruco {
         if (corner_method == 0 && !reduced)   // cornerSubPix(grey, Size(4, 4), TermCriteria(MAX_ITER | EPS, 12, 0.005)) (:8511)
             hipLaunchKernelGGL(k_corner_subpix_markers, dim3(16, B), dim3(256), 0, s, src0, cols, rows, d_out_m, d_n, capacity, 4, 12,
                                0.005 * 0.005, d_masks.as<float>() + (size_t)3 * 17 * 17);
-        timer.mark(s, "finalize");
-        ORBFE_HIP(hipGetLastError());
-        decode_dirty = false;   // k_finalize leaves the work-list length at zero
         return ORBFE_OK;
     }
 };
@@ -1013,11 +1045,10 @@ static int work_size(const orbfe_aruco* h, int rows, int cols, int* wr, int* wc)
     return ORBFE_OK;
 }
 
-// a batch on a reduced working image: INTER_NEAREST into the handle's buffer, then the pipeline with the full frames for the
-// pyramid, the warps and cornerUpsample
+// a batch on a reduced working image: INTER_NEAREST into the handle's buffer, then the pipeline (mode run `mr`) with the full frames for
+// the pyramid, the warps and cornerUpsample
 static int reduced_batch(orbfe_aruco* h, const uint8_t* d_imgs, int B, size_t frame_stride, int rows, int cols, size_t step, int wr, int wc,
-                         orbfe_marker* d_out, int capacity, int32_t* d_n, hipStream_t s, int fixed_thr, uint32_t* d_hist,
-                         std::function<int(hipStream_t)> before_finalize = nullptr)
+                         orbfe_marker* d_out, int capacity, int32_t* d_n, hipStream_t s, ModeRun mr = {}, Contours floor = Contours::tiled, Contours* ran = nullptr)
 {
     const size_t rpitch = (size_t)(wc + 63) / 64 * 64, rframe = rpitch * wr;
     int rc = h->d_red.ensure(rframe * B + 64);
@@ -1025,10 +1056,8 @@ static int reduced_batch(orbfe_aruco* h, const uint8_t* d_imgs, int B, size_t fr
     const double ifx = 1. / ((double)wc / cols), ify = 1. / ((double)wr / rows);
     hipLaunchKernelGGL(k_resize_nearest, dim3((wc + 63) / 64, (wr + 3) / 4, B), dim3(256), 0, s, ImgView{d_imgs, nullptr, frame_stride, (int)step},
                        ImgView{h->d_red.as<uint8_t>(), h->d_red.as<uint8_t>(), rframe, (int)rpitch}, cols, rows, wc, wr, ifx, ify);
-    ModeRun mr;
     mr.d_full = d_imgs; mr.full_fstride = frame_stride; mr.full_step = step; mr.full_rows = rows; mr.full_cols = cols;
-    mr.fixed_thr = fixed_thr; mr.d_hist = d_hist; mr.before_finalize = before_finalize;
-    return h->run_device(h->d_red.as<uint8_t>(), B, rframe, wr, wc, rpitch, d_out, capacity, d_n, s, &mr);
+    return h->run_device(h->d_red.as<uint8_t>(), B, rframe, wr, wc, rpitch, d_out, capacity, d_n, s, &mr, floor, ran);
 }
 
 // The threshold of the next frame: Otsu's criterion over the normalised float histogram of the detected markers' pixels, every
@@ -1257,7 +1286,7 @@ int orbfe_aruco_detect_batch_device(orbfe_aruco* h, const uint8_t* d_imgs, int n
         return fail(ORBFE_ERR_INVALID, "orbfe_aruco_detect_batch_device: DM_FAST / DM_VIDEO_FAST are frame-sequential (use orbfe_aruco_detect)");
     int wr, wc;
     if ((rc = work_size(h, rows, cols, &wr, &wc))) return rc;
-    if (wc != cols) return reduced_batch(h, d_imgs, nframes, frame_stride, rows, cols, step, wr, wc, d_out, capacity, d_n_out, (hipStream_t)stream, -1, nullptr);
+    if (wc != cols) return reduced_batch(h, d_imgs, nframes, frame_stride, rows, cols, step, wr, wc, d_out, capacity, d_n_out, (hipStream_t)stream);
     return h->run_device(d_imgs, nframes, frame_stride, rows, cols, step, d_out, capacity, d_n_out, (hipStream_t)stream);
 }
 
@@ -1360,7 +1389,6 @@ static int detect_frames_modes(orbfe_aruco* h, const uint8_t* imgs, int nframes,
     const int32_t* counts = reinterpret_cast<const int32_t*>(hp + o_cnt);
     const int32_t* np = reinterpret_cast<const int32_t*>(hp + o_n);
     const orbfe_marker* mk = reinterpret_cast<const orbfe_marker*>(hp + o_mk);
-    const bool user_big_mode = h->big_mode;
     for (int f = 0; f < nframes; f++) {
         const uint8_t* img = imgs + (size_t)f * frame_stride;
         if (channels == 3) {
@@ -1407,26 +1435,21 @@ static int detect_frames_modes(orbfe_aruco* h, const uint8_t* imgs, int nframes,
             };
         for (;;) {
             h->last_attempts++;
-            const int thr = h->thres_method == 1 ? h->thres_value : -1;
-            uint32_t* d_hist = h->thres_method == 1 ? h->d_mhist.as<uint32_t>() : nullptr;
-            for (int pass = 0; pass < 3; pass++) { // a frame that exceeds the capacities of the contour path it ran on is done again on the next one (escalate())
-                if (wc != cols) rc = reduced_batch(h, h->d_in.as<uint8_t>(), 1, dframe, rows, cols, dpitch, wr, wc, h->d_out.as<orbfe_marker>(), AR_MAX_RECTS,
-                                                   h->d_nout.as<int32_t>(), s, thr, d_hist, track_hook);
-                else {
-                    ModeRun mr;
-                    mr.fixed_thr = thr; mr.d_hist = d_hist; mr.before_finalize = track_hook;
-                    rc = h->run_device(h->d_in.as<uint8_t>(), 1, dframe, rows, cols, dpitch, h->d_out.as<orbfe_marker>(), AR_MAX_RECTS,
-                                       h->d_nout.as<int32_t>(), s, &mr);
-                }
-                if (rc) { h->big_mode = user_big_mode; h->tiled_off = false; return rc; }
+            ModeRun mr;   // THRES_AUTO_FIXED: the carried-over threshold and the histogram of the markers found with it
+            mr.fixed_thr = h->thres_method == 1 ? h->thres_value : -1; mr.d_hist = h->thres_method == 1 ? h->d_mhist.as<uint32_t>() : nullptr; mr.before_finalize = track_hook;
+            rc = h->with_retries([&](Contours floor, Contours* ran) -> int {
+                if (int e = wc != cols ? reduced_batch(h, h->d_in.as<uint8_t>(), 1, dframe, rows, cols, dpitch, wr, wc, h->d_out.as<orbfe_marker>(),
+                                                       AR_MAX_RECTS, h->d_nout.as<int32_t>(), s, mr, floor, ran)
+                                       : h->run_device(h->d_in.as<uint8_t>(), 1, dframe, rows, cols, dpitch, h->d_out.as<orbfe_marker>(), AR_MAX_RECTS,
+                                                       h->d_nout.as<int32_t>(), s, &mr, floor, ran))
+                    return e;
                 ORBFE_HIP(hipMemcpyAsync(hp + o_n, h->d_nout.p, 4, hipMemcpyDeviceToHost, s));
                 ORBFE_HIP(hipMemcpyAsync(hp + o_cnt, h->d_counts.p, 16, hipMemcpyDeviceToHost, s));
-                if (d_hist) ORBFE_HIP(hipMemcpyAsync(hp + o_h, d_hist, 1024, hipMemcpyDeviceToHost, s));
+                if (mr.d_hist) ORBFE_HIP(hipMemcpyAsync(hp + o_h, mr.d_hist, 1024, hipMemcpyDeviceToHost, s));
                 ORBFE_HIP(hipMemcpyAsync(hp + o_mk, h->d_out.p, (size_t)AR_MAX_RECTS * sizeof(orbfe_marker), hipMemcpyDeviceToHost, s));
-                ORBFE_HIP(hipStreamSynchronize(s));
-                if (!h->escalate(counts[2])) break;
-            }
-            h->big_mode = user_big_mode; h->tiled_off = false;
+                return ORBFE_OK;
+            }, counts, 1);
+            if (rc) return rc;
             if (counts[2]) return fail(ORBFE_ERR_CAPACITY, "frame %d: internal detector capacity exceeded (flags 0x%x)", f, counts[2]);
             // (the retry is decided on what the dictionary found, before the tracking block adds anything: :6903)
             if ((h->tracking_min > 0 ? pre_detected : np[0]) == 0 && h->thres_method == 1 && ++attempts < h->n_attempts_auto_fix) {
@@ -1533,11 +1556,12 @@ static int detect_batch_impl(orbfe_aruco* h, const uint8_t* imgs, int nframes, s
         for (int y = 0; y < rows; y++) memcpy(hp + f * dframe + (size_t)y * dpitch, imgs + f * frame_stride + (size_t)y * step, (size_t)cols);
     ORBFE_HIP(hipMemcpyAsync(h->d_in.p, hp, dframe * nframes, hipMemcpyHostToDevice, s));
     const int32_t* counts = reinterpret_cast<const int32_t*>(hp + o_cnt);
-    const bool user_big_mode = h->big_mode; // orbfe_aruco_set_big_frames applies to all following batches: keep it
-    for (int attempt = 0; attempt < 3; attempt++) {
-        rc = h->run_device(h->d_in.as<uint8_t>(), nframes, dframe, rows, cols, dpitch, h->d_out.as<orbfe_marker>(),
-                           AR_MAX_RECTS, h->d_nout.as<int32_t>(), s);
-        if (rc) { h->big_mode = user_big_mode; h->tiled_off = false; return rc; }
+    // a frame with more segments than the tiled path's lists hold: the batch is done again by the relay kernels; one with more kept
+    // borders (or border points) than those hold: by the single-walker kernel with its tables sized for AR_MAX_KEPT_BIG
+    rc = h->with_retries([&](Contours floor, Contours* ran) -> int {
+        if (int e = h->run_device(h->d_in.as<uint8_t>(), nframes, dframe, rows, cols, dpitch, h->d_out.as<orbfe_marker>(),
+                                  AR_MAX_RECTS, h->d_nout.as<int32_t>(), s, nullptr, floor, ran))
+            return e;
         if (cam)
             hipLaunchKernelGGL(k_marker_poses, dim3((AR_MAX_RECTS + 31) / 32, nframes), dim3(64), 0, s, h->d_out.as<orbfe_marker>(),
                                h->d_nout.as<int32_t>(), AR_MAX_RECTS, marker_size, *cam, h->d_poses.as<orbfe_marker_pose>());
@@ -1547,21 +1571,16 @@ static int detect_batch_impl(orbfe_aruco* h, const uint8_t* imgs, int nframes, s
             op.add(hp + o_cnt, h->d_counts.p, (size_t)nframes * 16);
             op.add(hp + o_mk, h->d_out.p, (size_t)AR_MAX_RECTS * nframes * sizeof(orbfe_marker));
             if (cam) op.add(hp + o_ps, h->d_poses.p, (size_t)AR_MAX_RECTS * nframes * sizeof(orbfe_marker_pose));
-            if ((rc = op.flush<2>(s))) { h->big_mode = user_big_mode; h->tiled_off = false; return rc; }
+            if (int e = op.flush<2>(s)) return e;
         } else {
             ORBFE_HIP(hipMemcpyAsync(hp + o_n, h->d_nout.p, (size_t)nframes * 4, hipMemcpyDeviceToHost, s));
             ORBFE_HIP(hipMemcpyAsync(hp + o_cnt, h->d_counts.p, (size_t)nframes * 16, hipMemcpyDeviceToHost, s));
             ORBFE_HIP(hipMemcpyAsync(hp + o_mk, h->d_out.p, (size_t)AR_MAX_RECTS * nframes * sizeof(orbfe_marker), hipMemcpyDeviceToHost, s));
             if (cam) ORBFE_HIP(hipMemcpyAsync(hp + o_ps, h->d_poses.p, (size_t)AR_MAX_RECTS * nframes * sizeof(orbfe_marker_pose), hipMemcpyDeviceToHost, s));
         }
-        ORBFE_HIP(hipStreamSynchronize(s));
-        int flags_or = 0;
-        for (int f = 0; f < nframes; f++) flags_or |= counts[f * 4 + 2];
-        // a frame with more segments than the tiled path's lists hold: the batch is done again by the relay kernels; one with more kept
-        // borders (or border points) than those hold: by the single-walker kernel with its tables sized for AR_MAX_KEPT_BIG
-        if (!h->escalate(flags_or)) break;
-    }
-    h->big_mode = user_big_mode; h->tiled_off = false;
+        return ORBFE_OK;
+    }, counts, nframes);
+    if (rc) return rc;
     memcpy(n_out, hp + o_n, (size_t)nframes * 4);
     for (int f = 0; f < nframes; f++) {
         if (counts[f * 4 + 2])
@@ -1634,17 +1653,7 @@ int orbfe_corner_subpix(const uint8_t* img, int rows, int cols, size_t step, flo
     for (int i = 0; i < n; i++) { mk[i >> 2].corners[i & 3][0] = pts[2 * i]; mk[i >> 2].corners[i & 3][1] = pts[2 * i + 1]; }
     for (int i = n; i < 4 * nm; i++) { mk[i >> 2].corners[i & 3][0] = pts[0]; mk[i >> 2].corners[i & 3][1] = pts[1]; }
     std::vector<float> mask((size_t)17 * 17, 0.f);
-    {
-        const int ww = 2 * win + 1;
-        for (int i = 0; i < ww; i++) {
-            const float y = (float)(i - win) / win;
-            const float vy = std::exp(-y * y);
-            for (int j = 0; j < ww; j++) {
-                const float x = (float)(j - win) / win;
-                mask[(size_t)i * ww + j] = (float)(vy * std::exp(-x * x));
-            }
-        }
-    }
+    subpix_window(win, mask.data());
     ORBFE_HIP(hipMemcpy2D(d_img.p, pitch, img, step, (size_t)cols, (size_t)rows, hipMemcpyHostToDevice));
     ORBFE_HIP(hipMemcpy(d_mk.p, mk.data(), mk.size() * sizeof(orbfe_marker), hipMemcpyHostToDevice));
     ORBFE_HIP(hipMemcpy(d_n.p, &nm, 4, hipMemcpyHostToDevice));
@@ -1663,18 +1672,9 @@ int orbfe_aruco_debug_image(orbfe_aruco* h, int frame, int stage, uint8_t* out)
     int rc = use_device(h->device);
     if (rc) return rc;
     ORBFE_HIP(hipDeviceSynchronize());
-    if (stage == 0) {
+    if (stage == 0 || stage == 104) { // the threshold image; 104: the bit image the contour kernels of the last batch read (after the speck passes, if they ran)
         std::vector<uint32_t> bits(h->bits_fu32);
-        ORBFE_HIP(hipMemcpy(bits.data(), h->d_bits.as<uint32_t>() + (size_t)frame * h->bits_fu32, bits.size() * 4,
-                            hipMemcpyDeviceToHost));
-        for (int y = 0; y < h->rows; y++)
-            for (int x = 0; x < h->cols; x++)
-                out[(size_t)y * h->cols + x] = ((bits[(size_t)y * h->wpr + (x >> 5)] >> (x & 31)) & 1) ? 255 : 0;
-        return ORBFE_OK;
-    }
-    if (stage == 104) { // the bit image the contour kernels of the last batch read (after the speck passes, if they ran)
-        std::vector<uint32_t> bits(h->bits_fu32);
-        ORBFE_HIP(hipMemcpy(bits.data(), (h->specks_ran ? h->d_bitsc : h->d_bits).as<uint32_t>() + (size_t)frame * h->bits_fu32, bits.size() * 4,
+        ORBFE_HIP(hipMemcpy(bits.data(), (stage == 104 && h->specks_ran ? h->d_bitsc : h->d_bits).as<uint32_t>() + (size_t)frame * h->bits_fu32, bits.size() * 4,
                             hipMemcpyDeviceToHost));
         for (int y = 0; y < h->rows; y++)
             for (int x = 0; x < h->cols; x++)
