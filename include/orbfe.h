@@ -22,6 +22,8 @@
  *   orbfe_search_for_initialization   ORBmatcher::SearchForInitialization  src/ORBmatcher.cc:409-524
  *   orbfe_initialize*   ORB_SLAM2::Initializer::Initialize src/Initializer.cc:44-121  (called from Tracking.cc:497-680)
  *                       Initializer::InitializeUseAruco    src/Initializer.cc:124-189 (Tracking.cc:632)
+ *   orbfe_pose_*        Optimizer::PoseOptimizationByAruco src/Optimizer.cc:522-770 (Tracking.cc:940, 1025, 1200, 1256, 1843)
+ *                       Optimizer::PoseOptimization        src/Optimizer.cc:308-520, monocular
  *
  * Memory convention: functions without a suffix take HOST pointers (drop-in for
  * the reference's call sites, which hand over cv::Mat / std::vector storage) and
@@ -460,6 +462,62 @@ int orbfe_initialize_check_poses(const orbfe_keypoint* kps1, int n1, const orbfe
 int orbfe_initialize_inspect(const orbfe_keypoint* kps1, int n1, const orbfe_keypoint* kps2, int n2, const int32_t* matches12,
                              const float* K4, float sigma, int iterations, const int32_t* rand_words, orbfe_init_result* res,
                              int32_t* nmatches, int32_t* sets, float* T12, float* pn1, float* pn2, float* models, float* scores, int device);
+
+/* ------------------------------------------------------------ motion-only pose optimization -- */
+/* Optimizer::PoseOptimizationByAruco(Frame*) (src/Optimizer.cc:522-770; every tracking path of Tracking.cc ends in it) and
+ * Optimizer::PoseOptimization(Frame*) without its stereo branch (:308-520; nm = 0): four rounds of 10 Levenberg-Marquardt iterations
+ * of the 6-DoF camera pose (g2o as ORB_SLAM2 vendors it, in double), each from the initial pose, with chi2 > 5.991 outlier
+ * classification of the monocular edges after every round and their Huber kernel (delta = sqrt(5.991)) dropped after round 2.
+ * Monocular edge i (has_mp[i] != 0): kps[i] = mvKeysUn[i] (x, y observed; octave picks inv_level_sigma2 = mvInvLevelSigma2),
+ * x3Dw[i] = the map point's world position (n x 3).  Marker edges (Frame::mbUArucoIni, and only for markers with !mvbOldAruco,
+ * mvbArucoGood and a MapAruco): four per marker record, corner k = mvArucoUn[4i + k] against Twm * get3DPointsLocalRefSystem(k),
+ * information marker_info * I (the reference's wei = 25), Huber in every round, numeric Jacobian (g2o's central differences).
+ * Poses are 3 x 4 row-major [R | t] floats (Tcw_in = mTcw, Tcw_out = what SetPose receives; they may be the same array).
+ * outlier[i] = mvbOutlier[i] for every i with has_mp[i]; entries without a map point are not written.  chi2 (may be NULL) = the
+ * chi2 of each monocular edge at the last classification (the value compared with 5.991).  With fewer than 3 monocular edges the
+ * call returns n_good = 0, writes outlier[i] = 0 for them and copies Tcw_in to Tcw_out (the reference leaves the pose untouched).
+ * An octave outside [0, nlevels) on an observation with a map point is ORBFE_ERR_INVALID.  nlevels <= 32.  Host pointers. */
+typedef struct orbfe_pose_marker {
+    float corners[8];           /* the four undistorted corners (x, y), mvArucoUn[4i .. 4i + 3] */
+    float Twm[12];              /* MapAruco::GetTwm(), 3 x 4 row-major */
+    float local[12];            /* get3DPointsLocalRefSystem(0 .. 3), the corners in the marker frame */
+} orbfe_pose_marker;
+
+typedef struct orbfe_pose_result {
+    int32_t n_good;             /* the return value: n_initial - nBad of the last round run (0 when n_initial < 3) */
+    int32_t n_initial;          /* nInitialCorrespondences: observations with a map point */
+    int32_t n_marker_edges;     /* 4 x the marker records used (0 when n_initial < 3) */
+    int32_t rounds;             /* rounds run: 4, 1 (fewer than 10 edges in all) or 0 (n_initial < 3) */
+    int32_t n_bad[4];           /* nBad of each round run */
+    int32_t iterations[4];      /* DIAGNOSTIC: LM iterations of each round run (-1: no active edge, optimize() returned -1) */
+    int32_t stale_mask;         /* DIAGNOSTIC: bit r = round r ended on a rejected trial (its inliers' chi2 read that trial's errors) */
+    int32_t status;             /* ORBFE_OK; the batch call: ORBFE_ERR_INVALID for a problem it skipped (see there) */
+} orbfe_pose_result;
+
+int orbfe_pose_optimization(const orbfe_keypoint* kps, int n, const uint8_t* has_mp, const float* x3Dw, const float* inv_level_sigma2,
+                            int nlevels, const float* K4, const orbfe_pose_marker* markers, int nm, float marker_info, const float* Tcw_in,
+                            float* Tcw_out, uint8_t* outlier, float* chi2, orbfe_pose_result* res, int device);
+
+/* The same over nframes problems resident on the device, one launch.  Frame f owns block f of `capacity` entries of d_kps (the
+ * layout of orbfe_extract_batch_device, d_n[f] valid), d_has_mp, d_x3Dw (x 3), d_outlier and d_chi2 (may be NULL), and block f
+ * of `mcapacity` marker records (d_nm[f] valid; d_markers / d_nm may be NULL when mcapacity = 0).  d_Tcw_in / d_Tcw_out: 12
+ * floats a frame (the same array works in place).  inv_level_sigma2, K4 and marker_info are read at the call.  A frame with an
+ * octave outside [0, nlevels) on an observation with a map point is skipped: its result record has status ORBFE_ERR_INVALID and
+ * every other field 0, its pose is copied, its outlier / chi2 entries are not written.  d_n / d_nm are clamped to the blocks.
+ * capacity x 25 B + mcapacity x 160 B + 2 KB must fit in a workgroup's LDS (ORBFE_ERR_CAPACITY otherwise: about 6 000 keypoints
+ * a frame on gfx950).  Asynchronous on `stream`; no scratch beyond the caller's buffers. */
+int orbfe_pose_optimization_batch_device(const orbfe_keypoint* d_kps, const int32_t* d_n, int capacity, int nframes, const uint8_t* d_has_mp,
+                                         const float* d_x3Dw, const orbfe_pose_marker* d_markers, const int32_t* d_nm, int mcapacity,
+                                         const float* inv_level_sigma2, int nlevels, const float* K4, float marker_info,
+                                         const float* d_Tcw_in, float* d_Tcw_out, uint8_t* d_outlier, float* d_chi2,
+                                         orbfe_pose_result* d_res, void* stream);
+
+/* The inputs of the batch call from what mode 2 of orbfe_search_by_projection_batch_device leaves on the device: for frame f and
+ * keypoint i < d_n[f], m = d_match_cur[f][i]; has_mp = 0 <= m < d_nq[f], x3Dw = d_q_x3Dw[f][m] (the world point of query m, blocks
+ * of qcapacity x 3 floats: the points the caller projected); entries without a match and those from d_n[f] to capacity get
+ * has_mp = 0, x3Dw = 0.  Asynchronous on `stream`. */
+int orbfe_pose_gather_device(const int32_t* d_match_cur, const int32_t* d_n, int capacity, int nframes, const float* d_q_x3Dw,
+                             const int32_t* d_nq, int qcapacity, uint8_t* d_has_mp, float* d_x3Dw, void* stream);
 
 /* MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:270-333; called after every new observation by Tracking,
  * LocalMapping and LoopClosing): for every map point, among the descriptors it was observed with (CSR: point p owns rows

@@ -57,6 +57,8 @@ SYMBOLS = [
     "orbfe_device_alloc", "orbfe_device_free", "orbfe_device_upload_rows", "orbfe_device_download",
     # the monocular initializer (csrc/initializer.hip)
     "orbfe_initialize", "orbfe_initialize_batch_device", "orbfe_initialize_check_poses", "orbfe_initialize_inspect",
+    # motion-only pose optimization (csrc/pose_optimizer.hip)
+    "orbfe_pose_optimization", "orbfe_pose_optimization_batch_device", "orbfe_pose_gather_device",
 ]
 
 _lib = None
@@ -192,6 +194,10 @@ def load():
         L.orbfe_initialize_inspect.argtypes = [vp, i32, vp, i32, vp, vp, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
         L.orbfe_initialize_check_poses.argtypes = [vp, i32, vp, i32, vp, vp, f32, vp, i32, vp, vp, vp, i32]
         L.orbfe_initialize_batch_device.argtypes = [vp, vp, i32, i32, vp, vp, f32, i32, vp, vp, vp, vp, vp]
+    if hasattr(L, "orbfe_pose_optimization"):
+        L.orbfe_pose_optimization.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, i32, f32, vp, vp, vp, vp, vp, i32]
+        L.orbfe_pose_optimization_batch_device.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, f32, vp, vp, vp, vp, vp, vp]
+        L.orbfe_pose_gather_device.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp]
     _lib = L
     return L
 
@@ -763,6 +769,66 @@ def initialize_batch_device(d_kps_ptr, d_n_ptr, capacity, npairs, d_matches12_pt
     _check(L, L.orbfe_initialize_batch_device(d_kps_ptr, d_n_ptr, int(capacity), int(npairs), d_matches12_ptr, _p(K4), float(sigma),
                                               int(iterations), d_rand_words_ptr, d_res_ptr, d_p3d_ptr, d_tri_ptr, stream),
            "orbfe_initialize_batch_device")
+
+
+# ------------------------------------------------------------------------------- pose optimization ----
+POSE_MARKER_DTYPE = np.dtype([("corners", "<f4", 8), ("Twm", "<f4", 12), ("local", "<f4", 12)])
+POSE_RESULT_DTYPE = np.dtype([("n_good", "<i4"), ("n_initial", "<i4"), ("n_marker_edges", "<i4"), ("rounds", "<i4"),
+                              ("n_bad", "<i4", 4), ("iterations", "<i4", 4), ("stale_mask", "<i4"), ("status", "<i4")])
+assert POSE_MARKER_DTYPE.itemsize == 128 and POSE_RESULT_DTYPE.itemsize == 56
+
+
+def _K4(K):
+    K = np.asarray(K, np.float32)
+    return np.ascontiguousarray([K[0, 0], K[1, 1], K[0, 2], K[1, 2]] if K.shape == (3, 3) else K.reshape(4), np.float32)
+
+
+def pose_optimization(kps, has_mp, x3Dw, inv_level_sigma2, K, Tcw, markers=None, marker_info=25.0, outlier=None, device=0):
+    """Optimizer::PoseOptimizationByAruco (Optimizer.cc:522-770) on the GPU; markers=None (or empty) is PoseOptimization without
+    its stereo branch.  kps: undistorted keypoints (KP_DTYPE); has_mp: n flags; x3Dw: n x 3 world points; inv_level_sigma2:
+    mvInvLevelSigma2; K: 3 x 3 or (fx, fy, cx, cy); Tcw: 3 x 4 [R | t]; markers: POSE_MARKER_DTYPE records.  outlier: n uint8 updated
+    in place where has_mp (a new zero array when None).  Returns (Tcw_out 3 x 4, outlier, chi2 (n floats: the last classification's,
+    NaN where not written), result record of POSE_RESULT_DTYPE)."""
+    L = load()
+    k = np.ascontiguousarray(kps, KP_DTYPE)
+    n = len(k)
+    has = np.ascontiguousarray(has_mp, np.uint8)
+    X = np.ascontiguousarray(x3Dw, np.float32).reshape(-1, 3)
+    if len(has) != n or len(X) != n:
+        raise ValueError("has_mp / x3Dw need one entry per keypoint")
+    sig = np.ascontiguousarray(inv_level_sigma2, np.float32)
+    mk = np.ascontiguousarray(np.zeros(0, POSE_MARKER_DTYPE) if markers is None else markers, POSE_MARKER_DTYPE)
+    T_in = np.ascontiguousarray(Tcw, np.float32).reshape(12)
+    T_out = np.zeros(12, np.float32)
+    out = np.zeros(n, np.uint8) if outlier is None else outlier
+    if out.dtype != np.uint8 or len(out) != n or not out.flags.c_contiguous:
+        raise ValueError("outlier must be a contiguous uint8 array of n entries")
+    chi2 = np.full(n, np.nan, np.float32)
+    res = np.zeros(1, POSE_RESULT_DTYPE)
+    _check(L, L.orbfe_pose_optimization(_ptr_or_none(k), n, _ptr_or_none(has), _ptr_or_none(X), _p(sig), len(sig), _p(_K4(K)),
+                                        _ptr_or_none(mk), len(mk), float(marker_info), _p(T_in), _p(T_out), _ptr_or_none(out),
+                                        _ptr_or_none(chi2), _p(res), device), "orbfe_pose_optimization")
+    return T_out.reshape(3, 4), out, chi2, res[0]
+
+
+def pose_optimization_batch_device(d_kps_ptr, d_n_ptr, capacity, nframes, d_has_mp_ptr, d_x3Dw_ptr, d_markers_ptr, d_nm_ptr, mcapacity,
+                                   inv_level_sigma2, K, marker_info, d_Tcw_in_ptr, d_Tcw_out_ptr, d_outlier_ptr, d_chi2_ptr, d_res_ptr,
+                                   stream=0):
+    """orbfe_pose_optimization_batch_device over nframes problems in `capacity` / `mcapacity` blocks (device pointers; d_markers /
+    d_nm / d_chi2 may be None).  Asynchronous on `stream`."""
+    L = load()
+    sig = np.ascontiguousarray(inv_level_sigma2, np.float32)
+    _check(L, L.orbfe_pose_optimization_batch_device(d_kps_ptr, d_n_ptr, int(capacity), int(nframes), d_has_mp_ptr, d_x3Dw_ptr,
+                                                     d_markers_ptr, d_nm_ptr, int(mcapacity), _p(sig), len(sig), _p(_K4(K)),
+                                                     float(marker_info), d_Tcw_in_ptr, d_Tcw_out_ptr, d_outlier_ptr, d_chi2_ptr,
+                                                     d_res_ptr, stream), "orbfe_pose_optimization_batch_device")
+
+
+def pose_gather_device(d_match_cur_ptr, d_n_ptr, capacity, nframes, d_q_x3Dw_ptr, d_nq_ptr, qcapacity, d_has_mp_ptr, d_x3Dw_ptr, stream=0):
+    """orbfe_pose_gather_device: has_mp / x3Dw blocks from mode 2's match_cur and the queries' world points (device pointers)."""
+    L = load()
+    _check(L, L.orbfe_pose_gather_device(d_match_cur_ptr, d_n_ptr, int(capacity), int(nframes), d_q_x3Dw_ptr, d_nq_ptr, int(qcapacity),
+                                         d_has_mp_ptr, d_x3Dw_ptr, stream), "orbfe_pose_gather_device")
 
 
 # ------------------------------------------------------------------------------------------ ArUco ----

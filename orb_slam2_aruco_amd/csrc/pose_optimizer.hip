@@ -1,0 +1,880 @@
+// pose_optimizer.hip -- motion-only pose optimization (Optimizer::PoseOptimizationByAruco / PoseOptimization, src/Optimizer.cc) on
+// gfx950.
+//
+// One workgroup of 256 threads per problem, one launch per batch (k_pose_opt), whatever the iteration and trial counts.  The
+// observations are staged in LDS (25 B each: observation, world point, information, flags; 160 B a marker).  The whole solve runs
+// in that workgroup, in double as g2o does: 4 rounds x up to 10 Levenberg-Marquardt iterations x up to 10 trials.
+//   - a linearisation pass: every lane evaluates its edges (slots tid, tid + 256, ...: the monocular edges by keypoint index, then
+//     the marker corners) -- error, Huber weight, Jacobian (analytic for mono edges, g2o's central differences for marker edges) --
+//     and sums the robust chi2, the 21 entries of H's upper triangle and b in registers; the 28 sums go through a fixed-order
+//     butterfly inside each wave and the four wave results are added in wave order by thread 0.  The order depends only on the
+//     problem, never on the batch it sits in;
+//   - thread 0 then does the 6 x 6 LDLT (diagonal pivoting), the exponential map and the lambda logic;
+//   - a trial pass per LM trial sums the robust chi2 at the trial pose, in the same order.
+// The edges' "cached" errors of g2o are not stored: they are the errors at the last pose the active edges were evaluated at (Tev),
+// recomputed bit for bit when the classification reads them.  After a round that ended on rejected trials Tev is the rejected
+// trial's pose, as the reference's stale errors are.
+#include "orbfe_common.hpp"
+#include <cfloat>
+#include <cmath>
+
+namespace orbfe {
+namespace {
+
+constexpr int PO_THREADS = 256;
+constexpr int PO_WAVES = PO_THREADS / 64;
+constexpr int PO_MAX_LEVELS = 32;
+constexpr int PO_NSUM = 28;   // robust chi2, H upper triangle (21), b (6)
+
+// ------------------------------------------------------------------------------------------ SE3Quat --
+struct Quat {
+    double x, y, z, w;
+};
+struct SE3 {
+    Quat q;
+    double t[3];
+    double pad;   // 64 B in LDS
+};
+
+__device__ __forceinline__ void normalize_rotation(Quat& q)
+{
+    if (q.w < 0) {
+        q.x *= -1; q.y *= -1; q.z *= -1; q.w *= -1;
+    }
+    const double n2 = q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w;
+    if (n2 > 0) {
+        const double n = sqrt(n2);
+        q.x /= n; q.y /= n; q.z /= n; q.w /= n;
+    }
+}
+
+// Eigen's Quaternion(const Matrix3&): the trace branch, else the largest diagonal entry
+__device__ Quat quat_from_matrix(const double (&m)[3][3])
+{
+    Quat q;
+    double t = m[0][0] + m[1][1] + m[2][2];
+    if (t > 0) {
+        t = sqrt(t + 1.0);
+        q.w = 0.5 * t;
+        t = 0.5 / t;
+        q.x = (m[2][1] - m[1][2]) * t;
+        q.y = (m[0][2] - m[2][0]) * t;
+        q.z = (m[1][0] - m[0][1]) * t;
+    } else {
+        int i = 0;
+        if (m[1][1] > m[0][0]) i = 1;
+        if (m[2][2] > m[i][i]) i = 2;
+        const int j = (i + 1) % 3, k = (j + 1) % 3;
+        double v[3];
+        t = sqrt(m[i][i] - m[j][j] - m[k][k] + 1.0);
+        v[i] = 0.5 * t;
+        t = 0.5 / t;
+        q.w = (m[k][j] - m[j][k]) * t;
+        v[j] = (m[j][i] + m[i][j]) * t;
+        v[k] = (m[k][i] + m[i][k]) * t;
+        q.x = v[0]; q.y = v[1]; q.z = v[2];
+    }
+    return q;
+}
+
+__device__ __forceinline__ void cross(const double (&a)[3], const double (&b)[3], double (&r)[3])
+{
+    r[0] = a[1] * b[2] - a[2] * b[1];
+    r[1] = a[2] * b[0] - a[0] * b[2];
+    r[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// q v = v + w uv + qv x uv, uv = 2 (qv x v)
+__device__ __forceinline__ void rotate(const Quat& q, const double (&v)[3], double (&r)[3])
+{
+    const double qv[3] = {q.x, q.y, q.z};
+    double uv[3], c[3];
+    cross(qv, v, uv);
+    for (int i = 0; i < 3; i++) uv[i] += uv[i];
+    cross(qv, uv, c);
+    for (int i = 0; i < 3; i++) r[i] = v[i] + q.w * uv[i] + c[i];
+}
+
+__device__ __forceinline__ SE3 mul(const SE3& a, const SE3& b)
+{
+    SE3 r = a;
+    double qt[3];
+    rotate(a.q, b.t, qt);
+    for (int i = 0; i < 3; i++) r.t[i] += qt[i];
+    r.q.w = a.q.w * b.q.w - a.q.x * b.q.x - a.q.y * b.q.y - a.q.z * b.q.z;
+    r.q.x = a.q.w * b.q.x + a.q.x * b.q.w + a.q.y * b.q.z - a.q.z * b.q.y;
+    r.q.y = a.q.w * b.q.y + a.q.y * b.q.w + a.q.z * b.q.x - a.q.x * b.q.z;
+    r.q.z = a.q.w * b.q.z + a.q.z * b.q.w + a.q.x * b.q.y - a.q.y * b.q.x;
+    normalize_rotation(r.q);
+    return r;
+}
+
+__device__ __forceinline__ void map(const SE3& T, const double (&p)[3], double (&r)[3])
+{
+    rotate(T.q, p, r);
+    for (int i = 0; i < 3; i++) r[i] += T.t[i];
+}
+
+__device__ SE3 se3_from_Rt(const double (&R)[3][3], const double (&t)[3])
+{
+    SE3 T;
+    T.q = quat_from_matrix(R);
+    for (int i = 0; i < 3; i++) T.t[i] = t[i];
+    T.pad = 0;
+    normalize_rotation(T.q);
+    return T;
+}
+
+// 3 x 4 row-major float -> SE3Quat (Converter::toSE3Quat)
+__device__ SE3 se3_from_float(const float* Rt)
+{
+    double R[3][3], t[3];
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) R[r][c] = Rt[r * 4 + c];
+        t[r] = Rt[r * 4 + 3];
+    }
+    return se3_from_Rt(R, t);
+}
+
+// SE3Quat::exp: the small-angle branch (theta < 1e-5) takes R = V = I + Omega + Omega^2
+__device__ SE3 se3_exp(const double (&u)[6])
+{
+    const double om0 = u[0], om1 = u[1], om2 = u[2];
+    const double theta = sqrt(om0 * om0 + om1 * om1 + om2 * om2);
+    const double O[3][3] = {{0, -om2, om1}, {om2, 0, -om0}, {-om1, om0, 0}};
+    double O2[3][3], R[3][3], V[3][3];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) O2[i][j] = O[i][0] * O[0][j] + O[i][1] * O[1][j] + O[i][2] * O[2][j];
+    if (theta < 0.00001) {
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) {
+                R[i][j] = ((i == j ? 1.0 : 0.0) + O[i][j]) + O2[i][j];
+                V[i][j] = R[i][j];
+            }
+    } else {
+        const double a = sin(theta) / theta, b = (1 - cos(theta)) / (theta * theta);
+        const double c = (theta - sin(theta)) / pow(theta, 3.0);
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) {
+                R[i][j] = ((i == j ? 1.0 : 0.0) + a * O[i][j]) + b * O2[i][j];
+                V[i][j] = ((i == j ? 1.0 : 0.0) + b * O[i][j]) + c * O2[i][j];
+            }
+    }
+    double t[3];
+    for (int i = 0; i < 3; i++) t[i] = V[i][0] * u[3] + V[i][1] * u[4] + V[i][2] * u[5];
+    return se3_from_Rt(R, t);
+}
+
+// Converter::toCvMat(SE3Quat): the rotation matrix of the quaternion (Eigen's toRotationMatrix), rounded to float
+__device__ void to_float(const SE3& T, float* Rt)
+{
+    const Quat& q = T.q;
+    const double tx = 2 * q.x, ty = 2 * q.y, tz = 2 * q.z;
+    const double twx = tx * q.w, twy = ty * q.w, twz = tz * q.w;
+    const double txx = tx * q.x, txy = ty * q.x, txz = tz * q.x;
+    const double tyy = ty * q.y, tyz = tz * q.y, tzz = tz * q.z;
+    const double R[9] = {1 - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1 - (txx + tzz), tyz - twx, txz - twy, tyz + twx, 1 - (txx + tyy)};
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) Rt[r * 4 + c] = (float)R[r * 3 + c];
+        Rt[r * 4 + 3] = (float)T.t[r];
+    }
+}
+
+// ------------------------------------------------------------------------------------------- edges --
+struct Cam {
+    double fx, fy, cx, cy;
+};
+
+__device__ __forceinline__ void project_error(const double (&Xc)[3], double ox, double oy, const Cam& K, double (&err)[2])
+{
+    err[0] = ox - ((Xc[0] / Xc[2]) * K.fx + K.cx);
+    err[1] = oy - ((Xc[1] / Xc[2]) * K.fy + K.cy);
+}
+
+// EdgeSE3ProjectXYZOnlyPose::linearizeOplus at the camera point Xc = T Xw
+__device__ __forceinline__ void mono_jacobian(const double (&Xc)[3], const Cam& K, double (&J)[2][6])
+{
+    const double x = Xc[0], y = Xc[1], invz = 1.0 / Xc[2], invz_2 = invz * invz;
+    J[0][0] = x * y * invz_2 * K.fx;
+    J[0][1] = -(1 + (x * x * invz_2)) * K.fx;
+    J[0][2] = y * invz * K.fx;
+    J[0][3] = -invz * K.fx;
+    J[0][4] = 0;
+    J[0][5] = x * invz_2 * K.fx;
+    J[1][0] = (1 + y * y * invz_2) * K.fy;
+    J[1][1] = -x * y * invz_2 * K.fy;
+    J[1][2] = -x * invz * K.fy;
+    J[1][3] = 0;
+    J[1][4] = -invz * K.fy;
+    J[1][5] = y * invz_2 * K.fy;
+}
+
+// EdgeMarker::computeError: obs - pi((T Twm) p)
+__device__ __forceinline__ void marker_error(const SE3& T, const SE3& Twm, const double (&p)[3], double ox, double oy, const Cam& K,
+                                             double (&err)[2])
+{
+    const SE3 Tcm = mul(T, Twm);
+    double Xc[3];
+    map(Tcm, p, Xc);
+    project_error(Xc, ox, oy, K, err);
+}
+
+// BaseBinaryEdge::linearizeOplus for the camera vertex: central differences through exp(+-1e-9 e_d) * T
+__device__ void marker_jacobian(const SE3& T, const SE3& Twm, const double (&p)[3], double ox, double oy, const Cam& K, double (&J)[2][6])
+{
+    const double delta = 1e-9, scalar = 1.0 / (2 * delta);
+    for (int d = 0; d < 6; d++) {
+        double u[6] = {0, 0, 0, 0, 0, 0}, ep[2], em[2];
+        u[d] = delta;
+        marker_error(mul(se3_exp(u), T), Twm, p, ox, oy, K, ep);
+        u[d] = -delta;
+        marker_error(mul(se3_exp(u), T), Twm, p, ox, oy, K, em);
+        J[0][d] = scalar * (ep[0] - em[0]);
+        J[1][d] = scalar * (ep[1] - em[1]);
+    }
+}
+
+__device__ __forceinline__ double chi2_of(const double (&e)[2], double info) { return e[0] * (info * e[0]) + e[1] * (info * e[1]); }
+
+// RobustKernelHuber::robustify: rho[0], rho[1]
+__device__ __forceinline__ void huber(double chi2, double delta, double (&rho)[2])
+{
+    const double dsqr = delta * delta;
+    if (chi2 <= dsqr) {
+        rho[0] = chi2;
+        rho[1] = 1.;
+    } else {
+        const double s = sqrt(chi2);
+        rho[0] = 2 * s * delta - dsqr;
+        rho[1] = delta / s;
+    }
+}
+
+// BaseUnaryEdge / BaseBinaryEdge::constructQuadraticForm for Omega = info I: H += J^T (rho' Omega) J, b += J^T rho' (-Omega e)
+__device__ __forceinline__ void add_edge(const double (&err)[2], const double (&J)[2][6], double info, double rho1, double (&s)[PO_NSUM])
+{
+    const double w = rho1 * info;
+    const double r0 = rho1 * -(info * err[0]), r1 = rho1 * -(info * err[1]);
+    int k = 1;
+    for (int a = 0; a < 6; a++)
+        for (int c = a; c < 6; c++, k++) s[k] += J[0][a] * (w * J[0][c]) + J[1][a] * (w * J[1][c]);
+    for (int a = 0; a < 6; a++) s[22 + a] += J[0][a] * r0 + J[1][a] * r1;
+}
+
+// ------------------------------------------------------------------------------------------ LDLT 6x6 --
+// Eigen's LDLT (lower triangle, diagonal pivoting on the largest remaining |diagonal|): isPositive() and x = H^-1 b (x untouched
+// when it is not)
+__device__ bool ldlt_solve(double (&m)[6][6], const double (&b)[6], double (&x)[6])
+{
+    const int n = 6;
+    int tr[6];
+    int sign = 0;   // 0 zero, 1 positive semidefinite, -1 negative semidefinite, 2 indefinite
+    for (int k = 0; k < n; k++) {
+        int big = k;
+        double bv = fabs(m[k][k]);
+        for (int i = k + 1; i < n; i++)
+            if (fabs(m[i][i]) > bv) {
+                bv = fabs(m[i][i]);
+                big = i;
+            }
+        tr[k] = big;
+        if (k != big) {
+            for (int j = 0; j < k; j++) {
+                const double t = m[k][j]; m[k][j] = m[big][j]; m[big][j] = t;
+            }
+            for (int i = big + 1; i < n; i++) {
+                const double t = m[i][k]; m[i][k] = m[i][big]; m[i][big] = t;
+            }
+            {
+                const double t = m[k][k]; m[k][k] = m[big][big]; m[big][big] = t;
+            }
+            for (int i = k + 1; i < big; i++) {
+                const double t = m[i][k];
+                m[i][k] = m[big][i];
+                m[big][i] = t;
+            }
+        }
+        if (k > 0) {
+            double temp[6];
+            for (int j = 0; j < k; j++) temp[j] = m[j][j] * m[k][j];
+            double s = 0;
+            for (int j = 0; j < k; j++) s += m[k][j] * temp[j];
+            m[k][k] -= s;
+            for (int i = k + 1; i < n; i++) {
+                double si = 0;
+                for (int j = 0; j < k; j++) si += m[i][j] * temp[j];
+                m[i][k] -= si;
+            }
+        }
+        const double akk = m[k][k];
+        const bool valid = fabs(akk) > 0;
+        if (k == 0 && !valid) {
+            sign = 0;
+            for (int j = 0; j < n; j++) tr[j] = j;
+            break;
+        }
+        if (valid)
+            for (int i = k + 1; i < n; i++) m[i][k] /= akk;
+        if (sign == 1) {
+            if (akk < 0) sign = 2;
+        } else if (sign == -1) {
+            if (akk > 0) sign = 2;
+        } else if (sign == 0) {
+            if (akk > 0) sign = 1;
+            else if (akk < 0) sign = -1;
+        }
+    }
+    if (!(sign == 1 || sign == 0)) return false;
+    double y[6];
+    for (int i = 0; i < n; i++) y[i] = b[i];
+    for (int k = 0; k < n; k++) {
+        const double t = y[k]; y[k] = y[tr[k]]; y[tr[k]] = t;
+    }
+    for (int i = 0; i < n; i++) {
+        double s = y[i];
+        for (int j = 0; j < i; j++) s -= m[i][j] * y[j];
+        y[i] = s;
+    }
+    for (int i = 0; i < n; i++) y[i] = fabs(m[i][i]) > DBL_MIN ? y[i] / m[i][i] : 0.0;
+    for (int i = n - 1; i >= 0; i--) {
+        double s = y[i];
+        for (int j = i + 1; j < n; j++) s -= m[j][i] * y[j];
+        y[i] = s;
+    }
+    for (int k = n - 1; k >= 0; k--) {
+        const double t = y[k]; y[k] = y[tr[k]]; y[tr[k]] = t;
+    }
+    for (int i = 0; i < n; i++) x[i] = y[i];
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------ the kernel --
+struct PoseArgs {
+    const orbfe_keypoint* kps;
+    const int32_t* n;
+    const uint8_t* has_mp;
+    const float* x3Dw;
+    const orbfe_pose_marker* markers;
+    const int32_t* nm;
+    const float* Tin;
+    float* Tout;
+    uint8_t* outlier;
+    float* chi2;
+    orbfe_pose_result* res;
+    int capacity, mcapacity, nlevels;
+    float fx, fy, cx, cy, marker_info;
+    double delta;                       // (double)(float)sqrt(5.991), as deltaMono reaches RobustKernelHuber::setDelta
+    float inv_sigma2[PO_MAX_LEVELS];
+};
+
+// thread 0's state, in LDS
+struct Ctl {
+    SE3 T, T0, Tev, Tsave;
+    double H[6][6], b[6], x[6];
+    double lambda, ni, currentChi, iniChi, rho;
+    int q, it, nbad_lm, ok2;
+    int cont, stop, nin, pad;
+};
+
+constexpr size_t al16(size_t b) { return (b + 15) & ~(size_t)15; }
+constexpr size_t PO_FIXED = al16(sizeof(Ctl)) + al16(sizeof(double) * PO_WAVES * PO_NSUM);
+
+size_t lds_bytes(int capacity, int mcapacity)
+{
+    const size_t cap = (size_t)capacity, mc = (size_t)mcapacity;
+    return PO_FIXED + al16(cap * 8) + al16(cap * 16) + al16(cap) + al16(mc * sizeof(SE3)) + al16(mc * 4 * 8) + al16(mc * 4 * 16);
+}
+
+// sum of N doubles over the workgroup: butterfly inside each wave, then the waves in order; the result is valid in thread 0
+template <int N> __device__ __forceinline__ void block_sum(double (&v)[N], double* red)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < N; k++) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) v[k] += __shfl_xor(v[k], off, 64);
+    }
+    if (lane == 0)
+        for (int k = 0; k < N; k++) red[w * N + k] = v[k];
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int k = 0; k < N; k++) {
+            double s = red[k];
+            for (int ww = 1; ww < PO_WAVES; ww++) s += red[ww * N + k];
+            v[k] = s;
+        }
+}
+
+__device__ __forceinline__ int block_count(int c, double* red)
+{
+    double v[1] = {(double)c};
+    block_sum<1>(v, red);
+    return (int)v[0];
+}
+
+__global__ __launch_bounds__(PO_THREADS) void k_pose_opt(PoseArgs a)
+{
+    extern __shared__ __align__(16) unsigned char po_smem[];
+    const int f = blockIdx.x, tid = threadIdx.x;
+    const int cap = a.capacity, mcap = a.mcapacity;
+    Ctl& c = *(Ctl*)po_smem;
+    double* red = (double*)(po_smem + al16(sizeof(Ctl)));
+    unsigned char* p = po_smem + PO_FIXED;
+    float2* s_obs = (float2*)p;
+    p += al16((size_t)cap * 8);
+    float4* s_xw = (float4*)p;   // X, Y, Z, information
+    p += al16((size_t)cap * 16);
+    uint8_t* s_st = p;           // bit 0: has a map point, bit 1: outlier (level 1)
+    p += al16((size_t)cap);
+    SE3* s_twm = (SE3*)p;
+    p += al16((size_t)mcap * sizeof(SE3));
+    float2* s_cobs = (float2*)p;
+    p += al16((size_t)mcap * 4 * 8);
+    float4* s_cpt = (float4*)p;
+
+    const int n = min(max(a.n[f], 0), cap);
+    const int nm = a.nm ? min(max(a.nm[f], 0), mcap) : 0;
+    const size_t base = (size_t)f * cap;
+    const Cam K{a.fx, a.fy, a.cx, a.cy};
+
+    // stage the problem
+    int cnt = 0, badoct = 0;
+    for (int i = tid; i < n; i += PO_THREADS) {
+        const orbfe_keypoint kp = a.kps[base + i];
+        const bool h = a.has_mp[base + i] != 0;
+        const bool okoct = kp.octave >= 0 && kp.octave < a.nlevels;
+        cnt += h;
+        badoct += h && !okoct;
+        s_obs[i] = make_float2(kp.x, kp.y);
+        const float* X = a.x3Dw + (base + i) * 3;
+        s_xw[i] = h ? make_float4(X[0], X[1], X[2], okoct ? a.inv_sigma2[kp.octave] : 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
+        s_st[i] = h ? 1 : 0;
+    }
+    for (int j = tid; j < 4 * nm; j += PO_THREADS) {
+        const orbfe_pose_marker& mk = a.markers[(size_t)f * mcap + j / 4];
+        const int k = j & 3;
+        s_cobs[j] = make_float2(mk.corners[2 * k], mk.corners[2 * k + 1]);
+        s_cpt[j] = make_float4(mk.local[3 * k], mk.local[3 * k + 1], mk.local[3 * k + 2], 0.f);
+    }
+    for (int m = tid; m < nm; m += PO_THREADS) s_twm[m] = se3_from_float(a.markers[(size_t)f * mcap + m].Twm);
+    const int n_initial = block_count(cnt, red);
+    const int nbadoct = block_count(badoct, red + PO_WAVES);
+    if (tid == 0) {
+        c.nin = n_initial;
+        c.stop = nbadoct;
+    }
+    __syncthreads();
+    const int n0 = c.nin;
+    if (c.stop) {
+        // an octave outside [0, nlevels): the problem is skipped
+        if (tid == 0) {
+            orbfe_pose_result r{};
+            r.status = ORBFE_ERR_INVALID;
+            a.res[f] = r;
+        }
+        if (tid < 12) a.Tout[(size_t)f * 12 + tid] = a.Tin[(size_t)f * 12 + tid];
+        return;
+    }
+    if (n0 < 3) {
+        for (int i = tid; i < n; i += PO_THREADS)
+            if (s_st[i]) a.outlier[base + i] = 0;
+        if (tid == 0) {
+            orbfe_pose_result r{};
+            r.n_initial = n0;
+            a.res[f] = r;
+        }
+        if (tid < 12) a.Tout[(size_t)f * 12 + tid] = a.Tin[(size_t)f * 12 + tid];
+        return;
+    }
+    if (tid == 0) c.T0 = se3_from_float(a.Tin + (size_t)f * 12);
+    const int nedges = n0 + 4 * nm;
+    int n_bad[4] = {0, 0, 0, 0}, iters[4] = {0, 0, 0, 0}, stale = 0, rounds = 0;
+    __syncthreads();
+
+    for (int round = 0; round < 4; round++) {
+        const bool mono_kernel = round < 3;
+        if (tid == 0) {
+            c.T = c.T0;
+            c.lambda = 0;
+            c.ni = 2;
+            c.nbad_lm = 0;
+            c.rho = 0;
+            for (int j = 0; j < 6; j++) c.x[j] = 0;
+        }
+        __syncthreads();
+        int round_iters = -1;
+        bool round_stale = false;
+        if (c.nin + 4 * nm > 0) {
+            for (int it = 0; it < 10;) {
+                // linearisation pass at T: robust chi2, H, b
+                {
+                    const SE3 T = c.T;
+                    double s[PO_NSUM];
+                    for (int k = 0; k < PO_NSUM; k++) s[k] = 0;
+                    for (int i = tid; i < n; i += PO_THREADS) {
+                        if (s_st[i] != 1) continue;
+                        const float2 o = s_obs[i];
+                        const float4 xw = s_xw[i];
+                        const double Xw[3] = {xw.x, xw.y, xw.z};
+                        double Xc[3], err[2], J[2][6], rho[2] = {0, 1};
+                        map(T, Xw, Xc);
+                        project_error(Xc, o.x, o.y, K, err);
+                        mono_jacobian(Xc, K, J);
+                        const double ch = chi2_of(err, xw.w);
+                        if (mono_kernel) {
+                            huber(ch, a.delta, rho);
+                            s[0] += rho[0];
+                        } else {
+                            s[0] += ch;
+                        }
+                        add_edge(err, J, xw.w, rho[1], s);
+                    }
+                    for (int j = tid; j < 4 * nm; j += PO_THREADS) {
+                        const float2 o = s_cobs[j];
+                        const float4 pt = s_cpt[j];
+                        const double pm[3] = {pt.x, pt.y, pt.z};
+                        const SE3 Twm = s_twm[j >> 2];
+                        double err[2], J[2][6], rho[2];
+                        marker_error(T, Twm, pm, o.x, o.y, K, err);
+                        marker_jacobian(T, Twm, pm, o.x, o.y, K, J);
+                        huber(chi2_of(err, (double)a.marker_info), a.delta, rho);
+                        s[0] += rho[0];
+                        add_edge(err, J, (double)a.marker_info, rho[1], s);
+                    }
+                    block_sum<PO_NSUM>(s, red);
+                    if (tid == 0) {
+                        c.Tev = c.T;
+                        c.currentChi = c.iniChi = s[0];
+                        int k = 1;
+                        for (int r = 0; r < 6; r++)
+                            for (int cc = r; cc < 6; cc++, k++) c.H[r][cc] = c.H[cc][r] = s[k];
+                        for (int r = 0; r < 6; r++) c.b[r] = s[22 + r];
+                        if (it == 0) {
+                            double md = 0;
+                            for (int j = 0; j < 6; j++) md = fmax(fabs(c.H[j][j]), md);
+                            c.lambda = 1e-5 * md;
+                            c.ni = 2;
+                            c.nbad_lm = 0;
+                        }
+                        c.rho = 0;
+                        c.q = 0;
+                    }
+                }
+                // trials
+                for (;;) {
+                    if (tid == 0) {
+                        c.Tsave = c.T;
+                        double Hl[6][6], x[6];
+                        for (int r = 0; r < 6; r++)
+                            for (int cc = 0; cc < 6; cc++) Hl[r][cc] = c.H[r][cc];
+                        for (int j = 0; j < 6; j++) Hl[j][j] += c.lambda;
+                        for (int j = 0; j < 6; j++) x[j] = c.x[j];
+                        c.ok2 = ldlt_solve(Hl, c.b, x) ? 1 : 0;
+                        for (int j = 0; j < 6; j++) c.x[j] = x[j];
+                        c.T = mul(se3_exp(x), c.T);
+                    }
+                    __syncthreads();
+                    const SE3 T = c.T;
+                    double s[1] = {0};
+                    for (int i = tid; i < n; i += PO_THREADS) {
+                        if (s_st[i] != 1) continue;
+                        const float2 o = s_obs[i];
+                        const float4 xw = s_xw[i];
+                        const double Xw[3] = {xw.x, xw.y, xw.z};
+                        double Xc[3], err[2], rho[2];
+                        map(T, Xw, Xc);
+                        project_error(Xc, o.x, o.y, K, err);
+                        const double ch = chi2_of(err, xw.w);
+                        if (mono_kernel) {
+                            huber(ch, a.delta, rho);
+                            s[0] += rho[0];
+                        } else {
+                            s[0] += ch;
+                        }
+                    }
+                    for (int j = tid; j < 4 * nm; j += PO_THREADS) {
+                        const float2 o = s_cobs[j];
+                        const float4 pt = s_cpt[j];
+                        const double pm[3] = {pt.x, pt.y, pt.z};
+                        double err[2], rho[2];
+                        marker_error(T, s_twm[j >> 2], pm, o.x, o.y, K, err);
+                        huber(chi2_of(err, (double)a.marker_info), a.delta, rho);
+                        s[0] += rho[0];
+                    }
+                    block_sum<1>(s, red);
+                    if (tid == 0) {
+                        c.Tev = c.T;
+                        double tempChi = s[0];
+                        if (!c.ok2) tempChi = DBL_MAX;
+                        double rho = c.currentChi - tempChi;
+                        double scale = 0;
+                        for (int j = 0; j < 6; j++) scale += c.x[j] * (c.lambda * c.x[j] + c.b[j]);
+                        scale += 1e-3;
+                        rho /= scale;
+                        if (rho > 0 && isfinite(tempChi)) {
+                            double alpha = 1. - pow((2 * rho - 1), 3.0);
+                            alpha = fmin(alpha, 2. / 3.);
+                            const double sf = fmax(1. / 3., alpha);
+                            c.lambda *= sf;
+                            c.ni = 2;
+                            c.currentChi = tempChi;
+                            c.ok2 = 2;   // accepted
+                        } else {
+                            c.lambda *= c.ni;
+                            c.ni *= 2;
+                            c.T = c.Tsave;
+                            c.ok2 = 3;   // rejected
+                        }
+                        c.rho = rho;
+                        c.q++;
+                        c.cont = rho < 0 && c.q < 10;
+                    }
+                    __syncthreads();
+                    if (!c.cont) break;
+                }
+                it++;
+                if (tid == 0) {
+                    bool stop = c.q == 10 || c.rho == 0;
+                    if (!stop) {
+                        if ((c.iniChi - c.currentChi) * 1e3 < c.iniChi) c.nbad_lm++;
+                        else c.nbad_lm = 0;
+                        stop = c.nbad_lm >= 3;
+                    }
+                    c.stop = stop;
+                }
+                __syncthreads();
+                round_iters = it;
+                round_stale = c.ok2 == 3;
+                if (c.stop) break;
+            }
+        }
+        // classification: the inliers read the errors at Tev, the outliers compute theirs at T
+        {
+            const SE3 T = c.T, Tev = c.Tev;
+            int nb = 0;
+            for (int i = tid; i < n; i += PO_THREADS) {
+                const uint8_t st = s_st[i];
+                if (!(st & 1)) continue;
+                const float2 o = s_obs[i];
+                const float4 xw = s_xw[i];
+                const double Xw[3] = {xw.x, xw.y, xw.z};
+                double Xc[3], err[2];
+                map((st & 2) ? T : Tev, Xw, Xc);
+                project_error(Xc, o.x, o.y, K, err);
+                const double ch = chi2_of(err, xw.w);
+                const bool out = (float)ch > 5.991f;
+                nb += out;
+                s_st[i] = out ? 3 : 1;
+                if (a.chi2) a.chi2[base + i] = (float)ch;
+            }
+            nb = block_count(nb, red);
+            if (tid == 0) c.nin = n0 - nb;
+            n_bad[round] = nb;   // valid in thread 0
+        }
+        iters[round] = round_iters;
+        stale |= round_stale ? 1 << round : 0;
+        rounds = round + 1;
+        __syncthreads();
+        if (nedges < 10) break;
+    }
+    for (int i = tid; i < n; i += PO_THREADS)
+        if (s_st[i] & 1) a.outlier[base + i] = (s_st[i] & 2) ? 1 : 0;
+    if (tid == 0) {
+        orbfe_pose_result r{};
+        r.n_initial = n0;
+        r.n_marker_edges = 4 * nm;
+        r.rounds = rounds;
+        for (int k = 0; k < 4; k++) {
+            r.n_bad[k] = k < rounds ? n_bad[k] : 0;
+            r.iterations[k] = k < rounds ? iters[k] : 0;
+        }
+        r.n_good = n0 - n_bad[rounds - 1];
+        r.stale_mask = stale;
+        r.status = ORBFE_OK;
+        a.res[f] = r;
+        float Tf[12];
+        to_float(c.T, Tf);
+        for (int k = 0; k < 12; k++) a.Tout[(size_t)f * 12 + k] = Tf[k];
+    }
+}
+
+// has_mp / x3Dw from mode 2's match_cur and the queries' world points
+__global__ void k_pose_gather(const int32_t* match_cur, const int32_t* nk, int capacity, const float* q_x3Dw, const int32_t* nq,
+                              int qcapacity, uint8_t* has_mp, float* x3Dw)
+{
+    const int f = blockIdx.y;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= capacity) return;
+    const size_t o = (size_t)f * capacity + i;
+    const int n = nk[f], nqf = min(nq[f], qcapacity);
+    const int m = i < n ? match_cur[o] : -1;
+    const bool h = m >= 0 && m < nqf;
+    has_mp[o] = h ? 1 : 0;
+    const float* X = q_x3Dw + ((size_t)f * qcapacity + (h ? m : 0)) * 3;
+    x3Dw[o * 3 + 0] = h ? X[0] : 0.f;
+    x3Dw[o * 3 + 1] = h ? X[1] : 0.f;
+    x3Dw[o * 3 + 2] = h ? X[2] : 0.f;
+}
+
+// ------------------------------------------------------------------------------------------- host --
+int max_lds()
+{
+    static int v = 0;
+    if (!v) {
+        int dev = 0, b = 0;
+        (void)hipGetDevice(&dev);
+        v = hipDeviceGetAttribute(&b, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) == hipSuccess && b > 0 ? b : 65536;
+    }
+    return v;
+}
+
+int fill_args(PoseArgs& a, const float* inv_sigma2, int nlevels, const float* K4, float marker_info, const char* name)
+{
+    if (!K4 || !inv_sigma2 || nlevels <= 0 || nlevels > PO_MAX_LEVELS) return fail(ORBFE_ERR_INVALID, "%s: invalid K4 / sigma table", name);
+    for (int i = 0; i < 4; i++)
+        if (!std::isfinite(K4[i])) return fail(ORBFE_ERR_INVALID, "%s: K is not finite", name);
+    if (K4[0] == 0 || K4[1] == 0) return fail(ORBFE_ERR_INVALID, "%s: fx or fy is 0", name);
+    if (!std::isfinite(marker_info)) return fail(ORBFE_ERR_INVALID, "%s: marker_info is not finite", name);
+    a.nlevels = nlevels;
+    for (int l = 0; l < PO_MAX_LEVELS; l++) a.inv_sigma2[l] = l < nlevels ? inv_sigma2[l] : 0.f;
+    a.fx = K4[0]; a.fy = K4[1]; a.cx = K4[2]; a.cy = K4[3];
+    a.marker_info = marker_info;
+    a.delta = (double)(float)std::sqrt(5.991);
+    return ORBFE_OK;
+}
+
+int launch(const PoseArgs& a, int nframes, hipStream_t s, const char* name)
+{
+    const size_t lds = lds_bytes(a.capacity, a.mcapacity);
+    if (lds > (size_t)max_lds())
+        return fail(ORBFE_ERR_CAPACITY, "%s: capacity %d / mcapacity %d need %zu B of LDS (at most %d)", name, a.capacity, a.mcapacity, lds, max_lds());
+    int rc = ensure_dyn_lds((const void*)k_pose_opt, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_pose_opt, dim3(nframes), dim3(PO_THREADS), lds, s, a);
+    ORBFE_HIP(hipGetLastError());
+    return ORBFE_OK;
+}
+
+struct PoseWorkspace {
+    DevBuf io;
+    PinnedBuf pinned;
+    hipStream_t stream = nullptr;
+    ~PoseWorkspace()
+    {
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+ThreadWorkspaces<PoseWorkspace>& pose_spaces()
+{
+    static thread_local ThreadWorkspaces<PoseWorkspace> w;
+    return w;
+}
+
+size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
+
+} // namespace
+} // namespace orbfe
+
+using namespace orbfe;
+
+extern "C" int orbfe_pose_optimization(const orbfe_keypoint* kps, int n, const uint8_t* has_mp, const float* x3Dw,
+                                       const float* inv_level_sigma2, int nlevels, const float* K4, const orbfe_pose_marker* markers, int nm,
+                                       float marker_info, const float* Tcw_in, float* Tcw_out, uint8_t* outlier, float* chi2,
+                                       orbfe_pose_result* res, int device)
+{
+    static const char* name = "orbfe_pose_optimization";
+    if (n < 0 || nm < 0 || !Tcw_in || !Tcw_out || !res || (n && (!kps || !has_mp || !x3Dw || !outlier)) || (nm && !markers))
+        return fail(ORBFE_ERR_INVALID, "%s: invalid argument", name);
+    PoseArgs a{};
+    int rc = fill_args(a, inv_level_sigma2, nlevels, K4, marker_info, name);
+    if (rc) return rc;
+    for (int i = 0; i < n; i++)
+        if (has_mp[i] && (kps[i].octave < 0 || kps[i].octave >= nlevels))
+            return fail(ORBFE_ERR_INVALID, "%s: keypoint %d has octave %d, outside [0, %d)", name, i, kps[i].octave, nlevels);
+    for (int i = 0; i < 12; i++)
+        if (!std::isfinite(Tcw_in[i])) return fail(ORBFE_ERR_INVALID, "%s: Tcw_in is not finite", name);
+    if ((rc = use_device(device))) return rc;
+    PoseWorkspace& w = pose_spaces().get();
+    if (!w.stream) ORBFE_HIP(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
+    const hipStream_t s = w.stream;
+    const size_t cap = (size_t)std::max(n, 1), mc = (size_t)std::max(nm, 1);
+    // device io: [kps | has | x3Dw | markers | n, nm | Tin] [Tout | res | outlier | chi2]
+    const size_t i_kps = 0, i_has = al(cap * sizeof(orbfe_keypoint)), i_x = i_has + al(cap), i_mk = i_x + al(cap * 12);
+    const size_t i_n = i_mk + al(mc * sizeof(orbfe_pose_marker)), i_T = i_n + 256, i_end = i_T + 256;
+    const size_t o_T = i_end, o_res = o_T + 256, o_out = o_res + al(sizeof(orbfe_pose_result)), o_chi = o_out + al(cap);
+    const size_t o_end = o_chi + al(cap * 4);
+    if ((rc = w.io.ensure(o_end)) || (rc = w.pinned.ensure(o_end))) return rc;
+    uint8_t* hp = w.pinned.as<uint8_t>();
+    uint8_t* dp = w.io.as<uint8_t>();
+    if (n) {
+        memcpy(hp + i_kps, kps, (size_t)n * sizeof(orbfe_keypoint));
+        memcpy(hp + i_has, has_mp, (size_t)n);
+        memcpy(hp + i_x, x3Dw, (size_t)n * 12);
+    }
+    if (nm) memcpy(hp + i_mk, markers, (size_t)nm * sizeof(orbfe_pose_marker));
+    const int32_t nn[2] = {n, nm};
+    memcpy(hp + i_n, nn, 8);
+    memcpy(hp + i_T, Tcw_in, 48);
+    ORBFE_HIP(hipMemcpyAsync(dp, hp, i_end, hipMemcpyHostToDevice, s));
+    a.kps = (const orbfe_keypoint*)(dp + i_kps);
+    a.has_mp = dp + i_has;
+    a.x3Dw = (const float*)(dp + i_x);
+    a.markers = (const orbfe_pose_marker*)(dp + i_mk);
+    a.n = (const int32_t*)(dp + i_n);
+    a.nm = (const int32_t*)(dp + i_n) + 1;
+    a.Tin = (const float*)(dp + i_T);
+    a.Tout = (float*)(dp + o_T);
+    a.res = (orbfe_pose_result*)(dp + o_res);
+    a.outlier = dp + o_out;
+    a.chi2 = (float*)(dp + o_chi);
+    a.capacity = (int)cap;
+    a.mcapacity = (int)mc;
+    if ((rc = launch(a, 1, s, name))) return rc;
+    ORBFE_HIP(hipMemcpyAsync(hp + o_T, dp + o_T, o_end - o_T, hipMemcpyDeviceToHost, s));
+    ORBFE_HIP(hipStreamSynchronize(s));
+    memcpy(Tcw_out, hp + o_T, 48);
+    *res = *(const orbfe_pose_result*)(hp + o_res);
+    // only the entries with a map point were written
+    const uint8_t* ho = hp + o_out;
+    const float* hc = (const float*)(hp + o_chi);
+    const bool classified = res->rounds > 0;
+    for (int i = 0; i < n; i++)
+        if (has_mp[i]) {
+            outlier[i] = ho[i];
+            if (chi2 && classified) chi2[i] = hc[i];
+        }
+    return ORBFE_OK;
+}
+
+extern "C" int orbfe_pose_optimization_batch_device(const orbfe_keypoint* d_kps, const int32_t* d_n, int capacity, int nframes,
+                                                    const uint8_t* d_has_mp, const float* d_x3Dw, const orbfe_pose_marker* d_markers,
+                                                    const int32_t* d_nm, int mcapacity, const float* inv_level_sigma2, int nlevels,
+                                                    const float* K4, float marker_info, const float* d_Tcw_in, float* d_Tcw_out,
+                                                    uint8_t* d_outlier, float* d_chi2, orbfe_pose_result* d_res, void* stream)
+{
+    static const char* name = "orbfe_pose_optimization_batch_device";
+    if (!d_kps || !d_n || !d_has_mp || !d_x3Dw || !d_Tcw_in || !d_Tcw_out || !d_outlier || !d_res || capacity <= 0 || nframes <= 0 ||
+        mcapacity < 0 || (mcapacity > 0 && (!d_markers || !d_nm)))
+        return fail(ORBFE_ERR_INVALID, "%s: invalid argument", name);
+    PoseArgs a{};
+    int rc = fill_args(a, inv_level_sigma2, nlevels, K4, marker_info, name);
+    if (rc) return rc;
+    a.kps = d_kps; a.n = d_n; a.has_mp = d_has_mp; a.x3Dw = d_x3Dw;
+    a.markers = mcapacity > 0 ? d_markers : nullptr;
+    a.nm = mcapacity > 0 ? d_nm : nullptr;
+    a.Tin = d_Tcw_in; a.Tout = d_Tcw_out; a.outlier = d_outlier; a.chi2 = d_chi2; a.res = d_res;
+    a.capacity = capacity;
+    a.mcapacity = mcapacity;
+    return launch(a, nframes, (hipStream_t)stream, name);
+}
+
+extern "C" int orbfe_pose_gather_device(const int32_t* d_match_cur, const int32_t* d_n, int capacity, int nframes, const float* d_q_x3Dw,
+                                        const int32_t* d_nq, int qcapacity, uint8_t* d_has_mp, float* d_x3Dw, void* stream)
+{
+    if (!d_match_cur || !d_n || !d_q_x3Dw || !d_nq || !d_has_mp || !d_x3Dw || capacity <= 0 || nframes <= 0 || qcapacity <= 0 || nframes > 65535)
+        return fail(ORBFE_ERR_INVALID, "orbfe_pose_gather_device: invalid argument");
+    hipLaunchKernelGGL(k_pose_gather, dim3((capacity + 255) / 256, nframes), dim3(256), 0, (hipStream_t)stream, d_match_cur, d_n, capacity,
+                       d_q_x3Dw, d_nq, qcapacity, d_has_mp, d_x3Dw);
+    ORBFE_HIP(hipGetLastError());
+    return ORBFE_OK;
+}

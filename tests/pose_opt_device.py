@@ -1,0 +1,51 @@
+"""Device buffers for the pose optimization GPU tests and tools/pose_opt_timing.py, through the library's own allocator
+(orbfe_device_alloc / _upload_rows / _download: ordinary HIP device pointers of the library's runtime; the download is blocking, so
+it also waits for work enqueued on the null stream)."""
+import ctypes as C
+
+import numpy as np
+
+from orb_slam2_aruco_amd import binding
+
+_L = None
+
+
+def _lib():
+    global _L
+    if _L is None:
+        L = binding.load()
+        vp = C.c_void_p
+        L.orbfe_device_alloc.argtypes = [C.c_int, C.c_size_t]
+        L.orbfe_device_alloc.restype = vp
+        L.orbfe_device_free.argtypes = [vp]
+        L.orbfe_device_free.restype = None
+        L.orbfe_device_upload_rows.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_size_t]
+        L.orbfe_device_download.argtypes = [vp, vp, C.c_size_t]
+        _L = L
+    return _L
+
+
+class Dev:
+    """A device copy of a numpy array (same dtype and shape)."""
+
+    def __init__(self, a):
+        L = _lib()
+        self.a = np.ascontiguousarray(a)
+        self.nbytes = max(self.a.nbytes, 1)
+        self.ptr = L.orbfe_device_alloc(0, self.nbytes)
+        if not self.ptr:
+            raise RuntimeError("orbfe_device_alloc: %s" % L.orbfe_last_error().decode())
+        if self.a.nbytes and L.orbfe_device_upload_rows(self.ptr, self.a.nbytes, self.a.ctypes.data_as(C.c_void_p), self.a.nbytes,
+                                                        self.a.nbytes, 1) != 0:
+            raise RuntimeError("orbfe_device_upload_rows: %s" % L.orbfe_last_error().decode())
+
+    def get(self):
+        out = np.empty_like(self.a)
+        if out.nbytes and _lib().orbfe_device_download(out.ctypes.data_as(C.c_void_p), self.ptr, out.nbytes) != 0:
+            raise RuntimeError("orbfe_device_download: %s" % _lib().orbfe_last_error().decode())
+        return out
+
+    def __del__(self):
+        if getattr(self, "ptr", None) and _L is not None:
+            _L.orbfe_device_free(self.ptr)
+            self.ptr = None
