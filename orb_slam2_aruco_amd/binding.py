@@ -27,7 +27,7 @@ SYMBOLS = [
     "orbfe_extractor_max_keypoints", "orbfe_extract", "orbfe_extract_batch", "orbfe_extract_batch_device",
     "orbfe_extractor_batch_status", "orbfe_search_for_initialization_batch_status", "orbfe_extractor_set_gaussian_taps",
     "orbfe_extractor_debug_level_size", "orbfe_extractor_debug_level_image",
-    "orbfe_extractor_debug_level_keypoints", "orbfe_extractor_debug_kernel_times", "orbfe_extractor_debug_control", "orbfe_extractor_set_aux_stream", "orbfe_extractor_set_early_stream", "orbfe_extractor_follow", "orbfe_extractor_stage_wait", "orbfe_extractor_pair_detector",
+    "orbfe_extractor_debug_level_keypoints", "orbfe_extractor_debug_kernel_times", "orbfe_extractor_debug_control", "orbfe_extractor_set_aux_stream", "orbfe_extractor_follow", "orbfe_extractor_stage_wait", "orbfe_extractor_pair_detector",
     "orbfe_debug_control", "orbfe_hamming", "orbfe_three_maxima", "orbfe_epipolar_distance_ok", "orbfe_knn2", "orbfe_knn2_csr", "orbfe_knn2_batch_device", "orbfe_search_for_initialization",
     "orbfe_search_for_initialization_batch_device", "orbfe_search_by_projection",
     "orbfe_undistort_points", "orbfe_undistort_keypoints_batch_device", "orbfe_compute_image_bounds",
@@ -100,7 +100,6 @@ def load():
     L.orbfe_extractor_debug_level_keypoints.argtypes = [vp, i32, i32, i32, vp, i32, vp]
     L.orbfe_extractor_debug_kernel_times.argtypes = [vp, vp, i32]
     L.orbfe_extractor_debug_control.argtypes = [vp, C.c_char_p, i32]
-    L.orbfe_extractor_set_early_stream.argtypes = [vp, vp]
     L.orbfe_extractor_follow.argtypes = [vp, vp, i32]
     L.orbfe_extractor_stage_wait.argtypes = [vp, i32, vp]
     L.orbfe_extractor_pair_detector.argtypes = [vp, vp]
@@ -350,10 +349,6 @@ class ORBextractor:
         _check(self.L, self.L.orbfe_extractor_follow(self.h, other.h if other is not None else None, int(stage)), "follow")
         self._followed = other
 
-    def set_early_stream(self, stream_ptr):
-        """Run the extractor's launch that needs no pyramid (FAST of level 0) on the caller's stream (None: the handle's own)."""
-        _check(self.L, self.L.orbfe_extractor_set_early_stream(self.h, stream_ptr), "set_early_stream")
-
     def debug_control(self, key, value):
         """orbfe_extractor_debug_control: a named test / diagnosis switch of this handle (include/orbfe.h lists the keys)."""
         _check(self.L, self.L.orbfe_extractor_debug_control(self.h, key.encode(), int(value)), "extractor_debug_control")
@@ -381,13 +376,11 @@ class ORBextractor:
 
     # order of kernel_times_us(); blur7 runs on the extractor's second stream, concurrently with fast_cells + distribute
     STAGES = ["resize", "blur7", "fast_cells", "distribute", "orient_describe"]
-    # with FAST of level 0 on its own stream from the start of the batch (the default): its interval comes first, and
-    # "fast_cells" is the launch over levels >= 1
-    STAGES_L0 = ["fast_cells_l0"] + STAGES
 
     @classmethod
     def stage_names(cls, n):
-        return cls.STAGES_L0 if n == len(cls.STAGES_L0) else cls.STAGES
+        """The names of n stage times (every batch times the same stages: STAGES)."""
+        return cls.STAGES
 
     def kernel_times_us(self, median=False):
         """Stage times of the last batch, or (median=True) the per-stage median over the batches since timing was enabled."""

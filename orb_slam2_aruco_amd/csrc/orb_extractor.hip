@@ -68,35 +68,8 @@ struct orbfe_extractor {
     PinnedBuf pinned;               // staging of the host-pointer entry points
     orbfe_aruco* paired = nullptr;  // orbfe_extractor_pair_detector
     hipEvent_t ev_up = nullptr;     // the image of the host-pointer call is on the device
-    // hipGraph replay of the host-pointer call (orbfe_extract_batch).  Built for VERDICT item 7 and measured: the capture works (inside
-    // the library, on its own streams; torch's capture API had segfaulted in round 2), the results are identical -- and the call is
-    // no faster (0.207 against 0.206 ms per 640 x 480 frame, profiles/r03_latency_graph.txt): the 13 launches of a frame are back to
-    // back on the GPU already, what a graph saves is host time that is not on the critical path.  Off by default (ORBFE_GRAPH=1).
-    bool use_graph = env_int("ORBFE_GRAPH", 0) != 0;
-    hipGraphExec_t g_exec = nullptr;
-    uint64_t g_key = 0;
-    int g_seen = 0;
-    void drop_graph()
-    {
-        if (g_exec) (void)hipGraphExecDestroy(g_exec);
-        g_exec = nullptr;
-    }
-    // everything that decides a launch parameter or a buffer address of the host-pointer call
-    uint64_t graph_key(int nframes, int rows_, int cols_, const void* hp) const
-    {
-        uint64_t k = 1469598103934665603ull;
-        auto mix = [&](uint64_t v) { k = (k ^ v) * 1099511628211ull; };
-        mix((uint64_t)nframes); mix((uint64_t)rows_); mix((uint64_t)cols_); mix((uint64_t)(uintptr_t)hp);
-        mix((uint64_t)(uintptr_t)d_in.p); mix((uint64_t)(uintptr_t)d_kps.p); mix((uint64_t)(uintptr_t)d_desc.p); mix((uint64_t)(uintptr_t)d_nout.p);
-        mix((uint64_t)(uintptr_t)d_pyr.p); mix((uint64_t)(uintptr_t)d_blur.p); mix((uint64_t)(uintptr_t)d_slots.p); mix((uint64_t)(uintptr_t)d_keys.p);
-        mix((uint64_t)(uintptr_t)d_flatkv.p); mix((uint64_t)(uintptr_t)d_lvlout.p); mix((uint64_t)(uintptr_t)user_aux); mix((uint64_t)(uintptr_t)user_early);
-        mix((uint64_t)gaussian_ed); mix((uint64_t)force_general_quadtree); mix((uint64_t)force_pyramid_depth);
-        mix((uint64_t)fast0_mode); mix((uint64_t)batch_cap);
-        return k | 1ull;
-    }
     hipStream_t user_aux = nullptr; // orbfe_extractor_set_aux_stream: run the blur there instead of on aux_stream
-    hipStream_t user_early = nullptr; // orbfe_extractor_set_early_stream: FAST of level 0 there instead of on aux_stream
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_fork0 = nullptr, ev_join0 = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     // orbfe_extractor_follow: this handle's batches start behind a stage of ANOTHER handle's latest batch (two engine sets of a
     // pipeline hold a fixed phase that way instead of whatever the contention of the moment settles on)
     orbfe_extractor* follow = nullptr;
@@ -106,10 +79,13 @@ struct orbfe_extractor {
     bool stage_recorded = false;         // a batch's front part has been enqueued.  A stage's event is created when the stage is first
                                          // enqueued -- the descriptors may come a step later (extractor_defer_describe) -- and a wait skips
                                          // an event that does not exist yet
-    // FAST of level 0 from the start of the batch, next to the resize chain: 0 off (default), 1 on the handle's second stream (or the one
-    // named by orbfe_extractor_set_early_stream), 2 on the lent one.  Measured in round 3 (profiles/r03_fast0_early.txt): the launch
-    // does overlap the resize chain, but the C2 step does not move (1.5365 ms either way) -- the chip was issue-bound there already
-    int fast0_mode = 0; // (set by orbfe_extractor_set_early_stream)
+    // queue on `st` a wait for stage k (1 .. 4 as in follow_stage; 0 = no gate) of h's newest batch.  No wait when h is null or is
+    // `self` (a handle is not gated by itself), nor before h's front part has been enqueued once.
+    static int wait_stage(const orbfe_extractor* h, int k, hipStream_t st, const orbfe_extractor* self = nullptr)
+    {
+        if (h && h != self && h->stage_recorded && k >= 1 && k <= 4 && h->ev_stage[k - 1]) ORBFE_HIP(hipStreamWaitEvent(st, h->ev_stage[k - 1], 0));
+        return ORBFE_OK;
+    }
     int rows = 0, cols = 0; // geometry currently built
     int batch_cap = 0;
     std::vector<LevelGeom> geom;
@@ -126,7 +102,6 @@ struct orbfe_extractor {
     // so that the other engine's latency-bound kernels (8 waves and 50-77 KB of LDS per workgroup) always find room on every CU
     // k_orient_describe2 (two keypoints per wave: 227 instead of 342 VALU instructions per keypoint, 238 instead of 256 us alone at C2)
     // is NOT the default: with the detector running the C2 step was 1.62 ms with it and 1.61 without (four interleaved runs each)
-    static int env_int(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }
     // (rounds 2 - 3 capped the VALU-bound kernels' workgroups per CU with an LDS request they did not use -- ORBFE_OCC_FAST / _BLUR /
     // _ORIENT -- so that the detector's 65 - 77 KB workgroups always found room: noise at best, slower when tighter; the switches went in round 5)
     bool force_general_quadtree = false; // test hook: run the general kernel for every level
@@ -147,11 +122,8 @@ struct orbfe_extractor {
         if (aux_stream) (void)hipStreamDestroy(aux_stream);
         if (ev_fork) (void)hipEventDestroy(ev_fork);
         if (ev_join) (void)hipEventDestroy(ev_join);
-        drop_graph();
         if (ev_up) (void)hipEventDestroy(ev_up);
         for (hipEvent_t e : ev_stage) if (e) (void)hipEventDestroy(e);
-        if (ev_fork0) (void)hipEventDestroy(ev_fork0);
-        if (ev_join0) (void)hipEventDestroy(ev_join0);
     }
 
     // ORBextractor::ORBextractor, src/ORBextractor.cc:410-470
@@ -499,40 +471,8 @@ struct orbfe_extractor {
         last_nframes = B;
         last_src0 = src0;
         timer.begin();
-        if (follow && follow != this && follow->stage_recorded && follow_stage >= 1 && follow_stage <= 4 && follow->ev_stage[follow_stage - 1])
-            ORBFE_HIP(hipStreamWaitEvent(s, follow->ev_stage[follow_stage - 1], 0));
+        if ((rc = wait_stage(follow, follow_stage, s, this))) return rc;
         timer.mark(s, "start");
-        auto launch_fast = [&](hipStream_t st, int cell_base, int cell_end) -> int {
-            if (cell_end <= cell_base) return ORBFE_OK;
-            // LDS per wave: ROI (cell + 6), score map (cell + 2), one u16 list of cell pixels
-            const int roi_pitch = align_up(max_wcell + 6 + 4, 4) + 8, roi_rows = max_hcell + 6; // +1 byte shift, +2 dwords read past a row (8-pixel groups)
-            const int map_pitch = max_wcell + 2, map_rows = max_hcell + 2;
-            const int list_cap = max_wcell * max_hcell;
-            auto a16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-            const size_t lds = 4 * (a16((size_t)roi_pitch * roi_rows) + a16((size_t)map_pitch * map_rows) +
-                                    a16((size_t)list_cap * 2));
-            const size_t lds_fast = lds;
-            { int rc_lds_ = ensure_dyn_lds(reinterpret_cast<const void*>(&k_fast_cells), (size_t)(lds_fast)); if (rc_lds_) return rc_lds_; }
-            const int nx = (cell_end - cell_base + 3) / 4;
-            for (int r_ = 0; r_ < ORBFE_REPS_ORB(1); r_++) hipLaunchKernelGGL(k_fast_cells, dim3(xcd_grid(nx * B)), dim3(256), lds_fast, st, src0, pyr, dg,
-                               d_cellinfo.as<uint32_t>(), d_slots.as<uint32_t>(), slots_fu32,
-                               d_cellcnt.as<int32_t>(), ncells_total, iniThFAST, minThFAST, roi_pitch, roi_rows,
-                               map_pitch, map_rows, list_cap, nx, nx * B, cell_base, cell_end);
-            return ORBFE_OK;
-        };
-        // Level 0 needs no resize: its cells (a third of all pixels) can be searched on a stream of their own from the start of the
-        // batch, next to the resize chain instead of behind it (fast0_mode; off by default, see there).
-        const int ncells_l0 = nlevels > 1 ? geom[1].cell_first : ncells_total;
-        const bool fast0 = fast0_mode != 0 && nlevels > 1;
-        hipStream_t fast0_stream = user_early ? user_early : fast0_mode == 2 && user_aux ? user_aux : this->aux_stream;
-        if (fast0) {
-            ORBFE_HIP(hipEventRecord(ev_fork0, s));
-            ORBFE_HIP(hipStreamWaitEvent(fast0_stream, ev_fork0, 0));
-            timer.mark(fast0_stream, "fast_cells level 0 starts", true);
-            if ((rc = launch_fast(fast0_stream, 0, ncells_l0))) return rc;
-            timer.mark(fast0_stream, "fast_cells_l0");
-            ORBFE_HIP(hipEventRecord(ev_join0, fast0_stream));
-        }
         for (int r16_ = 0; r16_ < ORBFE_REPS_ORB(16); r16_++)
         for (int l = 1; l < nlevels; l++) {
             const LevelGeom& g = geom[l];
@@ -590,11 +530,23 @@ struct orbfe_extractor {
             return ORBFE_OK;
         };
         if ((rc = launch_blur())) return rc;
-        if (follow && follow != this && follow->stage_recorded && follow_fast_stage >= 1 && follow_fast_stage <= 4 && follow->ev_stage[follow_fast_stage - 1])
-            ORBFE_HIP(hipStreamWaitEvent(s, follow->ev_stage[follow_fast_stage - 1], 0));
-        if ((rc = launch_fast(s, fast0 ? ncells_l0 : 0, ncells_total))) return rc;
+        if ((rc = wait_stage(follow, follow_fast_stage, s, this))) return rc;
+        {
+            // LDS per wave: ROI (cell + 6), score map (cell + 2), one u16 list of cell pixels
+            const int roi_pitch = align_up(max_wcell + 6 + 4, 4) + 8, roi_rows = max_hcell + 6; // +1 byte shift, +2 dwords read past a row (8-pixel groups)
+            const int map_pitch = max_wcell + 2, map_rows = max_hcell + 2;
+            const int list_cap = max_wcell * max_hcell;
+            auto a16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+            const size_t lds = 4 * (a16((size_t)roi_pitch * roi_rows) + a16((size_t)map_pitch * map_rows) +
+                                    a16((size_t)list_cap * 2));
+            if ((rc = ensure_dyn_lds(reinterpret_cast<const void*>(&k_fast_cells), lds))) return rc;
+            const int nx = (ncells_total + 3) / 4;   // (every level has at least one cell: build_geometry)
+            for (int r_ = 0; r_ < ORBFE_REPS_ORB(1); r_++) hipLaunchKernelGGL(k_fast_cells, dim3(xcd_grid(nx * B)), dim3(256), lds, s, src0, pyr, dg,
+                               d_cellinfo.as<uint32_t>(), d_slots.as<uint32_t>(), slots_fu32,
+                               d_cellcnt.as<int32_t>(), ncells_total, iniThFAST, minThFAST, roi_pitch, roi_rows,
+                               map_pitch, map_rows, list_cap, nx, nx * B, 0, ncells_total);
+        }
         timer.mark(s, "fast_cells");
-        if (fast0) ORBFE_HIP(hipStreamWaitEvent(s, ev_join0, 0));
         auto stage_event = [&](int k) -> int {
             if (!ev_stage[k]) ORBFE_HIP(hipEventCreateWithFlags(&ev_stage[k], hipEventDisableTiming));
             ORBFE_HIP(hipEventRecord(ev_stage[k], s));
@@ -657,8 +609,8 @@ struct orbfe_extractor {
         if (!late.pending) return ORBFE_OK;
         late.pending = false;
         hipStream_t s = late.s;
-        if (gate && gate != this && gate->stage_recorded && gate_stage >= 1 && gate_stage <= 4 && gate->ev_stage[gate_stage - 1])
-            ORBFE_HIP(hipStreamWaitEvent(s, gate->ev_stage[gate_stage - 1], 0));
+        int rc;
+        if ((rc = wait_stage(gate, gate_stage, s, this))) return rc;
         ImgView pyr{d_pyr.as<uint8_t>(), d_pyr.as<uint8_t>(), pyr_fbytes, 0};
         ImgView blur{d_blur.as<uint8_t>(), d_blur.as<uint8_t>(), blur_fbytes, 0};
         const int kcap_ = std::min(late.capacity, max_keypoints());
@@ -710,9 +662,7 @@ orbfe_extractor* orbfe_extractor_create(int nfeatures, float scaleFactor, int nl
     h->build_tables();
     if (hipStreamCreate(&h->own_stream) != hipSuccess || hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_fork0, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_join0, hipEventDisableTiming) != hipSuccess || h->upload_describe_tables() != ORBFE_OK) {
+        hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess || h->upload_describe_tables() != ORBFE_OK) {
         fail(ORBFE_ERR_HIP, "extractor device initialisation failed");
         delete h;
         return nullptr;
@@ -800,62 +750,32 @@ int orbfe_extract_batch(orbfe_extractor* h, const uint8_t* imgs, int nframes, si
     hipStream_t s = h->own_stream;
     for (int f = 0; f < nframes; f++)
         for (int y = 0; y < rows; y++) memcpy(hp + f * dframe + (size_t)y * dpitch, imgs + f * frame_stride + (size_t)y * step, (size_t)cols);
-    // The call's stream work -- upload, ~13 launches on two streams, four result copies -- is the same every time a caller feeds
-    // frames of one size (the drop-in path: Frame.cc:200-206 once per frame): with ORBFE_GRAPH=1 it is replayed from the third such
-    // call on as one hipGraph, captured inside the library on its own stream (everything that decides a launch parameter is part of
-    // the key).
-    const bool spec = h->paired && nframes == 1;
     if (h->paired) aruco_speculation_wait(h->paired); // the detector may still be reading the previous frame in d_in
-    auto enqueue = [&]() -> int {
-        ORBFE_HIP(hipMemcpyAsync(h->d_in.p, hp, dframe * nframes, hipMemcpyHostToDevice, s));
-        if (spec) { // the paired detector starts on the same device copy, on its own stream, next to the launches below
-            if (!h->ev_up) ORBFE_HIP(hipEventCreateWithFlags(&h->ev_up, hipEventDisableTiming));
-            ORBFE_HIP(hipEventRecord(h->ev_up, s));
-            // a frame the detector refuses, or a workspace it cannot get, is the detector's own call's business: the extraction runs
-            // "as if nothing had been started" (orbfe.h), and aruco_speculate() leaves no speculation pending when it fails
-            if (aruco_speculate(h->paired, h->d_in.as<uint8_t>(), dframe, rows, cols, dpitch, h->ev_up, hp, dpitch) != ORBFE_OK) (void)hipGetLastError();
-        }
-        int rc2 = h->run_device(h->d_in.as<uint8_t>(), nframes, dframe, rows, cols, dpitch, h->d_kps.as<orbfe_keypoint>(),
-                                h->d_desc.as<uint8_t>(), cap, h->d_nout.as<int32_t>(), s, /*flag_word*/ 1);
-        if (rc2) return rc2;
-        // the results: queued behind the kernels, one wait (blocking copies cost a round trip each: 4 x ~40 us per frame).  A single
-        // frame's four arrays go out in one launch that writes the page-locked staging buffer (OutPack); a batch by the copy engine.
-        if ((size_t)cap * nframes * 60 <= ((size_t)1 << 20)) {
-            OutPack op;
-            op.add(hp + o_n, h->d_nout.p, (size_t)nframes * 4);
-            op.add(hp + o_flag, h->d_overflow.as<int32_t>() + 1, 4);
-            op.add(hp + o_kps, h->d_kps.p, (size_t)cap * nframes * sizeof(orbfe_keypoint));
-            op.add(hp + o_desc, h->d_desc.p, (size_t)cap * nframes * 32);
-            return op.flush<0>(s);
-        }
+    ORBFE_HIP(hipMemcpyAsync(h->d_in.p, hp, dframe * nframes, hipMemcpyHostToDevice, s));
+    if (h->paired && nframes == 1) { // the paired detector starts on the same device copy, on its own stream, next to the launches below
+        if (!h->ev_up) ORBFE_HIP(hipEventCreateWithFlags(&h->ev_up, hipEventDisableTiming));
+        ORBFE_HIP(hipEventRecord(h->ev_up, s));
+        // a frame the detector refuses, or a workspace it cannot get, is the detector's own call's business: the extraction runs
+        // "as if nothing had been started" (orbfe.h), and aruco_speculate() leaves no speculation pending when it fails
+        if (aruco_speculate(h->paired, h->d_in.as<uint8_t>(), dframe, rows, cols, dpitch, h->ev_up, hp, dpitch) != ORBFE_OK) (void)hipGetLastError();
+    }
+    if ((rc = h->run_device(h->d_in.as<uint8_t>(), nframes, dframe, rows, cols, dpitch, h->d_kps.as<orbfe_keypoint>(),
+                            h->d_desc.as<uint8_t>(), cap, h->d_nout.as<int32_t>(), s, /*flag_word*/ 1)))
+        return rc;
+    // the results: queued behind the kernels, one wait (blocking copies cost a round trip each: 4 x ~40 us per frame).  A single
+    // frame's four arrays go out in one launch that writes the page-locked staging buffer (OutPack); a batch by the copy engine.
+    if ((size_t)cap * nframes * 60 <= ((size_t)1 << 20)) {
+        OutPack op;
+        op.add(hp + o_n, h->d_nout.p, (size_t)nframes * 4);
+        op.add(hp + o_flag, h->d_overflow.as<int32_t>() + 1, 4);
+        op.add(hp + o_kps, h->d_kps.p, (size_t)cap * nframes * sizeof(orbfe_keypoint));
+        op.add(hp + o_desc, h->d_desc.p, (size_t)cap * nframes * 32);
+        if ((rc = op.flush<0>(s))) return rc;
+    } else {
         ORBFE_HIP(hipMemcpyAsync(hp + o_n, h->d_nout.p, (size_t)nframes * 4, hipMemcpyDeviceToHost, s));
         ORBFE_HIP(hipMemcpyAsync(hp + o_flag, h->d_overflow.as<int32_t>() + 1, 4, hipMemcpyDeviceToHost, s));
         ORBFE_HIP(hipMemcpyAsync(hp + o_kps, h->d_kps.p, (size_t)cap * nframes * sizeof(orbfe_keypoint), hipMemcpyDeviceToHost, s));
         ORBFE_HIP(hipMemcpyAsync(hp + o_desc, h->d_desc.p, (size_t)cap * nframes * 32, hipMemcpyDeviceToHost, s));
-        return ORBFE_OK;
-    };
-    const uint64_t key = h->graph_key(nframes, rows, cols, hp);
-    bool replayed = false;
-    if (h->use_graph && !spec && !h->follow && !h->timer.enabled && key == h->g_key && h->g_exec) {
-        if (hipGraphLaunch(h->g_exec, s) == hipSuccess) replayed = true;
-        else h->drop_graph();
-    }
-    if (!replayed) {
-        const bool capture = h->use_graph && !spec && !h->follow && !h->timer.enabled && key == h->g_key && !h->g_exec && ++h->g_seen >= 2; // (a followed handle waits for an event recorded outside the capture)
-        if (key != h->g_key) { h->drop_graph(); h->g_key = key; h->g_seen = 0; }
-        bool captured = false;
-        if (capture && hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            rc = enqueue();
-            hipGraph_t g = nullptr;
-            const hipError_t e = hipStreamEndCapture(s, &g);
-            if (rc == ORBFE_OK && e == hipSuccess && g && hipGraphInstantiate(&h->g_exec, g, nullptr, nullptr, 0) == hipSuccess &&
-                hipGraphLaunch(h->g_exec, s) == hipSuccess)
-                captured = true;
-            else { h->drop_graph(); h->use_graph = false; (void)hipGetLastError(); } // capture is not available here: never again
-            if (getenv("ORBFE_GRAPH_VERBOSE")) fprintf(stderr, "orbfe_extract: hipGraph capture %s (rc %d, end %d)\n", captured ? "ok" : "FAILED", rc, (int)e);
-            if (g) (void)hipGraphDestroy(g);
-        }
-        if (!captured && (rc = enqueue())) return rc;
     }
     ORBFE_HIP(hipStreamSynchronize(s));
     const int32_t ovf = *reinterpret_cast<const int32_t*>(hp + o_flag);
@@ -992,16 +912,7 @@ int orbfe_extractor_stage_wait(orbfe_extractor* h, int stage, void* stream)
     if (!h || stage < 1 || stage > 4) return fail(ORBFE_ERR_INVALID, "orbfe_extractor_stage_wait: invalid argument");
     int rc = use_device(h->device);
     if (rc) return rc;
-    if (h->stage_recorded && h->ev_stage[stage - 1]) ORBFE_HIP(hipStreamWaitEvent((hipStream_t)stream, h->ev_stage[stage - 1], 0));
-    return ORBFE_OK;
-}
-
-int orbfe_extractor_set_early_stream(orbfe_extractor* h, void* stream)
-{
-    if (!h) return fail(ORBFE_ERR_INVALID, "null handle");
-    h->user_early = (hipStream_t)stream;
-    h->fast0_mode = stream ? 1 : 0;   // naming a stream switches the early launch on, NULL off
-    return ORBFE_OK;
+    return orbfe_extractor::wait_stage(h, stage, (hipStream_t)stream);
 }
 
 int orbfe_extractor_debug_control(orbfe_extractor* h, const char* key, int value)

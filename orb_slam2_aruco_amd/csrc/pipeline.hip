@@ -99,9 +99,8 @@ struct orbfe_pipeline {
     std::vector<long long> set_batch;      // per record set: the batch that was written to it last
     bool defer_post = false, det_nofork = false, use_orb = true, use_aruco = true;
     std::vector<orbfe_extractor*> ex;
-    orbfe_aruco* det = nullptr;               // detector of engine set 0 (= dets[0])
-    std::vector<orbfe_aruco*> dets;           // ORBFE_ENGINE_SETS_ARUCO detector sets alternate batches (measurement switch; default 1)
-    std::vector<hipStream_t> st_ex, st_dets;
+    orbfe_aruco* det = nullptr;
+    std::vector<hipStream_t> st_ex;
     hipStream_t st_det = nullptr, st_match = nullptr;
     orbfe_record_layout lay{};
     std::vector<uint8_t*> recs;
@@ -145,8 +144,7 @@ struct orbfe_pipeline {
         (void)hipDeviceSynchronize();
         if (own_comm && comm) { if (Rccl* R_ = rccl()) (void)R_->CommDestroy(comm); }
         for (auto e : ex) if (e) orbfe_extractor_destroy(e);
-        for (auto d : dets) if (d) orbfe_aruco_destroy(d);
-        for (size_t k = 1; k < st_dets.size(); k++) if (st_dets[k]) (void)hipStreamDestroy(st_dets[k]);
+        if (det) orbfe_aruco_destroy(det);
         for (auto r : recs) if (r) (void)hipFree(r);
         for (void* p : {(void*)d_bidx, (void*)d_bdist, (void*)d_sdist, (void*)d_m12, (void*)d_nm, (void*)blocks}) if (p) (void)hipFree(p);
         for (auto* v : {&ex_done, &det_done, &match_done, &gather_done, &gather_free}) for (auto e : *v) if (e) (void)hipEventDestroy(e);
@@ -298,10 +296,10 @@ struct orbfe_pipeline {
 const char* orbfe_pipeline_env_defaults(void)
 {
     // one list for the pipeline and the engines: bench.py marks a line as diagnostic when one of these is set to something else
-    return "ORBFE_ENGINE_SETS=2;ORBFE_ENGINE_SETS_ARUCO=1;ORBFE_RECORD_SETS=4;ORBFE_PHASE_PIN=size;ORBFE_DET_PIN=4;ORBFE_DEFER_POST=size;ORBFE_DET_NOFORK=size;"
+    return "ORBFE_ENGINE_SETS=2;ORBFE_RECORD_SETS=4;ORBFE_PHASE_PIN=size;ORBFE_DET_PIN=4;ORBFE_DEFER_POST=size;ORBFE_DET_NOFORK=size;"
            "ORBFE_ARUCO_RELAY_WIDE=1;"
-           "ORBFE_ARUCO_SPECKS=size;ORBFE_DESCRIBE_LATE=1;ORBFE_ARUCO_SMALL_SEPARATE=size;ORBFE_ARUCO_TILED=size;ORBFE_ARUCO_TILE_W=0;ORBFE_ARUCO_TPW=0;ORBFE_ARUCO_BANDED=size;ORBFE_ARUCO_BAND_ROWS=0;ORBFE_ARUCO_LCAP=0;ORBFE_GRAPH=0;"
-           "ORBFE_GATHER_STREAM=0;ORBFE_CU_DET=0;ORBFE_CU_EX=0;ORBFE_NO_LEND=0;ORBFE_GRAPH_VERBOSE=0;ORBFE_RCCL_LIB=";
+           "ORBFE_ARUCO_SPECKS=size;ORBFE_DESCRIBE_LATE=1;ORBFE_ARUCO_SMALL_SEPARATE=size;ORBFE_ARUCO_TILED=size;ORBFE_ARUCO_TILE_W=0;ORBFE_ARUCO_TPW=0;ORBFE_ARUCO_BANDED=size;ORBFE_ARUCO_BAND_ROWS=0;ORBFE_ARUCO_LCAP=0;"
+           "ORBFE_GATHER_STREAM=0;ORBFE_RCCL_LIB=";
 }
 
 int orbfe_pipeline_config_default(orbfe_pipeline_config* c, int frames, int rows, int cols)
@@ -355,24 +353,14 @@ orbfe_pipeline* orbfe_pipeline_create(const orbfe_pipeline_config* cfg)
         return nullptr;
     };
     auto mkstream = [&](hipStream_t* s) { return hipStreamCreateWithFlags(s, hipStreamNonBlocking) == hipSuccess; };
-    // CU partition (measurement switch, round 6): ORBFE_CU_DET = K gives the detector's stream the first K compute units of the
-    // enumeration (the driver deals mask bits round-robin over the eight XCDs, so K / 8 of every XCD); ORBFE_CU_EX = 1 gives the
-    // extractor sets' streams the complement, 2 also the matching stream.  Off by default: see tools/sweeps.md.
-    const int cu_det = env_or("ORBFE_CU_DET", 0), cu_ex = env_or("ORBFE_CU_EX", 0);
-    auto mkmasked = [&](hipStream_t* s, int first, int last) {
-        uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (int i = first; i < last && i < 256; i++) mask[i >> 5] |= 1u << (i & 31);
-        return hipExtStreamCreateWithCUMask(s, 8, mask) == hipSuccess;
-    };
-    if (cu_det > 0 ? !mkmasked(&p->st_det, 0, cu_det) : !mkstream(&p->st_det)) return bail("stream");
-    if (cu_det > 0 && cu_ex >= 2 ? !mkmasked(&p->st_match, cu_det, 256) : !mkstream(&p->st_match)) return bail("stream");
+    if (!mkstream(&p->st_det) || !mkstream(&p->st_match)) return bail("stream");
     if (env_or("ORBFE_GATHER_STREAM", 0)) {
         int lo = 0, hi = 0;
         if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) { (void)hipGetLastError(); lo = hi = 0; }
         if (hipStreamCreateWithPriority(&p->st_gather, hipStreamNonBlocking, lo) != hipSuccess) return bail("stream");
     }
     p->st_ex.assign((size_t)p->D, nullptr);
-    for (auto& s : p->st_ex) if (cu_det > 0 && cu_ex ? !mkmasked(&s, cu_det, 256) : !mkstream(&s)) return bail("stream");
+    for (auto& s : p->st_ex) if (!mkstream(&s)) return bail("stream");
     if (p->use_orb) {
         for (int d = 0; d < p->D; d++) {
             orbfe_extractor* e = orbfe_extractor_create(cfg->nfeatures, cfg->scale_factor, cfg->nlevels, cfg->ini_th_fast, cfg->min_th_fast, cfg->device);
@@ -382,7 +370,7 @@ orbfe_pipeline* orbfe_pipeline_create(const orbfe_pipeline_config* cfg)
             // queues with the busy ones)
             // (round 5: the blur of all sets on ONE extra stream with a hardware queue of its own -- lowest / highest stream priority --
             // 1.59 / 1.69 ms against 1.35: what the lending buys is that blur and matching do NOT run next to each other)
-            if (!env_or("ORBFE_NO_LEND", 0)) orbfe_extractor_set_aux_stream(e, p->st_match);
+            orbfe_extractor_set_aux_stream(e, p->st_match);
         }
         if (p->phase_pin && p->D > 1)
             for (int d = 0; d < p->D; d++) orbfe_extractor_follow(p->ex[d], p->ex[(d + p->D - 1) % p->D], p->phase_pin);
@@ -401,17 +389,8 @@ orbfe_pipeline* orbfe_pipeline_create(const orbfe_pipeline_config* cfg)
     } else
         p->cap = 1;
     if (p->use_aruco) {
-        const int DA = std::max(1, env_or("ORBFE_ENGINE_SETS_ARUCO", 1));
-        for (int d = 0; d < DA; d++) {
-            orbfe_aruco* a = orbfe_aruco_create(p->cfg.dictionary, cfg->device);
-            if (!a) return nullptr;
-            p->dets.push_back(a);
-            hipStream_t sd = p->st_det;
-            if (d > 0 && !mkstream(&sd)) return bail("stream");
-            p->st_dets.push_back(sd);
-            if (p->det_nofork) orbfe_aruco_set_aux_stream(a, sd);
-        }
-        p->det = p->dets[0];
+        if (!(p->det = orbfe_aruco_create(p->cfg.dictionary, cfg->device))) return nullptr;
+        if (p->det_nofork) orbfe_aruco_set_aux_stream(p->det, p->st_det);
         p->mcap = std::min(orbfe_aruco_max_markers(p->det), std::max(1, cfg->marker_capacity));
     }
     orbfe_record_layout& L = p->lay;
@@ -623,29 +602,23 @@ static int step_body(orbfe_pipeline* p, const uint8_t* d_imgs, size_t pitch, int
     p->set_batch[(size_t)cur] = i;
     auto enqueue_detector = [&]() -> int {
         if (!p->use_aruco) return ORBFE_OK;
-        const size_t aset = (size_t)(i % (long)p->dets.size());
-        orbfe_aruco* det_i = p->dets[aset];
-        hipStream_t st_det_i = p->st_dets[aset];
         // the detector only depends on the resident frames and on its own previous batch: it is not joined with the extractor per step
-        // (several detector sets -- a measurement switch -- alternate streams: the batch that used this record set R steps ago ran on
-        // another one when the number of sets does not divide R)
-        if (p->dets.size() > 1 && i >= p->R) ORBFE_HIP(hipStreamWaitEvent(st_det_i, p->det_done[cur], 0));
-        if (p->comm && i >= p->R) ORBFE_HIP(hipStreamWaitEvent(st_det_i, p->gather_done[cur], 0)); // batch i - R has left this record set
-        if (p->host_mode && p->rb_valid[(size_t)cur]) ORBFE_HIP(hipStreamWaitEvent(st_det_i, p->rb_done[(size_t)cur], 0)); // ... and has been copied to the host
-        if (in_slot >= 0) { ORBFE_HIP(hipStreamWaitEvent(st_det_i, p->in_ready[in_slot], 0)); }
+        if (p->comm && i >= p->R) ORBFE_HIP(hipStreamWaitEvent(p->st_det, p->gather_done[cur], 0)); // batch i - R has left this record set
+        if (p->host_mode && p->rb_valid[(size_t)cur]) ORBFE_HIP(hipStreamWaitEvent(p->st_det, p->rb_done[(size_t)cur], 0)); // ... and has been copied to the host
+        if (in_slot >= 0) { ORBFE_HIP(hipStreamWaitEvent(p->st_det, p->in_ready[in_slot], 0)); }
         if (p->det_pin % 10 && p->use_orb) {   // (det_pin = 10: the extractor first, the detector ungated)
             const long j = p->det_pin >= 10 ? i : i - 1; // + 10: a stage of THIS batch's extractor, which is then enqueued first
-            if (j >= 0 && (rc = orbfe_extractor_stage_wait(p->ex[(size_t)(j % p->D)], p->det_pin % 10, st_det_i))) return rc;
+            if (j >= 0 && (rc = orbfe_extractor_stage_wait(p->ex[(size_t)(j % p->D)], p->det_pin % 10, p->st_det))) return rc;
         }
         orbfe_marker* mk = reinterpret_cast<orbfe_marker*>(base + p->lay.off_markers);
         int32_t* nmk = reinterpret_cast<int32_t*>(base + p->lay.off_nmarkers);
-        if ((rc = orbfe_aruco_detect_batch_device(det_i, d_imgs, B, fstride, rows, cols, pitch, mk, p->mcap, nmk, st_det_i))) return rc;
+        if ((rc = orbfe_aruco_detect_batch_device(p->det, d_imgs, B, fstride, rows, cols, pitch, mk, p->mcap, nmk, p->st_det))) return rc;
         // detect(image, CameraParameters, 0.187): every marker gets its IPPE pose (markerdetector_impl.cpp:8720-8780)
         if ((rc = orbfe_marker_poses_batch_device(mk, nmk, p->mcap, B, p->cfg.marker_size, p->cfg.K, p->cfg.dist, p->cfg.ndist,
-                                                  reinterpret_cast<orbfe_marker_pose*>(base + p->lay.off_poses), st_det_i)))
+                                                  reinterpret_cast<orbfe_marker_pose*>(base + p->lay.off_poses), p->st_det)))
             return rc;
-        ORBFE_HIP(hipEventRecord(p->det_done[cur], st_det_i));
-        if (in_slot >= 0) ORBFE_HIP(hipEventRecord(p->in_used_det[in_slot], st_det_i));
+        ORBFE_HIP(hipEventRecord(p->det_done[cur], p->st_det));
+        if (in_slot >= 0) ORBFE_HIP(hipEventRecord(p->in_used_det[in_slot], p->st_det));
         return ORBFE_OK;
     };
     auto enqueue_extractor = [&]() -> int {
@@ -707,7 +680,6 @@ int orbfe_pipeline_synchronize(orbfe_pipeline* p)
     if (rc) return rc;
     for (auto s : p->st_ex) ORBFE_HIP(hipStreamSynchronize(s));
     ORBFE_HIP(hipStreamSynchronize(p->st_det));
-    for (auto sd : p->st_dets) ORBFE_HIP(hipStreamSynchronize(sd));
     ORBFE_HIP(hipStreamSynchronize(p->st_match));
     if (p->st_gather) ORBFE_HIP(hipStreamSynchronize(p->st_gather));
     if (p->host_mode) { ORBFE_HIP(hipStreamSynchronize(p->st_h2d)); ORBFE_HIP(hipStreamSynchronize(p->st_d2h)); }
@@ -744,10 +716,10 @@ int orbfe_pipeline_status(orbfe_pipeline* p, int32_t out[4])
         if (rc && rc != ORBFE_ERR_CAPACITY) return rc;
         out[1] = o;
     }
-    for (auto d : p->dets) {
+    if (p->det) {
         int32_t n = 0, fl = 0;
-        if ((rc = orbfe_aruco_batch_status(d, &n, &fl))) return rc;
-        out[2] += n; out[3] |= fl;
+        if ((rc = orbfe_aruco_batch_status(p->det, &n, &fl))) return rc;
+        out[2] = n; out[3] = fl;
     }
     return ORBFE_OK;
 }
@@ -755,8 +727,7 @@ int orbfe_pipeline_status(orbfe_pipeline* p, int32_t out[4])
 int orbfe_pipeline_set_big_frames(orbfe_pipeline* p, int on)
 {
     if (!p) return fail(ORBFE_ERR_INVALID, "null handle");
-    for (auto d : p->dets) { int rc = orbfe_aruco_set_big_frames(d, on); if (rc) return rc; }
-    return ORBFE_OK;
+    return p->det ? orbfe_aruco_set_big_frames(p->det, on) : ORBFE_OK;
 }
 
 int orbfe_pipeline_records(orbfe_pipeline* p, int set, uint8_t** d_records)

@@ -181,24 +181,6 @@ def test_gaussian_tap_variants(orbfe, oracle):
         ex.set_gaussian_taps(2)
 
 
-def test_hipgraph_replay_of_the_host_pointer_call():
-    """ORBFE_GRAPH=1: from the third call with one frame size on, orbfe_extract replays its upload, launches and result copies as a
-    hipGraph captured inside the library.  The end-to-end cases (several frames of one size through one handle) in a process with the
-    switch set: replayed calls must give the oracle's keypoints and descriptors like direct ones."""
-    import os, subprocess, sys
-    env = dict(os.environ, ORBFE_GRAPH="1", ORBFE_GRAPH_VERBOSE="1")
-    code = ("import sys, numpy as np; sys.path[:0] = [%r, %r]; from orb_slam2_aruco_amd import binding, synth; import oracle_lib\n"
-            "s = synth.stream(480, 640, 6, 4242)\n"
-            "ex = binding.ORBextractor(1000, 1.2, 8, 20, 7); ora = oracle_lib.OrbOracle(1000, 1.2, 8, 20, 7)\n"
-            "for img in list(s) + [s[0], s[3]]:\n"
-            "    k, d = ex(img); ok, od = ora.extract(img)\n"
-            "    assert np.array_equal(k, ok) and np.array_equal(d, od)\n"
-            "print('replays ok')\n" % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.path.dirname(os.path.abspath(__file__))))
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0 and "replays ok" in r.stdout, r.stdout[-1000:] + r.stderr[-2000:]
-    assert "hipGraph capture ok" in r.stderr, r.stderr[-1000:]
-
-
 def test_phase_lock_between_handles_changes_no_result(orbfe, oracle):
     """orbfe_extractor_follow: a handle's batches start behind a stage of another handle's latest batch (the engine sets of the
     batched pipeline).  Ordering only: results are those of the free-running handles; arguments outside the ranges are refused."""

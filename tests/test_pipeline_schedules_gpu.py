@@ -18,8 +18,6 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 GROUPS = {
     "c2": ("C2", 12, 7, {}, 900),
     "c2_describe_late_0": ("C2", 12, 7, {"ORBFE_DESCRIBE_LATE": "0"}, 600),
-    "c2_engine_sets_aruco_2": ("C2", 12, 7, {"ORBFE_ENGINE_SETS_ARUCO": "2"}, 600),
-    "c2_no_lend": ("C2", 12, 7, {"ORBFE_NO_LEND": "1"}, 600),
     "c3": ("C3", 8, 5, {}, 900),
     "c3_describe_late_0": ("C3", 8, 5, {"ORBFE_DESCRIBE_LATE": "0"}, 600),
     "c5": ("C5", 4, 4, {}, 900),
@@ -75,9 +73,6 @@ COMBOS = [
      "ORBFE_DESCRIBE_LATE=0: each batch's descriptors in its own step"),
     ("c2_describe_late_0", "describe_late_0_defer_post_0", "matrix", {"defer_post": 0}, {"defer_post": 0},
      "ORBFE_DESCRIBE_LATE=0 and defer_post = 0: matching in the step, behind the whole extraction"),
-    ("c2_engine_sets_aruco_2", "engine_sets_aruco_2_record_sets_3", "matrix", {"record_sets": 3}, {"R": 3},
-     "two detector sets with three record sets: a detector set waits for batch i - R of the OTHER detector stream"),
-    ("c2_no_lend", "no_lend", "matrix", {}, {}, "ORBFE_NO_LEND=1: the blur on the extractors' own fork streams"),
     # ---- A2: larger frames, where the size-dependent defaults differ
     ("c3", "default", "matrix", {}, {"D": 2, "R": 4, "phase_pin": 2, "defer_post": 1, "det_nofork": 0},
      "1280 x 720 defaults: no forced det_nofork, late describe forcing the deferred post-work"),
