@@ -183,8 +183,7 @@ int orbfe_extractor_debug_kernel_times(orbfe_extractor* h, float* out_us, int ca
 int orbfe_debug_control(const char* key, int value);
 /* The same for one engine handle.  An unknown key or a value outside its range is ORBFE_ERR_INVALID and changes nothing.
  * Extractor:  "kernel_timing" 0 / 1 (event timing off / on; either clears the history), "general_quadtree" 0 / 1 (the general
- *   quadtree kernel for every level), "pyramid_depth" 0 .. 6 (depth of the quadtree count pyramid; 0 = by the levels' node counts),
- *   "blur_mfma" 1 / 0 (the blur on the matrix cores where it applies, the default / k_blur7).
+ *   quadtree kernel for every level), "pyramid_depth" 0 .. 6 (depth of the quadtree count pyramid; 0 = by the levels' node counts).
  * Detector:  "kernel_timing" 0 / 1, "legacy_contours" 0 / 1 (the single-walker contour kernel for every frame), "tiled_contours"
  *   -1 / 0 / 1 (the tiled contour path by frame and batch size, the default / never / always), "speck_passes" 0 / 1 (as a launch of
  *   their own: never / wherever their tile fits LDS), "speck_passes_in_kernel" 0 / 1 (inside the one-workgroup relay kernels),

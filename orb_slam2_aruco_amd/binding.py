@@ -356,10 +356,6 @@ class ORBextractor:
     def enable_kernel_timing(self, on=True):
         self.debug_control("kernel_timing", on)
 
-    def set_blur_on_matrix_cores(self, on=True):
-        """k_blur7_mfma (default) / k_blur7: the tests run both."""
-        self.debug_control("blur_mfma", on)
-
     def force_general_quadtree(self, on=True):
         """Test hook: bypass the count-pyramid fast path of DistributeOctTree."""
         self.debug_control("general_quadtree", on)

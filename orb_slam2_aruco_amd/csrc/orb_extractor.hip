@@ -62,14 +62,19 @@ struct orbfe_extractor {
     double scaleFactor;
     std::vector<float> mvScaleFactor, mvInvScaleFactor, mvLevelSigma2, mvInvLevelSigma2;
     std::vector<int> mnFeaturesPerLevel, umax;
-    // --- device state
+    // --- configuration and test hooks
     int device = 0;
+    orbfe_aruco* paired = nullptr;       // orbfe_extractor_pair_detector
+    bool gaussian_ed = false;            // orbfe_extractor_set_gaussian_taps: 18 34 48 56 48 34 18 instead of 18 34 49 55 49 34 18
+    bool defer_describe = false;         // extractor_defer_describe: a batch's descriptors wait for describe_deferred()
+    bool force_general_quadtree = false; // test hook: run the general kernel for every level
+    int force_pyramid_depth = 0;         // test hook: shallow count pyramid so that levels fall back
+    KernelTimer timer;
+    // --- streams and events
     hipStream_t own_stream = nullptr, aux_stream = nullptr;
-    PinnedBuf pinned;               // staging of the host-pointer entry points
-    orbfe_aruco* paired = nullptr;  // orbfe_extractor_pair_detector
-    hipEvent_t ev_up = nullptr;     // the image of the host-pointer call is on the device
-    hipStream_t user_aux = nullptr; // orbfe_extractor_set_aux_stream: run the blur there instead of on aux_stream
+    hipStream_t user_aux = nullptr;      // orbfe_extractor_set_aux_stream: run the blur there instead of on aux_stream
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    hipEvent_t ev_up = nullptr;          // the image of the host-pointer call is on the device
     // orbfe_extractor_follow: this handle's batches start behind a stage of ANOTHER handle's latest batch (two engine sets of a
     // pipeline hold a fixed phase that way instead of whatever the contention of the moment settles on)
     orbfe_extractor* follow = nullptr;
@@ -79,45 +84,36 @@ struct orbfe_extractor {
     bool stage_recorded = false;         // a batch's front part has been enqueued.  A stage's event is created when the stage is first
                                          // enqueued -- the descriptors may come a step later (extractor_defer_describe) -- and a wait skips
                                          // an event that does not exist yet
-    // queue on `st` a wait for stage k (1 .. 4 as in follow_stage; 0 = no gate) of h's newest batch.  No wait when h is null or is
-    // `self` (a handle is not gated by itself), nor before h's front part has been enqueued once.
-    static int wait_stage(const orbfe_extractor* h, int k, hipStream_t st, const orbfe_extractor* self = nullptr)
-    {
-        if (h && h != self && h->stage_recorded && k >= 1 && k <= 4 && h->ev_stage[k - 1]) ORBFE_HIP(hipStreamWaitEvent(st, h->ev_stage[k - 1], 0));
-        return ORBFE_OK;
-    }
-    int rows = 0, cols = 0; // geometry currently built
-    int batch_cap = 0;
-    std::vector<LevelGeom> geom;
-    int ncells_total = 0, ntiles = 0, out_total = 0, max_out_cap = 0, max_wcell = 0, max_hcell = 0;
-    size_t pyr_fbytes = 0, blur_fbytes = 0, slots_fu32 = 0, keys_fu32 = 0;
-    int keycap_lds = 0, nodecap = 0, veccap = 0;
-    std::vector<char> resize_tab_ok; // per level >= 1: k_resize_tab's 8-byte windows fit
-    std::vector<size_t> tab_off; // per level >= 1: offsets (in ints) of xofs, xalpha, yofs, ybeta in d_tabs
-    DevBuf d_geom, d_cellinfo, d_tiles, d_tabs, d_pattern, d_umax;
-    DevBuf d_pyr, d_blur, d_slots, d_cellcnt, d_keys, d_lvlout, d_lvlcnt, d_lvloff, d_lvlncand, d_overflow, d_fallback,
-        d_flatkv, d_flatlvl, d_worklist;
-    bool gaussian_ed = false;            // orbfe_extractor_set_gaussian_taps: 18 34 48 56 48 34 18 instead of 18 34 49 55 49 34 18
-    // workgroups per CU the VALU-bound kernels may occupy (0 = what the hardware allows): the launch asks for LDS it does not use
-    // so that the other engine's latency-bound kernels (8 waves and 50-77 KB of LDS per workgroup) always find room on every CU
-    // k_orient_describe2 (two keypoints per wave: 227 instead of 342 VALU instructions per keypoint, 238 instead of 256 us alone at C2)
-    // is NOT the default: with the detector running the C2 step was 1.62 ms with it and 1.61 without (four interleaved runs each)
-    // (rounds 2 - 3 capped the VALU-bound kernels' workgroups per CU with an LDS request they did not use -- ORBFE_OCC_FAST / _BLUR /
-    // _ORIENT -- so that the detector's 65 - 77 KB workgroups always found room: noise at best, slower when tighter; the switches went in round 5)
-    bool force_general_quadtree = false; // test hook: run the general kernel for every level
-    int force_pyramid_depth = 0;         // test hook: shallow count pyramid so that levels fall back
-    DevBuf d_in, d_kps, d_desc, d_nout; // staging for the host-pointer entry points
-    KernelTimer timer;
+    // --- the plan of the input size in force (extractor_plan.hpp) and what a batch of it launches
+    ExtractorPlan plan;
+    int batch_cap = 0;                   // frames the workspace holds
     int last_nframes = 0;
     ImgView last_src0{};
+    struct BatchPlan {
+        int blur_K2 = 0, blur_nx = 0;    // k_blur7_mfma: its rounding constant for the taps' sum, workgroups (four strips each) per frame
+        int roi_pitch = 0, roi_rows = 0, map_pitch = 0, map_rows = 0, list_cap = 0, fast_nx = 0;   // k_fast_cells: LDS layout of a wave, workgroups per frame
+        size_t fast_lds = 0;
+        int D = 0;                       // k_distribute_pyr: depth of the count pyramid
+        size_t qp_lds = 0;
+        int qcap = 0;                    // k_distribute: keys it holds in LDS, its LDS and its grid
+        size_t qt_lds = 0;
+        dim3 qgrid;
+        int okx = 0;                     // k_orient_describe2: workgroups per frame
+    };
+    // --- device buffers: the plan's tables, the describe tables, the per-batch workspace, staging of the host-pointer entry points
+    DevBuf d_geom, d_cellinfo, d_tabs, d_bstrips, d_btabs, d_btab2;
+    DevBuf d_pattern, d_umax;
+    DevBuf d_pyr, d_blur, d_slots, d_cellcnt, d_keys, d_lvlout, d_lvlcnt, d_lvloff, d_lvlncand, d_overflow, d_fallback,
+        d_flatkv, d_flatlvl, d_worklist;
+    DevBuf d_in, d_kps, d_desc, d_nout;
+    PinnedBuf pinned;
+    // --- the newest batch's descriptors, owed while extractor_defer_describe is on
+    struct Late { bool pending; ImgView src0; int B, capacity, okx; orbfe_keypoint* kps; uint8_t* desc; int32_t* n; hipStream_t s; };
+    Late late{};
 
+    // (orbfe_extractor_destroy selects the device; the buffers release themselves behind this body)
     ~orbfe_extractor()
     {
-        for (DevBuf* b : {&d_geom, &d_cellinfo, &d_tiles, &d_tabs, &d_pattern, &d_umax, &d_bstrips, &d_btabs, &d_btab2, &d_pyr, &d_blur, &d_slots,
-                          &d_cellcnt, &d_keys, &d_lvlout, &d_lvlcnt, &d_lvloff, &d_lvlncand, &d_overflow, &d_fallback, &d_flatkv,
-                          &d_flatlvl, &d_worklist, &d_in,
-                          &d_kps, &d_desc, &d_nout})
-            b->release();
         if (own_stream) (void)hipStreamDestroy(own_stream);
         if (aux_stream) (void)hipStreamDestroy(aux_stream);
         if (ev_fork) (void)hipEventDestroy(ev_fork);
@@ -195,234 +191,28 @@ struct orbfe_extractor {
         return t + 8;
     }
 
-    // Level geometry for a rows x cols input: pyramid sizes (:1112), cell grid (:767-787), quadtree roots (:543-558),
-    // plus the HBM layout of every per-frame block.
-    int build_geometry(int rows_, int cols_)
+    template <class T> static int upload(DevBuf& d, const std::vector<T>& v)
     {
-        if (rows_ == rows && cols_ == cols && !geom.empty()) return ORBFE_OK;
-        geom.assign(nlevels, LevelGeom{});
-        std::vector<uint32_t> cellinfo, tiles;
-        std::vector<int> tabs;
-        tab_off.assign((size_t)nlevels * 4, 0);
-        resize_tab_ok.assign((size_t)nlevels, 0);
-        size_t pyr = 0, blur = 0, slots = 0, cand = 0;
-        int out = 0, maxcap = 0, mwc = 0, mhc = 0;
-        for (int l = 0; l < nlevels; l++) {
-            LevelGeom& g = geom[l];
-            const float scale = mvInvScaleFactor[l];
-            g.w = orbfe_round_f((float)cols_ * scale);
-            g.h = orbfe_round_f((float)rows_ * scale);
-            // the reference's own limit: its cell grid needs nCols = (w - 32) / 30 >= 1 (ORBextractor.cc:780-784; below that it divides by zero)
-            if (g.w < 32 + 30 || g.h < 32 + 30)
-                return fail(ORBFE_ERR_INVALID, "level %d is %dx%d: too small for a FAST cell grid (62 pixels a side)", l, g.w, g.h);
-            // a keypoint travels as x | y << 12 | score << 24 relative to the 16-px border
-            if (g.w - 32 > 4095 || g.h - 32 > 4095)
-                return fail(ORBFE_ERR_INVALID, "level %d is %dx%d: images above 4127 px a side are unsupported", l, g.w, g.h);
-            g.pitch = align_up(g.w, 64);
-            g.bpitch = align_up(g.w, 64);
-            g.img_off = (long long)pyr;
-            if (l > 0) pyr += (size_t)g.pitch * g.h;
-            g.blur_off = (long long)blur;
-            blur += (size_t)g.bpitch * g.h;
-            g.maxBX = g.w - 19 + 3;
-            g.maxBY = g.h - 19 + 3;
-            const float width = (float)(g.maxBX - 16), height = (float)(g.maxBY - 16);
-            g.nCols = (int)(width / 30.f);
-            g.nRows = (int)(height / 30.f);
-            g.wCell = (int)std::ceil(width / g.nCols);
-            g.hCell = (int)std::ceil(height / g.nRows);
-            if (g.wCell > 60 || g.hCell > 60) return fail(ORBFE_ERR_INVALID, "cell larger than 60 px");
-            mwc = std::max(mwc, g.wCell); mhc = std::max(mhc, g.hCell);
-            g.cell_first = (int)cellinfo.size();
-            for (int i = 0; i < g.nRows; i++) {
-                const float iniY = (float)(16 + i * g.hCell);
-                if (iniY >= g.maxBY - 3) continue;
-                for (int j = 0; j < g.nCols; j++) {
-                    const float iniX = (float)(16 + j * g.wCell);
-                    if (iniX >= g.maxBX - 6) continue;
-                    cellinfo.push_back((uint32_t)l | ((uint32_t)i << 4) | ((uint32_t)j << 14));
-                }
-            }
-            g.ncells = (int)cellinfo.size() - g.cell_first;
-            g.cell_cap = ((g.wCell + 1) / 2) * ((g.hCell + 1) / 2);
-            g.slot_off = (long long)slots;
-            g.cand_cap = g.ncells * g.cell_cap;
-            slots += (size_t)g.cand_cap;
-            g.cand_off = (long long)cand;
-            cand += (size_t)g.cand_cap;
-            g.quota = mnFeaturesPerLevel[l];
-            g.nIni = (int)std::round(static_cast<float>(g.maxBX - 16) / (g.maxBY - 16));
-            if (g.nIni < 1 || g.nIni > QT_MAXROOTS)
-                return fail(ORBFE_ERR_INVALID, "aspect ratio gives %d quadtree roots (supported: 1..%d)", g.nIni, QT_MAXROOTS);
-            g.hX = static_cast<float>(g.maxBX - 16) / g.nIni;
-            g.out_cap = std::max(g.quota + 3, 4 * g.nIni) + 5;
-            g.out_off = out;
-            out += g.out_cap;
-            maxcap = std::max(maxcap, g.out_cap);
-            g.scale = mvScaleFactor[l];
-            g.kp_size = (float)(int)(31 * mvScaleFactor[l]);
-            for (int tx = 0; tx < (g.w + 63) / 64; tx++) // k_blur7: one workgroup per 64-column strip, long strips first
-                tiles.push_back((uint32_t)l | ((uint32_t)tx << 4));
-            if (l > 0) {
-                // cv::resize(INTER_LINEAR) coefficient tables, OpenCV 3.4
-                const int sw = geom[l - 1].w, sh = geom[l - 1].h, dw = g.w, dh = g.h;
-                const double scale_x = 1. / ((double)dw / sw), scale_y = 1. / ((double)dh / sh);
-                const int dwp = align_up(dw, 4);
-                std::vector<int> xofs(dwp), xal(dwp), ytab((size_t)dh * 4);   // ytab: per row {source row, the row below (both clipped), b0 << 12, b1 << 12}
-                for (int dx = 0; dx < dw; dx++) {
-                    float fx = (float)((dx + 0.5) * scale_x - 0.5);
-                    int sx = orbfe_floor_d(fx);
-                    fx -= sx;
-                    if (sx < 0) { fx = 0; sx = 0; }
-                    if (sx >= sw - 1) { fx = 0; sx = sw - 1; }
-                    const int a0 = (short)orbfe_round_f((1.f - fx) * 2048.f), a1 = (short)orbfe_round_f(fx * 2048.f);
-                    xofs[dx] = sx;
-                    xal[dx] = (a0 & 0xffff) | (a1 << 16);
-                }
-                for (int dx = dw; dx < dwp; dx++) { xofs[dx] = xofs[dw - 1]; xal[dx] = xal[dw - 1]; }
-                // k_resize_tab reads columns sx[0] .. sx[3]+1 of a source row with one 8-byte load
-                bool ok = sw >= 8;
-                for (int x4 = 0; ok && x4 < dwp / 4; x4++) {
-                    const int w0 = std::min(xofs[x4 * 4], sw - 8);
-                    for (int k = 0; k < 4; k++)
-                        ok = ok && xofs[x4 * 4 + k] >= w0 && std::min(xofs[x4 * 4 + k] + 1, sw - 1) - w0 <= 7;
-                }
-                resize_tab_ok[l] = ok;
-                for (int dy = 0; dy < dh; dy++) {
-                    float fy = (float)((dy + 0.5) * scale_y - 0.5);
-                    int sy = orbfe_floor_d(fy);
-                    fy -= sy;
-                    const int b0 = (short)orbfe_round_f((1.f - fy) * 2048.f), b1 = (short)orbfe_round_f(fy * 2048.f);
-                    // rows are NOT clamped like columns: cv::resize keeps the fractional weight and clips the row index
-                    ytab[(size_t)dy * 4 + 0] = std::min(std::max(sy, 0), sh - 1);
-                    ytab[(size_t)dy * 4 + 1] = std::min(std::max(sy + 1, 0), sh - 1);
-                    ytab[(size_t)dy * 4 + 2] = (b0 & 0xffff) << 12;
-                    ytab[(size_t)dy * 4 + 3] = (b1 & 0xffff) << 12;
-                }
-                while (tabs.size() % 4) tabs.push_back(0); // k_resize_tab loads xofs/xal as int4
-                tab_off[l * 4 + 0] = tabs.size(); tabs.insert(tabs.end(), xofs.begin(), xofs.end());
-                tab_off[l * 4 + 1] = tabs.size(); tabs.insert(tabs.end(), xal.begin(), xal.end());
-                while (tabs.size() % 4) tabs.push_back(0); // ... and ytab as int4
-                tab_off[l * 4 + 2] = tabs.size(); tabs.insert(tabs.end(), ytab.begin(), ytab.end());
-                tab_off[l * 4 + 3] = 0;
-            }
-        }
-        rows = rows_; cols = cols_;
-        ncells_total = (int)cellinfo.size();
-        ntiles = (int)tiles.size();
-        out_total = out;
-        max_out_cap = maxcap;
-        max_wcell = mwc; max_hcell = mhc;
-        pyr_fbytes = pyr + 64;
-        blur_fbytes = blur + 64;
-        slots_fu32 = slots;
-        keys_fu32 = 2 * cand;
-        nodecap = maxcap + 8;
-        veccap = 1;
-        while (veccap < nodecap) veccap <<= 1;
-        keycap_lds = 6144;
-        {   // the general kernel's key buffers share LDS with the node lists: large quotas leave less room (levels whose candidates do
-            // not fit work out of the HBM key scratch)
-            const long long room = (long long)160 * 1024 - 3072 - (long long)qt_lds_bytes(0, nodecap, veccap);
-            keycap_lds = (int)std::max<long long>(0, std::min<long long>(6144, room / 8)) & ~63;
-        }
-        {
-            // the node lists of DistributeOctTree live in LDS, sized by the largest per-level quota: say so here, not at launch
-            int max_ini = 1;
-            for (const LevelGeom& g : geom) max_ini = std::max(max_ini, g.nIni);
-            const size_t need = std::max(qp_lds_bytes(max_ini, max_ini <= 4 ? 5 : 4, nodecap, veccap), qt_lds_bytes(keycap_lds, nodecap, veccap));
-            if (need + 2048 > (size_t)160 * 1024)
-                return fail(ORBFE_ERR_CAPACITY, "a pyramid level's quota of %d keypoints (nfeatures %d over %d levels at scale %.3f) needs %zu bytes "
-                            "of LDS for the quadtree: more than a workgroup has (about 2700 keypoints per level fit)", maxcap, nfeatures, nlevels,
-                            (double)scaleFactor, need);
-        }
-        batch_cap = 0; // force workspace re-allocation
-        if (tabs.empty()) tabs.push_back(0);
-        int rc;
-        if ((rc = d_geom.ensure(geom.size() * sizeof(LevelGeom)))) return rc;
-        if ((rc = d_cellinfo.ensure(cellinfo.size() * 4))) return rc;
-        if ((rc = d_tiles.ensure(tiles.size() * 4))) return rc;
-        if ((rc = d_tabs.ensure(tabs.size() * 4))) return rc;
-        ORBFE_HIP(hipMemcpy(d_geom.p, geom.data(), geom.size() * sizeof(LevelGeom), hipMemcpyHostToDevice));
-        ORBFE_HIP(hipMemcpy(d_cellinfo.p, cellinfo.data(), cellinfo.size() * 4, hipMemcpyHostToDevice));
-        ORBFE_HIP(hipMemcpy(d_tiles.p, tiles.data(), tiles.size() * 4, hipMemcpyHostToDevice));
-        ORBFE_HIP(hipMemcpy(d_tabs.p, tabs.data(), tabs.size() * 4, hipMemcpyHostToDevice));
+        if (int rc = d.ensure(v.size() * sizeof(T))) return rc;
+        if (!v.empty()) ORBFE_HIP(hipMemcpy(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
         return ORBFE_OK;
     }
-
-    // Tables of k_blur7_mfma for the geometry and the taps in force: the strips (level-major), per strip the two pass-1 tap matrices in the
-    // B-operand layout of v_mfma_i32_32x32x32_i8 (lane (n, half) holds B[16 half + i][n], i = 0 .. 15, as 16 bytes), BORDER_REFLECT_101
-    // folded in, and the two pass-2 matrices whose K index runs over a block's rows in the order pass 1 leaves them in a lane's registers.
-    DevBuf d_bstrips, d_btabs, d_btab2;
-    int n_bstrips = 0, blur_tabs_ed = -1, blur_tabs_rows = 0, blur_tabs_cols = 0;
-    bool blur_mfma_ok = false;
-    bool blur_mfma = true;               // test hook (debug key "blur_mfma" = 0): k_blur7 instead
-    int build_blur_tables()
+    // The plan for a rows x cols input with the taps in force.  A size the plan refuses leaves the handle as it was; a failed upload
+    // leaves it without a plan (the next batch starts over) rather than with host tables that disagree with the device's.
+    int ensure_plan(int rows_, int cols_)
     {
-        if (blur_tabs_ed == (int)gaussian_ed && blur_tabs_rows == rows && blur_tabs_cols == cols) return ORBFE_OK;
-        static const int T0[7] = {18, 34, 49, 55, 49, 34, 18}, T1[7] = {18, 34, 48, 56, 48, 34, 18};
-        const int* t = gaussian_ed ? T1 : T0;
-        std::vector<BlurStrip> st;
-        std::vector<uint8_t> tabs;
-        bool ok = true;
-        auto refl = [](int p, int n) { while (p < 0 || p >= n) p = (p < 0) ? -p : 2 * (n - 1) - p; return p; };
-        for (int l = 0; l < nlevels && ok; l++) {
-            const int w = geom[l].w, rowbytes = l == 0 ? w : geom[l].pitch;
-            if (w < 48 || rowbytes < 16) { ok = false; break; }
-            for (int X = 0; X < w; X += 32) {
-                BlurStrip S{};
-                S.level = l; S.x0 = X; S.tab = (int)(tabs.size() / 1024);
-                auto cl = [&](int c) { return std::min(std::max(c, 0), rowbytes - 16); };
-                S.c0 = cl(X - 4); S.c1 = cl(X + 12); S.c2 = cl(X + 28);
-                const int cs[3] = {S.c0, S.c1, S.c2};
-                // weight of input column xin for output column n
-                std::vector<int> W((size_t)w * 32, 0);
-                for (int n = 0; n < 32; n++) {
-                    if (X + n >= w) continue;
-                    for (int u = 0; u < 7; u++) W[(size_t)refl(X + n + u - 3, w) * 32 + n] += t[u];
-                }
-                std::vector<int> owner((size_t)w, -1);
-                for (int x = 0; x < w; x++)
-                    for (int pz = 0; pz < 3 && owner[x] < 0; pz++)
-                        if (x >= cs[pz] && x < cs[pz] + 16) owner[x] = pz;
-                for (int x = 0; x < w && ok; x++)
-                    for (int n = 0; n < 32; n++)
-                        if (W[(size_t)x * 32 + n] && (owner[x] < 0 || W[(size_t)x * 32 + n] > 127)) ok = false;
-                const size_t base = tabs.size();
-                tabs.resize(base + 2048, 0);
-                for (int ab = 0; ab < 2; ab++)
-                    for (int lane = 0; lane < 64; lane++) {
-                        const int n = lane & 31, half = lane >> 5;
-                        const int piece = ab == 0 ? half : (half == 0 ? 2 : -1);
-                        if (piece < 0) continue;
-                        for (int i = 0; i < 16; i++) {
-                            const int x = cs[piece] + i;
-                            if (x < 0 || x >= w || owner[x] != piece) continue;
-                            tabs[base + (size_t)ab * 1024 + (size_t)lane * 16 + i] = (uint8_t)(int8_t)W[(size_t)x * 32 + n];
-                        }
-                    }
-                st.push_back(S);
-            }
-        }
-        blur_mfma_ok = ok && !st.empty();
-        blur_tabs_ed = (int)gaussian_ed; blur_tabs_rows = rows; blur_tabs_cols = cols;
-        if (!blur_mfma_ok) return ORBFE_OK;   // (k_blur7 does such a geometry)
-        std::vector<uint8_t> t2(2048, 0);
-        for (int ab = 0; ab < 2; ab++)
-            for (int lane = 0; lane < 64; lane++) {
-                const int n = lane & 31, half = lane >> 5;
-                for (int i = 0; i < 16; i++) {
-                    const int q = 4 * half + (i & 3) + 8 * (i >> 2);
-                    const int u = ab == 0 ? q - n - 1 : q - n + 31;
-                    if (u >= 0 && u <= 6) t2[(size_t)ab * 1024 + (size_t)lane * 16 + i] = (uint8_t)t[u];
-                }
-            }
-        n_bstrips = (int)st.size();
+        if (rows_ == plan.rows && cols_ == plan.cols && gaussian_ed == plan.gaussian_ed) return ORBFE_OK;
+        ExtractorPlan fresh = plan_extractor(rows_, cols_, nlevels, mvScaleFactor.data(), mvInvScaleFactor.data(), mnFeaturesPerLevel.data(), gaussian_ed);
+        if (fresh.err) return fail(fresh.err, "%s", fresh.msg);
+        const bool resized = rows_ != plan.rows || cols_ != plan.cols;
+        plan = ExtractorPlan{};
+        last_nframes = 0;
         int rc;
-        if ((rc = d_bstrips.ensure(st.size() * sizeof(BlurStrip))) || (rc = d_btabs.ensure(tabs.size())) || (rc = d_btab2.ensure(t2.size()))) return rc;
-        ORBFE_HIP(hipMemcpy(d_bstrips.p, st.data(), st.size() * sizeof(BlurStrip), hipMemcpyHostToDevice));
-        ORBFE_HIP(hipMemcpy(d_btabs.p, tabs.data(), tabs.size(), hipMemcpyHostToDevice));
-        ORBFE_HIP(hipMemcpy(d_btab2.p, t2.data(), t2.size(), hipMemcpyHostToDevice));
+        if ((rc = upload(d_geom, fresh.geom)) || (rc = upload(d_cellinfo, fresh.cellinfo)) || (rc = upload(d_tabs, fresh.resize_tabs)) ||
+            (rc = upload(d_bstrips, fresh.blur_strips)) || (rc = upload(d_btabs, fresh.blur_tabs)) || (rc = upload(d_btab2, fresh.blur_tab2)))
+            return rc;
+        if (resized) batch_cap = 0;   // the per-frame blocks have other sizes: the workspace is allocated again
+        plan = std::move(fresh);
         return ORBFE_OK;
     }
 
@@ -430,12 +220,12 @@ struct orbfe_extractor {
     {
         if (B <= batch_cap) return ORBFE_OK;
         int rc;
-        if ((rc = d_pyr.ensure(pyr_fbytes * B))) return rc;
-        if ((rc = d_blur.ensure(blur_fbytes * B))) return rc;
-        if ((rc = d_slots.ensure(slots_fu32 * 4 * B))) return rc;
-        if ((rc = d_cellcnt.ensure((size_t)ncells_total * 4 * B))) return rc;
-        if ((rc = d_keys.ensure(keys_fu32 * 4 * B))) return rc;
-        if ((rc = d_lvlout.ensure((size_t)out_total * 4 * B))) return rc;
+        if ((rc = d_pyr.ensure(plan.pyr_fbytes * B))) return rc;
+        if ((rc = d_blur.ensure(plan.blur_fbytes * B))) return rc;
+        if ((rc = d_slots.ensure(plan.slots_fu32 * 4 * B))) return rc;
+        if ((rc = d_cellcnt.ensure((size_t)plan.ncells_total * 4 * B))) return rc;
+        if ((rc = d_keys.ensure(plan.keys_fu32 * 4 * B))) return rc;
+        if ((rc = d_lvlout.ensure((size_t)plan.out_total * 4 * B))) return rc;
         if ((rc = d_lvlcnt.ensure((size_t)nlevels * 4 * B))) return rc;
         if ((rc = d_lvloff.ensure((size_t)nlevels * 4 * B))) return rc;
         if ((rc = d_lvlncand.ensure((size_t)nlevels * 4 * B))) return rc;
@@ -452,41 +242,114 @@ struct orbfe_extractor {
         return ORBFE_OK;
     }
 
+    // What a batch of B frames launches, decided once; and everything that can fail -- the workspace, the flat keypoint list of
+    // `capacity` a frame, the kernels' dynamic LDS -- before the batch's first launch
+    int plan_batch(int B, int capacity, BatchPlan& p)
+    {
+        const int T = gaussian_ed ? 256 : 257;
+        p.blur_K2 = 128 * T * T + 32768;
+        p.blur_nx = ((int)plan.blur_strips.size() + 3) / 4;
+        // FAST, LDS per wave: ROI (cell + 6), score map (cell + 2), one u16 list of cell pixels
+        p.roi_pitch = align_up(plan.max_wcell + 6 + 4, 4) + 8; p.roi_rows = plan.max_hcell + 6; // +1 byte shift, +2 dwords read past a row (8-pixel groups)
+        p.map_pitch = plan.max_wcell + 2; p.map_rows = plan.max_hcell + 2;
+        p.list_cap = plan.max_wcell * plan.max_hcell;
+        auto a16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+        p.fast_lds = 4 * (a16((size_t)p.roi_pitch * p.roi_rows) + a16((size_t)p.map_pitch * p.map_rows) + a16((size_t)p.list_cap * 2));
+        p.fast_nx = (plan.ncells_total + 3) / 4;   // (every level has at least one cell: plan_levels)
+        // depth of the count pyramid: 1024 (2048) leaves for a level's 217 (434) nodes.  Its LDS decides how many of the
+        // nlevels x B workgroups are resident at once, and this kernel sits alone on the extractor's critical path: with six
+        // levels (4096 leaves, 54 KB, two workgroups per CU) the 2400 workgroups of a C2 batch ran in five rounds, 225 us;
+        // a level that needs more depth is flagged and redone by the general kernel
+        p.D = force_pyramid_depth ? force_pyramid_depth : plan.max_ini <= 4 ? 5 : 4;
+        p.qp_lds = qp_lds_bytes(plan.max_ini, p.D, plan.nodecap, plan.veccap);
+        // (the work-list launch keeps its keys in the HBM scratch: a workgroup that asks for 50 KB of LDS it will almost never use
+        //  waits for the CU's other tenants -- 87 us behind the detector's threshold kernel, with an EMPTY list)
+        p.qcap = force_general_quadtree ? plan.keycap_lds : 0;
+        p.qt_lds = qt_lds_bytes(p.qcap, plan.nodecap, plan.veccap);
+        // the general kernel drains the work list with a small grid (a launch of nlevels x B workgroups of this much LDS that found
+        // nothing to do cost the chain 73 us); the test hook runs it for every level, a workgroup each
+        p.qgrid = force_general_quadtree ? dim3(nlevels, B) : dim3(std::min(nlevels * B, 128));
+        p.okx = (std::min(capacity, max_keypoints()) + 7) / 8;   // 4 waves of two keypoints
+        int rc;
+        if ((rc = ensure_workspace(B)) || (rc = d_flatkv.ensure((size_t)B * capacity * 4)) || (rc = d_flatlvl.ensure((size_t)B * capacity))) return rc;
+        if ((rc = ensure_dyn_lds(reinterpret_cast<const void*>(&k_fast_cells), p.fast_lds)) ||
+            (rc = ensure_dyn_lds(reinterpret_cast<const void*>(&k_distribute_pyr), p.qp_lds)) ||
+            (rc = ensure_dyn_lds(reinterpret_cast<const void*>(&k_distribute), qt_lds_bytes(plan.keycap_lds, plan.nodecap, plan.veccap))))
+            return rc;
+        return ORBFE_OK;
+    }
+
+    // queue on `st` a wait for stage k (1 .. 4 as in follow_stage; 0 = no gate) of h's newest batch.  No wait when h is null or is
+    // `self` (a handle is not gated by itself), nor before h's front part has been enqueued once.
+    static int wait_stage(const orbfe_extractor* h, int k, hipStream_t st, const orbfe_extractor* self = nullptr)
+    {
+        if (h && h != self && h->stage_recorded && k >= 1 && k <= 4 && h->ev_stage[k - 1]) ORBFE_HIP(hipStreamWaitEvent(st, h->ev_stage[k - 1], 0));
+        return ORBFE_OK;
+    }
+    // stage k (as in follow_stage) of the batch being enqueued is complete at this point of `s`
+    int stage_event(int k, hipStream_t s)
+    {
+        if (!ev_stage[k - 1]) ORBFE_HIP(hipEventCreateWithFlags(&ev_stage[k - 1], hipEventDisableTiming));
+        ORBFE_HIP(hipEventRecord(ev_stage[k - 1], s));
+        return ORBFE_OK;
+    }
+
     // The batched pipeline: every launch covers all frames.  Asynchronous on `s`.
+    // flag_word: 0 = the sticky flag of the device-pointer batches (orbfe_extractor_batch_status), 1 = the host-pointer entry
+    // points' own word (they own their whole call, so a device batch's unread flag must not fail them)
     int run_device(const uint8_t* d_imgs, int B, size_t frame_stride, int rows_, int cols_, size_t step,
                    orbfe_keypoint* d_kps_out, uint8_t* d_desc_out, int capacity, int32_t* d_n, hipStream_t s, int flag_word = 0)
     {
-        // flag_word: 0 = the sticky flag of the device-pointer batches (orbfe_extractor_batch_status), 1 = the host-pointer entry
-        // points' own word (they own their whole call, so a device batch's unread flag must not fail them)
         int rc;
         // a batch whose descriptors are still owed (the pipeline defers them by a step) gets them before its buffers are used again
         if (late.pending && (rc = describe_deferred(nullptr, 0))) return rc;
-        if ((rc = build_geometry(rows_, cols_))) return rc;
-        if ((rc = ensure_workspace(B))) return rc;
-        if ((rc = build_blur_tables())) return rc;
-        ImgView src0{d_imgs, nullptr, frame_stride, (int)step};
-        ImgView pyr{d_pyr.as<uint8_t>(), d_pyr.as<uint8_t>(), pyr_fbytes, 0};
-        ImgView blur{d_blur.as<uint8_t>(), d_blur.as<uint8_t>(), blur_fbytes, 0};
-        const LevelGeom* dg = d_geom.as<LevelGeom>();
+        BatchPlan p;
+        if ((rc = ensure_plan(rows_, cols_)) || (rc = plan_batch(B, capacity, p))) return rc;
+        const ImgView src0{d_imgs, nullptr, frame_stride, (int)step};
         last_nframes = B;
         last_src0 = src0;
         timer.begin();
         if ((rc = wait_stage(follow, follow_stage, s, this))) return rc;
         timer.mark(s, "start");
-        for (int r16_ = 0; r16_ < ORBFE_REPS_ORB(16); r16_++)
+        for (int r_ = 0; r_ < ORBFE_REPS_ORB(16); r_++) resize_chain(src0, B, s);
+        timer.mark(s, "resize");
+        if ((rc = stage_event(4, s))) return rc;   // the pyramid is there, FAST starts
+        if ((rc = blur_fork(p, src0, B, s))) return rc;
+        if ((rc = wait_stage(follow, follow_fast_stage, s, this))) return rc;
+        for (int r_ = 0; r_ < ORBFE_REPS_ORB(1); r_++) fast(p, src0, B, s);
+        timer.mark(s, "fast_cells");
+        if ((rc = stage_event(1, s))) return rc;
+        quadtree(p, B, s);
+        timer.mark(s, "distribute");
+        if ((rc = stage_event(2, s))) return rc;
+        level_offsets(B, capacity, d_n, flag_word, s);
+        ORBFE_HIP(hipStreamWaitEvent(s, ev_join, 0));   // the blur joins: the descriptors read it
+        stage_recorded = true;
+        // the descriptors: here, or -- extractor_defer_describe(), the batched pipeline -- when the caller says so (describe_deferred())
+        late = Late{true, src0, B, capacity, p.okx, d_kps_out, d_desc_out, d_n, s};
+        return defer_describe ? ORBFE_OK : describe_deferred(nullptr, 0);
+    }
+
+    ImgView pyr_view() const { return ImgView{d_pyr.as<uint8_t>(), d_pyr.as<uint8_t>(), plan.pyr_fbytes, 0}; }
+    ImgView blur_view() const { return ImgView{d_blur.as<uint8_t>(), d_blur.as<uint8_t>(), plan.blur_fbytes, 0}; }
+
+    // the pyramid: level l from level l - 1, a launch each
+    void resize_chain(const ImgView& src0, int B, hipStream_t s)
+    {
+        const ImgView pyr = pyr_view();
         for (int l = 1; l < nlevels; l++) {
-            const LevelGeom& g = geom[l];
-            const LevelGeom& gp = geom[l - 1];
-            ImgView sv = (l == 1) ? src0 : ImgView{pyr.base + gp.img_off, nullptr, pyr_fbytes, gp.pitch};
-            ImgView dv{pyr.base + g.img_off, pyr.base_w + g.img_off, pyr_fbytes, g.pitch};
+            const LevelGeom& g = plan.geom[l];
+            const LevelGeom& gp = plan.geom[l - 1];
+            ImgView sv = (l == 1) ? src0 : ImgView{pyr.base + gp.img_off, nullptr, plan.pyr_fbytes, gp.pitch};
+            ImgView dv{pyr.base + g.img_off, pyr.base_w + g.img_off, plan.pyr_fbytes, g.pitch};
             const int dw4 = (g.w + 3) / 4;
-            if (resize_tab_ok[l]) {
+            if (plan.resize_tab_ok[l]) {
                 const int nthreads = dw4 * ((g.h + RS_ROWS - 1) / RS_ROWS);
                 const int* tb = d_tabs.as<int>();
                 const int nx = (nthreads + 255) / 256;
                 hipLaunchKernelGGL(k_resize_tab, dim3(xcd_grid(nx * B)), dim3(256), 0, s, sv, dv, gp.w, gp.h, dw4,
-                                   g.h, nthreads, tb + tab_off[l * 4 + 0], tb + tab_off[l * 4 + 1],
-                                   reinterpret_cast<const int4*>(tb + tab_off[l * 4 + 2]), nx, nx * B);
+                                   g.h, nthreads, tb + plan.tab_off[l * 3 + 0], tb + plan.tab_off[l * 3 + 1],
+                                   reinterpret_cast<const int4*>(tb + plan.tab_off[l * 3 + 2]), nx, nx * B);
             } else {
                 dim3 grid((dw4 + 63) / 64, (g.h + 7) / 8, B);
                 const double scale_x = 1. / ((double)g.w / gp.w), scale_y = 1. / ((double)g.h / gp.h);
@@ -494,116 +357,61 @@ struct orbfe_extractor {
                                    g.w);
             }
         }
-        timer.mark(s, "resize");
-        {   // stage 4: the pyramid is there, FAST starts
-            if (!ev_stage[3]) ORBFE_HIP(hipEventCreateWithFlags(&ev_stage[3], hipEventDisableTiming));
-            ORBFE_HIP(hipEventRecord(ev_stage[3], s));
-        }
-        // The blur only needs the pyramid, and only k_orient_describe needs the blur: it runs on a second stream, forked in front of
-        // FAST.  Measured on the C2 batch (step time with the detector running / extractor alone, ms): fork in front of FAST 1.83 /
-        // 1.76, fork after FAST (blur next to the quadtree) 1.88 / 1.76, no fork 1.97 / 1.75 (again in round 6: tools/sweeps.md).
-        hipStream_t aux_stream = user_aux ? user_aux : this->aux_stream;
-        // strips [first, first + count) of the strip list (level-major: level 0's strips come first)
-        auto blur_strips = [&](int first, int count) {
-            if (count <= 0) return;
-            if (gaussian_ed)
-                hipLaunchKernelGGL(k_blur7<true>, dim3(xcd_grid(count * B)), dim3(256), 0, aux_stream, src0, pyr, blur, dg,
-                                   d_tiles.as<uint32_t>() + first, count, count * B);
-            else
-                hipLaunchKernelGGL(k_blur7<false>, dim3(xcd_grid(count * B)), dim3(256), 0, aux_stream, src0, pyr, blur, dg,
-                                   d_tiles.as<uint32_t>() + first, count, count * B);
-        };
-        auto launch_blur = [&]() -> int {
-            ORBFE_HIP(hipEventRecord(ev_fork, s));
-            ORBFE_HIP(hipStreamWaitEvent(aux_stream, ev_fork, 0));
-            timer.mark(aux_stream, "blur7 starts", true);
-            for (int r_ = 0; r_ < ORBFE_REPS_ORB(8); r_++) {
-                if (blur_mfma && blur_mfma_ok) {   // the matrix-core kernel (a wave per 32-column strip, four to a workgroup)
-                    const int T = gaussian_ed ? 256 : 257, nxb = (n_bstrips + 3) / 4;
-                    hipLaunchKernelGGL(k_blur7_mfma, dim3(xcd_grid(nxb * B)), dim3(256), 0, aux_stream, src0, pyr, blur, dg, d_bstrips.as<BlurStrip>(),
-                                       d_btabs.as<uint4>(), d_btab2.as<uint4>(), 128 * T * T + 32768, n_bstrips, nxb, nxb * B);
-                } else
-                    blur_strips(0, ntiles);
-            }
-            timer.mark(aux_stream, "blur7");
-            ORBFE_HIP(hipEventRecord(ev_join, aux_stream));
-            return ORBFE_OK;
-        };
-        if ((rc = launch_blur())) return rc;
-        if ((rc = wait_stage(follow, follow_fast_stage, s, this))) return rc;
-        {
-            // LDS per wave: ROI (cell + 6), score map (cell + 2), one u16 list of cell pixels
-            const int roi_pitch = align_up(max_wcell + 6 + 4, 4) + 8, roi_rows = max_hcell + 6; // +1 byte shift, +2 dwords read past a row (8-pixel groups)
-            const int map_pitch = max_wcell + 2, map_rows = max_hcell + 2;
-            const int list_cap = max_wcell * max_hcell;
-            auto a16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-            const size_t lds = 4 * (a16((size_t)roi_pitch * roi_rows) + a16((size_t)map_pitch * map_rows) +
-                                    a16((size_t)list_cap * 2));
-            if ((rc = ensure_dyn_lds(reinterpret_cast<const void*>(&k_fast_cells), lds))) return rc;
-            const int nx = (ncells_total + 3) / 4;   // (every level has at least one cell: build_geometry)
-            for (int r_ = 0; r_ < ORBFE_REPS_ORB(1); r_++) hipLaunchKernelGGL(k_fast_cells, dim3(xcd_grid(nx * B)), dim3(256), lds, s, src0, pyr, dg,
-                               d_cellinfo.as<uint32_t>(), d_slots.as<uint32_t>(), slots_fu32,
-                               d_cellcnt.as<int32_t>(), ncells_total, iniThFAST, minThFAST, roi_pitch, roi_rows,
-                               map_pitch, map_rows, list_cap, nx, nx * B, 0, ncells_total);
-        }
-        timer.mark(s, "fast_cells");
-        auto stage_event = [&](int k) -> int {
-            if (!ev_stage[k]) ORBFE_HIP(hipEventCreateWithFlags(&ev_stage[k], hipEventDisableTiming));
-            ORBFE_HIP(hipEventRecord(ev_stage[k], s));
-            return ORBFE_OK;
-        };
-        if ((rc = stage_event(0))) return rc;
-        {
-            // fast path: count-pyramid quadtree (no keypoint movement); general kernel only for flagged levels
-            int max_ini = 1;
-            for (const LevelGeom& g : geom) max_ini = std::max(max_ini, g.nIni);
-            // depth of the count pyramid: 1024 (2048) leaves for a level's 217 (434) nodes.  Its LDS decides how many of the
-            // nlevels x B workgroups are resident at once, and this kernel sits alone on the extractor's critical path: with six
-            // levels (4096 leaves, 54 KB, two workgroups per CU) the 2400 workgroups of a C2 batch ran in five rounds, 225 us;
-            // a level that needs more depth is flagged and redone by the general kernel
-            const int D = force_pyramid_depth ? force_pyramid_depth : max_ini <= 4 ? 5 : 4;
-            const size_t lds_p = qp_lds_bytes(max_ini, D, nodecap, veccap);
-            { int rc_lds_ = ensure_dyn_lds(reinterpret_cast<const void*>(&k_distribute_pyr), (size_t)(lds_p)); if (rc_lds_) return rc_lds_; }
-            const int by_level = 0;   // (frames x levels, every frame's level 0 first: 1.419 against 1.420 ms per C2 step, ten interleaved runs each)
-            for (int r_ = 0; r_ < ORBFE_REPS_ORB(2); r_++) hipLaunchKernelGGL(k_distribute_pyr, by_level ? dim3(B, nlevels) : dim3(nlevels, B), dim3(QP_THREADS), lds_p, s, dg, d_slots.as<uint32_t>(),
-                               slots_fu32, d_cellcnt.as<int32_t>(), ncells_total, d_lvlout.as<uint32_t>(), out_total,
-                               d_lvlcnt.as<int32_t>(), nlevels, d_lvlncand.as<int32_t>(), d_fallback.as<int32_t>(), D,
-                               nodecap, veccap, d_worklist.as<int32_t>() + 4, d_worklist.as<int32_t>(), by_level);
-            // (the work-list launch keeps its keys in the HBM scratch: a workgroup that asks for 50 KB of LDS it will almost never use
-            //  waits for the CU's other tenants -- 87 us behind the detector's threshold kernel, with an EMPTY list)
-            const int qcap = force_general_quadtree ? keycap_lds : 0;
-            const size_t lds = qt_lds_bytes(qcap, nodecap, veccap);
-            { int rc_lds_ = ensure_dyn_lds(reinterpret_cast<const void*>(&k_distribute), qt_lds_bytes(keycap_lds, nodecap, veccap)); if (rc_lds_) return rc_lds_; }
-            // the general kernel drains the work list with a small grid (a launch of nlevels x B workgroups of this much LDS that found
-            // nothing to do cost the chain 73 us); the test hook runs it for every level, a workgroup each
-            const dim3 qgrid = force_general_quadtree ? dim3(nlevels, B) : dim3(std::min(nlevels * B, 128));
-            hipLaunchKernelGGL(k_distribute, qgrid, dim3(64), lds, s, dg, d_slots.as<uint32_t>(), slots_fu32,
-                               d_cellcnt.as<int32_t>(), ncells_total, d_keys.as<uint32_t>(), keys_fu32,
-                               d_lvlout.as<uint32_t>(), out_total, d_lvlcnt.as<int32_t>(), nlevels,
-                               d_lvlncand.as<int32_t>(), qcap, nodecap, veccap,
-                               force_general_quadtree ? nullptr : d_worklist.as<int32_t>() + 4, d_worklist.as<int32_t>());
-        }
-        timer.mark(s, "distribute");
-        if ((rc = stage_event(1))) return rc;
-        {
-            int rc2;
-            if ((rc2 = d_flatkv.ensure((size_t)B * capacity * 4)) || (rc2 = d_flatlvl.ensure((size_t)B * capacity))) return rc2;
-        }
+    }
+
+    // The blur only needs the pyramid, and only k_orient_describe2 needs the blur: it runs on a second stream, forked in front of
+    // FAST (run_device joins it in front of the descriptors).  Measured on the C2 batch (step time with the detector running /
+    // extractor alone, ms): fork in front of FAST 1.83 / 1.76, fork after FAST (blur next to the quadtree) 1.88 / 1.76, no fork
+    // 1.97 / 1.75 (again in round 6: tools/sweeps.md).  The matrix-core kernel: a wave per 32-column strip, four to a workgroup.
+    int blur_fork(const BatchPlan& p, const ImgView& src0, int B, hipStream_t s)
+    {
+        hipStream_t aux = user_aux ? user_aux : aux_stream;
+        ORBFE_HIP(hipEventRecord(ev_fork, s));
+        ORBFE_HIP(hipStreamWaitEvent(aux, ev_fork, 0));
+        timer.mark(aux, "blur7 starts", true);
+        for (int r_ = 0; r_ < ORBFE_REPS_ORB(8); r_++)
+            hipLaunchKernelGGL(k_blur7_mfma, dim3(xcd_grid(p.blur_nx * B)), dim3(256), 0, aux, src0, pyr_view(), blur_view(), d_geom.as<LevelGeom>(),
+                               d_bstrips.as<BlurStrip>(), d_btabs.as<uint4>(), d_btab2.as<uint4>(), p.blur_K2, (int)plan.blur_strips.size(),
+                               p.blur_nx, p.blur_nx * B);
+        timer.mark(aux, "blur7");
+        ORBFE_HIP(hipEventRecord(ev_join, aux));
+        return ORBFE_OK;
+    }
+
+    void fast(const BatchPlan& p, const ImgView& src0, int B, hipStream_t s)
+    {
+        hipLaunchKernelGGL(k_fast_cells, dim3(xcd_grid(p.fast_nx * B)), dim3(256), p.fast_lds, s, src0, pyr_view(), d_geom.as<LevelGeom>(),
+                           d_cellinfo.as<uint32_t>(), d_slots.as<uint32_t>(), plan.slots_fu32,
+                           d_cellcnt.as<int32_t>(), plan.ncells_total, iniThFAST, minThFAST, p.roi_pitch, p.roi_rows,
+                           p.map_pitch, p.map_rows, p.list_cap, p.fast_nx, p.fast_nx * B, 0, plan.ncells_total);
+    }
+
+    // fast path: count-pyramid quadtree (no keypoint movement); general kernel only for flagged levels (the work list)
+    void quadtree(const BatchPlan& p, int B, hipStream_t s)
+    {
+        const LevelGeom* dg = d_geom.as<LevelGeom>();
+        // (grid = levels x frames; frames x levels, every frame's level 0 first: 1.419 against 1.420 ms per C2 step, ten interleaved runs each)
+        for (int r_ = 0; r_ < ORBFE_REPS_ORB(2); r_++)
+            hipLaunchKernelGGL(k_distribute_pyr, dim3(nlevels, B), dim3(QP_THREADS), p.qp_lds, s, dg, d_slots.as<uint32_t>(),
+                               plan.slots_fu32, d_cellcnt.as<int32_t>(), plan.ncells_total, d_lvlout.as<uint32_t>(), plan.out_total,
+                               d_lvlcnt.as<int32_t>(), nlevels, d_lvlncand.as<int32_t>(), d_fallback.as<int32_t>(), p.D,
+                               plan.nodecap, plan.veccap, d_worklist.as<int32_t>() + 4, d_worklist.as<int32_t>(), /*by_level*/ 0);
+        hipLaunchKernelGGL(k_distribute, p.qgrid, dim3(64), p.qt_lds, s, dg, d_slots.as<uint32_t>(), plan.slots_fu32,
+                           d_cellcnt.as<int32_t>(), plan.ncells_total, d_keys.as<uint32_t>(), plan.keys_fu32,
+                           d_lvlout.as<uint32_t>(), plan.out_total, d_lvlcnt.as<int32_t>(), nlevels,
+                           d_lvlncand.as<int32_t>(), p.qcap, plan.nodecap, plan.veccap,
+                           force_general_quadtree ? nullptr : d_worklist.as<int32_t>() + 4, d_worklist.as<int32_t>());
+    }
+
+    // per frame: the levels' offsets in the output, the keypoint count, the flat (key, level) list of the descriptor kernel
+    void level_offsets(int B, int capacity, int32_t* d_n, int flag_word, hipStream_t s)
+    {
         hipLaunchKernelGGL(k_level_offsets, dim3(B), dim3(256), 0, s, d_lvlcnt.as<int32_t>(), d_lvloff.as<int32_t>(),
-                           d_n, nlevels, B, capacity, d_overflow.as<int32_t>() + flag_word, dg, d_lvlout.as<uint32_t>(), out_total,
-                           d_flatkv.as<uint32_t>(), d_flatlvl.as<uint8_t>(), d_worklist.as<int32_t>());
-        ORBFE_HIP(hipStreamWaitEvent(s, ev_join, 0));
-        stage_recorded = true;
-        // the descriptors: here, or -- extractor_defer_describe(), the batched pipeline -- when the caller says so (describe_deferred())
-        late = Late{true, src0, B, capacity, d_kps_out, d_desc_out, d_n, s};
-        if (defer_describe) return ORBFE_OK;
-        return describe_deferred(nullptr, 0);
+                           d_n, nlevels, B, capacity, d_overflow.as<int32_t>() + flag_word, d_geom.as<LevelGeom>(), d_lvlout.as<uint32_t>(),
+                           plan.out_total, d_flatkv.as<uint32_t>(), d_flatlvl.as<uint8_t>(), d_worklist.as<int32_t>());
     }
 
     // k_orient_describe2 of the newest batch, behind stage `gate_stage` of `gate`'s newest batch if one is named
-    struct Late { bool pending; ImgView src0; int B, capacity; orbfe_keypoint* kps; uint8_t* desc; int32_t* n; hipStream_t s; };
-    Late late{};
-    bool defer_describe = false;
     int describe_deferred(orbfe_extractor* gate, int gate_stage)
     {
         if (!late.pending) return ORBFE_OK;
@@ -611,16 +419,12 @@ struct orbfe_extractor {
         hipStream_t s = late.s;
         int rc;
         if ((rc = wait_stage(gate, gate_stage, s, this))) return rc;
-        ImgView pyr{d_pyr.as<uint8_t>(), d_pyr.as<uint8_t>(), pyr_fbytes, 0};
-        ImgView blur{d_blur.as<uint8_t>(), d_blur.as<uint8_t>(), blur_fbytes, 0};
-        const int kcap_ = std::min(late.capacity, max_keypoints());
-        const int okx = (kcap_ + 7) / 8;   // workgroups per frame: 4 waves of two keypoints
-        for (int r_ = 0; r_ < ORBFE_REPS_ORB(4); r_++) hipLaunchKernelGGL(k_orient_describe2, dim3(xcd_grid(okx * late.B)), dim3(256), 0, s, late.src0, pyr, blur, d_geom.as<LevelGeom>(),
-                           d_flatkv.as<uint32_t>(), d_flatlvl.as<uint8_t>(), late.n, nlevels, d_pattern.as<uint32_t>(),
-                           d_umax.as<uint4>(), late.kps, late.desc, late.capacity, okx, okx * late.B);
+        for (int r_ = 0; r_ < ORBFE_REPS_ORB(4); r_++)
+            hipLaunchKernelGGL(k_orient_describe2, dim3(xcd_grid(late.okx * late.B)), dim3(256), 0, s, late.src0, pyr_view(), blur_view(),
+                               d_geom.as<LevelGeom>(), d_flatkv.as<uint32_t>(), d_flatlvl.as<uint8_t>(), late.n, nlevels, d_pattern.as<uint32_t>(),
+                               d_umax.as<uint4>(), late.kps, late.desc, late.capacity, late.okx, late.okx * late.B);
         timer.mark(s, "orient_describe");
-        if (!ev_stage[2]) ORBFE_HIP(hipEventCreateWithFlags(&ev_stage[2], hipEventDisableTiming));
-        ORBFE_HIP(hipEventRecord(ev_stage[2], s));
+        if ((rc = stage_event(3, s))) return rc;
         ORBFE_HIP(hipGetLastError());
         return ORBFE_OK;
     }
@@ -800,9 +604,9 @@ int orbfe_extract(orbfe_extractor* h, const uint8_t* img, int rows, int cols, si
 
 int orbfe_extractor_debug_level_size(orbfe_extractor* h, int level, int* w, int* hgt)
 {
-    if (!h || level < 0 || level >= h->nlevels || h->geom.empty()) return fail(ORBFE_ERR_INVALID, "no geometry");
-    *w = h->geom[level].w;
-    *hgt = h->geom[level].h;
+    if (!h || level < 0 || level >= h->nlevels || h->plan.geom.empty()) return fail(ORBFE_ERR_INVALID, "no geometry");
+    *w = h->plan.geom[level].w;
+    *hgt = h->plan.geom[level].h;
     return ORBFE_OK;
 }
 
@@ -812,12 +616,12 @@ int orbfe_extractor_debug_level_image(orbfe_extractor* h, int frame, int level, 
         return fail(ORBFE_ERR_INVALID, "debug_level_image: invalid argument");
     int rc = use_device(h->device);
     if (rc) return rc;
-    const LevelGeom& g = h->geom[level];
+    const LevelGeom& g = h->plan.geom[level];
     const uint8_t* src;
     size_t pitch;
-    if (stage == 1) { src = h->d_blur.as<uint8_t>() + frame * h->blur_fbytes + g.blur_off; pitch = g.bpitch; }
+    if (stage == 1) { src = h->d_blur.as<uint8_t>() + frame * h->plan.blur_fbytes + g.blur_off; pitch = g.bpitch; }
     else if (level == 0) { src = h->last_src0.base + frame * h->last_src0.fstride; pitch = h->last_src0.pitch; }
-    else { src = h->d_pyr.as<uint8_t>() + frame * h->pyr_fbytes + g.img_off; pitch = g.pitch; }
+    else { src = h->d_pyr.as<uint8_t>() + frame * h->plan.pyr_fbytes + g.img_off; pitch = g.pitch; }
     ORBFE_HIP(hipDeviceSynchronize());
     ORBFE_HIP(hipMemcpy2D(out, g.w, src, pitch, g.w, g.h, hipMemcpyDeviceToHost));
     return ORBFE_OK;
@@ -831,7 +635,7 @@ int orbfe_extractor_debug_level_keypoints(orbfe_extractor* h, int frame, int lev
     int rc = use_device(h->device);
     if (rc) return rc;
     ORBFE_HIP(hipDeviceSynchronize());
-    const LevelGeom& g = h->geom[level];
+    const LevelGeom& g = h->plan.geom[level];
     std::vector<uint32_t> keys;
     if (stage == 2) { // raw per-level candidate counter written by k_distribute (instrumented builds pack timings here)
         ORBFE_HIP(hipMemcpy(n, h->d_lvlncand.as<int32_t>() + frame * h->nlevels + level, 4, hipMemcpyDeviceToHost));
@@ -843,10 +647,10 @@ int orbfe_extractor_debug_level_keypoints(orbfe_extractor* h, int frame, int lev
     }
     if (stage == 0) {
         std::vector<int32_t> cnt(g.ncells);
-        ORBFE_HIP(hipMemcpy(cnt.data(), h->d_cellcnt.as<int32_t>() + (size_t)frame * h->ncells_total + g.cell_first,
+        ORBFE_HIP(hipMemcpy(cnt.data(), h->d_cellcnt.as<int32_t>() + (size_t)frame * h->plan.ncells_total + g.cell_first,
                             (size_t)g.ncells * 4, hipMemcpyDeviceToHost));
         std::vector<uint32_t> slots((size_t)g.cand_cap);
-        ORBFE_HIP(hipMemcpy(slots.data(), h->d_slots.as<uint32_t>() + (size_t)frame * h->slots_fu32 + g.slot_off,
+        ORBFE_HIP(hipMemcpy(slots.data(), h->d_slots.as<uint32_t>() + (size_t)frame * h->plan.slots_fu32 + g.slot_off,
                             slots.size() * 4, hipMemcpyDeviceToHost));
         for (int c = 0; c < g.ncells; c++)
             for (int k = 0; k < cnt[c]; k++) keys.push_back(slots[(size_t)c * g.cell_cap + k]);
@@ -855,7 +659,7 @@ int orbfe_extractor_debug_level_keypoints(orbfe_extractor* h, int frame, int lev
         ORBFE_HIP(hipMemcpy(&c, h->d_lvlcnt.as<int32_t>() + frame * h->nlevels + level, 4, hipMemcpyDeviceToHost));
         keys.resize(c);
         if (c)
-            ORBFE_HIP(hipMemcpy(keys.data(), h->d_lvlout.as<uint32_t>() + (size_t)frame * h->out_total + g.out_off,
+            ORBFE_HIP(hipMemcpy(keys.data(), h->d_lvlout.as<uint32_t>() + (size_t)frame * h->plan.out_total + g.out_off,
                                 (size_t)c * 4, hipMemcpyDeviceToHost));
     }
     *n = (int32_t)keys.size();
@@ -922,7 +726,6 @@ int orbfe_extractor_debug_control(orbfe_extractor* h, const char* key, int value
     if (!strcmp(key, "kernel_timing") && on_off) { h->timer.enabled = value; h->timer.reset_history(); }
     else if (!strcmp(key, "general_quadtree") && on_off) h->force_general_quadtree = value;
     else if (!strcmp(key, "pyramid_depth") && value >= 0 && value <= 6) h->force_pyramid_depth = value;   // 0 = by the levels' node counts
-    else if (!strcmp(key, "blur_mfma") && on_off) h->blur_mfma = value;   // the blur on the matrix cores (default) / k_blur7
     else return fail(ORBFE_ERR_INVALID, "orbfe_extractor_debug_control: unknown key \"%s\" or value %d", key, value);
     return ORBFE_OK;
 }

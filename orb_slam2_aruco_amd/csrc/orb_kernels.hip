@@ -1369,8 +1369,6 @@ __global__ __launch_bounds__(256) void k_level_offsets(const int32_t* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------ blur ----
-// GaussianBlur 7x7 sigma 2, taps 18 34 49 55 49 34 18 (x256, sum 257), BORDER_REFLECT_101,
-// out = sat_u8((sum + 32768) >> 16).  64x64 output tile per workgroup (four 64x16 strips), separable through LDS.
 __device__ __forceinline__ int reflect101(int p, int n)
 {
     if (n == 1) return 0;
@@ -1378,186 +1376,7 @@ __device__ __forceinline__ int reflect101(int p, int n)
     return p;
 }
 
-// Instruction count, not bandwidth, limits this kernel, so both passes run on the packed dot-product instructions:
-//   horizontal: a thread loads the 12 bytes around 4 adjacent outputs of one row as three dwords; every 7-tap sum is
-//               two v_dot4_u32_u8 on byte windows cut out with v_alignbyte (sums <= 257 * 255 fit 16 bits);
-//   transpose:  the sums go to LDS column-major (one column = 70 consecutive u16), so that
-//   vertical:   a thread takes one column and 4 consecutive rows, reads ten sums as five dwords and forms each output
-//               from four v_dot2_u32_u16 on (row, row+1) pairs; odd rows use pairs re-cut with v_alignbit.
-#define BL_CP 74 // u16 per LDS column: 70 rows + pad, an odd number of dwords (conflict-free across columns)
-
 __device__ __forceinline__ uint32_t bl_dot4(uint32_t a, uint32_t b, uint32_t c) { return __builtin_amdgcn_udot4(a, b, c, false); }
-__device__ __forceinline__ uint32_t bl_dot2(uint32_t a, uint32_t b, uint32_t c)
-{
-    return __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b), c, false);
-}
-
-// right-border windows of bl_load_rows: v_perm selectors of the three window dwords and which dword pair each takes ({l1, l0} = 0,
-// {l2, l1} = 1; bits 0..2), indexed by r = w - x
-__device__ const uint4 bl_right_tab[8] = {
-    {0x00000000u, 0x00000000u, 0x00000000u, 0u},
-    {0x06050403u, 0x04050607u, 0x04050607u, 3u}, // r = 1
-    {0x05040302u, 0x05060706u, 0x01020304u, 7u}, // r = 2
-    {0x04030201u, 0x06070605u, 0x02030405u, 7u}, // r = 3
-    {0x07060504u, 0x07060504u, 0x03040506u, 6u}, // r = 4
-    {0x06050403u, 0x06050403u, 0x04050607u, 6u}, // r = 5
-    {0x05040302u, 0x05040302u, 0x05060706u, 6u}, // r = 6
-    {0x04030201u, 0x04030201u, 0x06070605u, 6u}, // r = 7
-};
-
-// One workgroup = one 64-column strip of a level, walked top to bottom in 64-row tiles.  The loads of the next tile's
-// rows are in flight while the vertical pass of the current one runs, and the six rows of horizontal sums two tiles
-// share are carried over in LDS instead of being recomputed, so every source row is fetched once per strip.
-__device__ __forceinline__ void bl_load_rows(const uint8_t* img, int pitch, const LevelGeom& g, int tx0, int row0,
-                                             int first_rr, int nrr, int tid, int nitems, uint32_t (*w)[3])
-{
-    typedef uint32_t u32_unaligned __attribute__((aligned(1))); // level 0 is the caller's buffer
-#pragma unroll
-    for (int k = 0; k < 5; k++) {
-        if (k >= nitems) break;
-        const int it = tid + 256 * k;
-        const int rr = first_rr + (it >> 4), x = tx0 + 4 * (it & 15);
-        w[k][0] = w[k][1] = w[k][2] = 0;
-        if (rr < nrr && x < g.bpitch) {
-            const uint8_t* row = img + off24(reflect101(row0 + rr, g.h), pitch);
-            if (x >= 4 && x + 8 <= g.w) {
-                const u32_unaligned* p = reinterpret_cast<const u32_unaligned*>(row + x - 4);
-                w[k][0] = p[0]; w[k][1] = p[1]; w[k][2] = p[2];
-            } else if (x == 0) {
-                // left border, BORDER_REFLECT_101: pixels -4 .. -1 are pixels 4 .. 1 -- one v_perm on the two dwords the window has anyway
-                // (a level is at least 62 pixels wide, orb_extractor.hip build_geometry)
-                const u32_unaligned* p = reinterpret_cast<const u32_unaligned*>(row);
-                const uint32_t d0 = p[0], d1 = p[1];
-                w[k][0] = __builtin_amdgcn_perm(d1, d0, 0x01020304u); w[k][1] = d0; w[k][2] = d1;
-            } else if (x < g.w) {
-                // right border: r = w - x (1 .. 7) pixels of the window's centre dword are inside.  Every window byte, reflected or not,
-                // is one of the row's last 12 pixels: three dwords, and per window dword one v_perm on two of them with a selector
-                // that depends only on r (bl_right_tab: byte j <- pixel index 8 - r + j inside, 14 + r - j reflected)
-                const u32_unaligned* p = reinterpret_cast<const u32_unaligned*>(row + g.w - 12);
-                const uint32_t l0 = p[0], l1 = p[1], l2 = p[2];
-                const uint4 s = bl_right_tab[g.w - x];
-                w[k][0] = (s.w & 1u) ? __builtin_amdgcn_perm(l2, l1, s.x) : __builtin_amdgcn_perm(l1, l0, s.x);
-                w[k][1] = (s.w & 2u) ? __builtin_amdgcn_perm(l2, l1, s.y) : __builtin_amdgcn_perm(l1, l0, s.y);
-                w[k][2] = (s.w & 4u) ? __builtin_amdgcn_perm(l2, l1, s.z) : __builtin_amdgcn_perm(l1, l0, s.z);
-            } // else: columns of the blurred row's padding (x >= w): nobody reads them
-        }
-    }
-}
-
-// The 8-bit taps of GaussianBlur(7x7, sigma 2) depend on the OpenCV release (orbfe_extractor_set_gaussian_taps):
-//   ED = false: every tap rounded on its own, 18 34 49 55 49 34 18 (sum 257) -- 2.4 / 3.2 (the version CMakeLists.txt:32-38 asks
-//               for) and the first fixed-point implementation of 3.4
-//   ED = true:  the bit-exact kernel with the rounding error carried tap to tap and the centre taking the rest, 18 34 48 56 48 34 18
-//               (sum 256) -- late 3.4.x and 4.x
-template <bool ED>
-__device__ __forceinline__ void bl_hsum_rows(uint16_t* sh, int first_rr, int nrr, int tid, int nitems, const uint32_t (*w)[3])
-{
-    constexpr uint32_t T2 = ED ? 48u : 49u, T3 = ED ? 56u : 55u;
-    constexpr uint32_t TA = 18u | (34u << 8) | (T2 << 16) | (T3 << 24); // taps 0..3
-    constexpr uint32_t TB = T2 | (34u << 8) | (18u << 16);              // taps 4..6
-#pragma unroll
-    for (int k = 0; k < 5; k++) {
-        if (k >= nitems) break;
-        const int it = tid + 256 * k;
-        const int rr = first_rr + (it >> 4), c = 4 * (it & 15);
-        if (rr < nrr) {
-            // byte j of the 12-byte window is pixel x - 4 + j; output i uses bytes i+1 .. i+7
-            const uint32_t w0 = w[k][0], w1 = w[k][1], w2 = w[k][2];
-            const uint32_t s0 = bl_dot4(__builtin_amdgcn_alignbyte(w1, w0, 1), TA, bl_dot4(__builtin_amdgcn_alignbyte(w2, w1, 1), TB, 0));
-            const uint32_t s1 = bl_dot4(__builtin_amdgcn_alignbyte(w1, w0, 2), TA, bl_dot4(__builtin_amdgcn_alignbyte(w2, w1, 2), TB, 0));
-            const uint32_t s2 = bl_dot4(__builtin_amdgcn_alignbyte(w1, w0, 3), TA, bl_dot4(__builtin_amdgcn_alignbyte(w2, w1, 3), TB, 0));
-            const uint32_t s3 = bl_dot4(w1, TA, bl_dot4(w2, TB, 0));
-            sh[(c + 0) * BL_CP + rr] = (uint16_t)s0;
-            sh[(c + 1) * BL_CP + rr] = (uint16_t)s1;
-            sh[(c + 2) * BL_CP + rr] = (uint16_t)s2;
-            sh[(c + 3) * BL_CP + rr] = (uint16_t)s3;
-        }
-    }
-}
-
-#ifndef BL_ATTR
-#define BL_ATTR
-#endif
-template <bool ED>
-__global__ __launch_bounds__(256) BL_ATTR void k_blur7(ImgView src0, ImgView pyr, ImgView blur,
-                                               const LevelGeom* __restrict__ geom, const uint32_t* __restrict__ strips,
-                                               int nx, int total)
-{
-    __shared__ __align__(16) uint16_t sh[64 * BL_CP];
-    int bx, f;
-    if (!xcd_remap(nx, total, bx, f)) return;
-    const uint32_t t = strips[bx];
-    const int level = t & 15, tx0 = (int)(t >> 4) * 64;
-    const LevelGeom g = geom[level];
-    const uint8_t* img = (level == 0) ? src0.base + (size_t)f * src0.fstride
-                                      : pyr.base + (size_t)f * pyr.fstride + g.img_off;
-    const int pitch = (level == 0) ? src0.pitch : g.pitch;
-    const int tid = threadIdx.x;
-    uint8_t* D = blur.base_w + (size_t)f * blur.fstride + g.blur_off;
-    constexpr uint32_t T2 = ED ? 48u : 49u, T3 = ED ? 56u : 55u;
-    constexpr uint32_t V01 = 18u | (34u << 16), V23 = T2 | (T3 << 16), V45 = T2 | (34u << 16), V6 = 18u, V6H = 18u << 16;
-    const int c4 = 4 * (tid & 15), q = tid >> 4;
-    const int x = tx0 + c4;
-
-    // LDS row rr of a tile that starts at image row tyb holds the horizontal sums of image row tyb - 3 + rr
-    uint32_t w[5][3];
-    {
-        const int nrr = min(64, g.h) + 6;
-        bl_load_rows(img, pitch, g, tx0, -3, 0, nrr, tid, 5, w);
-        bl_hsum_rows<ED>(sh, 0, nrr, tid, 5, w);
-    }
-    for (int tyb = 0; tyb < g.h; tyb += 64) {
-        const int nrows_out = min(64, g.h - tyb);
-        const bool more = tyb + 64 < g.h;
-        const int nrr_next = more ? min(64, g.h - tyb - 64) + 6 : 0;
-        __syncthreads(); // sums of this tile complete
-        if (more) bl_load_rows(img, pitch, g, tx0, tyb + 64 - 3, 6, nrr_next, tid, 4, w); // rows 6.. of the next tile
-        // ---- vertical pass: one thread = 4 adjacent columns x 4 consecutive rows, stored as four aligned dwords
-        if (4 * q < nrows_out && x < g.bpitch) {
-            // sat_u8(sum >> 16) of four columns into one dword per row: the high halves of two columns' sums side by side (v_perm), both
-            // saturated and packed by ONE v_sat_pk_u8_i16 (sum >> 16 <= 257), the two column pairs joined by a v_perm: 20 instructions for the
-            // 16 pixels where shift / min / shift-or per pixel took 48
-            uint32_t out[4], qp[2][4];
-#pragma unroll
-            for (int jp = 0; jp < 2; jp++) {
-                uint32_t o[2][4];
-#pragma unroll
-                for (int jj = 0; jj < 2; jj++) {
-                    const uint32_t* hp = reinterpret_cast<const uint32_t*>(&sh[(c4 + 2 * jp + jj) * BL_CP + 4 * q]);
-                    const uint32_t d0 = hp[0], d1 = hp[1], d2 = hp[2], d3 = hp[3], d4 = hp[4];
-                    const uint32_t a01 = __builtin_amdgcn_alignbit(d1, d0, 16), a12 = __builtin_amdgcn_alignbit(d2, d1, 16);
-                    const uint32_t a23 = __builtin_amdgcn_alignbit(d3, d2, 16), a34 = __builtin_amdgcn_alignbit(d4, d3, 16);
-                    o[jj][0] = bl_dot2(d0, V01, bl_dot2(d1, V23, bl_dot2(d2, V45, bl_dot2(d3, V6, 32768u))));
-                    o[jj][1] = bl_dot2(a01, V01, bl_dot2(a12, V23, bl_dot2(a23, V45, bl_dot2(a34, V6, 32768u))));
-                    o[jj][2] = bl_dot2(d1, V01, bl_dot2(d2, V23, bl_dot2(d3, V45, bl_dot2(d4, V6, 32768u))));
-                    o[jj][3] = bl_dot2(a12, V01, bl_dot2(a23, V23, bl_dot2(a34, V45, bl_dot2(d4, V6H, 32768u))));
-                }
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const uint32_t pr = __builtin_amdgcn_perm(o[1][r], o[0][r], 0x07060302u);   // (sum of column 2 jp) >> 16 | (column 2 jp + 1) >> 16 << 16
-                    asm("v_sat_pk_u8_i16 %0, %1" : "=v"(qp[jp][r]) : "v"(pr));
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 4; r++) out[r] = __builtin_amdgcn_perm(qp[1][r], qp[0][r], 0x05040100u);
-            const int y0 = tyb + 4 * q;
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-                if (y0 + j < g.h) *reinterpret_cast<uint32_t*>(D + (off24(y0 + j, g.bpitch) + (uint32_t)x)) = out[j];
-        }
-        if (!more) break;
-        // ---- carry rows 64..69 (= rows 0..5 of the next tile) over: 3 dwords per column
-        uint32_t carry = 0;
-        const int cc = tid / 3, cd = tid - cc * 3;
-        if (tid < 192) carry = reinterpret_cast<const uint32_t*>(&sh[cc * BL_CP + 64])[cd];
-        __syncthreads(); // every read of this tile's sums done
-        if (tid < 192) reinterpret_cast<uint32_t*>(&sh[cc * BL_CP])[cd] = carry;
-        bl_hsum_rows<ED>(sh, 6, nrr_next, tid, 4, w);
-    }
-}
-
-template __global__ void k_blur7<false>(ImgView, ImgView, ImgView, const LevelGeom*, const uint32_t*, int, int);
-template __global__ void k_blur7<true>(ImgView, ImgView, ImgView, const LevelGeom*, const uint32_t*, int, int);
 
 // The same blur on the matrix cores (round 6).  The pipeline is bound by vector-ALU issue (the twelve stages issue 985 us of VALU work in
 // a 1.3 ms step) while the matrix pipe idles; a 7-tap filter is a banded (Toeplitz) matrix, and v_mfma_i32_32x32x32_i8 does 32 K integer
@@ -1870,19 +1689,6 @@ __global__ __launch_bounds__(256) OD2_ATTR void k_orient_describe2(ImgView src0,
             }
         }
     }
-}
-
-// ------------------------------------------------------------------------------------------------ debug ---
-__global__ void k_unpack_keys(const uint32_t* __restrict__ in, int n, int add, orbfe_keypoint* __restrict__ out)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t kv = in[i];
-    orbfe_keypoint kp;
-    kp.x = (float)((int)(kv & 0xfff) + add);
-    kp.y = (float)((int)((kv >> 12) & 0xfff) + add);
-    kp.size = 7.f; kp.angle = -1.f; kp.response = (float)(kv >> 24); kp.octave = 0; kp.class_id = -1;
-    out[i] = kp;
 }
 
 } // namespace orbfe

@@ -169,7 +169,7 @@ int aruco_device_of(const orbfe_aruco* a);   // the HIP device the detector was 
 // The batched pipeline enqueues a batch's descriptor kernel itself, one step late: behind the NEXT batch's resize chain (gate / gate_stage
 // as in orbfe_extractor_stage_wait), so that the two kernels that live on the vector memory path do not run next to each other.
 void extractor_defer_describe(orbfe_extractor* h, bool on);
-int extractor_describe_now(orbfe_extractor* h, orbfe_extractor* gate, int gate_stage);   // FAST of every batch of `h` behind aruco_contours_wait(det) (nullptr: off)
+int extractor_describe_now(orbfe_extractor* h, orbfe_extractor* gate, int gate_stage);
 
 // Scratch of the entry points that have no handle (matching, poses, keyframe records): one workspace per calling thread,
 // HIP device and stream.  A buffer allocated on one GPU is never handed to a kernel on another, two asynchronous calls

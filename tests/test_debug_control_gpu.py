@@ -16,7 +16,7 @@ def test_debug_control_rejects_unknown_keys_and_values(orbfe):
     common = [(b"no_such_key", 0), (b"", 0), (b"Kernel_timing", 1), (b"kernel_timing", 2), (b"kernel_timing", -1)]
     cases = [
         (ex, ex.L.orbfe_extractor_debug_control, ex.L.orbfe_extractor_debug_kernel_times, ex,
-         [(b"general_quadtree", 2), (b"pyramid_depth", -1), (b"pyramid_depth", 7), (b"blur_mfma", -1), (b"tiled_contours", 1)]),
+         [(b"general_quadtree", 2), (b"pyramid_depth", -1), (b"pyramid_depth", 7), (b"tiled_contours", 1)]),
         (det, det.L.orbfe_aruco_debug_control, det.L.orbfe_aruco_debug_kernel_times, det.detect,
          [(b"legacy_contours", 2), (b"tiled_contours", -2), (b"tiled_contours", 2), (b"speck_passes", -1), (b"speck_passes_in_kernel", 2),
           (b"threshold_pyr", 2), (b"threshold_mfma", -2), (b"threshold_mfma", 2), (b"half_pyr", -1), (b"pyramid_depth", 1)]),

@@ -204,3 +204,22 @@ def test_phase_lock_between_handles_changes_no_result(orbfe, oracle):
     assert L.orbfe_extractor_stage_wait(a.h, 0, None) != 0 and L.orbfe_extractor_stage_wait(a.h, 5, None) != 0
     assert L.orbfe_extractor_stage_wait(a.h, 2, None) == 0      # the null stream waits for a's latest quadtree: harmless
     assert np.array_equal(b(imgs[1])[0], want[1][0])
+
+
+def test_refused_frame_leaves_the_handle_usable(orbfe, oracle):
+    """A frame size the extractor refuses (100 x 100 with 8 levels: level 3 is 58 pixels) changes nothing in the handle: the size it
+    was working on, and any other, are extracted as before."""
+    ex = orbfe.ORBextractor(1000, 1.2, 8, 20, 7)
+    ora = oracle.OrbOracle(1000, 1.2, 8, 20, 7)
+    a, _ = synth.scene(480, 640, 31, n_markers=3)
+    c, _ = synth.scene(360, 636, 32, n_markers=2)
+    small, _ = synth.scene(100, 100, 33, n_markers=1, side_range=(30, 40))
+    for img in (a, small, a, c, small, a):
+        if img is small:
+            with pytest.raises(orbfe.OrbfeError):
+                ex(img)
+            continue
+        kps, desc = ex(img)
+        okps, odesc = ora.extract(img)
+        assert len(okps) > 100
+        assert np.array_equal(kps, okps) and np.array_equal(desc, odesc)
