@@ -1158,12 +1158,14 @@ class MarkerDetector:
         self.debug_control("speck_passes", on)
 
     def set_threshold_on_matrix_cores(self, on=True):
-        """True: k_threshold_mfma wherever it applies (windows up to 15); False: the dot-product kernels; None: the default rule -- the
-        matrix-core kernel for calls of 8 frames and more, k_threshold_pyr (one launch instead of five) for the drop-in call's few."""
+        """True: k_threshold_mfma wherever it applies (windows up to 15); False: k_threshold_pyr, or the generic k_adaptive_threshold
+        where that is switched off or does not apply; None: the default rule -- the matrix-core kernel for calls of 8 frames and more,
+        k_threshold_pyr (one launch instead of five) for the drop-in call's few."""
         self.debug_control("threshold_mfma", -1 if on is None else bool(on))
 
     def set_threshold_pyramid_kernel(self, on=True):
-        """k_threshold_pyr (threshold + the /2 pyramid levels a tile holds, the default where it applies) / k_adaptive_threshold_t + k_half_area4."""
+        """k_threshold_pyr (threshold + the /2 pyramid levels a tile holds, the default where it applies) / the generic
+        k_adaptive_threshold + k_half_area4 (with the matrix-core kernel switched off as well; else that one takes the frame)."""
         self.debug_control("threshold_pyr", on)
 
     def set_half_pyramid_kernel(self, on=True):

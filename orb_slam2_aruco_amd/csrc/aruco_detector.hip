@@ -15,6 +15,7 @@
 
 #include "aruco_kernels.hpp"
 #include "aruco_pose.hpp"
+#include "detector_plan.hpp"
 #include "orbfe_common.hpp"
 #include "orbfe_tables.inc"
 
@@ -34,7 +35,7 @@ struct ModeRun {
 // k_contours_t in big-frame mode (bit image in HBM, AR_MAX_KEPT_BIG kept borders).  A batch with a frame over a capacity of its path is
 // done again on the next (escalate(): tiled -> relay, which coarsen their grid -> (kept borders / pool) big); run_device takes the first.
 enum class Contours : int8_t { tiled, relay, walker, big, none };
-enum class Thr : int8_t { fixed, mfma, pyr, magic, box };   // k_fixed_threshold, _mfma, _pyr<WIN>, k_adaptive_threshold_t<WIN>, <R>
+enum class Thr : int8_t { fixed, mfma, pyr, box };   // k_fixed_threshold, k_threshold_mfma, k_threshold_pyr<WIN>, k_adaptive_threshold<R>
 enum class Relay : int8_t { relay, relay8, wide, relay8g }; // k_contours_relay, _relay8, _relay_wide, _relay8g
 
 static Contours escalate(Contours ran, int flags_or, bool relay_ok)
@@ -64,18 +65,12 @@ struct orbfe_aruco {
     hipStream_t own_stream = nullptr, aux_stream = nullptr;
     hipStream_t user_aux = nullptr; // orbfe_aruco_set_aux_stream: run the pyramid there instead of on aux_stream
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    int rows = 0, cols = 0, batch_cap = 0;
-    int win = 0, wpr = 0, npyr = 0;
-    uint32_t th_magic = 0; // multiply-high constant of the box mean (0: use the generic threshold kernel)
-    std::vector<ArLevel> levels;
-    std::vector<int> lvl_exact;           // 1 if level p is an exact 2x reduction of level p-1
-    std::vector<size_t> tab_off;          // resize tables for non-exact levels
-    size_t pyr_fbytes = 0, bits_fu32 = 0, candq_fu32 = 0, pool_fu32 = 0, gpad_fu32 = 0;
-    int lds_bits_words = 0;
+    // what the kernels are told about the input size in force (detector_plan.hpp); swapped in whole by build_geometry
+    DetectorGeometry geo;
+    int batch_cap = 0;
     DevBuf d_twork, d_trect, d_tctr; // k_tail_prep -> k_tail_approx -> k_tail_finish: work list, 4-gon flags, list length
     DevBuf d_rstate, d_lut; // k_contours_relay -> k_contours_small: per-frame grid shift and pool fill; the walks' step table
     DevBuf d_segs, d_tailkeys, d_tailoff, d_small, d_hint; // d_hint: the relay kernel's grid spacing of the previous batch
-    int relay_kshift = 5;      // initial grid spacing (log2) of k_contours_relay
     PinnedBuf pinned; // staging of the host-pointer entry points
     DevBuf d_poses;   // orbfe_aruco_detect_poses
     // speculation for a paired extractor (orbfe_extractor_pair_detector; orbfe_common.hpp)
@@ -94,7 +89,6 @@ struct orbfe_aruco {
     DevBuf d_dwork, d_dctr, d_ditems, d_dhist, d_dpatch; // k_prefilter -> k_decode_warp / _otsu / _vote: the batch's candidates
     bool decode_dirty = false; // the decode work-list counter may be non-zero
     bool tail_dirty = false;   // the work-list counters may be non-zero (set while the tail's three launches are being enqueued)
-    int relay_kcap = RL_KCAP;  // kept borders per frame the relay kernels and their tail hold
     // experiment (ORBFE_ARUCO_SMALL_SEPARATE=1): k_contours_small also for frames whose bit image is in LDS
     // phase (c) of LDS-resident frames as its own launch (k_contours_small): -1 = by batch size (a few frames leave most of the chip
     // idle, so the many small workgroups of the separate kernel shorten the call: 0.62 -> 0.57 ms for one 640 x 480 frame; a full
@@ -116,7 +110,6 @@ struct orbfe_aruco {
     DevBuf d_ctmlist;
     int tile_w_env = getenv("ORBFE_ARUCO_TILE_W") ? atoi(getenv("ORBFE_ARUCO_TILE_W")) : 0;
     int tpw_env = getenv("ORBFE_ARUCO_TPW") ? atoi(getenv("ORBFE_ARUCO_TPW")) : 0;
-    int ct_segcap = 0, ct_hbits = 0, ct_lcap = 0, ct_items_per_frame = 0;
     bool ct_dirty = true;      // the per-frame counters of the walk kernel may be non-zero (first use; a batch abandoned before k_ct_lists)
     unsigned ct_gen = 0;       // generation tag of the hash table's entries (16 bits; the table is cleared when it wraps and before first use)
     bool ct_tab_dirty = true;
@@ -141,87 +134,30 @@ struct orbfe_aruco {
     bool thr_mfma = true;   // k_threshold_mfma where it applies (windows up to 15; debug key "threshold_mfma" = 1 / 0)
     bool thr_mfma_auto = true; // ... but k_threshold_pyr for calls of fewer than 8 frames ("threshold_mfma" = 1 forces the matrix-core kernel, -1 = this rule again)
     DevBuf d_tstrips, d_ttabs, d_ttab2;
-    int n_tstrips = 0, ttab_rows = 0, ttab_cols = 0, ttab_win = 0, ttab_rb = 0;
-    bool thr_mfma_ok = false;
-    // Tables of k_threshold_mfma: per 32-column strip the pass-1 matrices (box K blocks a / b, selection a / b) in the B-operand layout of
-    // v_mfma_i32_32x32x32_i8, BORDER_REPLICATE folded in; the pass-2 matrices (box over the previous / this block, centre x -WIN^2).
-    int build_threshold_tables()
+    ThresholdTables ttab;   // the tables of k_threshold_mfma on the device (detector_plan.hpp); .ok: the kernel applies
+    template <class T> static int upload(DevBuf& d, const std::vector<T>& v)
     {
-        if (ttab_rows == rows && ttab_cols == cols && ttab_win == win) return ORBFE_OK;
-        ttab_rows = rows; ttab_cols = cols; ttab_win = win;
-        const int R = win / 2, n2 = win * win, W = cols, rb = R <= 3 ? 4 : 8;
-        thr_mfma_ok = false;
-        if (n2 > 240 || R > 7 || W < 48) return ORBFE_OK;
-        std::vector<ThrStrip> st;
-        std::vector<uint8_t> tabs;
-        bool ok = true;
-        for (int X = 0; X < W; X += 32) {
-            ThrStrip S{};
-            S.x0 = X; S.tab = (int)(tabs.size() / 1024);
-            auto cl = [&](int c) { return std::min(std::max(c, 0), W - 16); };
-            S.c0 = cl(X - rb); S.c1 = cl(X - rb + 16); S.c2 = cl(X - rb + 32);
-            const int cs[3] = {S.c0, S.c1, S.c2};
-            std::vector<int> Wb((size_t)W * 32, 0), Wi((size_t)W * 32, 0);
-            for (int n = 0; n < 32; n++) {
-                if (X + n >= W) continue;
-                for (int u = -R; u <= R; u++) Wb[(size_t)std::min(std::max(X + n + u, 0), W - 1) * 32 + n] += 1;
-                Wi[(size_t)(X + n) * 32 + n] = 1;
-            }
-            std::vector<int> owner((size_t)W, -1);
-            for (int x = 0; x < W; x++)
-                for (int pz = 0; pz < 3 && owner[x] < 0; pz++)
-                    if (x >= cs[pz] && x < cs[pz] + 16) owner[x] = pz;
-            for (int x = 0; x < W && ok; x++)
-                for (int n = 0; n < 32; n++)
-                    if (Wb[(size_t)x * 32 + n] && owner[x] < 0) ok = false;
-            const size_t base = tabs.size();
-            tabs.resize(base + 4096, 0);
-            for (int m = 0; m < 4; m++)   // box a, box b, selection a, selection b
-                for (int lane = 0; lane < 64; lane++) {
-                    const int n = lane & 31, half = lane >> 5, ab = m & 1;
-                    const int piece = ab == 0 ? half : (half == 0 ? 2 : -1);
-                    if (piece < 0) continue;
-                    for (int i = 0; i < 16; i++) {
-                        const int x = cs[piece] + i;
-                        if (x < 0 || x >= W || owner[x] != piece) continue;
-                        tabs[base + (size_t)m * 1024 + (size_t)lane * 16 + i] = (uint8_t)(int8_t)((m < 2 ? Wb : Wi)[(size_t)x * 32 + n]);
-                    }
-                }
-            st.push_back(S);
-        }
-        if (!ok || st.empty()) return ORBFE_OK;
-        std::vector<uint8_t> t2(6144, 0);
-        const int cw1 = n2 <= 127 ? n2 : 113, cw2 = n2 - cw1;   // the centre's weight -n2 in one signed byte, or in two
-        for (int m = 0; m < 6; m++)   // box over the previous block, over this block, centre in the previous block, in this block (x 2)
-            for (int lane = 0; lane < 64; lane++) {
-                const int n = lane & 31, half = lane >> 5;
-                for (int i = 0; i < 16; i++) {
-                    const int q = 4 * half + (i & 3) + 8 * (i >> 2);
-                    const int d = ((m & 1) ? 32 : 0) + q - rb - n;   // the row's offset from the output row
-                    int v = 0;
-                    if (m < 2) v = (d >= -R && d <= R) ? 1 : 0;
-                    else v = d == 0 ? -(m < 4 ? cw1 : cw2) : 0;
-                    t2[(size_t)m * 1024 + (size_t)lane * 16 + i] = (uint8_t)(int8_t)v;
-                }
-            }
-        n_tstrips = (int)st.size();
-        ttab_rb = rb;
+        if (int rc = d.ensure(v.size() * sizeof(T))) return rc;
+        if (!v.empty()) ORBFE_HIP(hipMemcpy(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+        return ORBFE_OK;
+    }
+    // A failed upload leaves the handle without tables (the next batch that wants them starts over)
+    int ensure_threshold_tables()
+    {
+        if (ttab.cols == geo.cols && ttab.win == geo.win) return ORBFE_OK;
+        ThresholdTables fresh = plan_threshold_tables(geo.cols, geo.win);
+        ttab = ThresholdTables{};
         int rc;
-        if ((rc = d_tstrips.ensure(st.size() * sizeof(ThrStrip))) || (rc = d_ttabs.ensure(tabs.size())) || (rc = d_ttab2.ensure(t2.size()))) return rc;
-        ORBFE_HIP(hipMemcpy(d_tstrips.p, st.data(), st.size() * sizeof(ThrStrip), hipMemcpyHostToDevice));
-        ORBFE_HIP(hipMemcpy(d_ttabs.p, tabs.data(), tabs.size(), hipMemcpyHostToDevice));
-        ORBFE_HIP(hipMemcpy(d_ttab2.p, t2.data(), t2.size(), hipMemcpyHostToDevice));
-        thr_mfma_ok = true;
+        if (fresh.ok && ((rc = upload(d_tstrips, fresh.strips)) || (rc = upload(d_ttabs, fresh.tabs)) || (rc = upload(d_ttab2, fresh.tab2)))) return rc;
+        ttab = std::move(fresh);
         return ORBFE_OK;
     }
     bool thr_v2 = true;   // k_threshold_pyr where it applies (debug key "threshold_pyr": the tests run both threshold kernels)
     bool specks_ran = false;   // the last batch's contour kernels read d_bitsc
     DevBuf d_bitsc;
-    bool relay_global = false; // k_contours_relay8g: the bit image stays in HBM (it does not fit LDS)
-    int relay_tbits = 0;       // hash-table size of k_contours_relay (0: the kernel cannot run at this image size)
     bool force_legacy = false; // debug: always use k_contours_t
     bool big_mode = false;     // orbfe_aruco_set_big_frames: every batch on Contours::big (a retry passes its path to run_device instead)
-    DevBuf d_codes, d_levels, d_tabs, d_bits, d_pyr, d_candq, d_pool, d_kept, d_rects, d_counts, d_candidx, d_ncand,
+    DevBuf d_codes, d_levels, d_bits, d_pyr, d_candq, d_pool, d_kept, d_rects, d_counts, d_candidx, d_ncand,
         d_result, d_gpad;
     DevBuf d_in, d_out, d_nout;
     // MarkerDetector::Params the ABI exposes (markerdetector.h:96-214): error_correction_rate, cornerRefinementM
@@ -245,7 +181,6 @@ struct orbfe_aruco {
     std::vector<orbfe_marker> prev_markers;   // what the previous call returned
     int last_tracked = 0;
     int gray_bits15 = 0;         // BGR2GRAY with 15 fractional bits (OpenCV 3.4.2+) instead of 14
-    int pyr_rows = 0, pyr_cols = 0;   // the frame the /2 pyramid starts from (the working image is smaller when minSize > 0)
     int last_attempts = 0, last_work_rows = 0, last_work_cols = 0;
     size_t rl_static = 0;
     DevBuf d_red, d_mhist, d_masks, d_bgr, d_bits2;
@@ -258,7 +193,7 @@ struct orbfe_aruco {
             if ((rc = batch(floor, &ran))) return rc;
             ORBFE_HIP(hipStreamSynchronize(own_stream));
             for (int f = 0; f < nframes; f++) flags_or |= counts[f * 4 + 2];
-            if (force_legacy || (floor = escalate(ran, flags_or, relay_tbits != 0)) == Contours::none) return ORBFE_OK;
+            if (force_legacy || (floor = escalate(ran, flags_or, geo.relay_tbits != 0)) == Contours::none) return ORBFE_OK;
             n_escalations++;
         }
     }
@@ -268,7 +203,7 @@ struct orbfe_aruco {
 
     ~orbfe_aruco()
     {
-        for (DevBuf* b : {&d_codes, &d_levels, &d_tabs, &d_bits, &d_pyr, &d_candq, &d_pool, &d_kept, &d_rects,
+        for (DevBuf* b : {&d_codes, &d_levels, &d_bits, &d_pyr, &d_candq, &d_pool, &d_kept, &d_rects,
                           &d_counts, &d_candidx, &d_ncand, &d_result, &d_gpad, &d_in, &d_out, &d_nout, &d_segs, &d_tailkeys, &d_tailoff, &d_small, &d_hint, &d_rstate, &d_lut, &d_twork, &d_trect, &d_tctr, &d_dwork, &d_dctr, &d_ditems, &d_dhist, &d_dpatch, &d_poses, &d_scodes, &d_sids,
                           &d_msrc, &d_red, &d_mhist, &d_masks, &d_bgr, &d_bits2, &d_ctseg, &d_cthtab, &d_ctelem, &d_ctstate, &d_ctitemsA, &d_ctitemsB, &d_ctnitems, &d_ctcodes, &d_ctmlist, &d_bitsc, &d_tstrips, &d_ttabs, &d_ttab2})
             b->release();
@@ -309,172 +244,64 @@ struct orbfe_aruco {
                 }
                 tau = d.tau;
                 max_corr = (int)((float)tau * error_rate); // dictionary_based.cpp: static_cast<int>(static_cast<float>(tau()) * rate)
-                rows = cols = 0; // pyramid depth depends on S
+                invalidate_geometry(); // pyramid depth depends on S
                 return ORBFE_OK;
             }
         // the reference treats an unknown name as a file path and throws (dictionary.cpp:44-62)
         return fail(ORBFE_ERR_DICT, "unknown dictionary '%s'", name);
     }
 
-    // rows_ x cols_: the image that is thresholded and traced; prows x pcols: the frame the /2 pyramid is built from
+    void invalidate_geometry() { geo = DetectorGeometry{}; }   // an input of the plan other than the sizes changed: the next batch plans again
+    // rows_ x cols_: the image that is thresholded and traced; prows x pcols: the frame the /2 pyramid is built from.  The plan is made
+    // on the host and its level table uploaded to a buffer of its own before either replaces the handle's: a size the plan refuses and
+    // a failed allocation or upload leave the handle answering for the geometry it had.
     int build_geometry(int rows_, int cols_, int prows, int pcols)
     {
-        if (rows_ == rows && cols_ == cols && prows == pyr_rows && pcols == pyr_cols && !levels.empty()) return ORBFE_OK;
-        if (cols_ > 8000 || rows_ > 8000) return fail(ORBFE_ERR_INVALID, "image larger than 8000 px");
-        int w = std::max(3, int(15 * float(cols_) / 1920.)); // :3765-3809
-        if (w % 2 == 0) w++;
-        if (w > 2 * TH_MAXR_HOST + 1) return fail(ORBFE_ERR_INVALID, "threshold window %d too large", w);
-        win = w;
-        // k_adaptive_threshold_t computes the mean as (s + n/2) * magic >> 32, n = win^2: use it only if that equals the
-        // reference's rint(s * (1.0 / n)) for every possible box sum
-        th_magic = 0;
-        {
-            const int n = w * w;
-            const uint32_t mg = (uint32_t)((0x100000000ull + n - 1) / n);
-            bool same = (n & 1) != 0;
-            for (int sum = 0; same && sum <= 255 * n; sum++)
-                same = (int)(((unsigned long long)(sum + n / 2) * mg) >> 32) == orbfe_round_d((double)sum * (1.0 / n));
-            if (same) th_magic = mg;
-        }
-        wpr = (cols_ + 31) / 32;
-        bits_fu32 = (size_t)wpr * rows_;
-        // buildPyramid (:1299-1488): halve while width > 2 * S
-        levels.clear();
-        lvl_exact.clear();
-        std::vector<int> tabs;
-        tab_off.clear();
-        int lw = pcols, lh = prows;
-        size_t off = 0;
-        levels.push_back(ArLevel{lw, lh, 0, 0});
-        lvl_exact.push_back(1);
-        tab_off.resize(4, 0);
-        int n = 1, tw = pcols;
-        while (tw > 2 * S) { tw /= 2; n++; }
-        for (int p = 1; p < n; p++) {
-            const int sw = lw, sh = lh;
-            lw /= 2; lh /= 2;
-            if (lw < 1 || lh < 1) break;
-            ArLevel L{lw, lh, (lw + 63) / 64 * 64, (long long)off};
-            off += (size_t)L.pitch * lh;
-            levels.push_back(L);
-            const bool exact = (sw == 2 * lw && sh == 2 * lh);
-            lvl_exact.push_back(exact);
-            tab_off.resize((size_t)(p + 1) * 4, 0);
-            if (!exact) { // generic INTER_LINEAR tables, same format as the ORB pyramid's
-                const double scale_x = 1. / ((double)lw / sw), scale_y = 1. / ((double)lh / sh);
-                const int dwp = (lw + 3) / 4 * 4;
-                std::vector<int> xofs(dwp), xal(dwp), yofs(lh), ybe(lh);
-                for (int dx = 0; dx < lw; dx++) {
-                    float fx = (float)((dx + 0.5) * scale_x - 0.5);
-                    int sx = orbfe_floor_d(fx);
-                    fx -= sx;
-                    if (sx < 0) { fx = 0; sx = 0; }
-                    if (sx >= sw - 1) { fx = 0; sx = sw - 1; }
-                    const int a0 = (short)orbfe_round_f((1.f - fx) * 2048.f), a1 = (short)orbfe_round_f(fx * 2048.f);
-                    xofs[dx] = sx;
-                    xal[dx] = (a0 & 0xffff) | (a1 << 16);
-                }
-                for (int dx = lw; dx < dwp; dx++) { xofs[dx] = xofs[lw - 1]; xal[dx] = xal[lw - 1]; }
-                for (int dy = 0; dy < lh; dy++) {
-                    float fy = (float)((dy + 0.5) * scale_y - 0.5);
-                    int sy = orbfe_floor_d(fy);
-                    fy -= sy;
-                    const int b0 = (short)orbfe_round_f((1.f - fy) * 2048.f), b1 = (short)orbfe_round_f(fy * 2048.f);
-                    yofs[dy] = sy;
-                    ybe[dy] = (b0 & 0xffff) | (b1 << 16);
-                }
-                tab_off[p * 4 + 0] = tabs.size(); tabs.insert(tabs.end(), xofs.begin(), xofs.end());
-                tab_off[p * 4 + 1] = tabs.size(); tabs.insert(tabs.end(), xal.begin(), xal.end());
-                tab_off[p * 4 + 2] = tabs.size(); tabs.insert(tabs.end(), yofs.begin(), yofs.end());
-                tab_off[p * 4 + 3] = tabs.size(); tabs.insert(tabs.end(), ybe.begin(), ybe.end());
-            }
-        }
-        npyr = (int)levels.size();
-        pyr_fbytes = off + 64;
-        // HBM overflow of the single-walker kernel's long-walk queue / the relay kernels' start-candidate queue, + their speck scratch
-        // (the speck scratch -- four times the queue at 640 x 480 -- only where the in-kernel passes are switched on)
-        candq_fu32 = ((size_t)relay_queue_words(cols_, rows_) + (specks_inkernel ? speck_frame_scratch_words(cols_, rows_) : 0) + 63) / 64 * 64;
-        pool_fu32 = (size_t)CT_THREADS * std::max(4096, rows_ * cols_ / 48); // one private arena per lane of k_contours
-        const int pw = (cols_ + 2 + 31) / 32;
-        const size_t padded_words = (size_t)pw * (rows_ + 2) + 2; // + spare words for ring8()
-        // the padded bit image goes to LDS when it fits next to the other arrays (160 KiB per workgroup)
-        lds_bits_words = (contours_lds_bytes((int)padded_words, AR_MAX_KEPT) + 256 <= 160 * 1024) ? (int)padded_words : 0;
-        gpad_fu32 = padded_words; // always there: big_mode uses the HBM variant at any size
-        // k_contours_relay needs the bit image AND its marker table in LDS; otherwise k_contours_t does all frames.
-        // 4096 marker slots on a 32-pixel grid for ordinary frames (a 2048-slot table on a 64-pixel grid would let two workgroups
-        // share a CU, but its longer segments cost more than the sharing wins: 857 vs 726 us).  Large frames have more grid
-        // crossings than 4096 slots hold and would be coarsened to a 128-pixel grid, which doubles the kernel's time (640 x 480:
-        // 463 / 592 / 949 us at 32 / 64 / 128 pixels): they get 8192 slots (k_contours_relay8) when the LDS allows.
-        relay_tbits = 0;
-        // static LDS of the relay kernels (step table, counters), asked from the runtime: a constant here once fell behind the kernels
-        // and frames whose tables only just fitted (1582 x 619: 156,976 B dynamic) failed at launch
-        if (!rl_static) {
+        if (geo.matches(rows_, cols_, prows, pcols)) return ORBFE_OK;
+        if (!rl_static) {   // static LDS of the relay kernels, asked from the runtime (detector_plan.hpp)
+            size_t most = 0;
             const void* fns[4] = {reinterpret_cast<const void*>(k_contours_relay), reinterpret_cast<const void*>(k_contours_relay8),
                                   reinterpret_cast<const void*>(k_contours_relay8g), reinterpret_cast<const void*>(k_contours_relay_wide)};
             for (const void* fn : fns) {
                 hipFuncAttributes fa{};
                 ORBFE_HIP(hipFuncGetAttributes(&fa, fn));
-                rl_static = std::max(rl_static, (size_t)fa.sharedSizeBytes);
+                most = std::max(most, (size_t)fa.sharedSizeBytes);
             }
-            rl_static += 256;
+            rl_static = most + 256;
         }
-        const bool large = (size_t)rows_ * cols_ > (size_t)640 * 480 * 3 / 2;
-        if (lds_bits_words && large && relay_lds_bytes(lds_bits_words, RL_KCAP, 13) + rl_static <= 160 * 1024) { relay_tbits = 13; relay_kshift = 5; }
-        else if (lds_bits_words && relay_lds_bytes(lds_bits_words, RL_KCAP, 12) + rl_static <= 160 * 1024) { relay_tbits = 12; relay_kshift = 5; }
-        // frames whose bit image does not fit LDS: the relay formulation with the bit image in HBM (k_contours_relay8g)
-        // (and room for as many kept borders as the single-walker kernel's big-frame mode: busy 1920 x 1080 frames have > 1024)
-        // (also frames whose bit image fits LDS for the single-walker kernel but not next to a marker table)
-        // (round 2: the HBM-image formulation also for frames that fit LDS -- 45 KB workgroups instead of 151 KB -- was slower, 5.50 against 4.62 ms at C3)
-        relay_global = !relay_tbits && relay_lds_bytes(0, AR_MAX_KEPT_BIG, 13) + rl_static <= 160 * 1024;
-        relay_kcap = RL_KCAP;
-        if (relay_global) { relay_tbits = 13; relay_kshift = 5; relay_kcap = AR_MAX_KEPT_BIG; }
-        // tiled path: segments per frame the lists hold (a 640 x 480 frame of the synthetic streams has ~2000, salt noise ~15 k; ids
-        // are 16 bits), hash slots (twice that), segments whose list arrays k_ct_lists keeps in LDS (more: the same arrays in HBM)
-        {
-            int sc = 4096;
-            while (sc < rows_ * cols_ / 32 && sc < 65536) sc <<= 1;
-            ct_segcap = std::min(sc, 65535);
-            ct_hbits = 1;
-            while ((1 << ct_hbits) < 2 * sc) ct_hbits++;
-            ct_lcap = std::min(ct_segcap, large ? 16384 : 4096);   // list elements k_ct_lists keeps in LDS (8 B each)
-            if (getenv("ORBFE_ARUCO_LCAP") && atoi(getenv("ORBFE_ARUCO_LCAP")) > 0) ct_lcap = std::min(ct_segcap, atoi(getenv("ORBFE_ARUCO_LCAP"))); // (measurement switch)
-            ct_items_per_frame = std::max(4096, ct_segcap / 4);
-        }
-        rows = rows_; cols = cols_;
-        pyr_rows = prows; pyr_cols = pcols;
+        DetectorGeometry fresh = plan_detector(rows_, cols_, prows, pcols, S, specks_inkernel, getenv("ORBFE_ARUCO_LCAP") ? atoi(getenv("ORBFE_ARUCO_LCAP")) : 0, rl_static);
+        if (fresh.err) return fail(fresh.err, "%s", fresh.msg);
+        DevBuf lv;
+        if (int rc = upload(lv, fresh.levels)) return rc;
+        std::swap(d_levels.p, lv.p); std::swap(d_levels.bytes, lv.bytes);
+        geo = std::move(fresh);
         batch_cap = 0;
-        if (tabs.empty()) tabs.push_back(0);
-        int rc;
-        if ((rc = d_levels.ensure(levels.size() * sizeof(ArLevel))) || (rc = d_tabs.ensure(tabs.size() * 4))) return rc;
-        ORBFE_HIP(hipMemcpy(d_levels.p, levels.data(), levels.size() * sizeof(ArLevel), hipMemcpyHostToDevice));
-        ORBFE_HIP(hipMemcpy(d_tabs.p, tabs.data(), tabs.size() * 4, hipMemcpyHostToDevice));
         return ORBFE_OK;
     }
-    static const int TH_MAXR_HOST = 15; // windows up to 31 (k_adaptive_threshold<15>): frames up to 4095 pixels wide
 
     int ensure_workspace(int B)
     {
         if (B <= batch_cap) return ORBFE_OK;
         int rc;
-        if ((rc = d_bits.ensure(bits_fu32 * 4 * B)) || (rc = d_pyr.ensure(pyr_fbytes * B)) ||   // (d_bitsc: when the speck launch runs)
-            (rc = d_candq.ensure(candq_fu32 * 4 * B)) || (rc = d_pool.ensure(pool_fu32 * 4 * B)) ||
+        if ((rc = d_bits.ensure(geo.bits_fu32 * 4 * B)) || (rc = d_pyr.ensure(geo.pyr_fbytes * B)) ||   // (d_bitsc: when the speck launch runs)
+            (rc = d_candq.ensure(geo.candq_fu32 * 4 * B)) || (rc = d_pool.ensure(geo.pool_fu32 * 4 * B)) ||
             (rc = d_kept.ensure((size_t)AR_MAX_KEPT_BIG * sizeof(ArKept) * B)) ||
             (rc = d_rects.ensure((size_t)AR_MAX_RECTS * sizeof(ArRect) * B)) || (rc = d_counts.ensure((size_t)16 * B)) ||
             (rc = d_candidx.ensure((size_t)AR_MAX_RECTS * 4 * B)) || (rc = d_ncand.ensure((size_t)4 * B)) ||
             (rc = d_result.ensure((size_t)AR_MAX_RECTS * 8 * B)) || (rc = d_msrc.ensure((size_t)AR_MAX_RECTS * 4 * B)) ||
-            (rc = d_gpad.ensure(std::max<size_t>(gpad_fu32 * 4 * B, 16))) ||
-            (rc = d_segs.ensure(std::max<size_t>(((size_t)sizeof(RelaySeg) << relay_tbits) * B, 16))) ||
-            (rc = d_tailkeys.ensure((size_t)relay_kcap * 8 * B)) || (rc = d_tailoff.ensure((size_t)relay_kcap * 4 * B)) ||
-            (rc = d_small.ensure((size_t)relay_kcap * 16 * B)) || (rc = d_rstate.ensure((size_t)8 * B)) ||
-            (rc = d_twork.ensure((size_t)relay_kcap * 32 * B)) || (rc = d_trect.ensure((size_t)relay_kcap * B)))
+            (rc = d_gpad.ensure(std::max<size_t>(geo.gpad_fu32 * 4 * B, 16))) ||
+            (rc = d_segs.ensure(std::max<size_t>(((size_t)sizeof(RelaySeg) << geo.relay_tbits) * B, 16))) ||
+            (rc = d_tailkeys.ensure((size_t)geo.relay_kcap * 8 * B)) || (rc = d_tailoff.ensure((size_t)geo.relay_kcap * 4 * B)) ||
+            (rc = d_small.ensure((size_t)geo.relay_kcap * 16 * B)) || (rc = d_rstate.ensure((size_t)8 * B)) ||
+            (rc = d_twork.ensure((size_t)geo.relay_kcap * 32 * B)) || (rc = d_trect.ensure((size_t)geo.relay_kcap * B)))
             return rc;
         if (tiled != 0) {
-            const size_t elem_words = (size_t)ct_segcap + ((size_t)ct_segcap + 3) / 4; // u64 elements + u16 next ids, per frame
-            if ((rc = d_ctseg.ensure((size_t)5 * ct_segcap * 4 * B)) || (rc = d_cthtab.ensure(((size_t)8 << ct_hbits) * B)) ||
+            const size_t elem_words = (size_t)geo.ct_segcap + ((size_t)geo.ct_segcap + 3) / 4; // u64 elements + u16 next ids, per frame
+            if ((rc = d_ctseg.ensure((size_t)5 * geo.ct_segcap * 4 * B)) || (rc = d_cthtab.ensure(((size_t)8 << geo.ct_hbits) * B)) ||
                 (rc = d_ctelem.ensure(elem_words * 8 * B)) || (rc = d_ctstate.ensure((size_t)CT_STATE_INTS * 4 * B)) ||
-                (rc = d_ctitemsA.ensure((size_t)ct_items_per_frame * 16 * B)) || (rc = d_ctitemsB.ensure((size_t)ct_items_per_frame * 8 * B)) ||
-                (rc = d_ctnitems.ensure((size_t)4 * B)) || (rc = d_ctcodes.ensure((size_t)ct_segcap * CT_CODE_WORDS * 4 * B)) ||
-                (rc = d_ctmlist.ensure((size_t)CTB_MCAP * 4 * ((rows + 31) / 32) * B)))   // (one list per band; at most one band per cell row)
+                (rc = d_ctitemsA.ensure((size_t)geo.ct_items_per_frame * 16 * B)) || (rc = d_ctitemsB.ensure((size_t)geo.ct_items_per_frame * 8 * B)) ||
+                (rc = d_ctnitems.ensure((size_t)4 * B)) || (rc = d_ctcodes.ensure((size_t)geo.ct_segcap * CT_CODE_WORDS * 4 * B)) ||
+                (rc = d_ctmlist.ensure((size_t)CTB_MCAP * 4 * ((geo.rows + 31) / 32) * B)))   // (one list per band; at most one band per cell row)
                 return rc;
             ct_dirty = true; ct_tab_dirty = true;
         }
@@ -531,44 +358,44 @@ struct orbfe_aruco {
         const bool reduced = mr && mr->d_full;
         // The threshold kernel of the batched configuration writes the pyramid levels its 64 x 64 tiles hold whole (k_threshold_pyr): the
         // exact halvings, at most four, when the pyramid starts from the thresholded frame itself and n v + K stays within 16 bits
-        const long n2 = (long)win * win, K = n2 * thres_value - n2 / 2;
-        const bool adaptive = !(mr && mr->fixed_thr >= 0), win_t = win == 5 || win == 7 || win == 11 || win == 15;
-        const bool fused_ok = adaptive && thr_v2 && th_magic && win_t && K >= 0 && n2 * 255 + K <= 65535;
+        const long n2 = (long)geo.win * geo.win, K = n2 * thres_value - n2 / 2;
+        const bool adaptive = !(mr && mr->fixed_thr >= 0), win_t = geo.win == 5 || geo.win == 7 || geo.win == 11 || geo.win == 15;
+        const bool fused_ok = adaptive && thr_v2 && win_t && K >= 0 && n2 * 255 + K <= 65535;
         // A call of a few frames (the drop-in call: one) is a chain of launches that each wait for the one before: there the kernel that
         // also writes the pyramid (one launch instead of five) is the shorter chain -- detect 0.333 -> 0.303 ms per 640 x 480 frame;
         // a batch has the pyramid next to the contour kernels on a stream of its own and takes the matrix-core kernel
-        const bool try_mfma = adaptive && thr_mfma && th_magic && K > -(1 << 20) && K < (1 << 20) && !(fused_ok && !reduced && B < 8 && thr_mfma_auto);
-        if (int rc = try_mfma ? build_threshold_tables() : ORBFE_OK) return rc;
-        p.thr = !adaptive ? Thr::fixed : try_mfma && thr_mfma_ok ? Thr::mfma : fused_ok ? Thr::pyr : th_magic && win_t ? Thr::magic : Thr::box;
+        const bool try_mfma = adaptive && thr_mfma && K > -(1 << 20) && K < (1 << 20) && !(fused_ok && !reduced && B < 8 && thr_mfma_auto);
+        if (int rc = try_mfma ? ensure_threshold_tables() : ORBFE_OK) return rc;
+        p.thr = !adaptive ? Thr::fixed : try_mfma && ttab.ok ? Thr::mfma : fused_ok ? Thr::pyr : Thr::box;
         if (p.thr == Thr::pyr) p.thr_kk = (uint32_t)K | ((uint32_t)K << 16);
-        for (int l = 1; p.thr == Thr::pyr && !reduced && l < npyr && l <= 4; l++) {
-            if (!lvl_exact[l] || levels[l].pitch % 4 != 0 || levels[l].pitch < 4 * ((levels[l].w + 3) / 4)) break;
+        for (int l = 1; p.thr == Thr::pyr && !reduced && l < geo.npyr && l <= 4; l++) {
+            if (!geo.lvl_exact[l] || geo.levels[l].pitch % 4 != 0 || geo.levels[l].pitch < 4 * ((geo.levels[l].w + 3) / 4)) break;
             p.nfuse = l;
         }
         // the first contour path from `floor` on that may run (big_mode: orbfe_aruco_set_big_frames; the tiled rule: at `tiled`)
         if (big_mode || floor >= Contours::big) p.contours = Contours::big;
-        else if (!force_legacy && floor <= Contours::tiled && (tiled > 0 || (tiled < 0 && (relay_global || !relay_tbits || relay_tbits > 12 || B <= 32))))
+        else if (!force_legacy && floor <= Contours::tiled && (tiled > 0 || (tiled < 0 && (geo.relay_global || !geo.relay_tbits || geo.relay_tbits > 12 || B <= 32))))
             p.contours = Contours::tiled;
-        else p.contours = !force_legacy && floor <= Contours::relay && relay_tbits ? Contours::relay : Contours::walker;
+        else p.contours = !force_legacy && floor <= Contours::relay && geo.relay_tbits ? Contours::relay : Contours::walker;
         // the bit image the contour kernels read: after the speck passes, unless switched off or the frame is too wide for their LDS tile
-        p.specks = (specks > 0 || (specks < 0 && p.contours == Contours::relay && !relay_global && B > 32)) && speck_lds_bytes(cols) <= 150 * 1024;
+        p.specks = (specks > 0 || (specks < 0 && p.contours == Contours::relay && !geo.relay_global && B > 32)) && speck_lds_bytes(geo.cols) <= 150 * 1024;
         // Tile width and waves.  k_ct_walk's waves are persistent and overlap their tiles, so a wave wants several tiles (its
         // lanes always find work) and a SIMD wants several waves (a step is a chain of dependent LDS reads): narrow tiles for a
         // batch -- ORBFE_ARUCO_TILE_W / ORBFE_ARUCO_TPW (tiles per wave) are measurement switches --, and for a few frames as many
         // waves as there are tiles.
-        const int target = tile_w_env > 0 ? tile_w_env : (B <= 32 ? 192 : 480), ncols0 = std::max(1, (cols + target - 1) / target);
-        p.tile_w = std::min(CTW_MAX_CW, std::max(32, ((cols + ncols0 - 1) / ncols0 + 31) / 32 * 32));
+        const int target = tile_w_env > 0 ? tile_w_env : (B <= 32 ? 192 : 480), ncols0 = std::max(1, (geo.cols + target - 1) / target);
+        p.tile_w = std::min(CTW_MAX_CW, std::max(32, ((geo.cols + ncols0 - 1) / ncols0 + 31) / 32 * 32));
         p.tpw = tpw_env > 0 ? tpw_env : (B <= 32 ? 1 : 2);
         // bands for full batches (eight waves level each other's load through the band's ticket counters) and, one cell row each, for
         // up to four frames (single-frame call 0.385 -> 0.355 ms: the waves of a band share its start candidates, where a wave of
         // k_ct_walk has its tile's to itself); a wave per tile in between
         p.band = banded > 0 || (banded < 0 && (B > 32 || B <= 4));
-        const int pw = (cols + 2 + 31) / 32, rb = band_rows_env > 0 ? band_rows_env : B <= 4 ? 1 : std::max(1, std::min(8, (int)((36 * 1024 / (pw * 4) - 3) / 32)));
-        p.band_rows = std::max(1, std::min(rb, (rows + 31) / 32));
-        const bool wide = relay_tbits <= 12 && B <= 32 && relay_wide;   // few frames: 16 waves per frame (see k_contours_relay_wide)
-        p.relay = relay_global ? Relay::relay8g : relay_tbits > 12 ? Relay::relay8 : wide ? Relay::wide : Relay::relay;
-        p.small_separate = relay_global || (small_separate_mode < 0 ? B <= 32 : small_separate_mode != 0);   // (always behind relay8g)
-        p.walker_hbm = p.contours == Contours::big || !lds_bits_words;
+        const int pw = (geo.cols + 2 + 31) / 32, rb = band_rows_env > 0 ? band_rows_env : B <= 4 ? 1 : std::max(1, std::min(8, (int)((36 * 1024 / (pw * 4) - 3) / 32)));
+        p.band_rows = std::max(1, std::min(rb, (geo.rows + 31) / 32));
+        const bool wide = geo.relay_tbits <= 12 && B <= 32 && relay_wide;   // few frames: 16 waves per frame (see k_contours_relay_wide)
+        p.relay = geo.relay_global ? Relay::relay8g : geo.relay_tbits > 12 ? Relay::relay8 : wide ? Relay::wide : Relay::relay;
+        p.small_separate = geo.relay_global || (small_separate_mode < 0 ? B <= 32 : small_separate_mode != 0);   // (always behind relay8g)
+        p.walker_hbm = p.contours == Contours::big || !geo.lds_bits_words;
         return ORBFE_OK;
     }
 
@@ -598,7 +425,7 @@ struct orbfe_aruco {
         if (!p.nfuse) pyramid(1, src0, B, aux);
         timer.mark(aux, "pyramid");
         if (!p.nfuse) ORBFE_HIP(hipEventRecord(ev_join, aux));
-        int enlarge_k = win;   // detectEnclosedMarkers: the candidates grow by half the adaptive window, or half the erosion size
+        int enlarge_k = geo.win;   // detectEnclosedMarkers: the candidates grow by half the adaptive window, or half the erosion size
         if ((rc = threshold(p, srcW, src0, mr ? mr->fixed_thr : -1, B, s, &enlarge_k))) return rc;
         timer.mark(s, "threshold");
         ORBFE_HIP(hipGetLastError());
@@ -619,7 +446,7 @@ struct orbfe_aruco {
         return ORBFE_OK;
     }
 
-    ImgView pyr_view() { return ImgView{d_pyr.as<uint8_t>(), d_pyr.as<uint8_t>(), pyr_fbytes, 0}; }
+    ImgView pyr_view() { return ImgView{d_pyr.as<uint8_t>(), d_pyr.as<uint8_t>(), geo.pyr_fbytes, 0}; }
     // the /2 pyramid from level `first` on
     void pyramid(int first, const ImgView& src0, int B, hipStream_t st)
     {
@@ -628,31 +455,31 @@ struct orbfe_aruco {
             // the leading exact halvings in one launch (k_half_pyr): four from 16 x 16 source blocks, or three from 8 x 8
             for (int nf = 4; nf >= 3 && first == 1; nf--) {
                 const int bs = 1 << nf;
-                bool ok = npyr > nf && levels[0].w % bs == 0 && levels[0].h % bs == 0 && src0.pitch % (bs == 16 ? 16 : 8) == 0 &&
-                          src0.fstride % (bs == 16 ? 16 : 8) == 0 && ((uintptr_t)src0.base & (bs == 16 ? 15 : 7)) == 0 && pyr_fbytes % 8 == 0;
+                bool ok = geo.npyr > nf && geo.levels[0].w % bs == 0 && geo.levels[0].h % bs == 0 && src0.pitch % (bs == 16 ? 16 : 8) == 0 &&
+                          src0.fstride % (bs == 16 ? 16 : 8) == 0 && ((uintptr_t)src0.base & (bs == 16 ? 15 : 7)) == 0 && geo.pyr_fbytes % 8 == 0;
                 for (int p = 1; ok && p <= nf; p++) {
                     const int al = bs >> p;   // bytes a thread stores per row of level p
-                    ok = lvl_exact[p] && levels[p].w == levels[0].w >> p && levels[p].h == levels[0].h >> p && levels[p].pitch % al == 0 &&
-                         levels[p].off % al == 0 && levels[p].pitch >= levels[p].w;
+                    ok = geo.lvl_exact[p] && geo.levels[p].w == geo.levels[0].w >> p && geo.levels[p].h == geo.levels[0].h >> p && geo.levels[p].pitch % al == 0 &&
+                         geo.levels[p].off % al == 0 && geo.levels[p].pitch >= geo.levels[p].w;
                 }
                 if (!ok) continue;
                 HalfPyrDst P{};
-                P.base = pyr.base_w; P.fstride = pyr_fbytes;
-                for (int p = 1; p <= nf; p++) { P.off[p - 1] = (uint32_t)levels[p].off; P.pitch[p - 1] = levels[p].pitch; }
-                const int bw = levels[0].w / bs, nblocks = bw * (levels[0].h / bs);
+                P.base = pyr.base_w; P.fstride = geo.pyr_fbytes;
+                for (int p = 1; p <= nf; p++) { P.off[p - 1] = (uint32_t)geo.levels[p].off; P.pitch[p - 1] = geo.levels[p].pitch; }
+                const int bw = geo.levels[0].w / bs, nblocks = bw * (geo.levels[0].h / bs);
                 if (nf == 4) hipLaunchKernelGGL(k_half_pyr<4>, dim3((nblocks + 255) / 256, B), dim3(256), 0, st, src0, P, bw, nblocks);
                 else hipLaunchKernelGGL(k_half_pyr<3>, dim3((nblocks + 255) / 256, B), dim3(256), 0, st, src0, P, bw, nblocks);
                 first = nf + 1;
             }
         }
-        for (int p = first; p < npyr; p++) {
-            const ArLevel &L = levels[p], &Lp = levels[p - 1];
-            ImgView sv = (p == 1) ? src0 : ImgView{pyr.base + Lp.off, nullptr, pyr_fbytes, Lp.pitch};
-            ImgView dv{pyr.base + L.off, pyr.base_w + L.off, pyr_fbytes, L.pitch};
-            if (lvl_exact[p] && sv.pitch % 8 == 0 && sv.fstride % 8 == 0 && ((uintptr_t)sv.base & 7) == 0 && dv.pitch % 4 == 0 && dv.pitch >= 4 * ((L.w + 3) / 4)) {
+        for (int p = first; p < geo.npyr; p++) {
+            const ArLevel &L = geo.levels[p], &Lp = geo.levels[p - 1];
+            ImgView sv = (p == 1) ? src0 : ImgView{pyr.base + Lp.off, nullptr, geo.pyr_fbytes, Lp.pitch};
+            ImgView dv{pyr.base + L.off, pyr.base_w + L.off, geo.pyr_fbytes, L.pitch};
+            if (geo.lvl_exact[p] && sv.pitch % 8 == 0 && sv.fstride % 8 == 0 && ((uintptr_t)sv.base & 7) == 0 && dv.pitch % 4 == 0 && dv.pitch >= 4 * ((L.w + 3) / 4)) {
                 const int dw4 = (L.w + 3) / 4, nthreads = dw4 * ((L.h + 1) / 2);   // reads up to 2 * L.w + 6 < the source pitch (64-byte rows)
                 hipLaunchKernelGGL(k_half_area4, dim3((nthreads + 255) / 256, B), dim3(256), 0, st, sv, dv, dw4, L.h);
-            } else if (lvl_exact[p]) {
+            } else if (geo.lvl_exact[p]) {
                 hipLaunchKernelGGL(k_half_area, dim3((L.w + 63) / 64, (L.h + 3) / 4, B), dim3(256), 0, st, sv, dv, L.w, L.h);
             } else {
                 const int dw4 = (L.w + 3) / 4;
@@ -662,39 +489,36 @@ struct orbfe_aruco {
             }
         }
     }
-    // the instance of k_threshold_pyr / k_adaptive_threshold_t for the window (they are built for windows 5, 7, 11 and 15)
-    template <class K> K by_window(K k5, K k7, K k11, K k15) const { return win == 5 ? k5 : win == 7 ? k7 : win == 11 ? k11 : k15; }
+    // the instance of k_threshold_pyr for the window (it is built for windows 5, 7, 11 and 15)
+    template <class K> K by_window(K k5, K k7, K k11, K k15) const { return geo.win == 5 ? k5 : geo.win == 7 ? k7 : geo.win == 11 ? k11 : k15; }
     // the bit image d_bits (k_threshold_pyr: and the pyramid, its first levels in the kernel and the rest behind it)
     int threshold(const BatchPlan& p, const ImgView& srcW, const ImgView& src0, int fixed_thr, int B, hipStream_t s, int* enlarge_k)
     {
         for (int r_ = 0; r_ < ORBFE_REPS_ARUCO(8); r_++) {
-            const int ntx = (cols + 63) / 64, ntl = ntx * ((rows + 63) / 64);
-            const dim3 tg(ntx, (rows + 63) / 64, B), tg1(xcd_grid(ntl * B));
+            const int ntx = (geo.cols + 63) / 64, ntl = ntx * ((geo.rows + 63) / 64);
+            const dim3 tg(ntx, (geo.rows + 63) / 64, B), tg1(xcd_grid(ntl * B));
             uint32_t* bp = d_bits.as<uint32_t>();
             if (p.thr == Thr::fixed) {   // THRES_AUTO_FIXED: cv::threshold(THRESH_BINARY_INV) at the carried-over threshold
                 if (enclosed) {               // detectEnclosedMarkers: the inner edge band of the thresholded regions (erode + xor)
-                    if (int rc = d_bits2.ensure(bits_fu32 * 4 * B)) return rc;
-                    const int k = *enlarge_k = int(std::max(3.0, 3. / 1920. * float(cols))) | 1;   // (made odd)
+                    if (int rc = d_bits2.ensure(geo.bits_fu32 * 4 * B)) return rc;
+                    const int k = *enlarge_k = int(std::max(3.0, 3. / 1920. * float(geo.cols))) | 1;   // (made odd)
                     if (k / 2 > 15) return fail(ORBFE_ERR_INVALID, "detectEnclosedMarkers: frame too wide (erosion size %d)", k);
                 }
-                hipLaunchKernelGGL(k_fixed_threshold, dim3((wpr * rows + 255) / 256, B), dim3(256), 0, s, srcW, cols, rows, fixed_thr, enclosed ? d_bits2.as<uint32_t>() : bp, bits_fu32, wpr);
-                if (enclosed) hipLaunchKernelGGL(k_erode_cross_xor, dim3((wpr * rows + 255) / 256, B), dim3(256), 0, s, d_bits2.as<uint32_t>(), bp, bits_fu32, wpr, cols, rows, *enlarge_k / 2);
+                hipLaunchKernelGGL(k_fixed_threshold, dim3((geo.wpr * geo.rows + 255) / 256, B), dim3(256), 0, s, srcW, geo.cols, geo.rows, fixed_thr, enclosed ? d_bits2.as<uint32_t>() : bp, geo.bits_fu32, geo.wpr);
+                if (enclosed) hipLaunchKernelGGL(k_erode_cross_xor, dim3((geo.wpr * geo.rows + 255) / 256, B), dim3(256), 0, s, d_bits2.as<uint32_t>(), bp, geo.bits_fu32, geo.wpr, geo.cols, geo.rows, *enlarge_k / 2);
             } else if (p.thr == Thr::mfma) {
-                const int n2 = win * win, nxs = (n_tstrips + 3) / 4;
-                hipLaunchKernelGGL(k_threshold_mfma, dim3(xcd_grid(nxs * B)), dim3(256), 0, s, srcW, cols, rows, ttab_rb, -(n2 * thres_value - n2 / 2),
-                                   d_tstrips.as<ThrStrip>(), d_ttabs.as<uint4>(), d_ttab2.as<uint4>(), bp, bits_fu32, wpr, n_tstrips, nxs, nxs * B, n2 > 127 ? 1 : 0);
+                const int n2 = geo.win * geo.win, n_tstrips = (int)ttab.strips.size(), nxs = (n_tstrips + 3) / 4;
+                hipLaunchKernelGGL(k_threshold_mfma, dim3(xcd_grid(nxs * B)), dim3(256), 0, s, srcW, geo.cols, geo.rows, ttab.rb, -(n2 * thres_value - n2 / 2),
+                                   d_tstrips.as<ThrStrip>(), d_ttabs.as<uint4>(), d_ttab2.as<uint4>(), bp, geo.bits_fu32, geo.wpr, n_tstrips, nxs, nxs * B, n2 > 127 ? 1 : 0);
             } else if (p.thr == Thr::pyr) {
                 ThrPyr P{};
                 P.n = p.nfuse;
-                for (int l = 1; l <= p.nfuse; l++) { P.w[l - 1] = levels[l].w; P.h[l - 1] = levels[l].h; P.pitch[l - 1] = levels[l].pitch; P.off[l - 1] = levels[l].off; }
+                for (int l = 1; l <= p.nfuse; l++) { P.w[l - 1] = geo.levels[l].w; P.h[l - 1] = geo.levels[l].h; P.pitch[l - 1] = geo.levels[l].pitch; P.off[l - 1] = geo.levels[l].off; }
                 hipLaunchKernelGGL(by_window(k_threshold_pyr<5>, k_threshold_pyr<7>, k_threshold_pyr<11>, k_threshold_pyr<15>), tg1, dim3(256), 0, s,
-                                   srcW, cols, rows, p.thr_kk, bp, bits_fu32, wpr, ntx, ntl, ntl * B, pyr_view(), P);
+                                   srcW, geo.cols, geo.rows, p.thr_kk, bp, geo.bits_fu32, geo.wpr, ntx, ntl, ntl * B, pyr_view(), P);
                 if (p.nfuse && r_ == 0) pyramid(p.nfuse + 1, src0, B, s);
-            } else if (p.thr == Thr::magic)
-                hipLaunchKernelGGL(by_window(k_adaptive_threshold_t<5>, k_adaptive_threshold_t<7>, k_adaptive_threshold_t<11>, k_adaptive_threshold_t<15>), tg1,
-                                   dim3(256), 0, s, srcW, cols, rows, thres_value, th_magic, bp, bits_fu32, wpr, ntx, ntl, ntl * B);
-            else if (win <= 15) hipLaunchKernelGGL(k_adaptive_threshold<7>, tg, dim3(256), 0, s, srcW, cols, rows, win, thres_value, 1.0 / (win * win), bp, bits_fu32, wpr);
-            else hipLaunchKernelGGL(k_adaptive_threshold<15>, tg, dim3(256), 0, s, srcW, cols, rows, win, thres_value, 1.0 / (win * win), bp, bits_fu32, wpr);
+            } else if (geo.win <= 15) hipLaunchKernelGGL(k_adaptive_threshold<7>, tg, dim3(256), 0, s, srcW, geo.cols, geo.rows, geo.win, thres_value, 1.0 / (geo.win * geo.win), bp, geo.bits_fu32, geo.wpr);
+            else hipLaunchKernelGGL(k_adaptive_threshold<15>, tg, dim3(256), 0, s, srcW, geo.cols, geo.rows, geo.win, thres_value, 1.0 / (geo.win * geo.win), bp, geo.bits_fu32, geo.wpr);
         }
         return ORBFE_OK;
     }
@@ -702,21 +526,21 @@ struct orbfe_aruco {
     int speck_pass(const BatchPlan& p, int B, hipStream_t s)
     {
         int rc;
-        const size_t spk_lds = speck_lds_bytes(cols);
+        const size_t spk_lds = speck_lds_bytes(geo.cols);
         if (!(specks_ran = p.specks)) return ORBFE_OK;
-        if ((rc = d_bitsc.ensure(bits_fu32 * 4 * batch_cap)) || (rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_speck_clean), spk_lds))) return rc;
-        hipLaunchKernelGGL(k_speck_clean, dim3((rows + SPK_ROWS - 1) / SPK_ROWS, B), dim3(SPK_THREADS), spk_lds, s, d_bits.as<uint32_t>(), bits_fu32, wpr,
-                           cols, rows, d_bitsc.as<uint32_t>());
+        if ((rc = d_bitsc.ensure(geo.bits_fu32 * 4 * batch_cap)) || (rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_speck_clean), spk_lds))) return rc;
+        hipLaunchKernelGGL(k_speck_clean, dim3((geo.rows + SPK_ROWS - 1) / SPK_ROWS, B), dim3(SPK_THREADS), spk_lds, s, d_bits.as<uint32_t>(), geo.bits_fu32, geo.wpr,
+                           geo.cols, geo.rows, d_bitsc.as<uint32_t>());
         return ORBFE_OK;
     }
     // the tiled relay formulation (aruco_tiles.hip): k_ct_band or k_ct_walk, k_ct_lists, k_ct_points
     int contours_tiled(const BatchPlan& p, int B, const uint32_t* cbits, hipStream_t s)
     {
         int rc;
-        const int cw = p.tile_w, ncols = (cols + cw - 1) / cw, nbands = (rows + 31) / 32, total_tiles = ncols * nbands * B;
+        const int cw = p.tile_w, ncols = (geo.cols + cw - 1) / cw, nbands = (geo.rows + 31) / 32, total_tiles = ncols * nbands * B;
         const int wave_bytes = ctw_wave_lds_bytes(cw), wlds = wave_bytes * (CTW_THREADS / 64);
         const int walk_wgs = std::max(1, std::min((total_tiles / p.tpw + CTW_THREADS / 64 - 1) / (CTW_THREADS / 64), 256 * 8));
-        const size_t llds = (size_t)ct_lcap * 8 + 16;
+        const size_t llds = (size_t)geo.ct_lcap * 8 + 16;
         if ((rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_ct_walk), (size_t)wlds)) || (rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_ct_lists), llds))) return rc;
         if (ct_dirty) ORBFE_HIP(hipMemsetAsync(d_ctstate.p, 0, (size_t)CT_STATE_INTS * 4 * B, s)); // first use, or a batch abandoned before k_ct_lists (which leaves them at zero)
         ct_gen = (ct_gen + 1) & 0xffffu;
@@ -724,60 +548,60 @@ struct orbfe_aruco {
         if (ct_tab_dirty) { ORBFE_HIP(hipMemsetAsync(d_cthtab.p, 0, d_cthtab.bytes, s)); ct_tab_dirty = false; }
         ct_dirty = true;
         if (p.band) {
-            const int nb = ((rows + 31) / 32 + p.band_rows - 1) / p.band_rows;
-            const size_t blds = ctb_lds_bytes(cols, p.band_rows);
+            const int nb = ((geo.rows + 31) / 32 + p.band_rows - 1) / p.band_rows;
+            const size_t blds = ctb_lds_bytes(geo.cols, p.band_rows);
             if ((rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_ct_band), blds))) return rc;
-            hipLaunchKernelGGL(k_ct_band, dim3(nb, B), dim3(CTB_THREADS), blds, s, cbits, bits_fu32, wpr, cols, rows, 70,
-                               d_lut.as<uint16_t>(), p.band_rows, d_ctmlist.as<uint32_t>(), CTB_MCAP, d_cthtab.as<unsigned long long>(), ct_hbits, ct_gen,
-                               d_ctseg.as<uint32_t>(), (size_t)5 * ct_segcap, ct_segcap, d_ctstate.as<int32_t>(), d_pool.as<uint32_t>(), pool_fu32,
-                               (int)pool_fu32, relay_kcap, d_tailkeys.as<unsigned long long>(), d_tailoff.as<int32_t>(), d_ctcodes.as<uint4>());
+            hipLaunchKernelGGL(k_ct_band, dim3(nb, B), dim3(CTB_THREADS), blds, s, cbits, geo.bits_fu32, geo.wpr, geo.cols, geo.rows, 70,
+                               d_lut.as<uint16_t>(), p.band_rows, d_ctmlist.as<uint32_t>(), CTB_MCAP, d_cthtab.as<unsigned long long>(), geo.ct_hbits, ct_gen,
+                               d_ctseg.as<uint32_t>(), (size_t)5 * geo.ct_segcap, geo.ct_segcap, d_ctstate.as<int32_t>(), d_pool.as<uint32_t>(), geo.pool_fu32,
+                               (int)geo.pool_fu32, geo.relay_kcap, d_tailkeys.as<unsigned long long>(), d_tailoff.as<int32_t>(), d_ctcodes.as<uint4>());
         } else
-            hipLaunchKernelGGL(k_ct_walk, dim3(walk_wgs), dim3(CTW_THREADS), wlds, s, cbits, bits_fu32, wpr, cols, rows, 70,
-                               d_lut.as<uint16_t>(), cw, ncols, nbands, total_tiles, d_cthtab.as<unsigned long long>(), ct_hbits, ct_gen,
-                               d_ctseg.as<uint32_t>(), (size_t)5 * ct_segcap, ct_segcap, d_ctstate.as<int32_t>(), d_pool.as<uint32_t>(), pool_fu32,
-                               (int)pool_fu32, relay_kcap, d_tailkeys.as<unsigned long long>(), d_tailoff.as<int32_t>(), wave_bytes,
+            hipLaunchKernelGGL(k_ct_walk, dim3(walk_wgs), dim3(CTW_THREADS), wlds, s, cbits, geo.bits_fu32, geo.wpr, geo.cols, geo.rows, 70,
+                               d_lut.as<uint16_t>(), cw, ncols, nbands, total_tiles, d_cthtab.as<unsigned long long>(), geo.ct_hbits, ct_gen,
+                               d_ctseg.as<uint32_t>(), (size_t)5 * geo.ct_segcap, geo.ct_segcap, d_ctstate.as<int32_t>(), d_pool.as<uint32_t>(), geo.pool_fu32,
+                               (int)geo.pool_fu32, geo.relay_kcap, d_tailkeys.as<unsigned long long>(), d_tailoff.as<int32_t>(), wave_bytes,
                                d_ctcodes.as<uint4>());
-        hipLaunchKernelGGL(k_ct_lists, dim3(B), dim3(ct_lcap > 4096 ? 1024 : 512), llds, s, d_ctseg.as<uint32_t>(), (size_t)5 * ct_segcap, ct_segcap,
-                           d_ctstate.as<int32_t>(), d_cthtab.as<unsigned long long>(), ct_hbits, ct_gen, d_ctelem.as<unsigned long long>(), ct_lcap, 70,
-                           (int)pool_fu32, relay_kcap, d_tailkeys.as<unsigned long long>(), d_tailoff.as<int32_t>(), d_counts.as<int32_t>(),
-                           d_rstate.as<int32_t>(), d_ctitemsA.as<uint4>(), d_ctitemsB.as<uint2>(), ct_items_per_frame, d_ctnitems.as<int32_t>());
+        hipLaunchKernelGGL(k_ct_lists, dim3(B), dim3(geo.ct_lcap > 4096 ? 1024 : 512), llds, s, d_ctseg.as<uint32_t>(), (size_t)5 * geo.ct_segcap, geo.ct_segcap,
+                           d_ctstate.as<int32_t>(), d_cthtab.as<unsigned long long>(), geo.ct_hbits, ct_gen, d_ctelem.as<unsigned long long>(), geo.ct_lcap, 70,
+                           (int)geo.pool_fu32, geo.relay_kcap, d_tailkeys.as<unsigned long long>(), d_tailoff.as<int32_t>(), d_counts.as<int32_t>(),
+                           d_rstate.as<int32_t>(), d_ctitemsA.as<uint4>(), d_ctitemsB.as<uint2>(), geo.ct_items_per_frame, d_ctnitems.as<int32_t>());
         if (hipPeekAtLastError() == hipSuccess) ct_dirty = false;
-        hipLaunchKernelGGL(k_ct_points, dim3(ct_items_per_frame >= 8192 ? 32 : 8, B), dim3(256), 0, s, d_ctitemsA.as<uint4>(), d_ctitemsB.as<uint2>(),
-                           ct_items_per_frame, d_ctnitems.as<int32_t>(), d_ctcodes.as<uint32_t>(), ct_segcap, d_pool.as<uint32_t>(), pool_fu32);
+        hipLaunchKernelGGL(k_ct_points, dim3(geo.ct_items_per_frame >= 8192 ? 32 : 8, B), dim3(256), 0, s, d_ctitemsA.as<uint4>(), d_ctitemsB.as<uint2>(),
+                           geo.ct_items_per_frame, d_ctnitems.as<int32_t>(), d_ctcodes.as<uint32_t>(), geo.ct_segcap, d_pool.as<uint32_t>(), geo.pool_fu32);
         return ORBFE_OK;
     }
     // the one-workgroup relay kernels (a workgroup per frame), then k_contours_small
     int contours_relay(const BatchPlan& p, int B, const uint32_t* cbits, hipStream_t s)
     {
-        const size_t rlds = relay_lds_bytes(relay_global ? 0 : lds_bits_words, relay_kcap, relay_tbits);
+        const size_t rlds = relay_lds_bytes(geo.relay_global ? 0 : geo.lds_bits_words, geo.relay_kcap, geo.relay_tbits);
         // (round 2 launched the large-frame kernels, whose workgroups take a CU's whole LDS, in chunks of N frames: no gain at 128 / 192,
         // worse below -- profiles/r02_relay_chunks.txt; one launch since round 5)
         if (p.relay == Relay::relay8g) {
             if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_contours_relay8g), rlds)) return rc;
-            hipLaunchKernelGGL(k_contours_relay8g, dim3(B), dim3(RL_THREADS_BIG), rlds, s, cbits, bits_fu32, wpr,
-                               cols, rows, 0, 70, relay_kshift, relay_tbits, d_segs.as<RelaySeg>(),
-                               d_pool.as<uint32_t>(), pool_fu32, (int)pool_fu32, d_kept.as<ArKept>(), relay_kcap, relay_kcap,
+            hipLaunchKernelGGL(k_contours_relay8g, dim3(B), dim3(RL_THREADS_BIG), rlds, s, cbits, geo.bits_fu32, geo.wpr,
+                               geo.cols, geo.rows, 0, 70, geo.relay_kshift, geo.relay_tbits, d_segs.as<RelaySeg>(),
+                               d_pool.as<uint32_t>(), geo.pool_fu32, (int)geo.pool_fu32, d_kept.as<ArKept>(), geo.relay_kcap, geo.relay_kcap,
                                d_tailkeys.as<unsigned long long>(), d_tailoff.as<int32_t>(), d_counts.as<int32_t>(), d_hint.as<int32_t>(),
-                               d_small.as<uint4>(), d_rstate.as<int32_t>(), d_gpad.as<uint32_t>(), gpad_fu32, d_lut.as<uint16_t>(), 0);
+                               d_small.as<uint4>(), d_rstate.as<int32_t>(), d_gpad.as<uint32_t>(), geo.gpad_fu32, d_lut.as<uint16_t>(), 0);
         } else {
             auto rfn = p.relay == Relay::relay8 ? k_contours_relay8 : p.relay == Relay::wide ? k_contours_relay_wide : k_contours_relay;
             if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(rfn), rlds)) return rc;
-            hipLaunchKernelGGL(rfn, dim3(B), dim3(p.relay == Relay::relay ? RL_THREADS : RL_THREADS_BIG), rlds, s, cbits, bits_fu32, wpr,
-                               cols, rows, lds_bits_words, 70, relay_kshift, relay_tbits, d_segs.as<RelaySeg>(),
-                               d_pool.as<uint32_t>(), pool_fu32, (int)pool_fu32, d_kept.as<ArKept>(), relay_kcap, relay_kcap,
+            hipLaunchKernelGGL(rfn, dim3(B), dim3(p.relay == Relay::relay ? RL_THREADS : RL_THREADS_BIG), rlds, s, cbits, geo.bits_fu32, geo.wpr,
+                               geo.cols, geo.rows, geo.lds_bits_words, 70, geo.relay_kshift, geo.relay_tbits, d_segs.as<RelaySeg>(),
+                               d_pool.as<uint32_t>(), geo.pool_fu32, (int)geo.pool_fu32, d_kept.as<ArKept>(), geo.relay_kcap, geo.relay_kcap,
                                d_tailkeys.as<unsigned long long>(), d_tailoff.as<int32_t>(), d_counts.as<int32_t>(), d_hint.as<int32_t>(),
                                d_small.as<uint4>(), d_rstate.as<int32_t>(), (p.small_separate ? 1 : 0) | (specks_inkernel && !p.specks && !p.small_separate ? 2 : 0),
-                               d_lut.as<uint16_t>(), 0, d_candq.as<uint32_t>(), candq_fu32);
+                               d_lut.as<uint16_t>(), 0, d_candq.as<uint32_t>(), geo.candq_fu32);
         }
         // the borders that touch no grid line, for frames done with a grid by a relay kernel that leaves them out (the
         // HBM-resident one: its bands fit LDS here; for LDS-resident frames the separate launch halves the relay kernel's time
         // but issues twice the instructions of the in-kernel phase -- measured 1.85 -> 1.98 ms per C2 step -- so those keep
         // phase (c) inside): bands of K rows, K >= 2^relay_kshift
         if (p.small_separate) {
-            const int nwaves = ((cols >> RS_BLOCK_SHIFT) + 1) * ((rows >> relay_kshift) + 1); // blocks of the finest grid
+            const int nwaves = ((geo.cols >> RS_BLOCK_SHIFT) + 1) * ((geo.rows >> geo.relay_kshift) + 1); // blocks of the finest grid
             hipLaunchKernelGGL(k_contours_small, dim3((nwaves + RS_THREADS / 64 - 1) / (RS_THREADS / 64), B), dim3(RS_THREADS), 0, s,
-                               cbits, bits_fu32, wpr, cols, rows, 70, d_lut.as<uint16_t>(), d_rstate.as<int32_t>(),
-                               d_pool.as<uint32_t>(), pool_fu32, (int)pool_fu32, relay_kcap, d_tailkeys.as<unsigned long long>(),
+                               cbits, geo.bits_fu32, geo.wpr, geo.cols, geo.rows, 70, d_lut.as<uint16_t>(), d_rstate.as<int32_t>(),
+                               d_pool.as<uint32_t>(), geo.pool_fu32, (int)geo.pool_fu32, geo.relay_kcap, d_tailkeys.as<unsigned long long>(),
                                d_tailoff.as<int32_t>(), d_counts.as<int32_t>());
         }
         return ORBFE_OK;
@@ -788,17 +612,17 @@ struct orbfe_aruco {
         int rc;
         const int pts = RT_PTS, tail_wgs = std::min(RT_WGS, B * 128);   // pts: LDS point buffer per wave; longer borders are read from the pool
         const size_t alds = tail_approx_lds_bytes(pts);
-        if ((rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_tail_prep), tail_prep_lds_bytes(relay_kcap))) || (rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_tail_approx), alds))) return rc;
+        if ((rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_tail_prep), tail_prep_lds_bytes(geo.relay_kcap))) || (rc = ensure_dyn_lds(reinterpret_cast<const void*>(k_tail_approx), alds))) return rc;
         if (tail_dirty) ORBFE_HIP(hipMemsetAsync(d_tctr.p, 0, 16, s));   // a previous batch was abandoned between prep and finish
         tail_dirty = true;
-        hipLaunchKernelGGL(k_tail_prep, dim3(B), dim3(relay_global ? 1024 : 256), tail_prep_lds_bytes(relay_kcap), s,
-                           d_tailkeys.as<unsigned long long>(), d_tailoff.as<int32_t>(), relay_kcap, d_counts.as<int32_t>(),
-                           d_twork.as<uint4>(), (size_t)relay_kcap * B, d_tctr.as<int32_t>());
-        hipLaunchKernelGGL(k_tail_approx, dim3(tail_wgs), dim3(256), alds, s, relay_kcap, d_twork.as<uint4>(), (size_t)relay_kcap * B, d_tctr.as<int32_t>(),
-                           d_pool.as<uint32_t>(), pool_fu32, d_kept.as<ArKept>(), relay_kcap, d_trect.as<uint8_t>(), pts);
+        hipLaunchKernelGGL(k_tail_prep, dim3(B), dim3(geo.relay_global ? 1024 : 256), tail_prep_lds_bytes(geo.relay_kcap), s,
+                           d_tailkeys.as<unsigned long long>(), d_tailoff.as<int32_t>(), geo.relay_kcap, d_counts.as<int32_t>(),
+                           d_twork.as<uint4>(), (size_t)geo.relay_kcap * B, d_tctr.as<int32_t>());
+        hipLaunchKernelGGL(k_tail_approx, dim3(tail_wgs), dim3(256), alds, s, geo.relay_kcap, d_twork.as<uint4>(), (size_t)geo.relay_kcap * B, d_tctr.as<int32_t>(),
+                           d_pool.as<uint32_t>(), geo.pool_fu32, d_kept.as<ArKept>(), geo.relay_kcap, d_trect.as<uint8_t>(), pts);
         // (the rectangle lists: a launch of their own only when the enclosed-marker pass sits between them and k_prefilter)
         if ((*finish_in_prefilter = !enclosed)) return ORBFE_OK;
-        hipLaunchKernelGGL(k_tail_finish, dim3(B), dim3(64), 0, s, relay_kcap, d_trect.as<uint8_t>(), d_kept.as<ArKept>(), relay_kcap,
+        hipLaunchKernelGGL(k_tail_finish, dim3(B), dim3(64), 0, s, geo.relay_kcap, d_trect.as<uint8_t>(), d_kept.as<ArKept>(), geo.relay_kcap,
                            d_rects.as<ArRect>(), AR_MAX_RECTS, d_counts.as<int32_t>(), d_tctr.as<int32_t>());
         if (hipPeekAtLastError() == hipSuccess) tail_dirty = false;   // k_tail_finish leaves the list lengths at zero
         return ORBFE_OK;
@@ -806,14 +630,14 @@ struct orbfe_aruco {
     // the single-walker kernel: images whose bit image does not fit LDS next to the relay kernel's tables, big-frame mode, or forced
     int contours_single_walker(const BatchPlan& p, int B, const uint32_t* cbits, hipStream_t s)
     {
-        const int kcap = p.walker_hbm ? AR_MAX_KEPT_BIG : AR_MAX_KEPT, ldsw = p.walker_hbm ? 0 : lds_bits_words;
+        const int kcap = p.walker_hbm ? AR_MAX_KEPT_BIG : AR_MAX_KEPT, ldsw = p.walker_hbm ? 0 : geo.lds_bits_words;
         const size_t lds = contours_lds_bytes(ldsw, kcap);
         auto kfn = p.walker_hbm ? k_contours_t<false> : k_contours_t<true>;
         if (int rc = ensure_dyn_lds(reinterpret_cast<const void*>(kfn), lds)) return rc;
         if (!ORBFE_SKIP_ARUCO(1))
-            hipLaunchKernelGGL(kfn, dim3(B), dim3(CT_PROBE_THREADS), lds, s, cbits, bits_fu32, wpr, cols, rows, ldsw, 70, d_candq.as<uint32_t>(),
-                               candq_fu32, (int)candq_fu32, d_pool.as<uint32_t>(), pool_fu32, (int)pool_fu32, d_kept.as<ArKept>(), kcap,
-                               d_rects.as<ArRect>(), AR_MAX_RECTS, d_counts.as<int32_t>(), d_gpad.as<uint32_t>(), gpad_fu32, 0);
+            hipLaunchKernelGGL(kfn, dim3(B), dim3(CT_PROBE_THREADS), lds, s, cbits, geo.bits_fu32, geo.wpr, geo.cols, geo.rows, ldsw, 70, d_candq.as<uint32_t>(),
+                               geo.candq_fu32, (int)geo.candq_fu32, d_pool.as<uint32_t>(), geo.pool_fu32, (int)geo.pool_fu32, d_kept.as<ArKept>(), kcap,
+                               d_rects.as<ArRect>(), AR_MAX_RECTS, d_counts.as<int32_t>(), d_gpad.as<uint32_t>(), geo.gpad_fu32, 0);
         return ORBFE_OK;
     }
     // prefilterCandidates, then the batch's candidates decoded as one work list: a wave per candidate (persistent: 32 candidates per
@@ -825,16 +649,16 @@ struct orbfe_aruco {
                                (int)(float(enlarge_k) / 2.));
         if (decode_dirty) ORBFE_HIP(hipMemsetAsync(d_dctr.p, 0, 16, s));   // a previous batch was abandoned between prefilter and finalize
         decode_dirty = true;
-        const TailFinish tf = finish_in_prefilter ? TailFinish{relay_kcap, d_trect.as<uint8_t>(), d_kept.as<ArKept>(), relay_kcap, d_tctr.as<int32_t>()} : TailFinish{};
+        const TailFinish tf = finish_in_prefilter ? TailFinish{geo.relay_kcap, d_trect.as<uint8_t>(), d_kept.as<ArKept>(), geo.relay_kcap, d_tctr.as<int32_t>()} : TailFinish{};
         hipLaunchKernelGGL(k_prefilter, dim3(B), dim3(256), 0, s, d_rects.as<ArRect>(), AR_MAX_RECTS,
-                           d_counts.as<int32_t>(), cols, rows, win, d_candidx.as<int32_t>(), d_ncand.as<int32_t>(),
+                           d_counts.as<int32_t>(), geo.cols, geo.rows, geo.win, d_candidx.as<int32_t>(), d_ncand.as<int32_t>(),
                            d_dwork.as<uint32_t>(), d_dctr.as<int32_t>(), tf);
         if (finish_in_prefilter && hipPeekAtLastError() == hipSuccess) tail_dirty = false;   // (it leaves the tail's list lengths at zero)
         if (!p.nfuse) ORBFE_HIP(hipStreamWaitEvent(s, ev_join, 0));   // the pyramid of the aux stream
         const int max_items = B * AR_MAX_RECTS, wgs = std::max(1, std::min((B * 32 + DC_WAVES - 1) / DC_WAVES, 4096));
         for (int r_ = 0; r_ < ORBFE_REPS_ARUCO(2); r_++) {
-            hipLaunchKernelGGL(k_decode_warp, dim3(wgs), dim3(DC_WAVES * 64), 0, s, src0, pyr_view(), d_levels.as<ArLevel>(), npyr,
-                               d_rects.as<ArRect>(), AR_MAX_RECTS, d_candidx.as<int32_t>(), S, cols, d_dwork.as<uint32_t>(),
+            hipLaunchKernelGGL(k_decode_warp, dim3(wgs), dim3(DC_WAVES * 64), 0, s, src0, pyr_view(), d_levels.as<ArLevel>(), geo.npyr,
+                               d_rects.as<ArRect>(), AR_MAX_RECTS, d_candidx.as<int32_t>(), S, geo.cols, d_dwork.as<uint32_t>(),
                                d_dctr.as<int32_t>(), d_ditems.as<DcItem>(), d_dhist.as<uint16_t>(), d_dpatch.as<uint8_t>());
             hipLaunchKernelGGL(k_decode_otsu, dim3((max_items + 63) / 64), dim3(64), 0, s, d_dctr.as<int32_t>(), d_ditems.as<DcItem>(),
                                d_dhist.as<uint16_t>(), S);
@@ -854,9 +678,9 @@ struct orbfe_aruco {
                                AR_MAX_RECTS, d_dhist.as<uint16_t>(), mr->d_hist);
         if (reduced) {   // cornerUpsample: before sort / dedupe, whose perimeters are those of the upsampled corners
             int start = 0;
-            for (int i = 0; i < npyr && cols < levels[i].w; i++) start = i;
+            for (int i = 0; i < geo.npyr && geo.cols < geo.levels[i].w; i++) start = i;
             const int wgs = std::max(1, std::min((B * 32 * 4 + 3) / 4, 2048));
-            hipLaunchKernelGGL(k_upsample_corners, dim3(wgs), dim3(256), 0, s, src0, pyr_view(), d_levels.as<ArLevel>(), start, cols,
+            hipLaunchKernelGGL(k_upsample_corners, dim3(wgs), dim3(256), 0, s, src0, pyr_view(), d_levels.as<ArLevel>(), start, geo.cols,
                                d_rects.as<ArRect>(), AR_MAX_RECTS, d_candidx.as<int32_t>(), d_dwork.as<uint32_t>(), d_dctr.as<int32_t>(),
                                d_result.as<int32_t>(), d_masks.as<float>());
         }
@@ -864,10 +688,10 @@ struct orbfe_aruco {
         // corner refinement applies only when the input was not reduced (:8420): CORNER_LINES inside k_finalize, CORNER_SUBPIX after it
         for (int r_ = 0; r_ < ORBFE_REPS_ARUCO(4); r_++) hipLaunchKernelGGL(k_finalize, dim3(B), dim3(256), 0, s, d_rects.as<ArRect>(), AR_MAX_RECTS,
                            d_candidx.as<int32_t>(), d_ncand.as<int32_t>(), d_result.as<int32_t>(),
-                           d_pool.as<uint32_t>(), pool_fu32, d_out_m, capacity, d_n, (corner_method == 1 && !reduced) ? 1 : 0, d_msrc.as<int32_t>(),
+                           d_pool.as<uint32_t>(), geo.pool_fu32, d_out_m, capacity, d_n, (corner_method == 1 && !reduced) ? 1 : 0, d_msrc.as<int32_t>(),
                            d_dctr.as<int32_t>());
         if (corner_method == 0 && !reduced)   // cornerSubPix(grey, Size(4, 4), TermCriteria(MAX_ITER | EPS, 12, 0.005)) (:8511)
-            hipLaunchKernelGGL(k_corner_subpix_markers, dim3(16, B), dim3(256), 0, s, src0, cols, rows, d_out_m, d_n, capacity, 4, 12,
+            hipLaunchKernelGGL(k_corner_subpix_markers, dim3(16, B), dim3(256), 0, s, src0, geo.cols, geo.rows, d_out_m, d_n, capacity, 4, 12,
                                0.005 * 0.005, d_masks.as<float>() + (size_t)3 * 17 * 17);
         return ORBFE_OK;
     }
@@ -1232,7 +1056,7 @@ int orbfe_aruco_marker_contour(orbfe_aruco* h, int frame, int marker, int32_t* x
     const int m = std::min(r.len, capacity);
     if (m > 0) {
         std::vector<uint32_t> p(m);
-        ORBFE_HIP(hipMemcpy(p.data(), h->d_pool.as<uint32_t>() + (size_t)frame * h->pool_fu32 + r.off, (size_t)m * 4, hipMemcpyDeviceToHost));
+        ORBFE_HIP(hipMemcpy(p.data(), h->d_pool.as<uint32_t>() + (size_t)frame * h->geo.pool_fu32 + r.off, (size_t)m * 4, hipMemcpyDeviceToHost));
         for (int i = 0; i < m; i++) { xy[2 * i] = (int32_t)(p[i] & 0xffff); xy[2 * i + 1] = (int32_t)(p[i] >> 16); }
     }
     return ORBFE_OK;
@@ -1261,7 +1085,7 @@ int orbfe_aruco_marker_contours(orbfe_aruco* h, int frame, int nmarkers, int32_t
     }
     if (offsets[nmarkers] > capacity || hi <= lo) return ORBFE_OK; // the caller reads the total from offsets and comes back with room
     std::vector<uint32_t> p((size_t)(hi - lo));
-    ORBFE_HIP(hipMemcpy(p.data(), h->d_pool.as<uint32_t>() + (size_t)frame * h->pool_fu32 + lo, p.size() * 4, hipMemcpyDeviceToHost));
+    ORBFE_HIP(hipMemcpy(p.data(), h->d_pool.as<uint32_t>() + (size_t)frame * h->geo.pool_fu32 + lo, p.size() * 4, hipMemcpyDeviceToHost));
     for (int i = 0; i < nmarkers; i++) {
         const ArRect& r = rects[(size_t)src[i]];
         int32_t* o = xy + 2 * (size_t)offsets[i];
@@ -1673,17 +1497,17 @@ int orbfe_aruco_debug_image(orbfe_aruco* h, int frame, int stage, uint8_t* out)
     if (rc) return rc;
     ORBFE_HIP(hipDeviceSynchronize());
     if (stage == 0 || stage == 104) { // the threshold image; 104: the bit image the contour kernels of the last batch read (after the speck passes, if they ran)
-        std::vector<uint32_t> bits(h->bits_fu32);
-        ORBFE_HIP(hipMemcpy(bits.data(), (stage == 104 && h->specks_ran ? h->d_bitsc : h->d_bits).as<uint32_t>() + (size_t)frame * h->bits_fu32, bits.size() * 4,
+        std::vector<uint32_t> bits(h->geo.bits_fu32);
+        ORBFE_HIP(hipMemcpy(bits.data(), (stage == 104 && h->specks_ran ? h->d_bitsc : h->d_bits).as<uint32_t>() + (size_t)frame * h->geo.bits_fu32, bits.size() * 4,
                             hipMemcpyDeviceToHost));
-        for (int y = 0; y < h->rows; y++)
-            for (int x = 0; x < h->cols; x++)
-                out[(size_t)y * h->cols + x] = ((bits[(size_t)y * h->wpr + (x >> 5)] >> (x & 31)) & 1) ? 255 : 0;
+        for (int y = 0; y < h->geo.rows; y++)
+            for (int x = 0; x < h->geo.cols; x++)
+                out[(size_t)y * h->geo.cols + x] = ((bits[(size_t)y * h->geo.wpr + (x >> 5)] >> (x & 31)) & 1) ? 255 : 0;
         return ORBFE_OK;
     }
-    if (stage >= 1 && stage < h->npyr + 1 && stage - 1 >= 1) { // pyramid level stage-1 (>= 1)
-        const ArLevel& L = h->levels[stage - 1];
-        ORBFE_HIP(hipMemcpy2D(out, L.w, h->d_pyr.as<uint8_t>() + (size_t)frame * h->pyr_fbytes + L.off, L.pitch, L.w, L.h,
+    if (stage >= 1 && stage < h->geo.npyr + 1 && stage - 1 >= 1) { // pyramid level stage-1 (>= 1)
+        const ArLevel& L = h->geo.levels[stage - 1];
+        ORBFE_HIP(hipMemcpy2D(out, L.w, h->d_pyr.as<uint8_t>() + (size_t)frame * h->geo.pyr_fbytes + L.off, L.pitch, L.w, L.h,
                               hipMemcpyDeviceToHost));
         return ORBFE_OK;
     }
@@ -1751,7 +1575,7 @@ int orbfe_aruco_debug_control(orbfe_aruco* h, const char* key, int value)
         h->tiled = value;
     }
     else if (!strcmp(key, "speck_passes") && on_off) h->specks = value;
-    else if (!strcmp(key, "speck_passes_in_kernel") && on_off) { h->specks_inkernel = value; h->rows = h->cols = 0; }   // (the queue's size depends on it: geometry rebuilt)
+    else if (!strcmp(key, "speck_passes_in_kernel") && on_off) { h->specks_inkernel = value; h->invalidate_geometry(); }   // (the queue's size depends on it: geometry rebuilt)
     else if (!strcmp(key, "threshold_pyr") && on_off) h->thr_v2 = value;
     else if (!strcmp(key, "threshold_mfma") && by_rule) { h->thr_mfma = value != 0; h->thr_mfma_auto = value == -1; }
     else if (!strcmp(key, "half_pyr") && on_off) h->half_pyr = value;

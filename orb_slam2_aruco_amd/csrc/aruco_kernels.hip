@@ -1,7 +1,9 @@
 // aruco_kernels.hip -- gfx950 kernels of the ArUco marker detector (DM_NORMAL + CORNER_LINES, the configuration of
 // reference src/Frame.cc:129-142).  Pipeline per batch of B same-sized frames:
 //
-//   k_adaptive_threshold  box-mean adaptive threshold, writes a BIT image (1 bit/px)       (markerdetector_impl.cpp:2983)
+//   k_threshold_mfma / k_threshold_pyr / k_adaptive_threshold   box-mean adaptive threshold, writes a BIT image (1 bit/px):
+//                         on the matrix cores, on packed dot products (+ the pyramid's first levels), and the generic
+//                         fall-back for the windows and constants neither takes            (markerdetector_impl.cpp:2983)
 //   k_half_area / resize  the detector's /2 pyramid used by the 35x35 warps                 (:1299-1488)
 //   k_contours            one workgroup per frame: bit image -> LDS, border starts, read-only border following,
 //                         length gate (> 70), approxPolyDP, 4-gon + convexity               (:3104-3556)
@@ -99,132 +101,24 @@ __global__ __launch_bounds__(256) void k_adaptive_threshold(ImgView src, int W, 
 template __global__ void k_adaptive_threshold<7>(ImgView, int, int, int, int, double, uint32_t*, size_t, int);
 template __global__ void k_adaptive_threshold<15>(ImgView, int, int, int, int, double, uint32_t*, size_t, int);
 
-// The same threshold on the packed dot-product instructions (the generic kernel above issues 2 * 15 predicated LDS reads
-// and adds per pixel and an fp64 multiply for the mean).  64 x 64 tile per workgroup, WIN = 2 R + 1 a template parameter:
+// The threshold kernel of the batched path (round 6), on the packed dot-product instructions (the generic kernel above issues
+// 2 * 15 predicated LDS reads and adds per pixel and an fp64 multiply for the mean).  64 x 64 tile per workgroup, WIN = 2 R + 1 a
+// template parameter:
 //   horizontal: a thread loads the bytes around 4 adjacent outputs of one row as 3 (R <= 3) or 5 dwords; a box sum of WIN
 //               bytes is ceil(WIN / 4) v_dot4_u32_u8 with all-ones weights on windows cut out with v_alignbyte; the sums
 //               go to LDS column-major, the tile's own pixels row-major;
-//   vertical:   a lane owns one column and 16 consecutive rows: 16 + 2 R sums as dwords, sliding window down the column;
-//               mean = (s + WIN^2 / 2) / WIN^2 as a multiply-high (WIN^2 is odd, so the rounding has no ties and equals
-//               rint(s * (1.0 / WIN^2)) -- verified exhaustively by the host before this kernel is chosen);
-//               one 64-bit ballot per row = 64 bits of the bit image.
-typedef uint32_t u32_unaligned_t __attribute__((aligned(1)));
-template <int WIN>
-__global__ __launch_bounds__(256) void k_adaptive_threshold_t(ImgView src, int W, int H, int C, uint32_t magic,
-                                                              uint32_t* __restrict__ bits, size_t bits_fstride, int wpr, int ntx, int ntiles,
-                                                              int total)
-{
-    constexpr int R = WIN / 2, NDW = R <= 3 ? 3 : 5, LEAD = R <= 3 ? 4 : 8; // window = bytes x - LEAD .. x - LEAD + 4 NDW - 1
-    constexpr int ROWS = 64 + 2 * R, P0 = (ROWS + 1) & ~1, PITCH = ((P0 / 2) & 1) ? P0 : P0 + 2; // u16 per LDS column:
-    __shared__ __align__(16) uint16_t sh[64 * PITCH];                                           // an odd number of dwords
-    __shared__ __align__(16) uint32_t spx[64][16];
-    // 1-D grid renumbered so that the tiles of a frame run on one XCD (xcd_remap): neighbouring tiles share the 128-byte lines
-    // their 64-byte rows lie in and their halo rows; on eight different L2s every line was fetched 3.5 times
-    int tile, f;
-    if (!xcd_remap(ntiles, total, tile, f)) return;
-    const int tyi = tile / ntx;
-    const int tx0 = (tile - tyi * ntx) * 64, ty0 = tyi * 64;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const uint8_t* img = src.base + (size_t)f * src.fstride;
-    constexpr int NIT = (ROWS * 16 + 255) / 256;
-    uint32_t w[NIT][NDW];
-#pragma unroll
-    for (int k = 0; k < NIT; k++) {
-        const int it = tid + 256 * k;
-        const int rr = it >> 4, x = tx0 + 4 * (it & 15);
-#pragma unroll
-        for (int j = 0; j < NDW; j++) w[k][j] = 0;
-        if (rr < ROWS) {
-            const uint8_t* row = img + (uint32_t)__mul24(min(max(ty0 + rr - R, 0), H - 1), src.pitch); // BORDER_REPLICATE (24-bit multiply: a 32-bit offset off the uniform base instead of a 64-bit v_mad_i64_i32)
-            if (x >= LEAD && x - LEAD + 4 * NDW <= W) {
-#pragma unroll
-                for (int j = 0; j < NDW; j++) w[k][j] = reinterpret_cast<const u32_unaligned_t*>(row + x - LEAD)[j];
-            } else {
-                // the window crosses the left or right image border (BORDER_REPLICATE).  Its dwords start at multiples of four, so
-                // a dword is either inside (loaded), left of the image (pixel 0 four times) or at / beyond the right edge: its
-                // pixels then come out of the row's last four with one v_perm (n_in = 3, 2, 1, <= 0 pixels of it are inside)
-                const uint32_t first = reinterpret_cast<const u32_unaligned_t*>(row)[0];
-                const uint32_t last = reinterpret_cast<const u32_unaligned_t*>(row + W - 4)[0];
-#pragma unroll
-                for (int j = 0; j < NDW; j++) {
-                    const int q = x - LEAD + 4 * j, n_in = W - q;
-                    if (q < 0) w[k][j] = __builtin_amdgcn_perm(0u, first, 0x00000000u);
-                    else if (n_in >= 4) w[k][j] = reinterpret_cast<const u32_unaligned_t*>(row + q)[0];
-                    else w[k][j] = __builtin_amdgcn_perm(0u, last, n_in <= 1 ? 0x03030303u : n_in == 2 ? 0x03030302u : 0x03030201u);
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < NIT; k++) {
-        const int it = tid + 256 * k;
-        const int rr = it >> 4, c = 4 * (it & 15);
-        if (rr < ROWS) {
-            uint32_t sum[4];
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                // output i sums window bytes a .. a + WIN - 1, a = LEAD + i - R
-                constexpr uint32_t ONES = 0x01010101u;
-                const int a = LEAD + i - R;
-                uint32_t acc = 0;
-#pragma unroll
-                for (int q = 0; q < (WIN + 3) / 4; q++) {
-                    const int b = a + 4 * q, j = b >> 2, sft = b & 3;                 // window bytes b .. b+3
-                    const uint32_t hi = j + 1 < NDW ? w[k][j + 1] : 0u;
-                    const uint32_t v = sft ? __builtin_amdgcn_alignbyte(hi, w[k][j], sft) : w[k][j];
-                    const int left = WIN - 4 * q;                                       // bytes still to add
-                    acc = bl_dot4_a(v, left >= 4 ? ONES : (ONES >> (8 * (4 - left))), acc);
-                }
-                sum[i] = acc;
-            }
-#pragma unroll
-            for (int i = 0; i < 4; i++) sh[(c + i) * PITCH + rr] = (uint16_t)sum[i];
-            if (rr >= R && rr < 64 + R) spx[rr - R][it & 15] = w[k][LEAD / 4]; // the tile's own pixels x .. x+3
-        }
-    }
-    __syncthreads();
-    // vertical: lane = column, wave = 16 rows
-    {
-        const int c = lane, r0 = 16 * wid;
-        const uint16_t* hp = &sh[c * PITCH + r0];
-        int s = 0;
-#pragma unroll
-        for (int k = 0; k < WIN; k++) s += hp[k];
-        const int x = tx0 + c;
-        const uint8_t* px = reinterpret_cast<const uint8_t*>(&spx[r0][0]) + c;
-#pragma unroll
-        for (int k = 0; k < 16; k++) {
-            const int y = ty0 + r0 + k;
-            // mean = floor((s + WIN^2 / 2) / WIN^2) (<= 255: no saturation) and "v - mean <= -C" is "mean >= v + C", i.e.
-            // s + WIN^2 / 2 >= WIN^2 (v + C): one 24-bit multiply-add and a compare instead of the division (a quarter-rate v_mul_hi)
-            const int v = px[k * 64];
-            const bool on = (x < W) && (y < H) && (s + WIN * WIN / 2 >= __mul24(WIN * WIN, v + C));   // (v_mul_u32_u24; v_mul_lo_u32 without the hint)
-            const unsigned long long m = __ballot(on);
-            if (y < H && lane < 2) {
-                const int word = (tx0 >> 5) + lane;
-                if (word < wpr) bits[(size_t)f * bits_fstride + (uint32_t)(__mul24(y, wpr) + word)] = (uint32_t)(m >> (32 * lane));
-            }
-            if (k < 15) s += (int)hp[k + WIN] - (int)hp[k];
-        }
-    }
-}
-template __global__ void k_adaptive_threshold_t<5>(ImgView, int, int, int, uint32_t, uint32_t*, size_t, int, int, int, int);
-template __global__ void k_adaptive_threshold_t<7>(ImgView, int, int, int, uint32_t, uint32_t*, size_t, int, int, int, int);
-template __global__ void k_adaptive_threshold_t<11>(ImgView, int, int, int, uint32_t, uint32_t*, size_t, int, int, int, int);
-template __global__ void k_adaptive_threshold_t<15>(ImgView, int, int, int, uint32_t, uint32_t*, size_t, int, int, int, int);
-
-// The threshold kernel of the batched path (round 6): the same horizontal pass, then
 //   vertical:   TWO row strips per lane on packed 16-bit lanes.  A wave owns rows 8 w .. 8 w + 7 (low halves) and 8 w + 32 .. 8 w + 39
 //               (high halves) of the tile; the box sums lie in LDS as (row q, row q + 32) pairs, so one ds_read_b32 feeds both strips,
-//               the sliding window is one v_pk_add_u16 + one v_pk_sub_u16 for 128 pixels, and "mean >= v + C", i.e.
-//               s + n/2 >= n (v + C) with n = WIN^2, is v_pk_mad_u16 (n v + K, K = n C - n/2 >= 0: the host checks the range) and one
+//               the sliding window is one v_pk_add_u16 + one v_pk_sub_u16 for 128 pixels.  mean = (s + n / 2) / n with n = WIN^2 (n is
+//               odd, so the rounding has no ties and equals rint(s * (1.0 / n)): tests/test_detector_plan_cpu.py), and "mean >= v + C",
+//               i.e. s + n/2 >= n (v + C), is v_pk_mad_u16 (n v + K, K = n C - n/2 >= 0: the host checks the range) and one
 //               saturating v_pk_sub_u16 whose halves are zero where the pixel is set.  The two ballots of a row go into lanes k and 8 + k of
-//               two registers (v_writelane) and the 16 rows of a wave leave in ONE store instruction -- the per-row store of
-//               k_adaptive_threshold_t (address arithmetic on every lane for a store two lanes execute) was half of its vertical pass.
-//               12 -> ~5.5 instructions per 64 pixels and row.
+//               two registers (v_writelane) and the 16 rows of a wave leave in ONE store instruction (a store per row is address
+//               arithmetic on every lane for a store two lanes execute).  ~5.5 instructions per 64 pixels and row.
 //   pyramid:    the detector's /2 pyramid (buildPyramid, markerdetector_impl.cpp:1299-1488; exact halving = the 2 x 2 mean) from the
 //               tile's own pixels, which are in LDS anyway: a 64 x 64 tile holds its 32 x 32, 16 x 16, 8 x 8 and 4 x 4 descendants whole.
 //               Four launches (k_half_area4) and a second read of every frame less on the detector's chain.
+typedef uint32_t u32_unaligned_t __attribute__((aligned(1)));
 typedef unsigned short th_u16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t th_quad(uint32_t r0, uint32_t r1) // two outputs (16-bit lanes) from one dword of each source row
 {
@@ -262,12 +156,14 @@ __global__ __launch_bounds__(256) void k_threshold_pyr(ImgView src, int W, int H
 #pragma unroll
         for (int j = 0; j < NDW; j++) w[k][j] = 0;
         if (rr < ROWS) {
-            const uint8_t* row = img + (uint32_t)__mul24(min(max(ty0 + rr - R, 0), H - 1), src.pitch); // BORDER_REPLICATE
+            const uint8_t* row = img + (uint32_t)__mul24(min(max(ty0 + rr - R, 0), H - 1), src.pitch); // BORDER_REPLICATE (24-bit multiply: a 32-bit offset off the uniform base instead of a 64-bit v_mad_i64_i32)
             if (x >= LEAD && x - LEAD + 4 * NDW <= W) {
 #pragma unroll
                 for (int j = 0; j < NDW; j++) w[k][j] = reinterpret_cast<const u32_unaligned_t*>(row + x - LEAD)[j];
             } else {
-                // the window crosses the left or right image border: see k_adaptive_threshold_t
+                // the window crosses the left or right image border (BORDER_REPLICATE).  Its dwords start at multiples of four, so
+                // a dword is either inside (loaded), left of the image (pixel 0 four times) or at / beyond the right edge: its
+                // pixels then come out of the row's last four with one v_perm (n_in = 3, 2, 1, <= 0 pixels of it are inside)
                 const uint32_t first = reinterpret_cast<const u32_unaligned_t*>(row)[0];
                 const uint32_t last = reinterpret_cast<const u32_unaligned_t*>(row + W - 4)[0];
 #pragma unroll

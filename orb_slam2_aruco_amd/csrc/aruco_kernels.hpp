@@ -4,13 +4,12 @@
 #include <stdint.h>
 
 #include "aruco_trace.hpp"
+#include "detector_plan.hpp" // ArLevel, ThrStrip, the capacities and LDS sizes the host-only plan works with
 #include "orb_kernels.hpp" // ImgView, k_resize_level
 
 namespace orbfe {
 
 #define AR_MAX_RECTS 256
-#define AR_MAX_KEPT 1024
-#define AR_MAX_KEPT_BIG 4096 // the single-walker kernel with the bit image in HBM: LDS has room for this many kept borders
 
 // a border that passed the length gate and the 4-gon/convexity test
 struct ArKept {
@@ -22,21 +21,10 @@ struct ArRect {
     float c[4][2];
     int off, len;
 };
-// one level of the detector's /2 pyramid
-struct ArLevel {
-    int w, h, pitch;
-    long long off; // byte offset inside a frame's pyramid block (level 0 is the input image)
-};
 
 template <int TH_MAXR>
 __global__ void k_adaptive_threshold(ImgView src, int W, int H, int win, int C, double scale, uint32_t* bits,
                                      size_t bits_fstride, int wpr);
-template <int WIN>
-__global__ void k_adaptive_threshold_t(ImgView src, int W, int H, int C, uint32_t magic, uint32_t* bits,
-                                       size_t bits_fstride, int wpr, int ntx, int ntiles, int total);
-// k_threshold_mfma: a 32-column strip per wave; c0 / c1 / c2 = byte columns of the three 16-byte pieces of a row it loads, tab = index
-// (units of 64 uint4) of the strip's four pass-1 matrices (aruco_detector.hip: build_threshold_tables)
-struct ThrStrip { int x0, c0, c1, c2, tab; };
 __global__ void k_threshold_mfma(ImgView src, int W, int H, int rb, int kinit, const ThrStrip* strips, const uint4* tabs, const uint4* tab2,
                                  uint32_t* bits, size_t bits_fstride, int wpr, int nstrips, int nx, int total, int two_centre);
 // threshold + the /2 pyramid levels a 64 x 64 tile holds whole (levels 1 .. n <= 4 of the detector's pyramid), one launch
@@ -49,20 +37,7 @@ __global__ void k_threshold_pyr(ImgView src, int W, int H, uint32_t kk, uint32_t
 #ifndef ORBFE_CAND_FILTER
 #define ORBFE_CAND_FILTER 1
 #endif
-// the speck passes ("FEWER WALKS" (2)): bit image -> the bit image the contour kernels are handed
-#define SPK_THREADS 256
-#define SPK_ROWS 48   // output rows per workgroup (+ ORBFE_SPECK_REACH above and below)
-static inline size_t speck_lds_bytes(int cols) { return (size_t)4 * (SPK_ROWS + 2 * ORBFE_SPECK_REACH) * (((cols + 2 + 31) >> 5) + 1) * 4; }
 __global__ void k_speck_clean(const uint32_t* bits, size_t bits_fstride, int wpr_g, int W, int H, uint32_t* out);
-// Per-frame scratch of the relay kernels behind the long-walk queue words of d_candq: [start-candidate queue | rim masks and anchors
-// of the two speck passes when they run inside the kernel (speck_pass_frame): 3 arrays a pass, each (padded rows + 2 * (H + 1)) rows]
-__host__ __device__ inline int relay_queue_words(int W, int H) { return (W * H) / 16 + 64; }
-__host__ __device__ inline int speck_frame_rows(int H, int HH) { return H + 2 + 2 * (HH + 1); }
-__host__ __device__ inline size_t speck_frame_scratch_words(int W, int H)
-{
-    const size_t pw = (size_t)((W + 2 + 31) >> 5);
-    return 3 * pw * (size_t)speck_frame_rows(H, ORBFE_SPECK_H1) + 3 * pw * (size_t)speck_frame_rows(H, ORBFE_SPECK_H2);
-}
 __global__ void k_half_area(ImgView src, ImgView dst, int dw, int dh);
 __global__ void k_half_area4(ImgView src, ImgView dst, int dw4, int dh);
 // levels 1 .. NF of the /2 pyramid from the source in one launch (NF = 4: 16 x 16 source blocks, 16-byte aligned rows; NF = 3: 8 x 8, 8-byte)
@@ -146,11 +121,7 @@ __global__ void k_upsample_corners(ImgView src0, ImgView pyr, const ArLevel* lev
 
 #define DC_PATCH_BYTES 1232   // = DC_PXCAP of aruco_kernels.hip: bytes per kept patch
 
-#define CT_THREADS 256          // threads that run the whole kernel
-#define CT_WAVES (CT_THREADS / 64)
 #define CT_PROBE_THREADS 1024   // threads at launch: the extra ones help with the (throughput-bound) probe phase, then exit
-#define AP_STACK 64
-#define AP_OUT 64
 #define CT_PROBE 24 // steps a border start is followed before it is queued as a long walk (< the 70-point gate)
 
 #ifndef DC_WAVES
@@ -178,7 +149,6 @@ __global__ void k_upsample_corners(ImgView src0, ImgView pyr, const ArLevel* lev
 #define RL_FLAG_TABLE 32        // (kernel-internal) markers did not fit: coarsen the grid
 #define RL_FLAG_BUG 64          // an invariant of the relay formulation failed: redone by k_contours_t as well
 #define RL_FALLBACK_FLAGS (RL_FLAG_TABLE | RL_FLAG_BUG)
-#define RL_KCAP AR_MAX_KEPT      // kept borders per frame (k_contours_relay + k_contours_tail)
 #ifndef RL_STEPS_PER_ITER
 #define RL_STEPS_PER_ITER 2      // walk steps between two looks at the work queue
 #endif
@@ -242,32 +212,8 @@ __global__ void k_ct_lists(const uint32_t* seg, size_t seg_fstride, int segcap, 
 __global__ void k_ct_points(const uint4* itemsA, const uint2* itemsB, int ipf, const int32_t* nitems, const uint32_t* codes,
                             int segcap, uint32_t* pool, size_t pool_fstride);
 
-// LDS of k_contours_relay: region R (bit image | list arrays) followed by the marker keys
-__host__ __device__ inline size_t relay_region_bytes(int lds_bits_words, int kcap, int tbits)
-{
-    const size_t bits = ((size_t)lds_bits_words * 4 + 15) & ~(size_t)15;
-    const size_t lists = (size_t)kcap * 12 + ((size_t)8 << tbits);
-    size_t r = bits > lists ? bits : lists;
-    return (r + 15) & ~(size_t)15;
-}
-inline size_t relay_lds_bytes(int lds_bits_words, int kcap, int tbits)
-{
-    return relay_region_bytes(lds_bits_words, kcap, tbits) + ((size_t)4 << tbits);
-}
-
 // LDS of k_tail_prep (keys, pool offsets, lengths per kept border) and of k_tail_approx (per wave: approx output + stack + `pts` points)
 inline size_t tail_prep_lds_bytes(int kcap) { return (size_t)kcap * (8 + 4) + 16; }
 inline size_t tail_approx_lds_bytes(int pts) { return (size_t)4 * ((AP_OUT + AP_STACK) * 8 + (size_t)pts * 4) + 16; }
-
-inline size_t contours_lds_bytes(int lds_bits_words, int kept_cap)
-{
-    size_t b = ((size_t)lds_bits_words * 4 + 15) & ~(size_t)15;
-    b += (size_t)kept_cap * 8;      // keys
-    b += (size_t)kept_cap * 4 * 4;  // arena offsets, len, off, rect flag (the last three double as the long-walk queue)
-    b += (size_t)CT_WAVES * AP_OUT * 8;
-    b += (size_t)CT_WAVES * AP_STACK * 8;
-    b += (size_t)kept_cap * 2; // length ranking
-    return b + 16;
-}
 
 } // namespace orbfe

@@ -1,0 +1,245 @@
+// detector_plan.hpp -- what the ArUco detector's kernels are told about an input size: the adaptive-threshold window, the bit image,
+// the /2 pyramid, the per-frame block sizes, which contour kernels fit LDS, the matrix-core threshold tables.  Pure host arithmetic,
+// no HIP: csrc/aruco_detector.hip computes a geometry per input size and swaps it into the handle once its tables are on the device,
+// tests/test_detector_plan_cpu.py compiles this header with g++ and checks it against the oracle.  A geometry is a value:
+// plan_detector() returns either a complete one or an error (err, msg).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <cstdarg>
+#include <cstdio>
+#include <vector>
+
+#include "../../include/orbfe.h"
+#include "aruco_trace.hpp"
+
+namespace orbfe {
+
+#define AR_MAX_KEPT 1024
+#define AR_MAX_KEPT_BIG 4096 // the single-walker kernel with the bit image in HBM: LDS has room for this many kept borders
+#define RL_KCAP AR_MAX_KEPT  // kept borders per frame (k_contours_relay + k_contours_tail)
+
+// one level of the detector's /2 pyramid
+struct ArLevel {
+    int w, h, pitch;
+    long long off; // byte offset inside a frame's pyramid block (level 0 is the input image)
+};
+
+// the speck passes ("FEWER WALKS" (2)): bit image -> the bit image the contour kernels are handed
+#define SPK_THREADS 256
+#define SPK_ROWS 48   // output rows per workgroup (+ ORBFE_SPECK_REACH above and below)
+inline size_t speck_lds_bytes(int cols) { return (size_t)4 * (SPK_ROWS + 2 * ORBFE_SPECK_REACH) * (((cols + 2 + 31) >> 5) + 1) * 4; }
+// Per-frame scratch of the relay kernels behind the long-walk queue words of d_candq: [start-candidate queue | rim masks and anchors
+// of the two speck passes when they run inside the kernel (speck_pass_frame): 3 arrays a pass, each (padded rows + 2 * (H + 1)) rows]
+ORBFE_HD int relay_queue_words(int W, int H) { return (W * H) / 16 + 64; }
+ORBFE_HD int speck_frame_rows(int H, int HH) { return H + 2 + 2 * (HH + 1); }
+ORBFE_HD size_t speck_frame_scratch_words(int W, int H)
+{
+    const size_t pw = (size_t)((W + 2 + 31) >> 5);
+    return 3 * pw * (size_t)speck_frame_rows(H, ORBFE_SPECK_H1) + 3 * pw * (size_t)speck_frame_rows(H, ORBFE_SPECK_H2);
+}
+
+#define CT_THREADS 256          // threads that run the whole kernel
+#define CT_WAVES (CT_THREADS / 64)
+#define AP_STACK 64
+#define AP_OUT 64
+
+// LDS of k_contours_relay: region R (bit image | list arrays) followed by the marker keys
+ORBFE_HD size_t relay_region_bytes(int lds_bits_words, int kcap, int tbits)
+{
+    const size_t bits = ((size_t)lds_bits_words * 4 + 15) & ~(size_t)15;
+    const size_t lists = (size_t)kcap * 12 + ((size_t)8 << tbits);
+    size_t r = bits > lists ? bits : lists;
+    return (r + 15) & ~(size_t)15;
+}
+inline size_t relay_lds_bytes(int lds_bits_words, int kcap, int tbits)
+{
+    return relay_region_bytes(lds_bits_words, kcap, tbits) + ((size_t)4 << tbits);
+}
+
+inline size_t contours_lds_bytes(int lds_bits_words, int kept_cap)
+{
+    size_t b = ((size_t)lds_bits_words * 4 + 15) & ~(size_t)15;
+    b += (size_t)kept_cap * 8;      // keys
+    b += (size_t)kept_cap * 4 * 4;  // arena offsets, len, off, rect flag (the last three double as the long-walk queue)
+    b += (size_t)CT_WAVES * AP_OUT * 8;
+    b += (size_t)CT_WAVES * AP_STACK * 8;
+    b += (size_t)kept_cap * 2; // length ranking
+    return b + 16;
+}
+
+#define AR_MAX_WIN 31   // windows up to 31 (k_adaptive_threshold<15>): frames up to 4095 pixels wide
+
+struct DetectorGeometry {
+    int err = ORBFE_OK;               // ORBFE_OK, or why this input is refused (then nothing else below is meaningful)
+    char msg[256] = "";
+    // what it was planned for: the image that is thresholded and traced, the frame the /2 pyramid starts from (the working image is
+    // smaller when minSize > 0).  rows == 0: no geometry.
+    int rows = 0, cols = 0, pyr_rows = 0, pyr_cols = 0;
+    // Adaptive-threshold window.  The threshold kernels compare box sums as integers, mean = (s + n / 2) / n with n = win^2: n is odd,
+    // so the rounding has no ties and equals the reference's rint(s * (1.0 / n)) for every box sum of every window admitted here
+    // (tests/test_detector_plan_cpu.py runs through them all).
+    int win = 0;
+    int wpr = 0;                      // words per row of the bit image
+    size_t bits_fu32 = 0;
+    int npyr = 0;
+    std::vector<ArLevel> levels;
+    std::vector<int> lvl_exact;       // 1 if level p is an exact 2x reduction of level p-1
+    size_t pyr_fbytes = 0, candq_fu32 = 0, pool_fu32 = 0, gpad_fu32 = 0;
+    int lds_bits_words = 0;           // the padded bit image where it fits LDS next to k_contours_t's arrays (0: it does not)
+    int relay_tbits = 0;              // hash-table size of the relay kernels (0: they cannot run at this image size)
+    int relay_kshift = 5;             // their initial grid spacing (log2)
+    bool relay_global = false;        // k_contours_relay8g: the bit image stays in HBM (it does not fit LDS)
+    int relay_kcap = RL_KCAP;         // kept borders per frame the relay kernels and their tail hold
+    int ct_segcap = 0, ct_hbits = 0, ct_lcap = 0, ct_items_per_frame = 0;   // tiled path
+    bool matches(int rows_, int cols_, int prows, int pcols) const { return rows && rows_ == rows && cols_ == cols && prows == pyr_rows && pcols == pyr_cols; }
+};
+
+inline int plan_fail(DetectorGeometry& g, int code, const char* fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g.msg, sizeof(g.msg), fmt, ap);
+    va_end(ap);
+    return g.err = code;
+}
+
+// rows x cols: the image that is thresholded and traced; prows x pcols: the frame the /2 pyramid is built from; S: the dictionary's
+// warp size; lcap_override > 0: list elements k_ct_lists keeps in LDS (a measurement switch); rl_static: static LDS of the relay
+// kernels (step table, counters) as the runtime reports it -- a constant here once fell behind the kernels and frames whose tables
+// only just fitted (1582 x 619: 156,976 B dynamic) failed at launch
+inline DetectorGeometry plan_detector(int rows, int cols, int prows, int pcols, int S, bool specks_inkernel, int lcap_override, size_t rl_static)
+{
+    DetectorGeometry g;
+    if (cols > 8000 || rows > 8000) { plan_fail(g, ORBFE_ERR_INVALID, "image larger than 8000 px"); return g; }
+    int w = std::max(3, int(15 * float(cols) / 1920.)); // :3765-3809
+    if (w % 2 == 0) w++;
+    if (w > AR_MAX_WIN) { plan_fail(g, ORBFE_ERR_INVALID, "threshold window %d too large", w); return g; }
+    g.rows = rows; g.cols = cols; g.pyr_rows = prows; g.pyr_cols = pcols;
+    g.win = w;
+    g.wpr = (cols + 31) / 32;
+    g.bits_fu32 = (size_t)g.wpr * rows;
+    // buildPyramid (:1299-1488): halve while width > 2 * S; inexact levels go through k_resize_level
+    int lw = pcols, lh = prows;
+    size_t off = 0;
+    g.levels.push_back(ArLevel{lw, lh, 0, 0});
+    g.lvl_exact.push_back(1);
+    int n = 1, tw = pcols;
+    while (tw > 2 * S) { tw /= 2; n++; }
+    for (int p = 1; p < n; p++) {
+        const int sw = lw, sh = lh;
+        lw /= 2; lh /= 2;
+        if (lw < 1 || lh < 1) break;
+        const ArLevel L{lw, lh, (lw + 63) / 64 * 64, (long long)off};
+        off += (size_t)L.pitch * lh;
+        g.levels.push_back(L);
+        g.lvl_exact.push_back(sw == 2 * lw && sh == 2 * lh);
+    }
+    g.npyr = (int)g.levels.size();
+    g.pyr_fbytes = off + 64;
+    // HBM overflow of the single-walker kernel's long-walk queue / the relay kernels' start-candidate queue, + their speck scratch
+    // (the speck scratch -- four times the queue at 640 x 480 -- only where the in-kernel passes are switched on)
+    g.candq_fu32 = ((size_t)relay_queue_words(cols, rows) + (specks_inkernel ? speck_frame_scratch_words(cols, rows) : 0) + 63) / 64 * 64;
+    g.pool_fu32 = (size_t)CT_THREADS * std::max(4096, rows * cols / 48); // one private arena per lane of k_contours
+    const int pw = (cols + 2 + 31) / 32;
+    const size_t padded_words = (size_t)pw * (rows + 2) + 2; // + spare words for ring8()
+    // the padded bit image goes to LDS when it fits next to the other arrays (160 KiB per workgroup)
+    g.lds_bits_words = (contours_lds_bytes((int)padded_words, AR_MAX_KEPT) + 256 <= 160 * 1024) ? (int)padded_words : 0;
+    g.gpad_fu32 = padded_words; // always there: big_mode uses the HBM variant at any size
+    // k_contours_relay needs the bit image AND its marker table in LDS; otherwise k_contours_t does all frames.
+    // 4096 marker slots on a 32-pixel grid for ordinary frames (a 2048-slot table on a 64-pixel grid would let two workgroups
+    // share a CU, but its longer segments cost more than the sharing wins: 857 vs 726 us).  Large frames have more grid
+    // crossings than 4096 slots hold and would be coarsened to a 128-pixel grid, which doubles the kernel's time (640 x 480:
+    // 463 / 592 / 949 us at 32 / 64 / 128 pixels): they get 8192 slots (k_contours_relay8) when the LDS allows.
+    const bool large = (size_t)rows * cols > (size_t)640 * 480 * 3 / 2;
+    if (g.lds_bits_words && large && relay_lds_bytes(g.lds_bits_words, RL_KCAP, 13) + rl_static <= 160 * 1024) g.relay_tbits = 13;
+    else if (g.lds_bits_words && relay_lds_bytes(g.lds_bits_words, RL_KCAP, 12) + rl_static <= 160 * 1024) g.relay_tbits = 12;
+    // frames whose bit image does not fit LDS: the relay formulation with the bit image in HBM (k_contours_relay8g)
+    // (and room for as many kept borders as the single-walker kernel's big-frame mode: busy 1920 x 1080 frames have > 1024)
+    // (also frames whose bit image fits LDS for the single-walker kernel but not next to a marker table)
+    // (round 2: the HBM-image formulation also for frames that fit LDS -- 45 KB workgroups instead of 151 KB -- was slower, 5.50 against 4.62 ms at C3)
+    g.relay_global = !g.relay_tbits && relay_lds_bytes(0, AR_MAX_KEPT_BIG, 13) + rl_static <= 160 * 1024;
+    if (g.relay_global) { g.relay_tbits = 13; g.relay_kcap = AR_MAX_KEPT_BIG; }
+    // tiled path: segments per frame the lists hold (a 640 x 480 frame of the synthetic streams has ~2000, salt noise ~15 k; ids
+    // are 16 bits), hash slots (twice that), segments whose list arrays k_ct_lists keeps in LDS (more: the same arrays in HBM)
+    int sc = 4096;
+    while (sc < rows * cols / 32 && sc < 65536) sc <<= 1;
+    g.ct_segcap = std::min(sc, 65535);
+    g.ct_hbits = 1;
+    while ((1 << g.ct_hbits) < 2 * sc) g.ct_hbits++;
+    g.ct_lcap = std::min(g.ct_segcap, lcap_override > 0 ? lcap_override : large ? 16384 : 4096);   // list elements k_ct_lists keeps in LDS (8 B each)
+    g.ct_items_per_frame = std::max(4096, g.ct_segcap / 4);
+    return g;
+}
+
+// k_threshold_mfma: a 32-column strip per wave; c0 / c1 / c2 = byte columns of the three 16-byte pieces of a row it loads, tab = index
+// (units of 64 uint4) of the strip's four pass-1 matrices
+struct ThrStrip { int x0, c0, c1, c2, tab; };
+
+// Tables of k_threshold_mfma: per 32-column strip the pass-1 matrices (box K blocks a / b, selection a / b) in the B-operand layout of
+// v_mfma_i32_32x32x32_i8, BORDER_REPLICATE folded in; the pass-2 matrices (box over the previous / this block, centre x -WIN^2).
+struct ThresholdTables {
+    int cols = 0, win = 0;   // what they were built for (0: none)
+    bool ok = false;         // false: the kernel does not apply (windows above 15, frames narrower than 48 pixels); the rest is void
+    int rb = 0;              // rows / columns of halo in front of a block: 4 for radii up to 3, else 8
+    std::vector<ThrStrip> strips;
+    std::vector<uint8_t> tabs, tab2;
+};
+
+inline ThresholdTables plan_threshold_tables(int cols, int win)
+{
+    ThresholdTables t;
+    t.cols = cols; t.win = win;
+    const int R = win / 2, n2 = win * win, W = cols, rb = R <= 3 ? 4 : 8;
+    if (R > 7 || W < 48) return t;
+    t.tabs.reserve((size_t)(W + 31) / 32 * 4096);
+    for (int X = 0; X < W; X += 32) {
+        ThrStrip S{};
+        S.x0 = X; S.tab = (int)(t.tabs.size() / 1024);
+        auto cl = [&](int c) { return std::min(std::max(c, 0), W - 16); };
+        S.c0 = cl(X - rb); S.c1 = cl(X - rb + 16); S.c2 = cl(X - rb + 32);
+        const int cs[3] = {S.c0, S.c1, S.c2};
+        // the piece that supplies input column x: the first that holds it (-1: none)
+        auto owner = [&](int x) {
+            for (int pz = 0; pz < 3; pz++)
+                if (x >= cs[pz] && x < cs[pz] + 16) return pz;
+            return -1;
+        };
+        const size_t base = t.tabs.size();
+        t.tabs.resize(base + 4096, 0);
+        // matrices a hold pieces 0 (lanes 0 .. 31) and 1 (lanes 32 .. 63), matrices b piece 2 (lanes 0 .. 31); lane = output column
+        auto entry = [&](int m, int n, int piece, int x) -> uint8_t& {
+            return t.tabs[base + (size_t)(m + (piece == 2)) * 1024 + (size_t)(n + 32 * (piece == 1)) * 16 + (x - cs[piece])];
+        };
+        for (int n = 0; n < 32 && X + n < W; n++) {
+            for (int u = -R; u <= R; u++) {   // the taps of output column X + n, folded by BORDER_REPLICATE
+                const int x = std::min(std::max(X + n + u, 0), W - 1), piece = owner(x);
+                if (piece < 0) return t;      // an input column the strip's windows reach comes with none of the three pieces
+                entry(0, n, piece, x) += 1;
+            }
+            entry(2, n, owner(X + n), X + n) = 1;
+        }
+        t.strips.push_back(S);
+    }
+    t.tab2.assign(6144, 0);
+    const int cw1 = n2 <= 127 ? n2 : 113, cw2 = n2 - cw1;   // the centre's weight -n2 in one signed byte, or in two
+    for (int m = 0; m < 6; m++)   // box over the previous block, over this block, centre in the previous block, in this block (x 2)
+        for (int lane = 0; lane < 64; lane++) {
+            const int n = lane & 31, half = lane >> 5;
+            for (int i = 0; i < 16; i++) {
+                const int q = 4 * half + (i & 3) + 8 * (i >> 2);
+                const int d = ((m & 1) ? 32 : 0) + q - rb - n;   // the row's offset from the output row
+                int v = 0;
+                if (m < 2) v = (d >= -R && d <= R) ? 1 : 0;
+                else v = d == 0 ? -(m < 4 ? cw1 : cw2) : 0;
+                t.tab2[(size_t)m * 1024 + (size_t)lane * 16 + i] = (uint8_t)(int8_t)v;
+            }
+        }
+    t.rb = rb;
+    t.ok = true;
+    return t;
+}
+
+} // namespace orbfe

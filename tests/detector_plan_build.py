@@ -1,0 +1,62 @@
+"""Builds tests/detector_plan_driver.cpp (csrc/detector_plan.hpp behind a C ABI) with g++ and loads it with ctypes (test
+infrastructure, in the manner of tests/extractor_plan_build.py).  One build per process, in a temporary directory."""
+import ctypes as C
+import os
+import subprocess
+import tempfile
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+_lib = None
+
+SCALAR_FIELDS = ("win", "wpr", "npyr", "lds_bits_words", "relay_tbits", "relay_kshift", "relay_global", "relay_kcap", "ct_segcap", "ct_hbits",
+                 "ct_lcap", "ct_items_per_frame")
+SIZE_FIELDS = ("bits_fu32", "pyr_fbytes", "candq_fu32", "pool_fu32", "gpad_fu32")
+MAXLEVELS = 16
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        out = tempfile.mkdtemp(prefix="detector_plan_")
+        so = os.path.join(out, "detector_plan_driver.so")
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Werror",
+                               os.path.join(HERE, "detector_plan_driver.cpp"), "-o", so])
+        L = C.CDLL(so)
+        vp, i32, i64 = C.c_void_p, C.c_int, C.c_longlong
+        L.dplan_make.argtypes = [i32, i32, i32, i32, i32, i32, i32, i64, vp, vp, vp, i32, vp, i32]
+        L.dplan_threshold_sweep.argtypes = [i32, i32, i32, vp]
+        _lib = L
+    return _lib
+
+
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def make(rows, cols, prows=None, pcols=None, S=35, specks_inkernel=0, lcap_override=0, rl_static=4352):
+    """(error code, message, dict of scalars and sizes, levels as rows of (w, h, pitch, exact)) of the geometry.  S = 35: the ARUCO
+    dictionary's warp size; rl_static: static LDS of the relay kernels, which the library asks of the runtime (4 KiB + 256 here)."""
+    sc = np.zeros(len(SCALAR_FIELDS), np.int32); sz = np.zeros(len(SIZE_FIELDS), np.int64); lv = np.zeros((MAXLEVELS, 4), np.int32)
+    msg = C.create_string_buffer(256)
+    rc = lib().dplan_make(rows, cols, rows if prows is None else prows, cols if pcols is None else pcols, S, specks_inkernel, lcap_override,
+                          rl_static, _p(sc), _p(sz), _p(lv), MAXLEVELS, msg, 256)
+    d = {f: int(sc[i]) for i, f in enumerate(SCALAR_FIELDS)}
+    d.update({f: int(sz[i]) for i, f in enumerate(SIZE_FIELDS)})
+    return rc, msg.value.decode(), d, lv[:max(d["npyr"], 0)]
+
+
+def mean_mismatches(n):
+    """Box sums 0 .. 255 n whose integer mean (plain and multiply-shift) is not rint(s * (1.0 / n))."""
+    return lib().dplan_mean_mismatches(n)
+
+
+def threshold_sweep(w_first, w_last, win):
+    """(number of widths whose matrix-core threshold tables are refused or wrong, the first of them)."""
+    bad = np.zeros(1, np.int32)
+    return lib().dplan_threshold_sweep(w_first, w_last, win, _p(bad)), int(bad[0])
+
+
+def threshold_refused(cols, win):
+    return bool(lib().dplan_threshold_refused(cols, win))

@@ -1,0 +1,109 @@
+// C entry points over csrc/detector_plan.hpp for tests/test_detector_plan_cpu.py (built with g++ by tests/detector_plan_build.py:
+// the header has no HIP in it).  Test infrastructure only.
+#include <cmath>
+#include <cstring>
+
+#include "../orb_slam2_aruco_amd/csrc/detector_plan.hpp"
+
+using namespace orbfe;
+
+extern "C" {
+
+// The geometry of a rows x cols working image whose pyramid starts from prows x pcols.  scalars: win, wpr, npyr, lds_bits_words,
+// relay_tbits, relay_kshift, relay_global, relay_kcap, ct_segcap, ct_hbits, ct_lcap, ct_items_per_frame; sizes: bits_fu32, pyr_fbytes,
+// candq_fu32, pool_fu32, gpad_fu32; levels: (w, h, pitch, exact) per level, at most maxlevels.  Returns the plan's error code; msg
+// receives its message.
+int dplan_make(int rows, int cols, int prows, int pcols, int S, int specks_inkernel, int lcap_override, long long rl_static, int* scalars,
+               long long* sizes, int* levels, int maxlevels, char* msg, int msgcap)
+{
+    const DetectorGeometry g = plan_detector(rows, cols, prows, pcols, S, specks_inkernel != 0, lcap_override, (size_t)rl_static);
+    snprintf(msg, (size_t)msgcap, "%s", g.msg);
+    if (g.err) return g.err;
+    const int s[12] = {g.win, g.wpr, g.npyr, g.lds_bits_words, g.relay_tbits, g.relay_kshift, g.relay_global, g.relay_kcap,
+                       g.ct_segcap, g.ct_hbits, g.ct_lcap, g.ct_items_per_frame};
+    memcpy(scalars, s, sizeof(s));
+    const long long z[5] = {(long long)g.bits_fu32, (long long)g.pyr_fbytes, (long long)g.candq_fu32, (long long)g.pool_fu32, (long long)g.gpad_fu32};
+    memcpy(sizes, z, sizeof(z));
+    if (g.npyr != (int)g.levels.size() || g.npyr != (int)g.lvl_exact.size() || g.npyr > maxlevels) return -100;
+    for (int l = 0; l < g.npyr; l++) {
+        const ArLevel& L = g.levels[(size_t)l];
+        // a level's rows lie inside the frame's pyramid block, behind the level before
+        if (l > 0 && (L.pitch < L.w || L.off < 0 || (size_t)L.off + (size_t)L.pitch * L.h > g.pyr_fbytes)) return -101;
+        if (l > 1 && L.off < g.levels[(size_t)l - 1].off + (long long)g.levels[(size_t)l - 1].pitch * g.levels[(size_t)l - 1].h) return -101;
+        const int v[4] = {L.w, L.h, L.pitch, g.lvl_exact[(size_t)l]};
+        memcpy(levels + 4 * l, v, sizeof(v));
+    }
+    return ORBFE_OK;
+}
+
+// The box mean of the threshold kernels for a window of n pixels: for how many box sums s = 0 .. 255 n the integer mean
+// (s + n / 2) / n, or its multiply-shift form (s + n / 2) * ceil(2^32 / n) >> 32, is not the reference's rint(s * (1.0 / n))
+int dplan_mean_mismatches(int n)
+{
+    const uint32_t magic = (uint32_t)((0x100000000ull + (unsigned)n - 1) / (unsigned)n);
+    int bad = 0;
+    for (int s = 0; s <= 255 * n; s++) {
+        const int want = (int)std::rint((double)s * (1.0 / n));
+        bad += (int)(((unsigned long long)(s + n / 2) * magic) >> 32) != want || (s + n / 2) / n != want;
+    }
+    return bad;
+}
+
+// plan_threshold_tables for every width w_first .. w_last at window `win`.  Returns how many widths the matrix-core tables refuse
+// or get wrong; first_bad = the first one.  Every accepted strip is checked against the box filter itself: the weights its pass-1 box
+// matrices hold for an output column, summed per input column, are the `win` taps folded by BORDER_REPLICATE, its selection
+// matrices pick the column itself, and every 16-byte piece it loads lies inside the row.  (A strip whose windows stay clear of both
+// image borders and whose pieces lie where the last such strip's lay, relative to its first column, is compared with that one's
+// matrices byte by byte instead: the same weights at the same places.)
+int dplan_threshold_sweep(int w_first, int w_last, int win, int* first_bad)
+{
+    int bad = 0;
+    const int R = win / 2;
+    for (int w = w_first; w <= w_last; w++) {
+        const ThresholdTables t = plan_threshold_tables(w, win);
+        bool ok = t.ok && t.cols == w && t.win == win && (int)t.strips.size() == (w + 31) / 32 && t.tabs.size() == t.strips.size() * 4096 &&
+                  t.tab2.size() == 6144 && t.rb == (R <= 3 ? 4 : 8);
+        const ThrStrip* ref = nullptr;   // the last interior strip that went through the full check
+        for (size_t k = 0; ok && k < t.strips.size(); k++) {
+            const ThrStrip& S = t.strips[k];
+            const int cs[3] = {S.c0, S.c1, S.c2};
+            ok = S.x0 == (int)k * 32 && S.tab == (int)k * 4;
+            const bool interior = S.x0 - R >= 0 && S.x0 + 31 + R <= w - 1;
+            if (ok && interior && ref && S.c0 - S.x0 == ref->c0 - ref->x0 && S.c1 - S.x0 == ref->c1 - ref->x0 && S.c2 - S.x0 == ref->c2 - ref->x0) {
+                ok = !memcmp(&t.tabs[(size_t)S.tab * 1024], &t.tabs[(size_t)ref->tab * 1024], 4096);
+                continue;
+            }
+            const int lo = std::min(S.c0, std::max(0, S.x0 - R)), span = 64;   // the input columns a strip may touch
+            for (int n = 0; ok && n < 32; n++) {
+                int8_t box[span] = {0}, sel[span] = {0}, wbox[span] = {0}, wsel[span] = {0};
+                for (int piece = 0; piece < 3; piece++)
+                    for (int i = 0; i < 16; i++) {
+                        const int lane = n + 32 * (piece == 1), ab = piece == 2, x = cs[piece] + i;
+                        const uint8_t* m = &t.tabs[(size_t)S.tab * 1024 + (size_t)ab * 1024 + (size_t)lane * 16 + i];
+                        ok = ok && cs[piece] >= 0 && cs[piece] + 16 <= w && x - lo >= 0 && x - lo < span;
+                        if (ok) { box[x - lo] += (int8_t)m[0]; sel[x - lo] += (int8_t)m[2048]; }
+                    }
+                // (matrix b's lanes 32 .. 63 have no piece: they stay zero)
+                for (int i = 0; ok && i < 16; i++)
+                    ok = !t.tabs[(size_t)S.tab * 1024 + 1024 + (size_t)(n + 32) * 16 + i] && !t.tabs[(size_t)S.tab * 1024 + 3072 + (size_t)(n + 32) * 16 + i];
+                if (S.x0 + n < w) {
+                    for (int u = -R; ok && u <= R; u++) {
+                        const int x = std::min(std::max(S.x0 + n + u, 0), w - 1);
+                        ok = x - lo >= 0 && x - lo < span;
+                        if (ok) wbox[x - lo] += 1;
+                    }
+                    if (ok) wsel[S.x0 + n - lo] = 1;
+                }
+                ok = ok && !memcmp(box, wbox, sizeof(box)) && !memcmp(sel, wsel, sizeof(sel));
+            }
+            if (ok && interior) ref = &S;
+        }
+        if (!ok && !bad++) *first_bad = w;
+    }
+    return bad;
+}
+
+// 1 if plan_threshold_tables(cols, win) says "not applicable"
+int dplan_threshold_refused(int cols, int win) { return plan_threshold_tables(cols, win).ok ? 0 : 1; }
+
+} // extern "C"

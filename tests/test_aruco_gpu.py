@@ -617,13 +617,14 @@ def test_dense_noise_frame_in_a_small_batch(orbfe, oracle):
 @pytest.mark.parametrize("rows,cols", [(480, 640), (427, 641), (720, 1280), (1080, 1920), (96, 130), (64, 64)])
 def test_threshold_kernels_agree_and_the_fused_pyramid_is_the_pyramid(orbfe, oracle, rows, cols):
     """k_threshold_pyr (round 6: packed 16-bit vertical pass, ballots through v_writelane, the /2 pyramid levels a 64 x 64 tile holds
-    written by the same launch) against k_adaptive_threshold_t + k_half_area4: the bit image, every pyramid level and the markers are
-    the same, on frame sizes with partial tiles, odd widths, inexact deeper levels and all four window sizes' neighbours."""
+    written by the same launch) against the generic k_adaptive_threshold + k_half_area4: the bit image, every pyramid level and the
+    markers are the same, on frame sizes with partial tiles, odd widths, inexact deeper levels and all four window sizes' neighbours.
+    (Frames above 2048 columns, which only the generic kernel takes, are test_frames_at_the_lds_boundary_of_the_relay_kernels'.)"""
     n = 2 if rows * cols <= 1280 * 720 else 1
     imgs = synth.stream(rows, cols, n, 99, "ARUCO", n_markers=3 if rows >= 200 else 0)
     a, b, c = orbfe.MarkerDetector("ARUCO"), orbfe.MarkerDetector("ARUCO"), orbfe.MarkerDetector("ARUCO")
     a.set_threshold_on_matrix_cores(False)                                        # a: k_threshold_pyr
-    b.set_threshold_on_matrix_cores(False); b.set_threshold_pyramid_kernel(False)  # b: k_adaptive_threshold_t + k_half_area4 a level
+    b.set_threshold_on_matrix_cores(False); b.set_threshold_pyramid_kernel(False)  # b: the generic k_adaptive_threshold + k_half_area4 a level
     b.set_half_pyramid_kernel(False)                                              #    (c's pyramid: k_half_pyr, the leading exact levels in one launch)
     c.set_threshold_on_matrix_cores(True)                                         # c: k_threshold_mfma (a batch's default; calls of fewer than 8 frames
     ma, mb, mc = a.detect_batch(imgs), b.detect_batch(imgs), c.detect_batch(imgs)  #    take k_threshold_pyr unless told otherwise) + k_half_area4
@@ -642,3 +643,24 @@ def test_threshold_kernels_agree_and_the_fused_pyramid_is_the_pyramid(orbfe, ora
             assert np.array_equal(la, lb) and np.array_equal(lc, lb), (rows, cols, f, lvl)
             lvl += 1
         assert np.array_equal(ma[f], mb[f])
+
+
+def test_refused_frame_leaves_the_detector_usable(orbfe):
+    """A frame size the detector refuses (8001 columns) changes nothing in the handle: the size it was working on, and another one,
+    are detected as by a handle that never saw the refused frame."""
+    det = orbfe.MarkerDetector("ARUCO")
+    a, _ = synth.scene(480, 640, 51, "ARUCO", 3)
+    c, _ = synth.scene(360, 636, 52, "ARUCO", 2)
+    wide = np.zeros((8, 8001), np.uint8)
+    got = {}
+    for name, img in (("a", a), ("wide", wide), ("a again", a), ("c", c), ("wide", wide), ("a at last", a)):
+        if img is wide:
+            with pytest.raises(orbfe.OrbfeError, match="larger than 8000"):
+                det.detect(img)
+            continue
+        got[name] = (det.detect(img), det.thresholded(0), det.pyramid_level(1, 0))
+    for name, img in (("a", a), ("a again", a), ("c", c), ("a at last", a)):
+        fresh = orbfe.MarkerDetector("ARUCO")
+        want = (fresh.detect(img), fresh.thresholded(0), fresh.pyramid_level(1, 0))
+        assert len(want[0]) > 0
+        assert all(np.array_equal(g, w) for g, w in zip(got[name], want)), name

@@ -39,14 +39,14 @@ def named(*bases):
 
 
 steps = min(s[k]["dispatches"] for k in named("k_fast_cells", "k_blur7", "k_blur7_mfma")) if "k_fast_cells" in s else \
-    min(s[k]["dispatches"] for k in named("k_adaptive_threshold_t", "k_adaptive_threshold", "k_threshold_pyr", "k_threshold_mfma"))
+    min(s[k]["dispatches"] for k in named("k_adaptive_threshold", "k_threshold_pyr", "k_threshold_mfma"))
 per_step = lambda k: s[k]["dispatches"] / steps if k in s else 0
 stage = {
     "resize": named("k_resize_tab"), "fast_cells": named("k_fast_cells"),
     "distribute": named("k_distribute_pyr", "k_distribute", "k_level_offsets"), "blur7": named("k_blur7", "k_blur7_mfma"),
     "orient_describe": named("k_orient_describe", "k_orient_describe2"), "knn2": named("k_knn2_mfma", "k_knn2_tiles", "k_knn2_merge"),
     "search_init": named("k_search_init", "k_sfi_grid", "k_sfi_rows", "k_sfi_accept"),
-    "aruco_threshold": named("k_adaptive_threshold_t", "k_adaptive_threshold", "k_threshold_pyr", "k_threshold_mfma"), "aruco_pyramid": named("k_half_area", "k_half_area4", "k_half_pyr", "k_resize_level"),
+    "aruco_threshold": named("k_adaptive_threshold", "k_threshold_pyr", "k_threshold_mfma"), "aruco_pyramid": named("k_half_area", "k_half_area4", "k_half_pyr", "k_resize_level"),
     "aruco_contours": [k for k in s if k.startswith("k_contours") or k.startswith("k_tail_") or k.startswith("k_ct_") or k.startswith("k_speck")],
     "aruco_decode": named("k_prefilter", "k_decode", "k_decode_warp", "k_decode_otsu", "k_decode_vote"), "aruco_finalize": named("k_finalize", "k_marker_poses"),
 }
