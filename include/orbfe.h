@@ -24,6 +24,7 @@
  *                       Initializer::InitializeUseAruco    src/Initializer.cc:124-189 (Tracking.cc:632)
  *   orbfe_pose_*        Optimizer::PoseOptimizationByAruco src/Optimizer.cc:522-770 (Tracking.cc:940, 1025, 1200, 1256, 1843)
  *                       Optimizer::PoseOptimization        src/Optimizer.cc:308-520, monocular
+ *   orbfe_sim3_*        ORB_SLAM2::Sim3Solver              src/Sim3Solver.cc (LoopClosing.cc:402-425, :489-600)
  *
  * Memory convention: functions without a suffix take HOST pointers (drop-in for
  * the reference's call sites, which hand over cv::Mat / std::vector storage) and
@@ -455,6 +456,79 @@ int orbfe_initialize_check_poses(const orbfe_keypoint* kps1, int n1, const orbfe
 int orbfe_initialize_inspect(const orbfe_keypoint* kps1, int n1, const orbfe_keypoint* kps2, int n2, const int32_t* matches12,
                              const float* K4, float sigma, int iterations, const int32_t* rand_words, orbfe_init_result* res,
                              int32_t* nmatches, int32_t* sets, float* T12, float* pn1, float* pn2, float* models, float* scores, int device);
+
+/* ------------------------------------------------------------ Sim3 RANSAC of loop closing -- */
+/* ORB_SLAM2::Sim3Solver (src/Sim3Solver.cc), the step of LoopClosing::ComputeSim3 between SearchByBoW(KF, KF) and SearchBySim3
+ * (src/LoopClosing.cc:402-425, :489-600): RANSAC over closed-form Horn alignments of 3 correspondences.
+ * Side k: kps = mvKeysUn (n entries), x3Dw[i] = world position of feature i's map point (n x 3), valid[i] != 0 = "feature i has a
+ * map point, it is not bad, and its index in this keyframe is i" (Sim3Solver.cc:66-79; valid1 and valid2 both NULL = all),
+ * Tcw = the keyframe's pose, 3 x 4 row-major, K4 = fx, fy, cx, cy.  match12[i1] = i2 or -1: what orbfe_search_by_bow returns.
+ * level_sigma2 = mvLevelSigma2 (nlevels <= 32 entries, read at the call).  probability, min_inliers, max_iterations:
+ * SetRansacParameters' arguments; the result's max_iterations is mRansacMaxIts after it.
+ *
+ * One call = one iterate(n_iterations, ...): the window [first_iteration, first_iteration + n_iterations) clipped to
+ * mRansacMaxIts, with best_inliers_in = mnBestInliers on entry.  The library holds no state between calls: the caller carries
+ * mnIterations (found + 1 after a success, else the end of the window) and mnBestInliers (best_inliers), and keeps the model it
+ * holds when best = -1.  first_iteration = 0, n_iterations = max_iterations, best_inliers_in = 0 is find().  rand_words:
+ * n_iterations x 3 values as rand() returned them, in draw order (RandomInt(0, size - 1) and the swap-with-back removal of
+ * :163-177 are applied here); words past the clipped window are not read.  Every hypothesis of the window is computed, the
+ * first that iterate() would return decides (the reference stops there; the words after it are the caller's to account for).
+ * inliers12 (n1 bytes) = vbInliers: all 0 unless found >= 0.
+ * The chi-square gates are (size_t)(9.210 * level_sigma2[octave]): the reference keeps them in a std::vector<size_t>.
+ *
+ * Where the reference is undefined:
+ *   - N < 3 with min_inliers <= N (RandomInt(0, -1)): as N < min_inliers -- no_more = 1, found = -1, no word read;
+ *   - a hypothesis whose quaternion has no imaginary part (0 / 0 at :280, a NaN model in OpenCV): zero inliers, a zero model,
+ *     and it is never `best`;
+ *   - a point with z = 0: its projection is inf / NaN, it is never an inlier;
+ *   - an iteration count that is not finite or below 1 (log of a negative number when N < min_inliers; min_inliers = 0): 1.
+ * ORBFE_ERR_INVALID: NULL pointers, a match12 entry outside [-1, n2), an octave outside [0, nlevels) on a kept correspondence,
+ * a negative word, probability outside (0, 1), min_inliers < 0, best_inliers_in < 0, iteration counts outside 1 .. 100000.
+ * Host pointers. */
+typedef struct orbfe_sim3_result {
+    int32_t n;                  /* N: correspondences the constructor kept */
+    int32_t max_iterations;     /* mRansacMaxIts after SetRansacParameters */
+    int32_t no_more;            /* bNoMore of this call */
+    int32_t found;              /* global iteration index (0-based) of the hypothesis iterate() returned, -1 = none in this window */
+    int32_t n_inliers;          /* nInliers (0 when found < 0) */
+    int32_t best, best_inliers; /* mnBestInliers and the iteration that holds it, after this window (best = -1: no hypothesis of
+                                   the window reached best_inliers_in; best_inliers = best_inliers_in then, the model fields 0) */
+    float   s12, R12[9], t12[3];/* of `best` (== found on success): GetEstimatedScale / Rotation / Translation */
+    float   T12[16];            /* mBestT12, row-major */
+    int32_t status;             /* ORBFE_OK; the batch call: ORBFE_ERR_INVALID for a problem it skipped (see there) */
+} orbfe_sim3_result;
+
+int orbfe_sim3_solve(const orbfe_keypoint* kps1, int n1, const float* x3Dw1, const uint8_t* valid1, const float* Tcw1, const float* K4_1,
+                     const orbfe_keypoint* kps2, int n2, const float* x3Dw2, const uint8_t* valid2, const float* Tcw2, const float* K4_2,
+                     const int32_t* match12, const float* level_sigma2, int nlevels, int fix_scale, double probability, int min_inliers,
+                     int max_iterations, int first_iteration, int n_iterations, int best_inliers_in, const int32_t* rand_words,
+                     orbfe_sim3_result* res, uint8_t* inliers12, int device);
+
+/* npairs whole runs (find()) on resident data, in the conventions of orbfe_search_by_bow_batch_device: per-frame blocks of
+ * `capacity` entries of d_kps, d_x3Dw (x 3), d_valid (may be NULL) and d_n, d_Tcw 12 floats a frame; problem p is frame
+ * d_pair1[p] (side 1) against frame d_pair2[p] (NULL index arrays: p and p + 1); d_match12 block p of `capacity` = that call's
+ * output (an entry outside [-1, d_n[pair2]) counts as no match), so the two chain on one stream without a download.  One K4 for
+ * both sides.  d_rand_words: npairs x max_iterations x 3 (a word outside 0 .. RAND_MAX is clamped to the ends of the index
+ * range).  Outputs: d_res[npairs]; d_inliers12 blocks of `capacity`, the first d_n[pair1] entries written.  A problem with an
+ * octave outside [0, nlevels) on a kept correspondence is skipped: its record has status ORBFE_ERR_INVALID and every other field
+ * 0, its inliers are not written.  Four launches whatever npairs is; asynchronous on `stream`, no host synchronisation; scratch
+ * per (thread, device, stream). */
+int orbfe_sim3_solve_batch_device(const orbfe_keypoint* d_kps, const int32_t* d_n, int capacity, const float* d_x3Dw, const uint8_t* d_valid,
+                                  const float* d_Tcw, const int32_t* d_pair1, const int32_t* d_pair2, int npairs, const int32_t* d_match12,
+                                  const float* K4, const float* level_sigma2, int nlevels, int fix_scale, double probability,
+                                  int min_inliers, int max_iterations, const int32_t* d_rand_words, orbfe_sim3_result* d_res,
+                                  uint8_t* d_inliers12, void* stream);
+
+/* DIAGNOSTIC / TEST INTERFACE, no stability promise: orbfe_sim3_solve with its intermediate results (the parity tests).
+ * *n = N; per kept correspondence (n1 entries of capacity, the first N written, the rest 0): indices1, X3Dc1 / X3Dc2 (x 3),
+ * P1im1 / P2im2 (x 2), maxError1 / maxError2; per iteration of the window (n_iterations entries; those the window does not
+ * run are 0): sets (x 3 correspondence indices), models (x 13: s12, R12 row-major, t12), counts (inliers of the hypothesis). */
+int orbfe_sim3_inspect(const orbfe_keypoint* kps1, int n1, const float* x3Dw1, const uint8_t* valid1, const float* Tcw1, const float* K4_1,
+                       const orbfe_keypoint* kps2, int n2, const float* x3Dw2, const uint8_t* valid2, const float* Tcw2, const float* K4_2,
+                       const int32_t* match12, const float* level_sigma2, int nlevels, int fix_scale, double probability, int min_inliers,
+                       int max_iterations, int first_iteration, int n_iterations, int best_inliers_in, const int32_t* rand_words,
+                       orbfe_sim3_result* res, uint8_t* inliers12, int32_t* n, int32_t* indices1, float* X3Dc1, float* X3Dc2, float* P1im1,
+                       float* P2im2, float* maxError1, float* maxError2, int32_t* sets, float* models, int32_t* counts, int device);
 
 /* ------------------------------------------------------------ motion-only pose optimization -- */
 /* Optimizer::PoseOptimizationByAruco(Frame*) (src/Optimizer.cc:522-770; every tracking path of Tracking.cc ends in it) and

@@ -59,6 +59,8 @@ SYMBOLS = [
     "orbfe_initialize", "orbfe_initialize_batch_device", "orbfe_initialize_check_poses", "orbfe_initialize_inspect",
     # motion-only pose optimization (csrc/pose_optimizer.hip)
     "orbfe_pose_optimization", "orbfe_pose_optimization_batch_device", "orbfe_pose_gather_device",
+    # the Sim3 RANSAC of loop closing (csrc/sim3_solver.hip)
+    "orbfe_sim3_solve", "orbfe_sim3_solve_batch_device", "orbfe_sim3_inspect",
 ]
 
 _lib = None
@@ -188,6 +190,12 @@ def load():
         L.orbfe_search_by_bow_batch_device.argtypes = [vp] * 8 + [i32, vp, vp, i32, i32, f32, i32, i32, f32, vp, vp, vp, vp]
         L.orbfe_marker_poses.argtypes = [vp, i32, f32, vp, vp, i32, vp, i32]
         L.orbfe_marker_poses_batch_device.argtypes = [vp, vp, i32, i32, f32, vp, vp, i32, vp, vp]
+    if hasattr(L, "orbfe_sim3_solve"):
+        side = [vp, i32, vp, vp, vp, vp]
+        common = side + side + [vp, vp, i32, i32, C.c_double, i32, i32, i32, i32, i32, vp, vp, vp]
+        L.orbfe_sim3_solve.argtypes = common + [i32]
+        L.orbfe_sim3_inspect.argtypes = common + [vp] * 11 + [i32]
+        L.orbfe_sim3_solve_batch_device.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, C.c_double, i32, i32, vp, vp, vp, vp]
     if hasattr(L, "orbfe_initialize"):
         L.orbfe_initialize.argtypes = [vp, i32, vp, i32, vp, vp, f32, i32, vp, vp, vp, vp, i32]
         L.orbfe_initialize_inspect.argtypes = [vp, i32, vp, i32, vp, vp, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
@@ -758,6 +766,124 @@ def initialize_batch_device(d_kps_ptr, d_n_ptr, capacity, npairs, d_matches12_pt
     _check(L, L.orbfe_initialize_batch_device(d_kps_ptr, d_n_ptr, int(capacity), int(npairs), d_matches12_ptr, _p(K4), float(sigma),
                                               int(iterations), d_rand_words_ptr, d_res_ptr, d_p3d_ptr, d_tri_ptr, stream),
            "orbfe_initialize_batch_device")
+
+
+# ------------------------------------------------------------------------------- Sim3 RANSAC (loop closing) ----
+SIM3_RESULT_DTYPE = np.dtype([("n", "<i4"), ("max_iterations", "<i4"), ("no_more", "<i4"), ("found", "<i4"), ("n_inliers", "<i4"),
+                              ("best", "<i4"), ("best_inliers", "<i4"), ("s12", "<f4"), ("R12", "<f4", 9), ("t12", "<f4", 3),
+                              ("T12", "<f4", 16), ("status", "<i4")])
+assert SIM3_RESULT_DTYPE.itemsize == 148
+
+
+def _sim3_side(kps, x3Dw, valid, Tcw, K):
+    k = np.ascontiguousarray(kps, KP_DTYPE)
+    x = np.ascontiguousarray(np.asarray(x3Dw, np.float32).reshape(-1, 3))
+    if len(x) != len(k):
+        raise ValueError("x3Dw has %d rows for %d keypoints" % (len(x), len(k)))
+    v = None if valid is None else np.ascontiguousarray(np.asarray(valid) != 0, np.uint8)
+    if v is not None and len(v) != len(k):
+        raise ValueError("valid has %d entries for %d keypoints" % (len(v), len(k)))
+    T = np.ascontiguousarray(np.asarray(Tcw, np.float32)[:3, :4]) if np.ndim(Tcw) == 2 else np.ascontiguousarray(Tcw, np.float32).reshape(3, 4)
+    K = np.asarray(K, np.float32)
+    K4 = np.ascontiguousarray([K[0, 0], K[1, 1], K[0, 2], K[1, 2]] if K.shape == (3, 3) else K.reshape(4), np.float32)
+    return k, x, v, T, K4
+
+
+class Sim3Solver:
+    """ORB_SLAM2::Sim3Solver (src/Sim3Solver.cc) on the GPU: constructed from the two keyframes' flat arrays and SearchByBoW's
+    match12, then iterate(n) / find() as the reference's.  side = (kps (mvKeysUn, KP_DTYPE), x3Dw (n x 3), valid (n, or None), Tcw
+    (3 x 4 or 4 x 4), K (3 x 3 or fx, fy, cx, cy)).  The object carries mnIterations, mnBestInliers and the best model; every
+    iterate() is one orbfe_sim3_solve call.  rand_words given to iterate() / find(): 3 per iteration of the window, as rand()
+    returned them; None draws them with draw_rand_words (the C library's rand(), which DUtils::Random::RandomInt uses)."""
+
+    def __init__(self, side1, side2, match12, level_sigma2, fix_scale=True, device=0):
+        self.k1, self.x1, self.v1, self.T1, self.K1 = _sim3_side(*side1)
+        self.k2, self.x2, self.v2, self.T2, self.K2 = _sim3_side(*side2)
+        if (self.v1 is None) != (self.v2 is None):
+            raise ValueError("valid: give both sides or neither")
+        self.m12 = np.ascontiguousarray(match12, np.int32)
+        if len(self.m12) != len(self.k1):
+            raise ValueError("match12 has %d entries for %d keypoints" % (len(self.m12), len(self.k1)))
+        self.ls2 = np.ascontiguousarray(level_sigma2, np.float32)
+        self.fix_scale = bool(fix_scale)
+        self.device = device
+        self.set_ransac_parameters()
+
+    def set_ransac_parameters(self, probability=0.99, min_inliers=6, max_iterations=300):
+        self.probability, self.min_inliers, self.max_iterations = float(probability), int(min_inliers), int(max_iterations)
+        self.iterations = 0          # mnIterations
+        self.best_inliers = 0        # mnBestInliers
+        self.s12, self.R12, self.t12, self.T12 = None, None, None, None
+
+    def _args(self, first, n_iterations, best_in, words, res, inl):
+        vv = lambda v: None if v is None else _ptr_or_none(v)
+        return [_ptr_or_none(self.k1), len(self.k1), _ptr_or_none(self.x1), vv(self.v1), _p(self.T1), _p(self.K1),
+                _ptr_or_none(self.k2), len(self.k2), _ptr_or_none(self.x2), vv(self.v2), _p(self.T2), _p(self.K2),
+                _ptr_or_none(self.m12), _p(self.ls2), len(self.ls2), int(self.fix_scale), self.probability, self.min_inliers,
+                self.max_iterations, int(first), int(n_iterations), int(best_in), _p(words), _p(res), _p(inl)]
+
+    def solve(self, first, n_iterations, best_in, rand_words):
+        """One raw orbfe_sim3_solve call, no state kept: (result record, inliers12 as n1 bools)."""
+        L = load()
+        w = np.ascontiguousarray(rand_words, np.int32)
+        if len(w) != 3 * n_iterations:
+            raise ValueError("rand_words needs n_iterations * 3 = %d values" % (3 * n_iterations))
+        res = np.zeros(1, SIM3_RESULT_DTYPE); inl = np.zeros(max(len(self.k1), 1), np.uint8)
+        _check(L, L.orbfe_sim3_solve(*(self._args(first, n_iterations, best_in, w, res, inl) + [self.device])), "orbfe_sim3_solve")
+        return res[0], inl[:len(self.k1)].astype(bool)
+
+    def inspect(self, first, n_iterations, best_in, rand_words):
+        """solve() plus the intermediate results (orbfe_sim3_inspect): dict with result, inliers12, N, indices1, X3Dc1, X3Dc2, P1im1,
+        P2im2, maxError1, maxError2, sets, s12, R12, t12 (per hypothesis) and counts."""
+        L = load()
+        w = np.ascontiguousarray(rand_words, np.int32)
+        n1, it = max(len(self.k1), 1), int(n_iterations)
+        res = np.zeros(1, SIM3_RESULT_DTYPE); inl = np.zeros(n1, np.uint8)
+        n = C.c_int32(0)
+        idx = np.zeros(n1, np.int32); X1 = np.zeros((n1, 3), np.float32); X2 = np.zeros((n1, 3), np.float32)
+        P1 = np.zeros((n1, 2), np.float32); P2 = np.zeros((n1, 2), np.float32); e1 = np.zeros(n1, np.float32); e2 = np.zeros(n1, np.float32)
+        sets = np.zeros((it, 3), np.int32); models = np.zeros((it, 13), np.float32); counts = np.zeros(it, np.int32)
+        _check(L, L.orbfe_sim3_inspect(*(self._args(first, it, best_in, w, res, inl) +
+                                         [C.byref(n), _p(idx), _p(X1), _p(X2), _p(P1), _p(P2), _p(e1), _p(e2), _p(sets), _p(models),
+                                          _p(counts), self.device])), "orbfe_sim3_inspect")
+        N = n.value
+        return dict(result=res[0], inliers12=inl[:len(self.k1)].astype(bool), N=N, indices1=idx[:N], X3Dc1=X1[:N], X3Dc2=X2[:N],
+                    P1im1=P1[:N], P2im2=P2[:N], maxError1=e1[:N], maxError2=e2[:N], sets=sets, s12=models[:, 0],
+                    R12=models[:, 1:10].reshape(-1, 3, 3), t12=models[:, 10:13], counts=counts)
+
+    def iterate(self, n_iterations, rand_words=None):
+        """iterate(nIterations, bNoMore, vbInliers, nInliers): returns (T12 4 x 4 or None, no_more, inliers12, n_inliers)."""
+        n_iterations = int(n_iterations)
+        w = draw_rand_words(3 * n_iterations) if rand_words is None else rand_words
+        r, inl = self.solve(self.iterations, n_iterations, self.best_inliers, w)
+        if r["best"] >= 0:
+            self.best_inliers = int(r["best_inliers"])
+            self.s12, self.R12, self.t12 = float(r["s12"]), r["R12"].reshape(3, 3).copy(), r["t12"].copy()
+            self.T12 = r["T12"].reshape(4, 4).copy()
+        if r["n"] >= self.min_inliers and r["n"] >= 3:
+            self.iterations = int(r["found"]) + 1 if r["found"] >= 0 else min(self.iterations + n_iterations, int(r["max_iterations"]))
+        self.last = r
+        return (self.T12 if r["found"] >= 0 else None), bool(r["no_more"]), inl, int(r["n_inliers"])
+
+    def find(self, rand_words=None):
+        """find(vbInliers12, nInliers): (T12 or None, inliers12, n_inliers)."""
+        T, _, inl, n = self.iterate(self.max_iterations, rand_words)
+        return T, inl, n
+
+
+def sim3_solve_batch_device(d_kps_ptr, d_n_ptr, capacity, d_x3Dw_ptr, d_valid_ptr, d_Tcw_ptr, d_pair1_ptr, d_pair2_ptr, npairs,
+                            d_match12_ptr, K, level_sigma2, fix_scale, probability, min_inliers, max_iterations, d_rand_words_ptr,
+                            d_res_ptr, d_inliers12_ptr, stream=0):
+    """orbfe_sim3_solve_batch_device: npairs whole runs on the blocks orbfe_search_by_bow_batch_device reads and writes (device
+    pointers); results: npairs SIM3_RESULT_DTYPE records and blocks of `capacity` inlier flags.  Asynchronous on `stream`."""
+    L = load()
+    K = np.asarray(K, np.float32)
+    K4 = np.ascontiguousarray([K[0, 0], K[1, 1], K[0, 2], K[1, 2]] if K.shape == (3, 3) else K.reshape(4), np.float32)
+    ls2 = np.ascontiguousarray(level_sigma2, np.float32)
+    _check(L, L.orbfe_sim3_solve_batch_device(d_kps_ptr, d_n_ptr, int(capacity), d_x3Dw_ptr, d_valid_ptr, d_Tcw_ptr, d_pair1_ptr,
+                                              d_pair2_ptr, int(npairs), d_match12_ptr, _p(K4), _p(ls2), len(ls2), int(bool(fix_scale)),
+                                              float(probability), int(min_inliers), int(max_iterations), d_rand_words_ptr, d_res_ptr,
+                                              d_inliers12_ptr, stream), "orbfe_sim3_solve_batch_device")
 
 
 # ------------------------------------------------------------------------------- pose optimization ----

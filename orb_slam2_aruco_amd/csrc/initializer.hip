@@ -15,6 +15,7 @@
 // The numerics restate OpenCV 3.4 for CV_32F: cv::SVD is its one-sided Jacobi (double sums of float products, float rotations,
 // FLT_EPSILON*2), Mat products accumulate in double and round once, 3x3 inv / determinant are the cofactor formulas in double.
 #include "orbfe_common.hpp"
+#include "ransac_sets.hpp"
 #include <cfloat>
 #include <cmath>
 
@@ -331,24 +332,7 @@ __global__ __launch_bounds__(64) void k_init_prep(InitArgs a)
     // the sets (Initializer.cc:80-97): RandomInt(0, size - 1) on the caller's word, then swap-with-back removal from [0, N)
     const int32_t* w = a.words + (size_t)p * a.iters * 8;
     int32_t* sets = a.sets + (size_t)p * a.iters * 8;
-    for (int it = threadIdx.x; it < a.iters; it += blockDim.x) {
-        int pos[8], val[8], nov = 0;   // the positions of the available list that differ from the identity
-        for (int j = 0; j < 8; j++) {
-            const int size = N - j;
-            // rand() returns 0 .. RAND_MAX; a word outside that range (the device entry point cannot check it) is clamped, so that
-            // every index stays inside the match list
-            int randi = (int)(((double)w[it * 8 + j] / ((double)2147483647 + 1.0)) * size);
-            randi = randi < 0 ? 0 : randi >= size ? size - 1 : randi;
-            int idx = randi, back = size - 1;
-            for (int q = 0; q < nov; q++) { if (pos[q] == randi) idx = val[q]; }
-            for (int q = 0; q < nov; q++) { if (pos[q] == size - 1) back = val[q]; }
-            sets[it * 8 + j] = idx;
-            int q = 0;
-            while (q < nov && pos[q] != randi) q++;
-            pos[q] = randi; val[q] = back;
-            if (q == nov) nov++;
-        }
-    }
+    for (int it = threadIdx.x; it < a.iters; it += blockDim.x) decode_set<8>(w + it * 8, N, sets + it * 8);
 }
 
 __global__ __launch_bounds__(64) void k_init_models(InitArgs a)
