@@ -16,6 +16,7 @@
 #include "aruco_kernels.hpp"
 #include "aruco_pose.hpp"
 #include "detector_plan.hpp"
+#include "host_stage.hpp"
 #include "orbfe_common.hpp"
 #include "orbfe_tables.inc"
 
@@ -743,13 +744,7 @@ static int pose_camera(const float* K4, const float* dist, int ndist, float mark
     return ORBFE_OK;
 }
 
-struct PoseWorkspace {
-    hipStream_t stream = nullptr; // not the null stream: that one synchronises with every blocking stream of the process
-    PinnedBuf pinned;
-    ~PoseWorkspace() { if (stream) (void)hipStreamDestroy(stream); }
-    DevBuf markers, poses;
-};
-static thread_local ThreadWorkspaces<PoseWorkspace> tl_pose_ws; // per (thread, device)
+static thread_local ThreadWorkspaces<HostStage> tl_pose_ws; // orbfe_marker_poses, per (thread, device)
 
 // ---- trackingMinDetections: host logic, as in the reference (it walks two short lists; the device supplies the candidates) ----
 namespace {
@@ -1633,20 +1628,20 @@ int orbfe_marker_poses(const orbfe_marker* markers, int n, float marker_size, co
     int rc = pose_camera(K4, dist, ndist, marker_size, c, "orbfe_marker_poses");
     if (rc || (rc = use_device(device))) return rc;
     if (n == 0) return ORBFE_OK;
-    PoseWorkspace& w = tl_pose_ws.get();
-    const size_t mb = (size_t)n * sizeof(orbfe_marker), pb = (size_t)n * sizeof(orbfe_marker_pose);
-    if ((rc = w.markers.ensure(mb)) || (rc = w.poses.ensure(pb)) || (rc = w.pinned.ensure(mb + pb + 64))) return rc;
-    if (!w.stream) ORBFE_HIP(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
-    uint8_t* hp = w.pinned.as<uint8_t>();
-    const size_t o_p = (mb + 63) / 64 * 64;
-    memcpy(hp, markers, mb);
-    ORBFE_HIP(hipMemcpyAsync(w.markers.p, hp, mb, hipMemcpyHostToDevice, w.stream));
-    hipLaunchKernelGGL(k_marker_poses, dim3((n + 31) / 32, 1), dim3(64), 0, w.stream, w.markers.as<orbfe_marker>(), (const int32_t*)nullptr,
-                       n, marker_size, c, w.poses.as<orbfe_marker_pose>());
+    HostStage& w = tl_pose_ws.get();
+    const size_t pb = (size_t)n * sizeof(orbfe_marker_pose);
+    IoLayout l;
+    const size_t i_mk = l.take((size_t)n * sizeof(orbfe_marker));
+    l.outputs();
+    const size_t o_p = l.take(pb);
+    if ((rc = w.begin(l))) return rc;
+    w.put(i_mk, markers, (size_t)n * sizeof(orbfe_marker));
+    if ((rc = w.upload())) return rc;
+    hipLaunchKernelGGL(k_marker_poses, dim3((n + 31) / 32, 1), dim3(64), 0, w.stream, w.dev<const orbfe_marker>(i_mk), (const int32_t*)nullptr,
+                       n, marker_size, c, w.dev<orbfe_marker_pose>(o_p));
     ORBFE_HIP(hipGetLastError());
-    ORBFE_HIP(hipMemcpyAsync(hp + o_p, w.poses.p, pb, hipMemcpyDeviceToHost, w.stream));
-    ORBFE_HIP(hipStreamSynchronize(w.stream));
-    memcpy(poses, hp + o_p, pb);
+    if ((rc = w.download()) || (rc = w.sync())) return rc;
+    memcpy(poses, w.host<uint8_t>(o_p), pb);
     return ORBFE_OK;
 }
 

@@ -1,0 +1,56 @@
+// host_stage.hpp -- what the host-pointer entry points of the geometry solvers share (initializer.hip, sim3_solver.hip,
+// pose_optimizer.hip, orbfe_marker_poses): the layout of one staging block and the workspace that moves it.  Host code only.
+#pragma once
+#include <cstddef>
+
+namespace orbfe {
+
+// Offsets of the arrays of one block, each 256-byte aligned, in the order they are taken: [inputs] outputs() [outputs].  The scratch
+// of a solver is a block without outputs(): only take() and end() mean something there.
+struct IoLayout {
+    size_t off = 0, split = 0;
+    size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
+    void outputs() { split = off; }   // what was taken so far goes up, what is taken from here on comes down
+    size_t end() const { return off; }   // upload range [0, split), download range [split, end())
+};
+
+} // namespace orbfe
+
+#ifdef __HIPCC__
+#include "orbfe_common.hpp"
+
+namespace orbfe {
+
+// The workspace of a host-pointer call, one per (thread, device) through ThreadWorkspaces: the call stages its inputs in `pinned`,
+// sends them to `io` in ONE copy, runs its kernels on `stream`, fetches the outputs in ONE copy and synchronises once.
+struct HostStage {
+    // the RANSAC solvers: the batch entry point runs on the caller's stream, the host entry points on `stream`.  Each has scratch of
+    // its own, so that a host call never overwrites the scratch of a batch still running on the caller's stream of the same thread
+    DevBuf scratch, host_scratch, io;
+    PinnedBuf pinned;
+    hipStream_t stream = nullptr;   // not the null stream: that one synchronises with every blocking stream of the process
+    IoLayout lay;
+    ~HostStage() { if (stream) (void)hipStreamDestroy(stream); }
+    int begin(const IoLayout& l)
+    {
+        lay = l;
+        int rc;
+        if ((rc = io.ensure(l.end())) || (rc = pinned.ensure(l.end()))) return rc;
+        if (!stream) ORBFE_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        return ORBFE_OK;
+    }
+    template <class T> T* dev(size_t o) const { return (T*)(io.as<uint8_t>() + o); }
+    template <class T> T* host(size_t o) const { return (T*)(pinned.as<uint8_t>() + o); }
+    void put(size_t o, const void* src, size_t bytes) { if (bytes) memcpy(host<uint8_t>(o), src, bytes); }
+    int upload() { ORBFE_HIP(hipMemcpyAsync(io.p, pinned.p, lay.split, hipMemcpyHostToDevice, stream)); return ORBFE_OK; }
+    int download()
+    {
+        const size_t b = lay.split;
+        ORBFE_HIP(hipMemcpyAsync(host<uint8_t>(b), dev<uint8_t>(b), lay.end() - b, hipMemcpyDeviceToHost, stream));
+        return ORBFE_OK;
+    }
+    int sync() { ORBFE_HIP(hipStreamSynchronize(stream)); return ORBFE_OK; }
+};
+
+} // namespace orbfe
+#endif

@@ -14,6 +14,7 @@
 //   k_init_finalize 1 workgroup:   ReconstructH / ReconstructF acceptance (or InitializeUseAruco's), vP3D / vbTriangulated of the winner
 // The numerics restate OpenCV 3.4 for CV_32F: cv::SVD is its one-sided Jacobi (double sums of float products, float rotations,
 // FLT_EPSILON*2), Mat products accumulate in double and round once, 3x3 inv / determinant are the cofactor formulas in double.
+#include "host_stage.hpp"
 #include "orbfe_common.hpp"
 #include "ransac_sets.hpp"
 #include <cfloat>
@@ -272,8 +273,6 @@ struct InitArgs {
     const float* poses;          // npose x 12 (R row-major, t)
     int npose;
 };
-
-__device__ __forceinline__ int clampn(int n, int cap) { return n < 0 ? 0 : n > cap ? cap : n; }
 
 // Normalize (Initializer.cc:816-863) of one side, serial sums in index order
 __device__ void normalize_side(const orbfe_keypoint* k, int n, float2* out, float* T)
@@ -878,34 +877,17 @@ __global__ __launch_bounds__(256) void k_init_poses_fold(InitArgs a, int pose_ba
 }
 
 // ------------------------------------------------------------------------------------------- host --
-struct InitWorkspace {
-    // the batch entry point runs on the caller's stream, the host entry points on `stream`: each has scratch of its own, so that a
-    // host call never overwrites the scratch of a batch still running on the null stream of the same thread
-    DevBuf scratch, host_scratch, io;
-    PinnedBuf pinned;
-    hipStream_t stream = nullptr;
-    ~InitWorkspace()
-    {
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
-ThreadWorkspaces<InitWorkspace>& init_spaces()
-{
-    static thread_local ThreadWorkspaces<InitWorkspace> w;
-    return w;
-}
-
-size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
+thread_local ThreadWorkspaces<HostStage> tl_stages;
 
 // carve the scratch of npairs pairs out of buf
 int carve(DevBuf& buf, InitArgs& a, int npairs)
 {
     const size_t cap = (size_t)a.capacity, P = (size_t)npairs, it = (size_t)a.iters;
-    const size_t o_st = 0, o_ml = o_st + al(P * sizeof(PairState)), o_pn = o_ml + al(P * cap * sizeof(int2));
-    const size_t o_sets = o_pn + al(P * 2 * cap * sizeof(float2)), o_mod = o_sets + al(P * it * 8 * 4);
-    const size_t o_sc = o_mod + al(P * it * 27 * 4), o_inl = o_sc + al(P * 2 * it * 4), o_cos = o_inl + al(P * cap);
-    const size_t end = o_cos + al(P * INIT_MAX_MOT * cap * 4);
-    int rc = buf.ensure(end);
+    IoLayout l;
+    const size_t o_st = l.take(P * sizeof(PairState)), o_ml = l.take(P * cap * sizeof(int2)), o_pn = l.take(P * 2 * cap * sizeof(float2));
+    const size_t o_sets = l.take(P * it * 8 * 4), o_mod = l.take(P * it * 27 * 4), o_sc = l.take(P * 2 * it * 4), o_inl = l.take(P * cap);
+    const size_t o_cos = l.take(P * INIT_MAX_MOT * cap * 4);
+    int rc = buf.ensure(l.end());
     if (rc) return rc;
     uint8_t* b = buf.as<uint8_t>();
     a.st = (PairState*)(b + o_st);
@@ -976,9 +958,7 @@ int host_call(const HostCall& c, int device, const char* name)
         for (int i = 0; i < c.iters * 8; i++)
             if (c.words[i] < 0) return fail(ORBFE_ERR_INVALID, "%s: rand_words[%d] is negative (rand() returns 0 .. RAND_MAX)", name, i);
     if ((rc = use_device(device))) return rc;
-    InitWorkspace& w = init_spaces().get();
-    if (!w.stream) ORBFE_HIP(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
-    const hipStream_t s = w.stream;
+    HostStage& w = tl_stages.get();
     InitArgs a{};
     a.capacity = std::max(std::max(c.n1, c.n2), 1);
     a.iters = c.iters;
@@ -986,29 +966,26 @@ int host_call(const HostCall& c, int device, const char* name)
     a.sigma = c.sigma;
     a.npose = c.npose;
     const size_t cap = (size_t)a.capacity, nw = c.words ? (size_t)c.iters * 8 : 0, np = c.poses ? (size_t)c.npose * 12 : 0;
-    // device io: [kps 2 cap | n (16 B) | m12 cap | words | poses] [res | p3d 3 cap | tri cap]
-    const size_t i_kps = 0, i_n = al(2 * cap * sizeof(orbfe_keypoint)), i_m = i_n + 256, i_w = i_m + al(cap * 4), i_p = i_w + al(nw * 4);
-    const size_t i_end = i_p + al(np * 4);
-    const size_t o_res = i_end, o_p3 = o_res + al(sizeof(orbfe_init_result)), o_tri = o_p3 + al(cap * 12), o_end = o_tri + al(cap);
-    if ((rc = w.io.ensure(o_end)) || (rc = w.pinned.ensure(o_end)) || (rc = carve(w.host_scratch, a, 1))) return rc;
-    uint8_t* hp = w.pinned.as<uint8_t>();
-    uint8_t* dp = w.io.as<uint8_t>();
-    if (c.n1) memcpy(hp + i_kps, c.kps1, (size_t)c.n1 * sizeof(orbfe_keypoint));
-    if (c.n2) memcpy(hp + i_kps + cap * sizeof(orbfe_keypoint), c.kps2, (size_t)c.n2 * sizeof(orbfe_keypoint));
+    const size_t kb = sizeof(orbfe_keypoint);
+    // device io: [kps 2 cap | n | m12 cap | words | poses] [res | p3d 3 cap | tri cap]
+    IoLayout l;
+    const size_t i_kps = l.take(2 * cap * kb), i_n = l.take(8), i_m = l.take(cap * 4), i_w = l.take(nw * 4), i_p = l.take(np * 4);
+    l.outputs();
+    const size_t o_res = l.take(sizeof(orbfe_init_result)), o_p3 = l.take(cap * 12), o_tri = l.take(cap);
+    if ((rc = w.begin(l)) || (rc = carve(w.host_scratch, a, 1))) return rc;
+    const hipStream_t s = w.stream;
     const int32_t nn[2] = {c.n1, c.n2};
-    memcpy(hp + i_n, nn, 8);
-    if (c.n1) memcpy(hp + i_m, c.m12, (size_t)c.n1 * 4);
-    if (nw) memcpy(hp + i_w, c.words, nw * 4);
-    if (np) memcpy(hp + i_p, c.poses, np * 4);
-    ORBFE_HIP(hipMemcpyAsync(dp, hp, i_end, hipMemcpyHostToDevice, s));
-    a.kps = (const orbfe_keypoint*)(dp + i_kps);
-    a.nk = (const int32_t*)(dp + i_n);
-    a.m12 = (const int32_t*)(dp + i_m);
-    a.words = nw ? (const int32_t*)(dp + i_w) : nullptr;
-    a.poses = np ? (const float*)(dp + i_p) : nullptr;
-    a.res = (orbfe_init_result*)(dp + o_res);
-    a.p3d = (float*)(dp + o_p3);
-    a.tri = dp + o_tri;
+    w.put(i_kps, c.kps1, (size_t)c.n1 * kb);
+    w.put(i_kps + cap * kb, c.kps2, (size_t)c.n2 * kb);
+    w.put(i_n, nn, 8);
+    w.put(i_m, c.m12, (size_t)c.n1 * 4);
+    w.put(i_w, c.words, nw * 4);
+    w.put(i_p, c.poses, np * 4);
+    if ((rc = w.upload())) return rc;
+    a.kps = w.dev<const orbfe_keypoint>(i_kps); a.nk = w.dev<const int32_t>(i_n); a.m12 = w.dev<const int32_t>(i_m);
+    a.words = nw ? w.dev<const int32_t>(i_w) : nullptr;
+    a.poses = np ? w.dev<const float>(i_p) : nullptr;
+    a.res = w.dev<orbfe_init_result>(o_res); a.p3d = w.dev<float>(o_p3); a.tri = w.dev<uint8_t>(o_tri);
     if (c.poses) {
         // InitializeUseAruco: the words are not used; prep compacts and normalises (normalisation is not used either)
         InitArgs a0 = a;
@@ -1022,7 +999,7 @@ int host_call(const HostCall& c, int device, const char* name)
     } else if ((rc = launch_main(a, 1, s))) {
         return rc;
     }
-    ORBFE_HIP(hipMemcpyAsync(hp + o_res, dp + o_res, o_end - o_res, hipMemcpyDeviceToHost, s));
+    if ((rc = w.download())) return rc;
     if (c.sets) {
         // orbfe_initialize_inspect: the intermediate results, straight from the scratch
         const uint8_t* st0 = (const uint8_t*)a.st;
@@ -1037,16 +1014,25 @@ int host_call(const HostCall& c, int device, const char* name)
         if (c.n1) ORBFE_HIP(hipMemcpyAsync(c.pn1, a.pn, (size_t)c.n1 * 8, hipMemcpyDeviceToHost, s));
         if (c.n2) ORBFE_HIP(hipMemcpyAsync(c.pn2, a.pn + cap, (size_t)c.n2 * 8, hipMemcpyDeviceToHost, s));
     }
-    ORBFE_HIP(hipStreamSynchronize(s));
-    const orbfe_init_result* r = (const orbfe_init_result*)(hp + o_res);
+    if ((rc = w.sync())) return rc;
+    const orbfe_init_result* r = w.host<const orbfe_init_result>(o_res);
     *c.res = *r;
     // p3d / triangulated: written only where the reference assigns vP3D / vbTriangulated
     const bool wrote = c.poses ? r->best_h >= 0 : r->initialized != 0;
     if (wrote && c.n1) {
-        if (c.p3d) memcpy(c.p3d, hp + o_p3, (size_t)c.n1 * 12);
-        if (c.tri) memcpy(c.tri, hp + o_tri, (size_t)c.n1);
+        if (c.p3d) memcpy(c.p3d, w.host<uint8_t>(o_p3), (size_t)c.n1 * 12);
+        if (c.tri) memcpy(c.tri, w.host<uint8_t>(o_tri), (size_t)c.n1);
     }
     return ORBFE_OK;
+}
+
+// the fields every public wrapper sets
+HostCall pair_call(const orbfe_keypoint* kps1, int n1, const orbfe_keypoint* kps2, int n2, const int32_t* m12, const float* K4, float sigma,
+                   int iters, orbfe_init_result* res)
+{
+    HostCall c{};
+    c.kps1 = kps1; c.kps2 = kps2; c.n1 = n1; c.n2 = n2; c.m12 = m12; c.K4 = K4; c.sigma = sigma; c.iters = iters; c.res = res;
+    return c;
 }
 
 } // namespace
@@ -1058,9 +1044,8 @@ int orbfe_initialize(const orbfe_keypoint* kps1, int n1, const orbfe_keypoint* k
                      float sigma, int iterations, const int32_t* rand_words, orbfe_init_result* res, float* p3d, uint8_t* triangulated,
                      int device)
 {
-    HostCall c{};
-    c.kps1 = kps1; c.kps2 = kps2; c.n1 = n1; c.n2 = n2; c.m12 = matches12; c.K4 = K4; c.sigma = sigma; c.iters = iterations;
-    c.words = rand_words; c.res = res; c.p3d = p3d; c.tri = triangulated;
+    HostCall c = pair_call(kps1, n1, kps2, n2, matches12, K4, sigma, iterations, res);
+    c.words = rand_words; c.p3d = p3d; c.tri = triangulated;
     return host_call(c, device, "orbfe_initialize");
 }
 
@@ -1070,9 +1055,8 @@ int orbfe_initialize_inspect(const orbfe_keypoint* kps1, int n1, const orbfe_key
 {
     if (!nmatches || !sets || !T12 || (n1 > 0 && !pn1) || (n2 > 0 && !pn2) || !models || !scores)
         return fail(ORBFE_ERR_INVALID, "orbfe_initialize_inspect: null output");
-    HostCall c{};
-    c.kps1 = kps1; c.kps2 = kps2; c.n1 = n1; c.n2 = n2; c.m12 = matches12; c.K4 = K4; c.sigma = sigma; c.iters = iterations;
-    c.words = rand_words; c.res = res;
+    HostCall c = pair_call(kps1, n1, kps2, n2, matches12, K4, sigma, iterations, res);
+    c.words = rand_words;
     c.sets = sets; c.T12 = T12; c.pn1 = pn1; c.pn2 = pn2; c.models = models; c.scores = scores; c.nmatch = nmatches;
     return host_call(c, device, "orbfe_initialize_inspect");
 }
@@ -1092,9 +1076,8 @@ int orbfe_initialize_check_poses(const orbfe_keypoint* kps1, int n1, const orbfe
     }
     for (int i = 0; i < npose * 12; i++)
         if (!std::isfinite(poses[i])) return fail(ORBFE_ERR_INVALID, "orbfe_initialize_check_poses: pose %d is not finite", i / 12);
-    HostCall c{};
-    c.kps1 = kps1; c.kps2 = kps2; c.n1 = n1; c.n2 = n2; c.m12 = matches12; c.K4 = K4; c.sigma = sigma; c.iters = 1;
-    c.poses = poses; c.npose = npose; c.res = res; c.p3d = p3d; c.tri = triangulated;
+    HostCall c = pair_call(kps1, n1, kps2, n2, matches12, K4, sigma, 1, res);
+    c.poses = poses; c.npose = npose; c.p3d = p3d; c.tri = triangulated;
     return host_call(c, device, "orbfe_initialize_check_poses");
 }
 
@@ -1108,7 +1091,7 @@ int orbfe_initialize_batch_device(const orbfe_keypoint* d_kps, const int32_t* d_
     int rc = check_K(K4, sigma);
     if (rc) return rc;
     const hipStream_t s = (hipStream_t)stream;
-    InitWorkspace& w = init_spaces().get(s);
+    HostStage& w = tl_stages.get(s);
     InitArgs a{};
     a.kps = d_kps; a.nk = d_n; a.m12 = d_matches12; a.words = d_rand_words;
     a.capacity = capacity; a.iters = iterations;

@@ -10,6 +10,7 @@
 // 16 M lane-ops.  Train descriptors are staged through LDS and broadcast to all lanes of a wave.
 #include <climits>
 
+#include "host_stage.hpp"
 #include "orbfe_common.hpp"
 #include "wave_dpp.hpp"
 
@@ -1524,13 +1525,12 @@ static int sbp_host_run(const SbpHostCall& c)
 {
     MatchWorkspace& w = ws();
     const size_t n = (size_t)c.n, nq = (size_t)c.nq;
-    size_t end = 0;
-    auto slice = [&end](size_t bytes) { const size_t o = end; end += (bytes + 255) / 256 * 256; return o; };
-    const size_t s_kps = slice(n * sizeof(orbfe_keypoint)), s_desc = slice(n * 32), s_taken = slice(n), s_cur = slice(n * 4);
-    const size_t s_q = slice(nq * sizeof(SbpQuery)), s_qdesc = slice(nq * 32), s_obs = slice(nq), s_angle = slice(nq * 4);
-    const size_t s_x3 = slice(nq * 12), s_last = slice(nq * sizeof(orbfe_keypoint)), s_valid = slice(nq), s_cam = slice((12 + 16) * 4);
-    const size_t s_out = slice(nq * 4 * 7), s_cnt = slice(8); // best_idx .. second_level, match, qbin | nmatches, overflow
-    int rc = w.sbp_host.ensure(end);
+    IoLayout l;
+    const size_t s_kps = l.take(n * sizeof(orbfe_keypoint)), s_desc = l.take(n * 32), s_taken = l.take(n), s_cur = l.take(n * 4);
+    const size_t s_q = l.take(nq * sizeof(SbpQuery)), s_qdesc = l.take(nq * 32), s_obs = l.take(nq), s_angle = l.take(nq * 4);
+    const size_t s_x3 = l.take(nq * 12), s_last = l.take(nq * sizeof(orbfe_keypoint)), s_valid = l.take(nq), s_cam = l.take((12 + 16) * 4);
+    const size_t s_out = l.take(nq * 4 * 7), s_cnt = l.take(8); // best_idx .. second_level, match, qbin | nmatches, overflow
+    int rc = w.sbp_host.ensure(l.end());
     if (rc) return rc;
     uint8_t* b = w.sbp_host.as<uint8_t>();
     int32_t* o = reinterpret_cast<int32_t*>(b + s_out);

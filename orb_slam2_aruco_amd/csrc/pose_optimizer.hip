@@ -14,6 +14,7 @@
 // The edges' "cached" errors of g2o are not stored: they are the errors at the last pose the active edges were evaluated at (Tev),
 // recomputed bit for bit when the classification reads them.  After a round that ended on rejected trials Tev is the rejected
 // trial's pose, as the reference's stale errors are.
+#include "host_stage.hpp"
 #include "orbfe_common.hpp"
 #include <cfloat>
 #include <cmath>
@@ -755,22 +756,7 @@ int launch(const PoseArgs& a, int nframes, hipStream_t s, const char* name)
     return ORBFE_OK;
 }
 
-struct PoseWorkspace {
-    DevBuf io;
-    PinnedBuf pinned;
-    hipStream_t stream = nullptr;
-    ~PoseWorkspace()
-    {
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
-ThreadWorkspaces<PoseWorkspace>& pose_spaces()
-{
-    static thread_local ThreadWorkspaces<PoseWorkspace> w;
-    return w;
-}
-
-size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
+thread_local ThreadWorkspaces<HostStage> tl_stages;
 
 } // namespace
 } // namespace orbfe
@@ -794,49 +780,34 @@ extern "C" int orbfe_pose_optimization(const orbfe_keypoint* kps, int n, const u
     for (int i = 0; i < 12; i++)
         if (!std::isfinite(Tcw_in[i])) return fail(ORBFE_ERR_INVALID, "%s: Tcw_in is not finite", name);
     if ((rc = use_device(device))) return rc;
-    PoseWorkspace& w = pose_spaces().get();
-    if (!w.stream) ORBFE_HIP(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
-    const hipStream_t s = w.stream;
+    HostStage& w = tl_stages.get();
     const size_t cap = (size_t)std::max(n, 1), mc = (size_t)std::max(nm, 1);
     // device io: [kps | has | x3Dw | markers | n, nm | Tin] [Tout | res | outlier | chi2]
-    const size_t i_kps = 0, i_has = al(cap * sizeof(orbfe_keypoint)), i_x = i_has + al(cap), i_mk = i_x + al(cap * 12);
-    const size_t i_n = i_mk + al(mc * sizeof(orbfe_pose_marker)), i_T = i_n + 256, i_end = i_T + 256;
-    const size_t o_T = i_end, o_res = o_T + 256, o_out = o_res + al(sizeof(orbfe_pose_result)), o_chi = o_out + al(cap);
-    const size_t o_end = o_chi + al(cap * 4);
-    if ((rc = w.io.ensure(o_end)) || (rc = w.pinned.ensure(o_end))) return rc;
-    uint8_t* hp = w.pinned.as<uint8_t>();
-    uint8_t* dp = w.io.as<uint8_t>();
-    if (n) {
-        memcpy(hp + i_kps, kps, (size_t)n * sizeof(orbfe_keypoint));
-        memcpy(hp + i_has, has_mp, (size_t)n);
-        memcpy(hp + i_x, x3Dw, (size_t)n * 12);
-    }
-    if (nm) memcpy(hp + i_mk, markers, (size_t)nm * sizeof(orbfe_pose_marker));
+    IoLayout l;
+    const size_t i_kps = l.take(cap * sizeof(orbfe_keypoint)), i_has = l.take(cap), i_x = l.take(cap * 12);
+    const size_t i_mk = l.take(mc * sizeof(orbfe_pose_marker)), i_n = l.take(8), i_T = l.take(48);
+    l.outputs();
+    const size_t o_T = l.take(48), o_res = l.take(sizeof(orbfe_pose_result)), o_out = l.take(cap), o_chi = l.take(cap * 4);
+    if ((rc = w.begin(l))) return rc;
     const int32_t nn[2] = {n, nm};
-    memcpy(hp + i_n, nn, 8);
-    memcpy(hp + i_T, Tcw_in, 48);
-    ORBFE_HIP(hipMemcpyAsync(dp, hp, i_end, hipMemcpyHostToDevice, s));
-    a.kps = (const orbfe_keypoint*)(dp + i_kps);
-    a.has_mp = dp + i_has;
-    a.x3Dw = (const float*)(dp + i_x);
-    a.markers = (const orbfe_pose_marker*)(dp + i_mk);
-    a.n = (const int32_t*)(dp + i_n);
-    a.nm = (const int32_t*)(dp + i_n) + 1;
-    a.Tin = (const float*)(dp + i_T);
-    a.Tout = (float*)(dp + o_T);
-    a.res = (orbfe_pose_result*)(dp + o_res);
-    a.outlier = dp + o_out;
-    a.chi2 = (float*)(dp + o_chi);
-    a.capacity = (int)cap;
-    a.mcapacity = (int)mc;
-    if ((rc = launch(a, 1, s, name))) return rc;
-    ORBFE_HIP(hipMemcpyAsync(hp + o_T, dp + o_T, o_end - o_T, hipMemcpyDeviceToHost, s));
-    ORBFE_HIP(hipStreamSynchronize(s));
-    memcpy(Tcw_out, hp + o_T, 48);
-    *res = *(const orbfe_pose_result*)(hp + o_res);
+    w.put(i_kps, kps, (size_t)n * sizeof(orbfe_keypoint));
+    w.put(i_has, has_mp, (size_t)n);
+    w.put(i_x, x3Dw, (size_t)n * 12);
+    w.put(i_mk, markers, (size_t)nm * sizeof(orbfe_pose_marker));
+    w.put(i_n, nn, 8);
+    w.put(i_T, Tcw_in, 48);
+    if ((rc = w.upload())) return rc;
+    a.kps = w.dev<const orbfe_keypoint>(i_kps); a.has_mp = w.dev<const uint8_t>(i_has); a.x3Dw = w.dev<const float>(i_x);
+    a.markers = w.dev<const orbfe_pose_marker>(i_mk);
+    a.n = w.dev<const int32_t>(i_n); a.nm = a.n + 1; a.Tin = w.dev<const float>(i_T);
+    a.Tout = w.dev<float>(o_T); a.res = w.dev<orbfe_pose_result>(o_res); a.outlier = w.dev<uint8_t>(o_out); a.chi2 = w.dev<float>(o_chi);
+    a.capacity = (int)cap; a.mcapacity = (int)mc;
+    if ((rc = launch(a, 1, w.stream, name)) || (rc = w.download()) || (rc = w.sync())) return rc;
+    memcpy(Tcw_out, w.host<float>(o_T), 48);
+    *res = *w.host<const orbfe_pose_result>(o_res);
     // only the entries with a map point were written
-    const uint8_t* ho = hp + o_out;
-    const float* hc = (const float*)(hp + o_chi);
+    const uint8_t* ho = w.host<const uint8_t>(o_out);
+    const float* hc = w.host<const float>(o_chi);
     const bool classified = res->rounds > 0;
     for (int i = 0; i < n; i++)
         if (has_mp[i]) {

@@ -1,10 +1,13 @@
-// ransac_sets.hpp -- the minimal-set rule the RANSAC drivers share (initializer.hip: 8 indices, sim3_solver.hip: 3).
+// ransac_sets.hpp -- the device helpers the RANSAC drivers share (initializer.hip: sets of 8 indices, sim3_solver.hip: of 3).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 namespace orbfe {
+
+// a frame's keypoint count as the kernels use it: a count outside 0 .. capacity (a device entry point cannot check it) is clamped
+__device__ __forceinline__ int clampn(int n, int cap) { return n < 0 ? 0 : n > cap ? cap : n; }
 
 // One minimal set as the reference draws it (Initializer.cc:80-97, Sim3Solver.cc:163-177): for j = 0 .. K-1,
 // RandomInt(0, size - 1) on the caller's rand() word w[j] with size = N - j, the index taken from the list of available indices

@@ -36,6 +36,7 @@
 // word read); a hypothesis whose quaternion has no imaginary part (norm 0 or not finite: 0 / 0 at :280) -> zero model, zero
 // inliers, and it never becomes `best`; a point with z = 0 projects to inf / NaN and is never an inlier; an iteration count that
 // is not finite or below 1 (log of a negative number: N < min_inliers, min_inliers = 0) -> 1.
+#include "host_stage.hpp"
 #include "orbfe_common.hpp"
 #include "ransac_sets.hpp"
 #include <cfloat>
@@ -84,8 +85,6 @@ struct Sim3Args {
     orbfe_sim3_result* res;
     uint8_t* inl;                // capacity per problem
 };
-
-__device__ __forceinline__ int clampn(int n, int cap) { return n < 0 ? 0 : n > cap ? cap : n; }
 
 // d = A x + t for a 3 x 4 row-major [A | t]: the Mat product with C (alpha = beta = 1)
 __device__ __forceinline__ void rigid(const float* T, float x, float y, float z, float* d)
@@ -477,35 +476,18 @@ __global__ __launch_bounds__(256) void k_sim3_select(Sim3Args a)
 }
 
 // ------------------------------------------------------------------------------------------- host --
-struct Sim3Workspace {
-    // as the initializer's: the batch entry point runs on the caller's stream, the host entry points on `stream`
-    DevBuf scratch, host_scratch, io;
-    PinnedBuf pinned;
-    hipStream_t stream = nullptr;
-    ~Sim3Workspace()
-    {
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
-ThreadWorkspaces<Sim3Workspace>& sim3_spaces()
-{
-    static thread_local ThreadWorkspaces<Sim3Workspace> w;
-    return w;
-}
-
-size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
+thread_local ThreadWorkspaces<HostStage> tl_stages;
 
 int carve(DevBuf& buf, Sim3Args& a, int npairs)
 {
     const size_t cap = (size_t)a.capacity, P = (size_t)npairs, it = (size_t)a.iters;
     a.mwords = (int)((cap + 63) / 64);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes); return o; };
-    const size_t o_st = take(P * sizeof(Sim3State)), o_idx = take(P * cap * 4), o_X1 = take(P * cap * 12), o_X2 = take(P * cap * 12);
-    const size_t o_P1 = take(P * cap * 8), o_P2 = take(P * cap * 8), o_e1 = take(P * cap * 4), o_e2 = take(P * cap * 4);
-    const size_t o_sets = take(P * it * 12), o_mod = take(P * it * SIM3_MODEL * 4), o_cnt = take(P * it * 4);
-    const size_t o_mask = take(P * it * (size_t)a.mwords * 8);
-    int rc = buf.ensure(off);
+    IoLayout l;
+    const size_t o_st = l.take(P * sizeof(Sim3State)), o_idx = l.take(P * cap * 4), o_X1 = l.take(P * cap * 12), o_X2 = l.take(P * cap * 12);
+    const size_t o_P1 = l.take(P * cap * 8), o_P2 = l.take(P * cap * 8), o_e1 = l.take(P * cap * 4), o_e2 = l.take(P * cap * 4);
+    const size_t o_sets = l.take(P * it * 12), o_mod = l.take(P * it * SIM3_MODEL * 4), o_cnt = l.take(P * it * 4);
+    const size_t o_mask = l.take(P * it * (size_t)a.mwords * 8);
+    int rc = buf.ensure(l.end());
     if (rc) return rc;
     uint8_t* b = buf.as<uint8_t>();
     a.st = (Sim3State*)(b + o_st);
@@ -598,53 +580,42 @@ int sim3_host_call(const Sim3HostCall& c, int device, const char* name)
     for (int i = 0; i < c.n_iterations * 3; i++)
         if (c.words[i] < 0) return fail(ORBFE_ERR_INVALID, "%s: rand_words[%d] is negative (rand() returns 0 .. RAND_MAX)", name, i);
     if ((rc = use_device(device))) return rc;
-    Sim3Workspace& w = sim3_spaces().get();
-    if (!w.stream) ORBFE_HIP(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
-    const hipStream_t s = w.stream;
+    HostStage& w = tl_stages.get();
     Sim3Args a{};
     a.capacity = std::max(std::max(c.n1, c.n2), 1);
     a.iters = c.n_iterations;
     a.first = c.first;
     a.best_in = c.best_in;
     fill_common(a, c.K1, c.K2, c.ls2, c.nlevels, c.fix_scale, c.probability, c.min_inliers, c.max_iterations);
-    const size_t cap = (size_t)a.capacity, nw = (size_t)c.n_iterations * 3;
-    // device io: [kps 2 cap | n (256 B) | x3Dw 2 cap x 3 | valid 2 cap | Tcw 24 | m12 cap | words] [res | inliers cap]
-    size_t off = 0;
-    auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes); return o; };
-    const size_t i_kps = take(2 * cap * sizeof(orbfe_keypoint)), i_n = take(8), i_x = take(2 * cap * 12), i_v = take(2 * cap);
-    const size_t i_T = take(96), i_m = take(cap * 4), i_w = take(nw * 4), i_end = off;
-    const size_t o_res = take(sizeof(orbfe_sim3_result)), o_inl = take(cap), o_end = off;
-    if ((rc = w.io.ensure(o_end)) || (rc = w.pinned.ensure(o_end)) || (rc = carve(w.host_scratch, a, 1))) return rc;
-    uint8_t* hp = w.pinned.as<uint8_t>();
-    uint8_t* dp = w.io.as<uint8_t>();
-    if (c.n1) {
-        memcpy(hp + i_kps, c.kps1, (size_t)c.n1 * sizeof(orbfe_keypoint));
-        memcpy(hp + i_x, c.x1, (size_t)c.n1 * 12);
-        if (c.v1) memcpy(hp + i_v, c.v1, (size_t)c.n1);
-        memcpy(hp + i_m, c.m12, (size_t)c.n1 * 4);
-    }
-    if (c.n2) {
-        memcpy(hp + i_kps + cap * sizeof(orbfe_keypoint), c.kps2, (size_t)c.n2 * sizeof(orbfe_keypoint));
-        memcpy(hp + i_x + cap * 12, c.x2, (size_t)c.n2 * 12);
-        if (c.v2) memcpy(hp + i_v + cap, c.v2, (size_t)c.n2);
-    }
+    const size_t cap = (size_t)a.capacity, nw = (size_t)c.n_iterations * 3, kb = sizeof(orbfe_keypoint);
+    // device io: [kps 2 cap | n | x3Dw 2 cap x 3 | valid 2 cap | Tcw 24 | m12 cap | words] [res | inliers cap]
+    IoLayout l;
+    const size_t i_kps = l.take(2 * cap * kb), i_n = l.take(8), i_x = l.take(2 * cap * 12), i_v = l.take(2 * cap);
+    const size_t i_T = l.take(96), i_m = l.take(cap * 4), i_w = l.take(nw * 4);
+    l.outputs();
+    const size_t o_res = l.take(sizeof(orbfe_sim3_result)), o_inl = l.take(cap);
+    if ((rc = w.begin(l)) || (rc = carve(w.host_scratch, a, 1))) return rc;
+    const hipStream_t s = w.stream;
     const int32_t nn[2] = {c.n1, c.n2};
-    memcpy(hp + i_n, nn, 8);
-    memcpy(hp + i_T, c.Tcw1, 48);
-    memcpy(hp + i_T + 48, c.Tcw2, 48);
-    memcpy(hp + i_w, c.words, nw * 4);
-    ORBFE_HIP(hipMemcpyAsync(dp, hp, i_end, hipMemcpyHostToDevice, s));
-    a.kps = (const orbfe_keypoint*)(dp + i_kps);
-    a.nk = (const int32_t*)(dp + i_n);
-    a.x3Dw = (const float*)(dp + i_x);
-    a.valid = c.v1 ? dp + i_v : nullptr;
-    a.Tcw = (const float*)(dp + i_T);
-    a.m12 = (const int32_t*)(dp + i_m);
-    a.words = (const int32_t*)(dp + i_w);
-    a.res = (orbfe_sim3_result*)(dp + o_res);
-    a.inl = dp + o_inl;
-    if ((rc = launch(a, 1, s))) return rc;
-    ORBFE_HIP(hipMemcpyAsync(hp + o_res, dp + o_res, o_end - o_res, hipMemcpyDeviceToHost, s));
+    w.put(i_kps, c.kps1, (size_t)c.n1 * kb);
+    w.put(i_kps + cap * kb, c.kps2, (size_t)c.n2 * kb);
+    w.put(i_n, nn, 8);
+    w.put(i_x, c.x1, (size_t)c.n1 * 12);
+    w.put(i_x + cap * 12, c.x2, (size_t)c.n2 * 12);
+    if (c.v1) {
+        w.put(i_v, c.v1, (size_t)c.n1);
+        w.put(i_v + cap, c.v2, (size_t)c.n2);
+    }
+    w.put(i_T, c.Tcw1, 48);
+    w.put(i_T + 48, c.Tcw2, 48);
+    w.put(i_m, c.m12, (size_t)c.n1 * 4);
+    w.put(i_w, c.words, nw * 4);
+    if ((rc = w.upload())) return rc;
+    a.kps = w.dev<const orbfe_keypoint>(i_kps); a.nk = w.dev<const int32_t>(i_n); a.x3Dw = w.dev<const float>(i_x);
+    a.valid = c.v1 ? w.dev<const uint8_t>(i_v) : nullptr;
+    a.Tcw = w.dev<const float>(i_T); a.m12 = w.dev<const int32_t>(i_m); a.words = w.dev<const int32_t>(i_w);
+    a.res = w.dev<orbfe_sim3_result>(o_res); a.inl = w.dev<uint8_t>(o_inl);
+    if ((rc = launch(a, 1, s)) || (rc = w.download())) return rc;
     std::vector<float> mod;
     if (c.inspect) {
         // the intermediate results, straight from the scratch (a diagnostic path: one copy per array)
@@ -664,10 +635,10 @@ int sim3_host_call(const Sim3HostCall& c, int device, const char* name)
         ORBFE_HIP(hipMemcpyAsync(mod.data(), a.models, it * SIM3_MODEL * 4, hipMemcpyDeviceToHost, s));
         ORBFE_HIP(hipMemcpyAsync(c.counts, a.counts, it * 4, hipMemcpyDeviceToHost, s));
     }
-    ORBFE_HIP(hipStreamSynchronize(s));
-    const orbfe_sim3_result* r = (const orbfe_sim3_result*)(hp + o_res);
+    if ((rc = w.sync())) return rc;
+    const orbfe_sim3_result* r = w.host<const orbfe_sim3_result>(o_res);
     *c.res = *r;
-    if (c.n1) memcpy(c.inl, hp + o_inl, (size_t)c.n1);
+    if (c.n1) memcpy(c.inl, w.host<uint8_t>(o_inl), (size_t)c.n1);
     if (c.inspect) {
         // entries past N and hypotheses the window did not run (it ends at max_iterations, or at N < 3 / N < min_inliers) are 0.
         // Every hypothesis of the window is computed and scored, also those after the one that was found.
@@ -688,6 +659,22 @@ int sim3_host_call(const Sim3HostCall& c, int device, const char* name)
     return ORBFE_OK;
 }
 
+// the arguments orbfe_sim3_solve and orbfe_sim3_inspect share, as a call
+Sim3HostCall solve_call(const orbfe_keypoint* kps1, int n1, const float* x3Dw1, const uint8_t* valid1, const float* Tcw1, const float* K4_1,
+                        const orbfe_keypoint* kps2, int n2, const float* x3Dw2, const uint8_t* valid2, const float* Tcw2, const float* K4_2,
+                        const int32_t* match12, const float* level_sigma2, int nlevels, int fix_scale, double probability, int min_inliers,
+                        int max_iterations, int first_iteration, int n_iterations, int best_inliers_in, const int32_t* rand_words,
+                        orbfe_sim3_result* res, uint8_t* inliers12)
+{
+    Sim3HostCall c{};
+    c.kps1 = kps1; c.n1 = n1; c.x1 = x3Dw1; c.v1 = valid1; c.Tcw1 = Tcw1; c.K1 = K4_1;
+    c.kps2 = kps2; c.n2 = n2; c.x2 = x3Dw2; c.v2 = valid2; c.Tcw2 = Tcw2; c.K2 = K4_2;
+    c.m12 = match12; c.ls2 = level_sigma2; c.nlevels = nlevels; c.fix_scale = fix_scale; c.probability = probability;
+    c.min_inliers = min_inliers; c.max_iterations = max_iterations; c.first = first_iteration; c.n_iterations = n_iterations;
+    c.best_in = best_inliers_in; c.words = rand_words; c.res = res; c.inl = inliers12;
+    return c;
+}
+
 } // namespace
 } // namespace orbfe
 
@@ -699,12 +686,9 @@ int orbfe_sim3_solve(const orbfe_keypoint* kps1, int n1, const float* x3Dw1, con
                      int max_iterations, int first_iteration, int n_iterations, int best_inliers_in, const int32_t* rand_words,
                      orbfe_sim3_result* res, uint8_t* inliers12, int device)
 {
-    Sim3HostCall c{};
-    c.kps1 = kps1; c.n1 = n1; c.x1 = x3Dw1; c.v1 = valid1; c.Tcw1 = Tcw1; c.K1 = K4_1;
-    c.kps2 = kps2; c.n2 = n2; c.x2 = x3Dw2; c.v2 = valid2; c.Tcw2 = Tcw2; c.K2 = K4_2;
-    c.m12 = match12; c.ls2 = level_sigma2; c.nlevels = nlevels; c.fix_scale = fix_scale; c.probability = probability;
-    c.min_inliers = min_inliers; c.max_iterations = max_iterations; c.first = first_iteration; c.n_iterations = n_iterations;
-    c.best_in = best_inliers_in; c.words = rand_words; c.res = res; c.inl = inliers12;
+    const Sim3HostCall c = solve_call(kps1, n1, x3Dw1, valid1, Tcw1, K4_1, kps2, n2, x3Dw2, valid2, Tcw2, K4_2, match12, level_sigma2, nlevels,
+                                              fix_scale, probability, min_inliers, max_iterations, first_iteration, n_iterations, best_inliers_in,
+                                              rand_words, res, inliers12);
     return sim3_host_call(c, device, "orbfe_sim3_solve");
 }
 
@@ -717,12 +701,9 @@ int orbfe_sim3_inspect(const orbfe_keypoint* kps1, int n1, const float* x3Dw1, c
 {
     if (!n || !sets || !models || !counts || (n1 > 0 && (!indices1 || !X3Dc1 || !X3Dc2 || !P1im1 || !P2im2 || !maxError1 || !maxError2)))
         return fail(ORBFE_ERR_INVALID, "orbfe_sim3_inspect: null output");
-    Sim3HostCall c{};
-    c.kps1 = kps1; c.n1 = n1; c.x1 = x3Dw1; c.v1 = valid1; c.Tcw1 = Tcw1; c.K1 = K4_1;
-    c.kps2 = kps2; c.n2 = n2; c.x2 = x3Dw2; c.v2 = valid2; c.Tcw2 = Tcw2; c.K2 = K4_2;
-    c.m12 = match12; c.ls2 = level_sigma2; c.nlevels = nlevels; c.fix_scale = fix_scale; c.probability = probability;
-    c.min_inliers = min_inliers; c.max_iterations = max_iterations; c.first = first_iteration; c.n_iterations = n_iterations;
-    c.best_in = best_inliers_in; c.words = rand_words; c.res = res; c.inl = inliers12;
+    Sim3HostCall c = solve_call(kps1, n1, x3Dw1, valid1, Tcw1, K4_1, kps2, n2, x3Dw2, valid2, Tcw2, K4_2, match12, level_sigma2, nlevels,
+                                        fix_scale, probability, min_inliers, max_iterations, first_iteration, n_iterations, best_inliers_in,
+                                        rand_words, res, inliers12);
     c.inspect = true; c.n_out = n; c.indices1 = indices1; c.X3Dc1 = X3Dc1; c.X3Dc2 = X3Dc2; c.P1im1 = P1im1; c.P2im2 = P2im2;
     c.maxError1 = maxError1; c.maxError2 = maxError2; c.sets = sets; c.models = models; c.counts = counts;
     return sim3_host_call(c, device, "orbfe_sim3_inspect");
@@ -741,7 +722,7 @@ int orbfe_sim3_solve_batch_device(const orbfe_keypoint* d_kps, const int32_t* d_
     int rc = check_common(name, K4, K4, level_sigma2, nlevels, probability, min_inliers, max_iterations);
     if (rc) return rc;
     const hipStream_t s = (hipStream_t)stream;
-    Sim3Workspace& w = sim3_spaces().get(s);
+    HostStage& w = tl_stages.get(s);
     Sim3Args a{};
     a.kps = d_kps; a.nk = d_n; a.x3Dw = d_x3Dw; a.valid = d_valid; a.Tcw = d_Tcw; a.pair1 = d_pair1; a.pair2 = d_pair2;
     a.m12 = d_match12; a.words = d_rand_words;

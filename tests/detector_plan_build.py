@@ -1,13 +1,11 @@
 """Builds tests/detector_plan_driver.cpp (csrc/detector_plan.hpp behind a C ABI) with g++ and loads it with ctypes (test
 infrastructure, in the manner of tests/extractor_plan_build.py).  One build per process, in a temporary directory."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+import ref_build
+
 _lib = None
 
 SCALAR_FIELDS = ("win", "wpr", "npyr", "lds_bits_words", "relay_tbits", "relay_kshift", "relay_global", "relay_kcap", "ct_segcap", "ct_hbits",
@@ -19,11 +17,7 @@ MAXLEVELS = 16
 def lib():
     global _lib
     if _lib is None:
-        out = tempfile.mkdtemp(prefix="detector_plan_")
-        so = os.path.join(out, "detector_plan_driver.so")
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Werror",
-                               os.path.join(HERE, "detector_plan_driver.cpp"), "-o", so])
-        L = C.CDLL(so)
+        L = ref_build.build_shared("detector_plan_driver.cpp", std="c++17", prefix="detector_plan_")
         vp, i32, i64 = C.c_void_p, C.c_int, C.c_longlong
         L.dplan_make.argtypes = [i32, i32, i32, i32, i32, i32, i32, i64, vp, vp, vp, i32, vp, i32]
         L.dplan_threshold_sweep.argtypes = [i32, i32, i32, vp]

@@ -1,13 +1,11 @@
 """Builds tests/extractor_plan_driver.cpp (csrc/extractor_plan.hpp behind a C ABI) with g++ and loads it with ctypes (test
 infrastructure, in the manner of tests/initializer_build.py).  One build per process, in a temporary directory."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+import ref_build
+
 _lib = None
 
 LEVEL_FIELDS = ("w", "h", "nCols", "nRows", "wCell", "hCell", "ncells", "quota", "nIni", "out_cap", "resize_tab_ok", "blur_strips")
@@ -17,11 +15,7 @@ SCALAR_FIELDS = ("nodecap", "veccap", "keycap_lds", "max_wcell", "max_hcell", "m
 def lib():
     global _lib
     if _lib is None:
-        out = tempfile.mkdtemp(prefix="extractor_plan_")
-        so = os.path.join(out, "extractor_plan_driver.so")
-        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Werror",
-                               os.path.join(HERE, "extractor_plan_driver.cpp"), "-o", so])
-        L = C.CDLL(so)
+        L = ref_build.build_shared("extractor_plan_driver.cpp", std="c++17", prefix="extractor_plan_")
         vp, i32 = C.c_void_p, C.c_int
         L.xplan_make.argtypes = [i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32]
         L.xplan_blur_sweep.argtypes = [i32, i32, vp]

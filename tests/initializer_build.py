@@ -1,18 +1,14 @@
 """Builds tests/initializer_ref.cpp (the CPU restatement of ORB_SLAM2::Initializer) with g++ and loads it with ctypes (test
 infrastructure, in the manner of tests/shim_build.py).  One build per process, in a temporary directory."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
+import ref_build
+from oracle_lib import KP_DTYPE
+
 _lib = None
 
-KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
-                     ("octave", "<i4"), ("class_id", "<i4")])
 RESULT_DTYPE = np.dtype([("initialized", "<i4"), ("model", "<i4"), ("SH", "<f4"), ("SF", "<f4"), ("RH", "<f4"),
                          ("best_h", "<i4"), ("best_f", "<i4"), ("H21", "<f4", 9), ("F21", "<f4", 9), ("R21", "<f4", 9),
                          ("t21", "<f4", 3), ("n_good", "<i4"), ("parallax", "<f4")])
@@ -21,11 +17,7 @@ RESULT_DTYPE = np.dtype([("initialized", "<i4"), ("model", "<i4"), ("SH", "<f4")
 def lib():
     global _lib
     if _lib is None:
-        out = tempfile.mkdtemp(prefix="initializer_ref_")
-        so = os.path.join(out, "initializer_ref.so")
-        subprocess.check_call(["g++", "-std=c++14", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Werror",
-                               os.path.join(HERE, "initializer_ref.cpp"), "-o", so])
-        L = C.CDLL(so)
+        L = ref_build.build_shared("initializer_ref.cpp")
         vp, i32, f32 = C.c_void_p, C.c_int, C.c_float
         L.ref_initialize.argtypes = [vp, i32, vp, i32, vp, vp, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.ref_initialize_use_aruco.argtypes = [vp, i32, vp, i32, vp, vp, f32, vp, i32, vp, vp, vp, vp, vp]

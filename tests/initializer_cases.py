@@ -3,8 +3,7 @@ keypoint noise, a share of outlier matches, and unmatched keypoints in both fram
 the matches, as in the reference)."""
 import numpy as np
 
-KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
-                     ("octave", "<i4"), ("class_id", "<i4")])
+from oracle_lib import KP_DTYPE  # noqa: F401  (the scene modules take it from here)
 K = np.array([[500.0, 0, 320.0], [0, 500.0, 240.0], [0, 0, 1]], np.float32)
 COLS, ROWS = 640, 480
 

@@ -1,17 +1,14 @@
 """Builds tests/pose_opt_ref.cpp (the CPU restatement of ORB_SLAM2's motion-only pose optimization) with g++ and loads it with
 ctypes (test infrastructure, in the manner of tests/initializer_build.py).  One build per process, in a temporary directory."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+import ref_build
+from oracle_lib import KP_DTYPE
+
 _lib = None
 
-KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
-                     ("octave", "<i4"), ("class_id", "<i4")])
 MARKER_DTYPE = np.dtype([("corners", "<f4", 8), ("Twm", "<f4", 12), ("local", "<f4", 12)])
 RESULT_DTYPE = np.dtype([("n_good", "<i4"), ("n_initial", "<i4"), ("n_marker_edges", "<i4"), ("rounds", "<i4"),
                          ("n_bad", "<i4", 4), ("iterations", "<i4", 4), ("stale_mask", "<i4"), ("status", "<i4")])
@@ -20,11 +17,7 @@ RESULT_DTYPE = np.dtype([("n_good", "<i4"), ("n_initial", "<i4"), ("n_marker_edg
 def lib():
     global _lib
     if _lib is None:
-        out = tempfile.mkdtemp(prefix="pose_opt_ref_")
-        so = os.path.join(out, "pose_opt_ref.so")
-        subprocess.check_call(["g++", "-std=c++14", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Werror",
-                               os.path.join(HERE, "pose_opt_ref.cpp"), "-o", so])
-        L = C.CDLL(so)
+        L = ref_build.build_shared("pose_opt_ref.cpp")
         vp, i32, f32 = C.c_void_p, C.c_int, C.c_float
         L.ref_pose_optimization.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, i32, f32, vp, vp, vp, vp, vp]
         L.ref_pose_optimization.restype = i32

@@ -1,17 +1,14 @@
 """Builds tests/sim3_ref.cpp (the CPU restatement of ORB_SLAM2::Sim3Solver) with g++ and loads it with ctypes (test infrastructure,
 in the manner of tests/initializer_build.py).  One build per process, in a temporary directory."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
+import ref_build
+from oracle_lib import KP_DTYPE
+
 _lib = None
 
-KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
-                     ("octave", "<i4"), ("class_id", "<i4")])
 RESULT_DTYPE = np.dtype([("n", "<i4"), ("max_iterations", "<i4"), ("no_more", "<i4"), ("found", "<i4"), ("n_inliers", "<i4"),
                          ("best", "<i4"), ("best_inliers", "<i4"), ("s12", "<f4"), ("R12", "<f4", 9), ("t12", "<f4", 3),
                          ("T12", "<f4", 16), ("status", "<i4")])
@@ -20,11 +17,7 @@ RESULT_DTYPE = np.dtype([("n", "<i4"), ("max_iterations", "<i4"), ("no_more", "<
 def lib():
     global _lib
     if _lib is None:
-        out = tempfile.mkdtemp(prefix="sim3_ref_")
-        so = os.path.join(out, "sim3_ref.so")
-        subprocess.check_call(["g++", "-std=c++14", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-Wall", "-Werror",
-                               os.path.join(HERE, "sim3_ref.cpp"), "-o", so])
-        L = C.CDLL(so)
+        L = ref_build.build_shared("sim3_ref.cpp")
         vp, i32 = C.c_void_p, C.c_int
         side = [vp, i32, vp, vp, vp, vp]
         L.ref_sim3.argtypes = side + side + [vp, vp, i32, i32, C.c_double, i32, i32, i32, i32, i32, vp] + [vp] * 13

@@ -130,6 +130,9 @@ def test_fast_score_is_largest_threshold_still_a_corner(oracle):
 
 
 def test_quadtree_small_cases(oracle):
+    # the one keypoint record of tests/ (the restatements and the scene modules import it) is the library binding's, field for field
+    from orb_slam2_aruco_amd import binding
+    assert oracle.KP_DTYPE == binding.KP_DTYPE and oracle.KP_DTYPE.descr == binding.KP_DTYPE.descr
     kp = np.zeros(6, oracle.KP_DTYPE)
     kp["x"] = [10, 300, 20, 500, 310, 305]
     kp["y"] = [10, 20, 300, 400, 25, 22]
