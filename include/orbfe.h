@@ -277,7 +277,9 @@ int orbfe_search_by_projection_batch_status(void* stream, int32_t* overflow);
 /* Scratch of the matching entry points is kept per (calling thread, device, stream) so that Tracking / LocalMapping / LoopClosing
  * calls do not serialise on each other.  Reuse a small fixed set of streams: at most 16 (device, stream) slots are kept per thread,
  * least recently used first out.  Before destroying a stream that was handed to a `_device` matching call, release its scratch
- * (grown candidate strides, unread overflow flags) so that a new stream at the same address starts clean.  Synchronises `stream`. */
+ * (grown candidate strides, unread overflow flags) so that a new stream at the same address starts clean.  Synchronises `stream`.
+ * The host-pointer matching calls run on a stream of their own and keep their scratch under it: releasing NULL (the null stream)
+ * does not drop it, it goes when the calling thread exits. */
 int orbfe_release_stream_scratch(void* stream);
 
 /* ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, th, bMono) (src/ORBmatcher.cc:1332-1474; what

@@ -17,6 +17,7 @@
 #include <string>
 #include <vector>
 
+#include "host_stage.hpp"
 #include "orbfe_common.hpp"
 #include "wave_dpp.hpp"
 
@@ -373,37 +374,35 @@ __global__ __launch_bounds__(SB_THREADS) void k_search_by_bow(BowFrames F, const
     if (threadIdx.x == 0) nmatches[p] = s_nm;
 }
 
-struct BowMatchWorkspace {
-    DevBuf kps, desc, valid, n, fn, fo, ff, nf, m12, m21, nm;
-};
-thread_local ThreadWorkspaces<BowMatchWorkspace> tl_bow_ws; // per (thread, device): host-pointer entry points only
-
 // one frame of a host-pointer BoW search: keypoints, descriptors and its FeatureVector (nfv nodes)
 struct BowHostFrame {
     const orbfe_keypoint* kps; const uint8_t* desc; int n;
     const uint32_t* fv_node; const int32_t* fv_offset; const uint32_t* fv_feature; int nfv;
 };
 
-// stages the two frames of a host-pointer BoW search in w as the batch layout of one pair (frame 1 in block 0, frame 2 in block 1
-// of `cap` keypoints) with their per-keypoint flags (2 cap bytes)
-int bow_stage_pair(BowMatchWorkspace& w, const BowHostFrame (&f)[2], int cap, const uint8_t* flags)
+// A host-pointer BoW search in the matcher's stage: the two frames as the batch layout of one pair (frame 1 in block 0, frame 2 in
+// block 1 of `cap` keypoints), their per-keypoint flags (2 cap bytes, set: the caller clears what it must), `extra` floats of the
+// caller, and the results.
+struct BowPairIo {
+    size_t kps, desc, flags, n, fn, fo, ff, nf, extra, m12, m21, nm;
+};
+int bow_stage_pair(HostStage& w, const BowHostFrame (&f)[2], int cap, int extra_floats, BowPairIo& o)
 {
-    const size_t C = (size_t)cap;
-    int rc;
-    if ((rc = w.kps.ensure(2 * C * sizeof(orbfe_keypoint))) || (rc = w.desc.ensure(2 * C * 32)) || (rc = w.valid.ensure(2 * C)) ||
-        (rc = w.n.ensure(16)) || (rc = w.fn.ensure(2 * C * 4)) || (rc = w.fo.ensure(2 * (C + 1) * 4)) || (rc = w.ff.ensure(2 * C * 4)) ||
-        (rc = w.nf.ensure(16)) || (rc = w.m12.ensure(C * 4)) || (rc = w.m21.ensure(C * 4)) || (rc = w.nm.ensure(64)))
-        return rc;
+    const size_t C = (size_t)cap, kb = sizeof(orbfe_keypoint);
+    IoLayout l;
+    o.kps = l.take(2 * C * kb); o.desc = l.take(2 * C * 32); o.flags = l.take(2 * C); o.n = l.take(8); o.fn = l.take(2 * C * 4);
+    o.fo = l.take(2 * (C + 1) * 4); o.ff = l.take(2 * C * 4); o.nf = l.take(8); o.extra = l.take((size_t)extra_floats * 4);
+    l.outputs();
+    o.m12 = l.take(C * 4); o.m21 = l.take(C * 4); o.nm = l.take(4);
+    int rc = w.begin(l);
+    if (rc) return rc;
     const int32_t nn[2] = {f[0].n, f[1].n}, nf[2] = {f[0].nfv, f[1].nfv};
-    ORBFE_HIP(hipMemcpy(w.valid.p, flags, 2 * C, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.n.p, nn, 8, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.nf.p, nf, 8, hipMemcpyHostToDevice));
-    for (int i = 0; i < 2; i++) {
-        ORBFE_HIP(hipMemcpy(w.kps.as<orbfe_keypoint>() + i * C, f[i].kps, (size_t)f[i].n * sizeof(orbfe_keypoint), hipMemcpyHostToDevice));
-        ORBFE_HIP(hipMemcpy(w.desc.as<uint8_t>() + i * C * 32, f[i].desc, (size_t)f[i].n * 32, hipMemcpyHostToDevice));
-        ORBFE_HIP(hipMemcpy(w.fn.as<uint32_t>() + i * C, f[i].fv_node, (size_t)f[i].nfv * 4, hipMemcpyHostToDevice));
-        ORBFE_HIP(hipMemcpy(w.fo.as<int32_t>() + i * (C + 1), f[i].fv_offset, (size_t)(f[i].nfv + 1) * 4, hipMemcpyHostToDevice));
-        ORBFE_HIP(hipMemcpy(w.ff.as<uint32_t>() + i * C, f[i].fv_feature, (size_t)f[i].fv_offset[f[i].nfv] * 4, hipMemcpyHostToDevice));
+    memset(w.host<uint8_t>(o.flags), 1, 2 * C);
+    w.put(o.n, nn, 8); w.put(o.nf, nf, 8);
+    for (size_t i = 0; i < 2; i++) {
+        w.put(o.kps + i * C * kb, f[i].kps, (size_t)f[i].n * kb); w.put(o.desc + i * C * 32, f[i].desc, (size_t)f[i].n * 32);
+        w.put(o.fn + i * C * 4, f[i].fv_node, (size_t)f[i].nfv * 4); w.put(o.fo + i * (C + 1) * 4, f[i].fv_offset, (size_t)(f[i].nfv + 1) * 4);
+        w.put(o.ff + i * C * 4, f[i].fv_feature, (size_t)f[i].fv_offset[f[i].nfv] * 4);
     }
     return ORBFE_OK;
 }
@@ -715,22 +714,24 @@ int orbfe_search_for_triangulation(const orbfe_keypoint* kps1, const uint8_t* de
     if (n1 == 0 || n2 == 0 || nfv1 == 0 || nfv2 == 0) return ORBFE_OK;
     const int cap = std::max(n1, n2);
     if (cap > SB_MAX) return fail(ORBFE_ERR_CAPACITY, "orbfe_search_for_triangulation: at most %d features per frame", SB_MAX);
-    std::vector<uint8_t> freef(2 * (size_t)cap, 1); // "no map point yet" (:710-714, :731-735)
+    HostStage& w = match_host_stage();
+    const BowHostFrame f[2] = {{kps1, desc1, n1, fv_node1, fv_offset1, fv_feature1, nfv1}, {kps2, desc2, n2, fv_node2, fv_offset2, fv_feature2, nfv2}};
+    BowPairIo o;
+    if ((rc = bow_stage_pair(w, f, cap, 11, o))) return rc;
+    uint8_t* freef = w.host<uint8_t>(o.flags); // "no map point yet" (:710-714, :731-735)
     if (has_mp1) for (int i = 0; i < n1; i++) freef[i] = !has_mp1[i];
     if (has_mp2) for (int i = 0; i < n2; i++) freef[cap + i] = !has_mp2[i];
-    BowMatchWorkspace& w = tl_bow_ws.get();
-    const BowHostFrame f[2] = {{kps1, desc1, n1, fv_node1, fv_offset1, fv_feature1, nfv1}, {kps2, desc2, n2, fv_node2, fv_offset2, fv_feature2, nfv2}};
-    if ((rc = bow_stage_pair(w, f, cap, freef.data()))) return rc;
     const float fe[11] = {F12[0], F12[1], F12[2], F12[3], F12[4], F12[5], F12[6], F12[7], F12[8], ex, ey};
-    ORBFE_HIP(hipMemcpy(w.nm.as<float>() + 4, fe, sizeof fe, hipMemcpyHostToDevice));
-    rc = orbfe_search_for_triangulation_batch_device(w.kps.as<orbfe_keypoint>(), w.desc.as<uint8_t>(), w.valid.as<uint8_t>(), w.n.as<int32_t>(),
-                                                     w.fn.as<uint32_t>(), w.fo.as<int32_t>(), w.ff.as<uint32_t>(), w.nf.as<int32_t>(), cap, nullptr,
-                                                     nullptr, 1, w.nm.as<float>() + 4, w.nm.as<float>() + 13, scale_factors2, level_sigma2_2,
-                                                     nlevels, check_orientation, w.m12.as<int32_t>(), w.m21.as<int32_t>(), w.nm.as<int32_t>(),
-                                                     nullptr);
-    if (rc) return rc;
-    ORBFE_HIP(hipMemcpy(match12, w.m12.p, (size_t)n1 * 4, hipMemcpyDeviceToHost));
-    ORBFE_HIP(hipMemcpy(nmatches, w.nm.p, 4, hipMemcpyDeviceToHost));
+    w.put(o.extra, fe, sizeof fe);
+    if ((rc = w.upload()) ||
+        (rc = orbfe_search_for_triangulation_batch_device(w.dev<orbfe_keypoint>(o.kps), w.dev<uint8_t>(o.desc), w.dev<uint8_t>(o.flags),
+                                                          w.dev<int32_t>(o.n), w.dev<uint32_t>(o.fn), w.dev<int32_t>(o.fo), w.dev<uint32_t>(o.ff),
+                                                          w.dev<int32_t>(o.nf), cap, nullptr, nullptr, 1, w.dev<float>(o.extra),
+                                                          w.dev<float>(o.extra) + 9, scale_factors2, level_sigma2_2, nlevels, check_orientation,
+                                                          w.dev<int32_t>(o.m12), w.dev<int32_t>(o.m21), w.dev<int32_t>(o.nm), w.stream)) ||
+        (rc = w.download()) || (rc = w.sync()))
+        return rc;
+    w.get(match12, o.m12, (size_t)n1 * 4); w.get(nmatches, o.nm, 4);
     return ORBFE_OK;
 }
 
@@ -754,21 +755,19 @@ int orbfe_search_by_bow(const orbfe_keypoint* kps1, const uint8_t* desc1, const 
     if (n1 == 0 || n2 == 0 || nfv1 == 0 || nfv2 == 0) return ORBFE_OK;
     const int cap = std::max(n1, n2);
     if (cap > SB_MAX) return fail(ORBFE_ERR_CAPACITY, "orbfe_search_by_bow: at most %d features per frame", SB_MAX);
-    const bool any_valid = valid1 || valid2;
-    std::vector<uint8_t> valid(2 * (size_t)cap, 1);
-    if (valid1) memcpy(valid.data(), valid1, n1);
-    if (valid2) memcpy(valid.data() + cap, valid2, n2);
-    BowMatchWorkspace& w = tl_bow_ws.get();
+    HostStage& w = match_host_stage();
     const BowHostFrame f[2] = {{kps1, desc1, n1, fv_node1, fv_offset1, fv_feature1, nfv1}, {kps2, desc2, n2, fv_node2, fv_offset2, fv_feature2, nfv2}};
-    if ((rc = bow_stage_pair(w, f, cap, valid.data()))) return rc;
-    rc = orbfe_search_by_bow_batch_device(w.kps.as<orbfe_keypoint>(), w.desc.as<uint8_t>(), any_valid ? w.valid.as<uint8_t>() : nullptr,
-                                          w.n.as<int32_t>(), w.fn.as<uint32_t>(), w.fo.as<int32_t>(), w.ff.as<uint32_t>(), w.nf.as<int32_t>(),
-                                          cap, nullptr, nullptr, 1, valid2 != nullptr, nnratio, check_orientation, accept_max, factor,
-                                          w.m12.as<int32_t>(), w.m21.as<int32_t>(), w.nm.as<int32_t>(), nullptr);
-    if (rc) return rc;
-    ORBFE_HIP(hipMemcpy(match12, w.m12.p, (size_t)n1 * 4, hipMemcpyDeviceToHost));
-    ORBFE_HIP(hipMemcpy(match21, w.m21.p, (size_t)n2 * 4, hipMemcpyDeviceToHost));
-    ORBFE_HIP(hipMemcpy(nmatches, w.nm.p, 4, hipMemcpyDeviceToHost));
+    BowPairIo o;
+    if ((rc = bow_stage_pair(w, f, cap, 0, o))) return rc;
+    w.put(o.flags, valid1, (size_t)n1); w.put(o.flags + (size_t)cap, valid2, (size_t)n2);
+    if ((rc = w.upload()) ||
+        (rc = orbfe_search_by_bow_batch_device(w.dev<orbfe_keypoint>(o.kps), w.dev<uint8_t>(o.desc), valid1 || valid2 ? w.dev<uint8_t>(o.flags) : nullptr,
+                                               w.dev<int32_t>(o.n), w.dev<uint32_t>(o.fn), w.dev<int32_t>(o.fo), w.dev<uint32_t>(o.ff),
+                                               w.dev<int32_t>(o.nf), cap, nullptr, nullptr, 1, valid2 != nullptr, nnratio, check_orientation,
+                                               accept_max, factor, w.dev<int32_t>(o.m12), w.dev<int32_t>(o.m21), w.dev<int32_t>(o.nm), w.stream)) ||
+        (rc = w.download()) || (rc = w.sync()))
+        return rc;
+    w.get(match12, o.m12, (size_t)n1 * 4); w.get(match21, o.m21, (size_t)n2 * 4); w.get(nmatches, o.nm, 4);
     return ORBFE_OK;
 }
 

@@ -1,17 +1,20 @@
-// host_stage.hpp -- what the host-pointer entry points of the geometry solvers share (initializer.hip, sim3_solver.hip,
-// pose_optimizer.hip, orbfe_marker_poses): the layout of one staging block and the workspace that moves it.  Host code only.
+// host_stage.hpp -- what the host-pointer entry points of the geometry solvers (initializer.hip, sim3_solver.hip, pose_optimizer.hip,
+// orbfe_marker_poses) and of the matcher (match_kernels.hip, bow_vocabulary.hip, keyframe_io.hip) share: the layout of one staging
+// block and the workspace that moves it.  Host code only.
 #pragma once
 #include <cstddef>
 
 namespace orbfe {
 
-// Offsets of the arrays of one block, each 256-byte aligned, in the order they are taken: [inputs] outputs() [outputs].  The scratch
-// of a solver is a block without outputs(): only take() and end() mean something there.
+// Offsets of the arrays of one block, each 256-byte aligned, in the order they are taken: [inputs] inout() [in-out] outputs()
+// [outputs]; inout() is optional.  The scratch of a solver is a block without outputs(): only take() and end() mean something there.
 struct IoLayout {
-    size_t off = 0, split = 0;
+    size_t off = 0, split = 0, back = (size_t)-1;
     size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
+    void inout() { back = off; }      // what is taken from here to outputs() goes up and comes back (flags a kernel updates, a word it counts in)
     void outputs() { split = off; }   // what was taken so far goes up, what is taken from here on comes down
-    size_t end() const { return off; }   // upload range [0, split), download range [split, end())
+    size_t down() const { return back < split ? back : split; }
+    size_t end() const { return off; }   // upload range [0, split), download range [down(), end())
 };
 
 } // namespace orbfe
@@ -41,16 +44,22 @@ struct HostStage {
     }
     template <class T> T* dev(size_t o) const { return (T*)(io.as<uint8_t>() + o); }
     template <class T> T* host(size_t o) const { return (T*)(pinned.as<uint8_t>() + o); }
-    void put(size_t o, const void* src, size_t bytes) { if (bytes) memcpy(host<uint8_t>(o), src, bytes); }
+    // a host array that is absent (NULL) or empty is not copied, in either direction
+    void put(size_t o, const void* src, size_t bytes) { if (src && bytes) memcpy(host<uint8_t>(o), src, bytes); }
+    void get(void* dst, size_t o, size_t bytes) const { if (dst && bytes) memcpy(dst, host<uint8_t>(o), bytes); }
     int upload() { ORBFE_HIP(hipMemcpyAsync(io.p, pinned.p, lay.split, hipMemcpyHostToDevice, stream)); return ORBFE_OK; }
     int download()
     {
-        const size_t b = lay.split;
+        const size_t b = lay.down();
         ORBFE_HIP(hipMemcpyAsync(host<uint8_t>(b), dev<uint8_t>(b), lay.end() - b, hipMemcpyDeviceToHost, stream));
         return ORBFE_OK;
     }
     int sync() { ORBFE_HIP(hipStreamSynchronize(stream)); return ORBFE_OK; }
 };
+
+// The stage of the matcher's host-pointer calls, one per (thread, device): defined in match_kernels.hip, shared with
+// bow_vocabulary.hip and keyframe_io.hip.  The caller has selected the device already.
+HostStage& match_host_stage();
 
 } // namespace orbfe
 #endif

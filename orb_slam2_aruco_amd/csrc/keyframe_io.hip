@@ -4,6 +4,7 @@
 // Every offset in the file is a multiple of 4, so the records are moved as dwords.  Pure byte shuffling, HBM-bound:
 // a workgroup stages 256 records (17 KB) through LDS so that both the file side and the array side are read and written
 // as contiguous dwords; the stride of 17 dwords is odd, i.e. free of LDS bank conflicts.
+#include "host_stage.hpp"
 #include "orbfe_common.hpp"
 
 using namespace orbfe;
@@ -98,12 +99,6 @@ __global__ __launch_bounds__(KF_THREADS) void k_kf_pack(const uint32_t* __restri
     for (int j = threadIdx.x; j < cnt * KF_REC_DWORDS; j += KF_THREADS) dst[j] = s_rec[j];
 }
 
-struct KfWorkspace {
-    DevBuf file, kps, desc, mp, bad;
-};
-thread_local ThreadWorkspaces<KfWorkspace> tl_kf_ws; // per (thread, device): host-pointer entry points only
-KfWorkspace& kf_ws() { return tl_kf_ws.get(); }
-
 } // namespace
 
 extern "C" {
@@ -143,18 +138,20 @@ int orbfe_keyframe_features_pack(const orbfe_keypoint* kps, const uint8_t* desc,
     if (n < 0 || (n && (!kps || !desc || !out))) return fail(ORBFE_ERR_INVALID, "orbfe_keyframe_features_pack: invalid argument");
     int rc = use_device(device);
     if (rc || n == 0) return rc;
-    KfWorkspace& w = kf_ws();
+    HostStage& w = match_host_stage();
     const size_t N = (size_t)n;
-    if ((rc = w.file.ensure(N * ORBFE_KF_FEATURE_BYTES)) || (rc = w.kps.ensure(N * sizeof(orbfe_keypoint))) || (rc = w.desc.ensure(N * 32)) ||
-        (rc = w.mp.ensure(N * 8)))
+    IoLayout l;
+    const size_t i_kps = l.take(N * sizeof(orbfe_keypoint)), i_desc = l.take(N * 32), i_mp = l.take(mp_index ? N * 8 : 0);
+    l.outputs();
+    const size_t o_file = l.take(N * ORBFE_KF_FEATURE_BYTES);
+    if ((rc = w.begin(l))) return rc;
+    w.put(i_kps, kps, N * sizeof(orbfe_keypoint)); w.put(i_desc, desc, N * 32); w.put(i_mp, mp_index, N * 8);
+    if ((rc = w.upload()) ||
+        (rc = orbfe_keyframe_features_pack_device(w.dev<orbfe_keypoint>(i_kps), w.dev<uint8_t>(i_desc), mp_index ? w.dev<uint64_t>(i_mp) : nullptr,
+                                                  nullptr, nullptr, 1, n, w.dev<uint8_t>(o_file), w.stream)) ||
+        (rc = w.download()) || (rc = w.sync()))
         return rc;
-    ORBFE_HIP(hipMemcpy(w.kps.p, kps, N * sizeof(orbfe_keypoint), hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.desc.p, desc, N * 32, hipMemcpyHostToDevice));
-    if (mp_index) ORBFE_HIP(hipMemcpy(w.mp.p, mp_index, N * 8, hipMemcpyHostToDevice));
-    if ((rc = orbfe_keyframe_features_pack_device(w.kps.as<orbfe_keypoint>(), w.desc.as<uint8_t>(), mp_index ? w.mp.as<uint64_t>() : nullptr,
-                                                  nullptr, nullptr, 1, n, w.file.as<uint8_t>(), nullptr)))
-        return rc;
-    ORBFE_HIP(hipMemcpy(out, w.file.p, N * ORBFE_KF_FEATURE_BYTES, hipMemcpyDeviceToHost));
+    w.get(out, o_file, N * ORBFE_KF_FEATURE_BYTES);
     return ORBFE_OK;
 }
 
@@ -163,22 +160,25 @@ int orbfe_keyframe_features_unpack(const uint8_t* in, int n, orbfe_keypoint* kps
     if (n < 0 || (n && (!in || !kps || !desc))) return fail(ORBFE_ERR_INVALID, "orbfe_keyframe_features_unpack: invalid argument");
     int rc = use_device(device);
     if (rc || n == 0) return rc;
-    KfWorkspace& w = kf_ws();
+    HostStage& w = match_host_stage();
     const size_t N = (size_t)n;
-    if ((rc = w.file.ensure(N * ORBFE_KF_FEATURE_BYTES)) || (rc = w.kps.ensure(N * sizeof(orbfe_keypoint))) || (rc = w.desc.ensure(N * 32)) ||
-        (rc = w.mp.ensure(N * 8)) || (rc = w.bad.ensure(16)))
+    IoLayout l;
+    const size_t i_file = l.take(N * ORBFE_KF_FEATURE_BYTES);
+    l.inout();
+    const size_t io_bad = l.take(4); // the kernel counts in it: goes up as zero, comes back with the results
+    l.outputs();
+    const size_t o_kps = l.take(N * sizeof(orbfe_keypoint)), o_desc = l.take(N * 32), o_mp = l.take(mp_index ? N * 8 : 0);
+    if ((rc = w.begin(l))) return rc;
+    const int32_t zero = 0;
+    w.put(i_file, in, N * ORBFE_KF_FEATURE_BYTES); w.put(io_bad, &zero, 4);
+    if ((rc = w.upload()) ||
+        (rc = orbfe_keyframe_features_unpack_device(w.dev<uint8_t>(i_file), nullptr, nullptr, 1, n, w.dev<orbfe_keypoint>(o_kps), w.dev<uint8_t>(o_desc),
+                                                    mp_index ? w.dev<uint64_t>(o_mp) : nullptr, w.dev<int32_t>(io_bad), w.stream)) ||
+        (rc = w.download()) || (rc = w.sync()))
         return rc;
-    ORBFE_HIP(hipMemcpy(w.file.p, in, N * ORBFE_KF_FEATURE_BYTES, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemset(w.bad.p, 0, 4));
-    if ((rc = orbfe_keyframe_features_unpack_device(w.file.as<uint8_t>(), nullptr, nullptr, 1, n, w.kps.as<orbfe_keypoint>(), w.desc.as<uint8_t>(),
-                                                    mp_index ? w.mp.as<uint64_t>() : nullptr, w.bad.as<int32_t>(), nullptr)))
-        return rc;
-    int32_t bad = 0;
-    ORBFE_HIP(hipMemcpy(&bad, w.bad.p, 4, hipMemcpyDeviceToHost));
+    const int32_t bad = *w.host<const int32_t>(io_bad);
     if (bad) return fail(ORBFE_ERR_INVALID, "orbfe_keyframe_features_unpack: %d records with a descriptor length other than 32", bad);
-    ORBFE_HIP(hipMemcpy(kps, w.kps.p, N * sizeof(orbfe_keypoint), hipMemcpyDeviceToHost));
-    ORBFE_HIP(hipMemcpy(desc, w.desc.p, N * 32, hipMemcpyDeviceToHost));
-    if (mp_index) ORBFE_HIP(hipMemcpy(mp_index, w.mp.p, N * 8, hipMemcpyDeviceToHost));
+    w.get(kps, o_kps, N * sizeof(orbfe_keypoint)); w.get(desc, o_desc, N * 32); w.get(mp_index, o_mp, N * 8);
     return ORBFE_OK;
 }
 

@@ -1293,23 +1293,22 @@ __global__ __launch_bounds__(256) void k_distinctive(const uint8_t* __restrict__
     if (best_desc && lane < 8) reinterpret_cast<uint32_t*>(best_desc)[(size_t)p * 8 + lane] = reinterpret_cast<const uint32_t*>(D)[(size_t)best * 8 + lane];
 }
 
+// The kernels' scratch: the partials of knn2_launch, the grid records and pools of sfi_launch, the rows of sbp_launch.
 struct MatchWorkspace {
-    DevBuf pidx, pbest, psecond, csr_cnt, csr_idx, csr_dist, scratch, prev;
+    DevBuf pidx, pbest, psecond, csr_cnt, csr_idx, csr_dist, scratch;
     DevBuf sbp_batch_overflow; // flag of the _batch_device searches: sticky until orbfe_search_by_projection_batch_status reads it
     DevBuf sfi_overflow;  // SearchForInitialization's two flag words: zeroed when allocated and whenever they are read (no memset launch per batch)
-    DevBuf sbp_host;      // the host-pointer projection searches: inputs and results of one call, in slices (sbp_host_run)
-    DevBuf q, t, nt, oidx, obest, osecond, kps, desc, nk, m12, nm;
+    DevBuf q, obest;      // orbfe_fuse_search_batch_device: the projected queries, the result arrays nobody asked for
     int csr_per_pair = 0; // candidate pool entries per frame pair of SearchForInitialization (grown on overflow)
     int sbp_stride = 0;   // candidate row stride of k_search_by_projection_batch (grown on overflow)
-    // host-pointer SearchForInitialization: a stream of its own (the null stream synchronises with every blocking stream of the
-    // process) and page-locked staging, so that a call is a few queued copies and one wait
-    hipStream_t host_stream = nullptr;
-    PinnedBuf pinned;
-    ~MatchWorkspace() { if (host_stream) (void)hipStreamDestroy(host_stream); }
 };
-// one workspace per (thread, device, stream): see ThreadWorkspaces.  The host-pointer entry points run on the null stream.
+// one workspace per (thread, device, stream): see ThreadWorkspaces.  A _batch_device call takes the one of the caller's stream, a
+// host-pointer call the one of its stage's stream, so the two never share buffers, pool size or row stride.
 static thread_local ThreadWorkspaces<MatchWorkspace> tl_ws;
-static MatchWorkspace& ws(hipStream_t s = nullptr) { return tl_ws.get(s); }
+static MatchWorkspace& ws(hipStream_t s) { return tl_ws.get(s); }
+// the stage of the host-pointer calls of this file, bow_vocabulary.hip and keyframe_io.hip (host_stage.hpp)
+static thread_local ThreadWorkspaces<HostStage> tl_stage;
+HostStage& match_host_stage() { return tl_stage.get(); }
 // a capacity flag that is zeroed once, when it is allocated, and again only by the status call that reads it
 static int ensure_sticky_flag(DevBuf& b)
 {
@@ -1428,13 +1427,11 @@ static int sfi_launch(const orbfe_keypoint* d_kps, const uint8_t* d_desc, const 
     return ORBFE_OK;
 }
 
-// reads and clears the two flag words after the stream has drained; *need = 0, the level-0 count that does not fit (an error), or
-// the pool size a pair needed (the pool is grown: repeat the call)
-static int sfi_read_flags(MatchWorkspace& w, int32_t* need)
+// takes the two flag words f, read after stream s has drained, and clears them behind it; *need = 0, the level-0 count that does not
+// fit (an error), or the pool size a pair needed (the pool is grown: repeat the call)
+static int sfi_take_flags(MatchWorkspace& w, const int32_t* f, hipStream_t s, int32_t* need)
 {
-    int32_t f[2] = {0, 0};
-    ORBFE_HIP(hipMemcpy(f, w.sfi_overflow.p, 8, hipMemcpyDeviceToHost));
-    if (f[0] || f[1]) ORBFE_HIP(hipMemset(w.sfi_overflow.p, 0, 8)); // sticky until read
+    if (f[0] || f[1]) ORBFE_HIP(hipMemsetAsync(w.sfi_overflow.p, 0, 8, s)); // sticky until read
     *need = std::max(f[0], f[1]);
     if (f[0] > SFI_MAXL0) return fail(ORBFE_ERR_CAPACITY, "%d level-0 keypoints in a frame exceed the supported %d", f[0], SFI_MAXL0);
     if (f[1] > w.csr_per_pair) w.csr_per_pair = (f[1] + 1023) / 1024 * 1024; // the next batch on this stream has the room
@@ -1470,37 +1467,6 @@ static int sbp_launch(MatchWorkspace& w, SbpBatch B, int nframes, float4 bnd, in
     return ORBFE_OK;
 }
 
-// a host array that may be absent (NULL) or empty: copied when it is there
-static int upload(void* d, const void* h, size_t bytes)
-{
-    if (h && bytes) ORBFE_HIP(hipMemcpy(d, h, bytes, hipMemcpyHostToDevice));
-    return ORBFE_OK;
-}
-static int download(void* h, const void* d, size_t bytes)
-{
-    if (h && bytes) ORBFE_HIP(hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost));
-    return ORBFE_OK;
-}
-
-// uploads n map points (in w.scratch) and leaves their queries in d_q, on the null stream
-static int project_run(MatchWorkspace& w, const float* p3Dw, const uint8_t* valid, const float* min_dist, const float* max_dist,
-                       const float* normal, int n, const ProjectParams& P, SbpQuery* d_q)
-{
-    const size_t N = (size_t)n;
-    int rc;
-    if ((rc = w.scratch.ensure(N * (12 + 4 + 4 + 12 + 1)))) return rc;
-    float* d_p = w.scratch.as<float>();
-    float *d_min = d_p + 3 * N, *d_max = d_min + N, *d_nrm = d_max + N;
-    uint8_t* d_valid = reinterpret_cast<uint8_t*>(d_nrm + 3 * N);
-    if ((rc = upload(d_p, p3Dw, N * 12)) || (rc = upload(d_min, min_dist, N * 4)) || (rc = upload(d_max, max_dist, N * 4)) ||
-        (rc = upload(d_nrm, normal, N * 12)) || (rc = upload(d_valid, valid, N)))
-        return rc;
-    hipLaunchKernelGGL(k_project_map_points, dim3((n + 255) / 256), dim3(256), 0, 0, d_p, valid ? d_valid : nullptr, d_min, d_max,
-                       normal ? d_nrm : nullptr, n, P, d_q);
-    ORBFE_HIP(hipGetLastError());
-    return ORBFE_OK;
-}
-
 // One host-pointer search of one frame (orbfe_search_by_projection and the entry points after it).  Host arrays: a NULL input is
 // absent, a NULL output is not copied back.
 struct SbpHostCall {
@@ -1519,68 +1485,73 @@ struct SbpHostCall {
     uint8_t* taken_out;            // the taken flags after the search
 };
 
-// stages the call in w.sbp_host, builds or uploads the queries, searches (a second time, with a longer row stride, after an
-// overflow) and copies the results back; the null stream, one device synchronisation per search
+// stages the call in the matcher's stage, builds or uploads the queries, searches and fetches the results: one upload, the kernels,
+// one download, one synchronisation.  The taken flags and the two count words travel both ways: a search marks keypoints taken and
+// raises the overflow word, which goes up as zero.  After an overflow the whole sequence runs a second time with a longer row
+// stride, from the caller's flags again.
 static int sbp_host_run(const SbpHostCall& c)
 {
-    MatchWorkspace& w = ws();
-    const size_t n = (size_t)c.n, nq = (size_t)c.nq;
+    HostStage& w = match_host_stage();
+    const size_t n = (size_t)c.n, nq = (size_t)c.nq, kb = sizeof(orbfe_keypoint);
     IoLayout l;
-    const size_t s_kps = l.take(n * sizeof(orbfe_keypoint)), s_desc = l.take(n * 32), s_taken = l.take(n), s_cur = l.take(n * 4);
-    const size_t s_q = l.take(nq * sizeof(SbpQuery)), s_qdesc = l.take(nq * 32), s_obs = l.take(nq), s_angle = l.take(nq * 4);
-    const size_t s_x3 = l.take(nq * 12), s_last = l.take(nq * sizeof(orbfe_keypoint)), s_valid = l.take(nq), s_cam = l.take((12 + 16) * 4);
-    const size_t s_out = l.take(nq * 4 * 7), s_cnt = l.take(8); // best_idx .. second_level, match, qbin | nmatches, overflow
-    int rc = w.sbp_host.ensure(l.end());
+    const size_t s_kps = l.take(n * kb), s_desc = l.take(n * 32), s_q = l.take(nq * sizeof(SbpQuery)), s_qdesc = l.take(nq * 32);
+    const size_t s_obs = l.take(nq), s_angle = l.take(nq * 4), s_x3 = l.take(nq * 12), s_valid = l.take(nq);
+    const size_t s_last = l.take(c.kps_last ? nq * kb : 0), s_cam = l.take(c.kps_last ? (12 + 16) * 4 : 0);
+    const size_t s_min = l.take(c.P ? nq * 4 : 0), s_max = l.take(c.P ? nq * 4 : 0), s_nrm = l.take(c.P ? nq * 12 : 0);
+    l.inout();
+    const size_t s_taken = l.take(n), s_cnt = l.take(8); // nmatches, overflow
+    l.outputs();
+    const size_t s_cur = l.take(n * 4), s_out = l.take(nq * 4 * 7); // best_idx .. second_level, match, qbin
+    int rc = w.begin(l);
     if (rc) return rc;
-    uint8_t* b = w.sbp_host.as<uint8_t>();
-    int32_t* o = reinterpret_cast<int32_t*>(b + s_out);
+    const hipStream_t s = w.stream;
+    MatchWorkspace& m = ws(s);
+    int32_t* o = w.dev<int32_t>(s_out);
     SbpBatch B{};
-    B.kps = reinterpret_cast<const orbfe_keypoint*>(b + s_kps); B.desc = b + s_desc; B.capacity = c.n;
-    B.queries = reinterpret_cast<const SbpQuery*>(b + s_q); B.qdesc = b + s_qdesc; B.qcapacity = c.nq;
-    B.taken = c.taken ? b + s_taken : nullptr; B.q_observed = c.q_observed ? b + s_obs : nullptr;
-    B.q_angle = c.q_angle || c.kps_last ? reinterpret_cast<float*>(b + s_angle) : nullptr;
+    B.kps = w.dev<const orbfe_keypoint>(s_kps); B.desc = w.dev<const uint8_t>(s_desc); B.capacity = c.n;
+    B.queries = w.dev<const SbpQuery>(s_q); B.qdesc = w.dev<const uint8_t>(s_qdesc); B.qcapacity = c.nq;
+    B.taken = c.taken ? w.dev<uint8_t>(s_taken) : nullptr; B.q_observed = c.q_observed ? w.dev<const uint8_t>(s_obs) : nullptr;
+    B.q_angle = c.q_angle || c.kps_last ? w.dev<const float>(s_angle) : nullptr;
     if (c.best_idx) { B.best_idx = o; B.best_dist = o + nq; B.best_level = o + 2 * nq; B.second_dist = o + 3 * nq; B.second_level = o + 4 * nq; }
-    B.match = o + 5 * nq; B.qbin = o + 6 * nq; B.match_cur = reinterpret_cast<int32_t*>(b + s_cur);
-    B.nmatches = reinterpret_cast<int32_t*>(b + s_cnt); B.overflow = B.nmatches + 1;
+    B.match = o + 5 * nq; B.qbin = o + 6 * nq; B.match_cur = w.dev<int32_t>(s_cur);
+    B.nmatches = w.dev<int32_t>(s_cnt); B.overflow = B.nmatches + 1;
     if (c.chi2 > 0.0) { B.chi2 = c.chi2; for (int l = 0; l < 16; l++) B.inv_sigma2[l] = c.inv_sigma2[std::min(l, c.nlevels - 1)]; }
-    if ((rc = upload(b + s_kps, c.kps, n * sizeof(orbfe_keypoint))) || (rc = upload(b + s_desc, c.desc, n * 32)) ||
-        (rc = upload(b + s_qdesc, c.qdesc, nq * 32)) || (rc = upload(b + s_obs, c.q_observed, nq)) || (rc = upload(b + s_angle, c.q_angle, nq * 4)))
-        return rc;
-    SbpQuery* d_q = reinterpret_cast<SbpQuery*>(b + s_q);
-    if (c.window) rc = upload(d_q, c.window, nq * sizeof(orbfe_window_query));
-    else if (c.P) rc = project_run(w, c.x3Dw, c.valid, c.min_dist, c.max_dist, c.normal, c.nq, *c.P, d_q);
-    else {
+    w.put(s_kps, c.kps, n * kb); w.put(s_desc, c.desc, n * 32);
+    w.put(s_q, c.window, nq * sizeof(orbfe_window_query)); w.put(s_qdesc, c.qdesc, nq * 32);
+    w.put(s_obs, c.q_observed, nq); w.put(s_angle, c.q_angle, nq * 4);
+    w.put(s_x3, c.x3Dw, nq * 12); w.put(s_valid, c.valid, nq);
+    if (c.P) { w.put(s_min, c.min_dist, nq * 4); w.put(s_max, c.max_dist, nq * 4); w.put(s_nrm, c.normal, nq * 12); }
+    else if (c.kps_last) {
         float cam[12 + 16]; // Tcw, the scale factors
         memcpy(cam, c.Tcw, 48);
         for (int l = 0; l < 16; l++) cam[12 + l] = l < c.nlevels ? c.scale[l] : 0.0f;
-        if ((rc = upload(b + s_x3, c.x3Dw, nq * 12)) || (rc = upload(b + s_last, c.kps_last, nq * sizeof(orbfe_keypoint))) ||
-            (rc = upload(b + s_valid, c.valid, nq)) || (rc = upload(b + s_cam, cam, sizeof cam)))
-            return rc;
-        const float* d_cam = reinterpret_cast<const float*>(b + s_cam);
-        hipLaunchKernelGGL(k_project_last_frame, dim3((c.nq + 255) / 256), dim3(256), 0, 0, reinterpret_cast<const float*>(b + s_x3),
-                           c.valid ? b + s_valid : nullptr, reinterpret_cast<const orbfe_keypoint*>(b + s_last), c.nq, d_cam,
-                           make_float4(c.K4[0], c.K4[1], c.K4[2], c.K4[3]), c.bnd, d_cam + 12, c.nlevels, c.th, d_q,
-                           reinterpret_cast<float*>(b + s_angle));
-        ORBFE_HIP(hipGetLastError());
+        w.put(s_last, c.kps_last, nq * kb); w.put(s_cam, cam, sizeof cam);
     }
-    if (rc) return rc;
+    const uint8_t* d_valid = c.valid ? w.dev<const uint8_t>(s_valid) : nullptr;
     for (int attempt = 0;; attempt++) {
-        // a search marks keypoints taken: every attempt starts from the caller's flags
-        if ((rc = upload(b + s_taken, c.taken, n))) return rc;
-        ORBFE_HIP(hipMemset(B.overflow, 0, 4));
-        if ((rc = sbp_launch(w, B, 1, c.bnd, c.mode, c.th_high, c.nnratio, c.factor, c.check_ori, nullptr))) return rc;
-        ORBFE_HIP(hipDeviceSynchronize());
-        int32_t ovf = 0;
-        ORBFE_HIP(hipMemcpy(&ovf, B.overflow, 4, hipMemcpyDeviceToHost));
+        const int32_t zero[2] = {0, 0};
+        w.put(s_taken, c.taken, n); w.put(s_cnt, zero, 8);
+        if ((rc = w.upload())) return rc;
+        if (c.P)
+            hipLaunchKernelGGL(k_project_map_points, dim3((c.nq + 255) / 256), dim3(256), 0, s, w.dev<const float>(s_x3), d_valid,
+                               w.dev<const float>(s_min), w.dev<const float>(s_max), c.normal ? w.dev<const float>(s_nrm) : nullptr, c.nq, *c.P,
+                               w.dev<SbpQuery>(s_q));
+        else if (c.kps_last)
+            hipLaunchKernelGGL(k_project_last_frame, dim3((c.nq + 255) / 256), dim3(256), 0, s, w.dev<const float>(s_x3), d_valid,
+                               w.dev<const orbfe_keypoint>(s_last), c.nq, w.dev<const float>(s_cam), make_float4(c.K4[0], c.K4[1], c.K4[2], c.K4[3]),
+                               c.bnd, w.dev<const float>(s_cam) + 12, c.nlevels, c.th, w.dev<SbpQuery>(s_q), w.dev<float>(s_angle));
+        ORBFE_HIP(hipGetLastError());
+        if ((rc = sbp_launch(m, B, 1, c.bnd, c.mode, c.th_high, c.nnratio, c.factor, c.check_ori, s)) || (rc = w.download()) || (rc = w.sync()))
+            return rc;
+        const int32_t ovf = w.host<const int32_t>(s_cnt)[1];
         if (!ovf) break;
         if (attempt) return fail(ORBFE_ERR_CAPACITY, "candidate row overflow (%d)", ovf);
-        sbp_grow_stride(w, ovf);
+        sbp_grow_stride(m, ovf);
     }
     int32_t* const out[6] = {c.best_idx, c.best_dist, c.best_level, c.second_dist, c.second_level, c.match};
-    for (int k = 0; k < 6; k++)
-        if ((rc = download(out[k], o + k * nq, nq * 4))) return rc;
-    if ((rc = download(c.match_cur, B.match_cur, n * 4)) || (rc = download(c.nmatches, B.nmatches, 4))) return rc;
-    return download(c.taken_out, b + s_taken, n);
+    for (int k = 0; k < 6; k++) w.get(out[k], s_out + k * nq * 4, nq * 4);
+    w.get(c.match_cur, s_cur, n * 4); w.get(c.nmatches, s_cnt, 4); w.get(c.taken_out, s_taken, n);
+    return ORBFE_OK;
 }
 
 } // namespace orbfe
@@ -1661,21 +1632,20 @@ int orbfe_knn2(const uint8_t* Q, int nq, const uint8_t* T, int nt, int init, int
     int rc = use_device(device);
     if (rc) return rc;
     if (nq == 0) return ORBFE_OK;
-    MatchWorkspace& w = ws();
-    if ((rc = w.q.ensure((size_t)nq * 32)) || (rc = w.t.ensure((size_t)std::max(nt, 1) * 32)) ||
-        (rc = w.nt.ensure(16)) || (rc = w.oidx.ensure((size_t)nq * 4)) || (rc = w.obest.ensure((size_t)nq * 4)) ||
-        (rc = w.osecond.ensure((size_t)nq * 4)))
+    HostStage& w = match_host_stage();
+    const size_t Q4 = (size_t)nq * 4;
+    IoLayout l;
+    const size_t i_q = l.take((size_t)nq * 32), i_t = l.take((size_t)nt * 32), i_nt = l.take(4);
+    l.outputs();
+    const size_t o_idx = l.take(Q4), o_best = l.take(Q4), o_second = l.take(Q4);
+    if ((rc = w.begin(l))) return rc;
+    w.put(i_q, Q, (size_t)nq * 32); w.put(i_t, T, (size_t)nt * 32); w.put(i_nt, &nt, 4);
+    if ((rc = w.upload()) ||
+        (rc = knn2_launch(w.dev<const uint8_t>(i_q), nullptr, 0, nq, w.dev<const uint8_t>(i_t), w.dev<const int32_t>(i_nt), 0, nt, 1, init,
+                          w.dev<int32_t>(o_idx), w.dev<int32_t>(o_best), w.dev<int32_t>(o_second), w.stream)) ||
+        (rc = w.download()) || (rc = w.sync()))
         return rc;
-    ORBFE_HIP(hipMemcpy(w.q.p, Q, (size_t)nq * 32, hipMemcpyHostToDevice));
-    if (nt) ORBFE_HIP(hipMemcpy(w.t.p, T, (size_t)nt * 32, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.nt.p, &nt, 4, hipMemcpyHostToDevice));
-    rc = knn2_launch(w.q.as<uint8_t>(), nullptr, 0, nq, w.t.as<uint8_t>(), w.nt.as<int32_t>(), 0, nt, 1, init,
-                     w.oidx.as<int32_t>(), w.obest.as<int32_t>(), w.osecond.as<int32_t>(), nullptr);
-    if (rc) return rc;
-    ORBFE_HIP(hipDeviceSynchronize());
-    ORBFE_HIP(hipMemcpy(best_idx, w.oidx.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
-    ORBFE_HIP(hipMemcpy(best_dist, w.obest.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
-    ORBFE_HIP(hipMemcpy(second_dist, w.osecond.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
+    w.get(best_idx, o_idx, Q4); w.get(best_dist, o_best, Q4); w.get(second_dist, o_second, Q4);
     return ORBFE_OK;
 }
 
@@ -1699,7 +1669,9 @@ int orbfe_search_for_initialization_batch_status(void* stream, int32_t* overflow
     MatchWorkspace& w = ws(s);
     if (!w.sfi_overflow.p) return ORBFE_OK; // no batch on this (thread, device, stream) yet
     ORBFE_HIP(hipStreamSynchronize(s));
-    return sfi_read_flags(w, overflow);
+    int32_t f[2] = {0, 0};
+    ORBFE_HIP(hipMemcpy(f, w.sfi_overflow.p, 8, hipMemcpyDeviceToHost));
+    return sfi_take_flags(w, f, s, overflow);
 }
 
 int orbfe_search_for_initialization(const orbfe_keypoint* kps1, const uint8_t* desc1, int n1,
@@ -1714,65 +1686,45 @@ int orbfe_search_for_initialization(const orbfe_keypoint* kps1, const uint8_t* d
     if (rc) return rc;
     *nmatches = 0;
     if (n1 == 0) return ORBFE_OK;
-    const int cap = std::max(std::max(n1, n2), 1);
-    MatchWorkspace& w = ws();
-    if ((rc = w.kps.ensure((size_t)2 * cap * sizeof(orbfe_keypoint))) || (rc = w.desc.ensure((size_t)2 * cap * 32)) ||
-        (rc = w.nk.ensure(16)) || (rc = w.m12.ensure((size_t)cap * 4)) || (rc = w.nm.ensure(16)) ||
-        (rc = w.prev.ensure((size_t)cap * 8)))
-        return rc;
-    if (!w.host_stream) ORBFE_HIP(hipStreamCreateWithFlags(&w.host_stream, hipStreamNonBlocking));
-    hipStream_t s = w.host_stream;
-    // page-locked staging: in [kps1 | kps2 | desc1 | desc2 | n1, n2 | prev], out [m12 | prev | nmatches | 2 flag words]
-    const size_t kb = (size_t)cap * sizeof(orbfe_keypoint), db = (size_t)cap * 32;
-    const size_t i_kps = 0, i_desc = 2 * kb, i_nk = i_desc + 2 * db, i_prev = i_nk + 64, o_m12 = i_prev + (size_t)cap * 8;
-    const size_t o_prev = o_m12 + (size_t)cap * 4, o_nm = o_prev + (size_t)cap * 8, o_flags = o_nm + 16, o_end = o_flags + 16;
-    if ((rc = w.pinned.ensure(o_end))) return rc;
-    uint8_t* hp = w.pinned.as<uint8_t>();
-    memcpy(hp + i_kps, kps1, (size_t)n1 * sizeof(orbfe_keypoint));
-    memcpy(hp + i_desc, desc1, (size_t)n1 * 32);
-    if (n2) {
-        memcpy(hp + i_kps + kb, kps2, (size_t)n2 * sizeof(orbfe_keypoint));
-        memcpy(hp + i_desc + db, desc2, (size_t)n2 * 32);
-    }
+    const size_t cap = (size_t)std::max(std::max(n1, n2), 1), kb = cap * sizeof(orbfe_keypoint), db = cap * 32;
+    HostStage& w = match_host_stage();
+    // prev_matched travels both ways; the two flag words live in the kernels' workspace and come down to o_flags of the page-locked half
+    IoLayout l;
+    const size_t i_kps = l.take(2 * kb), i_desc = l.take(2 * db), i_nk = l.take(8);
+    l.inout();
+    const size_t io_prev = l.take(cap * 8);
+    l.outputs();
+    const size_t o_m12 = l.take(cap * 4), o_nm = l.take(4), o_flags = l.take(8);
+    if ((rc = w.begin(l))) return rc;
+    const hipStream_t s = w.stream;
+    MatchWorkspace& m = ws(s);
     const int32_t nn[2] = {n1, n2};
-    memcpy(hp + i_nk, nn, 8);
-    memcpy(hp + i_prev, prev_matched, (size_t)n1 * 8);
-    // the call's four inputs in one launch that reads the page-locked staging buffer, its four results in another (OutPack,
-    // orbfe_common.hpp: every small copy would be a blit kernel of its own)
-    {
-        OutPack ip;
-        ip.add(w.kps.p, hp + i_kps, 2 * kb);
-        ip.add(w.desc.p, hp + i_desc, 2 * db);
-        ip.add(w.nk.p, hp + i_nk, 8);
-        ip.add(w.prev.p, hp + i_prev, (size_t)n1 * 8);   // (with the other inputs: one launch less on the call's chain)
-        if ((rc = ip.flush<3>(s))) return rc;
-    }
+    w.put(i_kps, kps1, (size_t)n1 * sizeof(orbfe_keypoint)); w.put(i_kps + kb, kps2, (size_t)n2 * sizeof(orbfe_keypoint));
+    w.put(i_desc, desc1, (size_t)n1 * 32); w.put(i_desc + db, desc2, (size_t)n2 * 32);
+    w.put(i_nk, nn, 8);
     for (int attempt = 0;; attempt++) {
-        // the device copy of prev_matched is only overwritten by a run that did not overflow: a second attempt uploads it again
-        if (attempt) { OutPack ip; ip.add(w.prev.p, hp + i_prev, (size_t)n1 * 8); if ((rc = ip.flush<3>(s))) return rc; }
-        rc = sfi_launch(w.kps.as<orbfe_keypoint>(), w.desc.as<uint8_t>(), w.nk.as<int32_t>(), cap, 1, frame_bounds(cols, rows, bounds),
-                        window_size, nnratio, check_orientation, w.prev.as<float>(), w.prev.as<float>(),
-                        w.m12.as<int32_t>(), w.nm.as<int32_t>(), s, w);
-        if (rc) return rc;
-        // results and flags: copies queued behind the kernels, one wait
-        {
-            OutPack op;
-            op.add(hp + o_m12, w.m12.p, (size_t)n1 * 4);
-            op.add(hp + o_prev, w.prev.p, (size_t)n1 * 8);
-            op.add(hp + o_nm, w.nm.p, 4);
-            op.add(hp + o_flags, w.sfi_overflow.p, 8);
-            if ((rc = op.flush<3>(s))) return rc;
-        }
-        ORBFE_HIP(hipStreamSynchronize(s));
-        const int32_t* fl = reinterpret_cast<const int32_t*>(hp + o_flags);
+        // a run overwrites the device copy of prev_matched: every attempt starts from the caller's
+        w.put(io_prev, prev_matched, (size_t)n1 * 8);
+        if ((rc = w.upload()) ||
+            (rc = sfi_launch(w.dev<const orbfe_keypoint>(i_kps), w.dev<const uint8_t>(i_desc), w.dev<const int32_t>(i_nk), (int)cap, 1,
+                             frame_bounds(cols, rows, bounds), window_size, nnratio, check_orientation, w.dev<const float>(io_prev),
+                             w.dev<float>(io_prev), w.dev<int32_t>(o_m12), w.dev<int32_t>(o_nm), s, m)))
+            return rc;
+        // the download: the results and the flag words in ONE launch that writes the page-locked half (OutPack, orbfe_common.hpp:
+        // the flags are not part of the io block, and every small copy would be a blit kernel of its own)
+        OutPack op;
+        op.add(w.host<void>(o_m12), w.dev<void>(o_m12), (size_t)n1 * 4);
+        op.add(w.host<void>(io_prev), w.dev<void>(io_prev), (size_t)n1 * 8);
+        op.add(w.host<void>(o_nm), w.dev<void>(o_nm), 4);
+        op.add(w.host<void>(o_flags), m.sfi_overflow.p, 8);
+        if ((rc = op.flush<3>(s)) || (rc = w.sync())) return rc;
+        const int32_t* fl = w.host<const int32_t>(o_flags);
         if (!fl[0] && !fl[1]) break;
         int32_t ovf = 0;
-        if ((rc = sfi_read_flags(w, &ovf))) return rc; // clears the flags, grows the pool
+        if ((rc = sfi_take_flags(m, fl, s, &ovf))) return rc; // clears the flags, grows the pool
         if (attempt) return fail(ORBFE_ERR_CAPACITY, "candidate pool overflow (%d)", ovf);
     }
-    memcpy(matches12, hp + o_m12, (size_t)n1 * 4);
-    memcpy(prev_matched, hp + o_prev, (size_t)n1 * 8);
-    memcpy(nmatches, hp + o_nm, 4);
+    w.get(matches12, o_m12, (size_t)n1 * 4); w.get(prev_matched, io_prev, (size_t)n1 * 8); w.get(nmatches, o_nm, 4);
     return ORBFE_OK;
 }
 
@@ -1866,11 +1818,22 @@ int orbfe_project_map_points(const float* p3Dw, const uint8_t* valid, const floa
                             level_above, "orbfe_project_map_points");
     P.frame_variant = !keyframe_variant;
     if (rc || (rc = use_device(device)) || n == 0) return rc;
-    MatchWorkspace& w = ws();
-    if ((rc = w.q.ensure((size_t)n * sizeof(orbfe_window_query))) ||
-        (rc = project_run(w, p3Dw, valid, min_dist, max_dist, normal, n, P, w.q.as<SbpQuery>())))
-        return rc;
-    ORBFE_HIP(hipMemcpy(queries, w.q.p, (size_t)n * sizeof(orbfe_window_query), hipMemcpyDeviceToHost));
+    HostStage& w = match_host_stage();
+    const size_t N = (size_t)n;
+    IoLayout l;
+    const size_t i_p = l.take(N * 12), i_min = l.take(N * 4), i_max = l.take(N * 4), i_nrm = l.take(N * 12), i_valid = l.take(N);
+    l.outputs();
+    const size_t o_q = l.take(N * sizeof(orbfe_window_query));
+    if ((rc = w.begin(l))) return rc;
+    w.put(i_p, p3Dw, N * 12); w.put(i_min, min_dist, N * 4); w.put(i_max, max_dist, N * 4);
+    w.put(i_nrm, normal, N * 12); w.put(i_valid, valid, N);
+    if ((rc = w.upload())) return rc;
+    hipLaunchKernelGGL(k_project_map_points, dim3((n + 255) / 256), dim3(256), 0, w.stream, w.dev<const float>(i_p),
+                       valid ? w.dev<const uint8_t>(i_valid) : nullptr, w.dev<const float>(i_min), w.dev<const float>(i_max),
+                       normal ? w.dev<const float>(i_nrm) : nullptr, n, P, w.dev<SbpQuery>(o_q));
+    ORBFE_HIP(hipGetLastError());
+    if ((rc = w.download()) || (rc = w.sync())) return rc;
+    w.get(queries, o_q, N * sizeof(orbfe_window_query));
     return ORBFE_OK;
 }
 
@@ -2077,22 +2040,22 @@ int orbfe_knn2_csr(const uint8_t* Q, int nq, const uint8_t* T, int nt, const int
         if (offsets[q + 1] < offsets[q]) return fail(ORBFE_ERR_INVALID, "orbfe_knn2_csr: offsets must be non-decreasing");
     for (int k = 0; k < total; k++)
         if (idx[k] < 0 || idx[k] >= nt) return fail(ORBFE_ERR_INVALID, "orbfe_knn2_csr: candidate %d out of range", idx[k]);
-    MatchWorkspace& w = ws();
-    if ((rc = w.q.ensure((size_t)nq * 32)) || (rc = w.t.ensure((size_t)std::max(nt, 1) * 32)) ||
-        (rc = w.csr_cnt.ensure((size_t)(nq + 1) * 4)) || (rc = w.scratch.ensure((size_t)std::max(total, 1) * 4)) ||
-        (rc = w.oidx.ensure((size_t)nq * 4)) || (rc = w.obest.ensure((size_t)nq * 4)) || (rc = w.osecond.ensure((size_t)nq * 4)))
-        return rc;
-    ORBFE_HIP(hipMemcpy(w.q.p, Q, (size_t)nq * 32, hipMemcpyHostToDevice));
-    if (nt) ORBFE_HIP(hipMemcpy(w.t.p, T, (size_t)nt * 32, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.csr_cnt.p, offsets, (size_t)(nq + 1) * 4, hipMemcpyHostToDevice));
-    if (total) ORBFE_HIP(hipMemcpy(w.scratch.p, idx, (size_t)total * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_knn2_csr, dim3((nq + 3) / 4), dim3(256), 0, 0, w.q.as<uint8_t>(), nq, w.t.as<uint8_t>(),
-                       w.csr_cnt.as<int32_t>(), w.scratch.as<int32_t>(), init, w.oidx.as<int32_t>(), w.obest.as<int32_t>(),
-                       w.osecond.as<int32_t>());
+    HostStage& w = match_host_stage();
+    const size_t Q4 = (size_t)nq * 4;
+    IoLayout l;
+    const size_t i_q = l.take((size_t)nq * 32), i_t = l.take((size_t)nt * 32), i_off = l.take(Q4 + 4), i_idx = l.take((size_t)total * 4);
+    l.outputs();
+    const size_t o_idx = l.take(Q4), o_best = l.take(Q4), o_second = l.take(Q4);
+    if ((rc = w.begin(l))) return rc;
+    w.put(i_q, Q, (size_t)nq * 32); w.put(i_t, T, (size_t)nt * 32);
+    w.put(i_off, offsets, Q4 + 4); w.put(i_idx, idx, (size_t)total * 4);
+    if ((rc = w.upload())) return rc;
+    hipLaunchKernelGGL(k_knn2_csr, dim3((nq + 3) / 4), dim3(256), 0, w.stream, w.dev<const uint8_t>(i_q), nq, w.dev<const uint8_t>(i_t),
+                       w.dev<const int32_t>(i_off), w.dev<const int32_t>(i_idx), init, w.dev<int32_t>(o_idx), w.dev<int32_t>(o_best),
+                       w.dev<int32_t>(o_second));
     ORBFE_HIP(hipGetLastError());
-    ORBFE_HIP(hipMemcpy(best_idx, w.oidx.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
-    ORBFE_HIP(hipMemcpy(best_dist, w.obest.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
-    ORBFE_HIP(hipMemcpy(second_dist, w.osecond.p, (size_t)nq * 4, hipMemcpyDeviceToHost));
+    if ((rc = w.download()) || (rc = w.sync())) return rc;
+    w.get(best_idx, o_idx, Q4); w.get(best_dist, o_best, Q4); w.get(second_dist, o_second, Q4);
     return ORBFE_OK;
 }
 
@@ -2121,17 +2084,20 @@ int orbfe_distinctive_descriptors(const uint8_t* desc, const int32_t* offsets, i
     if (total && !desc) return fail(ORBFE_ERR_INVALID, "orbfe_distinctive_descriptors: null descriptors");
     int rc = use_device(device);
     if (rc) return rc;
-    MatchWorkspace& w = ws();
-    if ((rc = w.t.ensure((size_t)std::max(total, 1) * 32)) || (rc = w.csr_cnt.ensure((size_t)(npoints + 1) * 4)) ||
-        (rc = w.oidx.ensure((size_t)npoints * 4)) || (rc = w.q.ensure((size_t)npoints * 32)))
+    HostStage& w = match_host_stage();
+    const size_t NP = (size_t)npoints;
+    IoLayout l;
+    const size_t i_desc = l.take((size_t)total * 32), i_off = l.take((NP + 1) * 4);
+    l.outputs();
+    const size_t o_idx = l.take(NP * 4), o_desc = l.take(best_desc ? NP * 32 : 0);
+    if ((rc = w.begin(l))) return rc;
+    w.put(i_desc, desc, (size_t)total * 32); w.put(i_off, offsets, (NP + 1) * 4);
+    if ((rc = w.upload()) ||
+        (rc = orbfe_distinctive_descriptors_device(w.dev<const uint8_t>(i_desc), w.dev<const int32_t>(i_off), npoints, w.dev<int32_t>(o_idx),
+                                                   best_desc ? w.dev<uint8_t>(o_desc) : nullptr, w.stream)) ||
+        (rc = w.download()) || (rc = w.sync()))
         return rc;
-    if (total) ORBFE_HIP(hipMemcpy(w.t.p, desc, (size_t)total * 32, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(w.csr_cnt.p, offsets, (size_t)(npoints + 1) * 4, hipMemcpyHostToDevice));
-    if ((rc = orbfe_distinctive_descriptors_device(w.t.as<uint8_t>(), w.csr_cnt.as<int32_t>(), npoints, w.oidx.as<int32_t>(),
-                                                   best_desc ? w.q.as<uint8_t>() : nullptr, nullptr)))
-        return rc;
-    ORBFE_HIP(hipMemcpy(best_idx, w.oidx.p, (size_t)npoints * 4, hipMemcpyDeviceToHost));
-    if (best_desc) ORBFE_HIP(hipMemcpy(best_desc, w.q.p, (size_t)npoints * 32, hipMemcpyDeviceToHost));
+    w.get(best_idx, o_idx, NP * 4); w.get(best_desc, o_desc, NP * 32);
     return ORBFE_OK;
 }
 
@@ -2142,12 +2108,18 @@ int orbfe_undistort_points(const float* src, int n, const float* K4, const float
     int rc = undistort_params(K4, dist, ndist, P, "orbfe_undistort_points");
     if (rc || (rc = use_device(device))) return rc;
     if (n == 0) return ORBFE_OK;
-    MatchWorkspace& w = ws();
-    if ((rc = w.prev.ensure((size_t)n * 8))) return rc;
-    ORBFE_HIP(hipMemcpy(w.prev.p, src, (size_t)n * 8, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_undistort_points, dim3((n + 255) / 256), dim3(256), 0, 0, w.prev.as<float2>(), n, P, w.prev.as<float2>());
+    HostStage& w = match_host_stage();
+    IoLayout l;
+    const size_t i_src = l.take((size_t)n * 8);
+    l.outputs();
+    const size_t o_dst = l.take((size_t)n * 8);
+    if ((rc = w.begin(l))) return rc;
+    w.put(i_src, src, (size_t)n * 8);
+    if ((rc = w.upload())) return rc;
+    hipLaunchKernelGGL(k_undistort_points, dim3((n + 255) / 256), dim3(256), 0, w.stream, w.dev<const float2>(i_src), n, P, w.dev<float2>(o_dst));
     ORBFE_HIP(hipGetLastError());
-    ORBFE_HIP(hipMemcpy(dst, w.prev.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+    if ((rc = w.download()) || (rc = w.sync())) return rc;
+    w.get(dst, o_dst, (size_t)n * 8);
     return ORBFE_OK;
 }
 

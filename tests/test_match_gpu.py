@@ -523,6 +523,90 @@ def test_matching_entry_points_are_thread_safe(orbfe, oracle):
     assert not errors, errors
 
 
+def _in_fresh_thread(fn):
+    """fn() in a thread of its own: the library's per-thread workspaces start empty there (smallest row stride and candidate pool)"""
+    import threading
+    box = {}
+
+    def run():
+        try:
+            box["value"] = fn()
+        except BaseException as e:  # noqa: BLE001
+            box["error"] = e
+
+    t = threading.Thread(target=run)
+    t.start()
+    t.join()
+    if "error" in box:
+        raise box["error"]
+    return box["value"]
+
+
+def _patch_keypoints(rng, dtype, n, x0, y0, side, octaves=1):
+    """n keypoints scattered over the square patch of `side` pixels at (x0, y0)"""
+    k = np.zeros(n, dtype)
+    k["x"] = x0 + rng.random(n, dtype=np.float32) * side
+    k["y"] = y0 + rng.random(n, dtype=np.float32) * side
+    k["size"] = 31.0; k["angle"] = rng.random(n, dtype=np.float32) * 360.0; k["response"] = 50.0
+    k["octave"] = rng.integers(0, octaves, n); k["class_id"] = -1
+    return k
+
+
+def _flip_bits(rng, desc, most):
+    d = desc.copy()
+    for i in range(len(d)):
+        for b in rng.integers(0, 256, 8)[: rng.integers(0, most + 1)]:
+            d[i, b >> 3] ^= np.uint8(1 << (b & 7))
+    return d
+
+
+@pytest.mark.gpu
+def test_search_by_projection_retries_from_the_callers_flags(orbfe, oracle):
+    """One window over a patch of 600 keypoints: the row of 600 candidates exceeds the first row stride of a thread (128), so the
+    first attempt overflows and the search runs a second time.  The second attempt must start from the caller's taken flags, not
+    from those the first one left: match, nmatches and the returned flags equal the oracle's and those of a second call of the same
+    thread, which has the stride and does not retry."""
+    rng = np.random.default_rng(21)
+    kps = _patch_keypoints(rng, oracle.KP_DTYPE, 600, 300.0, 200.0, 40.0, octaves=8)
+    desc = synth.random_descriptors(600, 21)
+    taken = (rng.random(600) < 0.3).astype(np.uint8)
+    q = np.zeros(1, oracle.WINDOW_QUERY_DTYPE)
+    q["x"] = 320.0; q["y"] = 220.0; q["r"] = 50.0; q["min_level"] = 0; q["max_level"] = -1
+    free = np.flatnonzero(taken == 0)
+    qd = _flip_bits(rng, desc[free[len(free) // 2]][None], 6)
+    want = oracle.search_by_projection(kps, desc, 640, 480, q, qd, taken, 1, 100, 0.8)
+    first, second = _in_fresh_thread(lambda: [orbfe.search_by_projection(kps, desc, 640, 480, q, qd, taken, 1, 100, 0.8) for _ in range(2)])
+    assert want["nmatches"] == 1 and want["taken"].sum() == taken.sum() + 1
+    for got in (first, second):
+        assert got["nmatches"] == want["nmatches"]
+        for f in ("match", "taken", "best_idx", "best_dist", "best_level", "second_dist", "second_level"):
+            assert np.array_equal(got[f], want[f]), f
+
+
+@pytest.mark.gpu
+def test_search_for_initialization_retries_from_the_callers_prev_matched(orbfe, oracle):
+    """Two frames of 300 level-0 keypoints inside one 60 x 60 px patch at window 100: every keypoint of frame 2 is a candidate of
+    every query, 90 000 pool entries against the 16 384 a thread starts with, so the first attempt overflows and the search runs a
+    second time with the pool grown.  The second attempt must start from the caller's vbPrevMatched: matches, count and the updated
+    vbPrevMatched equal the oracle's and those of a second call of the same thread, which does not retry."""
+    rng = np.random.default_rng(22)
+    n = 300
+    k1 = _patch_keypoints(rng, oracle.KP_DTYPE, n, 280.0, 200.0, 60.0)
+    d1 = synth.random_descriptors(n, 22)
+    perm = rng.permutation(n)
+    k2 = k1[perm].copy()
+    k2["x"] = np.clip(k2["x"] + rng.normal(0, 2, n).astype(np.float32), 280.0, 340.0)
+    k2["y"] = np.clip(k2["y"] + rng.normal(0, 2, n).astype(np.float32), 200.0, 260.0)
+    d2 = _flip_bits(rng, d1[perm], 8)
+    prev = np.stack([k1["x"], k1["y"]], 1) + rng.normal(0, 5, (n, 2)).astype(np.float32)
+    on, om12, oprev = oracle.search_for_initialization(k1, d1, k2, d2, 640, 480, prev, 100, 0.9, True)
+    m = orbfe.ORBmatcher(0.9, True)
+    first, second = _in_fresh_thread(lambda: [m.SearchForInitialization(k1, d1, k2, d2, 640, 480, prev, 100) for _ in range(2)])
+    assert on > n // 2 and not np.array_equal(oprev, prev)
+    for gn, gm12, gprev in (first, second):
+        assert gn == on and np.array_equal(gm12, om12) and np.array_equal(gprev, oprev)
+
+
 @pytest.mark.gpu
 def test_distinctive_descriptors(orbfe, oracle):
     """MapPoint::ComputeDistinctiveDescriptors over a whole map at once: bit-exact against the oracle, N from 0 to 256, clusters of
