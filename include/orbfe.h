@@ -119,7 +119,19 @@ int orbfe_extract(orbfe_extractor* h, const uint8_t* img, int rows, int cols, si
 int orbfe_extract_batch(orbfe_extractor* h, const uint8_t* imgs, int nframes, size_t frame_stride, int rows, int cols,
                         size_t step, orbfe_keypoint* kps, uint8_t* desc, int capacity, int32_t* n_out);
 
-/* Batched video mode, device buffers, asynchronous on `stream` (hipStream_t). d_n_out: int32[nframes] on device. */
+/* Batched video mode, device buffers, asynchronous on `stream` (hipStream_t). d_n_out: int32[nframes] on device.
+ * LAYOUT OF DEVICE FRAMES (this call, orbfe_aruco_detect_batch_device, orbfe_pipeline_step): the kernels read the frames where they
+ * lie, so a ROI of a larger device frame or a pitched allocation is passed as it is --
+ *   - d_imgs may sit at any byte: no alignment is asked of the base, the step or the frame stride;
+ *   - step: any value >= cols and below 2^23 (8388608), with (rows - 1) * step + cols below 2^31: rows are addressed with 24-bit
+ *     multiplies and 32-bit offsets inside a frame (frames themselves with 64 bits);
+ *   - frame_stride: any value >= (rows - 1) * step + cols (not looked at when nframes is 1);
+ *   - the bytes between a row's last pixel and the next row, and between frames, are never written and their content has no
+ *     influence on any result.  They may be READ: every row, the last row of the last frame included, has to be followed by
+ *     readable memory up to `step` bytes from its first pixel.  (The one reader of such bytes is the detector's /2 pyramid where base,
+ *     step and frame stride are all multiples of 8: it loads a row in 8-byte pieces, up to 6 bytes past the pixels and never past
+ *     `step`.  No other kernel reads a byte behind the last row's last pixel; the requirement is not meant to grow.)
+ * Anything else is ORBFE_ERR_INVALID before a kernel is enqueued (orbfe_last_error names the bound). */
 int orbfe_extract_batch_device(orbfe_extractor* h, const uint8_t* d_imgs, int nframes, size_t frame_stride, int rows,
                                int cols, size_t step, orbfe_keypoint* d_kps, uint8_t* d_desc, int capacity,
                                int32_t* d_n_out, void* stream);
@@ -776,6 +788,7 @@ int orbfe_aruco_detect_bgr(orbfe_aruco* h, const uint8_t* bgr, int rows, int col
                            int32_t* n_out);
 int orbfe_aruco_detect_batch(orbfe_aruco* h, const uint8_t* imgs, int nframes, size_t frame_stride, int rows, int cols,
                              size_t step, orbfe_marker* out, int capacity, int32_t* n_out);
+/* device frames: any base byte, step and frame stride within the bounds given at orbfe_extract_batch_device (LAYOUT OF DEVICE FRAMES) */
 int orbfe_aruco_detect_batch_device(orbfe_aruco* h, const uint8_t* d_imgs, int nframes, size_t frame_stride, int rows,
                                     int cols, size_t step, orbfe_marker* d_out, int capacity, int32_t* d_n_out,
                                     void* stream);
@@ -894,7 +907,8 @@ int orbfe_pipeline_config_default(orbfe_pipeline_config* cfg, int frames, int ro
 orbfe_pipeline* orbfe_pipeline_create(const orbfe_pipeline_config* cfg);
 void orbfe_pipeline_destroy(orbfe_pipeline* p);
 int orbfe_pipeline_layout(const orbfe_pipeline* p, orbfe_record_layout* out);
-/* One batch: d_imgs = frames x rows x pitch bytes on the pipeline's device (pitch >= cols; the frames have to stay valid and unchanged
+/* One batch: d_imgs = frames x rows x pitch bytes on the pipeline's device (any base byte, any pitch >= cols within the bounds of LAYOUT
+ * OF DEVICE FRAMES at orbfe_extract_batch_device, frames rows * pitch apart; the frames have to stay valid and unchanged
  * until orbfe_pipeline_input_done for the batch, or orbfe_pipeline_synchronize, has returned: a kernel of the batch may be enqueued
  * after this call).  *record_set = index of the set the batch is written to. */
 int orbfe_pipeline_step(orbfe_pipeline* p, const uint8_t* d_imgs, size_t pitch, int32_t* record_set);

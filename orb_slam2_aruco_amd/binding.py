@@ -1235,6 +1235,7 @@ class MarkerDetector:
         _check(self.L, self.L.orbfe_aruco_detect_batch_device(self.h, d_imgs_ptr, B, frame_stride, rows, cols, step,
                                                               d_out_ptr, capacity, d_n_ptr, stream),
                "orbfe_aruco_detect_batch_device")
+        self._shape = (rows, cols)
 
     def batch_status(self):
         """(frames of the last device batch with incomplete results, union of their capacity flags)"""

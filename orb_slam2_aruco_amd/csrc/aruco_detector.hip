@@ -448,39 +448,30 @@ struct orbfe_aruco {
     }
 
     ImgView pyr_view() { return ImgView{d_pyr.as<uint8_t>(), d_pyr.as<uint8_t>(), geo.pyr_fbytes, 0}; }
-    // the /2 pyramid from level `first` on
+    // the /2 pyramid from level `first` on; which kernel makes a level: plan_pyramid_kernels (detector_plan.hpp)
     void pyramid(int first, const ImgView& src0, int B, hipStream_t st)
     {
         const ImgView pyr = pyr_view();
-        if (first == 1 && half_pyr) {
+        const std::vector<PyrKernel> K = plan_pyramid_kernels(geo, first, (unsigned)((uintptr_t)src0.base & 15), src0.pitch, src0.fstride, half_pyr != 0);
+        if (first == 1 && first < geo.npyr && (K[1] == PyrKernel::half_pyr4 || K[1] == PyrKernel::half_pyr3)) {
             // the leading exact halvings in one launch (k_half_pyr): four from 16 x 16 source blocks, or three from 8 x 8
-            for (int nf = 4; nf >= 3 && first == 1; nf--) {
-                const int bs = 1 << nf;
-                bool ok = geo.npyr > nf && geo.levels[0].w % bs == 0 && geo.levels[0].h % bs == 0 && src0.pitch % (bs == 16 ? 16 : 8) == 0 &&
-                          src0.fstride % (bs == 16 ? 16 : 8) == 0 && ((uintptr_t)src0.base & (bs == 16 ? 15 : 7)) == 0 && geo.pyr_fbytes % 8 == 0;
-                for (int p = 1; ok && p <= nf; p++) {
-                    const int al = bs >> p;   // bytes a thread stores per row of level p
-                    ok = geo.lvl_exact[p] && geo.levels[p].w == geo.levels[0].w >> p && geo.levels[p].h == geo.levels[0].h >> p && geo.levels[p].pitch % al == 0 &&
-                         geo.levels[p].off % al == 0 && geo.levels[p].pitch >= geo.levels[p].w;
-                }
-                if (!ok) continue;
-                HalfPyrDst P{};
-                P.base = pyr.base_w; P.fstride = geo.pyr_fbytes;
-                for (int p = 1; p <= nf; p++) { P.off[p - 1] = (uint32_t)geo.levels[p].off; P.pitch[p - 1] = geo.levels[p].pitch; }
-                const int bw = geo.levels[0].w / bs, nblocks = bw * (geo.levels[0].h / bs);
-                if (nf == 4) hipLaunchKernelGGL(k_half_pyr<4>, dim3((nblocks + 255) / 256, B), dim3(256), 0, st, src0, P, bw, nblocks);
-                else hipLaunchKernelGGL(k_half_pyr<3>, dim3((nblocks + 255) / 256, B), dim3(256), 0, st, src0, P, bw, nblocks);
-                first = nf + 1;
-            }
+            const int nf = K[1] == PyrKernel::half_pyr4 ? 4 : 3, bs = 1 << nf;
+            HalfPyrDst P{};
+            P.base = pyr.base_w; P.fstride = geo.pyr_fbytes;
+            for (int p = 1; p <= nf; p++) { P.off[p - 1] = (uint32_t)geo.levels[p].off; P.pitch[p - 1] = geo.levels[p].pitch; }
+            const int bw = geo.levels[0].w / bs, nblocks = bw * (geo.levels[0].h / bs);
+            if (nf == 4) hipLaunchKernelGGL(k_half_pyr<4>, dim3((nblocks + 255) / 256, B), dim3(256), 0, st, src0, P, bw, nblocks);
+            else hipLaunchKernelGGL(k_half_pyr<3>, dim3((nblocks + 255) / 256, B), dim3(256), 0, st, src0, P, bw, nblocks);
+            first = nf + 1;
         }
         for (int p = first; p < geo.npyr; p++) {
             const ArLevel &L = geo.levels[p], &Lp = geo.levels[p - 1];
             ImgView sv = (p == 1) ? src0 : ImgView{pyr.base + Lp.off, nullptr, geo.pyr_fbytes, Lp.pitch};
             ImgView dv{pyr.base + L.off, pyr.base_w + L.off, geo.pyr_fbytes, L.pitch};
-            if (geo.lvl_exact[p] && sv.pitch % 8 == 0 && sv.fstride % 8 == 0 && ((uintptr_t)sv.base & 7) == 0 && dv.pitch % 4 == 0 && dv.pitch >= 4 * ((L.w + 3) / 4)) {
-                const int dw4 = (L.w + 3) / 4, nthreads = dw4 * ((L.h + 1) / 2);   // reads up to 2 * L.w + 6 < the source pitch (64-byte rows)
+            if (K[p] == PyrKernel::half_area4) {
+                const int dw4 = (L.w + 3) / 4, nthreads = dw4 * ((L.h + 1) / 2);   // reads 8 * dw4 bytes of a source row: within a pitch that is a multiple of 8
                 hipLaunchKernelGGL(k_half_area4, dim3((nthreads + 255) / 256, B), dim3(256), 0, st, sv, dv, dw4, L.h);
-            } else if (geo.lvl_exact[p]) {
+            } else if (K[p] == PyrKernel::half_area) {
                 hipLaunchKernelGGL(k_half_area, dim3((L.w + 63) / 64, (L.h + 3) / 4, B), dim3(256), 0, st, sv, dv, L.w, L.h);
             } else {
                 const int dw4 = (L.w + 3) / 4;
@@ -1093,9 +1084,10 @@ int orbfe_aruco_detect_batch_device(orbfe_aruco* h, const uint8_t* d_imgs, int n
                                     int cols, size_t step, orbfe_marker* d_out, int capacity, int32_t* d_n_out,
                                     void* stream)
 {
-    if (!h || !d_imgs || !d_out || !d_n_out || nframes <= 0 || rows <= 0 || cols <= 0 || step < (size_t)cols ||
-        capacity <= 0)
+    if (!h || !d_imgs || !d_out || !d_n_out || nframes <= 0 || rows <= 0 || cols <= 0 || capacity <= 0)
         return fail(ORBFE_ERR_INVALID, "orbfe_aruco_detect_batch_device: invalid argument");
+    char why[192];   // level 0 is read from the caller's buffer as it lies: what the kernels' offsets cannot address is refused here
+    if (plan_input_layout(rows, cols, step, frame_stride, nframes, why, sizeof(why))) return fail(ORBFE_ERR_INVALID, "orbfe_aruco_detect_batch_device: %s", why);
     int rc = use_device(h->device);
     if (rc) return rc;
     if (h->spec.pending) { ORBFE_HIP(hipStreamSynchronize(h->own_stream)); h->spec.pending = false; } // the handle's buffers are in use

@@ -14,6 +14,7 @@
 
 #include "../../include/orbfe.h"
 #include "aruco_trace.hpp"
+#include "input_layout.hpp"   // plan_input_layout: the layouts of a caller's device frames the kernels can address
 
 namespace orbfe {
 
@@ -172,6 +173,48 @@ inline DetectorGeometry plan_detector(int rows, int cols, int prows, int pcols, 
     g.ct_lcap = std::min(g.ct_segcap, lcap_override > 0 ? lcap_override : large ? 16384 : 4096);   // list elements k_ct_lists keeps in LDS (8 B each)
     g.ct_items_per_frame = std::max(4096, g.ct_segcap / 4);
     return g;
+}
+
+// Which kernel writes a level of the /2 pyramid.  Level 1 is read from the caller's frames, whose alignment decides: k_half_pyr and
+// k_half_area4 cast the source rows to uint4 / uint2, k_half_area reads bytes, k_resize_level makes the inexact levels.
+enum class PyrKernel : int { none = 0, half_pyr4, half_pyr3, half_area4, half_area, resize_level };
+
+// The kernels of levels first .. npyr - 1 (entries below `first`: none).  src_align = the low four bits of the address of level 0's
+// first byte, src_pitch / src_fstride = its row and frame strides (the caller's); levels >= 2 are read from the detector's own
+// pyramid block, whose allocation is aligned and whose frames are pyr_fbytes apart.  half_pyr: the switch of the same name.
+//   k_half_pyr<4> / <3> (only from level 1: levels 1 .. 4 / 1 .. 3 in one launch, from 16 x 16 / 8 x 8 source blocks): those levels
+//     exact halvings of a level 0 that divides into the blocks; base, pitch and frame stride multiples of 16 / 8;
+//   k_half_area4: an exact level whose source base, pitch and frame stride are multiples of 8 (it reads 8 * ceil(w / 4) bytes of a row:
+//     up to 6 past the source's pixels, inside a pitch that is a multiple of 8);
+//   k_half_area: any other exact level;  k_resize_level: an inexact one.
+inline std::vector<PyrKernel> plan_pyramid_kernels(const DetectorGeometry& geo, int first, unsigned src_align, int src_pitch, size_t src_fstride, bool half_pyr)
+{
+    std::vector<PyrKernel> k((size_t)std::max(geo.npyr, 0), PyrKernel::none);
+    if (first == 1 && half_pyr)
+        for (int nf = 4; nf >= 3 && first == 1; nf--) {
+            const int bs = 1 << nf, al0 = bs == 16 ? 16 : 8;
+            bool ok = geo.npyr > nf && geo.levels[0].w % bs == 0 && geo.levels[0].h % bs == 0 && src_pitch % al0 == 0 && src_fstride % al0 == 0 &&
+                      (src_align & (unsigned)(al0 - 1)) == 0 && geo.pyr_fbytes % 8 == 0;
+            for (int p = 1; ok && p <= nf; p++) {
+                const int al = bs >> p;   // bytes a thread stores per row of level p
+                ok = geo.lvl_exact[p] && geo.levels[p].w == geo.levels[0].w >> p && geo.levels[p].h == geo.levels[0].h >> p && geo.levels[p].pitch % al == 0 &&
+                     geo.levels[p].off % al == 0 && geo.levels[p].pitch >= geo.levels[p].w;
+            }
+            if (!ok) continue;
+            for (int p = 1; p <= nf; p++) k[(size_t)p] = nf == 4 ? PyrKernel::half_pyr4 : PyrKernel::half_pyr3;
+            first = nf + 1;
+        }
+    for (int p = std::max(first, 1); p < geo.npyr; p++) {
+        const ArLevel &L = geo.levels[(size_t)p], &Lp = geo.levels[(size_t)p - 1];
+        const bool own = p > 1;   // the source is the detector's pyramid block
+        const int spitch = own ? Lp.pitch : src_pitch;
+        const size_t sfstride = own ? geo.pyr_fbytes : src_fstride;
+        const unsigned salign = own ? (unsigned)(Lp.off & 15) : src_align;
+        if (!geo.lvl_exact[(size_t)p]) k[(size_t)p] = PyrKernel::resize_level;
+        else if (spitch % 8 == 0 && sfstride % 8 == 0 && (salign & 7) == 0 && L.pitch % 4 == 0 && L.pitch >= 4 * ((L.w + 3) / 4)) k[(size_t)p] = PyrKernel::half_area4;
+        else k[(size_t)p] = PyrKernel::half_area;
+    }
+    return k;
 }
 
 // k_threshold_mfma: a 32-column strip per wave; c0 / c1 / c2 = byte columns of the three 16-byte pieces of a row it loads, tab = index

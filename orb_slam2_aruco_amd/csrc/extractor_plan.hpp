@@ -14,6 +14,7 @@
 
 #include "../../include/orbfe.h"
 #include "../../include/orbfe_math.h"
+#include "input_layout.hpp"   // plan_input_layout: the layouts of a caller's device frames the kernels can address
 
 namespace orbfe {
 

@@ -506,9 +506,10 @@ int orbfe_extract_batch_device(orbfe_extractor* h, const uint8_t* d_imgs, int nf
                                int cols, size_t step, orbfe_keypoint* d_kps, uint8_t* d_desc, int capacity,
                                int32_t* d_n_out, void* stream)
 {
-    if (!h || !d_imgs || !d_kps || !d_desc || !d_n_out || nframes <= 0 || rows <= 0 || cols <= 0 ||
-        step < (size_t)cols || capacity <= 0)
+    if (!h || !d_imgs || !d_kps || !d_desc || !d_n_out || nframes <= 0 || rows <= 0 || cols <= 0 || capacity <= 0)
         return fail(ORBFE_ERR_INVALID, "orbfe_extract_batch_device: invalid argument");
+    char why[192];   // level 0 is read from the caller's buffer as it lies: what the kernels' offsets cannot address is refused here
+    if (plan_input_layout(rows, cols, step, frame_stride, nframes, why, sizeof(why))) return fail(ORBFE_ERR_INVALID, "orbfe_extract_batch_device: %s", why);
     int rc = use_device(h->device);
     if (rc) return rc;
     return h->run_device(d_imgs, nframes, frame_stride, rows, cols, step, d_kps, d_desc, capacity, d_n_out,

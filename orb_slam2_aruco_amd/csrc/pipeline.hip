@@ -22,6 +22,7 @@
 
 #include "orbfe_common.hpp"
 #include "gather_plan.hpp"
+#include "input_layout.hpp"
 
 using namespace orbfe;
 
@@ -433,7 +434,9 @@ static int step_impl(orbfe_pipeline* p, const uint8_t* d_imgs, size_t pitch, int
 
 int orbfe_pipeline_step(orbfe_pipeline* p, const uint8_t* d_imgs, size_t pitch, int32_t* record_set)
 {
-    if (!p || !d_imgs || pitch < (size_t)p->cols) return fail(ORBFE_ERR_INVALID, "orbfe_pipeline_step: invalid argument");
+    if (!p || !d_imgs) return fail(ORBFE_ERR_INVALID, "orbfe_pipeline_step: invalid argument");
+    char why[192];   // the engines read the frames as they lie (step_body forwards the pitch): refused here, before anything is enqueued
+    if (orbfe::plan_input_layout(p->rows, p->cols, pitch, (size_t)p->rows * pitch, p->B, why, sizeof(why))) return fail(ORBFE_ERR_INVALID, "orbfe_pipeline_step: %s", why);
     int rc = use_device(p->cfg.device);
     if (rc) return rc;
     return step_impl(p, d_imgs, pitch, record_set, -1);

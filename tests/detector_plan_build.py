@@ -21,6 +21,8 @@ def lib():
         vp, i32, i64 = C.c_void_p, C.c_int, C.c_longlong
         L.dplan_make.argtypes = [i32, i32, i32, i32, i32, i32, i32, i64, vp, vp, vp, i32, vp, i32]
         L.dplan_threshold_sweep.argtypes = [i32, i32, i32, vp]
+        L.dplan_input_layout.argtypes = [i32, i32, C.c_ulonglong, C.c_ulonglong, i32, vp, i32]
+        L.dplan_pyramid_kernels.argtypes = [i32, i32, i32, i32, i32, i32, C.c_ulonglong, i32, vp, i32]
         _lib = L
     return _lib
 
@@ -54,3 +56,26 @@ def threshold_sweep(w_first, w_last, win):
 
 def threshold_refused(cols, win):
     return bool(lib().dplan_threshold_refused(cols, win))
+
+
+def input_layout(rows, cols, step, frame_stride, nframes):
+    """(error code, message) of plan_input_layout for a caller's device frames."""
+    msg = C.create_string_buffer(256)
+    rc = lib().dplan_input_layout(rows, cols, step, frame_stride, nframes, msg, 256)
+    return rc, msg.value.decode()
+
+
+def threshold_read_end(cols, win):
+    """the byte column behind the last one k_threshold_mfma loads from a row of a `cols`-wide frame (-1: tables do not apply)"""
+    return lib().dplan_threshold_read_end(cols, win)
+
+
+PYR_KERNELS = ("none", "k_half_pyr<4>", "k_half_pyr<3>", "k_half_area4", "k_half_area", "k_resize_level")   # PyrKernel (detector_plan.hpp)
+
+
+def pyramid_kernels(rows, cols, base_off, step, frame_stride, half_pyr=True, first=1, S=35):
+    """The kernel that writes each pyramid level >= `first` (names, level 1 first) for frames at an aligned allocation + base_off."""
+    out = np.zeros(MAXLEVELS, np.int32)
+    n = lib().dplan_pyramid_kernels(rows, cols, S, first, base_off & 15, step, frame_stride, int(half_pyr), _p(out), MAXLEVELS)
+    assert n >= 1, n
+    return [PYR_KERNELS[v] for v in out[1:n]]

@@ -106,4 +106,34 @@ int dplan_threshold_sweep(int w_first, int w_last, int win, int* first_bad)
 // 1 if plan_threshold_tables(cols, win) says "not applicable"
 int dplan_threshold_refused(int cols, int win) { return plan_threshold_tables(cols, win).ok ? 0 : 1; }
 
+// plan_input_layout (csrc/input_layout.hpp) as the detector's plan header carries it: the error code, the reason in msg
+int dplan_input_layout(int rows, int cols, unsigned long long step, unsigned long long frame_stride, int nframes, char* msg, int msgcap)
+{
+    return plan_input_layout(rows, cols, (size_t)step, (size_t)frame_stride, nframes, msg, (size_t)msgcap);
+}
+
+// The byte column behind the last one a load of k_threshold_mfma touches, over all strips of a `cols`-wide frame (the caller's rows may
+// end with their last pixel); -1 if the tables do not apply
+int dplan_threshold_read_end(int cols, int win)
+{
+    const ThresholdTables t = plan_threshold_tables(cols, win);
+    if (!t.ok) return -1;
+    int end = 0;
+    for (const ThrStrip& S : t.strips) end = std::max(end, std::max(S.c0, std::max(S.c1, S.c2)) + 16);
+    return end;
+}
+
+// plan_pyramid_kernels for the geometry of a rows x cols frame (pyramid from the frame itself) whose level 0 lies at an address with
+// the low bits src_align, rows src_pitch and frames src_fstride apart: out[p] = the PyrKernel of level p (0: none).  Returns the
+// number of levels, or the plan's error code.
+int dplan_pyramid_kernels(int rows, int cols, int S, int first, int src_align, int src_pitch, unsigned long long src_fstride, int half_pyr, int* out, int maxlevels)
+{
+    const DetectorGeometry g = plan_detector(rows, cols, rows, cols, S, false, 0, 4352);
+    if (g.err) return g.err;
+    if (g.npyr > maxlevels) return -100;
+    const std::vector<PyrKernel> k = plan_pyramid_kernels(g, first, (unsigned)src_align, src_pitch, (size_t)src_fstride, half_pyr != 0);
+    for (int p = 0; p < g.npyr; p++) out[p] = (int)k[(size_t)p];
+    return g.npyr;
+}
+
 } // extern "C"

@@ -19,6 +19,7 @@ def lib():
         vp, i32 = C.c_void_p, C.c_int
         L.xplan_make.argtypes = [i32, i32, i32, vp, vp, vp, i32, vp, vp, vp, i32]
         L.xplan_blur_sweep.argtypes = [i32, i32, vp]
+        L.xplan_input_layout.argtypes = [i32, i32, C.c_ulonglong, C.c_ulonglong, i32, vp, i32]
         _lib = L
     return _lib
 
@@ -42,3 +43,15 @@ def blur_sweep(w_first, w_last):
     """(number of refused (width, taps, row rule) combinations, the first of them)."""
     bad = np.zeros(3, np.int32)
     return lib().xplan_blur_sweep(w_first, w_last, _p(bad)), tuple(int(v) for v in bad)
+
+
+def input_layout(rows, cols, step, frame_stride, nframes):
+    """(error code, message) of plan_input_layout for a caller's device frames."""
+    msg = C.create_string_buffer(256)
+    rc = lib().xplan_input_layout(rows, cols, step, frame_stride, nframes, msg, 256)
+    return rc, msg.value.decode()
+
+
+def level0_read_end(cols, gaussian_ed=0):
+    """the byte column behind the last one k_blur7_mfma loads from a row of a `cols`-wide level 0 (-1: tables refused)"""
+    return lib().xplan_level0_read_end(cols, gaussian_ed)

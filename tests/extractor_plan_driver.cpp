@@ -70,4 +70,23 @@ int xplan_blur_sweep(int w_first, int w_last, int* first_bad)
     return bad;
 }
 
+// plan_input_layout (csrc/input_layout.hpp) as the extractor's plan header carries it: the error code, the reason in msg
+int xplan_input_layout(int rows, int cols, unsigned long long step, unsigned long long frame_stride, int nframes, char* msg, int msgcap)
+{
+    return plan_input_layout(rows, cols, (size_t)step, (size_t)frame_stride, nframes, msg, (size_t)msgcap);
+}
+
+// The byte column behind the last one a level-0 load of k_blur7_mfma touches, over all strips of a `cols`-wide level 0 (its three
+// 16-byte pieces are planned with rowbytes = cols: level 0 is the caller's buffer, whose rows may end with their last pixel); -1 if
+// the tables are refused
+int xplan_level0_read_end(int cols, int gaussian_ed)
+{
+    std::vector<BlurStrip> st;
+    std::vector<uint8_t> tabs;
+    if (!plan_blur_level(0, cols, cols, blur_taps(gaussian_ed != 0), st, tabs)) return -1;
+    int end = 0;
+    for (const BlurStrip& S : st) end = std::max(end, std::max(S.c0, std::max(S.c1, S.c2)) + 16);
+    return end;
+}
+
 } // extern "C"
