@@ -229,7 +229,11 @@ int orbfe_knn2_csr(const uint8_t* Q, int nq, const uint8_t* T, int nt, const int
                    int32_t* best_idx, int32_t* best_dist, int32_t* second_dist, int device);
 
 /* Batched device variant: npairs independent (Q,T) problems. Q/T: device pointers to descriptor blocks,
- * block p at Q + p*q_stride bytes with d_nq[p] valid rows (<= max_nq), same for T. Outputs blocks of max_nq. */
+ * block p at Q + p*q_stride bytes with d_nq[p] valid rows (<= max_nq), same for T. Outputs blocks of max_nq.
+ * d_nq == NULL: every pair has max_nq queries.  t_stride = 0 (q_stride = 0): one train (query) block shared by all pairs.  Strides
+ * are multiples of 16 bytes.  The counts are the caller's duty, 0 <= d_nq[p] <= max_nq and 0 <= d_nt[p] <= max_nt: they are not
+ * clamped.  Rows past d_nq[p] of a block are neither read nor written, rows past d_nt[p] are not read; d_nt[p] == 0 gives
+ * idx = -1 and both distances `init`.  Asynchronous on `stream`. */
 int orbfe_knn2_batch_device(const uint8_t* d_Q, const int32_t* d_nq, size_t q_stride, int max_nq, const uint8_t* d_T,
                             const int32_t* d_nt, size_t t_stride, int max_nt, int npairs, int init,
                             int32_t* d_best_idx, int32_t* d_best_dist, int32_t* d_second_dist, void* stream);
@@ -276,7 +280,13 @@ int orbfe_search_by_projection(const orbfe_keypoint* kps, const uint8_t* desc, i
  * per-stream scratch truncates silently, so ask orbfe_search_by_projection_batch_status afterwards: *overflow = 0, or the
  * longest candidate list -- the scratch has then been grown and repeating the call succeeds.  The flag is sticky like the extractor's
  * and SearchForInitialization's: it covers every _batch_device search / fuse call on this stream since it was last read (reading
- * clears it), so two batches may be enqueued before one status call. */
+ * clears it), so two batches may be enqueued before one status call.  After a truncated search the caller restores d_taken before
+ * it repeats the call: the first attempt has marked keypoints.
+ * Counts are clamped: a frame searches its first min(d_n[f], capacity) keypoints with its first min(d_nq[f], qcapacity) queries,
+ * a negative count is 0.  Nothing past those rows is read or written: the per-query outputs get nq entries, d_match_cur and
+ * d_taken n.  mode 0 writes only the five raw outputs (d_match is required but stays untouched, as does d_nmatches); modes 1 and
+ * 2 write d_match, d_nmatches[f] and, where given, the raw outputs; mode 2 also d_match_cur.  A frame without keypoints answers
+ * every query with best_idx = -1, distances 256, levels -1, match = -1. */
 int orbfe_search_by_projection_batch_device(const orbfe_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_n, int capacity, int nframes,
                                             int cols, int rows, const float* bounds, const orbfe_window_query* d_queries,
                                             const uint8_t* d_qdesc, const int32_t* d_nq, int qcapacity, uint8_t* d_taken,
@@ -340,7 +350,9 @@ int orbfe_fuse_search(const orbfe_keypoint* kps, const uint8_t* desc, int n, int
  * orbfe_extract_batch_device); the nmp map points (device arrays) are shared, d_valid (may be NULL) is [nkf][nmp] because
  * IsInKeyFrame(pKF) depends on the keyframe; Tcw / Ow are HOST arrays of nkf poses (12 / 3 floats each).  Outputs [nkf][nmp].
  * Asynchronous on `stream`; a candidate row that overflowed the per-stream scratch truncates silently:
- * orbfe_search_by_projection_batch_status(stream) reports it (and grows the scratch for a repeat). */
+ * orbfe_search_by_projection_batch_status(stream) reports it (and grows the scratch for a repeat).  Keyframe k searches its first
+ * min(d_n[k], capacity) keypoints (a negative count is 0); all nmp entries of both output blocks are written, -1 / 256 for a point
+ * that is not valid, does not project or has no candidate -- hence for every point of a keyframe without keypoints. */
 int orbfe_fuse_search_batch_device(const orbfe_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_n, int capacity, int nkf, int cols, int rows,
                                    const float* bounds, const float* d_p3Dw, const uint8_t* d_valid, const float* d_min_dist,
                                    const float* d_max_dist, const float* d_normal, const uint8_t* d_mp_desc, int nmp, const float* Tcw,
@@ -399,7 +411,10 @@ int orbfe_search_by_projection_keyframe(const orbfe_keypoint* kps_cur, const uin
 
 /* Batched device variant over npairs frame pairs (frame t vs t-1 of a stream); all arrays are blocks of `capacity`
  * records per frame; pair p matches frame p (as F1) against frame p+1 (as F2). prev_matched == NULL means
- * "start from F1's own keypoint positions" (what Tracking does on the first call, src/Tracking.cc:520-523). */
+ * "start from F1's own keypoint positions" (what Tracking does on the first call, src/Tracking.cc:520-523).
+ * The counts are the caller's duty, 0 <= d_n[f] <= capacity <= 65535: they are not clamped.  Records past d_n[f] are not read.
+ * d_matches12 block p gets d_n[p] entries, the entries from there to `capacity` are not written; d_nmatches[p] is always written
+ * (0 when either frame is empty).  Asynchronous on `stream`. */
 int orbfe_search_for_initialization_batch_device(const orbfe_keypoint* d_kps, const uint8_t* d_desc,
                                                  const int32_t* d_n, int capacity, int npairs, int cols, int rows, const float* bounds,
                                                  int window_size, float nnratio, int check_orientation,
@@ -407,9 +422,10 @@ int orbfe_search_for_initialization_batch_device(const orbfe_keypoint* d_kps, co
 /* The batch entry point cannot return a capacity error either (the host-pointer one retries by itself): the candidate rows of a
  * frame pair live in one pool, and a pair that needs more entries than the pool holds loses rows.  After a batch issued by THIS
  * thread on `stream` (synchronises the stream): *overflow = 0, or the number of pool entries the fullest pair needed -- the batch's
- * matches are then incomplete; the per-stream pool has been grown, so repeating the batch call succeeds.  More than 1024 level-0
- * keypoints in a frame: ORBFE_ERR_CAPACITY (*overflow = that count).  The flag covers every batch since it was last read (reading
- * clears it). */
+ * matches are then incomplete; the per-stream pool has been grown, so repeating the batch call succeeds.  Only the pairs that
+ * needed more than the pool are incomplete: every pair has a pool of its own.  More than 1024 level-0 keypoints in a frame:
+ * ORBFE_ERR_CAPACITY (*overflow = that count, also when a pool overflowed in the same batch; only the pairs that frame belongs to
+ * are wrong).  The flag covers every batch since it was last read (reading clears it, an error included). */
 int orbfe_search_for_initialization_batch_status(void* stream, int32_t* overflow);
 
 /* ------------------------------------------------------------ monocular two-view initializer -- */
@@ -605,7 +621,11 @@ int orbfe_pose_gather_device(const int32_t* d_match_cur, const int32_t* d_n, int
  * offsets[p] .. offsets[p + 1] of desc, in the order of its observation map), the one with the least median Hamming distance
  * to the others -- median = sorted row[(int)(0.5 * (N - 1))], first row wins ties.  best_idx[p] = its index inside the point's
  * list (-1 for a point without descriptors, which the reference leaves untouched); best_desc (may be NULL) receives the chosen
- * descriptor (npoints x 32).  At most 256 observations per point.  Host pointers / device pointers + stream. */
+ * descriptor (npoints x 32).  At most 256 observations per point.  Host pointers / device pointers + stream.
+ * The host call checks the offsets (start at 0, non-decreasing) and returns ORBFE_ERR_CAPACITY for a point with more than 256
+ * observations.  The device call cannot look at them: the offsets are the caller's duty, and a point with more than 256
+ * observations is answered from its FIRST 256 -- best_idx in [0, 256) is what the call returns for those rows alone, the later
+ * rows are not read.  best_desc of a point without descriptors is not written. */
 int orbfe_distinctive_descriptors(const uint8_t* desc, const int32_t* offsets, int npoints, int32_t* best_idx, uint8_t* best_desc, int device);
 int orbfe_distinctive_descriptors_device(const uint8_t* d_desc, const int32_t* d_offsets, int npoints, int32_t* d_best_idx, uint8_t* d_best_desc,
                                          void* stream);
@@ -638,7 +658,11 @@ int orbfe_vocabulary_transform(orbfe_vocabulary* v, const uint8_t* desc, int n, 
                                double* weight, uint32_t* bow_word, double* bow_value, int32_t* nbow, uint32_t* fv_node,
                                int32_t* fv_offset, uint32_t* fv_feature, int32_t* nfv);
 /* Batch on the device over the extractor's output (blocks of `capacity` records per frame, d_n[f] valid; fv_offset
- * blocks are capacity + 1).  d_word / d_node / d_weight are required (scratch for the vector kernel). */
+ * blocks are capacity + 1).  d_word / d_node / d_weight are required (scratch for the vector kernel).
+ * A frame transforms its first min(d_n[f], capacity) descriptors, a negative count is 0.  Written per frame: that many entries of
+ * d_word / d_node / d_weight, d_nbow[f] entries of the BowVector, d_nfv[f] node ids, d_nfv[f] + 1 offsets and
+ * d_fv_offset[f][d_nfv[f]] feature indices; everything behind them in a block is left alone.  An empty frame gives
+ * d_nbow[f] = d_nfv[f] = 0 and d_fv_offset[f][0] = 0.  Asynchronous on `stream`. */
 int orbfe_vocabulary_transform_batch_device(orbfe_vocabulary* v, const uint8_t* d_desc, const int32_t* d_n, int capacity, int nframes,
                                             int levelsup, int32_t* d_word, int32_t* d_node, double* d_weight, uint32_t* d_bow_word,
                                             double* d_bow_value, int32_t* d_nbow, uint32_t* d_fv_node, int32_t* d_fv_offset,
@@ -660,7 +684,9 @@ int orbfe_search_by_bow(const orbfe_keypoint* kps1, const uint8_t* desc1, const 
 /* Batch over npairs pairs of frames of one set of per-frame blocks (the layouts of orbfe_extract_batch_device and
  * orbfe_vocabulary_transform_batch_device; d_valid may be NULL): pair p matches frame d_pair1[p] (side 1) with frame
  * d_pair2[p] (side 2); NULL index arrays mean p and p + 1.  use_valid2 != 0 applies d_valid to side 2 as well.
- * d_match12 / d_match21 are blocks of `capacity` per pair. */
+ * d_match12 / d_match21 are blocks of `capacity` per pair: min(d_n[f], capacity) entries are written for the pair's side-1 resp.
+ * side-2 frame (a negative count is 0), the rest of a block is left alone; d_nmatches[p] is always written.  A frame may be paired
+ * with itself and a pair may occur twice.  Asynchronous on `stream`. */
 int orbfe_search_by_bow_batch_device(const orbfe_keypoint* d_kps, const uint8_t* d_desc, const uint8_t* d_valid, const int32_t* d_n,
                                      const uint32_t* d_fv_node, const int32_t* d_fv_offset, const uint32_t* d_fv_feature,
                                      const int32_t* d_nfv, int capacity, const int32_t* d_pair1, const int32_t* d_pair2, int npairs,
@@ -680,7 +706,8 @@ int orbfe_search_for_triangulation(const orbfe_keypoint* kps1, const uint8_t* de
                                    const float* level_sigma2_2, int nlevels, int check_orientation, int32_t* match12, int32_t* nmatches,
                                    int device);
 /* Batch over pairs of frames as orbfe_search_by_bow_batch_device; d_free[i] != 0 = "feature i has no map point" (NULL = all),
- * d_F12 npairs x 9 and d_epipole npairs x 2 on the device, the level tables on the host; d_scratch21 = capacity ints per pair. */
+ * d_F12 npairs x 9 and d_epipole npairs x 2 on the device, the level tables on the host; d_scratch21 = capacity ints per pair.
+ * Counts and written rows as there.  An all-zero F12 has no epipolar line: 0 matches. */
 int orbfe_search_for_triangulation_batch_device(const orbfe_keypoint* d_kps, const uint8_t* d_desc, const uint8_t* d_free, const int32_t* d_n,
                                                 const uint32_t* d_fv_node, const int32_t* d_fv_offset, const uint32_t* d_fv_feature,
                                                 const int32_t* d_nfv, int capacity, const int32_t* d_pair1, const int32_t* d_pair2, int npairs,
@@ -698,7 +725,9 @@ int orbfe_undistort_points(const float* src, int n, const float* K4, const float
 
 /* Frame::UndistortKeyPoints over a batch of extractor outputs on the device: frame f's first min(d_n[f], capacity)
  * records get undistorted (x, y), every other field is kept (Frame.cc:379-386); with ndist == 0 or dist[0] == 0 the
- * records are copied unchanged (:359-363).  d_kps_un may equal d_kps. */
+ * records are copied unchanged (:359-363).  d_kps_un may equal d_kps.  A negative count is 0.  With coefficients the records
+ * from min(d_n[f], capacity) to `capacity` of d_kps_un are not written; the copy of ndist == 0 / dist[0] == 0 is of whole blocks, so
+ * there d_kps_un receives those records of d_kps as well, bit for bit.  Asynchronous on `stream`. */
 int orbfe_undistort_keypoints_batch_device(const orbfe_keypoint* d_kps, const int32_t* d_n, int capacity, int nframes,
                                            const float* K4, const float* dist, int ndist, orbfe_keypoint* d_kps_un, void* stream);
 

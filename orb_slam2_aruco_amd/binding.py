@@ -66,6 +66,10 @@ SYMBOLS = [
 _lib = None
 
 
+# return codes of include/orbfe.h
+ORBFE_OK, ORBFE_ERR_INVALID, ORBFE_ERR_NO_DEVICE, ORBFE_ERR_HIP, ORBFE_ERR_CAPACITY, ORBFE_ERR_DICT = 0, -1, -2, -3, -4, -5
+
+
 class OrbfeError(RuntimeError):
     pass
 

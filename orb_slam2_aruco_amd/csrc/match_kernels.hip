@@ -1432,9 +1432,9 @@ static int sfi_launch(const orbfe_keypoint* d_kps, const uint8_t* d_desc, const 
 static int sfi_take_flags(MatchWorkspace& w, const int32_t* f, hipStream_t s, int32_t* need)
 {
     if (f[0] || f[1]) ORBFE_HIP(hipMemsetAsync(w.sfi_overflow.p, 0, 8, s)); // sticky until read
-    *need = std::max(f[0], f[1]);
-    if (f[0] > SFI_MAXL0) return fail(ORBFE_ERR_CAPACITY, "%d level-0 keypoints in a frame exceed the supported %d", f[0], SFI_MAXL0);
     if (f[1] > w.csr_per_pair) w.csr_per_pair = (f[1] + 1023) / 1024 * 1024; // the next batch on this stream has the room
+    *need = f[0] > SFI_MAXL0 ? f[0] : f[1]; // the level-0 count goes with the error, also when a pool overflowed in the same batch
+    if (f[0] > SFI_MAXL0) return fail(ORBFE_ERR_CAPACITY, "%d level-0 keypoints in a frame exceed the supported %d", f[0], SFI_MAXL0);
     return ORBFE_OK;
 }
 

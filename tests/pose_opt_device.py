@@ -39,6 +39,12 @@ class Dev:
                                                         self.a.nbytes, 1) != 0:
             raise RuntimeError("orbfe_device_upload_rows: %s" % L.orbfe_last_error().decode())
 
+    def put(self, a):
+        """the same bytes again from another array of this shape and dtype"""
+        src = np.ascontiguousarray(a, self.a.dtype).reshape(self.a.shape)
+        if src.nbytes and _lib().orbfe_device_upload_rows(self.ptr, src.nbytes, src.ctypes.data_as(C.c_void_p), src.nbytes, src.nbytes, 1) != 0:
+            raise RuntimeError("orbfe_device_upload_rows: %s" % _lib().orbfe_last_error().decode())
+
     def get(self):
         out = np.empty_like(self.a)
         if out.nbytes and _lib().orbfe_device_download(out.ctypes.data_as(C.c_void_p), self.ptr, out.nbytes) != 0:

@@ -2,6 +2,7 @@
 import numpy as np
 import pytest
 
+from match_batch_cases import flip_bits as _flip_bits, patch_keypoints as _patch_keypoints
 from orb_slam2_aruco_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -540,24 +541,6 @@ def _in_fresh_thread(fn):
     if "error" in box:
         raise box["error"]
     return box["value"]
-
-
-def _patch_keypoints(rng, dtype, n, x0, y0, side, octaves=1):
-    """n keypoints scattered over the square patch of `side` pixels at (x0, y0)"""
-    k = np.zeros(n, dtype)
-    k["x"] = x0 + rng.random(n, dtype=np.float32) * side
-    k["y"] = y0 + rng.random(n, dtype=np.float32) * side
-    k["size"] = 31.0; k["angle"] = rng.random(n, dtype=np.float32) * 360.0; k["response"] = 50.0
-    k["octave"] = rng.integers(0, octaves, n); k["class_id"] = -1
-    return k
-
-
-def _flip_bits(rng, desc, most):
-    d = desc.copy()
-    for i in range(len(d)):
-        for b in rng.integers(0, 256, 8)[: rng.integers(0, most + 1)]:
-            d[i, b >> 3] ^= np.uint8(1 << (b & 7))
-    return d
 
 
 @pytest.mark.gpu
