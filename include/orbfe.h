@@ -36,7 +36,8 @@
  * like the classes it replaces (one handle per stream of frames).  The
  * matching functions are thread-safe (device scratch per calling thread, device and stream, released when the thread
  * exits); so is orbfe_vocabulary_transform on one shared
- * vocabulary handle (ComputeBoW runs on the Tracking, LocalMapping and LoopClosing threads).
+ * vocabulary handle, and it does not serialise the callers (ComputeBoW runs on the Tracking, LocalMapping and LoopClosing
+ * threads: the handle is read-only, each thread stages in its own scratch).  orbfe_corner_subpix: scratch per (thread, device).
  */
 #ifndef ORBFE_H
 #define ORBFE_H

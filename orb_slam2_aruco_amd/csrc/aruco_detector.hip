@@ -735,7 +735,7 @@ static int pose_camera(const float* K4, const float* dist, int ndist, float mark
     return ORBFE_OK;
 }
 
-static thread_local ThreadWorkspaces<HostStage> tl_pose_ws; // orbfe_marker_poses, per (thread, device)
+static thread_local ThreadWorkspaces<HostStage> tl_host_ws; // orbfe_marker_poses and orbfe_corner_subpix, per (thread, device)
 
 // ---- trackingMinDetections: host logic, as in the reference (it walks two short lists; the device supplies the candidates) ----
 namespace {
@@ -1454,25 +1454,28 @@ int orbfe_corner_subpix(const uint8_t* img, int rows, int cols, size_t step, flo
     if (n == 0) return ORBFE_OK;
     int rc = use_device(device);
     if (rc) return rc;
-    // the markers kernel on a scratch detector-free path: corners as n / 4 "markers" (padded), one frame
+    // the markers kernel without a detector: the corners as n / 4 "markers" (padded with the first corner), one frame
     const int nm = (n + 3) / 4;
-    DevBuf d_img, d_mk, d_n, d_mask;
     const size_t pitch = (size_t)(cols + 63) / 64 * 64;
-    if ((rc = d_img.ensure(pitch * rows + 64)) || (rc = d_mk.ensure((size_t)nm * sizeof(orbfe_marker))) || (rc = d_n.ensure(4)) || (rc = d_mask.ensure(17 * 17 * 4))) return rc;
-    std::vector<orbfe_marker> mk((size_t)nm);
-    memset(mk.data(), 0, mk.size() * sizeof(orbfe_marker));
-    for (int i = 0; i < n; i++) { mk[i >> 2].corners[i & 3][0] = pts[2 * i]; mk[i >> 2].corners[i & 3][1] = pts[2 * i + 1]; }
-    for (int i = n; i < 4 * nm; i++) { mk[i >> 2].corners[i & 3][0] = pts[0]; mk[i >> 2].corners[i & 3][1] = pts[1]; }
-    std::vector<float> mask((size_t)17 * 17, 0.f);
-    subpix_window(win, mask.data());
-    ORBFE_HIP(hipMemcpy2D(d_img.p, pitch, img, step, (size_t)cols, (size_t)rows, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(d_mk.p, mk.data(), mk.size() * sizeof(orbfe_marker), hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(d_n.p, &nm, 4, hipMemcpyHostToDevice));
-    ORBFE_HIP(hipMemcpy(d_mask.p, mask.data(), mask.size() * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_corner_subpix_markers, dim3(std::max(1, std::min(nm, 256)), 1), dim3(256), 0, 0, ImgView{d_img.as<uint8_t>(), nullptr, 0, (int)pitch}, cols, rows,
-                       d_mk.as<orbfe_marker>(), d_n.as<int32_t>(), nm, win, std::min(max_iters, 100), eps * eps, d_mask.as<float>());
+    HostStage& w = tl_host_ws.get();
+    IoLayout l;
+    const size_t i_img = l.take(pitch * rows + 64), i_mask = l.take(17 * 17 * 4), i_n = l.take(4);
+    l.inout();
+    const size_t io_mk = l.take((size_t)nm * sizeof(orbfe_marker));
+    l.outputs();
+    if ((rc = w.begin(l))) return rc;
+    for (int y = 0; y < rows; y++) w.put(i_img + (size_t)y * pitch, img + (size_t)y * step, (size_t)cols);
+    subpix_window(win, w.host<float>(i_mask));
+    w.put(i_n, &nm, 4);
+    orbfe_marker* mk = w.host<orbfe_marker>(io_mk);
+    memset(mk, 0, (size_t)nm * sizeof(orbfe_marker));
+    for (int i = 0; i < 4 * nm; i++) { const int s = i < n ? i : 0; mk[i >> 2].corners[i & 3][0] = pts[2 * s]; mk[i >> 2].corners[i & 3][1] = pts[2 * s + 1]; }
+    if ((rc = w.upload())) return rc;
+    hipLaunchKernelGGL(k_corner_subpix_markers, dim3(std::max(1, std::min(nm, 256)), 1), dim3(256), 0, w.stream,
+                       ImgView{w.dev<uint8_t>(i_img), nullptr, 0, (int)pitch}, cols, rows, w.dev<orbfe_marker>(io_mk), w.dev<int32_t>(i_n), nm, win,
+                       std::min(max_iters, 100), eps * eps, w.dev<float>(i_mask));
     ORBFE_HIP(hipGetLastError());
-    ORBFE_HIP(hipMemcpy(mk.data(), d_mk.p, mk.size() * sizeof(orbfe_marker), hipMemcpyDeviceToHost));
+    if ((rc = w.download()) || (rc = w.sync())) return rc;
     for (int i = 0; i < n; i++) { pts[2 * i] = mk[i >> 2].corners[i & 3][0]; pts[2 * i + 1] = mk[i >> 2].corners[i & 3][1]; }
     return ORBFE_OK;
 }
@@ -1620,7 +1623,7 @@ int orbfe_marker_poses(const orbfe_marker* markers, int n, float marker_size, co
     int rc = pose_camera(K4, dist, ndist, marker_size, c, "orbfe_marker_poses");
     if (rc || (rc = use_device(device))) return rc;
     if (n == 0) return ORBFE_OK;
-    HostStage& w = tl_pose_ws.get();
+    HostStage& w = tl_host_ws.get();
     const size_t pb = (size_t)n * sizeof(orbfe_marker_pose);
     IoLayout l;
     const size_t i_mk = l.take((size_t)n * sizeof(orbfe_marker));

@@ -13,7 +13,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
 #include <string>
 #include <vector>
 
@@ -30,10 +29,8 @@ using namespace orbfe;
 struct orbfe_vocabulary {
     int device = 0;
     int k = 0, L = 0, scoring = 0, weighting = 0, nnodes = 0, nwords = 0;
-    DevBuf info, child_node, child_desc, word_id, weight;                     // the tree
-    DevBuf w_desc, w_n, w_word, w_nid, w_weight;                              // host-pointer calls: staging
-    DevBuf w_bw, w_bv, w_nb, w_fn, w_fo, w_ff, w_nf;
-    std::mutex staging; // ComputeBoW is called from the Tracking, LocalMapping and LoopClosing threads on ONE vocabulary
+    DevBuf info, child_node, child_desc, word_id, weight; // the tree
+    // immutable once created (blocking uploads): concurrent transforms on one handle need no lock, each stages in its thread's stage
 };
 
 namespace {
@@ -463,9 +460,7 @@ VocView view(const orbfe_vocabulary* v)
 
 void release(orbfe_vocabulary* v)
 {
-    for (DevBuf* b : {&v->info, &v->child_node, &v->child_desc, &v->word_id, &v->weight, &v->w_desc, &v->w_n, &v->w_word, &v->w_nid,
-                      &v->w_weight, &v->w_bw, &v->w_bv, &v->w_nb, &v->w_fn, &v->w_fo, &v->w_ff, &v->w_nf})
-        b->release();
+    for (DevBuf* b : {&v->info, &v->child_node, &v->child_desc, &v->word_id, &v->weight}) b->release();
 }
 
 } // namespace
@@ -622,34 +617,30 @@ int orbfe_vocabulary_transform(orbfe_vocabulary* v, const uint8_t* desc, int n, 
     if (rc) return rc;
     if (vectors) { *nbow = 0; *nfv = 0; fv_offset[0] = 0; }
     if (n == 0) return ORBFE_OK;
-    std::lock_guard<std::mutex> lock(v->staging); // the handle's staging buffers are shared by the calling threads
-    const size_t N = (size_t)n;
-    if ((rc = v->w_desc.ensure(N * 32)) || (rc = v->w_word.ensure(N * 4)) || (rc = v->w_nid.ensure(N * 4)) || (rc = v->w_weight.ensure(N * 8)) ||
-        (rc = v->w_bw.ensure(N * 4)) || (rc = v->w_bv.ensure(N * 8)) || (rc = v->w_nb.ensure(16)) || (rc = v->w_fn.ensure(N * 4)) ||
-        (rc = v->w_fo.ensure((N + 1) * 4)) || (rc = v->w_ff.ensure(N * 4)) || (rc = v->w_nf.ensure(16)))
+    if (vectors && n > BV_MAX) return fail(ORBFE_ERR_CAPACITY, "orbfe_vocabulary_transform: at most %d features per frame", BV_MAX);
+    HostStage& w = match_host_stage();
+    const size_t N = (size_t)n, V = vectors ? N : 0, one = vectors ? 4 : 0; // the vector outputs take no room when nobody asks for them
+    IoLayout l;
+    const size_t i_desc = l.take(N * 32);
+    l.outputs();
+    const size_t o_word = l.take(N * 4), o_node = l.take(N * 4), o_weight = l.take(N * 8), o_bw = l.take(V * 4), o_bv = l.take(V * 8),
+                 o_nb = l.take(one), o_fn = l.take(V * 4), o_fo = l.take(vectors ? (N + 1) * 4 : 0), o_ff = l.take(V * 4), o_nf = l.take(one);
+    if ((rc = w.begin(l))) return rc;
+    w.put(i_desc, desc, N * 32);
+    if ((rc = w.upload()) ||
+        (rc = orbfe_vocabulary_transform_batch_device(
+             v, w.dev<uint8_t>(i_desc), nullptr, n, 1, levelsup, w.dev<int32_t>(o_word), w.dev<int32_t>(o_node), w.dev<double>(o_weight),
+             vectors ? w.dev<uint32_t>(o_bw) : nullptr, vectors ? w.dev<double>(o_bv) : nullptr, vectors ? w.dev<int32_t>(o_nb) : nullptr,
+             vectors ? w.dev<uint32_t>(o_fn) : nullptr, vectors ? w.dev<int32_t>(o_fo) : nullptr, vectors ? w.dev<uint32_t>(o_ff) : nullptr,
+             vectors ? w.dev<int32_t>(o_nf) : nullptr, w.stream)) ||
+        (rc = w.download()) || (rc = w.sync()))
         return rc;
-    ORBFE_HIP(hipMemcpy(v->w_desc.p, desc, N * 32, hipMemcpyHostToDevice));
-    rc = orbfe_vocabulary_transform_batch_device(
-        v, v->w_desc.as<uint8_t>(), nullptr, n, 1, levelsup, v->w_word.as<int32_t>(), v->w_nid.as<int32_t>(), v->w_weight.as<double>(),
-        vectors ? v->w_bw.as<uint32_t>() : nullptr, vectors ? v->w_bv.as<double>() : nullptr, vectors ? v->w_nb.as<int32_t>() : nullptr,
-        vectors ? v->w_fn.as<uint32_t>() : nullptr, vectors ? v->w_fo.as<int32_t>() : nullptr, vectors ? v->w_ff.as<uint32_t>() : nullptr,
-        vectors ? v->w_nf.as<int32_t>() : nullptr, nullptr);
-    if (rc) return rc;
-    if (word_id) ORBFE_HIP(hipMemcpy(word_id, v->w_word.p, N * 4, hipMemcpyDeviceToHost));
-    if (node_id) ORBFE_HIP(hipMemcpy(node_id, v->w_nid.p, N * 4, hipMemcpyDeviceToHost));
-    if (weight) ORBFE_HIP(hipMemcpy(weight, v->w_weight.p, N * 8, hipMemcpyDeviceToHost));
-    if (vectors) {
-        ORBFE_HIP(hipMemcpy(nbow, v->w_nb.p, 4, hipMemcpyDeviceToHost));
-        ORBFE_HIP(hipMemcpy(nfv, v->w_nf.p, 4, hipMemcpyDeviceToHost));
-        if (*nbow) {
-            ORBFE_HIP(hipMemcpy(bow_word, v->w_bw.p, (size_t)*nbow * 4, hipMemcpyDeviceToHost));
-            ORBFE_HIP(hipMemcpy(bow_value, v->w_bv.p, (size_t)*nbow * 8, hipMemcpyDeviceToHost));
-        }
-        ORBFE_HIP(hipMemcpy(fv_offset, v->w_fo.p, (size_t)(*nfv + 1) * 4, hipMemcpyDeviceToHost));
-        if (*nfv) {
-            ORBFE_HIP(hipMemcpy(fv_node, v->w_fn.p, (size_t)*nfv * 4, hipMemcpyDeviceToHost));
-            ORBFE_HIP(hipMemcpy(fv_feature, v->w_ff.p, (size_t)fv_offset[*nfv] * 4, hipMemcpyDeviceToHost));
-        }
+    w.get(word_id, o_word, N * 4); w.get(node_id, o_node, N * 4); w.get(weight, o_weight, N * 8);
+    if (vectors) { // only what the frame filled: the caller's arrays stay untouched behind it
+        w.get(nbow, o_nb, 4); w.get(nfv, o_nf, 4);
+        w.get(bow_word, o_bw, (size_t)*nbow * 4); w.get(bow_value, o_bv, (size_t)*nbow * 8);
+        w.get(fv_offset, o_fo, (size_t)(*nfv + 1) * 4);
+        w.get(fv_node, o_fn, (size_t)*nfv * 4); w.get(fv_feature, o_ff, (size_t)fv_offset[*nfv] * 4);
     }
     return ORBFE_OK;
 }

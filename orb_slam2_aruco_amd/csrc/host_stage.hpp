@@ -1,6 +1,6 @@
 // host_stage.hpp -- what the host-pointer entry points of the geometry solvers (initializer.hip, sim3_solver.hip, pose_optimizer.hip,
-// orbfe_marker_poses) and of the matcher (match_kernels.hip, bow_vocabulary.hip, keyframe_io.hip) share: the layout of one staging
-// block and the workspace that moves it.  Host code only.
+// orbfe_marker_poses, orbfe_corner_subpix) and of the matcher (match_kernels.hip, bow_vocabulary.hip, keyframe_io.hip) share: the
+// layout of one staging block and the workspace that moves it.  Host code only.
 #pragma once
 #include <cstddef>
 

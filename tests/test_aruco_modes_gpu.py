@@ -3,6 +3,7 @@ DM_FAST / DM_VIDEO_FAST (THRES_AUTO_FIXED with its rand() retries and frame-to-f
 Params::minSize > 0 (reduced working image + cornerUpsample), CORNER_SUBPIX, CV_8UC3 input, cv::cornerSubPix by itself.
 rand() is the process's sequence on both sides: every sequence is run once per side behind the same srand()."""
 import ctypes
+import threading
 
 import numpy as np
 import pytest
@@ -258,6 +259,51 @@ def test_corner_subpix_primitive(orbfe, oracle, win, iters, eps):
     flat = np.full((64, 64), 77, np.uint8)
     p = np.array([[30.5, 31.25]], np.float32)
     assert np.array_equal(orbfe.corner_subpix(flat, p, win, iters, eps), p)
+
+
+def _raw_corner_subpix(orbfe, img, pts, win, iters, eps):
+    """orbfe_corner_subpix itself: the image as a view with step = cols + 13 into a poison-filled array, pts inside guards;
+    asserts that the slack bytes of the image and the guards are unchanged -> the refined points"""
+    rows, cols = img.shape
+    wide = np.full((rows, cols + 13), 0xA5, np.uint8)
+    wide[:, :cols] = img
+    before = wide.copy()
+    guard = 16
+    buf = np.full(2 * len(pts) + 2 * guard, np.float32(-12345.5), np.float32)
+    buf[guard:guard + 2 * len(pts)] = np.asarray(pts, np.float32).reshape(-1)
+    L = orbfe.load()
+    rc = L.orbfe_corner_subpix(wide.ctypes.data_as(ctypes.c_void_p), rows, cols, wide.strides[0], buf[guard:].ctypes.data_as(ctypes.c_void_p), len(pts),
+                               win, iters, eps, 0)
+    assert rc == 0, L.orbfe_last_error().decode()
+    assert np.array_equal(wide, before), "the image or its slack bytes were written"
+    assert np.all(buf[:guard] == np.float32(-12345.5)) and np.all(buf[guard + 2 * len(pts):] == np.float32(-12345.5)), "guards around pts"
+    return buf[guard:guard + 2 * len(pts)].reshape(-1, 2).copy()
+
+
+@pytest.mark.parametrize("n", [1, 4, 5])                      # the corners travel as (n + 3) / 4 padded "markers"
+def test_corner_subpix_strided_image_and_guarded_points(orbfe, oracle, n):
+    img, truth = synth.scene(480, 640, 8, "ARUCO", 5)
+    rng = np.random.default_rng(4)
+    pts = np.array([c for t in truth for c in np.asarray(t[1], np.float32).reshape(4, 2)], np.float32)
+    pts = (pts + rng.uniform(-1.5, 1.5, pts.shape).astype(np.float32))[:n]
+    assert len(pts) == n
+    got = _raw_corner_subpix(orbfe, img, pts, 4, 12, 0.005)
+    assert np.array_equal(got, orbfe.corner_subpix(img, pts, 4, 12, 0.005))
+    assert np.array_equal(got, oracle.corner_subpix(img, pts, 4, 12, 0.005))
+    assert np.abs(got - pts).max() > 0.05                     # something moved
+    # two image sizes in a row through one stage (pitch 64, then 128) = each as the only call of a thread of its own
+    cx, cy = (int(v) for v in pts[0])
+    x0, y0 = min(max(cx - 32, 0), 640 - 96), min(max(cy - 32, 0), 480 - 64)
+    small = [np.ascontiguousarray(img[y0:y0 + 64, x0:x0 + 64]), np.ascontiguousarray(img[y0:y0 + 40, x0:x0 + 96])]
+    q = np.vstack([pts[:1] - np.float32([x0, y0]), rng.uniform(2, 38, (n - 1, 2)).astype(np.float32)])
+    alone = []
+    for s in small:
+        t = threading.Thread(target=lambda: alone.append(orbfe.corner_subpix(s, q, 4, 12, 0.005)))
+        t.start(); t.join()
+    assert len(alone) == 2
+    for s, a in zip(small, alone):
+        assert np.array_equal(_raw_corner_subpix(orbfe, s, q, 4, 12, 0.005), a)
+        assert np.array_equal(a, oracle.corner_subpix(s, q, 4, 12, 0.005))
 
 
 def test_mode_setters_and_the_batch_entry_points(orbfe, oracle):

@@ -1,9 +1,14 @@
 """GPU parity: DBoW2 vocabulary transform through the C ABI vs the CPU oracle -- bit-exact, doubles included (the weights
 are added and normalised in the reference's map order on both sides)."""
+import ctypes as C
+import functools
+import threading
+
 import numpy as np
 import pytest
 
 import voc_cases as vc
+from orb_slam2_aruco_amd import binding
 
 pytestmark = pytest.mark.gpu
 
@@ -164,3 +169,145 @@ def test_search_for_triangulation(orbfe, oracle, seed, levelsup, ori):
     want = oracle.search_for_triangulation(k1, d1, fv1, k1, d1, fv1, F12, (1e5, 1e5), sf, sg, None, None, True)
     got = orbfe.search_for_triangulation(k1, d1, fv1, k1, d1, fv1, F12, (1e5, 1e5), sf, sg, None, None, True)
     assert got[0] == want[0] and np.array_equal(got[1], want[1]) and got[0] > 500
+
+
+# ---- orbfe_vocabulary_transform as a host-stage call: the raw function, poison around every range it may write --------------------
+_OUTS = (("word", np.int32, 0), ("node", np.int32, 0), ("weight", np.float64, 0), ("bow_word", np.uint32, 0), ("bow_value", np.float64, 0),
+         ("nbow", np.int32, 1), ("fv_node", np.uint32, 0), ("fv_offset", np.int32, 0), ("fv_feature", np.uint32, 0), ("nfv", np.int32, 1))
+_VECTORS = [name for name, _, _ in _OUTS[3:]]
+_PAD = 8
+
+
+@functools.lru_cache(maxsize=None)
+def _voc(k, L, seed):
+    import oracle_lib
+    voc = vc.make(k, L, seed)
+    args = (k, L, 0, 0, voc["parent"], voc["is_leaf"], voc["desc"], voc["weight"])
+    return voc, oracle_lib.VocabularyOracle.from_arrays(*args), binding.ORBVocabulary.from_arrays(*args)
+
+
+@functools.lru_cache(maxsize=None)
+def _features(k, L, seed, n):
+    f = vc.features(_voc(k, L, seed)[0], n, seed + 100)
+    f.setflags(write=False)
+    return f
+
+
+def _poison(count, dtype):
+    return np.full(count * np.dtype(dtype).itemsize, 0xA5, np.uint8).view(dtype)
+
+
+def _raw_transform(g, feats, levelsup, absent=()):
+    """orbfe_vocabulary_transform itself -> (return code, the output arrays: poison-filled, n + 8 entries (fv_offset one more))"""
+    n = len(feats)
+    out = {name: _poison((1 if scalar else n + (name == "fv_offset")) + _PAD, dt) for name, dt, scalar in _OUTS}
+    ptr = [None if name in absent else out[name].ctypes.data_as(C.c_void_p) for name, _, _ in _OUTS]
+    rc = g.L.orbfe_vocabulary_transform(g.h, feats.ctypes.data_as(C.c_void_p), n, levelsup, *ptr)
+    return rc, out
+
+
+def _written(out, n, absent=()):
+    """entries of every output the call may have written; asserts that everything behind them is still poison"""
+    vectors = not set(_VECTORS) & set(absent)
+    nb, nf = (int(out["nbow"][0]), int(out["nfv"][0])) if vectors else (0, 0)
+    count = dict(word=n, node=n, weight=n, nbow=1, nfv=1, bow_word=nb, bow_value=nb, fv_node=nf, fv_offset=nf + 1,
+                 fv_feature=int(out["fv_offset"][nf]) if vectors else 0)
+    got = {}
+    for name, dt, _ in _OUTS:
+        c = 0 if name in absent or (name in _VECTORS and not vectors) else count[name]
+        assert np.array_equal(out[name][c:].view(np.uint8), _poison(len(out[name]) - c, dt).view(np.uint8)), name + ": written behind its range"
+        got[name] = out[name][:c]
+    return got
+
+
+def _as_result(w):
+    return dict(word=w["word"], node=w["node"], weight=w["weight"], bow=(w["bow_word"], w["bow_value"]),
+                fv=(w["fv_node"], w["fv_offset"], w["fv_feature"]))
+
+
+def _batch_transform(g, feats, levelsup):
+    """orbfe_vocabulary_transform_batch_device on one frame of capacity n, no count array, null stream -> the whole output arrays"""
+    from pose_opt_device import Dev
+    n = len(feats)
+    d_desc = Dev(feats)
+    dev = {name: Dev(np.zeros((1 if scalar else n + (name == "fv_offset")), dt)) for name, dt, scalar in _OUTS}
+    rc = g.L.orbfe_vocabulary_transform_batch_device(g.h, d_desc.ptr, None, n, 1, levelsup, *[dev[name].ptr for name, _, _ in _OUTS], None)
+    assert rc == 0, g.L.orbfe_last_error().decode()
+    return {name: d.get() for name, d in dev.items()}
+
+
+def _bits(a):
+    return a.view(np.uint64) if a.dtype == np.float64 else a
+
+
+@pytest.mark.parametrize("levelsup", [1, 4])
+@pytest.mark.parametrize("n", [1, 255, 256, 257, 4096])       # k_bow_descend: blocks of 256 lanes; 4096 = BV_MAX
+@pytest.mark.parametrize("k,L,seed", [(10, 3, 41), (4, 5, 42)])
+def test_host_transform_equals_batch_call_prefix_exact(k, L, seed, n, levelsup):
+    _, o, g = _voc(k, L, seed)
+    feats = _features(k, L, seed, n)
+    rc, out = _raw_transform(g, feats, levelsup)
+    assert rc == 0, g.L.orbfe_last_error().decode()
+    got = _written(out, n)
+    want = _batch_transform(g, feats, levelsup)
+    for name, _, _ in _OUTS:
+        assert np.array_equal(_bits(got[name]), _bits(want[name][:len(got[name])])), name
+    _same(_as_result(got), o.transform(feats, levelsup))
+
+
+def test_host_transform_absent_outputs():
+    _, o, g = _voc(10, 3, 41)
+    big = _features(10, 3, 41, 5000)                          # above BV_MAX: allowed without the vectors
+    rc, out = _raw_transform(g, big, 4, absent=_VECTORS)
+    assert rc == 0, g.L.orbfe_last_error().decode()
+    got, want = _written(out, 5000, absent=_VECTORS), o.transform(big, 4)
+    assert np.array_equal(got["word"], want["word"]) and np.array_equal(got["node"], want["node"])
+    assert np.array_equal(_bits(got["weight"]), _bits(want["weight"]))
+    rc, _ = _raw_transform(g, big, 4)
+    assert rc == binding.ORBFE_ERR_CAPACITY
+    feats = _features(10, 3, 41, 700)
+    rc, full = _raw_transform(g, feats, 2)
+    assert rc == 0
+    rc, out = _raw_transform(g, feats, 2, absent=("word",))
+    assert rc == 0, g.L.orbfe_last_error().decode()
+    got, ref = _written(out, 700, absent=("word",)), _written(full, 700)
+    for name, _, _ in _OUTS[1:]:
+        assert np.array_equal(_bits(got[name]), _bits(ref[name])), name
+    _same(_as_result(ref), o.transform(feats, 2))
+    for missing in _VECTORS:                                  # the vector outputs are all or none
+        rc, _ = _raw_transform(g, feats, 2, absent=(missing,))
+        assert rc == binding.ORBFE_ERR_INVALID, missing
+
+
+def test_one_vocabulary_three_threads():
+    """ComputeBoW from the Tracking, LocalMapping and LoopClosing threads on ONE vocabulary, and a fourth thread on another."""
+    _, _, shared = _voc(10, 3, 41)
+    _, _, other = _voc(4, 5, 42)
+    jobs = [(shared, _features(10, 3, 41, n)) for n in (65, 700, 2000)] + [(other, _features(4, 5, 42, 900))]
+    serial = [g.transform(f, 2) for g, f in jobs]
+    errors = []
+
+    def work(g, feats, want):
+        try:
+            for _ in range(20):
+                _same(g.transform(feats, 2), want)
+        except BaseException as e:  # noqa: BLE001
+            errors.append(e)
+
+    threads = [threading.Thread(target=work, args=(g, f, w)) for (g, f), w in zip(jobs, serial)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(60)
+    assert not any(t.is_alive() for t in threads), "a transform did not return"
+    assert not errors, errors
+
+
+def test_two_vocabularies_alternating_share_one_stage():
+    _, o1, g1 = _voc(10, 3, 41)
+    _, o2, g2 = _voc(3, 2, 43)
+    f1, f2 = _features(10, 3, 41, 2000), _features(3, 2, 43, 7)
+    w1, w2 = o1.transform(f1, 4), o2.transform(f2, 4)
+    for _ in range(5):
+        _same(g1.transform(f1, 4), w1)
+        _same(g2.transform(f2, 4), w2)

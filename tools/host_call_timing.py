@@ -1,6 +1,7 @@
-"""Host-clock medians of the matcher's host-pointer calls: orbfe_knn2 (700 x 900), orbfe_search_by_projection (1000 keypoints, 1000
-queries, mode 1), orbfe_search_by_bow (two frames of 1000 features) and orbfe_keyframe_features_pack (1000), 200 timings each through
-the ctypes binding.  ORBFE_LIB selects the library, so two builds can be run alternately; prints one JSON line."""
+"""Host-clock medians of the host-pointer calls that stage through a thread's host stage: orbfe_knn2 (700 x 900),
+orbfe_search_by_projection (1000 keypoints, 1000 queries, mode 1), orbfe_search_by_bow (two frames of 1000 features),
+orbfe_keyframe_features_pack (1000), orbfe_vocabulary_transform (1000 features, levelsup 2) and orbfe_corner_subpix (64 corners of a
+480 x 640 frame, window 4, 12 iterations, eps 0.005), 200 timings each through the ctypes binding.  ORBFE_LIB selects the library, so two builds can be run alternately; prints one JSON line."""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -36,6 +37,7 @@ q["x"] = k1["x"][pick] + rng.normal(0, 2, 1000).astype(np.float32); q["y"] = k1[
 q["r"] = (4.0 * 1.2 ** k1["octave"][pick]).astype(np.float32); q["min_level"] = k1["octave"][pick] - 1; q["max_level"] = k1["octave"][pick]
 qd = d1[pick]
 taken = (rng.random(len(k1)) < 0.15).astype(np.uint8)
+corners = np.stack([k1["x"][:64], k1["y"][:64]], 1).astype(np.float32)
 Q = rng.integers(0, 256, (700, 32), dtype=np.uint8); T = rng.integers(0, 256, (900, 32), dtype=np.uint8)
 
 calls = {
@@ -43,6 +45,8 @@ calls = {
     "orbfe_search_by_projection": lambda: binding.search_by_projection(k1, d1, 640, 480, q, qd, taken, 1, 100, 0.8),
     "orbfe_search_by_bow": lambda: binding.search_by_bow(k1, d1, fv1, k2, d2, fv2),
     "orbfe_keyframe_features_pack": lambda: binding.keyframe_features_pack(k1, d1),
+    "orbfe_vocabulary_transform": lambda: voc.transform(d1, 2),
+    "orbfe_corner_subpix": lambda: binding.corner_subpix(frames[0], corners, 4, 12, 0.005),
 }
 out = {"lib": binding.LIB_PATH, "reps": REPS, "n1": len(k1), "n2": len(k2)}
 for name, call in calls.items():
