@@ -25,6 +25,7 @@
  *   orbfe_pose_*        Optimizer::PoseOptimizationByAruco src/Optimizer.cc:522-770 (Tracking.cc:940, 1025, 1200, 1256, 1843)
  *                       Optimizer::PoseOptimization        src/Optimizer.cc:308-520, monocular
  *   orbfe_sim3_*        ORB_SLAM2::Sim3Solver              src/Sim3Solver.cc (LoopClosing.cc:402-425, :489-600)
+ *   orbfe_optimize_sim3* Optimizer::OptimizeSim3           src/Optimizer.cc:1544-1739 (LoopClosing.cc:425, :580)
  *
  * Memory convention: functions without a suffix take HOST pointers (drop-in for
  * the reference's call sites, which hand over cv::Mat / std::vector storage) and
@@ -560,6 +561,67 @@ int orbfe_sim3_inspect(const orbfe_keypoint* kps1, int n1, const float* x3Dw1, c
                        int max_iterations, int first_iteration, int n_iterations, int best_inliers_in, const int32_t* rand_words,
                        orbfe_sim3_result* res, uint8_t* inliers12, int32_t* n, int32_t* indices1, float* X3Dc1, float* X3Dc2, float* P1im1,
                        float* P2im2, float* maxError1, float* maxError2, int32_t* sets, float* models, int32_t* counts, int device);
+
+/* ------------------------------------------------------------ Sim3 refinement of loop closing -- */
+/* Optimizer::OptimizeSim3 (src/Optimizer.cc:1544-1739), the step of LoopClosing::ComputeSim3 between SearchBySim3 and
+ * SearchByProjection(pKF, Scw, ...) (src/LoopClosing.cc:425, :580; its return value decides the loop): Levenberg-Marquardt on the
+ * 7-DoF similarity S12 (g2o as ORB_SLAM2 vendors it, in double) over two reprojection edges per correspondence, optimize(5), a
+ * chi2 > th2 check that removes pairs, then optimize(10 or 5) on what is left and a second check.
+ * The sides are those of orbfe_sim3_solve: kps = mvKeysUn, x3Dw (n x 3), valid (both NULL = all), Tcw 3 x 4 row-major, K4 = fx, fy,
+ * cx, cy.  match12[i1] = i2 or -1 = vpMatches1 as orbfe_search_by_sim3 / orbfe_sim3_solve leave it.  Correspondence i is kept
+ * when match12[i] = i2 >= 0, valid1[i] and valid2[i2]; its points are P3Dkc = Rkw x + tkw in CV_32F (the Mat product of the Sim3
+ * solver), widened to double.  Edges, in this order per correspondence: e12 = obs1 - cam_map1(project(S12.map(P2c))), information
+ * inv_level_sigma2[octave of kps1[i]] * I; e21 = obs2 - cam_map2(project(S12.inverse().map(P1c))), information
+ * inv_level_sigma2[octave of kps2[i2]] * I (inv_level_sigma2 = mvInvLevelSigma2, nlevels <= 32 entries, floats widened).  Huber,
+ * delta = (double)sqrtf(th2), in both rounds.  The Jacobian is g2o's numeric one (central differences, delta = 1e-9, through
+ * Sim3(update) * estimate); with fix_scale the update's 7th component is zeroed, column 6 of every Jacobian is exactly 0 and
+ * H(6, 6) is lambda alone.  A pair is bad when either chi2 > (double)th2, read from the errors the edges cached last -- those of
+ * a rejected trial when the round ended on one (stale_mask).  The initial similarity is g2o::Sim3(R12, t12, s12) of the floats:
+ * both call sites build it from float cv::Mats.
+ *
+ * Outputs: match12_out (n1 entries, may be match12 itself) = match12 with -1 where the reference sets vpMatches1 to NULL; the
+ * record.  When fewer than 10 pairs survive the first check the reference returns 0 at once: n_inliers = 0, more_iterations = 0,
+ * the pairs already removed stay removed, and the similarity in the record is the one given (g2oS12 is not written back).
+ *
+ * Where the reference is undefined:
+ *   - a projected point with z = 0 (an error or a numeric Jacobian that is not finite): that edge adds nothing to chi2, H and b in
+ *     the pass where it happens, and a pair one of whose chi2 is not finite at a check is bad (never an inlier);
+ *   - no kept correspondence (N = 0): no iteration runs (iterations[0] = -1), the early return, the similarity as given.
+ * ORBFE_ERR_INVALID: NULL pointers, a match12 entry outside [-1, n2), an octave outside [0, nlevels) on a kept correspondence,
+ * th2 <= 0, th2, K, the similarity, a pose, or a kept correspondence's point or observation not finite.  ORBFE_ERR_CAPACITY:
+ * max(n1, n2) above the bound of the batch call.  Host pointers. */
+typedef struct orbfe_sim3_opt_result {
+    int32_t n_inliers;          /* the return value: nIn of the second check (0 on the early return) */
+    int32_t n_correspondences;  /* nCorrespondences: the pairs kept */
+    int32_t n_bad;              /* nBad of the first check */
+    int32_t more_iterations;    /* nMoreIterations of the second optimize(): 10, 5, or 0 on the early return */
+    int32_t iterations[2];      /* DIAGNOSTIC: LM iterations of each optimize() run (-1: no active edge) */
+    int32_t stale_mask;         /* DIAGNOSTIC: bit r = optimize() r ended on a rejected trial (the check read that trial's errors) */
+    int32_t status;             /* ORBFE_OK; the batch call: ORBFE_ERR_INVALID for a problem it skipped (see there) */
+    double  s12, q12[4], t12[3];/* g2oS12 after the call: scale, rotation (x, y, z, w; not normalised, as g2o::Sim3 keeps it), translation */
+} orbfe_sim3_opt_result;
+
+int orbfe_optimize_sim3(const orbfe_keypoint* kps1, int n1, const float* x3Dw1, const uint8_t* valid1, const float* Tcw1, const float* K4_1,
+                        const orbfe_keypoint* kps2, int n2, const float* x3Dw2, const uint8_t* valid2, const float* Tcw2, const float* K4_2,
+                        const int32_t* match12, const float* inv_level_sigma2, int nlevels, float s12, const float* R12, const float* t12,
+                        float th2, int fix_scale, int32_t* match12_out, orbfe_sim3_opt_result* res, int device);
+
+/* npairs problems on resident data, in the layout of orbfe_sim3_solve_batch_device: per-frame blocks of `capacity` entries of
+ * d_kps, d_x3Dw (x 3), d_valid (may be NULL) and d_n (clamped to the block), d_Tcw 12 floats a frame; problem p is frame d_pair1[p]
+ * against frame d_pair2[p] (NULL index arrays: p and p + 1); d_match12 / d_match12_out blocks of `capacity` (the same array works
+ * in place; the first d_n[pair1] entries are written, an input entry outside [-1, d_n[pair2]) counts as no match and is copied as
+ * it is).  One K4 for both sides.  Problem p's initial similarity is the 13 floats s12, R12 (row-major), t12 at
+ * (char*)d_sim12 + p * sim12_stride: d_sim12 = &d_res[0].s12 of orbfe_sim3_result with sim12_stride = sizeof(orbfe_sim3_result)
+ * chains this call after orbfe_sim3_solve_batch_device on one stream without a download (stride and base multiples of 4, stride
+ * >= 52).  A problem with an octave outside [0, nlevels) on a kept correspondence is skipped: its record has status
+ * ORBFE_ERR_INVALID and every other field 0, its matches are not written.  One launch whatever npairs is; asynchronous on
+ * `stream`, no host synchronisation, no scratch beyond the caller's buffers.  A problem is staged in its workgroup's LDS:
+ * capacity x 53 B + 4 KB must fit (ORBFE_ERR_CAPACITY otherwise: capacity <= about 3 000 features a keyframe on gfx950's 160 KB). */
+int orbfe_optimize_sim3_batch_device(const orbfe_keypoint* d_kps, const int32_t* d_n, int capacity, const float* d_x3Dw,
+                                     const uint8_t* d_valid, const float* d_Tcw, const int32_t* d_pair1, const int32_t* d_pair2, int npairs,
+                                     const int32_t* d_match12, const float* K4, const float* inv_level_sigma2, int nlevels,
+                                     const void* d_sim12, size_t sim12_stride, float th2, int fix_scale, int32_t* d_match12_out,
+                                     orbfe_sim3_opt_result* d_res, void* stream);
 
 /* ------------------------------------------------------------ motion-only pose optimization -- */
 /* Optimizer::PoseOptimizationByAruco(Frame*) (src/Optimizer.cc:522-770; every tracking path of Tracking.cc ends in it) and

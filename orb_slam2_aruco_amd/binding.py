@@ -61,6 +61,8 @@ SYMBOLS = [
     "orbfe_pose_optimization", "orbfe_pose_optimization_batch_device", "orbfe_pose_gather_device",
     # the Sim3 RANSAC of loop closing (csrc/sim3_solver.hip)
     "orbfe_sim3_solve", "orbfe_sim3_solve_batch_device", "orbfe_sim3_inspect",
+    # the Sim3 refinement of loop closing (csrc/sim3_optimizer.hip)
+    "orbfe_optimize_sim3", "orbfe_optimize_sim3_batch_device",
 ]
 
 _lib = None
@@ -200,6 +202,10 @@ def load():
         L.orbfe_sim3_solve.argtypes = common + [i32]
         L.orbfe_sim3_inspect.argtypes = common + [vp] * 11 + [i32]
         L.orbfe_sim3_solve_batch_device.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, C.c_double, i32, i32, vp, vp, vp, vp]
+    if hasattr(L, "orbfe_optimize_sim3"):
+        side = [vp, i32, vp, vp, vp, vp]
+        L.orbfe_optimize_sim3.argtypes = side + side + [vp, vp, i32, f32, vp, vp, f32, i32, vp, vp, i32]
+        L.orbfe_optimize_sim3_batch_device.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, sz, f32, i32, vp, vp, vp]
     if hasattr(L, "orbfe_initialize"):
         L.orbfe_initialize.argtypes = [vp, i32, vp, i32, vp, vp, f32, i32, vp, vp, vp, vp, i32]
         L.orbfe_initialize_inspect.argtypes = [vp, i32, vp, i32, vp, vp, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
@@ -888,6 +894,57 @@ def sim3_solve_batch_device(d_kps_ptr, d_n_ptr, capacity, d_x3Dw_ptr, d_valid_pt
                                               d_pair2_ptr, int(npairs), d_match12_ptr, _p(K4), _p(ls2), len(ls2), int(bool(fix_scale)),
                                               float(probability), int(min_inliers), int(max_iterations), d_rand_words_ptr, d_res_ptr,
                                               d_inliers12_ptr, stream), "orbfe_sim3_solve_batch_device")
+
+
+# ------------------------------------------------------------------------------- Sim3 refinement (loop closing) ----
+SIM3_OPT_RESULT_DTYPE = np.dtype([("n_inliers", "<i4"), ("n_correspondences", "<i4"), ("n_bad", "<i4"), ("more_iterations", "<i4"),
+                                  ("iterations", "<i4", 2), ("stale_mask", "<i4"), ("status", "<i4"), ("s12", "<f8"), ("q12", "<f8", 4),
+                                  ("t12", "<f8", 3)])
+assert SIM3_OPT_RESULT_DTYPE.itemsize == 96
+SIM3_RESULT_S12_OFFSET = SIM3_RESULT_DTYPE.fields["s12"][1]   # s12, R12, t12: 13 contiguous floats of orbfe_sim3_result
+
+
+def optimize_sim3(side1, side2, match12, inv_level_sigma2, s12, R12, t12, th2, fix_scale, match12_out=None, device=0):
+    """Optimizer::OptimizeSim3 (Optimizer.cc:1544-1739) on the GPU.  side = (kps (mvKeysUn, KP_DTYPE), x3Dw (n x 3), valid (n, or
+    None), Tcw (3 x 4 or 4 x 4), K (3 x 3 or fx, fy, cx, cy)) as for Sim3Solver; match12[i1] = i2 or -1; s12, R12 (3 x 3), t12: the
+    initial similarity (floats).  match12_out: an int32 array of n1 entries to write (match12 itself works in place; a new array when
+    None).  Returns (match12_out, result record of SIM3_OPT_RESULT_DTYPE): n_inliers is the reference's return value, s12 / q12
+    (x, y, z, w) / t12 the optimized g2oS12 in double."""
+    L = load()
+    k1, x1, v1, T1, K1 = _sim3_side(*side1)
+    k2, x2, v2, T2, K2 = _sim3_side(*side2)
+    if (v1 is None) != (v2 is None):
+        raise ValueError("valid: give both sides or neither")
+    m12 = match12 if isinstance(match12, np.ndarray) and match12.dtype == np.int32 and match12.flags.c_contiguous else np.ascontiguousarray(match12, np.int32)
+    if len(m12) != len(k1):
+        raise ValueError("match12 has %d entries for %d keypoints" % (len(m12), len(k1)))
+    out = np.full(len(k1), -1, np.int32) if match12_out is None else match12_out
+    if out.dtype != np.int32 or len(out) != len(k1) or not out.flags.c_contiguous:
+        raise ValueError("match12_out must be a contiguous int32 array of n1 entries")
+    sig = np.ascontiguousarray(inv_level_sigma2, np.float32)
+    R = np.ascontiguousarray(R12, np.float32).reshape(9)
+    t = np.ascontiguousarray(t12, np.float32).reshape(3)
+    res = np.zeros(1, SIM3_OPT_RESULT_DTYPE)
+    vv = lambda v: None if v is None else _ptr_or_none(v)
+    _check(L, L.orbfe_optimize_sim3(_ptr_or_none(k1), len(k1), _ptr_or_none(x1), vv(v1), _p(T1), _p(K1),
+                                    _ptr_or_none(k2), len(k2), _ptr_or_none(x2), vv(v2), _p(T2), _p(K2),
+                                    _ptr_or_none(m12), _p(sig), len(sig), float(s12), _p(R), _p(t), float(th2), int(bool(fix_scale)),
+                                    _ptr_or_none(out), _p(res), device), "orbfe_optimize_sim3")
+    return out, res[0]
+
+
+def optimize_sim3_batch_device(d_kps_ptr, d_n_ptr, capacity, d_x3Dw_ptr, d_valid_ptr, d_Tcw_ptr, d_pair1_ptr, d_pair2_ptr, npairs,
+                               d_match12_ptr, K, inv_level_sigma2, d_sim12_ptr, sim12_stride, th2, fix_scale, d_match12_out_ptr,
+                               d_res_ptr, stream=0):
+    """orbfe_optimize_sim3_batch_device: npairs problems on the blocks orbfe_sim3_solve_batch_device reads (device pointers).
+    d_sim12_ptr / sim12_stride: 13 floats s12, R12, t12 per problem (d_res of the Sim3 solver + SIM3_RESULT_S12_OFFSET with its
+    itemsize as stride chains the two).  Results: npairs SIM3_OPT_RESULT_DTYPE records, match12_out blocks.  Asynchronous on `stream`."""
+    L = load()
+    sig = np.ascontiguousarray(inv_level_sigma2, np.float32)
+    _check(L, L.orbfe_optimize_sim3_batch_device(d_kps_ptr, d_n_ptr, int(capacity), d_x3Dw_ptr, d_valid_ptr, d_Tcw_ptr, d_pair1_ptr,
+                                                 d_pair2_ptr, int(npairs), d_match12_ptr, _p(_K4(K)), _p(sig), len(sig), d_sim12_ptr,
+                                                 int(sim12_stride), float(th2), int(bool(fix_scale)), d_match12_out_ptr, d_res_ptr,
+                                                 stream), "orbfe_optimize_sim3_batch_device")
 
 
 # ------------------------------------------------------------------------------- pose optimization ----

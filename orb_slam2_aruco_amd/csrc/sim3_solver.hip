@@ -39,6 +39,7 @@
 #include "host_stage.hpp"
 #include "orbfe_common.hpp"
 #include "ransac_sets.hpp"
+#include "sim3_points.hpp"
 #include <cfloat>
 #include <cmath>
 
@@ -85,13 +86,6 @@ struct Sim3Args {
     orbfe_sim3_result* res;
     uint8_t* inl;                // capacity per problem
 };
-
-// d = A x + t for a 3 x 4 row-major [A | t]: the Mat product with C (alpha = beta = 1)
-__device__ __forceinline__ void rigid(const float* T, float x, float y, float z, float* d)
-{
-    for (int r = 0; r < 3; r++)
-        d[r] = (float)((((double)T[4 * r] * x + (double)T[4 * r + 1] * y) + (double)T[4 * r + 2] * z) + (double)T[4 * r + 3]);
-}
 
 // FromCameraToImage / the tail of Project (:394-402, :415-422)
 __device__ __forceinline__ void to_image(const float* X, const float* K, float* uv)
