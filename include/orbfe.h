@@ -145,9 +145,14 @@ int orbfe_extract_batch_device(orbfe_extractor* h, const uint8_t* d_imgs, int nf
 int orbfe_extractor_set_gaussian_taps(orbfe_extractor* h, int mode);
 
 /* The device-pointer entry point is asynchronous and cannot return a capacity error: a frame whose keypoint total exceeds
- * `capacity` is clamped to it.  After the batch (synchronises the device): *overflow = 0, or the largest per-frame total
+ * `capacity` is clamped to it.  A clamped frame holds a PREFIX of its full result: records and descriptor rows 0 .. capacity - 1 of
+ * what a sufficient capacity gives, byte for byte (the output is the concatenation of the levels in ascending order, cut at
+ * `capacity`: level 0 comes first, the coarsest levels are what is cut); d_n_out[f] = capacity, slots of other frames and slots past
+ * d_n_out[f] are not written.  After the batch (synchronises the device): *overflow = 0, or the largest per-frame total
  * that did not fit -- the batch's records are then incomplete and the call must be repeated with capacity >= *overflow
- * (orbfe_extractor_max_keypoints() always suffices).  The flag covers every batch since it was last read (reading clears it). */
+ * (orbfe_extractor_max_keypoints() always suffices).  The flag covers every batch since it was last read (reading clears it).
+ * The host-pointer calls keep a flag of their own: they return ORBFE_ERR_CAPACITY themselves, never show here, and an unread
+ * flag of a device batch does not fail them. */
 int orbfe_extractor_batch_status(orbfe_extractor* h, int32_t* overflow);
 
 /* Stage read-back for parity tests (valid after an extract call; `frame` indexes the last batch).
@@ -880,14 +885,23 @@ int orbfe_aruco_detect_bgr(orbfe_aruco* h, const uint8_t* bgr, int rows, int col
                            int32_t* n_out);
 int orbfe_aruco_detect_batch(orbfe_aruco* h, const uint8_t* imgs, int nframes, size_t frame_stride, int rows, int cols,
                              size_t step, orbfe_marker* out, int capacity, int32_t* n_out);
-/* device frames: any base byte, step and frame stride within the bounds given at orbfe_extract_batch_device (LAYOUT OF DEVICE FRAMES) */
+/* Flag of orbfe_aruco_batch_status / orbfe_pipeline_status: the frame has more markers than the caller's `capacity` (the pipeline's
+ * marker_capacity) records.  Not an internal capacity: no other contour path helps, the batch is repeated with more records. */
+#define ORBFE_ARUCO_FLAG_TRUNCATED 128
+/* device frames: any base byte, step and frame stride within the bounds given at orbfe_extract_batch_device (LAYOUT OF DEVICE FRAMES).
+ * Frame f writes its first min(markers, capacity) records in id order -- a frame with more markers than `capacity` holds a prefix of
+ * its id-sorted list, d_n_out[f] = capacity, and is flagged ORBFE_ARUCO_FLAG_TRUNCATED in orbfe_aruco_batch_status; slots past
+ * d_n_out[f] are not written.  capacity = orbfe_aruco_max_markers() always suffices. */
 int orbfe_aruco_detect_batch_device(orbfe_aruco* h, const uint8_t* d_imgs, int nframes, size_t frame_stride, int rows,
                                     int cols, size_t step, orbfe_marker* d_out, int capacity, int32_t* d_n_out,
                                     void* stream);
 /* The batch entry point on device pointers cannot report a frame that exceeded the detector's internal capacities (more
  * than 1024 contours longer than 70 points in a frame that the LDS-resident contour kernels handle; the host-pointer
- * entry points retry such a batch with the big-frame kernel themselves).  After the batch: *nflagged = frames of the last
- * batch whose results are incomplete, *flags_or = the union of their capacity flags (synchronises the device).
+ * entry points retry such a batch with the big-frame kernel themselves), nor one with more markers than the caller's `capacity`
+ * (the host-pointer entry points return ORBFE_ERR_CAPACITY for that).  After the batch: *nflagged = frames of the last
+ * batch whose results are incomplete, *flags_or = the union of their capacity flags (synchronises the device).  A frame that was
+ * only cut at the caller's capacity carries ORBFE_ARUCO_FLAG_TRUNCATED and nothing else: repeat with capacity up to
+ * orbfe_aruco_max_markers(), which always suffices; any other bit is an internal capacity.
  * orbfe_aruco_set_big_frames(h, 1) selects the big-frame contour kernel (bit image in HBM, 4096 kept contours) for all
  * following batches. */
 int orbfe_aruco_batch_status(orbfe_aruco* h, int32_t* nflagged, int32_t* flags_or);
@@ -969,7 +983,7 @@ typedef struct orbfe_pipeline_config {
     int32_t ini_th_fast, min_th_fast;
     char dictionary[32];               /* MarkerDetector::setDictionary */
     int32_t device;
-    int32_t marker_capacity;           /* marker (+ pose) records per frame in a record set (<= orbfe_aruco_max_markers) */
+    int32_t marker_capacity;           /* marker (+ pose) records per frame in a record set (<= orbfe_aruco_max_markers; a frame with more: orbfe_pipeline_status) */
     int32_t use_orb, use_aruco;        /* 0 leaves an engine out (diagnostics) */
     float marker_size;                 /* metres (Frame.cc:131: 0.187) */
     float K[4], dist[12];              /* camera of the marker poses FOR THIS FRAME SIZE (orbfe_camera_resize), ndist coefficients */
@@ -1035,7 +1049,11 @@ int orbfe_pipeline_synchronize(orbfe_pipeline* p);           /* flush + wait for
  * the newest batch this call enqueues it first, so nothing has to be flushed before. */
 int orbfe_pipeline_input_done(orbfe_pipeline* p, int record_set);
 /* capacity flags since the last call (synchronises): out[0] extractor overflow, [1] SearchForInitialization pool overflow (the pool
- * has been grown: repeat), [2] frames the detector flagged, [3] the union of their flags.  All zero = results complete. */
+ * has been grown: repeat), [2] frames the detector flagged, [3] the union of their flags.  All zero = results complete.
+ * All four cover EVERY step since the last call (reading clears them), the detector's as well: [2] counts the flagged frames of all
+ * those steps.  ORBFE_ARUCO_FLAG_TRUNCATED in [3]: a frame had more markers than marker_capacity and its record holds the first
+ * marker_capacity of them in id order (with their poses) -- create the pipeline with a larger marker_capacity, up to
+ * orbfe_aruco_max_markers(), which always suffices; the other bits are as in orbfe_aruco_batch_status. */
 int orbfe_pipeline_status(orbfe_pipeline* p, int32_t out[4]);
 int orbfe_pipeline_set_big_frames(orbfe_pipeline* p, int on); /* orbfe_aruco_set_big_frames on the pipeline's detector */
 /* device pointers: record set `set`; the matching outputs of the newest batch ([frames][capacity] each, nmatches [frames]) */

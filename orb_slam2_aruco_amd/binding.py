@@ -70,6 +70,9 @@ _lib = None
 
 # return codes of include/orbfe.h
 ORBFE_OK, ORBFE_ERR_INVALID, ORBFE_ERR_NO_DEVICE, ORBFE_ERR_HIP, ORBFE_ERR_CAPACITY, ORBFE_ERR_DICT = 0, -1, -2, -3, -4, -5
+# ORBFE_ARUCO_FLAG_TRUNCATED: a frame of a device batch had more markers than the caller's capacity (MarkerDetector.batch_status,
+# FrontEndPipeline.status); every other flag bit is an internal capacity of the detector
+ARUCO_FLAG_TRUNCATED = 128
 
 
 class OrbfeError(RuntimeError):
@@ -1299,7 +1302,8 @@ class MarkerDetector:
         self._shape = (rows, cols)
 
     def batch_status(self):
-        """(frames of the last device batch with incomplete results, union of their capacity flags)"""
+        """(frames of the last device batch with incomplete results, union of their capacity flags; ARUCO_FLAG_TRUNCATED: the
+        caller's capacity was too small, repeat with up to self.capacity records a frame)"""
         n, fl = C.c_int32(0), C.c_int32(0)
         _check(self.L, self.L.orbfe_aruco_batch_status(self.h, C.byref(n), C.byref(fl)), "orbfe_aruco_batch_status")
         return n.value, fl.value

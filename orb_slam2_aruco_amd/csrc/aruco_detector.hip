@@ -316,7 +316,8 @@ struct orbfe_aruco {
                 (rc = d_dpatch.ensure(items * DC_PATCH_BYTES)))
                 return rc;
         }
-        if (!d_dctr.p) {   // k_finalize leaves the counter at zero for the next batch
+        if (!d_dctr.p) {   // [0]: k_finalize leaves the counter at zero for the next batch; [2], [3]: flagged frames and the union of their
+                           // flags over every batch since aruco_flags_since_read last cleared them (k_finalize adds to them)
             if ((rc = d_dctr.ensure(16))) return rc;
             ORBFE_HIP(hipMemset(d_dctr.p, 0, 16));
         }
@@ -639,7 +640,7 @@ struct orbfe_aruco {
         if (enclosed)   // enlargeMarkerCandidate on every rectangle, before prefilterCandidates sees them (:3560-3590)
             hipLaunchKernelGGL(k_enlarge_candidates, dim3(B), dim3(AR_MAX_RECTS), 0, s, d_rects.as<ArRect>(), AR_MAX_RECTS, d_counts.as<int32_t>(),
                                (int)(float(enlarge_k) / 2.));
-        if (decode_dirty) ORBFE_HIP(hipMemsetAsync(d_dctr.p, 0, 16, s));   // a previous batch was abandoned between prefilter and finalize
+        if (decode_dirty) ORBFE_HIP(hipMemsetAsync(d_dctr.p, 0, 4, s));   // a previous batch was abandoned between prefilter and finalize (the counter only: [2], [3] are the sticky flags)
         decode_dirty = true;
         const TailFinish tf = finish_in_prefilter ? TailFinish{geo.relay_kcap, d_trect.as<uint8_t>(), d_kept.as<ArKept>(), geo.relay_kcap, d_tctr.as<int32_t>()} : TailFinish{};
         hipLaunchKernelGGL(k_prefilter, dim3(B), dim3(256), 0, s, d_rects.as<ArRect>(), AR_MAX_RECTS,
@@ -678,10 +679,11 @@ struct orbfe_aruco {
         }
         if (int rc = mr && mr->before_finalize ? mr->before_finalize(s) : ORBFE_OK) return rc;
         // corner refinement applies only when the input was not reduced (:8420): CORNER_LINES inside k_finalize, CORNER_SUBPIX after it
+        // (a measuring build that repeats the launch counts a flagged frame into the sticky words once per repeat; the shipped build runs it once)
         for (int r_ = 0; r_ < ORBFE_REPS_ARUCO(4); r_++) hipLaunchKernelGGL(k_finalize, dim3(B), dim3(256), 0, s, d_rects.as<ArRect>(), AR_MAX_RECTS,
                            d_candidx.as<int32_t>(), d_ncand.as<int32_t>(), d_result.as<int32_t>(),
                            d_pool.as<uint32_t>(), geo.pool_fu32, d_out_m, capacity, d_n, (corner_method == 1 && !reduced) ? 1 : 0, d_msrc.as<int32_t>(),
-                           d_dctr.as<int32_t>());
+                           d_dctr.as<int32_t>(), d_counts.as<int32_t>());
         if (corner_method == 0 && !reduced)   // cornerSubPix(grey, Size(4, 4), TermCriteria(MAX_ITER | EPS, 12, 0.005)) (:8511)
             hipLaunchKernelGGL(k_corner_subpix_markers, dim3(16, B), dim3(256), 0, s, src0, geo.cols, geo.rows, d_out_m, d_n, capacity, 4, 12,
                                0.005 * 0.005, d_masks.as<float>() + (size_t)3 * 17 * 17);
@@ -1170,6 +1172,20 @@ void aruco_unpair_notice(orbfe_aruco* h)
 }
 
 int aruco_device_of(const orbfe_aruco* h) { return h ? h->device : -1; }
+
+int aruco_flags_since_read(orbfe_aruco* h, int32_t* nflagged, int32_t* flags_or)
+{
+    *nflagged = 0; *flags_or = 0;
+    if (!h || !h->d_dctr.p) return ORBFE_OK; // no batch yet
+    int rc = use_device(h->device);
+    if (rc) return rc;
+    ORBFE_HIP(hipDeviceSynchronize());
+    int32_t w[2] = {0, 0};
+    ORBFE_HIP(hipMemcpy(w, h->d_dctr.as<int32_t>() + 2, 8, hipMemcpyDeviceToHost));
+    if (w[0] || w[1]) ORBFE_HIP(hipMemset(h->d_dctr.as<int32_t>() + 2, 0, 8)); // sticky until read
+    *nflagged = w[0]; *flags_or = w[1];
+    return ORBFE_OK;
+}
 
 
 } // namespace orbfe

@@ -2902,7 +2902,7 @@ __global__ __launch_bounds__(256) void k_finalize(const ArRect* __restrict__ rec
                                                   orbfe_marker* __restrict__ out, int out_cap,
                                                   int32_t* __restrict__ n_out, int refine_lines,
                                                   int32_t* __restrict__ out_src /*per output slot: its rectangle (contour)*/,
-                                                  int32_t* __restrict__ wctr)
+                                                  int32_t* __restrict__ wctr, int32_t* __restrict__ counts)
 {
     __builtin_amdgcn_s_setprio(2); // latency-bound: its few waves go first when a VALU-bound kernel shares the CU
     __shared__ int s_id[AR_MAX_RECTS], s_src[AR_MAX_RECTS], s_rot[AR_MAX_RECTS], s_per[AR_MAX_RECTS], s_rm[AR_MAX_RECTS];
@@ -3058,7 +3058,19 @@ __global__ __launch_bounds__(256) void k_finalize(const ArRect* __restrict__ rec
             out[(size_t)f * out_cap + slot] = mk;
         }
     }
-    if (tid == 0) n_out[f] = s_written < out_cap ? s_written : out_cap;
+    if (tid == 0) {
+        n_out[f] = s_written < out_cap ? s_written : out_cap;
+        // more markers than the caller's records hold: the frame is flagged like one over an internal capacity (its first out_cap
+        // markers in id order are there).  Every flagged frame also goes into the handle's sticky words, wctr[2] = frames and
+        // wctr[3] = the union of their flags, which orbfe::aruco_flags_since_read reads and clears
+        const int flags_in = counts[f * 4 + 2]; // what the contour and tail kernels reported for the frame (nobody writes it after them)
+        const int flags = flags_in | (s_written > out_cap ? ORBFE_ARUCO_FLAG_TRUNCATED : 0);
+        if (flags) {
+            if (flags != flags_in) counts[f * 4 + 2] = flags;
+            atomicAdd(&wctr[2], 1);
+            atomicOr(&wctr[3], flags);
+        }
+    }
 }
 
 } // namespace orbfe

@@ -104,7 +104,7 @@ __global__ void k_decode_vote(ImgView src0, ImgView pyr, const ArLevel* levels, 
                               const uint8_t* patch, int32_t* result);
 __global__ void k_finalize(const ArRect* rects, int rect_cap, const int32_t* cand_idx, const int32_t* ncand,
                            const int32_t* result, const uint32_t* pool, size_t pool_fstride, orbfe_marker* out,
-                           int out_cap, int32_t* n_out, int refine_lines, int32_t* out_src, int32_t* wctr);
+                           int out_cap, int32_t* n_out, int refine_lines, int32_t* out_src, int32_t* wctr, int32_t* counts);
 // aruco_modes.hip: THRES_AUTO_FIXED, Params::minSize > 0, CORNER_SUBPIX, CV_8UC3 input
 __global__ void k_fixed_threshold(ImgView src, int W, int H, int thr, uint32_t* bits, size_t bits_fstride, int wpr);
 __global__ void k_erode_cross_xor(const uint32_t* in, uint32_t* out, size_t bits_fstride, int wpr, int W, int H, int r);

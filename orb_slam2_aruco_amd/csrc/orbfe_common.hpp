@@ -166,6 +166,12 @@ int aruco_speculate(orbfe_aruco* a, const uint8_t* d_img, size_t dframe, int row
 void aruco_speculation_wait(orbfe_aruco* a); // until the detector no longer reads the extractor's copy of the image
 void aruco_unpair_notice(orbfe_aruco* a);
 int aruco_device_of(const orbfe_aruco* a);   // the HIP device the detector was created on
+// The detector's capacity flags over EVERY batch of the handle since this was last called (synchronises; reading clears): frames that
+// were flagged and the union of their flags.  k_finalize adds to two device words at the end of each batch's chain, so a step of the
+// pipeline costs no launch and no wait for it; orbfe_aruco_batch_status keeps its per-frame meaning for the last batch alone.
+// The words count every run of k_finalize on the handle: also the attempts of a host-pointer call that with_retries() went on to do
+// again on the next contour path and completed.  The one reader is orbfe_pipeline_status, whose detector only ever runs device batches.
+int aruco_flags_since_read(orbfe_aruco* a, int32_t* nflagged, int32_t* flags_or);
 // The batched pipeline enqueues a batch's descriptor kernel itself, one step late: behind the NEXT batch's resize chain (gate / gate_stage
 // as in orbfe_extractor_stage_wait), so that the two kernels that live on the vector memory path do not run next to each other.
 void extractor_defer_describe(orbfe_extractor* h, bool on);

@@ -721,7 +721,7 @@ int orbfe_pipeline_status(orbfe_pipeline* p, int32_t out[4])
     }
     if (p->det) {
         int32_t n = 0, fl = 0;
-        if ((rc = orbfe_aruco_batch_status(p->det, &n, &fl))) return rc;
+        if ((rc = aruco_flags_since_read(p->det, &n, &fl))) return rc;   // every step since the last call, not the newest batch alone
         out[2] = n; out[3] = fl;
     }
     return ORBFE_OK;

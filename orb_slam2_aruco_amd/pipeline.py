@@ -347,7 +347,8 @@ class FrontEndPipeline:
 
     # ------------------------------------------------------------------------------------------------------------
     def status(self):
-        """Capacity flags since the last call (flushes and synchronises): dict, all zero = results complete."""
+        """Capacity flags of every step since the last call (flushes and synchronises; reading clears): dict, all zero = results
+        complete.  aruco_flags == binding.ARUCO_FLAG_TRUNCATED: frames had more markers than marker_capacity."""
         out = (C.c_int32 * 4)()
         binding._check(self.L, self.L.orbfe_pipeline_status(self.h, C.byref(out)), "orbfe_pipeline_status")
         return {"extractor_overflow": out[0], "search_init_overflow": out[1], "aruco_flagged_frames": out[2], "aruco_flags": out[3]}
@@ -360,7 +361,7 @@ class FrontEndPipeline:
             self.step(d_imgs)
         st = self.status()
         again = False
-        if st["aruco_flagged_frames"]:
+        if st["aruco_flags"] & ~binding.ARUCO_FLAG_TRUNCATED:             # (a frame over marker_capacity is no matter of the contour kernel)
             binding._check(self.L, self.L.orbfe_pipeline_set_big_frames(self.h, 1), "orbfe_pipeline_set_big_frames")
             self.big_frames = again = True
         if st["search_init_overflow"]:

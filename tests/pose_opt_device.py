@@ -1,4 +1,5 @@
-"""Device buffers for the pose optimization GPU tests and tools/pose_opt_timing.py, through the library's own allocator
+"""Device buffers for the GPU tests on device pointers and tools/pose_opt_timing.py (Dev: a device copy of an array; Out: an output
+between guard bytes), through the library's own allocator
 (orbfe_device_alloc / _upload_rows / _download: ordinary HIP device pointers of the library's runtime; the download is blocking, so
 it also waits for work enqueued on the null stream)."""
 import ctypes as C
@@ -55,3 +56,26 @@ class Dev:
         if getattr(self, "ptr", None) and _L is not None:
             _L.orbfe_device_free(self.ptr)
             self.ptr = None
+
+
+class Out:
+    """A device output with 256 guard bytes in front and behind; get() asserts that both are unchanged."""
+    GUARD = 256
+
+    def __init__(self, init):
+        self.a = np.ascontiguousarray(init)
+        self.dev = Dev(self._raw(self.a))
+        self.ptr = self.dev.ptr + self.GUARD
+
+    def _raw(self, a):
+        return np.concatenate([np.full(self.GUARD, 0xC3, np.uint8), a.view(np.uint8).reshape(-1), np.full(self.GUARD, 0x3C, np.uint8)])
+
+    def put(self, a):
+        """the whole buffer again, guards included"""
+        self.dev.put(self._raw(np.ascontiguousarray(a, self.a.dtype).reshape(self.a.shape)))
+
+    def get(self):
+        raw = self.dev.get()
+        assert np.all(raw[:self.GUARD] == 0xC3), "bytes in front of the output were overwritten"
+        assert np.all(raw[-self.GUARD:] == 0x3C), "bytes behind the output were overwritten"
+        return raw[self.GUARD:-self.GUARD].view(self.a.dtype).reshape(self.a.shape)

@@ -13,36 +13,13 @@ import pytest
 import match_batch_cases as mc
 import oracle_lib as oracle
 from orb_slam2_aruco_amd import binding as orbfe
-from pose_opt_device import Dev
+from pose_opt_device import Dev, Out
 
 pytestmark = pytest.mark.gpu
 
 SEED = 7
 P32 = mc.POISON_I32
 ORBFE_ERR_CAPACITY = orbfe.ORBFE_ERR_CAPACITY
-
-
-class Out:
-    """A device output with 256 guard bytes in front and behind; get() asserts that both are unchanged."""
-    GUARD = 256
-
-    def __init__(self, init):
-        self.a = np.ascontiguousarray(init)
-        self.dev = Dev(self._raw(self.a))
-        self.ptr = self.dev.ptr + self.GUARD
-
-    def _raw(self, a):
-        return np.concatenate([np.full(self.GUARD, 0xC3, np.uint8), a.view(np.uint8).reshape(-1), np.full(self.GUARD, 0x3C, np.uint8)])
-
-    def put(self, a):
-        """the whole buffer again, guards included"""
-        self.dev.put(self._raw(np.ascontiguousarray(a, self.a.dtype).reshape(self.a.shape)))
-
-    def get(self):
-        raw = self.dev.get()
-        assert np.all(raw[:self.GUARD] == 0xC3), "bytes in front of the output were overwritten"
-        assert np.all(raw[-self.GUARD:] == 0x3C), "bytes behind the output were overwritten"
-        return raw[self.GUARD:-self.GUARD].view(self.a.dtype).reshape(self.a.shape)
 
 
 def i32(*shape):
