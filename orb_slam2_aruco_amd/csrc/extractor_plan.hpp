@@ -23,7 +23,7 @@ namespace orbfe {
 struct LevelGeom {
     int w, h;            // level image size (:1112)
     int pitch;           // row pitch of the level inside the pyramid block (levels >= 1)
-    int bpitch;          // row pitch inside the blurred block
+    int btrow;           // bytes from one row of tiles to the next inside the blurred block (blur_tile_off)
     long long img_off;   // byte offset of the level inside a frame's pyramid block (levels >= 1)
     long long blur_off;  // byte offset inside a frame's blurred block
     int nCols, nRows, wCell, hCell; // FAST cell grid (:784-787)
@@ -42,6 +42,31 @@ struct LevelGeom {
     float scale;         // mvScaleFactor[level]
     float kp_size;       // (float)(int)(31 * scale) (:837)
 };
+
+// The blurred pyramid is stored in tiles of 128 bytes, one cache line each: BLUR_TW bytes of BLUR_TH consecutive rows, the tiles of a
+// level row-major, every level a whole number of tiles.  Its writer (k_blur7_mfma, 32-column strips) and its reader (k_orient_describe2,
+// a 37 x 37 window per keypoint) both work on 2-D pieces: a window lies in 15 - 24 lines instead of the 37 - 74 of a row-major level,
+// and a store instruction of the blur (256 bytes) writes two whole lines.  blur_tile_off is the one place that knows the layout: the
+// two kernels and the host's de-tiling (orbfe_extractor_debug_level_image) call it.  16 bytes at a column that is a multiple of 16 are
+// contiguous.  Padding columns and rows inside a level's last tiles hold whatever the blur computed there; nothing reads them.
+constexpr int BLUR_TW = 16, BLUR_TH = 8;   // (32 x 4 measured equal at 640 x 480: tools/sweeps.md; a window lies in fewer of these)
+static_assert(BLUR_TW * BLUR_TH == 128 && BLUR_TW % 16 == 0, "a tile is one 128-byte line of whole 16-byte chunks");
+
+// byte offset of pixel (x, y), both >= 0, inside a level whose rows of tiles are `trow` bytes apart (LevelGeom::btrow)
+ORBFE_HD uint32_t blur_tile_off(int trow, int x, int y)
+{
+    const uint32_t ux = (uint32_t)x, uy = (uint32_t)y;
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t rows = __umul24(uy / BLUR_TH, (uint32_t)trow);
+#else
+    const uint32_t rows = uy / BLUR_TH * (uint32_t)trow;
+#endif
+    return rows + ux / BLUR_TW * 128u + (uy % BLUR_TH * BLUR_TW + ux % BLUR_TW);
+}
+inline int blur_tiles_x(int w) { return (w + BLUR_TW - 1) / BLUR_TW; }
+inline int blur_tiles_y(int h) { return (h + BLUR_TH - 1) / BLUR_TH; }
+// (level geometry, x, y) -> byte offset inside a frame's blurred block
+template <class Geom> ORBFE_HD long long blur_pixel_off(const Geom& g, int x, int y) { return g.blur_off + (long long)blur_tile_off(g.btrow, x, y); }
 
 // k_blur7_mfma: a 32-column strip of a level per wave; c0 / c1 / c2 = byte columns of the three 16-byte pieces of a row it loads, tab =
 // index (units of 64 uint4) of the strip's two pass-1 tap matrices in operand layout (plan_blur_level)
@@ -120,11 +145,11 @@ inline int plan_levels(ExtractorPlan& p, int nlevels, const float* mvScaleFactor
         if (g.w - 32 > 4095 || g.h - 32 > 4095)
             return plan_fail(p, ORBFE_ERR_INVALID, "level %d is %dx%d: images above 4127 px a side are unsupported", l, g.w, g.h);
         g.pitch = plan_align_up(g.w, 64);
-        g.bpitch = plan_align_up(g.w, 64);
+        g.btrow = blur_tiles_x(g.w) * 128;
         g.img_off = (long long)pyr;
         if (l > 0) pyr += (size_t)g.pitch * g.h;
         g.blur_off = (long long)blur;
-        blur += (size_t)g.bpitch * g.h;
+        blur += (size_t)g.btrow * blur_tiles_y(g.h);
         g.maxBX = g.w - 19 + 3;
         g.maxBY = g.h - 19 + 3;
         const float width = (float)(g.maxBX - 16), height = (float)(g.maxBY - 16);
@@ -166,7 +191,7 @@ inline int plan_levels(ExtractorPlan& p, int nlevels, const float* mvScaleFactor
     }
     p.ncells_total = (int)p.cellinfo.size();
     p.pyr_fbytes = pyr + 64;
-    p.blur_fbytes = blur + 64;
+    p.blur_fbytes = blur + 128;   // (a frame's block stays a whole number of lines; k_orient_describe2 reads nothing outside a level's tiles)
     p.slots_fu32 = slots;
     p.keys_fu32 = 2 * cand;
     return ORBFE_OK;

@@ -618,12 +618,18 @@ int orbfe_extractor_debug_level_image(orbfe_extractor* h, int frame, int level, 
     int rc = use_device(h->device);
     if (rc) return rc;
     const LevelGeom& g = h->plan.geom[level];
+    ORBFE_HIP(hipDeviceSynchronize());
+    if (stage == 1) {   // the blurred level is tiled (extractor_plan.hpp): its tiles as they lie, put in rows here
+        std::vector<uint8_t> tiles((size_t)g.btrow * blur_tiles_y(g.h));
+        ORBFE_HIP(hipMemcpy(tiles.data(), h->d_blur.as<uint8_t>() + frame * h->plan.blur_fbytes + g.blur_off, tiles.size(), hipMemcpyDeviceToHost));
+        for (int y = 0; y < g.h; y++)
+            for (int x = 0; x < g.w; x++) out[(size_t)y * g.w + x] = tiles[blur_tile_off(g.btrow, x, y)];
+        return ORBFE_OK;
+    }
     const uint8_t* src;
     size_t pitch;
-    if (stage == 1) { src = h->d_blur.as<uint8_t>() + frame * h->plan.blur_fbytes + g.blur_off; pitch = g.bpitch; }
-    else if (level == 0) { src = h->last_src0.base + frame * h->last_src0.fstride; pitch = h->last_src0.pitch; }
+    if (level == 0) { src = h->last_src0.base + frame * h->last_src0.fstride; pitch = h->last_src0.pitch; }
     else { src = h->d_pyr.as<uint8_t>() + frame * h->plan.pyr_fbytes + g.img_off; pitch = g.pitch; }
-    ORBFE_HIP(hipDeviceSynchronize());
     ORBFE_HIP(hipMemcpy2D(out, g.w, src, pitch, g.w, g.h, hipMemcpyDeviceToHost));
     return ORBFE_OK;
 }

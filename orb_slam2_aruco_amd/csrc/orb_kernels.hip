@@ -1414,7 +1414,7 @@ __global__ __launch_bounds__(256) void k_blur7_mfma(ImgView src0, ImgView pyr, I
     const uint8_t* img = (S.level == 0) ? src0.base + (size_t)f * src0.fstride : pyr.base + (size_t)f * pyr.fstride + g.img_off;
     const int pitch = (S.level == 0) ? src0.pitch : g.pitch;
     uint8_t* D = blur.base_w + (size_t)f * blur.fstride + g.blur_off;
-    const int h = g.h, wst = (g.w + 3) & ~3, bpitch = g.bpitch;
+    const int h = g.h, btrow = g.btrow, wpad = btrow / BLUR_TH, hpad = (h + BLUR_TH - 1) & -BLUR_TH;   // the level's tiles: wpad x hpad bytes
     const bm_v4i B1a = __builtin_bit_cast(bm_v4i, tabs[(size_t)S.tab * 64 + lane]), B1b = __builtin_bit_cast(bm_v4i, tabs[(size_t)(S.tab + 1) * 64 + lane]);
     const bm_v4i B2a = __builtin_bit_cast(bm_v4i, tab2[lane]), B2b = __builtin_bit_cast(bm_v4i, tab2[64 + lane]);
     const uint32_t ca = (uint32_t)(half ? S.c1 : S.c0), cb = (uint32_t)S.c2;   // K block a: pieces 0 | 1 by half; K block b: piece 2 (its second half has no weight)
@@ -1458,7 +1458,7 @@ __global__ __launch_bounds__(256) void k_blur7_mfma(ImgView src0, ImgView pyr, I
             ah = __builtin_amdgcn_mfma_i32_32x32x32_i8(nh, B2b, ah, 0, 0, 0);
             al = __builtin_amdgcn_mfma_i32_32x32x32_i8(nl, B2b, al, 0, 0, 0);
             // the tile through the wave's LDS patch: written in the accumulators' layout (lane = row, four pixels a register group), read
-            // back with lanes along x -- a store instruction then covers 8 rows x 32 bytes instead of 32 rows x 8 bytes (stored straight
+            // back in the order of the blurred block's tiles -- a store instruction then writes two whole 128-byte lines (stored straight
             // from the accumulators the kernel was bound by its partial-line stores: 400 us next to FAST, 227 without them)
             __builtin_amdgcn_wave_barrier();
 #pragma unroll
@@ -1473,12 +1473,16 @@ __global__ __launch_bounds__(256) void k_blur7_mfma(ImgView src0, ImgView pyr, I
                 patch[r * BM_PP + half + 2 * q] = __builtin_amdgcn_perm(p23, p01, 0x05040100u);
             }
             __builtin_amdgcn_wave_barrier();
-            const int x = S.x0 + 4 * (lane & 7);
+            // a store instruction (64 dwords) writes the strip's two tiles of this group of eight rows: lane = (tile, row of it, dword)
+            constexpr int TD = BLUR_TW / 4;                                             // dwords in a tile's row
+            const int tile = lane >> 5, xd = (lane & (TD - 1)) + (BLUR_TW == 16 ? 4 * tile : 0);
+            const int rt = ((lane & 31) / TD) + (BLUR_TW == 16 ? 0 : BLUR_TH * tile);   // row inside the group
+            const int x = S.x0 + 4 * xd;
 #pragma unroll
             for (int it = 0; it < 4; it++) {
-                const int rr = (lane >> 3) + 8 * it, y = 32 * (j - 1) + rr;
-                const uint32_t v = patch[rr * BM_PP + (lane & 7)];
-                if (y < h && x < wst) *reinterpret_cast<uint32_t*>(D + (off24(y, bpitch) + (uint32_t)x)) = v;
+                const int rr = rt + 8 * it, y = 32 * (j - 1) + rr;
+                const uint32_t v = patch[rr * BM_PP + xd];
+                if (y < hpad && x < wpad) *reinterpret_cast<uint32_t*>(D + blur_tile_off(btrow, x, y)) = v;
             }
         }
         ph = nh; pl = nl;
@@ -1498,6 +1502,9 @@ __global__ __launch_bounds__(256) void k_blur7_mfma(ImgView src0, ImgView pyr, I
 // the width: 16 clocks for 256 bytes as dwords, 16 clocks for 1 KB as 16-byte lanes.  So:
 //   - the 37 x 40-byte window and the 31 x 36-byte patch are fetched as (row, 16-byte chunk) items, three chunks a row: two loads
 //     each (they were 6 + 5 dword loads: 24 vector memory instructions per wave for the images, now 8);
+//   - the blurred level is stored in 128-byte tiles (extractor_plan.hpp), and the window's chunks are the tiles' own: a window lies
+//     in 15 - 24 cache lines instead of 37 - 74, and a load instruction touches as many fewer (the C2 step 1.185 -> 1.152 ms, this
+//     kernel alone 235 -> 211 us).  A window that starts in the last four bytes of a chunk needs a fourth one: a dword load per row;
 //   - the two tables every wave needs -- the IC_Angle row weights (64 bytes a lane) and the test pattern -- come through LDS, fetched
 //     once per workgroup (8 loads per wave before);
 //   - the keypoint records are fetched WITH the frame's count, not behind it (one round trip less in a wave's life).
@@ -1518,7 +1525,7 @@ __global__ __launch_bounds__(256) OD2_ATTR void k_orient_describe2(ImgView src0,
     WT_BEGIN();
     int bx, f;
     if (!xcd_remap(nx, total, bx, f)) return;
-    constexpr int PROW = 40, PATB = 31 * PROW + 8, WINB = 37 * 40 + 8;   // (rows of 8-byte multiples: the chunks go in as 8-byte stores)
+    constexpr int PROW = 40, PATB = 31 * PROW + 8, WROW = 56, WINB = 37 * WROW;   // (rows of 8-byte multiples: the chunks go in as 8-byte stores)
     // LDS per wave: the two IC_Angle patches; once the moments are summed the same bytes hold one descriptor window at a time
     // (13 KB per workgroup with the tables: the footprint matters, an LDS request of 23 KB cost the C2 step 50 us in round 3)
     static_assert(2 * PATB >= WINB, "the window overlays the patches");
@@ -1554,6 +1561,7 @@ __global__ __launch_bounds__(256) OD2_ATTR void k_orient_describe2(ImgView src0,
     typedef u32x4 u32x4_unaligned __attribute__((aligned(1)));   // level 0 is the caller's buffer: no alignment is assumed there
     int kx[2], ky[2], level[2], score[2], xoff[2], xo[2];
     u32x4 wv[2][2], v[2][2];
+    uint32_t w4[2];
     uint32_t pat[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) pat[j] = s_pattern[j * 64 + lane];
@@ -1572,16 +1580,21 @@ __global__ __launch_bounds__(256) OD2_ATTR void k_orient_describe2(ImgView src0,
         const LevelGeom& g = geom[level[h]];
         kx[h] = (int)(kv & 0xfff) + 16; ky[h] = (int)((kv >> 12) & 0xfff) + 16;   // += minBorder (:843-844)
         score[h] = kv >> 24;
-        const int ax = (kx[h] - 18) & ~3;
+        const int ax = (kx[h] - 18) & ~15;
         xoff[h] = (kx[h] - 18) - ax;
         const uint8_t* img = (level[h] == 0) ? src0.base + (size_t)f * src0.fstride : pyr.base + (size_t)f * pyr.fstride + g.img_off;
         const int pitch = (level[h] == 0) ? src0.pitch : g.pitch;
-        const int bpitch = g.bpitch;
-        // rows ky - 18 .. ky + 18 of the blurred level from the 4-byte-aligned column at or below kx - 18: 48 bytes a row (40 used; a
-        // row's last chunk may end up to 9 bytes past the level's width: the next row, or the slack behind the last one)
-        const uint8_t* bimg = blur.base + (size_t)f * blur.fstride + g.blur_off + (off24(ky[h] - 18, bpitch) + (uint32_t)ax);
-        wv[h][0] = *reinterpret_cast<const u32x4_unaligned*>(bimg + (uint32_t)(__mul24(r0, bpitch) + c0));
-        wv[h][1] = *reinterpret_cast<const u32x4_unaligned*>(bimg + (uint32_t)(__mul24(wr1, bpitch) + c1));
+        const int btrow = g.btrow;
+        // rows ky - 18 .. ky + 18 of the blurred level from the 16-byte-aligned column at or below kx - 18, as chunks of its tiles:
+        // columns ax .. ax + 47 hold the 37 the tests use unless the window starts in a chunk's last four bytes (xoff >= 12, the same
+        // for the whole wave); then column ax + 48 .. 51 of every row come with a load of their own.  A keypoint is at least 19 pixels
+        // from the level's edges: every chunk asked for holds a pixel of the window and so lies inside the level's tiles.
+        const uint8_t* bimg = blur.base + (size_t)f * blur.fstride + g.blur_off;
+        const int wy = ky[h] - 18;
+        wv[h][0] = *reinterpret_cast<const u32x4*>(bimg + blur_tile_off(btrow, ax + c0, wy + r0));
+        wv[h][1] = *reinterpret_cast<const u32x4*>(bimg + blur_tile_off(btrow, ax + c1, wy + wr1));
+        w4[h] = 0;
+        if (xoff[h] >= 12) w4[h] = *reinterpret_cast<const uint32_t*>(bimg + blur_tile_off(btrow, ax + 48, wy + min(lane, 36)));
         // rows ky - 15 .. ky + 15 of the level itself from the aligned column at or below kx - 15 (36 bytes used)
         const int axp = (kx[h] - 15) & ~3;
         xo[h] = (kx[h] - 15) - axp;
@@ -1637,11 +1650,11 @@ __global__ __launch_bounds__(256) OD2_ATTR void k_orient_describe2(ImgView src0,
     // The rotation is separate multiplies and adds (the reference is compiled without fused multiply-add) on packed f32: the two
     // points of a test side by side, (x0, x1) (b, b) + (y0, y1) (a, a), six v_pk_* instead of twelve scalar operations.  cvRound
     // is "add 1.5 * 2^23": the sum is rounded to an integer by the adder (to nearest even, like cvRound), and its low mantissa
-    // bits are that integer plus 2^22; row * 40 + column is then one 24-bit multiply-add on the raw bits, the constants folded
+    // bits are that integer plus 2^22; row * 56 + column is then one 24-bit multiply-add on the raw bits, the constants folded
     // into the window's base address.  (The pattern as a float4 table saves 32 conversions per lane but quadruples the table: slower.)
     typedef float v2f __attribute__((ext_vector_type(2)));
     constexpr uint32_t MAGIC_BITS = 0x4B400000u;                                      // 12582912.0f = 1.5 * 2^23
-    constexpr uint32_t IDX_BIAS = (MAGIC_BITS & 0xffffffu) * 40u + MAGIC_BITS;         // what the raw-bit multiply-add carries along
+    constexpr uint32_t IDX_BIAS = (MAGIC_BITS & 0xffffffu) * (uint32_t)WROW + MAGIC_BITS;   // what the raw-bit multiply-add carries along
     const v2f magic = {12582912.0f, 12582912.0f};
 #pragma unroll
     for (int h = 0; h < 2; h++) {
@@ -1650,10 +1663,14 @@ __global__ __launch_bounds__(256) OD2_ATTR void k_orient_describe2(ImgView src0,
         const v2f aa = {ah, ah}, bb = {bh, bh};
         uint8_t* win = &s_pat[wid][0][0];
         __builtin_amdgcn_wave_barrier();   // the patches (h = 0) / the first window (h = 1) have been read
-        put_chunk(win, r0, c0, wv[h][0]);
-        put_chunk(win, wr1, c1, wv[h][1]);
+        // window rows of 56 bytes: the offset of column kx - 18 in its chunk (up to 15) and the 37 columns
+        *reinterpret_cast<uint2*>(win + r0 * WROW + c0) = make_uint2(wv[h][0].x, wv[h][0].y);
+        *reinterpret_cast<uint2*>(win + r0 * WROW + c0 + 8) = make_uint2(wv[h][0].z, wv[h][0].w);
+        *reinterpret_cast<uint2*>(win + wr1 * WROW + c1) = make_uint2(wv[h][1].x, wv[h][1].y);
+        *reinterpret_cast<uint2*>(win + wr1 * WROW + c1 + 8) = make_uint2(wv[h][1].z, wv[h][1].w);
+        if (xoff[h] >= 12 && lane < 37) *reinterpret_cast<uint32_t*>(win + lane * WROW + 48) = w4[h];
         __builtin_amdgcn_wave_barrier();
-        const uint8_t* bc = win + 18 * 40 + 18 + xoff[h];
+        const uint8_t* bc = win + 18 * WROW + 18 + xoff[h];
         unsigned long long words[4];
 #pragma unroll
         for (int j = 0; j < 4; j++) {
@@ -1662,8 +1679,8 @@ __global__ __launch_bounds__(256) OD2_ATTR void k_orient_describe2(ImgView src0,
             const v2f Y = {(float)(signed char)((pp >> 8) & 0xff), (float)(signed char)(pp >> 24)};
             const v2f R = (X * bb + Y * aa) + magic;   // rows of the two points (-ffp-contract=off: no fused multiply-add)
             const v2f C = (X * aa - Y * bb) + magic;   // columns
-            const uint32_t i0 = __umul24(__float_as_uint(R.x), 40u) + __float_as_uint(C.x) - IDX_BIAS;
-            const uint32_t i1 = __umul24(__float_as_uint(R.y), 40u) + __float_as_uint(C.y) - IDX_BIAS;
+            const uint32_t i0 = __umul24(__float_as_uint(R.x), (uint32_t)WROW) + __float_as_uint(C.x) - IDX_BIAS;
+            const uint32_t i1 = __umul24(__float_as_uint(R.y), (uint32_t)WROW) + __float_as_uint(C.y) - IDX_BIAS;
             const int t0 = bc[(int)i0], t1 = bc[(int)i1];
             words[j] = __ballot(t0 < t1);
         }
