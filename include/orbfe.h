@@ -995,8 +995,9 @@ typedef struct orbfe_pipeline_config {
      * phase lock of the engine sets (orbfe_extractor_follow stage), stage of the extractor's previous batch the detector's batch starts
      * behind, matching enqueued one step late, the detector's /2 pyramid in line on its stream.  They change the order of work, never
      * the results.  With two or more engine sets a batch's descriptor kernel is enqueued one step late (ORBFE_DESCRIBE_LATE, on by
-     * default), and that forces defer_post on whatever was asked for.  A lock on stage 3, the descriptors (phase_pin % 10 == 3,
-     * phase_pin / 10 == 3 or det_pin % 10 == 3), turns the late describe off.  orbfe_pipeline_engine_sets reads back the six fields in
+     * default), and that forces defer_post on whatever was asked for -- an explicit defer_post = 0 here or ORBFE_DEFER_POST=0 included;
+     * only turning the late describe off (ORBFE_DESCRIBE_LATE=0, one engine set, a stage-3 lock) gives it back.  A lock on stage 3, the descriptors (phase_pin % 10 == 3,
+     * phase_pin / 10 == 3 or det_pin % 10 == 3), turns the late describe off.  (The whole rule: plan_schedule, csrc/pipeline_plan.hpp.)  orbfe_pipeline_engine_sets reads back the six fields in
      * effect; whether the late describe is on is not reported (above 640 x 480, where defer_post defaults to 0, it shows there). */
     int32_t engine_sets, record_sets, phase_pin, det_pin, defer_post, det_nofork;
 } orbfe_pipeline_config;

@@ -32,23 +32,6 @@ struct ModeRun {
     std::function<int(hipStream_t)> before_finalize; // trackingMinDetections: the host looks at the decode results and may adopt rejected candidates
 };
 
-// The contour paths: tiled (aruco_tiles.hip), the one-workgroup relay kernels, k_contours_t where neither can run or forced ("walker"),
-// k_contours_t in big-frame mode (bit image in HBM, AR_MAX_KEPT_BIG kept borders).  A batch with a frame over a capacity of its path is
-// done again on the next (escalate(): tiled -> relay, which coarsen their grid -> (kept borders / pool) big); run_device takes the first.
-enum class Contours : int8_t { tiled, relay, walker, big, none };
-enum class Thr : int8_t { fixed, mfma, pyr, box };   // k_fixed_threshold, k_threshold_mfma, k_threshold_pyr<WIN>, k_adaptive_threshold<R>
-enum class Relay : int8_t { relay, relay8, wide, relay8g }; // k_contours_relay, _relay8, _relay_wide, _relay8g
-
-static Contours escalate(Contours ran, int flags_or, bool relay_ok)
-{
-    const bool was_tiled = ran == Contours::tiled;
-    // from the tiled path any exceeded capacity (segment lists, kept borders, pool) goes to the one-workgroup relay kernels first:
-    // they coarsen their grid and follow what is left whole, and get through frames of dense noise that neither the tiles nor the
-    // single-walker kernel's per-lane arenas hold (480 x 640 with +-40 grey levels of noise: 203 kept borders, no flag)
-    if (was_tiled && (flags_or & (2 | 4 | RL_FALLBACK_FLAGS)) && relay_ok) return Contours::relay;
-    return ran != Contours::big && (flags_or & (2 | 4 | (was_tiled ? RL_FALLBACK_FLAGS : 0))) ? Contours::big : Contours::none;
-}
-
 // the window of cv::cornerSubPix for half size w, (2 w + 1)^2 weights: exp(-y^2) exp(-x^2) in float, by the host's expf like the reference
 static void subpix_window(int w, float* mk)
 {
@@ -59,13 +42,27 @@ static void subpix_window(int w, float* mk)
         }
 }
 
-struct orbfe_aruco {
+// the handle's streams and events: a base of the handle, so that they are destroyed after its members -- the device buffers, which
+// release themselves
+struct DetectorQueues {
+    hipStream_t own_stream = nullptr, aux_stream = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    ~DetectorQueues()
+    {
+        if (own_stream) (void)hipStreamDestroy(own_stream);
+        if (aux_stream) (void)hipStreamDestroy(aux_stream);
+        if (ev_fork) (void)hipEventDestroy(ev_fork);
+        if (ev_join) (void)hipEventDestroy(ev_join);
+    }
+};
+
+struct orbfe_aruco : DetectorQueues {
     int device = 0;
     std::string dict_name;
     int nbits = 0, nb = 0, S = 0, ncodes = 0;
-    hipStream_t own_stream = nullptr, aux_stream = nullptr;
     hipStream_t user_aux = nullptr; // orbfe_aruco_set_aux_stream: run the pyramid there instead of on aux_stream
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    // every switch of how a batch runs (detector_plan.hpp): environment at creation, then orbfe_aruco_debug_control / _set_big_frames
+    DetectorSwitches sw;
     // what the kernels are told about the input size in force (detector_plan.hpp); swapped in whole by build_geometry
     DetectorGeometry geo;
     int batch_cap = 0;
@@ -86,78 +83,38 @@ struct orbfe_aruco {
     bool last_cam_valid = false; // camera and marker size of the last detect-with-poses call: what the speculation assumes
     PoseCamera last_cam{};
     float last_size = 0.f;
-    bool relay_wide = !(getenv("ORBFE_ARUCO_RELAY_WIDE") && !atoi(getenv("ORBFE_ARUCO_RELAY_WIDE")));
     DevBuf d_dwork, d_dctr, d_ditems, d_dhist, d_dpatch; // k_prefilter -> k_decode_warp / _otsu / _vote: the batch's candidates
     bool decode_dirty = false; // the decode work-list counter may be non-zero
     bool tail_dirty = false;   // the work-list counters may be non-zero (set while the tail's three launches are being enqueued)
-    // experiment (ORBFE_ARUCO_SMALL_SEPARATE=1): k_contours_small also for frames whose bit image is in LDS
-    // phase (c) of LDS-resident frames as its own launch (k_contours_small): -1 = by batch size (a few frames leave most of the chip
-    // idle, so the many small workgroups of the separate kernel shorten the call: 0.62 -> 0.57 ms for one 640 x 480 frame; a full
-    // batch issues more instructions that way and the pipeline is bound by those: 1.85 -> 1.98 ms per C2 step), 0 / 1 = forced
-    int small_separate_mode = getenv("ORBFE_ARUCO_SMALL_SEPARATE") ? atoi(getenv("ORBFE_ARUCO_SMALL_SEPARATE")) : -1;
-    // the tiled relay formulation (aruco_tiles.hip: k_ct_band or k_ct_walk / k_ct_lists / k_ct_points).  -1 = by frame and batch size:
-    // frames for which the one-workgroup relay kernel needs its 8192-slot table and a CU to itself (1280 x 720: 300-frame step 4.09 -
-    // 4.13 -> 3.96 - 4.07 ms) or whose bit image does not fit LDS at all (1920 x 1080: 100-frame step 4.88 -> 3.41 ms), and batches of
-    // up to 32 frames (a frame's walks spread over ~40 CUs instead of one); full batches of 640 x 480 frames keep the one-workgroup
-    // kernel, whose single launch costs the pipeline less than band + lists + points (1.32 - 1.34 against 1.45 - 1.62 ms per step).
-    // ORBFE_ARUCO_TILED = 0 / 1 (debug key "tiled_contours") forces it off / on for every batch (tests, A/B); ORBFE_ARUCO_TILE_W = tile
-    // width in pixels, ORBFE_ARUCO_TPW = tiles per wave of k_ct_walk: measurement switches.
-    int tiled = -1;
     int n_escalations = 0;     // batches done again on the next contour path (orbfe_aruco_debug_contour_retries: the tests assert 0 for ordinary frames)
-    // the walks of the tiled path by BANDS of cell rows, a workgroup of eight waves each (k_ct_band), instead of a wave per tile
-    // (k_ct_walk): -1 = by frame / batch size, 0 / 1 forced; ORBFE_ARUCO_BAND_ROWS = cell rows per band (0: what fits ~36 KB of LDS, at most 8)
-    int banded = getenv("ORBFE_ARUCO_BANDED") ? (atoi(getenv("ORBFE_ARUCO_BANDED")) ? 1 : 0) : -1;
-    int band_rows_env = getenv("ORBFE_ARUCO_BAND_ROWS") ? atoi(getenv("ORBFE_ARUCO_BAND_ROWS")) : 0;
     DevBuf d_ctmlist;
-    int tile_w_env = getenv("ORBFE_ARUCO_TILE_W") ? atoi(getenv("ORBFE_ARUCO_TILE_W")) : 0;
-    int tpw_env = getenv("ORBFE_ARUCO_TPW") ? atoi(getenv("ORBFE_ARUCO_TPW")) : 0;
     bool ct_dirty = true;      // the per-frame counters of the walk kernel may be non-zero (first use; a batch abandoned before k_ct_lists)
     unsigned ct_gen = 0;       // generation tag of the hash table's entries (16 bits; the table is cleared when it wraps and before first use)
     bool ct_tab_dirty = true;
     DevBuf d_ctseg, d_cthtab, d_ctelem, d_ctstate, d_ctitemsA, d_ctitemsB, d_ctnitems, d_ctcodes;
-    // The speck passes (aruco_trace.hpp "FEWER WALKS" (2)): result-neutral, a quarter of the contour stage's start candidates and walks
-    // gone -- and OFF by default, because neither way of running them pays in the pipeline:
-    //   = 1: as a launch of their own between threshold and contours (k_speck_clean), for every contour path: the contour stage of
-    //     300 x 640 x 480 alone 462 -> 408 us, but one more launch on the detector's chain costs the pipeline more than that (C2 step
-    //     1.40 - 1.46 against 1.34 - 1.38 ms, single-frame detect 0.357 against 0.358 ms; profiles/r05_contour_reductions_ab.txt);
-    //   = 2: inside the one-workgroup relay kernels, on the bit image they hold in LDS anyway (speck_pass_frame; batches of more than
-    //     32 frames whose image fits LDS): 462 -> 440 us alone and 140 -> 120 us of VALU issue, the C2 step unchanged (1.343 against
-    //     1.333 ms, four interleaved runs) -- and the rim masks and anchors of a frame (120 KB) go through scratch in HBM, which
-    //     doubles the stage's HBM traffic (148 -> 268 MB per step).
-    // ORBFE_ARUCO_SPECKS = 0 (default) / 1 / 2.  Debug keys "speck_passes": the launch on / off, "speck_passes_in_kernel": inside.
-    // Tested either way (tests/test_aruco_gpu.py, tests/test_stress_gpu.py).
-    // the speck passes as a launch between threshold and contours: -1 = where they pay (full batches on the one-workgroup relay kernels:
-    // 1.246 against 1.263 ms per C2 step with them, round 6; on the tiled paths 3.99 against 3.74 ms at 1280 x 720, 3.53 against 3.21 at
-    // 1920 x 1080), 0 / 1 = never / wherever their tile fits LDS (ORBFE_ARUCO_SPECKS, debug key "speck_passes")
-    int specks = -1;
-    bool specks_inkernel = false;
-    bool half_pyr = true;   // the leading exact pyramid levels in one launch (k_half_pyr; debug key "half_pyr")
-    bool thr_mfma = true;   // k_threshold_mfma where it applies (windows up to 15; debug key "threshold_mfma" = 1 / 0)
-    bool thr_mfma_auto = true; // ... but k_threshold_pyr for calls of fewer than 8 frames ("threshold_mfma" = 1 forces the matrix-core kernel, -1 = this rule again)
     DevBuf d_tstrips, d_ttabs, d_ttab2;
-    ThresholdTables ttab;   // the tables of k_threshold_mfma on the device (detector_plan.hpp); .ok: the kernel applies
+    ThresholdTables ttab;   // the tables of k_threshold_mfma on the device (detector_plan.hpp)
     template <class T> static int upload(DevBuf& d, const std::vector<T>& v)
     {
         if (int rc = d.ensure(v.size() * sizeof(T))) return rc;
         if (!v.empty()) ORBFE_HIP(hipMemcpy(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
         return ORBFE_OK;
     }
-    // A failed upload leaves the handle without tables (the next batch that wants them starts over)
+    // For a batch whose plan says Thr::mfma (plan_batch: threshold_tables_apply).  A failed upload leaves the handle without tables
+    // (the next batch that wants them starts over)
     int ensure_threshold_tables()
     {
         if (ttab.cols == geo.cols && ttab.win == geo.win) return ORBFE_OK;
         ThresholdTables fresh = plan_threshold_tables(geo.cols, geo.win);
         ttab = ThresholdTables{};
+        if (!fresh.ok) return fail(ORBFE_ERR_INVALID, "matrix-core threshold tables refused a %d-pixel row at window %d", geo.cols, geo.win);
         int rc;
-        if (fresh.ok && ((rc = upload(d_tstrips, fresh.strips)) || (rc = upload(d_ttabs, fresh.tabs)) || (rc = upload(d_ttab2, fresh.tab2)))) return rc;
+        if ((rc = upload(d_tstrips, fresh.strips)) || (rc = upload(d_ttabs, fresh.tabs)) || (rc = upload(d_ttab2, fresh.tab2))) return rc;
         ttab = std::move(fresh);
         return ORBFE_OK;
     }
-    bool thr_v2 = true;   // k_threshold_pyr where it applies (debug key "threshold_pyr": the tests run both threshold kernels)
     bool specks_ran = false;   // the last batch's contour kernels read d_bitsc
     DevBuf d_bitsc;
-    bool force_legacy = false; // debug: always use k_contours_t
-    bool big_mode = false;     // orbfe_aruco_set_big_frames: every batch on Contours::big (a retry passes its path to run_device instead)
     DevBuf d_codes, d_levels, d_bits, d_pyr, d_candq, d_pool, d_kept, d_rects, d_counts, d_candidx, d_ncand,
         d_result, d_gpad;
     DevBuf d_in, d_out, d_nout;
@@ -194,25 +151,13 @@ struct orbfe_aruco {
             if ((rc = batch(floor, &ran))) return rc;
             ORBFE_HIP(hipStreamSynchronize(own_stream));
             for (int f = 0; f < nframes; f++) flags_or |= counts[f * 4 + 2];
-            if (force_legacy || (floor = escalate(ran, flags_or, geo.relay_tbits != 0)) == Contours::none) return ORBFE_OK;
+            if (sw.force_legacy || (floor = escalate(ran, flags_or, geo.relay_tbits != 0)) == Contours::none) return ORBFE_OK;
             n_escalations++;
         }
     }
     bool stateful() const { return thres_method == 1 || auto_size || tracking_min > 0; } // a frame's result depends on the frames before it
     KernelTimer timer;
     int last_nframes = 0;
-
-    ~orbfe_aruco()
-    {
-        for (DevBuf* b : {&d_codes, &d_levels, &d_bits, &d_pyr, &d_candq, &d_pool, &d_kept, &d_rects,
-                          &d_counts, &d_candidx, &d_ncand, &d_result, &d_gpad, &d_in, &d_out, &d_nout, &d_segs, &d_tailkeys, &d_tailoff, &d_small, &d_hint, &d_rstate, &d_lut, &d_twork, &d_trect, &d_tctr, &d_dwork, &d_dctr, &d_ditems, &d_dhist, &d_dpatch, &d_poses, &d_scodes, &d_sids,
-                          &d_msrc, &d_red, &d_mhist, &d_masks, &d_bgr, &d_bits2, &d_ctseg, &d_cthtab, &d_ctelem, &d_ctstate, &d_ctitemsA, &d_ctitemsB, &d_ctnitems, &d_ctcodes, &d_ctmlist, &d_bitsc, &d_tstrips, &d_ttabs, &d_ttab2})
-            b->release();
-        if (own_stream) (void)hipStreamDestroy(own_stream);
-        if (aux_stream) (void)hipStreamDestroy(aux_stream);
-        if (ev_fork) (void)hipEventDestroy(ev_fork);
-        if (ev_join) (void)hipEventDestroy(ev_join);
-    }
 
     int set_dictionary(const char* name)
     {
@@ -270,7 +215,7 @@ struct orbfe_aruco {
             }
             rl_static = most + 256;
         }
-        DetectorGeometry fresh = plan_detector(rows_, cols_, prows, pcols, S, specks_inkernel, getenv("ORBFE_ARUCO_LCAP") ? atoi(getenv("ORBFE_ARUCO_LCAP")) : 0, rl_static);
+        DetectorGeometry fresh = plan_detector(rows_, cols_, prows, pcols, S, sw.specks_inkernel, sw.lcap, rl_static);
         if (fresh.err) return fail(fresh.err, "%s", fresh.msg);
         DevBuf lv;
         if (int rc = upload(lv, fresh.levels)) return rc;
@@ -296,7 +241,7 @@ struct orbfe_aruco {
             (rc = d_small.ensure((size_t)geo.relay_kcap * 16 * B)) || (rc = d_rstate.ensure((size_t)8 * B)) ||
             (rc = d_twork.ensure((size_t)geo.relay_kcap * 32 * B)) || (rc = d_trect.ensure((size_t)geo.relay_kcap * B)))
             return rc;
-        if (tiled != 0) {
+        if (sw.tiled != 0) {
             const size_t elem_words = (size_t)geo.ct_segcap + ((size_t)geo.ct_segcap + 3) / 4; // u64 elements + u16 next ids, per frame
             if ((rc = d_ctseg.ensure((size_t)5 * geo.ct_segcap * 4 * B)) || (rc = d_cthtab.ensure(((size_t)8 << geo.ct_hbits) * B)) ||
                 (rc = d_ctelem.ensure(elem_words * 8 * B)) || (rc = d_ctstate.ensure((size_t)CT_STATE_INTS * 4 * B)) ||
@@ -345,62 +290,6 @@ struct orbfe_aruco {
         return ORBFE_OK;
     }
 
-    // What run_device launches for a batch: every choice of kernel, variant and size, made once before its first launch
-    struct BatchPlan {
-        Thr thr = Thr::box; uint32_t thr_kk = 0;   // the threshold kernel; k_threshold_pyr: K | K << 16
-        int nfuse = 0;                // pyramid levels k_threshold_pyr writes, the rest in line behind it (0: the pyramid on the aux stream)
-        bool specks = false;          // k_speck_clean between threshold and contours
-        Contours contours = Contours::tiled;   // the path that runs; its variants:
-        bool band = false; int band_rows = 0, tile_w = 0, tpw = 0;   // tiled: k_ct_band, band_rows cell rows a band (else k_ct_walk: tile_w-pixel tiles, tpw tiles a wave)
-        Relay relay = Relay::relay;   // relay: the kernel, and k_contours_small behind it or not
-        bool small_separate = false, walker_hbm = false;   // walker: k_contours_t with its bit image in HBM and AR_MAX_KEPT_BIG kept borders
-    };
-    int plan_batch(int B, const ModeRun* mr, Contours floor, BatchPlan& p)
-    {
-        const bool reduced = mr && mr->d_full;
-        // The threshold kernel of the batched configuration writes the pyramid levels its 64 x 64 tiles hold whole (k_threshold_pyr): the
-        // exact halvings, at most four, when the pyramid starts from the thresholded frame itself and n v + K stays within 16 bits
-        const long n2 = (long)geo.win * geo.win, K = n2 * thres_value - n2 / 2;
-        const bool adaptive = !(mr && mr->fixed_thr >= 0), win_t = geo.win == 5 || geo.win == 7 || geo.win == 11 || geo.win == 15;
-        const bool fused_ok = adaptive && thr_v2 && win_t && K >= 0 && n2 * 255 + K <= 65535;
-        // A call of a few frames (the drop-in call: one) is a chain of launches that each wait for the one before: there the kernel that
-        // also writes the pyramid (one launch instead of five) is the shorter chain -- detect 0.333 -> 0.303 ms per 640 x 480 frame;
-        // a batch has the pyramid next to the contour kernels on a stream of its own and takes the matrix-core kernel
-        const bool try_mfma = adaptive && thr_mfma && K > -(1 << 20) && K < (1 << 20) && !(fused_ok && !reduced && B < 8 && thr_mfma_auto);
-        if (int rc = try_mfma ? ensure_threshold_tables() : ORBFE_OK) return rc;
-        p.thr = !adaptive ? Thr::fixed : try_mfma && ttab.ok ? Thr::mfma : fused_ok ? Thr::pyr : Thr::box;
-        if (p.thr == Thr::pyr) p.thr_kk = (uint32_t)K | ((uint32_t)K << 16);
-        for (int l = 1; p.thr == Thr::pyr && !reduced && l < geo.npyr && l <= 4; l++) {
-            if (!geo.lvl_exact[l] || geo.levels[l].pitch % 4 != 0 || geo.levels[l].pitch < 4 * ((geo.levels[l].w + 3) / 4)) break;
-            p.nfuse = l;
-        }
-        // the first contour path from `floor` on that may run (big_mode: orbfe_aruco_set_big_frames; the tiled rule: at `tiled`)
-        if (big_mode || floor >= Contours::big) p.contours = Contours::big;
-        else if (!force_legacy && floor <= Contours::tiled && (tiled > 0 || (tiled < 0 && (geo.relay_global || !geo.relay_tbits || geo.relay_tbits > 12 || B <= 32))))
-            p.contours = Contours::tiled;
-        else p.contours = !force_legacy && floor <= Contours::relay && geo.relay_tbits ? Contours::relay : Contours::walker;
-        // the bit image the contour kernels read: after the speck passes, unless switched off or the frame is too wide for their LDS tile
-        p.specks = (specks > 0 || (specks < 0 && p.contours == Contours::relay && !geo.relay_global && B > 32)) && speck_lds_bytes(geo.cols) <= 150 * 1024;
-        // Tile width and waves.  k_ct_walk's waves are persistent and overlap their tiles, so a wave wants several tiles (its
-        // lanes always find work) and a SIMD wants several waves (a step is a chain of dependent LDS reads): narrow tiles for a
-        // batch -- ORBFE_ARUCO_TILE_W / ORBFE_ARUCO_TPW (tiles per wave) are measurement switches --, and for a few frames as many
-        // waves as there are tiles.
-        const int target = tile_w_env > 0 ? tile_w_env : (B <= 32 ? 192 : 480), ncols0 = std::max(1, (geo.cols + target - 1) / target);
-        p.tile_w = std::min(CTW_MAX_CW, std::max(32, ((geo.cols + ncols0 - 1) / ncols0 + 31) / 32 * 32));
-        p.tpw = tpw_env > 0 ? tpw_env : (B <= 32 ? 1 : 2);
-        // bands for full batches (eight waves level each other's load through the band's ticket counters) and, one cell row each, for
-        // up to four frames (single-frame call 0.385 -> 0.355 ms: the waves of a band share its start candidates, where a wave of
-        // k_ct_walk has its tile's to itself); a wave per tile in between
-        p.band = banded > 0 || (banded < 0 && (B > 32 || B <= 4));
-        const int pw = (geo.cols + 2 + 31) / 32, rb = band_rows_env > 0 ? band_rows_env : B <= 4 ? 1 : std::max(1, std::min(8, (int)((36 * 1024 / (pw * 4) - 3) / 32)));
-        p.band_rows = std::max(1, std::min(rb, (geo.rows + 31) / 32));
-        const bool wide = geo.relay_tbits <= 12 && B <= 32 && relay_wide;   // few frames: 16 waves per frame (see k_contours_relay_wide)
-        p.relay = geo.relay_global ? Relay::relay8g : geo.relay_tbits > 12 ? Relay::relay8 : wide ? Relay::wide : Relay::relay;
-        p.small_separate = geo.relay_global || (small_separate_mode < 0 ? B <= 32 : small_separate_mode != 0);   // (always behind relay8g)
-        p.walker_hbm = p.contours == Contours::big || !geo.lds_bits_words;
-        return ORBFE_OK;
-    }
-
     // A batch: the pipeline on the first contour path from `floor` on that may run; *ran = the one it took (escalate())
     int run_device(const uint8_t* d_imgs, int B, size_t frame_stride, int rows_, int cols_, size_t step, orbfe_marker* d_out_m, int capacity,
                    int32_t* d_n, hipStream_t s, const ModeRun* mr = nullptr, Contours floor = Contours::tiled, Contours* ran = nullptr)
@@ -416,8 +305,8 @@ struct orbfe_aruco {
         const ImgView src0 = reduced ? ImgView{mr->d_full, nullptr, mr->full_fstride, (int)mr->full_step} : srcW;
         timer.begin();
         timer.mark(s, "start");
-        BatchPlan p;
-        if ((rc = plan_batch(B, mr, floor, p))) return rc;
+        const BatchPlan p = plan_batch(geo, B, BatchMode{!(mr && mr->fixed_thr >= 0), reduced, thres_value}, floor, sw);
+        if (p.thr == Thr::mfma && (rc = ensure_threshold_tables())) return rc;
         if (ran) *ran = p.contours;
         // the /2 pyramid is only needed by k_decode: it runs on a second stream next to threshold + contours (what the threshold kernel
         // leaves of it: behind that kernel, in line)
@@ -453,7 +342,7 @@ struct orbfe_aruco {
     void pyramid(int first, const ImgView& src0, int B, hipStream_t st)
     {
         const ImgView pyr = pyr_view();
-        const std::vector<PyrKernel> K = plan_pyramid_kernels(geo, first, (unsigned)((uintptr_t)src0.base & 15), src0.pitch, src0.fstride, half_pyr != 0);
+        const std::vector<PyrKernel> K = plan_pyramid_kernels(geo, first, (unsigned)((uintptr_t)src0.base & 15), src0.pitch, src0.fstride, sw.half_pyr);
         if (first == 1 && first < geo.npyr && (K[1] == PyrKernel::half_pyr4 || K[1] == PyrKernel::half_pyr3)) {
             // the leading exact halvings in one launch (k_half_pyr): four from 16 x 16 source blocks, or three from 8 x 8
             const int nf = K[1] == PyrKernel::half_pyr4 ? 4 : 3, bs = 1 << nf;
@@ -583,7 +472,7 @@ struct orbfe_aruco {
                                geo.cols, geo.rows, geo.lds_bits_words, 70, geo.relay_kshift, geo.relay_tbits, d_segs.as<RelaySeg>(),
                                d_pool.as<uint32_t>(), geo.pool_fu32, (int)geo.pool_fu32, d_kept.as<ArKept>(), geo.relay_kcap, geo.relay_kcap,
                                d_tailkeys.as<unsigned long long>(), d_tailoff.as<int32_t>(), d_counts.as<int32_t>(), d_hint.as<int32_t>(),
-                               d_small.as<uint4>(), d_rstate.as<int32_t>(), (p.small_separate ? 1 : 0) | (specks_inkernel && !p.specks && !p.small_separate ? 2 : 0),
+                               d_small.as<uint4>(), d_rstate.as<int32_t>(), (p.small_separate ? 1 : 0) | (sw.specks_inkernel && !p.specks && !p.small_separate ? 2 : 0),
                                d_lut.as<uint16_t>(), 0, d_candq.as<uint32_t>(), geo.candq_fu32);
         }
         // the borders that touch no grid line, for frames done with a grid by a relay kernel that leaves them out (the
@@ -904,12 +793,7 @@ orbfe_aruco* orbfe_aruco_create(const char* dictionary, int device)
     if (use_device(device) != ORBFE_OK) return nullptr;
     orbfe_aruco* h = new orbfe_aruco();
     h->device = device;
-    // the environment switches that have a debug key go through its setter
-    if (const char* v = getenv("ORBFE_ARUCO_TILED")) (void)orbfe_aruco_debug_control(h, "tiled_contours", atoi(v) ? 1 : 0);
-    if (const char* v = getenv("ORBFE_ARUCO_SPECKS")) {
-        (void)orbfe_aruco_debug_control(h, "speck_passes", atoi(v) == 1);
-        (void)orbfe_aruco_debug_control(h, "speck_passes_in_kernel", atoi(v) == 2);
-    }
+    read_detector_env(h->sw, [](const char* name) -> const char* { return getenv(name); });   // every ORBFE_ARUCO_* variable, here and nowhere else
     if (hipStreamCreate(&h->own_stream) != hipSuccess ||
         hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
@@ -1135,7 +1019,7 @@ int aruco_speculate(orbfe_aruco* h, const uint8_t* d_img, size_t dframe, int row
                     const uint8_t* host_copy, size_t host_pitch)
 {
     h->spec.pending = false;
-    if (h->big_mode) return ORBFE_OK; // the rare big-frame mode is left to the detector's own call
+    if (h->sw.big_mode) return ORBFE_OK; // the rare big-frame mode is left to the detector's own call
     if (h->stateful() || h->min_size > 0.f) return ORBFE_OK; // frame-sequential modes (aruco_modes.hip): the detector's own call too
     int rc;
     if ((rc = h->d_out.ensure((size_t)AR_MAX_RECTS * sizeof(orbfe_marker))) || (rc = h->d_nout.ensure(4))) return rc;
@@ -1559,7 +1443,7 @@ int orbfe_aruco_set_big_frames(orbfe_aruco* h, int on)
 {
     if (!h) return fail(ORBFE_ERR_INVALID, "null handle");
     end_speculation(h);
-    h->big_mode = on != 0;
+    h->sw.big_mode = on != 0;
     return ORBFE_OK;
 }
 
@@ -1575,16 +1459,16 @@ int orbfe_aruco_debug_control(orbfe_aruco* h, const char* key, int value)
     if (!h || !key) return fail(ORBFE_ERR_INVALID, "orbfe_aruco_debug_control: null argument");
     const bool on_off = value == 0 || value == 1, by_rule = on_off || value == -1;
     if (!strcmp(key, "kernel_timing") && on_off) { h->timer.enabled = value; h->timer.reset_history(); }
-    else if (!strcmp(key, "legacy_contours") && on_off) h->force_legacy = value;
+    else if (!strcmp(key, "legacy_contours") && on_off) h->sw.force_legacy = value;
     else if (!strcmp(key, "tiled_contours") && by_rule) {
-        if (h->tiled == 0 && value != 0) h->batch_cap = 0;   // the tiled path's workspace is only allocated while it can run: allocate on the next batch
-        h->tiled = value;
+        if (h->sw.tiled == 0 && value != 0) h->batch_cap = 0;   // the tiled path's workspace is only allocated while it can run: allocate on the next batch
+        h->sw.tiled = value;
     }
-    else if (!strcmp(key, "speck_passes") && on_off) h->specks = value;
-    else if (!strcmp(key, "speck_passes_in_kernel") && on_off) { h->specks_inkernel = value; h->invalidate_geometry(); }   // (the queue's size depends on it: geometry rebuilt)
-    else if (!strcmp(key, "threshold_pyr") && on_off) h->thr_v2 = value;
-    else if (!strcmp(key, "threshold_mfma") && by_rule) { h->thr_mfma = value != 0; h->thr_mfma_auto = value == -1; }
-    else if (!strcmp(key, "half_pyr") && on_off) h->half_pyr = value;
+    else if (!strcmp(key, "speck_passes") && on_off) h->sw.specks = value;
+    else if (!strcmp(key, "speck_passes_in_kernel") && on_off) { h->sw.specks_inkernel = value; h->invalidate_geometry(); }   // (the queue's size depends on it: geometry rebuilt)
+    else if (!strcmp(key, "threshold_pyr") && on_off) h->sw.thr_pyr = value;
+    else if (!strcmp(key, "threshold_mfma") && by_rule) { h->sw.thr_mfma = value != 0; h->sw.thr_mfma_auto = value == -1; }
+    else if (!strcmp(key, "half_pyr") && on_off) h->sw.half_pyr = value;
     else return fail(ORBFE_ERR_INVALID, "orbfe_aruco_debug_control: unknown key \"%s\" or value %d", key, value);
     return ORBFE_OK;
 }

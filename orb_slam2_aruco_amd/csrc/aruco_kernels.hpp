@@ -146,9 +146,6 @@ __global__ void k_upsample_corners(ImgView src0, ImgView pyr, const ArLevel* lev
 #define RL_SLOTS_PER_THREAD (4096 / RL_THREADS)   // table slots <= RL_THREADS * RL_SLOTS_PER_THREAD (tbits <= 12)
 #define RL_NIL 0xffff
 #define RL_COPY_CAP RL_THREADS  // (documentation) kept segments per frame the flat copy lists (== RL_THREADS; 14 bytes each <= the key table)
-#define RL_FLAG_TABLE 32        // (kernel-internal) markers did not fit: coarsen the grid
-#define RL_FLAG_BUG 64          // an invariant of the relay formulation failed: redone by k_contours_t as well
-#define RL_FALLBACK_FLAGS (RL_FLAG_TABLE | RL_FLAG_BUG)
 #ifndef RL_STEPS_PER_ITER
 #define RL_STEPS_PER_ITER 2      // walk steps between two looks at the work queue
 #endif
@@ -184,7 +181,6 @@ __global__ void k_upsample_corners(ImgView src0, ImgView pyr, const ArLevel* lev
 #ifndef CTW_TAKE
 #define CTW_TAKE 256             // enumeration items per refill of the queue (halved while they do not fit)
 #endif
-#define CTW_MAX_CW 480           // tile width limit: the marker pixels of all relay columns of a tile (31 x (cw / 32 + 1)) fit the queue
 #define CT_STATE_INTS 8          // per frame: segments, kept small borders, pool words in use, flags, start candidates
 #define CT_CODE_WORDS 4          // chain code of a segment: 10 steps of 3 bits per word, kept in registers while the segment is walked and written with
                                  // its record (16 bytes); a walk that fills it ends the segment there and goes on as the next one

@@ -3,6 +3,8 @@
 // no HIP: csrc/aruco_detector.hip computes a geometry per input size and swaps it into the handle once its tables are on the device,
 // tests/test_detector_plan_cpu.py compiles this header with g++ and checks it against the oracle.  A geometry is a value:
 // plan_detector() returns either a complete one or an error (err, msg).
+// Below it: the detector's switches (DetectorSwitches, read from the environment once per handle by read_detector_env) and what a
+// batch launches on a geometry (plan_batch, escalate): pure functions of plain inputs, pinned by the same CPU tests.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -10,6 +12,7 @@
 #include <algorithm>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <vector>
 
 #include "../../include/orbfe.h"
@@ -21,6 +24,15 @@ namespace orbfe {
 #define AR_MAX_KEPT 1024
 #define AR_MAX_KEPT_BIG 4096 // the single-walker kernel with the bit image in HBM: LDS has room for this many kept borders
 #define RL_KCAP AR_MAX_KEPT  // kept borders per frame (k_contours_relay + k_contours_tail)
+#define CTW_MAX_CW 480           // tile width limit: the marker pixels of all relay columns of a tile (31 x (cw / 32 + 1)) fit the queue
+// a frame's flag word (counts[f * 4 + 2]; ORBFE_ARUCO_FLAG_TRUNCATED, include/orbfe.h, is its bit 128): the two capacity bits every
+// contour kernel sets (as the literals 2 and 4), and the relay formulation's own
+#define AR_FLAG_KEPT 2          // more kept borders than the path's list holds
+#define AR_FLAG_POOL 4          // the frame's point pool (or a kernel's staging arena in it) is full
+#define AR_CAPACITY_FLAGS (AR_FLAG_KEPT | AR_FLAG_POOL)
+#define RL_FLAG_TABLE 32        // (kernel-internal) markers did not fit: coarsen the grid
+#define RL_FLAG_BUG 64          // an invariant of the relay formulation failed: redone by k_contours_t as well
+#define RL_FALLBACK_FLAGS (RL_FLAG_TABLE | RL_FLAG_BUG)
 
 // one level of the detector's /2 pyramid
 struct ArLevel {
@@ -231,12 +243,16 @@ struct ThresholdTables {
     std::vector<uint8_t> tabs, tab2;
 };
 
+// Where k_threshold_mfma applies: windows up to 15 and frames at least 48 pixels wide.  plan_batch chooses the kernel by this, the
+// handle builds and uploads the tables afterwards (tests/test_detector_plan_cpu.py: the tables of every such width and window come out ok)
+inline bool threshold_tables_apply(int cols, int win) { return win / 2 <= 7 && cols >= 48; }
+
 inline ThresholdTables plan_threshold_tables(int cols, int win)
 {
     ThresholdTables t;
     t.cols = cols; t.win = win;
     const int R = win / 2, n2 = win * win, W = cols, rb = R <= 3 ? 4 : 8;
-    if (R > 7 || W < 48) return t;
+    if (!threshold_tables_apply(cols, win)) return t;
     t.tabs.reserve((size_t)(W + 31) / 32 * 4096);
     for (int X = 0; X < W; X += 32) {
         ThrStrip S{};
@@ -283,6 +299,156 @@ inline ThresholdTables plan_threshold_tables(int cols, int win)
     t.rb = rb;
     t.ok = true;
     return t;
+}
+
+// ---- the detector's switches: what a handle may be told about HOW it runs (never about what it computes: every path is bit-exact).
+// The handle keeps one of these; read_detector_env fills the environment-driven fields once, at creation, and
+// orbfe_aruco_debug_control / orbfe_aruco_set_big_frames change the fields that have a key.  plan_batch reads nothing else.
+struct DetectorSwitches {
+    // the tiled relay formulation (aruco_tiles.hip: k_ct_band or k_ct_walk / k_ct_lists / k_ct_points).  -1 = by frame and batch size:
+    // frames for which the one-workgroup relay kernel needs its 8192-slot table and a CU to itself (1280 x 720: 300-frame step 4.09 -
+    // 4.13 -> 3.96 - 4.07 ms) or whose bit image does not fit LDS at all (1920 x 1080: 100-frame step 4.88 -> 3.41 ms), and batches of
+    // up to 32 frames (a frame's walks spread over ~40 CUs instead of one); full batches of 640 x 480 frames keep the one-workgroup
+    // kernel, whose single launch costs the pipeline less than band + lists + points (1.32 - 1.34 against 1.45 - 1.62 ms per step).
+    // ORBFE_ARUCO_TILED = 0 / 1 (debug key "tiled_contours") forces it off / on for every batch (tests, A/B)
+    int tiled = -1;
+    // the walks of the tiled path by BANDS of cell rows, a workgroup of eight waves each (k_ct_band), instead of a wave per tile
+    // (k_ct_walk): -1 = by frame / batch size, 0 / 1 forced (ORBFE_ARUCO_BANDED)
+    int banded = -1;
+    int band_rows = 0;   // ORBFE_ARUCO_BAND_ROWS = cell rows per band (0: what fits ~36 KB of LDS, at most 8)
+    int tile_w = 0;      // ORBFE_ARUCO_TILE_W = tile width in pixels of k_ct_walk, ORBFE_ARUCO_TPW = its tiles per wave: measurement
+    int tpw = 0;         // switches (0: by batch size)
+    int lcap = 0;        // ORBFE_ARUCO_LCAP > 0: list elements k_ct_lists keeps in LDS (a measurement switch; an input of plan_detector)
+    // The speck passes (aruco_trace.hpp "FEWER WALKS" (2)): result-neutral, a quarter of the contour stage's start candidates and walks
+    // gone -- and OFF by default, because neither way of running them pays in the pipeline:
+    //   = 1: as a launch of their own between threshold and contours (k_speck_clean), for every contour path: the contour stage of
+    //     300 x 640 x 480 alone 462 -> 408 us, but one more launch on the detector's chain costs the pipeline more than that (C2 step
+    //     1.40 - 1.46 against 1.34 - 1.38 ms, single-frame detect 0.357 against 0.358 ms; profiles/r05_contour_reductions_ab.txt);
+    //   = 2: inside the one-workgroup relay kernels, on the bit image they hold in LDS anyway (speck_pass_frame; batches of more than
+    //     32 frames whose image fits LDS): 462 -> 440 us alone and 140 -> 120 us of VALU issue, the C2 step unchanged (1.343 against
+    //     1.333 ms, four interleaved runs) -- and the rim masks and anchors of a frame (120 KB) go through scratch in HBM, which
+    //     doubles the stage's HBM traffic (148 -> 268 MB per step).
+    // ORBFE_ARUCO_SPECKS = 0 (default) / 1 / 2.  Debug keys "speck_passes": the launch on / off, "speck_passes_in_kernel": inside.
+    // Tested either way (tests/test_aruco_gpu.py, tests/test_stress_gpu.py).
+    // the speck passes as a launch between threshold and contours: -1 = where they pay (full batches on the one-workgroup relay kernels:
+    // 1.246 against 1.263 ms per C2 step with them, round 6; on the tiled paths 3.99 against 3.74 ms at 1280 x 720, 3.53 against 3.21 at
+    // 1920 x 1080), 0 / 1 = never / wherever their tile fits LDS
+    int specks = -1;
+    bool specks_inkernel = false;   // (an input of plan_detector: the relay kernels' scratch grows by the passes' rim masks)
+    bool relay_wide = true;   // k_contours_relay_wide for up to 32 frames that fit the 4096-slot table (ORBFE_ARUCO_RELAY_WIDE=0: k_contours_relay)
+    // phase (c) of LDS-resident frames as its own launch (k_contours_small): -1 = by batch size (a few frames leave most of the chip
+    // idle, so the many small workgroups of the separate kernel shorten the call: 0.62 -> 0.57 ms for one 640 x 480 frame; a full
+    // batch issues more instructions that way and the pipeline is bound by those: 1.85 -> 1.98 ms per C2 step), 0 / 1 = forced
+    // (ORBFE_ARUCO_SMALL_SEPARATE)
+    int small_separate = -1;
+    bool thr_mfma = true;        // k_threshold_mfma where it applies (windows up to 15; debug key "threshold_mfma" = 1 / 0)
+    bool thr_mfma_auto = true;   // ... but k_threshold_pyr for calls of fewer than 8 frames ("threshold_mfma" = 1 forces the matrix-core kernel, -1 = this rule again)
+    bool thr_pyr = true;         // k_threshold_pyr where it applies (debug key "threshold_pyr": the tests run both threshold kernels)
+    bool half_pyr = true;        // the leading exact pyramid levels in one launch (k_half_pyr; debug key "half_pyr")
+    bool force_legacy = false;   // debug key "legacy_contours": always k_contours_t, and no retry on another path
+    bool big_mode = false;       // orbfe_aruco_set_big_frames: every batch on Contours::big (a retry passes its path to plan_batch instead)
+};
+
+// The ORBFE_ARUCO_* variables, each looked up once (the library passes getenv, a test a table).  A variable that is not set leaves
+// its field as it is.
+typedef const char* (*EnvLookup)(const char* name);
+inline void read_detector_env(DetectorSwitches& sw, EnvLookup env)
+{
+    auto num = [&](const char* name, int unset) { const char* v = env(name); return v ? atoi(v) : unset; };
+    auto tri = [&](const char* name, int unset) { const char* v = env(name); return v ? (atoi(v) ? 1 : 0) : unset; };
+    sw.relay_wide = num("ORBFE_ARUCO_RELAY_WIDE", 1) != 0;
+    sw.small_separate = num("ORBFE_ARUCO_SMALL_SEPARATE", sw.small_separate);
+    sw.tiled = tri("ORBFE_ARUCO_TILED", sw.tiled);
+    sw.banded = tri("ORBFE_ARUCO_BANDED", sw.banded);
+    sw.band_rows = num("ORBFE_ARUCO_BAND_ROWS", sw.band_rows);
+    sw.tile_w = num("ORBFE_ARUCO_TILE_W", sw.tile_w);
+    sw.tpw = num("ORBFE_ARUCO_TPW", sw.tpw);
+    sw.lcap = num("ORBFE_ARUCO_LCAP", sw.lcap);
+    if (const char* v = env("ORBFE_ARUCO_SPECKS")) { sw.specks = atoi(v) == 1; sw.specks_inkernel = atoi(v) == 2; }
+}
+
+// The contour paths: tiled (aruco_tiles.hip), the one-workgroup relay kernels, k_contours_t where neither can run or forced ("walker"),
+// k_contours_t in big-frame mode (bit image in HBM, AR_MAX_KEPT_BIG kept borders).  A batch with a frame over a capacity of its path is
+// done again on the next (escalate(): tiled -> relay, which coarsen their grid -> (kept borders / pool) big); plan_batch takes the first.
+enum class Contours : int8_t { tiled, relay, walker, big, none };
+enum class Thr : int8_t { fixed, mfma, pyr, box };   // k_fixed_threshold, k_threshold_mfma, k_threshold_pyr<WIN>, k_adaptive_threshold<R>
+enum class Relay : int8_t { relay, relay8, wide, relay8g }; // k_contours_relay, _relay8, _relay_wide, _relay8g
+
+// The path a batch is done again on: `ran` = the one it took, flags_or = the union of its frames' flag words, relay_ok = the relay
+// kernels can run at this image size (DetectorGeometry::relay_tbits).  Contours::none: the batch stands.
+inline Contours escalate(Contours ran, int flags_or, bool relay_ok)
+{
+    const bool was_tiled = ran == Contours::tiled;
+    // from the tiled path any exceeded capacity (segment lists, kept borders, pool) goes to the one-workgroup relay kernels first:
+    // they coarsen their grid and follow what is left whole, and get through frames of dense noise that neither the tiles nor the
+    // single-walker kernel's per-lane arenas hold (480 x 640 with +-40 grey levels of noise: 203 kept borders, no flag)
+    if (was_tiled && (flags_or & (AR_CAPACITY_FLAGS | RL_FALLBACK_FLAGS)) && relay_ok) return Contours::relay;
+    return ran != Contours::big && (flags_or & (AR_CAPACITY_FLAGS | (was_tiled ? RL_FALLBACK_FLAGS : 0))) ? Contours::big : Contours::none;
+}
+
+// What a run of the pipeline is asked for besides its frames: THRES_AUTO_FIXED instead of the adaptive threshold, a reduced working
+// image under the full frame's pyramid (minSize > 0), Params::ThresHold
+struct BatchMode {
+    bool adaptive = true, reduced = false;
+    int thres_value = 7;
+};
+
+// What run_device launches for a batch: every choice of kernel, variant and size, made once before its first launch
+struct BatchPlan {
+    Thr thr = Thr::box; uint32_t thr_kk = 0;   // the threshold kernel; k_threshold_pyr: K | K << 16
+    int nfuse = 0;                // pyramid levels k_threshold_pyr writes, the rest in line behind it (0: the pyramid on the aux stream)
+    bool specks = false;          // k_speck_clean between threshold and contours
+    Contours contours = Contours::tiled;   // the path that runs; its variants:
+    bool band = false; int band_rows = 0, tile_w = 0, tpw = 0;   // tiled: k_ct_band, band_rows cell rows a band (else k_ct_walk: tile_w-pixel tiles, tpw tiles a wave)
+    Relay relay = Relay::relay;   // relay: the kernel, and k_contours_small behind it or not
+    bool small_separate = false, walker_hbm = false;   // walker: k_contours_t with its bit image in HBM and AR_MAX_KEPT_BIG kept borders
+};
+
+// The plan of a batch of B frames on geometry `geo`: the first contour path from `floor` on that may run (escalate()), and every
+// choice that depends on the batch size.  Host arithmetic only: Thr::mfma means the tables apply, the handle uploads them afterwards.
+inline BatchPlan plan_batch(const DetectorGeometry& geo, int B, const BatchMode& m, Contours floor, const DetectorSwitches& sw)
+{
+    BatchPlan p;
+    // The threshold kernel of the batched configuration writes the pyramid levels its 64 x 64 tiles hold whole (k_threshold_pyr): the
+    // exact halvings, at most four, when the pyramid starts from the thresholded frame itself and n v + K stays within 16 bits
+    const long n2 = (long)geo.win * geo.win, K = n2 * m.thres_value - n2 / 2;
+    const bool win_t = geo.win == 5 || geo.win == 7 || geo.win == 11 || geo.win == 15;
+    const bool fused_ok = m.adaptive && sw.thr_pyr && win_t && K >= 0 && n2 * 255 + K <= 65535;
+    // A call of a few frames (the drop-in call: one) is a chain of launches that each wait for the one before: there the kernel that
+    // also writes the pyramid (one launch instead of five) is the shorter chain -- detect 0.333 -> 0.303 ms per 640 x 480 frame;
+    // a batch has the pyramid next to the contour kernels on a stream of its own and takes the matrix-core kernel
+    const bool try_mfma = m.adaptive && sw.thr_mfma && K > -(1 << 20) && K < (1 << 20) && !(fused_ok && !m.reduced && B < 8 && sw.thr_mfma_auto);
+    p.thr = !m.adaptive ? Thr::fixed : try_mfma && threshold_tables_apply(geo.cols, geo.win) ? Thr::mfma : fused_ok ? Thr::pyr : Thr::box;
+    if (p.thr == Thr::pyr) p.thr_kk = (uint32_t)K | ((uint32_t)K << 16);
+    for (int l = 1; p.thr == Thr::pyr && !m.reduced && l < geo.npyr && l <= 4; l++) {
+        if (!geo.lvl_exact[l] || geo.levels[l].pitch % 4 != 0 || geo.levels[l].pitch < 4 * ((geo.levels[l].w + 3) / 4)) break;
+        p.nfuse = l;
+    }
+    // the first contour path from `floor` on that may run (big_mode: orbfe_aruco_set_big_frames; the tiled rule: at `tiled`)
+    if (sw.big_mode || floor >= Contours::big) p.contours = Contours::big;
+    else if (!sw.force_legacy && floor <= Contours::tiled && (sw.tiled > 0 || (sw.tiled < 0 && (geo.relay_global || !geo.relay_tbits || geo.relay_tbits > 12 || B <= 32))))
+        p.contours = Contours::tiled;
+    else p.contours = !sw.force_legacy && floor <= Contours::relay && geo.relay_tbits ? Contours::relay : Contours::walker;
+    // the bit image the contour kernels read: after the speck passes, unless switched off or the frame is too wide for their LDS tile
+    p.specks = (sw.specks > 0 || (sw.specks < 0 && p.contours == Contours::relay && !geo.relay_global && B > 32)) && speck_lds_bytes(geo.cols) <= 150 * 1024;
+    // Tile width and waves.  k_ct_walk's waves are persistent and overlap their tiles, so a wave wants several tiles (its
+    // lanes always find work) and a SIMD wants several waves (a step is a chain of dependent LDS reads): narrow tiles for a
+    // batch -- ORBFE_ARUCO_TILE_W / ORBFE_ARUCO_TPW (tiles per wave) are measurement switches --, and for a few frames as many
+    // waves as there are tiles.
+    const int target = sw.tile_w > 0 ? sw.tile_w : (B <= 32 ? 192 : 480), ncols0 = std::max(1, (geo.cols + target - 1) / target);
+    p.tile_w = std::min(CTW_MAX_CW, std::max(32, ((geo.cols + ncols0 - 1) / ncols0 + 31) / 32 * 32));
+    p.tpw = sw.tpw > 0 ? sw.tpw : (B <= 32 ? 1 : 2);
+    // bands for full batches (eight waves level each other's load through the band's ticket counters) and, one cell row each, for
+    // up to four frames (single-frame call 0.385 -> 0.355 ms: the waves of a band share its start candidates, where a wave of
+    // k_ct_walk has its tile's to itself); a wave per tile in between
+    p.band = sw.banded > 0 || (sw.banded < 0 && (B > 32 || B <= 4));
+    const int pw = (geo.cols + 2 + 31) / 32, rb = sw.band_rows > 0 ? sw.band_rows : B <= 4 ? 1 : std::max(1, std::min(8, (int)((36 * 1024 / (pw * 4) - 3) / 32)));
+    p.band_rows = std::max(1, std::min(rb, (geo.rows + 31) / 32));
+    const bool wide = geo.relay_tbits <= 12 && B <= 32 && sw.relay_wide;   // few frames: 16 waves per frame (see k_contours_relay_wide)
+    p.relay = geo.relay_global ? Relay::relay8g : geo.relay_tbits > 12 ? Relay::relay8 : wide ? Relay::wide : Relay::relay;
+    p.small_separate = geo.relay_global || (sw.small_separate < 0 ? B <= 32 : sw.small_separate != 0);   // (always behind relay8g)
+    p.walker_hbm = p.contours == Contours::big || !geo.lds_bits_words;
+    return p;
 }
 
 } // namespace orbfe

@@ -23,6 +23,7 @@
 #include "orbfe_common.hpp"
 #include "gather_plan.hpp"
 #include "input_layout.hpp"
+#include "pipeline_plan.hpp"
 
 using namespace orbfe;
 
@@ -79,7 +80,6 @@ Rccl* rccl()
 constexpr int NCCL_UINT8 = 1; // ncclUint8 (rccl.h: ncclInt8 = 0, ncclUint8 = 1)
 
 size_t up256(size_t v) { return (v + 255) / 256 * 256; }
-int env_or(const char* name, int v) { const char* e = getenv(name); return e && *e ? atoi(e) : v; }
 
 // the last frame of one record set -> the halo slot of another (keypoints, descriptors, count), one launch
 __global__ void k_copy_halo(const uint32_t* __restrict__ src_kps, uint32_t* __restrict__ dst_kps, const uint32_t* __restrict__ src_desc,
@@ -296,11 +296,7 @@ struct orbfe_pipeline {
 
 const char* orbfe_pipeline_env_defaults(void)
 {
-    // one list for the pipeline and the engines: bench.py marks a line as diagnostic when one of these is set to something else
-    return "ORBFE_ENGINE_SETS=2;ORBFE_RECORD_SETS=4;ORBFE_PHASE_PIN=size;ORBFE_DET_PIN=4;ORBFE_DEFER_POST=size;ORBFE_DET_NOFORK=size;"
-           "ORBFE_ARUCO_RELAY_WIDE=1;"
-           "ORBFE_ARUCO_SPECKS=size;ORBFE_DESCRIBE_LATE=1;ORBFE_ARUCO_SMALL_SEPARATE=size;ORBFE_ARUCO_TILED=size;ORBFE_ARUCO_TILE_W=0;ORBFE_ARUCO_TPW=0;ORBFE_ARUCO_BANDED=size;ORBFE_ARUCO_BAND_ROWS=0;ORBFE_ARUCO_LCAP=0;"
-           "ORBFE_GATHER_STREAM=0;ORBFE_RCCL_LIB=";
+    return pipeline_env_defaults();   // (pipeline_plan.hpp)
 }
 
 int orbfe_pipeline_config_default(orbfe_pipeline_config* c, int frames, int rows, int cols)
@@ -334,28 +330,18 @@ orbfe_pipeline* orbfe_pipeline_create(const orbfe_pipeline_config* cfg)
     p->cfg.dictionary[sizeof(p->cfg.dictionary) - 1] = 0;
     const int B = p->B = cfg->frames, rows = p->rows = cfg->rows, cols = p->cols = cfg->cols;
     p->use_orb = cfg->use_orb != 0; p->use_aruco = cfg->use_aruco != 0;
-    const bool vga = (size_t)rows * cols <= (size_t)640 * 480;
-    // defaults by frame size, each overridable by the configuration and, for measurements, by the environment
-    auto pick = [&](int cfgv, const char* env, int dflt) { return env_or(env, cfgv >= 0 ? cfgv : dflt); };
-    // two extractor sets (1.4955 against 1.5288 ms per C2 step in round 3; 1920 x 1080 lost then, 4.84 -> 5.00, while its contour
-    // stage held whole CUs -- with the banded contour kernels it gains: 3.58 against 3.64 ms, three interleaved runs each)
-    p->D = std::max(1, pick(cfg->engine_sets, "ORBFE_ENGINE_SETS", 2));
-    if (!p->use_orb) p->D = 1;
-    p->R = std::max(2, pick(cfg->record_sets, "ORBFE_RECORD_SETS", 4));
-    // the extractor sets' lock: behind the other set's quadtree up to 1280 x 720; behind its FAST above (1920 x 1080 with the banded contour
-    // kernels, four runs each: 3.15 - 3.19 ms per step, no lock at all 3.16 - 3.18, behind the quadtree 3.33 - 3.37, tools/r04_pins35b.sh)
-    const bool above_720p = (size_t)rows * cols > (size_t)1280 * 720;
-    p->phase_pin = pick(cfg->phase_pin, "ORBFE_PHASE_PIN", above_720p ? 1 : 2);
-    p->det_pin = pick(cfg->det_pin, "ORBFE_DET_PIN", 4);
-    p->defer_post = pick(cfg->defer_post, "ORBFE_DEFER_POST", vga ? 1 : 0) != 0;
-    p->det_nofork = pick(cfg->det_nofork, "ORBFE_DET_NOFORK", vga ? 1 : 0) != 0;
+    // every size-, configuration- and environment-dependent choice of the schedule (pipeline_plan.hpp); below only resources are created
+    const Schedule sched = plan_schedule(rows, cols, p->use_orb, ScheduleConfig{cfg->engine_sets, cfg->record_sets, cfg->phase_pin, cfg->det_pin, cfg->defer_post, cfg->det_nofork},
+                                         [](const char* name) -> const char* { return getenv(name); });
+    p->D = sched.D; p->R = sched.R; p->phase_pin = sched.phase_pin; p->det_pin = sched.det_pin;
+    p->defer_post = sched.defer_post; p->det_nofork = sched.det_nofork; p->describe_late = sched.describe_late;
     auto bail = [&](const char* what) -> orbfe_pipeline* {
         if (what) { std::string m = g_err; fail(ORBFE_ERR_HIP, "orbfe_pipeline_create: %s (%s)", what, m.c_str()); }
         return nullptr;
     };
     auto mkstream = [&](hipStream_t* s) { return hipStreamCreateWithFlags(s, hipStreamNonBlocking) == hipSuccess; };
     if (!mkstream(&p->st_det) || !mkstream(&p->st_match)) return bail("stream");
-    if (env_or("ORBFE_GATHER_STREAM", 0)) {
+    if (sched.gather_stream) {
         int lo = 0, hi = 0;
         if (hipDeviceGetStreamPriorityRange(&lo, &hi) != hipSuccess) { (void)hipGetLastError(); lo = hi = 0; }
         if (hipStreamCreateWithPriority(&p->st_gather, hipStreamNonBlocking, lo) != hipSuccess) return bail("stream");
@@ -375,17 +361,6 @@ orbfe_pipeline* orbfe_pipeline_create(const orbfe_pipeline_config* cfg)
         }
         if (p->phase_pin && p->D > 1)
             for (int d = 0; d < p->D; d++) orbfe_extractor_follow(p->ex[d], p->ex[(d + p->D - 1) % p->D], p->phase_pin);
-        // A batch's descriptor kernel one step late, behind the NEXT batch's resize chain (round 6).  Both live on the CU's vector memory
-        // path -- unaligned 8- and 16-byte lane loads -- and next to each other the resize chain, which is on the step's critical chain,
-        // took 400 - 450 us (200 alone); next to FAST, which is VALU-bound, the descriptors cost less than they gave back at 640 x 480:
-        // 1.308 against 1.338 ms per C2 step (twelve interleaved runs each; resize 294 - 336 us, FAST 810 - 890 instead of 610 - 690).
-        // With the blur on the matrix cores (k_blur7_mfma) FAST has the vector ALUs more to itself and every size gains: C2 1.265
-        // against 1.327, 1280 x 720 3.70 against 3.74, 1920 x 1080 3.13 against 3.21 ms.
-        // A lock on stage 3 -- the descriptors of a batch -- would be circular with it: the descriptors of batch i - 1 wait for the
-        // resize chain of batch i.  Such a lock turns it off.
-        const bool stage3_lock = p->phase_pin % 10 == 3 || p->phase_pin / 10 == 3 || p->det_pin % 10 == 3;
-        p->describe_late = pick(-1, "ORBFE_DESCRIBE_LATE", 1) != 0 && p->D > 1 && !stage3_lock;
-        if (p->describe_late) p->defer_post = true;
         p->cap = orbfe_extractor_max_keypoints(p->ex[0]);
     } else
         p->cap = 1;

@@ -23,6 +23,12 @@ def lib():
         L.dplan_threshold_sweep.argtypes = [i32, i32, i32, vp]
         L.dplan_input_layout.argtypes = [i32, i32, C.c_ulonglong, C.c_ulonglong, i32, vp, i32]
         L.dplan_pyramid_kernels.argtypes = [i32, i32, i32, i32, i32, i32, C.c_ulonglong, i32, vp, i32]
+        L.dplan_switch_defaults.argtypes = [vp]
+        L.dplan_read_env.argtypes = [vp, vp, i32, vp, vp, i32]
+        L.dplan_batch.argtypes = [i32, i32, i32, i32, i32, i64, i32, i32, i32, i32, i32, vp, vp]
+        L.dplan_escalate.argtypes = [i32, i32, i32]
+        L.dplan_forced_speck_launch.argtypes = [i32, i32]
+        L.dplan_threshold_predicate_differs.argtypes = [i32, i32]
         _lib = L
     return _lib
 
@@ -79,3 +85,59 @@ def pyramid_kernels(rows, cols, base_off, step, frame_stride, half_pyr=True, fir
     n = lib().dplan_pyramid_kernels(rows, cols, S, first, base_off & 15, step, frame_stride, int(half_pyr), _p(out), MAXLEVELS)
     assert n >= 1, n
     return [PYR_KERNELS[v] for v in out[1:n]]
+
+
+# DetectorSwitches (detector_plan.hpp), in the driver's order
+SWITCH_FIELDS = ("tiled", "banded", "band_rows", "tile_w", "tpw", "lcap", "specks", "specks_inkernel", "relay_wide", "small_separate", "thr_mfma",
+                 "thr_mfma_auto", "thr_pyr", "half_pyr", "force_legacy", "big_mode")
+PLAN_FIELDS = ("thr", "thr_kk", "nfuse", "specks", "contours", "band", "band_rows", "tile_w", "tpw", "relay", "small_separate", "walker_hbm")
+CONTOURS = ("tiled", "relay", "walker", "big", "none")       # enum class Contours
+THR = ("fixed", "mfma", "pyr", "box")                        # enum class Thr
+RELAY = ("relay", "relay8", "wide", "relay8g")               # enum class Relay
+
+
+def switch_defaults():
+    """DetectorSwitches as a handle has them with no ORBFE_ARUCO_* variable set."""
+    out = np.zeros(len(SWITCH_FIELDS), np.int32)
+    lib().dplan_switch_defaults(_p(out))
+    return {f: int(out[i]) for i, f in enumerate(SWITCH_FIELDS)}
+
+
+def read_env(env):
+    """(the switches read_detector_env leaves for the environment `env`, a dict -- the process environment is not touched --, the list
+    of names it asked for)."""
+    names = (C.c_char_p * max(len(env), 1))(*[k.encode() for k in env])
+    values = (C.c_char_p * max(len(env), 1))(*[v.encode() for v in env.values()])
+    out = np.zeros(len(SWITCH_FIELDS), np.int32)
+    asked = C.create_string_buffer(4096)
+    lib().dplan_read_env(names, values, len(env), _p(out), asked, 4096)
+    return {f: int(out[i]) for i, f in enumerate(SWITCH_FIELDS)}, [n for n in asked.value.decode().split(";") if n]
+
+
+def batch(rows, cols, B, floor="tiled", adaptive=True, thres_value=7, work=None, S=35, rl_static=4352, **switches):
+    """plan_batch for B frames of rows x cols, as a dict with the enums by name.  work = (rows, cols) of a reduced working image under
+    the frame's pyramid; keyword arguments override fields of the default DetectorSwitches."""
+    sw = switch_defaults()
+    assert set(switches) <= set(sw), switches
+    sw.update(switches)
+    swv = np.array([sw[f] for f in SWITCH_FIELDS], np.int32)
+    out = np.zeros(len(PLAN_FIELDS), np.int64)
+    wr, wc = work if work else (rows, cols)
+    rc = lib().dplan_batch(wr, wc, rows, cols, S, rl_static, B, int(adaptive), int(work is not None), thres_value, CONTOURS.index(floor), _p(swv), _p(out))
+    assert rc == 0, rc
+    d = {f: int(out[i]) for i, f in enumerate(PLAN_FIELDS)}
+    d["thr"] = THR[d["thr"]]; d["contours"] = CONTOURS[d["contours"]]; d["relay"] = RELAY[d["relay"]]
+    return d
+
+
+def escalate(ran, flags_or, relay_ok):
+    return CONTOURS[lib().dplan_escalate(CONTOURS.index(ran), flags_or, int(relay_ok))]
+
+
+def threshold_predicate_differs(cols, win):
+    return bool(lib().dplan_threshold_predicate_differs(cols, win))
+
+
+def forced_speck_launch(cols, B):
+    """whether plan_batch gives a `cols`-wide frame the speck launch when it is forced on"""
+    return bool(lib().dplan_forced_speck_launch(cols, B))

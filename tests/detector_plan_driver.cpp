@@ -136,4 +136,86 @@ int dplan_pyramid_kernels(int rows, int cols, int S, int first, int src_align, i
     return g.npyr;
 }
 
+// ---- the switches, the environment reader and the batch plan
+
+// DetectorSwitches as 16 ints, in the order of detector_plan_build.SWITCH_FIELDS
+static void switches_out(const DetectorSwitches& w, int* o)
+{
+    const int v[16] = {w.tiled, w.banded, w.band_rows, w.tile_w, w.tpw, w.lcap, w.specks, w.specks_inkernel, w.relay_wide, w.small_separate,
+                       w.thr_mfma, w.thr_mfma_auto, w.thr_pyr, w.half_pyr, w.force_legacy, w.big_mode};
+    memcpy(o, v, sizeof(v));
+}
+static DetectorSwitches switches_in(const int* v)
+{
+    DetectorSwitches w;
+    w.tiled = v[0]; w.banded = v[1]; w.band_rows = v[2]; w.tile_w = v[3]; w.tpw = v[4]; w.lcap = v[5]; w.specks = v[6]; w.specks_inkernel = v[7] != 0;
+    w.relay_wide = v[8] != 0; w.small_separate = v[9]; w.thr_mfma = v[10] != 0; w.thr_mfma_auto = v[11] != 0; w.thr_pyr = v[12] != 0;
+    w.half_pyr = v[13] != 0; w.force_legacy = v[14] != 0; w.big_mode = v[15] != 0;
+    return w;
+}
+
+// An environment that is a table: `n` (name, value) pairs.  Every name a reader asks for is appended to `asked` ("NAME;"), set or not.
+// (The readers take a plain function pointer, so the table of the call in progress is file-static.)
+static const char* const* g_env_names = nullptr;
+static const char* const* g_env_values = nullptr;
+static int g_env_n = 0, g_asked_cap = 0;
+static char* g_asked = nullptr;
+static const char* table_lookup(const char* name)
+{
+    if (g_asked && strlen(g_asked) + strlen(name) + 2 <= (size_t)g_asked_cap) { strcat(g_asked, name); strcat(g_asked, ";"); }
+    for (int i = 0; i < g_env_n; i++)
+        if (!strcmp(g_env_names[i], name)) return g_env_values[i];
+    return nullptr;
+}
+static void table_set(const char* const* names, const char* const* values, int n, char* asked, int asked_cap)
+{
+    g_env_names = names; g_env_values = values; g_env_n = n; g_asked = asked; g_asked_cap = asked_cap;
+    if (asked && asked_cap > 0) asked[0] = 0;
+}
+
+// the defaults (no environment at all), and read_detector_env over a table on top of them
+void dplan_switch_defaults(int* out) { switches_out(DetectorSwitches{}, out); }
+void dplan_read_env(const char* const* names, const char* const* values, int n, int* out, char* asked, int asked_cap)
+{
+    DetectorSwitches w;
+    table_set(names, values, n, asked, asked_cap);
+    read_detector_env(w, table_lookup);
+    table_set(nullptr, nullptr, 0, nullptr, 0);
+    switches_out(w, out);
+}
+
+// plan_batch for B frames of a rows x cols working image (pyramid from prows x pcols; specks_inkernel and lcap go into the geometry as
+// the handle passes them).  out: thr, thr_kk, nfuse, specks, contours, band, band_rows, tile_w, tpw, relay, small_separate, walker_hbm.
+// Returns the geometry's error code.
+int dplan_batch(int rows, int cols, int prows, int pcols, int S, long long rl_static, int B, int adaptive, int reduced, int thres_value, int floor,
+                const int* switches, long long* out)
+{
+    const DetectorSwitches w = switches_in(switches);
+    const DetectorGeometry g = plan_detector(rows, cols, prows, pcols, S, w.specks_inkernel, w.lcap, (size_t)rl_static);
+    if (g.err) return g.err;
+    BatchMode m;
+    m.adaptive = adaptive != 0; m.reduced = reduced != 0; m.thres_value = thres_value;
+    const BatchPlan p = plan_batch(g, B, m, (Contours)floor, w);
+    const long long v[12] = {(int)p.thr, (long long)p.thr_kk, p.nfuse, p.specks, (int)p.contours, p.band, p.band_rows, p.tile_w, p.tpw, (int)p.relay,
+                             p.small_separate, p.walker_hbm};
+    memcpy(out, v, sizeof(v));
+    return ORBFE_OK;
+}
+
+// Whether a batch gets the speck launch when it is forced on ("speck_passes" = 1) and the frame is `cols` wide: the geometry of a
+// 480 x 640 frame with its width replaced, because plan_detector admits no frame wide enough for the tile not to fit
+int dplan_forced_speck_launch(int cols, int B)
+{
+    DetectorGeometry g = plan_detector(480, 640, 480, 640, 35, false, 0, 4352);
+    g.cols = cols;
+    DetectorSwitches w;
+    w.specks = 1;
+    return plan_batch(g, B, BatchMode{}, Contours::tiled, w).specks;
+}
+
+int dplan_escalate(int ran, int flags_or, int relay_ok) { return (int)escalate((Contours)ran, flags_or, relay_ok != 0); }
+
+// 1 where threshold_tables_apply(cols, win) and plan_threshold_tables(cols, win).ok disagree
+int dplan_threshold_predicate_differs(int cols, int win) { return threshold_tables_apply(cols, win) != plan_threshold_tables(cols, win).ok; }
+
 } // extern "C"

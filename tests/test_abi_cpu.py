@@ -97,6 +97,6 @@ def test_every_environment_switch_of_the_library_is_in_its_own_list():
     for f in os.listdir(csrc):
         if f.endswith((".hip", ".hpp")):
             txt = open(os.path.join(csrc, f)).read()
-            read |= set(re.findall(r'(?:getenv|env_int|env_or|pick)\((?:[^"()]*,\s*)?"(ORBFE_[A-Z0-9_]+)"', txt))
+            read |= set(re.findall(r'(?:getenv|env_int|env_or|pick|num|tri|\benv)\((?:[^"()]*,\s*)?"(ORBFE_[A-Z0-9_]+)"', txt))
     assert read, "no getenv calls found: the pattern is stale"
     assert read <= listed, sorted(read - listed)
