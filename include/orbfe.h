@@ -197,7 +197,8 @@ int orbfe_extractor_pair_detector(orbfe_extractor* h, struct orbfe_aruco* detect
 int orbfe_extractor_debug_kernel_times(orbfe_extractor* h, float* out_us, int capacity);
 
 /* ------------------------------------------------------------------ descriptor matching -- */
-/* Debug/test switch.  "knn2_path": 0 = pick by problem size (default), 1 = VALU tile kernel, 2 = matrix-core kernel.
+/* Debug/test switch.  "knn2_path": 0 = the matrix-core kernel wherever it applies -- at most 65535 train descriptors and init > 0 --
+ * and the VALU tile kernel otherwise (default), 1 = the VALU tile kernel always, 2 = as 0.
  * Both kernels give identical results.  No key of the shipped library skips work ("orb_skip" / "aruco_skip" exist only in
  * the -DORBFE_ABLATION diagnosis build, whose orbfe_version() says "+ablation"; here they are ORBFE_ERR_INVALID). */
 int orbfe_debug_control(const char* key, int value);

@@ -11,6 +11,7 @@
 #include <climits>
 
 #include "host_stage.hpp"
+#include "match_plan.hpp"
 #include "orbfe_common.hpp"
 #include "wave_dpp.hpp"
 
@@ -28,8 +29,6 @@ __device__ __forceinline__ int hamming256(const uint4& a0, const uint4& a1, cons
     d += __popc(a1.w ^ b1.w);
     return d;
 }
-
-#define KNN_TILE 256
 
 // grid: (ceil(max_nq/256), npairs, nsplit).  Split s handles train rows [s*chunk, (s+1)*chunk).
 // Partial results go to part_* [pair][split][max_nq]; with nsplit == 1 they are the final arrays.
@@ -78,8 +77,6 @@ __global__ __launch_bounds__(256) void k_knn2_tiles(const uint8_t* __restrict__ 
 // Operand layout: lane l supplies row/column l & 31 and the 16 k-values of half l >> 5; A and B are loaded with the
 // same rule, so the order of the k-values inside the instruction does not matter (a.b is a sum over k).
 // C layout (cdna4 ISA, 32 x 32): column = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5).
-#define KM_WAVES 8
-#define KM_CHUNK 128
 #define KM_ROWB 272 // bytes per spread descriptor in LDS: 256 + 16 keeps the 16-byte reads of adjacent rows on distinct banks
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
@@ -267,9 +264,6 @@ __global__ void k_knn2_merge(const int32_t* __restrict__ pidx, const int32_t* __
 }
 
 // ---------------------------------------------------------------------------- SearchForInitialization ----------
-#define GRID_COLS 64
-#define GRID_ROWS 48
-
 
 // One workgroup (256 threads) per frame pair p: F1 = frame p, F2 = frame p+1 of a stream.
 // Phase A: F2's level-0 keypoints sorted by (grid column, grid row, index) in LDS.  That is exactly the order in which
@@ -280,7 +274,6 @@ __global__ void k_knn2_merge(const int32_t* __restrict__ pidx, const int32_t* __
 // Phase C (wave 0, serial over i1 as in the reference because vMatchedDistance couples the queries): best /
 //   second-best with the "already matched better" skip, ratio + TH_LOW tests, mutual-uniqueness bookkeeping,
 //   rotation histogram, ComputeThreeMaxima, final vbPrevMatched update.
-#define SFI_MAXL0 1024
 // Three launches (round 3; before: one 1024-thread workgroup + 55 KB of LDS per frame pair, fifteen of its sixteen waves parked
 // while one wave ran the serial loop -- 146 us alone, 640 us next to the other engines' kernels):
 //   k_sfi_grid    workgroup per FRAME: what a frame contributes in either role.  As F2: its level-0 keypoints inside the Frame
@@ -306,7 +299,6 @@ struct SfiGrid { // [frame][SFI_MAXL0] arrays in HBM, written by k_sfi_grid
                       //   the 65 k atomics of a batch do not queue on a handful of cache lines of one L2 channel
 };
 #define SFI_GRID_THREADS 256
-#define SFI_CURSOR_PAD 64
 #define SFI_ROWS_BX 64         // workgroups per pair in k_sfi_rows (4 waves each, one query per wave and trip)
 #define SFI_POOL_LDS 6144      // pool entries k_sfi_accept stages in LDS (24 KB); later ones are read from the pool in HBM
 #define SFI_ROW_BITS 11        // row record = offset << 11 | count (count <= SFI_MAXL0 = 1024)
@@ -789,7 +781,6 @@ __global__ __launch_bounds__(256) void k_knn2_csr(const uint8_t* __restrict__ Q,
 //              accept best <= th_high, the accepted keypoint is taken when the query's map point has observations, rotation
 //              histogram + ComputeThreeMaxima; the result is per keypoint of the frame (match_cur[i2] = query or -1).
 #define SBP_THREADS 1024
-#define SBP_CELLS (GRID_COLS * GRID_ROWS)
 struct SbpQuery { float x, y, r; int32_t min_level, max_level; }; // r < 0: no search (the point did not project into the frame)
 struct SbpBest { // mode 2 only (q_blocks: modes 1 and 2)
     const float* q_angle;     // LastFrame.mvKeysUn[i].angle per query
@@ -814,11 +805,12 @@ __device__ __forceinline__ void sbp_frame(
     extern __shared__ __align__(16) unsigned char sbp_smem[];
     __shared__ int s_nin;
     __shared__ int s_hist[30];
-    uint32_t* s_sorted = (uint32_t*)sbp_smem;                  // (cell << 16) | index, ascending; ncap entries
-    float2* s_xy = (float2*)(s_sorted + ncap);                 // by rank
-    uint16_t* s_cell0 = (uint16_t*)(s_xy + ncap);              // first rank of every cell, SBP_CELLS + 1 entries
-    uint8_t* s_lvl = (uint8_t*)(s_cell0 + SBP_CELLS + 2);      // by rank
-    uint8_t* s_taken = s_lvl + ncap;                           // by rank
+    const SbpLdsOffsets lo = sbp_lds_offsets(ncap);            // the layout sbp_launch sized (match_plan.hpp)
+    uint32_t* s_sorted = (uint32_t*)(sbp_smem + lo.sorted);    // (cell << 16) | index, ascending; ncap entries
+    float2* s_xy = (float2*)(sbp_smem + lo.xy);                // by rank
+    uint16_t* s_cell0 = (uint16_t*)(sbp_smem + lo.cell0);      // first rank of every cell, SBP_CELLS + 1 entries
+    uint8_t* s_lvl = sbp_smem + lo.lvl;                        // by rank
+    uint8_t* s_taken = sbp_smem + lo.taken;                    // by rank
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     // bounds of the undistorted image (Frame::ComputeImageBounds; 0, 0, cols, rows without distortion) and Frame.cc:112-113
     const float mnMinX = bnd.x, mnMinY = bnd.y;
@@ -1319,8 +1311,8 @@ static int ensure_sticky_flag(DevBuf& b)
     return ORBFE_OK;
 }
 
-// debug: 0 = choose by problem size, 1 = VALU tiles (+ split/merge), 2 = matrix cores (orbfe_debug_control "knn2_path")
-static int g_knn2_path = 0;
+// orbfe_debug_control sets them
+static MatchSwitches g_match_switches;
 #ifdef ORBFE_ABLATION
 int g_orb_skip = 0, g_aruco_skip = 0;
 #endif
@@ -1329,53 +1321,21 @@ static int knn2_launch(const uint8_t* d_Q, const int32_t* d_nq, size_t q_stride,
                        const int32_t* d_nt, size_t t_stride, int max_nt, int npairs, int init, int32_t* d_best_idx,
                        int32_t* d_best_dist, int32_t* d_second_dist, hipStream_t s)
 {
-    const bool mfma_ok = max_nt <= 65535 && init > 0;
-    const bool use_mfma = mfma_ok && g_knn2_path != 1;   // distances on the matrix cores unless the VALU kernel is forced
-    // split the train set when there are too few (query-tile, pair) workgroups to fill 256 CUs
-    const int qtiles = (max_nq + 255) / 256;
-    int nsplit = 1, chunk;
-    const long long wgs = (long long)qtiles * npairs;
-    if (use_mfma) {
-        // k_knn2_mfma: 8 waves of ~110 registers -> two workgroups per CU, 512 resident; the split aims at ONE round of them (a second,
-        // half-empty round costs as much as a full one), in whole 128-descriptor chunks
-        const int max_split = (max_nt + KM_CHUNK - 1) / KM_CHUNK;
-        if (wgs < 512) nsplit = (int)std::max<long long>(1, std::min<long long>(512 / wgs, max_split));
-        chunk = (max_nt + nsplit - 1) / nsplit;
-        chunk = std::max(KM_CHUNK, (chunk + KM_CHUNK - 1) / KM_CHUNK * KM_CHUNK);
-    } else {
-        if (wgs < 1024) {
-            nsplit = (int)std::min<long long>((1024 + wgs - 1) / wgs, (max_nt + KNN_TILE - 1) / KNN_TILE);
-            if (nsplit < 1) nsplit = 1;
-        }
-        chunk = (max_nt + nsplit - 1) / nsplit;
-        chunk = std::max(KNN_TILE, (chunk + KNN_TILE - 1) / KNN_TILE * KNN_TILE);
-    }
-    nsplit = std::max(1, (max_nt + chunk - 1) / chunk);
-    const dim3 mgrid((max_nq + KM_WAVES * 32 - 1) / (KM_WAVES * 32), npairs, nsplit);
-    if (nsplit == 1) {
-        if (use_mfma)
-            hipLaunchKernelGGL(k_knn2_mfma, mgrid, dim3(KM_WAVES * 64), 0, s, d_Q, d_nq, q_stride, max_nq, d_T, d_nt, t_stride, chunk, init,
-                               d_best_idx, d_best_dist, d_second_dist);
-        else
-            hipLaunchKernelGGL(k_knn2_tiles, dim3(qtiles, npairs, 1), dim3(256), 0, s, d_Q, d_nq, q_stride, max_nq, d_T,
-                               d_nt, t_stride, chunk, init, d_best_idx, d_best_dist, d_second_dist);
-    } else {
-        // too few (query tile, pair) workgroups to fill 256 CUs: the train set is split, partials merged in split order
+    const Knn2Plan p = plan_knn2(max_nq, max_nt, npairs, init, g_match_switches);
+    // with one split the scan writes the caller's arrays; the partials of more are merged in split order
+    int32_t *o_idx = d_best_idx, *o_best = d_best_dist, *o_second = d_second_dist;
+    if (p.nsplit > 1) {
         MatchWorkspace& w = ws(s);
-        const size_t nb = (size_t)npairs * nsplit * max_nq * 4;
         int rc;
-        if ((rc = w.pidx.ensure(nb)) || (rc = w.pbest.ensure(nb)) || (rc = w.psecond.ensure(nb))) return rc;
-        if (use_mfma)
-            hipLaunchKernelGGL(k_knn2_mfma, mgrid, dim3(KM_WAVES * 64), 0, s, d_Q, d_nq, q_stride, max_nq, d_T, d_nt, t_stride, chunk, init,
-                               w.pidx.as<int32_t>(), w.pbest.as<int32_t>(), w.psecond.as<int32_t>());
-        else
-            hipLaunchKernelGGL(k_knn2_tiles, dim3(qtiles, npairs, nsplit), dim3(256), 0, s, d_Q, d_nq, q_stride, max_nq,
-                               d_T, d_nt, t_stride, chunk, init, w.pidx.as<int32_t>(), w.pbest.as<int32_t>(),
-                               w.psecond.as<int32_t>());
-        hipLaunchKernelGGL(k_knn2_merge, dim3(qtiles, npairs), dim3(256), 0, s, w.pidx.as<int32_t>(),
-                           w.pbest.as<int32_t>(), w.psecond.as<int32_t>(), nsplit, max_nq, d_nq, d_best_idx,
-                           d_best_dist, d_second_dist);
+        if ((rc = w.pidx.ensure(p.part_bytes)) || (rc = w.pbest.ensure(p.part_bytes)) || (rc = w.psecond.ensure(p.part_bytes))) return rc;
+        o_idx = w.pidx.as<int32_t>(); o_best = w.pbest.as<int32_t>(); o_second = w.psecond.as<int32_t>();
     }
+    const auto k_scan = p.mfma ? k_knn2_mfma : k_knn2_tiles;
+    hipLaunchKernelGGL(k_scan, dim3(p.scan.x, p.scan.y, p.scan.z), dim3(p.scan_block), 0, s, d_Q, d_nq, q_stride, max_nq, d_T, d_nt, t_stride,
+                       p.chunk, init, o_idx, o_best, o_second);
+    if (p.nsplit > 1)
+        hipLaunchKernelGGL(k_knn2_merge, dim3(p.merge.x, p.merge.y), dim3(KNN_TILE), 0, s, o_idx, o_best, o_second, p.nsplit, max_nq, d_nq,
+                           d_best_idx, d_best_dist, d_second_dist);
     ORBFE_HIP(hipGetLastError());
     return ORBFE_OK;
 }
@@ -1390,32 +1350,23 @@ static int sfi_launch(const orbfe_keypoint* d_kps, const uint8_t* d_desc, const 
                       float* d_prev_out, int32_t* d_m12, int32_t* d_nm, hipStream_t s, MatchWorkspace& w)
 {
     if (capacity > 65535) return fail(ORBFE_ERR_INVALID, "capacity above 65535 keypoints per frame is unsupported");
-    // a pair's candidate rows share one dense pool; a pool that turns out too small is flagged, grown by the status call (or the
-    // host wrapper) and the batch repeated.  16 K entries hold a 640 x 480 / 1000-feature pair at window 100 more than twice.
-    const int pool_cap = std::max((w.csr_per_pair + 3) / 4 * 4, 16384);
-    w.csr_per_pair = pool_cap;
-    const int nframes = npairs + 1;
-    const size_t F = (size_t)nframes * SFI_MAXL0;
+    const SfiLayout l = plan_sfi(npairs, w.csr_per_pair);   // sizes and carves the grid records and the pairs' candidate pools
+    const int pool_cap = w.csr_per_pair = l.pool, nframes = l.nframes;
     int rc;
-    // grid records: nl0 | nq | cursor (ints), then sorted, xy, ang, desc, query per frame
-    if ((rc = w.csr_cnt.ensure((size_t)nframes * (2 + SFI_CURSOR_PAD) * 4 + 64)) || (rc = w.csr_idx.ensure(F * (4 + 8 + 4 + 32 + 8 + 2) + 256)) ||
-        (rc = w.csr_dist.ensure((size_t)npairs * pool_cap * 4 + 512 /* k_sfi_accept prefetches a row's next 64 entries unconditionally: up to 63 past the last pool */)) || (rc = w.scratch.ensure((size_t)npairs * SFI_MAXL0 * 4)))
+    if ((rc = w.csr_cnt.ensure(l.cnt_bytes)) || (rc = w.csr_idx.ensure(l.idx_bytes)) || (rc = w.csr_dist.ensure(l.dist_bytes)) ||
+        (rc = w.scratch.ensure(l.scratch_bytes)))
         return rc;
-    if (!w.sfi_overflow.p) {
-        if ((rc = w.sfi_overflow.ensure(16))) return rc;
-        ORBFE_HIP(hipMemset(w.sfi_overflow.p, 0, 16));
-    }
+    if ((rc = ensure_sticky_flag(w.sfi_overflow))) return rc;
     SfiGrid G;
-    G.nl0 = w.csr_cnt.as<int32_t>();
-    G.nq = G.nl0 + nframes;
-    G.cursor = G.nq + nframes;
+    int32_t* cnt = w.csr_cnt.as<int32_t>();
+    G.nl0 = cnt + l.nl0; G.nq = cnt + l.nq; G.cursor = cnt + l.cursor;
     uint8_t* b = w.csr_idx.as<uint8_t>();
-    G.desc = reinterpret_cast<uint4*>(b); b += F * 32;
-    G.xy = reinterpret_cast<float2*>(b); b += F * 8;
-    G.sorted = reinterpret_cast<uint32_t*>(b); b += F * 4;
-    G.qxy = reinterpret_cast<float2*>(b); b += F * 8;
-    G.ang = reinterpret_cast<float*>(b); b += F * 4;
-    G.query = reinterpret_cast<uint16_t*>(b);
+    G.desc = reinterpret_cast<uint4*>(b + l.desc);
+    G.xy = reinterpret_cast<float2*>(b + l.xy);
+    G.sorted = reinterpret_cast<uint32_t*>(b + l.sorted);
+    G.qxy = reinterpret_cast<float2*>(b + l.qxy);
+    G.ang = reinterpret_cast<float*>(b + l.ang);
+    G.query = reinterpret_cast<uint16_t*>(b + l.query);
     int32_t* ovf = w.sfi_overflow.as<int32_t>(); // [0]: level-0 keypoints beyond SFI_MAXL0, [1]: pool entries a pair needed
     hipLaunchKernelGGL(k_sfi_grid, dim3(nframes), dim3(SFI_GRID_THREADS), 0, s, d_kps, d_desc, d_n, capacity, nframes, bnd, G, ovf);
     // a wave per query for frames of up to 256 level-0 keypoints (ORB-SLAM's 1000 features at 640 x 480 have ~217), more per wave above
@@ -1431,17 +1382,12 @@ static int sfi_launch(const orbfe_keypoint* d_kps, const uint8_t* d_desc, const 
 // fit (an error), or the pool size a pair needed (the pool is grown: repeat the call)
 static int sfi_take_flags(MatchWorkspace& w, const int32_t* f, hipStream_t s, int32_t* need)
 {
-    if (f[0] || f[1]) ORBFE_HIP(hipMemsetAsync(w.sfi_overflow.p, 0, 8, s)); // sticky until read
-    if (f[1] > w.csr_per_pair) w.csr_per_pair = (f[1] + 1023) / 1024 * 1024; // the next batch on this stream has the room
-    *need = f[0] > SFI_MAXL0 ? f[0] : f[1]; // the level-0 count goes with the error, also when a pool overflowed in the same batch
-    if (f[0] > SFI_MAXL0) return fail(ORBFE_ERR_CAPACITY, "%d level-0 keypoints in a frame exceed the supported %d", f[0], SFI_MAXL0);
+    const SfiFlagsDecision d = sfi_flags_decision(f[0], f[1], w.csr_per_pair);
+    if (d.clear) ORBFE_HIP(hipMemsetAsync(w.sfi_overflow.p, 0, 8, s)); // sticky until read
+    w.csr_per_pair = d.pool; // the next batch on this stream has the room
+    *need = d.need;
+    if (d.err) return fail(d.err, "%d level-0 keypoints in a frame exceed the supported %d", d.need, SFI_MAXL0);
     return ORBFE_OK;
-}
-
-// the longest candidate list of a search that overflowed decides the row stride of the next one
-static void sbp_grow_stride(MatchWorkspace& w, int overflow)
-{
-    if (overflow > w.sbp_stride) w.sbp_stride = (overflow + 63) / 64 * 64;
 }
 
 // Every projection search is this launch: nframes workgroups over B, whose candidate rows (row_*) it sizes at the workspace's
@@ -1449,20 +1395,16 @@ static void sbp_grow_stride(MatchWorkspace& w, int overflow)
 static int sbp_launch(MatchWorkspace& w, SbpBatch B, int nframes, float4 bnd, int mode, int th_high, float nnratio, float factor,
                       int check_ori, hipStream_t s)
 {
-    if (B.capacity > 65535) return fail(ORBFE_ERR_INVALID, "more than 65535 keypoints per frame are unsupported");
-    int ncap = 64;
-    while (ncap < B.capacity) ncap <<= 1;
-    const size_t lds = (size_t)ncap * (4 + 8 + 1 + 1) + (SBP_CELLS + 2) * 2 + 64;
-    if (lds > 150 * 1024) return fail(ORBFE_ERR_CAPACITY, "%d keypoints do not fit the grid kernel's LDS", B.capacity);
-    w.sbp_stride = std::max(w.sbp_stride, 128);
-    const size_t NQ = (size_t)nframes * B.qcapacity;
+    const SbpLayout l = plan_sbp(B.capacity, B.qcapacity, nframes, w.sbp_stride);
+    if (l.err) return fail(l.err, "%s", l.msg);
+    w.sbp_stride = l.stride;
     int rc;
-    if ((rc = w.csr_idx.ensure(NQ * w.sbp_stride * 2)) || (rc = w.csr_dist.ensure(NQ * w.sbp_stride)) || (rc = w.csr_cnt.ensure(NQ * 4)) ||
-        (rc = ensure_dyn_lds(reinterpret_cast<const void*>(&k_search_by_projection_batch), lds)))
+    if ((rc = w.csr_idx.ensure(l.rank_bytes)) || (rc = w.csr_dist.ensure(l.dist_bytes)) || (rc = w.csr_cnt.ensure(l.cnt_bytes)) ||
+        (rc = ensure_dyn_lds(reinterpret_cast<const void*>(&k_search_by_projection_batch), l.lds_bytes)))
         return rc;
-    B.row_rank = w.csr_idx.as<uint16_t>(); B.row_dist = w.csr_dist.as<uint8_t>(); B.row_cnt = w.csr_cnt.as<int32_t>(); B.row_stride = w.sbp_stride;
-    hipLaunchKernelGGL(k_search_by_projection_batch, dim3(nframes), dim3(SBP_THREADS), lds, s, B, ncap, bnd, mode, th_high, nnratio, factor,
-                       check_ori);
+    B.row_rank = w.csr_idx.as<uint16_t>(); B.row_dist = w.csr_dist.as<uint8_t>(); B.row_cnt = w.csr_cnt.as<int32_t>(); B.row_stride = l.stride;
+    hipLaunchKernelGGL(k_search_by_projection_batch, dim3(nframes), dim3(SBP_THREADS), l.lds_bytes, s, B, l.ncap, bnd, mode, th_high, nnratio,
+                       factor, check_ori);
     ORBFE_HIP(hipGetLastError());
     return ORBFE_OK;
 }
@@ -1546,7 +1488,7 @@ static int sbp_host_run(const SbpHostCall& c)
         const int32_t ovf = w.host<const int32_t>(s_cnt)[1];
         if (!ovf) break;
         if (attempt) return fail(ORBFE_ERR_CAPACITY, "candidate row overflow (%d)", ovf);
-        sbp_grow_stride(m, ovf);
+        m.sbp_stride = sbp_stride_after(m.sbp_stride, ovf);
     }
     int32_t* const out[6] = {c.best_idx, c.best_dist, c.best_level, c.second_dist, c.second_level, c.match};
     for (int k = 0; k < 6; k++) w.get(out[k], s_out + k * nq * 4, nq * 4);
@@ -1562,7 +1504,7 @@ extern "C" {
 
 int orbfe_debug_control(const char* key, int value)
 {
-    if (key && !strcmp(key, "knn2_path") && value >= 0 && value <= 2) { g_knn2_path = value; return ORBFE_OK; }
+    if (key && !strcmp(key, "knn2_path") && value >= 0 && value <= 2) { g_match_switches.knn2_path = value; return ORBFE_OK; }
 #ifdef ORBFE_ABLATION // diagnosis build only; the shipped library cannot skip work
     if (key && !strcmp(key, "orb_skip")) { orbfe::g_orb_skip = value; return ORBFE_OK; }
     if (key && !strcmp(key, "aruco_skip")) { orbfe::g_aruco_skip = value; return ORBFE_OK; }
@@ -1976,12 +1918,9 @@ int orbfe_fuse_search_batch_device(const orbfe_keypoint* d_kps, const uint8_t* d
         return fail(ORBFE_ERR_INVALID, "orbfe_fuse_search_batch_device: invalid argument");
     hipStream_t s = (hipStream_t)stream;
     MatchWorkspace& w = ws(s);
-    const size_t NQ = (size_t)nkf * nmp;
+    const FuseBatchLayout fl = plan_fuse_batch(nkf, nmp);
     int rc;
-    // obest: [best_level | second_dist | second_level | match] x NQ, then nq[nkf], nmatches[nkf]
-    if ((rc = w.q.ensure(NQ * sizeof(orbfe_window_query))) || (rc = w.obest.ensure((NQ * 4 + 2 * (size_t)nkf) * 4 + 256)) ||
-        (rc = ensure_sticky_flag(w.sbp_batch_overflow)))
-        return rc;
+    if ((rc = w.q.ensure(fl.q_bytes)) || (rc = w.obest.ensure(fl.obest_bytes)) || (rc = ensure_sticky_flag(w.sbp_batch_overflow))) return rc;
     for (int k = 0; k < nkf; k++) { // the projection and the gates of :848-915, one small launch per keyframe pose
         ProjectParams P;
         if ((rc = project_params(P, Tcw + 12 * k, Ow + 3 * k, K4, cols, rows, bounds, 1, scale_factors, nlevels, log_scale_factor, th, 1, 0,
@@ -1991,13 +1930,13 @@ int orbfe_fuse_search_batch_device(const orbfe_keypoint* d_kps, const uint8_t* d
                            d_min_dist, d_max_dist, d_normal, nmp, P, w.q.as<SbpQuery>() + (size_t)k * nmp);
     }
     int32_t* o = w.obest.as<int32_t>();
-    int32_t* d_nq = o + 4 * NQ;
+    int32_t* d_nq = o + fl.nq;
     ORBFE_HIP(hipMemsetD32Async((hipDeviceptr_t)d_nq, nmp, nkf, s));
     SbpBatch B{};
     B.kps = d_kps; B.desc = d_desc; B.n = d_n; B.capacity = capacity;
     B.queries = w.q.as<SbpQuery>(); B.qdesc = d_mp_desc; B.qdesc_shared = 1; B.nq = d_nq; B.qcapacity = nmp;
-    B.best_idx = d_best_idx; B.best_dist = d_best_dist; B.best_level = o; B.second_dist = o + NQ; B.second_level = o + 2 * NQ;
-    B.match = o + 3 * NQ; B.nmatches = d_nq + nkf; B.overflow = w.sbp_batch_overflow.as<int32_t>();
+    B.best_idx = d_best_idx; B.best_dist = d_best_dist; B.best_level = o + fl.best_level; B.second_dist = o + fl.second_dist;
+    B.second_level = o + fl.second_level; B.match = o + fl.match; B.nmatches = o + fl.nmatches; B.overflow = w.sbp_batch_overflow.as<int32_t>();
     if (chi2 > 0.0) { B.chi2 = chi2; for (int l = 0; l < 16; l++) B.inv_sigma2[l] = inv_level_sigma2[std::min(l, nlevels - 1)]; }
     return sbp_launch(w, B, nkf, frame_bounds(cols, rows, bounds), 0, 256, 0.0f, 0.0f, 0, s);
 }
@@ -2012,7 +1951,7 @@ int orbfe_search_by_projection_batch_status(void* stream, int32_t* overflow)
     ORBFE_HIP(hipStreamSynchronize(s));
     ORBFE_HIP(hipMemcpy(overflow, w.sbp_batch_overflow.p, 4, hipMemcpyDeviceToHost));
     if (*overflow) ORBFE_HIP(hipMemset(w.sbp_batch_overflow.p, 0, 4)); // covers every batch since it was last read
-    sbp_grow_stride(w, *overflow); // the next batch on this stream has the room
+    w.sbp_stride = sbp_stride_after(w.sbp_stride, *overflow); // the next batch on this stream has the room
     return ORBFE_OK;
 }
 
