@@ -784,6 +784,104 @@ int orbfe_search_for_triangulation_batch_device(const orbfe_keypoint* d_kps, con
                                                 const float* level_sigma2, int nlevels, int check_orientation, int32_t* d_match12,
                                                 int32_t* d_scratch21, int32_t* d_nmatches, void* stream);
 
+/* ------------------------------------------------------------ KeyFrameDatabase: candidate queries -- */
+/* KeyFrameDatabase::DetectLoopCandidates(pKF, minScore) (src/KeyFrameDatabase.cc:76-197, called by LoopClosing::DetectLoop) and
+ * KeyFrameDatabase::DetectRelocalizationCandidates(F) (:199-309, called by Tracking::Relocalization) on flat arrays, with DBoW2's
+ * L1 score (Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68).  Every output is the reference's bit for bit: the score is additions,
+ * subtractions and fabs in double in ascending word order, everything behind it float comparisons and short float sums.
+ *
+ * The database is K keyframes in the order they were add()ed ("positions" 0 .. K-1), each with its BowVector (word ids strictly
+ * ascending, values) and an `active` flag (0 = erase()d: the keyframe is never met, as a keyframe or as a neighbour; NULL = all
+ * active).  neigh[k][0 .. 9] = GetBestCovisibilityKeyFrames(10) of keyframe k as positions, in order; a negative entry is skipped
+ * (fewer than ten neighbours, or a neighbour that is not in the database).  The steps, in the reference's order:
+ *   1. the sharing list: every active keyframe that holds a word of the query -- in loop mode except the positions of `connected`
+ *      (GetConnectedKeyFrames()) -- ordered as the walk over the inverted file meets them: ascending (first common word, position).
+ *      common[k] = the number of query words keyframe k holds (mnLoopWords / mnRelocWords) for the keyframes of the list, 0 elsewhere;
+ *   2. min_common_words = (int)(max_common_words * 0.8f); a keyframe of the list with common > min_common_words is scored:
+ *      si = (float)L1Scoring::score(query, keyframe), and scores[k] = si (mLoopScore / mRelocScore).  No other entry of scores
+ *      is written.  Loop mode keeps the scored keyframes with si >= min_score, relocalization mode all of them;
+ *   3. for each kept keyframe in list order: accScore = si + the scores of its neighbours that count, in neighbour order, in
+ *      float; pBestKF = the keyframe or the neighbour with the strictly greatest score.  A neighbour counts in loop mode when it
+ *      is in the sharing list and was scored in this call; in relocalization mode when it is in the sharing list, scored or not:
+ *      one that was not scored contributes scores[k] AS THE CALLER PASSED IT (the reference reads the mRelocScore an earlier
+ *      query left, or an uninitialised float).  That is why scores is in/out; loop mode never reads what it did not write;
+ *   4. best_acc_score = the greatest accScore, starting from min_score (loop) or 0; entries with accScore > 0.75f * best_acc_score
+ *      give their pBestKF, first occurrences only: candidates[0 .. n_candidates), in the reference's order.
+ * The reference's early returns (no sharing keyframe; nothing kept) give n_candidates = 0 and zero in the fields behind them.
+ * scoring is DBoW2's enum (0 = L1_NORM, what ORBvoc.txt declares); anything else is ORBFE_ERR_INVALID. */
+#define ORBFE_KFDB_LOOP 0
+#define ORBFE_KFDB_RELOC 1
+#define ORBFE_KFDB_NEIGHBOURS 10
+#define ORBFE_KFDB_MAX_KEYFRAMES 8192  /* K of one call */
+#define ORBFE_KFDB_MAX_WORDS 4096      /* words of a query BowVector (the bound of the vocabulary transform) */
+
+typedef struct orbfe_kfdb_result {
+    int32_t n_sharing;          /* lKFsSharingWords.size() */
+    int32_t max_common_words, min_common_words;
+    int32_t n_scored;           /* nscores */
+    int32_t n_kept;             /* lScoreAndMatch.size() */
+    int32_t n_candidates;       /* size of the returned vector */
+    float   best_acc_score, min_score_to_retain; /* 0 when the function returned early */
+    int32_t status;             /* ORBFE_OK; the batch call: ORBFE_ERR_INVALID for a query it skipped (see there) */
+} orbfe_kfdb_result;
+
+/* One query, host pointers.  Query: q_word / q_value, nbow entries.  Database: CSR, keyframe k owns entries offsets[k] ..
+ * offsets[k + 1] of word / value.  connected / nconn and min_score are read in loop mode only.  candidates: K entries of room,
+ * n_candidates are written; common (K entries, all written) may be NULL; scores: K entries, see above.
+ * ORBFE_ERR_INVALID: NULL pointers, an unknown mode or scoring, words not strictly ascending, offsets that do not start at 0 or
+ * decrease, a position outside [0, K) in connected, a neigh entry >= K, a value or min_score that is not finite.
+ * ORBFE_ERR_CAPACITY: K > ORBFE_KFDB_MAX_KEYFRAMES or nbow > ORBFE_KFDB_MAX_WORDS.  Nothing is written on an error.  K = 0 is an
+ * empty database: the zero record.  The call uploads the whole database: a caller with many queries keeps it on the device and
+ * uses the batch call. */
+int orbfe_detect_candidates(int mode, int scoring, const uint32_t* q_word, const double* q_value, int nbow, const int32_t* offsets,
+                            const uint32_t* word, const double* value, const uint8_t* active, int K, const int32_t* neigh,
+                            const int32_t* connected, int nconn, float min_score, float* scores, int32_t* candidates, int32_t* common,
+                            orbfe_kfdb_result* res, int device);
+
+/* nq queries against one resident database.  BowVectors in the layout orbfe_vocabulary_transform_batch_device writes: blocks of
+ * `capacity` entries of d_bow_word / d_bow_value per frame, d_nbow[f] valid (clamped to the block; capacity <=
+ * ORBFE_KFDB_MAX_WORDS).  Keyframe k of the database is frame d_db[k] (NULL: frame k), query q is frame d_query[q] of the same
+ * blocks; a negative frame index is an empty BowVector.  d_active[K] may be NULL; d_neigh as above (an entry >= K is skipped like
+ * a negative one).  Loop mode: query q's connected positions are d_conn[d_conn_offsets[q] .. d_conn_offsets[q + 1]) and its
+ * min_score is d_min_score[q], read ON THE DEVICE (orbfe_bow_min_score_batch_device in front of this call produces it).
+ * Relocalization mode reads none of the three (they may be NULL).
+ * d_scores[nq][K], in/out: row q is the score state query q sees and updates.  The queries of one call run side by side, each
+ * on its own row.  The reference's state is sequential -- a query sees what the queries before it left: a caller who wants
+ * exactly that runs ONE query a call, every call on the same row.
+ * Outputs: d_candidates[nq][K] (n_candidates entries of row q are written, the rest of the row is left alone), d_common[nq][K]
+ * (required: it is the call's scratch too; every entry is written), d_res[nq].  d_scratch: nq x K uint32 of scratch.
+ * A query frame that is itself in the database and not in its connected list finds itself, with every word in common: leaving
+ * it out (d_active, the connected list, or adding it afterwards as LoopClosing does) is the caller's duty.
+ * A query whose connected range decreases or holds a position outside [0, K) is skipped: status ORBFE_ERR_INVALID, every other
+ * field 0, its row of d_common zero, nothing else written.  Word order and finite values are the caller's duty here.
+ * K <= ORBFE_KFDB_MAX_KEYFRAMES (ORBFE_ERR_CAPACITY above; also for capacity > ORBFE_KFDB_MAX_WORDS and nq > 65535).  Two launches
+ * whatever nq is; asynchronous on `stream`, no host synchronisation, no scratch beyond the caller's buffers.
+ * Candidate positions become the next step's pair list as they are when d_db is NULL: d_pair2 = the candidates row, d_pair1 =
+ * the query frame repeated (orbfe_search_by_bow_batch_device, orbfe_sim3_solve_batch_device).  Those calls index their blocks by
+ * d_pair2 unchecked, and the entries of a row behind n_candidates are NOT written here: a caller who launches the next step over a
+ * fixed number of rows without reading n_candidates back MUST fill each row of d_candidates with a valid frame index (the query
+ * frame, say) before this call; the rows behind n_candidates then pair the query with that frame and are ignored afterwards. */
+int orbfe_detect_candidates_batch_device(int mode, int scoring, const uint32_t* d_bow_word, const double* d_bow_value, const int32_t* d_nbow,
+                                         int capacity, const int32_t* d_db, const uint8_t* d_active, int K, const int32_t* d_query, int nq,
+                                         const int32_t* d_neigh, const int32_t* d_conn_offsets, const int32_t* d_conn,
+                                         const float* d_min_score, float* d_scores, int32_t* d_candidates, int32_t* d_common,
+                                         uint32_t* d_scratch, orbfe_kfdb_result* d_res, void* stream);
+
+/* DetectLoop's minScore (src/LoopClosing.cc:232-246) for nq queries: d_min_score[q] = the least (float)score(query q, keyframe)
+ * over query q's connected positions, starting from 1.0f; arguments as above.  A position outside [0, K) and an inactive keyframe
+ * are skipped (SetBadFlag erases a keyframe from the database: the reference's isBad() skip).  Asynchronous on `stream`. */
+int orbfe_bow_min_score_batch_device(int scoring, const uint32_t* d_bow_word, const double* d_bow_value, const int32_t* d_nbow, int capacity,
+                                     const int32_t* d_db, const uint8_t* d_active, int K, const int32_t* d_query, int nq,
+                                     const int32_t* d_conn_offsets, const int32_t* d_conn, float* d_min_score, void* stream);
+
+/* The raw scores: scores[p] = (float)L1Scoring::score(frame pair1[p], frame pair2[p]).  Host call: nframes BowVectors in CSR
+ * (ORBFE_ERR_INVALID as in orbfe_detect_candidates, and for a pair outside [0, nframes)).  Device call: the block layout above,
+ * without the bound on capacity; frame indices are the caller's duty (a negative one is an empty vector: score -0.0f). */
+int orbfe_bow_score(int scoring, const int32_t* offsets, const uint32_t* word, const double* value, int nframes, const int32_t* pair1,
+                    const int32_t* pair2, int npairs, float* scores, int device);
+int orbfe_bow_score_batch_device(int scoring, const uint32_t* d_bow_word, const double* d_bow_value, const int32_t* d_nbow, int capacity,
+                                 const int32_t* d_pair1, const int32_t* d_pair2, int npairs, float* d_scores, void* stream);
+
 /* ------------------------------------------------------------------ Frame glue: undistortion -- */
 /* cv::undistortPoints(src, dst, K, distCoeffs, noArray(), K) (OpenCV 3.4: 5 fixed-point iterations in double) on n
  * (x, y) float pairs -- what Frame::UndistortKeyPoints (src/Frame.cc:357-387) and Frame::UndistortArucoCorners

@@ -63,6 +63,9 @@ SYMBOLS = [
     "orbfe_sim3_solve", "orbfe_sim3_solve_batch_device", "orbfe_sim3_inspect",
     # the Sim3 refinement of loop closing (csrc/sim3_optimizer.hip)
     "orbfe_optimize_sim3", "orbfe_optimize_sim3_batch_device",
+    # the candidate queries of KeyFrameDatabase and DBoW2's L1 score (csrc/keyframe_db.hip)
+    "orbfe_detect_candidates", "orbfe_detect_candidates_batch_device", "orbfe_bow_min_score_batch_device",
+    "orbfe_bow_score", "orbfe_bow_score_batch_device",
 ]
 
 _lib = None
@@ -209,6 +212,12 @@ def load():
         side = [vp, i32, vp, vp, vp, vp]
         L.orbfe_optimize_sim3.argtypes = side + side + [vp, vp, i32, f32, vp, vp, f32, i32, vp, vp, i32]
         L.orbfe_optimize_sim3_batch_device.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, sz, f32, i32, vp, vp, vp]
+    if hasattr(L, "orbfe_detect_candidates"):
+        L.orbfe_detect_candidates.argtypes = [i32, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, f32, vp, vp, vp, vp, i32]
+        L.orbfe_detect_candidates_batch_device.argtypes = [i32, i32, vp, vp, vp, i32, vp, vp, i32, vp, i32] + [vp] * 10
+        L.orbfe_bow_min_score_batch_device.argtypes = [i32, vp, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp]
+        L.orbfe_bow_score.argtypes = [i32, vp, vp, vp, i32, vp, vp, i32, vp, i32]
+        L.orbfe_bow_score_batch_device.argtypes = [i32, vp, vp, vp, i32, vp, vp, i32, vp, vp]
     if hasattr(L, "orbfe_initialize"):
         L.orbfe_initialize.argtypes = [vp, i32, vp, i32, vp, vp, f32, i32, vp, vp, vp, vp, i32]
         L.orbfe_initialize_inspect.argtypes = [vp, i32, vp, i32, vp, vp, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
@@ -948,6 +957,83 @@ def optimize_sim3_batch_device(d_kps_ptr, d_n_ptr, capacity, d_x3Dw_ptr, d_valid
                                                  d_pair2_ptr, int(npairs), d_match12_ptr, _p(_K4(K)), _p(sig), len(sig), d_sim12_ptr,
                                                  int(sim12_stride), float(th2), int(bool(fix_scale)), d_match12_out_ptr, d_res_ptr,
                                                  stream), "orbfe_optimize_sim3_batch_device")
+
+
+# ------------------------------------------------------------------------------- KeyFrameDatabase queries ----
+KFDB_LOOP, KFDB_RELOC, KFDB_NEIGHBOURS, KFDB_MAX_KEYFRAMES, KFDB_MAX_WORDS = 0, 1, 10, 8192, 4096
+L1_NORM = 0   # DBoW2::ScoringType
+KFDB_RESULT_DTYPE = np.dtype([("n_sharing", "<i4"), ("max_common_words", "<i4"), ("min_common_words", "<i4"), ("n_scored", "<i4"),
+                              ("n_kept", "<i4"), ("n_candidates", "<i4"), ("best_acc_score", "<f4"), ("min_score_to_retain", "<f4"),
+                              ("status", "<i4")])
+assert KFDB_RESULT_DTYPE.itemsize == 36
+
+
+def _bow_csr(offsets, word, value):
+    return np.ascontiguousarray(offsets, np.int32), np.ascontiguousarray(word, np.uint32), np.ascontiguousarray(value, np.float64)
+
+
+def detect_candidates(mode, q_word, q_value, offsets, word, value, neigh, scores, active=None, connected=None, min_score=0.0,
+                      scoring=L1_NORM, device=0):
+    """KeyFrameDatabase::DetectLoopCandidates (mode KFDB_LOOP) / DetectRelocalizationCandidates (KFDB_RELOC) on the GPU.  Query
+    BowVector q_word (ascending) / q_value; database of K keyframes in add order as CSR offsets / word / value, active (K flags or
+    None), neigh (K x 10 positions, negative = none); loop mode: connected positions and min_score.  scores: float32 array of K
+    entries, the mLoopScore / mRelocScore state, UPDATED IN PLACE.  Returns (candidates, common (K counts), record of
+    KFDB_RESULT_DTYPE)."""
+    L = load()
+    off, w, v = _bow_csr(offsets, word, value)
+    K = len(off) - 1
+    qw, qv = np.ascontiguousarray(q_word, np.uint32), np.ascontiguousarray(q_value, np.float64)
+    ng = np.ascontiguousarray(neigh, np.int32).reshape(K, KFDB_NEIGHBOURS)
+    act = None if active is None else np.ascontiguousarray(active, np.uint8)
+    conn = np.zeros(0, np.int32) if connected is None else np.ascontiguousarray(connected, np.int32)
+    if not (isinstance(scores, np.ndarray) and scores.dtype == np.float32 and scores.flags.c_contiguous and len(scores) == K):
+        raise ValueError("scores must be a contiguous float32 array of K entries")
+    cand, common, res = np.full(K, -1, np.int32), np.zeros(K, np.int32), np.zeros(1, KFDB_RESULT_DTYPE)
+    _check(L, L.orbfe_detect_candidates(int(mode), int(scoring), _ptr_or_none(qw), _ptr_or_none(qv), len(qw), _p(off), _ptr_or_none(w),
+                                        _ptr_or_none(v), None if act is None else _ptr_or_none(act), K, _ptr_or_none(ng),
+                                        _ptr_or_none(conn), len(conn), float(min_score), _ptr_or_none(scores), _ptr_or_none(cand),
+                                        _ptr_or_none(common), _p(res), device), "orbfe_detect_candidates")
+    return cand[:res[0]["n_candidates"]].copy(), common, res[0]
+
+
+def detect_candidates_batch_device(mode, d_bow_word_ptr, d_bow_value_ptr, d_nbow_ptr, capacity, d_db_ptr, d_active_ptr, K, d_query_ptr, nq,
+                                   d_neigh_ptr, d_conn_offsets_ptr, d_conn_ptr, d_min_score_ptr, d_scores_ptr, d_candidates_ptr,
+                                   d_common_ptr, d_scratch_ptr, d_res_ptr, stream=0, scoring=L1_NORM):
+    """orbfe_detect_candidates_batch_device: nq queries against K resident keyframes in the block layout of
+    orbfe_vocabulary_transform_batch_device (device pointers; see include/orbfe.h).  Asynchronous on `stream`."""
+    L = load()
+    _check(L, L.orbfe_detect_candidates_batch_device(int(mode), int(scoring), d_bow_word_ptr, d_bow_value_ptr, d_nbow_ptr, int(capacity),
+                                                     d_db_ptr, d_active_ptr, int(K), d_query_ptr, int(nq), d_neigh_ptr, d_conn_offsets_ptr,
+                                                     d_conn_ptr, d_min_score_ptr, d_scores_ptr, d_candidates_ptr, d_common_ptr,
+                                                     d_scratch_ptr, d_res_ptr, stream), "orbfe_detect_candidates_batch_device")
+
+
+def bow_min_score_batch_device(d_bow_word_ptr, d_bow_value_ptr, d_nbow_ptr, capacity, d_db_ptr, d_active_ptr, K, d_query_ptr, nq,
+                               d_conn_offsets_ptr, d_conn_ptr, d_min_score_ptr, stream=0, scoring=L1_NORM):
+    """orbfe_bow_min_score_batch_device: DetectLoop's minScore per query into d_min_score (device pointers)."""
+    L = load()
+    _check(L, L.orbfe_bow_min_score_batch_device(int(scoring), d_bow_word_ptr, d_bow_value_ptr, d_nbow_ptr, int(capacity), d_db_ptr,
+                                                 d_active_ptr, int(K), d_query_ptr, int(nq), d_conn_offsets_ptr, d_conn_ptr,
+                                                 d_min_score_ptr, stream), "orbfe_bow_min_score_batch_device")
+
+
+def bow_score(offsets, word, value, pair1, pair2, scoring=L1_NORM, device=0):
+    """(float)L1Scoring::score of the BowVector pairs (pair1[p], pair2[p]) of a CSR set, on the GPU."""
+    L = load()
+    off, w, v = _bow_csr(offsets, word, value)
+    p1, p2 = np.ascontiguousarray(pair1, np.int32), np.ascontiguousarray(pair2, np.int32)
+    out = np.zeros(len(p1), np.float32)
+    _check(L, L.orbfe_bow_score(int(scoring), _p(off), _ptr_or_none(w), _ptr_or_none(v), len(off) - 1, _ptr_or_none(p1), _ptr_or_none(p2),
+                                len(p1), _ptr_or_none(out), device), "orbfe_bow_score")
+    return out
+
+
+def bow_score_batch_device(d_bow_word_ptr, d_bow_value_ptr, d_nbow_ptr, capacity, d_pair1_ptr, d_pair2_ptr, npairs, d_scores_ptr, stream=0,
+                           scoring=L1_NORM):
+    """orbfe_bow_score_batch_device: the same on the block layout (device pointers)."""
+    L = load()
+    _check(L, L.orbfe_bow_score_batch_device(int(scoring), d_bow_word_ptr, d_bow_value_ptr, d_nbow_ptr, int(capacity), d_pair1_ptr,
+                                             d_pair2_ptr, int(npairs), d_scores_ptr, stream), "orbfe_bow_score_batch_device")
 
 
 # ------------------------------------------------------------------------------- pose optimization ----
