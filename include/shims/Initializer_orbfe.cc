@@ -11,43 +11,25 @@
 
 #include <cstdint>
 #include <cstdlib>
-#include <stdexcept>
 
 #include "Thirdparty/DBoW2/DUtils/Random.h"
-#include "orbfe.h"
+#include "orbfe_shim.h"
 
 using namespace std;
 
 namespace ORB_SLAM2
 {
 
+using namespace orbfe_shim;
+
 namespace
 {
-
-inline void check(int rc)
-{
-    if (rc != ORBFE_OK) throw std::runtime_error(orbfe_last_error());
-}
-
-inline const orbfe_keypoint* keys(const vector<cv::KeyPoint>& v)
-{
-    static_assert(sizeof(cv::KeyPoint) == sizeof(orbfe_keypoint), "cv::KeyPoint layout");
-    return reinterpret_cast<const orbfe_keypoint*>(v.data());
-}
 
 // vMatches12 as the library takes it: one entry per frame-1 keypoint (the reference indexes it by them, Initializer.cc:55-63)
 vector<int32_t> matches_of(const vector<int>& vMatches12, size_t n1)
 {
     vector<int32_t> m(n1, -1);
     for (size_t i = 0; i < n1 && i < vMatches12.size(); i++) m[i] = vMatches12[i];
-    return m;
-}
-
-cv::Mat mat32(int rows, int cols, const float* v)
-{
-    cv::Mat m(rows, cols, CV_32F);
-    for (int r = 0; r < rows; r++)
-        for (int c = 0; c < cols; c++) m.at<float>(r, c) = v[r * cols + c];
     return m;
 }
 
@@ -84,7 +66,8 @@ bool Initializer::Initialize(const Frame& CurrentFrame, const vector<int>& vMatc
     vector<int32_t> words((size_t)mMaxIterations * 8);
     for (size_t i = 0; i < words.size(); i++) words[i] = rand();
 
-    const float K4[4] = {mK.at<float>(0, 0), mK.at<float>(1, 1), mK.at<float>(0, 2), mK.at<float>(1, 2)};
+    float K4[4];
+    intrinsics(mK, K4);
     orbfe_init_result res;
     vector<float> p3d(n1 * 3 + 3);
     vector<uint8_t> tri(n1 + 1);
@@ -118,7 +101,8 @@ bool Initializer::InitializeUseAruco(const Frame& CurrentFrame, const vector<int
             for (int c = 0; c < 3; c++) poses[i * 12 + r * 3 + c] = R21[i].at<float>(r, c);
         for (int r = 0; r < 3; r++) poses[i * 12 + 9 + r] = t21[i].at<float>(r);
     }
-    const float K4[4] = {mK.at<float>(0, 0), mK.at<float>(1, 1), mK.at<float>(0, 2), mK.at<float>(1, 2)};
+    float K4[4];
+    intrinsics(mK, K4);
     orbfe_init_result res;
     vector<float> p3d(n1 * 3 + 3);
     vector<uint8_t> tri(n1 + 1);

@@ -16,7 +16,7 @@
 
 #include "cameraparameters.h"
 #include "marker.h"
-#include "orbfe.h"
+#include "orbfe_shim.h"
 
 namespace aruco
 {
@@ -90,9 +90,9 @@ public:
     void setDictionary(std::string dict_type, float error_correction_rate = 0)
     {
         if (!h_) h_ = orbfe_aruco_create(dict_type.c_str(), /*device*/ 0);
-        else if (orbfe_aruco_set_dictionary(h_, dict_type.c_str()) != ORBFE_OK) throw std::runtime_error(orbfe_last_error());
+        else orbfe_shim::check(orbfe_aruco_set_dictionary(h_, dict_type.c_str()));
         if (!h_) throw std::runtime_error(orbfe_last_error());
-        if (orbfe_aruco_set_error_correction_rate(h_, error_correction_rate) != ORBFE_OK) throw std::runtime_error(orbfe_last_error());
+        orbfe_shim::check(orbfe_aruco_set_error_correction_rate(h_, error_correction_rate));
         _params.dictionary = dict_type;
         _params.error_correction_rate = error_correction_rate;
     }
@@ -148,7 +148,8 @@ public:
             cv::Mat K32, D32;
             camMatrix.convertTo(K32, CV_32F);
             distCoeff.convertTo(D32, CV_32F);
-            const float K4[4] = {K32.at<float>(0, 0), K32.at<float>(1, 1), K32.at<float>(0, 2), K32.at<float>(1, 2)};
+            float K4[4];
+            orbfe_shim::intrinsics(K32, K4);
             poses.resize(cap);
             if ((bgr ? orbfe_aruco_detect_poses_bgr : orbfe_aruco_detect_poses)(h_, input.data, input.rows, input.cols, input.step, m.data(), poses.data(), cap, &n, markerSizeMeters,
                                          K4, D32.empty() ? nullptr : D32.ptr<float>(), (int)D32.total()) != ORBFE_OK)

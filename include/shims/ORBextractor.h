@@ -14,7 +14,7 @@
 
 #include <opencv2/core/core.hpp>
 
-#include "orbfe.h"
+#include "orbfe_shim.h"
 
 namespace ORB_SLAM2
 {
@@ -41,13 +41,10 @@ public:
         if (_image.empty()) return; // :1046: outputs untouched
         cv::Mat image = _image.getMat();
         assert(image.type() == CV_8UC1); // :1050
-        static_assert(sizeof(cv::KeyPoint) == sizeof(orbfe_keypoint), "cv::KeyPoint is 28 bytes: pt, size, angle, response, octave, class_id");
         _keypoints.resize(cap_);
         std::vector<unsigned char> desc((size_t)cap_ * 32);
         int32_t n = 0;
-        const int rc = orbfe_extract(h_, image.data, image.rows, image.cols, image.step, reinterpret_cast<orbfe_keypoint*>(_keypoints.data()),
-                                     desc.data(), cap_, &n);
-        if (rc != ORBFE_OK) throw std::runtime_error(orbfe_last_error());
+        orbfe_shim::check(orbfe_extract(h_, image.data, image.rows, image.cols, image.step, orbfe_shim::keys(_keypoints), desc.data(), cap_, &n));
         _keypoints.resize(n);
         if (n == 0) { _descriptors.release(); return; } // :1064-1065
         _descriptors.create(n, 32, CV_8U);              // :1068
@@ -57,9 +54,9 @@ public:
             mvImagePyramid.resize(nlevels_);
             for (int l = 0; l < nlevels_; l++) {
                 int w = 0, hgt = 0;
-                if (orbfe_extractor_debug_level_size(h_, l, &w, &hgt) != ORBFE_OK) throw std::runtime_error(orbfe_last_error());
+                orbfe_shim::check(orbfe_extractor_debug_level_size(h_, l, &w, &hgt));
                 mvImagePyramid[l].create(hgt, w, CV_8UC1);
-                if (orbfe_extractor_debug_level_image(h_, 0, l, 0, mvImagePyramid[l].data) != ORBFE_OK) throw std::runtime_error(orbfe_last_error());
+                orbfe_shim::check(orbfe_extractor_debug_level_image(h_, 0, l, 0, mvImagePyramid[l].data));
             }
         }
     }

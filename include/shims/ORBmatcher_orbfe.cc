@@ -16,9 +16,8 @@
 #include "ORBmatcher.h"
 
 #include <climits>
-#include <stdexcept>
 
-#include "orbfe.h"
+#include "orbfe_shim.h"
 
 using namespace std;
 
@@ -29,19 +28,10 @@ const int ORBmatcher::TH_HIGH = 100;
 const int ORBmatcher::TH_LOW = 50;
 const int ORBmatcher::HISTO_LENGTH = 30;
 
+using namespace orbfe_shim;
+
 namespace
 {
-
-inline void check(int rc)
-{
-    if (rc != ORBFE_OK) throw std::runtime_error(orbfe_last_error());
-}
-
-template <class FrameLike> inline const orbfe_keypoint* keys(const FrameLike& F)
-{
-    static_assert(sizeof(cv::KeyPoint) == sizeof(orbfe_keypoint), "cv::KeyPoint layout");
-    return reinterpret_cast<const orbfe_keypoint*>(F.mvKeysUn.data());
-}
 
 // {mnMinX, mnMinY, mnMaxX, mnMaxY} (Frame::ComputeImageBounds, Frame.cc:418-451); cols / rows only size internal tables
 template <class FrameLike> struct Bounds
@@ -68,22 +58,15 @@ struct MapPointArrays
     }
     void set(size_t i, MapPoint* pMP)
     {
-        const cv::Mat p = pMP->GetWorldPos(), nrm = pMP->GetNormal(), d = pMP->GetDescriptor();
-        for (int k = 0; k < 3; k++) { p3Dw[3 * i + k] = p.at<float>(k); normal[3 * i + k] = nrm.at<float>(k); }
+        point3(pMP->GetWorldPos(), &p3Dw[3 * i]);
+        point3(pMP->GetNormal(), &normal[3 * i]);
+        const cv::Mat d = pMP->GetDescriptor();
         min_dist[i] = pMP->GetMinDistance();
         max_dist[i] = pMP->GetMaxDistance();
         std::copy(d.data, d.data + 32, desc.begin() + 32 * i);
         valid[i] = 1;
     }
 };
-
-inline void pose34(const cv::Mat& R, const cv::Mat& t, float T[12])
-{
-    for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) T[4 * r + c] = R.at<float>(r, c);
-        T[4 * r + 3] = t.at<float>(r);
-    }
-}
 
 // DBoW2::FeatureVector (std::map<NodeId, std::vector<unsigned>>) as the flat arrays of orbfe_search_by_bow
 struct FlatFeatVec
@@ -138,7 +121,7 @@ int ORBmatcher::SearchByProjection(Frame& F, const vector<MapPoint*>& vpMapPoint
     vector<int32_t> match(q.size(), -1);
     int32_t n = 0;
     const Bounds<Frame> B(F);
-    check(orbfe_search_by_projection(keys(F), F.mDescriptors.data, F.N, B.cols, B.rows, B.b, q.data(), qd.data(), (int)q.size(), taken.data(),
+    check(orbfe_search_by_projection(keys(F.mvKeysUn), F.mDescriptors.data, F.N, B.cols, B.rows, B.b, q.data(), qd.data(), (int)q.size(), taken.data(),
                                      observed.data(), /*mode*/ 1, TH_HIGH, mfNNratio, NULL, NULL, NULL, NULL, NULL, match.data(), &n, 0));
     for (size_t k = 0; k < match.size(); k++)
         if (match[k] >= 0) F.mvpMapPoints[match[k]] = who[k]; // :125, in query order: a later assignment overwrites
@@ -157,8 +140,8 @@ int ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, 
         if (!pMP || LastFrame.mvbOutlier[i]) continue; // :1358-1362
         valid[i] = 1;
         observed[i] = pMP->Observations() > 0;
-        const cv::Mat p = pMP->GetWorldPos(), d = pMP->GetDescriptor();
-        for (int k = 0; k < 3; k++) x3Dw[3 * i + k] = p.at<float>(k);
+        point3(pMP->GetWorldPos(), &x3Dw[3 * i]);
+        const cv::Mat d = pMP->GetDescriptor();
         std::copy(d.data, d.data + 32, desc.begin() + (size_t)32 * i);
     }
     vector<uint8_t> taken(CurrentFrame.N, 0);
@@ -170,8 +153,8 @@ int ORBmatcher::SearchByProjection(Frame& CurrentFrame, const Frame& LastFrame, 
     vector<int32_t> match(CurrentFrame.N, -1);
     int32_t n = 0;
     const Bounds<Frame> B(CurrentFrame);
-    check(orbfe_search_by_projection_last_frame(keys(CurrentFrame), CurrentFrame.mDescriptors.data, CurrentFrame.N, taken.data(), B.cols, B.rows,
-                                                B.b, keys(LastFrame), NL, valid.data(), x3Dw.data(), desc.data(), observed.data(), T, K4,
+    check(orbfe_search_by_projection_last_frame(keys(CurrentFrame.mvKeysUn), CurrentFrame.mDescriptors.data, CurrentFrame.N, taken.data(), B.cols, B.rows,
+                                                B.b, keys(LastFrame.mvKeysUn), NL, valid.data(), x3Dw.data(), desc.data(), observed.data(), T, K4,
                                                 CurrentFrame.mvScaleFactors.data(), CurrentFrame.mnScaleLevels, th, TH_HIGH,
                                                 mbCheckOrientation, match.data(), &n, 0));
     for (int i2 = 0; i2 < CurrentFrame.N; i2++)
@@ -204,7 +187,7 @@ int ORBmatcher::SearchByProjection(Frame& CurrentFrame, KeyFrame* pKF, const set
     vector<int32_t> match(CurrentFrame.N, -1);
     int32_t n = 0;
     const Bounds<Frame> B(CurrentFrame);
-    check(orbfe_search_by_projection_keyframe(keys(CurrentFrame), CurrentFrame.mDescriptors.data, CurrentFrame.N, taken.data(), B.cols, B.rows,
+    check(orbfe_search_by_projection_keyframe(keys(CurrentFrame.mvKeysUn), CurrentFrame.mDescriptors.data, CurrentFrame.N, taken.data(), B.cols, B.rows,
                                               B.b, n_kf, angle.data(), A.valid.data(), A.p3Dw.data(), A.min_dist.data(), A.max_dist.data(),
                                               A.desc.data(), T, O, K4, CurrentFrame.mvScaleFactors.data(), CurrentFrame.mnScaleLevels,
                                               CurrentFrame.mfLogScaleFactor, th, ORBdist, mbCheckOrientation, match.data(), &n, 0));
@@ -238,7 +221,7 @@ int ORBmatcher::SearchByProjection(KeyFrame* pKF, cv::Mat Scw, const vector<MapP
     vector<int32_t> match(pKF->N, -1);
     int32_t n = 0;
     const Bounds<KeyFrame> B(*pKF);
-    check(orbfe_search_by_projection_sim3(keys(*pKF), pKF->mDescriptors.data, pKF->N, B.cols, B.rows, B.b, matched.data(), A.p3Dw.data(),
+    check(orbfe_search_by_projection_sim3(keys(pKF->mvKeysUn), pKF->mDescriptors.data, pKF->N, B.cols, B.rows, B.b, matched.data(), A.p3Dw.data(),
                                           A.valid.data(), A.min_dist.data(), A.max_dist.data(), A.normal.data(), A.desc.data(), nmp, T, O, K4,
                                           pKF->mvScaleFactors.data(), pKF->mnScaleLevels, pKF->mfLogScaleFactor, th, match.data(), &n, 0));
     for (int i = 0; i < pKF->N; i++)
@@ -257,8 +240,8 @@ int ORBmatcher::SearchByBoW(KeyFrame* pKF, Frame& F, vector<MapPoint*>& vpMapPoi
     vector<int32_t> m12(pKF->N, -1), m21(F.N, -1);
     int32_t n = 0;
     // this fork's histogram factor HISTO_LENGTH / 360.0f (:174); accept bestDist1 <= TH_LOW (:233)
-    check(orbfe_search_by_bow(keys(*pKF), pKF->mDescriptors.data, valid1.data(), pKF->N, fk.node.data(), fk.offset.data(), fk.feature.data(),
-                              (int)fk.node.size(), keys(F), F.mDescriptors.data, NULL, F.N, ff.node.data(), ff.offset.data(), ff.feature.data(),
+    check(orbfe_search_by_bow(keys(pKF->mvKeysUn), pKF->mDescriptors.data, valid1.data(), pKF->N, fk.node.data(), fk.offset.data(), fk.feature.data(),
+                              (int)fk.node.size(), keys(F.mvKeysUn), F.mDescriptors.data, NULL, F.N, ff.node.data(), ff.offset.data(), ff.feature.data(),
                               (int)ff.node.size(), mfNNratio, mbCheckOrientation, TH_LOW, HISTO_LENGTH / 360.0f, m12.data(), m21.data(), &n, 0));
     for (int i2 = 0; i2 < F.N; i2++)
         if (m21[i2] >= 0) vpMapPointMatches[i2] = vpMapPointsKF[m21[i2]]; // :239
@@ -278,8 +261,8 @@ int ORBmatcher::SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& v
     vector<int32_t> m12(pKF1->N, -1), m21(pKF2->N, -1);
     int32_t n = 0;
     // factor 1.0f / HISTO_LENGTH (:546); accept bestDist1 < TH_LOW (:602)
-    check(orbfe_search_by_bow(keys(*pKF1), pKF1->mDescriptors.data, valid1.data(), pKF1->N, f1.node.data(), f1.offset.data(), f1.feature.data(),
-                              (int)f1.node.size(), keys(*pKF2), pKF2->mDescriptors.data, valid2.data(), pKF2->N, f2.node.data(),
+    check(orbfe_search_by_bow(keys(pKF1->mvKeysUn), pKF1->mDescriptors.data, valid1.data(), pKF1->N, f1.node.data(), f1.offset.data(), f1.feature.data(),
+                              (int)f1.node.size(), keys(pKF2->mvKeysUn), pKF2->mDescriptors.data, valid2.data(), pKF2->N, f2.node.data(),
                               f2.offset.data(), f2.feature.data(), (int)f2.node.size(), mfNNratio, mbCheckOrientation, TH_LOW - 1,
                               1.0f / HISTO_LENGTH, m12.data(), m21.data(), &n, 0));
     for (int i1 = 0; i1 < pKF1->N; i1++)
@@ -294,7 +277,7 @@ int ORBmatcher::SearchForInitialization(Frame& F1, Frame& F2, vector<cv::Point2f
     static_assert(sizeof(cv::Point2f) == 8, "cv::Point2f is two floats");
     int32_t n = 0;
     const Bounds<Frame> B(F2);
-    check(orbfe_search_for_initialization(keys(F1), F1.mDescriptors.data, F1.N, keys(F2), F2.mDescriptors.data, F2.N, B.cols, B.rows, B.b,
+    check(orbfe_search_for_initialization(keys(F1.mvKeysUn), F1.mDescriptors.data, F1.N, keys(F2.mvKeysUn), F2.mDescriptors.data, F2.N, B.cols, B.rows, B.b,
                                           reinterpret_cast<float*>(vbPrevMatched.data()), vnMatches12.data(), windowSize, mfNNratio,
                                           mbCheckOrientation, &n, 0));
     return n;
@@ -322,8 +305,8 @@ int ORBmatcher::SearchForTriangulation(KeyFrame* pKF1, KeyFrame* pKF2, cv::Mat F
         for (int c = 0; c < 3; c++) F[3 * r + c] = F12.at<float>(r, c);
     vector<int32_t> m12(pKF1->N, -1);
     int32_t n = 0;
-    check(orbfe_search_for_triangulation(keys(*pKF1), pKF1->mDescriptors.data, has1.data(), pKF1->N, f1.node.data(), f1.offset.data(),
-                                         f1.feature.data(), (int)f1.node.size(), keys(*pKF2), pKF2->mDescriptors.data, has2.data(), pKF2->N,
+    check(orbfe_search_for_triangulation(keys(pKF1->mvKeysUn), pKF1->mDescriptors.data, has1.data(), pKF1->N, f1.node.data(), f1.offset.data(),
+                                         f1.feature.data(), (int)f1.node.size(), keys(pKF2->mvKeysUn), pKF2->mDescriptors.data, has2.data(), pKF2->N,
                                          f2.node.data(), f2.offset.data(), f2.feature.data(), (int)f2.node.size(), F, ex, ey,
                                          pKF2->mvScaleFactors.data(), pKF2->mvLevelSigma2.data(), pKF2->mnScaleLevels, mbCheckOrientation,
                                          m12.data(), &n, 0));
@@ -368,7 +351,7 @@ int ORBmatcher::SearchBySim3(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& 
     vector<int32_t> m12(N1, -1);
     int32_t n = 0;
     const Bounds<KeyFrame> B(*pKF1);
-    check(orbfe_search_by_sim3(keys(*pKF1), pKF1->mDescriptors.data, N1, keys(*pKF2), pKF2->mDescriptors.data, N2, B.cols, B.rows, B.b,
+    check(orbfe_search_by_sim3(keys(pKF1->mvKeysUn), pKF1->mDescriptors.data, N1, keys(pKF2->mvKeysUn), pKF2->mDescriptors.data, N2, B.cols, B.rows, B.b,
                                A1.p3Dw.data(), A1.valid.data(), A1.min_dist.data(), A1.max_dist.data(), A1.desc.data(), A2.p3Dw.data(),
                                A2.valid.data(), A2.min_dist.data(), A2.max_dist.data(), A2.desc.data(), T1, T2, S12, S21, K4,
                                pKF1->mvScaleFactors.data(), pKF1->mnScaleLevels, pKF1->mfLogScaleFactor, th, TH_HIGH, m12.data(), &n, 0));
@@ -394,7 +377,7 @@ int ORBmatcher::Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, const 
     const float K4[4] = {pKF->fx, pKF->fy, pKF->cx, pKF->cy};
     vector<int32_t> bestIdx(nMPs, -1), bestDist(nMPs, 256);
     const Bounds<KeyFrame> B(*pKF);
-    check(orbfe_fuse_search(keys(*pKF), pKF->mDescriptors.data, pKF->N, B.cols, B.rows, B.b, A.p3Dw.data(), A.valid.data(), A.min_dist.data(),
+    check(orbfe_fuse_search(keys(pKF->mvKeysUn), pKF->mDescriptors.data, pKF->N, B.cols, B.rows, B.b, A.p3Dw.data(), A.valid.data(), A.min_dist.data(),
                             A.max_dist.data(), A.normal.data(), A.desc.data(), nMPs, T, O, K4, pKF->mvScaleFactors.data(),
                             pKF->mvInvLevelSigma2.data(), pKF->mnScaleLevels, pKF->mfLogScaleFactor, th, 5.99, bestIdx.data(), bestDist.data(), 0));
     int nFused = 0;
@@ -439,7 +422,7 @@ int ORBmatcher::Fuse(KeyFrame* pKF, cv::Mat Scw, const vector<MapPoint*>& vpPoin
     const float K4[4] = {pKF->fx, pKF->fy, pKF->cx, pKF->cy};
     vector<int32_t> bestIdx(nPoints, -1), bestDist(nPoints, 256);
     const Bounds<KeyFrame> B(*pKF);
-    check(orbfe_fuse_search(keys(*pKF), pKF->mDescriptors.data, pKF->N, B.cols, B.rows, B.b, A.p3Dw.data(), A.valid.data(), A.min_dist.data(),
+    check(orbfe_fuse_search(keys(pKF->mvKeysUn), pKF->mDescriptors.data, pKF->N, B.cols, B.rows, B.b, A.p3Dw.data(), A.valid.data(), A.min_dist.data(),
                             A.max_dist.data(), A.normal.data(), A.desc.data(), nPoints, T, O, K4, pKF->mvScaleFactors.data(),
                             pKF->mvInvLevelSigma2.data(), pKF->mnScaleLevels, pKF->mfLogScaleFactor, th, 0.0, bestIdx.data(), bestDist.data(), 0));
     int nFused = 0;

@@ -20,12 +20,14 @@
 #include "Frame.h"
 #include "MapAruco.h"
 #include "MapPoint.h"
-#include "orbfe.h"
+#include "orbfe_shim.h"
 
 using namespace std;
 
 namespace ORB_SLAM2
 {
+
+using namespace orbfe_shim;
 
 namespace
 {
@@ -34,7 +36,6 @@ const float kMarkerInformation = 25.f;   // PoseOptimizationByAruco's wei
 
 int pose_optimization(Frame* pFrame, bool markers, const char* name)
 {
-    static_assert(sizeof(cv::KeyPoint) == sizeof(orbfe_keypoint), "cv::KeyPoint layout");
     const int N = pFrame->N;
     vector<uint8_t> has(N, 0), outlier(N, 0);
     vector<float> x3Dw(3 * (size_t)N, 0.f);
@@ -45,8 +46,7 @@ int pose_optimization(Frame* pFrame, bool markers, const char* name)
             if (!markers) throw std::runtime_error(string(name) + ": stereo observations are not supported");
             continue;
         }
-        const cv::Mat Xw = pMP->GetWorldPos();
-        for (int k = 0; k < 3; k++) x3Dw[3 * i + k] = Xw.at<float>(k);
+        point3(pMP->GetWorldPos(), &x3Dw[3 * (size_t)i]);
         has[i] = 1;
         outlier[i] = pFrame->mvbOutlier[i] ? 1 : 0;
     }
@@ -76,10 +76,9 @@ int pose_optimization(Frame* pFrame, bool markers, const char* name)
         for (int c = 0; c < 4; c++) Tin[r * 4 + c] = pFrame->mTcw.at<float>(r, c);
     const float K4[4] = {pFrame->fx, pFrame->fy, pFrame->cx, pFrame->cy};
     orbfe_pose_result res;
-    const int rc = orbfe_pose_optimization(reinterpret_cast<const orbfe_keypoint*>(pFrame->mvKeysUn.data()), N, has.data(), x3Dw.data(),
-                                           pFrame->mvInvLevelSigma2.data(), (int)pFrame->mvInvLevelSigma2.size(), K4, mk.data(),
-                                           (int)mk.size(), kMarkerInformation, Tin, Tout, outlier.data(), nullptr, &res, 0);
-    if (rc != ORBFE_OK) throw std::runtime_error(orbfe_last_error());
+    check(orbfe_pose_optimization(keys(pFrame->mvKeysUn), N, has.data(), x3Dw.data(), pFrame->mvInvLevelSigma2.data(),
+                                  (int)pFrame->mvInvLevelSigma2.size(), K4, mk.data(), (int)mk.size(), kMarkerInformation, Tin, Tout,
+                                  outlier.data(), nullptr, &res, 0));
     for (int i = 0; i < N; i++)
         if (has[i]) pFrame->mvbOutlier[i] = outlier[i] != 0;
     if (res.n_initial < 3) return 0;

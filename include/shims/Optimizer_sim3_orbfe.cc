@@ -20,33 +20,21 @@
 
 #include "KeyFrame.h"
 #include "MapPoint.h"
-#include "orbfe.h"
+#include "orbfe_shim.h"
 
 using namespace std;
 
 namespace ORB_SLAM2
 {
 
+using namespace orbfe_shim;
+
 namespace
 {
 
-void pose_of(KeyFrame* pKF, float* Tcw, float* K4)
-{
-    const cv::Mat R = pKF->GetRotation(), t = pKF->GetTranslation();
-    for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) Tcw[r * 4 + c] = R.at<float>(r, c);
-        Tcw[r * 4 + 3] = t.at<float>(r);
-    }
-    K4[0] = pKF->mK.at<float>(0, 0);
-    K4[1] = pKF->mK.at<float>(1, 1);
-    K4[2] = pKF->mK.at<float>(0, 2);
-    K4[3] = pKF->mK.at<float>(1, 2);
-}
-
 void put_point(MapPoint* pMP, size_t i, vector<float>& x3Dw, vector<uint8_t>& valid)
 {
-    const cv::Mat Xw = pMP->GetWorldPos();
-    for (int k = 0; k < 3; k++) x3Dw[3 * i + k] = Xw.at<float>(k);
+    point3(pMP->GetWorldPos(), &x3Dw[3 * i]);
     valid[i] = pMP->isBad() ? 0 : 1;
 }
 
@@ -55,7 +43,6 @@ void put_point(MapPoint* pMP, size_t i, vector<float>& x3Dw, vector<uint8_t>& va
 int Optimizer::OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& vpMatches1, g2o::Sim3& g2oS12, const float th2,
                             const bool bFixScale)
 {
-    static_assert(sizeof(cv::KeyPoint) == sizeof(orbfe_keypoint), "cv::KeyPoint layout");
     const size_t N = vpMatches1.size(), n2 = pKF2->mvKeysUn.size();
     const vector<MapPoint*> vpMapPoints1 = pKF1->GetMapPointMatches();
     if (N > pKF1->mvKeysUn.size() || N > vpMapPoints1.size()) throw std::runtime_error("Optimizer::OptimizeSim3: more matches than features");
@@ -72,19 +59,19 @@ int Optimizer::OptimizeSim3(KeyFrame* pKF1, KeyFrame* pKF2, vector<MapPoint*>& v
         m12[i] = i2;
     }
     float T1[12], T2[12], K1[4], K2[4], R12[9], t12[3];
-    pose_of(pKF1, T1, K1);
-    pose_of(pKF2, T2, K2);
+    pose34(pKF1->GetRotation(), pKF1->GetTranslation(), T1);
+    intrinsics(pKF1->mK, K1);
+    pose34(pKF2->GetRotation(), pKF2->GetTranslation(), T2);
+    intrinsics(pKF2->mK, K2);
     const Eigen::Matrix3d R = g2oS12.rotation().toRotationMatrix();
     for (int r = 0; r < 3; r++) {
         for (int c = 0; c < 3; c++) R12[3 * r + c] = (float)R(r, c);
         t12[r] = (float)g2oS12.translation()[r];
     }
     orbfe_sim3_opt_result res;
-    const int rc = orbfe_optimize_sim3(reinterpret_cast<const orbfe_keypoint*>(pKF1->mvKeysUn.data()), (int)N, x1.data(), v1.data(), T1, K1,
-                                       reinterpret_cast<const orbfe_keypoint*>(pKF2->mvKeysUn.data()), (int)n2, x2.data(), v2.data(), T2, K2,
-                                       m12.data(), pKF1->mvInvLevelSigma2.data(), (int)pKF1->mvInvLevelSigma2.size(),
-                                       (float)g2oS12.scale(), R12, t12, th2, bFixScale ? 1 : 0, out.data(), &res, 0);
-    if (rc != ORBFE_OK) throw std::runtime_error(orbfe_last_error());
+    check(orbfe_optimize_sim3(keys(pKF1->mvKeysUn), (int)N, x1.data(), v1.data(), T1, K1, keys(pKF2->mvKeysUn), (int)n2, x2.data(), v2.data(),
+                              T2, K2, m12.data(), pKF1->mvInvLevelSigma2.data(), (int)pKF1->mvInvLevelSigma2.size(), (float)g2oS12.scale(),
+                              R12, t12, th2, bFixScale ? 1 : 0, out.data(), &res, 0));
     for (size_t i = 0; i < N; i++)
         if (m12[i] >= 0 && out[i] < 0) vpMatches1[i] = static_cast<MapPoint*>(NULL);
     if (res.more_iterations == 0) return 0;   // the early return: g2oS12 stays

@@ -21,41 +21,25 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
-#include <stdexcept>
 
 #include "KeyFrame.h"
-#include "orbfe.h"
+#include "orbfe_shim.h"
 
 using namespace std;
 
 namespace ORB_SLAM2
 {
 
+using namespace orbfe_shim;
+
 namespace
 {
-
-inline void check(int rc)
-{
-    if (rc != ORBFE_OK) throw std::runtime_error(orbfe_last_error());
-}
-
-cv::Mat mat32(int rows, int cols, const float* v)
-{
-    cv::Mat m(rows, cols, CV_32F);
-    for (int r = 0; r < rows; r++)
-        for (int c = 0; c < cols; c++) m.at<float>(r, c) = v[r * cols + c];
-    return m;
-}
 
 // [R | t] of a keyframe, 3 x 4
 cv::Mat pose_of(KeyFrame* pKF)
 {
-    const cv::Mat R = pKF->GetRotation(), t = pKF->GetTranslation();
     cv::Mat T(3, 4, CV_32F);
-    for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) T.at<float>(r, c) = R.at<float>(r, c);
-        T.at<float>(r, 3) = t.at<float>(r);
-    }
+    pose34(pKF->GetRotation(), pKF->GetTranslation(), T.ptr<float>());
     return T;
 }
 
@@ -66,7 +50,6 @@ enum { X3DW = 0, POSE = 1, KEYS = 2 };   // the slots of mvX3Dc1 / mvX3Dc2
 Sim3Solver::Sim3Solver(KeyFrame* pKF1, KeyFrame* pKF2, const vector<MapPoint*>& vpMatched12, const bool bFixScale)
     : mnIterations(0), mnBestInliers(0), mbFixScale(bFixScale)
 {
-    static_assert(sizeof(cv::KeyPoint) == sizeof(orbfe_keypoint), "cv::KeyPoint layout");
     mpKF1 = pKF1;
     mpKF2 = pKF2;
     if (pKF1->mvLevelSigma2 != pKF2->mvLevelSigma2) throw std::runtime_error("Sim3Solver (orbfe): the keyframes' level tables differ");
@@ -103,11 +86,8 @@ Sim3Solver::Sim3Solver(KeyFrame* pKF1, KeyFrame* pKF2, const vector<MapPoint*>& 
         if (indexKF1 < 0 || indexKF2 < 0) continue;
         memcpy(mvX3Dc1[KEYS].ptr(i1), &pKF1->mvKeysUn[indexKF1], sizeof(orbfe_keypoint));
         memcpy(mvX3Dc2[KEYS].ptr(i1), &pKF2->mvKeysUn[indexKF2], sizeof(orbfe_keypoint));
-        const cv::Mat X1 = pMP1->GetWorldPos(), X2 = pMP2->GetWorldPos();
-        for (int k = 0; k < 3; k++) {
-            mvX3Dc1[X3DW].at<float>(i1, k) = X1.at<float>(k);
-            mvX3Dc2[X3DW].at<float>(i1, k) = X2.at<float>(k);
-        }
+        point3(pMP1->GetWorldPos(), mvX3Dc1[X3DW].ptr<float>(i1));
+        point3(pMP2->GetWorldPos(), mvX3Dc2[X3DW].ptr<float>(i1));
         match12[i1] = i1;
         mvpMapPoints1.push_back(pMP1);
         mvpMapPoints2.push_back(pMP2);
@@ -156,8 +136,9 @@ cv::Mat Sim3Solver::iterate(int nIterations, bool& bNoMore, vector<bool>& vbInli
     if (N >= 3)   // (fewer: the library reads no word and reports no_more)
         for (size_t i = 0; i < words.size(); i++) words[i] = rand();
 
-    const float K1[4] = {mK1.at<float>(0, 0), mK1.at<float>(1, 1), mK1.at<float>(0, 2), mK1.at<float>(1, 2)};
-    const float K2[4] = {mK2.at<float>(0, 0), mK2.at<float>(1, 1), mK2.at<float>(0, 2), mK2.at<float>(1, 2)};
+    float K1[4], K2[4];
+    intrinsics(mK1, K1);
+    intrinsics(mK2, K2);
     const vector<float>& ls2 = mpKF1->mvLevelSigma2;
     orbfe_sim3_result res;
     vector<uint8_t> inl((size_t)mN1 + 1);

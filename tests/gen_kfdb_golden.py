@@ -1,9 +1,9 @@
 """Writes tests/golden/kfdb_cases.npz: what the REFERENCE's own KeyFrameDatabase returns on every case of tests/kfdb_cases.py and on the
 script and the culling program of tests/kfdb_shim_driver.cpp.  Run by hand where the reference tree exists (REF, default /root/reference); no test calls it.
 
-The reference's src/KeyFrameDatabase.cc, Thirdparty/DBoW2/DBoW2/ScoringObject.cpp and BowVector.cpp are compiled where they lie,
-unchanged, into a temporary directory, against the mock headers of tests/mock_kfdb/ (KeyFrame.h, Frame.h, ORBVocabulary.h,
-KeyFrameDatabase.h) and with tests/kfdb_shim_driver.cpp as the program.  The mock KeyFrame starts its two scores from the case's
+The reference's src/KeyFrameDatabase.cc, Thirdparty/DBoW2/DBoW2/ScoringObject.cpp, BowVector.cpp and FeatureVector.cpp are compiled where they lie,
+unchanged, into a temporary directory, against the mock headers of tests/mock_orbslam/ (KeyFrame.h, Frame.h, ORBVocabulary.h,
+KeyFrameDatabase.h; the reference's real DBoW2 comes before the tree's stand-ins dbow2/) and with tests/kfdb_shim_driver.cpp as the program.  The mock KeyFrame starts its two scores from the case's
 state.  What the reference shows from outside is recorded as it is: the candidates, every keyframe's score after the call, and
 every keyframe's word count where its query field says it entered the sharing list.  Of the record, n_sharing, max / min common
 words, n_scored and n_candidates follow from those; n_kept, best_acc_score and min_score_to_retain are locals of the reference that
@@ -26,10 +26,11 @@ REF = os.environ.get("REF", "/root/reference")
 def build_reference_driver(tmp):
     dbow2 = os.path.join(REF, "Thirdparty", "DBoW2", "DBoW2")
     exe = os.path.join(tmp, "kfdb_reference_driver")
-    common = ["g++", "-O3", "-std=c++11", "-DKFDB_REFERENCE", "-I", REF, "-I", os.path.join(HERE, "mock_kfdb")]
+    common = ["g++", "-O3", "-std=c++11", "-DKFDB_REFERENCE", "-I", REF, "-I", os.path.join(HERE, "mock_orbslam")]
     objs = []
-    for src, extra in ((os.path.join(HERE, "kfdb_shim_driver.cpp"), []), (os.path.join(REF, "src", "KeyFrameDatabase.cc"), []),
-                       (os.path.join(dbow2, "BowVector.cpp"), []),
+    for src, extra in ((os.path.join(HERE, "kfdb_shim_driver.cpp"), []), (os.path.join(HERE, "mock_orbslam", "Frame_statics.cc"), []),
+                       (os.path.join(REF, "src", "KeyFrameDatabase.cc"), []),
+                       (os.path.join(dbow2, "BowVector.cpp"), []), (os.path.join(dbow2, "FeatureVector.cpp"), []),   # the mock KeyFrame holds both
                        (os.path.join(dbow2, "ScoringObject.cpp"),
                         ["-D__D_T_TEMPLATED_VOCABULARY__", "-include", "cmath", "-include", os.path.join(dbow2, "ScoringObject.h")])):
         obj = os.path.join(tmp, os.path.basename(src) + ".o")

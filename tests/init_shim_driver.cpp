@@ -1,6 +1,6 @@
 // TEST INFRASTRUCTURE ONLY -- drives include/shims/Initializer_orbfe.cc the way Tracking::MonocularInitialization does
 // (Initializer(mInitialFrame, 1.0, 200), then Initialize / InitializeUseAruco with the current frame), against the mock headers
-// of tests/mock_init/ + tests/mock_cv/, and dumps results as raw arrays for tests/test_initializer_shim_gpu.py.
+// of tests/mock_orbslam/, and dumps results as raw arrays for tests/test_initializer_shim_gpu.py.
 //   init_shim_driver <in prefix> <out prefix>      inputs: _kps1 _kps2 (28-byte keypoints), _m12 (int32), _K (4 floats),
 //                                                   _poses (npose x 12 floats)
 #include <cstdio>
@@ -9,28 +9,9 @@
 #include <vector>
 
 #include "Initializer.h"
+#include "shim_driver_io.hpp"
 
 using namespace ORB_SLAM2;
-
-template <class T> static std::vector<T> load(const std::string& path)
-{
-    std::vector<T> v;
-    FILE* f = fopen(path.c_str(), "rb");
-    if (!f) { fprintf(stderr, "cannot open %s\n", path.c_str()); exit(2); }
-    fseek(f, 0, SEEK_END);
-    const long n = ftell(f);
-    fseek(f, 0, SEEK_SET);
-    v.resize((size_t)n / sizeof(T));
-    if (n && fread(v.data(), sizeof(T), v.size(), f) != v.size()) exit(2);
-    fclose(f);
-    return v;
-}
-template <class T> static void dump(const std::string& path, const T* p, size_t n)
-{
-    FILE* f = fopen(path.c_str(), "wb");
-    if (n) fwrite(p, sizeof(T), n, f);
-    fclose(f);
-}
 
 int main(int argc, char** argv)
 {

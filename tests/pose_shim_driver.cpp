@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE ONLY -- drives include/shims/Optimizer_pose_orbfe.cc the way Tracking does (one Frame with map points and
-// mapped markers, Optimizer::PoseOptimizationByAruco), against the mock headers of tests/mock_pose/ + tests/mock_cv/, and dumps the
+// mapped markers, Optimizer::PoseOptimizationByAruco), against the mock headers of tests/mock_orbslam/, and dumps the
 // results as raw arrays for tests/test_pose_opt_shim_gpu.py.
 //   pose_shim_driver <in prefix> <out prefix> <side>   inputs: _kps (28-byte keypoints), _has (uint8), _x (n x 3 floats),
 //                                                       _sig (floats), _K (4 floats), _mk (128-byte marker records), _T (12 floats),
@@ -13,31 +13,9 @@
 #include "MapAruco.h"
 #include "MapPoint.h"
 #include "Optimizer.h"
+#include "shim_driver_io.hpp"
 
 using namespace ORB_SLAM2;
-
-float Frame::fx, Frame::fy, Frame::cx, Frame::cy;
-bool Frame::mbUArucoIni = false;
-
-template <class T> static std::vector<T> load(const std::string& path)
-{
-    std::vector<T> v;
-    FILE* f = fopen(path.c_str(), "rb");
-    if (!f) { fprintf(stderr, "cannot open %s\n", path.c_str()); exit(2); }
-    fseek(f, 0, SEEK_END);
-    const long n = ftell(f);
-    fseek(f, 0, SEEK_SET);
-    v.resize((size_t)n / sizeof(T));
-    if (n && fread(v.data(), sizeof(T), v.size(), f) != v.size()) exit(2);
-    fclose(f);
-    return v;
-}
-template <class T> static void dump(const std::string& path, const T* p, size_t n)
-{
-    FILE* f = fopen(path.c_str(), "wb");
-    if (n) fwrite(p, sizeof(T), n, f);
-    fclose(f);
-}
 
 int main(int argc, char** argv)
 {

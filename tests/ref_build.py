@@ -21,16 +21,21 @@ def build_shared(source, std="c++14", prefix=None):
     return _libs[source]
 
 
-def build_shim(shim_cc, driver_cpp, mock_dirs, out_dir):
-    """include/shims/<shim_cc> and tests/<driver_cpp>, against the mock headers of mock_dirs (in include-path order) and the built
-    library; returns the program's path in out_dir."""
+MOCK_DIRS = ("tests/mock_orbslam", "tests/mock_orbslam/aruco", "tests/mock_orbslam/dbow2")
+
+
+def build_shim(shim_ccs, driver_cpp, out_dir):
+    """The sources shim_ccs of include/shims/, tests/<driver_cpp> and the mock Frame's static members as one program, against the one
+    mock tree tests/mock_orbslam/ and the built library; returns the program's path in out_dir."""
     inc = []
-    for d in tuple(mock_dirs) + ("include", "include/shims"):
+    for d in MOCK_DIRS + ("include", "include/shims"):
         inc += ["-I", os.path.join(ROOT, d)]
-    obj = os.path.join(out_dir, os.path.splitext(shim_cc)[0] + ".o")
+    flags = ["g++", "-std=c++14", "-O1", "-Wall", "-Werror"]
+    objs = []
+    for src in [os.path.join(ROOT, "include", "shims", cc) for cc in shim_ccs] + [os.path.join(HERE, "mock_orbslam", "Frame_statics.cc")]:
+        objs.append(os.path.join(out_dir, os.path.splitext(os.path.basename(src))[0] + ".o"))
+        subprocess.check_call(flags + inc + ["-c", src, "-o", objs[-1]])
     exe = os.path.join(out_dir, os.path.splitext(driver_cpp)[0])
-    flags = ["g++", "-std=c++14", "-O1", "-Wall", "-Werror", "-Wno-unused-function"]
-    subprocess.check_call(flags + inc + ["-c", os.path.join(ROOT, "include", "shims", shim_cc), "-o", obj])
     lib_dir = os.path.join(ROOT, "orb_slam2_aruco_amd")
-    subprocess.check_call(flags + inc + [os.path.join(HERE, driver_cpp), obj, "-o", exe, "-L", lib_dir, "-lorbfe", "-Wl,-rpath," + lib_dir])
+    subprocess.check_call(flags + inc + [os.path.join(HERE, driver_cpp)] + objs + ["-o", exe, "-L", lib_dir, "-lorbfe", "-Wl,-rpath," + lib_dir])
     return exe

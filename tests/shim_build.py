@@ -1,6 +1,20 @@
-"""Builds tests/shim_driver.cpp + include/shims/ORBmatcher_orbfe.cc against the mock headers of tests/mock_cv/ (test infrastructure)."""
+"""Builds the shim programs (test infrastructure): the sources of include/shims/ and a driver of tests/, compiled -Wall -Werror against the
+one mock ORB-SLAM2 tree tests/mock_orbslam/ and linked against the built library.  "all" links every shim into one program, as an
+integration does."""
 import ref_build
 
+PROGRAMS = {
+    "matcher": (("ORBmatcher_orbfe.cc",), "shim_driver.cpp"),   # with ORBextractor.h and MarkerDetector.h, which the driver includes
+    "init": (("Initializer_orbfe.cc",), "init_shim_driver.cpp"),
+    "pose": (("Optimizer_pose_orbfe.cc",), "pose_shim_driver.cpp"),
+    "sim3": (("Sim3Solver_orbfe.cc",), "sim3_shim_driver.cpp"),
+    "sim3_opt": (("Optimizer_sim3_orbfe.cc",), "sim3_opt_shim_driver.cpp"),
+    "kfdb": (("KeyFrameDatabase_orbfe.cc",), "kfdb_shim_driver.cpp"),
+}
+PROGRAMS["all"] = (tuple(cc for name in sorted(PROGRAMS) for cc in PROGRAMS[name][0]), "all_shims_driver.cpp")
 
-def build(out_dir):
-    return ref_build.build_shim("ORBmatcher_orbfe.cc", "shim_driver.cpp", ("tests/mock_cv", "tests/mock_cv/orbslam", "tests/mock_cv/aruco"), out_dir)
+
+def build(name, out_dir):
+    """the program's path in out_dir"""
+    shim_ccs, driver = PROGRAMS[name]
+    return ref_build.build_shim(shim_ccs, driver, out_dir)

@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE ONLY -- drives the C++ shims of include/shims/ (ORBextractor, aruco::MarkerDetector, ORBmatcher) the way the
-// reference's Frame / Tracking code does, against the mock OpenCV / SLAM headers of tests/mock_cv/, and dumps inputs and results as
+// reference's Frame / Tracking code does, against the mock OpenCV / SLAM headers of tests/mock_orbslam/, and dumps inputs and results as
 // raw arrays; tests/test_shims_gpu.py repeats every call through the ctypes binding and compares.
 //   shim_driver <frames.raw> <rows> <cols> <nframes> <out prefix>          exit 3 = no GPU (the library has no CPU fallback)
 #include <cmath>
@@ -16,9 +16,6 @@
 
 using namespace ORB_SLAM2;
 
-float Frame::fx, Frame::fy, Frame::cx, Frame::cy, Frame::invfx, Frame::invfy;
-float Frame::mnMinX, Frame::mnMaxX, Frame::mnMinY, Frame::mnMaxY;
-
 static std::string g_prefix;
 template <class T> static void dump(const char* name, const T* p, size_t n)
 {
@@ -28,7 +25,7 @@ template <class T> static void dump(const char* name, const T* p, size_t n)
 }
 template <class T> static void dump(const char* name, const std::vector<T>& v) { dump(name, v.data(), v.size()); }
 
-static cv::Mat mat32(int r, int c, std::initializer_list<float> v)
+static cv::Mat matf(int r, int c, std::initializer_list<float> v)
 {
     cv::Mat m(r, c, CV_32F);
     int i = 0;
@@ -91,8 +88,8 @@ int main(int argc, char** argv)
     det.setDetectionMode(aruco::DM_NORMAL);
     det.getParameters().setCornerRefinementMethod(aruco::CORNER_LINES);
     aruco::CameraParameters cam;
-    cam.CameraMatrix = mat32(3, 3, {517.306408f, 0, 318.643040f, 0, 516.469215f, 255.313989f, 0, 0, 1});
-    cam.Distorsion = mat32(1, 5, {0.262383f, -0.953104f, -0.005358f, 0.002628f, 1.163314f});
+    cam.CameraMatrix = matf(3, 3, {517.306408f, 0, 318.643040f, 0, 516.469215f, 255.313989f, 0, 0, 1});
+    cam.Distorsion = matf(1, 5, {0.262383f, -0.953104f, -0.005358f, 0.002628f, 1.163314f});
     cam.CamSize = cv::Size(1280, 720);
     {
         cv::Mat im(rows, cols, CV_8UC1, raw.data(), (size_t)cols);
@@ -155,9 +152,9 @@ int main(int argc, char** argv)
     for (int i = 0; i < L.N; i++) {
         const float z = 1.0f + 0.1f * (float)(i % 50);
         const float X = (L.mvKeysUn[i].pt.x - Frame::cx) / Frame::fx * z, Y = (L.mvKeysUn[i].pt.y - Frame::cy) / Frame::fy * z;
-        mps[i].mWorldPos = mat32(3, 1, {X, Y, z});
+        mps[i].mWorldPos = matf(3, 1, {X, Y, z});
         const float d = sqrt(X * X + Y * Y + z * z);
-        mps[i].mNormal = mat32(3, 1, {X / d, Y / d, z / d});
+        mps[i].mNormal = matf(3, 1, {X / d, Y / d, z / d});
         mps[i].mDescriptor = L.mDescriptors.row(i);
         mps[i].mfMaxDistance = d * L.mvScaleFactors[L.mvKeysUn[i].octave];
         mps[i].mfMinDistance = mps[i].mfMaxDistance / L.mvScaleFactors[L.mnScaleLevels - 1];
@@ -167,7 +164,7 @@ int main(int argc, char** argv)
         if (i % 9 != 0) L.mvpMapPoints[i] = &mps[i];
     }
     dump("x3", x3); dump("dmin", dmin); dump("dmax", dmax);
-    C.mTcw = mat32(4, 4, {1, -0.002f, 0.001f, 0.004f, 0.002f, 1, -0.003f, -0.006f, -0.001f, 0.003f, 1, 0.01f, 0, 0, 0, 1});
+    C.mTcw = matf(4, 4, {1, -0.002f, 0.001f, 0.004f, 0.002f, 1, -0.003f, -0.006f, -0.001f, 0.003f, 1, 0.01f, 0, 0, 0, 1});
     {   // Tracking::TrackWithMotionModel (Tracking.cc:1011)
         res.push_back(matcher.SearchByProjection(C, L, 15.0f, true));
         std::vector<int> got(C.N, -1);
@@ -181,7 +178,7 @@ int main(int argc, char** argv)
     KF.mnMinX = 0; KF.mnMinY = 0; KF.mnMaxX = cols; KF.mnMaxY = rows;
     KF.mnScaleLevels = L.mnScaleLevels; KF.mfScaleFactor = L.mfScaleFactor; KF.mfLogScaleFactor = L.mfLogScaleFactor;
     KF.mvScaleFactors = L.mvScaleFactors; KF.mvLevelSigma2 = L.mvLevelSigma2; KF.mvInvLevelSigma2 = L.mvInvLevelSigma2;
-    KF.Rcw = mat32(3, 3, {1, 0, 0, 0, 1, 0, 0, 0, 1}); KF.tcw = mat32(3, 1, {0, 0, 0}); KF.Ow = mat32(3, 1, {0, 0, 0});
+    KF.Rcw = matf(3, 3, {1, 0, 0, 0, 1, 0, 0, 0, 1}); KF.tcw = matf(3, 1, {0, 0, 0}); KF.Ow = matf(3, 1, {0, 0, 0});
     {   // Tracking::Relocalization (Tracking.cc:1858): SearchByProjection(CurrentFrame, pKF, sFound, 10, 100)
         std::set<MapPoint*> sFound;
         for (int i = 0; i < L.N; i += 5) sFound.insert(&mps[i]);
@@ -246,7 +243,7 @@ int main(int argc, char** argv)
         KF2.mnScaleLevels = C.mnScaleLevels; KF2.mfScaleFactor = C.mfScaleFactor; KF2.mfLogScaleFactor = C.mfLogScaleFactor;
         KF2.mvScaleFactors = C.mvScaleFactors; KF2.mvLevelSigma2 = C.mvLevelSigma2; KF2.mvInvLevelSigma2 = C.mvInvLevelSigma2;
         const float t2[3] = {0.004f, -0.006f, 0.01f};
-        KF2.Rcw = mat32(3, 3, {1, 0, 0, 0, 1, 0, 0, 0, 1}); KF2.tcw = mat32(3, 1, {t2[0], t2[1], t2[2]}); KF2.Ow = mat32(3, 1, {-t2[0], -t2[1], -t2[2]});
+        KF2.Rcw = matf(3, 3, {1, 0, 0, 0, 1, 0, 0, 0, 1}); KF2.tcw = matf(3, 1, {t2[0], t2[1], t2[2]}); KF2.Ow = matf(3, 1, {-t2[0], -t2[1], -t2[2]});
         std::vector<MapPoint> mps2(C.N);
         std::vector<float> x3b(3 * (size_t)C.N), dminb(C.N), dmaxb(C.N);
         KF2.mvpMapPoints.assign(C.N, (MapPoint*)NULL);
@@ -254,9 +251,9 @@ int main(int argc, char** argv)
             const float z = 1.0f + 0.1f * (float)(i % 50);
             const float Xc = (C.mvKeysUn[i].pt.x - Frame::cx) / Frame::fx * z, Yc = (C.mvKeysUn[i].pt.y - Frame::cy) / Frame::fy * z;
             const float X = Xc - t2[0], Y = Yc - t2[1], Z = z - t2[2]; // world = camera - tcw (R = I)
-            mps2[i].mWorldPos = mat32(3, 1, {X, Y, Z});
+            mps2[i].mWorldPos = matf(3, 1, {X, Y, Z});
             const float d = sqrt(Xc * Xc + Yc * Yc + z * z);
-            mps2[i].mNormal = mat32(3, 1, {Xc / d, Yc / d, z / d});
+            mps2[i].mNormal = matf(3, 1, {Xc / d, Yc / d, z / d});
             mps2[i].mDescriptor = C.mDescriptors.row(i);
             mps2[i].mfMaxDistance = d * C.mvScaleFactors[C.mvKeysUn[i].octave];
             mps2[i].mfMinDistance = mps2[i].mfMaxDistance / C.mvScaleFactors[C.mnScaleLevels - 1];
@@ -293,7 +290,7 @@ int main(int argc, char** argv)
             // through its own pixel, so the epipolar gate has something to accept, which two unrelated synthetic frames do not give it)
             KeyFrame A = KF, B2 = KF;
             const float t3[3] = {0.05f, 0.0f, 0.001f};
-            B2.tcw = mat32(3, 1, {t3[0], t3[1], t3[2]}); B2.Ow = mat32(3, 1, {-t3[0], -t3[1], -t3[2]});
+            B2.tcw = matf(3, 1, {t3[0], t3[1], t3[2]}); B2.Ow = matf(3, 1, {-t3[0], -t3[1], -t3[2]});
             for (int i = 0; i < A.N; i++) if (i % 3) A.mvpMapPoints[i] = NULL;
             for (int i = 0; i < B2.N; i++) if (i % 3 != 1) B2.mvpMapPoints[i] = NULL;
             // F12 = K1^-T [t12]x R12 K2^-1 (LocalMapping::ComputeF12) for R12 = I, t12 = -t3, written out
@@ -304,7 +301,7 @@ int main(int argc, char** argv)
             for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) { float v = 0; for (int k = 0; k < 3; k++) v += E[3 * r + k] * Ki[3 * k + c]; EK[3 * r + c] = v; }
             for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) { float v = 0; for (int k = 0; k < 3; k++) v += Ki[3 * k + r] * EK[3 * k + c]; F12a[3 * r + c] = v; }
             dump("F12", F12a, 9);
-            cv::Mat F12 = mat32(3, 3, {F12a[0], F12a[1], F12a[2], F12a[3], F12a[4], F12a[5], F12a[6], F12a[7], F12a[8]});
+            cv::Mat F12 = matf(3, 3, {F12a[0], F12a[1], F12a[2], F12a[3], F12a[4], F12a[5], F12a[6], F12a[7], F12a[8]});
             std::vector<std::pair<size_t, size_t> > pairs;
             ORBmatcher m06(0.6f, false);
             res.push_back(m06.SearchForTriangulation(&A, &B2, F12, pairs, false));
@@ -318,7 +315,7 @@ int main(int argc, char** argv)
             std::vector<int> pre(L.N);
             for (int i = 0; i < L.N; i++) pre[i] = m12[i] ? (int)(m12[i] - mps2.data()) : -1;
             dump("sim3_pre", pre);
-            cv::Mat R12 = mat32(3, 3, {1, 0, 0, 0, 1, 0, 0, 0, 1}), t12 = mat32(3, 1, {-t2[0], -t2[1], -t2[2]});
+            cv::Mat R12 = matf(3, 3, {1, 0, 0, 0, 1, 0, 0, 0, 1}), t12 = matf(3, 1, {-t2[0], -t2[1], -t2[2]});
             const float s12 = 1.0f;
             res.push_back(matcher.SearchBySim3(&KF, &KF2, m12, s12, R12, t12, 7.5f));
             std::vector<int> idx(L.N);
@@ -329,7 +326,7 @@ int main(int argc, char** argv)
         // the two Scw members look at a keyframe through a similarity that is ALMOST the keyframe's own pose (frame 0 seen from 0.5 mm
         // to the side, scale 1): loop-closure candidates then project next to the keypoints they came from, as they do after a good Sim3
         const float ts[3] = {0.0005f, -0.0003f, 0.0f};
-        cv::Mat Scws = mat32(4, 4, {1, 0, 0, ts[0], 0, 1, 0, ts[1], 0, 0, 1, ts[2], 0, 0, 0, 1});
+        cv::Mat Scws = matf(4, 4, {1, 0, 0, ts[0], 0, 1, 0, ts[1], 0, 0, 1, ts[2], 0, 0, 0, 1});
         std::vector<MapPoint> mps3(mps.begin(), mps.end()); // the keyframe's own points (other objects than the candidates)
         KeyFrame KF3 = KF;
         for (int i = 0; i < KF3.N; i++) KF3.mvpMapPoints[i] = (i % 4 != 0) ? &mps3[i] : NULL;

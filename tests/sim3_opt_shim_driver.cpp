@@ -1,6 +1,6 @@
 // TEST INFRASTRUCTURE ONLY -- drives include/shims/Optimizer_sim3_orbfe.cc the way LoopClosing::ComputeSim3 does (g2oS12 built from a
 // float rotation, translation and scale; OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale)) against the mock headers of
-// tests/mock_optsim3/ + tests/mock_cv/, and dumps the results as raw arrays for tests/test_sim3_opt_shim_gpu.py.
+// tests/mock_orbslam/, and dumps the results as raw arrays for tests/test_sim3_opt_shim_gpu.py.
 //   sim3_opt_shim_driver <in prefix> <out prefix>
 //   inputs: <in>_kps1 _kps2 (28-byte keypoints), _x1 _x2 (n x 3 floats), _v1 _v2 (bytes), _m12 (int32), _T1 _T2 (12 floats), _K (4
 //   floats), _is2 (floats), _sim (13 floats: s12, R12, t12), _par (2 floats: th2, fix_scale)
@@ -13,28 +13,9 @@
 #include <vector>
 
 #include "Optimizer.h"
+#include "shim_driver_io.hpp"
 
 using namespace ORB_SLAM2;
-
-template <class T> static std::vector<T> load(const std::string& path)
-{
-    std::vector<T> v;
-    FILE* f = fopen(path.c_str(), "rb");
-    if (!f) { fprintf(stderr, "cannot open %s\n", path.c_str()); exit(2); }
-    fseek(f, 0, SEEK_END);
-    const long n = ftell(f);
-    fseek(f, 0, SEEK_SET);
-    v.resize((size_t)n / sizeof(T));
-    if (n && fread(v.data(), sizeof(T), v.size(), f) != v.size()) exit(2);
-    fclose(f);
-    return v;
-}
-template <class T> static void dump(const std::string& path, const std::vector<T>& v)
-{
-    FILE* f = fopen(path.c_str(), "wb");
-    if (!v.empty()) fwrite(v.data(), sizeof(T), v.size(), f);
-    fclose(f);
-}
 
 struct Side {
     KeyFrame kf;

@@ -1,6 +1,6 @@
 // TEST INFRASTRUCTURE ONLY -- drives include/shims/Sim3Solver_orbfe.cc the way LoopClosing::ComputeSim3 does (one solver per loop
 // candidate, SetRansacParameters(0.99, 20, 300), then iterate(5, ...) on every candidate in turn until each has no more), against
-// the mock headers of tests/mock_sim3/ + tests/mock_cv/, and dumps every call's results as raw arrays for
+// the mock headers of tests/mock_orbslam/, and dumps every call's results as raw arrays for
 // tests/test_sim3_shim_gpu.py.  A candidate that returns a transform stays in the round (the case of an OptimizeSim3 that rejects it).
 // The shim draws its words with rand().  The driver defines rand() itself (a 64-bit LCG seeded from the command line), so that the
 // shim's draws are the driver's alone -- the C library's rand() state is shared with every library in the process, and the GPU
@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "Sim3Solver.h"
+#include "shim_driver_io.hpp"
 
 using namespace ORB_SLAM2;
 
@@ -27,26 +28,6 @@ extern "C" __attribute__((visibility("hidden"))) int rand(void) noexcept
     const int v = (int)((g_rand_state >> 33) & 0x7fffffffULL);   // 0 .. RAND_MAX
     g_drawn.push_back(v);
     return v;
-}
-
-template <class T> static std::vector<T> load(const std::string& path)
-{
-    std::vector<T> v;
-    FILE* f = fopen(path.c_str(), "rb");
-    if (!f) { fprintf(stderr, "cannot open %s\n", path.c_str()); exit(2); }
-    fseek(f, 0, SEEK_END);
-    const long n = ftell(f);
-    fseek(f, 0, SEEK_SET);
-    v.resize((size_t)n / sizeof(T));
-    if (n && fread(v.data(), sizeof(T), v.size(), f) != v.size()) exit(2);
-    fclose(f);
-    return v;
-}
-template <class T> static void dump(const std::string& path, const std::vector<T>& v)
-{
-    FILE* f = fopen(path.c_str(), "wb");
-    if (!v.empty()) fwrite(v.data(), sizeof(T), v.size(), f);
-    fclose(f);
 }
 
 struct Side {

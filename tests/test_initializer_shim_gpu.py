@@ -1,4 +1,4 @@
-"""GPU: include/shims/Initializer_orbfe.cc, built with g++ against the mock headers of tests/mock_init/, runs one scene the way
+"""GPU: include/shims/Initializer_orbfe.cc, built with g++ against the mock headers of tests/mock_orbslam/, runs one scene the way
 Tracking does (Initializer(frame1, 1.0, 200).Initialize(frame2, ...), then InitializeUseAruco) and returns what the C ABI returns for
 the same inputs -- the rand() words being those of a fresh process after srand(0), as SeedRandOnce(0) draws them."""
 import json
@@ -8,7 +8,7 @@ import sys
 import numpy as np
 import pytest
 
-import init_shim_build
+import shim_build
 import initializer_cases as S
 
 pytestmark = pytest.mark.gpu
@@ -20,7 +20,7 @@ def _fresh_process_rand(n):
 
 
 def test_initializer_shim_equals_the_binding(orbfe, tmp_path):
-    exe = init_shim_build.build(str(tmp_path))
+    exe = shim_build.build("init", str(tmp_path))
     sc = S.scene("planar", 800, 0.2, seed=1, noise=0.5)
     tn = sc["t"] / np.linalg.norm(sc["t"])
     R = np.array([np.eye(3), sc["R"], sc["R"].T], np.float32)

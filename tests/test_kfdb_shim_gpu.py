@@ -8,7 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
-import kfdb_shim_build
+import shim_build
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -19,7 +19,7 @@ def test_shim_returns_the_reference_keyframes_in_order(tmp_path):
     lines = want.strip().split("\n")
     assert len(lines) == 10 and lines[7] == "reloc f3 empty:" and lines[6] == "loop kf39 high:"  # clear() and a min_score nothing reaches
     assert sum(len(l.split(":")[1].split()) >= 1 for l in lines) >= 6 and lines[0] != lines[2]    # erase() changed the repeated query
-    exe = kfdb_shim_build.build(str(tmp_path))
+    exe = shim_build.build("kfdb", str(tmp_path))
     got = subprocess.run([exe, "script"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
     assert got.returncode == 0, got.stderr
     assert got.stdout == want
@@ -31,7 +31,7 @@ def test_shim_survives_keyframe_culling_beyond_the_bound_of_one_call(tmp_path):
     want = str(np.load(os.path.join(ROOT, "tests", "golden", "kfdb_cases.npz"))["shim_cull"])
     lines = want.strip().split("\n")
     assert len(lines) == 3 and all(len(l.split(":")[1].split()) >= 1 for l in lines)
-    exe = kfdb_shim_build.build(str(tmp_path))
+    exe = shim_build.build("kfdb", str(tmp_path))
     got = subprocess.run([exe, "cull"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=120)
     assert got.returncode == 0, got.stderr
     assert got.stdout == want

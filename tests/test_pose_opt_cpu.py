@@ -34,17 +34,6 @@ def test_header_binding_and_library_agree_on_the_pose_optimization():
     assert binding.POSE_RESULT_DTYPE == B.RESULT_DTYPE and binding.POSE_MARKER_DTYPE == B.MARKER_DTYPE
 
 
-def test_pose_shim_compiles_and_links_against_the_mock_headers(tmp_path):
-    """include/shims/Optimizer_pose_orbfe.cc with the reference's signatures (tests/mock_pose/ before tests/mock_cv/): g++ -Wall
-    -Werror, linked against liborbfe.so."""
-    import pose_shim_build
-    from orb_slam2_aruco_amd import binding
-    if not os.path.exists(binding.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    assert os.path.exists(pose_shim_build.build(str(tmp_path)))
-
-
 def _rot_err(Ra, Rb):
     """rotation angle of Ra^T Rb, from the skew part (accurate near 0, unlike the trace)"""
     D = np.asarray(Ra, np.float64)[:3, :3].T @ np.asarray(Rb, np.float64)[:3, :3]

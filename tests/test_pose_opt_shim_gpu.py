@@ -1,4 +1,4 @@
-"""GPU: include/shims/Optimizer_pose_orbfe.cc, built with g++ against the mock headers of tests/mock_pose/, runs one frame with map
+"""GPU: include/shims/Optimizer_pose_orbfe.cc, built with g++ against the mock headers of tests/mock_orbslam/, runs one frame with map
 points and mapped markers (plus an old and a bad marker that must be left out) through Optimizer::PoseOptimizationByAruco and
 returns what the C ABI returns for the same inputs, bit for bit; PoseOptimization throws on a stereo observation."""
 import subprocess
@@ -7,13 +7,13 @@ import numpy as np
 import pytest
 
 import pose_opt_cases as S
-import pose_shim_build
+import shim_build
 
 pytestmark = pytest.mark.gpu
 
 
 def test_pose_shim_equals_the_binding(orbfe, tmp_path):
-    exe = pose_shim_build.build(str(tmp_path))
+    exe = shim_build.build("pose", str(tmp_path))
     pb = S.case("n500_out10_m3")
     rng = np.random.default_rng(0)
     out0 = (rng.random(len(pb["kps"])) < 0.3).astype(np.uint8)   # mvbOutlier before the call: overwritten where there is a map point

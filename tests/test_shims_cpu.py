@@ -1,16 +1,45 @@
-"""The C++ shims of include/shims/ are real code: they compile (-Wall -Werror) against minimal mock OpenCV / SLAM headers
-(tests/mock_cv/, test infrastructure), link against liborbfe.so, and without a GPU the driver stops at the library's loud
-"no device" answer instead of falling back to anything."""
+"""The C++ shims of include/shims/ are real code: they compile (-Wall -Werror) against ONE set of minimal mock OpenCV / ORB-SLAM2
+headers (tests/mock_orbslam/, test infrastructure) with the helper header include/shims/orbfe_shim.h, link against liborbfe.so --
+each with its driver, and all of them into one program, as an integration links them -- and without a GPU the driver stops at the
+library's loud "no device" answer instead of falling back to anything."""
+import os
 import subprocess
 
 import pytest
 
 import shim_build
 
+SHIM_PROGRAMS = ["matcher", "init", "pose", "sim3", "sim3_opt", "kfdb"]
+
+
+def _library():
+    from orb_slam2_aruco_amd import binding
+    if not os.path.exists(binding.LIB_PATH):
+        import __graft_entry__
+        __graft_entry__.build()
+
+
+@pytest.mark.parametrize("name", SHIM_PROGRAMS)
+def test_shim_compiles_and_links_against_the_mock_headers(name, tmp_path):
+    """every shim with the reference's signatures and its driver: g++ -Wall -Werror, linked against liborbfe.so"""
+    assert sorted(SHIM_PROGRAMS + ["all"]) == sorted(shim_build.PROGRAMS)
+    _library()
+    assert os.path.exists(shim_build.build(name, str(tmp_path)))
+
+
+def test_all_shims_compile_and_link_into_one_program(tmp_path):
+    """the five .cc shims, the two header shims and every mock class header in one program (tests/all_shims_driver.cpp): one Frame,
+    KeyFrame, MapPoint and Optimizer declaration serves them all, and no symbol is defined twice.  The program opens no device."""
+    _library()
+    exe = shim_build.build("all", str(tmp_path))
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    assert r.stdout.startswith("ok")
+
 
 def test_shims_compile_link_and_refuse_without_a_gpu(tmp_path):
     from orb_slam2_aruco_amd import binding
-    exe = shim_build.build(str(tmp_path))
+    exe = shim_build.build("matcher", str(tmp_path))
     if binding.load().orbfe_device_count() > 0:
         pytest.skip("a GPU is present: tests/test_shims_gpu.py runs the driver")
     r = subprocess.run([exe, "none", "1", "1", "1", str(tmp_path / "o")], capture_output=True, text=True)

@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 
 
 def test_shims_equal_the_binding(orbfe, oracle, tmp_path):
-    exe = shim_build.build(str(tmp_path))
+    exe = shim_build.build("matcher", str(tmp_path))
     s = synth.stream(480, 640, 2, 1000)
     s.tofile(tmp_path / "frames.raw")
     pre = str(tmp_path / "o")

@@ -162,13 +162,3 @@ def test_required_cases_have_a_clear_decision(c):
     prob, min_inl, max_it = S.ransac_of(c)
     want = B.solve(sc, prob, min_inl, max_it, words=S.case_words(c))
     assert P.decision_reason(want, sc, min_inl, max_it) is None
-
-
-def test_sim3_shim_compiles_against_the_mock_headers(tmp_path):
-    """include/shims/Sim3Solver_orbfe.cc with the reference's signatures (mock headers of tests/mock_sim3/): g++ -Wall -Werror."""
-    import sim3_shim_build
-    from orb_slam2_aruco_amd import binding
-    if not os.path.exists(binding.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    assert os.path.exists(sim3_shim_build.build(str(tmp_path)))

@@ -55,17 +55,6 @@ def test_header_binding_and_library_agree_on_optimize_sim3():
     assert f["R12"][1] == f["s12"][1] + 4 and f["t12"][1] == f["s12"][1] + 40 and binding.SIM3_RESULT_S12_OFFSET == f["s12"][1]
 
 
-def test_optimize_sim3_shim_compiles_and_links_against_the_mock_headers(tmp_path):
-    """include/shims/Optimizer_sim3_orbfe.cc with the reference's signature (tests/mock_optsim3/ before tests/mock_cv/): g++ -Wall
-    -Werror, linked against liborbfe.so."""
-    import sim3_opt_shim_build
-    from orb_slam2_aruco_amd import binding
-    if not os.path.exists(binding.LIB_PATH):
-        import __graft_entry__
-        __graft_entry__.build()
-    assert os.path.exists(sim3_opt_shim_build.build(str(tmp_path)))
-
-
 @pytest.mark.parametrize("name", S.CLEAN)
 def test_restatement_recovers_the_true_similarity_on_clean_scenes(name):
     """fixed and free scale, true scale 0.7, 1 and 1.3: the points are floats, so the truth comes back to float accuracy"""

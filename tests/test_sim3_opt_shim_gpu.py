@@ -1,4 +1,4 @@
-"""GPU: include/shims/Optimizer_sim3_orbfe.cc, built with g++ against the mock headers of tests/mock_optsim3/, runs one scene the way
+"""GPU: include/shims/Optimizer_sim3_orbfe.cc, built with g++ against the mock headers of tests/mock_orbslam/, runs one scene the way
 LoopClosing::ComputeSim3 does and returns what the C ABI returns for the same inputs through binding.optimize_sim3 -- fed the
 similarity as the shim rounds it to float (the driver dumps it, tests/sim3_opt_shim_driver.cpp)."""
 import subprocess
@@ -7,13 +7,13 @@ import numpy as np
 import pytest
 
 import sim3_opt_cases as S
-import sim3_opt_shim_build
+import shim_build
 
 pytestmark = pytest.mark.gpu
 
 
 def test_optimize_sim3_shim_returns_the_bindings_result(orbfe, tmp_path):
-    exe = sim3_opt_shim_build.build(str(tmp_path))
+    exe = shim_build.build("sim3_opt", str(tmp_path))
     pb = S.case("n257_out30")
     p = str(tmp_path / "in")
     pb["kps1"].tofile(p + "_kps1.bin"); pb["kps2"].tofile(p + "_kps2.bin")

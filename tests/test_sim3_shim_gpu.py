@@ -1,4 +1,4 @@
-"""GPU: include/shims/Sim3Solver_orbfe.cc, built with g++ against the mock headers of tests/mock_sim3/, runs three solvers the way
+"""GPU: include/shims/Sim3Solver_orbfe.cc, built with g++ against the mock headers of tests/mock_orbslam/, runs three solvers the way
 LoopClosing::ComputeSim3 does (SetRansacParameters(0.99, 20, 300), then iterate(5) on each candidate in turn until none has more) and
 returns, call for call, what the C ABI returns for the same inputs through binding.Sim3Solver -- fed the rand() words the shim drew
 (the driver supplies rand() itself and dumps every value, tests/sim3_shim_driver.cpp), in the shim's own schedule of
@@ -10,14 +10,14 @@ import pytest
 
 import sim3_build as B
 import sim3_cases as S
-import sim3_shim_build
+import shim_build
 
 pytestmark = pytest.mark.gpu
 SEED = 4242
 
 
 def test_sim3_shim_equals_the_binding_over_interleaved_solvers(orbfe, tmp_path):
-    exe = sim3_shim_build.build(str(tmp_path))
+    exe = shim_build.build("sim3", str(tmp_path))
     # a candidate that succeeds late, one that never has enough correspondences, one that succeeds at once
     scenes = [S.scene(100, 1.3, 0.6, False, seed=4), S.scene(19, 1.0, 0.0, True, seed=4), S.scene(40, 0.7, 0.3, False, seed=4)]
     pre = str(tmp_path / "in")
