@@ -7,6 +7,8 @@
  * Every operation is a single IEEE-754 add/sub/mul/div on float or double, so
  * host and device agree bit for bit provided contraction is off
  * (-ffp-contract=off on both compilers; the Makefile and build() pass it).
+ * tests/test_device_units_gpu.py holds the promise as such: every function of this header, compiled for the device with build()'s
+ * flags, against the g++ compile, bit for bit, on dense and edge inputs (signed zeros and float denormals included).
  *
  * Reference call sites these restate:
  *   cvRound      -- src/ORBextractor.cc:81,117-120,442,1112 (OpenCV: round half to even)
