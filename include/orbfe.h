@@ -1023,7 +1023,9 @@ int orbfe_aruco_debug_contour_retries(const orbfe_aruco* h);
  * and what Frame.cc:170-174 asks for again to judge the ambiguity (aruco::solvePnP returning both IPPE solutions,
  * ippe.cpp:72-89): rvec/tvec = the solution with the lower reprojection error (Marker::Rvec / Tvec as CV_32F), rvec2/tvec2
  * the other one, err = their reprojection errors in pixels (Frame.cc:172: mvbArucoGood = err[0] / err[1] < 0.7).
- * Object frame: marker centre, corners (-s/2, s/2, 0) (s/2, s/2, 0) (s/2, -s/2, 0) (-s/2, -s/2, 0) (marker.cpp:358-369). */
+ * Object frame: marker centre, corners (-s/2, s/2, 0) (s/2, s/2, 0) (s/2, -s/2, 0) (-s/2, -s/2, 0) (marker.cpp:358-369).
+ * For a marker within about 1e-3 rad of fronto-parallel, rvec and err carry the error of the reference's rot2vec (eps / (pi - angle)^2), and the
+ * rvec and err of a solution, or the whole record, can be NaN; tvec and tvec2 are unaffected. */
 typedef struct orbfe_marker_pose {
     float rvec[3], tvec[3];
     float rvec2[3], tvec2[3];

@@ -91,8 +91,8 @@ __device__ inline void smallest_eigenvector(double a00, double a01, double a02, 
     int m = 0;
     if (A[1][1] < A[m][m]) m = 1;
     if (A[2][2] < A[m][m]) m = 2;
-    // cv::eigen sorts descending and the estimator takes the last row; among equal eigenvalues the later one stays last
-    if (m == 0 && A[1][1] == A[0][0]) m = 1;
+    // cv::eigen sorts descending (a selection sort that swaps rows) and the estimator takes the last row: of equal smallest eigenvalues
+    // row 2 stays last when it is among them, else row 0 does -- (a, a, b) with a < b moves row 2 to the front and leaves row 0 last
     if (m <= 1 && A[2][2] == A[m][m]) m = 2;
     h[0] = m == 0 ? E[0][0] : m == 1 ? E[1][0] : E[2][0];
     h[1] = m == 0 ? E[0][1] : m == 1 ? E[1][1] : E[2][1];

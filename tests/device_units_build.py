@@ -2,7 +2,7 @@
 
 probe()             tests/device_units_probe.hip, compiled once per process into a temporary directory with hipcc and exactly the flags
                     build() gives the library's sources (__graft_entry__.HIPCC_FLAGS + ORBFE_EXTRA_HIPCC_FLAGS), loaded with ctypes.
-                    The probe includes include/orbfe_math.h and csrc/{wave_dpp,lm_dense,ransac_sets,sim3_points}.hpp unchanged; it is
+                    The probe includes include/orbfe_math.h and csrc/{wave_dpp,lm_dense,ransac_sets,sim3_points,aruco_pose}.hpp unchanged; it is
                     not part of liborbfe.so.
 host()              tests/device_units_host.cpp (include/orbfe_math.h under g++ -ffp-contract=off), the same array calls for the math group.
 sanitizer_program() that host file as a program of its own under -fsanitize=address,undefined; returns its path.
@@ -33,6 +33,10 @@ _DEVICE = {"du_wave_i32": [i32, vp, vp, i32], "du_wave_u64": [i32, vp, vp, vp, i
            "du_block_sum2": [vp, vp, i32], "du_block_sum7": [vp, vp, i32], "du_block_count": [vp, vp, i32],
            "du_decode8": [vp, i32, vp, i32], "du_decode3": [vp, i32, vp, i32], "du_clampn": [vp, vp, vp, i32],
            "du_rigid": [vp, vp, vp, i32], "du_device_count": []}
+_POSE = {"du_pose_normalise": [vp, vp, vp, i32], "du_pose_eig": [vp, vp, i32], "du_pose_homography": [vp, vp, vp, i32],
+         "du_pose_rotations": [vp, vp, vp, i32], "du_pose_translation": [vp, vp, vp, vp, i32], "du_pose_rot2vec": [vp, vp, i32],
+         "du_pose_reproj": [vp, vp, vp, vp, vp, vp, i32], "du_pose_solve": [vp, C.c_float, vp, vp, i32],
+         "du_pose_solve_half": [vp, C.c_float, vp, i32, vp, i32]}
 
 
 def hipcc_command(out, flags=None):
@@ -55,7 +59,7 @@ def probe():
     if _probe is None:
         so = os.path.join(tempfile.mkdtemp(prefix="device_units_"), "device_units_probe.so")
         subprocess.check_call(hipcc_command(so))
-        _probe = _declare(_declare(C.CDLL(so), _MATH), _DEVICE)
+        _probe = _declare(_declare(_declare(C.CDLL(so), _MATH), _DEVICE), _POSE)
     return _probe
 
 
@@ -244,3 +248,79 @@ def rigid(T, p):
     d = np.empty_like(p)
     _ok(probe().du_rigid(_p(T), _p(p), _p(d), len(T)), "du_rigid")
     return d
+
+
+# ---- csrc/aruco_pose.hpp: cam17 = fx fy cx cy k[12] has_dist as doubles, one camera per call
+def _cam(cam17):
+    cam17 = _in(cam17, np.float64)
+    assert cam17.shape == (17,)
+    return cam17
+
+
+def pose_normalise(uv, cam17):
+    uv, cam17 = _in(uv, np.float32).reshape(-1, 2), _cam(cam17)
+    out = np.empty(uv.shape, np.float64)
+    _ok(probe().du_pose_normalise(_p(uv), _p(cam17), _p(out), len(uv)), "du_pose_normalise")
+    return out
+
+
+def pose_eig(a6):
+    a6 = _in(a6, np.float64).reshape(-1, 6)
+    h = np.empty((len(a6), 3))
+    _ok(probe().du_pose_eig(_p(a6), _p(h), len(a6)), "du_pose_eig")
+    return h
+
+
+def pose_homography(src, dst):
+    src, dst = _in(src, np.float64).reshape(-1, 8), _in(dst, np.float64).reshape(-1, 8)
+    assert len(src) == len(dst)
+    H = np.empty((len(src), 9))
+    _ok(probe().du_pose_homography(_p(src), _p(dst), _p(H), len(src)), "du_pose_homography")
+    return H
+
+
+def pose_rotations(j6):
+    j6 = _in(j6, np.float64).reshape(-1, 6)
+    R1, R2 = np.empty((len(j6), 9)), np.empty((len(j6), 9))
+    _ok(probe().du_pose_rotations(_p(j6), _p(R1), _p(R2), len(j6)), "du_pose_rotations")
+    return R1, R2
+
+
+def pose_translation(obj, img, R):
+    obj, img, R = _in(obj, np.float64).reshape(-1, 8), _in(img, np.float64).reshape(-1, 8), _in(R, np.float64).reshape(-1, 9)
+    assert len(obj) == len(img) == len(R)
+    t = np.empty((len(R), 3))
+    _ok(probe().du_pose_translation(_p(obj), _p(img), _p(R), _p(t), len(R)), "du_pose_translation")
+    return t
+
+
+def pose_rot2vec(R):
+    R = _in(R, np.float64).reshape(-1, 9)
+    r = np.empty((len(R), 3))
+    _ok(probe().du_pose_rot2vec(_p(R), _p(r), len(R)), "du_pose_rot2vec")
+    return r
+
+
+def pose_reproj(obj, img, cam17, R, t):
+    obj, img = _in(obj, np.float32).reshape(-1, 8), _in(img, np.float32).reshape(-1, 8)
+    R, t, cam17 = _in(R, np.float64).reshape(-1, 9), _in(t, np.float64).reshape(-1, 3), _cam(cam17)
+    assert len(obj) == len(img) == len(R) == len(t)
+    err = np.empty(len(R), np.float32)
+    _ok(probe().du_pose_reproj(_p(obj), _p(img), _p(cam17), _p(R), _p(t), _p(err), len(R)), "du_pose_reproj")
+    return err
+
+
+def pose_solve(corners, size, cam17):
+    """solve_marker: n x 14 = rvec tvec rvec2 tvec2 err[2]"""
+    corners, cam17 = _in(corners, np.float32).reshape(-1, 8), _cam(cam17)
+    out = np.empty((len(corners), 14), np.float32)
+    _ok(probe().du_pose_solve(_p(corners), np.float32(size), _p(cam17), _p(out), len(corners)), "du_pose_solve")
+    return out
+
+
+def pose_solve_half(corners, size, cam17, which):
+    """solve_marker_half: n x 7 = err rvec tvec of solution `which`"""
+    corners, cam17 = _in(corners, np.float32).reshape(-1, 8), _cam(cam17)
+    out = np.empty((len(corners), 7), np.float32)
+    _ok(probe().du_pose_solve_half(_p(corners), np.float32(size), _p(cam17), int(which), _p(out), len(corners)), "du_pose_solve_half")
+    return out

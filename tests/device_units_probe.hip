@@ -1,8 +1,8 @@
 // device_units_probe.hip -- test infrastructure only: the device helpers that several kernels share, each behind a small kernel
 // that applies it to arrays, and extern "C" calls on HOST pointers (own hipMalloc / hipMemcpy / launch / hipDeviceSynchronize /
 // hipFree; the HIP error code is returned).  tests/device_units_build.py compiles this file with the library's flags and loads it
-// with ctypes; it is not part of liborbfe.so.  The five headers are included unchanged:
-//   include/orbfe_math.h, csrc/wave_dpp.hpp, csrc/lm_dense.hpp, csrc/ransac_sets.hpp, csrc/sim3_points.hpp
+// with ctypes; it is not part of liborbfe.so.  The six headers are included unchanged:
+//   include/orbfe_math.h, csrc/wave_dpp.hpp, csrc/lm_dense.hpp, csrc/ransac_sets.hpp, csrc/sim3_points.hpp, csrc/aruco_pose.hpp
 // What is tested is these headers as a translation unit of their own, not their instantiations inside the product kernels.
 //
 // Every kernel is bounds-guarded and every output buffer is sized by the caller's n.  The kernels on wave_dpp.hpp need every lane of
@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../include/orbfe_math.h"
+#include "../orb_slam2_aruco_amd/csrc/aruco_pose.hpp"
 #include "../orb_slam2_aruco_amd/csrc/lm_dense.hpp"
 #include "../orb_slam2_aruco_amd/csrc/ransac_sets.hpp"
 #include "../orb_slam2_aruco_amd/csrc/sim3_points.hpp"
@@ -237,6 +238,109 @@ __global__ __launch_bounds__(TPB) void k_rigid(const float* T12, const float* p3
     float d[3];
     rigid(&T12[12 * i], p3[3 * i], p3[3 * i + 1], p3[3 * i + 2], d);
     for (int c = 0; c < 3; c++) d3[3 * i + c] = d[c];
+}
+
+
+// ---- csrc/aruco_pose.hpp: one thread per case; cam17 = fx fy cx cy k[12] has_dist, one camera per call
+__device__ inline PoseCamera pose_cam(const double* cam17)
+{
+    PoseCamera c;
+    c.fx = cam17[0]; c.fy = cam17[1]; c.cx = cam17[2]; c.cy = cam17[3];
+    for (int j = 0; j < 12; j++) c.k[j] = cam17[4 + j];
+    c.has_dist = cam17[16] != 0.0;
+    return c;
+}
+__global__ __launch_bounds__(TPB) void k_pose_normalise(const float* uv, const double* cam17, double* out, int n)
+{
+    const int i = blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    const pose::V2 p = pose::normalise_point(uv[2 * i], uv[2 * i + 1], pose_cam(cam17));
+    out[2 * i] = p.x; out[2 * i + 1] = p.y;
+}
+__global__ __launch_bounds__(TPB) void k_pose_eig(const double* a6, double* h3, int n)
+{
+    const int i = blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    double h[3];
+    pose::smallest_eigenvector(a6[6 * i], a6[6 * i + 1], a6[6 * i + 2], a6[6 * i + 3], a6[6 * i + 4], a6[6 * i + 5], h);
+    for (int c = 0; c < 3; c++) h3[3 * i + c] = h[c];
+}
+__global__ __launch_bounds__(TPB) void k_pose_homography(const double* src8, const double* dst8, double* H9, int n)
+{
+    const int i = blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    pose::V2 a[4], b[4];
+    for (int c = 0; c < 4; c++) { a[c] = {src8[8 * i + 2 * c], src8[8 * i + 2 * c + 1]}; b[c] = {dst8[8 * i + 2 * c], dst8[8 * i + 2 * c + 1]}; }
+    double H[9];
+    pose::homography4(a, b, H);
+    for (int c = 0; c < 9; c++) H9[9 * i + c] = H[c];
+}
+__global__ __launch_bounds__(TPB) void k_pose_rotations(const double* j6, double* R1, double* R2, int n)
+{
+    const int i = blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    double a[9], b[9];
+    pose::rotations(j6[6 * i], j6[6 * i + 1], j6[6 * i + 2], j6[6 * i + 3], j6[6 * i + 4], j6[6 * i + 5], a, b);
+    for (int c = 0; c < 9; c++) { R1[9 * i + c] = a[c]; R2[9 * i + c] = b[c]; }
+}
+__global__ __launch_bounds__(TPB) void k_pose_translation(const double* obj8, const double* img8, const double* R9, double* t3, int n)
+{
+    const int i = blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    pose::V2 a[4], b[4];
+    for (int c = 0; c < 4; c++) { a[c] = {obj8[8 * i + 2 * c], obj8[8 * i + 2 * c + 1]}; b[c] = {img8[8 * i + 2 * c], img8[8 * i + 2 * c + 1]}; }
+    double R[9], t[3];
+    for (int c = 0; c < 9; c++) R[c] = R9[9 * i + c];
+    pose::translation(a, b, R, t);
+    for (int c = 0; c < 3; c++) t3[3 * i + c] = t[c];
+}
+__global__ __launch_bounds__(TPB) void k_pose_rot2vec(const double* R9, double* r3, int n)
+{
+    const int i = blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    double R[9], r[3];
+    for (int c = 0; c < 9; c++) R[c] = R9[9 * i + c];
+    pose::rot2vec(R, r);
+    for (int c = 0; c < 3; c++) r3[3 * i + c] = r[c];
+}
+__global__ __launch_bounds__(TPB) void k_pose_reproj(const float* obj8, const float* img8, const double* cam17, const double* R9, const double* t3, float* err,
+                                                     int n)
+{
+    const int i = blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    float obj[4][2], img[4][2];
+    for (int c = 0; c < 4; c++)
+        for (int d = 0; d < 2; d++) { obj[c][d] = obj8[8 * i + 2 * c + d]; img[c][d] = img8[8 * i + 2 * c + d]; }
+    double R[9], t[3];
+    for (int c = 0; c < 9; c++) R[c] = R9[9 * i + c];
+    for (int c = 0; c < 3; c++) t[c] = t3[3 * i + c];
+    err[i] = pose::reprojection_error(obj, img, pose_cam(cam17), R, t);
+}
+// out14 = rvec tvec rvec2 tvec2 err[2], the fields of orbfe_marker_pose in order
+__global__ __launch_bounds__(TPB) void k_pose_solve(const float* corners8, float size, const double* cam17, float* out14, int n)
+{
+    const int i = blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    float c[4][2];
+    for (int a = 0; a < 4; a++)
+        for (int d = 0; d < 2; d++) c[a][d] = corners8[8 * i + 2 * a + d];
+    orbfe_marker_pose p;
+    pose::solve_marker(c, size, pose_cam(cam17), &p);
+    for (int a = 0; a < 3; a++) { out14[14 * i + a] = p.rvec[a]; out14[14 * i + 3 + a] = p.tvec[a]; out14[14 * i + 6 + a] = p.rvec2[a]; out14[14 * i + 9 + a] = p.tvec2[a]; }
+    out14[14 * i + 12] = p.err[0]; out14[14 * i + 13] = p.err[1];
+}
+// out7 = err rvec tvec of solution `which`
+__global__ __launch_bounds__(TPB) void k_pose_solve_half(const float* corners8, float size, const double* cam17, int which, float* out7, int n)
+{
+    const int i = blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    float c[4][2];
+    for (int a = 0; a < 4; a++)
+        for (int d = 0; d < 2; d++) c[a][d] = corners8[8 * i + 2 * a + d];
+    float e, r[3], t[3];
+    pose::solve_marker_half(c, size, pose_cam(cam17), which, &e, r, t);
+    out7[7 * i] = e;
+    for (int a = 0; a < 3; a++) { out7[7 * i + 1 + a] = r[a]; out7[7 * i + 4 + a] = t[a]; }
 }
 
 template <int N> int ldlt_call(const double* H, const double* b, double* x, int* ok, int n)
@@ -476,5 +580,115 @@ DU_API int du_rigid(const float* T12, const float* p3, float* d3, int n)
     if (A.err == hipSuccess && n) hipLaunchKernelGGL(k_rigid, grid_of(n), dim3(TPB), 0, 0, dT, dp, dd, n);
     A.ran();
     A.back(d3, dd, (size_t)3 * n);
+    return (int)A.err;
+}
+
+// ---- csrc/aruco_pose.hpp.  cam17 = fx fy cx cy k[12] has_dist (doubles), one camera per call
+DU_API int du_pose_normalise(const float* uv, const double* cam17, double* out, int n)
+{
+    if (n < 0) return (int)hipErrorInvalidValue;
+    Arena A;
+    const float* duv = A.dev(uv, (size_t)2 * n);
+    const double* dcam = A.dev(cam17, 17);
+    double* dout = A.dev<double>(nullptr, (size_t)2 * n);
+    if (A.err == hipSuccess && n) hipLaunchKernelGGL(k_pose_normalise, grid_of(n), dim3(TPB), 0, 0, duv, dcam, dout, n);
+    A.ran();
+    A.back(out, dout, (size_t)2 * n);
+    return (int)A.err;
+}
+// a6 n x 6 = a00 a01 a02 a11 a12 a22; h3 n x 3
+DU_API int du_pose_eig(const double* a6, double* h3, int n)
+{
+    if (n < 0) return (int)hipErrorInvalidValue;
+    Arena A;
+    const double* da = A.dev(a6, (size_t)6 * n);
+    double* dh = A.dev<double>(nullptr, (size_t)3 * n);
+    if (A.err == hipSuccess && n) hipLaunchKernelGGL(k_pose_eig, grid_of(n), dim3(TPB), 0, 0, da, dh, n);
+    A.ran();
+    A.back(h3, dh, (size_t)3 * n);
+    return (int)A.err;
+}
+// src8, dst8 n x 4 x 2; H9 n x 9 row-major
+DU_API int du_pose_homography(const double* src8, const double* dst8, double* H9, int n)
+{
+    if (n < 0) return (int)hipErrorInvalidValue;
+    Arena A;
+    const double *ds = A.dev(src8, (size_t)8 * n), *dd = A.dev(dst8, (size_t)8 * n);
+    double* dH = A.dev<double>(nullptr, (size_t)9 * n);
+    if (A.err == hipSuccess && n) hipLaunchKernelGGL(k_pose_homography, grid_of(n), dim3(TPB), 0, 0, ds, dd, dH, n);
+    A.ran();
+    A.back(H9, dH, (size_t)9 * n);
+    return (int)A.err;
+}
+// j6 n x 6 = j00 j01 j10 j11 p q; R1, R2 n x 9
+DU_API int du_pose_rotations(const double* j6, double* R1, double* R2, int n)
+{
+    if (n < 0) return (int)hipErrorInvalidValue;
+    Arena A;
+    const double* dj = A.dev(j6, (size_t)6 * n);
+    double *d1 = A.dev<double>(nullptr, (size_t)9 * n), *d2 = A.dev<double>(nullptr, (size_t)9 * n);
+    if (A.err == hipSuccess && n) hipLaunchKernelGGL(k_pose_rotations, grid_of(n), dim3(TPB), 0, 0, dj, d1, d2, n);
+    A.ran();
+    A.back(R1, d1, (size_t)9 * n);
+    A.back(R2, d2, (size_t)9 * n);
+    return (int)A.err;
+}
+DU_API int du_pose_translation(const double* obj8, const double* img8, const double* R9, double* t3, int n)
+{
+    if (n < 0) return (int)hipErrorInvalidValue;
+    Arena A;
+    const double *dobj = A.dev(obj8, (size_t)8 * n), *dimg = A.dev(img8, (size_t)8 * n), *dR = A.dev(R9, (size_t)9 * n);
+    double* dt = A.dev<double>(nullptr, (size_t)3 * n);
+    if (A.err == hipSuccess && n) hipLaunchKernelGGL(k_pose_translation, grid_of(n), dim3(TPB), 0, 0, dobj, dimg, dR, dt, n);
+    A.ran();
+    A.back(t3, dt, (size_t)3 * n);
+    return (int)A.err;
+}
+DU_API int du_pose_rot2vec(const double* R9, double* r3, int n)
+{
+    if (n < 0) return (int)hipErrorInvalidValue;
+    Arena A;
+    const double* dR = A.dev(R9, (size_t)9 * n);
+    double* dr = A.dev<double>(nullptr, (size_t)3 * n);
+    if (A.err == hipSuccess && n) hipLaunchKernelGGL(k_pose_rot2vec, grid_of(n), dim3(TPB), 0, 0, dR, dr, n);
+    A.ran();
+    A.back(r3, dr, (size_t)3 * n);
+    return (int)A.err;
+}
+// obj8, img8 n x 4 x 2 float (marker plane, pixels); err n
+DU_API int du_pose_reproj(const float* obj8, const float* img8, const double* cam17, const double* R9, const double* t3, float* err, int n)
+{
+    if (n < 0) return (int)hipErrorInvalidValue;
+    Arena A;
+    const float *dobj = A.dev(obj8, (size_t)8 * n), *dimg = A.dev(img8, (size_t)8 * n);
+    const double *dcam = A.dev(cam17, 17), *dR = A.dev(R9, (size_t)9 * n), *dt = A.dev(t3, (size_t)3 * n);
+    float* derr = A.dev<float>(nullptr, n);
+    if (A.err == hipSuccess && n) hipLaunchKernelGGL(k_pose_reproj, grid_of(n), dim3(TPB), 0, 0, dobj, dimg, dcam, dR, dt, derr, n);
+    A.ran();
+    A.back(err, derr, n);
+    return (int)A.err;
+}
+DU_API int du_pose_solve(const float* corners8, float size, const double* cam17, float* out14, int n)
+{
+    if (n < 0) return (int)hipErrorInvalidValue;
+    Arena A;
+    const float* dc = A.dev(corners8, (size_t)8 * n);
+    const double* dcam = A.dev(cam17, 17);
+    float* dout = A.dev<float>(nullptr, (size_t)14 * n);
+    if (A.err == hipSuccess && n) hipLaunchKernelGGL(k_pose_solve, grid_of(n), dim3(TPB), 0, 0, dc, size, dcam, dout, n);
+    A.ran();
+    A.back(out14, dout, (size_t)14 * n);
+    return (int)A.err;
+}
+DU_API int du_pose_solve_half(const float* corners8, float size, const double* cam17, int which, float* out7, int n)
+{
+    if (n < 0 || which < 0 || which > 1) return (int)hipErrorInvalidValue;
+    Arena A;
+    const float* dc = A.dev(corners8, (size_t)8 * n);
+    const double* dcam = A.dev(cam17, 17);
+    float* dout = A.dev<float>(nullptr, (size_t)7 * n);
+    if (A.err == hipSuccess && n) hipLaunchKernelGGL(k_pose_solve_half, grid_of(n), dim3(TPB), 0, 0, dc, size, dcam, which, dout, n);
+    A.ran();
+    A.back(out7, dout, (size_t)7 * n);
     return (int)A.err;
 }

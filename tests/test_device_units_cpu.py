@@ -234,7 +234,7 @@ def test_probe_compiles_for_gfx950_with_the_library_flags():
     subprocess.check_call(cmd)
     assert os.path.getsize(so) > 0
     names = subprocess.check_output(["nm", "-D", "--defined-only", so], text=True)
-    assert all(n in names for n in list(B._MATH) + list(B._DEVICE))
+    assert all(n in names for n in list(B._MATH) + list(B._DEVICE) + list(B._POSE)) and len(B._POSE) == 9
     # the probe is no part of the product library
     assert "device_units_probe.hip" not in entry.HIP_SOURCES
     lib = subprocess.check_output(["nm", "-D", "--defined-only", entry.LIB], text=True)
