@@ -26,6 +26,8 @@
  *                       Optimizer::PoseOptimization        src/Optimizer.cc:308-520, monocular
  *   orbfe_sim3_*        ORB_SLAM2::Sim3Solver              src/Sim3Solver.cc (LoopClosing.cc:402-425, :489-600)
  *   orbfe_optimize_sim3* Optimizer::OptimizeSim3           src/Optimizer.cc:1544-1739 (LoopClosing.cc:425, :580)
+ *   orbfe_create_new_map_points*, orbfe_new_points_*, orbfe_triangulate_matches_batch_device
+ *                       LocalMapping::CreateNewMapPoints   src/LocalMapping.cc:222-467, monocular (+ ComputeF12, :904-921)
  *
  * Memory convention: functions without a suffix take HOST pointers (drop-in for
  * the reference's call sites, which hand over cv::Mat / std::vector storage) and
@@ -783,6 +785,124 @@ int orbfe_search_for_triangulation_batch_device(const orbfe_keypoint* d_kps, con
                                                 const float* d_F12, const float* d_epipole, const float* scale_factors,
                                                 const float* level_sigma2, int nlevels, int check_orientation, int32_t* d_match12,
                                                 int32_t* d_scratch21, int32_t* d_nmatches, void* stream);
+
+/* ------------------------------------------------------------ local mapping: CreateNewMapPoints -- */
+/* LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:222-467), monocular: the geometry between the covisibility query and the
+ * object-graph lines :449-464.  Per neighbour keyframe: the baseline / median-depth gate (:259-276), ComputeF12 (:904-921), the
+ * epipole of SearchForTriangulation (src/ORBmatcher.cc:668-674), that search, and per match (:306-446) the ray-parallax gate, the
+ * 4 x 4 DLT (cv::SVD, CV_32F), two cheirality gates, two chi-square gates (5.991 sigma2) and the scale-consistency gate; for a point
+ * that passes, MapPoint::UpdateNormalAndDepth of a two-observation point whose reference keyframe is the current one
+ * (src/MapPoint.cc:359-400).  Numerics: OpenCV 3.4's for CV_32F -- Mat products and dot products accumulate in double and round
+ * once, cv::norm is a double sum of float squares and a double square root, 3 x 3 inverses are cofactor formulas in double, "m / s"
+ * multiplies by (float)(1. / s); a float error is compared against the double product 5.991 * sigma2.  OpenCV itself is not part
+ * of the tests: parity is against a CPU restatement of the same conventions (tests/new_points_ref.cpp).
+ *
+ * Resident layout, as the Sim3 and the triangulation-search calls: per-frame blocks of `capacity` entries of d_kps (mvKeysUn),
+ * d_x3Dw (x 3), d_valid ("has a map point"), d_free ("has no map point": the flags of the search) and d_n (clamped to the block, a
+ * negative count is 0); d_Tcw 12 floats a frame (3 x 4 row-major); pair p is the current keyframe d_pair1[p] (side 1) against the
+ * neighbour d_pair2[p] (NULL index arrays: p and p + 1); K4 = fx, fy, cx, cy, one for both sides; the level tables
+ * (mvScaleFactors, mvLevelSigma2, nlevels <= 16) on the host.
+ *
+ * Status byte per side-1 feature (ORBFE_NMP_*): 0 no match, 1 created, 2 parallax gate (!(cos > 0 && cos < 0.9998)), 3 w == 0,
+ * 4 a point that is not finite, 5 z1 <= 0, 6 z2 <= 0, 7 reprojection error in keyframe 1, 8 in keyframe 2, 9 a zero distance,
+ * 10 scale consistency.
+ *
+ * Where the reference is undefined:
+ *   - a neighbour with no map point (the reference reads vDepths[-1 / 2] of an empty vector): the pair is skipped, median_depth 0;
+ *   - a triangulated point that is not finite would pass every comparison (NaN compares false) and become a map point: it is
+ *     rejected with status 4.  A STATED DEVIATION from the reference;
+ *   - an octave outside [0, nlevels) on a matched feature: the pair's record has status ORBFE_ERR_INVALID and every other field 0,
+ *     nothing else of that pair is written (status bytes, outputs, map state); the other pairs of the call are unaffected;
+ *   - a match12 entry outside [-1, d_n[f2]) counts as no match. */
+#define ORBFE_NMP_NO_MATCH 0
+#define ORBFE_NMP_CREATED 1
+#define ORBFE_NMP_PARALLAX 2
+#define ORBFE_NMP_W_ZERO 3
+#define ORBFE_NMP_NOT_FINITE 4
+#define ORBFE_NMP_Z1 5
+#define ORBFE_NMP_Z2 6
+#define ORBFE_NMP_REPROJECTION1 7
+#define ORBFE_NMP_REPROJECTION2 8
+#define ORBFE_NMP_ZERO_DISTANCE 9
+#define ORBFE_NMP_SCALE 10
+
+typedef struct orbfe_new_points_pair {
+    float   baseline;           /* cv::norm(Ow2 - Ow1) */
+    float   median_depth;       /* pKF2->ComputeSceneMedianDepth(2): the (m - 1) / 2-th smallest depth; 0 when m = 0 */
+    int32_t n_depths;           /* m: features of the neighbour with a map point */
+    int32_t skipped;            /* 1: baseline / median_depth < 0.01 (the reference's `continue`), or m = 0 */
+} orbfe_new_points_pair;
+
+typedef struct orbfe_new_points_result {
+    int32_t n_matches;          /* entries of the pair's match12 inside [0, d_n[f2]): vMatchedIndices.size() */
+    int32_t n_new;              /* nnew of this neighbour: status bytes equal to 1 */
+    int32_t status;             /* ORBFE_OK, or ORBFE_ERR_INVALID for a pair that was not processed (see above) */
+} orbfe_new_points_result;
+
+/* The gate and the inputs of the search, for npairs pairs in one launch (one workgroup per pair): d_prep[p], d_F12 (npairs x 9,
+ * row-major) and d_epipole (npairs x 2) as orbfe_search_for_triangulation_batch_device reads them.  The depths are
+ * z = (float)(Tcw2 row 2 . x3Dw in double + (double)zcw) over the neighbour's features with d_valid != 0 (NULL = all); the gate
+ * compares (double)(baseline / median_depth) < 0.01.  A skipped pair gets an all-zero F12 and epipole: the search then finds no match
+ * and the triangulation has nothing to do, so a chain needs no host decision.  Asynchronous on `stream`, no scratch. */
+int orbfe_new_points_prepare_batch_device(const int32_t* d_n, int capacity, const float* d_x3Dw, const uint8_t* d_valid, const float* d_Tcw,
+                                          const int32_t* d_pair1, const int32_t* d_pair2, int npairs, const float* K4, float* d_F12,
+                                          float* d_epipole, orbfe_new_points_pair* d_prep, void* stream);
+
+/* Lines :306-446 for every match of npairs pairs in one launch (one thread per side-1 feature).  d_match12: blocks of `capacity`
+ * per pair, match12[i1] = i2 or -1, as the search writes them.  Outputs, blocks of `capacity` per pair, slot i1 (ascending i1 is
+ * the reference's creation order, ORBmatcher.cc:816-824): d_status (the first d_n[f1] bytes are written), and for status 1 d_x3D (x 3),
+ * d_normal (x 3: mNormalVector) and d_dist (x 2: mfMaxDistance, mfMinDistance); the slots of other codes are left alone.  d_res[p]
+ * is always written.
+ * The map state is updated in place where status is 1, and nowhere else: d_free[f1][i1] = d_free[f2][i2] = 0, d_valid[..] = 1,
+ * d_x3Dw[..] = x3D (the three arrays are all given or all NULL: outputs only).  Within one pair i1 and i2 are each unique, so these
+ * writes do not race.  ALL PAIRS OF ONE CALL SEE THE MATCH LISTS AS THEY WERE GIVEN: two pairs of one call that share a frame may
+ * both create a point on the same feature, and which of the two the state arrays then hold is not defined.  The reference's
+ * sequential order -- a feature that received a point from neighbour p is no longer free for neighbour p + 1 -- is what
+ * orbfe_create_new_map_points_device is for.  The call itself does not read the state arrays.
+ * Asynchronous on `stream` (one memset of d_res and one launch), no host synchronisation, no scratch. */
+int orbfe_triangulate_matches_batch_device(const orbfe_keypoint* d_kps, const int32_t* d_n, int capacity, float* d_x3Dw, uint8_t* d_valid,
+                                           uint8_t* d_free, const float* d_Tcw, const int32_t* d_pair1, const int32_t* d_pair2, int npairs,
+                                           const int32_t* d_match12, const float* K4, const float* scale_factors, const float* level_sigma2,
+                                           int nlevels, float ratio_factor, uint8_t* d_status, float* d_x3D, float* d_normal, float* d_dist,
+                                           orbfe_new_points_result* d_res, void* stream);
+
+/* The product call: CreateNewMapPoints of resident keyframes.  One orbfe_new_points_prepare_batch_device over all pairs (on the
+ * state at entry), then STRICTLY IN LIST ORDER, per pair: orbfe_search_for_triangulation_batch_device on that one pair (with d_free
+ * as it is by then) and the triangulation of that pair, which clears d_free where it created a point -- the reference's skip of
+ * ORBmatcher.cc:710-714 for the next neighbour.  Everything is enqueued on `stream` with no host synchronisation:
+ * 1 + npairs x (1 search launch + 1) kernel launches (41 for 20 neighbours), one memset.  The per-frame arrays of the search
+ * (d_desc, the FeatureVector blocks d_fv_node / d_fv_offset (capacity + 1 a frame) / d_fv_feature / d_nfv) and its outputs
+ * d_match12, d_scratch21 (capacity ints a pair) and d_nmatches are those of that call; every other argument is that of the two
+ * calls above.  The caller ends the pair list where CheckNewKeyFrames() would return, and passes ratio_factor = 1.5f * mfScaleFactor. */
+int orbfe_create_new_map_points_device(const orbfe_keypoint* d_kps, const uint8_t* d_desc, const int32_t* d_n, const uint32_t* d_fv_node,
+                                       const int32_t* d_fv_offset, const uint32_t* d_fv_feature, const int32_t* d_nfv, int capacity,
+                                       float* d_x3Dw, uint8_t* d_valid, uint8_t* d_free, const float* d_Tcw, const int32_t* d_pair1,
+                                       const int32_t* d_pair2, int npairs, const float* K4, const float* scale_factors,
+                                       const float* level_sigma2, int nlevels, float ratio_factor, int check_orientation, float* d_F12,
+                                       float* d_epipole, orbfe_new_points_pair* d_prep, int32_t* d_match12, int32_t* d_scratch21,
+                                       int32_t* d_nmatches, uint8_t* d_status, float* d_x3D, float* d_normal, float* d_dist,
+                                       orbfe_new_points_result* d_res, void* stream);
+
+/* One neighbour, host pointers: both keyframes are staged once, prepare, search and triangulation run on the stage, one download.
+ * Side k: kps, descriptors, its FeatureVector (orbfe_vocabulary_transform), x3Dw (n x 3) and valid (n; 1 = has a map point) -- both
+ * IN / OUT: a created point is written to both sides -- and Tcw.  Outputs, n1 entries: match12, status, x3D, normal, dist (x 2);
+ * F12 (9), epipole (2), prep and res.  The caller walks the neighbours in order and hands the current keyframe's x3Dw / valid from
+ * call to call: that is the sequence of the device chain. */
+int orbfe_create_new_map_points(const orbfe_keypoint* kps1, const uint8_t* desc1, int n1, const uint32_t* fv_node1, const int32_t* fv_offset1,
+                                const uint32_t* fv_feature1, int nfv1, float* x3Dw1, uint8_t* valid1, const float* Tcw1,
+                                const orbfe_keypoint* kps2, const uint8_t* desc2, int n2, const uint32_t* fv_node2, const int32_t* fv_offset2,
+                                const uint32_t* fv_feature2, int nfv2, float* x3Dw2, uint8_t* valid2, const float* Tcw2, const float* K4,
+                                const float* scale_factors, const float* level_sigma2, int nlevels, float ratio_factor, int check_orientation,
+                                float* F12, float* epipole, orbfe_new_points_pair* prep, int32_t* match12, uint8_t* status, float* x3D,
+                                float* normal, float* dist, orbfe_new_points_result* res, int device);
+
+/* DIAGNOSTIC / TEST INTERFACE, no stability promise: the triangulation of one pair's given match list with its gate quantities
+ * (the parity tests).  No map state.  quantities: n1 x 6 = cosParallaxRays, the squared reprojection errors in keyframe 1 and 2,
+ * dist1, dist2, ratioOctave; a quantity behind the gate that rejected the match is 0.  The other outputs as above. */
+int orbfe_new_points_inspect(const orbfe_keypoint* kps1, int n1, const float* Tcw1, const orbfe_keypoint* kps2, int n2, const float* Tcw2,
+                             const int32_t* match12, const float* K4, const float* scale_factors, const float* level_sigma2, int nlevels,
+                             float ratio_factor, uint8_t* status, float* x3D, float* normal, float* dist, float* quantities,
+                             orbfe_new_points_result* res, int device);
 
 /* ------------------------------------------------------------ KeyFrameDatabase: candidate queries -- */
 /* KeyFrameDatabase::DetectLoopCandidates(pKF, minScore) (src/KeyFrameDatabase.cc:76-197, called by LoopClosing::DetectLoop) and

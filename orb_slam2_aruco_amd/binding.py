@@ -66,6 +66,9 @@ SYMBOLS = [
     # the candidate queries of KeyFrameDatabase and DBoW2's L1 score (csrc/keyframe_db.hip)
     "orbfe_detect_candidates", "orbfe_detect_candidates_batch_device", "orbfe_bow_min_score_batch_device",
     "orbfe_bow_score", "orbfe_bow_score_batch_device",
+    # the geometry of LocalMapping::CreateNewMapPoints (csrc/new_map_points.hip)
+    "orbfe_new_points_prepare_batch_device", "orbfe_triangulate_matches_batch_device", "orbfe_create_new_map_points_device",
+    "orbfe_create_new_map_points", "orbfe_new_points_inspect",
 ]
 
 _lib = None
@@ -218,6 +221,13 @@ def load():
         L.orbfe_bow_min_score_batch_device.argtypes = [i32, vp, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp]
         L.orbfe_bow_score.argtypes = [i32, vp, vp, vp, i32, vp, vp, i32, vp, i32]
         L.orbfe_bow_score_batch_device.argtypes = [i32, vp, vp, vp, i32, vp, vp, i32, vp, vp]
+    if hasattr(L, "orbfe_create_new_map_points"):
+        L.orbfe_new_points_prepare_batch_device.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
+        L.orbfe_triangulate_matches_batch_device.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, f32] + [vp] * 6
+        L.orbfe_create_new_map_points_device.argtypes = [vp] * 7 + [i32] + [vp] * 6 + [i32, vp, vp, vp, i32, f32, i32] + [vp] * 12
+        side = [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp]
+        L.orbfe_create_new_map_points.argtypes = side + side + [vp, vp, vp, i32, f32, i32] + [vp] * 9 + [i32]
+        L.orbfe_new_points_inspect.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, f32] + [vp] * 6 + [i32]
     if hasattr(L, "orbfe_initialize"):
         L.orbfe_initialize.argtypes = [vp, i32, vp, i32, vp, vp, f32, i32, vp, vp, vp, vp, i32]
         L.orbfe_initialize_inspect.argtypes = [vp, i32, vp, i32, vp, vp, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
@@ -1182,6 +1192,81 @@ def search_for_triangulation(kps1, desc1, fv1, kps2, desc2, fv2, F12, epipole, s
                                                _p(F), np.float32(epipole[0]), np.float32(epipole[1]), _p(sf), _p(sg), len(sf),
                                                int(check_orientation), _p(m12), C.byref(nm), device), "orbfe_search_for_triangulation")
     return nm.value, m12
+
+
+NEW_POINTS_PAIR_DTYPE = np.dtype([("baseline", np.float32), ("median_depth", np.float32), ("n_depths", np.int32), ("skipped", np.int32)])
+NEW_POINTS_RESULT_DTYPE = np.dtype([("n_matches", np.int32), ("n_new", np.int32), ("status", np.int32)])
+NMP_CREATED = 1
+
+
+def _tcw12(T):
+    return np.ascontiguousarray(np.asarray(T, np.float32).reshape(-1, 4)[:3], np.float32).reshape(12)
+
+
+def _new_points_keyframe(kf):
+    """a keyframe of create_new_map_points as contiguous arrays: kps, desc, fv (node, offset, feature), x3Dw, valid, Tcw"""
+    k = np.ascontiguousarray(kf["kps"], KP_DTYPE)
+    d = np.ascontiguousarray(kf["desc"], np.uint8).reshape(-1, 32)
+    fv = [np.ascontiguousarray(kf["fv"][0], np.uint32), np.ascontiguousarray(kf["fv"][1], np.int32), np.ascontiguousarray(kf["fv"][2], np.uint32)]
+    x = np.array(kf["x3Dw"], np.float32).reshape(-1, 3)
+    v = (np.asarray(kf["valid"]).reshape(-1) != 0).astype(np.uint8)
+    if not (len(k) == len(d) == len(x) == len(v)):
+        raise ValueError("a keyframe's arrays differ in length")
+    return dict(kps=k, desc=d, fv=fv, x3Dw=x, valid=v, Tcw=_tcw12(kf["Tcw"]))
+
+
+def create_new_map_points(cur, neighbours, K, scale_factors, level_sigma2, ratio_factor=None, check_orientation=False, device=0):
+    """LocalMapping::CreateNewMapPoints (LocalMapping.cc:222-467, monocular) of the keyframe `cur` against `neighbours`, in list
+    order.  A keyframe is a dict: kps (mvKeysUn, KP_DTYPE), desc (n x 32), fv (node, offset, feature: the FeatureVector), x3Dw
+    (n x 3), valid (n; has a map point), Tcw (3 x 4 or 4 x 4).  K: 3 x 3 or fx, fy, cx, cy.  ratio_factor defaults to
+    1.5f * scale_factors[1].  The inputs are not changed.  Returns (list with one dict per neighbour: i1, i2, x3D, normal,
+    max_distance, min_distance of the created points in ascending i1, status (n1 bytes), match12, F12, epipole, prep, result;
+    the current keyframe's (x3Dw, valid) after the last neighbour)."""
+    L = load()
+    c = _new_points_keyframe(cur)
+    Kf = np.asarray(K, np.float32)
+    K4 = np.ascontiguousarray([Kf[0, 0], Kf[1, 1], Kf[0, 2], Kf[1, 2]] if Kf.size == 9 else Kf.reshape(4), np.float32)
+    sf = np.ascontiguousarray(scale_factors, np.float32); sg = np.ascontiguousarray(level_sigma2, np.float32)
+    if len(sf) != len(sg):
+        raise ValueError("scale_factors and level_sigma2 differ in length")
+    rf = float(np.float32(1.5) * sf[min(1, len(sf) - 1)]) if ratio_factor is None else float(ratio_factor)
+    n1 = len(c["kps"])
+    out = []
+    for nb in neighbours:
+        b = _new_points_keyframe(nb)
+        F12 = np.zeros(9, np.float32); ep = np.zeros(2, np.float32)
+        prep = np.zeros(1, NEW_POINTS_PAIR_DTYPE); res = np.zeros(1, NEW_POINTS_RESULT_DTYPE)
+        m12 = np.full(n1, -1, np.int32); status = np.zeros(n1, np.uint8)
+        x3D = np.zeros((n1, 3), np.float32); normal = np.zeros((n1, 3), np.float32); dist = np.zeros((n1, 2), np.float32)
+        side = lambda f: [_ptr_or_none(f["kps"]), _ptr_or_none(f["desc"]), len(f["kps"]), _ptr_or_none(f["fv"][0]), _ptr_or_none(f["fv"][1]),
+                          _ptr_or_none(f["fv"][2]), len(f["fv"][0]), _ptr_or_none(f["x3Dw"]), _ptr_or_none(f["valid"]), _p(f["Tcw"])]
+        _check(L, L.orbfe_create_new_map_points(*(side(c) + side(b) + [_p(K4), _p(sf), _p(sg), len(sf), rf, int(bool(check_orientation)),
+                                                                        _p(F12), _p(ep), _p(prep), _ptr_or_none(m12), _ptr_or_none(status),
+                                                                        _ptr_or_none(x3D), _ptr_or_none(normal), _ptr_or_none(dist), _p(res), device])),
+               "orbfe_create_new_map_points")
+        i1 = np.flatnonzero(status == NMP_CREATED)
+        out.append(dict(i1=i1, i2=m12[i1], x3D=x3D[i1], normal=normal[i1], max_distance=dist[i1, 0], min_distance=dist[i1, 1], status=status,
+                        match12=m12, F12=F12.reshape(3, 3), epipole=ep, prep=prep[0], result=res[0], x3Dw2=b["x3Dw"], valid2=b["valid"]))
+    return out, (c["x3Dw"], c["valid"])
+
+
+def new_points_inspect(kps1, Tcw1, kps2, Tcw2, match12, K4, scale_factors, level_sigma2, ratio_factor, device=0):
+    """orbfe_new_points_inspect (diagnostic): the triangulation of a given match list with its gate quantities ->
+    dict(status, x3D, normal, dist, quantities (n1 x 6: cos, err1, err2, dist1, dist2, ratioOctave), result)."""
+    L = load()
+    k1 = np.ascontiguousarray(kps1, KP_DTYPE); k2 = np.ascontiguousarray(kps2, KP_DTYPE)
+    m12 = np.ascontiguousarray(match12, np.int32)
+    if len(m12) != len(k1):
+        raise ValueError("match12 has %d entries for %d keypoints" % (len(m12), len(k1)))
+    sf = np.ascontiguousarray(scale_factors, np.float32); sg = np.ascontiguousarray(level_sigma2, np.float32)
+    K = np.ascontiguousarray(K4, np.float32).reshape(4)
+    n1 = len(k1)
+    status = np.zeros(n1, np.uint8); x3D = np.zeros((n1, 3), np.float32); normal = np.zeros((n1, 3), np.float32)
+    dist = np.zeros((n1, 2), np.float32); q = np.zeros((n1, 6), np.float32); res = np.zeros(1, NEW_POINTS_RESULT_DTYPE)
+    _check(L, L.orbfe_new_points_inspect(_ptr_or_none(k1), n1, _p(_tcw12(Tcw1)), _ptr_or_none(k2), len(k2), _p(_tcw12(Tcw2)), _ptr_or_none(m12),
+                                         _p(K), _p(sf), _p(sg), len(sf), float(ratio_factor), _ptr_or_none(status), _ptr_or_none(x3D),
+                                         _ptr_or_none(normal), _ptr_or_none(dist), _ptr_or_none(q), _p(res), device), "orbfe_new_points_inspect")
+    return dict(status=status, x3D=x3D, normal=normal, dist=dist, quantities=q, result=res[0])
 
 
 class ORBVocabulary:

@@ -1,0 +1,424 @@
+"""GPU: orbfe_new_points_prepare_batch_device, orbfe_triangulate_matches_batch_device, orbfe_create_new_map_points_device and the
+host-pointer calls against the CPU restatement (tests/new_points_ref.cpp + the oracle's SearchForTriangulation).  The parity contract
+(DESIGN.md 4g): prepare is bit-exact; the cosine agrees within 1e-6; status bytes are equal except where a gate quantity of the
+restatement lies inside a band (at most 5 % of a case's matches); created points agree within 1e-4 relative; counts and state are exact
+when no match lies inside a band.  capacity = 512, at most 6 pairs a call, poison in every buffer, guard bytes around every output."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import new_points_cases as nc
+from orb_slam2_aruco_amd import binding as orbfe
+from pose_opt_device import Dev, Out
+
+pytestmark = pytest.mark.gpu
+
+CAP = nc.CAPACITY
+POISON_F = np.array([0x7FC0DEAD], np.uint32).view(np.float32)[0]
+ERR_INVALID = orbfe.ORBFE_ERR_INVALID
+
+
+def lib():
+    return orbfe.load()
+
+
+def ok(rc):
+    assert rc == 0, lib().orbfe_last_error().decode()
+
+
+def cp(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def same_bytes(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
+
+
+def fpoison(*shape):
+    return np.full(shape, POISON_F, np.float32)
+
+
+class Batch:
+    """frames as resident blocks, a pair list (None: pairs p, p + 1) and poisoned outputs for `npairs` pairs"""
+
+    def __init__(self, frames, pairs, npairs=None, n_claim=None, search=False):
+        self.frames, self.pairs = frames, pairs
+        self.npairs = len(pairs) if pairs is not None else npairs
+        P = self.P = nc.pack_frames(frames, CAP)
+        if n_claim:
+            for f, n in n_claim.items():
+                P["n"][f] = n
+        self.kps, self.n, self.T = Dev(P["kps"]), Dev(P["n"]), Dev(P["Tcw"])
+        self.x, self.valid, self.free = Out(P["x3Dw"]), Out(P["valid"]), Out(P["free"])
+        self.p1 = Dev(np.array([a for a, _ in pairs], np.int32)) if pairs is not None else None
+        self.p2 = Dev(np.array([b for _, b in pairs], np.int32)) if pairs is not None else None
+        n = self.npairs
+        self.status = Out(np.full((n, CAP), 0xDD, np.uint8))
+        self.x3D, self.normal, self.dist = Out(fpoison(n, CAP, 3)), Out(fpoison(n, CAP, 3)), Out(fpoison(n, CAP, 2))
+        self.res = Out(np.full(n * 3, -7, np.int32).view(nc.RESULT_DTYPE))
+        self.F12, self.epi = Out(fpoison(n, 9)), Out(fpoison(n, 2))
+        self.prep = Out(np.full(n * 4, -7, np.int32).view(nc.PAIR_DTYPE))
+        if search:
+            self.desc, self.fn, self.fo, self.ff, self.nfv = Dev(P["desc"]), Dev(P["fn"]), Dev(P["fo"]), Dev(P["ff"]), Dev(P["nfv"])
+            self.m12, self.s21, self.nm = Out(np.full((n, CAP), -77, np.int32)), Out(np.full((n, CAP), -77, np.int32)), Out(np.full(n, -77, np.int32))
+
+    def pair(self, p):
+        return self.pairs[p] if self.pairs is not None else (p, p + 1)
+
+    def pp(self, d):
+        return None if d is None else d.ptr
+
+    def prepare(self, with_valid=True):
+        ok(lib().orbfe_new_points_prepare_batch_device(self.n.ptr, CAP, self.x.ptr, self.valid.ptr if with_valid else None, self.T.ptr,
+                                                       self.pp(self.p1), self.pp(self.p2), self.npairs, cp(nc.K4), self.F12.ptr, self.epi.ptr,
+                                                       self.prep.ptr, None))
+        return self.F12.get(), self.epi.get(), self.prep.get()
+
+    def triangulate(self, m12_blocks, state=True, nlevels=nc.NLEVELS):
+        blocks = np.full((self.npairs, CAP), -1, np.int32)
+        for p, m in enumerate(m12_blocks):
+            blocks[p, :len(m)] = m
+            blocks[p, len(m):] = 3                       # behind a frame's rows: a valid-looking index that must not be read
+        self.m12_in = Dev(blocks)
+        ok(lib().orbfe_triangulate_matches_batch_device(
+            self.kps.ptr, self.n.ptr, CAP, self.x.ptr if state else None, self.valid.ptr if state else None, self.free.ptr if state else None,
+            self.T.ptr, self.pp(self.p1), self.pp(self.p2), self.npairs, self.m12_in.ptr, cp(nc.K4), cp(nc.SCALE), cp(nc.SIGMA2), nlevels,
+            nc.RATIO, self.status.ptr, self.x3D.ptr, self.normal.ptr, self.dist.ptr, self.res.ptr, None))
+        return self.outputs()
+
+    def chain(self, check_orientation=False):
+        ok(lib().orbfe_create_new_map_points_device(
+            self.kps.ptr, self.desc.ptr, self.n.ptr, self.fn.ptr, self.fo.ptr, self.ff.ptr, self.nfv.ptr, CAP, self.x.ptr, self.valid.ptr,
+            self.free.ptr, self.T.ptr, self.pp(self.p1), self.pp(self.p2), self.npairs, cp(nc.K4), cp(nc.SCALE), cp(nc.SIGMA2), nc.NLEVELS,
+            nc.RATIO, int(check_orientation), self.F12.ptr, self.epi.ptr, self.prep.ptr, self.m12.ptr, self.s21.ptr, self.nm.ptr,
+            self.status.ptr, self.x3D.ptr, self.normal.ptr, self.dist.ptr, self.res.ptr, None))
+        return self.outputs()
+
+    def outputs(self):
+        st, x, nr, di, res = self.status.get(), self.x3D.get(), self.normal.get(), self.dist.get(), self.res.get()
+        return [dict(status=st[p], x3D=x[p], normal=nr[p], dist=di[p], result=res[p]) for p in range(self.npairs)]
+
+    def check_untouched_outputs(self, outs):
+        """status bytes behind a pair's n1 and the slots of every code but 1 are as they were"""
+        for p, o in enumerate(outs):
+            n1 = int(np.clip(self.P["n"][self.pair(p)[0]], 0, CAP))
+            assert np.all(o["status"][n1:] == 0xDD)
+            made = np.zeros(CAP, bool); made[:n1] = o["status"][:n1] == 1
+            for key in ("x3D", "normal", "dist"):
+                assert same_bytes(o[key][~made], fpoison(*o[key][~made].shape)), (p, key)
+                assert np.all(np.isfinite(o[key][made])), (p, key)
+
+    def check_state(self, outs, m12_blocks):
+        """d_free, d_valid, d_x3Dw changed exactly where a pair created a point, to that pair's point; every other byte -- the padding
+        between d_n and capacity included -- is as it was"""
+        x, valid, free = self.P["x3Dw"].copy(), self.P["valid"].copy(), self.P["free"].copy()
+        for p, (o, m) in enumerate(zip(outs, m12_blocks)):
+            a, b = self.pair(p)
+            i1 = np.flatnonzero(o["status"][:len(m)] == 1)
+            i2 = np.asarray(m)[i1]
+            for f, i in ((a, i1), (b, i2)):
+                x[f, i] = o["x3D"][i1]; valid[f, i] = 1; free[f, i] = 0
+        assert same_bytes(self.valid.get(), valid) and same_bytes(self.free.get(), free)
+        assert same_bytes(self.x.get(), x)
+
+
+# ------------------------------------------------------------------------------------------------------------ parity
+@pytest.mark.parametrize("name", list(nc.PARITY_CASES))
+def test_triangulate_parity(name):
+    sc, m12, want = nc.parity_case(name)
+    f0, f1 = sc["frames"]
+    b = Batch(sc["frames"], None, npairs=1)
+    got = b.triangulate([m12])
+    excluded = nc.compare_pair(got[0], want, f0["kps"], f1["kps"], m12, name)
+    b.check_untouched_outputs(got)
+    b.check_state(got, [m12])
+    # the cosine gate's quantity, through the inspect call (which must give the device call's bytes)
+    ins = orbfe.new_points_inspect(f0["kps"], f0["Tcw"], f1["kps"], f1["Tcw"], m12, nc.K4, nc.SCALE, nc.SIGMA2, nc.RATIO)
+    assert np.array_equal(ins["status"], got[0]["status"]) and tuple(ins["result"]) == tuple(got[0]["result"])
+    made = ins["status"] == 1
+    assert same_bytes(ins["x3D"][made], got[0]["x3D"][made]) and same_bytes(ins["dist"][made], got[0]["dist"][made])
+    has = m12 >= 0
+    dcos = np.abs(ins["quantities"][has, 0].astype(np.float64) - want["quantities"][has, 0])
+    print("%s: cosParallaxRays differs by at most %.3g" % (name, dcos.max()))
+    assert dcos.max() <= 1e-6
+    if excluded == 0:
+        # the flags exactly the restatement's; the points are the device's own (check_state) and within 1e-4 of the restatement's
+        st = [np.array(f["valid"], np.uint8) for f in (f0, f1)]
+        r = nc.ref_triangulate(f0["kps"], f0["Tcw"], f1["kps"], f1["Tcw"], m12, (np.array(f0["x3Dw"]), st[0], np.array(f1["x3Dw"]), st[1]))
+        valid, free = b.valid.get(), b.free.get()
+        for f in range(2):
+            assert np.array_equal(valid[f], st[f]) and np.array_equal(free[f], (st[f] == 0).astype(np.uint8)), f
+        assert tuple(got[0]["result"]) == tuple(r["result"])
+
+
+EDGE_GROUPS = {"counts-0-to-257": nc.EDGE_COUNTS[:6], "full-empty-ragged": (512,)}
+
+
+@pytest.mark.parametrize("group", list(EDGE_GROUPS))
+def test_triangulate_edges(group):
+    """match counts 0, 1, 63, 64, 65, 257, 512 a pair (wave and workgroup boundaries), a list of -1 only, and ragged d_n: an empty
+    frame on either side, a count above capacity (clamped), a neighbour of 200 features whose higher indices count as no match"""
+    sc = nc.edge_case(512)[0]
+    f0, f1 = sc["frames"]
+    if group == "counts-0-to-257":
+        cases = [nc.edge_case(c) for c in EDGE_GROUPS[group]]
+        b = Batch([f0, f1], [(0, 1)] * len(cases))
+        lists = [m for _, m, _ in cases]
+        wants = [w for _, _, w in cases]
+        k2 = [f1["kps"]] * len(cases)
+        got = b.triangulate(lists, state=False)
+    else:
+        m = nc.edge_case(512)[1]
+        empty = dict(kps=f0["kps"][:0], Tcw=f0["Tcw"])
+        short = dict(kps=f1["kps"][:200], Tcw=f1["Tcw"])
+        frames = [f0, f1, empty, dict(f0), short]
+        pairs = [(0, 1), (0, 1), (2, 1), (0, 2), (3, 1), (0, 4)]
+        lists = [m, np.full(CAP, -1, np.int32), np.zeros(0, np.int32), m, m, m]
+        b = Batch(frames, pairs, n_claim={3: CAP + 5})
+        k2 = [f1["kps"], f1["kps"], f1["kps"], empty["kps"], f1["kps"], short["kps"]]
+        wants = [nc.ref_triangulate(frames[a]["kps"], frames[a]["Tcw"], frames[c]["kps"], frames[c]["Tcw"], l) for (a, c), l in zip(pairs, lists)]
+        assert [int(w["result"]["n_matches"]) for w in wants] == [512, 0, 0, 0, 512, int((m < 200).sum())]
+        got = b.triangulate(lists, state=False)
+    for p, (g, w, l) in enumerate(zip(got, wants, lists)):
+        a = b.pair(p)[0]
+        nc.compare_pair(g, w, b.frames[a]["kps"], k2[p], l, "%s pair %d" % (group, p))
+    b.check_untouched_outputs(got)
+    # no state arrays were given: nothing of them may have been touched
+    assert same_bytes(b.x.get(), b.P["x3Dw"]) and same_bytes(b.valid.get(), b.P["valid"]) and same_bytes(b.free.get(), b.P["free"])
+
+
+def test_every_status_code():
+    c = nc.every_code_case()
+    frames = [dict(kps=k, Tcw=T) for k, T in zip(c["kps"], c["Tcw"])]
+    b = Batch(frames, c["pairs"])
+    got = b.triangulate(c["match12"])
+    seen = set()
+    for p, ((a, d), m) in enumerate(zip(c["pairs"], c["match12"])):
+        w = nc.ref_triangulate(c["kps"][a], c["Tcw"][a], c["kps"][d], c["Tcw"][d], m)
+        assert got[p]["status"][:c["n"]].tolist() == w["status"].tolist(), p
+        assert tuple(got[p]["result"]) == tuple(w["result"]), p
+        seen |= set(got[p]["status"][:c["n"]].tolist())
+    assert seen == set(range(11))
+    b.check_untouched_outputs(got)
+    # 10 features in blocks of 512, every state byte poisoned: only the created point's two slots change
+    b.check_state(got, c["match12"])
+
+
+# ------------------------------------------------------------------------------------------------------------ prepare
+def _depth_frame(rng, T, depths, nvalid_extra=7):
+    """a frame whose valid features have exactly these depths in camera T, hidden among invalid features with other depths"""
+    n = len(depths) + nvalid_extra
+    order = rng.permutation(n)
+    z = np.r_[np.asarray(depths, np.float64), rng.uniform(-50, 50, nvalid_extra)]
+    xy = rng.uniform(-1, 1, (n, 2))
+    Xc = np.c_[xy * z[:, None], z]
+    R, t = T[:, :3].astype(np.float64), T[:, 3].astype(np.float64)
+    Xw = (Xc - t) @ R
+    valid = np.r_[np.ones(len(depths), np.uint8), np.zeros(nvalid_extra, np.uint8)]
+    return dict(kps=nc.keypoints(np.zeros((n, 2), np.float32), np.zeros(n, np.int64)), Tcw=T, x3Dw=Xw[order].astype(np.float32), valid=valid[order])
+
+
+def test_prepare_is_bit_exact():
+    """F12, the epipole, the baseline, the median depth and the skip flag against the restatement, bit for bit: a neighbour just below
+    and just above the 0.01 ratio, one without a map point, neighbours with 1, 2, 5 and 6 depths (the (m - 1) / 2 index), duplicate
+    depths, negative depths (the order of the keys), a general scene of 512 features, and d_valid = NULL"""
+    rng = np.random.default_rng(5)
+    cur = dict(kps=nc.keypoints(np.zeros((1, 2), np.float32), [0]), Tcw=nc.tcw(np.eye(3), [0, 0, 0]), x3Dw=np.zeros((1, 3), np.float32),
+               valid=np.zeros(1, np.uint8))
+
+    def nb(baseline, depths, deg=3.0):
+        R = nc.rot(rng.normal(size=3), deg)
+        c = np.array([baseline, 0, 0.0])
+        return _depth_frame(rng, nc.tcw(R, -R @ c), depths)
+
+    groups = [
+        [nb(0.0999, [10.0] * 9), nb(0.1001, [10.0] * 9), nb(0.3, []), nb(0.3, [4.0]), nb(0.3, [6.0, 2.0]), nb(0.3, [5, 1, 4, 2, 3.0])],
+        [nb(0.3, [5, 1, 4, 2, 3, 6.0]), nb(0.3, [2, 2, 2, 7, 7, 1.0]), nb(0.3, [-4, -1, -3, -2.0]), nb(0.3, [-2, 3, -5, 0.5, 1.0]),
+         nc.chain_scene()["frames"][1], nc.chain_scene()["frames"][2]],
+    ]
+    for g, nbs in enumerate(groups):
+        frames = [cur] + nbs
+        b = Batch(frames, [(0, p) for p in range(1, len(frames))])
+        F, e, rec = b.prepare()
+        for p, f in enumerate(nbs):
+            wF, we, wrec = nc.ref_prepare(cur, f)
+            label = "group %d pair %d" % (g, p)
+            assert same_bytes(rec[p:p + 1], np.array([wrec], nc.PAIR_DTYPE)), (label, rec[p], wrec)
+            assert same_bytes(F[p], wF) and same_bytes(e[p], we), (label, F[p], wF, e[p], we)
+            if wrec["skipped"]:
+                assert not F[p].any() and not e[p].any()
+            else:
+                assert F[p].any()
+        if g == 0:
+            assert rec["skipped"].tolist() == [1, 0, 1, 0, 0, 0] and rec["n_depths"].tolist() == [9, 9, 0, 1, 2, 5]
+            assert np.allclose(rec["median_depth"][3:], [4, 2, 3], rtol=1e-5)      # the lower median of 2, the middle of 5
+    # d_valid = NULL: every feature counts (the poisoned rows behind d_n do not)
+    frames = [cur, groups[1][0]]
+    b = Batch(frames, None, npairs=1)
+    _, _, rec = b.prepare(with_valid=False)
+    f = dict(frames[1], valid=np.ones(len(frames[1]["valid"]), np.uint8))
+    assert same_bytes(rec[0:1], np.array([nc.ref_prepare(cur, f)[2]], nc.PAIR_DTYPE))
+
+
+# ------------------------------------------------------------------------------------------------------------ the chain
+def _compare_chain(b, got, want, frames, pairs):
+    F, e, rec, m12, nm = b.F12.get(), b.epi.get(), b.prep.get(), b.m12.get(), b.nm.get()
+    clean = True
+    for p, (a, c) in enumerate(pairs):
+        w = want[p]
+        n1 = len(frames[a]["kps"])
+        assert same_bytes(F[p], w["F12"]) and same_bytes(e[p], w["epipole"]) and same_bytes(rec[p:p + 1], np.array([w["prep"]], nc.PAIR_DTYPE)), p
+        assert np.array_equal(m12[p, :n1], w["match12"]) and nm[p] == w["nmatches"], p
+        assert np.all(m12[p, n1:] == -77)
+        clean &= nc.compare_pair(got[p], w, frames[a]["kps"], frames[c]["kps"], w["match12"], "chain pair %d" % p) == 0
+    return clean, m12
+
+
+def test_chain_follows_the_neighbour_order():
+    """one current keyframe against three neighbours that share its free features, on one stream with no download before the end,
+    against the sequential restatement.  The inputs make the unordered result differ (asserted on the restatement), so equality here
+    shows the order."""
+    sc = nc.chain_scene()
+    frames = sc["frames"]
+    pairs = [(0, 1), (0, 2), (0, 3)]
+    want, wstate = nc.ref_sequence(frames, pairs)
+    unordered, _ = nc.ref_sequence(frames, pairs, ordered=False)
+    assert any(not np.array_equal(u["match12"], w["match12"]) for u, w in zip(unordered, want))
+    assert sum(int(w["result"]["n_new"]) > 20 for w in want) >= 2
+    b = Batch(frames, pairs, search=True)
+    got = b.chain()
+    clean, m12 = _compare_chain(b, got, want, frames, pairs)
+    b.check_untouched_outputs(got)
+    b.check_state(got, [m12[p, :CAP] for p in range(3)])
+    assert clean, "a match of the chain case lies inside a band: choose another seed"
+    for f in range(4):
+        assert np.array_equal(b.valid.get()[f], wstate[f][1]) and np.array_equal(b.free.get()[f], wstate[f][1] == 0), f
+    taken = np.zeros(CAP, bool)
+    for g in got:
+        assert not np.any(taken & (g["status"] == 1))
+        taken |= g["status"] == 1
+
+
+def test_chain_without_index_arrays():
+    """d_pair1 = d_pair2 = NULL: pair p is frames (p, p + 1); the chain advances every per-frame block by p frames"""
+    frames = nc.chain_scene()["frames"]
+    pairs = [(0, 1), (1, 2), (2, 3)]
+    want, wstate = nc.ref_sequence(frames, pairs)
+    b = Batch(frames, None, npairs=3, search=True)
+    got = b.chain()
+    _, m12 = _compare_chain(b, got, want, frames, pairs)
+    b.check_state(got, [m12[p] for p in range(3)])
+    assert sum(int(g["result"]["n_new"]) for g in got) > 50
+
+
+def test_invalid_octave_flags_its_pair_only():
+    good = nc.parity_case("mixed"); bad = nc.parity_case("long-baseline"); third = nc.parity_case("noise-free")
+    fb = [dict(f) for f in bad[0]["frames"]]
+    k = fb[1]["kps"].copy()
+    k["octave"][bad[1][np.flatnonzero(bad[1] >= 0)[300]]] = nc.NLEVELS       # in the second workgroup's rows of side 1
+    fb[1]["kps"] = k
+    frames = good[0]["frames"] + fb + third[0]["frames"]
+    pairs = [(0, 1), (2, 3), (4, 5)]
+    lists = [good[1], bad[1], third[1]]
+    b = Batch(frames, pairs)
+    got = b.triangulate(lists)
+    assert tuple(got[1]["result"]) == (0, 0, ERR_INVALID)
+    assert np.all(got[1]["status"] == 0xDD)
+    for key in ("x3D", "normal", "dist"):
+        assert same_bytes(got[1][key], fpoison(*got[1][key].shape))
+    for p, c in ((0, good), (2, third)):
+        nc.compare_pair(got[p], c[2], frames[pairs[p][0]]["kps"], frames[pairs[p][1]]["kps"], lists[p], "pair %d next to the invalid one" % p)
+    # the state of frames 2 and 3 is as it was; that of the others changed where their pairs created points
+    lists_for_state = [lists[0], np.full(CAP, -1, np.int32), lists[2]]
+    got[1] = dict(got[1], status=np.zeros(CAP, np.uint8))
+    b.check_state(got, lists_for_state)
+    # a negative octave, and one in range of a larger table: the same pair is fine with nlevels = 9
+    b2 = Batch(frames[2:4], None, npairs=1)
+    sf9 = np.r_[nc.SCALE, np.float32(1.2) ** 8].astype(np.float32)
+    dm = Dev(bad[1])
+    ok(lib().orbfe_triangulate_matches_batch_device(b2.kps.ptr, b2.n.ptr, CAP, None, None, None, b2.T.ptr, None, None, 1, dm.ptr, cp(nc.K4),
+                                                    cp(sf9), cp((sf9 * sf9).astype(np.float32)), 9, nc.RATIO, b2.status.ptr, b2.x3D.ptr, b2.normal.ptr,
+                                                    b2.dist.ptr, b2.res.ptr, None))
+    assert b2.res.get()[0]["status"] == 0 and b2.res.get()[0]["n_matches"] == (bad[1] >= 0).sum()
+
+
+# ------------------------------------------------------------------------------------------------------------ host calls
+def test_host_call_and_binding_equal_the_device_chain():
+    frames = nc.chain_scene()["frames"]
+    pairs = [(0, 1), (0, 2), (0, 3)]
+    b = Batch(frames, pairs, search=True)
+    dev = b.chain()
+    m12 = b.m12.get()
+    out, (x_cur, v_cur) = orbfe.create_new_map_points(frames[0], frames[1:], nc.K4, nc.SCALE, nc.SIGMA2, nc.RATIO, False)
+    for p, (o, d) in enumerate(zip(out, dev)):
+        n1 = len(frames[0]["kps"])
+        assert np.array_equal(o["status"], d["status"][:n1]) and np.array_equal(o["match12"], m12[p, :n1]), p
+        i1 = np.flatnonzero(d["status"][:n1] == 1)
+        assert np.array_equal(o["i1"], i1) and np.array_equal(o["i2"], m12[p, i1])
+        assert same_bytes(o["x3D"], d["x3D"][i1]) and same_bytes(o["normal"], d["normal"][i1]), p
+        assert same_bytes(o["max_distance"], d["dist"][i1, 0]) and same_bytes(o["min_distance"], d["dist"][i1, 1]), p
+        assert same_bytes(o["F12"].reshape(9), b.F12.get()[p]) and same_bytes(o["epipole"], b.epi.get()[p])
+        assert tuple(o["result"]) == tuple(d["result"]) and tuple(o["prep"]) == tuple(b.prep.get()[p])
+        assert same_bytes(o["valid2"], b.valid.get()[p + 1][:len(o["valid2"])]) and same_bytes(o["x3Dw2"], b.x.get()[p + 1][:len(o["x3Dw2"])])
+    assert same_bytes(v_cur, b.valid.get()[0]) and same_bytes(x_cur, b.x.get()[0])
+    # the inputs are not changed
+    assert np.array_equal(frames[0]["valid"], nc.chain_scene()["frames"][0]["valid"])
+
+
+def test_host_call_edges_and_errors():
+    sc, m12, _ = nc.parity_case("noise-free")
+    f0, f1 = sc["frames"]
+    empty = dict(kps=f0["kps"][:0], desc=f0["desc"][:0], fv=(np.zeros(0, np.uint32), np.zeros(1, np.int32), np.zeros(0, np.uint32)),
+                 x3Dw=np.zeros((0, 3), np.float32), valid=np.zeros(0, np.uint8), Tcw=f1["Tcw"])
+    out, _ = orbfe.create_new_map_points(f0, [empty], nc.K4, nc.SCALE, nc.SIGMA2)
+    assert out[0]["prep"]["skipped"] == 1 and out[0]["result"]["n_matches"] == 0 and not out[0]["status"].any()
+    out, _ = orbfe.create_new_map_points(empty, [f1], nc.K4, nc.SCALE, nc.SIGMA2)
+    assert len(out[0]["status"]) == 0 and out[0]["result"]["n_new"] == 0
+    k = f1["kps"].copy(); k["octave"][m12[np.flatnonzero(m12 >= 0)[3]]] = -1
+    with pytest.raises(orbfe.OrbfeError):
+        orbfe.new_points_inspect(f0["kps"], f0["Tcw"], k, f1["Tcw"], m12, nc.K4, nc.SCALE, nc.SIGMA2, nc.RATIO)
+    with pytest.raises(orbfe.OrbfeError):
+        orbfe.new_points_inspect(f0["kps"], f0["Tcw"], f1["kps"], f1["Tcw"], m12, nc.K4, nc.SCALE[:0], nc.SIGMA2[:0], nc.RATIO)
+    L = lib()
+    assert L.orbfe_triangulate_matches_batch_device(None, None, CAP, None, None, None, None, None, None, 1, None, cp(nc.K4), cp(nc.SCALE),
+                                                    cp(nc.SIGMA2), 8, nc.RATIO, None, None, None, None, None, None) == ERR_INVALID
+    d = Dev(np.zeros(64, np.uint8))
+    assert L.orbfe_new_points_prepare_batch_device(d.ptr, 4097, d.ptr, None, d.ptr, None, None, 1, cp(nc.K4), d.ptr, d.ptr, d.ptr,
+                                                   None) == orbfe.ORBFE_ERR_CAPACITY
+
+
+def test_noise_free_points_come_back_at_their_true_positions():
+    """search and triangulation of a noise-free pair: every free correspondence is found and lands on its landmark, within the bound of
+    the float64 second opinion (64 eps s1 / s3)"""
+    sc = nc.smoke_scene()
+    f0, f1 = sc["frames"]
+    m12 = nc.true_matches(sc, 1)
+    out, _ = orbfe.create_new_map_points(f0, [f1], nc.K4, nc.SCALE, nc.SIGMA2)
+    o = out[0]
+    assert o["prep"]["skipped"] == 0 and np.array_equal(o["match12"], m12)
+    assert len(o["i1"]) > 0.9 * (m12 >= 0).sum() and np.array_equal(o["i2"], m12[o["i1"]])
+    T1, T2 = f0["Tcw"].astype(np.float64), f1["Tcw"].astype(np.float64)
+    for i, j, x in zip(o["i1"], o["i2"], o["x3D"]):
+        _, s1, s3 = nc.dlt64(f0["kps"], T1, f1["kps"], T2, i, j)
+        Xt = sc["X"][sc["landmark"][0][i]]
+        assert np.linalg.norm(x - Xt) <= 64 * nc.FLT_EPS * s1 / s3 * np.linalg.norm(Xt)
+
+
+def test_shim_driver_equals_the_binding(tmp_path):
+    """include/shims/LocalMapping_orbfe.cc on mock keyframes: the (idx1, idx2, x3D) triples per neighbour are the binding's, bit for
+    bit; the eight-shim program links and runs"""
+    import subprocess
+    import local_mapping_shim_build as lb
+    frames = nc.chain_scene()["frames"]
+    out, _ = orbfe.create_new_map_points(frames[0], frames[1:], nc.K4, nc.SCALE, nc.SIGMA2, nc.RATIO, False)
+    lb.write_inputs(str(tmp_path / "in"), frames, nc.K4, nc.SCALE, nc.SIGMA2)
+    r = subprocess.run([lb.build(str(tmp_path)), str(tmp_path / "in"), str(tmp_path / "out")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    got = lb.read_outputs(str(tmp_path / "out"), len(frames) - 1)
+    assert sum(len(g[0]) for g in got) > 300
+    for (i1, i2, x), o in zip(got, out):
+        assert np.array_equal(i1, o["i1"]) and np.array_equal(i2, o["i2"]) and same_bytes(x, o["x3D"])
+    r = subprocess.run([lb.build_all(str(tmp_path))], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.startswith("ok: 8 shims"), r.stderr
