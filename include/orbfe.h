@@ -904,6 +904,114 @@ int orbfe_new_points_inspect(const orbfe_keypoint* kps1, int n1, const float* Tc
                              float ratio_factor, uint8_t* status, float* x3D, float* normal, float* dist, float* quantities,
                              orbfe_new_points_result* res, int device);
 
+/* ------------------------------------------------------------ LocalBundleAdjustment (local mapping) -- */
+/* Optimizer::LocalBundleAdjustment(KeyFrame*, bool*, Map*) (src/Optimizer.cc:772-1242) behind its collect step (:777-888), on flat
+ * arrays: g2o's Levenberg-Marquardt with BlockSolver_6_3 restated in double -- optimize(5) over all edges with Huber
+ * (delta = (double)sqrtf(5.991f)), the first check (a monocular edge whose cached chi2 > 5.991 or whose depth is not positive, and a
+ * marker edge whose chi2 > 5.991, go to level 1; Huber comes off every edge), optimize(10) on level 0 from the first round's
+ * estimates, the second check (the erase list) and the write-back.
+ *
+ * The problem:
+ *   - pose vertices 0 .. nkf-1: Tcw (12 floats each, 3 x 4 row-major, IN / OUT) and kf_fixed[k] (1 = lFixedCameras and the keyframe
+ *     with mnId 0; 0 = the other local keyframes).  The caller's order is the local keyframes in list order, then the fixed ones;
+ *   - points 0 .. np-1: x3Dw (np x 3 floats, IN / OUT);
+ *   - observations in CSR by point (obs_offset[np + 1], starting at 0, non-decreasing), in the point's GetObservations() order (the
+ *     order g2o adds the edges).  Two forms: obs_kf / obs_xy (x, y) / obs_octave, or -- the device call only, d_obs_xy == NULL --
+ *     obs_kf / obs_feature into d_kps blocks of `capacity` keypoints a keyframe (the layout of orbfe_extract_batch_device), so that
+ *     the call chains behind orbfe_create_new_map_points_device without repacking keypoints.  A keyframe observes a point once;
+ *   - one K4 = fx, fy, cx, cy; inv_level_sigma2[nlevels] = mvInvLevelSigma2, nlevels <= 32;
+ *   - markers 0 .. nma-1: Twm (12 floats, IN / OUT) and marker_local (12 floats: get3DPointsLocalRefSystem(0 .. 3)), as in
+ *     orbfe_pose_marker; their observations in CSR by marker (mobs_offset[nma + 1]) in GetObservations() order, each a keyframe index
+ *     and the 8 floats of mvArucoUn[4 idx .. 4 idx + 3]; four EdgeMarker edges an observation, information marker_info * I (the
+ *     reference's wei = 25);
+ *   - use_markers = Frame::mbUArucoIni: with 0 no marker vertex or edge exists and Twm is not written.
+ * EdgeSE3ProjectXYZ has g2o's analytic Jacobians; EdgeMarker (error = obs - pi((Tcw Twm) p)) g2o's numeric ones on both vertices:
+ * central differences, delta = 1e-9, through exp(+-delta e_d) T, none for a fixed vertex.  A fixed vertex has no Hessian block.
+ * LM as g2o runs it: lambda0 = 1e-5 x the largest diagonal entry over pose and point blocks, lambda on both, up to 10 trials an
+ * iteration, rho = dchi2 / (sum x (lambda x + b) + 1e-3) over all vertices, g2o's lambda / nu and stop rules (and the vendored
+ * "three iterations that gain less than 0.1 %" rule), lambda anew in each optimize().  The point blocks are marginalised:
+ * S = Hpp - sum Hpl Hll^-1 Hpl^T (Hll^-1 by cofactors, as Eigen inverts a 3 x 3), the dense S is factorised L L^T without pivoting
+ * (a pivot that is not positive and finite fails the solve: a failed trial with chi2 = DBL_MAX, the update of the last solve that
+ * succeeded applied as in g2o), the points follow by back-substitution.  A vertex all of whose edges are at level 1 is not part of
+ * the system and does not move; neither does a free keyframe without observations.
+ * Where the reference is undefined: an edge whose error or Jacobian is not finite adds nothing to H and b in that pass (its chi2
+ * still enters the sums, so that trial is rejected); a chi2 that is not finite at a check is bad.
+ *
+ * Outputs: Tcw of the keyframes with kf_fixed = 0 (floats as Converter::toCvMat(SE3Quat) makes them; the fixed ones are left as they
+ * are -- SetPose of the mnId 0 keyframe with its own pose is the shim's), x3Dw, Twm (use_markers), erase[e] = 1 for observation slot e
+ * of the erase list (one byte per slot, CSR order: vToErase is the slots with 1 in ascending order) and the record.
+ * MapPoint::UpdateNormalAndDepth is NOT done here: it needs the reference keyframe, the observations' levels and the scale factors of
+ * every observing keyframe, which the device function of new_map_points.hip (two observations, fresh point) does not take; it stays
+ * the shim's host call.
+ *
+ * stop (the reference's pbStopFlag, may be NULL): read at the call -- nonzero returns ORBFE_OK with status ORBFE_LBA_STOPPED and
+ * nothing else written (the reference returns before initializeOptimization) -- and, by the device call, at the start of every LM
+ * iteration, trial and round (d_stop must then stay readable by the device: device memory or mapped host memory): a set flag ends
+ * that optimize(), skips round 2 (bDoMore = false), and the second check and the write-back still run.  LIMITATION, to be lifted:
+ * the host call reads it at the call only (the flag is the caller's host byte, which the kernels cannot see; a caller that needs
+ * the abort inside a call uses the device call with a mapped byte).  Only the set-before-the-call case can be tested
+ * deterministically.
+ *
+ * ORBFE_ERR_CAPACITY: free pose vertices (keyframes with kf_fixed = 0, plus the markers when use_markers) above
+ * ORBFE_LBA_MAX_FREE_POSES, or a point with more than ORBFE_LBA_MAX_OBSERVATIONS observations.  ORBFE_ERR_INVALID: NULLs, offsets
+ * that do not start at 0 or decrease, a keyframe or feature index out of range, a keyframe that observes a point twice, an octave
+ * outside [0, nlevels), inputs that are not finite.  The host call returns these; the device call, which cannot look at device
+ * data without synchronising, returns them for what it can see on the host and writes the rest to d_res->status, and then writes
+ * nothing else.  iterations and stale_mask are diagnostics as in orbfe_pose_result.
+ *
+ * Scaling: the (keyframe, point) -> edge index is a dense table of nkf x np ints in the scratch (nkf x np < 2^30, ORBFE_ERR_INVALID
+ * beyond; orbfe_lba_scratch_bytes says what that costs: 0.5 MB of its 18 MB at 40 keyframes x 3 000 points), and the kernels that
+ * build a pose block or a block of the reduced system walk all np points once per block, whatever the number of observations.
+ * That is sized for local mapping (tens of keyframes, thousands of points); a map-sized problem wants a CSR by keyframe instead. */
+#define ORBFE_LBA_MAX_FREE_POSES 64
+#define ORBFE_LBA_MAX_OBSERVATIONS 256
+#define ORBFE_LBA_STOPPED 1
+
+typedef struct orbfe_lba_result {
+    int32_t n_edges_mono;       /* EdgeSE3ProjectXYZ edges = observation slots */
+    int32_t n_edges_marker;     /* EdgeMarker edges: 4 x marker observations (0 without use_markers) */
+    int32_t n_level1[2];        /* edges the first check sent to level 1: monocular, marker */
+    int32_t n_erase;            /* entries of the erase list */
+    int32_t iterations[2];      /* DIAGNOSTIC: LM iterations of the two optimize() calls */
+    int32_t stale_mask;         /* DIAGNOSTIC: bit r = round r ended on a rejected trial (the check after it read that trial's errors) */
+    int32_t status;             /* ORBFE_OK, ORBFE_LBA_STOPPED, or the device call's ORBFE_ERR_INVALID / ORBFE_ERR_CAPACITY (see above) */
+} orbfe_lba_result;
+
+/* Bytes of scratch orbfe_local_bundle_adjustment_device needs for a problem of these sizes (0 for negative sizes). */
+size_t orbfe_lba_scratch_bytes(int nkf, int np, int nobs, int nma, int nmobs);
+
+/* Host pointers; one upload, the chain below, one download, one synchronisation.  Gives the bits of the device call. */
+int orbfe_local_bundle_adjustment(float* Tcw, const uint8_t* kf_fixed, int nkf, float* x3Dw, int np, const int32_t* obs_offset,
+                                  const int32_t* obs_kf, const float* obs_xy, const int32_t* obs_octave, int nobs, const float* K4,
+                                  const float* inv_level_sigma2, int nlevels, float* Twm, const float* marker_local, int nma,
+                                  const int32_t* mobs_offset, const int32_t* mobs_kf, const float* mobs_corners, int nmobs, float marker_info,
+                                  int use_markers, const uint8_t* stop, uint8_t* erase, orbfe_lba_result* res, int device);
+
+/* Device pointers (K4 and inv_level_sigma2 are host arrays read at the call).  The call allocates nothing: d_scratch holds
+ * scratch_bytes >= orbfe_lba_scratch_bytes(...) bytes, 256-byte aligned.  Everything is enqueued on `stream` with no host
+ * synchronisation between entry and the last launch.  The LM state -- lambda, nu, both copies of the estimates, the "accepted / done /
+ * solve failed" flags, the counters -- lives in the scratch, and the sequence of launches does not depend on the problem: a launch
+ * that finds its step already decided returns at once.  Two memsets, then 1 launch of setup, per round 1 + iterations x (3 +
+ * 10 trials x 5) launches (5 and 10 iterations), a check behind each round and 1 launch of write-back: 1 + 2 x 1 + 15 x 53 + 2 + 1 =
+ * 801 launches whatever the problem.  Every sum has an order that depends on the problem's sizes alone (no floating-point atomics). */
+int orbfe_local_bundle_adjustment_device(float* d_Tcw, const uint8_t* d_kf_fixed, int nkf, float* d_x3Dw, int np, const int32_t* d_obs_offset,
+                                         const int32_t* d_obs_kf, const float* d_obs_xy, const int32_t* d_obs_octave,
+                                         const int32_t* d_obs_feature, const orbfe_keypoint* d_kps, int capacity, int nobs, const float* K4,
+                                         const float* inv_level_sigma2, int nlevels, float* d_Twm, const float* d_marker_local, int nma,
+                                         const int32_t* d_mobs_offset, const int32_t* d_mobs_kf, const float* d_mobs_corners, int nmobs,
+                                         float marker_info, int use_markers, const uint8_t* d_stop, uint8_t* d_erase, orbfe_lba_result* d_res,
+                                         void* d_scratch, size_t scratch_bytes, void* stream);
+
+/* DIAGNOSTIC / TEST INTERFACE, no stability promise: one linearisation at the given estimates (all edges, Huber) and the first LM
+ * trial.  Host pointers; the problem as above, nothing of it is written.  *nv = free pose vertices (keyframes in order, then markers);
+ * b (6 nv, then 3 np), Hpp (nv x 36, the diagonal blocks row-major), Hll (np x 6: the upper triangle xx xy xz yy yz zz), chi2 (the
+ * robust chi2 and lambda0), x (6 nv, then 3 np: the first trial's update).  Arrays sized for ORBFE_LBA_MAX_FREE_POSES vertices. */
+int orbfe_lba_inspect(const float* Tcw, const uint8_t* kf_fixed, int nkf, const float* x3Dw, int np, const int32_t* obs_offset,
+                      const int32_t* obs_kf, const float* obs_xy, const int32_t* obs_octave, int nobs, const float* K4,
+                      const float* inv_level_sigma2, int nlevels, const float* Twm, const float* marker_local, int nma,
+                      const int32_t* mobs_offset, const int32_t* mobs_kf, const float* mobs_corners, int nmobs, float marker_info,
+                      int use_markers, int32_t* nv, double* b, double* Hpp, double* Hll, double* chi2, double* x, int device);
+
 /* ------------------------------------------------------------ KeyFrameDatabase: candidate queries -- */
 /* KeyFrameDatabase::DetectLoopCandidates(pKF, minScore) (src/KeyFrameDatabase.cc:76-197, called by LoopClosing::DetectLoop) and
  * KeyFrameDatabase::DetectRelocalizationCandidates(F) (:199-309, called by Tracking::Relocalization) on flat arrays, with DBoW2's

@@ -1,8 +1,8 @@
 /*
  * Optimizer_pose_orbfe.cc (shim) -- Optimizer::PoseOptimization(Frame*) and Optimizer::PoseOptimizationByAruco(Frame*)
  * (src/Optimizer.cc:308-770) implemented on liborbfe.so.  Link it together with src/Optimizer.cc from which these two definitions
- * have been removed (the bundle adjustments stay the reference's own).  include/Optimizer.h, Frame, MapPoint and
- * MapAruco stay the reference's own.
+ * have been removed (LocalBundleAdjustment has a shim of its own, Optimizer_localba_orbfe.cc; the global bundle adjustment and the
+ * essential graph stay the reference's own).  include/Optimizer.h, Frame, MapPoint and MapAruco stay the reference's own.
  *
  * The shim walks the frame on the host -- mvpMapPoints (world positions), and for PoseOptimizationByAruco when Frame::mbUArucoIni
  * the markers with !mvbOldAruco, mvbArucoGood and a MapAruco (Twm, get3DPointsLocalRefSystem, mvArucoUn) -- and makes one

@@ -69,6 +69,8 @@ SYMBOLS = [
     # the geometry of LocalMapping::CreateNewMapPoints (csrc/new_map_points.hip)
     "orbfe_new_points_prepare_batch_device", "orbfe_triangulate_matches_batch_device", "orbfe_create_new_map_points_device",
     "orbfe_create_new_map_points", "orbfe_new_points_inspect",
+    # LocalBundleAdjustment of local mapping (csrc/local_ba.hip)
+    "orbfe_lba_scratch_bytes", "orbfe_local_bundle_adjustment", "orbfe_local_bundle_adjustment_device", "orbfe_lba_inspect",
 ]
 
 _lib = None
@@ -228,6 +230,14 @@ def load():
         side = [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp]
         L.orbfe_create_new_map_points.argtypes = side + side + [vp, vp, vp, i32, f32, i32] + [vp] * 9 + [i32]
         L.orbfe_new_points_inspect.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, f32] + [vp] * 6 + [i32]
+    if hasattr(L, "orbfe_local_bundle_adjustment"):
+        L.orbfe_lba_scratch_bytes.argtypes = [i32] * 5
+        L.orbfe_lba_scratch_bytes.restype = sz
+        prob = [vp, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, i32, f32, i32]
+        L.orbfe_local_bundle_adjustment.argtypes = prob + [vp, vp, vp, i32]
+        L.orbfe_lba_inspect.argtypes = prob + [vp] * 6 + [i32]
+        L.orbfe_local_bundle_adjustment_device.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp,
+                                                           i32, f32, i32, vp, vp, vp, vp, sz, vp]
     if hasattr(L, "orbfe_initialize"):
         L.orbfe_initialize.argtypes = [vp, i32, vp, i32, vp, vp, f32, i32, vp, vp, vp, vp, i32]
         L.orbfe_initialize_inspect.argtypes = [vp, i32, vp, i32, vp, vp, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
@@ -1575,3 +1585,85 @@ class MarkerDetector:
         wh = rows * cols
         return {"aruco_threshold": wh + wh // 8, "aruco_pyramid": wh + wh // 3, "aruco_contours": wh // 8,
                 "aruco_decode": 0, "aruco_finalize": 0}
+
+
+# ------------------------------------------------------------------------------- LocalBundleAdjustment (local mapping) ----
+LBA_MAX_FREE_POSES, LBA_MAX_OBSERVATIONS, LBA_STOPPED = 64, 256, 1
+LBA_RESULT_DTYPE = np.dtype([("n_edges_mono", "<i4"), ("n_edges_marker", "<i4"), ("n_level1", "<i4", 2), ("n_erase", "<i4"),
+                             ("iterations", "<i4", 2), ("stale_mask", "<i4"), ("status", "<i4")])
+assert LBA_RESULT_DTYPE.itemsize == 36
+
+
+def lba_arrays(pb):
+    """The flat arrays of a LocalBundleAdjustment problem, contiguous and typed as include/orbfe.h takes them.  pb: a dict with Tcw
+    (nkf x 3 x 4), kf_fixed, x3Dw (np x 3), obs_offset (np + 1), obs_kf, obs_xy (nobs x 2), obs_octave, K (3 x 3 or fx, fy, cx, cy),
+    inv_level_sigma2, and optionally Twm (nma x 3 x 4), marker_local (nma x 4 x 3), mobs_offset (nma + 1), mobs_kf, mobs_corners
+    (nmobs x 4 x 2), marker_info (25), use_markers (1 when markers are given)."""
+    c = lambda k, t, shape: np.ascontiguousarray(np.asarray(pb.get(k, np.zeros(0)), t).reshape(shape))
+    a = dict(Tcw=c("Tcw", np.float32, (-1, 12)).copy(), kf_fixed=c("kf_fixed", np.uint8, -1), x3Dw=c("x3Dw", np.float32, (-1, 3)).copy(),
+             obs_offset=c("obs_offset", np.int32, -1), obs_kf=c("obs_kf", np.int32, -1), obs_xy=c("obs_xy", np.float32, (-1, 2)),
+             obs_octave=c("obs_octave", np.int32, -1), K4=_K4(pb["K"]), inv_level_sigma2=c("inv_level_sigma2", np.float32, -1),
+             Twm=c("Twm", np.float32, (-1, 12)).copy(), marker_local=c("marker_local", np.float32, (-1, 12)),
+             mobs_offset=c("mobs_offset", np.int32, -1), mobs_kf=c("mobs_kf", np.int32, -1), mobs_corners=c("mobs_corners", np.float32, (-1, 8)))
+    a["marker_info"] = float(pb.get("marker_info", 25.0))
+    a["use_markers"] = int(pb.get("use_markers", 1 if len(a["Twm"]) else 0))
+    if len(a["Tcw"]) != len(a["kf_fixed"]) or len(a["obs_kf"]) != len(a["obs_xy"]) or len(a["obs_kf"]) != len(a["obs_octave"]) or \
+            len(a["obs_offset"]) != (len(a["x3Dw"]) + 1 if len(a["x3Dw"]) else len(a["obs_offset"])) or len(a["Twm"]) != len(a["marker_local"]) or \
+            len(a["mobs_kf"]) != len(a["mobs_corners"]) or len(a["mobs_offset"]) != (len(a["Twm"]) + 1 if len(a["Twm"]) else len(a["mobs_offset"])):
+        raise ValueError("LocalBundleAdjustment: array lengths do not agree")
+    return a
+
+
+def _lba_problem_args(a):
+    q = _ptr_or_none
+    return [q(a["Tcw"]), q(a["kf_fixed"]), len(a["Tcw"]), q(a["x3Dw"]), len(a["x3Dw"]), q(a["obs_offset"]), q(a["obs_kf"]), q(a["obs_xy"]),
+            q(a["obs_octave"]), len(a["obs_kf"]), _p(a["K4"]), q(a["inv_level_sigma2"]), len(a["inv_level_sigma2"]), q(a["Twm"]),
+            q(a["marker_local"]), len(a["Twm"]), q(a["mobs_offset"]), q(a["mobs_kf"]), q(a["mobs_corners"]), len(a["mobs_kf"]),
+            a["marker_info"], a["use_markers"]]
+
+
+def lba_scratch_bytes(nkf, np_, nobs, nma, nmobs):
+    return int(load().orbfe_lba_scratch_bytes(int(nkf), int(np_), int(nobs), int(nma), int(nmobs)))
+
+
+def local_bundle_adjustment(pb, stop=False, device=0):
+    """Optimizer::LocalBundleAdjustment (Optimizer.cc:892-1242, behind the collect step) on the GPU, host arrays.  pb as lba_arrays
+    takes it; stop = the value of *pbStopFlag at the call.  Returns dict(Tcw (nkf x 3 x 4), x3Dw, Twm, erase (a byte per observation
+    slot), result (LBA_RESULT_DTYPE)); the inputs are not modified."""
+    L = load()
+    a = lba_arrays(pb)
+    erase = np.zeros(len(a["obs_kf"]), np.uint8)
+    res = np.zeros(1, LBA_RESULT_DTYPE)
+    flag = np.array([1 if stop else 0], np.uint8)
+    _check(L, L.orbfe_local_bundle_adjustment(*(_lba_problem_args(a) + [_p(flag), _ptr_or_none(erase), _p(res), device])),
+           "orbfe_local_bundle_adjustment")
+    return dict(Tcw=a["Tcw"].reshape(-1, 3, 4), x3Dw=a["x3Dw"], Twm=a["Twm"].reshape(-1, 3, 4), erase=erase, result=res[0])
+
+
+def local_bundle_adjustment_device(d, nkf, np_, nobs, nma, nmobs, K, inv_level_sigma2, marker_info, use_markers, capacity=0, stream=0):
+    """orbfe_local_bundle_adjustment_device: d maps the argument names of include/orbfe.h without their d_ prefix (Tcw, kf_fixed, x3Dw,
+    obs_offset, obs_kf, obs_xy, obs_octave, obs_feature, kps, Twm, marker_local, mobs_offset, mobs_kf, mobs_corners, stop, erase, res,
+    scratch) to device addresses (0 / missing = NULL) and scratch_bytes to a size.  Asynchronous on `stream`."""
+    L = load()
+    g = lambda k: d.get(k) or None
+    sig = np.ascontiguousarray(inv_level_sigma2, np.float32)
+    _check(L, L.orbfe_local_bundle_adjustment_device(
+        g("Tcw"), g("kf_fixed"), int(nkf), g("x3Dw"), int(np_), g("obs_offset"), g("obs_kf"), g("obs_xy"), g("obs_octave"), g("obs_feature"),
+        g("kps"), int(capacity), int(nobs), _p(_K4(K)), _p(sig), len(sig), g("Twm"), g("marker_local"), int(nma), g("mobs_offset"),
+        g("mobs_kf"), g("mobs_corners"), int(nmobs), float(marker_info), int(use_markers), g("stop"), g("erase"), g("res"), g("scratch"),
+        int(d.get("scratch_bytes", 0)), stream), "orbfe_local_bundle_adjustment_device")
+
+
+def lba_inspect(pb, device=0):
+    """orbfe_lba_inspect: one linearisation and the first trial.  Returns dict(nv, b_pose (nv x 6), b_point (np x 3), Hpp (nv x 6 x 6),
+    Hll (np x 6: xx xy xz yy yz zz), chi2, lambda0, x_pose (nv x 6), x_point (np x 3))."""
+    L = load()
+    a = lba_arrays(pb)
+    n = len(a["x3Dw"])
+    nv = np.zeros(1, np.int32)
+    b = np.zeros(6 * LBA_MAX_FREE_POSES + 3 * n); x = np.zeros_like(b)
+    Hpp = np.zeros((LBA_MAX_FREE_POSES, 6, 6)); Hll = np.zeros((max(n, 1), 6)); chi2 = np.zeros(2)
+    _check(L, L.orbfe_lba_inspect(*(_lba_problem_args(a) + [_p(nv), _p(b), _p(Hpp), _p(Hll), _p(chi2), _p(x), device])), "orbfe_lba_inspect")
+    v = int(nv[0])
+    return dict(nv=v, b_pose=b[:6 * v].reshape(v, 6), b_point=b[6 * v:6 * v + 3 * n].reshape(n, 3), Hpp=Hpp[:v], Hll=Hll[:n], chi2=chi2[0],
+                lambda0=chi2[1], x_pose=x[:6 * v].reshape(v, 6), x_point=x[6 * v:6 * v + 3 * n].reshape(n, 3))

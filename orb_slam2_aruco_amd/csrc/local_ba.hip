@@ -1,0 +1,1176 @@
+// local_ba.hip -- Optimizer::LocalBundleAdjustment (src/Optimizer.cc:772-1242) behind its collect step, on gfx950: g2o's
+// Levenberg-Marquardt with BlockSolver_6_3 (pose blocks 6 x 6, point blocks 3 x 3 marginalised by a Schur complement), two rounds
+// (5 iterations with Huber, 10 on the edges the first check left at level 0), with the fork's marker poses as free SE3 vertices.
+//
+// One problem fills the chip, so the solve is a chain of small grid-wide kernels and the LM state lives on the device (LbaCtl, two
+// copies of every estimate: `cur` and the trial's).  The host enqueues the same launches whatever the problem; a launch whose step
+// is already decided (the round is over, the trial loop has ended, the call was refused) returns at once.
+//   setup          k_lba_setup: estimates in double, the edge arrays (either observation form), the (keyframe, point) -> edge table,
+//                  validation; k_lba_begin: the free-vertex numbering, bounds, the stop flag, the LM state of the round
+//   an iteration   k_lba_linearize (a thread per point, then a thread per marker corner edge: errors, chi2 cache, Jacobians, the
+//                  edge's blocks, Hll and bl of the point in observation order), k_lba_pose_blocks (a workgroup per free vertex:
+//                  Hpp, bp over the vertex's edges in point order), k_lba_ctl_lin (chi2, lambda0)
+//   a trial        k_lba_schur_points ((Hll + lambda I)^-1), k_lba_assemble (a wave per block (i, j) of S: Hpp - sum W_i D^-1 W_j^T
+//                  over the points both see, in point order), k_lba_solve (one workgroup: L L^T of S in LDS, or in global memory when it does not fit, the two
+//                  substitutions, the trial poses), k_lba_backsub (a thread per point: the point's update, the trial point, the
+//                  trial errors and chi2), k_lba_ctl_trial (rho, accept or reject, lambda / nu, the stop rules)
+//   a check        k_lba_check (a thread per edge: level 1 flags after round 1, the erase bytes after round 2)
+//   the end        k_lba_finish (poses, points, marker poses as floats; the record)
+// Sums: a thread adds its own items in their order (a point's observations; a contiguous run of points), a wave adds its lanes by a
+// fixed butterfly, the waves are added in order, and the per-workgroup partial sums of a grid-wide pass are added the same way by one
+// workgroup.  No floating-point atomic anywhere: the order of every sum is a function of the problem's sizes alone.
+// g2o's cached edge errors are the chi2 cache e_chi2 / m_chi2: written by every pass that evaluates an edge (the linearisation and
+// each trial, rejected ones included), read by the checks -- so a round that ends on a rejected trial leaves that trial's errors
+// there, and an edge at level 1 keeps its value of round 1, as in the reference.
+#include "host_stage.hpp"
+#include "lm_dense.hpp"
+#include "orbfe_common.hpp"
+#include "se3_quat.hpp"
+#include <cfloat>
+#include <cmath>
+
+namespace orbfe {
+namespace {
+
+constexpr int LBA_MAXV = ORBFE_LBA_MAX_FREE_POSES;
+constexpr int LBA_N = 6 * LBA_MAXV;     // rows of S, and its row stride
+constexpr int LBA_PT = 64;              // threads of the per-point kernels: one wave, so that a few thousand points are many workgroups
+constexpr int LBA_MAX_LEVELS = 32;
+constexpr int LBA_EBLK = 45;            // doubles of a monocular edge's blocks: A = Jp^T w Jp (21), b (6), W = Jp^T w Jx (6 x 3)
+constexpr int LBA_MBLK = 90;            // of a marker edge: Acc (21), bc (6), Amm (21), bm (6), Acm (36)
+constexpr int LBA_BAD_INVALID = 1, LBA_BAD_CAPACITY = 2;
+
+struct LbaCtl {
+    double lambda, ni, currentChi, iniChi, rho, lambda0;
+    int q, it, nbad_lm, ok2;
+    int iter_go, trial_go, cur, round;
+    int stopped, stale, abort_status, bad;
+    int nfree_kf, nv, aborted, pad0;
+    int iters[2], n_level1[2];
+    int n_erase, stale_mask, pad1, pad2;
+};
+
+struct LbaP {
+    // the caller's arrays
+    float* Tcw; const uint8_t* kf_fixed; float* x3Dw; const int32_t* obs_offset; const int32_t* obs_kf; const float* obs_xy;
+    const int32_t* obs_oct; const int32_t* obs_feat; const orbfe_keypoint* kps;
+    float* Twm; const float* mlocal; const int32_t* mobs_offset; const int32_t* mobs_kf; const float* mobs_corners;
+    const uint8_t* stop; uint8_t* erase; orbfe_lba_result* res;
+    int nkf, np, nobs, nma, nmobs, nme, capacity, nlevels, use_markers, npb, nb, pad;
+    Cam K;
+    double delta, marker_info;
+    float inv_sigma2[LBA_MAX_LEVELS];
+    // scratch
+    LbaCtl* ctl;
+    SE3* pose[2];          // nkf keyframes, then nma markers
+    double* pt[2];         // np x 3
+    int32_t *e_kf, *e_pt; float *e_ox, *e_oy, *e_info; uint8_t *e_level, *e_use; double *e_chi2, *e_blk;
+    int32_t* mo_marker; uint8_t *m_level, *m_use; double *m_chi2, *m_blk;
+    double *Hll, *bl, *Dinv, *xl; uint8_t* p_active;
+    double *Hpp, *bp, *xv, *vmax; int32_t *v_active, *v_kf, *kf_free;
+    int32_t* tbl;          // nkf x np: the edge of (keyframe, point), -1 none
+    double *S, *bs, *chi_part, *scale_part, *max_part;
+};
+
+// ---------------------------------------------------------------------------------------- scratch layout --
+struct LbaLayout {
+    size_t ctl, zero_end, pose[2], pt[2], e_kf, e_pt, e_ox, e_oy, e_info, e_level, e_use, e_chi2, e_blk, mo_marker, m_level, m_use, m_chi2,
+        m_blk, Hll, bl, Dinv, xl, p_active, Hpp, bp, xv, vmax, v_active, v_kf, kf_free, tbl, tbl_bytes, S, bs, chi_part, scale_part, max_part,
+        end;
+    int npb, nb;
+};
+
+LbaLayout lba_layout(int nkf, int np, int nobs, int nma, int nmobs)
+{
+    LbaLayout l{};
+    IoLayout o;
+    const size_t K = (size_t)std::max(nkf, 1), P = (size_t)std::max(np, 1), E = (size_t)std::max(nobs, 1), M = (size_t)std::max(nma, 1),
+                 MO = (size_t)std::max(nmobs, 1), ME = 4 * MO;
+    l.npb = (np + LBA_PT - 1) / LBA_PT;
+    l.nb = l.npb + (4 * nmobs + LBA_PT - 1) / LBA_PT;
+    const size_t NB = (size_t)std::max(l.nb, 1);
+    // zeroed at every call: the state, the updates, the chi2 caches (an edge no pass evaluated has g2o's initial error 0), the levels
+    l.ctl = o.take(sizeof(LbaCtl));
+    l.xv = o.take(LBA_N * 8);
+    l.xl = o.take(P * 24);
+    l.e_chi2 = o.take(E * 8);
+    l.m_chi2 = o.take(ME * 8);
+    l.e_level = o.take(E);
+    l.m_level = o.take(ME);
+    l.zero_end = o.end();
+    for (int k = 0; k < 2; k++) l.pose[k] = o.take((K + M) * sizeof(SE3));
+    for (int k = 0; k < 2; k++) l.pt[k] = o.take(P * 24);
+    l.e_kf = o.take(E * 4); l.e_pt = o.take(E * 4); l.e_ox = o.take(E * 4); l.e_oy = o.take(E * 4); l.e_info = o.take(E * 4);
+    l.e_use = o.take(E);
+    l.e_blk = o.take(E * LBA_EBLK * 8);
+    l.mo_marker = o.take(MO * 4);
+    l.m_use = o.take(ME);
+    l.m_blk = o.take(ME * LBA_MBLK * 8);
+    l.Hll = o.take(P * 48); l.bl = o.take(P * 24); l.Dinv = o.take(P * 72); l.p_active = o.take(P);
+    l.Hpp = o.take(LBA_MAXV * 36 * 8); l.bp = o.take(LBA_N * 8); l.vmax = o.take(LBA_MAXV * 8);
+    l.v_active = o.take(LBA_MAXV * 4); l.v_kf = o.take(LBA_MAXV * 4); l.kf_free = o.take(K * 4);
+    l.tbl_bytes = K * P * 4;
+    l.tbl = o.take(l.tbl_bytes);
+    l.S = o.take((size_t)LBA_N * LBA_N * 8); l.bs = o.take(LBA_N * 8);
+    l.chi_part = o.take(NB * 8); l.scale_part = o.take(NB * 8); l.max_part = o.take(NB * 8);
+    l.end = o.end();
+    return l;
+}
+
+void lba_bind(LbaP& p, const LbaLayout& l, void* scratch)
+{
+    unsigned char* s = (unsigned char*)scratch;
+    p.ctl = (LbaCtl*)(s + l.ctl);
+    for (int k = 0; k < 2; k++) { p.pose[k] = (SE3*)(s + l.pose[k]); p.pt[k] = (double*)(s + l.pt[k]); }
+    p.e_kf = (int32_t*)(s + l.e_kf); p.e_pt = (int32_t*)(s + l.e_pt); p.e_ox = (float*)(s + l.e_ox); p.e_oy = (float*)(s + l.e_oy);
+    p.e_info = (float*)(s + l.e_info); p.e_level = s + l.e_level; p.e_use = s + l.e_use; p.e_chi2 = (double*)(s + l.e_chi2);
+    p.e_blk = (double*)(s + l.e_blk);
+    p.mo_marker = (int32_t*)(s + l.mo_marker); p.m_level = s + l.m_level; p.m_use = s + l.m_use; p.m_chi2 = (double*)(s + l.m_chi2);
+    p.m_blk = (double*)(s + l.m_blk);
+    p.Hll = (double*)(s + l.Hll); p.bl = (double*)(s + l.bl); p.Dinv = (double*)(s + l.Dinv); p.xl = (double*)(s + l.xl);
+    p.p_active = s + l.p_active;
+    p.Hpp = (double*)(s + l.Hpp); p.bp = (double*)(s + l.bp); p.xv = (double*)(s + l.xv); p.vmax = (double*)(s + l.vmax);
+    p.v_active = (int32_t*)(s + l.v_active); p.v_kf = (int32_t*)(s + l.v_kf); p.kf_free = (int32_t*)(s + l.kf_free);
+    p.tbl = (int32_t*)(s + l.tbl);
+    p.S = (double*)(s + l.S); p.bs = (double*)(s + l.bs);
+    p.chi_part = (double*)(s + l.chi_part); p.scale_part = (double*)(s + l.scale_part); p.max_part = (double*)(s + l.max_part);
+    p.npb = l.npb; p.nb = l.nb;
+}
+
+// ---------------------------------------------------------------------------------------- small pieces --
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+__device__ __forceinline__ double wave_max(double v)
+{
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
+__device__ __forceinline__ bool finite_f(float v) { return isfinite(v); }
+
+// Eigen's Quaternion::toRotationMatrix
+__device__ __forceinline__ void rot_of(const Quat& q, double (&R)[3][3])
+{
+    const double tx = 2 * q.x, ty = 2 * q.y, tz = 2 * q.z;
+    const double twx = tx * q.w, twy = ty * q.w, twz = tz * q.w;
+    const double txx = tx * q.x, txy = ty * q.x, txz = tz * q.x;
+    const double tyy = ty * q.y, tyz = tz * q.y, tzz = tz * q.z;
+    R[0][0] = 1 - (tyy + tzz); R[0][1] = txy - twz; R[0][2] = txz + twy;
+    R[1][0] = txy + twz; R[1][1] = 1 - (txx + tzz); R[1][2] = tyz - twx;
+    R[2][0] = txz - twy; R[2][1] = tyz + twx; R[2][2] = 1 - (txx + tyy);
+}
+
+struct MonoLin {
+    double err[2], Jp[2][6], Jx[2][3];
+};
+
+// EdgeSE3ProjectXYZ: computeError and linearizeOplus (types_six_dof_expmap.cpp:103-139)
+__device__ __noinline__ void lba_mono_linearize(const SE3& T, const double (&Xw)[3], double ox, double oy, const Cam& K, MonoLin& o)
+{
+    double Xc[3], R[3][3];
+    map(T, Xw, Xc);
+    project_error(Xc, ox, oy, K, o.err);
+    const double x = Xc[0], y = Xc[1], z = Xc[2], z_2 = z * z;
+    const double s = -1. / z;
+    const double t0[3] = {s * K.fx, s * 0., s * (-x / z * K.fx)}, t1[3] = {s * 0., s * K.fy, s * (-y / z * K.fy)};
+    rot_of(T.q, R);
+    for (int c = 0; c < 3; c++) {
+        o.Jx[0][c] = t0[0] * R[0][c] + t0[1] * R[1][c] + t0[2] * R[2][c];
+        o.Jx[1][c] = t1[0] * R[0][c] + t1[1] * R[1][c] + t1[2] * R[2][c];
+    }
+    o.Jp[0][0] = x * y / z_2 * K.fx;
+    o.Jp[0][1] = -(1 + (x * x / z_2)) * K.fx;
+    o.Jp[0][2] = y / z * K.fx;
+    o.Jp[0][3] = -1. / z * K.fx;
+    o.Jp[0][4] = 0;
+    o.Jp[0][5] = x / z_2 * K.fx;
+    o.Jp[1][0] = (1 + y * y / z_2) * K.fy;
+    o.Jp[1][1] = -x * y / z_2 * K.fy;
+    o.Jp[1][2] = -x / z * K.fy;
+    o.Jp[1][3] = 0;
+    o.Jp[1][4] = -1. / z * K.fy;
+    o.Jp[1][5] = y / z_2 * K.fy;
+}
+
+__device__ __noinline__ void lba_mono_error(const SE3& T, const double (&Xw)[3], double ox, double oy, const Cam& K, double (&err)[2])
+{
+    double Xc[3];
+    map(T, Xw, Xc);
+    project_error(Xc, ox, oy, K, err);
+}
+
+// EdgeMarker::computeError: obs - pi((c2g g2m) point)
+__device__ __noinline__ void lba_marker_error(const SE3& Tc, const SE3& Tm, const double (&pm)[3], double ox, double oy, const Cam& K,
+                                              double (&err)[2])
+{
+    const SE3 Tcm = mul(Tc, Tm);
+    double Xc[3];
+    map(Tcm, pm, Xc);
+    project_error(Xc, ox, oy, K, err);
+}
+
+// BaseBinaryEdge::linearizeOplus for one vertex: central differences through exp(+-1e-9 e_d) * estimate
+__device__ __noinline__ void lba_marker_jacobian(const SE3& Tc, const SE3& Tm, bool camera, const double (&pm)[3], double ox, double oy,
+                                                 const Cam& K, double (&J)[2][6])
+{
+    const double delta = 1e-9, scalar = 1.0 / (2 * delta);
+    for (int d = 0; d < 6; d++) {
+        double u[6] = {0, 0, 0, 0, 0, 0}, ep[2], em[2];
+        u[d] = delta;
+        SE3 E = se3_exp(u);
+        if (camera) lba_marker_error(mul(E, Tc), Tm, pm, ox, oy, K, ep);
+        else lba_marker_error(Tc, mul(E, Tm), pm, ox, oy, K, ep);
+        u[d] = -delta;
+        E = se3_exp(u);
+        if (camera) lba_marker_error(mul(E, Tc), Tm, pm, ox, oy, K, em);
+        else lba_marker_error(Tc, mul(E, Tm), pm, ox, oy, K, em);
+        J[0][d] = scalar * (ep[0] - em[0]);
+        J[1][d] = scalar * (ep[1] - em[1]);
+    }
+}
+
+__device__ __forceinline__ bool all_finite(const double* v, int n)
+{
+    bool ok = true;
+    for (int i = 0; i < n; i++) ok = ok && isfinite(v[i]);
+    return ok;
+}
+
+// upper triangle of Ja^T w Ja (21) and Ja^T r (6)
+__device__ __noinline__ void lba_diag_block(const double (&J)[2][6], double w, double r0, double r1, double* out)
+{
+    int k = 0;
+    for (int a = 0; a < 6; a++)
+        for (int c = a; c < 6; c++, k++) out[k] = J[0][a] * (w * J[0][c]) + J[1][a] * (w * J[1][c]);
+    for (int a = 0; a < 6; a++) out[21 + a] = J[0][a] * r0 + J[1][a] * r1;
+}
+
+__device__ __forceinline__ bool stop_set(const LbaP& p) { return p.stop && *(const volatile uint8_t*)p.stop != 0; }
+
+// ---------------------------------------------------------------------------------------- setup --
+__global__ __launch_bounds__(256) void k_lba_setup(LbaP p)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    int bad = 0;
+    if (i < p.nkf + p.nma) {
+        const bool mk = i >= p.nkf;
+        const float* T = mk ? p.Twm + (size_t)(i - p.nkf) * 12 : p.Tcw + (size_t)i * 12;
+        bool fin = true;
+        for (int k = 0; k < 12; k++) fin = fin && finite_f(T[k]);
+        if (mk)
+            for (int k = 0; k < 12; k++) fin = fin && finite_f(p.mlocal[(size_t)(i - p.nkf) * 12 + k]);
+        if (!fin) bad |= LBA_BAD_INVALID;
+        const SE3 S = se3_from_float(T);
+        p.pose[0][i] = S;
+        p.pose[1][i] = S;
+    }
+    if (i < p.np) {
+        const int lo = p.obs_offset[i], hi = p.obs_offset[i + 1];
+        if ((i == 0 && lo != 0) || hi < lo || lo < 0 || hi > p.nobs || (i == p.np - 1 && hi != p.nobs)) bad |= LBA_BAD_INVALID;
+        else if (hi - lo > ORBFE_LBA_MAX_OBSERVATIONS) bad |= LBA_BAD_CAPACITY;
+        for (int k = 0; k < 3; k++) {
+            const float v = p.x3Dw[(size_t)i * 3 + k];
+            if (!finite_f(v)) bad |= LBA_BAD_INVALID;
+            p.pt[0][(size_t)i * 3 + k] = v;
+            p.pt[1][(size_t)i * 3 + k] = v;
+        }
+    }
+    if (i < p.nobs) {
+        // the point of slot i: the last point whose range starts at or before i (np > 0 here)
+        int lo = 0, hi = p.np - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (p.obs_offset[mid] <= i) lo = mid;
+            else hi = mid - 1;
+        }
+        const int pt = lo;
+        int kf = p.obs_kf[i], oct = 0;
+        float ox = 0.f, oy = 0.f;
+        if (kf < 0 || kf >= p.nkf) {
+            bad |= LBA_BAD_INVALID;
+            kf = 0;
+        } else if (p.obs_xy) {
+            ox = p.obs_xy[(size_t)i * 2];
+            oy = p.obs_xy[(size_t)i * 2 + 1];
+            oct = p.obs_oct[i];
+        } else {
+            const int f = p.obs_feat[i];
+            if (f < 0 || f >= p.capacity) bad |= LBA_BAD_INVALID;
+            else {
+                const orbfe_keypoint kp = p.kps[(size_t)kf * p.capacity + f];
+                ox = kp.x; oy = kp.y; oct = kp.octave;
+            }
+        }
+        if (oct < 0 || oct >= p.nlevels) {
+            bad |= LBA_BAD_INVALID;
+            oct = 0;
+        }
+        if (!finite_f(ox) || !finite_f(oy)) bad |= LBA_BAD_INVALID;
+        p.e_kf[i] = kf; p.e_pt[i] = pt; p.e_ox[i] = ox; p.e_oy[i] = oy; p.e_info[i] = p.inv_sigma2[oct];
+        if (atomicCAS(&p.tbl[(size_t)kf * p.np + pt], -1, i) != -1) bad |= LBA_BAD_INVALID;   // a keyframe observes a point once
+    }
+    if (i < p.nma) {
+        const int lo = p.mobs_offset[i], hi = p.mobs_offset[i + 1];
+        if ((i == 0 && lo != 0) || hi < lo || lo < 0 || hi > p.nmobs || (i == p.nma - 1 && hi != p.nmobs)) bad |= LBA_BAD_INVALID;
+        else
+            for (int o = lo; o < hi; o++) p.mo_marker[o] = i;
+    }
+    if (i < p.nmobs) {
+        const int kf = p.mobs_kf[i];
+        if (kf < 0 || kf >= p.nkf) bad |= LBA_BAD_INVALID;
+        for (int k = 0; k < 8; k++)
+            if (!finite_f(p.mobs_corners[(size_t)i * 8 + k])) bad |= LBA_BAD_INVALID;
+    }
+    if (bad) atomicOr(&p.ctl->bad, bad);
+}
+
+// round 0: the free-vertex numbering, the bounds, the stop flag at the call.  round 1: bDoMore.  One thread.
+__global__ void k_lba_begin(LbaP p, int round)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    LbaCtl& c = *p.ctl;
+    if (round == 0) {
+        int nf = 0;
+        for (int k = 0; k < p.nkf; k++) {
+            const bool fr = p.kf_fixed[k] == 0;
+            p.kf_free[k] = fr ? nf : -1;
+            if (fr) {
+                if (nf < LBA_MAXV) p.v_kf[nf] = k;
+                nf++;
+            }
+        }
+        const int nv = nf + (p.use_markers ? p.nma : 0);
+        for (int m = 0; p.use_markers && m < p.nma; m++)
+            if (nf + m < LBA_MAXV) p.v_kf[nf + m] = p.nkf + m;
+        c.nfree_kf = nf;
+        c.nv = nv;
+        if (c.bad & LBA_BAD_INVALID) c.abort_status = ORBFE_ERR_INVALID;
+        else if ((c.bad & LBA_BAD_CAPACITY) || nv > LBA_MAXV) c.abort_status = ORBFE_ERR_CAPACITY;
+        else if (stop_set(p)) c.abort_status = ORBFE_LBA_STOPPED;
+        c.aborted = c.abort_status != 0;
+        if (c.aborted) c.nv = 0;
+        c.iter_go = !c.aborted;
+    } else {
+        if (c.aborted) return;
+        if (stop_set(p)) c.stopped = 1;
+        c.iter_go = !c.stopped;
+    }
+    c.round = round;
+    c.it = 0;
+    c.trial_go = 0;
+    c.lambda = 0;
+    c.ni = 2;
+    c.nbad_lm = 0;
+    c.rho = 0;
+    c.stale = 0;
+}
+
+// ---------------------------------------------------------------------------------------- linearisation --
+__global__ __launch_bounds__(LBA_PT) void k_lba_linearize(LbaP p)
+{
+    const LbaCtl& c = *p.ctl;
+    if (c.aborted || !c.iter_go) return;
+    const int cur = c.cur;
+    const bool robust = c.round == 0;
+    double chi = 0, md = 0;
+    if ((int)blockIdx.x < p.npb) {
+        const int pi = blockIdx.x * LBA_PT + threadIdx.x;
+        if (pi < p.np) {
+            const double Xw[3] = {p.pt[cur][(size_t)pi * 3], p.pt[cur][(size_t)pi * 3 + 1], p.pt[cur][(size_t)pi * 3 + 2]};
+            double H[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0};
+            int nact = 0;
+            for (int e = p.obs_offset[pi]; e < p.obs_offset[pi + 1]; e++) {
+                if (p.e_level[e]) {
+                    p.e_use[e] = 0;
+                    continue;
+                }
+                nact++;
+                const int kf = p.e_kf[e];
+                const SE3 T = p.pose[cur][kf];
+                const double info = p.e_info[e];
+                MonoLin L;
+                lba_mono_linearize(T, Xw, p.e_ox[e], p.e_oy[e], p.K, L);
+                const double ch = chi2_of(L.err, info);
+                p.e_chi2[e] = ch;
+                double rho[2] = {ch, 1.};
+                if (robust) huber(ch, p.delta, rho);
+                chi += rho[0];
+                const bool fin = all_finite(L.err, 2) && all_finite(&L.Jp[0][0], 12) && all_finite(&L.Jx[0][0], 6) && isfinite(rho[1]);
+                const int vf = p.kf_free[kf];
+                p.e_use[e] = fin ? (vf >= 0 ? 3 : 1) : 0;
+                if (!fin) continue;
+                const double w = rho[1] * info;
+                const double r0 = rho[1] * -(info * L.err[0]), r1 = rho[1] * -(info * L.err[1]);
+                int k = 0;
+                for (int a = 0; a < 3; a++)
+                    for (int cc = a; cc < 3; cc++, k++) H[k] += L.Jx[0][a] * (w * L.Jx[0][cc]) + L.Jx[1][a] * (w * L.Jx[1][cc]);
+                for (int a = 0; a < 3; a++) b[a] += L.Jx[0][a] * r0 + L.Jx[1][a] * r1;
+                if (vf >= 0) {
+                    double* out = p.e_blk + (size_t)e * LBA_EBLK;
+                    lba_diag_block(L.Jp, w, r0, r1, out);
+                    for (int a = 0; a < 6; a++)
+                        for (int cc = 0; cc < 3; cc++) out[27 + a * 3 + cc] = L.Jp[0][a] * (w * L.Jx[0][cc]) + L.Jp[1][a] * (w * L.Jx[1][cc]);
+                }
+            }
+            for (int k = 0; k < 6; k++) p.Hll[(size_t)pi * 6 + k] = H[k];
+            for (int k = 0; k < 3; k++) p.bl[(size_t)pi * 3 + k] = b[k];
+            p.p_active[pi] = nact > 0;
+            if (nact > 0) md = fmax(fmax(fabs(H[0]), fabs(H[3])), fabs(H[5]));
+        }
+    } else {
+        const int j = (blockIdx.x - p.npb) * LBA_PT + threadIdx.x;
+        if (j < p.nme) {
+            if (p.m_level[j]) p.m_use[j] = 0;
+            else {
+                const int o = j >> 2, k = j & 3, kf = p.mobs_kf[o], m = p.mo_marker[o];
+                const SE3 Tc = p.pose[cur][kf], Tm = p.pose[cur][p.nkf + m];
+                const double pm[3] = {p.mlocal[(size_t)m * 12 + 3 * k], p.mlocal[(size_t)m * 12 + 3 * k + 1], p.mlocal[(size_t)m * 12 + 3 * k + 2]};
+                const double ox = p.mobs_corners[(size_t)o * 8 + 2 * k], oy = p.mobs_corners[(size_t)o * 8 + 2 * k + 1];
+                const bool camfree = p.kf_free[kf] >= 0;
+                double err[2], Jc[2][6], Jm[2][6], rho[2];
+                lba_marker_error(Tc, Tm, pm, ox, oy, p.K, err);
+                const double ch = chi2_of(err, p.marker_info);
+                p.m_chi2[j] = ch;
+                rho[0] = ch; rho[1] = 1.;
+                if (robust) huber(ch, p.delta, rho);
+                chi += rho[0];
+                for (int a = 0; a < 6; a++) Jc[0][a] = Jc[1][a] = 0;
+                if (camfree) lba_marker_jacobian(Tc, Tm, true, pm, ox, oy, p.K, Jc);
+                lba_marker_jacobian(Tc, Tm, false, pm, ox, oy, p.K, Jm);
+                const bool fin = all_finite(err, 2) && all_finite(&Jc[0][0], 12) && all_finite(&Jm[0][0], 12) && isfinite(rho[1]);
+                p.m_use[j] = fin ? 1 : 0;
+                if (fin) {
+                    const double w = rho[1] * p.marker_info;
+                    const double r0 = rho[1] * -(p.marker_info * err[0]), r1 = rho[1] * -(p.marker_info * err[1]);
+                    double* out = p.m_blk + (size_t)j * LBA_MBLK;
+                    lba_diag_block(Jc, w, r0, r1, out);
+                    lba_diag_block(Jm, w, r0, r1, out + 27);
+                    for (int a = 0; a < 6; a++)
+                        for (int cc = 0; cc < 6; cc++) out[54 + a * 6 + cc] = Jc[0][a] * (w * Jm[0][cc]) + Jc[1][a] * (w * Jm[1][cc]);
+                }
+            }
+        }
+    }
+    chi = wave_sum(chi);
+    md = wave_max(md);
+    if (threadIdx.x == 0) {
+        p.chi_part[blockIdx.x] = chi;
+        p.max_part[blockIdx.x] = md;
+    }
+}
+
+// Hpp and bp of free vertex v: a keyframe's monocular edges in point order (each thread a contiguous run of points), then its marker
+// edges in edge order; a marker's edges in edge order
+__global__ __launch_bounds__(LM_THREADS) void k_lba_pose_blocks(LbaP p)
+{
+    __shared__ double red[LM_WAVES * 28];
+    const LbaCtl& c = *p.ctl;
+    const int v = blockIdx.x, tid = threadIdx.x;
+    if (c.aborted || !c.iter_go || v >= c.nv) return;
+    const int kf = p.v_kf[v];
+    double s[28];
+    for (int k = 0; k < 28; k++) s[k] = 0;
+    if (kf < p.nkf) {
+        const int per = (p.np + LM_THREADS - 1) / LM_THREADS;
+        const int lo = min(tid * per, p.np), hi = min(lo + per, p.np);
+        for (int pi = lo; pi < hi; pi++) {
+            const int e = p.tbl[(size_t)kf * p.np + pi];
+            if (e < 0 || p.e_level[e]) continue;
+            s[27] += 1;
+            if (p.e_use[e] != 3) continue;
+            const double* blk = p.e_blk + (size_t)e * LBA_EBLK;
+            for (int k = 0; k < 27; k++) s[k] += blk[k];
+        }
+    }
+    block_sum<28>(s, red);
+    if (tid != 0) return;
+    if (kf < p.nkf) {
+        for (int j = 0; j < p.nme; j++) {
+            if (p.mobs_kf[j >> 2] != kf || p.m_level[j]) continue;
+            s[27] += 1;
+            if (!p.m_use[j]) continue;
+            const double* blk = p.m_blk + (size_t)j * LBA_MBLK;
+            for (int k = 0; k < 27; k++) s[k] += blk[k];
+        }
+    } else {
+        const int m = kf - p.nkf;
+        for (int j = 4 * p.mobs_offset[m]; j < 4 * p.mobs_offset[m + 1]; j++) {
+            if (p.m_level[j]) continue;
+            s[27] += 1;
+            if (!p.m_use[j]) continue;
+            const double* blk = p.m_blk + (size_t)j * LBA_MBLK + 27;
+            for (int k = 0; k < 27; k++) s[k] += blk[k];
+        }
+    }
+    double* H = p.Hpp + (size_t)v * 36;
+    int k = 0;
+    double md = 0;
+    for (int a = 0; a < 6; a++)
+        for (int cc = a; cc < 6; cc++, k++) H[a * 6 + cc] = H[cc * 6 + a] = s[k];
+    for (int a = 0; a < 6; a++) {
+        p.bp[v * 6 + a] = s[21 + a];
+        md = fmax(md, fabs(s[a * 6 - a * (a - 1) / 2]));   // the diagonal entries of the packed upper triangle: 0, 6, 11, 15, 18, 20
+    }
+    p.v_active[v] = s[27] > 0;
+    p.vmax[v] = s[27] > 0 ? md : 0;
+}
+
+// the sum of n per-workgroup partial sums: each thread a contiguous run, then the workgroup (valid in thread 0)
+__device__ __forceinline__ double part_sum(const double* part, int n)
+{
+    const int per = (n + LM_THREADS - 1) / LM_THREADS;
+    const int lo = min((int)threadIdx.x * per, n), hi = min(lo + per, n);
+    double s = 0;
+    for (int i = lo; i < hi; i++) s += part[i];
+    return s;
+}
+
+__global__ __launch_bounds__(LM_THREADS) void k_lba_ctl_lin(LbaP p)
+{
+    __shared__ double red[LM_WAVES];
+    __shared__ double mx[LM_THREADS];
+    LbaCtl& c = *p.ctl;
+    if (c.aborted || !c.iter_go) return;
+    double s[1] = {part_sum(p.chi_part, p.nb)};
+    double m = 0;
+    for (int i = threadIdx.x; i < p.nb; i += LM_THREADS) m = fmax(m, p.max_part[i]);
+    mx[threadIdx.x] = m;
+    block_sum<1>(s, red);
+    if (threadIdx.x != 0) return;
+    c.currentChi = c.iniChi = s[0];
+    if (c.it == 0) {
+        double md = 0;
+        for (int i = 0; i < LM_THREADS; i++) md = fmax(md, mx[i]);
+        for (int v = 0; v < c.nv; v++) md = fmax(md, p.vmax[v]);
+        c.lambda = c.lambda0 = 1e-5 * md;
+        c.ni = 2;
+        c.nbad_lm = 0;
+    }
+    c.rho = 0;
+    c.q = 0;
+    c.trial_go = 1;
+}
+
+// ---------------------------------------------------------------------------------------- a trial --
+// (Hll + lambda I)^-1 by cofactors (Eigen's 3 x 3 inverse)
+__global__ __launch_bounds__(LBA_PT) void k_lba_schur_points(LbaP p)
+{
+    const LbaCtl& c = *p.ctl;
+    if (c.aborted || !c.trial_go) return;
+    const int pi = blockIdx.x * LBA_PT + threadIdx.x;
+    if (pi >= p.np || !p.p_active[pi]) return;
+    const double* H = p.Hll + (size_t)pi * 6;
+    const double m00 = H[0] + c.lambda, m01 = H[1], m02 = H[2], m11 = H[3] + c.lambda, m12 = H[4], m22 = H[5] + c.lambda;
+    const double c00 = m11 * m22 - m12 * m12, c10 = m12 * m02 - m01 * m22, c20 = m01 * m12 - m11 * m02;
+    const double det = c00 * m00 + c10 * m01 + c20 * m02, id = 1. / det;
+    double* D = p.Dinv + (size_t)pi * 9;
+    D[0] = c00 * id; D[1] = c10 * id; D[2] = c20 * id;
+    D[3] = D[1]; D[4] = (m00 * m22 - m02 * m02) * id; D[5] = (m02 * m01 - m00 * m12) * id;
+    D[6] = D[2]; D[7] = D[5]; D[8] = (m00 * m11 - m01 * m01) * id;
+}
+
+// block (i, j), i <= j, of S and the rows i of its right-hand side; one wave
+__global__ __launch_bounds__(64) void k_lba_assemble(LbaP p)
+{
+    const LbaCtl& c = *p.ctl;
+    const int i = blockIdx.y, j = blockIdx.x, lane = threadIdx.x;
+    if (c.aborted || !c.trial_go || i > j || j >= c.nv) return;
+    const int ki = p.v_kf[i], kj = p.v_kf[j];
+    const bool act = p.v_active[i] && p.v_active[j];
+    double acc[36], accb[6];
+    for (int k = 0; k < 36; k++) acc[k] = 0;
+    for (int k = 0; k < 6; k++) accb[k] = 0;
+    if (act && ki < p.nkf && kj < p.nkf) {
+        const int per = (p.np + 63) / 64;
+        const int lo = min(lane * per, p.np), hi = min(lo + per, p.np);
+        for (int pi = lo; pi < hi; pi++) {
+            if (!p.p_active[pi]) continue;
+            const int ei = p.tbl[(size_t)ki * p.np + pi], ej = p.tbl[(size_t)kj * p.np + pi];
+            if (ei < 0 || ej < 0 || p.e_level[ei] || p.e_level[ej] || p.e_use[ei] != 3 || p.e_use[ej] != 3) continue;
+            const double* Wi = p.e_blk + (size_t)ei * LBA_EBLK + 27;
+            const double* Wj = p.e_blk + (size_t)ej * LBA_EBLK + 27;
+            const double* D = p.Dinv + (size_t)pi * 9;
+            const double* bl = p.bl + (size_t)pi * 3;
+            for (int a = 0; a < 6; a++) {
+                double Y[3];
+                for (int cc = 0; cc < 3; cc++) Y[cc] = Wi[a * 3] * D[cc] + Wi[a * 3 + 1] * D[3 + cc] + Wi[a * 3 + 2] * D[6 + cc];
+                for (int bb = 0; bb < 6; bb++) acc[a * 6 + bb] += Y[0] * Wj[bb * 3] + Y[1] * Wj[bb * 3 + 1] + Y[2] * Wj[bb * 3 + 2];
+                if (i == j) accb[a] += Y[0] * bl[0] + Y[1] * bl[1] + Y[2] * bl[2];
+            }
+        }
+        for (int k = 0; k < 36; k++) acc[k] = wave_sum(acc[k]);
+        if (i == j)
+            for (int k = 0; k < 6; k++) accb[k] = wave_sum(accb[k]);
+    }
+    if (lane != 0) return;
+    double B[36];
+    for (int k = 0; k < 36; k++) B[k] = 0;
+    if (!act) {
+        // a vertex without an active edge is not part of the system: an identity block, a zero right-hand side
+        if (i == j)
+            for (int a = 0; a < 6; a++) B[a * 6 + a] = 1;
+    } else if (i == j) {
+        for (int k = 0; k < 36; k++) B[k] = p.Hpp[(size_t)i * 36 + k];
+        for (int a = 0; a < 6; a++) B[a * 6 + a] += c.lambda;
+        for (int k = 0; k < 36; k++) B[k] -= acc[k];
+    } else if (kj < p.nkf) {
+        for (int k = 0; k < 36; k++) B[k] = 0. - acc[k];
+    } else if (ki < p.nkf) {
+        const int m = kj - p.nkf;
+        for (int e = 4 * p.mobs_offset[m]; e < 4 * p.mobs_offset[m + 1]; e++) {
+            if (p.mobs_kf[e >> 2] != ki || p.m_level[e] || !p.m_use[e]) continue;
+            const double* blk = p.m_blk + (size_t)e * LBA_MBLK + 54;
+            for (int k = 0; k < 36; k++) B[k] += blk[k];
+        }
+    }
+    for (int a = 0; a < 6; a++)
+        for (int bb = 0; bb < 6; bb++) {
+            p.S[(size_t)(6 * i + a) * LBA_N + 6 * j + bb] = B[a * 6 + bb];
+            p.S[(size_t)(6 * j + bb) * LBA_N + 6 * i + a] = B[a * 6 + bb];
+        }
+    if (i == j)
+        for (int a = 0; a < 6; a++) p.bs[6 * i + a] = act ? p.bp[6 * i + a] - accb[a] : 0.;
+}
+
+// S = L L^T in place (lower triangle, right-looking, no pivoting), L y = b, L^T x = y; y holds b on entry and x on return (when the
+// factorisation succeeds: the return value).  PACKED: M is the lower triangle row after row (the LDS copy), else rows of LBA_N.
+template <bool PACKED> __device__ __forceinline__ bool lba_llt_solve(double* M, int n, double* y, int* fail_s)
+{
+    const int tid = threadIdx.x;
+    auto row = [](int i) { return PACKED ? (size_t)i * (i + 1) / 2 : (size_t)i * LBA_N; };
+    for (int k = 0; k < n; k++) {
+        if (tid == 0) {
+            const double d = M[row(k) + k];
+            if (!(d > 0) || !isfinite(d)) *fail_s = 1;
+            else M[row(k) + k] = sqrt(d);
+        }
+        __syncthreads();
+        if (*fail_s) return false;
+        const double lkk = M[row(k) + k];
+        for (int i = k + 1 + tid; i < n; i += LM_THREADS) M[row(i) + k] /= lkk;
+        __syncthreads();
+        for (int i = k + 1 + (tid >> 4); i < n; i += LM_THREADS / 16) {
+            const double lik = M[row(i) + k];
+            for (int j = k + 1 + (tid & 15); j <= i; j += 16) M[row(i) + j] -= lik * M[row(j) + k];
+        }
+        __syncthreads();
+    }
+    for (int k = 0; k < n; k++) {
+        if (tid == 0) y[k] /= M[row(k) + k];
+        __syncthreads();
+        const double yk = y[k];
+        for (int i = k + 1 + tid; i < n; i += LM_THREADS) y[i] -= M[row(i) + k] * yk;
+        __syncthreads();
+    }
+    for (int k = n - 1; k >= 0; k--) {
+        if (tid == 0) y[k] /= M[row(k) + k];
+        __syncthreads();
+        const double yk = y[k];
+        for (int i = tid; i < k; i += LM_THREADS) y[i] -= M[row(k) + i] * yk;
+        __syncthreads();
+    }
+    return true;
+}
+
+// The reduced solve and the trial poses exp(x_v) T_v.  One workgroup: the factorisation is a chain of 3 n barrier-separated steps, so
+// it runs on a copy of the lower triangle in LDS when n <= lds_rows (what the launch reserved), and in global memory otherwise; the
+// arithmetic and its order are the same.
+__global__ __launch_bounds__(LM_THREADS) void k_lba_solve(LbaP p, int lds_rows)
+{
+    extern __shared__ __align__(16) double lba_tri[];
+    __shared__ double y[LBA_N];
+    __shared__ int fail_s;
+    LbaCtl& c = *p.ctl;
+    if (c.aborted || !c.trial_go) return;
+    const int tid = threadIdx.x, n = 6 * c.nv, cur = c.cur;
+    if (tid == 0) fail_s = 0;
+    for (int i = tid; i < n; i += LM_THREADS) y[i] = p.bs[i];
+    bool ok;
+    if (n <= lds_rows) {
+        for (int i = 0; i < n; i++)
+            for (int j = tid; j <= i; j += LM_THREADS) lba_tri[(size_t)i * (i + 1) / 2 + j] = p.S[(size_t)i * LBA_N + j];
+        __syncthreads();
+        ok = lba_llt_solve<true>(lba_tri, n, y, &fail_s);
+    } else {
+        __syncthreads();
+        ok = lba_llt_solve<false>(p.S, n, y, &fail_s);
+    }
+    if (ok)
+        for (int i = tid; i < n; i += LM_THREADS) p.xv[i] = y[i];
+    __syncthreads();
+    if (tid == 0) c.ok2 = ok;
+    if (tid < c.nv) {
+        const int idx = p.v_kf[tid];
+        SE3 T = p.pose[cur][idx];
+        if (p.v_active[tid]) {
+            double u[6];
+            for (int a = 0; a < 6; a++) u[a] = p.xv[tid * 6 + a];
+            T = mul(se3_exp(u), T);
+        }
+        p.pose[1 - cur][idx] = T;
+    }
+}
+
+// the point's update xl = D^-1 (bl - sum W^T x_pose), the trial point, the trial errors of every active edge
+__global__ __launch_bounds__(LBA_PT) void k_lba_backsub(LbaP p)
+{
+    const LbaCtl& c = *p.ctl;
+    if (c.aborted || !c.trial_go) return;
+    const int cur = c.cur, nxt = 1 - cur;
+    const bool robust = c.round == 0;
+    double chi = 0, scale = 0;
+    if ((int)blockIdx.x < p.npb) {
+        const int pi = blockIdx.x * LBA_PT + threadIdx.x;
+        if (pi < p.np) {
+            double X[3] = {p.pt[cur][(size_t)pi * 3], p.pt[cur][(size_t)pi * 3 + 1], p.pt[cur][(size_t)pi * 3 + 2]};
+            if (p.p_active[pi]) {
+                const int lo = p.obs_offset[pi], hi = p.obs_offset[pi + 1];
+                double* xl = p.xl + (size_t)pi * 3;
+                const double* bl = p.bl + (size_t)pi * 3;
+                if (c.ok2) {
+                    double r[3] = {bl[0], bl[1], bl[2]};
+                    for (int e = lo; e < hi; e++) {
+                        if (p.e_level[e] || p.e_use[e] != 3) continue;
+                        const double* W = p.e_blk + (size_t)e * LBA_EBLK + 27;
+                        const double* x = p.xv + (size_t)p.kf_free[p.e_kf[e]] * 6;
+                        for (int cc = 0; cc < 3; cc++) {
+                            double s = 0;
+                            for (int a = 0; a < 6; a++) s += W[a * 3 + cc] * x[a];
+                            r[cc] -= s;
+                        }
+                    }
+                    const double* D = p.Dinv + (size_t)pi * 9;
+                    for (int a = 0; a < 3; a++) xl[a] = D[a * 3] * r[0] + D[a * 3 + 1] * r[1] + D[a * 3 + 2] * r[2];
+                }
+                for (int a = 0; a < 3; a++) {
+                    scale += xl[a] * (c.lambda * xl[a] + bl[a]);
+                    X[a] += xl[a];
+                }
+                for (int e = lo; e < hi; e++) {
+                    if (p.e_level[e]) continue;
+                    double err[2], rho[2];
+                    lba_mono_error(p.pose[nxt][p.e_kf[e]], X, p.e_ox[e], p.e_oy[e], p.K, err);
+                    const double ch = chi2_of(err, (double)p.e_info[e]);
+                    p.e_chi2[e] = ch;
+                    rho[0] = ch;
+                    if (robust) huber(ch, p.delta, rho);
+                    chi += rho[0];
+                }
+            }
+            for (int a = 0; a < 3; a++) p.pt[nxt][(size_t)pi * 3 + a] = X[a];
+        }
+    } else {
+        const int j = (blockIdx.x - p.npb) * LBA_PT + threadIdx.x;
+        if (j < p.nme && !p.m_level[j]) {
+            const int o = j >> 2, k = j & 3, m = p.mo_marker[o];
+            const double pm[3] = {p.mlocal[(size_t)m * 12 + 3 * k], p.mlocal[(size_t)m * 12 + 3 * k + 1], p.mlocal[(size_t)m * 12 + 3 * k + 2]};
+            double err[2], rho[2];
+            lba_marker_error(p.pose[nxt][p.mobs_kf[o]], p.pose[nxt][p.nkf + m], pm, p.mobs_corners[(size_t)o * 8 + 2 * k],
+                             p.mobs_corners[(size_t)o * 8 + 2 * k + 1], p.K, err);
+            const double ch = chi2_of(err, p.marker_info);
+            p.m_chi2[j] = ch;
+            rho[0] = ch;
+            if (robust) huber(ch, p.delta, rho);
+            chi += rho[0];
+        }
+    }
+    chi = wave_sum(chi);
+    scale = wave_sum(scale);
+    if (threadIdx.x == 0) {
+        p.chi_part[blockIdx.x] = chi;
+        p.scale_part[blockIdx.x] = scale;
+    }
+}
+
+// OptimizationAlgorithmLevenberg::solve behind the trial's chi2: rho, accept or reject, lambda and nu, the end of the iteration
+__global__ __launch_bounds__(LM_THREADS) void k_lba_ctl_trial(LbaP p, int maxit)
+{
+    __shared__ double red[LM_WAVES * 2];
+    LbaCtl& c = *p.ctl;
+    if (c.aborted || !c.trial_go) return;
+    double s[2] = {part_sum(p.chi_part, p.nb), part_sum(p.scale_part, p.nb)};
+    block_sum<2>(s, red);
+    if (threadIdx.x != 0) return;
+    double tempChi = s[0];
+    if (!c.ok2) tempChi = DBL_MAX;
+    double scale = 0;
+    for (int j = 0; j < 6 * c.nv; j++) scale += p.xv[j] * (c.lambda * p.xv[j] + (p.v_active[j / 6] ? p.bp[j] : 0.));
+    scale += s[1];
+    scale += 1e-3;
+    double rho = (c.currentChi - tempChi);
+    rho /= scale;
+    if (rho > 0 && isfinite(tempChi)) {
+        double alpha = 1. - pow((2 * rho - 1), 3.0);
+        alpha = fmin(alpha, 2. / 3.);
+        const double sf = fmax(1. / 3., alpha);
+        c.lambda *= sf;
+        c.ni = 2;
+        c.currentChi = tempChi;
+        c.cur = 1 - c.cur;
+        c.stale = 0;
+    } else {
+        c.lambda *= c.ni;
+        c.ni *= 2;
+        c.stale = 1;
+    }
+    c.rho = rho;
+    c.q++;
+    const bool halt = stop_set(p);
+    const bool cont = rho < 0 && c.q < 10 && !halt;
+    c.trial_go = cont;
+    if (cont) return;
+    c.it++;
+    c.iters[c.round] = c.it;
+    c.stale_mask = (c.stale_mask & ~(1 << c.round)) | (c.stale << c.round);
+    bool stop = c.q == 10 || rho == 0;
+    if (!stop) {
+        if ((c.iniChi - c.currentChi) * 1e3 < c.iniChi) c.nbad_lm++;
+        else c.nbad_lm = 0;
+        stop = c.nbad_lm >= 3;
+    }
+    if (halt) c.stopped = 1;
+    c.iter_go = !stop && !halt && c.it < maxit;
+}
+
+// ---------------------------------------------------------------------------------------- checks and the end --
+__global__ __launch_bounds__(256) void k_lba_check(LbaP p, int second)
+{
+    LbaCtl& c = *p.ctl;
+    if (c.aborted || (!second && c.stopped)) return;
+    const int i = blockIdx.x * 256 + threadIdx.x, cur = c.cur;
+    if (i < p.nobs) {
+        const double* X = p.pt[cur] + (size_t)p.e_pt[i] * 3;
+        const double Xw[3] = {X[0], X[1], X[2]};
+        double Xc[3];
+        map(p.pose[cur][p.e_kf[i]], Xw, Xc);
+        const bool bad = !(p.e_chi2[i] <= 5.991) || !(Xc[2] > 0.0);
+        if (second) {
+            p.erase[i] = bad;
+            if (bad) atomicAdd(&c.n_erase, 1);
+        } else if (bad) {
+            p.e_level[i] = 1;
+            atomicAdd(&c.n_level1[0], 1);
+        }
+    } else if (!second && i - p.nobs < p.nme) {
+        const int j = i - p.nobs;
+        if (!(p.m_chi2[j] <= 5.991)) {
+            p.m_level[j] = 1;
+            atomicAdd(&c.n_level1[1], 1);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_lba_finish(LbaP p)
+{
+    const LbaCtl& c = *p.ctl;
+    const int i = blockIdx.x * 256 + threadIdx.x, cur = c.cur;
+    if (i == 0) {
+        orbfe_lba_result r{};
+        r.status = c.abort_status;
+        if (!c.aborted) {
+            r.n_edges_mono = p.nobs;
+            r.n_edges_marker = p.nme;
+            r.n_level1[0] = c.n_level1[0]; r.n_level1[1] = c.n_level1[1];
+            r.n_erase = c.n_erase;
+            r.iterations[0] = c.iters[0]; r.iterations[1] = c.iters[1];
+            r.stale_mask = c.stale_mask;
+        }
+        *p.res = r;
+    }
+    if (c.aborted) return;
+    if (i < p.nkf && p.kf_free[i] >= 0) to_float(p.pose[cur][i], p.Tcw + (size_t)i * 12);
+    if (i < p.nma && p.use_markers) to_float(p.pose[cur][p.nkf + i], p.Twm + (size_t)i * 12);
+    if (i < p.np)
+        for (int k = 0; k < 3; k++) p.x3Dw[(size_t)i * 3 + k] = (float)p.pt[cur][(size_t)i * 3 + k];
+}
+
+// ---------------------------------------------------------------------------------------- host --
+int lba_fill(LbaP& p, const float* K4, const float* inv_sigma2, int nlevels, float marker_info, const char* name)
+{
+    if (!K4 || !inv_sigma2 || nlevels <= 0 || nlevels > LBA_MAX_LEVELS) return fail(ORBFE_ERR_INVALID, "%s: invalid K4 / sigma table", name);
+    for (int i = 0; i < 4; i++)
+        if (!std::isfinite(K4[i])) return fail(ORBFE_ERR_INVALID, "%s: K is not finite", name);
+    if (K4[0] == 0 || K4[1] == 0) return fail(ORBFE_ERR_INVALID, "%s: fx or fy is 0", name);
+    if (!std::isfinite(marker_info)) return fail(ORBFE_ERR_INVALID, "%s: marker_info is not finite", name);
+    for (int l = 0; l < nlevels; l++)
+        if (!std::isfinite(inv_sigma2[l])) return fail(ORBFE_ERR_INVALID, "%s: inv_level_sigma2 is not finite", name);
+    p.nlevels = nlevels;
+    for (int l = 0; l < LBA_MAX_LEVELS; l++) p.inv_sigma2[l] = l < nlevels ? inv_sigma2[l] : 0.f;
+    p.K = Cam{K4[0], K4[1], K4[2], K4[3]};
+    p.marker_info = marker_info;
+    p.delta = (double)(float)std::sqrt(5.991);
+    return ORBFE_OK;
+}
+
+// the launches of one call: inspect = one linearisation and one trial, nothing written to the caller's arrays
+int lba_enqueue(LbaP& p, void* scratch, hipStream_t s, bool inspect)
+{
+    const LbaLayout l = lba_layout(p.nkf, p.np, p.nobs, p.nma, p.nmobs);
+    lba_bind(p, l, scratch);
+    p.nme = p.use_markers ? 4 * p.nmobs : 0;
+    if (!p.use_markers) p.nb = p.npb;
+    ORBFE_HIP(hipMemsetAsync(scratch, 0, l.zero_end, s));
+    ORBFE_HIP(hipMemsetAsync(p.tbl, 0xff, l.tbl_bytes, s));
+    const int nmax = std::max(std::max(p.nobs, p.np), std::max(p.nkf + p.nma, p.nmobs));
+    const dim3 gsetup((nmax + 255) / 256 > 0 ? (nmax + 255) / 256 : 1), gpt(std::max(p.nb, 1)), gpo(std::max(p.npb, 1));
+    const dim3 gedge((p.nobs + p.nme + 255) / 256 > 0 ? (p.nobs + p.nme + 255) / 256 : 1);
+    // the free vertices are counted on the device; the host knows an upper bound, which keeps the grids of the per-vertex kernels small
+    const int vmax = std::max(1, std::min(LBA_MAXV, p.nkf + (p.use_markers ? p.nma : 0)));
+    // the reduced system's lower triangle in LDS, as many rows as the workgroup may have (the kernel's own 3 KB aside)
+    int lds_rows = 6 * vmax;
+    while (lds_rows > 0 && (size_t)lds_rows * (lds_rows + 1) / 2 * 8 + 4096 > (size_t)max_lds()) lds_rows -= 6;
+    const size_t tri_bytes = (size_t)lds_rows * (lds_rows + 1) / 2 * 8;
+    int rc = ensure_dyn_lds((const void*)k_lba_solve, tri_bytes);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_lba_setup, gsetup, dim3(256), 0, s, p);
+    for (int round = 0; round < (inspect ? 1 : 2); round++) {
+        hipLaunchKernelGGL(k_lba_begin, dim3(1), dim3(64), 0, s, p, round);
+        if (round == 1) hipLaunchKernelGGL(k_lba_check, gedge, dim3(256), 0, s, p, 0);
+        const int maxit = inspect ? 1 : round == 0 ? 5 : 10;
+        for (int it = 0; it < maxit; it++) {
+            hipLaunchKernelGGL(k_lba_linearize, gpt, dim3(LBA_PT), 0, s, p);
+            hipLaunchKernelGGL(k_lba_pose_blocks, dim3(vmax), dim3(LM_THREADS), 0, s, p);
+            hipLaunchKernelGGL(k_lba_ctl_lin, dim3(1), dim3(LM_THREADS), 0, s, p);
+            for (int q = 0; q < (inspect ? 1 : 10); q++) {
+                hipLaunchKernelGGL(k_lba_schur_points, gpo, dim3(LBA_PT), 0, s, p);
+                hipLaunchKernelGGL(k_lba_assemble, dim3(vmax, vmax), dim3(64), 0, s, p);
+                hipLaunchKernelGGL(k_lba_solve, dim3(1), dim3(LM_THREADS), tri_bytes, s, p, lds_rows);
+                hipLaunchKernelGGL(k_lba_backsub, gpt, dim3(LBA_PT), 0, s, p);
+                if (!inspect) hipLaunchKernelGGL(k_lba_ctl_trial, dim3(1), dim3(LM_THREADS), 0, s, p, maxit);
+            }
+        }
+    }
+    if (!inspect) {
+        hipLaunchKernelGGL(k_lba_check, gedge, dim3(256), 0, s, p, 1);
+        hipLaunchKernelGGL(k_lba_finish, gsetup, dim3(256), 0, s, p);
+    }
+    ORBFE_HIP(hipGetLastError());
+    return ORBFE_OK;
+}
+
+bool lba_sizes_ok(int nkf, int np, int nobs, int nma, int nmobs)
+{
+    return nkf >= 0 && np >= 0 && nobs >= 0 && nma >= 0 && nmobs >= 0 && (size_t)std::max(nkf, 1) * (size_t)std::max(np, 1) < ((size_t)1 << 30) &&
+           nmobs < (1 << 24);
+}
+
+thread_local ThreadWorkspaces<HostStage> tl_lba_stages;
+
+// the checks of the host call (the device call leaves them to k_lba_setup / k_lba_begin)
+int lba_check_host(const float* Tcw, const uint8_t* kf_fixed, int nkf, const float* x3Dw, int np, const int32_t* obs_offset,
+                   const int32_t* obs_kf, const float* obs_xy, const int32_t* obs_octave, int nobs, int nlevels, const float* Twm,
+                   const float* marker_local, int nma, const int32_t* mobs_offset, const int32_t* mobs_kf, const float* mobs_corners, int nmobs,
+                   int use_markers, const char* name)
+{
+    if (!lba_sizes_ok(nkf, np, nobs, nma, nmobs) || (nkf && (!Tcw || !kf_fixed)) || (np && (!x3Dw || !obs_offset)) ||
+        (nobs && (!obs_kf || !obs_xy || !obs_octave || !np)) || (nma && (!Twm || !marker_local || !mobs_offset)) ||
+        (nmobs && (!mobs_kf || !mobs_corners || !nma)))
+        return fail(ORBFE_ERR_INVALID, "%s: invalid argument", name);
+    auto fin = [](const float* v, size_t n) {
+        for (size_t i = 0; i < n; i++)
+            if (!std::isfinite(v[i])) return false;
+        return true;
+    };
+    if (!fin(Tcw, (size_t)nkf * 12) || !fin(x3Dw, (size_t)np * 3) || !fin(obs_xy, (size_t)nobs * 2) || !fin(Twm, (size_t)nma * 12) ||
+        !fin(marker_local, (size_t)nma * 12) || !fin(mobs_corners, (size_t)nmobs * 8))
+        return fail(ORBFE_ERR_INVALID, "%s: an input is not finite", name);
+    if (np && (obs_offset[0] != 0 || obs_offset[np] != nobs)) return fail(ORBFE_ERR_INVALID, "%s: obs_offset does not span [0, nobs]", name);
+    if (!np && nobs) return fail(ORBFE_ERR_INVALID, "%s: observations without points", name);
+    for (int i = 0; i < np; i++)
+        if (obs_offset[i + 1] < obs_offset[i]) return fail(ORBFE_ERR_INVALID, "%s: obs_offset decreases at point %d", name, i);
+    if (nma && (mobs_offset[0] != 0 || mobs_offset[nma] != nmobs)) return fail(ORBFE_ERR_INVALID, "%s: mobs_offset does not span [0, nmobs]", name);
+    for (int i = 0; i < nma; i++)
+        if (mobs_offset[i + 1] < mobs_offset[i]) return fail(ORBFE_ERR_INVALID, "%s: mobs_offset decreases at marker %d", name, i);
+    for (int e = 0; e < nobs; e++) {
+        if (obs_kf[e] < 0 || obs_kf[e] >= nkf) return fail(ORBFE_ERR_INVALID, "%s: observation %d names keyframe %d of %d", name, e, obs_kf[e], nkf);
+        if (obs_octave[e] < 0 || obs_octave[e] >= nlevels)
+            return fail(ORBFE_ERR_INVALID, "%s: observation %d has octave %d, outside [0, %d)", name, e, obs_octave[e], nlevels);
+    }
+    for (int e = 0; e < nmobs; e++)
+        if (mobs_kf[e] < 0 || mobs_kf[e] >= nkf) return fail(ORBFE_ERR_INVALID, "%s: marker observation %d names keyframe %d of %d", name, e, mobs_kf[e], nkf);
+    std::vector<int> seen((size_t)std::max(nkf, 1), -1);
+    for (int i = 0; i < np; i++)
+        for (int e = obs_offset[i]; e < obs_offset[i + 1]; e++) {
+            if (seen[(size_t)obs_kf[e]] == i) return fail(ORBFE_ERR_INVALID, "%s: keyframe %d observes point %d twice", name, obs_kf[e], i);
+            seen[(size_t)obs_kf[e]] = i;
+        }
+    int nv = use_markers ? nma : 0;
+    for (int k = 0; k < nkf; k++) nv += kf_fixed[k] == 0;
+    if (nv > LBA_MAXV)
+        return fail(ORBFE_ERR_CAPACITY, "%s: %d free pose vertices (keyframes and markers), at most ORBFE_LBA_MAX_FREE_POSES = %d", name, nv, LBA_MAXV);
+    for (int i = 0; i < np; i++)
+        if (obs_offset[i + 1] - obs_offset[i] > ORBFE_LBA_MAX_OBSERVATIONS)
+            return fail(ORBFE_ERR_CAPACITY, "%s: point %d has %d observations, at most ORBFE_LBA_MAX_OBSERVATIONS = %d", name, i,
+                        obs_offset[i + 1] - obs_offset[i], ORBFE_LBA_MAX_OBSERVATIONS);
+    return ORBFE_OK;
+}
+
+struct LbaHostIo {
+    size_t fixed, off, kf, xy, oct, mloc, moff, mkf, mcor, T, X, M, erase, res;
+};
+
+// stage a problem of host arrays: everything up, the estimates, the erase bytes and the record down
+int lba_stage(HostStage& w, LbaHostIo& io, LbaP& p, const float* Tcw, const uint8_t* kf_fixed, int nkf, const float* x3Dw, int np,
+              const int32_t* obs_offset, const int32_t* obs_kf, const float* obs_xy, const int32_t* obs_octave, int nobs, const float* Twm,
+              const float* marker_local, int nma, const int32_t* mobs_offset, const int32_t* mobs_kf, const float* mobs_corners, int nmobs)
+{
+    const size_t K = (size_t)std::max(nkf, 1), P = (size_t)std::max(np, 1), E = (size_t)std::max(nobs, 1), M = (size_t)std::max(nma, 1),
+                 MO = (size_t)std::max(nmobs, 1);
+    IoLayout l;
+    io.fixed = l.take(K); io.off = l.take((P + 1) * 4); io.kf = l.take(E * 4); io.xy = l.take(E * 8); io.oct = l.take(E * 4);
+    io.mloc = l.take(M * 48); io.moff = l.take((M + 1) * 4); io.mkf = l.take(MO * 4); io.mcor = l.take(MO * 32);
+    l.inout();
+    io.T = l.take(K * 48); io.X = l.take(P * 12); io.M = l.take(M * 48);
+    l.outputs();
+    io.erase = l.take(E); io.res = l.take(sizeof(orbfe_lba_result));
+    int rc;
+    if ((rc = w.begin(l))) return rc;
+    const int32_t zero2[2] = {0, 0};
+    w.put(io.fixed, kf_fixed, (size_t)nkf);
+    w.put(io.off, np ? (const void*)obs_offset : (const void*)zero2, np ? (size_t)(np + 1) * 4 : 8);
+    w.put(io.kf, obs_kf, (size_t)nobs * 4); w.put(io.xy, obs_xy, (size_t)nobs * 8); w.put(io.oct, obs_octave, (size_t)nobs * 4);
+    w.put(io.mloc, marker_local, (size_t)nma * 48);
+    w.put(io.moff, nma ? (const void*)mobs_offset : (const void*)zero2, nma ? (size_t)(nma + 1) * 4 : 8);
+    w.put(io.mkf, mobs_kf, (size_t)nmobs * 4); w.put(io.mcor, mobs_corners, (size_t)nmobs * 32);
+    w.put(io.T, Tcw, (size_t)nkf * 48); w.put(io.X, x3Dw, (size_t)np * 12); w.put(io.M, Twm, (size_t)nma * 48);
+    if ((rc = w.upload())) return rc;
+    // upload() sends [0, split): the in-out arrays lie before the split
+    p.kf_fixed = w.dev<const uint8_t>(io.fixed); p.obs_offset = w.dev<const int32_t>(io.off); p.obs_kf = w.dev<const int32_t>(io.kf);
+    p.obs_xy = w.dev<const float>(io.xy); p.obs_oct = w.dev<const int32_t>(io.oct); p.obs_feat = nullptr; p.kps = nullptr; p.capacity = 0;
+    p.mlocal = w.dev<const float>(io.mloc); p.mobs_offset = w.dev<const int32_t>(io.moff); p.mobs_kf = w.dev<const int32_t>(io.mkf);
+    p.mobs_corners = w.dev<const float>(io.mcor);
+    p.Tcw = w.dev<float>(io.T); p.x3Dw = w.dev<float>(io.X); p.Twm = w.dev<float>(io.M);
+    p.erase = w.dev<uint8_t>(io.erase); p.res = w.dev<orbfe_lba_result>(io.res);
+    p.nkf = nkf; p.np = np; p.nobs = nobs; p.nma = nma; p.nmobs = nmobs;
+    return ORBFE_OK;
+}
+
+} // namespace
+} // namespace orbfe
+
+using namespace orbfe;
+
+extern "C" size_t orbfe_lba_scratch_bytes(int nkf, int np, int nobs, int nma, int nmobs)
+{
+    if (!lba_sizes_ok(nkf, np, nobs, nma, nmobs)) return 0;
+    return lba_layout(nkf, np, nobs, nma, nmobs).end;
+}
+
+extern "C" int orbfe_local_bundle_adjustment(float* Tcw, const uint8_t* kf_fixed, int nkf, float* x3Dw, int np, const int32_t* obs_offset,
+                                             const int32_t* obs_kf, const float* obs_xy, const int32_t* obs_octave, int nobs, const float* K4,
+                                             const float* inv_level_sigma2, int nlevels, float* Twm, const float* marker_local, int nma,
+                                             const int32_t* mobs_offset, const int32_t* mobs_kf, const float* mobs_corners, int nmobs,
+                                             float marker_info, int use_markers, const uint8_t* stop, uint8_t* erase, orbfe_lba_result* res,
+                                             int device)
+{
+    static const char* name = "orbfe_local_bundle_adjustment";
+    if (!res || (nobs > 0 && !erase)) return fail(ORBFE_ERR_INVALID, "%s: invalid argument", name);
+    LbaP p{};
+    int rc = lba_fill(p, K4, inv_level_sigma2, nlevels, marker_info, name);
+    if (rc) return rc;
+    if ((rc = lba_check_host(Tcw, kf_fixed, nkf, x3Dw, np, obs_offset, obs_kf, obs_xy, obs_octave, nobs, nlevels, Twm, marker_local, nma,
+                             mobs_offset, mobs_kf, mobs_corners, nmobs, use_markers, name)))
+        return rc;
+    if (stop && *stop) {
+        orbfe_lba_result r{};
+        r.status = ORBFE_LBA_STOPPED;
+        *res = r;
+        return ORBFE_OK;
+    }
+    if ((rc = use_device(device))) return rc;
+    HostStage& w = tl_lba_stages.get();
+    LbaHostIo io;
+    if ((rc = lba_stage(w, io, p, Tcw, kf_fixed, nkf, x3Dw, np, obs_offset, obs_kf, obs_xy, obs_octave, nobs, Twm, marker_local, nma,
+                        mobs_offset, mobs_kf, mobs_corners, nmobs)))
+        return rc;
+    p.use_markers = use_markers != 0;
+    p.stop = nullptr;
+    if ((rc = w.host_scratch.ensure(lba_layout(nkf, np, nobs, nma, nmobs).end))) return rc;
+    if ((rc = lba_enqueue(p, w.host_scratch.p, w.stream, false)) || (rc = w.download()) || (rc = w.sync())) return rc;
+    *res = *w.host<const orbfe_lba_result>(io.res);
+    if (res->status < 0) return fail(res->status, "%s: the device refused the problem (status %d)", name, res->status);
+    w.get(Tcw, io.T, (size_t)nkf * 48);
+    w.get(x3Dw, io.X, (size_t)np * 12);
+    if (use_markers) w.get(Twm, io.M, (size_t)nma * 48);
+    w.get(erase, io.erase, (size_t)nobs);
+    return ORBFE_OK;
+}
+
+extern "C" int orbfe_local_bundle_adjustment_device(float* d_Tcw, const uint8_t* d_kf_fixed, int nkf, float* d_x3Dw, int np,
+                                                    const int32_t* d_obs_offset, const int32_t* d_obs_kf, const float* d_obs_xy,
+                                                    const int32_t* d_obs_octave, const int32_t* d_obs_feature, const orbfe_keypoint* d_kps,
+                                                    int capacity, int nobs, const float* K4, const float* inv_level_sigma2, int nlevels,
+                                                    float* d_Twm, const float* d_marker_local, int nma, const int32_t* d_mobs_offset,
+                                                    const int32_t* d_mobs_kf, const float* d_mobs_corners, int nmobs, float marker_info,
+                                                    int use_markers, const uint8_t* d_stop, uint8_t* d_erase, orbfe_lba_result* d_res,
+                                                    void* d_scratch, size_t scratch_bytes, void* stream)
+{
+    static const char* name = "orbfe_local_bundle_adjustment_device";
+    const bool form_xy = d_obs_xy != nullptr;
+    if (!lba_sizes_ok(nkf, np, nobs, nma, nmobs) || !d_res || !d_scratch || ((uintptr_t)d_scratch & 255) || (nkf && (!d_Tcw || !d_kf_fixed)) ||
+        (np && (!d_x3Dw || !d_obs_offset)) || (nobs && (!d_obs_kf || !d_erase || !np)) || (nobs && form_xy && !d_obs_octave) ||
+        (nobs && !form_xy && (!d_obs_feature || !d_kps || capacity <= 0)) || (nma && (!d_Twm || !d_marker_local || !d_mobs_offset)) ||
+        (nmobs && (!d_mobs_kf || !d_mobs_corners || !nma)))
+        return fail(ORBFE_ERR_INVALID, "%s: invalid argument", name);
+    const size_t need = lba_layout(nkf, np, nobs, nma, nmobs).end;
+    if (scratch_bytes < need) return fail(ORBFE_ERR_CAPACITY, "%s: %zu bytes of scratch, orbfe_lba_scratch_bytes asks for %zu", name, scratch_bytes, need);
+    LbaP p{};
+    int rc = lba_fill(p, K4, inv_level_sigma2, nlevels, marker_info, name);
+    if (rc) return rc;
+    p.Tcw = d_Tcw; p.kf_fixed = d_kf_fixed; p.x3Dw = d_x3Dw; p.obs_offset = d_obs_offset; p.obs_kf = d_obs_kf; p.obs_xy = d_obs_xy;
+    p.obs_oct = d_obs_octave; p.obs_feat = d_obs_feature; p.kps = d_kps; p.capacity = capacity;
+    p.Twm = d_Twm; p.mlocal = d_marker_local; p.mobs_offset = d_mobs_offset; p.mobs_kf = d_mobs_kf; p.mobs_corners = d_mobs_corners;
+    p.stop = d_stop; p.erase = d_erase; p.res = d_res;
+    p.nkf = nkf; p.np = np; p.nobs = nobs; p.nma = nma; p.nmobs = nmobs;
+    p.use_markers = use_markers != 0;
+    return lba_enqueue(p, d_scratch, (hipStream_t)stream, false);
+}
+
+extern "C" int orbfe_lba_inspect(const float* Tcw, const uint8_t* kf_fixed, int nkf, const float* x3Dw, int np, const int32_t* obs_offset,
+                                 const int32_t* obs_kf, const float* obs_xy, const int32_t* obs_octave, int nobs, const float* K4,
+                                 const float* inv_level_sigma2, int nlevels, const float* Twm, const float* marker_local, int nma,
+                                 const int32_t* mobs_offset, const int32_t* mobs_kf, const float* mobs_corners, int nmobs, float marker_info,
+                                 int use_markers, int32_t* nv, double* b, double* Hpp, double* Hll, double* chi2, double* x, int device)
+{
+    static const char* name = "orbfe_lba_inspect";
+    if (!nv || !b || !Hpp || !Hll || !chi2 || !x) return fail(ORBFE_ERR_INVALID, "%s: invalid argument", name);
+    LbaP p{};
+    int rc = lba_fill(p, K4, inv_level_sigma2, nlevels, marker_info, name);
+    if (rc) return rc;
+    if ((rc = lba_check_host(Tcw, kf_fixed, nkf, x3Dw, np, obs_offset, obs_kf, obs_xy, obs_octave, nobs, nlevels, Twm, marker_local, nma,
+                             mobs_offset, mobs_kf, mobs_corners, nmobs, use_markers, name)))
+        return rc;
+    if ((rc = use_device(device))) return rc;
+    HostStage& w = tl_lba_stages.get();
+    LbaHostIo io;
+    if ((rc = lba_stage(w, io, p, Tcw, kf_fixed, nkf, x3Dw, np, obs_offset, obs_kf, obs_xy, obs_octave, nobs, Twm, marker_local, nma,
+                        mobs_offset, mobs_kf, mobs_corners, nmobs)))
+        return rc;
+    p.use_markers = use_markers != 0;
+    p.stop = nullptr;
+    if ((rc = w.host_scratch.ensure(lba_layout(nkf, np, nobs, nma, nmobs).end))) return rc;
+    if ((rc = lba_enqueue(p, w.host_scratch.p, w.stream, true)) || (rc = w.sync())) return rc;
+    LbaCtl c;
+    ORBFE_HIP(hipMemcpy(&c, p.ctl, sizeof(c), hipMemcpyDeviceToHost));
+    if (c.abort_status < 0) return fail(c.abort_status, "%s: the device refused the problem (status %d)", name, c.abort_status);
+    *nv = c.nv;
+    chi2[0] = c.currentChi;
+    chi2[1] = c.lambda0;
+    if (c.nv) {
+        ORBFE_HIP(hipMemcpy(b, p.bp, (size_t)c.nv * 48, hipMemcpyDeviceToHost));
+        ORBFE_HIP(hipMemcpy(Hpp, p.Hpp, (size_t)c.nv * 36 * 8, hipMemcpyDeviceToHost));
+        ORBFE_HIP(hipMemcpy(x, p.xv, (size_t)c.nv * 48, hipMemcpyDeviceToHost));
+    }
+    if (np) {
+        ORBFE_HIP(hipMemcpy(b + 6 * c.nv, p.bl, (size_t)np * 24, hipMemcpyDeviceToHost));
+        ORBFE_HIP(hipMemcpy(Hll, p.Hll, (size_t)np * 48, hipMemcpyDeviceToHost));
+        ORBFE_HIP(hipMemcpy(x + 6 * c.nv, p.xl, (size_t)np * 24, hipMemcpyDeviceToHost));
+    }
+    return ORBFE_OK;
+}

@@ -1,0 +1,996 @@
+// lba_ref.cpp -- CPU restatement of ORB_SLAM2's Optimizer::LocalBundleAdjustment (src/Optimizer.cc:892-1242 of the reference, behind
+// its collect step, with this fork's marker poses as free SE3 vertices) for the parity tests of orbfe_local_bundle_adjustment*.
+// No g2o or Eigen here; the pieces are restated from their algorithms, SE3Quat / Huber as in tests/pose_opt_ref.cpp:
+//   EdgeSE3ProjectXYZ        e = obs - pi(T Xw), Omega = invSigma2 I, g2o's analytic Jacobians for the point and the pose
+//   EdgeMarker               e = obs - pi((Tcw Twm) p), Omega = w I, numeric Jacobians on both vertices: central differences,
+//                            delta = 1e-9, through exp(+-delta e_d) * estimate; none for a fixed keyframe
+//   BlockSolver_6_3          Hpp (6 x 6 per free pose vertex), Hll (3 x 3 per point), Hpl per edge; fixed vertices have no block;
+//                            S = Hpp - sum Hpl Hll^-1 Hpl^T with Hll^-1 by cofactors; S = L L^T without pivoting (a pivot that is not
+//                            positive and finite fails the solve); points by back-substitution
+//   Levenberg-Marquardt      lambda0 = 1e-5 max diagonal over pose and point blocks, up to 10 trials an iteration,
+//                            rho = dchi / (sum x (lambda x + b) + 1e-3), g2o's lambda / nu and stop rules
+//   two rounds               optimize(5) with Huber on all edges; first check (chi2 > 5.991 or depth <= 0 -> level 1); optimize(10)
+//                            on level 0 without Huber; second check -> the erase flags.  The checks read the cached errors: those of
+//                            the last evaluation of the edge (a rejected trial's when the round ended on one; round 1's for level 1)
+// Two summation orders: 0 = g2o's (every block and the chi2 summed edge by edge in insertion order, S reduced point by point),
+// 1 = the device's (a point's observations in order; a pose block over contiguous runs of points, one run a thread of 256, the
+// threads by a butterfly inside each wave of 64 and the waves in order; a block of S the same over 64 threads; the chi2 by waves
+// of 64 points, then runs of those partial sums over 256 threads).
+// Built by tests/lba_build.py (g++ -O2 -ffp-contract=off) and loaded with ctypes.
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+namespace {
+
+struct Result {     // the layout of orbfe_lba_result
+    int32_t n_edges_mono, n_edges_marker;
+    int32_t n_level1[2];
+    int32_t n_erase;
+    int32_t iterations[2];
+    int32_t stale_mask;
+    int32_t status;
+};
+
+// ------------------------------------------------------------------------------------------ SE3Quat --
+struct Quat {
+    double x, y, z, w;
+};
+struct SE3 {
+    Quat q;
+    double t[3];
+};
+
+void normalize_rotation(Quat& q)
+{
+    if (q.w < 0) {
+        q.x *= -1; q.y *= -1; q.z *= -1; q.w *= -1;
+    }
+    const double n2 = q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w;
+    if (n2 > 0) {
+        const double n = std::sqrt(n2);
+        q.x /= n; q.y /= n; q.z /= n; q.w /= n;
+    }
+}
+
+Quat quat_from_matrix(const double m[3][3])
+{
+    Quat q;
+    double* v[3] = {&q.x, &q.y, &q.z};
+    double t = m[0][0] + m[1][1] + m[2][2];
+    if (t > 0) {
+        t = std::sqrt(t + 1.0);
+        q.w = 0.5 * t;
+        t = 0.5 / t;
+        q.x = (m[2][1] - m[1][2]) * t;
+        q.y = (m[0][2] - m[2][0]) * t;
+        q.z = (m[1][0] - m[0][1]) * t;
+    } else {
+        int i = 0;
+        if (m[1][1] > m[0][0]) i = 1;
+        if (m[2][2] > m[i][i]) i = 2;
+        const int j = (i + 1) % 3, k = (j + 1) % 3;
+        t = std::sqrt(m[i][i] - m[j][j] - m[k][k] + 1.0);
+        *v[i] = 0.5 * t;
+        t = 0.5 / t;
+        q.w = (m[k][j] - m[j][k]) * t;
+        *v[j] = (m[j][i] + m[i][j]) * t;
+        *v[k] = (m[k][i] + m[i][k]) * t;
+    }
+    return q;
+}
+
+void cross(const double a[3], const double b[3], double r[3])
+{
+    r[0] = a[1] * b[2] - a[2] * b[1];
+    r[1] = a[2] * b[0] - a[0] * b[2];
+    r[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// q v: v + w uv + qv x uv, uv = 2 (qv x v)
+void rotate(const Quat& q, const double v[3], double r[3])
+{
+    const double qv[3] = {q.x, q.y, q.z};
+    double uv[3], c[3];
+    cross(qv, v, uv);
+    for (int i = 0; i < 3; i++) uv[i] += uv[i];
+    cross(qv, uv, c);
+    for (int i = 0; i < 3; i++) r[i] = v[i] + q.w * uv[i] + c[i];
+}
+
+Quat qmul(const Quat& a, const Quat& b)
+{
+    Quat r;
+    r.w = a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z;
+    r.x = a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y;
+    r.y = a.w * b.y + a.y * b.w + a.z * b.x - a.x * b.z;
+    r.z = a.w * b.z + a.z * b.w + a.x * b.y - a.y * b.x;
+    return r;
+}
+
+SE3 mul(const SE3& a, const SE3& b)
+{
+    SE3 r = a;
+    double qt[3];
+    rotate(a.q, b.t, qt);
+    for (int i = 0; i < 3; i++) r.t[i] += qt[i];
+    r.q = qmul(a.q, b.q);
+    normalize_rotation(r.q);
+    return r;
+}
+
+void map(const SE3& T, const double p[3], double r[3])
+{
+    rotate(T.q, p, r);
+    for (int i = 0; i < 3; i++) r[i] += T.t[i];
+}
+
+SE3 se3_from_Rt(const double R[3][3], const double t[3])
+{
+    SE3 T;
+    T.q = quat_from_matrix(R);
+    for (int i = 0; i < 3; i++) T.t[i] = t[i];
+    normalize_rotation(T.q);
+    return T;
+}
+
+SE3 se3_from_float(const float* Rt)
+{
+    double R[3][3], t[3];
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) R[r][c] = Rt[r * 4 + c];
+        t[r] = Rt[r * 4 + 3];
+    }
+    return se3_from_Rt(R, t);
+}
+
+void mat3mul(const double a[3][3], const double b[3][3], double r[3][3])
+{
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) r[i][j] = a[i][0] * b[0][j] + a[i][1] * b[1][j] + a[i][2] * b[2][j];
+}
+
+SE3 se3_exp(const double u[6])
+{
+    const double om[3] = {u[0], u[1], u[2]}, up[3] = {u[3], u[4], u[5]};
+    const double theta = std::sqrt(om[0] * om[0] + om[1] * om[1] + om[2] * om[2]);
+    const double O[3][3] = {{0, -om[2], om[1]}, {om[2], 0, -om[0]}, {-om[1], om[0], 0}};
+    double O2[3][3], R[3][3], V[3][3];
+    mat3mul(O, O, O2);
+    if (theta < 0.00001) {
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) R[i][j] = ((i == j ? 1.0 : 0.0) + O[i][j]) + O2[i][j];
+        std::memcpy(V, R, sizeof(R));
+    } else {
+        const double a = std::sin(theta) / theta, b = (1 - std::cos(theta)) / (theta * theta);
+        const double c = (theta - std::sin(theta)) / std::pow(theta, 3);
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++) {
+                R[i][j] = ((i == j ? 1.0 : 0.0) + a * O[i][j]) + b * O2[i][j];
+                V[i][j] = ((i == j ? 1.0 : 0.0) + b * O[i][j]) + c * O2[i][j];
+            }
+    }
+    double t[3];
+    for (int i = 0; i < 3; i++) t[i] = V[i][0] * up[0] + V[i][1] * up[1] + V[i][2] * up[2];
+    return se3_from_Rt(R, t);
+}
+
+void to_float(const SE3& T, float* Rt)
+{
+    const Quat& q = T.q;
+    const double tx = 2 * q.x, ty = 2 * q.y, tz = 2 * q.z;
+    const double twx = tx * q.w, twy = ty * q.w, twz = tz * q.w;
+    const double txx = tx * q.x, txy = ty * q.x, txz = tz * q.x;
+    const double tyy = ty * q.y, tyz = tz * q.y, tzz = tz * q.z;
+    const double R[9] = {1 - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1 - (txx + tzz), tyz - twx, txz - twy, tyz + twx, 1 - (txx + tyy)};
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) Rt[r * 4 + c] = (float)R[r * 3 + c];
+        Rt[r * 4 + 3] = (float)T.t[r];
+    }
+}
+
+struct Cam {
+    double fx, fy, cx, cy;
+};
+
+double chi2_of(const double e[2], double info) { return e[0] * (info * e[0]) + e[1] * (info * e[1]); }
+
+// Huber: rho[0], rho[1]
+void huber(double chi2, double delta, double rho[2])
+{
+    const double dsqr = delta * delta;
+    if (chi2 <= dsqr) {
+        rho[0] = chi2;
+        rho[1] = 1.;
+    } else {
+        const double s = std::sqrt(chi2);
+        rho[0] = 2 * s * delta - dsqr;
+        rho[1] = delta / s;
+    }
+}
+
+void rot_of(const Quat& q, double R[3][3])
+{
+    const double tx = 2 * q.x, ty = 2 * q.y, tz = 2 * q.z;
+    const double twx = tx * q.w, twy = ty * q.w, twz = tz * q.w;
+    const double txx = tx * q.x, txy = ty * q.x, txz = tz * q.x;
+    const double tyy = ty * q.y, tyz = tz * q.y, tzz = tz * q.z;
+    R[0][0] = 1 - (tyy + tzz); R[0][1] = txy - twz; R[0][2] = txz + twy;
+    R[1][0] = txy + twz; R[1][1] = 1 - (txx + tzz); R[1][2] = tyz - twx;
+    R[2][0] = txz - twy; R[2][1] = tyz + twx; R[2][2] = 1 - (txx + tyy);
+}
+
+void project_error(const double Xc[3], double ox, double oy, const Cam& K, double err[2])
+{
+    err[0] = ox - ((Xc[0] / Xc[2]) * K.fx + K.cx);
+    err[1] = oy - ((Xc[1] / Xc[2]) * K.fy + K.cy);
+}
+
+void mono_error(const SE3& T, const double Xw[3], double ox, double oy, const Cam& K, double err[2])
+{
+    double Xc[3];
+    map(T, Xw, Xc);
+    project_error(Xc, ox, oy, K, err);
+}
+
+// EdgeSE3ProjectXYZ::linearizeOplus
+void mono_linearize(const SE3& T, const double Xw[3], double ox, double oy, const Cam& K, double err[2], double Jp[2][6], double Jx[2][3])
+{
+    double Xc[3], R[3][3];
+    map(T, Xw, Xc);
+    project_error(Xc, ox, oy, K, err);
+    const double x = Xc[0], y = Xc[1], z = Xc[2], z_2 = z * z;
+    const double s = -1. / z;
+    const double t0[3] = {s * K.fx, s * 0., s * (-x / z * K.fx)}, t1[3] = {s * 0., s * K.fy, s * (-y / z * K.fy)};
+    rot_of(T.q, R);
+    for (int c = 0; c < 3; c++) {
+        Jx[0][c] = t0[0] * R[0][c] + t0[1] * R[1][c] + t0[2] * R[2][c];
+        Jx[1][c] = t1[0] * R[0][c] + t1[1] * R[1][c] + t1[2] * R[2][c];
+    }
+    Jp[0][0] = x * y / z_2 * K.fx;
+    Jp[0][1] = -(1 + (x * x / z_2)) * K.fx;
+    Jp[0][2] = y / z * K.fx;
+    Jp[0][3] = -1. / z * K.fx;
+    Jp[0][4] = 0;
+    Jp[0][5] = x / z_2 * K.fx;
+    Jp[1][0] = (1 + y * y / z_2) * K.fy;
+    Jp[1][1] = -x * y / z_2 * K.fy;
+    Jp[1][2] = -x / z * K.fy;
+    Jp[1][3] = 0;
+    Jp[1][4] = -1. / z * K.fy;
+    Jp[1][5] = y / z_2 * K.fy;
+}
+
+void marker_error(const SE3& Tc, const SE3& Tm, const double pm[3], double ox, double oy, const Cam& K, double err[2])
+{
+    const SE3 Tcm = mul(Tc, Tm);
+    double Xc[3];
+    map(Tcm, pm, Xc);
+    project_error(Xc, ox, oy, K, err);
+}
+
+void marker_jacobian(const SE3& Tc, const SE3& Tm, bool camera, const double pm[3], double ox, double oy, const Cam& K, double J[2][6])
+{
+    const double delta = 1e-9, scalar = 1.0 / (2 * delta);
+    for (int d = 0; d < 6; d++) {
+        double u[6] = {0, 0, 0, 0, 0, 0}, ep[2], em[2];
+        u[d] = delta;
+        SE3 E = se3_exp(u);
+        if (camera) marker_error(mul(E, Tc), Tm, pm, ox, oy, K, ep);
+        else marker_error(Tc, mul(E, Tm), pm, ox, oy, K, ep);
+        u[d] = -delta;
+        E = se3_exp(u);
+        if (camera) marker_error(mul(E, Tc), Tm, pm, ox, oy, K, em);
+        else marker_error(Tc, mul(E, Tm), pm, ox, oy, K, em);
+        J[0][d] = scalar * (ep[0] - em[0]);
+        J[1][d] = scalar * (ep[1] - em[1]);
+    }
+}
+
+bool all_finite(const double* v, int n)
+{
+    for (int i = 0; i < n; i++)
+        if (!std::isfinite(v[i])) return false;
+    return true;
+}
+
+void diag_block(const double J[2][6], double w, double r0, double r1, double* out)
+{
+    int k = 0;
+    for (int a = 0; a < 6; a++)
+        for (int c = a; c < 6; c++, k++) out[k] = J[0][a] * (w * J[0][c]) + J[1][a] * (w * J[1][c]);
+    for (int a = 0; a < 6; a++) out[21 + a] = J[0][a] * r0 + J[1][a] * r1;
+}
+
+// ------------------------------------------------------------------------------------------ the device's sums --
+double butterfly64(double* v)
+{
+    double t[64];
+    for (int off = 32; off >= 1; off >>= 1) {
+        for (int l = 0; l < 64; l++) t[l] = v[l] + v[l ^ off];
+        std::memcpy(v, t, sizeof(t));
+    }
+    return v[0];
+}
+
+double block256(double* v)   // 256 thread values: a butterfly per wave, the waves in order
+{
+    double s = butterfly64(v);
+    for (int w = 1; w < 4; w++) s += butterfly64(v + 64 * w);
+    return s;
+}
+
+double parts_sum(const std::vector<double>& part)
+{
+    const int n = (int)part.size(), per = (n + 255) / 256;
+    double v[256];
+    for (int t = 0; t < 256; t++) {
+        const int lo = std::min(t * per, n), hi = std::min(lo + per, n);
+        double s = 0;
+        for (int i = lo; i < hi; i++) s += part[i];
+        v[t] = s;
+    }
+    return block256(v);
+}
+
+// ------------------------------------------------------------------------------------------ the problem --
+constexpr int EB = 45, MB = 90, MAXV = 64;
+
+struct Prob {
+    int nkf, np, nobs, nma, nmobs, nme, nv, order;
+    bool fix_points = false;   // the anchor's hook: the points are held, only pose blocks are built (what a motion-only optimization solves)
+    const uint8_t* fixed;
+    const int32_t *off, *okf;
+    const float* oxy;
+    std::vector<double> info;
+    Cam K;
+    double delta, minfo;
+    const float* mlocal;
+    const int32_t *moff, *mkf;
+    const float* mcor;
+    std::vector<int> mo_marker, kf_free, v_kf, e_pt, tbl;
+};
+
+struct Est {
+    std::vector<SE3> pose;      // nkf keyframes, then nma markers
+    std::vector<double> pt;
+};
+
+struct Lin {
+    std::vector<double> Hll, bl, Hpp, bp, eblk, mblk, Dinv;
+    std::vector<uint8_t> euse, muse, pact, vact;
+    double chi, maxdiag;
+};
+
+struct Cache {
+    std::vector<double> e_chi2, m_chi2;
+    std::vector<uint8_t> e_level, m_level;
+};
+
+// the chi2 of a pass from the per-edge robust values: edge by edge, or the device's tree
+double chi_sum(const Prob& P, const std::vector<double>& e_rho, const std::vector<double>& m_rho, const Cache& C)
+{
+    if (P.order == 0) {
+        double s = 0;
+        for (int e = 0; e < P.nobs; e++)
+            if (!C.e_level[e]) s += e_rho[e];
+        for (int j = 0; j < P.nme; j++)
+            if (!C.m_level[j]) s += m_rho[j];
+        return s;
+    }
+    const int npb = (P.np + 63) / 64, nb = npb + (P.nme + 63) / 64;
+    std::vector<double> part((size_t)nb, 0.);
+    for (int b = 0; b < nb; b++) {
+        double v[64];
+        for (int l = 0; l < 64; l++) {
+            double s = 0;
+            if (b < npb) {
+                const int pi = b * 64 + l;
+                if (pi < P.np)
+                    for (int e = P.off[pi]; e < P.off[pi + 1]; e++)
+                        if (!C.e_level[e]) s += e_rho[e];
+            } else {
+                const int j = (b - npb) * 64 + l;
+                if (j < P.nme && !C.m_level[j]) s += m_rho[j];
+            }
+            v[l] = s;
+        }
+        part[(size_t)b] = butterfly64(v);
+    }
+    return parts_sum(part);
+}
+
+void linearize(const Prob& P, const Est& X, bool robust, Cache& C, Lin& L)
+{
+    L.Hll.assign((size_t)P.np * 6, 0.); L.bl.assign((size_t)P.np * 3, 0.); L.Hpp.assign((size_t)P.nv * 36, 0.); L.bp.assign((size_t)P.nv * 6, 0.);
+    L.eblk.assign((size_t)P.nobs * EB, 0.); L.mblk.assign((size_t)P.nme * MB, 0.);
+    L.euse.assign((size_t)P.nobs, 0); L.muse.assign((size_t)P.nme, 0); L.pact.assign((size_t)P.np, 0); L.vact.assign((size_t)P.nv, 0);
+    L.Dinv.assign((size_t)P.np * 9, 0.);
+    std::vector<double> e_rho((size_t)P.nobs, 0.), m_rho((size_t)P.nme, 0.);
+    double md = 0;
+    for (int pi = 0; pi < P.np; pi++) {
+        const double* Xw = &X.pt[(size_t)pi * 3];
+        double* H = &L.Hll[(size_t)pi * 6];
+        double* b = &L.bl[(size_t)pi * 3];
+        int nact = 0;
+        for (int e = P.off[pi]; e < P.off[pi + 1]; e++) {
+            if (C.e_level[e]) continue;
+            nact++;
+            const int kf = P.okf[e];
+            double err[2], Jp[2][6], Jx[2][3];
+            mono_linearize(X.pose[(size_t)kf], Xw, P.oxy[2 * e], P.oxy[2 * e + 1], P.K, err, Jp, Jx);
+            const double info = P.info[(size_t)e], ch = chi2_of(err, info);
+            C.e_chi2[e] = ch;
+            double rho[2] = {ch, 1.};
+            if (robust) huber(ch, P.delta, rho);
+            e_rho[e] = rho[0];
+            const bool fin = all_finite(err, 2) && all_finite(&Jp[0][0], 12) && all_finite(&Jx[0][0], 6) && std::isfinite(rho[1]);
+            const int vf = P.kf_free[(size_t)kf];
+            L.euse[e] = fin ? (vf >= 0 ? 3 : 1) : 0;
+            if (!fin) continue;
+            const double w = rho[1] * info, r0 = rho[1] * -(info * err[0]), r1 = rho[1] * -(info * err[1]);
+            int k = 0;
+            for (int a = 0; a < 3; a++)
+                for (int c = a; c < 3; c++, k++) H[k] += Jx[0][a] * (w * Jx[0][c]) + Jx[1][a] * (w * Jx[1][c]);
+            for (int a = 0; a < 3; a++) b[a] += Jx[0][a] * r0 + Jx[1][a] * r1;
+            if (vf >= 0) {
+                double* out = &L.eblk[(size_t)e * EB];
+                diag_block(Jp, w, r0, r1, out);
+                for (int a = 0; a < 6; a++)
+                    for (int c = 0; c < 3; c++) out[27 + a * 3 + c] = Jp[0][a] * (w * Jx[0][c]) + Jp[1][a] * (w * Jx[1][c]);
+            }
+        }
+        L.pact[pi] = nact > 0 && !P.fix_points;
+        if (L.pact[pi]) md = std::max(md, std::max(std::max(std::fabs(H[0]), std::fabs(H[3])), std::fabs(H[5])));
+    }
+    for (int j = 0; j < P.nme; j++) {
+        if (C.m_level[j]) continue;
+        const int o = j >> 2, k = j & 3, kf = P.mkf[o], m = P.mo_marker[(size_t)o];
+        const SE3 &Tc = X.pose[(size_t)kf], &Tm = X.pose[(size_t)(P.nkf + m)];
+        const double pm[3] = {P.mlocal[m * 12 + 3 * k], P.mlocal[m * 12 + 3 * k + 1], P.mlocal[m * 12 + 3 * k + 2]};
+        const double ox = P.mcor[o * 8 + 2 * k], oy = P.mcor[o * 8 + 2 * k + 1];
+        const bool camfree = P.kf_free[(size_t)kf] >= 0;
+        double err[2], Jc[2][6] = {}, Jm[2][6], rho[2];
+        marker_error(Tc, Tm, pm, ox, oy, P.K, err);
+        const double ch = chi2_of(err, P.minfo);
+        C.m_chi2[j] = ch;
+        rho[0] = ch; rho[1] = 1.;
+        if (robust) huber(ch, P.delta, rho);
+        m_rho[j] = rho[0];
+        if (camfree) marker_jacobian(Tc, Tm, true, pm, ox, oy, P.K, Jc);
+        marker_jacobian(Tc, Tm, false, pm, ox, oy, P.K, Jm);
+        const bool fin = all_finite(err, 2) && all_finite(&Jc[0][0], 12) && all_finite(&Jm[0][0], 12) && std::isfinite(rho[1]);
+        L.muse[j] = fin;
+        if (!fin) continue;
+        const double w = rho[1] * P.minfo, r0 = rho[1] * -(P.minfo * err[0]), r1 = rho[1] * -(P.minfo * err[1]);
+        double* out = &L.mblk[(size_t)j * MB];
+        diag_block(Jc, w, r0, r1, out);
+        diag_block(Jm, w, r0, r1, out + 27);
+        for (int a = 0; a < 6; a++)
+            for (int c = 0; c < 6; c++) out[54 + a * 6 + c] = Jc[0][a] * (w * Jm[0][c]) + Jc[1][a] * (w * Jm[1][c]);
+    }
+    L.chi = chi_sum(P, e_rho, m_rho, C);
+    // the pose blocks
+    for (int v = 0; v < P.nv; v++) {
+        const int kf = P.v_kf[(size_t)v];
+        double s[28] = {};
+        if (kf < P.nkf) {
+            if (P.order == 0) {
+                for (int e = 0; e < P.nobs; e++) {
+                    if (P.okf[e] != kf || C.e_level[e]) continue;
+                    s[27] += 1;
+                    if (L.euse[e] != 3) continue;
+                    for (int k = 0; k < 27; k++) s[k] += L.eblk[(size_t)e * EB + k];
+                }
+            } else {
+                std::vector<double> th((size_t)256 * 28, 0.);
+                const int per = (P.np + 255) / 256;
+                for (int t = 0; t < 256; t++) {
+                    const int lo = std::min(t * per, P.np), hi = std::min(lo + per, P.np);
+                    for (int pi = lo; pi < hi; pi++) {
+                        const int e = P.tbl[(size_t)kf * P.np + pi];
+                        if (e < 0 || C.e_level[e]) continue;
+                        th[(size_t)27 * 256 + t] += 1;
+                        if (L.euse[e] != 3) continue;
+                        for (int k = 0; k < 27; k++) th[(size_t)k * 256 + t] += L.eblk[(size_t)e * EB + k];
+                    }
+                }
+                for (int k = 0; k < 28; k++) s[k] = block256(&th[(size_t)k * 256]);
+            }
+            for (int j = 0; j < P.nme; j++) {
+                if (P.mkf[j >> 2] != kf || C.m_level[j]) continue;
+                s[27] += 1;
+                if (!L.muse[j]) continue;
+                for (int k = 0; k < 27; k++) s[k] += L.mblk[(size_t)j * MB + k];
+            }
+        } else {
+            const int m = kf - P.nkf;
+            for (int j = 4 * P.moff[m]; j < 4 * P.moff[m + 1]; j++) {
+                if (C.m_level[j]) continue;
+                s[27] += 1;
+                if (!L.muse[j]) continue;
+                for (int k = 0; k < 27; k++) s[k] += L.mblk[(size_t)j * MB + 27 + k];
+            }
+        }
+        double* H = &L.Hpp[(size_t)v * 36];
+        int k = 0;
+        double mv = 0;
+        for (int a = 0; a < 6; a++)
+            for (int c = a; c < 6; c++, k++) H[a * 6 + c] = H[c * 6 + a] = s[k];
+        for (int a = 0; a < 6; a++) {
+            L.bp[(size_t)v * 6 + a] = s[21 + a];
+            mv = std::max(mv, std::fabs(H[a * 6 + a]));
+        }
+        L.vact[v] = s[27] > 0;
+        if (s[27] > 0) md = std::max(md, mv);
+    }
+    L.maxdiag = md;
+}
+
+// the reduced system of one trial: S (n x n, n = 6 nv) and bs; Dinv of the active points
+void schur(const Prob& P, const Cache& C, Lin& L, double lambda, std::vector<double>& S, std::vector<double>& bs)
+{
+    const int n = 6 * P.nv;
+    S.assign((size_t)n * n, 0.);
+    bs.assign((size_t)n, 0.);
+    for (int pi = 0; pi < P.np; pi++) {
+        if (!L.pact[pi]) continue;
+        const double* H = &L.Hll[(size_t)pi * 6];
+        const double m00 = H[0] + lambda, m01 = H[1], m02 = H[2], m11 = H[3] + lambda, m12 = H[4], m22 = H[5] + lambda;
+        const double c00 = m11 * m22 - m12 * m12, c10 = m12 * m02 - m01 * m22, c20 = m01 * m12 - m11 * m02;
+        const double det = c00 * m00 + c10 * m01 + c20 * m02, id = 1. / det;
+        double* D = &L.Dinv[(size_t)pi * 9];
+        D[0] = c00 * id; D[1] = c10 * id; D[2] = c20 * id;
+        D[3] = D[1]; D[4] = (m00 * m22 - m02 * m02) * id; D[5] = (m02 * m01 - m00 * m12) * id;
+        D[6] = D[2]; D[7] = D[5]; D[8] = (m00 * m11 - m01 * m01) * id;
+    }
+    auto contribution = [&](int ei, int ej, int pi, bool diag, double* acc, double* accb) {
+        const double *Wi = &L.eblk[(size_t)ei * EB + 27], *Wj = &L.eblk[(size_t)ej * EB + 27], *D = &L.Dinv[(size_t)pi * 9], *bl = &L.bl[(size_t)pi * 3];
+        for (int a = 0; a < 6; a++) {
+            double Y[3];
+            for (int c = 0; c < 3; c++) Y[c] = Wi[a * 3] * D[c] + Wi[a * 3 + 1] * D[3 + c] + Wi[a * 3 + 2] * D[6 + c];
+            for (int b = 0; b < 6; b++) acc[a * 6 + b] += Y[0] * Wj[b * 3] + Y[1] * Wj[b * 3 + 1] + Y[2] * Wj[b * 3 + 2];
+            if (diag) accb[a] += Y[0] * bl[0] + Y[1] * bl[1] + Y[2] * bl[2];
+        }
+    };
+    for (int i = 0; i < P.nv; i++)
+        for (int j = i; j < P.nv; j++) {
+            const int ki = P.v_kf[(size_t)i], kj = P.v_kf[(size_t)j];
+            const bool act = L.vact[i] && L.vact[j];
+            double B[36] = {}, acc[36] = {}, accb[6] = {};
+            if (act && ki < P.nkf && kj < P.nkf) {
+                auto usable = [&](int pi, int& ei, int& ej) {
+                    if (!L.pact[pi]) return false;
+                    ei = P.tbl[(size_t)ki * P.np + pi];
+                    ej = P.tbl[(size_t)kj * P.np + pi];
+                    return ei >= 0 && ej >= 0 && !C.e_level[ei] && !C.e_level[ej] && L.euse[ei] == 3 && L.euse[ej] == 3;
+                };
+                if (P.order == 0) {
+                    for (int pi = 0; pi < P.np; pi++) {
+                        int ei, ej;
+                        if (usable(pi, ei, ej)) contribution(ei, ej, pi, i == j, acc, accb);
+                    }
+                } else {
+                    std::vector<double> th((size_t)42 * 64, 0.);
+                    const int per = (P.np + 63) / 64;
+                    for (int t = 0; t < 64; t++) {
+                        double a36[36] = {}, a6[6] = {};
+                        const int lo = std::min(t * per, P.np), hi = std::min(lo + per, P.np);
+                        for (int pi = lo; pi < hi; pi++) {
+                            int ei, ej;
+                            if (usable(pi, ei, ej)) contribution(ei, ej, pi, i == j, a36, a6);
+                        }
+                        for (int k = 0; k < 36; k++) th[(size_t)k * 64 + t] = a36[k];
+                        for (int k = 0; k < 6; k++) th[(size_t)(36 + k) * 64 + t] = a6[k];
+                    }
+                    for (int k = 0; k < 36; k++) acc[k] = butterfly64(&th[(size_t)k * 64]);
+                    for (int k = 0; k < 6; k++) accb[k] = butterfly64(&th[(size_t)(36 + k) * 64]);
+                }
+            }
+            if (!act) {
+                if (i == j)
+                    for (int a = 0; a < 6; a++) B[a * 6 + a] = 1;
+            } else if (i == j) {
+                for (int k = 0; k < 36; k++) B[k] = L.Hpp[(size_t)i * 36 + k];
+                for (int a = 0; a < 6; a++) B[a * 6 + a] += lambda;
+                for (int k = 0; k < 36; k++) B[k] -= acc[k];
+            } else if (kj < P.nkf) {
+                for (int k = 0; k < 36; k++) B[k] = 0. - acc[k];
+            } else if (ki < P.nkf) {
+                const int m = kj - P.nkf;
+                for (int e = 4 * P.moff[m]; e < 4 * P.moff[m + 1]; e++) {
+                    if (P.mkf[e >> 2] != ki || C.m_level[e] || !L.muse[e]) continue;
+                    for (int k = 0; k < 36; k++) B[k] += L.mblk[(size_t)e * MB + 54 + k];
+                }
+            }
+            for (int a = 0; a < 6; a++)
+                for (int b = 0; b < 6; b++) S[(size_t)(6 * i + a) * n + 6 * j + b] = S[(size_t)(6 * j + b) * n + 6 * i + a] = B[a * 6 + b];
+            if (i == j)
+                for (int a = 0; a < 6; a++) bs[(size_t)6 * i + a] = act ? L.bp[(size_t)6 * i + a] - accb[a] : 0.;
+        }
+}
+
+// L L^T in place, right-looking, no pivoting; then the two substitutions.  x is untouched when a pivot fails.
+bool llt_solve(std::vector<double>& S, int n, const std::vector<double>& b, double* x)
+{
+    for (int k = 0; k < n; k++) {
+        const double d = S[(size_t)k * n + k];
+        if (!(d > 0) || !std::isfinite(d)) return false;
+        const double lkk = S[(size_t)k * n + k] = std::sqrt(d);
+        for (int i = k + 1; i < n; i++) S[(size_t)i * n + k] /= lkk;
+        for (int i = k + 1; i < n; i++) {
+            const double lik = S[(size_t)i * n + k];
+            for (int j = k + 1; j <= i; j++) S[(size_t)i * n + j] -= lik * S[(size_t)j * n + k];
+        }
+    }
+    std::vector<double> y(b);
+    for (int k = 0; k < n; k++) {
+        y[(size_t)k] /= S[(size_t)k * n + k];
+        for (int i = k + 1; i < n; i++) y[(size_t)i] -= S[(size_t)i * n + k] * y[(size_t)k];
+    }
+    for (int k = n - 1; k >= 0; k--) {
+        y[(size_t)k] /= S[(size_t)k * n + k];
+        for (int i = 0; i < k; i++) y[(size_t)i] -= S[(size_t)k * n + i] * y[(size_t)k];
+    }
+    for (int i = 0; i < n; i++) x[i] = y[(size_t)i];
+    return true;
+}
+
+struct Lm {
+    double lambda, ni, currentChi, iniChi, rho, lambda0;
+    int q, nbad;
+};
+
+// one trial: the reduced solve, the updates, the trial estimates and their chi2 (written to the cache).  Returns ok2.
+bool trial(const Prob& P, Cache& C, Lin& L, double lambda, bool robust, const Est& X, Est& Xt, std::vector<double>& xv, std::vector<double>& xl,
+           double& tempChi, double& scale_points)
+{
+    std::vector<double> S, bs;
+    schur(P, C, L, lambda, S, bs);
+    const bool ok = llt_solve(S, 6 * P.nv, bs, xv.data());
+    Xt = X;
+    for (int v = 0; v < P.nv; v++)
+        if (L.vact[v]) {
+            const int idx = P.v_kf[(size_t)v];
+            Xt.pose[(size_t)idx] = mul(se3_exp(&xv[(size_t)v * 6]), X.pose[(size_t)idx]);
+        }
+    std::vector<double> e_rho((size_t)P.nobs, 0.), m_rho((size_t)P.nme, 0.), sc((size_t)P.np, 0.);
+    for (int pi = 0; pi < P.np; pi++) {
+        if (!L.pact[pi] && !P.fix_points) continue;
+        double* x = &xl[(size_t)pi * 3];
+        const double* bl = &L.bl[(size_t)pi * 3];
+        if (ok && L.pact[pi]) {
+            double r[3] = {bl[0], bl[1], bl[2]};
+            for (int e = P.off[pi]; e < P.off[pi + 1]; e++) {
+                if (C.e_level[e] || L.euse[e] != 3) continue;
+                const double* W = &L.eblk[(size_t)e * EB + 27];
+                const double* xp = &xv[(size_t)P.kf_free[(size_t)P.okf[e]] * 6];
+                for (int c = 0; c < 3; c++) {
+                    double s = 0;
+                    for (int a = 0; a < 6; a++) s += W[a * 3 + c] * xp[a];
+                    r[c] -= s;
+                }
+            }
+            const double* D = &L.Dinv[(size_t)pi * 9];
+            for (int a = 0; a < 3; a++) x[a] = D[a * 3] * r[0] + D[a * 3 + 1] * r[1] + D[a * 3 + 2] * r[2];
+        }
+        double s = 0;
+        for (int a = 0; a < 3 && L.pact[pi]; a++) {
+            s += x[a] * (lambda * x[a] + bl[a]);
+            Xt.pt[(size_t)pi * 3 + a] = X.pt[(size_t)pi * 3 + a] + x[a];
+        }
+        sc[(size_t)pi] = s;
+        for (int e = P.off[pi]; e < P.off[pi + 1]; e++) {
+            if (C.e_level[e]) continue;
+            double err[2], rho[2];
+            mono_error(Xt.pose[(size_t)P.okf[e]], &Xt.pt[(size_t)pi * 3], P.oxy[2 * e], P.oxy[2 * e + 1], P.K, err);
+            const double ch = chi2_of(err, P.info[(size_t)e]);
+            C.e_chi2[e] = ch;
+            rho[0] = ch;
+            if (robust) huber(ch, P.delta, rho);
+            e_rho[e] = rho[0];
+        }
+    }
+    for (int j = 0; j < P.nme; j++) {
+        if (C.m_level[j]) continue;
+        const int o = j >> 2, k = j & 3, m = P.mo_marker[(size_t)o];
+        const double pm[3] = {P.mlocal[m * 12 + 3 * k], P.mlocal[m * 12 + 3 * k + 1], P.mlocal[m * 12 + 3 * k + 2]};
+        double err[2], rho[2];
+        marker_error(Xt.pose[(size_t)P.mkf[o]], Xt.pose[(size_t)(P.nkf + m)], pm, P.mcor[o * 8 + 2 * k], P.mcor[o * 8 + 2 * k + 1], P.K, err);
+        const double ch = chi2_of(err, P.minfo);
+        C.m_chi2[j] = ch;
+        rho[0] = ch;
+        if (robust) huber(ch, P.delta, rho);
+        m_rho[j] = rho[0];
+    }
+    tempChi = chi_sum(P, e_rho, m_rho, C);
+    if (P.order == 0) {
+        double s = 0;
+        for (int pi = 0; pi < P.np; pi++) s += sc[(size_t)pi];
+        scale_points = s;
+    } else {
+        const int npb = (P.np + 63) / 64, nb = npb + (P.nme + 63) / 64;
+        std::vector<double> part((size_t)nb, 0.);
+        for (int b = 0; b < npb; b++) {
+            double v[64];
+            for (int l = 0; l < 64; l++) v[l] = b * 64 + l < P.np ? sc[(size_t)(b * 64 + l)] : 0.;
+            part[(size_t)b] = butterfly64(v);
+        }
+        scale_points = parts_sum(part);
+    }
+    return ok;
+}
+
+// optimize(maxit): returns the iterations run; `stale` = the last trial was rejected
+int optimize(const Prob& P, Cache& C, Est& X, bool robust, int maxit, std::vector<double>& xv, std::vector<double>& xl, bool& stale)
+{
+    Lm c{};
+    c.ni = 2;
+    stale = false;
+    int it = 0;
+    Lin L;
+    Est Xt;
+    while (it < maxit) {
+        linearize(P, X, robust, C, L);
+        c.currentChi = c.iniChi = L.chi;
+        if (it == 0) {
+            c.lambda = c.lambda0 = 1e-5 * L.maxdiag;
+            c.ni = 2;
+            c.nbad = 0;
+        }
+        c.rho = 0;
+        c.q = 0;
+        for (;;) {
+            double tempChi, sp;
+            const bool ok2 = trial(P, C, L, c.lambda, robust, X, Xt, xv, xl, tempChi, sp);
+            if (!ok2) tempChi = DBL_MAX;
+            double scale = 0;
+            for (int j = 0; j < 6 * P.nv; j++) scale += xv[(size_t)j] * (c.lambda * xv[(size_t)j] + (L.vact[j / 6] ? L.bp[(size_t)j] : 0.));
+            scale += sp;
+            scale += 1e-3;
+            double rho = (c.currentChi - tempChi);
+            rho /= scale;
+            if (rho > 0 && std::isfinite(tempChi)) {
+                double alpha = 1. - std::pow((2 * rho - 1), 3);
+                alpha = std::min(alpha, 2. / 3.);
+                c.lambda *= std::max(1. / 3., alpha);
+                c.ni = 2;
+                c.currentChi = tempChi;
+                X = Xt;
+                stale = false;
+            } else {
+                c.lambda *= c.ni;
+                c.ni *= 2;
+                stale = true;
+            }
+            c.rho = rho;
+            c.q++;
+            if (!(rho < 0 && c.q < 10)) break;
+        }
+        it++;
+        bool stop = c.q == 10 || c.rho == 0;
+        if (!stop) {
+            if ((c.iniChi - c.currentChi) * 1e3 < c.iniChi) c.nbad++;
+            else c.nbad = 0;
+            stop = c.nbad >= 3;
+        }
+        if (stop) break;
+    }
+    return it;
+}
+
+bool setup(Prob& P, Est& X, const float* Tcw, const uint8_t* kf_fixed, int nkf, const float* x3Dw, int np, const int32_t* obs_offset,
+           const int32_t* obs_kf, const float* obs_xy, const int32_t* obs_octave, int nobs, const float* K4, const float* inv_sigma2,
+           const float* Twm, const float* marker_local, int nma, const int32_t* mobs_offset, const int32_t* mobs_kf, const float* mobs_corners,
+           int nmobs, float marker_info, int use_markers, int order)
+{
+    P.nkf = nkf; P.np = np; P.nobs = nobs; P.nma = nma; P.nmobs = nmobs; P.nme = use_markers ? 4 * nmobs : 0; P.order = order;
+    P.fixed = kf_fixed; P.off = obs_offset; P.okf = obs_kf; P.oxy = obs_xy;
+    P.K = Cam{K4[0], K4[1], K4[2], K4[3]};
+    P.delta = (double)(float)std::sqrt(5.991);
+    P.minfo = marker_info;
+    P.mlocal = marker_local; P.moff = mobs_offset; P.mkf = mobs_kf; P.mcor = mobs_corners;
+    P.info.resize((size_t)nobs);
+    for (int e = 0; e < nobs; e++) P.info[(size_t)e] = inv_sigma2[obs_octave[e]];
+    P.mo_marker.assign((size_t)nmobs, 0);
+    for (int m = 0; m < nma; m++)
+        for (int o = mobs_offset[m]; o < mobs_offset[m + 1]; o++) P.mo_marker[(size_t)o] = m;
+    P.kf_free.assign((size_t)nkf, -1);
+    P.v_kf.clear();
+    for (int k = 0; k < nkf; k++)
+        if (!kf_fixed[k]) {
+            P.kf_free[(size_t)k] = (int)P.v_kf.size();
+            P.v_kf.push_back(k);
+        }
+    for (int m = 0; use_markers && m < nma; m++) P.v_kf.push_back(nkf + m);
+    P.nv = (int)P.v_kf.size();
+    P.tbl.assign((size_t)std::max(nkf, 1) * std::max(np, 1), -1);
+    for (int pi = 0; pi < np; pi++)
+        for (int e = obs_offset[pi]; e < obs_offset[pi + 1]; e++) P.tbl[(size_t)obs_kf[e] * np + pi] = e;
+    X.pose.resize((size_t)(nkf + nma));
+    for (int k = 0; k < nkf; k++) X.pose[(size_t)k] = se3_from_float(Tcw + 12 * k);
+    for (int m = 0; m < nma; m++) X.pose[(size_t)(nkf + m)] = se3_from_float(Twm + 12 * m);
+    X.pt.resize((size_t)np * 3);
+    for (int i = 0; i < 3 * np; i++) X.pt[(size_t)i] = x3Dw[i];
+    return P.nv <= MAXV;
+}
+
+} // namespace
+
+// Tcw, x3Dw, Twm are in / out as in the library.  chi2_checks: 2 x (nobs + 4 nmobs) doubles, the cached chi2 of every edge at the two
+// checks (monocular edges, then marker edges).  Returns 0, or -4 beyond the pose bound.
+extern "C" int ref_lba(float* Tcw, const uint8_t* kf_fixed, int nkf, float* x3Dw, int np, const int32_t* obs_offset, const int32_t* obs_kf,
+                       const float* obs_xy, const int32_t* obs_octave, int nobs, const float* K4, const float* inv_sigma2, int nlevels,
+                       float* Twm, const float* marker_local, int nma, const int32_t* mobs_offset, const int32_t* mobs_kf,
+                       const float* mobs_corners, int nmobs, float marker_info, int use_markers, int order, uint8_t* erase, Result* res,
+                       double* chi2_checks)
+{
+    (void)nlevels;
+    std::memset(res, 0, sizeof(*res));
+    Prob P;
+    Est X;
+    if (!setup(P, X, Tcw, kf_fixed, nkf, x3Dw, np, obs_offset, obs_kf, obs_xy, obs_octave, nobs, K4, inv_sigma2, Twm, marker_local, nma,
+               mobs_offset, mobs_kf, mobs_corners, nmobs, marker_info, use_markers, order))
+        return -4;
+    Cache C;
+    C.e_chi2.assign((size_t)nobs, 0.); C.m_chi2.assign((size_t)P.nme, 0.); C.e_level.assign((size_t)nobs, 0); C.m_level.assign((size_t)P.nme, 0);
+    std::vector<double> xv((size_t)6 * MAXV, 0.), xl((size_t)3 * std::max(np, 1), 0.);
+    const int ne = nobs + 4 * nmobs;
+    bool stale;
+    res->n_edges_mono = nobs;
+    res->n_edges_marker = P.nme;
+    res->iterations[0] = optimize(P, C, X, true, 5, xv, xl, stale);
+    res->stale_mask |= stale ? 1 : 0;
+    auto depth = [&](int e) {
+        double Xc[3];
+        map(X.pose[(size_t)obs_kf[e]], &X.pt[(size_t)P.e_pt[(size_t)e] * 3], Xc);
+        return Xc[2];
+    };
+    P.e_pt.assign((size_t)nobs, 0);
+    for (int pi = 0; pi < np; pi++)
+        for (int e = obs_offset[pi]; e < obs_offset[pi + 1]; e++) P.e_pt[(size_t)e] = pi;
+    for (int e = 0; e < nobs; e++) {
+        if (chi2_checks) chi2_checks[e] = C.e_chi2[(size_t)e];
+        if (!(C.e_chi2[(size_t)e] <= 5.991) || !(depth(e) > 0.0)) {
+            C.e_level[(size_t)e] = 1;
+            res->n_level1[0]++;
+        }
+    }
+    for (int j = 0; j < P.nme; j++) {
+        if (chi2_checks) chi2_checks[nobs + j] = C.m_chi2[(size_t)j];
+        if (!(C.m_chi2[(size_t)j] <= 5.991)) {
+            C.m_level[(size_t)j] = 1;
+            res->n_level1[1]++;
+        }
+    }
+    res->iterations[1] = optimize(P, C, X, false, 10, xv, xl, stale);
+    res->stale_mask |= stale ? 2 : 0;
+    for (int e = 0; e < nobs; e++) {
+        if (chi2_checks) chi2_checks[ne + e] = C.e_chi2[(size_t)e];
+        erase[e] = !(C.e_chi2[(size_t)e] <= 5.991) || !(depth(e) > 0.0);
+        res->n_erase += erase[e];
+    }
+    for (int j = 0; j < P.nme && chi2_checks; j++) chi2_checks[ne + nobs + j] = C.m_chi2[(size_t)j];
+    for (int k = 0; k < nkf; k++)
+        if (!kf_fixed[k]) to_float(X.pose[(size_t)k], Tcw + 12 * k);
+    for (int m = 0; use_markers && m < nma; m++) to_float(X.pose[(size_t)(nkf + m)], Twm + 12 * m);
+    for (int i = 0; i < 3 * np; i++) x3Dw[i] = (float)X.pt[(size_t)i];
+    return 0;
+}
+
+// One linearisation (all edges, Huber) and the first trial, as orbfe_lba_inspect.  full_H (may be NULL): the whole system with lambda0
+// on its diagonal, (6 nv + 3 np)^2 row-major, poses first; b holds its right-hand side.
+extern "C" int ref_lba_inspect(const float* Tcw, const uint8_t* kf_fixed, int nkf, const float* x3Dw, int np, const int32_t* obs_offset,
+                               const int32_t* obs_kf, const float* obs_xy, const int32_t* obs_octave, int nobs, const float* K4,
+                               const float* inv_sigma2, int nlevels, const float* Twm, const float* marker_local, int nma,
+                               const int32_t* mobs_offset, const int32_t* mobs_kf, const float* mobs_corners, int nmobs, float marker_info,
+                               int use_markers, int order, int32_t* nv, double* b, double* Hpp, double* Hll, double* chi2, double* x,
+                               double* full_H)
+{
+    (void)nlevels;
+    Prob P;
+    Est X, Xt;
+    if (!setup(P, X, Tcw, kf_fixed, nkf, x3Dw, np, obs_offset, obs_kf, obs_xy, obs_octave, nobs, K4, inv_sigma2, Twm, marker_local, nma,
+               mobs_offset, mobs_kf, mobs_corners, nmobs, marker_info, use_markers, order))
+        return -4;
+    Cache C;
+    C.e_chi2.assign((size_t)nobs, 0.); C.m_chi2.assign((size_t)P.nme, 0.); C.e_level.assign((size_t)nobs, 0); C.m_level.assign((size_t)P.nme, 0);
+    Lin L;
+    linearize(P, X, true, C, L);
+    const double lambda = 1e-5 * L.maxdiag;
+    *nv = P.nv;
+    chi2[0] = L.chi;
+    chi2[1] = lambda;
+    std::memcpy(b, L.bp.data(), (size_t)P.nv * 48);
+    std::memcpy(b + 6 * P.nv, L.bl.data(), (size_t)np * 24);
+    std::memcpy(Hpp, L.Hpp.data(), (size_t)P.nv * 288);
+    std::memcpy(Hll, L.Hll.data(), (size_t)np * 48);
+    if (full_H) {
+        const int n = 6 * P.nv + 3 * np;
+        std::fill(full_H, full_H + (size_t)n * n, 0.);
+        auto at = [&](int r, int c) -> double& { return full_H[(size_t)r * n + c]; };
+        for (int v = 0; v < P.nv; v++)
+            for (int a = 0; a < 6; a++)
+                for (int c = 0; c < 6; c++) at(6 * v + a, 6 * v + c) = L.Hpp[(size_t)v * 36 + a * 6 + c] + (a == c ? lambda : 0.);
+        for (int pi = 0; pi < np; pi++) {
+            const double* H = &L.Hll[(size_t)pi * 6];
+            const int o = 6 * P.nv + 3 * pi, idx[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
+            for (int a = 0; a < 3; a++)
+                for (int c = 0; c < 3; c++) at(o + a, o + c) = H[idx[a][c]] + (a == c ? lambda : 0.);
+            for (int e = obs_offset[pi]; e < obs_offset[pi + 1]; e++) {
+                if (L.euse[(size_t)e] != 3) continue;
+                const int v = P.kf_free[(size_t)obs_kf[e]];
+                for (int a = 0; a < 6; a++)
+                    for (int c = 0; c < 3; c++) at(6 * v + a, o + c) = at(o + c, 6 * v + a) = L.eblk[(size_t)e * EB + 27 + a * 3 + c];
+            }
+        }
+        for (int j = 0; j < P.nme; j++) {
+            const int vc = P.kf_free[(size_t)mobs_kf[j >> 2]], vm = P.nv - (use_markers ? nma : 0) + P.mo_marker[(size_t)(j >> 2)];
+            if (vc < 0 || !L.muse[(size_t)j]) continue;
+            for (int a = 0; a < 6; a++)
+                for (int c = 0; c < 6; c++) {
+                    at(6 * vc + a, 6 * vm + c) += L.mblk[(size_t)j * MB + 54 + a * 6 + c];
+                    at(6 * vm + c, 6 * vc + a) += L.mblk[(size_t)j * MB + 54 + a * 6 + c];
+                }
+        }
+    }
+    std::vector<double> xv((size_t)6 * MAXV, 0.), xl((size_t)3 * std::max(np, 1), 0.);
+    double tempChi, sp;
+    trial(P, C, L, lambda, true, X, Xt, xv, xl, tempChi, sp);
+    std::memcpy(x, xv.data(), (size_t)P.nv * 48);
+    std::memcpy(x + 6 * P.nv, xl.data(), (size_t)np * 24);
+    return 0;
+}
+
+// One EdgeSE3ProjectXYZ at exp(u) * Tcw and X: the error and g2o's analytic Jacobians (pose 2 x 6, point 2 x 3)
+extern "C" void ref_lba_mono_edge(const float* Tcw, const double* u, const double* X, const double* obs, const float* K4, double* err,
+                                  double* Jp, double* Jx)
+{
+    const Cam K{K4[0], K4[1], K4[2], K4[3]};
+    const SE3 T = mul(se3_exp(u), se3_from_float(Tcw));
+    double e[2], jp[2][6], jx[2][3];
+    mono_linearize(T, X, obs[0], obs[1], K, e, jp, jx);
+    std::memcpy(err, e, sizeof(e));
+    std::memcpy(Jp, jp, sizeof(jp));
+    std::memcpy(Jx, jx, sizeof(jx));
+}
+
+// One EdgeMarker: the error and g2o's numeric Jacobians on the camera and on the marker vertex
+extern "C" void ref_lba_marker_edge(const float* Tcw, const float* Twm, const double* p, const double* obs, const float* K4, double* err,
+                                    double* Jc, double* Jm)
+{
+    const Cam K{K4[0], K4[1], K4[2], K4[3]};
+    const SE3 Tc = se3_from_float(Tcw), Tm = se3_from_float(Twm);
+    double e[2], jc[2][6], jm[2][6];
+    marker_error(Tc, Tm, p, obs[0], obs[1], K, e);
+    marker_jacobian(Tc, Tm, true, p, obs[0], obs[1], K, jc);
+    marker_jacobian(Tc, Tm, false, p, obs[0], obs[1], K, jm);
+    std::memcpy(err, e, sizeof(e));
+    std::memcpy(Jc, jc, sizeof(jc));
+    std::memcpy(Jm, jm, sizeof(jm));
+}
+
+// The anchor to tests/pose_opt_ref.cpp: the points are held, so the problem is the motion-only one -- one optimize(maxit) with Huber
+// over the same edges, from the same poses.  Tcw is in / out; returns the LM iterations run.
+extern "C" int ref_lba_poses_only(float* Tcw, const uint8_t* kf_fixed, int nkf, const float* x3Dw, int np, const int32_t* obs_offset,
+                                  const int32_t* obs_kf, const float* obs_xy, const int32_t* obs_octave, int nobs, const float* K4,
+                                  const float* inv_sigma2, int maxit, int order)
+{
+    Prob P;
+    Est X;
+    P.fix_points = true;
+    if (!setup(P, X, Tcw, kf_fixed, nkf, x3Dw, np, obs_offset, obs_kf, obs_xy, obs_octave, nobs, K4, inv_sigma2, nullptr, nullptr, 0, nullptr,
+               nullptr, nullptr, 0, 0.f, 0, order))
+        return -4;
+    Cache C;
+    C.e_chi2.assign((size_t)nobs, 0.); C.e_level.assign((size_t)nobs, 0);
+    std::vector<double> xv((size_t)6 * MAXV, 0.), xl((size_t)3 * std::max(np, 1), 0.);
+    bool stale;
+    const int it = optimize(P, C, X, true, maxit, xv, xl, stale);
+    for (int k = 0; k < nkf; k++)
+        if (!kf_fixed[k]) to_float(X.pose[(size_t)k], Tcw + 12 * k);
+    return it;
+}
