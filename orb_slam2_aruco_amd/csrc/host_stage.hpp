@@ -1,6 +1,7 @@
 // host_stage.hpp -- what the host-pointer entry points of the geometry solvers (initializer.hip, sim3_solver.hip, pose_optimizer.hip,
 // orbfe_marker_poses, orbfe_corner_subpix) and of the matcher (match_kernels.hip, bow_vocabulary.hip, keyframe_io.hip) share: the
-// layout of one staging block and the workspace that moves it.  Host code only.
+// layout of one staging block and the workspace that moves it.  Host code only.  IoLayout alone is what the HIP-free plan headers
+// take from here: new_points_plan.hpp for its staging block, lba_plan.hpp for the staging block and the scratch of local_ba.hip.
 #pragma once
 #include <cstddef>
 

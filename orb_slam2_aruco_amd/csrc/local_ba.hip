@@ -22,7 +22,10 @@
 // g2o's cached edge errors are the chi2 cache e_chi2 / m_chi2: written by every pass that evaluates an edge (the linearisation and
 // each trial, rejected ones included), read by the checks -- so a round that ends on a rejected trial leaves that trial's errors
 // there, and an edge at level 1 keeps its value of round 1, as in the reference.
+// What the entry points decide before they launch -- the validation, the scratch layout, the staging block, the launch schedule --
+// is host arithmetic in lba_plan.hpp (the camera and level-table step, shared with pose_optimizer.hip, in ba_camera.hpp).
 #include "host_stage.hpp"
+#include "lba_plan.hpp"
 #include "lm_dense.hpp"
 #include "orbfe_common.hpp"
 #include "se3_quat.hpp"
@@ -32,23 +35,8 @@
 namespace orbfe {
 namespace {
 
-constexpr int LBA_MAXV = ORBFE_LBA_MAX_FREE_POSES;
-constexpr int LBA_N = 6 * LBA_MAXV;     // rows of S, and its row stride
-constexpr int LBA_PT = 64;              // threads of the per-point kernels: one wave, so that a few thousand points are many workgroups
-constexpr int LBA_MAX_LEVELS = 32;
-constexpr int LBA_EBLK = 45;            // doubles of a monocular edge's blocks: A = Jp^T w Jp (21), b (6), W = Jp^T w Jx (6 x 3)
-constexpr int LBA_MBLK = 90;            // of a marker edge: Acc (21), bc (6), Amm (21), bm (6), Acm (36)
 constexpr int LBA_BAD_INVALID = 1, LBA_BAD_CAPACITY = 2;
-
-struct LbaCtl {
-    double lambda, ni, currentChi, iniChi, rho, lambda0;
-    int q, it, nbad_lm, ok2;
-    int iter_go, trial_go, cur, round;
-    int stopped, stale, abort_status, bad;
-    int nfree_kf, nv, aborted, pad0;
-    int iters[2], n_level1[2];
-    int n_erase, stale_mask, pad1, pad2;
-};
+static_assert(sizeof(SE3) == LBA_SE3_BYTES, "lba_plan.hpp lays the pose arrays out for this size");
 
 struct LbaP {
     // the caller's arrays
@@ -60,7 +48,7 @@ struct LbaP {
     Cam K;
     double delta, marker_info;
     float inv_sigma2[LBA_MAX_LEVELS];
-    // scratch
+    // scratch: lba_scratch of lba_plan.hpp gives every pointer its array
     LbaCtl* ctl;
     SE3* pose[2];          // nkf keyframes, then nma markers
     double* pt[2];         // np x 3
@@ -72,70 +60,6 @@ struct LbaP {
     double *S, *bs, *chi_part, *scale_part, *max_part;
 };
 
-// ---------------------------------------------------------------------------------------- scratch layout --
-struct LbaLayout {
-    size_t ctl, zero_end, pose[2], pt[2], e_kf, e_pt, e_ox, e_oy, e_info, e_level, e_use, e_chi2, e_blk, mo_marker, m_level, m_use, m_chi2,
-        m_blk, Hll, bl, Dinv, xl, p_active, Hpp, bp, xv, vmax, v_active, v_kf, kf_free, tbl, tbl_bytes, S, bs, chi_part, scale_part, max_part,
-        end;
-    int npb, nb;
-};
-
-LbaLayout lba_layout(int nkf, int np, int nobs, int nma, int nmobs)
-{
-    LbaLayout l{};
-    IoLayout o;
-    const size_t K = (size_t)std::max(nkf, 1), P = (size_t)std::max(np, 1), E = (size_t)std::max(nobs, 1), M = (size_t)std::max(nma, 1),
-                 MO = (size_t)std::max(nmobs, 1), ME = 4 * MO;
-    l.npb = (np + LBA_PT - 1) / LBA_PT;
-    l.nb = l.npb + (4 * nmobs + LBA_PT - 1) / LBA_PT;
-    const size_t NB = (size_t)std::max(l.nb, 1);
-    // zeroed at every call: the state, the updates, the chi2 caches (an edge no pass evaluated has g2o's initial error 0), the levels
-    l.ctl = o.take(sizeof(LbaCtl));
-    l.xv = o.take(LBA_N * 8);
-    l.xl = o.take(P * 24);
-    l.e_chi2 = o.take(E * 8);
-    l.m_chi2 = o.take(ME * 8);
-    l.e_level = o.take(E);
-    l.m_level = o.take(ME);
-    l.zero_end = o.end();
-    for (int k = 0; k < 2; k++) l.pose[k] = o.take((K + M) * sizeof(SE3));
-    for (int k = 0; k < 2; k++) l.pt[k] = o.take(P * 24);
-    l.e_kf = o.take(E * 4); l.e_pt = o.take(E * 4); l.e_ox = o.take(E * 4); l.e_oy = o.take(E * 4); l.e_info = o.take(E * 4);
-    l.e_use = o.take(E);
-    l.e_blk = o.take(E * LBA_EBLK * 8);
-    l.mo_marker = o.take(MO * 4);
-    l.m_use = o.take(ME);
-    l.m_blk = o.take(ME * LBA_MBLK * 8);
-    l.Hll = o.take(P * 48); l.bl = o.take(P * 24); l.Dinv = o.take(P * 72); l.p_active = o.take(P);
-    l.Hpp = o.take(LBA_MAXV * 36 * 8); l.bp = o.take(LBA_N * 8); l.vmax = o.take(LBA_MAXV * 8);
-    l.v_active = o.take(LBA_MAXV * 4); l.v_kf = o.take(LBA_MAXV * 4); l.kf_free = o.take(K * 4);
-    l.tbl_bytes = K * P * 4;
-    l.tbl = o.take(l.tbl_bytes);
-    l.S = o.take((size_t)LBA_N * LBA_N * 8); l.bs = o.take(LBA_N * 8);
-    l.chi_part = o.take(NB * 8); l.scale_part = o.take(NB * 8); l.max_part = o.take(NB * 8);
-    l.end = o.end();
-    return l;
-}
-
-void lba_bind(LbaP& p, const LbaLayout& l, void* scratch)
-{
-    unsigned char* s = (unsigned char*)scratch;
-    p.ctl = (LbaCtl*)(s + l.ctl);
-    for (int k = 0; k < 2; k++) { p.pose[k] = (SE3*)(s + l.pose[k]); p.pt[k] = (double*)(s + l.pt[k]); }
-    p.e_kf = (int32_t*)(s + l.e_kf); p.e_pt = (int32_t*)(s + l.e_pt); p.e_ox = (float*)(s + l.e_ox); p.e_oy = (float*)(s + l.e_oy);
-    p.e_info = (float*)(s + l.e_info); p.e_level = s + l.e_level; p.e_use = s + l.e_use; p.e_chi2 = (double*)(s + l.e_chi2);
-    p.e_blk = (double*)(s + l.e_blk);
-    p.mo_marker = (int32_t*)(s + l.mo_marker); p.m_level = s + l.m_level; p.m_use = s + l.m_use; p.m_chi2 = (double*)(s + l.m_chi2);
-    p.m_blk = (double*)(s + l.m_blk);
-    p.Hll = (double*)(s + l.Hll); p.bl = (double*)(s + l.bl); p.Dinv = (double*)(s + l.Dinv); p.xl = (double*)(s + l.xl);
-    p.p_active = s + l.p_active;
-    p.Hpp = (double*)(s + l.Hpp); p.bp = (double*)(s + l.bp); p.xv = (double*)(s + l.xv); p.vmax = (double*)(s + l.vmax);
-    p.v_active = (int32_t*)(s + l.v_active); p.v_kf = (int32_t*)(s + l.v_kf); p.kf_free = (int32_t*)(s + l.kf_free);
-    p.tbl = (int32_t*)(s + l.tbl);
-    p.S = (double*)(s + l.S); p.bs = (double*)(s + l.bs);
-    p.chi_part = (double*)(s + l.chi_part); p.scale_part = (double*)(s + l.scale_part); p.max_part = (double*)(s + l.max_part);
-    p.npb = l.npb; p.nb = l.nb;
-}
 
 // ---------------------------------------------------------------------------------------- small pieces --
 __device__ __forceinline__ double wave_sum(double v)
@@ -891,154 +815,81 @@ __global__ __launch_bounds__(256) void k_lba_finish(LbaP p)
 }
 
 // ---------------------------------------------------------------------------------------- host --
-int lba_fill(LbaP& p, const float* K4, const float* inv_sigma2, int nlevels, float marker_info, const char* name)
+int report(const BaCheck& c) { return c.err ? fail(c.err, "%s", c.msg) : ORBFE_OK; }
+
+// what a call is given beside its arrays: the camera and the level table (every entry finite here), the marker weight and switch
+int lba_fill(LbaP& p, const float* K4, const float* inv_sigma2, int nlevels, float marker_info, int use_markers, const char* name)
 {
-    if (!K4 || !inv_sigma2 || nlevels <= 0 || nlevels > LBA_MAX_LEVELS) return fail(ORBFE_ERR_INVALID, "%s: invalid K4 / sigma table", name);
-    for (int i = 0; i < 4; i++)
-        if (!std::isfinite(K4[i])) return fail(ORBFE_ERR_INVALID, "%s: K is not finite", name);
-    if (K4[0] == 0 || K4[1] == 0) return fail(ORBFE_ERR_INVALID, "%s: fx or fy is 0", name);
-    if (!std::isfinite(marker_info)) return fail(ORBFE_ERR_INVALID, "%s: marker_info is not finite", name);
+    BaCamera c;
+    const int rc = report(ba_camera(c, K4, inv_sigma2, nlevels, marker_info, name));
+    if (rc) return rc;
     for (int l = 0; l < nlevels; l++)
         if (!std::isfinite(inv_sigma2[l])) return fail(ORBFE_ERR_INVALID, "%s: inv_level_sigma2 is not finite", name);
     p.nlevels = nlevels;
-    for (int l = 0; l < LBA_MAX_LEVELS; l++) p.inv_sigma2[l] = l < nlevels ? inv_sigma2[l] : 0.f;
-    p.K = Cam{K4[0], K4[1], K4[2], K4[3]};
+    for (int l = 0; l < LBA_MAX_LEVELS; l++) p.inv_sigma2[l] = c.inv_sigma2[l];
+    p.K = Cam{c.fx, c.fy, c.cx, c.cy};
     p.marker_info = marker_info;
-    p.delta = (double)(float)std::sqrt(5.991);
+    p.delta = c.delta;
+    p.use_markers = use_markers != 0;
     return ORBFE_OK;
 }
 
-// the launches of one call: inspect = one linearisation and one trial, nothing written to the caller's arrays
+// the launches of one call, every number from the schedule: inspect = one linearisation and one trial, nothing written to the
+// caller's arrays
 int lba_enqueue(LbaP& p, void* scratch, hipStream_t s, bool inspect)
 {
-    const LbaLayout l = lba_layout(p.nkf, p.np, p.nobs, p.nma, p.nmobs);
-    lba_bind(p, l, scratch);
+    const LbaSizes n{p.nkf, p.np, p.nobs, p.nma, p.nmobs};
+    const LbaExtent x = lba_scratch(p, n, scratch);
+    const LbaSchedule k = lba_schedule(n, p.use_markers != 0, inspect, (size_t)max_lds());
     p.nme = p.use_markers ? 4 * p.nmobs : 0;
-    if (!p.use_markers) p.nb = p.npb;
-    ORBFE_HIP(hipMemsetAsync(scratch, 0, l.zero_end, s));
-    ORBFE_HIP(hipMemsetAsync(p.tbl, 0xff, l.tbl_bytes, s));
-    const int nmax = std::max(std::max(p.nobs, p.np), std::max(p.nkf + p.nma, p.nmobs));
-    const dim3 gsetup((nmax + 255) / 256 > 0 ? (nmax + 255) / 256 : 1), gpt(std::max(p.nb, 1)), gpo(std::max(p.npb, 1));
-    const dim3 gedge((p.nobs + p.nme + 255) / 256 > 0 ? (p.nobs + p.nme + 255) / 256 : 1);
-    // the free vertices are counted on the device; the host knows an upper bound, which keeps the grids of the per-vertex kernels small
-    const int vmax = std::max(1, std::min(LBA_MAXV, p.nkf + (p.use_markers ? p.nma : 0)));
-    // the reduced system's lower triangle in LDS, as many rows as the workgroup may have (the kernel's own 3 KB aside)
-    int lds_rows = 6 * vmax;
-    while (lds_rows > 0 && (size_t)lds_rows * (lds_rows + 1) / 2 * 8 + 4096 > (size_t)max_lds()) lds_rows -= 6;
-    const size_t tri_bytes = (size_t)lds_rows * (lds_rows + 1) / 2 * 8;
-    int rc = ensure_dyn_lds((const void*)k_lba_solve, tri_bytes);
+    p.npb = k.npb;
+    p.nb = k.nb;
+    ORBFE_HIP(hipMemsetAsync(scratch, 0, x.zero_end, s));
+    ORBFE_HIP(hipMemsetAsync(p.tbl, 0xff, x.tbl_bytes, s));
+    int rc = ensure_dyn_lds((const void*)k_lba_solve, k.tri_bytes);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_lba_setup, gsetup, dim3(256), 0, s, p);
-    for (int round = 0; round < (inspect ? 1 : 2); round++) {
+    hipLaunchKernelGGL(k_lba_setup, dim3(k.g_setup), dim3(256), 0, s, p);
+    for (int round = 0; round < k.rounds; round++) {
         hipLaunchKernelGGL(k_lba_begin, dim3(1), dim3(64), 0, s, p, round);
-        if (round == 1) hipLaunchKernelGGL(k_lba_check, gedge, dim3(256), 0, s, p, 0);
-        const int maxit = inspect ? 1 : round == 0 ? 5 : 10;
-        for (int it = 0; it < maxit; it++) {
-            hipLaunchKernelGGL(k_lba_linearize, gpt, dim3(LBA_PT), 0, s, p);
-            hipLaunchKernelGGL(k_lba_pose_blocks, dim3(vmax), dim3(LM_THREADS), 0, s, p);
+        if (round == 1) hipLaunchKernelGGL(k_lba_check, dim3(k.g_edges), dim3(256), 0, s, p, 0);
+        for (int it = 0; it < k.maxit[round]; it++) {
+            hipLaunchKernelGGL(k_lba_linearize, dim3(k.g_pass), dim3(LBA_PT), 0, s, p);
+            hipLaunchKernelGGL(k_lba_pose_blocks, dim3(k.vmax), dim3(LM_THREADS), 0, s, p);
             hipLaunchKernelGGL(k_lba_ctl_lin, dim3(1), dim3(LM_THREADS), 0, s, p);
-            for (int q = 0; q < (inspect ? 1 : 10); q++) {
-                hipLaunchKernelGGL(k_lba_schur_points, gpo, dim3(LBA_PT), 0, s, p);
-                hipLaunchKernelGGL(k_lba_assemble, dim3(vmax, vmax), dim3(64), 0, s, p);
-                hipLaunchKernelGGL(k_lba_solve, dim3(1), dim3(LM_THREADS), tri_bytes, s, p, lds_rows);
-                hipLaunchKernelGGL(k_lba_backsub, gpt, dim3(LBA_PT), 0, s, p);
-                if (!inspect) hipLaunchKernelGGL(k_lba_ctl_trial, dim3(1), dim3(LM_THREADS), 0, s, p, maxit);
+            for (int q = 0; q < k.trials; q++) {
+                hipLaunchKernelGGL(k_lba_schur_points, dim3(k.g_points), dim3(LBA_PT), 0, s, p);
+                hipLaunchKernelGGL(k_lba_assemble, dim3(k.vmax, k.vmax), dim3(64), 0, s, p);
+                hipLaunchKernelGGL(k_lba_solve, dim3(1), dim3(LM_THREADS), k.tri_bytes, s, p, k.lds_rows);
+                hipLaunchKernelGGL(k_lba_backsub, dim3(k.g_pass), dim3(LBA_PT), 0, s, p);
+                if (!inspect) hipLaunchKernelGGL(k_lba_ctl_trial, dim3(1), dim3(LM_THREADS), 0, s, p, k.maxit[round]);
             }
         }
     }
     if (!inspect) {
-        hipLaunchKernelGGL(k_lba_check, gedge, dim3(256), 0, s, p, 1);
-        hipLaunchKernelGGL(k_lba_finish, gsetup, dim3(256), 0, s, p);
+        hipLaunchKernelGGL(k_lba_check, dim3(k.g_edges), dim3(256), 0, s, p, 1);
+        hipLaunchKernelGGL(k_lba_finish, dim3(k.g_setup), dim3(256), 0, s, p);
     }
     ORBFE_HIP(hipGetLastError());
     return ORBFE_OK;
 }
 
-bool lba_sizes_ok(int nkf, int np, int nobs, int nma, int nmobs)
-{
-    return nkf >= 0 && np >= 0 && nobs >= 0 && nma >= 0 && nmobs >= 0 && (size_t)std::max(nkf, 1) * (size_t)std::max(np, 1) < ((size_t)1 << 30) &&
-           nmobs < (1 << 24);
-}
-
 thread_local ThreadWorkspaces<HostStage> tl_lba_stages;
 
-// the checks of the host call (the device call leaves them to k_lba_setup / k_lba_begin)
-int lba_check_host(const float* Tcw, const uint8_t* kf_fixed, int nkf, const float* x3Dw, int np, const int32_t* obs_offset,
-                   const int32_t* obs_kf, const float* obs_xy, const int32_t* obs_octave, int nobs, int nlevels, const float* Twm,
-                   const float* marker_local, int nma, const int32_t* mobs_offset, const int32_t* mobs_kf, const float* mobs_corners, int nmobs,
-                   int use_markers, const char* name)
+// stage a problem of host arrays as lba_host_io lays it out, send it, and point the kernels' argument at the device copy
+int lba_stage(HostStage& w, LbaHostIo& io, LbaP& p, const LbaProblem& pb)
 {
-    if (!lba_sizes_ok(nkf, np, nobs, nma, nmobs) || (nkf && (!Tcw || !kf_fixed)) || (np && (!x3Dw || !obs_offset)) ||
-        (nobs && (!obs_kf || !obs_xy || !obs_octave || !np)) || (nma && (!Twm || !marker_local || !mobs_offset)) ||
-        (nmobs && (!mobs_kf || !mobs_corners || !nma)))
-        return fail(ORBFE_ERR_INVALID, "%s: invalid argument", name);
-    auto fin = [](const float* v, size_t n) {
-        for (size_t i = 0; i < n; i++)
-            if (!std::isfinite(v[i])) return false;
-        return true;
-    };
-    if (!fin(Tcw, (size_t)nkf * 12) || !fin(x3Dw, (size_t)np * 3) || !fin(obs_xy, (size_t)nobs * 2) || !fin(Twm, (size_t)nma * 12) ||
-        !fin(marker_local, (size_t)nma * 12) || !fin(mobs_corners, (size_t)nmobs * 8))
-        return fail(ORBFE_ERR_INVALID, "%s: an input is not finite", name);
-    if (np && (obs_offset[0] != 0 || obs_offset[np] != nobs)) return fail(ORBFE_ERR_INVALID, "%s: obs_offset does not span [0, nobs]", name);
-    if (!np && nobs) return fail(ORBFE_ERR_INVALID, "%s: observations without points", name);
-    for (int i = 0; i < np; i++)
-        if (obs_offset[i + 1] < obs_offset[i]) return fail(ORBFE_ERR_INVALID, "%s: obs_offset decreases at point %d", name, i);
-    if (nma && (mobs_offset[0] != 0 || mobs_offset[nma] != nmobs)) return fail(ORBFE_ERR_INVALID, "%s: mobs_offset does not span [0, nmobs]", name);
-    for (int i = 0; i < nma; i++)
-        if (mobs_offset[i + 1] < mobs_offset[i]) return fail(ORBFE_ERR_INVALID, "%s: mobs_offset decreases at marker %d", name, i);
-    for (int e = 0; e < nobs; e++) {
-        if (obs_kf[e] < 0 || obs_kf[e] >= nkf) return fail(ORBFE_ERR_INVALID, "%s: observation %d names keyframe %d of %d", name, e, obs_kf[e], nkf);
-        if (obs_octave[e] < 0 || obs_octave[e] >= nlevels)
-            return fail(ORBFE_ERR_INVALID, "%s: observation %d has octave %d, outside [0, %d)", name, e, obs_octave[e], nlevels);
-    }
-    for (int e = 0; e < nmobs; e++)
-        if (mobs_kf[e] < 0 || mobs_kf[e] >= nkf) return fail(ORBFE_ERR_INVALID, "%s: marker observation %d names keyframe %d of %d", name, e, mobs_kf[e], nkf);
-    std::vector<int> seen((size_t)std::max(nkf, 1), -1);
-    for (int i = 0; i < np; i++)
-        for (int e = obs_offset[i]; e < obs_offset[i + 1]; e++) {
-            if (seen[(size_t)obs_kf[e]] == i) return fail(ORBFE_ERR_INVALID, "%s: keyframe %d observes point %d twice", name, obs_kf[e], i);
-            seen[(size_t)obs_kf[e]] = i;
-        }
-    int nv = use_markers ? nma : 0;
-    for (int k = 0; k < nkf; k++) nv += kf_fixed[k] == 0;
-    if (nv > LBA_MAXV)
-        return fail(ORBFE_ERR_CAPACITY, "%s: %d free pose vertices (keyframes and markers), at most ORBFE_LBA_MAX_FREE_POSES = %d", name, nv, LBA_MAXV);
-    for (int i = 0; i < np; i++)
-        if (obs_offset[i + 1] - obs_offset[i] > ORBFE_LBA_MAX_OBSERVATIONS)
-            return fail(ORBFE_ERR_CAPACITY, "%s: point %d has %d observations, at most ORBFE_LBA_MAX_OBSERVATIONS = %d", name, i,
-                        obs_offset[i + 1] - obs_offset[i], ORBFE_LBA_MAX_OBSERVATIONS);
-    return ORBFE_OK;
-}
-
-struct LbaHostIo {
-    size_t fixed, off, kf, xy, oct, mloc, moff, mkf, mcor, T, X, M, erase, res;
-};
-
-// stage a problem of host arrays: everything up, the estimates, the erase bytes and the record down
-int lba_stage(HostStage& w, LbaHostIo& io, LbaP& p, const float* Tcw, const uint8_t* kf_fixed, int nkf, const float* x3Dw, int np,
-              const int32_t* obs_offset, const int32_t* obs_kf, const float* obs_xy, const int32_t* obs_octave, int nobs, const float* Twm,
-              const float* marker_local, int nma, const int32_t* mobs_offset, const int32_t* mobs_kf, const float* mobs_corners, int nmobs)
-{
-    const size_t K = (size_t)std::max(nkf, 1), P = (size_t)std::max(np, 1), E = (size_t)std::max(nobs, 1), M = (size_t)std::max(nma, 1),
-                 MO = (size_t)std::max(nmobs, 1);
-    IoLayout l;
-    io.fixed = l.take(K); io.off = l.take((P + 1) * 4); io.kf = l.take(E * 4); io.xy = l.take(E * 8); io.oct = l.take(E * 4);
-    io.mloc = l.take(M * 48); io.moff = l.take((M + 1) * 4); io.mkf = l.take(MO * 4); io.mcor = l.take(MO * 32);
-    l.inout();
-    io.T = l.take(K * 48); io.X = l.take(P * 12); io.M = l.take(M * 48);
-    l.outputs();
-    io.erase = l.take(E); io.res = l.take(sizeof(orbfe_lba_result));
+    const LbaSizes& n = pb.n;
+    io = lba_host_io(n);
     int rc;
-    if ((rc = w.begin(l))) return rc;
+    if ((rc = w.begin(io.io))) return rc;
     const int32_t zero2[2] = {0, 0};
-    w.put(io.fixed, kf_fixed, (size_t)nkf);
-    w.put(io.off, np ? (const void*)obs_offset : (const void*)zero2, np ? (size_t)(np + 1) * 4 : 8);
-    w.put(io.kf, obs_kf, (size_t)nobs * 4); w.put(io.xy, obs_xy, (size_t)nobs * 8); w.put(io.oct, obs_octave, (size_t)nobs * 4);
-    w.put(io.mloc, marker_local, (size_t)nma * 48);
-    w.put(io.moff, nma ? (const void*)mobs_offset : (const void*)zero2, nma ? (size_t)(nma + 1) * 4 : 8);
-    w.put(io.mkf, mobs_kf, (size_t)nmobs * 4); w.put(io.mcor, mobs_corners, (size_t)nmobs * 32);
-    w.put(io.T, Tcw, (size_t)nkf * 48); w.put(io.X, x3Dw, (size_t)np * 12); w.put(io.M, Twm, (size_t)nma * 48);
+    w.put(io.fixed, pb.kf_fixed, (size_t)n.nkf);
+    w.put(io.off, n.np ? (const void*)pb.obs_offset : (const void*)zero2, n.np ? (size_t)(n.np + 1) * 4 : 8);
+    w.put(io.kf, pb.obs_kf, (size_t)n.nobs * 4); w.put(io.xy, pb.obs_xy, (size_t)n.nobs * 8); w.put(io.oct, pb.obs_octave, (size_t)n.nobs * 4);
+    w.put(io.mloc, pb.marker_local, (size_t)n.nma * 48);
+    w.put(io.moff, n.nma ? (const void*)pb.mobs_offset : (const void*)zero2, n.nma ? (size_t)(n.nma + 1) * 4 : 8);
+    w.put(io.mkf, pb.mobs_kf, (size_t)n.nmobs * 4); w.put(io.mcor, pb.mobs_corners, (size_t)n.nmobs * 32);
+    w.put(io.T, pb.Tcw, (size_t)n.nkf * 48); w.put(io.X, pb.x3Dw, (size_t)n.np * 12); w.put(io.M, pb.Twm, (size_t)n.nma * 48);
     if ((rc = w.upload())) return rc;
     // upload() sends [0, split): the in-out arrays lie before the split
     p.kf_fixed = w.dev<const uint8_t>(io.fixed); p.obs_offset = w.dev<const int32_t>(io.off); p.obs_kf = w.dev<const int32_t>(io.kf);
@@ -1047,8 +898,24 @@ int lba_stage(HostStage& w, LbaHostIo& io, LbaP& p, const float* Tcw, const uint
     p.mobs_corners = w.dev<const float>(io.mcor);
     p.Tcw = w.dev<float>(io.T); p.x3Dw = w.dev<float>(io.X); p.Twm = w.dev<float>(io.M);
     p.erase = w.dev<uint8_t>(io.erase); p.res = w.dev<orbfe_lba_result>(io.res);
-    p.nkf = nkf; p.np = np; p.nobs = nobs; p.nma = nma; p.nmobs = nmobs;
+    p.stop = nullptr;
+    p.nkf = n.nkf; p.np = n.np; p.nobs = n.nobs; p.nma = n.nma; p.nmobs = n.nmobs;
     return ORBFE_OK;
+}
+
+// What both host calls do before they enqueue: the camera and the checks, on the host alone; then, unless the caller's stop flag is
+// set already (ORBFE_LBA_STOPPED: no device touched), the device, the stage `w` of this thread with the problem sent, the scratch.
+int lba_host_begin(LbaP& p, HostStage*& w, LbaHostIo& io, const LbaProblem& pb, const float* K4, const float* inv_sigma2, int nlevels,
+                   float marker_info, int use_markers, const uint8_t* stop, int device, const char* name)
+{
+    int rc;
+    if ((rc = lba_fill(p, K4, inv_sigma2, nlevels, marker_info, use_markers, name)) || (rc = report(lba_check_host(pb, nlevels, use_markers, name))))
+        return rc;
+    if (stop && *stop) return ORBFE_LBA_STOPPED;
+    if ((rc = use_device(device))) return rc;
+    w = &tl_lba_stages.get();
+    if ((rc = lba_stage(*w, io, p, pb))) return rc;
+    return w->host_scratch.ensure(lba_scratch_bytes(pb.n));
 }
 
 } // namespace
@@ -1058,8 +925,8 @@ using namespace orbfe;
 
 extern "C" size_t orbfe_lba_scratch_bytes(int nkf, int np, int nobs, int nma, int nmobs)
 {
-    if (!lba_sizes_ok(nkf, np, nobs, nma, nmobs)) return 0;
-    return lba_layout(nkf, np, nobs, nma, nmobs).end;
+    const LbaSizes n{nkf, np, nobs, nma, nmobs};
+    return lba_sizes_ok(n) ? lba_scratch_bytes(n) : 0;
 }
 
 extern "C" int orbfe_local_bundle_adjustment(float* Tcw, const uint8_t* kf_fixed, int nkf, float* x3Dw, int np, const int32_t* obs_offset,
@@ -1071,34 +938,25 @@ extern "C" int orbfe_local_bundle_adjustment(float* Tcw, const uint8_t* kf_fixed
 {
     static const char* name = "orbfe_local_bundle_adjustment";
     if (!res || (nobs > 0 && !erase)) return fail(ORBFE_ERR_INVALID, "%s: invalid argument", name);
+    const LbaProblem pb{{nkf, np, nobs, nma, nmobs}, Tcw, kf_fixed, x3Dw, obs_offset, obs_kf, obs_xy, obs_octave, nullptr, nullptr, 0,
+                        Twm, marker_local, mobs_offset, mobs_kf, mobs_corners};
     LbaP p{};
-    int rc = lba_fill(p, K4, inv_level_sigma2, nlevels, marker_info, name);
-    if (rc) return rc;
-    if ((rc = lba_check_host(Tcw, kf_fixed, nkf, x3Dw, np, obs_offset, obs_kf, obs_xy, obs_octave, nobs, nlevels, Twm, marker_local, nma,
-                             mobs_offset, mobs_kf, mobs_corners, nmobs, use_markers, name)))
-        return rc;
-    if (stop && *stop) {
+    HostStage* w = nullptr;
+    LbaHostIo io;
+    int rc = lba_host_begin(p, w, io, pb, K4, inv_level_sigma2, nlevels, marker_info, use_markers, stop, device, name);
+    if (rc == ORBFE_LBA_STOPPED) {
         orbfe_lba_result r{};
         r.status = ORBFE_LBA_STOPPED;
         *res = r;
         return ORBFE_OK;
     }
-    if ((rc = use_device(device))) return rc;
-    HostStage& w = tl_lba_stages.get();
-    LbaHostIo io;
-    if ((rc = lba_stage(w, io, p, Tcw, kf_fixed, nkf, x3Dw, np, obs_offset, obs_kf, obs_xy, obs_octave, nobs, Twm, marker_local, nma,
-                        mobs_offset, mobs_kf, mobs_corners, nmobs)))
-        return rc;
-    p.use_markers = use_markers != 0;
-    p.stop = nullptr;
-    if ((rc = w.host_scratch.ensure(lba_layout(nkf, np, nobs, nma, nmobs).end))) return rc;
-    if ((rc = lba_enqueue(p, w.host_scratch.p, w.stream, false)) || (rc = w.download()) || (rc = w.sync())) return rc;
-    *res = *w.host<const orbfe_lba_result>(io.res);
+    if (rc || (rc = lba_enqueue(p, w->host_scratch.p, w->stream, false)) || (rc = w->download()) || (rc = w->sync())) return rc;
+    *res = *w->host<const orbfe_lba_result>(io.res);
     if (res->status < 0) return fail(res->status, "%s: the device refused the problem (status %d)", name, res->status);
-    w.get(Tcw, io.T, (size_t)nkf * 48);
-    w.get(x3Dw, io.X, (size_t)np * 12);
-    if (use_markers) w.get(Twm, io.M, (size_t)nma * 48);
-    w.get(erase, io.erase, (size_t)nobs);
+    w->get(Tcw, io.T, (size_t)nkf * 48);
+    w->get(x3Dw, io.X, (size_t)np * 12);
+    if (use_markers) w->get(Twm, io.M, (size_t)nma * 48);
+    w->get(erase, io.erase, (size_t)nobs);
     return ORBFE_OK;
 }
 
@@ -1112,23 +970,18 @@ extern "C" int orbfe_local_bundle_adjustment_device(float* d_Tcw, const uint8_t*
                                                     void* d_scratch, size_t scratch_bytes, void* stream)
 {
     static const char* name = "orbfe_local_bundle_adjustment_device";
-    const bool form_xy = d_obs_xy != nullptr;
-    if (!lba_sizes_ok(nkf, np, nobs, nma, nmobs) || !d_res || !d_scratch || ((uintptr_t)d_scratch & 255) || (nkf && (!d_Tcw || !d_kf_fixed)) ||
-        (np && (!d_x3Dw || !d_obs_offset)) || (nobs && (!d_obs_kf || !d_erase || !np)) || (nobs && form_xy && !d_obs_octave) ||
-        (nobs && !form_xy && (!d_obs_feature || !d_kps || capacity <= 0)) || (nma && (!d_Twm || !d_marker_local || !d_mobs_offset)) ||
-        (nmobs && (!d_mobs_kf || !d_mobs_corners || !nma)))
-        return fail(ORBFE_ERR_INVALID, "%s: invalid argument", name);
-    const size_t need = lba_layout(nkf, np, nobs, nma, nmobs).end;
-    if (scratch_bytes < need) return fail(ORBFE_ERR_CAPACITY, "%s: %zu bytes of scratch, orbfe_lba_scratch_bytes asks for %zu", name, scratch_bytes, need);
+    const LbaProblem d{{nkf, np, nobs, nma, nmobs}, d_Tcw, d_kf_fixed, d_x3Dw, d_obs_offset, d_obs_kf, d_obs_xy, d_obs_octave, d_obs_feature,
+                       d_kps, capacity, d_Twm, d_marker_local, d_mobs_offset, d_mobs_kf, d_mobs_corners};
     LbaP p{};
-    int rc = lba_fill(p, K4, inv_level_sigma2, nlevels, marker_info, name);
-    if (rc) return rc;
+    int rc;
+    if ((rc = report(lba_check_device(d, d_erase, d_res, d_scratch, name))) || (rc = report(lba_check_scratch(d.n, scratch_bytes, name))) ||
+        (rc = lba_fill(p, K4, inv_level_sigma2, nlevels, marker_info, use_markers, name)))
+        return rc;
     p.Tcw = d_Tcw; p.kf_fixed = d_kf_fixed; p.x3Dw = d_x3Dw; p.obs_offset = d_obs_offset; p.obs_kf = d_obs_kf; p.obs_xy = d_obs_xy;
     p.obs_oct = d_obs_octave; p.obs_feat = d_obs_feature; p.kps = d_kps; p.capacity = capacity;
     p.Twm = d_Twm; p.mlocal = d_marker_local; p.mobs_offset = d_mobs_offset; p.mobs_kf = d_mobs_kf; p.mobs_corners = d_mobs_corners;
     p.stop = d_stop; p.erase = d_erase; p.res = d_res;
     p.nkf = nkf; p.np = np; p.nobs = nobs; p.nma = nma; p.nmobs = nmobs;
-    p.use_markers = use_markers != 0;
     return lba_enqueue(p, d_scratch, (hipStream_t)stream, false);
 }
 
@@ -1140,22 +993,16 @@ extern "C" int orbfe_lba_inspect(const float* Tcw, const uint8_t* kf_fixed, int 
 {
     static const char* name = "orbfe_lba_inspect";
     if (!nv || !b || !Hpp || !Hll || !chi2 || !x) return fail(ORBFE_ERR_INVALID, "%s: invalid argument", name);
+    // the estimates are read only: an inspect call fetches nothing back into them
+    const LbaProblem pb{{nkf, np, nobs, nma, nmobs}, const_cast<float*>(Tcw), kf_fixed, const_cast<float*>(x3Dw), obs_offset, obs_kf, obs_xy,
+                        obs_octave, nullptr, nullptr, 0, const_cast<float*>(Twm), marker_local, mobs_offset, mobs_kf, mobs_corners};
     LbaP p{};
-    int rc = lba_fill(p, K4, inv_level_sigma2, nlevels, marker_info, name);
-    if (rc) return rc;
-    if ((rc = lba_check_host(Tcw, kf_fixed, nkf, x3Dw, np, obs_offset, obs_kf, obs_xy, obs_octave, nobs, nlevels, Twm, marker_local, nma,
-                             mobs_offset, mobs_kf, mobs_corners, nmobs, use_markers, name)))
-        return rc;
-    if ((rc = use_device(device))) return rc;
-    HostStage& w = tl_lba_stages.get();
+    HostStage* w = nullptr;
     LbaHostIo io;
-    if ((rc = lba_stage(w, io, p, Tcw, kf_fixed, nkf, x3Dw, np, obs_offset, obs_kf, obs_xy, obs_octave, nobs, Twm, marker_local, nma,
-                        mobs_offset, mobs_kf, mobs_corners, nmobs)))
+    int rc;
+    if ((rc = lba_host_begin(p, w, io, pb, K4, inv_level_sigma2, nlevels, marker_info, use_markers, nullptr, device, name)) ||
+        (rc = lba_enqueue(p, w->host_scratch.p, w->stream, true)) || (rc = w->sync()))
         return rc;
-    p.use_markers = use_markers != 0;
-    p.stop = nullptr;
-    if ((rc = w.host_scratch.ensure(lba_layout(nkf, np, nobs, nma, nmobs).end))) return rc;
-    if ((rc = lba_enqueue(p, w.host_scratch.p, w.stream, true)) || (rc = w.sync())) return rc;
     LbaCtl c;
     ORBFE_HIP(hipMemcpy(&c, p.ctl, sizeof(c), hipMemcpyDeviceToHost));
     if (c.abort_status < 0) return fail(c.abort_status, "%s: the device refused the problem (status %d)", name, c.abort_status);

@@ -14,6 +14,7 @@
 // The edges' "cached" errors of g2o are not stored: they are the errors at the last pose the active edges were evaluated at (Tev),
 // recomputed bit for bit when the classification reads them.  After a round that ended on rejected trials Tev is the rejected
 // trial's pose, as the reference's stale errors are.
+#include "ba_camera.hpp"
 #include "host_stage.hpp"
 #include "lm_dense.hpp"
 #include "orbfe_common.hpp"
@@ -26,7 +27,7 @@ namespace {
 
 constexpr int PO_THREADS = LM_THREADS;
 constexpr int PO_WAVES = LM_WAVES;
-constexpr int PO_MAX_LEVELS = 32;
+constexpr int PO_MAX_LEVELS = BA_MAX_LEVELS;
 constexpr int PO_NSUM = 28;   // robust chi2, H upper triangle (21), b (6)
 
 // ------------------------------------------------------------------------------------------- edges --
@@ -427,16 +428,14 @@ __global__ void k_pose_gather(const int32_t* match_cur, const int32_t* nk, int c
 // ------------------------------------------------------------------------------------------- host --
 int fill_args(PoseArgs& a, const float* inv_sigma2, int nlevels, const float* K4, float marker_info, const char* name)
 {
-    if (!K4 || !inv_sigma2 || nlevels <= 0 || nlevels > PO_MAX_LEVELS) return fail(ORBFE_ERR_INVALID, "%s: invalid K4 / sigma table", name);
-    for (int i = 0; i < 4; i++)
-        if (!std::isfinite(K4[i])) return fail(ORBFE_ERR_INVALID, "%s: K is not finite", name);
-    if (K4[0] == 0 || K4[1] == 0) return fail(ORBFE_ERR_INVALID, "%s: fx or fy is 0", name);
-    if (!std::isfinite(marker_info)) return fail(ORBFE_ERR_INVALID, "%s: marker_info is not finite", name);
-    a.nlevels = nlevels;
-    for (int l = 0; l < PO_MAX_LEVELS; l++) a.inv_sigma2[l] = l < nlevels ? inv_sigma2[l] : 0.f;
-    a.fx = K4[0]; a.fy = K4[1]; a.cx = K4[2]; a.cy = K4[3];
-    a.marker_info = marker_info;
-    a.delta = (double)(float)std::sqrt(5.991);
+    BaCamera c;
+    const BaCheck chk = ba_camera(c, K4, inv_sigma2, nlevels, marker_info, name);
+    if (chk.err) return fail(chk.err, "%s", chk.msg);
+    a.nlevels = c.nlevels;
+    for (int l = 0; l < PO_MAX_LEVELS; l++) a.inv_sigma2[l] = c.inv_sigma2[l];
+    a.fx = c.fx; a.fy = c.fy; a.cx = c.cx; a.cy = c.cy;
+    a.marker_info = c.marker_info;
+    a.delta = c.delta;
     return ORBFE_OK;
 }
 

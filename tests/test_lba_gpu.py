@@ -172,6 +172,28 @@ def test_bounds_and_invalid_input(orbfe):
         assert np.array_equal(d["x3Dw"].view(np.uint32), a["x3Dw"].view(np.uint32))
 
 
+def test_device_call_refuses_a_short_or_misaligned_scratch_before_any_launch(orbfe):
+    """one byte less than orbfe_lba_scratch_bytes asks for is ORBFE_ERR_CAPACITY, a scratch that is not 256-byte aligned is
+    ORBFE_ERR_INVALID; both are decided on the host: the record, the estimates, the erase bytes and the scratch keep their pattern"""
+    a = orbfe.lba_arrays(S.case("k3_p40_clean"))
+    nkf, n, nobs = len(a["Tcw"]), len(a["x3Dw"]), len(a["obs_kf"])
+    assert (nkf, n, len(a["Twm"])) == (3, 40, 0)
+    nbytes = orbfe.lba_scratch_bytes(nkf, n, nobs, 0, 0)
+    # the scratch has 256 bytes to spare, so that the shifted pointer with the full size still names memory of the buffer
+    out = dict(Tcw=Out(a["Tcw"]), x3Dw=Out(a["x3Dw"]), erase=Out(np.full(nobs, 7, np.uint8)), res=Out(np.full(1, -1, np.int32).repeat(9)),
+               scratch=Out(np.full(nbytes + 256, 0xA5, np.uint8)))
+    d = dict(out, **{k: Dev(a[k]) for k in ("kf_fixed", "obs_offset", "obs_kf", "obs_xy", "obs_octave")})
+    for shift, short, code in ((0, 1, "(-4)"), (128, 0, "(-1)")):
+        ptr = {k: v.ptr for k, v in d.items()}
+        ptr["scratch"] += shift
+        ptr["scratch_bytes"] = nbytes - short
+        with pytest.raises(orbfe.OrbfeError) as e:
+            orbfe.local_bundle_adjustment_device(ptr, nkf, n, nobs, 0, 0, a["K4"], a["inv_level_sigma2"], a["marker_info"], 0)
+        assert code in str(e.value)
+        for k, v in out.items():
+            assert np.array_equal(v.get().view(np.uint8), v.a.view(np.uint8)), k
+
+
 def test_special_vertices_do_not_move(orbfe):
     """the free keyframe without observations keeps its pose to the bit; the marker whose edges all went to level 1 keeps in round 2
     what round 1 left (the restatement's value, within the tolerance, is what the parity test checks); a projection through z = 0 is
