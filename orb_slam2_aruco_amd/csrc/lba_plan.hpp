@@ -13,6 +13,7 @@
 #include "../../include/orbfe.h"
 #include "ba_camera.hpp"    // BaCheck, ba_fail
 #include "host_stage.hpp"   // IoLayout
+#include "lm_rules.hpp"     // LmState
 
 namespace orbfe {
 
@@ -26,14 +27,16 @@ constexpr size_t LBA_SE3_BYTES = 64;    // sizeof(SE3) of se3_quat.hpp, a device
 constexpr size_t LBA_SOLVE_LDS = 4096;  // what k_lba_solve holds in LDS beside the reduced system, rounded up
 
 struct LbaCtl {
-    double lambda, ni, currentChi, iniChi, rho, lambda0;
-    int q, it, nbad_lm, ok2;
+    LmState lm;            // g2o's Levenberg scalars and their rules (lm_rules.hpp), as the dense optimizers run them
+    double lambda0;        // the round's initial lambda, for orbfe_lba_inspect
+    int it, ok2;
     int iter_go, trial_go, cur, round;
     int stopped, stale, abort_status, bad;
     int nfree_kf, nv, aborted, pad0;
     int iters[2], n_level1[2];
     int n_erase, stale_mask, pad1, pad2;
 };
+static_assert(sizeof(LbaCtl) == 144, "the scratch layout and tests/test_lba_plan_cpu.py pin this size");
 
 struct LbaSizes {
     int nkf, np, nobs, nma, nmobs;

@@ -1,7 +1,11 @@
-// lm_dense.hpp -- what the two g2o restatements on the device (pose_optimizer.hip: SE3Quat, 6 DoF; sim3_optimizer.hip: Sim3, 7 DoF)
-// share: Eigen's quaternion pieces, the projection error, the Huber kernel, the dense LDLT with diagonal pivoting, and the
-// fixed-order sum over a workgroup of 256.  Everything in double, as g2o runs it.
+// lm_dense.hpp -- what the two g2o restatements on the device with a dense system (pose_optimizer.hip: SE3Quat, 6 DoF;
+// sim3_optimizer.hip: Sim3, 7 DoF) share: Eigen's quaternion pieces, the projection error, the Huber kernel, and the dense
+// Levenberg-Marquardt step templated on the dimension D -- an edge's quadratic form added to the lm_nsum<D> sums (each kernel
+// unpacks them into H and b itself: the note above so_optimize in sim3_optimizer.hip), the dense LDLT with diagonal pivoting behind
+// (H + lambda I) x = b, the gain denominator -- and the fixed-order sum over a workgroup of 256.  The scalar lambda / rho / stop
+// rules are lm_rules.hpp's (local_ba.hip runs them too).  Everything in double, as g2o runs it.
 #pragma once
+#include "lm_rules.hpp"
 #include "orbfe_common.hpp"
 #include <cfloat>
 #include <cmath>
@@ -184,6 +188,45 @@ template <int N> __device__ bool ldlt_solve(double (&m)[N][N], const double (&b)
     }
     for (int i = 0; i < n; i++) x[i] = y[i];
     return true;
+}
+
+// ------------------------------------------------------------------------------------- the dense system, D = 6 or 7 --
+// what a linearisation pass sums: the robust chi2, H's upper triangle row by row, b
+template <int D> constexpr int lm_nsum = 1 + D * (D + 1) / 2 + D;
+
+// BaseUnaryEdge / BaseBinaryEdge::constructQuadraticForm for Omega = info I: H += J^T (rho' Omega) J, b += J^T rho' (-Omega e)
+template <int D>
+__device__ __forceinline__ void add_edge(const double (&err)[2], const double (&J)[2][D], double info, double rho1, double (&s)[lm_nsum<D>])
+{
+    const double w = rho1 * info;
+    const double r0 = rho1 * -(info * err[0]), r1 = rho1 * -(info * err[1]);
+    int k = 1;
+#pragma unroll
+    for (int a = 0; a < D; a++)
+#pragma unroll
+        for (int c = a; c < D; c++, k++) s[k] += J[0][a] * (w * J[0][c]) + J[1][a] * (w * J[1][c]);
+#pragma unroll
+    for (int a = 0; a < D; a++) s[1 + D * (D + 1) / 2 + a] += J[0][a] * r0 + J[1][a] * r1;
+}
+
+// (H + lambda I) x = b from the previous update x0 (which stays when the damped system is not positive); returns isPositive()
+template <int D>
+__device__ __forceinline__ bool damped_solve(const double (&H)[D][D], const double (&b)[D], double lambda, const double (&x0)[D], double (&x)[D])
+{
+    double Hl[D][D];
+    for (int r = 0; r < D; r++)
+        for (int cc = 0; cc < D; cc++) Hl[r][cc] = H[r][cc];
+    for (int j = 0; j < D; j++) Hl[j][j] += lambda;
+    for (int j = 0; j < D; j++) x[j] = x0[j];
+    return ldlt_solve(Hl, b, x);
+}
+
+// the denominator of the gain ratio, without its 1e-3 (lm_judge_trial adds it)
+template <int D> __device__ __forceinline__ double gain_scale(const double (&x)[D], const double (&b)[D], double lambda)
+{
+    double scale = 0;
+    for (int j = 0; j < D; j++) scale += x[j] * (lambda * x[j] + b[j]);
+    return scale;
 }
 
 // sum of N doubles over the workgroup: butterfly inside each wave, then the waves in order; the result is valid in thread 0

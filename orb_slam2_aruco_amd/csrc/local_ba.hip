@@ -13,7 +13,8 @@
 //   a trial        k_lba_schur_points ((Hll + lambda I)^-1), k_lba_assemble (a wave per block (i, j) of S: Hpp - sum W_i D^-1 W_j^T
 //                  over the points both see, in point order), k_lba_solve (one workgroup: L L^T of S in LDS, or in global memory when it does not fit, the two
 //                  substitutions, the trial poses), k_lba_backsub (a thread per point: the point's update, the trial point, the
-//                  trial errors and chi2), k_lba_ctl_trial (rho, accept or reject, lambda / nu, the stop rules)
+//                  trial errors and chi2), k_lba_ctl_trial (rho, accept or reject, lambda / nu, the stop rules: lm_rules.hpp's,
+//                  the ones pose_optimizer.hip and sim3_optimizer.hip run)
 //   a check        k_lba_check (a thread per edge: level 1 flags after round 1, the erase bytes after round 2)
 //   the end        k_lba_finish (poses, points, marker poses as floats; the record)
 // Sums: a thread adds its own items in their order (a point's observations; a contiguous run of points), a wave adds its lanes by a
@@ -288,10 +289,7 @@ __global__ void k_lba_begin(LbaP p, int round)
     c.round = round;
     c.it = 0;
     c.trial_go = 0;
-    c.lambda = 0;
-    c.ni = 2;
-    c.nbad_lm = 0;
-    c.rho = 0;
+    lm_round_start(c.lm);
     c.stale = 0;
 }
 
@@ -467,17 +465,13 @@ __global__ __launch_bounds__(LM_THREADS) void k_lba_ctl_lin(LbaP p)
     mx[threadIdx.x] = m;
     block_sum<1>(s, red);
     if (threadIdx.x != 0) return;
-    c.currentChi = c.iniChi = s[0];
+    double md = 0;
     if (c.it == 0) {
-        double md = 0;
         for (int i = 0; i < LM_THREADS; i++) md = fmax(md, mx[i]);
         for (int v = 0; v < c.nv; v++) md = fmax(md, p.vmax[v]);
-        c.lambda = c.lambda0 = 1e-5 * md;
-        c.ni = 2;
-        c.nbad_lm = 0;
     }
-    c.rho = 0;
-    c.q = 0;
+    lm_linearised(c.lm, s[0], c.it == 0, md);
+    if (c.it == 0) c.lambda0 = c.lm.lambda;
     c.trial_go = 1;
 }
 
@@ -490,7 +484,7 @@ __global__ __launch_bounds__(LBA_PT) void k_lba_schur_points(LbaP p)
     const int pi = blockIdx.x * LBA_PT + threadIdx.x;
     if (pi >= p.np || !p.p_active[pi]) return;
     const double* H = p.Hll + (size_t)pi * 6;
-    const double m00 = H[0] + c.lambda, m01 = H[1], m02 = H[2], m11 = H[3] + c.lambda, m12 = H[4], m22 = H[5] + c.lambda;
+    const double m00 = H[0] + c.lm.lambda, m01 = H[1], m02 = H[2], m11 = H[3] + c.lm.lambda, m12 = H[4], m22 = H[5] + c.lm.lambda;
     const double c00 = m11 * m22 - m12 * m12, c10 = m12 * m02 - m01 * m22, c20 = m01 * m12 - m11 * m02;
     const double det = c00 * m00 + c10 * m01 + c20 * m02, id = 1. / det;
     double* D = p.Dinv + (size_t)pi * 9;
@@ -541,7 +535,7 @@ __global__ __launch_bounds__(64) void k_lba_assemble(LbaP p)
             for (int a = 0; a < 6; a++) B[a * 6 + a] = 1;
     } else if (i == j) {
         for (int k = 0; k < 36; k++) B[k] = p.Hpp[(size_t)i * 36 + k];
-        for (int a = 0; a < 6; a++) B[a * 6 + a] += c.lambda;
+        for (int a = 0; a < 6; a++) B[a * 6 + a] += c.lm.lambda;
         for (int k = 0; k < 36; k++) B[k] -= acc[k];
     } else if (kj < p.nkf) {
         for (int k = 0; k < 36; k++) B[k] = 0. - acc[k];
@@ -673,7 +667,7 @@ __global__ __launch_bounds__(LBA_PT) void k_lba_backsub(LbaP p)
                     for (int a = 0; a < 3; a++) xl[a] = D[a * 3] * r[0] + D[a * 3 + 1] * r[1] + D[a * 3 + 2] * r[2];
                 }
                 for (int a = 0; a < 3; a++) {
-                    scale += xl[a] * (c.lambda * xl[a] + bl[a]);
+                    scale += xl[a] * (c.lm.lambda * xl[a] + bl[a]);
                     X[a] += xl[a];
                 }
                 for (int e = lo; e < hi; e++) {
@@ -721,43 +715,23 @@ __global__ __launch_bounds__(LM_THREADS) void k_lba_ctl_trial(LbaP p, int maxit)
     double s[2] = {part_sum(p.chi_part, p.nb), part_sum(p.scale_part, p.nb)};
     block_sum<2>(s, red);
     if (threadIdx.x != 0) return;
-    double tempChi = s[0];
-    if (!c.ok2) tempChi = DBL_MAX;
     double scale = 0;
-    for (int j = 0; j < 6 * c.nv; j++) scale += p.xv[j] * (c.lambda * p.xv[j] + (p.v_active[j / 6] ? p.bp[j] : 0.));
+    for (int j = 0; j < 6 * c.nv; j++) scale += p.xv[j] * (c.lm.lambda * p.xv[j] + (p.v_active[j / 6] ? p.bp[j] : 0.));
     scale += s[1];
-    scale += 1e-3;
-    double rho = (c.currentChi - tempChi);
-    rho /= scale;
-    if (rho > 0 && isfinite(tempChi)) {
-        double alpha = 1. - pow((2 * rho - 1), 3.0);
-        alpha = fmin(alpha, 2. / 3.);
-        const double sf = fmax(1. / 3., alpha);
-        c.lambda *= sf;
-        c.ni = 2;
-        c.currentChi = tempChi;
+    if (lm_judge_trial(c.lm, s[0], c.ok2 != 0, scale)) {
         c.cur = 1 - c.cur;
         c.stale = 0;
     } else {
-        c.lambda *= c.ni;
-        c.ni *= 2;
         c.stale = 1;
     }
-    c.rho = rho;
-    c.q++;
     const bool halt = stop_set(p);
-    const bool cont = rho < 0 && c.q < 10 && !halt;
+    const bool cont = lm_try_again(c.lm) && !halt;
     c.trial_go = cont;
     if (cont) return;
     c.it++;
     c.iters[c.round] = c.it;
     c.stale_mask = (c.stale_mask & ~(1 << c.round)) | (c.stale << c.round);
-    bool stop = c.q == 10 || rho == 0;
-    if (!stop) {
-        if ((c.iniChi - c.currentChi) * 1e3 < c.iniChi) c.nbad_lm++;
-        else c.nbad_lm = 0;
-        stop = c.nbad_lm >= 3;
-    }
+    const bool stop = lm_iteration_end(c.lm);
     if (halt) c.stopped = 1;
     c.iter_go = !stop && !halt && c.it < maxit;
 }
@@ -1007,7 +981,7 @@ extern "C" int orbfe_lba_inspect(const float* Tcw, const uint8_t* kf_fixed, int 
     ORBFE_HIP(hipMemcpy(&c, p.ctl, sizeof(c), hipMemcpyDeviceToHost));
     if (c.abort_status < 0) return fail(c.abort_status, "%s: the device refused the problem (status %d)", name, c.abort_status);
     *nv = c.nv;
-    chi2[0] = c.currentChi;
+    chi2[0] = c.lm.currentChi;
     chi2[1] = c.lambda0;
     if (c.nv) {
         ORBFE_HIP(hipMemcpy(b, p.bp, (size_t)c.nv * 48, hipMemcpyDeviceToHost));

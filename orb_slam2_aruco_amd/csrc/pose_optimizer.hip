@@ -9,7 +9,8 @@
 //     and sums the robust chi2, the 21 entries of H's upper triangle and b in registers; the 28 sums go through a fixed-order
 //     butterfly inside each wave and the four wave results are added in wave order by thread 0.  The order depends only on the
 //     problem, never on the batch it sits in;
-//   - thread 0 then does the 6 x 6 LDLT (diagonal pivoting), the exponential map and the lambda logic;
+//   - thread 0 then does the 6 x 6 LDLT (diagonal pivoting), the exponential map and the lambda logic: the dense step is
+//     lm_dense.hpp's, shared with sim3_optimizer.hip, the scalar rules are lm_rules.hpp's, shared with local_ba.hip too;
 //   - a trial pass per LM trial sums the robust chi2 at the trial pose, in the same order.
 // The edges' "cached" errors of g2o are not stored: they are the errors at the last pose the active edges were evaluated at (Tev),
 // recomputed bit for bit when the classification reads them.  After a round that ended on rejected trials Tev is the rejected
@@ -25,10 +26,7 @@
 namespace orbfe {
 namespace {
 
-constexpr int PO_THREADS = LM_THREADS;
-constexpr int PO_WAVES = LM_WAVES;
-constexpr int PO_MAX_LEVELS = BA_MAX_LEVELS;
-constexpr int PO_NSUM = 28;   // robust chi2, H upper triangle (21), b (6)
+constexpr int PO_NSUM = lm_nsum<6>;   // 28: robust chi2, H upper triangle (21), b (6)
 
 // ------------------------------------------------------------------------------------------- edges --
 // EdgeSE3ProjectXYZOnlyPose::linearizeOplus at the camera point Xc = T Xw
@@ -74,17 +72,6 @@ __device__ void marker_jacobian(const SE3& T, const SE3& Twm, const double (&p)[
     }
 }
 
-// BaseUnaryEdge / BaseBinaryEdge::constructQuadraticForm for Omega = info I: H += J^T (rho' Omega) J, b += J^T rho' (-Omega e)
-__device__ __forceinline__ void add_edge(const double (&err)[2], const double (&J)[2][6], double info, double rho1, double (&s)[PO_NSUM])
-{
-    const double w = rho1 * info;
-    const double r0 = rho1 * -(info * err[0]), r1 = rho1 * -(info * err[1]);
-    int k = 1;
-    for (int a = 0; a < 6; a++)
-        for (int c = a; c < 6; c++, k++) s[k] += J[0][a] * (w * J[0][c]) + J[1][a] * (w * J[1][c]);
-    for (int a = 0; a < 6; a++) s[22 + a] += J[0][a] * r0 + J[1][a] * r1;
-}
-
 // ------------------------------------------------------------------------------------------ the kernel --
 struct PoseArgs {
     const orbfe_keypoint* kps;
@@ -101,19 +88,19 @@ struct PoseArgs {
     int capacity, mcapacity, nlevels;
     float fx, fy, cx, cy, marker_info;
     double delta;                       // (double)(float)sqrt(5.991), as deltaMono reaches RobustKernelHuber::setDelta
-    float inv_sigma2[PO_MAX_LEVELS];
+    float inv_sigma2[BA_MAX_LEVELS];
 };
 
 // thread 0's state, in LDS
 struct Ctl {
     SE3 T, T0, Tev, Tsave;
     double H[6][6], b[6], x[6];
-    double lambda, ni, currentChi, iniChi, rho;
-    int q, it, nbad_lm, ok2;
-    int cont, stop, nin, pad;
+    LmState lm;
+    int ok2, cont, stop, nin, pad[2];
 };
+static_assert(sizeof(Ctl) == 712, "PO_FIXED and the capacity limits behind it hang on this size");
 
-constexpr size_t PO_FIXED = al16(sizeof(Ctl)) + al16(sizeof(double) * PO_WAVES * PO_NSUM);
+constexpr size_t PO_FIXED = al16(sizeof(Ctl)) + al16(sizeof(double) * LM_WAVES * PO_NSUM);
 
 size_t lds_bytes(int capacity, int mcapacity)
 {
@@ -121,7 +108,7 @@ size_t lds_bytes(int capacity, int mcapacity)
     return PO_FIXED + al16(cap * 8) + al16(cap * 16) + al16(cap) + al16(mc * sizeof(SE3)) + al16(mc * 4 * 8) + al16(mc * 4 * 16);
 }
 
-__global__ __launch_bounds__(PO_THREADS) void k_pose_opt(PoseArgs a)
+__global__ __launch_bounds__(LM_THREADS) void k_pose_opt(PoseArgs a)
 {
     extern __shared__ __align__(16) unsigned char po_smem[];
     const int f = blockIdx.x, tid = threadIdx.x;
@@ -148,7 +135,7 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(PoseArgs a)
 
     // stage the problem
     int cnt = 0, badoct = 0;
-    for (int i = tid; i < n; i += PO_THREADS) {
+    for (int i = tid; i < n; i += LM_THREADS) {
         const orbfe_keypoint kp = a.kps[base + i];
         const bool h = a.has_mp[base + i] != 0;
         const bool okoct = kp.octave >= 0 && kp.octave < a.nlevels;
@@ -159,15 +146,15 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(PoseArgs a)
         s_xw[i] = h ? make_float4(X[0], X[1], X[2], okoct ? a.inv_sigma2[kp.octave] : 0.f) : make_float4(0.f, 0.f, 0.f, 0.f);
         s_st[i] = h ? 1 : 0;
     }
-    for (int j = tid; j < 4 * nm; j += PO_THREADS) {
+    for (int j = tid; j < 4 * nm; j += LM_THREADS) {
         const orbfe_pose_marker& mk = a.markers[(size_t)f * mcap + j / 4];
         const int k = j & 3;
         s_cobs[j] = make_float2(mk.corners[2 * k], mk.corners[2 * k + 1]);
         s_cpt[j] = make_float4(mk.local[3 * k], mk.local[3 * k + 1], mk.local[3 * k + 2], 0.f);
     }
-    for (int m = tid; m < nm; m += PO_THREADS) s_twm[m] = se3_from_float(a.markers[(size_t)f * mcap + m].Twm);
+    for (int m = tid; m < nm; m += LM_THREADS) s_twm[m] = se3_from_float(a.markers[(size_t)f * mcap + m].Twm);
     const int n_initial = block_count(cnt, red);
-    const int nbadoct = block_count(badoct, red + PO_WAVES);
+    const int nbadoct = block_count(badoct, red + LM_WAVES);
     if (tid == 0) {
         c.nin = n_initial;
         c.stop = nbadoct;
@@ -185,7 +172,7 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(PoseArgs a)
         return;
     }
     if (n0 < 3) {
-        for (int i = tid; i < n; i += PO_THREADS)
+        for (int i = tid; i < n; i += LM_THREADS)
             if (s_st[i]) a.outlier[base + i] = 0;
         if (tid == 0) {
             orbfe_pose_result r{};
@@ -204,10 +191,7 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(PoseArgs a)
         const bool mono_kernel = round < 3;
         if (tid == 0) {
             c.T = c.T0;
-            c.lambda = 0;
-            c.ni = 2;
-            c.nbad_lm = 0;
-            c.rho = 0;
+            lm_round_start(c.lm);
             for (int j = 0; j < 6; j++) c.x[j] = 0;
         }
         __syncthreads();
@@ -220,7 +204,7 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(PoseArgs a)
                     const SE3 T = c.T;
                     double s[PO_NSUM];
                     for (int k = 0; k < PO_NSUM; k++) s[k] = 0;
-                    for (int i = tid; i < n; i += PO_THREADS) {
+                    for (int i = tid; i < n; i += LM_THREADS) {
                         if (s_st[i] != 1) continue;
                         const float2 o = s_obs[i];
                         const float4 xw = s_xw[i];
@@ -238,7 +222,7 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(PoseArgs a)
                         }
                         add_edge(err, J, xw.w, rho[1], s);
                     }
-                    for (int j = tid; j < 4 * nm; j += PO_THREADS) {
+                    for (int j = tid; j < 4 * nm; j += LM_THREADS) {
                         const float2 o = s_cobs[j];
                         const float4 pt = s_cpt[j];
                         const double pm[3] = {pt.x, pt.y, pt.z};
@@ -253,39 +237,30 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(PoseArgs a)
                     block_sum<PO_NSUM>(s, red);
                     if (tid == 0) {
                         c.Tev = c.T;
-                        c.currentChi = c.iniChi = s[0];
+                        // the sums as H and b, here and not in a function of lm_dense.hpp: see the note above so_optimize (sim3_optimizer.hip)
                         int k = 1;
                         for (int r = 0; r < 6; r++)
                             for (int cc = r; cc < 6; cc++, k++) c.H[r][cc] = c.H[cc][r] = s[k];
                         for (int r = 0; r < 6; r++) c.b[r] = s[22 + r];
-                        if (it == 0) {
-                            double md = 0;
+                        double md = 0;
+                        if (it == 0)
                             for (int j = 0; j < 6; j++) md = fmax(fabs(c.H[j][j]), md);
-                            c.lambda = 1e-5 * md;
-                            c.ni = 2;
-                            c.nbad_lm = 0;
-                        }
-                        c.rho = 0;
-                        c.q = 0;
+                        lm_linearised(c.lm, s[0], it == 0, md);
                     }
                 }
                 // trials
                 for (;;) {
                     if (tid == 0) {
                         c.Tsave = c.T;
-                        double Hl[6][6], x[6];
-                        for (int r = 0; r < 6; r++)
-                            for (int cc = 0; cc < 6; cc++) Hl[r][cc] = c.H[r][cc];
-                        for (int j = 0; j < 6; j++) Hl[j][j] += c.lambda;
-                        for (int j = 0; j < 6; j++) x[j] = c.x[j];
-                        c.ok2 = ldlt_solve(Hl, c.b, x) ? 1 : 0;
+                        double x[6];
+                        c.ok2 = damped_solve(c.H, c.b, c.lm.lambda, c.x, x) ? 1 : 0;
                         for (int j = 0; j < 6; j++) c.x[j] = x[j];
                         c.T = mul(se3_exp(x), c.T);
                     }
                     __syncthreads();
                     const SE3 T = c.T;
                     double s[1] = {0};
-                    for (int i = tid; i < n; i += PO_THREADS) {
+                    for (int i = tid; i < n; i += LM_THREADS) {
                         if (s_st[i] != 1) continue;
                         const float2 o = s_obs[i];
                         const float4 xw = s_xw[i];
@@ -301,7 +276,7 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(PoseArgs a)
                             s[0] += ch;
                         }
                     }
-                    for (int j = tid; j < 4 * nm; j += PO_THREADS) {
+                    for (int j = tid; j < 4 * nm; j += LM_THREADS) {
                         const float2 o = s_cobs[j];
                         const float4 pt = s_cpt[j];
                         const double pm[3] = {pt.x, pt.y, pt.z};
@@ -313,44 +288,19 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(PoseArgs a)
                     block_sum<1>(s, red);
                     if (tid == 0) {
                         c.Tev = c.T;
-                        double tempChi = s[0];
-                        if (!c.ok2) tempChi = DBL_MAX;
-                        double rho = c.currentChi - tempChi;
-                        double scale = 0;
-                        for (int j = 0; j < 6; j++) scale += c.x[j] * (c.lambda * c.x[j] + c.b[j]);
-                        scale += 1e-3;
-                        rho /= scale;
-                        if (rho > 0 && isfinite(tempChi)) {
-                            double alpha = 1. - pow((2 * rho - 1), 3.0);
-                            alpha = fmin(alpha, 2. / 3.);
-                            const double sf = fmax(1. / 3., alpha);
-                            c.lambda *= sf;
-                            c.ni = 2;
-                            c.currentChi = tempChi;
+                        if (lm_judge_trial(c.lm, s[0], c.ok2 != 0, gain_scale(c.x, c.b, c.lm.lambda))) {
                             c.ok2 = 2;   // accepted
                         } else {
-                            c.lambda *= c.ni;
-                            c.ni *= 2;
                             c.T = c.Tsave;
                             c.ok2 = 3;   // rejected
                         }
-                        c.rho = rho;
-                        c.q++;
-                        c.cont = rho < 0 && c.q < 10;
+                        c.cont = lm_try_again(c.lm);
                     }
                     __syncthreads();
                     if (!c.cont) break;
                 }
                 it++;
-                if (tid == 0) {
-                    bool stop = c.q == 10 || c.rho == 0;
-                    if (!stop) {
-                        if ((c.iniChi - c.currentChi) * 1e3 < c.iniChi) c.nbad_lm++;
-                        else c.nbad_lm = 0;
-                        stop = c.nbad_lm >= 3;
-                    }
-                    c.stop = stop;
-                }
+                if (tid == 0) c.stop = lm_iteration_end(c.lm);
                 __syncthreads();
                 round_iters = it;
                 round_stale = c.ok2 == 3;
@@ -361,7 +311,7 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(PoseArgs a)
         {
             const SE3 T = c.T, Tev = c.Tev;
             int nb = 0;
-            for (int i = tid; i < n; i += PO_THREADS) {
+            for (int i = tid; i < n; i += LM_THREADS) {
                 const uint8_t st = s_st[i];
                 if (!(st & 1)) continue;
                 const float2 o = s_obs[i];
@@ -386,7 +336,7 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(PoseArgs a)
         __syncthreads();
         if (nedges < 10) break;
     }
-    for (int i = tid; i < n; i += PO_THREADS)
+    for (int i = tid; i < n; i += LM_THREADS)
         if (s_st[i] & 1) a.outlier[base + i] = (s_st[i] & 2) ? 1 : 0;
     if (tid == 0) {
         orbfe_pose_result r{};
@@ -432,7 +382,7 @@ int fill_args(PoseArgs& a, const float* inv_sigma2, int nlevels, const float* K4
     const BaCheck chk = ba_camera(c, K4, inv_sigma2, nlevels, marker_info, name);
     if (chk.err) return fail(chk.err, "%s", chk.msg);
     a.nlevels = c.nlevels;
-    for (int l = 0; l < PO_MAX_LEVELS; l++) a.inv_sigma2[l] = c.inv_sigma2[l];
+    for (int l = 0; l < BA_MAX_LEVELS; l++) a.inv_sigma2[l] = c.inv_sigma2[l];
     a.fx = c.fx; a.fy = c.fy; a.cx = c.cx; a.cy = c.cy;
     a.marker_info = c.marker_info;
     a.delta = c.delta;
@@ -446,7 +396,7 @@ int launch(const PoseArgs& a, int nframes, hipStream_t s, const char* name)
         return fail(ORBFE_ERR_CAPACITY, "%s: capacity %d / mcapacity %d need %zu B of LDS (at most %d)", name, a.capacity, a.mcapacity, lds, max_lds());
     int rc = ensure_dyn_lds((const void*)k_pose_opt, lds);
     if (rc) return rc;
-    hipLaunchKernelGGL(k_pose_opt, dim3(nframes), dim3(PO_THREADS), lds, s, a);
+    hipLaunchKernelGGL(k_pose_opt, dim3(nframes), dim3(LM_THREADS), lds, s, a);
     ORBFE_HIP(hipGetLastError());
     return ORBFE_OK;
 }

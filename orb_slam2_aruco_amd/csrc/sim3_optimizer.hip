@@ -9,7 +9,8 @@
 //     central-difference Jacobian (14 map-and-project evaluations an edge) -- and sums the robust chi2, the 28 entries of H's upper
 //     triangle and b in registers; the 36 sums go through a fixed-order butterfly inside each wave and the four wave results are
 //     added in wave order by thread 0.  The order depends only on the problem, never on the batch it sits in;
-//   - thread 0 does the 7 x 7 LDLT (diagonal pivoting), Sim3(update) * S and the lambda logic;
+//   - thread 0 does the 7 x 7 LDLT (diagonal pivoting), Sim3(update) * S and the lambda logic: the dense step is lm_dense.hpp's,
+//     shared with pose_optimizer.hip, the scalar rules are lm_rules.hpp's, shared with local_ba.hip too;
 //   - a trial pass per LM trial sums the robust chi2 at the trial estimate, in the same order.
 // The perturbed estimates are functions of the vertex alone: g2o recomputes them for every edge and gets these bits.
 // The edges' "cached" errors are not stored: they are the errors at the last estimate the active edges were evaluated at (Sev),
@@ -31,7 +32,7 @@ namespace orbfe {
 namespace {
 
 constexpr int SO_MAX_LEVELS = 32;
-constexpr int SO_NSUM = 36;   // robust chi2, H upper triangle (28), b (7)
+constexpr int SO_NSUM = lm_nsum<7>;   // 36: robust chi2, H upper triangle (28), b (7)
 constexpr int SO_SIM_FLOATS = 13;   // s12, R12 row-major, t12
 
 // ------------------------------------------------------------------------------------------ g2o::Sim3 --
@@ -151,20 +152,6 @@ __device__ __forceinline__ bool edge_jacobian(const Sim3* sp, const double (&P)[
     return ok;
 }
 
-// BaseBinaryEdge::constructQuadraticForm for Omega = info I: H += J^T (rho' Omega) J, b += J^T rho' (-Omega e)
-__device__ __forceinline__ void add_edge(const double (&err)[2], const double (&J)[2][7], double info, double rho1, double (&s)[SO_NSUM])
-{
-    const double w = rho1 * info;
-    const double r0 = rho1 * -(info * err[0]), r1 = rho1 * -(info * err[1]);
-    int k = 1;
-#pragma unroll
-    for (int a = 0; a < 7; a++)
-#pragma unroll
-        for (int c = a; c < 7; c++, k++) s[k] += J[0][a] * (w * J[0][c]) + J[1][a] * (w * J[1][c]);
-#pragma unroll
-    for (int a = 0; a < 7; a++) s[29 + a] += J[0][a] * r0 + J[1][a] * r1;
-}
-
 // ------------------------------------------------------------------------------------------ the kernel --
 struct SimOptArgs {
     // per-frame blocks of `capacity` (x3Dw: x 3; Tcw: 12 floats a frame)
@@ -190,11 +177,12 @@ struct SimOptArgs {
 struct SoCtl {
     Sim3 S, S0, Sev, Ssave;
     double H[7][7], b[7], x[7];
-    double lambda, ni, currentChi, iniChi, rho;
-    int q, nbad_lm, ok2, cont, stop, nact, base, bad;
+    LmState lm;
+    int ok2, cont, stop, nact, base, bad;
     int cnt[LM_WAVES];
     float Tcw[24];
 };
+static_assert(sizeof(SoCtl) == 944, "SO_FIXED and the capacity limit behind it hang on this size");
 
 struct SoLds {
     SoCtl* c;
@@ -218,6 +206,10 @@ size_t lds_bytes(int capacity)
 // function at the limit of the register file (256 VGPR + 120 AGPR, 153 SGPR spills), and that build gave wrong reduction results on
 // the MI355X: thread 0 read slots of `red` that held an earlier pass's sums.  The cause was not found in its
 // assembly; the out-of-line build passes every test.  Do not force these inline without rerunning them.
+// The same symptom came back, here and in k_pose_opt, when the unpacking of the linearisation's sums into H and b was moved into a
+// forceinline template of lm_dense.hpp (same operations, same barriers, same register and scratch figures for this kernel): stale
+// slots of `red` in the counts and sums that followed.  With the unpacking written in the kernels, as below, both give the bits they
+// always gave.  So that loop stays in each kernel, and any change to thread 0's code behind block_sum wants the GPU tests rerun.
 //
 // SparseOptimizer::optimize(iterations) with OptimizationAlgorithmLevenberg over the pairs that are not removed.  Returns the
 // iterations run (-1 without an active edge); c.ok2 == 3 afterwards: the last trial was rejected.  Called by the whole workgroup.
@@ -231,10 +223,7 @@ __device__ __noinline__ int so_optimize(const SoLds& L, const SimOptArgs& a, int
     cnt = block_count(cnt, L.red);
     if (tid == 0) {
         c.nact = cnt;
-        c.lambda = 0;
-        c.ni = 2;
-        c.nbad_lm = 0;
-        c.rho = 0;
+        lm_round_start(c.lm);
         c.ok2 = 0;
         for (int j = 0; j < 7; j++) c.x[j] = 0;
     }
@@ -284,32 +273,22 @@ __device__ __noinline__ int so_optimize(const SoLds& L, const SimOptArgs& a, int
             block_sum<SO_NSUM>(s, L.red);
             if (tid == 0) {
                 c.Sev = c.S;
-                c.currentChi = c.iniChi = s[0];
                 int k = 1;
                 for (int r = 0; r < 7; r++)
                     for (int cc = r; cc < 7; cc++, k++) c.H[r][cc] = c.H[cc][r] = s[k];
                 for (int r = 0; r < 7; r++) c.b[r] = s[29 + r];
-                if (it == 0) {
-                    double md = 0;
+                double md = 0;
+                if (it == 0)
                     for (int j = 0; j < 7; j++) md = fmax(fabs(c.H[j][j]), md);
-                    c.lambda = 1e-5 * md;
-                    c.ni = 2;
-                    c.nbad_lm = 0;
-                }
-                c.rho = 0;
-                c.q = 0;
+                lm_linearised(c.lm, s[0], it == 0, md);
             }
         }
         // trials
         for (;;) {
             if (tid == 0) {
                 c.Ssave = c.S;
-                double Hl[7][7], x[7];
-                for (int r = 0; r < 7; r++)
-                    for (int cc = 0; cc < 7; cc++) Hl[r][cc] = c.H[r][cc];
-                for (int j = 0; j < 7; j++) Hl[j][j] += c.lambda;
-                for (int j = 0; j < 7; j++) x[j] = c.x[j];
-                c.ok2 = ldlt_solve(Hl, c.b, x) ? 1 : 0;
+                double x[7];
+                c.ok2 = damped_solve(c.H, c.b, c.lm.lambda, c.x, x) ? 1 : 0;
                 if (a.fix_scale) x[6] = 0;   // oplusImpl zeroes it in the solver's own vector
                 for (int j = 0; j < 7; j++) c.x[j] = x[j];
                 c.S = mul(sim3_exp(x), c.S);
@@ -336,44 +315,19 @@ __device__ __noinline__ int so_optimize(const SoLds& L, const SimOptArgs& a, int
             block_sum<1>(s, L.red);
             if (tid == 0) {
                 c.Sev = c.S;
-                double tempChi = s[0];
-                if (!c.ok2) tempChi = DBL_MAX;
-                double rho = c.currentChi - tempChi;
-                double scale = 0;
-                for (int j = 0; j < 7; j++) scale += c.x[j] * (c.lambda * c.x[j] + c.b[j]);
-                scale += 1e-3;
-                rho /= scale;
-                if (rho > 0 && isfinite(tempChi)) {
-                    double alpha = 1. - pow((2 * rho - 1), 3.0);
-                    alpha = fmin(alpha, 2. / 3.);
-                    const double sf = fmax(1. / 3., alpha);
-                    c.lambda *= sf;
-                    c.ni = 2;
-                    c.currentChi = tempChi;
+                if (lm_judge_trial(c.lm, s[0], c.ok2 != 0, gain_scale(c.x, c.b, c.lm.lambda))) {
                     c.ok2 = 2;   // accepted
                 } else {
-                    c.lambda *= c.ni;
-                    c.ni *= 2;
                     c.S = c.Ssave;
                     c.ok2 = 3;   // rejected
                 }
-                c.rho = rho;
-                c.q++;
-                c.cont = rho < 0 && c.q < 10;
+                c.cont = lm_try_again(c.lm);
             }
             __syncthreads();
             if (!c.cont) break;
         }
         it++;
-        if (tid == 0) {
-            bool stop = c.q == 10 || c.rho == 0;
-            if (!stop) {
-                if ((c.iniChi - c.currentChi) * 1e3 < c.iniChi) c.nbad_lm++;
-                else c.nbad_lm = 0;
-                stop = c.nbad_lm >= 3;
-            }
-            c.stop = stop;
-        }
+        if (tid == 0) c.stop = lm_iteration_end(c.lm);
         __syncthreads();
         if (c.stop) break;
     }

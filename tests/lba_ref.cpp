@@ -1,6 +1,7 @@
 // lba_ref.cpp -- CPU restatement of ORB_SLAM2's Optimizer::LocalBundleAdjustment (src/Optimizer.cc:892-1242 of the reference, behind
 // its collect step, with this fork's marker poses as free SE3 vertices) for the parity tests of orbfe_local_bundle_adjustment*.
-// No g2o or Eigen here; the pieces are restated from their algorithms, SE3Quat / Huber as in tests/pose_opt_ref.cpp:
+// No g2o or Eigen here; the pieces are restated from their algorithms, SE3Quat, the Huber kernel and the Levenberg-Marquardt rules in
+// tests/g2o_ref.hpp (shared by the three restatements):
 //   EdgeSE3ProjectXYZ        e = obs - pi(T Xw), Omega = invSigma2 I, g2o's analytic Jacobians for the point and the pose
 //   EdgeMarker               e = obs - pi((Tcw Twm) p), Omega = w I, numeric Jacobians on both vertices: central differences,
 //                            delta = 1e-9, through exp(+-delta e_d) * estimate; none for a fixed keyframe
@@ -24,6 +25,8 @@
 #include <cstring>
 #include <vector>
 
+#include "g2o_ref.hpp"
+
 namespace {
 
 struct Result {     // the layout of orbfe_lba_result
@@ -35,183 +38,6 @@ struct Result {     // the layout of orbfe_lba_result
     int32_t status;
 };
 
-// ------------------------------------------------------------------------------------------ SE3Quat --
-struct Quat {
-    double x, y, z, w;
-};
-struct SE3 {
-    Quat q;
-    double t[3];
-};
-
-void normalize_rotation(Quat& q)
-{
-    if (q.w < 0) {
-        q.x *= -1; q.y *= -1; q.z *= -1; q.w *= -1;
-    }
-    const double n2 = q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w;
-    if (n2 > 0) {
-        const double n = std::sqrt(n2);
-        q.x /= n; q.y /= n; q.z /= n; q.w /= n;
-    }
-}
-
-Quat quat_from_matrix(const double m[3][3])
-{
-    Quat q;
-    double* v[3] = {&q.x, &q.y, &q.z};
-    double t = m[0][0] + m[1][1] + m[2][2];
-    if (t > 0) {
-        t = std::sqrt(t + 1.0);
-        q.w = 0.5 * t;
-        t = 0.5 / t;
-        q.x = (m[2][1] - m[1][2]) * t;
-        q.y = (m[0][2] - m[2][0]) * t;
-        q.z = (m[1][0] - m[0][1]) * t;
-    } else {
-        int i = 0;
-        if (m[1][1] > m[0][0]) i = 1;
-        if (m[2][2] > m[i][i]) i = 2;
-        const int j = (i + 1) % 3, k = (j + 1) % 3;
-        t = std::sqrt(m[i][i] - m[j][j] - m[k][k] + 1.0);
-        *v[i] = 0.5 * t;
-        t = 0.5 / t;
-        q.w = (m[k][j] - m[j][k]) * t;
-        *v[j] = (m[j][i] + m[i][j]) * t;
-        *v[k] = (m[k][i] + m[i][k]) * t;
-    }
-    return q;
-}
-
-void cross(const double a[3], const double b[3], double r[3])
-{
-    r[0] = a[1] * b[2] - a[2] * b[1];
-    r[1] = a[2] * b[0] - a[0] * b[2];
-    r[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-// q v: v + w uv + qv x uv, uv = 2 (qv x v)
-void rotate(const Quat& q, const double v[3], double r[3])
-{
-    const double qv[3] = {q.x, q.y, q.z};
-    double uv[3], c[3];
-    cross(qv, v, uv);
-    for (int i = 0; i < 3; i++) uv[i] += uv[i];
-    cross(qv, uv, c);
-    for (int i = 0; i < 3; i++) r[i] = v[i] + q.w * uv[i] + c[i];
-}
-
-Quat qmul(const Quat& a, const Quat& b)
-{
-    Quat r;
-    r.w = a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z;
-    r.x = a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y;
-    r.y = a.w * b.y + a.y * b.w + a.z * b.x - a.x * b.z;
-    r.z = a.w * b.z + a.z * b.w + a.x * b.y - a.y * b.x;
-    return r;
-}
-
-SE3 mul(const SE3& a, const SE3& b)
-{
-    SE3 r = a;
-    double qt[3];
-    rotate(a.q, b.t, qt);
-    for (int i = 0; i < 3; i++) r.t[i] += qt[i];
-    r.q = qmul(a.q, b.q);
-    normalize_rotation(r.q);
-    return r;
-}
-
-void map(const SE3& T, const double p[3], double r[3])
-{
-    rotate(T.q, p, r);
-    for (int i = 0; i < 3; i++) r[i] += T.t[i];
-}
-
-SE3 se3_from_Rt(const double R[3][3], const double t[3])
-{
-    SE3 T;
-    T.q = quat_from_matrix(R);
-    for (int i = 0; i < 3; i++) T.t[i] = t[i];
-    normalize_rotation(T.q);
-    return T;
-}
-
-SE3 se3_from_float(const float* Rt)
-{
-    double R[3][3], t[3];
-    for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) R[r][c] = Rt[r * 4 + c];
-        t[r] = Rt[r * 4 + 3];
-    }
-    return se3_from_Rt(R, t);
-}
-
-void mat3mul(const double a[3][3], const double b[3][3], double r[3][3])
-{
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) r[i][j] = a[i][0] * b[0][j] + a[i][1] * b[1][j] + a[i][2] * b[2][j];
-}
-
-SE3 se3_exp(const double u[6])
-{
-    const double om[3] = {u[0], u[1], u[2]}, up[3] = {u[3], u[4], u[5]};
-    const double theta = std::sqrt(om[0] * om[0] + om[1] * om[1] + om[2] * om[2]);
-    const double O[3][3] = {{0, -om[2], om[1]}, {om[2], 0, -om[0]}, {-om[1], om[0], 0}};
-    double O2[3][3], R[3][3], V[3][3];
-    mat3mul(O, O, O2);
-    if (theta < 0.00001) {
-        for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 3; j++) R[i][j] = ((i == j ? 1.0 : 0.0) + O[i][j]) + O2[i][j];
-        std::memcpy(V, R, sizeof(R));
-    } else {
-        const double a = std::sin(theta) / theta, b = (1 - std::cos(theta)) / (theta * theta);
-        const double c = (theta - std::sin(theta)) / std::pow(theta, 3);
-        for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 3; j++) {
-                R[i][j] = ((i == j ? 1.0 : 0.0) + a * O[i][j]) + b * O2[i][j];
-                V[i][j] = ((i == j ? 1.0 : 0.0) + b * O[i][j]) + c * O2[i][j];
-            }
-    }
-    double t[3];
-    for (int i = 0; i < 3; i++) t[i] = V[i][0] * up[0] + V[i][1] * up[1] + V[i][2] * up[2];
-    return se3_from_Rt(R, t);
-}
-
-void to_float(const SE3& T, float* Rt)
-{
-    const Quat& q = T.q;
-    const double tx = 2 * q.x, ty = 2 * q.y, tz = 2 * q.z;
-    const double twx = tx * q.w, twy = ty * q.w, twz = tz * q.w;
-    const double txx = tx * q.x, txy = ty * q.x, txz = tz * q.x;
-    const double tyy = ty * q.y, tyz = tz * q.y, tzz = tz * q.z;
-    const double R[9] = {1 - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1 - (txx + tzz), tyz - twx, txz - twy, tyz + twx, 1 - (txx + tyy)};
-    for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) Rt[r * 4 + c] = (float)R[r * 3 + c];
-        Rt[r * 4 + 3] = (float)T.t[r];
-    }
-}
-
-struct Cam {
-    double fx, fy, cx, cy;
-};
-
-double chi2_of(const double e[2], double info) { return e[0] * (info * e[0]) + e[1] * (info * e[1]); }
-
-// Huber: rho[0], rho[1]
-void huber(double chi2, double delta, double rho[2])
-{
-    const double dsqr = delta * delta;
-    if (chi2 <= dsqr) {
-        rho[0] = chi2;
-        rho[1] = 1.;
-    } else {
-        const double s = std::sqrt(chi2);
-        rho[0] = 2 * s * delta - dsqr;
-        rho[1] = delta / s;
-    }
-}
-
 void rot_of(const Quat& q, double R[3][3])
 {
     const double tx = 2 * q.x, ty = 2 * q.y, tz = 2 * q.z;
@@ -221,12 +47,6 @@ void rot_of(const Quat& q, double R[3][3])
     R[0][0] = 1 - (tyy + tzz); R[0][1] = txy - twz; R[0][2] = txz + twy;
     R[1][0] = txy + twz; R[1][1] = 1 - (txx + tzz); R[1][2] = tyz - twx;
     R[2][0] = txz - twy; R[2][1] = tyz + twx; R[2][2] = 1 - (txx + tyy);
-}
-
-void project_error(const double Xc[3], double ox, double oy, const Cam& K, double err[2])
-{
-    err[0] = ox - ((Xc[0] / Xc[2]) * K.fx + K.cx);
-    err[1] = oy - ((Xc[1] / Xc[2]) * K.fy + K.cy);
 }
 
 void mono_error(const SE3& T, const double Xw[3], double ox, double oy, const Cam& K, double err[2])
@@ -639,11 +459,6 @@ bool llt_solve(std::vector<double>& S, int n, const std::vector<double>& b, doub
     return true;
 }
 
-struct Lm {
-    double lambda, ni, currentChi, iniChi, rho, lambda0;
-    int q, nbad;
-};
-
 // one trial: the reduced solve, the updates, the trial estimates and their chi2 (written to the cache).  Returns ok2.
 bool trial(const Prob& P, Cache& C, Lin& L, double lambda, bool robust, const Est& X, Est& Xt, std::vector<double>& xv, std::vector<double>& xl,
            double& tempChi, double& scale_points)
@@ -727,57 +542,26 @@ bool trial(const Prob& P, Cache& C, Lin& L, double lambda, bool robust, const Es
 // optimize(maxit): returns the iterations run; `stale` = the last trial was rejected
 int optimize(const Prob& P, Cache& C, Est& X, bool robust, int maxit, std::vector<double>& xv, std::vector<double>& xl, bool& stale)
 {
-    Lm c{};
-    c.ni = 2;
+    Levenberg c;
+    lm_begin(c);
     stale = false;
     int it = 0;
     Lin L;
     Est Xt;
     while (it < maxit) {
         linearize(P, X, robust, C, L);
-        c.currentChi = c.iniChi = L.chi;
-        if (it == 0) {
-            c.lambda = c.lambda0 = 1e-5 * L.maxdiag;
-            c.ni = 2;
-            c.nbad = 0;
-        }
-        c.rho = 0;
-        c.q = 0;
-        for (;;) {
+        lm_linearised(c, L.chi, it == 0, L.maxdiag);
+        do {
             double tempChi, sp;
             const bool ok2 = trial(P, C, L, c.lambda, robust, X, Xt, xv, xl, tempChi, sp);
-            if (!ok2) tempChi = DBL_MAX;
             double scale = 0;
             for (int j = 0; j < 6 * P.nv; j++) scale += xv[(size_t)j] * (c.lambda * xv[(size_t)j] + (L.vact[j / 6] ? L.bp[(size_t)j] : 0.));
             scale += sp;
-            scale += 1e-3;
-            double rho = (c.currentChi - tempChi);
-            rho /= scale;
-            if (rho > 0 && std::isfinite(tempChi)) {
-                double alpha = 1. - std::pow((2 * rho - 1), 3);
-                alpha = std::min(alpha, 2. / 3.);
-                c.lambda *= std::max(1. / 3., alpha);
-                c.ni = 2;
-                c.currentChi = tempChi;
-                X = Xt;
-                stale = false;
-            } else {
-                c.lambda *= c.ni;
-                c.ni *= 2;
-                stale = true;
-            }
-            c.rho = rho;
-            c.q++;
-            if (!(rho < 0 && c.q < 10)) break;
-        }
+            stale = !lm_trial(c, tempChi, ok2, scale);
+            if (!stale) X = Xt;
+        } while (lm_again(c));
         it++;
-        bool stop = c.q == 10 || c.rho == 0;
-        if (!stop) {
-            if ((c.iniChi - c.currentChi) * 1e3 < c.iniChi) c.nbad++;
-            else c.nbad = 0;
-            stop = c.nbad >= 3;
-        }
-        if (stop) break;
+        if (lm_iteration_end(c)) break;
     }
     return it;
 }

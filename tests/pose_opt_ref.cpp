@@ -1,16 +1,11 @@
 // pose_opt_ref.cpp -- CPU restatement of ORB_SLAM2's motion-only pose optimization (Optimizer::PoseOptimizationByAruco,
 // src/Optimizer.cc of the reference, and PoseOptimization without its stereo branch) for the parity tests of
-// orbfe_pose_optimization*.  No g2o or Eigen here: the pieces the reference runs through are restated from their algorithms:
-//   SE3Quat                  quaternion + translation; product = t1 + q1 t2, q1 q2, then w >= 0 and normalisation; exp() with the
-//                            small-angle branch below theta = 1e-5; construction from a rotation matrix (Eigen's trace /
-//                            largest-diagonal quaternion) followed by the same normalisation
+// orbfe_pose_optimization*.  No g2o or Eigen here: the pieces the reference runs through are restated from their algorithms.
+// SE3Quat, the Huber kernel, the Levenberg-Marquardt rules and the dense LDLT (not positive -> chi2 = DBL_MAX) are those of
+// tests/g2o_ref.hpp, which the three restatements share; this file's own:
 //   mono edge                e = obs - pi(T Xw), Omega = invSigma2 I, analytic Jacobian of the left-multiplied increment
 //   marker edge              e = obs - pi((T Twm) p), Omega = w I, numeric Jacobian: central differences, delta = 1e-9, through
 //                            exp(+-delta e_d) * T (the marker vertex is fixed, so only the camera's six columns)
-//   Huber kernel             rho = (e, 1) inside delta^2, (2 delta sqrt(e) - delta^2, delta / sqrt(e)) outside; H and b weigh by rho'
-//   Levenberg-Marquardt      lambda0 = 1e-5 max diag H, up to 10 trials an iteration, rho = dchi / (x (lambda x + b) + 1e-3),
-//                            lambda *= max(1/3, min(2/3, 1 - (2 rho - 1)^3)) on success, *= nu (nu *= 2) on failure, the stop rules
-//   dense solve              LDLT with diagonal pivoting (largest remaining |diagonal|), not positive -> chi2 = DBL_MAX
 // Edges are summed in insertion order: mono edges by keypoint index, then the marker edges, marker by marker, corner 0..3.  The
 // "cached" error an inlier's chi2 reads after a round is the error at the last pose the active edges were evaluated at, which
 // is a rejected trial's pose when the round ended on rejected trials.
@@ -20,6 +15,8 @@
 #include <cstdint>
 #include <cstring>
 #include <vector>
+
+#include "g2o_ref.hpp"
 
 namespace {
 
@@ -42,168 +39,7 @@ struct Result {     // the layout of the library's result record
     int32_t status;
 };
 
-// ------------------------------------------------------------------------------------------ SE3Quat --
-struct Quat {
-    double x, y, z, w;
-};
-struct SE3 {
-    Quat q;
-    double t[3];
-};
-
-void normalize_rotation(Quat& q)
-{
-    if (q.w < 0) {
-        q.x *= -1; q.y *= -1; q.z *= -1; q.w *= -1;
-    }
-    const double n2 = q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w;
-    if (n2 > 0) {
-        const double n = std::sqrt(n2);
-        q.x /= n; q.y /= n; q.z /= n; q.w /= n;
-    }
-}
-
-Quat quat_from_matrix(const double m[3][3])
-{
-    Quat q;
-    double* v[3] = {&q.x, &q.y, &q.z};
-    double t = m[0][0] + m[1][1] + m[2][2];
-    if (t > 0) {
-        t = std::sqrt(t + 1.0);
-        q.w = 0.5 * t;
-        t = 0.5 / t;
-        q.x = (m[2][1] - m[1][2]) * t;
-        q.y = (m[0][2] - m[2][0]) * t;
-        q.z = (m[1][0] - m[0][1]) * t;
-    } else {
-        int i = 0;
-        if (m[1][1] > m[0][0]) i = 1;
-        if (m[2][2] > m[i][i]) i = 2;
-        const int j = (i + 1) % 3, k = (j + 1) % 3;
-        t = std::sqrt(m[i][i] - m[j][j] - m[k][k] + 1.0);
-        *v[i] = 0.5 * t;
-        t = 0.5 / t;
-        q.w = (m[k][j] - m[j][k]) * t;
-        *v[j] = (m[j][i] + m[i][j]) * t;
-        *v[k] = (m[k][i] + m[i][k]) * t;
-    }
-    return q;
-}
-
-void cross(const double a[3], const double b[3], double r[3])
-{
-    r[0] = a[1] * b[2] - a[2] * b[1];
-    r[1] = a[2] * b[0] - a[0] * b[2];
-    r[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-// q v: v + w uv + qv x uv, uv = 2 (qv x v)
-void rotate(const Quat& q, const double v[3], double r[3])
-{
-    const double qv[3] = {q.x, q.y, q.z};
-    double uv[3], c[3];
-    cross(qv, v, uv);
-    for (int i = 0; i < 3; i++) uv[i] += uv[i];
-    cross(qv, uv, c);
-    for (int i = 0; i < 3; i++) r[i] = v[i] + q.w * uv[i] + c[i];
-}
-
-Quat qmul(const Quat& a, const Quat& b)
-{
-    Quat r;
-    r.w = a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z;
-    r.x = a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y;
-    r.y = a.w * b.y + a.y * b.w + a.z * b.x - a.x * b.z;
-    r.z = a.w * b.z + a.z * b.w + a.x * b.y - a.y * b.x;
-    return r;
-}
-
-SE3 mul(const SE3& a, const SE3& b)
-{
-    SE3 r = a;
-    double qt[3];
-    rotate(a.q, b.t, qt);
-    for (int i = 0; i < 3; i++) r.t[i] += qt[i];
-    r.q = qmul(a.q, b.q);
-    normalize_rotation(r.q);
-    return r;
-}
-
-void map(const SE3& T, const double p[3], double r[3])
-{
-    rotate(T.q, p, r);
-    for (int i = 0; i < 3; i++) r[i] += T.t[i];
-}
-
-SE3 se3_from_Rt(const double R[3][3], const double t[3])
-{
-    SE3 T;
-    T.q = quat_from_matrix(R);
-    for (int i = 0; i < 3; i++) T.t[i] = t[i];
-    normalize_rotation(T.q);
-    return T;
-}
-
-SE3 se3_from_float(const float* Rt)
-{
-    double R[3][3], t[3];
-    for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) R[r][c] = Rt[r * 4 + c];
-        t[r] = Rt[r * 4 + 3];
-    }
-    return se3_from_Rt(R, t);
-}
-
-void mat3mul(const double a[3][3], const double b[3][3], double r[3][3])
-{
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) r[i][j] = a[i][0] * b[0][j] + a[i][1] * b[1][j] + a[i][2] * b[2][j];
-}
-
-SE3 se3_exp(const double u[6])
-{
-    const double om[3] = {u[0], u[1], u[2]}, up[3] = {u[3], u[4], u[5]};
-    const double theta = std::sqrt(om[0] * om[0] + om[1] * om[1] + om[2] * om[2]);
-    const double O[3][3] = {{0, -om[2], om[1]}, {om[2], 0, -om[0]}, {-om[1], om[0], 0}};
-    double O2[3][3], R[3][3], V[3][3];
-    mat3mul(O, O, O2);
-    if (theta < 0.00001) {
-        for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 3; j++) R[i][j] = ((i == j ? 1.0 : 0.0) + O[i][j]) + O2[i][j];
-        std::memcpy(V, R, sizeof(R));
-    } else {
-        const double a = std::sin(theta) / theta, b = (1 - std::cos(theta)) / (theta * theta);
-        const double c = (theta - std::sin(theta)) / std::pow(theta, 3);
-        for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 3; j++) {
-                R[i][j] = ((i == j ? 1.0 : 0.0) + a * O[i][j]) + b * O2[i][j];
-                V[i][j] = ((i == j ? 1.0 : 0.0) + b * O[i][j]) + c * O2[i][j];
-            }
-    }
-    double t[3];
-    for (int i = 0; i < 3; i++) t[i] = V[i][0] * up[0] + V[i][1] * up[1] + V[i][2] * up[2];
-    return se3_from_Rt(R, t);
-}
-
-void to_float(const SE3& T, float* Rt)
-{
-    const Quat& q = T.q;
-    const double tx = 2 * q.x, ty = 2 * q.y, tz = 2 * q.z;
-    const double twx = tx * q.w, twy = ty * q.w, twz = tz * q.w;
-    const double txx = tx * q.x, txy = ty * q.x, txz = tz * q.x;
-    const double tyy = ty * q.y, tyz = tz * q.y, tzz = tz * q.z;
-    const double R[9] = {1 - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1 - (txx + tzz), tyz - twx, txz - twy, tyz + twx, 1 - (txx + tyy)};
-    for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) Rt[r * 4 + c] = (float)R[r * 3 + c];
-        Rt[r * 4 + 3] = (float)T.t[r];
-    }
-}
-
 // ------------------------------------------------------------------------------------------- edges --
-struct Cam {
-    double fx, fy, cx, cy;
-};
-
 struct MonoEdge {
     double obs[2], Xw[3], info;
     int idx;          // keypoint index
@@ -219,8 +55,7 @@ void mono_error(const MonoEdge& e, const SE3& T, const Cam& K, double err[2])
 {
     double Xc[3];
     map(T, e.Xw, Xc);
-    err[0] = e.obs[0] - ((Xc[0] / Xc[2]) * K.fx + K.cx);
-    err[1] = e.obs[1] - ((Xc[1] / Xc[2]) * K.fy + K.cy);
+    project_error(Xc, e.obs[0], e.obs[1], K, err);
 }
 
 void mono_jacobian(const MonoEdge& e, const SE3& T, const Cam& K, double J[2][6])
@@ -247,8 +82,7 @@ void marker_error(const MarkerEdge& e, const SE3& T, const Cam& K, double err[2]
     const SE3 Tcm = mul(T, e.Twm);
     double p[3];
     map(Tcm, e.p, p);
-    err[0] = e.obs[0] - ((p[0] / p[2]) * K.fx + K.cx);
-    err[1] = e.obs[1] - ((p[1] / p[2]) * K.fy + K.cy);
+    project_error(p, e.obs[0], e.obs[1], K, err);
 }
 
 void marker_jacobian(const MarkerEdge& e, const SE3& T, const Cam& K, double J[2][6])
@@ -263,100 +97,6 @@ void marker_jacobian(const MarkerEdge& e, const SE3& T, const Cam& K, double J[2
         J[0][d] = scalar * (ep[0] - em[0]);
         J[1][d] = scalar * (ep[1] - em[1]);
     }
-}
-
-double chi2_of(const double e[2], double info) { return e[0] * (info * e[0]) + e[1] * (info * e[1]); }
-
-// Huber: rho[0], rho[1]
-void huber(double chi2, double delta, double rho[2])
-{
-    const double dsqr = delta * delta;
-    if (chi2 <= dsqr) {
-        rho[0] = chi2;
-        rho[1] = 1.;
-    } else {
-        const double s = std::sqrt(chi2);
-        rho[0] = 2 * s * delta - dsqr;
-        rho[1] = delta / s;
-    }
-}
-
-// ------------------------------------------------------------------------------------------ LDLT 6x6 --
-// Diagonal pivoting on the lower triangle, as Eigen's LDLT; returns isPositive() and x = H^-1 b (x untouched when not positive)
-bool ldlt_solve(const double Hin[6][6], const double b[6], double x[6])
-{
-    const int n = 6;
-    double m[6][6];
-    std::memcpy(m, Hin, sizeof(m));
-    int tr[6];
-    int sign = 0;   // 0 zero, 1 positive semidefinite, -1 negative semidefinite, 2 indefinite
-    for (int k = 0; k < n; k++) {
-        int big = k;
-        double bv = std::fabs(m[k][k]);
-        for (int i = k + 1; i < n; i++)
-            if (std::fabs(m[i][i]) > bv) {
-                bv = std::fabs(m[i][i]);
-                big = i;
-            }
-        tr[k] = big;
-        if (k != big) {
-            for (int j = 0; j < k; j++) std::swap(m[k][j], m[big][j]);
-            for (int i = big + 1; i < n; i++) std::swap(m[i][k], m[i][big]);
-            std::swap(m[k][k], m[big][big]);
-            for (int i = k + 1; i < big; i++) {
-                const double tmp = m[i][k];
-                m[i][k] = m[big][i];
-                m[big][i] = tmp;
-            }
-        }
-        double temp[6];
-        if (k > 0) {
-            for (int j = 0; j < k; j++) temp[j] = m[j][j] * m[k][j];
-            double s = 0;
-            for (int j = 0; j < k; j++) s += m[k][j] * temp[j];
-            m[k][k] -= s;
-            for (int i = k + 1; i < n; i++) {
-                double si = 0;
-                for (int j = 0; j < k; j++) si += m[i][j] * temp[j];
-                m[i][k] -= si;
-            }
-        }
-        const double akk = m[k][k];
-        const bool valid = std::fabs(akk) > 0;
-        if (k == 0 && !valid) {
-            sign = 0;
-            for (int j = 0; j < n; j++) tr[j] = j;
-            break;
-        }
-        if (valid)
-            for (int i = k + 1; i < n; i++) m[i][k] /= akk;
-        if (sign == 1) {
-            if (akk < 0) sign = 2;
-        } else if (sign == -1) {
-            if (akk > 0) sign = 2;
-        } else if (sign == 0) {
-            if (akk > 0) sign = 1;
-            else if (akk < 0) sign = -1;
-        }
-    }
-    if (!(sign == 1 || sign == 0)) return false;
-    double y[6];
-    std::memcpy(y, b, sizeof(y));
-    for (int k = 0; k < n; k++) std::swap(y[k], y[tr[k]]);
-    for (int i = 0; i < n; i++) {
-        double s = y[i];
-        for (int j = 0; j < i; j++) s -= m[i][j] * y[j];
-        y[i] = s;
-    }
-    for (int i = 0; i < n; i++) y[i] = std::fabs(m[i][i]) > DBL_MIN ? y[i] / m[i][i] : 0.0;
-    for (int i = n - 1; i >= 0; i--) {
-        double s = y[i];
-        for (int j = i + 1; j < n; j++) s -= m[j][i] * y[j];
-        y[i] = s;
-    }
-    for (int k = n - 1; k >= 0; k--) std::swap(y[k], y[tr[k]]);
-    std::memcpy(x, y, sizeof(y));
-    return true;
 }
 
 // ------------------------------------------------------------------------------------------ the graph --
@@ -436,57 +176,32 @@ int optimize(Graph& g, int iterations, bool* stale)
     bool any = !g.marker.empty();
     for (const MonoEdge& e : g.mono) any = any || !e.outlier;
     if (!any) return -1;
-    double lambda = 0, ni = 2, x[6] = {0, 0, 0, 0, 0, 0};
-    int nbad = 0, it = 0;
-    for (it = 0; it < iterations;) {
-        double currentChi = active_chi2(g);
-        const double iniChi = currentChi;
+    Levenberg lm;
+    lm_begin(lm);
+    double x[6] = {0, 0, 0, 0, 0, 0};
+    int it = 0;
+    while (it < iterations) {
+        const double chi = active_chi2(g);
         double H[6][6], b[6];
         build_system(g, H, b);
-        if (it == 0) {
-            double md = 0;
-            for (int j = 0; j < 6; j++) md = std::max(std::fabs(H[j][j]), md);
-            lambda = 1e-5 * md;
-            ni = 2;
-            nbad = 0;
-        }
-        double rho = 0;
-        int q = 0;
+        double md = 0;
+        for (int j = 0; j < 6; j++) md = std::max(std::fabs(H[j][j]), md);
+        lm_linearised(lm, chi, it == 0, md);
         do {
             const SE3 saved = g.T;
             double Hl[6][6];
             std::memcpy(Hl, H, sizeof(Hl));
-            for (int j = 0; j < 6; j++) Hl[j][j] += lambda;
-            const bool ok2 = ldlt_solve(Hl, b, x);
+            for (int j = 0; j < 6; j++) Hl[j][j] += lm.lambda;
+            const bool ok2 = ldlt_solve<6>(Hl, b, x);
             g.T = mul(se3_exp(x), g.T);
-            double tempChi = active_chi2(g);
-            if (!ok2) tempChi = DBL_MAX;
-            rho = currentChi - tempChi;
+            const double tempChi = active_chi2(g);
             double scale = 0;
-            for (int j = 0; j < 6; j++) scale += x[j] * (lambda * x[j] + b[j]);
-            scale += 1e-3;
-            rho /= scale;
-            if (rho > 0 && std::isfinite(tempChi)) {
-                double alpha = 1. - std::pow((2 * rho - 1), 3);
-                alpha = std::min(alpha, 2. / 3.);
-                const double sf = std::max(1. / 3., alpha);
-                lambda *= sf;
-                ni = 2;
-                currentChi = tempChi;
-                *stale = false;
-            } else {
-                lambda *= ni;
-                ni *= 2;
-                g.T = saved;
-                *stale = true;
-            }
-            q++;
-        } while (rho < 0 && q < 10);
+            for (int j = 0; j < 6; j++) scale += x[j] * (lm.lambda * x[j] + b[j]);
+            *stale = !lm_trial(lm, tempChi, ok2, scale);
+            if (*stale) g.T = saved;
+        } while (lm_again(lm));
         it++;
-        if (q == 10 || rho == 0) break;
-        if ((iniChi - currentChi) * 1e3 < iniChi) nbad++;
-        else nbad = 0;
-        if (nbad >= 3) break;
+        if (lm_iteration_end(lm)) break;
     }
     return it;
 }

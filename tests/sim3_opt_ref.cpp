@@ -9,10 +9,8 @@
 //                            Omega = invSigma2 I (a float widened), numeric Jacobian: central differences, delta = 1e-9,
 //                            through Sim3(update) * S; with a fixed scale the update's 7th component is zeroed first
 //   Huber kernel             delta = (double)sqrtf(th2), in both rounds
-//   Levenberg-Marquardt      as tests/pose_opt_ref.cpp restates it, 7 x 7: lambda0 = 1e-5 max diag H, up to 10 trials an iteration,
-//                            rho = dchi / (x (lambda x + b) + 1e-3), the lambda and stop rules; lambda and nu start again in
-//                            every optimize()
-//   dense solve              LDLT with diagonal pivoting (largest remaining |diagonal|); a zero pivot solves to 0
+//   Levenberg-Marquardt      the rules of tests/g2o_ref.hpp (shared by the three restatements, with the quaternion pieces and the
+//   and the dense solve      Huber kernel), 7 x 7; lambda and nu start again in every optimize()
 //   OptimizeSim3             optimize(5), pairs with a cached chi2 > (double)th2 removed, return 0 when fewer than 10 are left
 //                            (the estimate is not written back), optimize(10 or 5) from the first round's estimate, second check
 // The "cached" error a check reads is the error at the last estimate the active edges were evaluated at, which is a rejected
@@ -28,6 +26,8 @@
 #include <cstdint>
 #include <cstring>
 #include <vector>
+
+#include "g2o_ref.hpp"
 
 namespace {
 
@@ -47,69 +47,11 @@ struct Result {     // the layout of the library's result record
 constexpr int NSUM = 36;   // robust chi2, H upper triangle (28), b (7)
 
 // ------------------------------------------------------------------------------------------ g2o::Sim3 --
-struct Quat {
-    double x, y, z, w;
-};
 struct Sim3 {
     Quat q;
     double t[3];
     double s;
 };
-
-Quat quat_from_matrix(const double m[3][3])
-{
-    Quat q;
-    double* v[3] = {&q.x, &q.y, &q.z};
-    double t = m[0][0] + m[1][1] + m[2][2];
-    if (t > 0) {
-        t = std::sqrt(t + 1.0);
-        q.w = 0.5 * t;
-        t = 0.5 / t;
-        q.x = (m[2][1] - m[1][2]) * t;
-        q.y = (m[0][2] - m[2][0]) * t;
-        q.z = (m[1][0] - m[0][1]) * t;
-    } else {
-        int i = 0;
-        if (m[1][1] > m[0][0]) i = 1;
-        if (m[2][2] > m[i][i]) i = 2;
-        const int j = (i + 1) % 3, k = (j + 1) % 3;
-        t = std::sqrt(m[i][i] - m[j][j] - m[k][k] + 1.0);
-        *v[i] = 0.5 * t;
-        t = 0.5 / t;
-        q.w = (m[k][j] - m[j][k]) * t;
-        *v[j] = (m[j][i] + m[i][j]) * t;
-        *v[k] = (m[k][i] + m[i][k]) * t;
-    }
-    return q;
-}
-
-void cross(const double a[3], const double b[3], double r[3])
-{
-    r[0] = a[1] * b[2] - a[2] * b[1];
-    r[1] = a[2] * b[0] - a[0] * b[2];
-    r[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-// q v: v + w uv + qv x uv, uv = 2 (qv x v)
-void rotate(const Quat& q, const double v[3], double r[3])
-{
-    const double qv[3] = {q.x, q.y, q.z};
-    double uv[3], c[3];
-    cross(qv, v, uv);
-    for (int i = 0; i < 3; i++) uv[i] += uv[i];
-    cross(qv, uv, c);
-    for (int i = 0; i < 3; i++) r[i] = v[i] + q.w * uv[i] + c[i];
-}
-
-Quat qmul(const Quat& a, const Quat& b)
-{
-    Quat r;
-    r.w = a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z;
-    r.x = a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y;
-    r.y = a.w * b.y + a.y * b.w + a.z * b.x - a.x * b.z;
-    r.z = a.w * b.z + a.z * b.w + a.x * b.y - a.y * b.x;
-    return r;
-}
 
 Sim3 mul(const Sim3& a, const Sim3& b)
 {
@@ -213,10 +155,6 @@ Sim3 sim3_from_floats(float s, const float* R9, const float* t3)
 }
 
 // ------------------------------------------------------------------------------------------- edges --
-struct Cam {
-    double fx, fy, cx, cy;
-};
-
 struct Pair {       // one kept correspondence: its two edges
     double P1[3], P2[3], obs1[2], obs2[2], info1, info2;
     int idx;        // index in keyframe 1
@@ -227,8 +165,7 @@ void edge_error(const Sim3& S, const double P[3], const double obs[2], const Cam
 {
     double X[3];
     map(S, P, X);
-    err[0] = obs[0] - ((X[0] / X[2]) * K.fx + K.cx);
-    err[1] = obs[1] - ((X[1] / X[2]) * K.fy + K.cy);
+    project_error(X, obs[0], obs[1], K, err);
 }
 
 // central differences over the perturbed estimates sp[2 d] (+delta), sp[2 d + 1] (-delta); false when an entry is not finite
@@ -257,21 +194,6 @@ void perturbed(const Sim3& S, bool fix_scale, Sim3 sp[14], Sim3 spi[14])
     }
 }
 
-double chi2_of(const double e[2], double info) { return e[0] * (info * e[0]) + e[1] * (info * e[1]); }
-
-void huber(double chi2, double delta, double rho[2])
-{
-    const double dsqr = delta * delta;
-    if (chi2 <= dsqr) {
-        rho[0] = chi2;
-        rho[1] = 1.;
-    } else {
-        const double s = std::sqrt(chi2);
-        rho[0] = 2 * s * delta - dsqr;
-        rho[1] = delta / s;
-    }
-}
-
 void add_edge(const double err[2], const double J[2][7], double info, double rho1, double s[NSUM])
 {
     const double w = rho1 * info;
@@ -280,83 +202,6 @@ void add_edge(const double err[2], const double J[2][7], double info, double rho
     for (int a = 0; a < 7; a++)
         for (int c = a; c < 7; c++, k++) s[k] += J[0][a] * (w * J[0][c]) + J[1][a] * (w * J[1][c]);
     for (int a = 0; a < 7; a++) s[29 + a] += J[0][a] * r0 + J[1][a] * r1;
-}
-
-// ------------------------------------------------------------------------------------------ LDLT 7x7 --
-bool ldlt_solve(const double Hin[7][7], const double b[7], double x[7])
-{
-    const int n = 7;
-    double m[7][7];
-    std::memcpy(m, Hin, sizeof(m));
-    int tr[7];
-    int sign = 0;   // 0 zero, 1 positive semidefinite, -1 negative semidefinite, 2 indefinite
-    for (int k = 0; k < n; k++) {
-        int big = k;
-        double bv = std::fabs(m[k][k]);
-        for (int i = k + 1; i < n; i++)
-            if (std::fabs(m[i][i]) > bv) {
-                bv = std::fabs(m[i][i]);
-                big = i;
-            }
-        tr[k] = big;
-        if (k != big) {
-            for (int j = 0; j < k; j++) std::swap(m[k][j], m[big][j]);
-            for (int i = big + 1; i < n; i++) std::swap(m[i][k], m[i][big]);
-            std::swap(m[k][k], m[big][big]);
-            for (int i = k + 1; i < big; i++) {
-                const double tmp = m[i][k];
-                m[i][k] = m[big][i];
-                m[big][i] = tmp;
-            }
-        }
-        double temp[7];
-        if (k > 0) {
-            for (int j = 0; j < k; j++) temp[j] = m[j][j] * m[k][j];
-            double s = 0;
-            for (int j = 0; j < k; j++) s += m[k][j] * temp[j];
-            m[k][k] -= s;
-            for (int i = k + 1; i < n; i++) {
-                double si = 0;
-                for (int j = 0; j < k; j++) si += m[i][j] * temp[j];
-                m[i][k] -= si;
-            }
-        }
-        const double akk = m[k][k];
-        const bool valid = std::fabs(akk) > 0;
-        if (k == 0 && !valid) {
-            sign = 0;
-            for (int j = 0; j < n; j++) tr[j] = j;
-            break;
-        }
-        if (valid)
-            for (int i = k + 1; i < n; i++) m[i][k] /= akk;
-        if (sign == 1) {
-            if (akk < 0) sign = 2;
-        } else if (sign == -1) {
-            if (akk > 0) sign = 2;
-        } else if (sign == 0) {
-            if (akk > 0) sign = 1;
-            else if (akk < 0) sign = -1;
-        }
-    }
-    if (!(sign == 1 || sign == 0)) return false;
-    double y[7];
-    std::memcpy(y, b, sizeof(y));
-    for (int k = 0; k < n; k++) std::swap(y[k], y[tr[k]]);
-    for (int i = 0; i < n; i++) {
-        double s = y[i];
-        for (int j = 0; j < i; j++) s -= m[i][j] * y[j];
-        y[i] = s;
-    }
-    for (int i = 0; i < n; i++) y[i] = std::fabs(m[i][i]) > DBL_MIN ? y[i] / m[i][i] : 0.0;
-    for (int i = n - 1; i >= 0; i--) {
-        double s = y[i];
-        for (int j = i + 1; j < n; j++) s -= m[j][i] * y[j];
-        y[i] = s;
-    }
-    for (int k = n - 1; k >= 0; k--) std::swap(y[k], y[tr[k]]);
-    std::memcpy(x, y, sizeof(y));
-    return true;
 }
 
 // ------------------------------------------------------------------------------------------ the graph --
@@ -435,64 +280,37 @@ int optimize(Graph& g, int iterations, bool* stale)
     bool any = false;
     for (const Pair& p : g.pairs) any = any || !p.removed;
     if (!any) return -1;
-    double lambda = 0, ni = 2, x[7] = {0, 0, 0, 0, 0, 0, 0};
-    int nbad = 0, it = 0;
-    for (it = 0; it < iterations;) {
+    Levenberg lm;
+    lm_begin(lm);
+    double x[7] = {0, 0, 0, 0, 0, 0, 0};
+    int it = 0;
+    while (it < iterations) {
         double s[NSUM];
         sum_pairs(g, true, s);
-        double currentChi = s[0];
-        const double iniChi = currentChi;
         double H[7][7], b[7];
         int k = 1;
         for (int r = 0; r < 7; r++)
             for (int c = r; c < 7; c++, k++) H[r][c] = H[c][r] = s[k];
         for (int r = 0; r < 7; r++) b[r] = s[29 + r];
-        if (it == 0) {
-            double md = 0;
-            for (int j = 0; j < 7; j++) md = std::max(std::fabs(H[j][j]), md);
-            lambda = 1e-5 * md;
-            ni = 2;
-            nbad = 0;
-        }
-        double rho = 0;
-        int q = 0;
+        double md = 0;
+        for (int j = 0; j < 7; j++) md = std::max(std::fabs(H[j][j]), md);
+        lm_linearised(lm, s[0], it == 0, md);
         do {
             const Sim3 saved = g.S;
             double Hl[7][7];
             std::memcpy(Hl, H, sizeof(Hl));
-            for (int j = 0; j < 7; j++) Hl[j][j] += lambda;
-            const bool ok2 = ldlt_solve(Hl, b, x);
+            for (int j = 0; j < 7; j++) Hl[j][j] += lm.lambda;
+            const bool ok2 = ldlt_solve<7>(Hl, b, x);
             g.S = oplus(g.S, x, g.fix_scale);
             double t[NSUM];
             sum_pairs(g, false, t);
-            double tempChi = t[0];
-            if (!ok2) tempChi = DBL_MAX;
-            rho = currentChi - tempChi;
             double scale = 0;
-            for (int j = 0; j < 7; j++) scale += x[j] * (lambda * x[j] + b[j]);
-            scale += 1e-3;
-            rho /= scale;
-            if (rho > 0 && std::isfinite(tempChi)) {
-                double alpha = 1. - std::pow((2 * rho - 1), 3);
-                alpha = std::min(alpha, 2. / 3.);
-                const double sf = std::max(1. / 3., alpha);
-                lambda *= sf;
-                ni = 2;
-                currentChi = tempChi;
-                *stale = false;
-            } else {
-                lambda *= ni;
-                ni *= 2;
-                g.S = saved;
-                *stale = true;
-            }
-            q++;
-        } while (rho < 0 && q < 10);
+            for (int j = 0; j < 7; j++) scale += x[j] * (lm.lambda * x[j] + b[j]);
+            *stale = !lm_trial(lm, t[0], ok2, scale);
+            if (*stale) g.S = saved;
+        } while (lm_again(lm));
         it++;
-        if (q == 10 || rho == 0) break;
-        if ((iniChi - currentChi) * 1e3 < iniChi) nbad++;
-        else nbad = 0;
-        if (nbad >= 3) break;
+        if (lm_iteration_end(lm)) break;
     }
     return it;
 }
