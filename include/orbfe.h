@@ -1012,6 +1012,73 @@ int orbfe_lba_inspect(const float* Tcw, const uint8_t* kf_fixed, int nkf, const 
                       const int32_t* mobs_offset, const int32_t* mobs_kf, const float* mobs_corners, int nmobs, float marker_info,
                       int use_markers, int32_t* nv, double* b, double* Hpp, double* Hll, double* chi2, double* x, int device);
 
+/* ------------------------------------------------------------ OptimizeEssentialGraph (loop closing's pose graph) -- */
+/* Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:1245-1542, called by LoopClosing::CorrectLoopByAruco with bFixScale = true)
+ * behind its collect step: Sim3 vertices, EdgeSim3 edges with identity information, g2o's Levenberg-Marquardt with
+ * setUserLambdaInit(1e-16), then the SE3 recovery of every keyframe and the correction of every map point.  Flat arrays in the
+ * reference's vpKFs order ("positions" 0 .. nkf - 1; bad keyframes are left out by the caller), nothing pointer-shaped.
+ *   keyframes   kf_id[nkf] (mnId; read for the messages of orbfe_last_error alone, may be NULL), Tcw[nkf][12] (3 x 4 row-major),
+ *               fixed (the position of pLoopKF), corrected_pos[nc] + corrected[nc][8] (CorrectedSim3) and noncorrected_pos[nn] +
+ *               noncorrected[nn][8] (NonCorrectedSim3): quaternion x y z w, t, s in double, as g2o::Sim3 holds them; a position
+ *               at most once in each list.  vScw of a keyframe is its CorrectedSim3 entry, else Sim3(Rcw, tcw, 1)
+ *   edges       in the order the reference adds them: edge_i[ne] (vertex 0), edge_j[ne] (vertex 1), edge_kind[ne].  Kind 0
+ *               (LoopConnections, :1316-1344) measures vScw[j] * vScw[i]^-1; kind 1 (spanning tree, old loop edges, covisibility,
+ *               :1347-1447) measures the same with the NonCorrectedSim3 entry of a keyframe that has one.  Two edges on one pair
+ *               are legal and both count
+ *   points      x3Dw[np][3], point_ref[np]: the position of the keyframe whose id the reference calls nIDr (:1487-1496), -1
+ *               leaves the point as it is
+ *   options     iterations (the reference: 20, at most 20), fix_scale, leaf_vertices (the elimination plan's leaf size, 0 = default)
+ * Outputs: Tcw_out[nkf][12] (the corrected Siw as [R t/s], :1462-1473), x3Dw_out[np][3] (correctedSwr.map(Srw.map(P)) in double,
+ * then float), Siw_out[nkf][8] (may be NULL), the record.  nkf == 1 or ne == 0 is a legal call that returns its inputs.
+ * ORBFE_ERR_INVALID: NULLs, positions out of range, a self edge, an edge kind other than 0 / 1, a pose, similarity or point that is
+ * not finite, `fixed` out of range, a scale <= 0.  ORBFE_ERR_CAPACITY: more than ORBFE_EG_MAX_KEYFRAMES keyframes or
+ * ORBFE_EG_MAX_EDGES edges (at these the scratch is 0.9 GB), or a graph whose elimination fronts need more than the 768 MB of
+ * scratch set aside for them (a graph that dense is no essential graph).  A refused call writes nothing. */
+#define ORBFE_EG_MAX_KEYFRAMES 4096
+#define ORBFE_EG_MAX_EDGES 65536
+
+typedef struct orbfe_eg_result {
+    int32_t status;       /* ORBFE_OK, or the device call's ORBFE_ERR_INVALID (values it could only check on the device) */
+    int32_t iterations;   /* iterations run */
+    int32_t trials;       /* LM trials run over all iterations */
+    int32_t pad;
+    double chi2_first, chi2_last, lambda_last;
+} orbfe_eg_result;
+
+/* bytes of device scratch a problem of these sizes needs, whatever its graph; 0: sizes out of range */
+size_t orbfe_essential_graph_scratch_bytes(int nkf, int nedges, int npoints, int leaf_vertices);
+
+/* host pointers, one call, synchronous */
+int orbfe_optimize_essential_graph(const int32_t* kf_id, const float* Tcw, int nkf, int fixed, const int32_t* corrected_pos,
+                                   const double* corrected, int nc, const int32_t* noncorrected_pos, const double* noncorrected, int nn,
+                                   const int32_t* edge_i, const int32_t* edge_j, const int32_t* edge_kind, int ne, const float* x3Dw,
+                                   const int32_t* point_ref, int np, int iterations, int fix_scale, int leaf_vertices, float* Tcw_out,
+                                   float* x3Dw_out, double* Siw_out, orbfe_eg_result* res, int device);
+
+/* The values on the device (d_*), the graph -- kf_id, edge_i, edge_j, edge_kind -- on the host: the elimination plan is made from it
+ * before anything is enqueued.  Everything runs on `stream` with no host synchronisation (a second call on one stream waits, on the
+ * host, until the first one's tables have left their staging block); the worst case of 20 x 10 trials is enqueued and decided steps
+ * fall through.  d_scratch: scratch_bytes >= orbfe_essential_graph_scratch_bytes(...) bytes, 256-byte aligned.  What only the device
+ * can check (values that are not finite, scales, positions of the similarity lists and of point_ref) comes back as d_res->status,
+ * with no output written. */
+int orbfe_optimize_essential_graph_device(const int32_t* kf_id, const float* d_Tcw, int nkf, int fixed, const int32_t* d_corrected_pos,
+                                          const double* d_corrected, int nc, const int32_t* d_noncorrected_pos, const double* d_noncorrected,
+                                          int nn, const int32_t* edge_i, const int32_t* edge_j, const int32_t* edge_kind, int ne,
+                                          const float* d_x3Dw, const int32_t* d_point_ref, int np, int iterations, int fix_scale,
+                                          int leaf_vertices, float* d_Tcw_out, float* d_x3Dw_out, double* d_Siw_out, orbfe_eg_result* d_res,
+                                          void* d_scratch, size_t scratch_bytes, void* stream);
+
+/* DIAGNOSTIC / TEST INTERFACE, no stability promise: one linearisation and one solve at lambda0.  err (ne x 7), Ji and Jj (ne x 49,
+ * row-major 7 x 7; zeros for the fixed vertex), Hd (nkf x 49, the diagonal blocks) and b (nkf x 7) in the caller's positions, chi2
+ * (chi2, lambda0, 1 when every pivot was positive), x (nkf x 7, caller's positions), tree (2 + 2 nkf + 4 nodes, at most 10 nkf + 10
+ * entries: nodes, levels; node and place in the elimination order of every vertex, -1 the fixed one; parent, level, own and boundary
+ * vertices of every node). */
+int orbfe_essential_graph_inspect(const int32_t* kf_id, const float* Tcw, int nkf, int fixed, const int32_t* corrected_pos,
+                                  const double* corrected, int nc, const int32_t* noncorrected_pos, const double* noncorrected, int nn,
+                                  const int32_t* edge_i, const int32_t* edge_j, const int32_t* edge_kind, int ne, int fix_scale,
+                                  int leaf_vertices, double* err, double* Ji, double* Jj, double* Hd, double* b, double* chi2, double* x,
+                                  int32_t* tree, int device);
+
 /* ------------------------------------------------------------ KeyFrameDatabase: candidate queries -- */
 /* KeyFrameDatabase::DetectLoopCandidates(pKF, minScore) (src/KeyFrameDatabase.cc:76-197, called by LoopClosing::DetectLoop) and
  * KeyFrameDatabase::DetectRelocalizationCandidates(F) (:199-309, called by Tracking::Relocalization) on flat arrays, with DBoW2's

@@ -71,6 +71,9 @@ SYMBOLS = [
     "orbfe_create_new_map_points", "orbfe_new_points_inspect",
     # LocalBundleAdjustment of local mapping (csrc/local_ba.hip)
     "orbfe_lba_scratch_bytes", "orbfe_local_bundle_adjustment", "orbfe_local_bundle_adjustment_device", "orbfe_lba_inspect",
+    # OptimizeEssentialGraph of loop closing (csrc/essential_graph.hip)
+    "orbfe_essential_graph_scratch_bytes", "orbfe_optimize_essential_graph", "orbfe_optimize_essential_graph_device",
+    "orbfe_essential_graph_inspect",
 ]
 
 _lib = None
@@ -236,6 +239,12 @@ def load():
         prob = [vp, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, i32, f32, i32]
         L.orbfe_local_bundle_adjustment.argtypes = prob + [vp, vp, vp, i32]
         L.orbfe_lba_inspect.argtypes = prob + [vp] * 6 + [i32]
+        egp = [vp, vp, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, i32]   # keyframes, the two similarity lists, edges
+        L.orbfe_essential_graph_scratch_bytes.argtypes = [i32] * 4
+        L.orbfe_essential_graph_scratch_bytes.restype = sz
+        L.orbfe_optimize_essential_graph.argtypes = egp + [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32]
+        L.orbfe_optimize_essential_graph_device.argtypes = egp + [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]
+        L.orbfe_essential_graph_inspect.argtypes = egp + [i32, i32] + [vp] * 8 + [i32]
         L.orbfe_local_bundle_adjustment_device.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp,
                                                            i32, f32, i32, vp, vp, vp, vp, sz, vp]
     if hasattr(L, "orbfe_initialize"):
@@ -1667,3 +1676,87 @@ def lba_inspect(pb, device=0):
     v = int(nv[0])
     return dict(nv=v, b_pose=b[:6 * v].reshape(v, 6), b_point=b[6 * v:6 * v + 3 * n].reshape(n, 3), Hpp=Hpp[:v], Hll=Hll[:n], chi2=chi2[0],
                 lambda0=chi2[1], x_pose=x[:6 * v].reshape(v, 6), x_point=x[6 * v:6 * v + 3 * n].reshape(n, 3))
+
+
+# ------------------------------------------------------------------------------- OptimizeEssentialGraph (loop closing) ----
+EG_MAX_KEYFRAMES, EG_MAX_EDGES = 4096, 65536
+EG_RESULT_DTYPE = np.dtype([("status", "<i4"), ("iterations", "<i4"), ("trials", "<i4"), ("pad", "<i4"), ("chi2_first", "<f8"),
+                            ("chi2_last", "<f8"), ("lambda_last", "<f8")])
+assert EG_RESULT_DTYPE.itemsize == 40
+
+
+def eg_arrays(pb):
+    """The flat arrays of an OptimizeEssentialGraph problem, contiguous and typed as include/orbfe.h takes them.  pb: a dict with Tcw
+    (nkf x 3 x 4), fixed, edge_i, edge_j, edge_kind, and optionally kf_id, corrected_pos + corrected (nc x 8: quaternion x y z w, t, s),
+    noncorrected_pos + noncorrected, x3Dw (np x 3) + point_ref, iterations (20), fix_scale (1), leaf_vertices (0)."""
+    c = lambda k, t, shape: np.ascontiguousarray(np.asarray(pb.get(k, np.zeros(0)), t).reshape(shape))
+    a = dict(Tcw=c("Tcw", np.float32, (-1, 12)), corrected_pos=c("corrected_pos", np.int32, -1), corrected=c("corrected", np.float64, (-1, 8)),
+             noncorrected_pos=c("noncorrected_pos", np.int32, -1), noncorrected=c("noncorrected", np.float64, (-1, 8)),
+             edge_i=c("edge_i", np.int32, -1), edge_j=c("edge_j", np.int32, -1), edge_kind=c("edge_kind", np.int32, -1),
+             x3Dw=c("x3Dw", np.float32, (-1, 3)), point_ref=c("point_ref", np.int32, -1))
+    a["kf_id"] = c("kf_id", np.int32, -1) if "kf_id" in pb else np.arange(len(a["Tcw"]), dtype=np.int32)
+    a["fixed"] = int(pb["fixed"])
+    a["iterations"] = int(pb.get("iterations", 20))
+    a["fix_scale"] = int(pb.get("fix_scale", 1))
+    a["leaf_vertices"] = int(pb.get("leaf_vertices", 0))
+    if len(a["corrected_pos"]) != len(a["corrected"]) or len(a["noncorrected_pos"]) != len(a["noncorrected"]) or \
+            len(a["edge_i"]) != len(a["edge_j"]) or len(a["edge_i"]) != len(a["edge_kind"]) or len(a["x3Dw"]) != len(a["point_ref"]) or \
+            len(a["kf_id"]) != len(a["Tcw"]):
+        raise ValueError("OptimizeEssentialGraph: array lengths do not agree")
+    return a
+
+
+def _eg_graph_args(a, q=None):
+    q = q or _ptr_or_none
+    return [_ptr_or_none(a["kf_id"]), q(a["Tcw"]), len(a["Tcw"]), a["fixed"], q(a["corrected_pos"]), q(a["corrected"]), len(a["corrected"]),
+            q(a["noncorrected_pos"]), q(a["noncorrected"]), len(a["noncorrected"]), _ptr_or_none(a["edge_i"]), _ptr_or_none(a["edge_j"]),
+            _ptr_or_none(a["edge_kind"]), len(a["edge_i"])]
+
+
+def essential_graph_scratch_bytes(nkf, nedges, npoints, leaf_vertices=0):
+    return int(load().orbfe_essential_graph_scratch_bytes(int(nkf), int(nedges), int(npoints), int(leaf_vertices)))
+
+
+def optimize_essential_graph(pb, device=0):
+    """Optimizer::OptimizeEssentialGraph (Optimizer.cc:1245-1542, behind the collect step) on the GPU, host arrays.  pb as eg_arrays
+    takes it.  Returns dict(Tcw (nkf x 3 x 4), x3Dw, Siw (nkf x 8), result (EG_RESULT_DTYPE))."""
+    L = load()
+    a = eg_arrays(pb)
+    nkf, n = len(a["Tcw"]), len(a["x3Dw"])
+    Tout = np.zeros((nkf, 12), np.float32); Xout = np.zeros((n, 3), np.float32); Siw = np.zeros((nkf, 8)); res = np.zeros(1, EG_RESULT_DTYPE)
+    _check(L, L.orbfe_optimize_essential_graph(*(_eg_graph_args(a) + [_ptr_or_none(a["x3Dw"]), _ptr_or_none(a["point_ref"]), n, a["iterations"],
+                                                                      a["fix_scale"], a["leaf_vertices"], _p(Tout), _ptr_or_none(Xout), _p(Siw),
+                                                                      _p(res), device])), "orbfe_optimize_essential_graph")
+    return dict(Tcw=Tout.reshape(-1, 3, 4), x3Dw=Xout, Siw=Siw, result=res[0])
+
+
+def optimize_essential_graph_device(pb, d, stream=0):
+    """orbfe_optimize_essential_graph_device: pb as eg_arrays takes it, of which the graph (kf_id, edge_i, edge_j, edge_kind) and the
+    sizes are read; d maps the d_ argument names of include/orbfe.h without their prefix (Tcw, corrected_pos, corrected,
+    noncorrected_pos, noncorrected, x3Dw, point_ref, Tcw_out, x3Dw_out, Siw_out, res, scratch) to device addresses (0 / missing = NULL)
+    and scratch_bytes to a size.  Asynchronous on `stream`."""
+    L = load()
+    a = eg_arrays(pb)
+    g = lambda k: d.get(k) or None
+    _check(L, L.orbfe_optimize_essential_graph_device(
+        _ptr_or_none(a["kf_id"]), g("Tcw"), len(a["Tcw"]), a["fixed"], g("corrected_pos"), g("corrected"), len(a["corrected"]), g("noncorrected_pos"),
+        g("noncorrected"), len(a["noncorrected"]), _ptr_or_none(a["edge_i"]), _ptr_or_none(a["edge_j"]), _ptr_or_none(a["edge_kind"]), len(a["edge_i"]),
+        g("x3Dw"), g("point_ref"), len(a["x3Dw"]), a["iterations"], a["fix_scale"], a["leaf_vertices"], g("Tcw_out"), g("x3Dw_out"), g("Siw_out"),
+        g("res"), g("scratch"), int(d.get("scratch_bytes", 0)), stream), "orbfe_optimize_essential_graph_device")
+
+
+def essential_graph_inspect(pb, device=0):
+    """orbfe_essential_graph_inspect: one linearisation and one solve at lambda0.  Returns dict(err (ne x 7), Ji, Jj (ne x 7 x 7), Hd
+    (nkf x 7 x 7), b (nkf x 7), chi2, lambda0, solved, x (nkf x 7), nlevels, node_of, order_of (nkf), parent, level, nown, nb (per node))."""
+    L = load()
+    a = eg_arrays(pb)
+    nkf, ne = len(a["Tcw"]), len(a["edge_i"])
+    err = np.zeros((ne, 7)); Ji = np.zeros((ne, 7, 7)); Jj = np.zeros((ne, 7, 7)); Hd = np.zeros((nkf, 7, 7)); b = np.zeros((nkf, 7))
+    chi2 = np.zeros(3); x = np.zeros((nkf, 7)); tree = np.zeros(10 * nkf + 10, np.int32)
+    _check(L, L.orbfe_essential_graph_inspect(*(_eg_graph_args(a) + [a["fix_scale"], a["leaf_vertices"], _p(err), _p(Ji), _p(Jj), _p(Hd), _p(b),
+                                                                     _p(chi2), _p(x), _p(tree), device])), "orbfe_essential_graph_inspect")
+    nn = int(tree[0])
+    nodes = tree[2 + 2 * nkf:2 + 2 * nkf + 4 * nn].reshape(nn, 4)
+    return dict(err=err, Ji=Ji, Jj=Jj, Hd=Hd, b=b, chi2=chi2[0], lambda0=chi2[1], solved=bool(chi2[2]), x=x, nlevels=int(tree[1]),
+                node_of=tree[2:2 + nkf].copy(), order_of=tree[2 + nkf:2 + 2 * nkf].copy(), parent=nodes[:, 0].copy(), level=nodes[:, 1].copy(),
+                nown=nodes[:, 2].copy(), nb=nodes[:, 3].copy())

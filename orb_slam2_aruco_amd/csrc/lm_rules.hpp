@@ -40,6 +40,18 @@ ORBFE_HD void lm_linearised(LmState& c, double chi, bool first, double maxdiag)
     c.q = 0;
 }
 
+// the same behind setUserLambdaInit(user_lambda): computeLambdaInit returns the user's value instead of 1e-5 max |H_jj|
+// (essential_graph.hip: 1e-16)
+ORBFE_HD void lm_linearised_user(LmState& c, double chi, bool first, double user_lambda)
+{
+    lm_linearised(c, chi, false, 0.);
+    if (first) {
+        c.lambda = user_lambda;
+        c.ni = 2;
+        c.nbad_lm = 0;
+    }
+}
+
 // A trial with robust chi2 tempChi; solved: the damped system was positive; scale = sum x (lambda x + b) over every update, to
 // which g2o's 1e-3 is added here, last.  Returns whether the trial is accepted; the caller restores its estimate when it is not.
 ORBFE_HD bool lm_judge_trial(LmState& c, double tempChi, bool solved, double scale)

@@ -24,6 +24,7 @@
 #include "lm_dense.hpp"
 #include "orbfe_common.hpp"
 #include "ransac_sets.hpp"   // clampn
+#include "sim3_group.hpp"
 #include "sim3_points.hpp"
 #include <cfloat>
 #include <cmath>
@@ -34,97 +35,6 @@ namespace {
 constexpr int SO_MAX_LEVELS = 32;
 constexpr int SO_NSUM = lm_nsum<7>;   // 36: robust chi2, H upper triangle (28), b (7)
 constexpr int SO_SIM_FLOATS = 13;   // s12, R12 row-major, t12
-
-// ------------------------------------------------------------------------------------------ g2o::Sim3 --
-struct Sim3 {
-    Quat q;       // not normalised: Sim3's product and constructors never do
-    double t[3];
-    double s;
-};
-
-__device__ __forceinline__ Sim3 mul(const Sim3& a, const Sim3& b)
-{
-    Sim3 r;
-    double qt[3];
-    r.q = qmul(a.q, b.q);
-    rotate(a.q, b.t, qt);
-    for (int i = 0; i < 3; i++) r.t[i] = a.s * qt[i] + a.t[i];
-    r.s = a.s * b.s;
-    return r;
-}
-
-__device__ __forceinline__ void map(const Sim3& S, const double (&p)[3], double (&r)[3])
-{
-    double qp[3];
-    rotate(S.q, p, qp);
-    for (int i = 0; i < 3; i++) r[i] = S.s * qp[i] + S.t[i];
-}
-
-__device__ __forceinline__ Sim3 inverse(const Sim3& S)
-{
-    Sim3 r;
-    r.q = Quat{-S.q.x, -S.q.y, -S.q.z, S.q.w};
-    const double c = -1. / S.s;
-    const double v[3] = {c * S.t[0], c * S.t[1], c * S.t[2]};
-    rotate(r.q, v, r.t);
-    r.s = 1. / S.s;
-    return r;
-}
-
-// Sim3(const Vector7d&): omega, upsilon, sigma.  Below eps = 1e-5 the rotation is I + Omega + Omega^2 (not orthonormal) and the
-// quaternion made of it is not normalised.
-__device__ __noinline__ Sim3 sim3_exp(const double (&u)[7])
-{
-    const double om0 = u[0], om1 = u[1], om2 = u[2], sigma = u[6];
-    const double theta = sqrt(om0 * om0 + om1 * om1 + om2 * om2);
-    const double O[3][3] = {{0, -om2, om1}, {om2, 0, -om0}, {-om1, om0, 0}};
-    double O2[3][3], R[3][3];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) O2[i][j] = O[i][0] * O[0][j] + O[i][1] * O[1][j] + O[i][2] * O[2][j];
-    Sim3 S;
-    S.s = exp(sigma);
-    const double eps = 0.00001;
-    double A, B, C;
-    if (theta < eps) {
-        for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 3; j++) R[i][j] = ((i == j ? 1.0 : 0.0) + O[i][j]) + O2[i][j];
-    } else {
-        const double a = sin(theta) / theta, b = (1 - cos(theta)) / (theta * theta);
-        for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 3; j++) R[i][j] = ((i == j ? 1.0 : 0.0) + a * O[i][j]) + b * O2[i][j];
-    }
-    if (fabs(sigma) < eps) {
-        C = 1;
-        if (theta < eps) {
-            A = 1. / 2.;
-            B = 1. / 6.;
-        } else {
-            const double theta2 = theta * theta;
-            A = (1 - cos(theta)) / theta2;
-            B = (theta - sin(theta)) / (theta2 * theta);
-        }
-    } else {
-        C = (S.s - 1) / sigma;
-        if (theta < eps) {
-            const double sigma2 = sigma * sigma;
-            A = ((sigma - 1) * S.s + 1) / sigma2;
-            B = ((0.5 * sigma2 - sigma + 1) * S.s) / (sigma2 * sigma);
-        } else {
-            const double a = S.s * sin(theta), b = S.s * cos(theta);
-            const double theta2 = theta * theta, sigma2 = sigma * sigma;
-            const double c = theta2 + sigma2;
-            A = (a * sigma + (1 - b) * theta) / (theta * c);
-            B = (C - ((b - 1) * sigma + a * theta) / c) * 1. / theta2;
-        }
-    }
-    S.q = quat_from_matrix(R);
-    for (int i = 0; i < 3; i++) {
-        double W[3];
-        for (int j = 0; j < 3; j++) W[j] = (A * O[i][j] + B * O2[i][j]) + C * (i == j ? 1.0 : 0.0);
-        S.t[i] = W[0] * u[3] + W[1] * u[4] + W[2] * u[5];
-    }
-    return S;
-}
 
 // EdgeSim3ProjectXYZ / EdgeInverseSim3ProjectXYZ::computeError with S or its inverse: obs - cam_map(project(S.map(P)))
 __device__ __forceinline__ void edge_error(const Sim3& S, const double (&P)[3], double ox, double oy, const Cam& K, double (&err)[2])

@@ -1,0 +1,97 @@
+// TEST INFRASTRUCTURE ONLY -- ORB_SLAM2::KeyFrame of tests/mock_orbslam/ with what include/shims/Optimizer_essential_orbfe.cc touches
+// on top (include/KeyFrame.h of the reference): SetPose, the spanning tree, the loop edges, the covisibility weights, and the
+// markers by id.  A superset, so that every shim of the one-program driver compiles against it; this directory goes ahead of
+// tests/mock_orbslam/ on the include path.
+#ifndef MOCK_KEYFRAME_H
+#define MOCK_KEYFRAME_H
+#include <map>
+#include <set>
+#include <unordered_map>
+#include <vector>
+#include <opencv2/core/core.hpp>
+#include "Thirdparty/DBoW2/DBoW2/BowVector.h"
+#include "Thirdparty/DBoW2/DBoW2/FeatureVector.h"
+#include "MapPoint.h"
+#include "MapAruco.h"
+namespace ORB_SLAM2 {
+class KeyFrame {
+public:
+    // ORBmatcher, Sim3Solver, OptimizeSim3: undistorted keypoints, the pose (3 x 3, 3 x 1) and the map points by feature index
+    std::vector<cv::KeyPoint> mvKeys, mvKeysUn;
+    cv::Mat Rcw, tcw;
+    std::vector<MapPoint*> mvpMapPoints;
+    cv::Mat GetRotation() { return Rcw.clone(); }
+    cv::Mat GetTranslation() { return tcw.clone(); }
+    std::vector<MapPoint*> GetMapPointMatches() { return mvpMapPoints; }
+    // Sim3Solver, OptimizeSim3: the calibration matrix, 3 x 3 CV_32F
+    cv::Mat mK;
+    // ORBmatcher and Sim3Solver read mvLevelSigma2, ORBmatcher and OptimizeSim3 mvInvLevelSigma2
+    std::vector<float> mvLevelSigma2, mvInvLevelSigma2;
+    // ORBmatcher: descriptors, FeatureVector, intrinsics, image bounds, scale pyramid, camera centre, map bookkeeping
+    int N = 0;
+    cv::Mat mDescriptors;
+    DBoW2::FeatureVector mFeatVec;
+    float fx = 0, fy = 0, cx = 0, cy = 0;
+    int mnMinX = 0, mnMinY = 0, mnMaxX = 0, mnMaxY = 0;
+    int mnScaleLevels = 8;
+    float mfScaleFactor = 1.2f, mfLogScaleFactor = 0;
+    std::vector<float> mvScaleFactors;
+    cv::Mat Ow;
+    cv::Mat GetCameraCenter() { return Ow.clone(); }
+    std::set<MapPoint*> GetMapPoints() { std::set<MapPoint*> s; for (MapPoint* p : mvpMapPoints) if (p && !p->isBad()) s.insert(p); return s; }
+    MapPoint* GetMapPoint(const size_t& idx) { return mvpMapPoints[idx]; }
+    void AddMapPoint(MapPoint* pMP, const size_t& idx) { mvpMapPoints[idx] = pMP; }
+    // KeyFrameDatabase: the id, the BowVector, the six query fields (written by the reference's class only), and the covisibility
+    // graph as the test sets it
+    long unsigned int mnId = 0;
+    DBoW2::BowVector mBowVec;
+    long unsigned int mnLoopQuery = 0;
+    int mnLoopWords = 0;
+    float mLoopScore = 0;
+    long unsigned int mnRelocQuery = 0;
+    int mnRelocWords = 0;
+    float mRelocScore = 0;
+    bool mbBad = false;
+    std::vector<KeyFrame*> mvpOrderedConnectedKeyFrames;   // by weight, best first
+    std::set<KeyFrame*> GetConnectedKeyFrames() { return std::set<KeyFrame*>(mvpOrderedConnectedKeyFrames.begin(), mvpOrderedConnectedKeyFrames.end()); }
+    std::vector<KeyFrame*> GetVectorCovisibleKeyFrames() { return mvpOrderedConnectedKeyFrames; }
+    std::vector<KeyFrame*> GetBestCovisibilityKeyFrames(const int& N)
+    {
+        if ((int)mvpOrderedConnectedKeyFrames.size() < N) return mvpOrderedConnectedKeyFrames;
+        return std::vector<KeyFrame*>(mvpOrderedConnectedKeyFrames.begin(), mvpOrderedConnectedKeyFrames.begin() + N);
+    }
+    // OptimizeEssentialGraph: the pose setter (Rcw, tcw and the centre follow), the spanning tree, the loop edges, the weights
+    int nSetPose = 0;
+    void SetPose(const cv::Mat& Tcw_)
+    {
+        Rcw = Tcw_.rowRange(0, 3).colRange(0, 3);
+        tcw = Tcw_.rowRange(0, 3).col(3);
+        Ow = cv::Mat(3, 1, CV_32F);
+        for (int r = 0; r < 3; r++) {
+            float s = 0;
+            for (int c = 0; c < 3; c++) s -= Rcw.at<float>(c, r) * tcw.at<float>(c);
+            Ow.at<float>(r) = s;
+        }
+        nSetPose++;
+    }
+    KeyFrame* mpParent = nullptr;
+    std::set<KeyFrame*> mspChildrens, mspLoopEdges;
+    std::map<KeyFrame*, int> mConnectedKeyFrameWeights;
+    KeyFrame* GetParent() { return mpParent; }
+    bool hasChild(KeyFrame* pKF) { return mspChildrens.count(pKF) != 0; }
+    std::set<KeyFrame*> GetLoopEdges() { return mspLoopEdges; }
+    int GetWeight(KeyFrame* pKF) { return mConnectedKeyFrameWeights.count(pKF) ? mConnectedKeyFrameWeights[pKF] : 0; }
+    std::vector<KeyFrame*> GetCovisiblesByWeight(const int& w)   // mvpOrderedConnectedKeyFrames is by weight, best first
+    {
+        std::vector<KeyFrame*> v;
+        for (KeyFrame* p : mvpOrderedConnectedKeyFrames)
+            if (GetWeight(p) >= w) v.push_back(p);
+        return v;
+    }
+    std::unordered_map<int, int> mmArucoIdandIdx;
+    std::vector<MapAruco*> mvpMapArucos;
+    MapAruco* GetMapAruco(size_t i) { return mvpMapArucos[i]; }
+    bool isBad() { return mbBad; }
+};
+}
+#endif
