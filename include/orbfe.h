@@ -962,7 +962,8 @@ int orbfe_new_points_inspect(const orbfe_keypoint* kps1, int n1, const float* Tc
  * Scaling: the (keyframe, point) -> edge index is a dense table of nkf x np ints in the scratch (nkf x np < 2^30, ORBFE_ERR_INVALID
  * beyond; orbfe_lba_scratch_bytes says what that costs: 0.5 MB of its 18 MB at 40 keyframes x 3 000 points), and the kernels that
  * build a pose block or a block of the reduced system walk all np points once per block, whatever the number of observations.
- * That is sized for local mapping (tens of keyframes, thousands of points); a map-sized problem wants a CSR by keyframe instead. */
+ * That is sized for local mapping (tens of keyframes, thousands of points); a map-sized problem is orbfe_global_bundle_adjustment's (lists by
+ * vertex and by covisible pair, a block-sparse reduced system). */
 #define ORBFE_LBA_MAX_FREE_POSES 64
 #define ORBFE_LBA_MAX_OBSERVATIONS 256
 #define ORBFE_LBA_STOPPED 1
@@ -1078,6 +1079,105 @@ int orbfe_essential_graph_inspect(const int32_t* kf_id, const float* Tcw, int nk
                                   const int32_t* edge_i, const int32_t* edge_j, const int32_t* edge_kind, int ne, int fix_scale,
                                   int leaf_vertices, double* err, double* Ji, double* Jj, double* Hd, double* b, double* chi2, double* x,
                                   int32_t* tree, int device);
+
+/* ------------------------------------------------------------ GlobalBundleAdjustment (map-wide BA, sparse Schur) -- */
+/* Optimizer::BundleAdjustment (src/Optimizer.cc:49-307; GlobalBundleAdjustemnt above it collects the whole map and calls it) behind
+ * its collect step: ONE optimize(iterations) of g2o's Levenberg-Marquardt with BlockSolver_6_3 over keyframes, map points and this
+ * fork's marker poses, in double.  The reference calls it from Tracking::CreateInitialMapMonocular (20 iterations, robust, two
+ * keyframes) and from LoopClosing::RunGlobalBundleAdjustment (10 iterations, not robust), the step behind
+ * orbfe_optimize_essential_graph.  Flat arrays laid out as orbfe_local_bundle_adjustment's, nothing pointer-shaped:
+ *   keyframes   Tcw[nkf][12] (IN / OUT) and kf_fixed[nkf] (the shim sets it for mnId == 0).  Any number of fixed keyframes is legal,
+ *               none included: keyframe 0 may be bad and left out
+ *   points      x3Dw[np][3] (IN / OUT) with their observations in CSR by point (obs_offset, obs_kf and obs_xy / obs_octave, or -- the
+ *               device call only -- obs_feature into d_kps blocks of `capacity` keypoints a keyframe), in GetObservations() order
+ *   markers     Twm[nma][12] (IN / OUT), marker_local, mobs_offset, mobs_kf, mobs_corners, marker_info (the reference's wei = 25)
+ *               and use_markers (Frame::mbUArucoIni), as in orbfe_local_bundle_adjustment
+ *   camera      K4, inv_level_sigma2[nlevels], nlevels <= 32
+ *   options     iterations (1 .. 20), robust (bRobust), stop (pbStopFlag, may be NULL), leaf_vertices (the elimination plan's leaf
+ *               size, 0 = default, as in orbfe_optimize_essential_graph)
+ * What differs from the local bundle adjustment, from the reference's lines:
+ *   - one round: no levels, no chi2 checks, no erase list; the output is the estimates and the record;
+ *   - robust != 0 puts Huber on every monocular edge with delta = (double)(float)sqrt(5.99) (5.99 here, :91, not 5.991);
+ *   - the four EdgeMarker edges of a marker observation always carry Huber with that delta, whatever robust says (:218-220); their
+ *     Jacobians are g2o's numeric ones;
+ *   - a point without observations is no vertex (:157-161): its x3Dw is not written, and it counts in n_points_left_out.
+ * As there: a free keyframe or marker without an edge is not part of the system and keeps its bits (a deviation: g2o would solve a
+ * block that holds lambda alone and leave the estimate where it is, rounded through the quaternion); LM as g2o runs it
+ * (lambda0 = 1e-5 x the largest diagonal entry over pose and point blocks, up to 10 trials an iteration, rho, the stop rules, a
+ * failed solve as a trial with chi2 = DBL_MAX); an edge whose error or Jacobian is not finite adds nothing to H and b in that pass
+ * while its chi2 still enters the sum, so the trial is rejected.
+ *
+ * The solve.  Lists index the blocks, not a dense (keyframe, point) table: the edges of every vertex, and the covisible pairs of
+ * free vertices -- joined by a point or by a marker edge -- each with its items.  The reduced camera system S = Hpp - sum W D^-1 W^T
+ * has one 6 x 6 block per covisible pair and is kept that way; it is factored L L^T without pivoting along the elimination tree of a
+ * nested dissection on the caller's keyframe order (the essential graph's plan, 6 rows a vertex), one workgroup per front, with the
+ * markers as own vertices of the root so that a marker seen along the whole trajectory pulls no keyframe into a separator.  No
+ * kernel's work grows with nkf x np.  Every sum has an order fixed by the plan (no floating-point atomics): the host call, the device
+ * call and a repeat give equal bits.
+ *
+ * stop: read at the call -- nonzero returns ORBFE_OK with status ORBFE_GBA_STOPPED and nothing else written -- and, by the device
+ * call, at every iteration and trial (d_stop must then stay readable by the device): a set flag ends the optimize() and the
+ * estimates of the last accepted trial are written.  The choice between SetPose and mTcwGBA / mPosGBA / mnBAGlobalForKF (nLoopKF,
+ * :251-285) and MapPoint::UpdateNormalAndDepth are the shim's.
+ *
+ * ORBFE_ERR_CAPACITY: nkf + nma above ORBFE_GBA_MAX_POSES (checked by the sizes alone), a point with more than
+ * ORBFE_GBA_MAX_OBSERVATIONS observations (the per-point kernels need no bound; the one on the pair items of the device call's
+ * scratch, sized from the sizes alone, does), a scratch smaller than orbfe_gba_scratch_bytes says, or a covisibility graph whose
+ * fronts need more than GBA_FRONT_BUDGET = 768 MB of scratch.  ORBFE_ERR_INVALID: the cases of orbfe_local_bundle_adjustment, and
+ * iterations outside [1, 20].  The host call returns all of these; the device call returns what the host can see (the sizes, the
+ * graph, the plan) and writes what only the device can check (values that are not finite, an octave or feature out of range) to
+ * d_res->status, and then writes nothing else.  A refused call writes nothing. */
+#define ORBFE_GBA_MAX_POSES 4096          /* keyframes plus markers: the value of ORBFE_EG_MAX_KEYFRAMES */
+#define ORBFE_GBA_MAX_OBSERVATIONS 256    /* observations of one point: the value of ORBFE_LBA_MAX_OBSERVATIONS */
+#define ORBFE_GBA_STOPPED 1
+
+typedef struct orbfe_gba_result {
+    int32_t status;             /* ORBFE_OK, ORBFE_GBA_STOPPED, or the device call's ORBFE_ERR_INVALID (see above) */
+    int32_t iterations;         /* DIAGNOSTIC: LM iterations run */
+    int32_t trials;             /* DIAGNOSTIC: LM trials run over all iterations */
+    int32_t n_edges_mono;       /* EdgeSE3ProjectXYZ edges = observation slots */
+    int32_t n_edges_marker;     /* EdgeMarker edges: 4 x marker observations (0 without use_markers) */
+    int32_t n_points_left_out;  /* points without observations: no vertex, not written */
+    double chi2_first, chi2_last, lambda_last;   /* the robust chi2 of the first linearisation and of the last accepted estimate */
+} orbfe_gba_result;
+
+/* bytes of device scratch orbfe_global_bundle_adjustment_device needs for a problem of these sizes, whatever its graph; 0: sizes out
+ * of range */
+size_t orbfe_gba_scratch_bytes(int nkf, int np, int nobs, int nma, int nmobs, int leaf_vertices);
+
+/* host pointers, one call, synchronous */
+int orbfe_global_bundle_adjustment(float* Tcw, const uint8_t* kf_fixed, int nkf, float* x3Dw, int np, const int32_t* obs_offset,
+                                   const int32_t* obs_kf, const float* obs_xy, const int32_t* obs_octave, int nobs, const float* K4,
+                                   const float* inv_level_sigma2, int nlevels, float* Twm, const float* marker_local, int nma,
+                                   const int32_t* mobs_offset, const int32_t* mobs_kf, const float* mobs_corners, int nmobs, float marker_info,
+                                   int use_markers, int iterations, int robust, const uint8_t* stop, int leaf_vertices, orbfe_gba_result* res,
+                                   int device);
+
+/* The values on the device (d_*), the graph -- kf_fixed, obs_offset, obs_kf, mobs_offset, mobs_kf -- on the host: the pair lists and
+ * the elimination plan are made from it before anything is enqueued (K4 and inv_level_sigma2 are host arrays read at the call).
+ * Everything runs on `stream` with no host synchronisation (a second call on one stream waits, on the host, until the first one's
+ * tables have left their staging block); the worst case of iterations x 10 trials is enqueued and decided steps fall through.
+ * d_scratch: scratch_bytes >= orbfe_gba_scratch_bytes(...) bytes, 256-byte aligned. */
+int orbfe_global_bundle_adjustment_device(float* d_Tcw, const uint8_t* kf_fixed, int nkf, float* d_x3Dw, int np, const int32_t* obs_offset,
+                                          const int32_t* obs_kf, const float* d_obs_xy, const int32_t* d_obs_octave,
+                                          const int32_t* d_obs_feature, const orbfe_keypoint* d_kps, int capacity, int nobs, const float* K4,
+                                          const float* inv_level_sigma2, int nlevels, float* d_Twm, const float* d_marker_local, int nma,
+                                          const int32_t* mobs_offset, const int32_t* mobs_kf, const float* d_mobs_corners, int nmobs,
+                                          float marker_info, int use_markers, int iterations, int robust, const uint8_t* d_stop,
+                                          int leaf_vertices, orbfe_gba_result* d_res, void* d_scratch, size_t scratch_bytes, void* stream);
+
+/* DIAGNOSTIC / TEST INTERFACE, no stability promise: one linearisation at the given estimates and the first LM trial.  Host pointers;
+ * nothing of the problem is written.  *nv = free pose vertices (free keyframes in order, then the markers); b (6 nv, then 3 np), Hpp
+ * (nv x 36, the diagonal blocks row-major), Hll (np x 6: the upper triangle xx xy xz yy yz zz), chi2 (the robust chi2, lambda0, 1
+ * when every pivot was positive), x (6 nv, then 3 np: the first trial's update), tree (2 + 2 nv + 4 nodes entries, at most
+ * 10 (nkf + nma) + 10: nodes, levels; node and place in the elimination order of every free vertex; parent, level, own and boundary
+ * vertices of every node).  Arrays sized for nkf + nma vertices. */
+int orbfe_gba_inspect(const float* Tcw, const uint8_t* kf_fixed, int nkf, const float* x3Dw, int np, const int32_t* obs_offset,
+                      const int32_t* obs_kf, const float* obs_xy, const int32_t* obs_octave, int nobs, const float* K4,
+                      const float* inv_level_sigma2, int nlevels, const float* Twm, const float* marker_local, int nma,
+                      const int32_t* mobs_offset, const int32_t* mobs_kf, const float* mobs_corners, int nmobs, float marker_info,
+                      int use_markers, int robust, int leaf_vertices, int32_t* nv, double* b, double* Hpp, double* Hll, double* chi2, double* x,
+                      int32_t* tree, int device);
 
 /* ------------------------------------------------------------ KeyFrameDatabase: candidate queries -- */
 /* KeyFrameDatabase::DetectLoopCandidates(pKF, minScore) (src/KeyFrameDatabase.cc:76-197, called by LoopClosing::DetectLoop) and

@@ -74,6 +74,8 @@ SYMBOLS = [
     # OptimizeEssentialGraph of loop closing (csrc/essential_graph.hip)
     "orbfe_essential_graph_scratch_bytes", "orbfe_optimize_essential_graph", "orbfe_optimize_essential_graph_device",
     "orbfe_essential_graph_inspect",
+    # GlobalBundleAdjustment: the map-wide BA of the initial map and of loop closing (csrc/global_ba.hip)
+    "orbfe_gba_scratch_bytes", "orbfe_global_bundle_adjustment", "orbfe_global_bundle_adjustment_device", "orbfe_gba_inspect",
 ]
 
 _lib = None
@@ -247,6 +249,14 @@ def load():
         L.orbfe_essential_graph_inspect.argtypes = egp + [i32, i32] + [vp] * 8 + [i32]
         L.orbfe_local_bundle_adjustment_device.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp,
                                                            i32, f32, i32, vp, vp, vp, vp, sz, vp]
+    if hasattr(L, "orbfe_global_bundle_adjustment"):
+        prob = [vp, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, i32, f32, i32]
+        L.orbfe_gba_scratch_bytes.argtypes = [i32] * 6
+        L.orbfe_gba_scratch_bytes.restype = sz
+        L.orbfe_global_bundle_adjustment.argtypes = prob + [i32, i32, vp, i32, vp, i32]
+        L.orbfe_gba_inspect.argtypes = prob + [i32, i32] + [vp] * 7 + [i32]
+        L.orbfe_global_bundle_adjustment_device.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp,
+                                                            i32, f32, i32, i32, i32, vp, i32, vp, vp, sz, vp]
     if hasattr(L, "orbfe_initialize"):
         L.orbfe_initialize.argtypes = [vp, i32, vp, i32, vp, vp, f32, i32, vp, vp, vp, vp, i32]
         L.orbfe_initialize_inspect.argtypes = [vp, i32, vp, i32, vp, vp, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
@@ -1760,3 +1770,74 @@ def essential_graph_inspect(pb, device=0):
     return dict(err=err, Ji=Ji, Jj=Jj, Hd=Hd, b=b, chi2=chi2[0], lambda0=chi2[1], solved=bool(chi2[2]), x=x, nlevels=int(tree[1]),
                 node_of=tree[2:2 + nkf].copy(), order_of=tree[2 + nkf:2 + 2 * nkf].copy(), parent=nodes[:, 0].copy(), level=nodes[:, 1].copy(),
                 nown=nodes[:, 2].copy(), nb=nodes[:, 3].copy())
+
+
+# ------------------------------------------------------------------------------- GlobalBundleAdjustment (map-wide BA) ----
+GBA_MAX_POSES, GBA_MAX_OBSERVATIONS, GBA_STOPPED = 4096, 256, 1
+GBA_RESULT_DTYPE = np.dtype([("status", "<i4"), ("iterations", "<i4"), ("trials", "<i4"), ("n_edges_mono", "<i4"), ("n_edges_marker", "<i4"),
+                             ("n_points_left_out", "<i4"), ("chi2_first", "<f8"), ("chi2_last", "<f8"), ("lambda_last", "<f8")])
+assert GBA_RESULT_DTYPE.itemsize == 48
+
+
+def gba_arrays(pb):
+    """The flat arrays of a GlobalBundleAdjustment problem: lba_arrays(pb) plus the options iterations (10), robust (0) and
+    leaf_vertices (0)."""
+    a = lba_arrays(pb)
+    a["iterations"] = int(pb.get("iterations", 10))
+    a["robust"] = int(pb.get("robust", 0))
+    a["leaf_vertices"] = int(pb.get("leaf_vertices", 0))
+    return a
+
+
+def gba_scratch_bytes(nkf, np_, nobs, nma, nmobs, leaf_vertices=0):
+    return int(load().orbfe_gba_scratch_bytes(int(nkf), int(np_), int(nobs), int(nma), int(nmobs), int(leaf_vertices)))
+
+
+def global_bundle_adjustment(pb, stop=False, device=0):
+    """Optimizer::BundleAdjustment (Optimizer.cc:49-307, behind the collect step) on the GPU, host arrays.  pb as gba_arrays takes it;
+    stop = the value of *pbStopFlag at the call.  Returns dict(Tcw (nkf x 3 x 4), x3Dw, Twm, result (GBA_RESULT_DTYPE)); the inputs
+    are not modified."""
+    L = load()
+    a = gba_arrays(pb)
+    res = np.zeros(1, GBA_RESULT_DTYPE)
+    flag = np.array([1 if stop else 0], np.uint8)
+    _check(L, L.orbfe_global_bundle_adjustment(*(_lba_problem_args(a) + [a["iterations"], a["robust"], _p(flag), a["leaf_vertices"], _p(res), device])),
+           "orbfe_global_bundle_adjustment")
+    return dict(Tcw=a["Tcw"].reshape(-1, 3, 4), x3Dw=a["x3Dw"], Twm=a["Twm"].reshape(-1, 3, 4), result=res[0])
+
+
+def global_bundle_adjustment_device(pb, d, capacity=0, stream=0):
+    """orbfe_global_bundle_adjustment_device: pb as gba_arrays takes it, of which the graph (kf_fixed, obs_offset, obs_kf, mobs_offset,
+    mobs_kf), the camera, the options and the sizes are read; d maps the d_ argument names of include/orbfe.h without their prefix
+    (Tcw, x3Dw, obs_xy, obs_octave, obs_feature, kps, Twm, marker_local, mobs_corners, stop, res, scratch) to device addresses
+    (0 / missing = NULL) and scratch_bytes to a size.  Asynchronous on `stream`."""
+    L = load()
+    a = gba_arrays(pb)
+    g = lambda k: d.get(k) or None
+    q = _ptr_or_none
+    _check(L, L.orbfe_global_bundle_adjustment_device(
+        g("Tcw"), q(a["kf_fixed"]), len(a["Tcw"]), g("x3Dw"), len(a["x3Dw"]), q(a["obs_offset"]), q(a["obs_kf"]), g("obs_xy"), g("obs_octave"),
+        g("obs_feature"), g("kps"), int(capacity), len(a["obs_kf"]), _p(a["K4"]), q(a["inv_level_sigma2"]), len(a["inv_level_sigma2"]), g("Twm"),
+        g("marker_local"), len(a["Twm"]), q(a["mobs_offset"]), q(a["mobs_kf"]), g("mobs_corners"), len(a["mobs_kf"]), a["marker_info"], a["use_markers"],
+        a["iterations"], a["robust"], g("stop"), a["leaf_vertices"], g("res"), g("scratch"), int(d.get("scratch_bytes", 0)), stream),
+        "orbfe_global_bundle_adjustment_device")
+
+
+def gba_inspect(pb, device=0):
+    """orbfe_gba_inspect: one linearisation and the first trial.  Returns dict(nv, b_pose (nv x 6), b_point (np x 3), Hpp (nv x 6 x 6),
+    Hll (np x 6: xx xy xz yy yz zz), chi2, lambda0, solved, x_pose (nv x 6), x_point (np x 3), nlevels, node_of, order_of (nv), parent,
+    level, nown, nb (per node))."""
+    L = load()
+    a = gba_arrays(pb)
+    n, V = len(a["x3Dw"]), len(a["Tcw"]) + len(a["Twm"])
+    nv = np.zeros(1, np.int32)
+    b = np.zeros(6 * V + 3 * n + 1); x = np.zeros_like(b)
+    Hpp = np.zeros((max(V, 1), 6, 6)); Hll = np.zeros((max(n, 1), 6)); chi2 = np.zeros(3); tree = np.zeros(10 * V + 10, np.int32)
+    _check(L, L.orbfe_gba_inspect(*(_lba_problem_args(a) + [a["robust"], a["leaf_vertices"], _p(nv), _p(b), _p(Hpp), _p(Hll), _p(chi2), _p(x), _p(tree),
+                                                          device])), "orbfe_gba_inspect")
+    v, nn = int(nv[0]), int(tree[0])
+    nodes = tree[2 + 2 * v:2 + 2 * v + 4 * nn].reshape(nn, 4)
+    return dict(nv=v, b_pose=b[:6 * v].reshape(v, 6), b_point=b[6 * v:6 * v + 3 * n].reshape(n, 3), Hpp=Hpp[:v], Hll=Hll[:n], chi2=chi2[0],
+                lambda0=chi2[1], solved=bool(chi2[2]), x_pose=x[:6 * v].reshape(v, 6), x_point=x[6 * v:6 * v + 3 * n].reshape(n, 3),
+                nlevels=int(tree[1]), node_of=tree[2:2 + v].copy(), order_of=tree[2 + v:2 + 2 * v].copy(), parent=nodes[:, 0].copy(),
+                level=nodes[:, 1].copy(), nown=nodes[:, 2].copy(), nb=nodes[:, 3].copy())

@@ -32,12 +32,15 @@ __attribute__((format(printf, 2, 3))) inline BaCheck ba_fail(int err, const char
 struct BaCamera {
     float fx, fy, cx, cy, marker_info;
     int nlevels;
-    double delta;                       // (double)(float)sqrt(5.991), as deltaMono reaches RobustKernelHuber::setDelta
+    double delta;                       // (double)(float)sqrt(chi2_delta), as deltaMono reaches RobustKernelHuber::setDelta
     float inv_sigma2[BA_MAX_LEVELS];    // zeros from nlevels on
 };
 
-// the sigma table's entries are not looked at: local_ba.hip refuses a non-finite one, pose_optimizer.hip takes them as they are
-inline BaCheck ba_camera(BaCamera& c, const float* K4, const float* inv_sigma2, int nlevels, float marker_info, const char* name)
+// the sigma table's entries are not looked at: local_ba.hip refuses a non-finite one, pose_optimizer.hip takes them as they are.
+// chi2_delta: the square of the Huber delta as the reference writes it (5.991 in PoseOptimization and LocalBundleAdjustment, 5.99 in
+// BundleAdjustment)
+inline BaCheck ba_camera(BaCamera& c, const float* K4, const float* inv_sigma2, int nlevels, float marker_info, const char* name,
+                         double chi2_delta = 5.991)
 {
     if (!K4 || !inv_sigma2 || nlevels <= 0 || nlevels > BA_MAX_LEVELS) return ba_fail(ORBFE_ERR_INVALID, "%s: invalid K4 / sigma table", name);
     for (int i = 0; i < 4; i++)
@@ -47,7 +50,7 @@ inline BaCheck ba_camera(BaCamera& c, const float* K4, const float* inv_sigma2, 
     c.fx = K4[0]; c.fy = K4[1]; c.cx = K4[2]; c.cy = K4[3];
     c.marker_info = marker_info;
     c.nlevels = nlevels;
-    c.delta = (double)(float)std::sqrt(5.991);
+    c.delta = (double)(float)std::sqrt(chi2_delta);
     for (int l = 0; l < BA_MAX_LEVELS; l++) c.inv_sigma2[l] = l < nlevels ? inv_sigma2[l] : 0.f;
     return BaCheck{};
 }

@@ -23,6 +23,7 @@
 // A non-positive or non-finite pivot in any front means "not solved": the trial is judged with chi2 = DBL_MAX and the update of the
 // last solved trial stays, as g2o's does.
 #include "essential_plan.hpp"
+#include "front_solve.hpp"
 #include "host_stage.hpp"
 #include "lm_dense.hpp"
 #include "orbfe_common.hpp"
@@ -263,59 +264,7 @@ __global__ __launch_bounds__(LM_THREADS) void k_eg_ctl_lin(EgP p)
 }
 
 // ---------------------------------------------------------------------------------------- a trial --
-// The first k columns of M = L L^T in place (lower triangle, right-looking, no pivoting) with the trailing update carried over all n
-// rows, which leaves the Schur complement of the last n - k; r, the right-hand side, is one more column: r[0, k) becomes L11^-1 r and
-// r[k, n) what the parent adds.  PACKED: M is the lower triangle row after row (the LDS copy), else rows of n.  Returns whether every
-// pivot was positive.
-template <bool PACKED> __device__ __forceinline__ bool eg_partial_llt(double* M, int n, int k, double* r, int* fail_s)
-{
-    const int tid = threadIdx.x;
-    auto row = [n](int i) { return PACKED ? (size_t)i * (i + 1) / 2 : (size_t)i * n; };
-    for (int kk = 0; kk < k; kk++) {
-        if (tid == 0) {
-            const double d = M[row(kk) + kk];
-            if (!(d > 0) || !isfinite(d)) *fail_s = 1;
-            else M[row(kk) + kk] = sqrt(d);
-        }
-        __syncthreads();
-        if (*fail_s) return false;
-        const double lkk = M[row(kk) + kk];
-        for (int i = kk + 1 + tid; i < n; i += LM_THREADS) M[row(i) + kk] /= lkk;
-        if (tid == 0) r[kk] /= lkk;
-        __syncthreads();
-        const double yk = r[kk];
-        for (int i = kk + 1 + (tid >> 4); i < n; i += LM_THREADS / 16) {
-            const double lik = M[row(i) + kk];
-            for (int j = kk + 1 + (tid & 15); j <= i; j += 16) M[row(i) + j] -= lik * M[row(j) + kk];
-            if ((tid & 15) == 0) r[i] -= lik * yk;
-        }
-        __syncthreads();
-    }
-    return true;
-}
-
-// x_own of a factored front: L11^T x = y - L21^T x_boundary, the boundary's x being the ancestors'.  F holds L (rows of n), r holds
-// y in [0, k), w is the front's work vector.
-__device__ __forceinline__ void eg_substitute_back(const EgP& p, const EgNode& nd, const double* F, const double* r, double* w)
-{
-    const int tid = threadIdx.x, n = 7 * (nd.nown + nd.nb), k = 7 * nd.nown;
-    const int32_t* vtx = p.node_vtx + nd.vtx;
-    for (int i = tid; i < k; i += LM_THREADS) {
-        double s = r[i];
-        for (int j = k; j < n; j++) s -= F[(size_t)j * n + i] * p.xt[(size_t)vtx[j / 7] * 7 + j % 7];
-        w[i] = s;
-    }
-    __syncthreads();
-    for (int kk = k - 1; kk >= 0; kk--) {
-        if (tid == 0) w[kk] /= F[(size_t)kk * n + kk];
-        __syncthreads();
-        const double xk = w[kk];
-        for (int i = tid; i < kk; i += LM_THREADS) w[i] -= F[(size_t)kk * n + i] * xk;
-        __syncthreads();
-    }
-    for (int i = tid; i < k; i += LM_THREADS) p.xt[(size_t)vtx[i / 7] * 7 + i % 7] = w[i];
-}
-
+// The partial Cholesky factorisation of a front and its substitution back are front_solve.hpp's, shared with global_ba.hip.
 // the fronts of one level, a workgroup each; lds_rows: the largest front (in rows) the launch reserved LDS for
 __global__ __launch_bounds__(LM_THREADS) void k_eg_front(EgP p, int first, int lds_rows)
 {
@@ -374,19 +323,19 @@ __global__ __launch_bounds__(LM_THREADS) void k_eg_front(EgP p, int first, int l
         for (int i = 0; i < n; i++)
             for (int j = tid; j <= i; j += LM_THREADS) eg_tri[(size_t)i * (i + 1) / 2 + j] = F[(size_t)i * n + j];
         __syncthreads();
-        ok = eg_partial_llt<true>(eg_tri, n, k, r, &fail_s);
+        ok = front_partial_llt<true>(eg_tri, n, k, r, &fail_s);
         if (ok)
             for (int i = 0; i < n; i++)
                 for (int j = tid; j <= i; j += LM_THREADS) F[(size_t)i * n + j] = eg_tri[(size_t)i * (i + 1) / 2 + j];
         __syncthreads();
     } else {
-        ok = eg_partial_llt<false>(F, n, k, r, &fail_s);
+        ok = front_partial_llt<false>(F, n, k, r, &fail_s);
     }
     if (!ok) {
         if (tid == 0) atomicOr(&c.fail, 1);
         return;
     }
-    if (nd.nb == 0) eg_substitute_back(p, nd, F, r, w);
+    if (nd.nb == 0) front_substitute_back<7>(nd, p.node_vtx + nd.vtx, p.xt, F, r, w);
 }
 
 // the fronts of one level that have a boundary, top-down
@@ -398,7 +347,7 @@ __global__ __launch_bounds__(LM_THREADS) void k_eg_back(EgP p, int first)
     const int n = 7 * (nd.nown + nd.nb);
     if (nd.nb == 0 || nd.nown == 0) return;
     const double* F = p.fronts + nd.front;
-    eg_substitute_back(p, nd, F, F + (size_t)n * n, p.fronts + nd.front + (size_t)n * n + n);
+    front_substitute_back<7>(nd, p.node_vtx + nd.vtx, p.xt, F, F + (size_t)n * n, p.fronts + nd.front + (size_t)n * n + n);
 }
 
 // the trial estimates: VertexSim3Expmap::oplusImpl.  When the system was not solved the update of the last solved trial stays.

@@ -4,14 +4,8 @@
 // walk, the scratch layout and the launch schedule.  Pure host arithmetic, no HIP: tests/essential_plan_driver.cpp compiles this
 // header with g++.
 //
-// The elimination plan.  The fixed vertex is no unknown.  The free vertices keep the caller's order, which is temporal: edges are
-// short except for loop edges.  A range of them longer than leaf_vertices is split at its middle; its separator is every vertex of the
-// left half not yet in a separator that has an edge to such a vertex of the right half; both halves recurse.  A node of the tree owns
-// its separator (a leaf: what is left of its range); leaves are eliminated first, then the separators bottom-up (by level, a node's
-// level being one more than its highest child's).  Every edge joins two vertices of one node, or a vertex with one of an ancestor:
-// the separator cuts every edge that crosses the middle, whatever the graph, and a far loop edge only enlarges a separator.  A node's
-// boundary is the set of ancestor vertices that its own vertices' edges or its children's boundaries touch; its front is the dense
-// symmetric matrix over (own, boundary), 7 rows a vertex, both lists in elimination order.  Children are always (left, right).
+// The elimination plan.  The fixed vertex is no unknown.  The tree of fronts over the free vertices is front_plan.hpp's (which says
+// how it is made), with 7 rows a vertex and no vertex held back for the root; the bundle adjustment of gba_plan.hpp shares it.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -23,6 +17,7 @@
 
 #include "../../include/orbfe.h"
 #include "ba_camera.hpp"    // BaCheck, ba_fail
+#include "front_plan.hpp"   // the elimination tree and its fronts
 #include "host_stage.hpp"   // IoLayout
 #include "lm_rules.hpp"     // LmState
 
@@ -47,23 +42,9 @@ struct EgSizes {
     int nkf, ne, np, nc, nn;   // keyframes, edges, points, entries of CorrectedSim3 and of NonCorrectedSim3
 };
 
-// a node of the elimination tree, as the kernels read it
-struct EgNode {
-    long long front;        // offset in doubles: the front (n x n, row-major, lower triangle in use), its right-hand side (n), a work vector (n)
-    int parent, level, nown, nb;
-    int vtx;                // offset in node_vtx: own vertices, then the boundary; caller's positions
-    int src, nsrc;          // its blocks of the linearised system (EgSrc)
-    int child[2], cmap[2];  // left and right child (-1: none) and where each one's scatter map starts: for every boundary vertex of the
-                            // child, its index in this node's (own, boundary) list
-    int pad;
-};
-static_assert(sizeof(EgNode) == 56, "the tables' layout pins this size");
-
-struct EgSrc {
-    int id;                 // a vertex (its diagonal block and right-hand side) or a pair
-    int r, c;               // the block's place in the front, r >= c
-    int flags;              // 1: a pair; 2: the pair's block goes in transposed
-};
+// a node of the elimination tree and a block's place in its front, as the kernels read them (front_plan.hpp)
+using EgNode = FrontNode;
+using EgSrc = FrontSrc;
 
 inline int eg_leaf(int leaf_vertices) { return leaf_vertices > 0 ? leaf_vertices : EG_LEAF_DEFAULT; }
 
@@ -131,16 +112,8 @@ inline BaCheck eg_check_values(const EgSizes& n, const float* Tcw, const int32_t
 }
 
 // ---------------------------------------------------------------------------------------- the elimination plan --
-// A bound on the doubles of all fronts that holds for every graph of nfree free vertices, from the sizes alone: a node of a range of r
-// vertices under `anc` separator vertices of its ancestors has at most r + anc vertices in its front.
-inline double eg_front_bound(int r, int anc, int leaf)
-{
-    const double m = 7.0 * (r + anc);
-    const double own = m * m + 2 * m;
-    if (r <= leaf) return own;
-    const int left = r / 2;
-    return own + eg_front_bound(left, anc, leaf) + eg_front_bound(r - left, anc + left, leaf);
-}
+// A bound on the doubles of all fronts that holds for every graph of nfree free vertices, from the sizes alone (front_plan.hpp)
+inline double eg_front_bound(int r, int anc, int leaf) { return front_bound(r, anc, leaf, 7); }
 
 // doubles of the scratch set aside for fronts: the bound above where it is smaller than the budget
 inline size_t eg_front_cap(int nkf, int leaf_vertices)
@@ -150,86 +123,15 @@ inline size_t eg_front_cap(int nkf, int leaf_vertices)
     return (size_t)std::min(bound, (double)(EG_FRONT_BUDGET / 8)) + 1;
 }
 
-struct EgPlan {
+// the tree, the order, the fronts and their blocks are front_plan.hpp's (7 rows a vertex, no vertex eliminated last)
+struct EgPlan : FrontTree {
     EgSizes n{};
-    int fixed = 0, nfree = 0, leaf = 0, nlevels = 0, npairs = 0, max_rows = 0, max_level_nodes = 0;
+    int fixed = 0, nfree = 0, leaf = 0, npairs = 0;
     bool passthrough = false;               // nkf == 1 or ne == 0: the call returns its inputs
-    std::vector<int> node_of, order_of;     // per vertex, caller's positions: its node and its place in the elimination order, -1 the fixed one
-    std::vector<int> perm;                  // the free vertices in elimination order
-    std::vector<EgNode> nodes;
-    std::vector<int> node_vtx, cmap, level_off, level_nodes;
-    std::vector<EgSrc> src;
     std::vector<int> pair_u, pair_v, pair_off, pair_items;   // unique pairs of free vertices u < v; items: edge * 2 + (the edge's vertex 0 is v), edge order
     std::vector<int> vtx_off, vtx_items;                     // per vertex: edge * 2 + (the vertex is the edge's vertex 1), edge order; none for the fixed one
     size_t front_doubles = 0;
 };
-
-namespace eg_detail {
-
-struct Builder {
-    EgPlan& p;
-    const std::vector<int>& free_list;
-    const std::vector<std::vector<int>>& adj;   // over free indices
-    std::vector<char> assigned;
-    std::vector<std::vector<int>> own;          // per node, free indices
-
-    int new_node()
-    {
-        EgNode nd{};
-        nd.parent = -1;
-        nd.child[0] = nd.child[1] = -1;
-        p.nodes.push_back(nd);
-        own.emplace_back();
-        return (int)p.nodes.size() - 1;
-    }
-    // the node of the free indices [lo, hi), -1 when every one of them sits in a separator above
-    int build(int lo, int hi)
-    {
-        bool any = false;
-        for (int u = lo; u < hi && !any; u++) any = !assigned[(size_t)u];
-        if (!any) return -1;
-        if (hi - lo <= p.leaf) {
-            const int id = new_node();
-            for (int u = lo; u < hi; u++)
-                if (!assigned[(size_t)u]) {
-                    assigned[(size_t)u] = 1;
-                    own[(size_t)id].push_back(u);
-                }
-            return id;
-        }
-        const int mid = lo + (hi - lo) / 2;
-        std::vector<int> sep;
-        for (int u = lo; u < mid; u++) {
-            if (assigned[(size_t)u]) continue;
-            for (int w : adj[(size_t)u])
-                if (w >= mid && w < hi && !assigned[(size_t)w]) {
-                    sep.push_back(u);
-                    break;
-                }
-        }
-        for (int u : sep) assigned[(size_t)u] = 1;
-        const int l = build(lo, mid), r = build(mid, hi);
-        if (sep.empty() && l < 0) return r;   // a node without own vertices joins two children, or is not made
-        if (sep.empty() && r < 0) return l;
-        const int id = new_node();
-        own[(size_t)id] = sep;
-        p.nodes[(size_t)id].child[0] = l;
-        p.nodes[(size_t)id].child[1] = r;
-        if (l >= 0) p.nodes[(size_t)l].parent = id;
-        if (r >= 0) p.nodes[(size_t)r].parent = id;
-        return id;
-    }
-    int level_of(int id)
-    {
-        int lv = 0;
-        for (int k = 0; k < 2; k++)
-            if (p.nodes[(size_t)id].child[k] >= 0) lv = std::max(lv, 1 + level_of(p.nodes[(size_t)id].child[k]));
-        p.nodes[(size_t)id].level = lv;
-        return lv;
-    }
-};
-
-} // namespace eg_detail
 
 // The plan of one call.  edge_i / edge_j have passed eg_check_edges.  Returns ORBFE_ERR_CAPACITY when the fronts of this graph do not
 // fit the scratch orbfe_essential_graph_scratch_bytes sets aside for them.
@@ -262,64 +164,7 @@ inline BaCheck eg_make_plan(EgPlan& p, const EgSizes& n, int fixed, const int32_
         adj[(size_t)a].push_back(b);
         adj[(size_t)b].push_back(a);
     }
-    eg_detail::Builder B{p, free_list, adj, std::vector<char>((size_t)p.nfree, 0), {}};
-    const int root = B.build(0, p.nfree);
-    const int nnodes = (int)p.nodes.size();
-    if (root >= 0) p.nlevels = B.level_of(root) + 1;
-
-    // levels, the elimination order
-    p.level_off.assign((size_t)p.nlevels + 1, 0);
-    for (const EgNode& nd : p.nodes) p.level_off[(size_t)nd.level + 1]++;
-    for (int l = 0; l < p.nlevels; l++) {
-        p.max_level_nodes = std::max(p.max_level_nodes, p.level_off[(size_t)l + 1]);
-        p.level_off[(size_t)l + 1] += p.level_off[(size_t)l];
-    }
-    p.level_nodes.assign((size_t)nnodes, 0);
-    {
-        std::vector<int> at(p.level_off.begin(), p.level_off.end() - 1);
-        for (int id = 0; id < nnodes; id++) p.level_nodes[(size_t)at[(size_t)p.nodes[(size_t)id].level]++] = id;
-    }
-    for (int id : p.level_nodes)
-        for (int u : B.own[(size_t)id]) {
-            const int v = free_list[(size_t)u];
-            p.node_of[(size_t)v] = id;
-            p.order_of[(size_t)v] = (int)p.perm.size();
-            p.perm.push_back(v);
-        }
-
-    // boundaries, bottom-up; the lists (own, boundary) of every node in elimination order
-    std::vector<std::vector<int>> bnd((size_t)nnodes);
-    for (int id : p.level_nodes) {
-        std::vector<int>& b = bnd[(size_t)id];
-        int last = -1;   // the place of this node's last own vertex; below a node without own vertices, of its subtree's last one
-        for (int u : B.own[(size_t)id]) last = std::max(last, p.order_of[(size_t)free_list[(size_t)u]]);
-        for (int u : B.own[(size_t)id])
-            for (int w : adj[(size_t)u]) {
-                const int v = free_list[(size_t)w];
-                if (p.order_of[(size_t)v] > last) b.push_back(v);
-            }
-        for (int k = 0; k < 2; k++) {
-            const int c = p.nodes[(size_t)id].child[k];
-            if (c < 0) continue;
-            for (int v : bnd[(size_t)c])
-                if (p.node_of[(size_t)v] != id) b.push_back(v);
-        }
-        std::sort(b.begin(), b.end(), [&](int x, int y) { return p.order_of[(size_t)x] < p.order_of[(size_t)y]; });
-        b.erase(std::unique(b.begin(), b.end()), b.end());
-    }
-    double total = 0;
-    for (int id = 0; id < nnodes; id++) {
-        EgNode& nd = p.nodes[(size_t)id];
-        nd.nown = (int)B.own[(size_t)id].size();
-        nd.nb = (int)bnd[(size_t)id].size();
-        nd.vtx = (int)p.node_vtx.size();
-        for (int u : B.own[(size_t)id]) p.node_vtx.push_back(free_list[(size_t)u]);
-        for (int v : bnd[(size_t)id]) p.node_vtx.push_back(v);
-        const double m = 7.0 * (nd.nown + nd.nb);
-        nd.front = (long long)total;
-        total += m * m + 2 * m;
-        p.max_rows = std::max(p.max_rows, (int)m);
-    }
+    const double total = front_build_tree(p, n.nkf, free_list, adj, adj, p.nfree, p.leaf, 7);
     if (total + 1 > (double)eg_front_cap(n.nkf, leaf_vertices))
         return ba_fail(ORBFE_ERR_CAPACITY, "%s: the fronts of this graph take %.0f MB of scratch, the budget is %zu MB", name, total * 8 / 1048576.,
                        EG_FRONT_BUDGET >> 20);
@@ -357,44 +202,11 @@ inline BaCheck eg_make_plan(EgPlan& p, const EgSizes& n, int fixed, const int32_
     }
     p.npairs = (int)p.pair_u.size();
 
-    // every node's blocks: the diagonal blocks of its own vertices; a pair's block in the node of whichever vertex goes first
-    std::vector<std::vector<EgSrc>> srcs((size_t)nnodes);
-    std::vector<int> pos(K, -1);
-    for (int id = 0; id < nnodes; id++) {
-        const EgNode& nd = p.nodes[(size_t)id];
-        for (int k = 0; k < nd.nown; k++) srcs[(size_t)id].push_back(EgSrc{p.node_vtx[(size_t)nd.vtx + k], k, k, 0});
-    }
-    for (int q = 0; q < p.npairs; q++) {
-        const int u = p.pair_u[(size_t)q], v = p.pair_v[(size_t)q];
-        const int id = p.order_of[(size_t)u] < p.order_of[(size_t)v] ? p.node_of[(size_t)u] : p.node_of[(size_t)v];
-        const EgNode& nd = p.nodes[(size_t)id];
-        int iu = -1, iv = -1;
-        for (int k = 0; k < nd.nown + nd.nb; k++) {
-            if (p.node_vtx[(size_t)nd.vtx + k] == u) iu = k;
-            if (p.node_vtx[(size_t)nd.vtx + k] == v) iv = k;
-        }
-        if (iu < 0 || iv < 0) return ba_fail(ORBFE_ERR_INVALID, "%s: the elimination plan lost the pair (%d, %d)", name, u, v);
-        srcs[(size_t)id].push_back(iu > iv ? EgSrc{q, iu, iv, 1} : EgSrc{q, iv, iu, 3});
-    }
-    for (int id = 0; id < nnodes; id++) {
-        EgNode& nd = p.nodes[(size_t)id];
-        nd.src = (int)p.src.size();
-        nd.nsrc = (int)srcs[(size_t)id].size();
-        p.src.insert(p.src.end(), srcs[(size_t)id].begin(), srcs[(size_t)id].end());
-        for (int k = 0; k < nd.nown + nd.nb; k++) pos[(size_t)p.node_vtx[(size_t)nd.vtx + k]] = k;
-        for (int k = 0; k < 2; k++) {
-            const int c = nd.child[k];
-            nd.cmap[k] = (int)p.cmap.size();
-            if (c < 0) continue;
-            const EgNode& ch = p.nodes[(size_t)c];
-            for (int b = 0; b < ch.nb; b++) {
-                const int at = pos[(size_t)p.node_vtx[(size_t)ch.vtx + ch.nown + b]];
-                if (at < 0) return ba_fail(ORBFE_ERR_INVALID, "%s: the elimination plan lost a boundary vertex of node %d", name, c);
-                p.cmap.push_back(at);
-            }
-        }
-        for (int k = 0; k < nd.nown + nd.nb; k++) pos[(size_t)p.node_vtx[(size_t)nd.vtx + k]] = -1;
-    }
+    // every node's blocks and the children's scatter maps
+    const long long lost = front_place_blocks(p, n.nkf, p.pair_u, p.pair_v);
+    if (lost < 0 && -1 - lost < p.npairs)
+        return ba_fail(ORBFE_ERR_INVALID, "%s: the elimination plan lost the pair (%d, %d)", name, p.pair_u[(size_t)(-1 - lost)], p.pair_v[(size_t)(-1 - lost)]);
+    if (lost < 0) return ba_fail(ORBFE_ERR_INVALID, "%s: the elimination plan lost a boundary vertex of node %d", name, (int)(-1 - lost - p.npairs));
     return BaCheck{};
 }
 
@@ -553,16 +365,7 @@ inline EgSchedule eg_schedule(const EgPlan& p, int iterations, bool inspect, siz
     return s;
 }
 
-// The rows k_eg_front reserves LDS for at each level: the largest front of the level that fits lds_rows (0: none does, the level
-// runs in global memory).  A level of small fronts then shares a compute unit among several workgroups.
-inline std::vector<int> eg_level_lds_rows(const EgPlan& p, int lds_rows)
-{
-    std::vector<int> rows((size_t)p.nlevels, 0);
-    for (const EgNode& nd : p.nodes) {
-        const int m = 7 * (nd.nown + nd.nb);
-        if (m <= lds_rows) rows[(size_t)nd.level] = std::max(rows[(size_t)nd.level], m);
-    }
-    return rows;
-}
+// The rows k_eg_front reserves LDS for at each level (front_plan.hpp)
+inline std::vector<int> eg_level_lds_rows(const EgPlan& p, int lds_rows) { return front_level_lds_rows(p, 7, lds_rows); }
 
 } // namespace orbfe
