@@ -39,12 +39,12 @@ _POSE = {"du_pose_normalise": [vp, vp, vp, i32], "du_pose_eig": [vp, vp, i32], "
          "du_pose_solve_half": [vp, C.c_float, vp, i32, vp, i32]}
 
 
-def hipcc_command(out, flags=None):
-    """the hipcc line of the probe: the library's flags as build() composes them (`flags` replaces them, for a scratch experiment)"""
+def hipcc_command(out, flags=None, source=SOURCE):
+    """the hipcc line of a probe (`source`): the library's flags as build() composes them (`flags` replaces them, for a scratch experiment)"""
     hipcc = "hipcc" if subprocess.call(["which", "hipcc"], stdout=subprocess.DEVNULL) == 0 else "/opt/rocm/bin/hipcc"
     if flags is None:
         flags = list(entry.HIPCC_FLAGS) + [f for f in os.environ.get("ORBFE_EXTRA_HIPCC_FLAGS", "").split() if f]
-    return [hipcc] + list(flags) + [SOURCE, "-o", out]
+    return [hipcc] + list(flags) + [source, "-o", out]
 
 
 def _declare(L, table):

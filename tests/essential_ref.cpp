@@ -375,6 +375,13 @@ void ref_eg_exp(const double* u, double* sim8) { sim_to8(sim_exp(u), sim8); }
 void ref_eg_log(const double* sim8, double* out7) { sim_log(sim_of8(sim8), out7); }
 void ref_eg_mul(const double* a8, const double* b8, double* out8) { sim_to8(sim_of8(a8) * sim_of8(b8), out8); }
 void ref_eg_inverse(const double* a8, double* out8) { sim_to8(inv(sim_of8(a8)), out8); }
+void ref_eg_map(const double* a8, const double* p3, double* out3) { sim_map(sim_of8(a8), p3, out3); }
+void ref_eg_lu3(const double* m9, const double* b3, double* x3)
+{
+    double a[3][3];
+    std::memcpy(a, m9, sizeof(a));
+    lu_solve3(a, b3, x3);
+}
 
 // error and both numeric Jacobians of one edge
 void ref_eg_edge(const double* C8, const double* vi8, const double* vj8, int fix_scale, double* err, double* Ji, double* Jj)

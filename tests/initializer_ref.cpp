@@ -682,6 +682,9 @@ void decode_sets(int N, int iters, const int32_t* words, std::vector<std::vector
 
 extern "C" {
 
+// jacobi_svd on its own (tests/solver_units_build.py): At n1 x m in / out, W n, Vt n x n
+void ref_jacobi_svd(float* At, int m, int n, int n1, float* W, float* Vt) { jacobi_svd(At, m, n, n1, W, Vt); }
+
 // Initializer(frame1, sigma, iterations).Initialize(frame2, matches12, ...) with the sets drawn from `words`.  Outputs as
 // orbfe_initialize; debug outputs (any may be NULL): sets iters x 8, T12 18, pn1 n1 x 2, pn2 n2 x 2, models iters x 27, scores
 // 2 x iters, sv 2 x iters x 2 (the two smallest singular values of each eight-point system), margins 10 (inliers of the chosen model,
