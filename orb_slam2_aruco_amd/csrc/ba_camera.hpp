@@ -56,3 +56,34 @@ inline BaCheck ba_camera(BaCamera& c, const float* K4, const float* inv_sigma2, 
 }
 
 } // namespace orbfe
+
+#ifdef __HIPCC__
+// for the entry points (hipcc only; the rules above stay free of HIP)
+#include "orbfe_common.hpp"
+
+namespace orbfe {
+
+// what a host-only rule found, as the entry points return it
+inline int report(const BaCheck& c) { return c.err ? fail(c.err, "%s", c.msg) : ORBFE_OK; }
+
+// what a call is given beside its arrays, into the kernels' argument: the camera and the level table (every entry finite here), the
+// marker weight and switch, the Huber delta of chi2_delta (ba_camera.hpp)
+template <class P>
+int ba_fill(P& p, const float* K4, const float* inv_sigma2, int nlevels, float marker_info, int use_markers, double chi2_delta, const char* name)
+{
+    BaCamera c;
+    const int rc = report(ba_camera(c, K4, inv_sigma2, nlevels, marker_info, name, chi2_delta));
+    if (rc) return rc;
+    for (int l = 0; l < nlevels; l++)
+        if (!std::isfinite(inv_sigma2[l])) return fail(ORBFE_ERR_INVALID, "%s: inv_level_sigma2 is not finite", name);
+    p.nlevels = nlevels;
+    for (int l = 0; l < BA_MAX_LEVELS; l++) p.inv_sigma2[l] = c.inv_sigma2[l];
+    p.K = {c.fx, c.fy, c.cx, c.cy};
+    p.marker_info = marker_info;
+    p.delta = c.delta;
+    p.use_markers = use_markers != 0;
+    return ORBFE_OK;
+}
+
+} // namespace orbfe
+#endif

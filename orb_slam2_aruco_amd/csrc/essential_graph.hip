@@ -94,16 +94,6 @@ __device__ __noinline__ void eg_error(const Sim3& C, const Sim3& Si, const Sim3&
     sim3_log(E, err);
 }
 
-// the sum of n doubles: each thread a contiguous run, then the workgroup (valid in thread 0)
-__device__ __forceinline__ double eg_part_sum(const double* v, int n)
-{
-    const int per = (n + LM_THREADS - 1) / LM_THREADS;
-    const int lo = min((int)threadIdx.x * per, n), hi = min(lo + per, n);
-    double s = 0;
-    for (int i = lo; i < hi; i++) s += v[i];
-    return s;
-}
-
 // ---------------------------------------------------------------------------------------- setup --
 __global__ __launch_bounds__(256) void k_eg_setup(EgP p)
 {
@@ -251,7 +241,7 @@ __global__ __launch_bounds__(LM_THREADS) void k_eg_ctl_lin(EgP p)
     __shared__ double red[LM_WAVES];
     EgCtl& c = *p.ctl;
     if (c.aborted || !c.iter_go) return;
-    double s[1] = {eg_part_sum(p.e_chi, p.ne)};
+    double s[1] = {run_sum(p.e_chi, p.ne)};
     block_sum<1>(s, red);
     if (threadIdx.x != 0) return;
     lm_linearised_user(c.lm, s[0], c.it == 0, EG_LAMBDA_INIT);
@@ -298,26 +288,7 @@ __global__ __launch_bounds__(LM_THREADS) void k_eg_front(EgP p, int first, int l
         }
     }
     __syncthreads();
-    // the children's Schur complements, left then right
-    for (int ch = 0; ch < 2; ch++) {
-        if (nd.child[ch] < 0) continue;
-        const EgNode cn = p.nodes[nd.child[ch]];
-        const int m = 7 * (cn.nown + cn.nb), ck = 7 * cn.nown, cb = 7 * cn.nb;
-        const double* G = p.fronts + cn.front;
-        const double* gr = G + (size_t)m * m;
-        const int32_t* map = p.cmap + nd.cmap[ch];
-        for (int idx = tid; idx < cb * cb; idx += LM_THREADS) {
-            const int bi = idx / cb, bj = idx % cb;
-            if (bj > bi) continue;
-            int R = 7 * map[bi / 7] + bi % 7, Cc = 7 * map[bj / 7] + bj % 7;
-            if (R < Cc) {
-                const int t = R; R = Cc; Cc = t;
-            }
-            F[(size_t)R * n + Cc] += G[(size_t)(ck + bi) * m + ck + bj];
-        }
-        for (int bi = tid; bi < cb; bi += LM_THREADS) r[7 * map[bi / 7] + bi % 7] += gr[ck + bi];
-        __syncthreads();
-    }
+    front_merge_children<7>(nd, p.nodes, p.cmap, p.fronts, F, r);
     bool ok;
     if (n <= lds_rows) {
         for (int i = 0; i < n; i++)
@@ -343,11 +314,7 @@ __global__ __launch_bounds__(LM_THREADS) void k_eg_back(EgP p, int first)
 {
     const EgCtl& c = *p.ctl;
     if (c.aborted || !c.trial_go || c.fail) return;
-    const EgNode nd = p.nodes[p.level_nodes[first + blockIdx.x]];
-    const int n = 7 * (nd.nown + nd.nb);
-    if (nd.nb == 0 || nd.nown == 0) return;
-    const double* F = p.fronts + nd.front;
-    front_substitute_back<7>(nd, p.node_vtx + nd.vtx, p.xt, F, F + (size_t)n * n, p.fronts + nd.front + (size_t)n * n + n);
+    front_back<7>(p.nodes[p.level_nodes[first + blockIdx.x]], p.fronts, p.node_vtx, p.xt);
 }
 
 // the trial estimates: VertexSim3Expmap::oplusImpl.  When the system was not solved the update of the last solved trial stays.
@@ -390,10 +357,8 @@ __global__ __launch_bounds__(LM_THREADS) void k_eg_ctl_trial(EgP p)
     if (c.aborted || !c.trial_go) return;
     // chi2 over the edges and x (lambda x + b) over the 7 nkf unknowns: each thread a contiguous run, then the workgroup
     const double lambda = c.lm.lambda;
-    const int n = 7 * p.nkf, per = (n + LM_THREADS - 1) / LM_THREADS;
-    const int lo = min((int)threadIdx.x * per, n), hi = min(lo + per, n);
-    double s[2] = {eg_part_sum(p.e_chi, p.ne), 0.};
-    for (int j = lo; j < hi; j++) s[1] += p.xv[j] * (lambda * p.xv[j] + p.bv[j]);
+    double s[2] = {run_sum(p.e_chi, p.ne), 0.};
+    run_for(7 * p.nkf, [&](int j) { s[1] += p.xv[j] * (lambda * p.xv[j] + p.bv[j]); });
     block_sum<2>(s, red);
     if (threadIdx.x != 0) return;
     if (lm_judge_trial(c.lm, s[0], c.fail == 0, s[1])) c.cur = 1 - c.cur;
@@ -432,15 +397,11 @@ __global__ __launch_bounds__(256) void k_eg_finish(EgP p)
             for (int a = 0; a < 12; a++) p.Tcw_out[(size_t)i * 12 + a] = p.Tcw[(size_t)i * 12 + a];
         } else {
             // [sR t] -> [R t/s]: toRotationMatrix, eigt *= 1. / s, Converter::toCvSE3's casts
-            const Quat& q = S.q;
-            const double tx = 2 * q.x, ty = 2 * q.y, tz = 2 * q.z;
-            const double twx = tx * q.w, twy = ty * q.w, twz = tz * q.w;
-            const double txx = tx * q.x, txy = ty * q.x, txz = tz * q.x;
-            const double tyy = ty * q.y, tyz = tz * q.y, tzz = tz * q.z;
-            const double R[9] = {1 - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1 - (txx + tzz), tyz - twx, txz - twy, tyz + twx, 1 - (txx + tyy)};
+            double R[3][3];
+            rot_of(S.q, R);
             const double is = 1. / S.s;
             for (int r = 0; r < 3; r++) {
-                for (int cc = 0; cc < 3; cc++) p.Tcw_out[(size_t)i * 12 + r * 4 + cc] = (float)R[r * 3 + cc];
+                for (int cc = 0; cc < 3; cc++) p.Tcw_out[(size_t)i * 12 + r * 4 + cc] = (float)R[r][cc];
                 p.Tcw_out[(size_t)i * 12 + r * 4 + 3] = (float)(S.t[r] * is);
             }
         }
@@ -460,17 +421,7 @@ __global__ __launch_bounds__(256) void k_eg_finish(EgP p)
 }
 
 // ---------------------------------------------------------------------------------------- host --
-int report(const BaCheck& c) { return c.err ? fail(c.err, "%s", c.msg) : ORBFE_OK; }
-
-// The plan's tables on their way to the device, one page-locked block per (thread, device, stream).  A call overwrites the block of
-// the call before it on the same stream, so it first waits until that call's copy has left the block (an event behind the copy).
-struct EgTablesStage {
-    PinnedBuf pinned;
-    hipEvent_t ev = nullptr;
-    bool pending = false;
-    ~EgTablesStage() { if (ev) (void)hipEventDestroy(ev); }
-};
-thread_local ThreadWorkspaces<EgTablesStage> tl_eg_tables;
+thread_local ThreadWorkspaces<TablesStage> tl_eg_tables;
 thread_local ThreadWorkspaces<HostStage> tl_eg_stages;
 
 struct EgCall {
@@ -494,16 +445,9 @@ int eg_prepare(EgCall& cl, EgP& p, const EgSizes& n, const int32_t* edge_i, cons
     cl.level_rows = eg_level_lds_rows(cl.plan, cl.k.lds_rows);
     eg_pack_tables(cl.blob, cl.plan, edge_i, edge_j, edge_kind);
     eg_tables(p, eg_counts(cl.plan), p.tables);
-    EgTablesStage& ts = tl_eg_tables.get(s);
-    if (ts.pending) ORBFE_HIP(hipEventSynchronize(ts.ev));
-    if (!ts.ev) ORBFE_HIP(hipEventCreateWithFlags(&ts.ev, hipEventDisableTiming));
-    if ((rc = ts.pinned.ensure(cl.blob.size()))) return rc;
-    memcpy(ts.pinned.p, cl.blob.data(), cl.blob.size());
     ORBFE_HIP(hipMemsetAsync(scratch, 0, x.zero_end, s));
     ORBFE_HIP(hipMemsetAsync((unsigned char*)scratch + x.ff_begin, 0xff, x.ff_end - x.ff_begin, s));
-    ORBFE_HIP(hipMemcpyAsync(p.tables, ts.pinned.p, cl.blob.size(), hipMemcpyHostToDevice, s));
-    ORBFE_HIP(hipEventRecord(ts.ev, s));
-    ts.pending = true;
+    if ((rc = tl_eg_tables.get(s).send(cl.blob, p.tables, s))) return rc;
     return ensure_dyn_lds((const void*)k_eg_front, cl.k.tri_bytes);
 }
 
@@ -518,19 +462,11 @@ int eg_enqueue_setup(const EgCall& cl, const EgP& p, hipStream_t s)
 
 int eg_enqueue_iteration(const EgCall& cl, const EgP& p, hipStream_t s, bool inspect)
 {
-    const EgPlan& pl = cl.plan;
     hipLaunchKernelGGL(k_eg_linearize, dim3(cl.k.g_lin), dim3(256), 0, s, p);
     hipLaunchKernelGGL(k_eg_blocks, dim3(cl.k.g_blocks), dim3(64), 0, s, p);
     hipLaunchKernelGGL(k_eg_ctl_lin, dim3(1), dim3(LM_THREADS), 0, s, p);
     for (int q = 0; q < cl.k.trials; q++) {
-        for (int l = 0; l < pl.nlevels; l++)
-        {
-            const int rows = cl.level_rows[(size_t)l];
-            hipLaunchKernelGGL(k_eg_front, dim3(pl.level_off[(size_t)l + 1] - pl.level_off[(size_t)l]), dim3(LM_THREADS),
-                               (size_t)rows * (rows + 1) / 2 * 8, s, p, pl.level_off[(size_t)l], rows);
-        }
-        for (int l = pl.nlevels - 2; l >= 0; l--)
-            hipLaunchKernelGGL(k_eg_back, dim3(pl.level_off[(size_t)l + 1] - pl.level_off[(size_t)l]), dim3(LM_THREADS), 0, s, p, pl.level_off[(size_t)l]);
+        front_enqueue_levels(k_eg_front, k_eg_back, cl.plan.level_off, cl.level_rows, LM_THREADS, p, s);
         hipLaunchKernelGGL(k_eg_update, dim3(cl.k.g_kf), dim3(256), 0, s, p);
         if (!inspect) {
             hipLaunchKernelGGL(k_eg_trial_errors, dim3(cl.k.g_edges), dim3(256), 0, s, p);

@@ -18,6 +18,9 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+#endif
 
 #include <algorithm>
 #include <vector>
@@ -264,5 +267,22 @@ inline std::vector<int> front_level_lds_rows(const FrontTree& p, int rows, int l
     }
     return out;
 }
+
+#ifdef __HIPCC__
+// the launches of one solve: the front kernel once per level, leaves first, with the LDS of the level's largest front that fits
+// (level_rows), then the back kernel once per level downwards from below the root's
+template <class P>
+void front_enqueue_levels(void (*front)(P, int, int), void (*back)(P, int), const std::vector<int>& level_off, const std::vector<int>& level_rows, int threads,
+                          const P& p, hipStream_t s)
+{
+    const int nlevels = (int)level_off.size() - 1;
+    auto grid = [&](int l) { return dim3(level_off[(size_t)l + 1] - level_off[(size_t)l]); };
+    for (int l = 0; l < nlevels; l++) {
+        const int rows = level_rows[(size_t)l];
+        hipLaunchKernelGGL(front, grid(l), dim3(threads), (size_t)rows * (rows + 1) / 2 * 8, s, p, level_off[(size_t)l], rows);
+    }
+    for (int l = nlevels - 2; l >= 0; l--) hipLaunchKernelGGL(back, grid(l), dim3(threads), 0, s, p, level_off[(size_t)l]);
+}
+#endif
 
 } // namespace orbfe

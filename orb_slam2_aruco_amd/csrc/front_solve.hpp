@@ -1,6 +1,9 @@
 // front_solve.hpp -- what a workgroup does with one front of an elimination tree (front_plan.hpp), shared by essential_graph.hip
-// (7 rows a vertex) and global_ba.hip (6): the partial Cholesky factorisation that leaves the boundary's Schur complement, and the
-// substitution back once the ancestors' unknowns are known.  LM_THREADS threads.
+// (7 rows a vertex) and global_ba.hip (6): the children's Schur complements added to it, the partial Cholesky factorisation that
+// leaves the boundary's own complement, and the substitution back once the ancestors' unknowns are known.  A front kernel gathers
+// its own blocks, calls front_merge_children, runs front_partial_llt on the LDS copy or in place (that branch stays in the kernel's
+// own text: DESIGN.md 4k), and substitutes at once when it has no boundary; front_back is the body of a back kernel.  LM_THREADS
+// threads.
 #pragma once
 #include "front_plan.hpp"
 #include "lm_dense.hpp"
@@ -59,6 +62,43 @@ template <int R> __device__ __forceinline__ void front_substitute_back(const Fro
         __syncthreads();
     }
     for (int i = tid; i < k; i += LM_THREADS) xt[(size_t)vtx[i / R] * R + i % R] = w[i];
+}
+
+// The children's Schur complements added to front F (rows of n = R (nown + nb), lower triangle) and to its right-hand side r, the
+// left child then the right one: the child's boundary vertex b is the front's vertex map[b], and where the map turns two of them
+// round the entry goes to the transposed place.  Every entry has one thread; a barrier behind each child.
+template <int R> __device__ __forceinline__ void front_merge_children(const FrontNode& nd, const FrontNode* nodes, const int32_t* cmap, const double* fronts,
+                                                                      double* F, double* r)
+{
+    const int tid = threadIdx.x, n = R * (nd.nown + nd.nb);
+    for (int ch = 0; ch < 2; ch++) {
+        if (nd.child[ch] < 0) continue;
+        const FrontNode cn = nodes[nd.child[ch]];
+        const int m = R * (cn.nown + cn.nb), ck = R * cn.nown, cb = R * cn.nb;
+        const double* G = fronts + cn.front;
+        const double* gr = G + (size_t)m * m;
+        const int32_t* map = cmap + nd.cmap[ch];
+        for (int idx = tid; idx < cb * cb; idx += LM_THREADS) {
+            const int bi = idx / cb, bj = idx % cb;
+            if (bj > bi) continue;
+            int row = R * map[bi / R] + bi % R, col = R * map[bj / R] + bj % R;
+            if (row < col) {
+                const int t = row; row = col; col = t;
+            }
+            F[(size_t)row * n + col] += G[(size_t)(ck + bi) * m + ck + bj];
+        }
+        for (int bi = tid; bi < cb; bi += LM_THREADS) r[R * map[bi / R] + bi % R] += gr[ck + bi];
+        __syncthreads();
+    }
+}
+
+// A back kernel: the unknowns of a front that has a boundary, once its ancestors' are known
+template <int R> __device__ __forceinline__ void front_back(const FrontNode& nd, double* fronts, const int32_t* node_vtx, double* xt)
+{
+    const int n = R * (nd.nown + nd.nb);
+    if (nd.nb == 0 || nd.nown == 0) return;
+    double* F = fronts + nd.front;
+    front_substitute_back<R>(nd, node_vtx + nd.vtx, xt, F, F + (size_t)n * n, F + (size_t)n * n + n);
 }
 
 } // namespace

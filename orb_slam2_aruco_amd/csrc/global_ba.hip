@@ -61,18 +61,6 @@ struct GbaP {
         *pair_off, *pair_items, *pair_moff, *pair_mitems, *obs_offset, *obs_kf, *mobs_offset, *mobs_kf, *mo_marker;
 };
 
-__device__ __forceinline__ bool stop_set(const GbaP& p) { return p.stop && *(const volatile uint8_t*)p.stop != 0; }
-
-// the sum of n doubles: each thread a contiguous run, then the workgroup (valid in thread 0 behind block_sum)
-__device__ __forceinline__ double gba_run_sum(const double* v, int n)
-{
-    const int per = (n + LM_THREADS - 1) / LM_THREADS;
-    const int lo = min((int)threadIdx.x * per, n), hi = min(lo + per, n);
-    double s = 0;
-    for (int i = lo; i < hi; i++) s += v[i];
-    return s;
-}
-
 // ---------------------------------------------------------------------------------------- setup --
 // the graph has been checked on the host; what is left are the values
 __global__ __launch_bounds__(256) void k_gba_setup(GbaP p)
@@ -100,34 +88,9 @@ __global__ __launch_bounds__(256) void k_gba_setup(GbaP p)
         }
     }
     if (i < p.nobs) {
-        // the point of slot i: the last point whose range starts at or before i (np > 0 here)
-        int lo = 0, hi = p.np - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (p.obs_offset[mid] <= i) lo = mid;
-            else hi = mid - 1;
-        }
-        const int kf = p.obs_kf[i];
-        int oct = 0;
-        float ox = 0.f, oy = 0.f;
-        if (p.obs_xy) {
-            ox = p.obs_xy[(size_t)i * 2];
-            oy = p.obs_xy[(size_t)i * 2 + 1];
-            oct = p.obs_oct[i];
-        } else {
-            const int f = p.obs_feat[i];
-            if (f < 0 || f >= p.capacity) bad |= GBA_BAD_INVALID;
-            else {
-                const orbfe_keypoint kp = p.kps[(size_t)kf * p.capacity + f];
-                ox = kp.x; oy = kp.y; oct = kp.octave;
-            }
-        }
-        if (oct < 0 || oct >= p.nlevels) {
-            bad |= GBA_BAD_INVALID;
-            oct = 0;
-        }
-        if (!finite_f(ox) || !finite_f(oy)) bad |= GBA_BAD_INVALID;
-        p.e_pt[i] = lo; p.e_ox[i] = ox; p.e_oy[i] = oy; p.e_info[i] = p.inv_sigma2[oct];
+        const ObsPixel o = obs_pixel(i, p.obs_kf[i], p.obs_xy, p.obs_oct, p.obs_feat, p.kps, p.capacity, p.nlevels);
+        if (!o.ok) bad |= GBA_BAD_INVALID;
+        p.e_pt[i] = obs_point(p.obs_offset, p.np, i); p.e_ox[i] = o.x; p.e_oy[i] = o.y; p.e_info[i] = p.inv_sigma2[o.oct];
     }
     if (i < p.nmobs)
         for (int k = 0; k < 8; k++)
@@ -141,7 +104,7 @@ __global__ void k_gba_begin(GbaP p)
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     GbaCtl& c = *p.ctl;
     if (c.bad & GBA_BAD_INVALID) c.abort_status = ORBFE_ERR_INVALID;
-    else if (stop_set(p)) c.abort_status = ORBFE_GBA_STOPPED;
+    else if (stop_set(p.stop)) c.abort_status = ORBFE_GBA_STOPPED;
     c.aborted = c.abort_status != 0;
     c.iter_go = !c.aborted && p.maxit > 0;
     c.trial_go = 0;
@@ -197,28 +160,10 @@ __global__ __launch_bounds__(GBA_PT) void k_gba_linearize(GbaP p)
         if (j < p.nme) {
             const int o = j >> 2, k = j & 3, kf = p.mobs_kf[o], m = p.mo_marker[o];
             const SE3 Tc = p.pose[cur][kf], Tm = p.pose[cur][p.nkf + m];
-            const double pm[3] = {p.mlocal[(size_t)m * 12 + 3 * k], p.mlocal[(size_t)m * 12 + 3 * k + 1], p.mlocal[(size_t)m * 12 + 3 * k + 2]};
-            const double ox = p.mobs_corners[(size_t)o * 8 + 2 * k], oy = p.mobs_corners[(size_t)o * 8 + 2 * k + 1];
-            const bool camfree = p.kf_free[kf] >= 0;
-            double err[2], Jc[2][6], Jm[2][6], rho[2];
-            lba_marker_error(Tc, Tm, pm, ox, oy, p.K, err);
-            const double ch = chi2_of(err, p.marker_info);
-            huber(ch, p.delta, rho);
-            chi += rho[0];
-            for (int a = 0; a < 6; a++) Jc[0][a] = Jc[1][a] = 0;
-            if (camfree) lba_marker_jacobian(Tc, Tm, true, pm, ox, oy, p.K, Jc);
-            lba_marker_jacobian(Tc, Tm, false, pm, ox, oy, p.K, Jm);
-            const bool fin = all_finite(err, 2) && all_finite(&Jc[0][0], 12) && all_finite(&Jm[0][0], 12) && isfinite(rho[1]);
-            p.m_use[j] = fin ? 1 : 0;
-            if (fin) {
-                const double w = rho[1] * p.marker_info;
-                const double r0 = rho[1] * -(p.marker_info * err[0]), r1 = rho[1] * -(p.marker_info * err[1]);
-                double* out = p.m_blk + (size_t)j * GBA_MBLK;
-                lba_diag_block(Jc, w, r0, r1, out);
-                lba_diag_block(Jm, w, r0, r1, out + 27);
-                for (int a = 0; a < 6; a++)
-                    for (int cc = 0; cc < 6; cc++) out[54 + a * 6 + cc] = Jc[0][a] * (w * Jm[0][cc]) + Jc[1][a] * (w * Jm[1][cc]);
-            }
+            double ch, rho0;
+            p.m_use[j] = marker_edge_linearize(Tc, Tm, marker_corner(p.mlocal, p.mobs_corners, m, o, k), p.K, p.kf_free[kf] >= 0, true, p.marker_info,
+                                               p.delta, p.m_blk + (size_t)j * GBA_MBLK, ch, rho0);
+            chi += rho0;
         }
     }
     chi = wave_sum(chi);
@@ -239,17 +184,13 @@ __global__ __launch_bounds__(LM_THREADS) void k_gba_pose_blocks(GbaP p)
     if (c.aborted || !c.iter_go || v >= p.nv) return;
     double s[27];
     for (int k = 0; k < 27; k++) s[k] = 0;
-    {
-        const int first = p.vtx_eoff[v], n = p.vtx_eoff[v + 1] - first;
-        const int per = (n + LM_THREADS - 1) / LM_THREADS;
-        const int lo = min(tid * per, n), hi = min(lo + per, n);
-        for (int it = lo; it < hi; it++) {
-            const int e = p.vtx_eitems[first + it];
-            if (p.e_use[e] != 3) continue;
-            const double* blk = p.e_blk + (size_t)e * GBA_EBLK;
-            for (int k = 0; k < 27; k++) s[k] += blk[k];
-        }
-    }
+    const int first = p.vtx_eoff[v];
+    run_for(p.vtx_eoff[v + 1] - first, [&](int it) {
+        const int e = p.vtx_eitems[first + it];
+        if (p.e_use[e] != 3) return;
+        const double* blk = p.e_blk + (size_t)e * GBA_EBLK;
+        for (int k = 0; k < 27; k++) s[k] += blk[k];
+    });
     block_sum<27>(s, red);
     if (tid != 0) return;
     const int side = p.v_kf[v] < p.nkf ? 0 : 27;   // a keyframe's half of a marker edge's blocks, or the marker's
@@ -259,15 +200,7 @@ __global__ __launch_bounds__(LM_THREADS) void k_gba_pose_blocks(GbaP p)
         const double* blk = p.m_blk + (size_t)j * GBA_MBLK + side;
         for (int k = 0; k < 27; k++) s[k] += blk[k];
     }
-    double* H = p.Hpp + (size_t)v * 36;
-    int k = 0;
-    double md = 0;
-    for (int a = 0; a < 6; a++)
-        for (int cc = a; cc < 6; cc++, k++) H[a * 6 + cc] = H[cc * 6 + a] = s[k];
-    for (int a = 0; a < 6; a++) {
-        p.bp[(size_t)v * 6 + a] = s[21 + a];
-        md = fmax(md, fabs(H[a * 6 + a]));
-    }
+    const double md = unpack_pose_sums(s, p.Hpp + (size_t)v * 36, p.bp + (size_t)v * 6);
     p.vmax[v] = p.v_active[v] ? md : 0;
 }
 
@@ -277,7 +210,7 @@ __global__ __launch_bounds__(LM_THREADS) void k_gba_ctl_lin(GbaP p)
     __shared__ double mx[LM_THREADS];
     GbaCtl& c = *p.ctl;
     if (c.aborted || !c.iter_go) return;
-    double s[1] = {gba_run_sum(p.chi_part, p.nb)};
+    double s[1] = {run_sum(p.chi_part, p.nb)};
     double m = 0;
     if (c.it == 0) {
         for (int i = threadIdx.x; i < p.nb; i += LM_THREADS) m = fmax(m, p.max_part[i]);
@@ -299,21 +232,14 @@ __global__ __launch_bounds__(LM_THREADS) void k_gba_ctl_lin(GbaP p)
 }
 
 // ---------------------------------------------------------------------------------------- a trial --
-// (Hll + lambda I)^-1 by cofactors (Eigen's 3 x 3 inverse)
+// (Hll + lambda I)^-1 of every point that has an edge
 __global__ __launch_bounds__(GBA_PT) void k_gba_schur_points(GbaP p)
 {
     const GbaCtl& c = *p.ctl;
     if (c.aborted || !c.trial_go) return;
     const int pi = blockIdx.x * GBA_PT + threadIdx.x;
     if (pi >= p.np || p.obs_offset[pi + 1] == p.obs_offset[pi]) return;
-    const double* H = p.Hll + (size_t)pi * 6;
-    const double m00 = H[0] + c.lm.lambda, m01 = H[1], m02 = H[2], m11 = H[3] + c.lm.lambda, m12 = H[4], m22 = H[5] + c.lm.lambda;
-    const double c00 = m11 * m22 - m12 * m12, c10 = m12 * m02 - m01 * m22, c20 = m01 * m12 - m11 * m02;
-    const double det = c00 * m00 + c10 * m01 + c20 * m02, id = 1. / det;
-    double* D = p.Dinv + (size_t)pi * 9;
-    D[0] = c00 * id; D[1] = c10 * id; D[2] = c20 * id;
-    D[3] = D[1]; D[4] = (m00 * m22 - m02 * m02) * id; D[5] = (m02 * m01 - m00 * m12) * id;
-    D[6] = D[2]; D[7] = D[5]; D[8] = (m00 * m11 - m01 * m01) * id;
+    damped_inverse3(p.Hll + (size_t)pi * 6, c.lm.lambda, p.Dinv + (size_t)pi * 9);
 }
 
 // the block of covisible pair q = (u, v), u <= v, in its slot of S, and on the diagonal the rows u of the right-hand side; one wave:
@@ -330,23 +256,13 @@ __global__ __launch_bounds__(64) void k_gba_reduce(GbaP p)
     for (int k = 0; k < 6; k++) accb[k] = 0;
     const int first = p.pair_off[q], n = p.pair_off[q + 1] - first;
     if (n > 0) {
-        const int per = (n + 63) / 64;
-        const int lo = min(lane * per, n), hi = min(lo + per, n);
-        for (int it = lo; it < hi; it++) {
+        run_for<64>(n, [&](int it) {
             const int ei = p.pair_items[2 * (first + it)], ej = p.pair_items[2 * (first + it) + 1];
-            if (p.e_use[ei] != 3 || p.e_use[ej] != 3) continue;
+            if (p.e_use[ei] != 3 || p.e_use[ej] != 3) return;
             const int pi = p.e_pt[ei];
-            const double* Wi = p.e_blk + (size_t)ei * GBA_EBLK + 27;
-            const double* Wj = p.e_blk + (size_t)ej * GBA_EBLK + 27;
-            const double* D = p.Dinv + (size_t)pi * 9;
-            const double* bl = p.bl + (size_t)pi * 3;
-            for (int a = 0; a < 6; a++) {
-                double Y[3];
-                for (int cc = 0; cc < 3; cc++) Y[cc] = Wi[a * 3] * D[cc] + Wi[a * 3 + 1] * D[3 + cc] + Wi[a * 3 + 2] * D[6 + cc];
-                for (int bb = 0; bb < 6; bb++) acc[a * 6 + bb] += Y[0] * Wj[bb * 3] + Y[1] * Wj[bb * 3 + 1] + Y[2] * Wj[bb * 3 + 2];
-                if (diag) accb[a] += Y[0] * bl[0] + Y[1] * bl[1] + Y[2] * bl[2];
-            }
-        }
+            pair_item_add(p.e_blk + (size_t)ei * GBA_EBLK + 27, p.e_blk + (size_t)ej * GBA_EBLK + 27, p.Dinv + (size_t)pi * 9, p.bl + (size_t)pi * 3, diag, acc,
+                          accb);
+        });
         for (int k = 0; k < 36; k++) acc[k] = wave_sum(acc[k]);
         if (diag)
             for (int k = 0; k < 6; k++) accb[k] = wave_sum(accb[k]);
@@ -404,26 +320,7 @@ __global__ __launch_bounds__(LM_THREADS) void k_gba_front(GbaP p, int first, int
         }
     }
     __syncthreads();
-    // the children's Schur complements, left then right
-    for (int ch = 0; ch < 2; ch++) {
-        if (nd.child[ch] < 0) continue;
-        const FrontNode cn = p.nodes[nd.child[ch]];
-        const int m = 6 * (cn.nown + cn.nb), ck = 6 * cn.nown, cb = 6 * cn.nb;
-        const double* G = p.fronts + cn.front;
-        const double* gr = G + (size_t)m * m;
-        const int32_t* map = p.cmap + nd.cmap[ch];
-        for (int idx = tid; idx < cb * cb; idx += LM_THREADS) {
-            const int bi = idx / cb, bj = idx % cb;
-            if (bj > bi) continue;
-            int R = 6 * map[bi / 6] + bi % 6, Cc = 6 * map[bj / 6] + bj % 6;
-            if (R < Cc) {
-                const int t = R; R = Cc; Cc = t;
-            }
-            F[(size_t)R * n + Cc] += G[(size_t)(ck + bi) * m + ck + bj];
-        }
-        for (int bi = tid; bi < cb; bi += LM_THREADS) r[6 * map[bi / 6] + bi % 6] += gr[ck + bi];
-        __syncthreads();
-    }
+    front_merge_children<6>(nd, p.nodes, p.cmap, p.fronts, F, r);
     bool ok;
     if (n <= lds_rows) {
         for (int i = 0; i < n; i++)
@@ -449,11 +346,7 @@ __global__ __launch_bounds__(LM_THREADS) void k_gba_back(GbaP p, int first)
 {
     const GbaCtl& c = *p.ctl;
     if (c.aborted || !c.trial_go || c.fail) return;
-    const FrontNode nd = p.nodes[p.level_nodes[first + blockIdx.x]];
-    const int n = 6 * (nd.nown + nd.nb);
-    if (nd.nb == 0 || nd.nown == 0) return;
-    const double* F = p.fronts + nd.front;
-    front_substitute_back<6>(nd, p.node_vtx + nd.vtx, p.xt, F, F + (size_t)n * n, p.fronts + nd.front + (size_t)n * n + n);
+    front_back<6>(p.nodes[p.level_nodes[first + blockIdx.x]], p.fronts, p.node_vtx, p.xt);
 }
 
 // the trial poses exp(x_v) T_v.  When the system was not solved the update of the last solved trial stays, as in g2o.
@@ -494,16 +387,9 @@ __global__ __launch_bounds__(GBA_PT) void k_gba_backsub(GbaP p)
                     double r[3] = {bl[0], bl[1], bl[2]};
                     for (int e = lo; e < hi; e++) {
                         if (p.e_use[e] != 3) continue;
-                        const double* W = p.e_blk + (size_t)e * GBA_EBLK + 27;
-                        const double* x = p.xv + (size_t)p.kf_free[p.obs_kf[e]] * 6;
-                        for (int cc = 0; cc < 3; cc++) {
-                            double s = 0;
-                            for (int a = 0; a < 6; a++) s += W[a * 3 + cc] * x[a];
-                            r[cc] -= s;
-                        }
+                        point_rhs_sub(p.e_blk + (size_t)e * GBA_EBLK + 27, p.xv + (size_t)p.kf_free[p.obs_kf[e]] * 6, r);
                     }
-                    const double* D = p.Dinv + (size_t)pi * 9;
-                    for (int a = 0; a < 3; a++) xl[a] = D[a * 3] * r[0] + D[a * 3 + 1] * r[1] + D[a * 3 + 2] * r[2];
+                    point_solve(p.Dinv + (size_t)pi * 9, r, xl);
                 }
                 for (int a = 0; a < 3; a++) {
                     scale += xl[a] * (c.lm.lambda * xl[a] + bl[a]);
@@ -524,10 +410,9 @@ __global__ __launch_bounds__(GBA_PT) void k_gba_backsub(GbaP p)
         const int j = (blockIdx.x - p.npb) * GBA_PT + threadIdx.x;
         if (j < p.nme) {
             const int o = j >> 2, k = j & 3, m = p.mo_marker[o];
-            const double pm[3] = {p.mlocal[(size_t)m * 12 + 3 * k], p.mlocal[(size_t)m * 12 + 3 * k + 1], p.mlocal[(size_t)m * 12 + 3 * k + 2]};
+            const MarkerCorner mc = marker_corner(p.mlocal, p.mobs_corners, m, o, k);
             double err[2], rho[2];
-            lba_marker_error(p.pose[nxt][p.mobs_kf[o]], p.pose[nxt][p.nkf + m], pm, p.mobs_corners[(size_t)o * 8 + 2 * k],
-                             p.mobs_corners[(size_t)o * 8 + 2 * k + 1], p.K, err);
+            lba_marker_error(p.pose[nxt][p.mobs_kf[o]], p.pose[nxt][p.nkf + m], mc.pm, mc.ox, mc.oy, p.K, err);
             huber(chi2_of(err, p.marker_info), p.delta, rho);
             chi += rho[0];
         }
@@ -549,16 +434,14 @@ __global__ __launch_bounds__(LM_THREADS) void k_gba_ctl_trial(GbaP p)
     // chi2 and the points' x (lambda x + b) from the passes' partial sums, the poses' over the 6 nv unknowns: each thread a
     // contiguous run, then the workgroup
     const double lambda = c.lm.lambda;
-    const int n = 6 * p.nv, per = (n + LM_THREADS - 1) / LM_THREADS;
-    const int lo = min((int)threadIdx.x * per, n), hi = min(lo + per, n);
-    double s[3] = {gba_run_sum(p.chi_part, p.nb), gba_run_sum(p.scale_part, p.nb), 0.};
-    for (int j = lo; j < hi; j++) s[2] += p.xv[j] * (lambda * p.xv[j] + (p.v_active[j / 6] ? p.bp[j] : 0.));
+    double s[3] = {run_sum(p.chi_part, p.nb), run_sum(p.scale_part, p.nb), 0.};
+    run_for(6 * p.nv, [&](int j) { s[2] += p.xv[j] * (lambda * p.xv[j] + (p.v_active[j / 6] ? p.bp[j] : 0.)); });
     block_sum<3>(s, red);
     if (threadIdx.x != 0) return;
     if (lm_judge_trial(c.lm, s[0], c.fail == 0, s[2] + s[1])) c.cur = 1 - c.cur;
     c.trials++;
     c.fail = 0;
-    const bool halt = stop_set(p);
+    const bool halt = stop_set(p.stop);
     const bool cont = lm_try_again(c.lm) && !halt;
     c.trial_go = cont;
     if (cont) return;
@@ -598,35 +481,7 @@ __global__ __launch_bounds__(256) void k_gba_finish(GbaP p)
 }
 
 // ---------------------------------------------------------------------------------------- host --
-int report(const BaCheck& c) { return c.err ? fail(c.err, "%s", c.msg) : ORBFE_OK; }
-
-// what a call is given beside its arrays: the camera and the level table (every entry finite here), the marker weight, the switches
-int gba_fill(GbaP& p, const float* K4, const float* inv_sigma2, int nlevels, float marker_info, int use_markers, int robust, const char* name)
-{
-    BaCamera c;
-    const int rc = report(ba_camera(c, K4, inv_sigma2, nlevels, marker_info, name, 5.99));
-    if (rc) return rc;
-    for (int l = 0; l < nlevels; l++)
-        if (!std::isfinite(inv_sigma2[l])) return fail(ORBFE_ERR_INVALID, "%s: inv_level_sigma2 is not finite", name);
-    p.nlevels = nlevels;
-    for (int l = 0; l < GBA_MAX_LEVELS; l++) p.inv_sigma2[l] = c.inv_sigma2[l];
-    p.K = Cam{c.fx, c.fy, c.cx, c.cy};
-    p.marker_info = marker_info;
-    p.delta = c.delta;
-    p.use_markers = use_markers != 0;
-    p.robust = robust != 0;
-    return ORBFE_OK;
-}
-
-// The plan's tables on their way to the device, one page-locked block per (thread, device, stream).  A call overwrites the block of
-// the call before it on the same stream, so it first waits until that call's copy has left the block (an event behind the copy).
-struct GbaTablesStage {
-    PinnedBuf pinned;
-    hipEvent_t ev = nullptr;
-    bool pending = false;
-    ~GbaTablesStage() { if (ev) (void)hipEventDestroy(ev); }
-};
-thread_local ThreadWorkspaces<GbaTablesStage> tl_gba_tables;
+thread_local ThreadWorkspaces<TablesStage> tl_gba_tables;
 thread_local ThreadWorkspaces<HostStage> tl_gba_stages;
 
 struct GbaCall {
@@ -655,15 +510,8 @@ int gba_prepare(GbaCall& cl, GbaP& p, const GbaProblem& pb, int iterations, int 
     cl.level_rows = front_level_lds_rows(cl.plan, 6, cl.k.lds_rows);
     gba_pack_tables(cl.blob, cl.plan, pb);
     gba_tables(p, gba_counts(cl.plan), p.tables);
-    GbaTablesStage& ts = tl_gba_tables.get(s);
-    if (ts.pending) ORBFE_HIP(hipEventSynchronize(ts.ev));
-    if (!ts.ev) ORBFE_HIP(hipEventCreateWithFlags(&ts.ev, hipEventDisableTiming));
-    if ((rc = ts.pinned.ensure(cl.blob.size()))) return rc;
-    memcpy(ts.pinned.p, cl.blob.data(), cl.blob.size());
     ORBFE_HIP(hipMemsetAsync(scratch, 0, x.zero_end, s));
-    ORBFE_HIP(hipMemcpyAsync(p.tables, ts.pinned.p, cl.blob.size(), hipMemcpyHostToDevice, s));
-    ORBFE_HIP(hipEventRecord(ts.ev, s));
-    ts.pending = true;
+    if ((rc = tl_gba_tables.get(s).send(cl.blob, p.tables, s))) return rc;
     return ensure_dyn_lds((const void*)k_gba_front, cl.k.tri_bytes);
 }
 
@@ -677,20 +525,13 @@ int gba_enqueue_setup(const GbaCall& cl, const GbaP& p, hipStream_t s)
 
 int gba_enqueue_iteration(const GbaCall& cl, const GbaP& p, hipStream_t s, bool inspect)
 {
-    const GbaPlan& pl = cl.plan;
     hipLaunchKernelGGL(k_gba_linearize, dim3(cl.k.g_pass), dim3(GBA_PT), 0, s, p);
     hipLaunchKernelGGL(k_gba_pose_blocks, dim3(cl.k.g_vertices), dim3(LM_THREADS), 0, s, p);
     hipLaunchKernelGGL(k_gba_ctl_lin, dim3(1), dim3(LM_THREADS), 0, s, p);
     for (int q = 0; q < cl.k.trials; q++) {
         hipLaunchKernelGGL(k_gba_schur_points, dim3(cl.k.g_points), dim3(GBA_PT), 0, s, p);
         hipLaunchKernelGGL(k_gba_reduce, dim3(cl.k.g_pairs), dim3(64), 0, s, p);
-        for (int l = 0; l < pl.nlevels; l++) {
-            const int rows = cl.level_rows[(size_t)l];
-            hipLaunchKernelGGL(k_gba_front, dim3(pl.level_off[(size_t)l + 1] - pl.level_off[(size_t)l]), dim3(LM_THREADS),
-                               (size_t)rows * (rows + 1) / 2 * 8, s, p, pl.level_off[(size_t)l], rows);
-        }
-        for (int l = pl.nlevels - 2; l >= 0; l--)
-            hipLaunchKernelGGL(k_gba_back, dim3(pl.level_off[(size_t)l + 1] - pl.level_off[(size_t)l]), dim3(LM_THREADS), 0, s, p, pl.level_off[(size_t)l]);
+        front_enqueue_levels(k_gba_front, k_gba_back, cl.plan.level_off, cl.level_rows, LM_THREADS, p, s);
         hipLaunchKernelGGL(k_gba_update, dim3(cl.k.g_update), dim3(256), 0, s, p);
         hipLaunchKernelGGL(k_gba_backsub, dim3(cl.k.g_pass), dim3(GBA_PT), 0, s, p);
         if (!inspect) hipLaunchKernelGGL(k_gba_ctl_trial, dim3(1), dim3(LM_THREADS), 0, s, p);
@@ -715,7 +556,8 @@ int gba_host_begin(GbaCall& cl, GbaP& p, HostStage*& w, GbaHostIo& io, const Gba
 {
     const GbaSizes& n = pb.n;
     int rc;
-    if ((rc = report(gba_check_sizes(n, iterations, leaf_vertices, name))) || (rc = gba_fill(p, K4, inv_sigma2, nlevels, marker_info, use_markers, robust, name)) ||
+    p.robust = robust != 0;
+    if ((rc = report(gba_check_sizes(n, iterations, leaf_vertices, name))) || (rc = ba_fill(p, K4, inv_sigma2, nlevels, marker_info, use_markers, 5.99, name)) ||
         (rc = report(gba_check_graph(pb, name))) || (rc = report(gba_check_values(pb, nlevels, name))) ||
         (rc = report(gba_make_plan(cl.plan, pb, use_markers, leaf_vertices, name))))
         return rc;
@@ -811,7 +653,8 @@ extern "C" int orbfe_global_bundle_adjustment_device(float* d_Tcw, const uint8_t
     if ((rc = report(gba_check_sizes(d.n, iterations, leaf_vertices, name))) || (rc = report(gba_check_device(d, d_res, d_scratch, name)))) return rc;
     const size_t need = gba_scratch_bytes(d.n, leaf_vertices);
     if (scratch_bytes < need) return fail(ORBFE_ERR_CAPACITY, "%s: %zu bytes of scratch, orbfe_gba_scratch_bytes asks for %zu", name, scratch_bytes, need);
-    if ((rc = gba_fill(p, K4, inv_level_sigma2, nlevels, marker_info, use_markers, robust, name)) || (rc = report(gba_check_graph(d, name))) ||
+    p.robust = robust != 0;
+    if ((rc = ba_fill(p, K4, inv_level_sigma2, nlevels, marker_info, use_markers, 5.99, name)) || (rc = report(gba_check_graph(d, name))) ||
         (rc = report(gba_make_plan(cl.plan, d, use_markers, leaf_vertices, name))))
         return rc;
     p.Tcw = d_Tcw; p.x3Dw = d_x3Dw; p.obs_xy = d_obs_xy; p.obs_oct = d_obs_octave; p.obs_feat = d_obs_feature; p.kps = d_kps; p.capacity = capacity;

@@ -22,6 +22,8 @@ struct IoLayout {
 
 #ifdef __HIPCC__
 #include "orbfe_common.hpp"
+#include <cstring>
+#include <vector>
 
 namespace orbfe {
 
@@ -56,6 +58,28 @@ struct HostStage {
         return ORBFE_OK;
     }
     int sync() { ORBFE_HIP(hipStreamSynchronize(stream)); return ORBFE_OK; }
+};
+
+// A plan's tables on their way to the device (essential_graph.hip, global_ba.hip), one page-locked block per (thread, device,
+// stream).  A call overwrites the block of the call before it on the same stream, so it first waits until that call's copy has left
+// the block (an event behind the copy).
+struct TablesStage {
+    PinnedBuf pinned;
+    hipEvent_t ev = nullptr;
+    bool pending = false;
+    ~TablesStage() { if (ev) (void)hipEventDestroy(ev); }
+    int send(const std::vector<unsigned char>& blob, void* dst, hipStream_t s)
+    {
+        if (pending) ORBFE_HIP(hipEventSynchronize(ev));
+        if (!ev) ORBFE_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        const int rc = pinned.ensure(blob.size());
+        if (rc) return rc;
+        memcpy(pinned.p, blob.data(), blob.size());
+        ORBFE_HIP(hipMemcpyAsync(dst, pinned.p, blob.size(), hipMemcpyHostToDevice, s));
+        ORBFE_HIP(hipEventRecord(ev, s));
+        pending = true;
+        return ORBFE_OK;
+    }
 };
 
 // The stage of the matcher's host-pointer calls, one per (thread, device): defined in match_kernels.hip, shared with

@@ -20,6 +20,18 @@ struct Quat {
     double x, y, z, w;
 };
 
+// Eigen's Quaternion::toRotationMatrix
+__device__ __forceinline__ void rot_of(const Quat& q, double (&R)[3][3])
+{
+    const double tx = 2 * q.x, ty = 2 * q.y, tz = 2 * q.z;
+    const double twx = tx * q.w, twy = ty * q.w, twz = tz * q.w;
+    const double txx = tx * q.x, txy = ty * q.x, txz = tz * q.x;
+    const double tyy = ty * q.y, tyz = tz * q.y, tzz = tz * q.z;
+    R[0][0] = 1 - (tyy + tzz); R[0][1] = txy - twz; R[0][2] = txz + twy;
+    R[1][0] = txy + twz; R[1][1] = 1 - (txx + tzz); R[1][2] = tyz - twx;
+    R[2][0] = txz - twy; R[2][1] = tyz + twx; R[2][2] = 1 - (txx + tyy);
+}
+
 // Eigen's Quaternion(const Matrix3&): the trace branch, else the largest diagonal entry
 __device__ Quat quat_from_matrix(const double (&m)[3][3])
 {
@@ -247,6 +259,23 @@ template <int N> __device__ __forceinline__ void block_sum(double (&v)[N], doubl
             for (int ww = 1; ww < LM_WAVES; ww++) s += red[ww * N + k];
             v[k] = s;
         }
+}
+
+// "Each thread a contiguous run, then the workgroup": f(i) for the run of [0, n) that is thread threadIdx.x's of T, in index order.
+// What f adds up, block_sum (or a wave's butterfly, T = 64) adds over the threads.
+template <int T = LM_THREADS, class F> __device__ __forceinline__ void run_for(int n, F f)
+{
+    const int per = (n + T - 1) / T;
+    const int lo = min((int)threadIdx.x * per, n), hi = min(lo + per, n);
+    for (int i = lo; i < hi; i++) f(i);
+}
+
+// this thread's part of the sum of n doubles (the whole sum in thread 0 behind block_sum)
+__device__ __forceinline__ double run_sum(const double* v, int n)
+{
+    double s = 0;
+    run_for(n, [&](int i) { s += v[i]; });
+    return s;
 }
 
 __device__ __forceinline__ int block_count(int c, double* red)

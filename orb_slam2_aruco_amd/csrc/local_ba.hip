@@ -62,9 +62,7 @@ struct LbaP {
     double *S, *bs, *chi_part, *scale_part, *max_part;
 };
 
-
-// the edges, their blocks and the wave sums are ba_edges.hpp's, shared with global_ba.hip
-__device__ __forceinline__ bool stop_set(const LbaP& p) { return p.stop && *(const volatile uint8_t*)p.stop != 0; }
+// the edges, their blocks, the wave sums and the steps of the passes that global_ba.hip has too are ba_edges.hpp's
 
 // ---------------------------------------------------------------------------------------- setup --
 __global__ __launch_bounds__(256) void k_lba_setup(LbaP p)
@@ -95,37 +93,17 @@ __global__ __launch_bounds__(256) void k_lba_setup(LbaP p)
         }
     }
     if (i < p.nobs) {
-        // the point of slot i: the last point whose range starts at or before i (np > 0 here)
-        int lo = 0, hi = p.np - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (p.obs_offset[mid] <= i) lo = mid;
-            else hi = mid - 1;
-        }
-        const int pt = lo;
-        int kf = p.obs_kf[i], oct = 0;
-        float ox = 0.f, oy = 0.f;
+        const int pt = obs_point(p.obs_offset, p.np, i);
+        int kf = p.obs_kf[i];
+        ObsPixel o;
         if (kf < 0 || kf >= p.nkf) {
-            bad |= LBA_BAD_INVALID;
+            o.ok = false;
             kf = 0;
-        } else if (p.obs_xy) {
-            ox = p.obs_xy[(size_t)i * 2];
-            oy = p.obs_xy[(size_t)i * 2 + 1];
-            oct = p.obs_oct[i];
         } else {
-            const int f = p.obs_feat[i];
-            if (f < 0 || f >= p.capacity) bad |= LBA_BAD_INVALID;
-            else {
-                const orbfe_keypoint kp = p.kps[(size_t)kf * p.capacity + f];
-                ox = kp.x; oy = kp.y; oct = kp.octave;
-            }
+            o = obs_pixel(i, kf, p.obs_xy, p.obs_oct, p.obs_feat, p.kps, p.capacity, p.nlevels);
         }
-        if (oct < 0 || oct >= p.nlevels) {
-            bad |= LBA_BAD_INVALID;
-            oct = 0;
-        }
-        if (!finite_f(ox) || !finite_f(oy)) bad |= LBA_BAD_INVALID;
-        p.e_kf[i] = kf; p.e_pt[i] = pt; p.e_ox[i] = ox; p.e_oy[i] = oy; p.e_info[i] = p.inv_sigma2[oct];
+        if (!o.ok) bad |= LBA_BAD_INVALID;
+        p.e_kf[i] = kf; p.e_pt[i] = pt; p.e_ox[i] = o.x; p.e_oy[i] = o.y; p.e_info[i] = p.inv_sigma2[o.oct];
         if (atomicCAS(&p.tbl[(size_t)kf * p.np + pt], -1, i) != -1) bad |= LBA_BAD_INVALID;   // a keyframe observes a point once
     }
     if (i < p.nma) {
@@ -165,13 +143,13 @@ __global__ void k_lba_begin(LbaP p, int round)
         c.nv = nv;
         if (c.bad & LBA_BAD_INVALID) c.abort_status = ORBFE_ERR_INVALID;
         else if ((c.bad & LBA_BAD_CAPACITY) || nv > LBA_MAXV) c.abort_status = ORBFE_ERR_CAPACITY;
-        else if (stop_set(p)) c.abort_status = ORBFE_LBA_STOPPED;
+        else if (stop_set(p.stop)) c.abort_status = ORBFE_LBA_STOPPED;
         c.aborted = c.abort_status != 0;
         if (c.aborted) c.nv = 0;
         c.iter_go = !c.aborted;
     } else {
         if (c.aborted) return;
-        if (stop_set(p)) c.stopped = 1;
+        if (stop_set(p.stop)) c.stopped = 1;
         c.iter_go = !c.stopped;
     }
     c.round = round;
@@ -240,30 +218,11 @@ __global__ __launch_bounds__(LBA_PT) void k_lba_linearize(LbaP p)
             else {
                 const int o = j >> 2, k = j & 3, kf = p.mobs_kf[o], m = p.mo_marker[o];
                 const SE3 Tc = p.pose[cur][kf], Tm = p.pose[cur][p.nkf + m];
-                const double pm[3] = {p.mlocal[(size_t)m * 12 + 3 * k], p.mlocal[(size_t)m * 12 + 3 * k + 1], p.mlocal[(size_t)m * 12 + 3 * k + 2]};
-                const double ox = p.mobs_corners[(size_t)o * 8 + 2 * k], oy = p.mobs_corners[(size_t)o * 8 + 2 * k + 1];
-                const bool camfree = p.kf_free[kf] >= 0;
-                double err[2], Jc[2][6], Jm[2][6], rho[2];
-                lba_marker_error(Tc, Tm, pm, ox, oy, p.K, err);
-                const double ch = chi2_of(err, p.marker_info);
+                double ch, rho0;
+                p.m_use[j] = marker_edge_linearize(Tc, Tm, marker_corner(p.mlocal, p.mobs_corners, m, o, k), p.K, p.kf_free[kf] >= 0, robust,
+                                                   p.marker_info, p.delta, p.m_blk + (size_t)j * LBA_MBLK, ch, rho0);
                 p.m_chi2[j] = ch;
-                rho[0] = ch; rho[1] = 1.;
-                if (robust) huber(ch, p.delta, rho);
-                chi += rho[0];
-                for (int a = 0; a < 6; a++) Jc[0][a] = Jc[1][a] = 0;
-                if (camfree) lba_marker_jacobian(Tc, Tm, true, pm, ox, oy, p.K, Jc);
-                lba_marker_jacobian(Tc, Tm, false, pm, ox, oy, p.K, Jm);
-                const bool fin = all_finite(err, 2) && all_finite(&Jc[0][0], 12) && all_finite(&Jm[0][0], 12) && isfinite(rho[1]);
-                p.m_use[j] = fin ? 1 : 0;
-                if (fin) {
-                    const double w = rho[1] * p.marker_info;
-                    const double r0 = rho[1] * -(p.marker_info * err[0]), r1 = rho[1] * -(p.marker_info * err[1]);
-                    double* out = p.m_blk + (size_t)j * LBA_MBLK;
-                    lba_diag_block(Jc, w, r0, r1, out);
-                    lba_diag_block(Jm, w, r0, r1, out + 27);
-                    for (int a = 0; a < 6; a++)
-                        for (int cc = 0; cc < 6; cc++) out[54 + a * 6 + cc] = Jc[0][a] * (w * Jm[0][cc]) + Jc[1][a] * (w * Jm[1][cc]);
-                }
+                chi += rho0;
             }
         }
     }
@@ -286,18 +245,15 @@ __global__ __launch_bounds__(LM_THREADS) void k_lba_pose_blocks(LbaP p)
     const int kf = p.v_kf[v];
     double s[28];
     for (int k = 0; k < 28; k++) s[k] = 0;
-    if (kf < p.nkf) {
-        const int per = (p.np + LM_THREADS - 1) / LM_THREADS;
-        const int lo = min(tid * per, p.np), hi = min(lo + per, p.np);
-        for (int pi = lo; pi < hi; pi++) {
+    if (kf < p.nkf)
+        run_for(p.np, [&](int pi) {
             const int e = p.tbl[(size_t)kf * p.np + pi];
-            if (e < 0 || p.e_level[e]) continue;
+            if (e < 0 || p.e_level[e]) return;
             s[27] += 1;
-            if (p.e_use[e] != 3) continue;
+            if (p.e_use[e] != 3) return;
             const double* blk = p.e_blk + (size_t)e * LBA_EBLK;
             for (int k = 0; k < 27; k++) s[k] += blk[k];
-        }
-    }
+        });
     block_sum<28>(s, red);
     if (tid != 0) return;
     if (kf < p.nkf) {
@@ -318,27 +274,9 @@ __global__ __launch_bounds__(LM_THREADS) void k_lba_pose_blocks(LbaP p)
             for (int k = 0; k < 27; k++) s[k] += blk[k];
         }
     }
-    double* H = p.Hpp + (size_t)v * 36;
-    int k = 0;
-    double md = 0;
-    for (int a = 0; a < 6; a++)
-        for (int cc = a; cc < 6; cc++, k++) H[a * 6 + cc] = H[cc * 6 + a] = s[k];
-    for (int a = 0; a < 6; a++) {
-        p.bp[v * 6 + a] = s[21 + a];
-        md = fmax(md, fabs(s[a * 6 - a * (a - 1) / 2]));   // the diagonal entries of the packed upper triangle: 0, 6, 11, 15, 18, 20
-    }
+    const double md = unpack_pose_sums(s, p.Hpp + (size_t)v * 36, p.bp + v * 6);
     p.v_active[v] = s[27] > 0;
     p.vmax[v] = s[27] > 0 ? md : 0;
-}
-
-// the sum of n per-workgroup partial sums: each thread a contiguous run, then the workgroup (valid in thread 0)
-__device__ __forceinline__ double part_sum(const double* part, int n)
-{
-    const int per = (n + LM_THREADS - 1) / LM_THREADS;
-    const int lo = min((int)threadIdx.x * per, n), hi = min(lo + per, n);
-    double s = 0;
-    for (int i = lo; i < hi; i++) s += part[i];
-    return s;
 }
 
 __global__ __launch_bounds__(LM_THREADS) void k_lba_ctl_lin(LbaP p)
@@ -347,7 +285,7 @@ __global__ __launch_bounds__(LM_THREADS) void k_lba_ctl_lin(LbaP p)
     __shared__ double mx[LM_THREADS];
     LbaCtl& c = *p.ctl;
     if (c.aborted || !c.iter_go) return;
-    double s[1] = {part_sum(p.chi_part, p.nb)};
+    double s[1] = {run_sum(p.chi_part, p.nb)};
     double m = 0;
     for (int i = threadIdx.x; i < p.nb; i += LM_THREADS) m = fmax(m, p.max_part[i]);
     mx[threadIdx.x] = m;
@@ -364,21 +302,14 @@ __global__ __launch_bounds__(LM_THREADS) void k_lba_ctl_lin(LbaP p)
 }
 
 // ---------------------------------------------------------------------------------------- a trial --
-// (Hll + lambda I)^-1 by cofactors (Eigen's 3 x 3 inverse)
+// (Hll + lambda I)^-1 of every active point
 __global__ __launch_bounds__(LBA_PT) void k_lba_schur_points(LbaP p)
 {
     const LbaCtl& c = *p.ctl;
     if (c.aborted || !c.trial_go) return;
     const int pi = blockIdx.x * LBA_PT + threadIdx.x;
     if (pi >= p.np || !p.p_active[pi]) return;
-    const double* H = p.Hll + (size_t)pi * 6;
-    const double m00 = H[0] + c.lm.lambda, m01 = H[1], m02 = H[2], m11 = H[3] + c.lm.lambda, m12 = H[4], m22 = H[5] + c.lm.lambda;
-    const double c00 = m11 * m22 - m12 * m12, c10 = m12 * m02 - m01 * m22, c20 = m01 * m12 - m11 * m02;
-    const double det = c00 * m00 + c10 * m01 + c20 * m02, id = 1. / det;
-    double* D = p.Dinv + (size_t)pi * 9;
-    D[0] = c00 * id; D[1] = c10 * id; D[2] = c20 * id;
-    D[3] = D[1]; D[4] = (m00 * m22 - m02 * m02) * id; D[5] = (m02 * m01 - m00 * m12) * id;
-    D[6] = D[2]; D[7] = D[5]; D[8] = (m00 * m11 - m01 * m01) * id;
+    damped_inverse3(p.Hll + (size_t)pi * 6, c.lm.lambda, p.Dinv + (size_t)pi * 9);
 }
 
 // block (i, j), i <= j, of S and the rows i of its right-hand side; one wave
@@ -393,23 +324,13 @@ __global__ __launch_bounds__(64) void k_lba_assemble(LbaP p)
     for (int k = 0; k < 36; k++) acc[k] = 0;
     for (int k = 0; k < 6; k++) accb[k] = 0;
     if (act && ki < p.nkf && kj < p.nkf) {
-        const int per = (p.np + 63) / 64;
-        const int lo = min(lane * per, p.np), hi = min(lo + per, p.np);
-        for (int pi = lo; pi < hi; pi++) {
-            if (!p.p_active[pi]) continue;
+        run_for<64>(p.np, [&](int pi) {
+            if (!p.p_active[pi]) return;
             const int ei = p.tbl[(size_t)ki * p.np + pi], ej = p.tbl[(size_t)kj * p.np + pi];
-            if (ei < 0 || ej < 0 || p.e_level[ei] || p.e_level[ej] || p.e_use[ei] != 3 || p.e_use[ej] != 3) continue;
-            const double* Wi = p.e_blk + (size_t)ei * LBA_EBLK + 27;
-            const double* Wj = p.e_blk + (size_t)ej * LBA_EBLK + 27;
-            const double* D = p.Dinv + (size_t)pi * 9;
-            const double* bl = p.bl + (size_t)pi * 3;
-            for (int a = 0; a < 6; a++) {
-                double Y[3];
-                for (int cc = 0; cc < 3; cc++) Y[cc] = Wi[a * 3] * D[cc] + Wi[a * 3 + 1] * D[3 + cc] + Wi[a * 3 + 2] * D[6 + cc];
-                for (int bb = 0; bb < 6; bb++) acc[a * 6 + bb] += Y[0] * Wj[bb * 3] + Y[1] * Wj[bb * 3 + 1] + Y[2] * Wj[bb * 3 + 2];
-                if (i == j) accb[a] += Y[0] * bl[0] + Y[1] * bl[1] + Y[2] * bl[2];
-            }
-        }
+            if (ei < 0 || ej < 0 || p.e_level[ei] || p.e_level[ej] || p.e_use[ei] != 3 || p.e_use[ej] != 3) return;
+            pair_item_add(p.e_blk + (size_t)ei * LBA_EBLK + 27, p.e_blk + (size_t)ej * LBA_EBLK + 27, p.Dinv + (size_t)pi * 9, p.bl + (size_t)pi * 3, i == j,
+                          acc, accb);
+        });
         for (int k = 0; k < 36; k++) acc[k] = wave_sum(acc[k]);
         if (i == j)
             for (int k = 0; k < 6; k++) accb[k] = wave_sum(accb[k]);
@@ -543,16 +464,9 @@ __global__ __launch_bounds__(LBA_PT) void k_lba_backsub(LbaP p)
                     double r[3] = {bl[0], bl[1], bl[2]};
                     for (int e = lo; e < hi; e++) {
                         if (p.e_level[e] || p.e_use[e] != 3) continue;
-                        const double* W = p.e_blk + (size_t)e * LBA_EBLK + 27;
-                        const double* x = p.xv + (size_t)p.kf_free[p.e_kf[e]] * 6;
-                        for (int cc = 0; cc < 3; cc++) {
-                            double s = 0;
-                            for (int a = 0; a < 6; a++) s += W[a * 3 + cc] * x[a];
-                            r[cc] -= s;
-                        }
+                        point_rhs_sub(p.e_blk + (size_t)e * LBA_EBLK + 27, p.xv + (size_t)p.kf_free[p.e_kf[e]] * 6, r);
                     }
-                    const double* D = p.Dinv + (size_t)pi * 9;
-                    for (int a = 0; a < 3; a++) xl[a] = D[a * 3] * r[0] + D[a * 3 + 1] * r[1] + D[a * 3 + 2] * r[2];
+                    point_solve(p.Dinv + (size_t)pi * 9, r, xl);
                 }
                 for (int a = 0; a < 3; a++) {
                     scale += xl[a] * (c.lm.lambda * xl[a] + bl[a]);
@@ -575,10 +489,9 @@ __global__ __launch_bounds__(LBA_PT) void k_lba_backsub(LbaP p)
         const int j = (blockIdx.x - p.npb) * LBA_PT + threadIdx.x;
         if (j < p.nme && !p.m_level[j]) {
             const int o = j >> 2, k = j & 3, m = p.mo_marker[o];
-            const double pm[3] = {p.mlocal[(size_t)m * 12 + 3 * k], p.mlocal[(size_t)m * 12 + 3 * k + 1], p.mlocal[(size_t)m * 12 + 3 * k + 2]};
+            const MarkerCorner mc = marker_corner(p.mlocal, p.mobs_corners, m, o, k);
             double err[2], rho[2];
-            lba_marker_error(p.pose[nxt][p.mobs_kf[o]], p.pose[nxt][p.nkf + m], pm, p.mobs_corners[(size_t)o * 8 + 2 * k],
-                             p.mobs_corners[(size_t)o * 8 + 2 * k + 1], p.K, err);
+            lba_marker_error(p.pose[nxt][p.mobs_kf[o]], p.pose[nxt][p.nkf + m], mc.pm, mc.ox, mc.oy, p.K, err);
             const double ch = chi2_of(err, p.marker_info);
             p.m_chi2[j] = ch;
             rho[0] = ch;
@@ -600,7 +513,7 @@ __global__ __launch_bounds__(LM_THREADS) void k_lba_ctl_trial(LbaP p, int maxit)
     __shared__ double red[LM_WAVES * 2];
     LbaCtl& c = *p.ctl;
     if (c.aborted || !c.trial_go) return;
-    double s[2] = {part_sum(p.chi_part, p.nb), part_sum(p.scale_part, p.nb)};
+    double s[2] = {run_sum(p.chi_part, p.nb), run_sum(p.scale_part, p.nb)};
     block_sum<2>(s, red);
     if (threadIdx.x != 0) return;
     double scale = 0;
@@ -612,7 +525,7 @@ __global__ __launch_bounds__(LM_THREADS) void k_lba_ctl_trial(LbaP p, int maxit)
     } else {
         c.stale = 1;
     }
-    const bool halt = stop_set(p);
+    const bool halt = stop_set(p.stop);
     const bool cont = lm_try_again(c.lm) && !halt;
     c.trial_go = cont;
     if (cont) return;
@@ -677,25 +590,6 @@ __global__ __launch_bounds__(256) void k_lba_finish(LbaP p)
 }
 
 // ---------------------------------------------------------------------------------------- host --
-int report(const BaCheck& c) { return c.err ? fail(c.err, "%s", c.msg) : ORBFE_OK; }
-
-// what a call is given beside its arrays: the camera and the level table (every entry finite here), the marker weight and switch
-int lba_fill(LbaP& p, const float* K4, const float* inv_sigma2, int nlevels, float marker_info, int use_markers, const char* name)
-{
-    BaCamera c;
-    const int rc = report(ba_camera(c, K4, inv_sigma2, nlevels, marker_info, name));
-    if (rc) return rc;
-    for (int l = 0; l < nlevels; l++)
-        if (!std::isfinite(inv_sigma2[l])) return fail(ORBFE_ERR_INVALID, "%s: inv_level_sigma2 is not finite", name);
-    p.nlevels = nlevels;
-    for (int l = 0; l < LBA_MAX_LEVELS; l++) p.inv_sigma2[l] = c.inv_sigma2[l];
-    p.K = Cam{c.fx, c.fy, c.cx, c.cy};
-    p.marker_info = marker_info;
-    p.delta = c.delta;
-    p.use_markers = use_markers != 0;
-    return ORBFE_OK;
-}
-
 // the launches of one call, every number from the schedule: inspect = one linearisation and one trial, nothing written to the
 // caller's arrays
 int lba_enqueue(LbaP& p, void* scratch, hipStream_t s, bool inspect)
@@ -771,7 +665,7 @@ int lba_host_begin(LbaP& p, HostStage*& w, LbaHostIo& io, const LbaProblem& pb, 
                    float marker_info, int use_markers, const uint8_t* stop, int device, const char* name)
 {
     int rc;
-    if ((rc = lba_fill(p, K4, inv_sigma2, nlevels, marker_info, use_markers, name)) || (rc = report(lba_check_host(pb, nlevels, use_markers, name))))
+    if ((rc = ba_fill(p, K4, inv_sigma2, nlevels, marker_info, use_markers, 5.991, name)) || (rc = report(lba_check_host(pb, nlevels, use_markers, name))))
         return rc;
     if (stop && *stop) return ORBFE_LBA_STOPPED;
     if ((rc = use_device(device))) return rc;
@@ -837,7 +731,7 @@ extern "C" int orbfe_local_bundle_adjustment_device(float* d_Tcw, const uint8_t*
     LbaP p{};
     int rc;
     if ((rc = report(lba_check_device(d, d_erase, d_res, d_scratch, name))) || (rc = report(lba_check_scratch(d.n, scratch_bytes, name))) ||
-        (rc = lba_fill(p, K4, inv_level_sigma2, nlevels, marker_info, use_markers, name)))
+        (rc = ba_fill(p, K4, inv_level_sigma2, nlevels, marker_info, use_markers, 5.991, name)))
         return rc;
     p.Tcw = d_Tcw; p.kf_fixed = d_kf_fixed; p.x3Dw = d_x3Dw; p.obs_offset = d_obs_offset; p.obs_kf = d_obs_kf; p.obs_xy = d_obs_xy;
     p.obs_oct = d_obs_octave; p.obs_feat = d_obs_feature; p.kps = d_kps; p.capacity = capacity;

@@ -4,7 +4,8 @@ probe()  tests/solver_units_probe.hip, compiled once per process into a temporar
          gives the library's sources (device_units_build.hipcc_command), loaded with ctypes.  The probe includes
          csrc/{se3_quat,sim3_group,svd_jacobi,front_solve,ba_edges}.hpp unchanged; it is not part of liborbfe.so.
 host()   the CPU restatements of the same helpers (glibc's libm, g++ -ffp-contract=off) through ref_build.build_shared:
-         tests/solver_units_host.cpp (the SE3Quat of g2o_ref.hpp), essential_ref.cpp (g2o::Sim3), initializer_ref.cpp (jacobi_svd),
+         tests/solver_units_host.cpp (the SE3Quat of g2o_ref.hpp; the passes' shared steps, sequentially), essential_ref.cpp
+         (g2o::Sim3), initializer_ref.cpp (jacobi_svd),
          lba_ref.cpp (the marker edge).
 
 The wrappers take and return numpy arrays.  Where a helper has both sides the first argument `L` is probe() or host(); the Sim3 and SVD
@@ -35,6 +36,9 @@ _DEVICE = {"su_device_count": [], "su_lm_threads": [], "su_sim3_exp": [vp, vp, i
            "su_front_back6": [i32, i32, i32, i32, vp, vp, vp, vp], "su_front_back7": [i32, i32, i32, i32, vp, vp, vp, vp],
            "su_mono": [vp, vp, vp, vp, vp, i32], "su_marker": [vp, vp, vp, vp, vp, vp, i32], "su_diag": [vp, vp, i32],
            "su_rot_of": [vp, vp, i32], "su_wave": [i32, vp, vp, i32]}
+# the shared steps of the passes: on both sides (L = probe() or host())
+_PASSES = {"su_lm_threads": [], "su_dinv3": [vp, vp, i32], "su_pair_items": [vp, vp, vp, i32, i32, vp, vp, i32],
+           "su_merge": [i32, vp, i32, vp, i32, vp, i32, i32], "su_run_sum": [vp, i32, vp]}
 SVD_SHAPES = solver_units_cases.SVD_SHAPES      # (M, N, N1, WANT_U) of the four product instantiations of svd_jacobi
 
 
@@ -47,7 +51,7 @@ def probe():
     global _probe
     if _probe is None:
         so = compile_probe(os.path.join(tempfile.mkdtemp(prefix="solver_units_"), "solver_units_probe.so"))
-        _probe = D._declare(D._declare(C.CDLL(so), _SE3), _DEVICE)
+        _probe = D._declare(D._declare(D._declare(C.CDLL(so), _SE3), _DEVICE), _PASSES)
     return _probe
 
 
@@ -63,7 +67,7 @@ def host():
         init.ref_jacobi_svd.argtypes, init.ref_jacobi_svd.restype = [vp, i32, i32, i32, vp, vp], None
         lba = ref_build.build_shared("lba_ref.cpp")
         lba.ref_lba_marker_edge.argtypes, lba.ref_lba_marker_edge.restype = [vp] * 8, None
-        se3 = D._declare(ref_build.build_shared("solver_units_host.cpp", prefix="solver_units_host_"), _SE3)
+        se3 = D._declare(D._declare(ref_build.build_shared("solver_units_host.cpp", prefix="solver_units_host_"), _SE3), _PASSES)
         _host = types.SimpleNamespace(se3=se3, eg=eg, init=init, lba=lba)
     return _host
 
@@ -237,6 +241,51 @@ def diag_block(J, w, r0, r1):
 
 def rot_of(q):
     return _call(probe().su_rot_of, "su_rot_of", (4,), 9, q).reshape(-1, 3, 3)
+
+
+# ---- the steps the passes share (L = probe() or host()): csrc/ba_edges.hpp, front_solve.hpp, lm_dense.hpp
+def dinv3(L, H6, lam):
+    """damped_inverse3: (Hll + lambda I)^-1 of n packed upper triangles, n x 3 x 3"""
+    H6 = _in(H6, np.float64).reshape(-1, 6)
+    return _call(_se3lib(L).su_dinv3, "su_dinv3", (7,), 9, np.concatenate([H6, _in(lam, np.float64).reshape(-1, 1)], 1)).reshape(-1, 3, 3)
+
+
+def pair_items(L, Wi, Wj, Dm, bl, diag, acc, accb):
+    """pair_item_add over the items of nsys systems, item after item: Wi, Wj nsys x nitems x 6 x 3, Dm nsys x nitems x 3 x 3, bl nsys x
+    nitems x 3; acc nsys x 6 x 6 and accb nsys x 6 are the accumulators' starts; returns them behind the items"""
+    Wi, Wj, Dm, bl = _in(Wi, np.float64), _in(Wj, np.float64), _in(Dm, np.float64), _in(bl, np.float64)
+    nsys, nitems = Wi.shape[:2]
+    assert Wi.shape == Wj.shape == (nsys, nitems, 6, 3) and Dm.shape == (nsys, nitems, 3, 3) and bl.shape == (nsys, nitems, 3)
+    w = np.ascontiguousarray(np.concatenate([Wi.reshape(nsys, nitems, 18), Wj.reshape(nsys, nitems, 18)], 2))
+    acc, accb = np.array(acc, np.float64, order="C"), np.array(accb, np.float64, order="C")
+    assert acc.shape == (nsys, 6, 6) and accb.shape == (nsys, 6)
+    _ok(_se3lib(L).su_pair_items(_p(w), _p(Dm), _p(bl), nitems, int(bool(diag)), _p(acc), _p(accb), nsys), "su_pair_items")
+    return acc, accb
+
+
+def merge(L, R, desc, cmap, fronts, node):
+    """front_merge_children<R> of node `node`: desc nn x 7 (front offset, nown, nb, child[2], cmap[2]), fronts the doubles of every front
+    (returned).  Every front, every child and every map entry is checked to lie inside before the call."""
+    desc, cmap, fronts = _in(desc, np.int32), _in(cmap, np.int32), np.array(fronts, np.float64, order="C")
+    nn = len(desc)
+    assert R in (6, 7) and desc.shape == (nn, 7) and 0 <= node < nn
+    for off, nown, nb, c0, c1, m0, m1 in desc:
+        n = R * (nown + nb)
+        assert 0 <= off and off + n * n + 2 * n <= len(fronts) and nown >= 0 and nb >= 0
+        for c, m in ((c0, m0), (c1, m1)):
+            assert -1 <= c < nn
+            if c >= 0:
+                assert 0 <= m and m + desc[c][2] <= len(cmap) and (0 <= cmap[m:m + desc[c][2]]).all() and (cmap[m:m + desc[c][2]] < nown + nb).all()
+    _ok(_se3lib(L).su_merge(R, _p(desc), nn, _p(cmap), len(cmap), _p(fronts), len(fronts), node), "su_merge")
+    return fronts
+
+
+def run_sum(L, v):
+    """run_sum followed by block_sum over one workgroup"""
+    v = _in(v, np.float64).ravel()
+    out = np.full(1, np.nan)
+    _ok(_se3lib(L).su_run_sum(_p(v), len(v), _p(out)), "su_run_sum")
+    return out[0]
 
 
 SUM, MAX = 0, 1

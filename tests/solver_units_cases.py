@@ -1233,3 +1233,117 @@ def wave_rows_with_nan():
     at = np.array([0, 1, 31, 32, 63, 17])[np.arange(len(rows)) % 6]
     rows[np.arange(len(rows)), at] = np.nan
     return rows
+
+
+# ====================================================================================== the steps the passes share
+DINV_N = 65          # a second wave of the probe's workgroup runs with one lane
+
+
+def dinv_inputs():
+    """(Hll packed 00 01 02 11 12 22, lambda, class) of DINV_N systems: the identity with lambda 0; J^T J of two and of six random
+    observations (J 2 x 3 each) with lambda = 1e-4 x the largest diagonal entry; J^T J of a single observation, rank 2, plus such a
+    lambda -- the shape at which a wrong cofactor shows, since the inverse's large entries are cofactors over a small determinant"""
+    rng = np.random.default_rng(2101)
+    H, lam, cls = [np.array([1., 0, 0, 1, 0, 1])], [0.0], ["identity"]
+    for name, nobs, count in (("two", 2, 22), ("six", 6, 21), ("single", 1, 21)):
+        for _ in range(count):
+            J = rng.normal(size=(2 * nobs, 3)) * 10 ** rng.uniform(-1, 2)
+            A = J.T @ J
+            H.append(A[np.triu_indices(3)])
+            lam.append(1e-4 * A.diagonal().max())
+            cls.append(name)
+    assert len(H) == DINV_N
+    return np.array(H), np.array(lam), cls
+
+
+def dinv_full(H6, lam):
+    M = np.zeros((len(H6), 3, 3))
+    iu = np.triu_indices(3)
+    M[:, iu[0], iu[1]] = H6
+    M[:, iu[1], iu[0]] = H6
+    return M + lam[:, None, None] * np.eye(3)
+
+
+def dinv_bound(M):
+    """|D M - I| of the cofactor inverse in doubles, entry by entry.  With m = max |M_ij|: a cofactor is p - q, |p|, |q| <= m^2, off by
+    3 eps m^2; the determinant, three cofactors times an entry, by 20 eps m^3 at most; so an entry of D = C / det by
+    3 eps m^2 / |det| + max |M^-1| (2 + 20 g) eps, g = m^3 / |det|, and a row of D M adds three of them times m:
+        3 eps (3 g + k (2 + 20 g)),   k = m max |M^-1|, the condition number in the max norm (g <= 81 k^2)"""
+    Mm = MP.matrix(M.tolist())
+    m = max(abs(Mm[i, j]) for i in range(3) for j in range(3))
+    inv = Mm ** -1
+    g = m ** 3 / abs(MP.det(Mm))
+    k = m * max(abs(inv[i, j]) for i in range(3) for j in range(3))
+    return float(3 * EPS * (3 * g + k * (2 + 20 * g))), float(k)
+
+
+PAIR_NSYS = 5
+PAIR_CASES = tuple((nitems, diag) for nitems in (0, 1, 3) for diag in (False, True))
+
+
+def pair_inputs(nitems, diag):
+    """random W_i, W_j (6 x 3), D (3 x 3), bl per item, and accumulators that start non-zero"""
+    rng = np.random.default_rng(2200 + 10 * nitems + int(diag))
+    Wi, Wj = rng.normal(size=(PAIR_NSYS, nitems, 6, 3)), rng.normal(size=(PAIR_NSYS, nitems, 6, 3))
+    return Wi, Wj, rng.normal(size=(PAIR_NSYS, nitems, 3, 3)), rng.normal(size=(PAIR_NSYS, nitems, 3)), rng.normal(size=(PAIR_NSYS, 6, 6)), rng.normal(size=(PAIR_NSYS, 6))
+
+
+def merge_case(R, seed=2300):
+    """desc, cmap, fronts of four nodes: 0 the parent (1 own vertex, 2 boundary), 1 its left child (1 own, boundary mapped {2, 0}: it
+    arrives reversed, so the row / column swap runs), 2 its right child (2 own, boundary mapped {0}: the parent's block (0, 0) receives
+    both children), 3 a node of the parent's shape with the right child alone.  Every double of every front is random."""
+    shapes = ((1, 2), (1, 2), (2, 1), (1, 2))
+    off, desc = 0, []
+    for nown, nb in shapes:
+        n = R * (nown + nb)
+        desc.append([off, nown, nb, -1, -1, 0, 0])
+        off += n * n + 2 * n
+    desc[0][3:] = [1, 2, 0, 2]
+    desc[3][3:] = [-1, 2, 0, 2]
+    rng = np.random.default_rng(seed + R)
+    return np.array(desc, np.int32), np.array([2, 0, 0], np.int32), rng.normal(size=off) * 10 ** rng.uniform(-3, 3, off)
+
+
+def merge_dense(R, desc, cmap, fronts, node, order=(0, 1)):
+    """the same by dense algebra: the child's boundary block made symmetric, scattered by the map, its lower triangle added; children
+    in `order`"""
+    out = fronts.copy()
+    off, nown, nb = desc[node][:3]
+    n = R * (nown + nb)
+    F, r = out[off:off + n * n].reshape(n, n), out[off + n * n:off + n * n + n]
+    for ch in order:
+        c = desc[node][3 + ch]
+        if c < 0:
+            continue
+        coff, cown, cnb = desc[c][:3]
+        m, ck = R * (cown + cnb), R * cown
+        G = fronts[coff:coff + m * m].reshape(m, m)[ck:, ck:]
+        G = np.tril(G) + np.tril(G, -1).T
+        idx = np.concatenate([R * v + np.arange(R) for v in cmap[desc[node][5 + ch]:desc[node][5 + ch] + cnb]])
+        T = np.zeros((n, n))
+        T[np.ix_(idx, idx)] = G
+        F += np.tril(T)          # the places the child does not reach get + 0.0, which leaves every finite double as it is
+        t = np.zeros(n)
+        t[idx] = fronts[coff + m * m + ck:coff + m * m + m]
+        r += t
+    return out
+
+
+RUN_SUM_THREADS = 256
+RUN_SUM_SIZES = (0, 1, RUN_SUM_THREADS - 1, RUN_SUM_THREADS + 1, 3 * RUN_SUM_THREADS + 5)
+
+
+def run_sum_inputs(n):
+    rng = np.random.default_rng(2400 + n)
+    return rng.normal(size=n) * 10 ** rng.uniform(-8, 8, n)
+
+
+def run_sum_strided(v, threads=RUN_SUM_THREADS):
+    """another order: thread t adds v[t], v[t + threads], ..; then the same butterfly and waves"""
+    part = np.zeros(threads)
+    for i, x in enumerate(v):
+        part[i % threads] += x
+    total = 0.0
+    for i, w in enumerate(butterfly(part.reshape(-1, 64), np.add)[:, 0]):
+        total = w if i == 0 else total + w
+    return total

@@ -340,6 +340,46 @@ __global__ __launch_bounds__(TPB) void k_wave(int op, const double* in, double* 
     out[row * 64 + lane] = op == 0 ? wave_sum(v) : wave_max(v);
 }
 
+// in7 = Hll[6] lambda
+__global__ __launch_bounds__(TPB) void k_dinv3(const double* in7, double* d9, int n)
+{
+    const int i = blockIdx.x * TPB + threadIdx.x;
+    if (i >= n) return;
+    damped_inverse3(in7 + 7 * i, in7[7 * i + 6], d9 + 9 * i);
+}
+// a thread a system of nitems items, the accumulators in / out: w nsys x nitems x 2 x 18 (Wi, Wj), d nsys x nitems x 9, bl nsys x nitems x 3
+__global__ __launch_bounds__(TPB) void k_pair_items(const double* w, const double* d, const double* bl, int nitems, int diag, double* acc36, double* accb6,
+                                                    int nsys)
+{
+    const int i = blockIdx.x * TPB + threadIdx.x;
+    if (i >= nsys) return;
+    double acc[36], accb[6];
+    for (int k = 0; k < 36; k++) acc[k] = acc36[36 * i + k];
+    for (int k = 0; k < 6; k++) accb[k] = accb6[6 * i + k];
+    for (int it = 0; it < nitems; it++) {
+        const size_t q = (size_t)i * nitems + it;
+        pair_item_add(w + q * 36, w + q * 36 + 18, d + q * 9, bl + q * 3, diag != 0, acc, accb);
+    }
+    for (int k = 0; k < 36; k++) acc36[36 * i + k] = acc[k];
+    for (int k = 0; k < 6; k++) accb6[6 * i + k] = accb[k];
+}
+// one workgroup: the children of nodes[node] into its front
+template <int R> __global__ __launch_bounds__(LM_THREADS) void k_merge(const FrontNode* nodes, int node, const int32_t* cmap, double* fronts)
+{
+    const FrontNode nd = nodes[node];
+    const int n = R * (nd.nown + nd.nb);
+    double* F = fronts + nd.front;
+    front_merge_children<R>(nd, nodes, cmap, fronts, F, F + (size_t)n * n);
+}
+// one workgroup: run_sum, then block_sum
+__global__ __launch_bounds__(LM_THREADS) void k_run_sum(const double* v, int n, double* out)
+{
+    __shared__ double red[LM_WAVES];
+    double s[1] = {run_sum(v, n)};
+    block_sum<1>(s, red);
+    if (threadIdx.x == 0) out[0] = s[0];
+}
+
 // out = f(in...) over n items of the given widths, all doubles
 template <class K> int call1(K kernel, const double* in, int win, double* out, int wout, int n)
 {
@@ -487,6 +527,60 @@ int su_marker(const float* tcw12, const float* twm12, const double* p3, const do
 }
 int su_diag(const double* in15, double* out27, int n) { return call1(k_diag, in15, 15, out27, 27, n); }
 int su_rot_of(const double* q4, double* r9, int n) { return call1(k_rot_of, q4, 4, r9, 9, n); }
+int su_dinv3(const double* in7, double* d9, int n) { return call1(k_dinv3, in7, 7, d9, 9, n); }
+int su_pair_items(const double* w, const double* d, const double* bl, int nitems, int diag, double* acc36, double* accb6, int nsys)
+{
+    Arena a;
+    const double* d_w = a.dev(w, (size_t)nsys * nitems * 36);
+    const double* d_d = a.dev(d, (size_t)nsys * nitems * 9);
+    const double* d_b = a.dev(bl, (size_t)nsys * nitems * 3);
+    double* d_acc = a.dev(acc36, (size_t)nsys * 36);
+    double* d_accb = a.dev(accb6, (size_t)nsys * 6);
+    if (a.err == hipSuccess && nsys > 0) {
+        k_pair_items<<<grid_of(nsys), TPB>>>(d_w, d_d, d_b, nitems, diag, d_acc, d_accb, nsys);
+        a.ran();
+    }
+    a.back(acc36, d_acc, (size_t)nsys * 36);
+    a.back(accb6, d_accb, (size_t)nsys * 6);
+    return (int)a.err;
+}
+// desc: nn x 7 = front (in doubles), nown, nb, child[2], cmap[2]; fronts (nfronts doubles) in / out.  The caller has checked that every
+// front and every map entry lies inside (solver_units_build.merge).
+int su_merge(int R, const int32_t* desc, int nn, const int32_t* cmap, int ncmap, double* fronts, int nfronts, int node)
+{
+    if ((R != 6 && R != 7) || node < 0 || node >= nn) return (int)hipErrorInvalidValue;
+    std::vector<FrontNode> nodes((size_t)nn);
+    for (int i = 0; i < nn; i++) {
+        const int32_t* d = desc + 7 * i;
+        FrontNode nd = {};
+        nd.front = d[0]; nd.nown = d[1]; nd.nb = d[2];
+        nd.child[0] = d[3]; nd.child[1] = d[4]; nd.cmap[0] = d[5]; nd.cmap[1] = d[6];
+        nodes[(size_t)i] = nd;
+    }
+    Arena a;
+    const FrontNode* d_nodes = a.dev(nodes.data(), (size_t)nn);
+    const int32_t* d_cmap = a.dev(cmap, (size_t)ncmap);
+    double* d_f = a.dev(fronts, (size_t)nfronts);
+    if (a.err == hipSuccess) {
+        if (R == 6) k_merge<6><<<1, LM_THREADS>>>(d_nodes, node, d_cmap, d_f);
+        else k_merge<7><<<1, LM_THREADS>>>(d_nodes, node, d_cmap, d_f);
+        a.ran();
+    }
+    a.back(fronts, d_f, (size_t)nfronts);
+    return (int)a.err;
+}
+int su_run_sum(const double* v, int n, double* out)
+{
+    Arena a;
+    const double* d_v = a.dev(v, (size_t)n);
+    double* d_out = a.dev<double>(nullptr, 1);
+    if (a.err == hipSuccess) {
+        k_run_sum<<<1, LM_THREADS>>>(d_v, n, d_out);
+        a.ran();
+    }
+    a.back(out, d_out, 1);
+    return (int)a.err;
+}
 int su_wave(int op, const double* in, double* out, int n)
 {
     if (n % 64) return (int)hipErrorInvalidValue;

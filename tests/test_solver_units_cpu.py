@@ -340,4 +340,88 @@ def test_probe_cross_compiles_for_gfx950():
     assert os.path.getsize(so) > 0
     # every call the wrappers declare is exported (the library's flags hide what is not marked)
     exported = subprocess.check_output(["nm", "-D", "--defined-only", so], text=True).split()
-    assert not [name for name in list(B._SE3) + list(B._DEVICE) if name not in exported]
+    assert not [name for name in list(B._SE3) + list(B._DEVICE) + list(B._PASSES) if name not in exported]
+
+
+# ====================================================================================== the steps the passes share
+def test_damped_inverse_cases_and_the_restatement():
+    """the classes and their count; D (H + lambda I) = I within the bound the condition number gives; one cofactor's sign is far outside"""
+    H6, lam, cls = S.dinv_inputs()
+    assert len(H6) == S.DINV_N == 65 and cls.count("identity") == 1 and min(cls.count(c) for c in ("two", "six", "single")) >= 20
+    M = S.dinv_full(H6, lam)
+    D = B.dinv3(B.host(), H6, lam)
+    assert np.array_equal(D[0], np.eye(3)) and np.array_equal(D, np.swapaxes(D, 1, 2))
+    worst, kmax = 0.0, {}
+    for i in range(len(M)):
+        bound, k = S.dinv_bound(M[i])
+        kmax[cls[i]] = max(kmax.get(cls[i], 0), k)
+        err = np.abs(D[i] @ M[i] - np.eye(3)).max()
+        worst = max(worst, err / bound)
+        assert err <= bound, (i, cls[i], err, bound)
+        if cls[i] == "single":           # rank 2 plus lambda: the plain J^T J is singular to rounding
+            s = np.linalg.svd(M[i] - lam[i] * np.eye(3), compute_uv=False)
+            assert s[2] <= 1e-12 * s[0]
+            flipped = D[i].copy()
+            flipped[0, 1] = flipped[1, 0] = -D[i][0, 1]
+            assert np.abs(flipped @ M[i] - np.eye(3)).max() > 1e3 * bound
+    print("damped inverse: worst |D M - I| / bound", worst, "largest condition number per class", kmax)
+    assert kmax["single"] > 1e3
+
+
+@pytest.mark.parametrize("nitems,diag", S.PAIR_CASES)
+def test_pair_item_cases_and_the_restatement(nitems, diag):
+    Wi, Wj, Dm, bl, acc0, accb0 = S.pair_inputs(nitems, diag)
+    assert np.abs(acc0).min() > 0 and np.abs(accb0).min() > 0
+    acc, accb = B.pair_items(B.host(), Wi, Wj, Dm, bl, diag, acc0, accb0)
+    want = acc0 + np.einsum("siab,sibc,sidc->sad", Wi, Dm, Wj)
+    wantb = accb0 + (np.einsum("siab,sibc,sic->sa", Wi, Dm, bl) if diag else 0)
+    tol = 64 * S.EPS * max(1.0, np.abs(want).max())
+    assert np.abs(acc - want).max() <= tol and np.abs(accb - wantb).max() <= tol
+    if not diag:
+        assert S.same_bits(accb, accb0)
+    if nitems:           # W_i for W_j, and an assignment for the addition, are far outside
+        assert np.abs(B.pair_items(B.host(), Wj, Wi, Dm, bl, diag, acc0, accb0)[0] - want).max() > 1e-3
+        assert np.abs(acc - acc0 - want).max() > 1e-3
+
+
+@pytest.mark.parametrize("R", (6, 7))
+def test_merge_cases_and_the_restatement(R):
+    """the sequential restatement is the dense scatter, bit for bit; the children's order and the swap show"""
+    desc, cmap, fronts = S.merge_case(R)
+    n = 3 * R
+    for node in (0, 3):
+        got = B.merge(B.host(), R, desc, cmap, fronts, node)
+        assert S.same_bits(got, S.merge_dense(R, desc, cmap, fronts, node)), node
+        F0, F1 = fronts[desc[node][0]:][:n * n].reshape(n, n), got[desc[node][0]:][:n * n].reshape(n, n)
+        other = np.ones(len(fronts), bool)
+        other[desc[node][0]:desc[node][0] + n * n + n] = False
+        assert S.same_bits(got[other], fronts[other]) and S.same_bits(np.triu(F1, 1), np.triu(F0, 1))       # nothing else is written
+        changed = S.bits(F1) != S.bits(F0)
+        if node == 0:
+            # left: the parent's vertices 2 and 0 with their cross block at (2, 0); right: vertex 0; vertex 1 receives nothing
+            want = np.zeros((3, 3), bool)
+            want[0, 0] = want[2, 2] = want[2, 0] = True
+            assert np.array_equal(changed.reshape(3, R, 3, R).any((1, 3)), want)
+            assert changed[2 * R:, :R].all()            # the cross block whole: its upper half came through the swap
+            swapped = S.merge_dense(R, desc, cmap, fronts, node, order=(1, 0))
+            d = S.bits(swapped) != S.bits(got)
+            assert d.any() and not d[other].any()
+            blk = d[desc[0][0]:][:n * n].reshape(n, n)
+            assert blk[:R, :R].any() and not blk[R:].any()       # only where both children add
+        else:
+            assert np.array_equal(changed.reshape(3, R, 3, R).any((1, 3)), np.diag([True, False, False]))
+
+
+@pytest.mark.parametrize("n", S.RUN_SUM_SIZES)
+def test_run_sum_cases_and_the_restatement(n):
+    v = S.run_sum_inputs(n)
+    got = B.run_sum(B.host(), v)
+    assert B.host().se3.su_lm_threads() == S.RUN_SUM_THREADS
+    assert abs(got - math.fsum(v)) <= max(n, 1) * S.EPS * np.abs(v).sum()
+    if n <= 1:
+        assert got == (v[0] if n else 0.0)
+    if n > S.RUN_SUM_THREADS:          # the order shows: a strided assignment, and one sum from the left, give other bits
+        assert got != S.run_sum_strided(v)
+    if n == max(S.RUN_SUM_SIZES):
+        assert got != float(np.add.reduce(v)) or got != sum(v.tolist())
+        assert np.log10(np.abs(v).max() / np.abs(v).min()) > 10

@@ -5,6 +5,9 @@
   C  csrc/svd_jacobi.hpp   OpenCV's float Jacobi SVD in its four product instantiations
   D  csrc/front_solve.hpp  the partial Cholesky of a front in both storage forms, the substitution back
   E  csrc/ba_edges.hpp     the mono edge's analytic Jacobians, the marker edge's numeric ones, the diagonal block, the wave sums
+  F  the steps the passes of the bundle adjustments and the front solvers share: the damped 3 x 3 inverse and the pair item
+     (ba_edges.hpp), the children's merge (front_solve.hpp), run_sum behind block_sum (lm_dense.hpp), each bit-equal to a sequential
+     restatement in tests/solver_units_host.cpp
 
 The helpers run inside tests/solver_units_probe.hip: the five headers, included unchanged, as a translation unit of their own that
 tests/solver_units_build.py compiles with the library's flags.  Inputs and references are in tests/solver_units_cases.py;
@@ -382,3 +385,34 @@ def test_wave_sum_and_max_in_the_butterfly_order():
     nan = S.wave_rows_with_nan()
     got = B.wave(B.MAX, nan)
     assert same_bits(got, S.butterfly(nan, np.fmax)) and same_bits(got[:, 0], np.fmax.reduce(nan, axis=1)) and np.isfinite(got).all()
+
+
+# ====================================================================================== the steps the passes share
+# each held to the sequential host restatement of tests/solver_units_host.cpp, bit for bit (only + - * / enter)
+def test_damped_inverse_equals_the_restatement():
+    H6, lam, _ = S.dinv_inputs()
+    got, want = B.dinv3(B.probe(), H6, lam), B.dinv3(B.host(), H6, lam)
+    assert same_bits(got, want), first_difference(got, want)
+
+
+@pytest.mark.parametrize("nitems,diag", S.PAIR_CASES)
+def test_pair_item_equals_the_restatement(nitems, diag):
+    args = S.pair_inputs(nitems, diag)
+    got, want = B.pair_items(B.probe(), *args[:4], diag, *args[4:]), B.pair_items(B.host(), *args[:4], diag, *args[4:])
+    assert same_bits(got[0], want[0]) and same_bits(got[1], want[1]), (first_difference(got[0], want[0]), first_difference(got[1], want[1]))
+
+
+@pytest.mark.parametrize("R", (6, 7))
+def test_children_merge_equals_the_restatement(R):
+    desc, cmap, fronts = S.merge_case(R)
+    for node in (0, 3):        # both children, left then right; the right child alone
+        got, want = B.merge(B.probe(), R, desc, cmap, fronts, node), B.merge(B.host(), R, desc, cmap, fronts, node)
+        assert same_bits(got, want), (node, np.flatnonzero(bits(got) != bits(want))[:8])
+
+
+@pytest.mark.parametrize("n", S.RUN_SUM_SIZES)
+def test_run_sum_then_block_sum_equals_the_restatement(n):
+    assert B.probe().su_lm_threads() == B.host().se3.su_lm_threads() == S.RUN_SUM_THREADS
+    v = S.run_sum_inputs(n)
+    got, want = B.run_sum(B.probe(), v), B.run_sum(B.host(), v)
+    assert same_bits(np.array([got]), np.array([want])), (got, want)
