@@ -41,26 +41,6 @@ using namespace orbfe_shim;
 namespace orbfe_globalba
 {
 
-namespace
-{
-
-const float kMarkerInformation = 25.f;   // the weight the reference gives a marker corner
-
-void append_pose(const cv::Mat& T, std::vector<float>& out)
-{
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 4; c++) out.push_back(T.at<float>(r, c));
-}
-
-cv::Mat pose4x4(const float* T12)
-{
-    cv::Mat pose(4, 4, CV_32F);
-    for (int i = 0; i < 16; i++) pose.at<float>(i / 4, i % 4) = i < 12 ? T12[i] : (i == 15 ? 1.f : 0.f);
-    return pose;
-}
-
-} // namespace
-
 void Collect(const std::vector<KeyFrame*>& vpKFs, const std::vector<MapPoint*>& vpMP, const std::vector<MapAruco*>& vpMA, Problem& pb)
 {
     pb = Problem();
@@ -78,25 +58,13 @@ void Collect(const std::vector<KeyFrame*>& vpKFs, const std::vector<MapPoint*>& 
         pb.inv_level_sigma2 = kf->mvInvLevelSigma2;
     }
 
+    // an observer that is bad, or not among the collected keyframes, gives no edge
+    const auto collected = [&slot](KeyFrame* kf) { return !kf->isBad() && slot.count(kf) != 0; };
     pb.obs_offset.push_back(0);
     for (MapPoint* mp : vpMP) {
         if (mp->isBad()) continue;
         pb.vpMapPoints.push_back(mp);
-        float X[3];
-        point3(mp->GetWorldPos(), X);
-        pb.x3Dw.insert(pb.x3Dw.end(), X, X + 3);
-        const std::map<KeyFrame*, size_t> seen = mp->GetObservations();
-        for (const auto& o : seen) {
-            KeyFrame* kf = o.first;
-            if (kf->isBad() || !slot.count(kf)) continue;
-            if (kf->mvuRight[o.second] >= 0) throw std::runtime_error("Optimizer::BundleAdjustment: stereo observations are not supported");
-            const cv::KeyPoint& kp = kf->mvKeysUn[o.second];
-            pb.obs_kf.push_back(slot.at(kf));
-            pb.obs_xy.push_back(kp.pt.x);
-            pb.obs_xy.push_back(kp.pt.y);
-            pb.obs_octave.push_back(kp.octave);
-        }
-        pb.obs_offset.push_back((int32_t)pb.obs_kf.size());
+        orbfe_ba::AppendPoint(mp, slot, collected, "Optimizer::BundleAdjustment", pb);
     }
 
     pb.mobs_offset.push_back(0);
@@ -104,25 +72,7 @@ void Collect(const std::vector<KeyFrame*>& vpKFs, const std::vector<MapPoint*>& 
     for (MapAruco* ma : vpMA) {
         if (ma->isBad()) continue;
         pb.vpMapArucos.push_back(ma);
-        append_pose(ma->GetTwm(), pb.Twm);
-        for (size_t k = 0; k < 4; k++) {
-            const cv::Point3f c = ma->get3DPointsLocalRefSystem(k);
-            pb.marker_local.push_back(c.x);
-            pb.marker_local.push_back(c.y);
-            pb.marker_local.push_back(c.z);
-        }
-        const std::map<KeyFrame*, size_t> seen = ma->GetObservations();
-        for (const auto& o : seen) {
-            KeyFrame* kf = o.first;
-            if (kf->isBad() || !slot.count(kf)) continue;
-            pb.mobs_kf.push_back(slot.at(kf));
-            for (size_t k = 0; k < 4; k++) {
-                const cv::Point2f& c = kf->mvArucoUn[4 * o.second + k];
-                pb.mobs_corners.push_back(c.x);
-                pb.mobs_corners.push_back(c.y);
-            }
-        }
-        pb.mobs_offset.push_back((int32_t)pb.mobs_kf.size());
+        orbfe_ba::AppendMarker(ma, slot, collected, pb);
     }
 }
 
@@ -141,14 +91,14 @@ void Optimizer::BundleAdjustment(const std::vector<KeyFrame*>& vpKFs, const std:
     check(orbfe_global_bundle_adjustment(pb.Tcw.data(), pb.kf_fixed.data(), nkf, pb.x3Dw.data(), np, pb.obs_offset.data(), pb.obs_kf.data(),
                                          pb.obs_xy.data(), pb.obs_octave.data(), nobs, pb.K4, pb.inv_level_sigma2.data(),
                                          (int)pb.inv_level_sigma2.size(), pb.Twm.data(), pb.marker_local.data(), nma, pb.mobs_offset.data(),
-                                         pb.mobs_kf.data(), pb.mobs_corners.data(), nmobs, orbfe_globalba::kMarkerInformation,
+                                         pb.mobs_kf.data(), pb.mobs_corners.data(), nmobs, kMarkerInformation,
                                          Frame::mbUArucoIni ? 1 : 0, nIterations, bRobust ? 1 : 0, &stop, 0, &res, 0));
     if (res.status == ORBFE_GBA_STOPPED) return;   // nothing was optimized: the map stays as it is
 
     for (int k = 0; k < nkf; k++) {
         KeyFrame* kf = pb.vpKeyFrames[(size_t)k];
         if (kf->isBad()) continue;
-        const cv::Mat pose = orbfe_globalba::pose4x4(&pb.Tcw[12 * (size_t)k]);
+        const cv::Mat pose = pose4x4(&pb.Tcw[12 * (size_t)k]);
         if (nLoopKF == 0) {
             kf->SetPose(pose);
         } else {

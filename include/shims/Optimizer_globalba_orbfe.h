@@ -8,25 +8,18 @@
 #include <cstdint>
 #include <vector>
 
+#include "Optimizer_ba_orbfe.h"
+
 namespace ORB_SLAM2
 {
-
-class KeyFrame;
-class MapAruco;
-class MapPoint;
 
 namespace orbfe_globalba
 {
 
-struct Problem {
+struct Problem : orbfe_ba::Arrays {   // with the arrays of orbfe_global_bundle_adjustment
     std::vector<KeyFrame*> vpKeyFrames;   // the keyframes of vpKFs that are not bad, in their order: the pose vertices
     std::vector<MapPoint*> vpMapPoints;   // the points of vpMP that are not bad, in their order
     std::vector<MapAruco*> vpMapArucos;   // with Frame::mbUArucoIni: the markers of vpMA that are not bad, in their order
-    // the arrays of orbfe_global_bundle_adjustment
-    std::vector<float> Tcw, x3Dw, obs_xy, Twm, marker_local, mobs_corners, inv_level_sigma2;
-    std::vector<uint8_t> kf_fixed;
-    std::vector<int32_t> obs_offset, obs_kf, obs_octave, mobs_offset, mobs_kf;
-    float K4[4] = {0, 0, 0, 0};
 };
 
 // Lines 76-232 of src/Optimizer.cc as flat arrays, in the order g2o would have received the vertices and edges.  Throws

@@ -45,14 +45,6 @@ namespace orbfe_localba
 namespace
 {
 
-const float kMarkerInformation = 25.f;   // the weight the reference gives a marker corner
-
-void append_pose(const cv::Mat& T, std::vector<float>& out)
-{
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 4; c++) out.push_back(T.at<float>(r, c));
-}
-
 // The vertex keyframes while they are being gathered.  A keyframe is marked the first time it is met -- as a local one or as a
 // fixed one, with the current keyframe's id in the member the reference uses -- and becomes a vertex unless it is bad; a bad one
 // keeps its mark, so that it is not looked at again.
@@ -124,47 +116,17 @@ void Collect(KeyFrame* pKF, Map* /*pMap*/, Problem& pb)
 
     pb.obs_offset.push_back(0);
     for (MapPoint* mp : pb.vpMapPoints) {
-        float X[3];
-        point3(mp->GetWorldPos(), X);
-        pb.x3Dw.insert(pb.x3Dw.end(), X, X + 3);
-        const std::map<KeyFrame*, size_t> seen = mp->GetObservations();
-        for (const auto& o : seen) {
-            KeyFrame* kf = o.first;
-            if (kf->isBad()) continue;   // marked, but no vertex
-            if (kf->mvuRight[o.second] >= 0) throw std::runtime_error("Optimizer::LocalBundleAdjustment: stereo observations are not supported");
-            const cv::KeyPoint& kp = kf->mvKeysUn[o.second];
-            pb.obs_kf.push_back(V.slot.at(kf));
-            pb.obs_xy.push_back(kp.pt.x);
-            pb.obs_xy.push_back(kp.pt.y);
-            pb.obs_octave.push_back(kp.octave);
-            pb.vpEdgeKF.push_back(kf);
+        // a bad observer is marked, but no vertex
+        orbfe_ba::AppendPoint(mp, V.slot, [](KeyFrame* kf) { return !kf->isBad(); }, "Optimizer::LocalBundleAdjustment", pb);
+        for (size_t e = pb.vpEdgeKF.size(); e < pb.obs_kf.size(); e++) {
+            pb.vpEdgeKF.push_back(pb.vpKeyFrames[(size_t)pb.obs_kf[e]]);
             pb.vpEdgeMP.push_back(mp);
         }
-        pb.obs_offset.push_back((int32_t)pb.obs_kf.size());
     }
 
     pb.mobs_offset.push_back(0);
-    for (MapAruco* ma : pb.vpMapArucos) {
-        append_pose(ma->GetTwm(), pb.Twm);
-        for (size_t k = 0; k < 4; k++) {
-            const cv::Point3f c = ma->get3DPointsLocalRefSystem(k);
-            pb.marker_local.push_back(c.x);
-            pb.marker_local.push_back(c.y);
-            pb.marker_local.push_back(c.z);
-        }
-        const std::map<KeyFrame*, size_t> seen = ma->GetObservations();
-        for (const auto& o : seen) {
-            KeyFrame* kf = o.first;
-            if (kf->isBad() || !V.has_id(kf->mnId)) continue;
-            pb.mobs_kf.push_back(V.slot.at(kf));
-            for (size_t k = 0; k < 4; k++) {
-                const cv::Point2f& c = kf->mvArucoUn[4 * o.second + k];
-                pb.mobs_corners.push_back(c.x);
-                pb.mobs_corners.push_back(c.y);
-            }
-        }
-        pb.mobs_offset.push_back((int32_t)pb.mobs_kf.size());
-    }
+    for (MapAruco* ma : pb.vpMapArucos)
+        orbfe_ba::AppendMarker(ma, V.slot, [&V](KeyFrame* kf) { return !kf->isBad() && V.has_id(kf->mnId); }, pb);
 }
 
 } // namespace orbfe_localba
@@ -181,7 +143,7 @@ void Optimizer::LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Map* pMap
     check(orbfe_local_bundle_adjustment(pb.Tcw.data(), pb.kf_fixed.data(), nkf, pb.x3Dw.data(), np, pb.obs_offset.data(), pb.obs_kf.data(),
                                         pb.obs_xy.data(), pb.obs_octave.data(), nobs, pb.K4, pb.inv_level_sigma2.data(),
                                         (int)pb.inv_level_sigma2.size(), pb.Twm.data(), pb.marker_local.data(), nma, pb.mobs_offset.data(),
-                                        pb.mobs_kf.data(), pb.mobs_corners.data(), nmobs, orbfe_localba::kMarkerInformation,
+                                        pb.mobs_kf.data(), pb.mobs_corners.data(), nmobs, kMarkerInformation,
                                         Frame::mbUArucoIni ? 1 : 0, &stop, erase.data(), &res, 0));
     if (res.status == ORBFE_LBA_STOPPED) return;   // nothing was optimized: the map stays as it is
 
@@ -192,11 +154,7 @@ void Optimizer::LocalBundleAdjustment(KeyFrame* pKF, bool* pbStopFlag, Map* pMap
         pb.vpEdgeKF[(size_t)e]->EraseMapPointMatch(mp);
         mp->EraseObservation(pb.vpEdgeKF[(size_t)e]);
     }
-    for (size_t k = 0; k < pb.nLocal; k++) {
-        cv::Mat pose(4, 4, CV_32F);
-        for (int i = 0; i < 16; i++) pose.at<float>(i / 4, i % 4) = i < 12 ? pb.Tcw[12 * k + (size_t)i] : (i == 15 ? 1.f : 0.f);
-        pb.vpKeyFrames[k]->SetPose(pose);
-    }
+    for (size_t k = 0; k < pb.nLocal; k++) pb.vpKeyFrames[k]->SetPose(pose4x4(&pb.Tcw[12 * k]));
     for (int i = 0; i < np; i++) {
         pb.vpMapPoints[(size_t)i]->SetWorldPos(mat32(3, 1, &pb.x3Dw[3 * (size_t)i]));
         pb.vpMapPoints[(size_t)i]->UpdateNormalAndDepth();

@@ -8,27 +8,21 @@
 #include <cstdint>
 #include <vector>
 
+#include "Optimizer_ba_orbfe.h"
+
 namespace ORB_SLAM2
 {
 
-class KeyFrame;
 class Map;
-class MapAruco;
-class MapPoint;
 
 namespace orbfe_localba
 {
 
-struct Problem {
+struct Problem : orbfe_ba::Arrays {   // with the arrays of orbfe_local_bundle_adjustment
     std::vector<KeyFrame*> vpKeyFrames;   // lLocalKeyFrames in list order, then lFixedCameras in list order: the pose vertices
     size_t nLocal = 0;                    // how many of them are local
     std::vector<MapPoint*> vpMapPoints;   // lLocalMapPoints in list order
     std::vector<MapAruco*> vpMapArucos;   // vLocalMapArucosMono
-    // the arrays of orbfe_local_bundle_adjustment
-    std::vector<float> Tcw, x3Dw, obs_xy, Twm, marker_local, mobs_corners, inv_level_sigma2;
-    std::vector<uint8_t> kf_fixed;
-    std::vector<int32_t> obs_offset, obs_kf, obs_octave, mobs_offset, mobs_kf;
-    float K4[4] = {0, 0, 0, 0};
     // edge e is the observation of vpEdgeMP[e] in vpEdgeKF[e], in the order g2o would have received the edges
     std::vector<KeyFrame*> vpEdgeKF;
     std::vector<MapPoint*> vpEdgeMP;

@@ -50,6 +50,24 @@ inline void pose34(const cv::Mat& R, const cv::Mat& t, float T[12])
     }
 }
 
+// the top three rows of a 4 x 4 (or 3 x 4) CV_32F pose, appended as 12 floats
+inline void append_pose(const cv::Mat& T, std::vector<float>& out)
+{
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 4; c++) out.push_back(T.at<float>(r, c));
+}
+
+// the 12 floats of a row-major 3 x 4 pose as the 4 x 4 CV_32F matrix KeyFrame::SetPose takes
+inline cv::Mat pose4x4(const float* T12)
+{
+    cv::Mat pose(4, 4, CV_32F);
+    for (int i = 0; i < 16; i++) pose.at<float>(i / 4, i % 4) = i < 12 ? T12[i] : (i == 15 ? 1.f : 0.f);
+    return pose;
+}
+
+// the information the reference's bundle adjustments give a marker corner edge
+const float kMarkerInformation = 25.f;
+
 // {fx, fy, cx, cy} of a 3 x 3 CV_32F calibration matrix
 inline void intrinsics(const cv::Mat& K, float K4[4])
 {

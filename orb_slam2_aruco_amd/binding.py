@@ -1673,6 +1673,22 @@ def local_bundle_adjustment_device(d, nkf, np_, nobs, nma, nmobs, K, inv_level_s
         int(d.get("scratch_bytes", 0)), stream), "orbfe_local_bundle_adjustment_device")
 
 
+def _ba_system(nv, b, Hpp, Hll, chi2, x, n):
+    """what lba_inspect and gba_inspect return of one linearisation and the first trial, from the buffers the library filled (n points)"""
+    v = int(nv[0])
+    return dict(nv=v, b_pose=b[:6 * v].reshape(v, 6), b_point=b[6 * v:6 * v + 3 * n].reshape(n, 3), Hpp=Hpp[:v], Hll=Hll[:n], chi2=chi2[0],
+                lambda0=chi2[1], x_pose=x[:6 * v].reshape(v, 6), x_point=x[6 * v:6 * v + 3 * n].reshape(n, 3))
+
+
+def _front_tree(tree, nv):
+    """what essential_graph_inspect and gba_inspect return of the elimination tree over nv vertices: nlevels, node_of, order_of (per
+    vertex), parent, level, nown, nb (per node)"""
+    nn = int(tree[0])
+    nodes = tree[2 + 2 * nv:2 + 2 * nv + 4 * nn].reshape(nn, 4)
+    return dict(nlevels=int(tree[1]), node_of=tree[2:2 + nv].copy(), order_of=tree[2 + nv:2 + 2 * nv].copy(), parent=nodes[:, 0].copy(),
+                level=nodes[:, 1].copy(), nown=nodes[:, 2].copy(), nb=nodes[:, 3].copy())
+
+
 def lba_inspect(pb, device=0):
     """orbfe_lba_inspect: one linearisation and the first trial.  Returns dict(nv, b_pose (nv x 6), b_point (np x 3), Hpp (nv x 6 x 6),
     Hll (np x 6: xx xy xz yy yz zz), chi2, lambda0, x_pose (nv x 6), x_point (np x 3))."""
@@ -1683,9 +1699,7 @@ def lba_inspect(pb, device=0):
     b = np.zeros(6 * LBA_MAX_FREE_POSES + 3 * n); x = np.zeros_like(b)
     Hpp = np.zeros((LBA_MAX_FREE_POSES, 6, 6)); Hll = np.zeros((max(n, 1), 6)); chi2 = np.zeros(2)
     _check(L, L.orbfe_lba_inspect(*(_lba_problem_args(a) + [_p(nv), _p(b), _p(Hpp), _p(Hll), _p(chi2), _p(x), device])), "orbfe_lba_inspect")
-    v = int(nv[0])
-    return dict(nv=v, b_pose=b[:6 * v].reshape(v, 6), b_point=b[6 * v:6 * v + 3 * n].reshape(n, 3), Hpp=Hpp[:v], Hll=Hll[:n], chi2=chi2[0],
-                lambda0=chi2[1], x_pose=x[:6 * v].reshape(v, 6), x_point=x[6 * v:6 * v + 3 * n].reshape(n, 3))
+    return _ba_system(nv, b, Hpp, Hll, chi2, x, n)
 
 
 # ------------------------------------------------------------------------------- OptimizeEssentialGraph (loop closing) ----
@@ -1765,11 +1779,7 @@ def essential_graph_inspect(pb, device=0):
     chi2 = np.zeros(3); x = np.zeros((nkf, 7)); tree = np.zeros(10 * nkf + 10, np.int32)
     _check(L, L.orbfe_essential_graph_inspect(*(_eg_graph_args(a) + [a["fix_scale"], a["leaf_vertices"], _p(err), _p(Ji), _p(Jj), _p(Hd), _p(b),
                                                                      _p(chi2), _p(x), _p(tree), device])), "orbfe_essential_graph_inspect")
-    nn = int(tree[0])
-    nodes = tree[2 + 2 * nkf:2 + 2 * nkf + 4 * nn].reshape(nn, 4)
-    return dict(err=err, Ji=Ji, Jj=Jj, Hd=Hd, b=b, chi2=chi2[0], lambda0=chi2[1], solved=bool(chi2[2]), x=x, nlevels=int(tree[1]),
-                node_of=tree[2:2 + nkf].copy(), order_of=tree[2 + nkf:2 + 2 * nkf].copy(), parent=nodes[:, 0].copy(), level=nodes[:, 1].copy(),
-                nown=nodes[:, 2].copy(), nb=nodes[:, 3].copy())
+    return dict(err=err, Ji=Ji, Jj=Jj, Hd=Hd, b=b, chi2=chi2[0], lambda0=chi2[1], solved=bool(chi2[2]), x=x, **_front_tree(tree, nkf))
 
 
 # ------------------------------------------------------------------------------- GlobalBundleAdjustment (map-wide BA) ----
@@ -1835,9 +1845,4 @@ def gba_inspect(pb, device=0):
     Hpp = np.zeros((max(V, 1), 6, 6)); Hll = np.zeros((max(n, 1), 6)); chi2 = np.zeros(3); tree = np.zeros(10 * V + 10, np.int32)
     _check(L, L.orbfe_gba_inspect(*(_lba_problem_args(a) + [a["robust"], a["leaf_vertices"], _p(nv), _p(b), _p(Hpp), _p(Hll), _p(chi2), _p(x), _p(tree),
                                                           device])), "orbfe_gba_inspect")
-    v, nn = int(nv[0]), int(tree[0])
-    nodes = tree[2 + 2 * v:2 + 2 * v + 4 * nn].reshape(nn, 4)
-    return dict(nv=v, b_pose=b[:6 * v].reshape(v, 6), b_point=b[6 * v:6 * v + 3 * n].reshape(n, 3), Hpp=Hpp[:v], Hll=Hll[:n], chi2=chi2[0],
-                lambda0=chi2[1], solved=bool(chi2[2]), x_pose=x[:6 * v].reshape(v, 6), x_point=x[6 * v:6 * v + 3 * n].reshape(n, 3),
-                nlevels=int(tree[1]), node_of=tree[2:2 + v].copy(), order_of=tree[2 + v:2 + 2 * v].copy(), parent=nodes[:, 0].copy(),
-                level=nodes[:, 1].copy(), nown=nodes[:, 2].copy(), nb=nodes[:, 3].copy())
+    return dict(_ba_system(nv, b, Hpp, Hll, chi2, x, n), solved=bool(chi2[2]), **_front_tree(tree, int(nv[0])))

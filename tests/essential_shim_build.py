@@ -1,13 +1,11 @@
-"""Builds the programs of the OptimizeEssentialGraph shim (test infrastructure): include/shims/Optimizer_essential_orbfe.cc with
-tests/essential_shim_driver.cpp, and every shim of include/shims/ that shares the one mock tree with tests/all_shims9_driver.cpp, both
-against the mock headers of tests/mock_orbslam_eg/ ahead of tests/mock_orbslam/ and the built library."""
+"""Builds and runs the program of the OptimizeEssentialGraph shim (test infrastructure): include/shims/Optimizer_essential_orbfe.cc with
+tests/essential_shim_driver.cpp, through ref_build.build_shim as tests/shim_build.py does for the other shims."""
 import os
 import subprocess
 
 import numpy as np
 
 import ref_build
-import shim_build
 
 SHIM = "Optimizer_essential_orbfe.cc"
 FILES = dict(vk=np.int32, id=np.int32, fixed=np.int32, cpos=np.int32, npos=np.int32, ei=np.int32, ej=np.int32, ek=np.int32, pref=np.int32, Tcw=np.float32,
@@ -15,29 +13,8 @@ FILES = dict(vk=np.int32, id=np.int32, fixed=np.int32, cpos=np.int32, npos=np.in
 RUN_FILES = dict(T=np.float32, P=np.float32, M=np.float32, counts=np.int32)
 
 
-def build(shim_ccs, driver_cpp, out_dir):
-    root, here = ref_build.ROOT, ref_build.HERE
-    inc = []
-    for d in ("tests/mock_orbslam_eg",) + ref_build.MOCK_DIRS + ("include", "include/shims", "tests"):
-        inc += ["-I", os.path.join(root, d)]
-    flags = ["g++", "-std=c++14", "-O1", "-Wall", "-Werror"]
-    objs = []
-    for src in [os.path.join(root, "include", "shims", cc) for cc in shim_ccs] + [os.path.join(here, "mock_orbslam", "Frame_statics.cc")]:
-        objs.append(os.path.join(out_dir, os.path.splitext(os.path.basename(src))[0] + ".o"))
-        subprocess.check_call(flags + inc + ["-c", src, "-o", objs[-1]])
-    exe = os.path.join(out_dir, os.path.splitext(driver_cpp)[0])
-    lib_dir = os.path.join(root, "orb_slam2_aruco_amd")
-    subprocess.check_call(flags + inc + [os.path.join(here, driver_cpp)] + objs + ["-o", exe, "-L", lib_dir, "-lorbfe", "-Wl,-rpath," + lib_dir])
-    return exe
-
-
 def build_driver(out_dir):
-    return build((SHIM,), "essential_shim_driver.cpp", out_dir)
-
-
-def build_all9(out_dir):
-    """the shims of shim_build.PROGRAMS["all"], the LocalMapping shim and this one in one program"""
-    return build(tuple(shim_build.PROGRAMS["all"][0]) + ("LocalMapping_orbfe.cc", SHIM), "all_shims9_driver.cpp", out_dir)
+    return ref_build.build_shim((SHIM,), "essential_shim_driver.cpp", out_dir)
 
 
 def run(exe, mode, out_dir):

@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE ONLY -- drives include/shims/Optimizer_essential_orbfe.cc the way LoopClosing::CorrectLoopByAruco does, on a
-// hand-built mock map (the mock headers of tests/mock_orbslam_eg/ ahead of tests/mock_orbslam/), and dumps raw arrays for
+// hand-built mock map (the mock headers of tests/mock_orbslam/), and dumps raw arrays for
 // tests/test_essential_shim_cpu.py and tests/test_essential_shim_gpu.py.
 //   essential_shim_driver collect <out prefix>   the collect step alone (no library call): the flat arrays
 //   essential_shim_driver run <out prefix>       the flat arrays, then Optimizer::OptimizeEssentialGraph (bFixScale = true) and the map

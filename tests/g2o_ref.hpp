@@ -1,9 +1,10 @@
-// g2o_ref.hpp -- what the three CPU restatements of the g2o optimizers (pose_opt_ref.cpp, sim3_opt_ref.cpp, lba_ref.cpp) have in
-// common: SE3Quat, the projection error, the Huber kernel, the dense LDLT, and OptimizationAlgorithmLevenberg's scalar rules.  No g2o
-// or Eigen here: the pieces are restated from their algorithms.
+// g2o_ref.hpp -- what the five CPU restatements of the g2o optimizers (pose_opt_ref.cpp, sim3_opt_ref.cpp, essential_ref.cpp, and
+// lba_ref.cpp and gba_ref.cpp through ba_ref.hpp, which holds what those two share on top of this) have in common: SE3Quat, the
+// projection error, the Huber kernel, the dense LDLT, and OptimizationAlgorithmLevenberg's scalar rules.  No g2o or Eigen here: the
+// pieces are restated from their algorithms.
 //
 // This header includes nothing from orb_slam2_aruco_amd/csrc/, and nothing there includes anything from tests/.  The restatements
-// are the second opinion on the device code: the three of them sharing their common pieces keeps that, while sharing a line with the
+// are the second opinion on the device code: the five of them sharing their common pieces keeps that, while sharing a line with the
 // device would turn every parity test into a comparison of the code with itself.  The same rules are therefore written twice in this
 // repository, once here and once in csrc/ (lm_rules.hpp, lm_dense.hpp, se3_quat.hpp), on purpose.
 //

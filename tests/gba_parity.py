@@ -5,8 +5,7 @@ orders run a different number of accepted trials is left out of the spread and o
 tests/gba_cases.py none is (tests/test_gba_cpu.py checks that)."""
 import gba_build
 import gba_cases
-from lba_parity import rot_angle, within, QUANTITIES   # noqa: F401
-import numpy as np
+from lba_parity import rot_angle, scaled_distance, within, QUANTITIES   # noqa: F401
 
 MAX_NOT_COMPARED = 0.10
 NAMES = list(gba_cases.CASES)
@@ -21,16 +20,7 @@ def problem(name):
 
 
 def distance(a, b, pb):
-    """max |dR|, |dt| / extent, |dX| / extent over the keyframes, the points and the marker poses of two results"""
-    ex = gba_cases.extent(pb)
-    out = dict(dR=rot_angle(a["Tcw"][:, :, :3], b["Tcw"][:, :, :3]), dt=0.0, dX=0.0, dRm=rot_angle(a["Twm"][:, :, :3], b["Twm"][:, :, :3]), dtm=0.0)
-    if len(a["Tcw"]):
-        out["dt"] = float(np.abs(a["Tcw"][:, :, 3].astype(np.float64) - b["Tcw"][:, :, 3]).max() / ex)
-    if len(a["x3Dw"]):
-        out["dX"] = float(np.abs(a["x3Dw"].astype(np.float64) - b["x3Dw"]).max() / ex)
-    if len(a["Twm"]):
-        out["dtm"] = float(np.abs(a["Twm"][:, :, 3].astype(np.float64) - b["Twm"][:, :, 3]).max() / ex)
-    return out
+    return scaled_distance(a, b, gba_cases.extent(pb))
 
 
 def same_path(r0, r1):

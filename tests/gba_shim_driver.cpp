@@ -1,6 +1,6 @@
 // TEST INFRASTRUCTURE ONLY -- drives include/shims/Optimizer_globalba_orbfe.cc the way Tracking and LoopClosing do, on the mock map that
 // tests/lba_shim_map.py describes (its files, plus <in>_order.bin: the keyframes handed over, by position), against the mock headers
-// of tests/mock_orbslam_gba/ (ahead of tests/mock_orbslam_lba/ and tests/mock_orbslam/), and dumps raw arrays for
+// of tests/mock_orbslam/, and dumps raw arrays for
 // tests/test_gba_shim_cpu.py and tests/test_gba_shim_gpu.py.
 //   gba_shim_driver collect <in prefix> <out prefix> <use>                                  the collect step alone (no library call)
 //   gba_shim_driver run <in prefix> <out prefix> <use> <stop> <nLoopKF> <iterations> <robust>   Optimizer::BundleAdjustment, then the map

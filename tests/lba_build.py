@@ -1,47 +1,23 @@
 """Builds tests/lba_ref.cpp (the CPU restatement of ORB_SLAM2's Optimizer::LocalBundleAdjustment) with g++ and loads it with ctypes
-(test infrastructure, in the manner of tests/sim3_opt_build.py).  One build per process, in a temporary directory."""
-import ctypes as C
+(test infrastructure, in the manner of tests/sim3_opt_build.py).  One build per process, in a temporary directory.  What it shares with
+tests/gba_build.py is in tests/ba_ref_call.py."""
+import functools
 
 import numpy as np
 
+import ba_ref_call as R
 import ref_build
+from ba_ref_call import INSERTION, DEVICE   # noqa: F401
 from orb_slam2_aruco_amd import binding
 
-_lib = None
-
 RESULT_DTYPE = binding.LBA_RESULT_DTYPE
-INSERTION, DEVICE = 0, 1     # the summation orders of the restatement
+_p = R.p
 
 
+@functools.lru_cache(None)
 def lib():
-    global _lib
-    if _lib is None:
-        L = ref_build.build_shared("lba_ref.cpp")
-        vp, i32, f32 = C.c_void_p, C.c_int, C.c_float
-        prob = [vp, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, i32, f32, i32, i32]
-        L.ref_lba.argtypes = prob + [vp, vp, vp]
-        L.ref_lba.restype = i32
-        L.ref_lba_inspect.argtypes = prob + [vp] * 7
-        L.ref_lba_inspect.restype = i32
-        L.ref_lba_mono_edge.argtypes = [vp] * 8
-        L.ref_lba_mono_edge.restype = None
-        L.ref_lba_marker_edge.argtypes = [vp] * 8
-        L.ref_lba_marker_edge.restype = None
-        L.ref_lba_poses_only.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, i32]
-        L.ref_lba_poses_only.restype = i32
-        _lib = L
-    return _lib
-
-
-def _p(a):
-    return None if a is None or a.size == 0 else a.ctypes.data_as(C.c_void_p)
-
-
-def _args(a, order):
-    return [_p(a["Tcw"]), _p(a["kf_fixed"]), len(a["Tcw"]), _p(a["x3Dw"]), len(a["x3Dw"]), _p(a["obs_offset"]), _p(a["obs_kf"]), _p(a["obs_xy"]),
-            _p(a["obs_octave"]), len(a["obs_kf"]), _p(a["K4"]), _p(a["inv_level_sigma2"]), len(a["inv_level_sigma2"]), _p(a["Twm"]),
-            _p(a["marker_local"]), len(a["Twm"]), _p(a["mobs_offset"]), _p(a["mobs_kf"]), _p(a["mobs_corners"]), len(a["mobs_kf"]),
-            a["marker_info"], a["use_markers"], int(order)]
+    return R.declare(ref_build.build_shared("lba_ref.cpp"), dict(ref_lba=[R.i32] + [R.vp] * 3, ref_lba_inspect=[R.i32] + [R.vp] * 7,
+                                                                 ref_lba_poses_only=[R.i32, R.i32]))
 
 
 def local_bundle_adjustment(pb, order=INSERTION):
@@ -52,7 +28,7 @@ def local_bundle_adjustment(pb, order=INSERTION):
     erase = np.zeros(max(nobs, 1), np.uint8)
     chi2 = np.zeros((2, max(nobs + nme, 1)))
     res = np.zeros(1, RESULT_DTYPE)
-    rc = lib().ref_lba(*(_args(a, order) + [_p(erase), _p(res), _p(chi2)]))
+    rc = lib().ref_lba(R.problem(a), int(order), _p(erase), _p(res), _p(chi2))
     return dict(rc=rc, Tcw=a["Tcw"].reshape(-1, 3, 4), x3Dw=a["x3Dw"], Twm=a["Twm"].reshape(-1, 3, 4), erase=erase[:nobs], result=res[0],
                 chi2=chi2[:, :nobs + nme])
 
@@ -60,72 +36,29 @@ def local_bundle_adjustment(pb, order=INSERTION):
 def inspect(pb, order=DEVICE, full=False):
     """As binding.lba_inspect; full=True adds H (the whole system with lambda0 on its diagonal, poses first) and b (its right side)."""
     a = binding.lba_arrays(pb)
-    n, V = len(a["x3Dw"]), binding.LBA_MAX_FREE_POSES
-    nv = np.zeros(1, np.int32)
-    b = np.zeros(6 * V + 3 * n); x = np.zeros_like(b)
-    Hpp = np.zeros((V, 6, 6)); Hll = np.zeros((max(n, 1), 6)); chi2 = np.zeros(2)
-    H = np.zeros((6 * V + 3 * n) ** 2) if full else None
-    rc = lib().ref_lba_inspect(*(_args(a, order) + [_p(nv), _p(b), _p(Hpp), _p(Hll), _p(chi2), _p(x), _p(H)]))
+    n = len(a["x3Dw"])
+    w = R.inspect_buffers(n, binding.LBA_MAX_FREE_POSES, 2, full)
+    rc = lib().ref_lba_inspect(R.problem(a), int(order), *[_p(w[k]) for k in ("nv", "b", "Hpp", "Hll", "chi2", "x", "H")])
     assert rc == 0, rc
-    v = int(nv[0])
-    out = dict(nv=v, b_pose=b[:6 * v].reshape(v, 6), b_point=b[6 * v:6 * v + 3 * n].reshape(n, 3), Hpp=Hpp[:v], Hll=Hll[:n], chi2=chi2[0],
-               lambda0=chi2[1], x_pose=x[:6 * v].reshape(v, 6), x_point=x[6 * v:6 * v + 3 * n].reshape(n, 3))
-    if full:
-        m = 6 * v + 3 * n
-        out["H"] = H[:m * m].reshape(m, m)
-        out["b"] = b[:m].copy()
-        out["x"] = x[:m].copy()
-    return out
+    return R.inspect_unpack(w, n, full)
 
 
 def poses_only(pb, maxit, order=INSERTION):
     """The restatement with its points held (the anchor to tests/pose_opt_ref.cpp): one optimize(maxit) with Huber.  Returns
     (Tcw n x 3 x 4, iterations)."""
     a = binding.lba_arrays(pb)
-    it = lib().ref_lba_poses_only(_p(a["Tcw"]), _p(a["kf_fixed"]), len(a["Tcw"]), _p(a["x3Dw"]), len(a["x3Dw"]), _p(a["obs_offset"]), _p(a["obs_kf"]),
-                                  _p(a["obs_xy"]), _p(a["obs_octave"]), len(a["obs_kf"]), _p(a["K4"]), _p(a["inv_level_sigma2"]), int(maxit), int(order))
+    it = lib().ref_lba_poses_only(R.problem(a), int(maxit), int(order))
     return a["Tcw"].reshape(-1, 3, 4), it
 
 
-def _d(a):
-    return np.ascontiguousarray(a, np.float64)
-
-
-def _f(a, n):
-    return np.ascontiguousarray(a, np.float32).reshape(n)
-
-
 def mono_edge(Tcw, u, X, obs, K4):
-    """(err, Jpose 2 x 6, Jpoint 2 x 3) of one EdgeSE3ProjectXYZ at exp(u) * Tcw and X."""
-    err = np.zeros(2); Jp = np.zeros((2, 6)); Jx = np.zeros((2, 3))
-    u, X, obs, T, K = _d(u), _d(X), _d(obs), _f(Tcw, 12), _f(K4, 4)
-    lib().ref_lba_mono_edge(_p(T), _p(u), _p(X), _p(obs), _p(K), _p(err), _p(Jp), _p(Jx))
-    return err, Jp, Jx
+    return R.mono_edge(lib(), Tcw, u, X, obs, K4)
 
 
 def marker_edge(Tcw, Twm, p, obs, K4):
-    """(err, Jcamera 2 x 6, Jmarker 2 x 6): one EdgeMarker with g2o's numeric Jacobians."""
-    err = np.zeros(2); Jc = np.zeros((2, 6)); Jm = np.zeros((2, 6))
-    Tc, Tm, p, obs, K = _f(Tcw, 12), _f(Twm, 12), _d(p), _d(obs), _f(K4, 4)
-    lib().ref_lba_marker_edge(_p(Tc), _p(Tm), _p(p), _p(obs), _p(K), _p(err), _p(Jc), _p(Jm))
-    return err, Jc, Jm
+    return R.marker_edge(lib(), Tcw, Twm, p, obs, K4)
 
 
 def build_shim(out_dir):
-    """include/shims/Optimizer_localba_orbfe.cc and tests/lba_shim_driver.cpp as one program: the fuller mock headers of
-    tests/mock_orbslam_lba/ ahead of the one mock tree tests/mock_orbslam/, linked against the built library."""
-    import os
-    import subprocess
-    root, here = ref_build.ROOT, ref_build.HERE
-    inc = []
-    for d in ("tests/mock_orbslam_lba",) + ref_build.MOCK_DIRS + ("include", "include/shims", "tests"):
-        inc += ["-I", os.path.join(root, d)]
-    flags = ["g++", "-std=c++14", "-O1", "-Wall", "-Werror", "-pthread"]
-    objs = []
-    for src in (os.path.join(root, "include", "shims", "Optimizer_localba_orbfe.cc"), os.path.join(here, "mock_orbslam", "Frame_statics.cc")):
-        objs.append(os.path.join(out_dir, os.path.splitext(os.path.basename(src))[0] + ".o"))
-        subprocess.check_call(flags + inc + ["-c", src, "-o", objs[-1]])
-    exe = os.path.join(out_dir, "lba_shim_driver")
-    lib_dir = os.path.join(root, "orb_slam2_aruco_amd")
-    subprocess.check_call(flags + inc + [os.path.join(here, "lba_shim_driver.cpp")] + objs + ["-o", exe, "-L", lib_dir, "-lorbfe", "-Wl,-rpath," + lib_dir])
-    return exe
+    """include/shims/Optimizer_localba_orbfe.cc and tests/lba_shim_driver.cpp as one program"""
+    return ref_build.build_shim(("Optimizer_localba_orbfe.cc",), "lba_shim_driver.cpp", out_dir)

@@ -29,8 +29,11 @@ def rot_angle(Ra, Rb):
 
 
 def distance(a, b, pb):
-    """max |dR|, |dt| / extent, |dX| / extent over the keyframes, the points and the marker poses of two results"""
-    ex = lba_cases.extent(pb)
+    return scaled_distance(a, b, lba_cases.extent(pb))
+
+
+def scaled_distance(a, b, ex):
+    """max |dR|, |dt| / ex, |dX| / ex over the keyframes, the points and the marker poses of two results; ex is the problem's extent"""
     out = dict(dR=rot_angle(a["Tcw"][:, :, :3], b["Tcw"][:, :, :3]), dt=0.0, dX=0.0, dRm=rot_angle(a["Twm"][:, :, :3], b["Twm"][:, :, :3]), dtm=0.0)
     if len(a["Tcw"]):
         out["dt"] = float(np.abs(a["Tcw"][:, :, 3].astype(np.float64) - b["Tcw"][:, :, 3]).max() / ex)

@@ -1,7 +1,7 @@
 // lba_ref.cpp -- CPU restatement of ORB_SLAM2's Optimizer::LocalBundleAdjustment (src/Optimizer.cc:892-1242 of the reference, behind
 // its collect step, with this fork's marker poses as free SE3 vertices) for the parity tests of orbfe_local_bundle_adjustment*.
 // No g2o or Eigen here; the pieces are restated from their algorithms, SE3Quat, the Huber kernel and the Levenberg-Marquardt rules in
-// tests/g2o_ref.hpp (shared by the three restatements):
+// tests/g2o_ref.hpp (shared by the restatements), and what this one has in common with tests/gba_ref.cpp in tests/ba_ref.hpp:
 //   EdgeSE3ProjectXYZ        e = obs - pi(T Xw), Omega = invSigma2 I, g2o's analytic Jacobians for the point and the pose
 //   EdgeMarker               e = obs - pi((Tcw Twm) p), Omega = w I, numeric Jacobians on both vertices: central differences,
 //                            delta = 1e-9, through exp(+-delta e_d) * estimate; none for a fixed keyframe
@@ -25,7 +25,7 @@
 #include <cstring>
 #include <vector>
 
-#include "g2o_ref.hpp"
+#include "ba_ref.hpp"
 
 namespace {
 
@@ -38,151 +38,16 @@ struct Result {     // the layout of orbfe_lba_result
     int32_t status;
 };
 
-void rot_of(const Quat& q, double R[3][3])
-{
-    const double tx = 2 * q.x, ty = 2 * q.y, tz = 2 * q.z;
-    const double twx = tx * q.w, twy = ty * q.w, twz = tz * q.w;
-    const double txx = tx * q.x, txy = ty * q.x, txz = tz * q.x;
-    const double tyy = ty * q.y, tyz = tz * q.y, tzz = tz * q.z;
-    R[0][0] = 1 - (tyy + tzz); R[0][1] = txy - twz; R[0][2] = txz + twy;
-    R[1][0] = txy + twz; R[1][1] = 1 - (txx + tzz); R[1][2] = tyz - twx;
-    R[2][0] = txz - twy; R[2][1] = tyz + twx; R[2][2] = 1 - (txx + tyy);
-}
-
-void mono_error(const SE3& T, const double Xw[3], double ox, double oy, const Cam& K, double err[2])
-{
-    double Xc[3];
-    map(T, Xw, Xc);
-    project_error(Xc, ox, oy, K, err);
-}
-
-// EdgeSE3ProjectXYZ::linearizeOplus
-void mono_linearize(const SE3& T, const double Xw[3], double ox, double oy, const Cam& K, double err[2], double Jp[2][6], double Jx[2][3])
-{
-    double Xc[3], R[3][3];
-    map(T, Xw, Xc);
-    project_error(Xc, ox, oy, K, err);
-    const double x = Xc[0], y = Xc[1], z = Xc[2], z_2 = z * z;
-    const double s = -1. / z;
-    const double t0[3] = {s * K.fx, s * 0., s * (-x / z * K.fx)}, t1[3] = {s * 0., s * K.fy, s * (-y / z * K.fy)};
-    rot_of(T.q, R);
-    for (int c = 0; c < 3; c++) {
-        Jx[0][c] = t0[0] * R[0][c] + t0[1] * R[1][c] + t0[2] * R[2][c];
-        Jx[1][c] = t1[0] * R[0][c] + t1[1] * R[1][c] + t1[2] * R[2][c];
-    }
-    Jp[0][0] = x * y / z_2 * K.fx;
-    Jp[0][1] = -(1 + (x * x / z_2)) * K.fx;
-    Jp[0][2] = y / z * K.fx;
-    Jp[0][3] = -1. / z * K.fx;
-    Jp[0][4] = 0;
-    Jp[0][5] = x / z_2 * K.fx;
-    Jp[1][0] = (1 + y * y / z_2) * K.fy;
-    Jp[1][1] = -x * y / z_2 * K.fy;
-    Jp[1][2] = -x / z * K.fy;
-    Jp[1][3] = 0;
-    Jp[1][4] = -1. / z * K.fy;
-    Jp[1][5] = y / z_2 * K.fy;
-}
-
-void marker_error(const SE3& Tc, const SE3& Tm, const double pm[3], double ox, double oy, const Cam& K, double err[2])
-{
-    const SE3 Tcm = mul(Tc, Tm);
-    double Xc[3];
-    map(Tcm, pm, Xc);
-    project_error(Xc, ox, oy, K, err);
-}
-
-void marker_jacobian(const SE3& Tc, const SE3& Tm, bool camera, const double pm[3], double ox, double oy, const Cam& K, double J[2][6])
-{
-    const double delta = 1e-9, scalar = 1.0 / (2 * delta);
-    for (int d = 0; d < 6; d++) {
-        double u[6] = {0, 0, 0, 0, 0, 0}, ep[2], em[2];
-        u[d] = delta;
-        SE3 E = se3_exp(u);
-        if (camera) marker_error(mul(E, Tc), Tm, pm, ox, oy, K, ep);
-        else marker_error(Tc, mul(E, Tm), pm, ox, oy, K, ep);
-        u[d] = -delta;
-        E = se3_exp(u);
-        if (camera) marker_error(mul(E, Tc), Tm, pm, ox, oy, K, em);
-        else marker_error(Tc, mul(E, Tm), pm, ox, oy, K, em);
-        J[0][d] = scalar * (ep[0] - em[0]);
-        J[1][d] = scalar * (ep[1] - em[1]);
-    }
-}
-
-bool all_finite(const double* v, int n)
-{
-    for (int i = 0; i < n; i++)
-        if (!std::isfinite(v[i])) return false;
-    return true;
-}
-
-void diag_block(const double J[2][6], double w, double r0, double r1, double* out)
-{
-    int k = 0;
-    for (int a = 0; a < 6; a++)
-        for (int c = a; c < 6; c++, k++) out[k] = J[0][a] * (w * J[0][c]) + J[1][a] * (w * J[1][c]);
-    for (int a = 0; a < 6; a++) out[21 + a] = J[0][a] * r0 + J[1][a] * r1;
-}
-
-// ------------------------------------------------------------------------------------------ the device's sums --
-double butterfly64(double* v)
-{
-    double t[64];
-    for (int off = 32; off >= 1; off >>= 1) {
-        for (int l = 0; l < 64; l++) t[l] = v[l] + v[l ^ off];
-        std::memcpy(v, t, sizeof(t));
-    }
-    return v[0];
-}
-
-double block256(double* v)   // 256 thread values: a butterfly per wave, the waves in order
-{
-    double s = butterfly64(v);
-    for (int w = 1; w < 4; w++) s += butterfly64(v + 64 * w);
-    return s;
-}
-
-double parts_sum(const std::vector<double>& part)
-{
-    const int n = (int)part.size(), per = (n + 255) / 256;
-    double v[256];
-    for (int t = 0; t < 256; t++) {
-        const int lo = std::min(t * per, n), hi = std::min(lo + per, n);
-        double s = 0;
-        for (int i = lo; i < hi; i++) s += part[i];
-        v[t] = s;
-    }
-    return block256(v);
-}
-
 // ------------------------------------------------------------------------------------------ the problem --
-constexpr int EB = 45, MB = 90, MAXV = 64;
+constexpr int MAXV = 64;
 
-struct Prob {
-    int nkf, np, nobs, nma, nmobs, nme, nv, order;
+struct Prob : Core {
     bool fix_points = false;   // the anchor's hook: the points are held, only pose blocks are built (what a motion-only optimization solves)
-    const uint8_t* fixed;
-    const int32_t *off, *okf;
-    const float* oxy;
-    std::vector<double> info;
-    Cam K;
-    double delta, minfo;
-    const float* mlocal;
-    const int32_t *moff, *mkf;
-    const float* mcor;
-    std::vector<int> mo_marker, kf_free, v_kf, e_pt, tbl;
+    std::vector<int> tbl;      // the edge of keyframe kf and point pi at kf * np + pi, or -1
 };
 
-struct Est {
-    std::vector<SE3> pose;      // nkf keyframes, then nma markers
-    std::vector<double> pt;
-};
-
-struct Lin {
-    std::vector<double> Hll, bl, Hpp, bp, eblk, mblk, Dinv;
-    std::vector<uint8_t> euse, muse, pact, vact;
-    double chi, maxdiag;
+struct LbaLin : Lin {   // with the activity of the round: a point with an edge at level 0, a vertex with one
+    std::vector<uint8_t> pact, vact;
 };
 
 struct Cache {
@@ -190,109 +55,26 @@ struct Cache {
     std::vector<uint8_t> e_level, m_level;
 };
 
-// the chi2 of a pass from the per-edge robust values: edge by edge, or the device's tree
-double chi_sum(const Prob& P, const std::vector<double>& e_rho, const std::vector<double>& m_rho, const Cache& C)
+void linearize(const Prob& P, const Est& X, bool robust, Cache& C, LbaLin& L)
 {
-    if (P.order == 0) {
-        double s = 0;
-        for (int e = 0; e < P.nobs; e++)
-            if (!C.e_level[e]) s += e_rho[e];
-        for (int j = 0; j < P.nme; j++)
-            if (!C.m_level[j]) s += m_rho[j];
-        return s;
-    }
-    const int npb = (P.np + 63) / 64, nb = npb + (P.nme + 63) / 64;
-    std::vector<double> part((size_t)nb, 0.);
-    for (int b = 0; b < nb; b++) {
-        double v[64];
-        for (int l = 0; l < 64; l++) {
-            double s = 0;
-            if (b < npb) {
-                const int pi = b * 64 + l;
-                if (pi < P.np)
-                    for (int e = P.off[pi]; e < P.off[pi + 1]; e++)
-                        if (!C.e_level[e]) s += e_rho[e];
-            } else {
-                const int j = (b - npb) * 64 + l;
-                if (j < P.nme && !C.m_level[j]) s += m_rho[j];
-            }
-            v[l] = s;
-        }
-        part[(size_t)b] = butterfly64(v);
-    }
-    return parts_sum(part);
-}
-
-void linearize(const Prob& P, const Est& X, bool robust, Cache& C, Lin& L)
-{
-    L.Hll.assign((size_t)P.np * 6, 0.); L.bl.assign((size_t)P.np * 3, 0.); L.Hpp.assign((size_t)P.nv * 36, 0.); L.bp.assign((size_t)P.nv * 6, 0.);
-    L.eblk.assign((size_t)P.nobs * EB, 0.); L.mblk.assign((size_t)P.nme * MB, 0.);
-    L.euse.assign((size_t)P.nobs, 0); L.muse.assign((size_t)P.nme, 0); L.pact.assign((size_t)P.np, 0); L.vact.assign((size_t)P.nv, 0);
-    L.Dinv.assign((size_t)P.np * 9, 0.);
+    lin_clear(P, L);
+    L.pact.assign((size_t)P.np, 0); L.vact.assign((size_t)P.nv, 0);
     std::vector<double> e_rho((size_t)P.nobs, 0.), m_rho((size_t)P.nme, 0.);
     double md = 0;
     for (int pi = 0; pi < P.np; pi++) {
-        const double* Xw = &X.pt[(size_t)pi * 3];
-        double* H = &L.Hll[(size_t)pi * 6];
-        double* b = &L.bl[(size_t)pi * 3];
+        const double* H = &L.Hll[(size_t)pi * 6];
         int nact = 0;
         for (int e = P.off[pi]; e < P.off[pi + 1]; e++) {
             if (C.e_level[e]) continue;
             nact++;
-            const int kf = P.okf[e];
-            double err[2], Jp[2][6], Jx[2][3];
-            mono_linearize(X.pose[(size_t)kf], Xw, P.oxy[2 * e], P.oxy[2 * e + 1], P.K, err, Jp, Jx);
-            const double info = P.info[(size_t)e], ch = chi2_of(err, info);
-            C.e_chi2[e] = ch;
-            double rho[2] = {ch, 1.};
-            if (robust) huber(ch, P.delta, rho);
-            e_rho[e] = rho[0];
-            const bool fin = all_finite(err, 2) && all_finite(&Jp[0][0], 12) && all_finite(&Jx[0][0], 6) && std::isfinite(rho[1]);
-            const int vf = P.kf_free[(size_t)kf];
-            L.euse[e] = fin ? (vf >= 0 ? 3 : 1) : 0;
-            if (!fin) continue;
-            const double w = rho[1] * info, r0 = rho[1] * -(info * err[0]), r1 = rho[1] * -(info * err[1]);
-            int k = 0;
-            for (int a = 0; a < 3; a++)
-                for (int c = a; c < 3; c++, k++) H[k] += Jx[0][a] * (w * Jx[0][c]) + Jx[1][a] * (w * Jx[1][c]);
-            for (int a = 0; a < 3; a++) b[a] += Jx[0][a] * r0 + Jx[1][a] * r1;
-            if (vf >= 0) {
-                double* out = &L.eblk[(size_t)e * EB];
-                diag_block(Jp, w, r0, r1, out);
-                for (int a = 0; a < 6; a++)
-                    for (int c = 0; c < 3; c++) out[27 + a * 3 + c] = Jp[0][a] * (w * Jx[0][c]) + Jp[1][a] * (w * Jx[1][c]);
-            }
+            mono_edge_add(P, X, robust, pi, e, L, C.e_chi2[e], e_rho[e]);
         }
         L.pact[pi] = nact > 0 && !P.fix_points;
         if (L.pact[pi]) md = std::max(md, std::max(std::max(std::fabs(H[0]), std::fabs(H[3])), std::fabs(H[5])));
     }
-    for (int j = 0; j < P.nme; j++) {
-        if (C.m_level[j]) continue;
-        const int o = j >> 2, k = j & 3, kf = P.mkf[o], m = P.mo_marker[(size_t)o];
-        const SE3 &Tc = X.pose[(size_t)kf], &Tm = X.pose[(size_t)(P.nkf + m)];
-        const double pm[3] = {P.mlocal[m * 12 + 3 * k], P.mlocal[m * 12 + 3 * k + 1], P.mlocal[m * 12 + 3 * k + 2]};
-        const double ox = P.mcor[o * 8 + 2 * k], oy = P.mcor[o * 8 + 2 * k + 1];
-        const bool camfree = P.kf_free[(size_t)kf] >= 0;
-        double err[2], Jc[2][6] = {}, Jm[2][6], rho[2];
-        marker_error(Tc, Tm, pm, ox, oy, P.K, err);
-        const double ch = chi2_of(err, P.minfo);
-        C.m_chi2[j] = ch;
-        rho[0] = ch; rho[1] = 1.;
-        if (robust) huber(ch, P.delta, rho);
-        m_rho[j] = rho[0];
-        if (camfree) marker_jacobian(Tc, Tm, true, pm, ox, oy, P.K, Jc);
-        marker_jacobian(Tc, Tm, false, pm, ox, oy, P.K, Jm);
-        const bool fin = all_finite(err, 2) && all_finite(&Jc[0][0], 12) && all_finite(&Jm[0][0], 12) && std::isfinite(rho[1]);
-        L.muse[j] = fin;
-        if (!fin) continue;
-        const double w = rho[1] * P.minfo, r0 = rho[1] * -(P.minfo * err[0]), r1 = rho[1] * -(P.minfo * err[1]);
-        double* out = &L.mblk[(size_t)j * MB];
-        diag_block(Jc, w, r0, r1, out);
-        diag_block(Jm, w, r0, r1, out + 27);
-        for (int a = 0; a < 6; a++)
-            for (int c = 0; c < 6; c++) out[54 + a * 6 + c] = Jc[0][a] * (w * Jm[0][c]) + Jc[1][a] * (w * Jm[1][c]);
-    }
-    L.chi = chi_sum(P, e_rho, m_rho, C);
+    for (int j = 0; j < P.nme; j++)
+        if (!C.m_level[j]) corner_edge_add(P, X, robust, j, L, C.m_chi2[j], m_rho[j]);
+    L.chi = chi_sum(P, e_rho, m_rho, C.e_level.data(), C.m_level.data());
     // the pose blocks
     for (int v = 0; v < P.nv; v++) {
         const int kf = P.v_kf[(size_t)v];
@@ -335,15 +117,7 @@ void linearize(const Prob& P, const Est& X, bool robust, Cache& C, Lin& L)
                 for (int k = 0; k < 27; k++) s[k] += L.mblk[(size_t)j * MB + 27 + k];
             }
         }
-        double* H = &L.Hpp[(size_t)v * 36];
-        int k = 0;
-        double mv = 0;
-        for (int a = 0; a < 6; a++)
-            for (int c = a; c < 6; c++, k++) H[a * 6 + c] = H[c * 6 + a] = s[k];
-        for (int a = 0; a < 6; a++) {
-            L.bp[(size_t)v * 6 + a] = s[21 + a];
-            mv = std::max(mv, std::fabs(H[a * 6 + a]));
-        }
+        const double mv = pose_block_store(s, v, L);
         L.vact[v] = s[27] > 0;
         if (s[27] > 0) md = std::max(md, mv);
     }
@@ -351,31 +125,13 @@ void linearize(const Prob& P, const Est& X, bool robust, Cache& C, Lin& L)
 }
 
 // the reduced system of one trial: S (n x n, n = 6 nv) and bs; Dinv of the active points
-void schur(const Prob& P, const Cache& C, Lin& L, double lambda, std::vector<double>& S, std::vector<double>& bs)
+void schur(const Prob& P, const Cache& C, LbaLin& L, double lambda, std::vector<double>& S, std::vector<double>& bs)
 {
     const int n = 6 * P.nv;
     S.assign((size_t)n * n, 0.);
     bs.assign((size_t)n, 0.);
-    for (int pi = 0; pi < P.np; pi++) {
-        if (!L.pact[pi]) continue;
-        const double* H = &L.Hll[(size_t)pi * 6];
-        const double m00 = H[0] + lambda, m01 = H[1], m02 = H[2], m11 = H[3] + lambda, m12 = H[4], m22 = H[5] + lambda;
-        const double c00 = m11 * m22 - m12 * m12, c10 = m12 * m02 - m01 * m22, c20 = m01 * m12 - m11 * m02;
-        const double det = c00 * m00 + c10 * m01 + c20 * m02, id = 1. / det;
-        double* D = &L.Dinv[(size_t)pi * 9];
-        D[0] = c00 * id; D[1] = c10 * id; D[2] = c20 * id;
-        D[3] = D[1]; D[4] = (m00 * m22 - m02 * m02) * id; D[5] = (m02 * m01 - m00 * m12) * id;
-        D[6] = D[2]; D[7] = D[5]; D[8] = (m00 * m11 - m01 * m01) * id;
-    }
-    auto contribution = [&](int ei, int ej, int pi, bool diag, double* acc, double* accb) {
-        const double *Wi = &L.eblk[(size_t)ei * EB + 27], *Wj = &L.eblk[(size_t)ej * EB + 27], *D = &L.Dinv[(size_t)pi * 9], *bl = &L.bl[(size_t)pi * 3];
-        for (int a = 0; a < 6; a++) {
-            double Y[3];
-            for (int c = 0; c < 3; c++) Y[c] = Wi[a * 3] * D[c] + Wi[a * 3 + 1] * D[3 + c] + Wi[a * 3 + 2] * D[6 + c];
-            for (int b = 0; b < 6; b++) acc[a * 6 + b] += Y[0] * Wj[b * 3] + Y[1] * Wj[b * 3 + 1] + Y[2] * Wj[b * 3 + 2];
-            if (diag) accb[a] += Y[0] * bl[0] + Y[1] * bl[1] + Y[2] * bl[2];
-        }
-    };
+    for (int pi = 0; pi < P.np; pi++)
+        if (L.pact[pi]) damped_inverse(L, pi, lambda);
     for (int i = 0; i < P.nv; i++)
         for (int j = i; j < P.nv; j++) {
             const int ki = P.v_kf[(size_t)i], kj = P.v_kf[(size_t)j];
@@ -391,7 +147,7 @@ void schur(const Prob& P, const Cache& C, Lin& L, double lambda, std::vector<dou
                 if (P.order == 0) {
                     for (int pi = 0; pi < P.np; pi++) {
                         int ei, ej;
-                        if (usable(pi, ei, ej)) contribution(ei, ej, pi, i == j, acc, accb);
+                        if (usable(pi, ei, ej)) schur_contribution(L, ei, ej, pi, i == j, acc, accb);
                     }
                 } else {
                     std::vector<double> th((size_t)42 * 64, 0.);
@@ -401,13 +157,12 @@ void schur(const Prob& P, const Cache& C, Lin& L, double lambda, std::vector<dou
                         const int lo = std::min(t * per, P.np), hi = std::min(lo + per, P.np);
                         for (int pi = lo; pi < hi; pi++) {
                             int ei, ej;
-                            if (usable(pi, ei, ej)) contribution(ei, ej, pi, i == j, a36, a6);
+                            if (usable(pi, ei, ej)) schur_contribution(L, ei, ej, pi, i == j, a36, a6);
                         }
                         for (int k = 0; k < 36; k++) th[(size_t)k * 64 + t] = a36[k];
                         for (int k = 0; k < 6; k++) th[(size_t)(36 + k) * 64 + t] = a6[k];
                     }
-                    for (int k = 0; k < 36; k++) acc[k] = butterfly64(&th[(size_t)k * 64]);
-                    for (int k = 0; k < 6; k++) accb[k] = butterfly64(&th[(size_t)(36 + k) * 64]);
+                    lanes_sum(th, acc, accb);
                 }
             }
             if (!act) {
@@ -426,46 +181,17 @@ void schur(const Prob& P, const Cache& C, Lin& L, double lambda, std::vector<dou
                     for (int k = 0; k < 36; k++) B[k] += L.mblk[(size_t)e * MB + 54 + k];
                 }
             }
-            for (int a = 0; a < 6; a++)
-                for (int b = 0; b < 6; b++) S[(size_t)(6 * i + a) * n + 6 * j + b] = S[(size_t)(6 * j + b) * n + 6 * i + a] = B[a * 6 + b];
-            if (i == j)
-                for (int a = 0; a < 6; a++) bs[(size_t)6 * i + a] = act ? L.bp[(size_t)6 * i + a] - accb[a] : 0.;
+            schur_store(P, L, i, j, B, act, accb, S, bs);
         }
-}
-
-// L L^T in place, right-looking, no pivoting; then the two substitutions.  x is untouched when a pivot fails.
-bool llt_solve(std::vector<double>& S, int n, const std::vector<double>& b, double* x)
-{
-    for (int k = 0; k < n; k++) {
-        const double d = S[(size_t)k * n + k];
-        if (!(d > 0) || !std::isfinite(d)) return false;
-        const double lkk = S[(size_t)k * n + k] = std::sqrt(d);
-        for (int i = k + 1; i < n; i++) S[(size_t)i * n + k] /= lkk;
-        for (int i = k + 1; i < n; i++) {
-            const double lik = S[(size_t)i * n + k];
-            for (int j = k + 1; j <= i; j++) S[(size_t)i * n + j] -= lik * S[(size_t)j * n + k];
-        }
-    }
-    std::vector<double> y(b);
-    for (int k = 0; k < n; k++) {
-        y[(size_t)k] /= S[(size_t)k * n + k];
-        for (int i = k + 1; i < n; i++) y[(size_t)i] -= S[(size_t)i * n + k] * y[(size_t)k];
-    }
-    for (int k = n - 1; k >= 0; k--) {
-        y[(size_t)k] /= S[(size_t)k * n + k];
-        for (int i = 0; i < k; i++) y[(size_t)i] -= S[(size_t)k * n + i] * y[(size_t)k];
-    }
-    for (int i = 0; i < n; i++) x[i] = y[(size_t)i];
-    return true;
 }
 
 // one trial: the reduced solve, the updates, the trial estimates and their chi2 (written to the cache).  Returns ok2.
-bool trial(const Prob& P, Cache& C, Lin& L, double lambda, bool robust, const Est& X, Est& Xt, std::vector<double>& xv, std::vector<double>& xl,
+bool trial(const Prob& P, Cache& C, LbaLin& L, double lambda, bool robust, const Est& X, Est& Xt, std::vector<double>& xv, std::vector<double>& xl,
            double& tempChi, double& scale_points)
 {
     std::vector<double> S, bs;
     schur(P, C, L, lambda, S, bs);
-    const bool ok = llt_solve(S, 6 * P.nv, bs, xv.data());
+    const bool ok = llt_solve(S, 6 * P.nv, bs, xv.data(), false);
     Xt = X;
     for (int v = 0; v < P.nv; v++)
         if (L.vact[v]) {
@@ -477,21 +203,7 @@ bool trial(const Prob& P, Cache& C, Lin& L, double lambda, bool robust, const Es
         if (!L.pact[pi] && !P.fix_points) continue;
         double* x = &xl[(size_t)pi * 3];
         const double* bl = &L.bl[(size_t)pi * 3];
-        if (ok && L.pact[pi]) {
-            double r[3] = {bl[0], bl[1], bl[2]};
-            for (int e = P.off[pi]; e < P.off[pi + 1]; e++) {
-                if (C.e_level[e] || L.euse[e] != 3) continue;
-                const double* W = &L.eblk[(size_t)e * EB + 27];
-                const double* xp = &xv[(size_t)P.kf_free[(size_t)P.okf[e]] * 6];
-                for (int c = 0; c < 3; c++) {
-                    double s = 0;
-                    for (int a = 0; a < 6; a++) s += W[a * 3 + c] * xp[a];
-                    r[c] -= s;
-                }
-            }
-            const double* D = &L.Dinv[(size_t)pi * 9];
-            for (int a = 0; a < 3; a++) x[a] = D[a * 3] * r[0] + D[a * 3 + 1] * r[1] + D[a * 3 + 2] * r[2];
-        }
+        if (ok && L.pact[pi]) back_substitute(P, L, pi, xv, x);
         double s = 0;
         for (int a = 0; a < 3 && L.pact[pi]; a++) {
             s += x[a] * (lambda * x[a] + bl[a]);
@@ -511,30 +223,21 @@ bool trial(const Prob& P, Cache& C, Lin& L, double lambda, bool robust, const Es
     }
     for (int j = 0; j < P.nme; j++) {
         if (C.m_level[j]) continue;
-        const int o = j >> 2, k = j & 3, m = P.mo_marker[(size_t)o];
-        const double pm[3] = {P.mlocal[m * 12 + 3 * k], P.mlocal[m * 12 + 3 * k + 1], P.mlocal[m * 12 + 3 * k + 2]};
         double err[2], rho[2];
-        marker_error(Xt.pose[(size_t)P.mkf[o]], Xt.pose[(size_t)(P.nkf + m)], pm, P.mcor[o * 8 + 2 * k], P.mcor[o * 8 + 2 * k + 1], P.K, err);
+        corner_error(P, Xt, j, err);
         const double ch = chi2_of(err, P.minfo);
         C.m_chi2[j] = ch;
         rho[0] = ch;
         if (robust) huber(ch, P.delta, rho);
         m_rho[j] = rho[0];
     }
-    tempChi = chi_sum(P, e_rho, m_rho, C);
+    tempChi = chi_sum(P, e_rho, m_rho, C.e_level.data(), C.m_level.data());
     if (P.order == 0) {
         double s = 0;
         for (int pi = 0; pi < P.np; pi++) s += sc[(size_t)pi];
         scale_points = s;
     } else {
-        const int npb = (P.np + 63) / 64, nb = npb + (P.nme + 63) / 64;
-        std::vector<double> part((size_t)nb, 0.);
-        for (int b = 0; b < npb; b++) {
-            double v[64];
-            for (int l = 0; l < 64; l++) v[l] = b * 64 + l < P.np ? sc[(size_t)(b * 64 + l)] : 0.;
-            part[(size_t)b] = butterfly64(v);
-        }
-        scale_points = parts_sum(part);
+        scale_points = points_scale_device(P, sc);
     }
     return ok;
 }
@@ -546,7 +249,7 @@ int optimize(const Prob& P, Cache& C, Est& X, bool robust, int maxit, std::vecto
     lm_begin(c);
     stale = false;
     int it = 0;
-    Lin L;
+    LbaLin L;
     Est Xt;
     while (it < maxit) {
         linearize(P, X, robust, C, L);
@@ -566,63 +269,36 @@ int optimize(const Prob& P, Cache& C, Est& X, bool robust, int maxit, std::vecto
     return it;
 }
 
-bool setup(Prob& P, Est& X, const float* Tcw, const uint8_t* kf_fixed, int nkf, const float* x3Dw, int np, const int32_t* obs_offset,
-           const int32_t* obs_kf, const float* obs_xy, const int32_t* obs_octave, int nobs, const float* K4, const float* inv_sigma2,
-           const float* Twm, const float* marker_local, int nma, const int32_t* mobs_offset, const int32_t* mobs_kf, const float* mobs_corners,
-           int nmobs, float marker_info, int use_markers, int order)
+// the Huber constant is the reference's for this optimizer, sqrt(5.991); tests/gba_ref.cpp has the reference's other one, on purpose
+bool setup(Prob& P, Est& X, const Flat& f, int order)
 {
-    P.nkf = nkf; P.np = np; P.nobs = nobs; P.nma = nma; P.nmobs = nmobs; P.nme = use_markers ? 4 * nmobs : 0; P.order = order;
-    P.fixed = kf_fixed; P.off = obs_offset; P.okf = obs_kf; P.oxy = obs_xy;
-    P.K = Cam{K4[0], K4[1], K4[2], K4[3]};
-    P.delta = (double)(float)std::sqrt(5.991);
-    P.minfo = marker_info;
-    P.mlocal = marker_local; P.moff = mobs_offset; P.mkf = mobs_kf; P.mcor = mobs_corners;
-    P.info.resize((size_t)nobs);
-    for (int e = 0; e < nobs; e++) P.info[(size_t)e] = inv_sigma2[obs_octave[e]];
-    P.mo_marker.assign((size_t)nmobs, 0);
-    for (int m = 0; m < nma; m++)
-        for (int o = mobs_offset[m]; o < mobs_offset[m + 1]; o++) P.mo_marker[(size_t)o] = m;
-    P.kf_free.assign((size_t)nkf, -1);
-    P.v_kf.clear();
-    for (int k = 0; k < nkf; k++)
-        if (!kf_fixed[k]) {
-            P.kf_free[(size_t)k] = (int)P.v_kf.size();
-            P.v_kf.push_back(k);
-        }
-    for (int m = 0; use_markers && m < nma; m++) P.v_kf.push_back(nkf + m);
-    P.nv = (int)P.v_kf.size();
-    P.tbl.assign((size_t)std::max(nkf, 1) * std::max(np, 1), -1);
-    for (int pi = 0; pi < np; pi++)
-        for (int e = obs_offset[pi]; e < obs_offset[pi + 1]; e++) P.tbl[(size_t)obs_kf[e] * np + pi] = e;
-    X.pose.resize((size_t)(nkf + nma));
-    for (int k = 0; k < nkf; k++) X.pose[(size_t)k] = se3_from_float(Tcw + 12 * k);
-    for (int m = 0; m < nma; m++) X.pose[(size_t)(nkf + m)] = se3_from_float(Twm + 12 * m);
-    X.pt.resize((size_t)np * 3);
-    for (int i = 0; i < 3 * np; i++) X.pt[(size_t)i] = x3Dw[i];
+    setup_core(P, X, f, order, (double)(float)std::sqrt(5.991));
+    P.tbl.assign((size_t)std::max(f.nkf, 1) * std::max(f.np, 1), -1);
+    for (int pi = 0; pi < f.np; pi++)
+        for (int e = f.obs_offset[pi]; e < f.obs_offset[pi + 1]; e++) P.tbl[(size_t)f.obs_kf[e] * f.np + pi] = e;
     return P.nv <= MAXV;
+}
+
+void cache_clear(const Prob& P, Cache& C)
+{
+    C.e_chi2.assign((size_t)P.nobs, 0.); C.m_chi2.assign((size_t)P.nme, 0.); C.e_level.assign((size_t)P.nobs, 0); C.m_level.assign((size_t)P.nme, 0);
 }
 
 } // namespace
 
-// Tcw, x3Dw, Twm are in / out as in the library.  chi2_checks: 2 x (nobs + 4 nmobs) doubles, the cached chi2 of every edge at the two
+// f's Tcw, x3Dw, Twm are in / out as in the library.  chi2_checks: 2 x (nobs + 4 nmobs) doubles, the cached chi2 of every edge at the two
 // checks (monocular edges, then marker edges).  Returns 0, or -4 beyond the pose bound.
-extern "C" int ref_lba(float* Tcw, const uint8_t* kf_fixed, int nkf, float* x3Dw, int np, const int32_t* obs_offset, const int32_t* obs_kf,
-                       const float* obs_xy, const int32_t* obs_octave, int nobs, const float* K4, const float* inv_sigma2, int nlevels,
-                       float* Twm, const float* marker_local, int nma, const int32_t* mobs_offset, const int32_t* mobs_kf,
-                       const float* mobs_corners, int nmobs, float marker_info, int use_markers, int order, uint8_t* erase, Result* res,
-                       double* chi2_checks)
+extern "C" int ref_lba(const Flat* f, int order, uint8_t* erase, Result* res, double* chi2_checks)
 {
-    (void)nlevels;
     std::memset(res, 0, sizeof(*res));
     Prob P;
     Est X;
-    if (!setup(P, X, Tcw, kf_fixed, nkf, x3Dw, np, obs_offset, obs_kf, obs_xy, obs_octave, nobs, K4, inv_sigma2, Twm, marker_local, nma,
-               mobs_offset, mobs_kf, mobs_corners, nmobs, marker_info, use_markers, order))
-        return -4;
+    if (!setup(P, X, *f, order)) return -4;
     Cache C;
-    C.e_chi2.assign((size_t)nobs, 0.); C.m_chi2.assign((size_t)P.nme, 0.); C.e_level.assign((size_t)nobs, 0); C.m_level.assign((size_t)P.nme, 0);
-    std::vector<double> xv((size_t)6 * MAXV, 0.), xl((size_t)3 * std::max(np, 1), 0.);
-    const int ne = nobs + 4 * nmobs;
+    cache_clear(P, C);
+    const int nobs = f->nobs;
+    std::vector<double> xv((size_t)6 * MAXV, 0.), xl((size_t)3 * std::max(P.np, 1), 0.);
+    const int ne = nobs + 4 * f->nmobs;
     bool stale;
     res->n_edges_mono = nobs;
     res->n_edges_marker = P.nme;
@@ -630,12 +306,9 @@ extern "C" int ref_lba(float* Tcw, const uint8_t* kf_fixed, int nkf, float* x3Dw
     res->stale_mask |= stale ? 1 : 0;
     auto depth = [&](int e) {
         double Xc[3];
-        map(X.pose[(size_t)obs_kf[e]], &X.pt[(size_t)P.e_pt[(size_t)e] * 3], Xc);
+        map(X.pose[(size_t)P.okf[e]], &X.pt[(size_t)P.e_pt[(size_t)e] * 3], Xc);
         return Xc[2];
     };
-    P.e_pt.assign((size_t)nobs, 0);
-    for (int pi = 0; pi < np; pi++)
-        for (int e = obs_offset[pi]; e < obs_offset[pi + 1]; e++) P.e_pt[(size_t)e] = pi;
     for (int e = 0; e < nobs; e++) {
         if (chi2_checks) chi2_checks[e] = C.e_chi2[(size_t)e];
         if (!(C.e_chi2[(size_t)e] <= 5.991) || !(depth(e) > 0.0)) {
@@ -658,123 +331,49 @@ extern "C" int ref_lba(float* Tcw, const uint8_t* kf_fixed, int nkf, float* x3Dw
         res->n_erase += erase[e];
     }
     for (int j = 0; j < P.nme && chi2_checks; j++) chi2_checks[ne + nobs + j] = C.m_chi2[(size_t)j];
-    for (int k = 0; k < nkf; k++)
-        if (!kf_fixed[k]) to_float(X.pose[(size_t)k], Tcw + 12 * k);
-    for (int m = 0; use_markers && m < nma; m++) to_float(X.pose[(size_t)(nkf + m)], Twm + 12 * m);
-    for (int i = 0; i < 3 * np; i++) x3Dw[i] = (float)X.pt[(size_t)i];
+    for (int k = 0; k < f->nkf; k++)
+        if (!f->kf_fixed[k]) to_float(X.pose[(size_t)k], f->Tcw + 12 * k);
+    for (int m = 0; f->use_markers && m < f->nma; m++) to_float(X.pose[(size_t)(f->nkf + m)], f->Twm + 12 * m);
+    for (int i = 0; i < 3 * f->np; i++) f->x3Dw[i] = (float)X.pt[(size_t)i];
     return 0;
 }
 
 // One linearisation (all edges, Huber) and the first trial, as orbfe_lba_inspect.  full_H (may be NULL): the whole system with lambda0
 // on its diagonal, (6 nv + 3 np)^2 row-major, poses first; b holds its right-hand side.
-extern "C" int ref_lba_inspect(const float* Tcw, const uint8_t* kf_fixed, int nkf, const float* x3Dw, int np, const int32_t* obs_offset,
-                               const int32_t* obs_kf, const float* obs_xy, const int32_t* obs_octave, int nobs, const float* K4,
-                               const float* inv_sigma2, int nlevels, const float* Twm, const float* marker_local, int nma,
-                               const int32_t* mobs_offset, const int32_t* mobs_kf, const float* mobs_corners, int nmobs, float marker_info,
-                               int use_markers, int order, int32_t* nv, double* b, double* Hpp, double* Hll, double* chi2, double* x,
-                               double* full_H)
+extern "C" int ref_lba_inspect(const Flat* f, int order, int32_t* nv, double* b, double* Hpp, double* Hll, double* chi2, double* x, double* full_H)
 {
-    (void)nlevels;
     Prob P;
     Est X, Xt;
-    if (!setup(P, X, Tcw, kf_fixed, nkf, x3Dw, np, obs_offset, obs_kf, obs_xy, obs_octave, nobs, K4, inv_sigma2, Twm, marker_local, nma,
-               mobs_offset, mobs_kf, mobs_corners, nmobs, marker_info, use_markers, order))
-        return -4;
+    if (!setup(P, X, *f, order)) return -4;
     Cache C;
-    C.e_chi2.assign((size_t)nobs, 0.); C.m_chi2.assign((size_t)P.nme, 0.); C.e_level.assign((size_t)nobs, 0); C.m_level.assign((size_t)P.nme, 0);
-    Lin L;
+    cache_clear(P, C);
+    LbaLin L;
     linearize(P, X, true, C, L);
     const double lambda = 1e-5 * L.maxdiag;
-    *nv = P.nv;
-    chi2[0] = L.chi;
-    chi2[1] = lambda;
-    std::memcpy(b, L.bp.data(), (size_t)P.nv * 48);
-    std::memcpy(b + 6 * P.nv, L.bl.data(), (size_t)np * 24);
-    std::memcpy(Hpp, L.Hpp.data(), (size_t)P.nv * 288);
-    std::memcpy(Hll, L.Hll.data(), (size_t)np * 48);
-    if (full_H) {
-        const int n = 6 * P.nv + 3 * np;
-        std::fill(full_H, full_H + (size_t)n * n, 0.);
-        auto at = [&](int r, int c) -> double& { return full_H[(size_t)r * n + c]; };
-        for (int v = 0; v < P.nv; v++)
-            for (int a = 0; a < 6; a++)
-                for (int c = 0; c < 6; c++) at(6 * v + a, 6 * v + c) = L.Hpp[(size_t)v * 36 + a * 6 + c] + (a == c ? lambda : 0.);
-        for (int pi = 0; pi < np; pi++) {
-            const double* H = &L.Hll[(size_t)pi * 6];
-            const int o = 6 * P.nv + 3 * pi, idx[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}};
-            for (int a = 0; a < 3; a++)
-                for (int c = 0; c < 3; c++) at(o + a, o + c) = H[idx[a][c]] + (a == c ? lambda : 0.);
-            for (int e = obs_offset[pi]; e < obs_offset[pi + 1]; e++) {
-                if (L.euse[(size_t)e] != 3) continue;
-                const int v = P.kf_free[(size_t)obs_kf[e]];
-                for (int a = 0; a < 6; a++)
-                    for (int c = 0; c < 3; c++) at(6 * v + a, o + c) = at(o + c, 6 * v + a) = L.eblk[(size_t)e * EB + 27 + a * 3 + c];
-            }
-        }
-        for (int j = 0; j < P.nme; j++) {
-            const int vc = P.kf_free[(size_t)mobs_kf[j >> 2]], vm = P.nv - (use_markers ? nma : 0) + P.mo_marker[(size_t)(j >> 2)];
-            if (vc < 0 || !L.muse[(size_t)j]) continue;
-            for (int a = 0; a < 6; a++)
-                for (int c = 0; c < 6; c++) {
-                    at(6 * vc + a, 6 * vm + c) += L.mblk[(size_t)j * MB + 54 + a * 6 + c];
-                    at(6 * vm + c, 6 * vc + a) += L.mblk[(size_t)j * MB + 54 + a * 6 + c];
-                }
-        }
-    }
-    std::vector<double> xv((size_t)6 * MAXV, 0.), xl((size_t)3 * std::max(np, 1), 0.);
+    inspect_out(P, L, lambda, nv, b, Hpp, Hll, chi2, full_H);
+    std::vector<double> xv((size_t)6 * MAXV, 0.), xl((size_t)3 * std::max(P.np, 1), 0.);
     double tempChi, sp;
     trial(P, C, L, lambda, true, X, Xt, xv, xl, tempChi, sp);
-    std::memcpy(x, xv.data(), (size_t)P.nv * 48);
-    std::memcpy(x + 6 * P.nv, xl.data(), (size_t)np * 24);
+    inspect_update(P, xv, xl, x);
     return 0;
 }
 
-// One EdgeSE3ProjectXYZ at exp(u) * Tcw and X: the error and g2o's analytic Jacobians (pose 2 x 6, point 2 x 3)
-extern "C" void ref_lba_mono_edge(const float* Tcw, const double* u, const double* X, const double* obs, const float* K4, double* err,
-                                  double* Jp, double* Jx)
-{
-    const Cam K{K4[0], K4[1], K4[2], K4[3]};
-    const SE3 T = mul(se3_exp(u), se3_from_float(Tcw));
-    double e[2], jp[2][6], jx[2][3];
-    mono_linearize(T, X, obs[0], obs[1], K, e, jp, jx);
-    std::memcpy(err, e, sizeof(e));
-    std::memcpy(Jp, jp, sizeof(jp));
-    std::memcpy(Jx, jx, sizeof(jx));
-}
-
-// One EdgeMarker: the error and g2o's numeric Jacobians on the camera and on the marker vertex
-extern "C" void ref_lba_marker_edge(const float* Tcw, const float* Twm, const double* p, const double* obs, const float* K4, double* err,
-                                    double* Jc, double* Jm)
-{
-    const Cam K{K4[0], K4[1], K4[2], K4[3]};
-    const SE3 Tc = se3_from_float(Tcw), Tm = se3_from_float(Twm);
-    double e[2], jc[2][6], jm[2][6];
-    marker_error(Tc, Tm, p, obs[0], obs[1], K, e);
-    marker_jacobian(Tc, Tm, true, p, obs[0], obs[1], K, jc);
-    marker_jacobian(Tc, Tm, false, p, obs[0], obs[1], K, jm);
-    std::memcpy(err, e, sizeof(e));
-    std::memcpy(Jc, jc, sizeof(jc));
-    std::memcpy(Jm, jm, sizeof(jm));
-}
-
 // The anchor to tests/pose_opt_ref.cpp: the points are held, so the problem is the motion-only one -- one optimize(maxit) with Huber
-// over the same edges, from the same poses.  Tcw is in / out; returns the LM iterations run.
-extern "C" int ref_lba_poses_only(float* Tcw, const uint8_t* kf_fixed, int nkf, const float* x3Dw, int np, const int32_t* obs_offset,
-                                  const int32_t* obs_kf, const float* obs_xy, const int32_t* obs_octave, int nobs, const float* K4,
-                                  const float* inv_sigma2, int maxit, int order)
+// over the same edges, from the same poses, without the markers.  f's Tcw is in / out; returns the LM iterations run.
+extern "C" int ref_lba_poses_only(const Flat* f, int maxit, int order)
 {
+    Flat q = *f;
+    q.nma = q.nmobs = q.use_markers = 0;
     Prob P;
     Est X;
     P.fix_points = true;
-    if (!setup(P, X, Tcw, kf_fixed, nkf, x3Dw, np, obs_offset, obs_kf, obs_xy, obs_octave, nobs, K4, inv_sigma2, nullptr, nullptr, 0, nullptr,
-               nullptr, nullptr, 0, 0.f, 0, order))
-        return -4;
+    if (!setup(P, X, q, order)) return -4;
     Cache C;
-    C.e_chi2.assign((size_t)nobs, 0.); C.e_level.assign((size_t)nobs, 0);
-    std::vector<double> xv((size_t)6 * MAXV, 0.), xl((size_t)3 * std::max(np, 1), 0.);
+    cache_clear(P, C);
+    std::vector<double> xv((size_t)6 * MAXV, 0.), xl((size_t)3 * std::max(P.np, 1), 0.);
     bool stale;
     const int it = optimize(P, C, X, true, maxit, xv, xl, stale);
-    for (int k = 0; k < nkf; k++)
-        if (!kf_fixed[k]) to_float(X.pose[(size_t)k], Tcw + 12 * k);
+    for (int k = 0; k < q.nkf; k++)
+        if (!q.kf_fixed[k]) to_float(X.pose[(size_t)k], q.Tcw + 12 * k);
     return it;
 }

@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE ONLY -- drives include/shims/Optimizer_localba_orbfe.cc the way LocalMapping does, on the mock map that
-// tests/lba_shim_map.py describes, against the mock headers of tests/mock_orbslam_lba/ (ahead of tests/mock_orbslam/), and dumps raw
+// tests/lba_shim_map.py describes, against the mock headers of tests/mock_orbslam/, and dumps raw
 // arrays for tests/test_lba_shim_cpu.py and tests/test_lba_shim_gpu.py.
 //   lba_shim_driver collect <in prefix> <out prefix>            the collect step alone (no library call): the lists and the flat arrays
 //   lba_shim_driver run <in prefix> <out prefix> <use> <stop>   Optimizer::LocalBundleAdjustment with Frame::mbUArucoIni = use and

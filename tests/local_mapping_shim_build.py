@@ -1,9 +1,8 @@
 """Builds the LocalMapping shim programs (test infrastructure), through ref_build.build_shim as tests/shim_build.py does for the other
-shims: include/shims/LocalMapping_orbfe.cc with its driver, and all eight shims in one program."""
+shims: include/shims/LocalMapping_orbfe.cc with its driver."""
 import numpy as np
 
 import ref_build
-import shim_build
 
 SHIM = "LocalMapping_orbfe.cc"
 
@@ -11,11 +10,6 @@ SHIM = "LocalMapping_orbfe.cc"
 def build(out_dir):
     """the shim with tests/local_mapping_shim_driver.cpp: the program's path in out_dir"""
     return ref_build.build_shim((SHIM,), "local_mapping_shim_driver.cpp", out_dir)
-
-
-def build_all(out_dir):
-    """the seven shims of shim_build.PROGRAMS["all"] and the LocalMapping shim in one program (tests/all_shims8_driver.cpp)"""
-    return ref_build.build_shim(tuple(shim_build.PROGRAMS["all"][0]) + (SHIM,), "all_shims8_driver.cpp", out_dir)
 
 
 def write_inputs(prefix, frames, K4, scale, sigma2):

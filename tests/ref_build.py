@@ -26,11 +26,13 @@ MOCK_DIRS = ("tests/mock_orbslam", "tests/mock_orbslam/aruco", "tests/mock_orbsl
 
 def build_shim(shim_ccs, driver_cpp, out_dir):
     """The sources shim_ccs of include/shims/, tests/<driver_cpp> and the mock Frame's static members as one program, against the one
-    mock tree tests/mock_orbslam/ and the built library; returns the program's path in out_dir."""
+    mock tree tests/mock_orbslam/ and the built library; returns the program's path in out_dir.  The only function that compiles a shim
+    program: tests/ is on the include path for the drivers that share tests/shim_driver_io.hpp, and -pthread serves the shims that
+    lock Map::mMutexMapUpdate."""
     inc = []
-    for d in MOCK_DIRS + ("include", "include/shims"):
+    for d in MOCK_DIRS + ("include", "include/shims", "tests"):
         inc += ["-I", os.path.join(ROOT, d)]
-    flags = ["g++", "-std=c++14", "-O1", "-Wall", "-Werror"]
+    flags = ["g++", "-std=c++14", "-O1", "-Wall", "-Werror", "-pthread"]
     objs = []
     for src in [os.path.join(ROOT, "include", "shims", cc) for cc in shim_ccs] + [os.path.join(HERE, "mock_orbslam", "Frame_statics.cc")]:
         objs.append(os.path.join(out_dir, os.path.splitext(os.path.basename(src))[0] + ".o"))

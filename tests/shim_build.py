@@ -11,7 +11,9 @@ PROGRAMS = {
     "sim3_opt": (("Optimizer_sim3_orbfe.cc",), "sim3_opt_shim_driver.cpp"),
     "kfdb": (("KeyFrameDatabase_orbfe.cc",), "kfdb_shim_driver.cpp"),
 }
-PROGRAMS["all"] = (tuple(cc for name in sorted(PROGRAMS) for cc in PROGRAMS[name][0]), "all_shims_driver.cpp")
+# the shims that have build modules of their own (tests/local_mapping_shim_build.py, essential_shim_build.py, lba_build.py, gba_build.py)
+OTHER_SHIMS = ("LocalMapping_orbfe.cc", "Optimizer_essential_orbfe.cc", "Optimizer_localba_orbfe.cc", "Optimizer_globalba_orbfe.cc")
+PROGRAMS["all"] = (tuple(cc for name in sorted(PROGRAMS) for cc in PROGRAMS[name][0]) + OTHER_SHIMS, "all_shims_driver.cpp")
 
 
 def build(name, out_dir):

@@ -66,7 +66,7 @@ def host():
         init = ref_build.build_shared("initializer_ref.cpp")
         init.ref_jacobi_svd.argtypes, init.ref_jacobi_svd.restype = [vp, i32, i32, i32, vp, vp], None
         lba = ref_build.build_shared("lba_ref.cpp")
-        lba.ref_lba_marker_edge.argtypes, lba.ref_lba_marker_edge.restype = [vp] * 8, None
+        lba.ref_ba_marker_edge.argtypes, lba.ref_ba_marker_edge.restype = [vp] * 8, None
         se3 = D._declare(D._declare(ref_build.build_shared("solver_units_host.cpp", prefix="solver_units_host_"), _SE3), _PASSES)
         _host = types.SimpleNamespace(se3=se3, eg=eg, init=init, lba=lba)
     return _host
@@ -230,7 +230,7 @@ def marker(device, Tcw, Twm, p, obs, cam4):
         K4 = cam4.astype(np.float32)
         assert np.array_equal(K4.astype(np.float64), cam4), "the restatement takes the camera as floats"
         for i in range(n):
-            host().lba.ref_lba_marker_edge(_p(Tcw[i]), _p(Twm[i]), _p(p[i]), _p(obs[i]), _p(K4), _p(out[i, :2]), _p(out[i, 2:14]), _p(out[i, 14:]))
+            host().lba.ref_ba_marker_edge(_p(Tcw[i]), _p(Twm[i]), _p(p[i]), _p(obs[i]), _p(K4), _p(out[i, :2]), _p(out[i, 2:14]), _p(out[i, 14:]))
     return out[:, :2], out[:, 2:14].reshape(n, 2, 6), out[:, 14:].reshape(n, 2, 6)
 
 

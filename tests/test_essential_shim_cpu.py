@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import essential_shim_build as B
+import shim_build
 
 
 @pytest.fixture(scope="module")
@@ -46,5 +47,5 @@ def test_point_references(collected):
 
 
 def test_all_shims_link_into_one_program(tmp_path):
-    exe = B.build_all9(str(tmp_path))
-    assert subprocess.check_output([exe], text=True).strip() == "ok: 9 shims in one program"
+    exe = shim_build.build("all", str(tmp_path))
+    assert subprocess.check_output([exe], text=True).strip() == "ok: 11 shims in one program"

@@ -1,4 +1,4 @@
-"""GPU: include/shims/Optimizer_localba_orbfe.cc, built with g++ against the mock headers of tests/mock_orbslam_lba/ and
+"""GPU: include/shims/Optimizer_localba_orbfe.cc, built with g++ against the mock headers of
 tests/mock_orbslam/, runs Optimizer::LocalBundleAdjustment on the hand-built map of tests/lba_shim_map.py and leaves in the map what
 the C ABI returns for the collected problem, bit for bit: erased observations, poses, points, marker poses."""
 import subprocess

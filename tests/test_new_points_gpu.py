@@ -408,9 +408,10 @@ def test_noise_free_points_come_back_at_their_true_positions():
 
 def test_shim_driver_equals_the_binding(tmp_path):
     """include/shims/LocalMapping_orbfe.cc on mock keyframes: the (idx1, idx2, x3D) triples per neighbour are the binding's, bit for
-    bit; the eight-shim program links and runs"""
+    bit; the program of all shims links and runs"""
     import subprocess
     import local_mapping_shim_build as lb
+    import shim_build
     frames = nc.chain_scene()["frames"]
     out, _ = orbfe.create_new_map_points(frames[0], frames[1:], nc.K4, nc.SCALE, nc.SIGMA2, nc.RATIO, False)
     lb.write_inputs(str(tmp_path / "in"), frames, nc.K4, nc.SCALE, nc.SIGMA2)
@@ -420,5 +421,5 @@ def test_shim_driver_equals_the_binding(tmp_path):
     assert sum(len(g[0]) for g in got) > 300
     for (i1, i2, x), o in zip(got, out):
         assert np.array_equal(i1, o["i1"]) and np.array_equal(i2, o["i2"]) and same_bytes(x, o["x3D"])
-    r = subprocess.run([lb.build_all(str(tmp_path))], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.startswith("ok: 8 shims"), r.stderr
+    r = subprocess.run([shim_build.build("all", str(tmp_path))], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.startswith("ok: 11 shims"), r.stderr

@@ -28,13 +28,13 @@ def test_shim_compiles_and_links_against_the_mock_headers(name, tmp_path):
 
 
 def test_all_shims_compile_and_link_into_one_program(tmp_path):
-    """the five .cc shims, the two header shims and every mock class header in one program (tests/all_shims_driver.cpp): one Frame,
+    """the eleven .cc shims, the two header shims and every mock class header in one program (tests/all_shims_driver.cpp): one Frame,
     KeyFrame, MapPoint and Optimizer declaration serves them all, and no symbol is defined twice.  The program opens no device."""
     _library()
     exe = shim_build.build("all", str(tmp_path))
     r = subprocess.run([exe], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
-    assert r.stdout.startswith("ok")
+    assert r.stdout.startswith("ok: 11 shims")
 
 
 def test_shims_compile_link_and_refuse_without_a_gpu(tmp_path):

@@ -354,7 +354,7 @@ def test_mono_edge_equals_the_plain_evaluation_and_the_true_derivative():
 
 def test_marker_edge_equals_the_restatement_and_the_true_derivative():
     """Both vertices.  The steps of 1e-9 take se3_exp's small branch, so no libm enters: kind 1 against the restatement's entry
-    (ref_lba_marker_edge), which is stronger than the kind-2 bound.  Kind 3: the numeric Jacobians against the derivative at 50
+    (ref_ba_marker_edge), which is stronger than the kind-2 bound.  Kind 3: the numeric Jacobians against the derivative at 50
     digits with the project's numeric-Jacobian tolerance, E the size of the projected values."""
     Tcw, Twm, p, obs = S.marker_inputs()
     err, Jc, Jm = B.marker(True, Tcw, Twm, p, obs, S.CAM)
