@@ -8,84 +8,32 @@ import os
 
 import numpy as np
 
+from . import header
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ORBFE_LIB", os.path.join(_HERE, "liborbfe.so"))
 
-KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
-                     ("octave", "<i4"), ("class_id", "<i4")])
-MARKER_DTYPE = np.dtype([("id", "<i4"), ("corners", "<f4", (4, 2))])
-POSE_DTYPE = np.dtype([("rvec", "<f4", 3), ("tvec", "<f4", 3), ("rvec2", "<f4", 3), ("tvec2", "<f4", 3), ("err", "<f4", 2)])
+KP_DTYPE = header.dtype("orbfe_keypoint")
+MARKER_DTYPE = header.dtype("orbfe_marker")
+POSE_DTYPE = header.dtype("orbfe_marker_pose")
 assert KP_DTYPE.itemsize == 28 and MARKER_DTYPE.itemsize == 36
 
-# every symbol include/orbfe.h declares (tests/test_abi.py checks the header against this list and the .so)
-SYMBOLS = [
-    "orbfe_last_error", "orbfe_version", "orbfe_device_count",
-    "orbfe_extractor_create", "orbfe_extractor_destroy", "orbfe_extractor_get_levels",
-    "orbfe_extractor_get_scale_factor", "orbfe_extractor_get_scale_factors",
-    "orbfe_extractor_get_inverse_scale_factors", "orbfe_extractor_get_scale_sigma_squares",
-    "orbfe_extractor_get_inverse_scale_sigma_squares", "orbfe_extractor_get_features_per_level",
-    "orbfe_extractor_max_keypoints", "orbfe_extract", "orbfe_extract_batch", "orbfe_extract_batch_device",
-    "orbfe_extractor_batch_status", "orbfe_search_for_initialization_batch_status", "orbfe_extractor_set_gaussian_taps",
-    "orbfe_extractor_debug_level_size", "orbfe_extractor_debug_level_image",
-    "orbfe_extractor_debug_level_keypoints", "orbfe_extractor_debug_kernel_times", "orbfe_extractor_debug_control", "orbfe_extractor_set_aux_stream", "orbfe_extractor_follow", "orbfe_extractor_stage_wait", "orbfe_extractor_pair_detector",
-    "orbfe_debug_control", "orbfe_hamming", "orbfe_three_maxima", "orbfe_epipolar_distance_ok", "orbfe_knn2", "orbfe_knn2_csr", "orbfe_knn2_batch_device", "orbfe_search_for_initialization",
-    "orbfe_search_for_initialization_batch_device", "orbfe_search_by_projection",
-    "orbfe_undistort_points", "orbfe_undistort_keypoints_batch_device", "orbfe_compute_image_bounds",
-    "orbfe_aruco_create", "orbfe_aruco_destroy", "orbfe_aruco_set_dictionary", "orbfe_aruco_max_markers",
-    "orbfe_aruco_detect", "orbfe_aruco_detect_batch", "orbfe_aruco_detect_batch_device", "orbfe_aruco_debug_image",
-    "orbfe_aruco_debug_kernel_times", "orbfe_aruco_debug_control", "orbfe_aruco_debug_contour_retries", "orbfe_aruco_set_aux_stream",
-    "orbfe_aruco_batch_status", "orbfe_aruco_set_big_frames", "orbfe_aruco_set_error_correction_rate",
-    "orbfe_aruco_set_detection_mode", "orbfe_aruco_set_corner_refinement", "orbfe_aruco_marker_contour", "orbfe_aruco_marker_contours",
-    "orbfe_camera_resize", "orbfe_marker_poses", "orbfe_marker_poses_batch_device", "orbfe_aruco_detect_poses",
-    "orbfe_aruco_detect_bgr", "orbfe_aruco_detect_poses_bgr", "orbfe_aruco_get_state", "orbfe_aruco_set_gray_conversion", "orbfe_aruco_set_enclosed_markers", "orbfe_aruco_set_tracking", "orbfe_aruco_last_tracked", "orbfe_corner_subpix",
-    "orbfe_vocabulary_load_text", "orbfe_vocabulary_create", "orbfe_vocabulary_destroy", "orbfe_vocabulary_info",
-    "orbfe_vocabulary_transform", "orbfe_vocabulary_transform_batch_device",
-    "orbfe_search_by_bow", "orbfe_search_by_bow_batch_device",
-    "orbfe_search_for_triangulation", "orbfe_search_for_triangulation_batch_device",
-    "orbfe_distinctive_descriptors", "orbfe_distinctive_descriptors_device", "orbfe_search_by_projection_batch_device",
-    "orbfe_search_by_projection_batch_status", "orbfe_release_stream_scratch", "orbfe_search_by_projection_last_frame", "orbfe_search_by_projection_best", "orbfe_search_by_projection_keyframe", "orbfe_fuse_search", "orbfe_fuse_search_batch_device", "orbfe_project_map_points", "orbfe_search_by_sim3", "orbfe_search_by_projection_sim3",
-    "orbfe_keyframe_features_pack", "orbfe_keyframe_features_unpack", "orbfe_keyframe_features_pack_device",
-    "orbfe_keyframe_features_unpack_device",
-    # the batched-video mode (csrc/pipeline.hip; ctypes prototypes in pipeline.py)
-    "orbfe_pipeline_config_default", "orbfe_pipeline_create", "orbfe_pipeline_destroy", "orbfe_pipeline_layout", "orbfe_pipeline_step",
-    "orbfe_pipeline_flush", "orbfe_pipeline_synchronize", "orbfe_pipeline_input_done", "orbfe_pipeline_status", "orbfe_pipeline_set_big_frames",
-    "orbfe_pipeline_records", "orbfe_pipeline_matches", "orbfe_pipeline_reset_stream", "orbfe_pipeline_extractor", "orbfe_pipeline_detector",
-    "orbfe_pipeline_engine_sets", "orbfe_pipeline_enable_timing", "orbfe_pipeline_timing_us", "orbfe_pipeline_env_defaults",
-    "orbfe_pipeline_comm_unique_id", "orbfe_pipeline_comm_init", "orbfe_pipeline_set_comm", "orbfe_pipeline_gathered",
-    "orbfe_pipeline_host_copy_us", "orbfe_pipeline_gathered_set", "orbfe_pipeline_gathered_wait", "orbfe_pipeline_gathered_release", "orbfe_pipeline_gathered_batch", "orbfe_pipeline_copy_stream_priority", "orbfe_pipeline_gather_plan",
-    "orbfe_pipeline_step_host", "orbfe_pipeline_host_records", "orbfe_host_alloc", "orbfe_host_free",
-    "orbfe_device_alloc", "orbfe_device_free", "orbfe_device_upload_rows", "orbfe_device_download",
-    # the monocular initializer (csrc/initializer.hip)
-    "orbfe_initialize", "orbfe_initialize_batch_device", "orbfe_initialize_check_poses", "orbfe_initialize_inspect",
-    # motion-only pose optimization (csrc/pose_optimizer.hip)
-    "orbfe_pose_optimization", "orbfe_pose_optimization_batch_device", "orbfe_pose_gather_device",
-    # the Sim3 RANSAC of loop closing (csrc/sim3_solver.hip)
-    "orbfe_sim3_solve", "orbfe_sim3_solve_batch_device", "orbfe_sim3_inspect",
-    # the Sim3 refinement of loop closing (csrc/sim3_optimizer.hip)
-    "orbfe_optimize_sim3", "orbfe_optimize_sim3_batch_device",
-    # the candidate queries of KeyFrameDatabase and DBoW2's L1 score (csrc/keyframe_db.hip)
-    "orbfe_detect_candidates", "orbfe_detect_candidates_batch_device", "orbfe_bow_min_score_batch_device",
-    "orbfe_bow_score", "orbfe_bow_score_batch_device",
-    # the geometry of LocalMapping::CreateNewMapPoints (csrc/new_map_points.hip)
-    "orbfe_new_points_prepare_batch_device", "orbfe_triangulate_matches_batch_device", "orbfe_create_new_map_points_device",
-    "orbfe_create_new_map_points", "orbfe_new_points_inspect",
-    # LocalBundleAdjustment of local mapping (csrc/local_ba.hip)
-    "orbfe_lba_scratch_bytes", "orbfe_local_bundle_adjustment", "orbfe_local_bundle_adjustment_device", "orbfe_lba_inspect",
-    # OptimizeEssentialGraph of loop closing (csrc/essential_graph.hip)
-    "orbfe_essential_graph_scratch_bytes", "orbfe_optimize_essential_graph", "orbfe_optimize_essential_graph_device",
-    "orbfe_essential_graph_inspect",
-    # GlobalBundleAdjustment: the map-wide BA of the initial map and of loop closing (csrc/global_ba.hip)
-    "orbfe_gba_scratch_bytes", "orbfe_global_bundle_adjustment", "orbfe_global_bundle_adjustment_device", "orbfe_gba_inspect",
-]
+# every function include/orbfe.h declares (tests/test_abi_cpu.py checks them against what the .so exports)
+SYMBOLS = list(header.functions)
 
 _lib = None
 
 
+def _defines(*names):
+    return [header.defines[n] for n in names]
+
+
 # return codes of include/orbfe.h
-ORBFE_OK, ORBFE_ERR_INVALID, ORBFE_ERR_NO_DEVICE, ORBFE_ERR_HIP, ORBFE_ERR_CAPACITY, ORBFE_ERR_DICT = 0, -1, -2, -3, -4, -5
+ORBFE_OK, ORBFE_ERR_INVALID, ORBFE_ERR_NO_DEVICE, ORBFE_ERR_HIP, ORBFE_ERR_CAPACITY, ORBFE_ERR_DICT = _defines(
+    "OK", "ERR_INVALID", "ERR_NO_DEVICE", "ERR_HIP", "ERR_CAPACITY", "ERR_DICT")
 # ORBFE_ARUCO_FLAG_TRUNCATED: a frame of a device batch had more markers than the caller's capacity (MarkerDetector.batch_status,
 # FrontEndPipeline.status); every other flag bit is an internal capacity of the detector
-ARUCO_FLAG_TRUNCATED = 128
+ARUCO_FLAG_TRUNCATED = header.defines["ARUCO_FLAG_TRUNCATED"]
 
 
 class OrbfeError(RuntimeError):
@@ -101,171 +49,10 @@ def load():
         raise OrbfeError("%s not found: build it with __graft_entry__.build() (hipcc --offload-arch=gfx950)"
                          % LIB_PATH)
     L = C.CDLL(LIB_PATH)
-    vp, i32, f32, sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
-    L.orbfe_last_error.restype = C.c_char_p
-    L.orbfe_version.restype = C.c_char_p
-    L.orbfe_extractor_create.restype = vp
-    L.orbfe_extractor_create.argtypes = [i32, f32, i32, i32, i32, i32]
-    L.orbfe_extractor_destroy.argtypes = [vp]
-    L.orbfe_extractor_get_levels.argtypes = [vp]
-    L.orbfe_extractor_get_scale_factor.argtypes = [vp]
-    L.orbfe_extractor_get_scale_factor.restype = f32
-    for nm in ("scale_factors", "inverse_scale_factors", "scale_sigma_squares", "inverse_scale_sigma_squares",
-               "features_per_level"):
-        getattr(L, "orbfe_extractor_get_" + nm).argtypes = [vp, vp]
-    L.orbfe_extractor_max_keypoints.argtypes = [vp]
-    L.orbfe_extract.argtypes = [vp, vp, i32, i32, sz, vp, vp, i32, vp]
-    L.orbfe_extract_batch.argtypes = [vp, vp, i32, sz, i32, i32, sz, vp, vp, i32, vp]
-    L.orbfe_extract_batch_device.argtypes = [vp, vp, i32, sz, i32, i32, sz, vp, vp, i32, vp, vp]
-    L.orbfe_extractor_batch_status.argtypes = [vp, vp]
-    L.orbfe_extractor_set_gaussian_taps.argtypes = [vp, i32]
-    L.orbfe_extractor_debug_level_size.argtypes = [vp, i32, vp, vp]
-    L.orbfe_extractor_debug_level_image.argtypes = [vp, i32, i32, i32, vp]
-    L.orbfe_extractor_debug_level_keypoints.argtypes = [vp, i32, i32, i32, vp, i32, vp]
-    L.orbfe_extractor_debug_kernel_times.argtypes = [vp, vp, i32]
-    L.orbfe_extractor_debug_control.argtypes = [vp, C.c_char_p, i32]
-    L.orbfe_extractor_follow.argtypes = [vp, vp, i32]
-    L.orbfe_extractor_stage_wait.argtypes = [vp, i32, vp]
-    L.orbfe_extractor_pair_detector.argtypes = [vp, vp]
-    L.orbfe_extractor_set_aux_stream.argtypes = [vp, vp]
-    if hasattr(L, "orbfe_knn2"):
-        L.orbfe_debug_control.argtypes = [C.c_char_p, i32]
-        L.orbfe_search_by_projection.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, i32, i32, C.c_float] + [vp] * 7 + [i32]
-        L.orbfe_hamming.argtypes = [vp, vp]
-        L.orbfe_search_by_projection_last_frame.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, f32,
-                                                            i32, i32, vp, vp, i32]
-        L.orbfe_fuse_search.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, f32, f32, C.c_double,
-                                        vp, vp, i32]
-        L.orbfe_search_by_sim3.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, vp] + [vp] * 10 + [vp] * 6 + [i32, f32, f32, i32, vp, vp, i32]
-        L.orbfe_search_by_projection_sim3.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, f32, i32,
-                                                      vp, vp, i32]
-        L.orbfe_project_map_points.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, vp, i32, vp, i32, f32, f32, i32, i32, vp, i32]
-        L.orbfe_search_by_projection_keyframe.argtypes = [vp, vp, i32, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, f32,
-                                                          i32, i32, vp, vp, i32]
-        L.orbfe_search_by_projection_best.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, i32, i32, f32, vp, vp, i32]
-        L.orbfe_search_by_projection_batch_device.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, f32, f32, i32] + [vp] * 9
-        L.orbfe_search_by_projection_batch_status.argtypes = [vp, vp]
-        L.orbfe_fuse_search_batch_device.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, i32, f32, f32,
-                                                     C.c_double, vp, vp, vp]
-        L.orbfe_distinctive_descriptors.argtypes = [vp, vp, i32, vp, vp, i32]
-        L.orbfe_distinctive_descriptors_device.argtypes = [vp, vp, i32, vp, vp, vp]
-        L.orbfe_undistort_points.argtypes = [vp, i32, vp, vp, i32, vp, i32]
-        L.orbfe_undistort_keypoints_batch_device.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp]
-        L.orbfe_compute_image_bounds.argtypes = [i32, i32, vp, vp, i32, vp, i32]
-        L.orbfe_knn2.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp, i32]
-        L.orbfe_knn2_csr.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, vp, vp, i32]
-        L.orbfe_knn2_batch_device.argtypes = [vp, vp, sz, i32, vp, vp, sz, i32, i32, i32, vp, vp, vp, vp]
-        L.orbfe_search_for_initialization.argtypes = [vp, vp, i32, vp, vp, i32, i32, i32, vp, vp, vp, i32, f32, i32, vp,
-                                                      i32]
-        L.orbfe_search_for_initialization_batch_device.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, i32, f32, i32, vp,
-                                                                   vp, vp]
-        L.orbfe_search_for_initialization_batch_status.argtypes = [vp, vp]
-    if hasattr(L, "orbfe_aruco_create"):
-        L.orbfe_aruco_create.restype = vp
-        L.orbfe_aruco_create.argtypes = [C.c_char_p, i32]
-        L.orbfe_aruco_destroy.argtypes = [vp]
-        L.orbfe_aruco_set_dictionary.argtypes = [vp, C.c_char_p]
-        L.orbfe_aruco_max_markers.argtypes = [vp]
-        L.orbfe_aruco_detect.argtypes = [vp, vp, i32, i32, sz, vp, i32, vp]
-        L.orbfe_aruco_detect_poses.argtypes = [vp, vp, i32, i32, sz, vp, vp, i32, vp, f32, vp, vp, i32]
-        L.orbfe_aruco_detect_batch.argtypes = [vp, vp, i32, sz, i32, i32, sz, vp, i32, vp]
-        L.orbfe_aruco_detect_batch_device.argtypes = [vp, vp, i32, sz, i32, i32, sz, vp, i32, vp, vp]
-        L.orbfe_aruco_debug_image.argtypes = [vp, i32, i32, vp]
-        L.orbfe_aruco_debug_kernel_times.argtypes = [vp, vp, i32]
-        L.orbfe_aruco_debug_control.argtypes = [vp, C.c_char_p, i32]
-        L.orbfe_aruco_debug_contour_retries.argtypes = [vp]
-        L.orbfe_aruco_set_aux_stream.argtypes = [vp, vp]
-        L.orbfe_aruco_batch_status.argtypes = [vp, vp, vp]
-        L.orbfe_aruco_set_big_frames.argtypes = [vp, i32]
-        L.orbfe_aruco_set_error_correction_rate.argtypes = [vp, f32]
-        L.orbfe_aruco_set_detection_mode.argtypes = [vp, i32, f32]
-        L.orbfe_aruco_set_corner_refinement.argtypes = [vp, i32]
-        L.orbfe_aruco_detect_bgr.argtypes = [vp, vp, i32, i32, sz, vp, i32, vp]
-        L.orbfe_aruco_detect_poses_bgr.argtypes = [vp, vp, i32, i32, sz, vp, vp, i32, vp, f32, vp, vp, i32]
-        L.orbfe_aruco_get_state.argtypes = [vp, vp, vp, vp, vp, vp]
-        L.orbfe_aruco_set_gray_conversion.argtypes = [vp, i32]
-        L.orbfe_aruco_set_enclosed_markers.argtypes = [vp, i32]
-        L.orbfe_aruco_set_tracking.argtypes = [vp, i32]
-        L.orbfe_aruco_last_tracked.argtypes = [vp]
-        L.orbfe_corner_subpix.argtypes = [vp, i32, i32, sz, vp, i32, i32, i32, C.c_double, i32]
-        L.orbfe_aruco_marker_contour.argtypes = [vp, i32, i32, vp, i32, vp]
-        L.orbfe_aruco_marker_contours.argtypes = [vp, i32, i32, vp, i32, vp]
-        L.orbfe_camera_resize.argtypes = [vp, i32, i32, i32, i32, vp]
-    if hasattr(L, "orbfe_vocabulary_create"):
-        L.orbfe_vocabulary_load_text.restype = vp
-        L.orbfe_vocabulary_load_text.argtypes = [C.c_char_p, i32]
-        L.orbfe_vocabulary_create.restype = vp
-        L.orbfe_vocabulary_create.argtypes = [i32, i32, i32, i32, i32, vp, vp, vp, vp, i32]
-        L.orbfe_vocabulary_destroy.restype = None
-        L.orbfe_vocabulary_destroy.argtypes = [vp]
-        L.orbfe_vocabulary_info.argtypes = [vp, vp]
-        L.orbfe_vocabulary_transform.argtypes = [vp, vp, i32, i32] + [vp] * 10
-        L.orbfe_vocabulary_transform_batch_device.argtypes = [vp, vp, vp, i32, i32, i32] + [vp] * 11
-        L.orbfe_keyframe_features_pack.argtypes = [vp, vp, vp, i32, vp, i32]
-        L.orbfe_keyframe_features_unpack.argtypes = [vp, i32, vp, vp, vp, i32]
-        L.orbfe_keyframe_features_unpack_device.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp, vp]
-        L.orbfe_keyframe_features_pack_device.argtypes = [vp, vp, vp, vp, vp, i32, i32, vp, vp]
-        side = [vp, vp, vp, i32, vp, vp, vp, i32]
-        L.orbfe_search_by_bow.argtypes = side + side + [f32, i32, i32, f32, vp, vp, vp, i32]
-        L.orbfe_search_for_triangulation.argtypes = side + side + [vp, f32, f32, vp, vp, i32, i32, vp, vp, i32]
-        L.orbfe_search_for_triangulation_batch_device.argtypes = [vp] * 8 + [i32, vp, vp, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
-        L.orbfe_search_by_bow_batch_device.argtypes = [vp] * 8 + [i32, vp, vp, i32, i32, f32, i32, i32, f32, vp, vp, vp, vp]
-        L.orbfe_marker_poses.argtypes = [vp, i32, f32, vp, vp, i32, vp, i32]
-        L.orbfe_marker_poses_batch_device.argtypes = [vp, vp, i32, i32, f32, vp, vp, i32, vp, vp]
-    if hasattr(L, "orbfe_sim3_solve"):
-        side = [vp, i32, vp, vp, vp, vp]
-        common = side + side + [vp, vp, i32, i32, C.c_double, i32, i32, i32, i32, i32, vp, vp, vp]
-        L.orbfe_sim3_solve.argtypes = common + [i32]
-        L.orbfe_sim3_inspect.argtypes = common + [vp] * 11 + [i32]
-        L.orbfe_sim3_solve_batch_device.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, i32, C.c_double, i32, i32, vp, vp, vp, vp]
-    if hasattr(L, "orbfe_optimize_sim3"):
-        side = [vp, i32, vp, vp, vp, vp]
-        L.orbfe_optimize_sim3.argtypes = side + side + [vp, vp, i32, f32, vp, vp, f32, i32, vp, vp, i32]
-        L.orbfe_optimize_sim3_batch_device.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, i32, vp, sz, f32, i32, vp, vp, vp]
-    if hasattr(L, "orbfe_detect_candidates"):
-        L.orbfe_detect_candidates.argtypes = [i32, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, f32, vp, vp, vp, vp, i32]
-        L.orbfe_detect_candidates_batch_device.argtypes = [i32, i32, vp, vp, vp, i32, vp, vp, i32, vp, i32] + [vp] * 10
-        L.orbfe_bow_min_score_batch_device.argtypes = [i32, vp, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp]
-        L.orbfe_bow_score.argtypes = [i32, vp, vp, vp, i32, vp, vp, i32, vp, i32]
-        L.orbfe_bow_score_batch_device.argtypes = [i32, vp, vp, vp, i32, vp, vp, i32, vp, vp]
-    if hasattr(L, "orbfe_create_new_map_points"):
-        L.orbfe_new_points_prepare_batch_device.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
-        L.orbfe_triangulate_matches_batch_device.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, i32, f32] + [vp] * 6
-        L.orbfe_create_new_map_points_device.argtypes = [vp] * 7 + [i32] + [vp] * 6 + [i32, vp, vp, vp, i32, f32, i32] + [vp] * 12
-        side = [vp, vp, i32, vp, vp, vp, i32, vp, vp, vp]
-        L.orbfe_create_new_map_points.argtypes = side + side + [vp, vp, vp, i32, f32, i32] + [vp] * 9 + [i32]
-        L.orbfe_new_points_inspect.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, f32] + [vp] * 6 + [i32]
-    if hasattr(L, "orbfe_local_bundle_adjustment"):
-        L.orbfe_lba_scratch_bytes.argtypes = [i32] * 5
-        L.orbfe_lba_scratch_bytes.restype = sz
-        prob = [vp, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, i32, f32, i32]
-        L.orbfe_local_bundle_adjustment.argtypes = prob + [vp, vp, vp, i32]
-        L.orbfe_lba_inspect.argtypes = prob + [vp] * 6 + [i32]
-        egp = [vp, vp, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, i32]   # keyframes, the two similarity lists, edges
-        L.orbfe_essential_graph_scratch_bytes.argtypes = [i32] * 4
-        L.orbfe_essential_graph_scratch_bytes.restype = sz
-        L.orbfe_optimize_essential_graph.argtypes = egp + [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, i32]
-        L.orbfe_optimize_essential_graph_device.argtypes = egp + [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]
-        L.orbfe_essential_graph_inspect.argtypes = egp + [i32, i32] + [vp] * 8 + [i32]
-        L.orbfe_local_bundle_adjustment_device.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp,
-                                                           i32, f32, i32, vp, vp, vp, vp, sz, vp]
-    if hasattr(L, "orbfe_global_bundle_adjustment"):
-        prob = [vp, vp, i32, vp, i32, vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, i32, f32, i32]
-        L.orbfe_gba_scratch_bytes.argtypes = [i32] * 6
-        L.orbfe_gba_scratch_bytes.restype = sz
-        L.orbfe_global_bundle_adjustment.argtypes = prob + [i32, i32, vp, i32, vp, i32]
-        L.orbfe_gba_inspect.argtypes = prob + [i32, i32] + [vp] * 7 + [i32]
-        L.orbfe_global_bundle_adjustment_device.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp,
-                                                            i32, f32, i32, i32, i32, vp, i32, vp, vp, sz, vp]
-    if hasattr(L, "orbfe_initialize"):
-        L.orbfe_initialize.argtypes = [vp, i32, vp, i32, vp, vp, f32, i32, vp, vp, vp, vp, i32]
-        L.orbfe_initialize_inspect.argtypes = [vp, i32, vp, i32, vp, vp, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32]
-        L.orbfe_initialize_check_poses.argtypes = [vp, i32, vp, i32, vp, vp, f32, vp, i32, vp, vp, vp, i32]
-        L.orbfe_initialize_batch_device.argtypes = [vp, vp, i32, i32, vp, vp, f32, i32, vp, vp, vp, vp, vp]
-    if hasattr(L, "orbfe_pose_optimization"):
-        L.orbfe_pose_optimization.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, i32, f32, vp, vp, vp, vp, vp, i32]
-        L.orbfe_pose_optimization_batch_device.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, f32, vp, vp, vp, vp, vp, vp]
-        L.orbfe_pose_gather_device.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp, vp, vp]
+    for name, (restype, argtypes) in header.functions.items():     # a partial library (a test build of some engines) is accepted
+        if hasattr(L, name):
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -499,7 +286,7 @@ def knn2(Q, T, init=256, device=0):
     return bi, bd, sd
 
 
-WINDOW_QUERY_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("r", "<f4"), ("min_level", "<i4"), ("max_level", "<i4")])
+WINDOW_QUERY_DTYPE = header.dtype("orbfe_window_query")
 
 
 def search_by_projection(kps, desc, cols, rows, queries, qdesc, taken=None, mode=0, th_high=100, nnratio=0.8, device=0,
@@ -724,9 +511,7 @@ class ORBmatcher:
 
 
 # ------------------------------------------------------------------------------------- Initializer ----
-INIT_RESULT_DTYPE = np.dtype([("initialized", "<i4"), ("model", "<i4"), ("SH", "<f4"), ("SF", "<f4"), ("RH", "<f4"),
-                              ("best_h", "<i4"), ("best_f", "<i4"), ("H21", "<f4", 9), ("F21", "<f4", 9), ("R21", "<f4", 9),
-                              ("t21", "<f4", 3), ("n_good", "<i4"), ("parallax", "<f4")])
+INIT_RESULT_DTYPE = header.dtype("orbfe_init_result")
 assert INIT_RESULT_DTYPE.itemsize == 156
 
 _libc_rand = None
@@ -830,9 +615,7 @@ def initialize_batch_device(d_kps_ptr, d_n_ptr, capacity, npairs, d_matches12_pt
 
 
 # ------------------------------------------------------------------------------- Sim3 RANSAC (loop closing) ----
-SIM3_RESULT_DTYPE = np.dtype([("n", "<i4"), ("max_iterations", "<i4"), ("no_more", "<i4"), ("found", "<i4"), ("n_inliers", "<i4"),
-                              ("best", "<i4"), ("best_inliers", "<i4"), ("s12", "<f4"), ("R12", "<f4", 9), ("t12", "<f4", 3),
-                              ("T12", "<f4", 16), ("status", "<i4")])
+SIM3_RESULT_DTYPE = header.dtype("orbfe_sim3_result")
 assert SIM3_RESULT_DTYPE.itemsize == 148
 
 
@@ -948,9 +731,7 @@ def sim3_solve_batch_device(d_kps_ptr, d_n_ptr, capacity, d_x3Dw_ptr, d_valid_pt
 
 
 # ------------------------------------------------------------------------------- Sim3 refinement (loop closing) ----
-SIM3_OPT_RESULT_DTYPE = np.dtype([("n_inliers", "<i4"), ("n_correspondences", "<i4"), ("n_bad", "<i4"), ("more_iterations", "<i4"),
-                                  ("iterations", "<i4", 2), ("stale_mask", "<i4"), ("status", "<i4"), ("s12", "<f8"), ("q12", "<f8", 4),
-                                  ("t12", "<f8", 3)])
+SIM3_OPT_RESULT_DTYPE = header.dtype("orbfe_sim3_opt_result")
 assert SIM3_OPT_RESULT_DTYPE.itemsize == 96
 SIM3_RESULT_S12_OFFSET = SIM3_RESULT_DTYPE.fields["s12"][1]   # s12, R12, t12: 13 contiguous floats of orbfe_sim3_result
 
@@ -999,11 +780,10 @@ def optimize_sim3_batch_device(d_kps_ptr, d_n_ptr, capacity, d_x3Dw_ptr, d_valid
 
 
 # ------------------------------------------------------------------------------- KeyFrameDatabase queries ----
-KFDB_LOOP, KFDB_RELOC, KFDB_NEIGHBOURS, KFDB_MAX_KEYFRAMES, KFDB_MAX_WORDS = 0, 1, 10, 8192, 4096
+KFDB_LOOP, KFDB_RELOC, KFDB_NEIGHBOURS, KFDB_MAX_KEYFRAMES, KFDB_MAX_WORDS = _defines(
+    "KFDB_LOOP", "KFDB_RELOC", "KFDB_NEIGHBOURS", "KFDB_MAX_KEYFRAMES", "KFDB_MAX_WORDS")
 L1_NORM = 0   # DBoW2::ScoringType
-KFDB_RESULT_DTYPE = np.dtype([("n_sharing", "<i4"), ("max_common_words", "<i4"), ("min_common_words", "<i4"), ("n_scored", "<i4"),
-                              ("n_kept", "<i4"), ("n_candidates", "<i4"), ("best_acc_score", "<f4"), ("min_score_to_retain", "<f4"),
-                              ("status", "<i4")])
+KFDB_RESULT_DTYPE = header.dtype("orbfe_kfdb_result")
 assert KFDB_RESULT_DTYPE.itemsize == 36
 
 
@@ -1076,9 +856,8 @@ def bow_score_batch_device(d_bow_word_ptr, d_bow_value_ptr, d_nbow_ptr, capacity
 
 
 # ------------------------------------------------------------------------------- pose optimization ----
-POSE_MARKER_DTYPE = np.dtype([("corners", "<f4", 8), ("Twm", "<f4", 12), ("local", "<f4", 12)])
-POSE_RESULT_DTYPE = np.dtype([("n_good", "<i4"), ("n_initial", "<i4"), ("n_marker_edges", "<i4"), ("rounds", "<i4"),
-                              ("n_bad", "<i4", 4), ("iterations", "<i4", 4), ("stale_mask", "<i4"), ("status", "<i4")])
+POSE_MARKER_DTYPE = header.dtype("orbfe_pose_marker")
+POSE_RESULT_DTYPE = header.dtype("orbfe_pose_result")
 assert POSE_MARKER_DTYPE.itemsize == 128 and POSE_RESULT_DTYPE.itemsize == 56
 
 
@@ -1179,7 +958,7 @@ def search_by_bow(kps1, desc1, fv1, kps2, desc2, fv2, valid1=None, valid2=None, 
     return nm.value, m12, m21
 
 
-KF_FEATURE_BYTES = 68
+KF_FEATURE_BYTES = header.defines["KF_FEATURE_BYTES"]
 
 
 def keyframe_features_pack(kps, desc, mp_index=None, device=0):
@@ -1223,9 +1002,9 @@ def search_for_triangulation(kps1, desc1, fv1, kps2, desc2, fv2, F12, epipole, s
     return nm.value, m12
 
 
-NEW_POINTS_PAIR_DTYPE = np.dtype([("baseline", np.float32), ("median_depth", np.float32), ("n_depths", np.int32), ("skipped", np.int32)])
-NEW_POINTS_RESULT_DTYPE = np.dtype([("n_matches", np.int32), ("n_new", np.int32), ("status", np.int32)])
-NMP_CREATED = 1
+NEW_POINTS_PAIR_DTYPE = header.dtype("orbfe_new_points_pair")
+NEW_POINTS_RESULT_DTYPE = header.dtype("orbfe_new_points_result")
+NMP_CREATED = header.defines["NMP_CREATED"]
 
 
 def _tcw12(T):
@@ -1607,9 +1386,8 @@ class MarkerDetector:
 
 
 # ------------------------------------------------------------------------------- LocalBundleAdjustment (local mapping) ----
-LBA_MAX_FREE_POSES, LBA_MAX_OBSERVATIONS, LBA_STOPPED = 64, 256, 1
-LBA_RESULT_DTYPE = np.dtype([("n_edges_mono", "<i4"), ("n_edges_marker", "<i4"), ("n_level1", "<i4", 2), ("n_erase", "<i4"),
-                             ("iterations", "<i4", 2), ("stale_mask", "<i4"), ("status", "<i4")])
+LBA_MAX_FREE_POSES, LBA_MAX_OBSERVATIONS, LBA_STOPPED = _defines("LBA_MAX_FREE_POSES", "LBA_MAX_OBSERVATIONS", "LBA_STOPPED")
+LBA_RESULT_DTYPE = header.dtype("orbfe_lba_result")
 assert LBA_RESULT_DTYPE.itemsize == 36
 
 
@@ -1703,9 +1481,8 @@ def lba_inspect(pb, device=0):
 
 
 # ------------------------------------------------------------------------------- OptimizeEssentialGraph (loop closing) ----
-EG_MAX_KEYFRAMES, EG_MAX_EDGES = 4096, 65536
-EG_RESULT_DTYPE = np.dtype([("status", "<i4"), ("iterations", "<i4"), ("trials", "<i4"), ("pad", "<i4"), ("chi2_first", "<f8"),
-                            ("chi2_last", "<f8"), ("lambda_last", "<f8")])
+EG_MAX_KEYFRAMES, EG_MAX_EDGES = _defines("EG_MAX_KEYFRAMES", "EG_MAX_EDGES")
+EG_RESULT_DTYPE = header.dtype("orbfe_eg_result")
 assert EG_RESULT_DTYPE.itemsize == 40
 
 
@@ -1783,9 +1560,8 @@ def essential_graph_inspect(pb, device=0):
 
 
 # ------------------------------------------------------------------------------- GlobalBundleAdjustment (map-wide BA) ----
-GBA_MAX_POSES, GBA_MAX_OBSERVATIONS, GBA_STOPPED = 4096, 256, 1
-GBA_RESULT_DTYPE = np.dtype([("status", "<i4"), ("iterations", "<i4"), ("trials", "<i4"), ("n_edges_mono", "<i4"), ("n_edges_marker", "<i4"),
-                             ("n_points_left_out", "<i4"), ("chi2_first", "<f8"), ("chi2_last", "<f8"), ("lambda_last", "<f8")])
+GBA_MAX_POSES, GBA_MAX_OBSERVATIONS, GBA_STOPPED = _defines("GBA_MAX_POSES", "GBA_MAX_OBSERVATIONS", "GBA_STOPPED")
+GBA_RESULT_DTYPE = header.dtype("orbfe_gba_result")
 assert GBA_RESULT_DTYPE.itemsize == 48
 
 

@@ -7,29 +7,15 @@ import ctypes as C
 
 import numpy as np
 
-from . import binding
+from . import binding, header
 
 TUM1_K = [517.306408, 516.469215, 318.643040, 255.313989]       # Examples/Monocular/TUM1.yaml
 TUM1_DIST = [0.262383, -0.953104, -0.005358, 0.002628, 1.163314]
 MARKER_SIZE = 0.187                                             # Frame.cc:131
 
 
-class PipelineConfig(C.Structure):
-    """orbfe_pipeline_config (include/orbfe.h)."""
-    _fields_ = [("frames", C.c_int32), ("rows", C.c_int32), ("cols", C.c_int32), ("nfeatures", C.c_int32), ("nlevels", C.c_int32),
-                ("scale_factor", C.c_float), ("ini_th_fast", C.c_int32), ("min_th_fast", C.c_int32), ("dictionary", C.c_char * 32),
-                ("device", C.c_int32), ("marker_capacity", C.c_int32), ("use_orb", C.c_int32), ("use_aruco", C.c_int32),
-                ("marker_size", C.c_float), ("K", C.c_float * 4), ("dist", C.c_float * 12), ("ndist", C.c_int32),
-                ("window_size", C.c_int32), ("nnratio", C.c_float), ("check_orientation", C.c_int32),
-                ("engine_sets", C.c_int32), ("record_sets", C.c_int32), ("phase_pin", C.c_int32), ("det_pin", C.c_int32),
-                ("defer_post", C.c_int32), ("det_nofork", C.c_int32)]
-
-
-class RecordLayoutC(C.Structure):
-    """orbfe_record_layout (include/orbfe.h)."""
-    _fields_ = [("frames", C.c_int32), ("capacity", C.c_int32), ("marker_capacity", C.c_int32), ("halo", C.c_int32),
-                ("off_kps", C.c_uint64), ("off_desc", C.c_uint64), ("off_n", C.c_uint64), ("off_markers", C.c_uint64),
-                ("off_nmarkers", C.c_uint64), ("off_poses", C.c_uint64), ("nbytes", C.c_uint64)]
+PipelineConfig = header.structure("orbfe_pipeline_config")
+RecordLayoutC = header.structure("orbfe_record_layout")
 
 
 class RecordLayout:
@@ -75,9 +61,7 @@ class DeviceBatch:
     pipeline itself uses; freed with the object)."""
 
     def __init__(self, frames_u8, pitch, device=0):
-        from . import binding
         self.L = binding.load()
-        _setup(self.L)
         f = np.ascontiguousarray(frames_u8, np.uint8)
         B, rows, cols = f.shape
         self.shape, self.pitch, self.nbytes = (B, rows, pitch), pitch, B * rows * pitch
@@ -99,64 +83,11 @@ class DeviceBatch:
 
 def device_bytes(ptr, nbytes):
     """nbytes at device address ptr -> numpy uint8 (blocking copy, device to host)."""
-    from . import binding
     L = binding.load()
-    _setup(L)
     out = np.empty(nbytes, np.uint8)
     if L.orbfe_device_download(out.ctypes.data_as(C.c_void_p), ptr, nbytes) != 0:
         raise RuntimeError("orbfe_device_download: %s" % L.orbfe_last_error().decode())
     return out
-
-
-def _setup(L):
-    if getattr(L, "_pipeline_ready", False):
-        return
-    vp, i32p = C.c_void_p, C.POINTER(C.c_int32)
-    L.orbfe_pipeline_config_default.argtypes = [C.POINTER(PipelineConfig), C.c_int, C.c_int, C.c_int]
-    L.orbfe_pipeline_create.argtypes = [C.POINTER(PipelineConfig)]
-    L.orbfe_pipeline_create.restype = vp
-    L.orbfe_pipeline_destroy.argtypes = [vp]
-    L.orbfe_pipeline_destroy.restype = None
-    L.orbfe_pipeline_layout.argtypes = [vp, C.POINTER(RecordLayoutC)]
-    L.orbfe_pipeline_step.argtypes = [vp, vp, C.c_size_t, i32p]
-    for f in ("flush", "synchronize", "reset_stream"):
-        getattr(L, "orbfe_pipeline_" + f).argtypes = [vp]
-    L.orbfe_pipeline_input_done.argtypes = [vp, C.c_int]
-    L.orbfe_pipeline_status.argtypes = [vp, C.POINTER(C.c_int32 * 4)]
-    L.orbfe_pipeline_set_big_frames.argtypes = [vp, C.c_int]
-    L.orbfe_pipeline_records.argtypes = [vp, C.c_int, C.POINTER(vp)]
-    L.orbfe_pipeline_matches.argtypes = [vp] + [C.POINTER(vp)] * 5
-    L.orbfe_pipeline_extractor.argtypes = [vp, C.c_int]
-    L.orbfe_pipeline_extractor.restype = vp
-    L.orbfe_pipeline_detector.argtypes = [vp]
-    L.orbfe_pipeline_detector.restype = vp
-    L.orbfe_pipeline_engine_sets.argtypes = [vp] + [i32p] * 6
-    L.orbfe_pipeline_enable_timing.argtypes = [vp, C.c_int]
-    L.orbfe_pipeline_timing_us.argtypes = [vp, C.c_int, C.POINTER(C.c_float * 3)]
-    L.orbfe_pipeline_env_defaults.restype = C.c_char_p
-    L.orbfe_pipeline_comm_unique_id.argtypes = [C.POINTER(C.c_uint8 * 128)]
-    L.orbfe_pipeline_comm_init.argtypes = [vp, C.POINTER(C.c_uint8 * 128), C.c_int, C.c_int, C.c_int]
-    L.orbfe_pipeline_set_comm.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int]
-    L.orbfe_pipeline_gathered.argtypes = [vp, C.c_int, C.POINTER(vp)]
-    L.orbfe_pipeline_gathered_set.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]
-    L.orbfe_pipeline_gathered_wait.argtypes = [vp, C.c_int]
-    L.orbfe_pipeline_gathered_release.argtypes = [vp, C.c_int, vp]
-    L.orbfe_pipeline_gathered_batch.argtypes = [vp, C.c_int, C.POINTER(C.c_longlong)]
-    L.orbfe_pipeline_copy_stream_priority.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.orbfe_pipeline_step_host.argtypes = [vp, vp, C.c_size_t, i32p]
-    L.orbfe_pipeline_host_records.argtypes = [vp, C.c_int, C.POINTER(vp)]
-    L.orbfe_pipeline_host_copy_us.argtypes = [vp, C.POINTER(C.c_float * 2)]
-    L.orbfe_host_alloc.argtypes = [C.c_size_t]
-    L.orbfe_host_alloc.restype = vp
-    L.orbfe_host_free.argtypes = [vp]
-    L.orbfe_host_free.restype = None
-    L.orbfe_device_alloc.argtypes = [C.c_int, C.c_size_t]
-    L.orbfe_device_alloc.restype = vp
-    L.orbfe_device_free.argtypes = [vp]
-    L.orbfe_device_free.restype = None
-    L.orbfe_device_upload_rows.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_size_t]
-    L.orbfe_device_download.argtypes = [vp, vp, C.c_size_t]
-    L._pipeline_ready = True
 
 
 class PinnedFrames:
@@ -164,7 +95,6 @@ class PinnedFrames:
 
     def __init__(self, frames_u8):
         self.L = binding.load()
-        _setup(self.L)
         f = np.ascontiguousarray(frames_u8, np.uint8)
         self.ptr = self.L.orbfe_host_alloc(f.nbytes)
         if not self.ptr:
@@ -182,14 +112,12 @@ class PinnedFrames:
 def env_defaults():
     """{ORBFE_* variable: default} as the library states them (orbfe_pipeline_env_defaults): "size" = decided by the frame size."""
     L = binding.load()
-    _setup(L)
     return dict(kv.split("=", 1) for kv in L.orbfe_pipeline_env_defaults().decode().split(";") if kv)
 
 
 def comm_unique_id():
     """ncclGetUniqueId through the library (128 bytes): rank 0 calls it and hands the bytes to every rank."""
     L = binding.load()
-    _setup(L)
     buf = (C.c_uint8 * 128)()
     binding._check(L, L.orbfe_pipeline_comm_unique_id(C.byref(buf)), "orbfe_pipeline_comm_unique_id")
     return bytes(buf)
@@ -206,7 +134,6 @@ class FrontEndPipeline:
                  use_orb=True, use_aruco=True, engine_sets=None, record_sets=None, phase_pin=None, det_pin=None, defer_post=None,
                  det_nofork=None):
         self.L = L = binding.load()
-        _setup(L)
         self.B, self.rows, self.cols = frames, rows, cols
         self.pitch = (cols + 63) // 64 * 64
         self.use_orb, self.use_aruco = use_orb, use_aruco

@@ -54,22 +54,16 @@ def gather_records(tensors, dst=0):
 
 
 # ---- the library's own gather plan over any transport -------------------------------------------------------------------------------
-import ctypes as _C
+from . import binding, header
 
-
-class _GatherOp(_C.Structure):
-    _fields_ = [("kind", _C.c_int32), ("peer", _C.c_int32), ("offset", _C.c_ulonglong)]
-
-
-GATHER_RECV, GATHER_SEND, GATHER_COPY_OWN = 0, 1, 2
+_GatherOp = header.structure("orbfe_gather_op")
+GATHER_RECV, GATHER_SEND, GATHER_COPY_OWN = (header.defines[n] for n in ("GATHER_RECV", "GATHER_SEND", "GATHER_COPY_OWN"))
 
 
 def gather_plan(rank, world, dst, record_set, record_sets, nbytes):
     """The operations of one batch's gather on `rank`, from the LIBRARY (orbfe_pipeline_gather_plan = csrc/gather_plan.hpp, the function
     csrc/pipeline.hip executes over RCCL): a list of (kind, peer, byte offset into dst's block buffer).  No device is touched."""
-    from . import binding
     L = binding.load()
-    L.orbfe_pipeline_gather_plan.argtypes = [_C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_int, _C.c_size_t, _C.POINTER(_GatherOp), _C.c_int]
     ops = (_GatherOp * (world + 2))()
     n = L.orbfe_pipeline_gather_plan(rank, world, dst, record_set, record_sets, nbytes, ops, world + 2)
     if n < 0:

@@ -14,15 +14,7 @@ _L = None
 def _lib():
     global _L
     if _L is None:
-        L = binding.load()
-        vp = C.c_void_p
-        L.orbfe_device_alloc.argtypes = [C.c_int, C.c_size_t]
-        L.orbfe_device_alloc.restype = vp
-        L.orbfe_device_free.argtypes = [vp]
-        L.orbfe_device_free.restype = None
-        L.orbfe_device_upload_rows.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_size_t]
-        L.orbfe_device_download.argtypes = [vp, vp, C.c_size_t]
-        _L = L
+        _L = binding.load()
     return _L
 
 

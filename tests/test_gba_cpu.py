@@ -3,8 +3,6 @@ parity tests use has second opinions of its own: noise-free scenes come back exp
 match differences and its numeric ones analytic ones, its reduced solve solves the full system, chi2 never rises, and its two
 summation orders run the same path on every case.  The spread between the two orders, printed here, sets the tolerance of the GPU
 parity tests (tests/gba_parity.py)."""
-import os
-import re
 
 import numpy as np
 import pytest
@@ -12,26 +10,22 @@ import pytest
 import gba_build as B
 import gba_cases as S
 import gba_parity as P
-from test_lba_cpu import _exports, _header_record
+from test_abi_cpu import _exports
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["orbfe_gba_scratch_bytes", "orbfe_global_bundle_adjustment", "orbfe_global_bundle_adjustment_device", "orbfe_gba_inspect"]
 
 
 def test_header_binding_and_library_agree_on_global_bundle_adjustment():
-    from orb_slam2_aruco_amd import binding
-    hdr = open(os.path.join(ROOT, "include", "orbfe.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    declared = set(re.findall(r"\b(orbfe_[a-z0-9_]+)\s*\(", code))
-    assert set(NEW) <= declared, sorted(set(NEW) - declared)
+    from orb_slam2_aruco_amd import binding, header
+    assert set(NEW) <= set(header.functions), sorted(set(NEW) - set(header.functions))
     assert set(NEW) <= set(binding.SYMBOLS)
     assert set(NEW) <= _exports(), sorted(set(NEW) - _exports())
-    rec = _header_record(hdr, "orbfe_gba_result")
+    rec = header.dtype("orbfe_gba_result")
     assert rec == binding.GBA_RESULT_DTYPE == B.RESULT_DTYPE and rec.itemsize == 48
-    defines = dict(re.findall(r"#define (ORBFE_\w+) (\d+)", code))
-    assert int(defines["ORBFE_GBA_MAX_POSES"]) == binding.GBA_MAX_POSES == int(defines["ORBFE_EG_MAX_KEYFRAMES"]) == 4096
-    assert int(defines["ORBFE_GBA_MAX_OBSERVATIONS"]) == binding.GBA_MAX_OBSERVATIONS == int(defines["ORBFE_LBA_MAX_OBSERVATIONS"])
-    assert int(defines["ORBFE_GBA_STOPPED"]) == binding.GBA_STOPPED
+    defines = header.defines
+    assert defines["GBA_MAX_POSES"] == binding.GBA_MAX_POSES == defines["EG_MAX_KEYFRAMES"] == 4096
+    assert defines["GBA_MAX_OBSERVATIONS"] == binding.GBA_MAX_OBSERVATIONS == defines["LBA_MAX_OBSERVATIONS"]
+    assert defines["GBA_STOPPED"] == binding.GBA_STOPPED
     for f in ("global_bundle_adjustment", "global_bundle_adjustment_device", "gba_inspect", "gba_scratch_bytes"):
         assert callable(getattr(binding, f))
     import __graft_entry__

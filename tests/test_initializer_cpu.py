@@ -1,29 +1,23 @@
 """CPU tests of the monocular initializer: the ABI declares and exports it, and the CPU restatement (tests/initializer_ref.cpp)
 that the GPU parity tests use recovers ground truth on synthetic two-view scenes (its own second opinion)."""
 import os
-import re
 
 import numpy as np
 import pytest
 
 import initializer_build as B
 import initializer_cases as S
+from test_abi_cpu import _exports
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["orbfe_initialize", "orbfe_initialize_batch_device", "orbfe_initialize_check_poses", "orbfe_initialize_inspect"]
 
 
 def test_header_declares_and_library_exports_the_initializer():
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "orbfe.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(orbfe_[a-z0-9_]+)\s*\(", txt))
-    assert set(NEW) <= declared, sorted(set(NEW) - declared)
-    exports = os.path.join(ROOT, "build", "EXPORTS")
-    if not os.path.exists(exports):
-        import __graft_entry__
-        __graft_entry__.build()
-    names = set(open(exports).read().split("\n")[1:])
-    assert set(NEW) <= names, sorted(set(NEW) - names)
-    assert "orbfe_init_result" in open(os.path.join(ROOT, "include", "orbfe.h")).read()
+    from orb_slam2_aruco_amd import header
+    assert set(NEW) <= set(header.functions), sorted(set(NEW) - set(header.functions))
+    assert set(NEW) <= _exports(), sorted(set(NEW) - _exports())
+    assert "orbfe_init_result" in header.records
 
 
 def _random_int_with_removal(N, words):

@@ -208,11 +208,6 @@ def test_batch_device_equals_per_pair_calls(orbfe):
     """orbfe_initialize_batch_device on 16 pairs, chained after orbfe_search_for_initialization_batch_device on the same stream,
     equals one orbfe_initialize per pair bit for bit (the same device code).  Device memory from the library's own allocator."""
     L = orbfe.load()
-    vp = C.c_void_p
-    L.orbfe_device_alloc.argtypes = [C.c_int, C.c_size_t]; L.orbfe_device_alloc.restype = vp
-    L.orbfe_device_free.argtypes = [vp]; L.orbfe_device_free.restype = None
-    L.orbfe_device_upload_rows.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_size_t]
-    L.orbfe_device_download.argtypes = [vp, vp, C.c_size_t]
     held = []
 
     def dev(arr):

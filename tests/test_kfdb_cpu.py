@@ -3,14 +3,13 @@ headers, the CPU restatement (tests/kfdb_ref.cpp) equals the reference's recorde
 every case, the fixture covers the branches that make such parity mean something, and two second opinions (numpy for the score, an
 inverted file in Python for the sharing order) agree with the restatement."""
 import os
-import re
 
 import numpy as np
 import pytest
 
 import kfdb_build as B
 import kfdb_cases as S
-from test_sim3_opt_cpu import _exports, _header_record
+from test_abi_cpu import _exports
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["orbfe_detect_candidates", "orbfe_detect_candidates_batch_device", "orbfe_bow_min_score_batch_device", "orbfe_bow_score",
@@ -29,16 +28,14 @@ def ref():
 
 
 def test_header_binding_and_library_agree_on_the_database_queries():
-    from orb_slam2_aruco_amd import binding
-    hdr = open(os.path.join(ROOT, "include", "orbfe.h")).read()
-    declared = set(re.findall(r"\b(orbfe_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)))
-    assert set(NEW) <= declared, sorted(set(NEW) - declared)
+    from orb_slam2_aruco_amd import binding, header
+    assert set(NEW) <= set(header.functions), sorted(set(NEW) - set(header.functions))
     assert set(NEW) <= set(binding.SYMBOLS)
     assert set(NEW) <= _exports(), sorted(set(NEW) - _exports())
-    rec = _header_record(hdr, "orbfe_kfdb_result")
+    rec = header.dtype("orbfe_kfdb_result")
     assert rec == binding.KFDB_RESULT_DTYPE == B.RESULT_DTYPE and rec.itemsize == 36
     for name in ("KFDB_LOOP", "KFDB_RELOC", "KFDB_NEIGHBOURS", "KFDB_MAX_KEYFRAMES", "KFDB_MAX_WORDS"):
-        assert int(re.search(r"#define ORBFE_%s (\d+)" % name, hdr).group(1)) == getattr(binding, name), name
+        assert header.defines[name] == getattr(binding, name), name
     assert (binding.KFDB_LOOP, binding.KFDB_RELOC, binding.KFDB_MAX_WORDS) == (S.LOOP, S.RELOC, S.CAPACITY) == (B.LOOP, B.RELOC, 4096)
     assert binding.KFDB_MAX_KEYFRAMES >= 4096
 

@@ -2,8 +2,6 @@
 parity tests use has second opinions of its own: it recovers ground truth on clean scenes, flags the injected outliers, its analytic
 Jacobians match differences and its numeric ones analytic ones, its Schur solve solves the full system, and its two summation
 orders give the same decisions.  The spread between the two orders, printed here, sets the tolerance of the GPU parity tests."""
-import os
-import re
 
 import numpy as np
 import pytest
@@ -11,50 +9,21 @@ import pytest
 import lba_build as B
 import lba_cases as S
 import lba_parity as P
+from test_abi_cpu import _exports
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["orbfe_lba_scratch_bytes", "orbfe_local_bundle_adjustment", "orbfe_local_bundle_adjustment_device", "orbfe_lba_inspect"]
-C_TYPES = {"int32_t": "<i4", "double": "<f8", "float": "<f4"}
-
-
-def _exports():
-    exports = os.path.join(ROOT, "build", "EXPORTS")
-    if not os.path.exists(exports):
-        import __graft_entry__
-        __graft_entry__.build()
-    return set(open(exports).read().split("\n")[1:])
-
-
-def _header_record(hdr, name):
-    """the fields of a typedef struct of include/orbfe.h as numpy dtype entries, in order"""
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), hdr, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        ctype, rest = decl.split(None, 1)
-        for item in rest.split(","):
-            m = re.match(r"\s*(\w+)(?:\[(\d+)\])?\s*$", item)
-            fields.append((m.group(1), C_TYPES[ctype]) + (((int(m.group(2)),),) if m.group(2) else ()))
-    return np.dtype(fields)
 
 
 def test_header_binding_and_library_agree_on_local_bundle_adjustment():
-    from orb_slam2_aruco_amd import binding
-    hdr = open(os.path.join(ROOT, "include", "orbfe.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    declared = set(re.findall(r"\b(orbfe_[a-z0-9_]+)\s*\(", code))
-    assert set(NEW) <= declared, sorted(set(NEW) - declared)
+    from orb_slam2_aruco_amd import binding, header
+    assert set(NEW) <= set(header.functions), sorted(set(NEW) - set(header.functions))
     assert set(NEW) <= set(binding.SYMBOLS)
     assert set(NEW) <= _exports(), sorted(set(NEW) - _exports())
-    rec = _header_record(hdr, "orbfe_lba_result")
+    rec = header.dtype("orbfe_lba_result")
     assert rec == binding.LBA_RESULT_DTYPE == B.RESULT_DTYPE and rec.itemsize == 36
-    defines = dict(re.findall(r"#define (ORBFE_LBA_\w+) (\d+)", code))
-    assert int(defines["ORBFE_LBA_MAX_FREE_POSES"]) == binding.LBA_MAX_FREE_POSES >= 64
-    assert int(defines["ORBFE_LBA_MAX_OBSERVATIONS"]) == binding.LBA_MAX_OBSERVATIONS == 256
-    assert int(defines["ORBFE_LBA_STOPPED"]) == binding.LBA_STOPPED
+    assert header.defines["LBA_MAX_FREE_POSES"] == binding.LBA_MAX_FREE_POSES >= 64
+    assert header.defines["LBA_MAX_OBSERVATIONS"] == binding.LBA_MAX_OBSERVATIONS == 256
+    assert header.defines["LBA_STOPPED"] == binding.LBA_STOPPED
     import __graft_entry__
     assert "local_ba.hip" in __graft_entry__.HIP_SOURCES
 

@@ -16,6 +16,27 @@ def _case(*argv, timeout=1500):
 
 
 @pytest.mark.gpu
+def test_device_buffers_after_load_alone():
+    """A fresh interpreter with binding.load() alone and no pipeline object: 64 rows of 64 bytes through orbfe_device_alloc,
+    _upload_rows, _download and _free come back unchanged (load() types every function: the 64-bit address is not cut to an int)."""
+    code = """
+import numpy as np
+from orb_slam2_aruco_amd import binding
+L = binding.load()
+src = np.random.default_rng(1).integers(0, 256, (64, 64), dtype=np.uint8); out = np.zeros_like(src)
+d = L.orbfe_device_alloc(0, 4096)
+assert d, L.orbfe_last_error()
+assert L.orbfe_device_upload_rows(d, 64, src.ctypes.data, 64, 64, 64) == 0, L.orbfe_last_error()
+assert L.orbfe_device_download(out.ctypes.data, d, 4096) == 0, L.orbfe_last_error()
+L.orbfe_device_free(d)
+assert np.array_equal(out, src)
+print("ok")
+"""
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout[-2000:] + r.stderr[-4000:]
+
+
+@pytest.mark.gpu
 def test_timed_path_c2_full_batch_against_oracle():
     """The 300-frame C2 batch exactly as bench.py runs it: all 300 frames and all 299 pairs."""
     _case("C2", 300, 3)

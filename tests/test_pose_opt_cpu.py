@@ -1,35 +1,23 @@
 """CPU tests of the motion-only pose optimization: the ABI declares and exports it, the shim compiles and links against the mock
 headers, and the CPU restatement (tests/pose_opt_ref.cpp) that the GPU parity tests use recovers ground truth on synthetic scenes
 (its own second opinion)."""
-import os
-import re
 
 import numpy as np
 import pytest
 
 import pose_opt_build as B
 import pose_opt_cases as S
+from test_abi_cpu import _exports
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["orbfe_pose_optimization", "orbfe_pose_optimization_batch_device", "orbfe_pose_gather_device"]
 
 
-def _exports():
-    exports = os.path.join(ROOT, "build", "EXPORTS")
-    if not os.path.exists(exports):
-        import __graft_entry__
-        __graft_entry__.build()
-    return set(open(exports).read().split("\n")[1:])
-
-
 def test_header_binding_and_library_agree_on_the_pose_optimization():
-    from orb_slam2_aruco_amd import binding
-    hdr = open(os.path.join(ROOT, "include", "orbfe.h")).read()
-    declared = set(re.findall(r"\b(orbfe_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)))
-    assert set(NEW) <= declared, sorted(set(NEW) - declared)
+    from orb_slam2_aruco_amd import binding, header
+    assert set(NEW) <= set(header.functions), sorted(set(NEW) - set(header.functions))
     assert set(NEW) <= set(binding.SYMBOLS)
     assert set(NEW) <= _exports(), sorted(set(NEW) - _exports())
-    assert "orbfe_pose_result" in hdr and "orbfe_pose_marker" in hdr
+    assert "orbfe_pose_result" in header.records and "orbfe_pose_marker" in header.records
     # the record layouts the bindings and the restatement use
     assert binding.POSE_RESULT_DTYPE == B.RESULT_DTYPE and binding.POSE_MARKER_DTYPE == B.MARKER_DTYPE
 

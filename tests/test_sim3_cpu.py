@@ -1,8 +1,6 @@
 """CPU tests of the Sim3 RANSAC: the ABI declares and exports it, and the CPU restatement (tests/sim3_ref.cpp) that the GPU parity
 tests use recovers the known similarity, counts iterations as SetRansacParameters does, decodes sets by the initializer's rule and
 replays a run window by window (its own second opinion)."""
-import os
-import re
 
 import numpy as np
 import pytest
@@ -11,27 +9,20 @@ import initializer_build
 import sim3_build as B
 import sim3_cases as S
 import sim3_parity as P
+from test_abi_cpu import _exports
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["orbfe_sim3_solve", "orbfe_sim3_solve_batch_device", "orbfe_sim3_inspect"]
 
 
 def test_header_declares_and_library_exports_the_solver():
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "orbfe.h")).read(), flags=re.S)
-    declared = set(re.findall(r"\b(orbfe_[a-z0-9_]+)\s*\(", txt))
-    assert set(NEW) <= declared, sorted(set(NEW) - declared)
-    from orb_slam2_aruco_amd import binding
+    from orb_slam2_aruco_amd import binding, header
+    assert set(NEW) <= set(header.functions), sorted(set(NEW) - set(header.functions))
     assert set(NEW) <= set(binding.SYMBOLS)
     import __graft_entry__
     assert "sim3_solver.hip" in __graft_entry__.HIP_SOURCES
-    exports = os.path.join(ROOT, "build", "EXPORTS")
-    if not os.path.exists(exports):
-        __graft_entry__.build()
-    names = set(open(exports).read().split("\n")[1:])
-    assert set(NEW) <= names, sorted(set(NEW) - names)
+    assert set(NEW) <= _exports(), sorted(set(NEW) - _exports())
     assert binding.SIM3_RESULT_DTYPE == B.RESULT_DTYPE       # the record of orbfe.h, field for field
-    m = re.search(r"typedef struct orbfe_sim3_result \{(.*?)\} orbfe_sim3_result;", txt, flags=re.S)
-    fields = re.findall(r"\b([A-Za-z_][A-Za-z0-9_]*)(?:\[\d+\])?\s*[,;]", m.group(1))
+    fields = [name for name, _, _ in header.records["orbfe_sim3_result"]]
     assert fields == list(B.RESULT_DTYPE.names), fields
 
 

@@ -12,7 +12,6 @@ the two sides):
   5. Sixty iterate(5)-shaped calls with the carried best equal one whole run bit for bit.
   6. The batch call over 16 pairs, chained after orbfe_search_by_bow_batch_device, equals 16 host-pointer calls bit for bit.
   7. Argument errors and the defined corner cases."""
-import ctypes as C
 
 import numpy as np
 import pytest
@@ -138,11 +137,6 @@ def test_batch_device_equals_per_pair_calls(orbfe):
     the synthetic stream, a small synthetic vocabulary, made-up world points: every keypoint back-projected to a plane in front of its
     camera), equals one orbfe_sim3_solve per pair bit for bit, padding untouched.  Device memory from the library's own allocator."""
     L = orbfe.load()
-    vp = C.c_void_p
-    L.orbfe_device_alloc.argtypes = [C.c_int, C.c_size_t]; L.orbfe_device_alloc.restype = vp
-    L.orbfe_device_free.argtypes = [vp]; L.orbfe_device_free.restype = None
-    L.orbfe_device_upload_rows.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_size_t]
-    L.orbfe_device_download.argtypes = [vp, vp, C.c_size_t]
     held = []
 
     def dev(arr):

@@ -1,8 +1,6 @@
 """CPU tests of OptimizeSim3: the ABI declares and exports it, the shim compiles and links against the mock headers, and the CPU
 restatement (tests/sim3_opt_ref.cpp) that the GPU parity tests use recovers ground truth on synthetic scenes, takes every branch
 of the reference, and gives the same decisions in its two summation orders (its own second opinion)."""
-import os
-import re
 
 import numpy as np
 import pytest
@@ -10,45 +8,18 @@ import pytest
 import sim3_opt_build as B
 import sim3_opt_cases as S
 import sim3_opt_parity as P
+from test_abi_cpu import _exports
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ["orbfe_optimize_sim3", "orbfe_optimize_sim3_batch_device"]
-C_TYPES = {"int32_t": "<i4", "double": "<f8", "float": "<f4"}
-
-
-def _exports():
-    exports = os.path.join(ROOT, "build", "EXPORTS")
-    if not os.path.exists(exports):
-        import __graft_entry__
-        __graft_entry__.build()
-    return set(open(exports).read().split("\n")[1:])
-
-
-def _header_record(hdr, name):
-    """the fields of a typedef struct of include/orbfe.h as numpy dtype entries, in order"""
-    body = re.search(r"typedef struct %s \{(.*?)\} %s;" % (name, name), hdr, flags=re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if not decl:
-            continue
-        ctype, rest = decl.split(None, 1)
-        for item in rest.split(","):
-            m = re.match(r"\s*(\w+)(?:\[(\d+)\])?\s*$", item)
-            fields.append((m.group(1), C_TYPES[ctype]) + (((int(m.group(2)),),) if m.group(2) else ()))
-    return np.dtype(fields)
 
 
 def test_header_binding_and_library_agree_on_optimize_sim3():
-    from orb_slam2_aruco_amd import binding
-    hdr = open(os.path.join(ROOT, "include", "orbfe.h")).read()
-    declared = set(re.findall(r"\b(orbfe_[a-z0-9_]+)\s*\(", re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)))
-    assert set(NEW) <= declared, sorted(set(NEW) - declared)
+    from orb_slam2_aruco_amd import binding, header
+    assert set(NEW) <= set(header.functions), sorted(set(NEW) - set(header.functions))
     assert set(NEW) <= set(binding.SYMBOLS)
     assert set(NEW) <= _exports(), sorted(set(NEW) - _exports())
     # the record layout the header, the binding and the restatement use
-    rec = _header_record(hdr, "orbfe_sim3_opt_result")
+    rec = header.dtype("orbfe_sim3_opt_result")
     assert rec == binding.SIM3_OPT_RESULT_DTYPE == B.RESULT_DTYPE and rec.itemsize == 96
     # s12, R12, t12 of the Sim3 solver's record are 13 contiguous floats: what the batch call's stride points at
     f = binding.SIM3_RESULT_DTYPE.fields
